@@ -10,13 +10,20 @@ completed by all ranks / wall time of the timed region.
 A single QP does not shard: with --gpus N every rank solves
 its own replica (seed = 1 + rank), no data-path collective; scaling is "weak".
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps steps and prints the headline
+line.  --dump-outputs DIR writes what the last timed step returned to its
+caller (x, y, the two certificates, the info scalars) as DIR/<name>.npy.
+
+Extra objects on the JSON line, with --full only:
   roofline     dominant PCG kernel: algorithmic bytes per launch / measured
                launch-to-launch period (HIP events on the engine's stream)
+  inexact_mode the opt-in inexact PCG mode on the same QP
+  other_configs configs 3 and 5 at full size
   cpu_baseline the oracle (plain-C restatement of the reference CPU path,
                single-threaded direct LDL^T) on a bounded sample of the same
                recipe, timed on this host (rank 0, N=1 only)
   batch        QPs/s of the batched MPC engine (config 4), when built
+  config5_row_partitioned  with --gpus N > 1: one config-5 QP over N ranks
 """
 import argparse
 import ctypes as C
@@ -50,7 +57,43 @@ def parse():
     ap.add_argument("--cpu-batch-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-single-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg: roofline, inexact mode, configs 3 / 5, batch, CPU baselines, "
+                         "the row-partitioned leg with --gpus N > 1 (the --no-* options and --batch select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (x, y, certificates, info) as DIR/<name>.npy, float64")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_BUDGET = 64 << 20      # bytes of all the .npy arrays of --dump-outputs together
+
+
+def dump_outputs(path, res, budget=DUMP_BUDGET):
+    """--dump-outputs: the arrays the caller of the timed path receives from its last step, float64.  The info scalars that depend
+    neither on timing nor on the number of steps (rho_updates counts from setup) go into info.npy: iter, status_val, status_polish,
+    obj_val, pri_res, dua_res, rho_estimate.  Vectors too large for the budget are replaced by a fixed, seeded sample of their
+    entries, with the sampled positions in <name>_index.npy."""
+    i = res.info
+    arrays = dict(x=res.x, y=res.y, prim_inf_cert=res.prim_inf_cert, dual_inf_cert=res.dual_inf_cert)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    info = np.array([i.iter, i.status_val, i.status_polish, i.obj_val, i.pri_res, i.dua_res, i.rho_estimate], dtype=np.float64)
+    total = sum(v.nbytes for v in arrays.values())
+    room = budget - info.nbytes - 128 * 2 * (len(arrays) + 1)          # (a .npy header is 128 bytes)
+    if total > room:
+        rng = np.random.default_rng(0)
+        for k in list(arrays):
+            v = arrays[k]
+            keep = min(v.size, int(v.size * room // (2 * total)))      # values and their positions: twice the bytes
+            idx = np.sort(rng.choice(v.size, keep, replace=False))
+            arrays[k], arrays[k + "_index"] = v[idx], idx.astype(np.float64)
+    arrays["info"] = info
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return sorted(arrays)
 
 
 def kernel_roofline(solver, reps=300):
@@ -592,7 +635,7 @@ def main():
     if world != max(1, a.gpus) and rank == 0:
         print("bench.py: --gpus %d but WORLD_SIZE=%d: running %d rank(s)" % (a.gpus, world, world), file=sys.stderr)
     cpu_child = None
-    if world == 1 and rank == 0 and not a.no_cpu:
+    if a.full and world == 1 and rank == 0 and not a.no_cpu:
         cpu_child = cpu_baseline_start(a)          # one core, beside the GPU legs; joined before the CPU legs of the batch
     import torch
     dist = None
@@ -661,12 +704,15 @@ def main():
         it = torch.tensor([float(iters)], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(it, op=dist.ReduceOp.SUM)
         max_t, tot_iters = float(t.item()), float(it.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last)
 
+    # everything below the headline runs with --full only
     batch = None
-    if a.batch and world > 1:
+    if a.full and a.batch and world > 1:
         batch = bench_batch(a.batch, dist, rank, dev_id, world, coll_dev, with_cpu=False)
     rowpart5, wedged = None, False
-    if world > 1 and not a.no_configs:
+    if a.full and world > 1 and not a.no_configs:
         # a reported side leg: it must not cost the headline line.  A rank that fails or stalls in here leaves the others
         # inside a collective, so every rank runs it under an alarm; after a failure the process group is not used again.
         import signal
@@ -703,7 +749,7 @@ def main():
                                          else "launch-per-step PCG kernels (k_cg_A, k_cg_B)"),
                        "parallelism": "replicas x%d (a single QP does not shard)" % world},
         }
-        if world == 1 and not a.no_inexact:
+        if a.full and world == 1 and not a.no_inexact:
             # opt-in inexact mode (PCG tolerance tied to the ADMM residuals): NOT parity-exact,
             # reported beside the headline, never as `value`
             solver.set_options(pcg_adaptive=1)
@@ -716,7 +762,7 @@ def main():
             out["inexact_mode"] = {"value": round(fi / tf, 2), "unit": "ADMM iters/s", "admm_iters_per_solve": int(rf.info.iter),
                                    "status": rf.info.status, "obj_rel_diff_vs_strict": abs(rf.info.obj_val - last.info.obj_val) / abs(last.info.obj_val),
                                    "note": "OSQP_AMD_PCG_ADAPTIVE=1; results agree with the strict mode only to the ADMM tolerance"}
-        if world == 1:
+        if a.full and world == 1:
             out["roofline"] = kernel_roofline(solver)
             if not a.no_configs:
                 out["other_configs"] = other_configs(a.eps)

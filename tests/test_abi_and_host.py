@@ -251,6 +251,49 @@ def test_bench_spawns_before_touching_the_gpu():
     assert "import torch" not in head and "import osqp_amd" not in head
 
 
+def test_bench_options(monkeypatch):
+    """A plain run is the headline alone (--full off by default); --steps of 0 is refused."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: float64 .npy files of the last step's result; over the byte budget, the same seeded sample every time."""
+    from types import SimpleNamespace
+    import bench
+    rng = np.random.default_rng(1)
+    n, m = 3000, 5000
+    info = SimpleNamespace(iter=125, status_val=1, status_polish=0, obj_val=-3.5, pri_res=1e-5, dua_res=2e-5, rho_updates=1,
+                           rho_estimate=0.3, solve_time=0.01)
+    res = SimpleNamespace(x=rng.standard_normal(n), y=rng.standard_normal(m), prim_inf_cert=rng.standard_normal(m),
+                          dual_inf_cert=rng.standard_normal(n), info=info)
+    names = bench.dump_outputs(str(tmp_path / "all"), res)
+    assert names == ["dual_inf_cert", "info", "prim_inf_cert", "x", "y"]
+    for k in ("x", "y", "prim_inf_cert", "dual_inf_cert"):
+        v = np.load(tmp_path / "all" / (k + ".npy"))
+        assert v.dtype == np.float64 and np.array_equal(v, getattr(res, k))
+    assert np.load(tmp_path / "all" / "info.npy").tolist() == [125, 1, 0, -3.5, 1e-5, 2e-5, 0.3]
+    budget = 64 << 10
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), res, budget=budget)
+        files = sorted(os.listdir(tmp_path / d))
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= budget
+    for f in files:
+        a, b = np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+        if not f.endswith("_index.npy") and f != "info.npy":
+            idx = np.load(tmp_path / "s1" / f.replace(".npy", "_index.npy")).astype(np.int64)
+            assert 0 < a.size < getattr(res, f[:-4]).size and np.array_equal(a, getattr(res, f[:-4])[idx])
+
+
 def test_every_environment_variable_is_documented():
     """Every OSQP_AMD_* variable the sources read appears in INTEGRATION.md (section F or the diagnostics paragraph)."""
     import glob

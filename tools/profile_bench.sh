@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; TAG=${1:-profb}; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 ROC_AQL_QUEUE_SIZE=${ROC_AQL_QUEUE_SIZE:-524288}
-ARGS="--steps 4 --warmup 1 --no-cpu --no-configs --no-inexact"
+ARGS="--full --steps 4 --warmup 1 --no-cpu --no-configs --no-inexact"
 run() {
   local name=$1; shift
   timeout -k 10 900 "$@" > $O/$name.json 2> $O/$name.err
