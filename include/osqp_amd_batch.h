@@ -20,7 +20,10 @@ typedef struct osqp_amd_batch osqp_amd_batch;
 /* P (upper triangle) and A give the shared CSC pattern (and the shared values
  * when Px_all / Ax_all are NULL).  Px_all [batch][nnzP] / Ax_all [batch][nnzA]
  * optionally give per-QP values.  Q [batch][n], L, U [batch][m] row-major.
- * Returns 0 or an osqp_error_type code (include/constants.h:42-50 numbering). */
+ * Returns 0 or an osqp_error_type code (include/constants.h:42-50 numbering):
+ * OSQP_NONCVX_ERROR when some member's K = P + sigma I + A' rho A is not positive definite
+ * (stderr names the first such member), OSQP_SETTINGS_VALIDATION_ERROR for polish or
+ * time_limit > 0, which the batched kernel does not implement. */
 c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const csc *P, const csc *A,
                            const c_float *Px_all, const c_float *Ax_all,
                            const c_float *Q, const c_float *L, const c_float *U,
@@ -38,6 +41,14 @@ c_int osqp_amd_batch_get(osqp_amd_batch *b, c_float *X, c_float *Y, c_float *inf
 /* Device pointers of the result arrays, for device-side gathers (RCCL). */
 c_int osqp_amd_batch_device_ptrs(osqp_amd_batch *b, void **X, void **Y, void **info8);
 void  osqp_amd_batch_cleanup(osqp_amd_batch *b);
+
+/* For the tests: member qp's workspace as the last setup / update / solve left it.  NULL = skip.
+ * D [n], E [m], c [1], rho [1] (current scalar rho), ctype [m] (-1 free, 0 ineq, 1 eq),
+ * Pv [nnzP], Av [nnzA] (scaled values, CSC order), Kinv [NP*NP] row-major, *NP = 64 or 128
+ * (K^-1 of the kernel, padded with identity rows and columns; un-permuted from the kernel's
+ * GEMV order with the kernel's own index function).  Returns 0 or an osqp_error_type code. */
+c_int osqp_amd_batch_member(osqp_amd_batch *b, c_int qp, c_float *D, c_float *E, c_float *c, c_float *rho,
+                            c_int *ctype, c_float *Pv, c_float *Av, c_float *Kinv, c_int *NP);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,8 @@ def _bind(L):
     L.osqp_amd_batch_get.argtypes = [H, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p]
     L.osqp_amd_batch_cleanup.restype = None
     L.osqp_amd_batch_cleanup.argtypes = [H]
+    L.osqp_amd_batch_member.restype = abi.c_int
+    L.osqp_amd_batch_member.argtypes = [H, abi.c_int] + [abi.c_float_p] * 4 + [abi.c_int_p] + [abi.c_float_p] * 3 + [abi.c_int_p]
 
 
 def _p(a):
@@ -45,6 +47,11 @@ class BatchOSQP:
         pattern/values.  Q [B, n], L, U [B, m].  Px_all / Ax_all [B, nnz] optional
         per-QP values in CSC order of triu(P) / A."""
         from . import engine_options
+        # neither path may hand back an unpolished or unclocked answer to a caller who asked for one: the batch
+        # kernel implements neither, so both paths refuse them (OSQP_SETTINGS_VALIDATION_ERROR = 2)
+        for k in ("polish", "time_limit"):
+            if settings.get(k, 0) and settings[k] > 0:
+                raise ValueError("osqp_amd_batch_setup failed with error 2: %s is not implemented by the batched engine" % k)
         self.Pu = abi.CscHolder(sparse.triu(P, format="csc"))
         self.Ah = abi.CscHolder(A)
         Q = abi.as_f64(Q)
@@ -90,7 +97,13 @@ class BatchOSQP:
                         Pb = sparse.triu(Pf, format="csc"); Pb.sort_indices(); Pb.data = Px_all[b].copy()
                     if Ax_all is not None:
                         Ab.sort_indices(); Ab.data = Ax_all[b].copy()
-                    self._many.append(OSQP().setup(P=Pb, q=Q[b], A=Ab, l=L[b], u=U[b], **settings))
+                    try:
+                        self._many.append(OSQP().setup(P=Pb, q=Q[b], A=Ab, l=L[b], u=U[b], **settings))
+                    except ValueError as e:       # e.g. error 5 (non-convex member), as the kernel path reports it
+                        for s in self._many:
+                            s.cleanup()
+                        self._many = None
+                        raise ValueError("%s (QP %d of the batch)" % (e, b)) from None
             finally:
                 set_engine_options(device=old)
             self._last = None
@@ -162,6 +175,25 @@ class BatchOSQP:
             col = info[:, k]
             setattr(out, name, col.astype(np.int64) if name in ("iter", "status_val", "rho_updates") else col)
         return out
+
+    def member_workspace(self, qp):
+        """Test hook: member qp's workspace as the last setup / update / solve left it -- D, E, c, rho (scalar),
+        ctype (-1 free, 0 inequality, 1 equality), scaled Pv / Av (CSC order of triu(P) / A) and the kernel's
+        K^-1 as an NP x NP matrix (padded with identity to NP = 64 or 128)."""
+        if self._many is not None:
+            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): there is no packed batch "
+                               "workspace to read" % BATCH_MAX_N)
+        NP = 16 * (4 if self.n <= 64 else 8)
+        D = np.zeros(self.n); E = np.zeros(max(self.m, 1)); c = np.zeros(1); rho = np.zeros(1)
+        ct = np.zeros(max(self.m, 1), np.int64); Pv = np.zeros(max(self.Pu.nnz, 1)); Av = np.zeros(max(self.Ah.nnz, 1))
+        K = np.zeros((NP, NP)); npo = np.zeros(1, np.int64)
+        rc = self._lib.osqp_amd_batch_member(self._h, int(qp), abi.fptr(D), abi.fptr(E), abi.fptr(c), abi.fptr(rho), abi.iptr(ct),
+                                             abi.fptr(Pv), abi.fptr(Av), abi.fptr(K), abi.iptr(npo))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_member failed (%d)" % rc)
+        assert int(npo[0]) == NP
+        return dict(D=D, E=E[:self.m], c=float(c[0]), rho=float(rho[0]), ctype=ct[:self.m], Pv=Pv[:self.Pu.nnz],
+                    Av=Av[:self.Ah.nnz], Kinv=K, NP=NP)
 
     def device_arrays(self):
         """The result arrays as they sit in HBM -- X [B, n], Y [B, m], info8 [B, 8] -- as objects carrying

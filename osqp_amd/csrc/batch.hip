@@ -73,7 +73,8 @@ struct BIO {               // per-batch arrays (device)
   double *Wd, *We, *Wc;    // D [B][n], E [B][m], c [B]
   double *Wk;              // [B][NP*NP] K^-1 in per-thread tile order
   int    *Wt;              // [B][m] constraint class
-  int    *flag;            // [B] 1 = K^-1 must be rebuilt (constraint class changed)
+  int    *flag;            // [B] 1 = K^-1 must be rebuilt (constraint class changed); 2, 4: refinement
+                           // verdict; 8 (setup phase only): K was not positive definite
   double *info;            // [B][8]: iter, status, obj, pri, dua, rho_updates, rho_estimate, rho
   const int *order;        // [B] solve phase: workgroup k works on QP order[k] (longest expected first)
 };
@@ -290,8 +291,12 @@ __device__ __forceinline__ void form_K(double (&a)[TR][TC], int n, const BL &s, 
 
 // In-place Gauss-Jordan inversion without pivoting (K is SPD).  One barrier per
 // pivot: the pivot row / column are exchanged through double-buffered LDS.
+// Returns true (uniformly: every lane reads every pivot) when a pivot was not
+// positive -- NaN included.  The pivots are the D of K = L D L', so all of them
+// are positive exactly when K is positive definite (Sylvester); the setup phase
+// turns this into OSQP_NONCVX_ERROR, the solve phase ignores it.
 template <int TR, int TC, int GC>
-__device__ __forceinline__ void invert_tiles(double (&a)[TR][TC], const BL &s, int n) {
+__device__ __forceinline__ bool invert_tiles(double (&a)[TR][TC], const BL &s, int n) {
   // The pivot loop is unrolled by TR (a multiple of TC) so that the pivot's
   // position inside a tile (ko, kco) is a compile-time constant: the register
   // tile is only ever indexed statically.  Per pivot: owners publish row k and
@@ -301,6 +306,7 @@ __device__ __forceinline__ void invert_tiles(double (&a)[TR][TC], const BL &s, i
   constexpr int NP = 16 * TR;
   const int tr = threadIdx.x / GC, tc = threadIdx.x % GC;
   const int nkb = (n + TR - 1) / TR;    // padded rows/columns are identity: nothing to eliminate
+  bool notpd = false;
 #pragma unroll 1
   for (int kb = 0; kb < nkb; ++kb) {
 #pragma unroll
@@ -318,7 +324,9 @@ __device__ __forceinline__ void invert_tiles(double (&a)[TR][TC], const BL &s, i
         for (int r = 0; r < TR; ++r) colk[tr * TR + r] = a[r][kco];
       }
       __syncthreads();
-      const double piv = 1.0 / rowk[kco * GC + kc];
+      const double akk = rowk[kco * GC + kc];
+      notpd |= !(akk > 0.0);
+      const double piv = 1.0 / akk;
       double rk[TC];
 #pragma unroll
       for (int c = 0; c < TC; ++c) rk[c] = rowk[c * GC + tc] * piv;
@@ -339,6 +347,7 @@ __device__ __forceinline__ void invert_tiles(double (&a)[TR][TC], const BL &s, i
     }
   }
   __syncthreads();
+  return notpd;
 }
 
 // K^-1 for the per-iteration GEMV lives in a second register layout ("G"): eight adjacent
@@ -375,9 +384,9 @@ __device__ __forceinline__ void tile_gemv(const double (&ag)[GL<NP>::RG][GL<NP>:
   __syncthreads();
 }
 // element (i, j) of K^-1 -> position in the per-QP array (G order, slot-major so that the
-// loads of the solve phase are coalesced)
+// loads of the solve phase are coalesced).  Host and device: osqp_amd_batch_member un-permutes with it.
 template <int NP, int NT>
-__device__ __forceinline__ int g_index(int i, int j) {
+__host__ __device__ __forceinline__ int g_index(int i, int j) {
   constexpr int RG = GL<NP>::RG, CG = GL<NP>::CG;
   const int tg = (i / RG) * 8 + ((j & 15) >> 1);
   const int sg = (i % RG) * CG + ((j >> 4) << 1) + (j & 1);
@@ -401,15 +410,17 @@ __device__ __forceinline__ void load_kinv(double (&ag)[GL<NP>::RG][GL<NP>::CG], 
     for (int c = 0; c < GL<NP>::CG; ++c)
       ag[r][c] = __hip_atomic_load(Wk + (r * GL<NP>::CG + c) * NT + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// form K, invert it in the Gauss-Jordan tile layout and leave it in HBM in GEMV order
+// form K, invert it in the Gauss-Jordan tile layout and leave it in HBM in GEMV order;
+// true when K was not positive definite (invert_tiles)
 template <int TR, int TC, int GC>
-__device__ __forceinline__ void rebuild_kinv(int n, const BL &s, double sigma, double *Wk) {
+__device__ __forceinline__ bool rebuild_kinv(int n, const BL &s, double sigma, double *Wk) {
   double a[TR][TC];
   form_K<TR, TC, GC>(a, n, s, sigma);
-  invert_tiles<TR, TC, GC>(a, s, n);
+  const bool notpd = invert_tiles<TR, TC, GC>(a, s, n);
   store_kinv<TR, TC, GC>(a, Wk);
   __threadfence();               // the stores are re-read by other lanes of this workgroup
   __syncthreads();
+  return notpd;
 }
 
 // ---------------------------------------------------------------------------
@@ -553,8 +564,9 @@ __global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k
   const int qflag = phase == 0 ? 1 : io.flag[qp];
   bool need_refine = (qflag & 2) != 0, check_pending = false;
   double *Wk = io.Wk + qp * (long long)(NP * NP);
+  bool notpd = false;
   if (phase == 0 || (qflag & 1)) {
-    rebuild_kinv<TR, TC, GC>(n, s, st.sigma, Wk);
+    notpd = rebuild_kinv<TR, TC, GC>(n, s, st.sigma, Wk);   // (the solve phase drops the verdict: not covered in-loop)
     check_pending = true;
   } else if (qflag & 4) check_pending = true;
   DBG(tstamp[4] = wall_clock64();)
@@ -570,7 +582,8 @@ __global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k
       io.Wl[qp * m + i] = s_l[i]; io.Wu[qp * m + i] = s_u[i]; io.We[qp * m + i] = s_E[i];
       io.Wt[qp * m + i] = s.ctype[i]; io.Zs[qp * m + i] = 0.0; io.Ys[qp * m + i] = 0.0;
     }
-    if (tid == 0) { io.Wc[qp] = cs; io.rho_io[qp] = rho; io.flag[qp] = 4; }   // 4: verdict on refinement still open
+    // 4: verdict on refinement still open; 8: K not positive definite (read by the host after the launch)
+    if (tid == 0) { io.Wc[qp] = cs; io.rho_io[qp] = rho; io.flag[qp] = notpd ? 4 | 8 : 4; }
     return;
   }
 
@@ -587,7 +600,9 @@ __global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k
   if (tid == 0) { for (int k = 0; k < S_COUNT_; ++k) sc[k] = 0.0; sc[S_STATUS] = OSQP_UNSOLVED; sc[S_RHO] = rho; }
   for (int i = tid; i < m; i += NT) s_w[i] = s_rho[i] * s_z[i] - s_y[i];
   __syncthreads();
-  int iter = 0, rho_updates = 0, stage = 0, probe_until = 0;
+  // rho_updates counts on from the previous solve until an update resets it, like the reference's info
+  // (set to 0 by osqp_setup and by reset_info in every osqp_update_*, src/auxil.c:632-649)
+  int iter = 0, rho_updates = (int)io.info[qp * 8 + 5], stage = 0, probe_until = 0;
 #ifdef OSQP_AMD_BATCH_DEBUG
   unsigned long long pacc[5] = {0, 0, 0, 0, 0}, pt0 = 0, pt1 = 0;
 #define PSTAMP(slot) do { if (st.profile) { pt1 = wall_clock64(); pacc[slot] += pt1 - pt0; pt0 = pt1; } } while (0)
@@ -618,7 +633,7 @@ __global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k
       if (!ABL(2)) tile_gemv<NP>(ag, s_b, s_xt);
       PSTAMP(1);
       // One step of iterative refinement, xt += Kinv (b - K xt), for QPs whose K^-1 needs it.
-      // Whether it does is probed (relative residual of the solve above refine_tol) in the first
+      // Whether it does is probed (relative residual of the solve above refine_tol, fill_settings) in the first
       // four iterations after K^-1 was built; one hit turns refinement on for good (kept per QP
       // across solves).  refine = 2: always on.
       const bool probe = !need_refine && (check_pending || iter <= probe_until);
@@ -910,6 +925,7 @@ __global__ void __launch_bounds__(256) k_batch_update(int n, int m, BIO io, cons
   }
   __syncthreads();
   if (threadIdx.x == 0 && changed) io.flag[qp] = 1;   // rebuild; the refinement verdict is re-taken after it
+  if (threadIdx.x == 0) io.info[qp * 8 + 5] = 0.0;      // reset_info: rho_updates (src/auxil.c:647)
 }
 
 // ---------------------------------------------------------------------------
@@ -1002,8 +1018,12 @@ static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
   t.scaled_termination = (int)s->scaled_termination; t.warm_start = (int)s->warm_start;
   const char *e = getenv("OSQP_AMD_BATCH_REFINE");
   t.refine = e ? atoi(e) : 1;
+  // Refine when the explicit-inverse solve leaves a relative residual above ~50 eps.  The reference's LDL'
+  // solve leaves O(eps); a GEMV with K^-1 leaves up to eps cond(K), and ADMM carries that difference into
+  // y (equality rows multiply it by 1e3 rho every iteration).  At 1e-12, unscaled members with equality rows
+  // (cond(K) ~ 1e4) were left unrefined and missed the parity bar; the MPC batch stays below 5e-15.
   e = getenv("OSQP_AMD_BATCH_REFINE_TOL");
-  t.refine_tol = e ? atof(e) : 1e-12;
+  t.refine_tol = e ? atof(e) : 1e-14;
   e = getenv("OSQP_AMD_BATCH_PROFILE");
   t.profile = e ? atoi(e) : 0;
   e = getenv("OSQP_AMD_BATCH_ABLATE");   // timing experiments only: skip phases of the loop (results are garbage)
@@ -1026,6 +1046,12 @@ extern "C" c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const c
   if (settings->rho <= 0 || settings->sigma <= 0 || settings->alpha <= 0 || settings->alpha >= 2 ||
       settings->max_iter <= 0 || settings->scaling < 0 || settings->check_termination < 0)
     return OSQP_SETTINGS_VALIDATION_ERROR;
+  // the kernel has no polish step and no clock: refusing beats an answer the caller did not ask for
+  if (settings->polish || settings->time_limit > 0) {
+    fprintf(stderr, "osqp_amd batch: %s is not implemented by the batched engine\n",
+            settings->polish ? "polish" : "time_limit");
+    return OSQP_SETTINGS_VALIDATION_ERROR;
+  }
   if (n > 128) {
     fprintf(stderr, "osqp_amd batch: n = %d > 128 is not supported by the register-tiled engine; "
                     "use one osqp_setup workspace per QP (one-QP-per-stream)\n", n);
@@ -1130,20 +1156,34 @@ extern "C" c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const c
     osqp_amd_batch_cleanup(b);
     return OSQP_LINSYS_SOLVER_INIT_ERROR;
   }
-  if (b->lds_bytes > 64 * 1024) batch_set_lds(b);
   b->h_info.assign(B * 8, 0.0);
   // setup phase on the device: Ruiz scaling, rho classes, K^-1 (one workgroup per QP)
   batch_launch(b, 0);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) {
+  std::vector<int> hflag(B);
+  if (hipGetLastError() != hipSuccess ||
+      hipMemcpyAsync(hflag.data(), io.flag, B * sizeof(int), hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
+      hipStreamSynchronize(b->stream) != hipSuccess) {
     osqp_amd_batch_cleanup(b);
     return OSQP_LINSYS_SOLVER_INIT_ERROR;
   }
+  // a non-positive Gauss-Jordan pivot: K = P + sigma I + A' rho A is not positive definite, which
+  // the reference's LDL' inertia check rejects at osqp_setup (qdldl_interface.c:93-99)
+  for (size_t q = 0; q < B; q++)
+    if (hflag[q] & 8) {
+      fprintf(stderr, "osqp_amd batch: QP %zu of the batch is non-convex (K = P + sigma I + A' rho A is not "
+                      "positive definite)\n", q);
+      osqp_amd_batch_cleanup(b);
+      return OSQP_NONCVX_ERROR;
+    }
   *out = b;
   return 0;
 }
 
 static void batch_launch(osqp_amd_batch *b, int phase) {
   const dim3 g((unsigned)b->B);
+  // The dynamic-LDS limit is a property of the kernel function, not of this batch: a later batch
+  // of the same tile may have set it to its own, smaller size.  Set it for this one every launch.
+  if (b->lds_bytes > 64 * 1024) batch_set_lds(b);
 #define BL_(TR, TC, GC, PH) hipLaunchKernelGGL((k_batch_solve<TR, TC, GC, PH>), g, dim3(16 * GC), b->lds_bytes, b->stream, b->pat, b->st, b->io)
   if (b->tile == 8) { if (phase == 0) BL_(8, 4, 32, 0); else BL_(8, 4, 32, 1); }
   else              { if (phase == 0) BL_(4, 2, 32, 0); else BL_(4, 2, 32, 1); }
@@ -1204,6 +1244,39 @@ extern "C" c_int osqp_amd_batch_get(osqp_amd_batch *b, c_float *X, c_float *Y, c
   if (DX) BCHK(hipMemcpyAsync(DX, b->io.DXo, B * b->n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
   if (DY && b->m) BCHK(hipMemcpyAsync(DY, b->io.DYo, B * b->m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
   BCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+// Test hook: one member's workspace as the last setup / update / solve left it (K^-1 un-permuted
+// from the GEMV order on the host with the kernel's own g_index).
+extern "C" c_int osqp_amd_batch_member(osqp_amd_batch *b, c_int qp, c_float *D, c_float *E, c_float *c, c_float *rho,
+                                      c_int *ctype, c_float *Pv, c_float *Av, c_float *Kinv, c_int *NPo) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (qp < 0 || qp >= b->B) return OSQP_DATA_VALIDATION_ERROR;
+  BCHK(hipSetDevice(b->device));
+  const int n = b->n, m = b->m, NP = 16 * b->tile;
+  const long long q = qp, nv = (long long)b->nnzP + b->nnzA;
+  std::vector<int> t(m);
+  std::vector<double> wk(Kinv ? (size_t)NP * NP : 0);
+  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) : hipSuccess;
+  };
+  if (D) BCHK(get(D, b->io.Wd + q * n, n * sizeof(double)));
+  if (E) BCHK(get(E, b->io.We + q * m, m * sizeof(double)));
+  if (c) BCHK(get(c, b->io.Wc + q, sizeof(double)));
+  if (rho) BCHK(get(rho, b->io.rho_io + q, sizeof(double)));
+  if (ctype) BCHK(get(t.data(), b->io.Wt + q * m, m * sizeof(int)));
+  if (Pv) BCHK(get(Pv, b->io.Wv + q * nv, b->nnzP * sizeof(double)));
+  if (Av) BCHK(get(Av, b->io.Wv + q * nv + b->nnzP, b->nnzA * sizeof(double)));
+  if (Kinv) BCHK(get(wk.data(), b->io.Wk + q * NP * NP, wk.size() * sizeof(double)));
+  BCHK(hipStreamSynchronize(b->stream));
+  if (ctype) for (int i = 0; i < m; i++) ctype[i] = t[i];
+  if (Kinv) {
+    for (int i = 0; i < NP; i++)
+      for (int j = 0; j < NP; j++)
+        Kinv[(size_t)i * NP + j] = wk[b->tile == 8 ? g_index<128, BT>(i, j) : g_index<64, BT>(i, j)];
+  }
+  if (NPo) *NPo = NP;
   return 0;
 }
 
