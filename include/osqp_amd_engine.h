@@ -127,6 +127,9 @@ int hipeng_sync(hipeng *e);
  * qdldl_interface.c:350-376): b = [sigma x - q ; z - y/rho] on the host is
  * overwritten by [x_tilde ; z_tilde]. */
 int hipeng_kkt_solve(hipeng *e, c_float *b);
+/* The same solve without the refinement step hipeng_kkt_solve takes on the direct forms (res_kind 3 / 4): one application of
+ * the inverse the engine iterates with.  Used by the setup-time convexity probe and the direct-solve tests. */
+int hipeng_kkt_solve_unrefined(hipeng *e, c_float *b);
 
 /* Kernel-level entry points used by the parity tests (host in, host out):
  * which = 0: y = A x   (mat_vec, lin_alg.c:241-271)

@@ -122,6 +122,7 @@ static int build_dense_direct(hipeng *e, const csc *P, const csc *A, bool small_
 // fresh inverse multiplies a fixed probe vector and the formed matrix multiplies the result; more than DD_CHECK off (or a pivot that
 // was not positive) and the inverse is computed again by the Cholesky route; if that fails too the engine drops the dense solve.
 #define DD_CHECK 1e-6
+#define DD_FWD 8.0
 static int dd_refresh(hipeng *e) {
   const DdCtx &dd = e->dd;
   const int nap = dd.nap;
@@ -161,12 +162,24 @@ static int dd_refresh(hipeng *e) {
     hipLaunchKernelGGL(k_dd_gemv, gg, dim3(TB), lds, e->stream, e->c, nap, (const double *)dd.S, (const double *)dd.rr, dd.vv, 0);
     hipLaunchKernelGGL(k_dd_gemv, gg, dim3(TB), lds, e->stream, e->c, nap, (const double *)dd.S0, (const double *)dd.vv, dd.Bp, 0);
     hipLaunchKernelGGL(k_dd_probe_err, dim3(1), dim3(TB), 0, e->stream, dd, (const double *)dd.Bp, dd.D);
+    double fwd = 0.0;
+    if (attempt == 0) {
+      // The sweeps' inverse also gets a probe with a known solution: y = S^-1 (S0 p) against p, the forward error of the inverse itself.
+      // The residual above stays small while the sweeps lose digits in the directions of the small eigenvalues (a one-off solve
+      // 30x less accurate than an LU solve, rho x10 in tests/test_gpu_direct_solve_edges.py); more than DD_FWD nap eps off (|p| in
+      // [1, 2)) and the Cholesky route forms the inverse instead.
+      hipLaunchKernelGGL(k_dd_gemv, gg, dim3(TB), lds, e->stream, e->c, nap, (const double *)dd.S0, (const double *)dd.rr, dd.vv, 0);
+      hipLaunchKernelGGL(k_dd_gemv, gg, dim3(TB), lds, e->stream, e->c, nap, (const double *)dd.S, (const double *)dd.vv, dd.Bp, 0);
+      hipLaunchKernelGGL(k_dd_probe_err, dim3(1), dim3(TB), 0, e->stream, dd, (const double *)dd.Bp, dd.D + 1);
+      HIPCHK(hipMemcpyAsync(&fwd, dd.D + 1, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&err, dd.D, sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(&flag, dd.flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (!flag && err <= DD_CHECK) break;
-    if (e->trace) fprintf(stderr, "[osqp_amd] dense-direct: the %s inverse failed its check (%.2e%s)\n", attempt ? "Cholesky" : "block-sweep", err, flag ? ", a pivot was not positive" : "");
+    if (!flag && err <= DD_CHECK && fwd <= DD_FWD * nap * 0x1p-52) break;
+    if (e->trace) fprintf(stderr, "[osqp_amd] dense-direct: the %s inverse failed its check (%.2e, forward %.2e%s)\n", attempt ? "Cholesky" : "block-sweep", err, fwd,
+                          flag ? ", a pivot was not positive" : "");
   }
   e->dd_chol = attempt >= 1;                // (the inverse in use came from the Cholesky route)
   e->dd_check = err;

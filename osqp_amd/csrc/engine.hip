@@ -4270,7 +4270,7 @@ extern "C" int hipeng_download(hipeng *e, c_float *x, c_float *y, c_float *z, c_
 }
 
 // ---- plugin-boundary solve --------------------------------------------------
-extern "C" int hipeng_kkt_solve(hipeng *e, c_float *b) {
+extern "C" int hipeng_kkt_solve_unrefined(hipeng *e, c_float *b) {
   if (!e || !b) return HIPENG_ERR_ARG;
   HIPCHK(hipSetDevice(e->device));
   const int n = e->n, m = e->m;
@@ -4297,6 +4297,36 @@ extern "C" int hipeng_kkt_solve(hipeng *e, c_float *b) {
   }
   HIPCHK(hipStreamSynchronize(e->stream));
   if (e->c.nelim) for (int j = 0; j < n; j++) if (e->erow[(size_t)j] >= 0) b[j] = xte[(size_t)e->erow[(size_t)j]];
+  return 0;
+}
+extern "C" int hipeng_kkt_solve(hipeng *e, c_float *b) {
+  if (!e || !b) return HIPENG_ERR_ARG;
+  HIPCHK(hipSetDevice(e->device));
+  const int n = e->n, m = e->m;
+  // The direct forms apply an explicit inverse: inside the ADMM loop to a residual (the warm start absorbs its error), here to the whole
+  // right-hand side, where even an exact inverse leaves an error of cond(K) eps relative to |K^-1| |b| -- 15x that of an LU solve at
+  // cond 500.  So one step of refinement: r = b1 + A'(rho . b2) - K x~ from the host copies of [P | A'] (long double sums), then
+  // x~ += K^-1 r, z~ += A K^-1 r.
+  const bool direct = e->res_use && (e->res_kind == 3 || e->res_kind == 4) && (m == 0 || e->h_rho.size() == (size_t)m);
+  std::vector<double> b0;
+  if (direct) b0.assign(b, b + n + m);
+  if (int rc = hipeng_kkt_solve_unrefined(e, b)) return rc;
+  if (!direct || !(e->res_use && (e->res_kind == 3 || e->res_kind == 4))) return 0;
+  const HostMat &M = e->M;
+  const long double sigma = e->prm.sigma;
+  std::vector<long double> w((size_t)m, 0.0L);            // rho . (b2 - A x~)
+  for (int j = 0; j < n; j++)
+    for (int k = M.split[j]; k < M.rowptr[j + 1]; k++) w[(size_t)(M.col[k] - n)] -= (long double)M.val[k] * b[j];
+  for (int i = 0; i < m; i++) w[(size_t)i] = (long double)e->h_rho[(size_t)i] * (w[(size_t)i] + b0[(size_t)n + i]);
+  std::vector<double> r((size_t)n + m, 0.0);
+  for (int j = 0; j < n; j++) {
+    long double s = (long double)b0[(size_t)j] - sigma * b[j];
+    for (int k = M.rowptr[j]; k < M.split[j]; k++) s -= (long double)M.val[k] * b[M.col[k]];
+    for (int k = M.split[j]; k < M.rowptr[j + 1]; k++) s += (long double)M.val[k] * w[(size_t)(M.col[k] - n)];
+    r[(size_t)j] = (double)s;
+  }
+  if (int rc = hipeng_kkt_solve_unrefined(e, r.data())) return rc;
+  for (int q = 0; q < n + m; q++) b[q] += r[(size_t)q];
   return 0;
 }
 

@@ -494,7 +494,7 @@ c_int osqp_setup(OSQPWorkspace **workp, const OSQPData *data, const OSQPSettings
       rhs[k] = (c_float)((lcg >> 11) & 0xFFFFF) / 1048576.0 - 0.5;
     }
     hipeng_stats hs;
-    int bad = hipeng_set_params(s->eng, &pp) || hipeng_kkt_solve(s->eng, rhs) || hipeng_get_stats(s->eng, &hs);
+    int bad = hipeng_set_params(s->eng, &pp) || hipeng_kkt_solve_unrefined(s->eng, rhs) || hipeng_get_stats(s->eng, &hs);
     c_free(rhs);
     if (bad) return setup_fail(OSQP_LINSYS_SOLVER_INIT_ERROR, "HIP engine initialisation failed");
     if (hs.neg_curvature > 0)

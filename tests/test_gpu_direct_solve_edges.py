@@ -1,0 +1,528 @@
+"""GPU tests of the two direct linear-solve forms one KKT solve at a time, at their structural edges.
+
+Dense-direct (res_kind 4, csrc/dense_direct.h, dense_direct_host.h) and block-direct (res_kind 3, k_blk_* / k_cap_* /
+k_blk_apply_multi in engine.hip) are driven through the C shim: hipeng_create with no q, l, u, hipeng_kkt_solve, and the
+three calls that form the inverse again (hipeng_upload_rho, hipeng_upload_matrices, hipeng_set_params with a new sigma).
+Every case first asserts which form and which route inside it served the solve (hipeng_resident_info: [9] form, [3] dense
+unknowns or blocks, [5] Cholesky route, [15] coupling rows kc or sparse-Schur variables nb2), then measures [x~; z~]
+against the refined reference of tests/_kkt_reference.py:
+
+  direct form in use, hipeng_kkt_solve (one refinement step on these forms):
+      relative inf-norm forward error <= 10 x numpy's plain float64 error + 1e-14
+  direct form in use, hipeng_kkt_solve_unrefined (one application of the inverse the ADMM loop iterates with):
+      relative inf-norm forward error <= 10 x that of the float64 inverse of K (LAPACK) applied to the same rhs + 1e-14
+  engine reports it fell back: ||rhs - K x~|| / ||rhs|| <= 10 x 1e-10 (the PCG stop of a solve outside the ADMM loop), both calls
+
+Each solve prints its form, route and ratio (error / bar) for the record (pytest -s).
+
+The refresh that drives the dense-direct engine off its direct form (cond 9e11, sigma 1e-10) asserts only that it left: the PCG
+kernels it drops to reach no better than a relative residual of 0.3 there, far from the 1e-9 of the fallback bar; that leg is
+left open."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+from scipy import sparse
+
+from tests._kkt_reference import KKTReference, reduced_matrix
+
+pytestmark = pytest.mark.gpu
+
+RHO, RHO_MIN, EQ = 0.1, 1e-6, 1e3
+SIGMA = 1e-6
+PCG_STOP = 1e-10
+SWEEP, CHOL = 0, 1
+
+
+class HipengParams(C.Structure):          # include/osqp_amd_engine.h: hipeng_params
+    _fields_ = [("sigma", C.c_double), ("alpha", C.c_double), ("pcg_eps_rel", C.c_double), ("pcg_eps_abs", C.c_double),
+                ("pcg_max_iter", C.c_longlong), ("no_restart", C.c_longlong)]
+
+
+class _env:
+    def __init__(self, **kw): self.kw = kw
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in self.kw}
+        for k, v in self.kw.items():
+            os.environ[k] = str(v)
+    def __exit__(self, *a):
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+DD_ENV = dict(OSQP_AMD_RESIDENT=0, OSQP_AMD_DENSE_DIRECT=2)        # dense-direct whatever the size (block forms off)
+BD_ENV = dict(OSQP_AMD_BLOCK_DIRECT=1)
+
+
+def _lib():
+    import osqp_amd
+    from osqp_amd import _abi
+    L = osqp_amd.lib()
+    vp, fp = C.c_void_p, _abi.c_float_p
+    for name, args in (("hipeng_create", [C.POINTER(vp), C.POINTER(_abi.csc), C.POINTER(_abi.csc), fp, fp, fp, fp, C.POINTER(HipengParams), C.c_int]),
+                       ("hipeng_kkt_solve", [vp, fp]), ("hipeng_kkt_solve_unrefined", [vp, fp]), ("hipeng_upload_rho", [vp, fp]),
+                       ("hipeng_upload_matrices", [vp, C.POINTER(_abi.csc), C.POINTER(_abi.csc)]),
+                       ("hipeng_set_params", [vp, C.POINTER(HipengParams)]), ("hipeng_resident_info", [vp, C.POINTER(C.c_longlong)])):
+        f = getattr(L, name)
+        f.restype, f.argtypes = C.c_int, args
+    L.hipeng_destroy.restype, L.hipeng_destroy.argtypes = None, [vp]
+    L.hipeng_elim_count.restype, L.hipeng_elim_count.argtypes = C.c_longlong, [vp]
+    return L
+
+
+class Engine:
+    """One hipeng on device 0 and the refined reference of its current (P, A, sigma, rho)."""
+
+    def __init__(self, Pu, A, rho, sigma=SIGMA, env=None):
+        from osqp_amd import _abi
+        self.L, self.abi = _lib(), _abi
+        self.n, self.m = Pu.shape[0], A.shape[0]
+        self.Pu, self.A, self.rho, self.sigma = sparse.csc_matrix(Pu), sparse.csc_matrix(A), np.asarray(rho, float), sigma
+        self._hold = [_abi.CscHolder(self.Pu), _abi.CscHolder(self.A)]
+        self.prm = HipengParams(sigma, 1.6, PCG_STOP, 1e-15, max(20000, 10 * self.n), 0)
+        r = _abi.as_f64(self.rho)
+        self.h = C.c_void_p()
+        with _env(**(env or {})):
+            rc = self.L.hipeng_create(C.byref(self.h), C.byref(self._hold[0].struct), C.byref(self._hold[1].struct), None, None, None,
+                                      _abi.fptr(r), C.byref(self.prm), 0)
+        assert rc == 0, rc
+        self.ref = None
+
+    def close(self):
+        if self.h:
+            self.L.hipeng_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def info(self):
+        out = (C.c_longlong * 16)()
+        assert self.L.hipeng_resident_info(self.h, out) == 0
+        return list(out)
+
+    def elim(self):
+        return int(self.L.hipeng_elim_count(self.h))
+
+    def set_rho(self, rho):
+        self.rho = np.asarray(rho, float)
+        r = self.abi.as_f64(self.rho)
+        assert self.L.hipeng_upload_rho(self.h, self.abi.fptr(r)) == 0
+        self.ref = None
+
+    def set_sigma(self, sigma):
+        self.sigma = self.prm.sigma = sigma
+        assert self.L.hipeng_set_params(self.h, C.byref(self.prm)) == 0
+        self.ref = None
+
+    def set_matrices(self, Pu, A):
+        Pu, A = sparse.csc_matrix(Pu), sparse.csc_matrix(A)
+        hp, ha = self.abi.CscHolder(Pu), self.abi.CscHolder(A)
+        assert (hp.nnz, ha.nnz) == (self._hold[0].nnz, self._hold[1].nnz)
+        assert self.L.hipeng_upload_matrices(self.h, C.byref(hp.struct), C.byref(ha.struct)) == 0
+        self.Pu, self.A, self._hold = Pu, A, [hp, ha]
+        self.ref = None
+
+    def reference(self):
+        if self.ref is None:
+            self.ref = KKTReference(self.Pu, self.A, self.sigma, self.rho)
+        return self.ref
+
+    def solve(self, b, refined=True):
+        out = self.abi.as_f64(b).copy()
+        f = self.L.hipeng_kkt_solve if refined else self.L.hipeng_kkt_solve_unrefined
+        assert f(self.h, self.abi.fptr(out)) == 0
+        return out
+
+    def check(self, tag, form, route=None, seed=0, nrhs=2):
+        """Assert the form (and, where given, the route) in use, then the bar for it on nrhs right-hand sides; returns the worst
+        ratio.  Where no route is given, which one serves depends on how far the sweeps' inverse is off its probes -- close to the
+        thresholds on well-conditioned systems, and the formation of S sums with atomics -- and the bar holds on either."""
+        inf = self.info()
+        if isinstance(form, (set, tuple)):
+            assert inf[9] in form, (tag, inf)
+        else:
+            assert inf[9] == form, (tag, "form", inf[9], "expected", form, inf)
+        if route is not None and inf[9] == 4:
+            assert inf[5] == route, (tag, "route", inf[5], "expected", route)
+        ref = self.reference()
+        rng = np.random.default_rng(seed)
+        worst = 0.0
+        for k in range(nrhs):
+            b = rng.standard_normal(self.n + self.m) * (1.0 if k == 0 else rng.uniform(0.1, 10.0, self.n + self.m))
+            _, _, plain = ref.solve(b)
+            for refined in (False, True):
+                out = self.solve(b, refined)
+                if inf[9] in (3, 4):
+                    err = ref.forward_error(out)
+                    yard = plain if refined else ref.inverse_error(b)
+                    bar = 10.0 * yard + 1e-14
+                    what = f"fwd {err:.2e} {'numpy' if refined else 'inv(K)'} {yard:.2e}"
+                else:
+                    err = ref.residual(out[: self.n], b)
+                    bar = 10.0 * PCG_STOP
+                    what = f"res {err:.2e}"
+                ratio = err / bar
+                worst = max(worst, ratio)
+                route_s = "" if inf[9] != 4 else (" chol" if inf[5] else " sweep")
+                kind = "refined" if refined else "unrefined"
+                print(f"[direct-edges] {tag}: {kind} form {inf[9]}{route_s} n3={inf[3]} n15={inf[15]} {what} ratio {ratio:.3f}")
+                assert err <= bar, (tag, kind, inf[9], inf[5], err, bar, plain)
+        return worst
+
+
+def _classes(m, rng, eq=0.3, loose=0.2):
+    r = rng.random(m)
+    rho = np.full(m, RHO)
+    rho[r < eq] = EQ * RHO
+    rho[r > 1.0 - loose] = RHO_MIN
+    return rho
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# dense-direct problems
+# ---------------------------------------------------------------------------------------------------------------
+def dd_problem(na, seed, row_len=40, nd=None, nshort=None, b2_nbrs=(), nslack=0, pyy=0.0, Pcore=None, a_scale=1.0):
+    """Core variables 0..na-1 all coupled in P (tridiagonal unless Pcore is given: no B2 candidates, no elimination), so they
+    are exactly the dense unknowns.  nd rows of row_len entries over the core (dense when row_len >= 32), nshort rows of 2-3
+    entries.  Then one extra variable per entry of b2_nbrs with that many core neighbours (in two rows of A: never eliminated)
+    and nslack slack variables (diagonal P = pyy, one entry each in a row of its own plus core entries: eliminated).
+    Returns triu(P), A, rho."""
+    rng = np.random.default_rng(seed)
+    nb, ns = len(b2_nbrs), nslack
+    n = na + nb + ns
+    if Pcore is None:
+        d = rng.uniform(2.0, 3.0, na)
+        Pcore = sparse.diags([d, np.full(na - 1, -0.5)], [0, 1], shape=(na, na), format="csc") if na > 1 else sparse.csc_matrix(d.reshape(1, 1))
+    parts = [sparse.triu(Pcore), sparse.diags(rng.uniform(0.5, 2.0, nb)) if nb else None, sparse.diags(np.full(ns, pyy)) if ns and pyy else None]
+    P = sparse.block_diag([q for q in parts if q is not None], format="csc")
+    if ns and pyy == 0.0:            # P_yy = 0 stored as explicit zeros on the diagonal
+        P = sparse.coo_matrix(P, shape=(na + nb, na + nb))
+        P = sparse.coo_matrix((np.concatenate([P.data, np.zeros(ns)]), (np.concatenate([P.row, np.arange(na + nb, n)]),
+                                                                        np.concatenate([P.col, np.arange(na + nb, n)]))), shape=(n, n)).tocsc()
+    rows = []
+    nd = max(1, na // 64) if nd is None else nd
+    nshort = max(1, na // 4) if nshort is None else nshort
+    for _ in range(nd):
+        k = min(row_len, na)
+        cols = rng.choice(na, k, replace=False)
+        rows.append((cols, rng.standard_normal(k) * a_scale / np.sqrt(k)))
+    for _ in range(nshort):
+        k = min(int(rng.integers(2, 4)), na)
+        cols = rng.choice(na, k, replace=False)
+        rows.append((cols, rng.standard_normal(k) * a_scale))
+    for t, nbrs in enumerate(b2_nbrs):
+        v = na + t
+        nbr = rng.choice(na, nbrs, replace=False) if nbrs else np.zeros(0, int)
+        half = (nbrs + 1) // 2
+        for part in (nbr[:half], nbr[half:]):
+            cols = np.concatenate([[v], part])
+            rows.append((cols, np.concatenate([[1.0], 0.5 * rng.standard_normal(part.size)]) * a_scale))
+    for s in range(ns):
+        v = na + nb + s
+        part = rng.choice(na, min(na, 3), replace=False)
+        rows.append((np.concatenate([[v], part]), np.concatenate([[rng.uniform(0.5, 2.0) * rng.choice([-1, 1])], rng.standard_normal(part.size)]) * a_scale))
+    m = len(rows)
+    ri = np.concatenate([np.full(len(c), i) for i, (c, _) in enumerate(rows)])
+    ci = np.concatenate([c for c, _ in rows])
+    vi = np.concatenate([v for _, v in rows])
+    A = sparse.csc_matrix((vi, (ri, ci)), shape=(m, n))
+    return sparse.triu(P, format="csc"), A, _classes(m, rng)
+
+
+def spectrum_p(nv, cond, seed, top=10.0):
+    """Dense SPD matrix with eigenvalues log-spaced in [top / cond, top]."""
+    rng = np.random.default_rng(seed)
+    Q, _ = np.linalg.qr(rng.standard_normal((nv, nv)))
+    P = (Q * np.logspace(np.log10(top), np.log10(top / cond), nv)) @ Q.T
+    return 0.5 * (P + P.T)
+
+
+DD_SIZES = [1, 127, 128, 129, 1023, 1024, 1025, 1920, 1921]
+
+
+@pytest.mark.parametrize("na", DD_SIZES)
+def test_dense_direct_sizes(na):
+    """Dense unknowns around the 128 padding, the small_only limit (1024) and the gemv / symv-tile switch (nap 2048).
+    (One dense unknown: a variable with nine one-neighbour variables around it, which leave by the sparse Schur complement.)"""
+    b2 = (1,) * 9 if na == 1 else ()
+    Pu, A, rho = dd_problem(na, seed=na, row_len=40 if na >= 40 else na, nd=1 if na < 40 else None, b2_nbrs=b2)
+    e = Engine(Pu, A, rho, env=DD_ENV)
+    try:
+        e.check(f"dd na={na}", 4)
+        assert e.info()[3] == na and e.info()[15] == len(b2), e.info()
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("row_len", [0, 31, 32])
+def test_dense_direct_row_lengths(row_len):
+    """No dense rows, rows of exactly 31 entries (scattered) and of 32 (rows of R)."""
+    Pu, A, rho = dd_problem(300, seed=row_len + 7, row_len=row_len, nd=0 if row_len == 0 else 6)
+    e = Engine(Pu, A, rho, env=DD_ENV)
+    try:
+        e.check(f"dd rows of {row_len}", 4)
+        assert e.info()[3] == 300
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("nbrs,in_b2", [((0, 8, 3), 3), ((9,), 0), ((8, 9, 0, 8), 3)])
+def test_dense_direct_b2_neighbours(nbrs, in_b2):
+    """Variables with 0 and 8 neighbours leave by the sparse Schur complement; one with 9 stays a dense unknown."""
+    Pu, A, rho = dd_problem(200, seed=len(nbrs) * 11 + sum(nbrs), b2_nbrs=nbrs)
+    e = Engine(Pu, A, rho, env=DD_ENV)
+    try:
+        e.check(f"dd B2 nbrs={nbrs}", 4)
+        inf = e.info()
+        assert inf[15] == in_b2 and inf[3] == 200 + len(nbrs) - in_b2, inf
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("pyy", [0.0, 0.7])
+@pytest.mark.parametrize("shape", ["plain", "b2", "coupledP", "rows31"])
+def test_dense_direct_with_eliminated_slacks(pyy, shape):
+    """Slack-like variables eliminated by the engine (P_yy = 0 and > 0) next to B2 variables, a dense coupled P and
+    31-entry rows: they must not count toward a row's length nor enter the dense set."""
+    kw = dict(plain={}, b2=dict(b2_nbrs=(2, 8, 9)), coupledP=dict(Pcore=sparse.csc_matrix(spectrum_p(150, 100.0, 5))),
+              rows31=dict(row_len=31, nd=4))[shape]
+    Pu, A, rho = dd_problem(150, seed=int(pyy * 10) + len(shape), nslack=20, pyy=pyy, **kw)
+    e = Engine(Pu, A, rho, env=DD_ENV)
+    try:
+        e.check(f"dd slacks pyy={pyy} {shape}", 4)
+        assert e.elim() == 20
+        inf = e.info()
+        nb2 = 2 if shape == "b2" else 0
+        assert inf[15] == nb2 and inf[3] == 150 + (1 if shape == "b2" else 0), inf
+    finally:
+        e.close()
+
+
+def test_dense_direct_small_call_and_default_choice():
+    """Without the forcing switch: at most 1024 dense unknowns take the dense-direct solve ahead of the resident PCG."""
+    Pu, A, rho = dd_problem(1024, seed=3)
+    e = Engine(Pu, A, rho, env=dict(OSQP_AMD_BLOCK_DIRECT=0))
+    try:
+        e.check("dd default 1024", 4)
+    finally:
+        e.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# block-direct problems
+# ---------------------------------------------------------------------------------------------------------------
+def bd_problem(blocks, seed, kc=0, nhuge=0, cond=None, zeros_in=None, single=True):
+    """P = dense diagonal blocks of the given sizes (cond: each block's spectrum spans cond; zeros_in: a block index whose
+    upper triangle stores a third of its entries as explicit zeros), A = one single-entry row per variable (single), kc
+    coupling rows of 2-6 entries across blocks, nhuge rows over every variable."""
+    rng = np.random.default_rng(seed)
+    n = int(sum(blocks))
+    Pb = []
+    for t, b in enumerate(blocks):
+        if cond is not None:
+            B = spectrum_p(b, cond, seed * 100 + t, top=10.0)
+        else:
+            G = rng.standard_normal((b, b)) / np.sqrt(b)
+            B = G @ G.T + np.eye(b)
+        if zeros_in == t:
+            iu = np.triu_indices(b, 1)
+            pick = rng.random(iu[0].size) < 1.0 / 3.0
+            B[iu[0][pick], iu[1][pick]] = 0.0
+            B[iu[1][pick], iu[0][pick]] = 0.0
+            B += np.eye(b) * (1.0 + np.abs(np.linalg.eigvalsh(B)).max())
+        U = np.triu(B)
+        r, c = np.nonzero(np.triu(np.ones((b, b))))
+        Pb.append(sparse.csc_matrix((U[r, c], (r, c)), shape=(b, b)))     # full upper triangle stored, zeros included
+    Pu = sparse.block_diag(Pb, format="csc")
+    rows = []
+    if single:
+        for j in range(n):
+            rows.append(([j], [rng.uniform(0.5, 2.0) * rng.choice([-1.0, 1.0]) * (0.3 / np.sqrt(cond) if cond else 1.0)]))   # (cond: at the scale of the smallest eigenvalues)
+    for _ in range(kc):
+        k = int(rng.integers(2, 7))
+        cols = rng.choice(n, k, replace=False)
+        rows.append((cols, rng.standard_normal(k) * (0.3 if cond else 1.0)))
+    for _ in range(nhuge):
+        rows.append((np.arange(n), rng.standard_normal(n) / np.sqrt(n)))
+    m = len(rows)
+    ri = np.concatenate([np.full(len(c), i) for i, (c, _) in enumerate(rows)])
+    ci = np.concatenate([np.asarray(c) for c, _ in rows])
+    vi = np.concatenate([np.asarray(v, float) for _, v in rows])
+    A = sparse.csc_matrix((vi, (ri, ci)), shape=(m, n))
+    return Pu, A, _classes(m, rng)
+
+
+BLOCKS = {"32": [32] * 6, "33": [33] * 5, "63": [63] * 4, "64": [64] * 4, "96": [96] * 3, "127": [127] * 2, "128": [128] * 2,
+          "mixed": [32, 128, 33, 63, 96, 64, 127, 40]}
+
+
+@pytest.mark.parametrize("name", list(BLOCKS))
+def test_block_direct_block_sizes(name):
+    """Plain form (single-entry rows only) at block sizes 32 .. 128, around the pitch rule and a mixed tiling."""
+    blocks = BLOCKS[name]
+    Pu, A, rho = bd_problem(blocks, seed=len(name) + blocks[0])
+    e = Engine(Pu, A, rho, env=BD_ENV)
+    try:
+        e.check(f"bd blocks {name}", 3)
+        inf = e.info()
+        assert inf[3] == len(blocks) and inf[15] == 0, inf
+    finally:
+        e.close()
+
+
+def test_block_direct_explicit_zeros_in_block():
+    """A block whose stored upper triangle is a third explicit zeros still passes the density rule and is inverted whole."""
+    Pu, A, rho = bd_problem([64, 96, 64], seed=9, zeros_in=1)
+    assert (Pu.data == 0.0).sum() > 1000
+    e = Engine(Pu, A, rho, env=BD_ENV)
+    try:
+        e.check("bd explicit zeros", 3)
+        assert e.info()[3] == 3
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("kc", [1, 15, 16, 17, 32, 33, 512])
+def test_block_direct_coupled_rows(kc):
+    """Coupling rows as the Woodbury term, in 16-column groups of k_blk_apply_multi / k_cpl_dot, up to CPL_MAX."""
+    Pu, A, rho = bd_problem([64, 128, 96, 64, 128, 32, 100], seed=kc, kc=kc)
+    e = Engine(Pu, A, rho, env=BD_ENV)
+    try:
+        e.check(f"bd kc={kc}", 3)
+        assert e.info()[15] == kc
+    finally:
+        e.close()
+
+
+def test_block_direct_not_chosen_above_cpl_max():
+    """513 coupling rows: not the block-direct form; the dense-direct small call takes the 612 unknowns instead."""
+    Pu, A, rho = bd_problem([64, 128, 96, 64, 128, 32, 100], seed=513, kc=513)
+    e = Engine(Pu, A, rho, env=BD_ENV)
+    try:
+        inf = e.info()
+        assert inf[9] == 4 and inf[3] == 612, inf
+        e.check("bd kc=513", 4)
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("nhuge,form_kc", [(1, 0), (4, 0), (5, 5)])
+def test_block_direct_huge_rows(nhuge, form_kc):
+    """Huge rows (>= 8192 entries): up to 4 folded into the plain form; 5 are not folded and enter as coupling rows."""
+    Pu, A, rho = bd_problem([128] * 64, seed=nhuge, nhuge=nhuge)
+    e = Engine(Pu, A, rho, env=BD_ENV)
+    try:
+        inf = e.info()
+        assert inf[9] == 3 and inf[3] == 64 and inf[15] == form_kc, inf
+        e.check(f"bd huge={nhuge}", 3, nrhs=2)
+    finally:
+        e.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# conditioning
+# ---------------------------------------------------------------------------------------------------------------
+CONDS = [1e1, 1e4, 1e5, 1e6, 1e8]
+
+
+def _cond(e):
+    return float(np.linalg.cond(reduced_matrix(e.Pu, e.A, e.sigma, e.rho)))
+
+
+@pytest.mark.parametrize("cond", CONDS)
+def test_dense_direct_conditioning(cond):
+    Pu, A, rho = dd_problem(256, seed=int(np.log10(cond)), Pcore=sparse.csc_matrix(spectrum_p(256, cond, 1)), nshort=20, nd=2, a_scale=0.3)
+    e = Engine(Pu, A, rho, env=DD_ENV)
+    try:
+        c = _cond(e)
+        assert cond / 30 <= c <= cond * 30, c
+        inf = e.info()
+        print(f"[direct-edges] dd cond {c:.1e}: form {inf[9]} route {inf[5]}")
+        e.check(f"dd cond {c:.0e}", 4, CHOL if cond >= 1e6 else None)     # (the sweeps' inverse fails its probe checks from cond ~1e6 on)     # (the sweep inverse fails its probe check from cond ~1e6 on)
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("cond", CONDS)
+def test_block_direct_conditioning(cond):
+    Pu, A, rho = bd_problem([64] * 4, seed=int(np.log10(cond)) + 40, cond=cond, kc=8, single=True)
+    e = Engine(Pu, A, rho, env=BD_ENV)
+    try:
+        c = _cond(e)
+        print(f"[direct-edges] bd cond {c:.1e}: form {e.info()[9]}")      # (the 64-wide blocks pass their check up to cond 2e7)
+        e.check(f"bd cond {c:.0e}", 3)
+    finally:
+        e.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# refresh paths on one live engine
+# ---------------------------------------------------------------------------------------------------------------
+def test_dense_direct_refresh_paths():
+    Pu, A, rho = dd_problem(200, seed=21, b2_nbrs=(3, 5), nslack=10, pyy=0.3)
+    e = Engine(Pu, A, rho, env=DD_ENV)
+    try:
+        e.check("dd refresh: start", 4)
+        # (the sweeps' inverse of this one is 100x less accurate than a float64 inverse; its known-solution probe sends it to the
+        # Cholesky route)
+        e.set_rho(rho * 10.0); e.check("dd refresh: rho x10", 4, CHOL)
+        e.set_rho(rho / 10.0); e.check("dd refresh: rho /10", 4)
+        e.set_rho(_classes(e.m, np.random.default_rng(5), eq=0.5, loose=0.3)); e.check("dd refresh: classes", 4)
+        e.set_sigma(1e-3); e.check("dd refresh: sigma", 4)
+        # new values, same pattern: the core of P scaled toward singular, then back; then far enough (sigma 1e-10 too) that
+        # the Cholesky inverse fails its check and the engine leaves the dense-direct form for the PCG kernels for good
+        for s, tag, route in ((1e-3, "P x1e-3", None), (1e-7, "P x1e-7", CHOL), (1.0, "P x1", None)):
+            coo = Pu.tocoo()
+            scale = np.where(coo.col < 200, s, 1.0)
+            Pn = sparse.csc_matrix((coo.data * scale, (coo.row, coo.col)), shape=Pu.shape)
+            An = A.copy(); An.data = An.data * (1.0 + 0.1 * np.sin(np.arange(An.nnz)))
+            e.set_matrices(Pn, An)
+            inf = e.info()
+            print(f"[direct-edges] dd refresh {tag}: cond {_cond(e):.1e} form {inf[9]} route {inf[5]}")
+            e.check(f"dd refresh: {tag}", 4, route)
+        e.set_sigma(1e-10)
+        coo = Pu.tocoo()
+        e.set_matrices(sparse.csc_matrix((coo.data * np.where(coo.col < 200, 1e-9, 1.0), (coo.row, coo.col)), shape=Pu.shape), A)
+        inf = e.info()
+        print(f"[direct-edges] dd refresh P x1e-9 sigma 1e-10: cond {_cond(e):.1e} form {inf[9]} route {inf[5]}")
+        assert inf[9] == 0, inf          # (its accuracy: see the note in the module docstring)
+    finally:
+        e.close()
+
+
+def test_block_direct_refresh_paths():
+    Pu, A, rho = bd_problem([64, 96, 128, 64], seed=31, kc=20)
+    e = Engine(Pu, A, rho, env=BD_ENV)
+    try:
+        e.check("bd refresh: start", 3)
+        e.set_rho(rho * 10.0); e.check("bd refresh: rho x10", 3)
+        e.set_rho(rho / 10.0); e.check("bd refresh: rho /10", 3)
+        e.set_rho(_classes(e.m, np.random.default_rng(6), eq=0.5, loose=0.3)); e.check("bd refresh: classes", 3)
+        e.set_sigma(1e-3); e.check("bd refresh: sigma", 3)
+        for s, tag in ((1e-3, "P x1e-3"), (1e-7, "P x1e-7"), (1.0, "P x1")):
+            An = A.copy(); An.data = An.data * (1.0 + 0.1 * np.cos(np.arange(An.nnz)))
+            e.set_matrices(Pu * s, An)
+            inf = e.info()
+            print(f"[direct-edges] bd refresh {tag}: cond {_cond(e):.1e} form {inf[9]}")
+            e.check(f"bd refresh: {tag}", 3)
+    finally:
+        e.close()
+
+
+def test_two_dense_direct_engines_interleaved():
+    """Engines of nap 1920 (k_dd_gemv, 15 KiB of LDS) and 128: the smaller one is created second, then both are refreshed and
+    solved in turn.  Each stays within its own bar."""
+    big = Engine(*dd_problem(1920, seed=41), env=DD_ENV)
+    small = Engine(*dd_problem(100, seed=42), env=DD_ENV)
+    try:
+        for k in range(2):
+            big.check(f"two engines: nap 1920 #{k}", 4, seed=k)
+            small.check(f"two engines: nap 128 #{k}", 4, seed=k)
+            big.set_rho(big.rho * 3.0)
+            small.set_rho(small.rho * 3.0)
+        assert big.info()[3] == 1920 and small.info()[3] == 100
+    finally:
+        big.close()
+        small.close()
