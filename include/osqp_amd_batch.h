@@ -28,6 +28,26 @@ c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const csc *P, cons
                            const c_float *Px_all, const c_float *Ax_all,
                            const c_float *Q, const c_float *L, const c_float *U,
                            const OSQPSettings *settings, c_int device);
+/* Engines of a batch handle.  TILED: the engine of osqp_amd_batch_setup (n <= 128, K^-1 in registers, the
+ * pattern, values and vectors of a member in LDS).  STREAMED: 1 <= n <= 1024, any m as long as the member's
+ * vectors fit 160 KiB of LDS; K^-1 of every member lives in HBM (B x NP x NP doubles, NP = n rounded up to
+ * 32) and is streamed once per ADMM iteration. */
+#define OSQP_AMD_BATCH_TILED    0
+#define OSQP_AMD_BATCH_STREAMED 1
+/* osqp_amd_batch_setup with a choice of engine; TILED is osqp_amd_batch_setup itself.  Same return codes:
+ * OSQP_SETTINGS_VALIDATION_ERROR for polish / time_limit > 0 (or an unknown engine), OSQP_LINSYS_SOLVER_INIT_ERROR
+ * with a stderr line naming the limit when the shape does not fit, OSQP_NONCVX_ERROR naming the first
+ * non-convex member, OSQP_MEM_ALLOC_ERROR when the device arrays cannot be allocated. */
+c_int osqp_amd_batch_setup_engine(osqp_amd_batch **out, c_int engine, c_int batch, const csc *P, const csc *A,
+                                  const c_float *Px_all, const c_float *Ax_all,
+                                  const c_float *Q, const c_float *L, const c_float *U,
+                                  const OSQPSettings *settings, c_int device);
+/* The engine of a handle and the padded order NP of its K^-1 (the Kinv buffer of osqp_amd_batch_member is
+ * NP x NP).  NULL = skip. */
+c_int osqp_amd_batch_shape(osqp_amd_batch *b, c_int *engine, c_int *NP);
+/* Of the last solve: rounds = launches of the ADMM loop (streamed engine: 1 + rounds that resumed members after
+ * a K^-1 rebuild; tiled engine: 1), refined = members whose K^-1 solve takes the refinement step.  NULL = skip. */
+c_int osqp_amd_batch_rounds(osqp_amd_batch *b, c_int *rounds, c_int *refined);
 /* osqp_update_lin_cost / osqp_update_bounds for every QP (NULL = keep). */
 c_int osqp_amd_batch_update(osqp_amd_batch *b, const c_float *Q, const c_float *L, const c_float *U);
 /* osqp_solve for every QP; iterates persist on the device between calls
@@ -46,7 +66,8 @@ void  osqp_amd_batch_cleanup(osqp_amd_batch *b);
  * D [n], E [m], c [1], rho [1] (current scalar rho), ctype [m] (-1 free, 0 ineq, 1 eq),
  * Pv [nnzP], Av [nnzA] (scaled values, CSC order), Kinv [NP*NP] row-major, *NP = 64 or 128
  * (K^-1 of the kernel, padded with identity rows and columns; un-permuted from the kernel's
- * GEMV order with the kernel's own index function).  Returns 0 or an osqp_error_type code. */
+ * GEMV order with the kernel's own index function).  Streamed engine: *NP = n rounded up to 32
+ * (osqp_amd_batch_shape), K^-1 as stored.  Returns 0 or an osqp_error_type code. */
 c_int osqp_amd_batch_member(osqp_amd_batch *b, c_int qp, c_float *D, c_float *E, c_float *c, c_float *rho,
                             c_int *ctype, c_float *Pv, c_float *Av, c_float *Kinv, c_int *NP);
 

@@ -11,6 +11,8 @@ from . import _abi as abi
 from ._lib import lib
 
 BATCH_MAX_N = 128     # register-tiled K^-1 of the batch kernel (batch.hip)
+STREAMED_MAX_N = 1024  # streamed-inverse engine (batch_streamed.h)
+ENGINES = {"tiled": 0, "streamed": 1}   # OSQP_AMD_BATCH_TILED / _STREAMED
 INFO_FIELDS = ["iter", "status_val", "obj_val", "pri_res", "dua_res", "rho_updates", "rho_estimate", "rho"]
 
 
@@ -28,6 +30,14 @@ def _bind(L):
     L.osqp_amd_batch_get.argtypes = [H, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p]
     L.osqp_amd_batch_cleanup.restype = None
     L.osqp_amd_batch_cleanup.argtypes = [H]
+    L.osqp_amd_batch_setup_engine.restype = abi.c_int
+    L.osqp_amd_batch_setup_engine.argtypes = [C.POINTER(H), abi.c_int, abi.c_int, C.POINTER(abi.csc), C.POINTER(abi.csc),
+                                              abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p,
+                                              abi.c_float_p, C.POINTER(abi.OSQPSettings), abi.c_int]
+    L.osqp_amd_batch_shape.restype = abi.c_int
+    L.osqp_amd_batch_shape.argtypes = [H, abi.c_int_p, abi.c_int_p]
+    L.osqp_amd_batch_rounds.restype = abi.c_int
+    L.osqp_amd_batch_rounds.argtypes = [H, abi.c_int_p, abi.c_int_p]
     L.osqp_amd_batch_member.restype = abi.c_int
     L.osqp_amd_batch_member.argtypes = [H, abi.c_int] + [abi.c_float_p] * 4 + [abi.c_int_p] + [abi.c_float_p] * 3 + [abi.c_int_p]
 
@@ -42,11 +52,16 @@ class BatchOSQP:
         _bind(self._lib)
         self._h = None
 
-    def setup(self, P, A, Q, L, U, Px_all=None, Ax_all=None, device=None, **settings):
+    def setup(self, P, A, Q, L, U, Px_all=None, Ax_all=None, device=None, engine="auto", **settings):
         """P (n x n, any triangle content; upper triangle is used), A (m x n): shared
         pattern/values.  Q [B, n], L, U [B, m].  Px_all / Ax_all [B, nnz] optional
-        per-QP values in CSC order of triu(P) / A."""
+        per-QP values in CSC order of triu(P) / A.  engine: "auto" (the register-tiled kernel for
+        n <= 128, one single-QP engine per member above) or "streamed" (the streamed-inverse batch
+        engine, K^-1 in HBM, any n <= 1024)."""
         from . import engine_options
+        if engine not in ("auto", "streamed"):
+            raise ValueError("engine must be 'auto' or 'streamed', not %r" % (engine,))
+        self.engine = engine
         # neither path may hand back an unpolished or unclocked answer to a caller who asked for one: the batch
         # kernel implements neither, so both paths refuse them (OSQP_SETTINGS_VALIDATION_ERROR = 2)
         for k in ("polish", "time_limit"):
@@ -82,7 +97,7 @@ class BatchOSQP:
         if device is None:
             device = engine_options()["device"]
         self._many = None
-        if self.n > BATCH_MAX_N:
+        if engine == "auto" and self.n > BATCH_MAX_N:
             # The one-workgroup-per-QP kernel keeps K^-1 in registers (n <= 128).  Larger members of a batch go
             # one QP per HIP stream through the single-QP engine (osqp_amd/multi.py): same results, the PCG path.
             from . import OSQP, set_engine_options
@@ -109,13 +124,35 @@ class BatchOSQP:
             self._last = None
             return self
         h = C.c_void_p()
-        rc = self._lib.osqp_amd_batch_setup(C.byref(h), self.B, C.byref(self.Pu.struct), C.byref(self.Ah.struct),
-                                            _p(Px_all), _p(Ax_all), abi.fptr(Q), _p(L if self.m else None),
-                                            _p(U if self.m else None), C.byref(st), device)
-        if rc:
-            raise ValueError("osqp_amd_batch_setup failed with error %d" % rc)
+        if engine == "streamed":
+            rc = self._lib.osqp_amd_batch_setup_engine(C.byref(h), ENGINES["streamed"], self.B, C.byref(self.Pu.struct),
+                                                       C.byref(self.Ah.struct), _p(Px_all), _p(Ax_all), abi.fptr(Q),
+                                                       _p(L if self.m else None), _p(U if self.m else None), C.byref(st),
+                                                       device)
+            if rc:
+                raise ValueError("osqp_amd_batch_setup_engine failed with error %d" % rc)
+        else:
+            rc = self._lib.osqp_amd_batch_setup(C.byref(h), self.B, C.byref(self.Pu.struct), C.byref(self.Ah.struct),
+                                                _p(Px_all), _p(Ax_all), abi.fptr(Q), _p(L if self.m else None),
+                                                _p(U if self.m else None), C.byref(st), device)
+            if rc:
+                raise ValueError("osqp_amd_batch_setup failed with error %d" % rc)
         self._h = h
         return self
+
+    def shape(self):
+        """(engine, NP) of a kernel batch: engine 0 = tiled, 1 = streamed; K^-1 is NP x NP (padded)."""
+        e = np.zeros(1, np.int64); npo = np.zeros(1, np.int64)
+        if self._lib.osqp_amd_batch_shape(self._h, abi.iptr(e), abi.iptr(npo)):
+            raise RuntimeError("osqp_amd_batch_shape failed")
+        return int(e[0]), int(npo[0])
+
+    def rounds(self):
+        """Of the last solve: (launches of the ADMM loop, members whose K^-1 solve is refined)."""
+        r = np.zeros(1, np.int64); f = np.zeros(1, np.int64)
+        if self._lib.osqp_amd_batch_rounds(self._h, abi.iptr(r), abi.iptr(f)):
+            raise RuntimeError("osqp_amd_batch_rounds failed")
+        return int(r[0]), int(f[0])
 
     def _many_update(self, Q, L, U):
         # the first failing member's code comes back (and which member it was stays readable in `last_update_failed`)
@@ -179,11 +216,11 @@ class BatchOSQP:
     def member_workspace(self, qp):
         """Test hook: member qp's workspace as the last setup / update / solve left it -- D, E, c, rho (scalar),
         ctype (-1 free, 0 inequality, 1 equality), scaled Pv / Av (CSC order of triu(P) / A) and the kernel's
-        K^-1 as an NP x NP matrix (padded with identity to NP = 64 or 128)."""
+        K^-1 as an NP x NP matrix (padded with identity to NP = 64 or 128; the streamed engine: n rounded up to 32)."""
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): there is no packed batch "
                                "workspace to read" % BATCH_MAX_N)
-        NP = 16 * (4 if self.n <= 64 else 8)
+        NP = self.shape()[1]
         D = np.zeros(self.n); E = np.zeros(max(self.m, 1)); c = np.zeros(1); rho = np.zeros(1)
         ct = np.zeros(max(self.m, 1), np.int64); Pv = np.zeros(max(self.Pu.nnz, 1)); Av = np.zeros(max(self.Ah.nnz, 1))
         K = np.zeros((NP, NP)); npo = np.zeros(1, np.int64)

@@ -966,7 +966,14 @@ __global__ void __launch_bounds__(1024) k_batch_order(long long B, const double 
   for (long long b = tid; b < B; b += 1024) order[atomicAdd(&hist[1023 - (int)(info[b * 8] * sc)], 1)] = (int)b;
 }
 
+#include "batch_streamed.h"
+
 struct osqp_amd_batch {
+  int engine = OSQP_AMD_BATCH_TILED;
+  int NPs = 0;              // streamed engine: padded order of K^-1 (n rounded up to 32)
+  BSPattern kpat{};         // streamed engine: pattern of K for k_bs_form
+  int *d_count = nullptr, *d_list[2] = {nullptr, nullptr};   // streamed engine: rebuild requests of a round
+  int last_rounds = 0;
   int device = 0, tile = 8, threads = 512;
   long long B = 0;
   int n = 0, m = 0, nnzP = 0, nnzA = 0;
@@ -1032,11 +1039,17 @@ static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
   b->lpt = e ? atoi(e) : 1;   // phase time stamps (wall_clock64 ticks) written into DX[0..7]
 }
 
-extern "C" c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const csc *P, const csc *A,
-                                     const c_float *Px_all, const c_float *Ax_all,
-                                     const c_float *Q, const c_float *L, const c_float *U,
-                                     const OSQPSettings *settings, c_int device) {
+static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, const std::vector<int> &Pi,
+                             const std::vector<int> &Ap, const std::vector<int> &Ai);
+static int bs_setup_launch(osqp_amd_batch *b);
+
+static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const csc *P, const csc *A,
+                         const c_float *Px_all, const c_float *Ax_all,
+                         const c_float *Q, const c_float *L, const c_float *U,
+                         const OSQPSettings *settings, c_int device) {
   if (!out || !P || !A || !Q || !settings || batch <= 0) return OSQP_DATA_VALIDATION_ERROR;
+  if (engine != OSQP_AMD_BATCH_TILED && engine != OSQP_AMD_BATCH_STREAMED) return OSQP_SETTINGS_VALIDATION_ERROR;
+  const bool streamed = engine == OSQP_AMD_BATCH_STREAMED;
   *out = nullptr;
   const int n = (int)P->n, m = (int)A->m;
   if (P->m != P->n || A->n != P->n || n <= 0 || (m > 0 && (!L || !U))) return OSQP_DATA_VALIDATION_ERROR;
@@ -1052,10 +1065,35 @@ extern "C" c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const c
             settings->polish ? "polish" : "time_limit");
     return OSQP_SETTINGS_VALIDATION_ERROR;
   }
-  if (n > 128) {
+  if (!streamed && n > 128) {
     fprintf(stderr, "osqp_amd batch: n = %d > 128 is not supported by the register-tiled engine; "
                     "use one osqp_setup workspace per QP (one-QP-per-stream)\n", n);
     return OSQP_LINSYS_SOLVER_INIT_ERROR;
+  }
+  if (streamed && n > BS_MAX_N) {
+    fprintf(stderr, "osqp_amd batch: n = %d > %d is not supported by the streamed engine\n", n, BS_MAX_N);
+    return OSQP_LINSYS_SOLVER_INIT_ERROR;
+  }
+  if (streamed && batch > 65535) {   // k_bs_form's grid: y = members
+    fprintf(stderr, "osqp_amd batch: %lld members > 65535 are not supported by the streamed engine\n", (long long)batch);
+    return OSQP_LINSYS_SOLVER_INIT_ERROR;
+  }
+  const int NPs = (n + 31) & ~31;
+  if (streamed && bs_lds_bytes(NPs, m) > 160 * 1024) {
+    fprintf(stderr, "osqp_amd batch: problem needs %zu B of LDS per QP (> 160 KiB) in the streamed engine\n",
+            bs_lds_bytes(NPs, m));
+    return OSQP_LINSYS_SOLVER_INIT_ERROR;
+  }
+  if (streamed && m > 0) {   // products of the A'A term of K: sum over rows of c (c + 1) / 2, c entries per row
+    std::vector<size_t> rc_(m, 0);
+    for (c_int k = 0; k < A->p[n]; k++) rc_[A->i[k]]++;
+    size_t ntri = 0;
+    for (size_t c : rc_) ntri += c * (c + 1) / 2;
+    if (ntri > (size_t)BS_MAX_TRIPLES) {
+      fprintf(stderr, "osqp_amd batch: A'A has %zu row products (> %d) -- A's rows are too dense for the streamed "
+                      "engine\n", ntri, BS_MAX_TRIPLES);
+      return OSQP_LINSYS_SOLVER_INIT_ERROR;
+    }
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -1065,6 +1103,7 @@ extern "C" c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const c
   osqp_amd_batch *b = new (std::nothrow) osqp_amd_batch();
   if (!b) return OSQP_MEM_ALLOC_ERROR;
   b->device = (int)device; b->B = batch; b->n = n; b->m = m;
+  b->engine = (int)engine; b->NPs = streamed ? NPs : 0;
   b->nnzP = (int)P->p[n]; b->nnzA = (int)A->p[n];
   b->tile = n <= 64 ? 4 : 8;
   b->threads = 512;   // 8x4 (n <= 128) or 4x2 (n <= 64) register tiles; 256-thread variants (8x8 tiles) spill
@@ -1128,12 +1167,13 @@ extern "C" c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const c
   rc |= balloc(b, &io.rho_io, B); rc |= balloc(b, &io.info, B * 8);
   { int *ord = nullptr; rc |= balloc(b, &ord, B); b->d_order = ord; }
   {
-    const size_t NPs = (size_t)16 * b->tile;
+    const size_t NPk = streamed ? (size_t)b->NPs : (size_t)16 * b->tile;
     rc |= balloc(b, &io.Wv, B * ((size_t)b->nnzP + b->nnzA));
     rc |= balloc(b, &io.Wq, B * n); rc |= balloc(b, &io.Wl, B * m); rc |= balloc(b, &io.Wu, B * m);
     rc |= balloc(b, &io.Wd, B * n); rc |= balloc(b, &io.We, B * m); rc |= balloc(b, &io.Wc, B);
-    rc |= balloc(b, &io.Wk, B * NPs * NPs); rc |= balloc(b, &io.Wt, B * m); rc |= balloc(b, &io.flag, B);
+    rc |= balloc(b, &io.Wk, B * NPk * NPk); rc |= balloc(b, &io.Wt, B * m); rc |= balloc(b, &io.flag, B);
     rc |= balloc(b, &b->dQ, B * n); rc |= balloc(b, &b->dL, B * m); rc |= balloc(b, &b->dU, B * m);
+    if (streamed) { rc |= balloc(b, &b->d_count, 1); rc |= balloc(b, &b->d_list[0], B); rc |= balloc(b, &b->d_list[1], B); }
   }
   if (rc) { osqp_amd_batch_cleanup(b); return OSQP_MEM_ALLOC_ERROR; }
   io.Px = dPx; io.Ax = dAx; io.Q = dQ; io.L = dL; io.U = dU;
@@ -1146,19 +1186,26 @@ extern "C" c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const c
   rc |= up(dQ, Q, B * n); rc |= up(dL, L, B * m); rc |= up(dU, U, B * m);
   if (rc || hipStreamSynchronize(b->stream) != hipSuccess) { osqp_amd_batch_cleanup(b); return OSQP_LINSYS_SOLVER_INIT_ERROR; }
 
-  const int NP = 16 * b->tile;
-  b->lds_bytes = sizeof(double) * ((size_t)b->nnzP + b->nnzA + 1 + 7 * NP + 11 * (size_t)m + 4 * NP + 64 + 256) +
-                 sizeof(int) * ((size_t)m + 4 + 3 * ((size_t)n + 1) + 2 * (size_t)b->nnzP + 2 * (size_t)Fp[n] +
-                                4 * (size_t)b->nnzA + (size_t)m + 1);
-  b->lds_bytes = (b->lds_bytes + 15) & ~(size_t)15;
-  if (b->lds_bytes > 160 * 1024) {
-    fprintf(stderr, "osqp_amd batch: problem needs %zu B of LDS per QP (> 160 KiB)\n", b->lds_bytes);
-    osqp_amd_batch_cleanup(b);
-    return OSQP_LINSYS_SOLVER_INIT_ERROR;
+  if (streamed) {
+    const int krc = bs_build_kpattern(b, Pp, Pi, Ap, Ai);
+    if (krc) { osqp_amd_batch_cleanup(b); return krc; }
+    b->lds_bytes = bs_lds_bytes(b->NPs, m);
+  } else {
+    const int NP = 16 * b->tile;
+    b->lds_bytes = sizeof(double) * ((size_t)b->nnzP + b->nnzA + 1 + 7 * NP + 11 * (size_t)m + 4 * NP + 64 + 256) +
+                   sizeof(int) * ((size_t)m + 4 + 3 * ((size_t)n + 1) + 2 * (size_t)b->nnzP + 2 * (size_t)Fp[n] +
+                                  4 * (size_t)b->nnzA + (size_t)m + 1);
+    b->lds_bytes = (b->lds_bytes + 15) & ~(size_t)15;
+    if (b->lds_bytes > 160 * 1024) {
+      fprintf(stderr, "osqp_amd batch: problem needs %zu B of LDS per QP (> 160 KiB)\n", b->lds_bytes);
+      osqp_amd_batch_cleanup(b);
+      return OSQP_LINSYS_SOLVER_INIT_ERROR;
+    }
   }
   b->h_info.assign(B * 8, 0.0);
   // setup phase on the device: Ruiz scaling, rho classes, K^-1 (one workgroup per QP)
-  batch_launch(b, 0);
+  if (streamed) (void)bs_setup_launch(b);
+  else batch_launch(b, 0);
   std::vector<int> hflag(B);
   if (hipGetLastError() != hipSuccess ||
       hipMemcpyAsync(hflag.data(), io.flag, B * sizeof(int), hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
@@ -1176,6 +1223,144 @@ extern "C" c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const c
       return OSQP_NONCVX_ERROR;
     }
   *out = b;
+  return 0;
+}
+
+extern "C" c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const csc *P, const csc *A,
+                                     const c_float *Px_all, const c_float *Ax_all,
+                                     const c_float *Q, const c_float *L, const c_float *U,
+                                     const OSQPSettings *settings, c_int device) {
+  return batch_setup(out, OSQP_AMD_BATCH_TILED, batch, P, A, Px_all, Ax_all, Q, L, U, settings, device);
+}
+
+extern "C" c_int osqp_amd_batch_setup_engine(osqp_amd_batch **out, c_int engine, c_int batch, const csc *P, const csc *A,
+                                            const c_float *Px_all, const c_float *Ax_all,
+                                            const c_float *Q, const c_float *L, const c_float *U,
+                                            const OSQPSettings *settings, c_int device) {
+  if (out) *out = nullptr;
+  return batch_setup(out, engine, batch, P, A, Px_all, Ax_all, Q, L, U, settings, device);
+}
+
+// ---------------------------------------------------------------------------
+// streamed engine: host side
+// ---------------------------------------------------------------------------
+// The pattern of K = P + sigma I + A' diag(rho) A for k_bs_form.  Every entry (i <= j) of triu(K) -- the diagonal,
+// triu(P) and triu(A'A) -- gets its triu(P) slot and the list of (A slot in column i, A slot in column j, row)
+// triples of its A'A term in ascending row order; each row of K lists its stored entries (i, j) and (j, i).  Both
+// halves of K sum the same triples in the same order, so K is symmetric to the bit.
+static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, const std::vector<int> &Pi,
+                             const std::vector<int> &Ap, const std::vector<int> &Ai) {
+  const int n = b->n, m = b->m;
+  std::vector<int> eid((size_t)n * n, -1);          // (i, j), i <= j -> entry
+  std::vector<int> ei, ej;
+  auto entry = [&](int i, int j) {
+    int &e = eid[(size_t)i * n + j];
+    if (e < 0) { e = (int)ei.size(); ei.push_back(i); ej.push_back(j); }
+    return e;
+  };
+  for (int j = 0; j < n; j++) entry(j, j);
+  for (int j = 0; j < n; j++)
+    for (int k = Pp[j]; k < Pp[j + 1]; k++) entry(Pi[k], j);
+  // rows of A (slots in column order) -> triples, counted first then filled in ascending row order
+  std::vector<int> Rp(m + 1, 0);
+  for (int k = 0; k < b->nnzA; k++) Rp[Ai[k] + 1]++;
+  for (int i = 0; i < m; i++) Rp[i + 1] += Rp[i];
+  std::vector<int> Rk(b->nnzA), Rc(b->nnzA), nx(Rp.begin(), Rp.end() - 1);
+  for (int j = 0; j < n; j++)
+    for (int k = Ap[j]; k < Ap[j + 1]; k++) { const int d = nx[Ai[k]]++; Rk[d] = k; Rc[d] = j; }
+  size_t ntri = 0;
+  for (int r = 0; r < m; r++) {
+    const size_t c = (size_t)(Rp[r + 1] - Rp[r]);
+    ntri += c * (c + 1) / 2;
+  }
+  for (int r = 0; r < m; r++)   // (ntri <= BS_MAX_TRIPLES: checked by batch_setup)
+    for (int a = Rp[r]; a < Rp[r + 1]; a++)
+      for (int c = a; c < Rp[r + 1]; c++) entry(Rc[a], Rc[c]);
+  const int nent = (int)ei.size();
+  std::vector<int> Ep(nent + 1, 0), slot(nent, -1);
+  for (int j = 0; j < n; j++)
+    for (int k = Pp[j]; k < Pp[j + 1]; k++) slot[eid[(size_t)Pi[k] * n + j]] = k;
+  for (int r = 0; r < m; r++)
+    for (int a = Rp[r]; a < Rp[r + 1]; a++)
+      for (int c = a; c < Rp[r + 1]; c++) Ep[eid[(size_t)Rc[a] * n + Rc[c]] + 1]++;
+  for (int e = 0; e < nent; e++) Ep[e + 1] += Ep[e];
+  std::vector<int> Ta(ntri), Tb(ntri), Tr(ntri), tx(Ep.begin(), Ep.end() - 1);
+  for (int r = 0; r < m; r++)
+    for (int a = Rp[r]; a < Rp[r + 1]; a++)
+      for (int c = a; c < Rp[r + 1]; c++) {
+        const int t = tx[eid[(size_t)Rc[a] * n + Rc[c]]]++;
+        Ta[t] = Rk[a]; Tb[t] = Rk[c]; Tr[t] = r;       // Rc[a] <= Rc[c]: slot of the smaller column first
+      }
+  // rows of K: entry (i, j) is stored in row i and, off the diagonal, in row j
+  std::vector<int> Kp(n + 1, 0);
+  for (int e = 0; e < nent; e++) { Kp[ei[e] + 1]++; if (ei[e] != ej[e]) Kp[ej[e] + 1]++; }
+  for (int i = 0; i < n; i++) Kp[i + 1] += Kp[i];
+  std::vector<int> Kj(Kp[n]), Ke(Kp[n]), kx(Kp.begin(), Kp.end() - 1);
+  for (int e = 0; e < nent; e++) {
+    int d = kx[ei[e]]++; Kj[d] = ej[e]; Ke[d] = e;
+    if (ei[e] != ej[e]) { d = kx[ej[e]]++; Kj[d] = ei[e]; Ke[d] = e; }
+  }
+  BSPattern &kp = b->kpat;
+  int rc = 0;
+  rc |= bupload(b, &kp.Ep, Ep); rc |= bupload(b, &kp.Eslot, slot);
+  rc |= bupload(b, &kp.Ta, Ta); rc |= bupload(b, &kp.Tb, Tb); rc |= bupload(b, &kp.Tr, Tr);
+  rc |= bupload(b, &kp.Rp, Kp); rc |= bupload(b, &kp.Rj, Kj); rc |= bupload(b, &kp.Re, Ke);
+  return rc ? OSQP_MEM_ALLOC_ERROR : 0;
+}
+
+// The dynamic-LDS limit of the streamed setup and loop kernels, set on the current device before every launch
+// (a batch of another size may have changed it since).
+static void bs_set_lds(osqp_amd_batch *b) {
+  if (b->lds_bytes <= 64 * 1024) return;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bs_setup), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bs_loop), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes);
+}
+
+// form and invert K for the members of list[0..count) (the whole batch when list is null) that have a rebuild due
+static void bs_rebuild(osqp_amd_batch *b, const int *list, long long count) {
+  hipLaunchKernelGGL(k_bs_form, dim3((unsigned)b->NPs, (unsigned)count), dim3(256), 0, b->stream,
+                     b->pat, b->kpat, b->io, b->NPs, b->st.sigma, list);
+  hipLaunchKernelGGL(k_bs_invert, dim3((unsigned)count), dim3(BS_NTI), 0, b->stream, b->n, b->io, b->NPs, list);
+}
+
+static int bs_setup_launch(osqp_amd_batch *b) {
+  bs_set_lds(b);
+  hipLaunchKernelGGL(k_bs_setup, dim3((unsigned)b->B), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, b->NPs);
+  bs_rebuild(b, nullptr, b->B);
+  return 0;
+}
+
+// One solve of the streamed engine: rounds of the ADMM loop.  Round 0 runs every member; a member whose rho
+// moves leaves with a rebuild request, and the next round re-forms and re-inverts K for those members and
+// resumes them.  One counter is read back per round; rounds <= rho updates of the slowest member + 1.
+static int bs_solve(osqp_amd_batch *b) {
+  b->io.order = (b->lpt && b->solves > 0) ? b->d_order : nullptr;   // first solve: no history, index order
+  bs_rebuild(b, nullptr, b->B);                  // members whose class changed in an update, or rho at max_iter
+  const int *list = nullptr;
+  long long count = b->B;
+  int cur = 0, rounds = 0;
+  for (;;) {
+    BCHK(hipMemsetAsync(b->d_count, 0, sizeof(int), b->stream));
+    bs_set_lds(b);
+    hipLaunchKernelGGL(k_bs_loop, dim3((unsigned)count), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io,
+                       b->NPs, list, b->d_count, b->d_list[cur]);
+    BCHK(hipGetLastError());
+    int h = 0;
+    BCHK(hipMemcpyAsync(&h, b->d_count, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    BCHK(hipStreamSynchronize(b->stream));
+    rounds++;
+    if (h == 0) break;
+    list = b->d_list[cur];
+    count = h;
+    bs_rebuild(b, list, count);
+    cur ^= 1;
+  }
+  bs_rebuild(b, nullptr, b->B);                  // rho moved in the last iteration: K^-1 follows it, as in k_batch_solve
+  if (b->lpt) hipLaunchKernelGGL(k_batch_order, dim3(1), dim3(1024), 0, b->stream, b->B, b->io.info, b->d_order);
+  BCHK(hipGetLastError());
+  BCHK(hipStreamSynchronize(b->stream));
+  b->last_rounds = rounds;
+  b->solves++;
   return 0;
 }
 
@@ -1224,6 +1409,7 @@ extern "C" c_int osqp_amd_batch_update(osqp_amd_batch *b, const c_float *Q, cons
 extern "C" c_int osqp_amd_batch_solve(osqp_amd_batch *b) {
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   BCHK(hipSetDevice(b->device));
+  if (b->engine == OSQP_AMD_BATCH_STREAMED) return bs_solve(b);
   b->io.order = (b->lpt && b->solves > 0) ? b->d_order : nullptr;   // first solve: no history, index order
   batch_launch(b, 1);
   if (b->lpt) hipLaunchKernelGGL(k_batch_order, dim3(1), dim3(1024), 0, b->stream, b->B, b->io.info, b->d_order);
@@ -1254,7 +1440,8 @@ extern "C" c_int osqp_amd_batch_member(osqp_amd_batch *b, c_int qp, c_float *D, 
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (qp < 0 || qp >= b->B) return OSQP_DATA_VALIDATION_ERROR;
   BCHK(hipSetDevice(b->device));
-  const int n = b->n, m = b->m, NP = 16 * b->tile;
+  const bool streamed = b->engine == OSQP_AMD_BATCH_STREAMED;
+  const int n = b->n, m = b->m, NP = streamed ? b->NPs : 16 * b->tile;
   const long long q = qp, nv = (long long)b->nnzP + b->nnzA;
   std::vector<int> t(m);
   std::vector<double> wk(Kinv ? (size_t)NP * NP : 0);
@@ -1271,12 +1458,36 @@ extern "C" c_int osqp_amd_batch_member(osqp_amd_batch *b, c_int qp, c_float *D, 
   if (Kinv) BCHK(get(wk.data(), b->io.Wk + q * NP * NP, wk.size() * sizeof(double)));
   BCHK(hipStreamSynchronize(b->stream));
   if (ctype) for (int i = 0; i < m; i++) ctype[i] = t[i];
-  if (Kinv) {
+  if (Kinv && streamed) {
+    std::copy(wk.begin(), wk.end(), Kinv);      // row-major already
+  } else if (Kinv) {
     for (int i = 0; i < NP; i++)
       for (int j = 0; j < NP; j++)
         Kinv[(size_t)i * NP + j] = wk[b->tile == 8 ? g_index<128, BT>(i, j) : g_index<64, BT>(i, j)];
   }
   if (NPo) *NPo = NP;
+  return 0;
+}
+
+extern "C" c_int osqp_amd_batch_shape(osqp_amd_batch *b, c_int *engine, c_int *NP) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (engine) *engine = b->engine;
+  if (NP) *NP = b->engine == OSQP_AMD_BATCH_STREAMED ? b->NPs : 16 * b->tile;
+  return 0;
+}
+
+extern "C" c_int osqp_amd_batch_rounds(osqp_amd_batch *b, c_int *rounds, c_int *refined) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (rounds) *rounds = b->engine == OSQP_AMD_BATCH_STREAMED ? b->last_rounds : (b->solves ? 1 : 0);
+  if (refined) {
+    BCHK(hipSetDevice(b->device));
+    std::vector<int> f((size_t)b->B);
+    BCHK(hipMemcpyAsync(f.data(), b->io.flag, f.size() * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    BCHK(hipStreamSynchronize(b->stream));
+    c_int c = 0;
+    for (int v : f) c += (v & 2) ? 1 : 0;
+    *refined = c;
+  }
   return 0;
 }
 
