@@ -17,7 +17,9 @@
 //     (src/auxil.c:76-98), the iteration (src/osqp.c:356-370), residuals and
 //     termination incl. infeasibility tests (src/auxil.c:227-512, 681-786), rho
 //     adaptation (src/auxil.c:13-74) and solution unscaling (src/scaling.c:177)
-//     follow the reference statement by statement, per QP.
+//     follow the reference statement by statement, per QP: batch_admm.h, the one copy
+//     that the streamed engine (batch_streamed.h, K^-1 in HBM) runs too.  This file adds
+//     the tiled engine's LDS layout, its K^-1 (form_K .. rebuild_kinv, TiledK) and the host side.
 // Sparsity patterns (shared by the batch) are read from global memory and stay
 // L1/L2 resident; per-QP data is read once and written once.
 #include <hip/hip_runtime.h>
@@ -253,6 +255,8 @@ __device__ __forceinline__ void b_reduce_many(double (&mx)[NMAX], double (&sm)[N
   __syncthreads();
 }
 
+#include "batch_admm.h"
+
 // ---------------------------------------------------------------------------
 template <int TR, int TC, int GC>
 __device__ __forceinline__ void form_K(double (&a)[TR][TC], int n, const BL &s, double sigma) {
@@ -424,477 +428,115 @@ __device__ __forceinline__ bool rebuild_kinv(int n, const BL &s, double sigma, d
 }
 
 // ---------------------------------------------------------------------------
-// the kernel
+// the tiled engine: LDS layout, its K solve, the kernel
 // ---------------------------------------------------------------------------
+// LDS working set: matrix values (+1: the n-vectors are read 16 bytes at a time by the GEMV), 7 n-vectors of
+// NP, 11 m-vectors, the Gauss-Jordan exchange (4 NP), 64 + 256 reduction doubles, m class ints (+4) and the
+// twelve pattern arrays.
+__host__ __device__ __forceinline__ size_t bt_lds_bytes(const BPattern &p, int NP) {
+  const size_t b = sizeof(double) * ((size_t)p.nnzP + p.nnzA + 1 + 7 * NP + 11 * (size_t)p.m + 4 * NP + 64 + 256) +
+                   sizeof(int) * ((size_t)p.m + 4 + 3 * ((size_t)p.n + 1) + 2 * (size_t)p.nnzP + 2 * (size_t)p.nnzPf +
+                                  4 * (size_t)p.nnzA + (size_t)p.m + 1);
+  return (b + 15) & ~(size_t)15;
+}
+// (also copies the shared pattern into LDS: visible after the next barrier)
+template <int NP, int NT>
+__device__ __forceinline__ BL bt_layout(double *lds, const BPattern &p) {
+  BL s;
+  const int n = p.n, m = p.m;
+  double *w = lds;
+  s.NP = NP; s.m = m;
+  s.Pv = w; w += p.nnzP; s.Av = w; w += p.nnzA;
+  w += (p.nnzP + p.nnzA) & 1;
+  s.nv = w; w += 7 * NP; s.mv = w; w += 11 * m;
+  s.rowk = w; w += 2 * NP; s.colk = w; w += 2 * NP; s.red = w; w += 64; s.gp = w; w += 256;
+  int *iw = reinterpret_cast<int *>(w);
+  s.ctype = iw; iw += m;
+  int *ib = iw;
+  s.Pp = iw; iw += n + 1; s.Pi = iw; iw += p.nnzP; s.Pc = iw; iw += p.nnzP;
+  s.Fp = iw; iw += n + 1; s.Fi = iw; iw += p.nnzPf; s.Fk = iw; iw += p.nnzPf;
+  s.Ap = iw; iw += n + 1; s.Ai = iw; iw += p.nnzA; s.Ac = iw; iw += p.nnzA;
+  s.Rp = iw; iw += m + 1; s.Rj = iw; iw += p.nnzA; s.Rk = iw; iw += p.nnzA;
+  // the host packs the twelve index arrays back to back in this order
+  const int tot = (int)(iw - ib);
+  for (int k = threadIdx.x; k < tot; k += NT) ib[k] = p.packed[k];
+  return s;
+}
+
+// K^-1 in registers.  A rho move re-forms and re-inverts K inside the loop, exactly like the reference's
+// re-factorisation, and the refinement verdict is taken again.
+template <int TR, int TC, int GC>
+struct TiledK {
+  static constexpr int NP = 16 * TR, NT = 16 * GC;
+  double ag[GL<NP>::RG][GL<NP>::CG];     // K^-1 in the GEMV layout
+  double *Wk;
+  __device__ __forceinline__ void solve(const BL &, const double *in, double *out) const { tile_gemv<NP>(ag, in, out); }
+  __device__ __forceinline__ bool leave(const BL &, const BPattern &, const BSettings &, const BIO &, long long, const BA &) const { return false; }
+  __device__ __forceinline__ void rho_moved(const BL &s, const BPattern &p, const BSettings &st, BA &a) {
+    rebuild_kinv<TR, TC, GC>(p.n, s, st.sigma, Wk);
+    load_kinv<NP, NT>(ag, Wk);
+    a.check_pending = true;
+  }
+};
+
 // PH = 0: setup phase (scale, classify, build K^-1, store the workspace);
 // PH = 1: solve phase (load the workspace, ADMM loop, store the solution).
-// Phase time stamps / per-phase accumulators exist only in -DOSQP_AMD_BATCH_DEBUG builds
-// (make BATCH_DEBUG=1): they cost ~26 registers and a 2 us s_memrealtime each.
-#ifdef OSQP_AMD_BATCH_DEBUG
-#define DBG(...) __VA_ARGS__
-#else
-#define DBG(...)
-#endif
 #ifndef BATCH_WAVES_PER_SIMD
 #define BATCH_WAVES_PER_SIMD 2   // 4 (two workgroups per CU, <= 128 registers) was measured slower: spills lengthen the slowest QP
 #endif
 template <int TR, int TC, int GC, int PH>
 __global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k_batch_solve(BPattern p, BSettings st, BIO io) {
-  constexpr int NP = 16 * TR, NT = 16 * GC, NW = NT / 64, phase = PH;
+  constexpr int NP = 16 * TR, NT = 16 * GC;
   static_assert(GC * TC == NP, "tile shape");
   static_assert(4 * NP <= NT, "the GEMV reduction and the column dots use four lanes per row/column");
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  const int n = p.n, m = p.m, tid = threadIdx.x;
-  const long long qp = (phase == 1 && io.order) ? io.order[blockIdx.x] : (int)blockIdx.x;
-  BL s;
-  {
-    double *w = lds;
-    s.NP = NP; s.m = m;
-    s.Pv = w; w += p.nnzP; s.Av = w; w += p.nnzA;
-    w += (p.nnzP + p.nnzA) & 1;          // n-vectors are read 16 bytes at a time by the GEMV
-    s.nv = w; w += 7 * NP; s.mv = w; w += 11 * m;
-    s.rowk = w; w += 2 * NP; s.colk = w; w += 2 * NP; s.red = w; w += 64; s.gp = w; w += 256;
-    int *iw = reinterpret_cast<int *>(w);
-    s.ctype = iw; iw += m;
-    int *ib = iw;
-    s.Pp = iw; iw += n + 1; s.Pi = iw; iw += p.nnzP; s.Pc = iw; iw += p.nnzP;
-    s.Fp = iw; iw += n + 1; s.Fi = iw; iw += p.nnzPf; s.Fk = iw; iw += p.nnzPf;
-    s.Ap = iw; iw += n + 1; s.Ai = iw; iw += p.nnzA; s.Ac = iw; iw += p.nnzA;
-    s.Rp = iw; iw += m + 1; s.Rj = iw; iw += p.nnzA; s.Rk = iw; iw += p.nnzA;
-    // the host packs the twelve index arrays back to back in this order
-    const int tot = (int)(iw - ib);
-    for (int k = tid; k < tot; k += NT) ib[k] = p.packed[k];
-  }
-  double ag[GL<NP>::RG][GL<NP>::CG];     // K^-1 in the GEMV layout
-  DBG(unsigned long long tstamp[8]; tstamp[0] = wall_clock64(); const unsigned long long cyc0 = clock64();)
-
-  // ---- load: raw problem (setup phase) or the per-QP workspace (solve phase) ---
-  double cs = 1.0;   // cost scaling c
-  for (int j = tid; j < NP; j += NT) {
-    s_q[j] = 0.0; s_x[j] = 0.0; s_xt[j] = 0.0; s_dx[j] = 0.0; s_D[j] = 1.0; s_tn[j] = 0.0; s_b[j] = 0.0;
-  }
-  for (int i = tid; i < m; i += NT) { s_z[i] = 0.0; s_y[i] = 0.0; s_E[i] = 1.0; s_dy[i] = 0.0; s_ws[i] = 0.0; }
-  __syncthreads();
-  const long long nv_ = (long long)p.nnzP + p.nnzA;
-  if (phase == 0) {
-    const double *Pg = io.Px + qp * io.strideP, *Ag = io.Ax + qp * io.strideA;
-    for (int k = tid; k < p.nnzP; k += NT) s.Pv[k] = Pg[k];
-    for (int k = tid; k < p.nnzA; k += NT) s.Av[k] = Ag[k];
-    for (int j = tid; j < n; j += NT) s_q[j] = io.Q[qp * n + j];
-    for (int i = tid; i < m; i += NT) { s_l[i] = io.L[qp * m + i]; s_u[i] = io.U[qp * m + i]; }
-  } else {
-    const double *Wv = io.Wv + qp * nv_;
-    for (int k = tid; k < p.nnzP; k += NT) s.Pv[k] = Wv[k];
-    for (int k = tid; k < p.nnzA; k += NT) s.Av[k] = Wv[p.nnzP + k];
-    for (int j = tid; j < n; j += NT) { s_q[j] = io.Wq[qp * n + j]; s_D[j] = io.Wd[qp * n + j]; }
-    for (int i = tid; i < m; i += NT) {
-      s_l[i] = io.Wl[qp * m + i]; s_u[i] = io.Wu[qp * m + i]; s_E[i] = io.We[qp * m + i];
-      s.ctype[i] = io.Wt[qp * m + i];
-    }
-    cs = io.Wc[qp];
-  }
-  __syncthreads();
-
-  DBG(tstamp[1] = wall_clock64();)
-  // ---- Ruiz equilibration (scaling.c:44-156), per QP -------------------------
-  for (int pass = 0; phase == 0 && pass < st.scaling; ++pass) {
-    for (int j = tid; j < n; j += NT) {
-      double v = 0.0;
-      for (int k = s.Fp[j]; k < s.Fp[j + 1]; ++k) v = fmax(v, fabs(s.Pv[s.Fk[k]]));
-      for (int k = s.Ap[j]; k < s.Ap[j + 1]; ++k) v = fmax(v, fabs(s.Av[k]));
-      s_tn[j] = 1.0 / sqrt(clip_scale(v));
-    }
-    for (int i = tid; i < m; i += NT) {
-      double v = 0.0;
-      for (int k = s.Rp[i]; k < s.Rp[i + 1]; ++k) v = fmax(v, fabs(s.Av[s.Rk[k]]));
-      s_tm[i] = 1.0 / sqrt(clip_scale(v));
-    }
-    __syncthreads();
-    for (int k = tid; k < p.nnzP; k += NT) s.Pv[k] = (s.Pv[k] * s_tn[s.Pi[k]]) * s_tn[s.Pc[k]];
-    for (int k = tid; k < p.nnzA; k += NT) s.Av[k] = (s.Av[k] * s_tm[s.Ai[k]]) * s_tn[s.Ac[k]];
-    for (int j = tid; j < n; j += NT) { s_q[j] = s_q[j] * s_tn[j]; s_D[j] = s_tn[j] * s_D[j]; }
-    for (int i = tid; i < m; i += NT) s_E[i] = s_tm[i] * s_E[i];
-    __syncthreads();
-    // cost normalisation: mean column norm of P (sequential sum, reference order) vs |q|_inf
-    double cn = 0.0, qn = 0.0;
-    for (int j = tid; j < n; j += NT) {
-      double v = 0.0;
-      for (int k = s.Fp[j]; k < s.Fp[j + 1]; ++k) v = fmax(v, fabs(s.Pv[s.Fk[k]]));
-      s_tn[j] = v;
-      qn = fmax(qn, fabs(s_q[j]));
-    }
-    qn = b_max<NW>(qn, s.red);
-    if (tid == 0) { double acc = 0.0; for (int j = 0; j < n; ++j) acc += s_tn[j]; s.red[12] = acc / (double)n; }
-    __syncthreads();
-    cn = s.red[12];
-    double ct = fmax(cn, clip_scale(qn));
-    ct = 1.0 / clip_scale(ct);
-    for (int k = tid; k < p.nnzP; k += NT) s.Pv[k] *= ct;
-    for (int j = tid; j < n; j += NT) s_q[j] *= ct;
-    cs *= ct;
-    __syncthreads();
-  }
-  const double cinv = 1.0 / cs;
-  const bool unscaled = st.scaling && !st.scaled_termination;
-  if (phase == 0) { for (int i = tid; i < m; i += NT) { s_l[i] = s_l[i] * s_E[i]; s_u[i] = s_u[i] * s_E[i]; } }
-  __syncthreads();
-
-  DBG(tstamp[2] = wall_clock64();)
-  // ---- rho vector (auxil.c:76-98) and warm start -----------------------------
-  double rho = phase == 0 ? st.rho : io.rho_io[qp];
-  rho = fmin(fmax(rho, 1e-6), 1e6);
-  for (int i = tid; i < m; i += NT) {
-    int t = 0;
-    if (phase == 0) {
-      if (s_l[i] < -BINF && s_u[i] > BINF) t = -1;
-      else if (s_u[i] - s_l[i] < st.rho_tol) t = 1;
-      s.ctype[i] = t;
-    } else t = s.ctype[i];
-    const double r = t == -1 ? 1e-6 : (t == 1 ? 1e3 * rho : rho);
-    s_rho[i] = r; s_rinv[i] = 1.0 / r;
-  }
-  if (st.warm_start && phase != 0) {
-    for (int j = tid; j < n; j += NT) s_x[j] = io.Xs[qp * n + j];
-    for (int i = tid; i < m; i += NT) { s_z[i] = io.Zs[qp * m + i]; s_y[i] = io.Ys[qp * m + i]; }
-  }
-  __syncthreads();
-  DBG(tstamp[3] = wall_clock64();)
-  // refinement is applied only to QPs whose K^-1 left a relative residual above 1e-10 in the
-  // first solve after it was (re)built; the verdict is kept in bit 1 of flag[]
-  const int qflag = phase == 0 ? 1 : io.flag[qp];
-  bool need_refine = (qflag & 2) != 0, check_pending = false;
+  const int tid = threadIdx.x;
+  const long long qp = (PH == 1 && io.order) ? io.order[blockIdx.x] : (int)blockIdx.x;
+  const BL s = bt_layout<NP, NT>(lds, p);
   double *Wk = io.Wk + qp * (long long)(NP * NP);
-  bool notpd = false;
-  if (phase == 0 || (qflag & 1)) {
-    notpd = rebuild_kinv<TR, TC, GC>(n, s, st.sigma, Wk);   // (the solve phase drops the verdict: not covered in-loop)
-    check_pending = true;
-  } else if (qflag & 4) check_pending = true;
-  DBG(tstamp[4] = wall_clock64();)
-  if (phase != 0) load_kinv<NP, NT>(ag, Wk);
-  DBG(tstamp[5] = wall_clock64();)
-  if (phase == 0) {
-    // ---- store the workspace and stop: the solve phase starts from here -------
-    double *Wv = io.Wv + qp * nv_;
-    for (int k = tid; k < p.nnzP; k += NT) Wv[k] = s.Pv[k];
-    for (int k = tid; k < p.nnzA; k += NT) Wv[p.nnzP + k] = s.Av[k];
-    for (int j = tid; j < n; j += NT) { io.Wq[qp * n + j] = s_q[j]; io.Wd[qp * n + j] = s_D[j]; io.Xs[qp * n + j] = 0.0; }
-    for (int i = tid; i < m; i += NT) {
-      io.Wl[qp * m + i] = s_l[i]; io.Wu[qp * m + i] = s_u[i]; io.We[qp * m + i] = s_E[i];
-      io.Wt[qp * m + i] = s.ctype[i]; io.Zs[qp * m + i] = 0.0; io.Ys[qp * m + i] = 0.0;
-    }
+  BDbg dbg;
+  DBG(dbg.tstamp[0] = wall_clock64(); dbg.cyc0 = clock64();)
+  clear_vectors<NT>(s);
+  if (PH == 0) {
+    load_problem<NT, false>(s, p, io, qp);
+    const double cs = ruiz_scale<NT, false>(s, p, st);
+    const double rho = fmin(fmax(st.rho, 1e-6), 1e6);
+    set_rho_vectors<NT>(s, rho);
+    __syncthreads();
+    const bool notpd = rebuild_kinv<TR, TC, GC>(p.n, s, st.sigma, Wk);
     // 4: verdict on refinement still open; 8: K not positive definite (read by the host after the launch)
-    if (tid == 0) { io.Wc[qp] = cs; io.rho_io[qp] = rho; io.flag[qp] = notpd ? 4 | 8 : 4; }
+    store_workspace<NT, false>(s, p, io, qp, cs, rho, notpd ? 4 | 8 : 4);
     return;
   }
-
-  // ---- ADMM loop (osqp.c:354-532) ---------------------------------------------
-  // Uniform scalars (norms, residuals, status) live in LDS (`sc`), not in
-  // registers, and the residual/termination code has ONE call site: a small
-  // stage machine replaces the reference's in-loop / post-loop / approximate
-  // calls of update_info + check_termination (osqp.c:411-437, 537-581).
-  const double alpha = st.alpha, oma = 1.0 - st.alpha, sigma = st.sigma;
-  double *sc = s.red + 13;
-  enum { S_PRI, S_DUA, S_OBJ, S_NPRI_S, S_NDUA_S, S_NZ_S, S_NAX_S, S_NQ_S, S_NATY_S, S_NPX_S,
-         S_NZ, S_NAX, S_NQ, S_NATY, S_NPX, S_STATUS, S_RHO, S_ND, S_LHS, S_NDX, S_QDX, S_COUNT_ };
-  enum { F_NORMS = 1, F_STATUS = 2, F_APPROX = 4 };
-  if (tid == 0) { for (int k = 0; k < S_COUNT_; ++k) sc[k] = 0.0; sc[S_STATUS] = OSQP_UNSOLVED; sc[S_RHO] = rho; }
-  for (int i = tid; i < m; i += NT) s_w[i] = s_rho[i] * s_z[i] - s_y[i];
-  __syncthreads();
-  // rho_updates counts on from the previous solve until an update resets it, like the reference's info
-  // (set to 0 by osqp_setup and by reset_info in every osqp_update_*, src/auxil.c:632-649)
-  int iter = 0, rho_updates = (int)io.info[qp * 8 + 5], stage = 0, probe_until = 0;
-#ifdef OSQP_AMD_BATCH_DEBUG
-  unsigned long long pacc[5] = {0, 0, 0, 0, 0}, pt0 = 0, pt1 = 0;
-#define PSTAMP(slot) do { if (st.profile) { pt1 = wall_clock64(); pacc[slot] += pt1 - pt0; pt0 = pt1; } } while (0)
-#define ABL(bit) (st.ablate & (bit))
-#else
-#define PSTAMP(slot) do { } while (0)
-#define ABL(bit) 0
-#endif
-  bool norms_fresh = false;
-
-  while (stage != 3) {
-    int flags = 0;
-    bool checked = false, adapt_due = false;
-    if (stage == 0) {
-      ++iter;
-      DBG(if (st.profile) pt0 = wall_clock64();)
-      // rhs of the reduced system: b = sigma x - q + A'(rho z - y); w = rho z - y is kept
-      // up to date by the z/y update below.  Four lanes per column.
-      if (!ABL(1)) {
-        const int j = tid >> 2, l = tid & 3;
-        if (j < NP) {
-          const double acc = j < n ? a_col_dot4(s, s_w, j, l) : 0.0;
-          if (l == 0) s_b[j] = j < n ? (sigma * s_x[j] - s_q[j]) + acc : 0.0;
-        }
-        __syncthreads();
-      }
-      PSTAMP(0);
-      if (!ABL(2)) tile_gemv<NP>(ag, s_b, s_xt);
-      PSTAMP(1);
-      // One step of iterative refinement, xt += Kinv (b - K xt), for QPs whose K^-1 needs it.
-      // Whether it does is probed (relative residual of the solve above refine_tol, fill_settings) in the first
-      // four iterations after K^-1 was built; one hit turns refinement on for good (kept per QP
-      // across solves).  refine = 2: always on.
-      const bool probe = !need_refine && (check_pending || iter <= probe_until);
-      if (st.refine && (st.refine == 2 || need_refine || probe)) {
-        for (int i = tid; i < m; i += NT) s_ws[i] = s_rho[i] * a_row_dot(s, s_xt, i);
-        __syncthreads();
-        double rmax = 0.0, bmax = 0.0;
-        for (int j = tid; j < NP; j += NT) {
-          s_tn[j] = j < n ? s_b[j] - (p_row_dot(s, s_xt, j) + sigma * s_xt[j] + a_col_dot(s, s_ws, j)) : 0.0;
-          rmax = fmax(rmax, fabs(s_tn[j])); bmax = fmax(bmax, fabs(s_b[j]));
-        }
-        if (probe) {
-          rmax = b_max<NW>(rmax, s.red); bmax = b_max<NW>(bmax, s.red);
-          need_refine = rmax > st.refine_tol * bmax;
-          if (check_pending) { check_pending = false; probe_until = iter + 3; }
-        }
-        __syncthreads();
-        tile_gemv<NP>(ag, s_tn, s_dx);   // dx is free until the x update below
-        for (int j = tid; j < n; j += NT) s_xt[j] += s_dx[j];
-        __syncthreads();
-      }
-      PSTAMP(2);
-      // z~ = A x~ ; x, z, y updates (auxil.c:185-225, proj.c:4-14); two lanes per row
-      if (!ABL(4))
-      for (int i = tid >> 1; i < m; i += NT / 2) {
-        const double zt = a_row_dot2(s, s_xt, i, tid & 1);
-        if ((tid & 1) == 0) {
-          const double zo = s_z[i], yo = s_y[i], ri = s_rho[i];
-          double v = alpha * zt + oma * zo + s_rinv[i] * yo;
-          v = fmax(v, s_l[i]);
-          const double zn = fmin(v, s_u[i]);
-          const double dy = ri * (alpha * zt + oma * zo - zn);
-          const double yn = yo + dy;
-          s_z[i] = zn; s_dy[i] = dy; s_y[i] = yn;
-          s_w[i] = ri * zn - yn;
-        }
-      }
-      if (!ABL(8))
-      for (int j = tid; j < n; j += NT) {
-        const double xo = s_x[j];
-        const double xn = alpha * s_xt[j] + oma * xo;
-        s_dx[j] = xn - xo; s_x[j] = xn;
-      }
-      __syncthreads();
-      PSTAMP(3);
-      norms_fresh = false;
-      checked = st.check_termination && (iter % st.check_termination == 0);
-      adapt_due = st.adaptive_rho && st.rho_interval && (iter % st.rho_interval == 0);
-      if (checked) flags = F_NORMS | F_STATUS;
-      else if (adapt_due) flags = F_NORMS;
-    } else if (stage == 1) flags = F_STATUS | (norms_fresh ? 0 : F_NORMS);
-    else flags = F_STATUS | F_APPROX;
-
-    bool term = false;
-    if (flags & F_NORMS) {
-      // ---- update_info: residuals and norms (auxil.c:227-318), plus the cheap halves of both
-      // infeasibility tests (auxil.c:361-512), in two passes and ONE workgroup reduction ----
-      double mx[16], sm[3];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) mx[k] = 0.0;
-      sm[0] = sm[1] = sm[2] = 0.0;
-      for (int i = tid >> 1; i < m; i += NT / 2) {          // rows: two lanes each
-        const double ax = a_row_dot2(s, s_x, i, tid & 1);
-        if ((tid & 1) == 0) {
-          const double zi = s_z[i], pr = ax + (-1.0) * zi;
-          const double ei = unscaled ? 1.0 / s_E[i] : 1.0;
-          mx[0] = fmax(mx[0], fabs(ei * pr)); mx[1] = fmax(mx[1], fabs(pr));
-          mx[2] = fmax(mx[2], fabs(ei * zi)); mx[3] = fmax(mx[3], fabs(zi));
-          mx[4] = fmax(mx[4], fabs(ei * ax)); mx[5] = fmax(mx[5], fabs(ax));
-          // delta_y projected on the polar of the recession cone (is_primal_infeasible)
-          double dy = s_dy[i];
-          const double li = s_l[i], ui = s_u[i];
-          if (ui > BINF) { if (li < -BINF) dy = 0.0; else dy = fmin(dy, 0.0); }
-          else if (li < -BINF) dy = fmax(dy, 0.0);
-          s_ws[i] = dy;
-          mx[14] = fmax(mx[14], fabs(unscaled ? s_E[i] * dy : dy));
-          sm[1] += ui * fmax(dy, 0.0) + li * fmin(dy, 0.0);
-        }
-      }
-      {                                                     // columns: four lanes each
-        const int j = tid >> 2, l = tid & 3;
-        if (j < n) {
-          const double px = p_row_dot4(s, s_x, j, l);
-          const double aty = a_col_dot4(s, s_y, j, l);
-          if (l == 0) {
-            const double qj = s_q[j], xj = s_x[j], dxj = s_dx[j];
-            double dr = qj + px;
-            if (m > 0) dr = dr + aty;
-            const double di = unscaled ? 1.0 / s_D[j] : 1.0;
-            mx[6] = fabs(di * dr); mx[7] = fabs(dr);
-            mx[8] = fabs(di * qj); mx[9] = fabs(qj);
-            mx[10] = fabs(di * aty); mx[11] = fabs(aty);
-            mx[12] = fabs(di * px); mx[13] = fabs(px);
-            sm[0] = xj * (0.5 * px + qj);
-            mx[15] = fabs(unscaled ? s_D[j] * dxj : dxj);      // is_dual_infeasible: |delta_x|, q'delta_x
-            sm[2] = qj * dxj;
-          }
-        }
-      }
-      b_reduce_many<NW, 16, 3>(mx, sm, s.gp);
-      if (tid == 0) {
-        const double *g = s.gp + NW * 19;                 // combined values
-        sc[S_PRI] = m == 0 ? 0.0 : (unscaled ? g[0] : g[1]);
-        sc[S_NPRI_S] = g[1]; sc[S_NZ] = unscaled ? g[2] : g[3]; sc[S_NZ_S] = g[3];
-        sc[S_NAX] = unscaled ? g[4] : g[5]; sc[S_NAX_S] = g[5];
-        const double f = unscaled ? cinv : 1.0;
-        sc[S_DUA] = unscaled ? g[6] * cinv : g[7]; sc[S_NDUA_S] = g[7];
-        sc[S_NQ] = (unscaled ? g[8] : g[9]) * f; sc[S_NQ_S] = g[9];
-        sc[S_NATY] = (unscaled ? g[10] : g[11]) * f; sc[S_NATY_S] = g[11];
-        sc[S_NPX] = (unscaled ? g[12] : g[13]) * f; sc[S_NPX_S] = g[13];
-        sc[S_OBJ] = g[16] * (st.scaling ? cinv : 1.0);
-        sc[S_ND] = g[14]; sc[S_LHS] = g[17]; sc[S_NDX] = g[15]; sc[S_QDX] = g[18];
-      }
-      __syncthreads();
-      norms_fresh = true;
-    }
-    if (flags & F_STATUS) {
-      // ---- check_termination (auxil.c:681-786) ----
-      const bool approximate = flags & F_APPROX;
-      const double pri_res = sc[S_PRI], dua_res = sc[S_DUA];
-      int newstatus = 0;      // 0 = keep going
-      double newobj = 0.0;
-      if (pri_res > 1e30 || dua_res > 1e30) { newstatus = OSQP_NON_CVX; newobj = OSQP_NAN; }
-      else {
-        double ea = st.eps_abs, er = st.eps_rel, epi = st.eps_pinf, edi = st.eps_dinf;
-        if (approximate) { ea *= 10; er *= 10; epi *= 10; edi *= 10; }
-        bool prim_ok = false, dual_ok = false, pinf = false, dinf = false;
-        if (m == 0) prim_ok = true;
-        else if (pri_res < ea + er * fmax(sc[S_NZ], sc[S_NAX])) prim_ok = true;
-        else {
-          // is_primal_infeasible (auxil.c:361-424); the projected delta_y is in ws
-          const double nd = sc[S_ND], lhs = sc[S_LHS];
-          if (nd > 1e-30 && lhs < epi * nd) {
-            double mxv = 0;
-            for (int j = tid; j < n; j += NT) {
-              double v = a_col_dot(s, s_ws, j);
-              if (unscaled) v = v / s_D[j];
-              mxv = fmax(mxv, fabs(v));
-            }
-            mxv = b_max<NW>(mxv, s.red);
-            pinf = mxv < epi * nd;
-          }
-        }
-        if (dua_res < ea + er * fmax(fmax(sc[S_NQ], sc[S_NATY]), sc[S_NPX])) dual_ok = true;
-        else {
-          // is_dual_infeasible (auxil.c:426-512)
-          const double ndx = sc[S_NDX], qdx = sc[S_QDX];
-          const double csc_ = unscaled ? cs : 1.0;
-          if (ndx > 1e-30 && qdx < csc_ * edi * ndx) {
-            double mxv = 0;
-            for (int j = tid; j < n; j += NT) {
-              double v = p_row_dot(s, s_dx, j);
-              if (unscaled) v = v / s_D[j];
-              mxv = fmax(mxv, fabs(v));
-            }
-            mxv = b_max<NW>(mxv, s.red);
-            if (mxv < csc_ * edi * ndx) {
-              double viol = 0;
-              for (int i = tid; i < m; i += NT) {
-                double v = a_row_dot(s, s_dx, i);
-                if (unscaled) v = v / s_E[i];
-                if ((s_u[i] < BINF && v > edi * ndx) || (s_l[i] > -BINF && v < -edi * ndx)) viol += 1.0;
-              }
-              viol = b_sum<NW>(viol, s.red);
-              dinf = viol == 0.0;
-            }
-          }
-        }
-        if (prim_ok && dual_ok) newstatus = approximate ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED;
-        else if (pinf) { newstatus = approximate ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE; newobj = OSQP_INFTY; }
-        else if (dinf) { newstatus = approximate ? OSQP_DUAL_INFEASIBLE_INACCURATE : OSQP_DUAL_INFEASIBLE; newobj = -OSQP_INFTY; }
-      }
-      __syncthreads();
-      if (newstatus != 0) {
-        term = true;
-        if (tid == 0) { sc[S_STATUS] = newstatus; if (newstatus != OSQP_SOLVED && newstatus != OSQP_SOLVED_INACCURATE) sc[S_OBJ] = newobj; }
-      }
-      __syncthreads();
-    }
-    if (stage == 0) {
-      if (checked && term) { stage = 3; continue; }
-      if (adapt_due) {     // adapt_rho (auxil.c:13-74)
-        const double pr = (m ? sc[S_NPRI_S] : 0.0) / (fmax(sc[S_NZ_S], sc[S_NAX_S]) + 1e-30);
-        const double du = sc[S_NDUA_S] / (fmax(fmax(sc[S_NQ_S], sc[S_NATY_S]), sc[S_NPX_S]) + 1e-30);
-        const double rn = fmin(fmax(rho * sqrt(pr / du), 1e-6), 1e6);
-        if (rn > rho * st.adapt_tol || rn < rho / st.adapt_tol) {
-          rho = rn; rho_updates++;
-          for (int i = tid; i < m; i += NT) {
-            const int t = s.ctype[i];
-            if (t == 0) { s_rho[i] = rho; s_rinv[i] = 1.0 / rho; }
-            else if (t == 1) { s_rho[i] = 1e3 * rho; s_rinv[i] = 1.0 / s_rho[i]; }
-            s_w[i] = s_rho[i] * s_z[i] - s_y[i];
-          }
-          __syncthreads();
-          rebuild_kinv<TR, TC, GC>(n, s, sigma, Wk);
-          load_kinv<NP, NT>(ag, Wk);
-          check_pending = true;
-        }
-      }
-      if (iter >= st.max_iter) stage = checked ? 2 : 1;
-    } else if (stage == 1) stage = term ? 3 : 2;
-    else {
-      if (!term && tid == 0) sc[S_STATUS] = OSQP_MAX_ITER_REACHED;
-      __syncthreads();
-      stage = 3;
-    }
-  }
-  DBG(tstamp[6] = wall_clock64();)
-  const int status = (int)sc[S_STATUS];
-  const double pri_res = sc[S_PRI], dua_res = sc[S_DUA], obj = sc[S_OBJ];
-  double rho_est;
-  {
-    const double pr = (m ? sc[S_NPRI_S] : 0.0) / (fmax(sc[S_NZ_S], sc[S_NAX_S]) + 1e-30);
-    const double du = sc[S_NDUA_S] / (fmax(fmax(sc[S_NQ_S], sc[S_NATY_S]), sc[S_NPX_S]) + 1e-30);
-    rho_est = fmin(fmax(rho * sqrt(pr / du), 1e-6), 1e6);
-  }
-
-  // ---- store_solution (auxil.c:524-562) ---------------------------------------
-  const bool has_sol = !(status == OSQP_PRIMAL_INFEASIBLE || status == OSQP_PRIMAL_INFEASIBLE_INACCURATE ||
-                         status == OSQP_DUAL_INFEASIBLE || status == OSQP_DUAL_INFEASIBLE_INACCURATE ||
-                         status == OSQP_NON_CVX);
-  __syncthreads();
-  if (has_sol) {
-    for (int j = tid; j < n; j += NT) {
-      io.Xo[qp * n + j] = st.scaling ? s_x[j] * s_D[j] : s_x[j];
-      io.Xs[qp * n + j] = s_x[j];
-    }
-    for (int i = tid; i < m; i += NT) {
-      io.Yo[qp * m + i] = st.scaling ? (s_y[i] * s_E[i]) * cinv : s_y[i];
-      io.Ys[qp * m + i] = s_y[i]; io.Zs[qp * m + i] = s_z[i];
-    }
-  } else {
-    for (int j = tid; j < n; j += NT) { io.Xo[qp * n + j] = OSQP_NAN; io.Xs[qp * n + j] = 0.0; }
-    for (int i = tid; i < m; i += NT) { io.Yo[qp * m + i] = OSQP_NAN; io.Ys[qp * m + i] = 0.0; io.Zs[qp * m + i] = 0.0; }
-    if (status == OSQP_PRIMAL_INFEASIBLE || status == OSQP_PRIMAL_INFEASIBLE_INACCURATE) {
-      double mx = 0;
-      for (int i = tid; i < m; i += NT) { s_ws[i] = unscaled ? s_ws[i] * s_E[i] : s_ws[i]; mx = fmax(mx, fabs(s_ws[i])); }
-      mx = b_max<NW>(mx, s.red);
-      for (int i = tid; i < m; i += NT) io.DYo[qp * m + i] = s_ws[i] * (1.0 / mx);
-    }
-    if (status == OSQP_DUAL_INFEASIBLE || status == OSQP_DUAL_INFEASIBLE_INACCURATE) {
-      double mx = 0;
-      for (int j = tid; j < n; j += NT) { s_tn[j] = unscaled ? s_dx[j] * s_D[j] : s_dx[j]; mx = fmax(mx, fabs(s_tn[j])); }
-      mx = b_max<NW>(mx, s.red);
-      for (int j = tid; j < n; j += NT) io.DXo[qp * n + j] = s_tn[j] * (1.0 / mx);
-    }
-  }
+  TiledK<TR, TC, GC> eng;
+  eng.Wk = Wk;
+  BA a;
+  a.cs = load_workspace<NT, false>(s, p, io, qp);
+  DBG(dbg.tstamp[1] = dbg.tstamp[2] = wall_clock64();)
+  a.rho = fmin(fmax(io.rho_io[qp], 1e-6), 1e6);
+  init_iterates<NT>(s, p, io, qp, a.rho, st.warm_start);
+  DBG(dbg.tstamp[3] = wall_clock64();)
+  // refinement is applied only to QPs whose K^-1 left a relative residual above refine_tol in the
+  // first solves after it was (re)built; the verdict is kept in bit 1 of flag[]
+  const int qflag = io.flag[qp];
+  a.need_refine = (qflag & 2) != 0;
+  a.check_pending = (qflag & 5) != 0;
+  if (qflag & 1) rebuild_kinv<TR, TC, GC>(p.n, s, st.sigma, Wk);   // (the verdict on K is dropped: not covered in-loop)
+  DBG(dbg.tstamp[4] = wall_clock64();)
+  load_kinv<NP, NT>(eng.ag, Wk);
+  DBG(dbg.tstamp[5] = wall_clock64();)
+  admm_loop<NT, true>(s, p, st, io, qp, a, 0, eng, dbg);
+  DBG(dbg.tstamp[6] = wall_clock64();)
+  store_solution<NT>(s, p, st, io, qp, a, a.check_pending ? 4 : (a.need_refine ? 2 : 0));
   DBG(if (st.profile && tid == 0) {
-    tstamp[7] = wall_clock64();
-    for (int k = 0; k < 8; ++k) io.DXo[qp * n + k] = (double)(tstamp[k] - tstamp[0]);
-    for (int k = 0; k < 4; ++k) io.DXo[qp * n + 8 + k] = (double)pacc[k];
-    io.DXo[qp * n + 12] = (double)(clock64() - cyc0);
-    io.DXo[qp * n + 13] = (double)tstamp[0]; io.DXo[qp * n + 14] = (double)tstamp[7];
+    const int n = p.n;
+    dbg.tstamp[7] = wall_clock64();
+    for (int k = 0; k < 8; ++k) io.DXo[qp * n + k] = (double)(dbg.tstamp[k] - dbg.tstamp[0]);
+    for (int k = 0; k < 4; ++k) io.DXo[qp * n + 8 + k] = (double)dbg.pacc[k];
+    io.DXo[qp * n + 12] = (double)(clock64() - dbg.cyc0);
+    io.DXo[qp * n + 13] = (double)dbg.tstamp[0]; io.DXo[qp * n + 14] = (double)dbg.tstamp[7];
   })
-  if (tid == 0) {
-    io.flag[qp] = check_pending ? 4 : (need_refine ? 2 : 0);
-    double *inf = io.info + qp * 8;
-    inf[0] = iter; inf[1] = status; inf[2] = obj; inf[3] = pri_res; inf[4] = dua_res;
-    inf[5] = rho_updates; inf[6] = rho_est; inf[7] = rho;
-    if (io.rho_io) io.rho_io[qp] = rho;
-  }
+  if (tid == 0 && io.rho_io) io.rho_io[qp] = a.rho;
 }
 
 // osqp_update_lin_cost / osqp_update_bounds for every QP of the batch
@@ -916,10 +558,7 @@ __global__ void __launch_bounds__(256) k_batch_update(int n, int m, BIO io, cons
     if (L) io.Wl[qp * m + i] = L[qp * m + i] * e;
     if (U) io.Wu[qp * m + i] = U[qp * m + i] * e;
     if (L || U) {
-      const double l = io.Wl[qp * m + i], u = io.Wu[qp * m + i];
-      int t = 0;
-      if (l < -BINF && u > BINF) t = -1;
-      else if (u - l < rho_tol) t = 1;
+      const int t = row_class(io.Wl[qp * m + i], io.Wu[qp * m + i], rho_tol);
       if (t != io.Wt[qp * m + i]) { io.Wt[qp * m + i] = t; changed = 1; }
     }
   }
@@ -991,7 +630,6 @@ struct osqp_amd_batch {
 };
 
 static void batch_launch(osqp_amd_batch *b, int phase);
-static void batch_set_lds(osqp_amd_batch *b);
 
 template <typename Tp>
 static int balloc(osqp_amd_batch *b, Tp **p, size_t cnt) {
@@ -1040,7 +678,7 @@ static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
 }
 
 static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, const std::vector<int> &Pi,
-                             const std::vector<int> &Ap, const std::vector<int> &Ai);
+                             const std::vector<int> &Rp, const std::vector<int> &Rc, const std::vector<int> &Rk);
 static int bs_setup_launch(osqp_amd_batch *b);
 
 static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const csc *P, const csc *A,
@@ -1187,15 +825,11 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
   if (rc || hipStreamSynchronize(b->stream) != hipSuccess) { osqp_amd_batch_cleanup(b); return OSQP_LINSYS_SOLVER_INIT_ERROR; }
 
   if (streamed) {
-    const int krc = bs_build_kpattern(b, Pp, Pi, Ap, Ai);
+    const int krc = bs_build_kpattern(b, Pp, Pi, Rp, Rj, Rk);
     if (krc) { osqp_amd_batch_cleanup(b); return krc; }
     b->lds_bytes = bs_lds_bytes(b->NPs, m);
   } else {
-    const int NP = 16 * b->tile;
-    b->lds_bytes = sizeof(double) * ((size_t)b->nnzP + b->nnzA + 1 + 7 * NP + 11 * (size_t)m + 4 * NP + 64 + 256) +
-                   sizeof(int) * ((size_t)m + 4 + 3 * ((size_t)n + 1) + 2 * (size_t)b->nnzP + 2 * (size_t)Fp[n] +
-                                  4 * (size_t)b->nnzA + (size_t)m + 1);
-    b->lds_bytes = (b->lds_bytes + 15) & ~(size_t)15;
+    b->lds_bytes = bt_lds_bytes(pt, 16 * b->tile);
     if (b->lds_bytes > 160 * 1024) {
       fprintf(stderr, "osqp_amd batch: problem needs %zu B of LDS per QP (> 160 KiB)\n", b->lds_bytes);
       osqp_amd_batch_cleanup(b);
@@ -1249,7 +883,7 @@ extern "C" c_int osqp_amd_batch_setup_engine(osqp_amd_batch **out, c_int engine,
 // triples of its A'A term in ascending row order; each row of K lists its stored entries (i, j) and (j, i).  Both
 // halves of K sum the same triples in the same order, so K is symmetric to the bit.
 static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, const std::vector<int> &Pi,
-                             const std::vector<int> &Ap, const std::vector<int> &Ai) {
+                             const std::vector<int> &Rp, const std::vector<int> &Rc, const std::vector<int> &Rk) {
   const int n = b->n, m = b->m;
   std::vector<int> eid((size_t)n * n, -1);          // (i, j), i <= j -> entry
   std::vector<int> ei, ej;
@@ -1261,13 +895,8 @@ static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, cons
   for (int j = 0; j < n; j++) entry(j, j);
   for (int j = 0; j < n; j++)
     for (int k = Pp[j]; k < Pp[j + 1]; k++) entry(Pi[k], j);
-  // rows of A (slots in column order) -> triples, counted first then filled in ascending row order
-  std::vector<int> Rp(m + 1, 0);
-  for (int k = 0; k < b->nnzA; k++) Rp[Ai[k] + 1]++;
-  for (int i = 0; i < m; i++) Rp[i + 1] += Rp[i];
-  std::vector<int> Rk(b->nnzA), Rc(b->nnzA), nx(Rp.begin(), Rp.end() - 1);
-  for (int j = 0; j < n; j++)
-    for (int k = Ap[j]; k < Ap[j + 1]; k++) { const int d = nx[Ai[k]]++; Rk[d] = k; Rc[d] = j; }
+  // rows of A (CSR view: column Rc and CSC slot Rk, slots in column order) -> triples, counted first then
+  // filled in ascending row order
   size_t ntri = 0;
   for (int r = 0; r < m; r++) {
     const size_t c = (size_t)(Rp[r + 1] - Rp[r]);
@@ -1364,21 +993,19 @@ static int bs_solve(osqp_amd_batch *b) {
   return 0;
 }
 
+// the one instantiation of k_batch_solve for (tile, phase)
+static const void *batch_kernel(int tile, int phase) {
+  if (tile == 8) return phase ? reinterpret_cast<const void *>(&k_batch_solve<8, 4, 32, 1>) : reinterpret_cast<const void *>(&k_batch_solve<8, 4, 32, 0>);
+  return phase ? reinterpret_cast<const void *>(&k_batch_solve<4, 2, 32, 1>) : reinterpret_cast<const void *>(&k_batch_solve<4, 2, 32, 0>);
+}
 static void batch_launch(osqp_amd_batch *b, int phase) {
-  const dim3 g((unsigned)b->B);
   // The dynamic-LDS limit is a property of the kernel function, not of this batch: a later batch
   // of the same tile may have set it to its own, smaller size.  Set it for this one every launch.
-  if (b->lds_bytes > 64 * 1024) batch_set_lds(b);
-#define BL_(TR, TC, GC, PH) hipLaunchKernelGGL((k_batch_solve<TR, TC, GC, PH>), g, dim3(16 * GC), b->lds_bytes, b->stream, b->pat, b->st, b->io)
-  if (b->tile == 8) { if (phase == 0) BL_(8, 4, 32, 0); else BL_(8, 4, 32, 1); }
-  else              { if (phase == 0) BL_(4, 2, 32, 0); else BL_(4, 2, 32, 1); }
-#undef BL_
-}
-static void batch_set_lds(osqp_amd_batch *b) {
-#define SA_(TR, TC, GC, PH) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch_solve<TR, TC, GC, PH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes)
-  if (b->tile == 8) { SA_(8, 4, 32, 0); SA_(8, 4, 32, 1); }
-  else              { SA_(4, 2, 32, 0); SA_(4, 2, 32, 1); }
-#undef SA_
+  const void *fn = batch_kernel(b->tile, phase);
+  if (b->lds_bytes > 64 * 1024)
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes);
+  void *args[] = {&b->pat, &b->st, &b->io};
+  (void)hipLaunchKernel(fn, dim3((unsigned)b->B), dim3(BT), args, b->lds_bytes, b->stream);
 }
 
 extern "C" void osqp_amd_batch_cleanup(osqp_amd_batch *b) {
