@@ -50,6 +50,29 @@ c_int osqp_amd_batch_shape(osqp_amd_batch *b, c_int *engine, c_int *NP);
 c_int osqp_amd_batch_rounds(osqp_amd_batch *b, c_int *rounds, c_int *refined);
 /* osqp_update_lin_cost / osqp_update_bounds for every QP (NULL = keep). */
 c_int osqp_amd_batch_update(osqp_amd_batch *b, const c_float *Q, const c_float *L, const c_float *U);
+/* osqp_update_P / osqp_update_A / osqp_update_P_A (src/osqp.c:1012-1279) for every QP: new values, same pattern.
+ * Px / Ax NULL = keep.  Px_idx / Ax_idx NULL: all nnzP / nnzA values in CSC order of triu(P) / A; otherwise P_n /
+ * A_n values for the listed slots (one index list for the batch: it belongs to the pattern).  *_per_member = 0: one
+ * value array [k] for every member; 1: [batch][k] row-major.  A handle set up with shared values that receives
+ * per-member values switches to per-member storage (one allocation, kept); a shared update of a per-member handle
+ * writes every member.  Per member as the reference: the equilibration is recomputed from scratch on the new raw
+ * data (q, l, u as last given) and K is re-formed and re-inverted with the member's current rho (the adapted value of
+ * the last solve) and its current row classes; the scaled iterates stay as they are; rho_updates is reset.
+ * Returns, before anything is written: 1 when P_n > nnzP, 2 when A_n > nnzA (the reference's codes),
+ * OSQP_DATA_VALIDATION_ERROR for an index outside [0, nnz).  OSQP_NONCVX_ERROR when some member's new K has a
+ * non-positive pivot (stderr names the first such member): the values are written, the handle stays alive,
+ * osqp_amd_batch_solve returns OSQP_NONCVX_ERROR until a later osqp_amd_batch_update_matrices succeeds. */
+c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
+                                     const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
+                                     const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member);
+/* osqp_update_rho (src/osqp.c:1281-1332) for every QP: rho points at one value (per_member = 0) or at [batch].  Any
+ * value <= 0: returns 1 and changes nothing.  Each member's rho becomes min(max(rho, 1e-6), 1e6) and its K^-1 is
+ * rebuilt at the start of the next solve; rho_updates is not reset. */
+c_int osqp_amd_batch_update_rho(osqp_amd_batch *b, const c_float *rho, c_int per_member);
+/* osqp_warm_start / _x / _y (src/osqp.c:942-1010) for every QP: X [batch][n], Y [batch][m], unscaled, either may
+ * be NULL.  x = D^-1 x and z = A x (when X is given), y = c E^-1 y (when Y is given), on the device; turns
+ * settings->warm_start on for the handle, as the reference does. */
+c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, const c_float *Y);
 /* osqp_solve for every QP; iterates persist on the device between calls
  * (warm start, settings->warm_start). */
 c_int osqp_amd_batch_solve(osqp_amd_batch *b);

@@ -24,6 +24,13 @@ def _bind(L):
                                        abi.c_float_p, C.POINTER(abi.OSQPSettings), abi.c_int]
     L.osqp_amd_batch_update.restype = abi.c_int
     L.osqp_amd_batch_update.argtypes = [H, abi.c_float_p, abi.c_float_p, abi.c_float_p]
+    L.osqp_amd_batch_update_matrices.restype = abi.c_int
+    L.osqp_amd_batch_update_matrices.argtypes = [H, abi.c_float_p, abi.c_int_p, abi.c_int, abi.c_int,
+                                                 abi.c_float_p, abi.c_int_p, abi.c_int, abi.c_int]
+    L.osqp_amd_batch_update_rho.restype = abi.c_int
+    L.osqp_amd_batch_update_rho.argtypes = [H, abi.c_float_p, abi.c_int]
+    L.osqp_amd_batch_warm_start.restype = abi.c_int
+    L.osqp_amd_batch_warm_start.argtypes = [H, abi.c_float_p, abi.c_float_p]
     L.osqp_amd_batch_solve.restype = abi.c_int
     L.osqp_amd_batch_solve.argtypes = [H]
     L.osqp_amd_batch_get.restype = abi.c_int
@@ -44,6 +51,38 @@ def _bind(L):
 
 def _p(a):
     return C.cast(None, abi.c_float_p) if a is None else abi.fptr(a)
+
+
+def check_matrix_update(B, nnzP, nnzA, Px=None, Px_idx=None, Ax=None, Ax_idx=None):
+    """Shape and index checks of BatchOSQP.update_matrices, as interface.py: update makes them for one QP (the C
+    entry point reads what the shapes promise).  A 1-D value array is shared by the batch, a 2-D one is [B, k];
+    without an index list k is the matrix's nnz, with one it is the list's length.  Returns the arrays as the C
+    side takes them: (Px, Px_idx, P per-member flag, Ax, Ax_idx, A per-member flag)."""
+    out = []
+    for name, V, I, nnz in (("P", Px, Px_idx, nnzP), ("A", Ax, Ax_idx, nnzA)):
+        if V is None:
+            if I is not None:
+                raise ValueError("%sx_idx given without %sx" % (name, name))
+            out += [None, None, 0]
+            continue
+        V = abi.as_f64(V)
+        if V.ndim not in (1, 2):
+            raise ValueError("%sx must be [k] (shared) or [B, k] (per member)" % name)
+        if V.ndim == 2 and V.shape[0] != B:
+            raise ValueError("%sx has %d rows, the batch has %d members" % (name, V.shape[0], B))
+        k = V.shape[-1]
+        if I is None:
+            if k != nnz:
+                raise ValueError("%sx has %d values per member, %s has %d non-zeros (pass %sx_idx for a partial update)"
+                                 % (name, k, name, nnz, name))
+        else:
+            I = abi.as_i64(I)
+            if I.ndim != 1 or I.size != k:
+                raise ValueError("%sx_idx must be a vector as long as a member's %sx" % (name, name))
+            if I.size and (I.min() < 0 or I.max() >= nnz):
+                raise ValueError("%sx_idx out of range [0, %d)" % (name, nnz))
+        out += [V, I, int(V.ndim == 2)]
+    return tuple(out)
 
 
 class BatchOSQP:
@@ -188,6 +227,55 @@ class BatchOSQP:
         if self._many is not None:
             return self._many_update(Q, L, U)
         return int(self._lib.osqp_amd_batch_update(self._h, _p(Q), _p(L), _p(U)))
+
+    def _many_each(self, call):
+        # as _many_update: the first failing member's code comes back
+        self.last_update_failed = None
+        for b, s in enumerate(self._many):
+            rc = call(b, s)
+            if rc:
+                self.last_update_failed = b
+                return rc
+        return 0
+
+    def update_matrices(self, Px=None, Px_idx=None, Ax=None, Ax_idx=None):
+        """osqp_update_P / _A / _P_A for every QP: new values on the pattern of setup.  Px / Ax: [k] (shared by the
+        batch) or [B, k] (per member); k = nnz of triu(P) / A in CSC order, or the length of Px_idx / Ax_idx (slots, one
+        list for the batch).  Scaling is recomputed; rho, row classes and iterates stay.  Returns the C return code
+        (5: some member's new K is not positive definite; solve then refuses until an update succeeds)."""
+        Px, Px_idx, pper, Ax, Ax_idx, aper = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
+        if Px is None and Ax is None:
+            return 0
+        if self._many is not None:
+            return self._many_each(lambda b, s: s.update(Px=None if Px is None else (Px[b] if pper else Px), Px_idx=Px_idx,
+                                                         Ax=None if Ax is None else (Ax[b] if aper else Ax), Ax_idx=Ax_idx))
+        ip = lambda a: C.cast(None, abi.c_int_p) if a is None else abi.iptr(a)
+        return int(self._lib.osqp_amd_batch_update_matrices(
+            self._h, _p(Px), ip(Px_idx), 0 if Px is None else Px.shape[-1], pper,
+            _p(Ax), ip(Ax_idx), 0 if Ax is None else Ax.shape[-1], aper))
+
+    def update_rho(self, rho):
+        """osqp_update_rho for every QP: a scalar, or [B] values.  Returns 1 (nothing changed) when a value is <= 0."""
+        rho = np.asarray(rho, dtype=np.float64)
+        if rho.shape not in ((), (self.B,)):
+            raise ValueError("rho must be a scalar or [B]")
+        per = int(rho.ndim == 1)
+        rho = np.ascontiguousarray(rho.reshape(-1))
+        if self._many is not None:
+            if np.any(rho <= 0):
+                return 1
+            return self._many_each(lambda b, s: s.update_rho(rho[b if per else 0]))
+        return int(self._lib.osqp_amd_batch_update_rho(self._h, abi.fptr(rho), per))
+
+    def warm_start(self, X=None, Y=None):
+        """osqp_warm_start (_x, _y) for every QP: X [B, n], Y [B, m], unscaled; turns the warm_start setting on."""
+        X = None if X is None else abi.as_f64(X)
+        Y = None if Y is None else abi.as_f64(Y)
+        if (X is not None and X.shape != (self.B, self.n)) or (Y is not None and Y.shape != (self.B, self.m)):
+            raise ValueError("warm start arrays must be X [B, n], Y [B, m]")
+        if self._many is not None:
+            return self._many_each(lambda b, s: s.warm_start(x=None if X is None else X[b], y=None if Y is None else Y[b]))
+        return int(self._lib.osqp_amd_batch_warm_start(self._h, _p(X), _p(Y if self.m else None)))
 
     def solve(self, fetch=True):
         if self._many is not None:

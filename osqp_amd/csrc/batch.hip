@@ -480,7 +480,9 @@ struct TiledK {
 };
 
 // PH = 0: setup phase (scale, classify, build K^-1, store the workspace);
-// PH = 1: solve phase (load the workspace, ADMM loop, store the solution).
+// PH = 1: solve phase (load the workspace, ADMM loop, store the solution);
+// PH = 2: matrix-update phase (osqp_update_P_A, osqp.c:1171-1279): the setup phase on the current raw data with
+//         the member's row classes, rho and iterates kept.
 #ifndef BATCH_WAVES_PER_SIMD
 #define BATCH_WAVES_PER_SIMD 2   // 4 (two workgroups per CU, <= 128 registers) was measured slower: spills lengthen the slowest QP
 #endif
@@ -506,6 +508,18 @@ __global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k
     const bool notpd = rebuild_kinv<TR, TC, GC>(p.n, s, st.sigma, Wk);
     // 4: verdict on refinement still open; 8: K not positive definite (read by the host after the launch)
     store_workspace<NT, false>(s, p, io, qp, cs, rho, notpd ? 4 | 8 : 4);
+    return;
+  }
+  if (PH == 2) {
+    load_problem<NT, false>(s, p, io, qp);
+    load_classes<NT>(s, p, io, qp);
+    const double cs = ruiz_scale<NT, false, false>(s, p, st);
+    const double rho = fmin(fmax(io.rho_io[qp], 1e-6), 1e6);
+    __syncthreads();
+    set_rho_vectors<NT>(s, rho);
+    __syncthreads();
+    const bool notpd = rebuild_kinv<TR, TC, GC>(p.n, s, st.sigma, Wk);
+    store_workspace<NT, false, false>(s, p, io, qp, cs, rho, notpd ? 4 | 8 : 4);
     return;
   }
   TiledK<TR, TC, GC> eng;
@@ -567,6 +581,52 @@ __global__ void __launch_bounds__(256) k_batch_update(int n, int m, BIO io, cons
   if (threadIdx.x == 0) io.info[qp * 8 + 5] = 0.0;      // reset_info: rho_updates (src/auxil.c:647)
 }
 
+// New matrix values into the raw value array of the batch: slot idx[k] (k itself when idx is null) of every member
+// receives src[k] (shared values) or src[member][k].  dstride = 0: the raw array is shared and so is src.  One
+// thread per (member, k), k fastest: the reads are coalesced, and so are the writes of a full update.
+__global__ void __launch_bounds__(256) k_batch_scatter(double *dst, long long dstride, const double *src, long long sstride,
+                                                       const int *idx, long long cnt, long long members) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= cnt * members) return;
+  const long long b = t / cnt, k = t - b * cnt;
+  dst[b * dstride + (idx ? idx[k] : k)] = src[b * sstride + k];
+}
+
+// osqp_update_rho for every QP (osqp.c:1281-1332): the clipped value, and a rebuild of K^-1 at the start of the next
+// solve, after which the refinement verdict is re-taken (as after a class change in k_batch_update)
+__global__ void __launch_bounds__(256) k_batch_update_rho(long long B, BIO io, const double *rho, int per_member) {
+  const long long qp = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (qp >= B) return;
+  io.rho_io[qp] = fmin(fmax(rho[per_member ? qp : 0], 1e-6), 1e6);
+  io.flag[qp] = 1;
+}
+
+// osqp_warm_start / _x / _y for every QP (osqp.c:942-1010): x = D^-1 x, z = A x with the scaled A, y = c E^-1 y.
+// One workgroup per QP; the scaled x is handed from its writers to the row sums through LDS.
+#define BW_MAX_N 1024      // largest n of either engine
+__global__ void __launch_bounds__(256) k_batch_warm_start(BPattern p, BIO io, const double *X, const double *Y) {
+  __shared__ double xs[BW_MAX_N];
+  const long long qp = blockIdx.x;
+  const int n = p.n, m = p.m;
+  if (X) {
+    for (int j = threadIdx.x; j < n; j += 256) {
+      const double v = (1.0 / io.Wd[qp * n + j]) * X[qp * n + j];
+      xs[j] = v; io.Xs[qp * n + j] = v;
+    }
+    __syncthreads();
+    const double *Av = io.Wv + qp * ((long long)p.nnzP + p.nnzA) + p.nnzP;
+    for (int i = threadIdx.x; i < m; i += 256) {
+      double acc = 0.0;
+      for (int k = p.Rp[i]; k < p.Rp[i + 1]; ++k) acc += Av[p.Rk[k]] * xs[p.Rj[k]];
+      io.Zs[qp * m + i] = acc;
+    }
+  }
+  if (Y) {
+    const double c = io.Wc[qp];
+    for (int i = threadIdx.x; i < m; i += 256) io.Ys[qp * m + i] = ((1.0 / io.We[qp * m + i]) * Y[qp * m + i]) * c;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -624,7 +684,12 @@ struct osqp_amd_batch {
   size_t lds_bytes = 0;
   int solves = 0;
   std::vector<double> h_info;
-  double *dQ = nullptr, *dL = nullptr, *dU = nullptr;   // staging for updates
+  double *dQ = nullptr, *dL = nullptr, *dU = nullptr;   // the raw q, l, u (io.Q, io.L, io.U), written by updates
+  double *dPx = nullptr, *dAx = nullptr;                // the raw matrix values (io.Px, io.Ax), written by matrix updates
+  double *d_vals = nullptr, *d_rho = nullptr;           // staging of update_matrices / update_rho / warm_start
+  int *d_idx = nullptr;
+  size_t vals_cap = 0, idx_cap = 0;
+  bool noncvx = false;      // the last matrix update left some member's K indefinite: solve refuses
   int *d_order = nullptr;   // dispatch order for the next solve (k_batch_order)
   int lpt = 1;
 };
@@ -679,7 +744,7 @@ static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
 
 static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, const std::vector<int> &Pi,
                              const std::vector<int> &Rp, const std::vector<int> &Rc, const std::vector<int> &Rk);
-static int bs_setup_launch(osqp_amd_batch *b);
+static int bs_setup_launch(osqp_amd_batch *b, bool update);
 
 static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const csc *P, const csc *A,
                          const c_float *Px_all, const c_float *Ax_all,
@@ -810,11 +875,11 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
     rc |= balloc(b, &io.Wq, B * n); rc |= balloc(b, &io.Wl, B * m); rc |= balloc(b, &io.Wu, B * m);
     rc |= balloc(b, &io.Wd, B * n); rc |= balloc(b, &io.We, B * m); rc |= balloc(b, &io.Wc, B);
     rc |= balloc(b, &io.Wk, B * NPk * NPk); rc |= balloc(b, &io.Wt, B * m); rc |= balloc(b, &io.flag, B);
-    rc |= balloc(b, &b->dQ, B * n); rc |= balloc(b, &b->dL, B * m); rc |= balloc(b, &b->dU, B * m);
     if (streamed) { rc |= balloc(b, &b->d_count, 1); rc |= balloc(b, &b->d_list[0], B); rc |= balloc(b, &b->d_list[1], B); }
   }
   if (rc) { osqp_amd_batch_cleanup(b); return OSQP_MEM_ALLOC_ERROR; }
   io.Px = dPx; io.Ax = dAx; io.Q = dQ; io.L = dL; io.U = dU;
+  b->dPx = dPx; b->dAx = dAx; b->dQ = dQ; b->dL = dL; b->dU = dU;
   auto up = [&](double *d, const c_float *s, size_t cnt) -> int {
     if (cnt && s && hipMemcpyAsync(d, s, cnt * sizeof(double), hipMemcpyHostToDevice, b->stream) != hipSuccess) return 1;
     return 0;
@@ -838,7 +903,7 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
   }
   b->h_info.assign(B * 8, 0.0);
   // setup phase on the device: Ruiz scaling, rho classes, K^-1 (one workgroup per QP)
-  if (streamed) (void)bs_setup_launch(b);
+  if (streamed) (void)bs_setup_launch(b, false);
   else batch_launch(b, 0);
   std::vector<int> hflag(B);
   if (hipGetLastError() != hipSuccess ||
@@ -941,7 +1006,8 @@ static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, cons
 // (a batch of another size may have changed it since).
 static void bs_set_lds(osqp_amd_batch *b) {
   if (b->lds_bytes <= 64 * 1024) return;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bs_setup), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bs_setup<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bs_setup<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bs_loop), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes);
 }
 
@@ -952,9 +1018,11 @@ static void bs_rebuild(osqp_amd_batch *b, const int *list, long long count) {
   hipLaunchKernelGGL(k_bs_invert, dim3((unsigned)count), dim3(BS_NTI), 0, b->stream, b->n, b->io, b->NPs, list);
 }
 
-static int bs_setup_launch(osqp_amd_batch *b) {
+// update = true: the re-equilibration of a matrix update; K is re-formed and re-inverted for every member either way
+static int bs_setup_launch(osqp_amd_batch *b, bool update) {
   bs_set_lds(b);
-  hipLaunchKernelGGL(k_bs_setup, dim3((unsigned)b->B), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, b->NPs);
+  if (update) hipLaunchKernelGGL(k_bs_setup<true>, dim3((unsigned)b->B), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, b->NPs);
+  else hipLaunchKernelGGL(k_bs_setup<false>, dim3((unsigned)b->B), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, b->NPs);
   bs_rebuild(b, nullptr, b->B);
   return 0;
 }
@@ -995,6 +1063,7 @@ static int bs_solve(osqp_amd_batch *b) {
 
 // the one instantiation of k_batch_solve for (tile, phase)
 static const void *batch_kernel(int tile, int phase) {
+  if (phase == 2) return tile == 8 ? reinterpret_cast<const void *>(&k_batch_solve<8, 4, 32, 2>) : reinterpret_cast<const void *>(&k_batch_solve<4, 2, 32, 2>);
   if (tile == 8) return phase ? reinterpret_cast<const void *>(&k_batch_solve<8, 4, 32, 1>) : reinterpret_cast<const void *>(&k_batch_solve<8, 4, 32, 0>);
   return phase ? reinterpret_cast<const void *>(&k_batch_solve<4, 2, 32, 1>) : reinterpret_cast<const void *>(&k_batch_solve<4, 2, 32, 0>);
 }
@@ -1033,8 +1102,119 @@ extern "C" c_int osqp_amd_batch_update(osqp_amd_batch *b, const c_float *Q, cons
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// matrix-value, rho and warm-start updates
+// ---------------------------------------------------------------------------
+static int stage_reserve(osqp_amd_batch *b, size_t vals, size_t idx) {
+  if (vals > b->vals_cap) { if (balloc(b, &b->d_vals, vals)) return -102; b->vals_cap = vals; }
+  if (idx > b->idx_cap) { if (balloc(b, &b->d_idx, idx)) return -102; b->idx_cap = idx; }
+  return 0;
+}
+
+// One of P, A: new values into the raw value array (switched to per-member storage first when the handle holds
+// shared values and the update brings per-member ones).  at / iat: where this matrix's values and indices sit in
+// the staging buffers.
+static int patch_values(osqp_amd_batch *b, double **raw, const double **io_raw, long long *stride, int nnz,
+                        const c_float *vals, const c_int *idx, c_int cnt, c_int per_member, size_t at, size_t iat) {
+  const long long B = b->B;
+  if (per_member && !*stride) {
+    double *all = nullptr;
+    if (balloc(b, &all, (size_t)B * nnz)) return -102;
+    if (nnz) hipLaunchKernelGGL(k_batch_scatter, dim3((unsigned)((B * nnz + 255) / 256)), dim3(256), 0, b->stream,
+                                all, (long long)nnz, *raw, 0LL, (const int *)nullptr, (long long)nnz, B);
+    *raw = all; *io_raw = all; *stride = nnz;   // (the shared array stays in b->allocs until cleanup)
+  }
+  if (!cnt) return 0;
+  const size_t tot = per_member ? (size_t)B * cnt : (size_t)cnt;
+  if (!idx && (per_member || !*stride)) {       // same layout as the raw array: straight in
+    BCHK(hipMemcpyAsync(*raw, vals, tot * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    return 0;
+  }
+  BCHK(hipMemcpyAsync(b->d_vals + at, vals, tot * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  if (idx) {
+    std::vector<int> h(idx, idx + cnt);
+    BCHK(hipMemcpyAsync(b->d_idx + iat, h.data(), (size_t)cnt * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    BCHK(hipStreamSynchronize(b->stream));      // h goes out of scope
+  }
+  const long long members = *stride ? B : 1;
+  hipLaunchKernelGGL(k_batch_scatter, dim3((unsigned)((members * cnt + 255) / 256)), dim3(256), 0, b->stream,
+                     *raw, *stride, b->d_vals + at, per_member ? (long long)cnt : 0LL,
+                     idx ? b->d_idx + iat : (const int *)nullptr, (long long)cnt, members);
+  return 0;
+}
+
+extern "C" c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
+                                                const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
+                                                const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  // nothing is written before every argument has passed (osqp.c:1197-1222; the index range is this project's check)
+  if (Px && Px_idx && P_n > b->nnzP) return 1;
+  if (Ax && Ax_idx && A_n > b->nnzA) return 2;
+  if ((Px && Px_idx && P_n < 0) || (Ax && Ax_idx && A_n < 0)) return OSQP_DATA_VALIDATION_ERROR;
+  if (Px && Px_idx) for (c_int k = 0; k < P_n; k++) if (Px_idx[k] < 0 || Px_idx[k] >= b->nnzP) return OSQP_DATA_VALIDATION_ERROR;
+  if (Ax && Ax_idx) for (c_int k = 0; k < A_n; k++) if (Ax_idx[k] < 0 || Ax_idx[k] >= b->nnzA) return OSQP_DATA_VALIDATION_ERROR;
+  if (!Px && !Ax) return 0;
+  BCHK(hipSetDevice(b->device));
+  const c_int pc = Px ? (Px_idx ? P_n : (c_int)b->nnzP) : 0, ac = Ax ? (Ax_idx ? A_n : (c_int)b->nnzA) : 0;
+  const size_t B = (size_t)b->B;
+  const size_t pv = (size_t)pc * (Px_per_member ? B : 1), av = (size_t)ac * (Ax_per_member ? B : 1);
+  if (stage_reserve(b, pv + av, (size_t)pc + ac)) return OSQP_MEM_ALLOC_ERROR;
+  if (Px && patch_values(b, &b->dPx, &b->io.Px, &b->io.strideP, b->nnzP, Px, Px_idx, pc, Px_per_member, 0, 0))
+    return OSQP_MEM_ALLOC_ERROR;
+  if (Ax && patch_values(b, &b->dAx, &b->io.Ax, &b->io.strideA, b->nnzA, Ax, Ax_idx, ac, Ax_per_member, pv, (size_t)pc))
+    return OSQP_MEM_ALLOC_ERROR;
+  // re-equilibrate from the raw data, re-form and re-invert K with each member's current rho and classes
+  if (b->engine == OSQP_AMD_BATCH_STREAMED) (void)bs_setup_launch(b, true);
+  else batch_launch(b, 2);
+  BCHK(hipGetLastError());
+  std::vector<int> hflag(B);
+  BCHK(hipMemcpyAsync(hflag.data(), b->io.flag, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  BCHK(hipStreamSynchronize(b->stream));
+  b->noncvx = false;
+  for (size_t q = 0; q < B; q++)
+    if (hflag[q] & 8) {
+      fprintf(stderr, "osqp_amd batch: the new K of QP %zu of the batch is not positive definite (K = P + sigma I + "
+                      "A' rho A with the updated values); solves are refused until a matrix update succeeds\n", q);
+      b->noncvx = true;
+      return OSQP_NONCVX_ERROR;
+    }
+  return 0;
+}
+
+extern "C" c_int osqp_amd_batch_update_rho(osqp_amd_batch *b, const c_float *rho, c_int per_member) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!rho) return OSQP_DATA_VALIDATION_ERROR;
+  const size_t cnt = per_member ? (size_t)b->B : 1;
+  for (size_t k = 0; k < cnt; k++) if (!(rho[k] > 0)) return 1;   // osqp.c:1288-1293
+  BCHK(hipSetDevice(b->device));
+  if (!b->d_rho && balloc(b, &b->d_rho, (size_t)b->B)) return OSQP_MEM_ALLOC_ERROR;
+  BCHK(hipMemcpyAsync(b->d_rho, rho, cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  hipLaunchKernelGGL(k_batch_update_rho, dim3((unsigned)((b->B + 255) / 256)), dim3(256), 0, b->stream,
+                     b->B, b->io, b->d_rho, (int)(per_member != 0));
+  BCHK(hipGetLastError());
+  BCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+extern "C" c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, const c_float *Y) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  b->st.warm_start = 1;                          // osqp.c:948
+  if (!X && !Y) return 0;
+  BCHK(hipSetDevice(b->device));
+  const size_t B = (size_t)b->B, nx = X ? B * b->n : 0, ny = Y ? B * b->m : 0;
+  if (stage_reserve(b, nx + ny, 0)) return OSQP_MEM_ALLOC_ERROR;
+  if (nx) BCHK(hipMemcpyAsync(b->d_vals, X, nx * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  if (ny) BCHK(hipMemcpyAsync(b->d_vals + nx, Y, ny * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  hipLaunchKernelGGL(k_batch_warm_start, dim3((unsigned)B), dim3(256), 0, b->stream, b->pat, b->io,
+                     X ? b->d_vals : (const double *)nullptr, Y ? b->d_vals + nx : (const double *)nullptr);
+  BCHK(hipGetLastError());
+  BCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
 extern "C" c_int osqp_amd_batch_solve(osqp_amd_batch *b) {
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (b->noncvx) return OSQP_NONCVX_ERROR;
   BCHK(hipSetDevice(b->device));
   if (b->engine == OSQP_AMD_BATCH_STREAMED) return bs_solve(b);
   b->io.order = (b->lpt && b->solves > 0) ? b->d_order : nullptr;   // first solve: no history, index order

@@ -93,7 +93,8 @@ __device__ __forceinline__ void load_problem(const BL &s, const BPattern &p, con
 
 // Ruiz equilibration (scaling.c:44-156) with cost scaling, then the scaled bounds and their row classes.
 // Returns the cost scaling c; D, E, the scaled q, l, u and matrix values are left in s.
-template <int NT, bool SLAB>
+// CLASSIFY = false: the scale_data of a matrix update (osqp.c:1254-1257), which keeps the row classes s.ctype holds.
+template <int NT, bool SLAB, bool CLASSIFY = true>
 __device__ __forceinline__ double ruiz_scale(const BL &s, const BPattern &p, const BSettings &st) {
   constexpr int NW = NT / 64;
   const int n = p.n, m = p.m, tid = threadIdx.x;
@@ -137,13 +138,15 @@ __device__ __forceinline__ double ruiz_scale(const BL &s, const BPattern &p, con
   }
   for (int i = tid; i < m; i += NT) {
     s_l[i] = s_l[i] * s_E[i]; s_u[i] = s_u[i] * s_E[i];
-    s.ctype[i] = row_class(s_l[i], s_u[i], st.rho_tol);
+    if (CLASSIFY) s.ctype[i] = row_class(s_l[i], s_u[i], st.rho_tol);
   }
   return cs;
 }
 
-// the setup workspace of one member: the analogue of the reference's scaled OSQPData, kept across solves
-template <int NT, bool SLAB>
+// the setup workspace of one member: the analogue of the reference's scaled OSQPData, kept across solves.
+// FRESH = false (a matrix update): the iterates, the row classes and rho stay what they are, and rho_updates is
+// reset as reset_info does in every osqp_update_* (src/auxil.c:632-649).
+template <int NT, bool SLAB, bool FRESH = true>
 __device__ __forceinline__ void store_workspace(const BL &s, const BPattern &p, const BIO &io, long long qp,
                                                 double cs, double rho, int flag) {
   const int n = p.n, m = p.m, tid = threadIdx.x;
@@ -152,12 +155,24 @@ __device__ __forceinline__ void store_workspace(const BL &s, const BPattern &p, 
     for (int k = tid; k < p.nnzP; k += NT) Wv[k] = s.Pv[k];
     for (int k = tid; k < p.nnzA; k += NT) Wv[p.nnzP + k] = s.Av[k];
   }
-  for (int j = tid; j < n; j += NT) { io.Wq[qp * n + j] = s_q[j]; io.Wd[qp * n + j] = s_D[j]; io.Xs[qp * n + j] = 0.0; }
+  for (int j = tid; j < n; j += NT) {
+    io.Wq[qp * n + j] = s_q[j]; io.Wd[qp * n + j] = s_D[j];
+    if (FRESH) io.Xs[qp * n + j] = 0.0;
+  }
   for (int i = tid; i < m; i += NT) {
     io.Wl[qp * m + i] = s_l[i]; io.Wu[qp * m + i] = s_u[i]; io.We[qp * m + i] = s_E[i];
-    io.Wt[qp * m + i] = s.ctype[i]; io.Zs[qp * m + i] = 0.0; io.Ys[qp * m + i] = 0.0;
+    if (FRESH) { io.Wt[qp * m + i] = s.ctype[i]; io.Zs[qp * m + i] = 0.0; io.Ys[qp * m + i] = 0.0; }
   }
-  if (tid == 0) { io.Wc[qp] = cs; io.rho_io[qp] = rho; io.flag[qp] = flag; }
+  if (tid == 0) {
+    io.Wc[qp] = cs; io.flag[qp] = flag;
+    if (FRESH) io.rho_io[qp] = rho; else io.info[qp * 8 + 5] = 0.0;
+  }
+}
+
+// the row classes of the workspace back into s (a matrix update keeps them)
+template <int NT>
+__device__ __forceinline__ void load_classes(const BL &s, const BPattern &p, const BIO &io, long long qp) {
+  for (int i = threadIdx.x; i < p.m; i += NT) s.ctype[i] = io.Wt[qp * p.m + i];
 }
 
 // ---------------------------------------------------------------------------

@@ -5,7 +5,8 @@
 // iteration (twice for refined members) as a GEMV with 16-byte loads.  Only the n- and m-vectors of one member
 // live in LDS; the shared pattern is read from global memory (L2 resident) and the member's scaled P and A
 // values from its slab io.Wv.  Four kernels, each one launch over the batch:
-//   k_bs_setup   one workgroup per member: Ruiz scaling, row classes, workspace (batch_admm.h, as the tiled setup phase);
+//   k_bs_setup   one workgroup per member: Ruiz scaling, row classes, workspace (batch_admm.h, as the tiled setup phase;
+//                <true>: the re-equilibration of a matrix update, classes, rho and iterates kept);
 //   k_bs_form    grid (NP rows, members): K = P + sigma I + A' diag(rho) A, dense, from a host-built list of
 //                (A slot, A slot, row) triples per entry of triu(K): a fixed summation order, no atomics;
 //   k_bs_invert  one workgroup per member: Gauss-Jordan in place in HBM without pivoting (K is SPD); a
@@ -72,16 +73,18 @@ __device__ __forceinline__ BL bs_layout(double *lds, const BPattern &p, const BI
 
 // ---------------------------------------------------------------------------
 // setup: the tiled engine's setup phase with the matrix values in the member's HBM slab (SLAB: the slab is
-// written and re-read by different lanes of this workgroup, so its hand-offs are fenced)
+// written and re-read by different lanes of this workgroup, so its hand-offs are fenced).
+// UPD: the same on the current raw data for a matrix update (osqp.c:1171-1279): row classes, rho and iterates stay.
 // ---------------------------------------------------------------------------
+template <bool UPD>
 __global__ void __launch_bounds__(BS_NT) k_bs_setup(BPattern p, BSettings st, BIO io, int NP) {
   const long long qp = blockIdx.x;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const BL s = bs_layout(lds, p, io, qp, NP);
   clear_vectors<BS_NT>(s);
   load_problem<BS_NT, true>(s, p, io, qp);
-  const double cs = ruiz_scale<BS_NT, true>(s, p, st);
-  store_workspace<BS_NT, true>(s, p, io, qp, cs, fmin(fmax(st.rho, 1e-6), 1e6), 1);   // 1: K^-1 is due (k_bs_form, k_bs_invert)
+  const double cs = ruiz_scale<BS_NT, true, !UPD>(s, p, st);
+  store_workspace<BS_NT, true, !UPD>(s, p, io, qp, cs, fmin(fmax(st.rho, 1e-6), 1e6), 1);   // 1: K^-1 is due (k_bs_form, k_bs_invert)
 }
 
 // ---------------------------------------------------------------------------
