@@ -22,8 +22,9 @@ typedef struct osqp_amd_batch osqp_amd_batch;
  * optionally give per-QP values.  Q [batch][n], L, U [batch][m] row-major.
  * Returns 0 or an osqp_error_type code (include/constants.h:42-50 numbering):
  * OSQP_NONCVX_ERROR when some member's K = P + sigma I + A' rho A is not positive definite
- * (stderr names the first such member), OSQP_SETTINGS_VALIDATION_ERROR for polish or
- * time_limit > 0, which the batched kernel does not implement. */
+ * (stderr names the first such member), OSQP_SETTINGS_VALIDATION_ERROR for settings->polish != 0
+ * (polish is a call on a solved handle: osqp_amd_batch_polish) or time_limit > 0, which the batched
+ * kernel does not implement. */
 c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const csc *P, const csc *A,
                            const c_float *Px_all, const c_float *Ax_all,
                            const c_float *Q, const c_float *L, const c_float *U,
@@ -76,6 +77,26 @@ c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, const c_flo
 /* osqp_solve for every QP; iterates persist on the device between calls
  * (warm start, settings->warm_start). */
 c_int osqp_amd_batch_solve(osqp_amd_batch *b);
+/* polish (src/polish.c:19-350) for every member whose last solve ended OSQP_SOLVED; the others are skipped.
+ * Polish is this call on a solved handle, with settings->delta and settings->polish_refine_iter as given at setup;
+ * settings->polish != 0 itself stays refused by the setup functions.  Per member, in its scaled space: the active
+ * rows are guessed from the iterates of the solve, the dense regularised KKT matrix [P + delta I, Ar'; Ar, -delta I]
+ * is inverted on the device, exactly polish_refine_iter refinement steps against the unregularised matrix follow,
+ * and the reference's three-clause rule accepts or rejects the polished point.  An accepted member's X, Y,
+ * info8[2..4] (obj_val, pri_res, dua_res) and stored iterates (the start of the next warm-started solve) are
+ * overwritten; of a rejected or skipped member nothing changes.  rho, K^-1, row classes and rho_updates never change.
+ * status_polish [batch] (NULL = skip): 1 accepted, -1 tried and rejected (a KKT pivot of the wrong sign included),
+ * 0 not tried.  A second call without a solve in between does no work and reports the same values.
+ * Memory: the KKT matrices are NPOL x NPOL doubles per member, NPOL = n + the largest number of active rows in the
+ * batch, rounded up to 32, in one buffer separate from K^-1, allocated at the first call and freed by cleanup.  The
+ * solved members go through it in chunks; the buffer never exceeds 8 GiB (or the number of bytes the environment
+ * variable OSQP_AMD_BATCH_POLISH_CAP_BYTES held when the handle was set up; one member's matrix at the least).
+ * Returns 0; OSQP_WORKSPACE_NOT_INIT_ERROR when no solve has run since setup or since the last update of data,
+ * matrices or rho (or a warm start with arrays: the stored iterates are then not a solve's);
+ * OSQP_MEM_ALLOC_ERROR when the buffer cannot be allocated (the handle stays usable);
+ * OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line when n + active rows exceeds 2176, which only the tiled engine
+ * with many rows can reach. */
+c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish);
 /* Results: X [batch][n], Y [batch][m] (unscaled; OSQP_NAN when infeasible),
  * info8 [batch][8] = {iter, status_val, obj_val, pri_res, dua_res, rho_updates,
  * rho_estimate, rho}; DX / DY infeasibility certificates.  NULL = skip. */

@@ -33,6 +33,8 @@ def _bind(L):
     L.osqp_amd_batch_warm_start.argtypes = [H, abi.c_float_p, abi.c_float_p]
     L.osqp_amd_batch_solve.restype = abi.c_int
     L.osqp_amd_batch_solve.argtypes = [H]
+    L.osqp_amd_batch_polish.restype = abi.c_int
+    L.osqp_amd_batch_polish.argtypes = [H, abi.c_int_p]
     L.osqp_amd_batch_get.restype = abi.c_int
     L.osqp_amd_batch_get.argtypes = [H, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p]
     L.osqp_amd_batch_cleanup.restype = None
@@ -90,6 +92,7 @@ class BatchOSQP:
         self._lib = lib()
         _bind(self._lib)
         self._h = None
+        self._status_polish = None
 
     def setup(self, P, A, Q, L, U, Px_all=None, Ax_all=None, device=None, engine="auto", **settings):
         """P (n x n, any triangle content; upper triangle is used), A (m x n): shared
@@ -282,10 +285,27 @@ class BatchOSQP:
             from .multi import solve_many
             self._last = solve_many(self._many, max_workers=8)
             return self._many_results() if fetch else None
+        self._status_polish = None
         rc = self._lib.osqp_amd_batch_solve(self._h)
         if rc:
             raise RuntimeError("osqp_amd_batch_solve failed (%d)" % rc)
         return self.results() if fetch else None
+
+    def polish(self):
+        """Polish (src/polish.c) on the device for every member whose last solve ended `solved`, with the handle's
+        `delta` and `polish_refine_iter`.  Returns results() -- x, y, obj_val, pri_res, dua_res of the accepted
+        members are the polished ones -- with `status_polish` [B]: 1 accepted, -1 tried and rejected (nothing of
+        that member changed), 0 not tried.  Needs a solve since setup or the last update."""
+        if self._many is not None:
+            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): polish is a call of the batch "
+                               "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
+        sp = np.zeros(self.B, np.int64)
+        rc = self._lib.osqp_amd_batch_polish(self._h, abi.iptr(sp))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_polish failed (%d)%s" % (rc, ": no solve has run on the current problem"
+                                                                        if rc == 7 else ""))
+        self._status_polish = sp
+        return self.results()
 
     def results(self):
         if self._many is not None:
@@ -296,6 +316,7 @@ class BatchOSQP:
         if rc:
             raise RuntimeError("osqp_amd_batch_get failed (%d)" % rc)
         out = SimpleNamespace(x=X, y=Y[:, :self.m], dual_inf_cert=DX, prim_inf_cert=DY[:, :self.m], info_raw=info)
+        out.status_polish = np.zeros(self.B, np.int64) if self._status_polish is None else self._status_polish.copy()
         for k, name in enumerate(INFO_FIELDS):
             col = info[:, k]
             setattr(out, name, col.astype(np.int64) if name in ("iter", "status_val", "rho_updates") else col)

@@ -666,6 +666,7 @@ __global__ void __launch_bounds__(1024) k_batch_order(long long B, const double 
 }
 
 #include "batch_streamed.h"
+#include "batch_polish.h"
 
 struct osqp_amd_batch {
   int engine = OSQP_AMD_BATCH_TILED;
@@ -692,6 +693,15 @@ struct osqp_amd_batch {
   bool noncvx = false;      // the last matrix update left some member's K indefinite: solve refuses
   int *d_order = nullptr;   // dispatch order for the next solve (k_batch_order)
   int lpt = 1;
+  // polish (batch_polish.h)
+  double pol_delta = 0.0;   // settings->delta
+  int pol_refine = 0;       // settings->polish_refine_iter
+  size_t pol_cap = 0;       // largest KKT buffer in bytes (OSQP_AMD_BATCH_POLISH_CAP_BYTES)
+  size_t pol_bytes = 0;     // size of pol.K as allocated
+  BPol pol{};
+  int *d_plist = nullptr;   // [B] the solved members, in index order
+  bool solved = false;      // the iterates and info on the device are those of a solve of the current problem
+  bool polished = false;    // ... and polish has already run on them
 };
 
 static void batch_launch(osqp_amd_batch *b, int phase);
@@ -740,6 +750,11 @@ static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
   t.ablate = e ? atoi(e) : 0;
   e = getenv("OSQP_AMD_BATCH_LPT");
   b->lpt = e ? atoi(e) : 1;   // phase time stamps (wall_clock64 ticks) written into DX[0..7]
+  b->pol_delta = s->delta; b->pol_refine = (int)s->polish_refine_iter;
+  // cap of the polish buffer (osqp_amd_batch_polish works through the solved members in chunks that fit it);
+  // read here, once per handle
+  e = getenv("OSQP_AMD_BATCH_POLISH_CAP_BYTES");
+  b->pol_cap = e ? (size_t)strtoull(e, nullptr, 10) : (size_t)8 << 30;
 }
 
 static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, const std::vector<int> &Pi,
@@ -762,7 +777,8 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
   if (settings->rho <= 0 || settings->sigma <= 0 || settings->alpha <= 0 || settings->alpha >= 2 ||
       settings->max_iter <= 0 || settings->scaling < 0 || settings->check_termination < 0)
     return OSQP_SETTINGS_VALIDATION_ERROR;
-  // the kernel has no polish step and no clock: refusing beats an answer the caller did not ask for
+  // the solve has no polish step (polish is a call of its own on a solved handle, osqp_amd_batch_polish) and no
+  // clock: refusing beats an answer the caller did not ask for
   if (settings->polish || settings->time_limit > 0) {
     fprintf(stderr, "osqp_amd batch: %s is not implemented by the batched engine\n",
             settings->polish ? "polish" : "time_limit");
@@ -1082,6 +1098,7 @@ extern "C" void osqp_amd_batch_cleanup(osqp_amd_batch *b) {
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   for (void *p : b->allocs) (void)hipFree(p);
+  if (b->pol.K) (void)hipFree(b->pol.K);
   if (b->stream) (void)hipStreamDestroy(b->stream);
   delete b;
 }
@@ -1092,6 +1109,7 @@ extern "C" c_int osqp_amd_batch_update(osqp_amd_batch *b, const c_float *Q, cons
   const size_t B = (size_t)b->B;
   if (L && U)
     for (size_t k = 0; k < B * (size_t)b->m; k++) if (L[k] > U[k]) return 1;   // osqp.c:815-822
+  b->solved = false;
   if (Q) BCHK(hipMemcpyAsync(b->dQ, Q, B * b->n * sizeof(double), hipMemcpyHostToDevice, b->stream));
   if (L) BCHK(hipMemcpyAsync(b->dL, L, B * b->m * sizeof(double), hipMemcpyHostToDevice, b->stream));
   if (U) BCHK(hipMemcpyAsync(b->dU, U, B * b->m * sizeof(double), hipMemcpyHostToDevice, b->stream));
@@ -1155,6 +1173,7 @@ extern "C" c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
   if (Ax && Ax_idx) for (c_int k = 0; k < A_n; k++) if (Ax_idx[k] < 0 || Ax_idx[k] >= b->nnzA) return OSQP_DATA_VALIDATION_ERROR;
   if (!Px && !Ax) return 0;
   BCHK(hipSetDevice(b->device));
+  b->solved = false;
   const c_int pc = Px ? (Px_idx ? P_n : (c_int)b->nnzP) : 0, ac = Ax ? (Ax_idx ? A_n : (c_int)b->nnzA) : 0;
   const size_t B = (size_t)b->B;
   const size_t pv = (size_t)pc * (Px_per_member ? B : 1), av = (size_t)ac * (Ax_per_member ? B : 1);
@@ -1187,6 +1206,7 @@ extern "C" c_int osqp_amd_batch_update_rho(osqp_amd_batch *b, const c_float *rho
   const size_t cnt = per_member ? (size_t)b->B : 1;
   for (size_t k = 0; k < cnt; k++) if (!(rho[k] > 0)) return 1;   // osqp.c:1288-1293
   BCHK(hipSetDevice(b->device));
+  b->solved = false;
   if (!b->d_rho && balloc(b, &b->d_rho, (size_t)b->B)) return OSQP_MEM_ALLOC_ERROR;
   BCHK(hipMemcpyAsync(b->d_rho, rho, cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
   hipLaunchKernelGGL(k_batch_update_rho, dim3((unsigned)((b->B + 255) / 256)), dim3(256), 0, b->stream,
@@ -1201,6 +1221,7 @@ extern "C" c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, 
   b->st.warm_start = 1;                          // osqp.c:948
   if (!X && !Y) return 0;
   BCHK(hipSetDevice(b->device));
+  b->solved = false;                             // the stored iterates are the caller's now, not a solve's
   const size_t B = (size_t)b->B, nx = X ? B * b->n : 0, ny = Y ? B * b->m : 0;
   if (stage_reserve(b, nx + ny, 0)) return OSQP_MEM_ALLOC_ERROR;
   if (nx) BCHK(hipMemcpyAsync(b->d_vals, X, nx * sizeof(double), hipMemcpyHostToDevice, b->stream));
@@ -1216,13 +1237,85 @@ extern "C" c_int osqp_amd_batch_solve(osqp_amd_batch *b) {
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (b->noncvx) return OSQP_NONCVX_ERROR;
   BCHK(hipSetDevice(b->device));
-  if (b->engine == OSQP_AMD_BATCH_STREAMED) return bs_solve(b);
+  b->solved = b->polished = false;
+  if (b->engine == OSQP_AMD_BATCH_STREAMED) {
+    const int rc = bs_solve(b);
+    b->solved = rc == 0;
+    return rc;
+  }
   b->io.order = (b->lpt && b->solves > 0) ? b->d_order : nullptr;   // first solve: no history, index order
   batch_launch(b, 1);
   if (b->lpt) hipLaunchKernelGGL(k_batch_order, dim3(1), dim3(1024), 0, b->stream, b->B, b->io.info, b->d_order);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   b->solves++;
+  b->solved = true;
+  return 0;
+}
+
+// polish for the solved members, in chunks of at most pol_cap bytes of KKT matrices (batch_polish.h)
+extern "C" c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish) {
+  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  BCHK(hipSetDevice(b->device));
+  const size_t B = (size_t)b->B;
+  const int n = b->n, m = b->m;
+  BPol &pl = b->pol;
+  if (!b->d_plist) {
+    int rc = 0;
+    rc |= balloc(b, &pl.map, B * m); rc |= balloc(b, &pl.rows, B * m); rc |= balloc(b, &pl.mred, B);
+    rc |= balloc(b, &pl.nlow, B); rc |= balloc(b, &pl.stat, B);
+    if (!rc) rc |= balloc(b, &b->d_plist, B);
+    if (rc) { (void)hipGetLastError(); return OSQP_MEM_ALLOC_ERROR; }
+  }
+  std::vector<int> h(B);
+  if (!b->polished) {       // (a second call without a solve in between finds the work done and reports it again)
+    hipLaunchKernelGGL(k_bp_active, dim3((unsigned)B), dim3(256), 0, b->stream, m, b->io, pl);
+    BCHK(hipGetLastError());
+    BCHK(hipMemcpyAsync(h.data(), pl.mred, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    BCHK(hipStreamSynchronize(b->stream));
+    std::vector<int> list;
+    int mmax = 0;
+    for (size_t q = 0; q < B; q++) if (h[q] >= 0) { list.push_back((int)q); mmax = std::max(mmax, h[q]); }
+    if (!list.empty()) {
+      const int NPOL = (n + mmax + 31) & ~31;
+      const size_t lds = bp_lds_bytes(n, m, NPOL);
+      if (NPOL > BP_MAX_N || lds > 160 * 1024) {
+        fprintf(stderr, "osqp_amd batch: polish needs a KKT matrix of order n + active rows = %d (> %d) or %zu B of LDS "
+                        "(> 160 KiB) for some member\n", n + mmax, BP_MAX_N, lds);
+        return OSQP_LINSYS_SOLVER_INIT_ERROR;
+      }
+      const size_t per = (size_t)NPOL * NPOL * sizeof(double);
+      const size_t chunk = std::min(std::min(list.size(), (size_t)65535), std::max((size_t)1, b->pol_cap / per));
+      if (chunk * per > b->pol_bytes) {
+        if (pl.K) (void)hipFree(pl.K);
+        pl.K = nullptr; b->pol_bytes = 0;
+        void *k = nullptr;
+        if (hipMalloc(&k, chunk * per) != hipSuccess) { (void)hipGetLastError(); return OSQP_MEM_ALLOC_ERROR; }
+        pl.K = static_cast<double *>(k); b->pol_bytes = chunk * per;
+      }
+      BCHK(hipMemcpyAsync(b->d_plist, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+      const size_t ilds = 4 * (size_t)NPOL * sizeof(double);
+      if (ilds > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bp_invert), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ilds);
+      if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bp_polish), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      for (size_t c0 = 0; c0 < list.size(); c0 += chunk) {
+        const unsigned cnt = (unsigned)std::min(chunk, list.size() - c0);
+        const int *lp = b->d_plist + c0;
+        hipLaunchKernelGGL(k_bp_form, dim3((unsigned)NPOL, cnt), dim3(256), 0, b->stream, b->pat, b->io, pl, NPOL, b->pol_delta, lp);
+        hipLaunchKernelGGL(k_bp_invert, dim3(cnt), dim3(BS_NTI), ilds, b->stream, n, pl, NPOL, lp);
+        hipLaunchKernelGGL(k_bp_polish, dim3(cnt), dim3(BP_NT), lds, b->stream, b->pat, b->st, b->io, pl, NPOL, b->pol_refine, lp);
+        BCHK(hipGetLastError());
+      }
+      BCHK(hipStreamSynchronize(b->stream));   // (list goes out of scope)
+    }
+    b->polished = true;
+  }
+  if (status_polish) {
+    BCHK(hipMemcpyAsync(h.data(), pl.stat, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    BCHK(hipStreamSynchronize(b->stream));
+    for (size_t q = 0; q < B; q++) status_polish[q] = h[q];
+  }
   return 0;
 }
 

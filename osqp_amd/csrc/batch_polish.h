@@ -1,0 +1,247 @@
+// batch_polish.h -- polish (src/polish.c:19-350) for the solved members of a batch, included by batch.hip after
+// both engines.  It serves either engine: it needs only the shared pattern, the member's scaled values (io.Wv),
+// its scaled q, l, u, D, E, c and the scaled iterates the last solve left (io.Xs, io.Zs, io.Ys).
+//
+// Per member, in the member's scaled space like the reference (its w->data is scaled): guess the active rows,
+// form the regularised KKT matrix [P + delta I, Ar'; Ar, -delta I] of order N = n + mred densely, invert it in
+// place, solve for [-q; l_low; u_upp], take exactly polish_refine_iter refinement steps against the unregularised
+// [P, Ar'; Ar, 0], project (z, y) on the normal cone, compute objective and residuals as update_info
+// (batch_admm.h) does and apply the acceptance rule of polish.c:301-311.  The reference's delta and step count
+// are kept on purpose: where active rows are linearly dependent x is unique but the multipliers are not, and
+// the y the reference returns is a function of both.
+//   k_bp_active  one workgroup per member: the two active tests, the index scan (lows first), mred and the
+//                row <-> reduced-row maps;
+//   k_bp_form    grid (NPOL rows, members of the chunk): row i of the member's NPOL x NPOL matrix, identity
+//                beyond N; NPOL = n + largest mred of the batch, rounded up to 32;
+//   k_bp_invert  one workgroup per member: k_bs_invert's in-place Gauss-Jordan over N.  A quasi-definite
+//                matrix is strongly factorisable in this order: n positive pivots, then mred negative ones; a
+//                pivot of the wrong sign (zero and NaN included) rejects the member's polish;
+//   k_bp_polish  one workgroup per member: everything after the inversion.
+// An accepted member's X, Y, info8[2..4] and scaled iterates are overwritten; of a rejected or skipped
+// member nothing is written but its status_polish.  rho, K^-1, io.flag, the row classes and rho_updates are
+// never touched.
+
+#define BP_MAX_N 2176      // largest order n + mred (n <= 1024, m <= 1129 in the streamed engine); k_bp_form's row buffer
+#define BP_NT 512
+
+struct BPol {              // polish workspace of a handle (device pointers)
+  int *map;                // [B][m] reduced row of a row (lows first, then upps), -1 = not active
+  int *rows;               // [B][m] row of a reduced row
+  int *mred;               // [B] active rows; -1: the member's last solve did not end OSQP_SOLVED (skipped)
+  int *nlow;               // [B] how many of them are active at the lower bound
+  int *stat;               // [B] status_polish: 1 accepted, -1 tried and rejected, 0 not tried
+  double *K;               // [members of a chunk][NPOL * NPOL] the KKT matrix, then its inverse
+};
+
+// Active rows from the stored scaled iterates and bounds (polish.c:19-100): low z - l < -y, upp u - z < y.
+// (Both cannot hold for l <= u; a row that passed the low test is not tested again.)
+__global__ void __launch_bounds__(256) k_bp_active(int m, BIO io, BPol pl) {
+  __shared__ int sc[256];
+  __shared__ int base;
+  const long long qp = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (tid == 0) pl.stat[qp] = 0;
+  if ((int)io.info[qp * 8 + 1] != OSQP_SOLVED) {
+    if (tid == 0) pl.mred[qp] = -1;
+    return;
+  }
+  const double *z = io.Zs + qp * m, *y = io.Ys + qp * m, *l = io.Wl + qp * m, *u = io.Wu + qp * m;
+  int *map = pl.map + qp * m, *rows = pl.rows + qp * m;
+  if (tid == 0) base = 0;
+  __syncthreads();
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int t0 = 0; t0 < m; t0 += 256) {
+      const int i = t0 + tid;
+      int f = 0;
+      if (i < m) {
+        const bool low = z[i] - l[i] < -y[i];
+        f = pass == 0 ? low : (!low && u[i] - z[i] < y[i]);
+      }
+      sc[tid] = f;
+      __syncthreads();
+      for (int o = 1; o < 256; o <<= 1) {      // inclusive scan of the 256 flags
+        const int v = tid >= o ? sc[tid - o] : 0;
+        __syncthreads();
+        sc[tid] += v;
+        __syncthreads();
+      }
+      if (i < m) {
+        if (f) { const int a = base + sc[tid] - 1; map[i] = a; rows[a] = i; }
+        else if (pass == 0) map[i] = -1;
+      }
+      __syncthreads();
+      if (tid == 255) base += sc[255];
+      __syncthreads();
+    }
+    if (pass == 0 && tid == 0) pl.nlow[qp] = base;
+  }
+  if (tid == 0) pl.mred[qp] = base;
+}
+
+// Row i of [P + delta I, Ar'; Ar, -delta I] of member list[blockIdx.y] into slot blockIdx.y of the buffer.
+// Both halves copy the same stored values, so the matrix is symmetric to the bit.
+__global__ void __launch_bounds__(256) k_bp_form(BPattern p, BIO io, BPol pl, int NPOL, double delta, const int *list) {
+  __shared__ __attribute__((aligned(16))) double row[BP_MAX_N];
+  const long long qp = list[blockIdx.y];
+  const int i = blockIdx.x, n = p.n, m = p.m, tid = threadIdx.x;
+  const int N = n + pl.mred[qp];
+  for (int j = tid; j < NPOL; j += 256) row[j] = 0.0;
+  __syncthreads();
+  const double *Pv = io.Wv + qp * ((long long)p.nnzP + p.nnzA), *Av = Pv + p.nnzP;
+  if (i < n) {
+    const int *map = pl.map + qp * m;
+    for (int k = p.Fp[i] + tid; k < p.Fp[i + 1]; k += 256) row[p.Fi[k]] = Pv[p.Fk[k]];
+    for (int k = p.Ap[i] + tid; k < p.Ap[i + 1]; k += 256) {
+      const int a = map[p.Ai[k]];
+      if (a >= 0) row[n + a] = Av[k];
+    }
+    __syncthreads();
+    if (tid == 0) row[i] = row[i] + delta;
+  } else if (i < N) {
+    const int r = pl.rows[qp * m + (i - n)];
+    for (int k = p.Rp[r] + tid; k < p.Rp[r + 1]; k += 256) row[p.Rj[k]] = Av[p.Rk[k]];
+    if (tid == 0) row[i] = 0.0 - delta;
+  } else if (tid == 0) row[i] = 1.0;             // identity padding
+  __syncthreads();
+  double *out = pl.K + (long long)blockIdx.y * NPOL * NPOL + (long long)i * NPOL;
+  for (int j = tid; j < NPOL; j += 256) out[j] = row[j];
+}
+
+// k_bs_invert over the order N = n + mred of the member in slot blockIdx.x, with exchange buffers of NPOL
+// doubles (dynamic LDS: 4 * NPOL doubles) and the quasi-definite pivot verdict.
+__global__ void __launch_bounds__(BS_NTI) k_bp_invert(int n, BPol pl, int NPOL, const int *list) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const long long qp = list[blockIdx.x];
+  const int N = n + pl.mred[qp];
+  double *Ka = pl.K + (long long)blockIdx.x * NPOL * NPOL;
+  const int tr = threadIdx.x >> 5, tc = threadIdx.x & 31;
+  bool bad = false;
+#pragma unroll 1
+  for (int k = 0; k < N; ++k) {
+    double *rk = lds + (k & 1) * NPOL, *ck = lds + (2 + (k & 1)) * NPOL;
+    if (tr == (k & 31)) for (int j = tc; j < N; j += 32) rk[j] = Ka[(long long)k * NPOL + j];
+    if (tc == (k & 31)) for (int i = tr; i < N; i += 32) ck[i] = Ka[(long long)i * NPOL + k];
+    __syncthreads();
+    const double akk = rk[k];
+    bad |= k < n ? !(akk > 0.0) : !(akk < 0.0);
+    const double piv = 1.0 / akk;
+    for (int i = tr; i < N; i += 32) {
+      const double ci = ck[i];
+      double *Ki = Ka + (long long)i * NPOL;
+      if (i == k) {
+        for (int j = tc; j < N; j += 32) Ki[j] = j == k ? piv : rk[j] * piv;
+      } else {
+        for (int j = tc; j < N; j += 32) Ki[j] = j == k ? 0.0 - ci * piv : __builtin_fma(-ci, rk[j] * piv, Ki[j]);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && bad) pl.stat[qp] = -1;
+}
+
+// LDS of k_bp_polish: three vectors of NPOL (solution, residual, correction), q, D, five m-vectors (l, u, E, z, y),
+// 32 reduction doubles and the two row maps.
+__host__ __device__ __forceinline__ size_t bp_lds_bytes(int n, int m, int NPOL) {
+  const size_t b = sizeof(double) * (3 * (size_t)NPOL + 2 * (size_t)n + 5 * (size_t)m + 32) + sizeof(int) * 2 * (size_t)m;
+  return (b + 15) & ~(size_t)15;
+}
+
+__global__ void __launch_bounds__(BP_NT) k_bp_polish(BPattern p, BSettings st, BIO io, BPol pl, int NPOL, int refine_iter,
+                                                     const int *list) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const long long qp = list[blockIdx.x];
+  if (pl.stat[qp] == -1) return;                 // the inversion met a pivot of the wrong sign
+  const int n = p.n, m = p.m, tid = threadIdx.x;
+  const int mred = pl.mred[qp], nlow = pl.nlow[qp], N = n + mred;
+  const double *Kinv = pl.K + (long long)blockIdx.x * NPOL * NPOL;
+  double *sol = lds, *res = sol + NPOL, *cor = res + NPOL;
+  double *q = cor + NPOL, *D = q + n, *l = D + n, *u = l + m, *E = u + m, *z = E + m, *y = z + m, *gp = y + m;
+  int *map = reinterpret_cast<int *>(gp + 32), *rows = map + m;
+  BL s;
+  s.Pv = io.Wv + qp * ((long long)p.nnzP + p.nnzA); s.Av = s.Pv + p.nnzP;
+  s.Pp = p.Pp; s.Pi = p.Pi; s.Pc = p.Pc; s.Fp = p.Fp; s.Fi = p.Fi; s.Fk = p.Fk;
+  s.Ap = p.Ap; s.Ai = p.Ai; s.Ac = p.Ac; s.Rp = p.Rp; s.Rj = p.Rj; s.Rk = p.Rk;
+  for (int j = tid; j < n; j += BP_NT) { q[j] = io.Wq[qp * n + j]; D[j] = io.Wd[qp * n + j]; }
+  for (int i = tid; i < m; i += BP_NT) {
+    l[i] = io.Wl[qp * m + i]; u[i] = io.Wu[qp * m + i]; E[i] = io.We[qp * m + i];
+    map[i] = pl.map[qp * m + i];
+    if (i < mred) rows[i] = pl.rows[qp * m + i];
+  }
+  const double cs = io.Wc[qp], pri0 = io.info[qp * 8 + 3], dua0 = io.info[qp * 8 + 4];
+  __syncthreads();
+  // rhs = [-q; l of the active lows; u of the active upps] (polish.c:226-233), zero in the padding
+  auto rhs = [&](int k) -> double {
+    if (k < n) return -q[k];
+    if (k >= N) return 0.0;
+    const int r = rows[k - n];
+    return k - n < nlow ? l[r] : u[r];
+  };
+  for (int k = tid; k < NPOL; k += BP_NT) res[k] = rhs(k);
+  __syncthreads();
+  bs_gemv(Kinv, NPOL, N, res, sol);
+  // iterative refinement against the unregularised KKT matrix (polish.c:134-181): a fixed number of steps
+  for (int it = 0; it < refine_iter; ++it) {
+    for (int k = tid; k < NPOL; k += BP_NT) {
+      double v = 0.0;
+      if (k < n) {
+        double aty = 0.0;
+        for (int kk = s.Ap[k]; kk < s.Ap[k + 1]; ++kk) {
+          const int a = map[s.Ai[kk]];
+          if (a >= 0) aty += s.Av[kk] * sol[n + a];
+        }
+        v = (rhs(k) - p_row_dot(s, sol, k)) - aty;
+      } else if (k < N) v = rhs(k) - a_row_dot(s, sol, rows[k - n]);
+      res[k] = v;
+    }
+    __syncthreads();
+    bs_gemv(Kinv, NPOL, N, res, cor);
+    for (int k = tid; k < N; k += BP_NT) sol[k] += cor[k];
+    __syncthreads();
+  }
+  // z = A x, y from the multipliers of the active rows, (z, y) on the normal cone (polish.c:262-279, proj.c:16-29);
+  // then objective and residuals of the polished point as update_info computes them (auxil.c:227-318)
+  const bool unscaled = st.scaling && !st.scaled_termination;
+  const double cinv = 1.0 / cs;
+  double mx[2] = {0.0, 0.0}, sm[1] = {0.0};
+  for (int i = tid; i < m; i += BP_NT) {
+    const double ax = a_row_dot(s, sol, i);
+    const int a = map[i];
+    const double t = ax + (a >= 0 ? sol[n + a] : 0.0);
+    const double zi = fmin(fmax(t, l[i]), u[i]);
+    z[i] = zi; y[i] = t - zi;
+    const double pr = ax + (-1.0) * zi;
+    mx[0] = fmax(mx[0], fabs(unscaled ? (1.0 / E[i]) * pr : pr));
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += BP_NT) {
+    const double px = p_row_dot(s, sol, j), qj = q[j];
+    double dr = qj + px;
+    if (m > 0) dr = dr + a_col_dot(s, y, j);
+    mx[1] = fmax(mx[1], fabs(unscaled ? (1.0 / D[j]) * dr : dr));
+    sm[0] += sol[j] * (0.5 * px + qj);
+  }
+  b_reduce_many<BP_NT / 64, 2, 1>(mx, sm, gp);
+  const double *g = gp + (BP_NT / 64) * 3;
+  const double pri = m == 0 ? 0.0 : g[0];
+  const double dua = unscaled ? g[1] * cinv : g[1];
+  const double obj = g[2] * (st.scaling ? cinv : 1.0);
+  // polish.c:301-311
+  const bool ok = (pri < pri0 && dua < dua0) || (pri < pri0 && dua0 < 1e-10) || (dua < dua0 && pri0 < 1e-10);
+  if (!ok) {
+    if (tid == 0) pl.stat[qp] = -1;
+    return;
+  }
+  for (int j = tid; j < n; j += BP_NT) {
+    io.Xo[qp * n + j] = st.scaling ? sol[j] * D[j] : sol[j];
+    io.Xs[qp * n + j] = sol[j];
+  }
+  for (int i = tid; i < m; i += BP_NT) {
+    io.Yo[qp * m + i] = st.scaling ? (y[i] * E[i]) * cinv : y[i];
+    io.Ys[qp * m + i] = y[i]; io.Zs[qp * m + i] = z[i];
+  }
+  if (tid == 0) {
+    double *inf = io.info + qp * 8;
+    inf[2] = obj; inf[3] = pri; inf[4] = dua;
+    pl.stat[qp] = 1;
+  }
+}
