@@ -97,6 +97,32 @@ c_int osqp_amd_batch_solve(osqp_amd_batch *b);
  * OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line when n + active rows exceeds 2176, which only the tiled engine
  * with many rows can reach. */
 c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish);
+/* Adjoint derivatives of the solution, for every member whose last solve ended OSQP_SOLVED: from dX = dl/dx
+ * [batch][n] and dY = dl/dy [batch][m] (NULL = 0; only its active rows matter) of a scalar l, the gradients
+ * dQ [batch][n], dL and dU [batch][m] and, where asked for, dPx [batch][nnzP] and dAx [batch][nnzA] on the pattern of
+ * setup (CSC order of triu(P) / A; NULL = skip; an off-diagonal slot of triu(P) stands for both halves of P).  The
+ * point differentiated is the one the handle holds: the polished one where osqp_amd_batch_polish was accepted,
+ * the ADMM iterate otherwise.  Per member, in its scaled space: the active rows as polish guesses them (lows first,
+ * then upps), the same regularised KKT matrix inverted on the device, one solve M [rx; rnu] = [dX; dY_active] with
+ * exactly polish_refine_iter refinement steps against the unregularised M = [P, Ar'; Ar, 0], then dQ = -rx,
+ * dL_i / dU_i = rnu at a row active at its lower / upper bound and 0 elsewhere, dA_ij = -(y_i rx_j + rnu_i x_j) on
+ * active rows, dP_ii = -rx_i x_i, dP_ij = -(rx_i x_j + rx_j x_i).  Where active rows are linearly dependent the
+ * multipliers are not unique and neither are dL, dU, dAx; where strict complementarity fails the solution is not
+ * differentiable and the values are those of the guessed active set.
+ * active [batch][m] (NULL = skip): -1 active at the lower bound, +1 at the upper, 0 inactive.  status_adjoint
+ * [batch] (NULL = skip): 1 computed; -1 a KKT pivot of the wrong sign (that member's outputs are 0); 0 not tried, the
+ * member's last solve did not end OSQP_SOLVED (outputs 0).  Nothing of the handle changes: X, Y, info8, the stored
+ * iterates, rho, K^-1 and the status_polish a later osqp_amd_batch_polish reports stay bit-equal.
+ * Memory: polish's KKT buffer with its cap and chunks, plus staging of the inputs and outputs, allocated at the first
+ * call (dPx / dAx at the first call that asks for them) and freed by cleanup.
+ * Returns as osqp_amd_batch_polish: 0; OSQP_WORKSPACE_NOT_INIT_ERROR when no solve has run on the current problem;
+ * OSQP_MEM_ALLOC_ERROR (the handle stays usable); OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line when
+ * n + active rows exceeds 2176 or the LDS does not fit; OSQP_DATA_VALIDATION_ERROR when dX, dQ (or, with m > 0,
+ * dL, dU) is NULL. */
+c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, const c_float *dY /*NULL = 0*/,
+                             c_float *dQ, c_float *dL, c_float *dU,
+                             c_float *dPx /*[batch][nnzP], NULL = skip*/, c_float *dAx /*[batch][nnzA], NULL = skip*/,
+                             c_int *active /*[batch][m], NULL = skip*/, c_int *status_adjoint /*[batch]*/);
 /* Results: X [batch][n], Y [batch][m] (unscaled; OSQP_NAN when infeasible),
  * info8 [batch][8] = {iter, status_val, obj_val, pri_res, dua_res, rho_updates,
  * rho_estimate, rho}; DX / DY infeasibility certificates.  NULL = skip. */

@@ -12,7 +12,15 @@ from .interface import SolverHandle, Results
 from .batch import BatchOSQP
 from .multi import solve_many
 
-__all__ = ["OSQP", "BatchOSQP", "solve_many", "abi", "lib", "build", "engine_options", "set_engine_options"]
+__all__ = ["OSQP", "BatchOSQP", "BatchQPLayer", "solve_many", "abi", "lib", "build", "engine_options", "set_engine_options"]
+
+
+def __getattr__(name):
+    # the PyTorch layer over the batch engines (osqp_amd/layer.py), imported on first use: nothing else here needs torch
+    if name == "BatchQPLayer":
+        from .layer import BatchQPLayer
+        return BatchQPLayer
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 class _Options(C.Structure):

@@ -35,6 +35,8 @@ def _bind(L):
     L.osqp_amd_batch_solve.argtypes = [H]
     L.osqp_amd_batch_polish.restype = abi.c_int
     L.osqp_amd_batch_polish.argtypes = [H, abi.c_int_p]
+    L.osqp_amd_batch_adjoint.restype = abi.c_int
+    L.osqp_amd_batch_adjoint.argtypes = [H] + [abi.c_float_p] * 7 + [abi.c_int_p] * 2
     L.osqp_amd_batch_get.restype = abi.c_int
     L.osqp_amd_batch_get.argtypes = [H, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p]
     L.osqp_amd_batch_cleanup.restype = None
@@ -85,6 +87,16 @@ def check_matrix_update(B, nnzP, nnzA, Px=None, Px_idx=None, Ax=None, Ax_idx=Non
                 raise ValueError("%sx_idx out of range [0, %d)" % (name, nnz))
         out += [V, I, int(V.ndim == 2)]
     return tuple(out)
+
+
+def check_adjoint(B, n, m, dX, dY=None):
+    """Shape checks of BatchOSQP.adjoint, as update makes them: dX [B, n], dY [B, m] or None.  Returns the arrays as
+    the C side takes them."""
+    dX = abi.as_f64(dX)
+    dY = None if dY is None else abi.as_f64(dY)
+    if dX.shape != (B, n) or (dY is not None and dY.shape != (B, m)):
+        raise ValueError("adjoint arrays must be dX [B, n], dY [B, m]")
+    return dX, dY
 
 
 class BatchOSQP:
@@ -306,6 +318,32 @@ class BatchOSQP:
                                                                         if rc == 7 else ""))
         self._status_polish = sp
         return self.results()
+
+    def adjoint(self, dX, dY=None, matrices=False):
+        """Adjoint derivatives of the solution on the device, for every member whose last solve ended `solved`: from
+        dX = dl/dx [B, n] and dY = dl/dy [B, m] (None = 0) of a scalar l, a namespace with dq [B, n], dl, du [B, m],
+        dPx [B, nnzP] and dAx [B, nnzA] (CSC order of triu(P) / A; None unless matrices=True; an off-diagonal dPx slot
+        stands for both halves of P), active [B, m] (-1 active at the lower bound, +1 at the upper, 0 inactive) and
+        status_adjoint [B]: 1 computed, -1 a KKT pivot of the wrong sign, 0 not tried (the member did not end
+        `solved`); the gradients of members that are not 1 are 0.  The point differentiated is the one the handle
+        holds: the polished one where polish() was accepted, the ADMM iterate otherwise.  Changes nothing in the
+        handle.  Needs a solve since setup or the last update."""
+        if self._many is not None:
+            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): adjoint is a call of the batch "
+                               "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
+        B, n, m = self.B, self.n, self.m
+        dX, dY = check_adjoint(B, n, m, dX, dY)
+        dq = np.zeros((B, n)); dl = np.zeros((B, max(m, 1))); du = np.zeros((B, max(m, 1)))
+        dPx = np.zeros((B, max(self.Pu.nnz, 1))) if matrices else None
+        dAx = np.zeros((B, max(self.Ah.nnz, 1))) if matrices else None
+        act = np.zeros((B, max(m, 1)), np.int64); sa = np.zeros(B, np.int64)
+        rc = self._lib.osqp_amd_batch_adjoint(self._h, abi.fptr(dX), _p(dY if m else None), abi.fptr(dq), abi.fptr(dl),
+                                              abi.fptr(du), _p(dPx), _p(dAx), abi.iptr(act), abi.iptr(sa))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_adjoint failed (%d)%s" % (rc, ": no solve has run on the current problem"
+                                                                         if rc == 7 else ""))
+        return SimpleNamespace(dq=dq, dl=dl[:, :m], du=du[:, :m], dPx=None if dPx is None else dPx[:, :self.Pu.nnz],
+                               dAx=None if dAx is None else dAx[:, :self.Ah.nnz], active=act[:, :m], status_adjoint=sa)
 
     def results(self):
         if self._many is not None:

@@ -667,6 +667,7 @@ __global__ void __launch_bounds__(1024) k_batch_order(long long B, const double 
 
 #include "batch_streamed.h"
 #include "batch_polish.h"
+#include "batch_adjoint.h"
 
 struct osqp_amd_batch {
   int engine = OSQP_AMD_BATCH_TILED;
@@ -702,6 +703,11 @@ struct osqp_amd_batch {
   int *d_plist = nullptr;   // [B] the solved members, in index order
   bool solved = false;      // the iterates and info on the device are those of a solve of the current problem
   bool polished = false;    // ... and polish has already run on them
+  // adjoint (batch_adjoint.h): staging of the inputs and outputs, allocated at the first call that needs them
+  double *adj_in = nullptr;   // [B][n + m] dl/dx, then dl/dy
+  double *adj_out = nullptr;  // [B][n + 2 m] dQ, dL, dU
+  double *adj_dP = nullptr, *adj_dA = nullptr;   // [B][nnzP], [B][nnzA]
+  int *adj_act = nullptr, *adj_stat = nullptr;   // [B][m], [B]
 };
 
 static void batch_launch(osqp_amd_batch *b, int phase);
@@ -1253,69 +1259,171 @@ extern "C" c_int osqp_amd_batch_solve(osqp_amd_batch *b) {
   return 0;
 }
 
+// the row maps, counts and status of polish and the list of solved members, allocated at the first polish or adjoint
+static int bp_reserve_maps(osqp_amd_batch *b) {
+  if (b->d_plist) return 0;
+  const size_t B = (size_t)b->B, m = (size_t)b->m;
+  BPol &pl = b->pol;
+  int rc = 0;                // each buffer once: a call that follows a failed allocation asks only for the rest
+  if (!pl.map) rc |= balloc(b, &pl.map, B * m);
+  if (!rc && !pl.rows) rc |= balloc(b, &pl.rows, B * m);
+  if (!rc && !pl.mred) rc |= balloc(b, &pl.mred, B);
+  if (!rc && !pl.nlow) rc |= balloc(b, &pl.nlow, B);
+  if (!rc && !pl.stat) rc |= balloc(b, &pl.stat, B);
+  if (!rc) rc |= balloc(b, &b->d_plist, B);
+  if (rc) { (void)hipGetLastError(); return -102; }
+  return 0;
+}
+// the KKT buffer of at least `bytes` (it only grows)
+static int bp_reserve_K(osqp_amd_batch *b, size_t bytes) {
+  BPol &pl = b->pol;
+  if (bytes <= b->pol_bytes) return 0;
+  if (pl.K) (void)hipFree(pl.K);
+  pl.K = nullptr; b->pol_bytes = 0;
+  void *k = nullptr;
+  if (hipMalloc(&k, bytes) != hipSuccess) { (void)hipGetLastError(); return -102; }
+  pl.K = static_cast<double *>(k); b->pol_bytes = bytes;
+  return 0;
+}
+
+// What polish and adjoint share before their own kernel: the active rows of every solved member (k_bp_active with
+// pl, whose stat is the caller's status array), the list of solved members on the device, the padded order NPOL,
+// the refusals, the KKT buffer and the members per chunk.  lds_of: the caller's kernel's LDS for (n, m, NPOL).
+struct BPlan { size_t count = 0, chunk = 0, lds = 0, ilds = 0; int NPOL = 0; };
+static c_int bp_plan(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_of)(int, int, int), BPlan *out) {
+  const size_t B = (size_t)b->B;
+  const int n = b->n, m = b->m;
+  hipLaunchKernelGGL(k_bp_active, dim3((unsigned)B), dim3(256), 0, b->stream, m, b->io, pl);
+  BCHK(hipGetLastError());
+  std::vector<int> h(B), list;
+  BCHK(hipMemcpyAsync(h.data(), pl.mred, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  BCHK(hipStreamSynchronize(b->stream));
+  int mmax = 0;
+  for (size_t q = 0; q < B; q++) if (h[q] >= 0) { list.push_back((int)q); mmax = std::max(mmax, h[q]); }
+  *out = BPlan{};
+  if (list.empty()) return 0;
+  const int NPOL = (n + mmax + 31) & ~31;
+  const size_t lds = lds_of(n, m, NPOL);
+  if (NPOL > BP_MAX_N || lds > 160 * 1024) {
+    fprintf(stderr, "osqp_amd batch: %s needs a KKT matrix of order n + active rows = %d (> %d) or %zu B of LDS "
+                    "(> 160 KiB) for some member\n", what, n + mmax, BP_MAX_N, lds);
+    return OSQP_LINSYS_SOLVER_INIT_ERROR;
+  }
+  const size_t per = (size_t)NPOL * NPOL * sizeof(double);
+  const size_t chunk = std::min(std::min(list.size(), (size_t)65535), std::max((size_t)1, b->pol_cap / per));
+  if (bp_reserve_K(b, chunk * per)) return OSQP_MEM_ALLOC_ERROR;
+  pl.K = b->pol.K;
+  BCHK(hipMemcpyAsync(b->d_plist, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+  BCHK(hipStreamSynchronize(b->stream));         // (list goes out of scope)
+  const size_t ilds = 4 * (size_t)NPOL * sizeof(double);
+  if (ilds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bp_invert), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ilds);
+  out->count = list.size(); out->chunk = chunk; out->lds = lds; out->ilds = ilds; out->NPOL = NPOL;
+  return 0;
+}
+static size_t bp_lds_of(int n, int m, int NPOL) { return bp_lds_bytes(n, m, NPOL); }
+static size_t ba_lds_of(int n, int m, int NPOL) { return ba_lds_bytes(n, m, NPOL); }
+
 // polish for the solved members, in chunks of at most pol_cap bytes of KKT matrices (batch_polish.h)
 extern "C" c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish) {
   if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   BCHK(hipSetDevice(b->device));
   const size_t B = (size_t)b->B;
-  const int n = b->n, m = b->m;
+  const int n = b->n;
   BPol &pl = b->pol;
-  if (!b->d_plist) {
-    int rc = 0;
-    rc |= balloc(b, &pl.map, B * m); rc |= balloc(b, &pl.rows, B * m); rc |= balloc(b, &pl.mred, B);
-    rc |= balloc(b, &pl.nlow, B); rc |= balloc(b, &pl.stat, B);
-    if (!rc) rc |= balloc(b, &b->d_plist, B);
-    if (rc) { (void)hipGetLastError(); return OSQP_MEM_ALLOC_ERROR; }
-  }
-  std::vector<int> h(B);
+  if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
   if (!b->polished) {       // (a second call without a solve in between finds the work done and reports it again)
-    hipLaunchKernelGGL(k_bp_active, dim3((unsigned)B), dim3(256), 0, b->stream, m, b->io, pl);
-    BCHK(hipGetLastError());
-    BCHK(hipMemcpyAsync(h.data(), pl.mred, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-    BCHK(hipStreamSynchronize(b->stream));
-    std::vector<int> list;
-    int mmax = 0;
-    for (size_t q = 0; q < B; q++) if (h[q] >= 0) { list.push_back((int)q); mmax = std::max(mmax, h[q]); }
-    if (!list.empty()) {
-      const int NPOL = (n + mmax + 31) & ~31;
-      const size_t lds = bp_lds_bytes(n, m, NPOL);
-      if (NPOL > BP_MAX_N || lds > 160 * 1024) {
-        fprintf(stderr, "osqp_amd batch: polish needs a KKT matrix of order n + active rows = %d (> %d) or %zu B of LDS "
-                        "(> 160 KiB) for some member\n", n + mmax, BP_MAX_N, lds);
-        return OSQP_LINSYS_SOLVER_INIT_ERROR;
-      }
-      const size_t per = (size_t)NPOL * NPOL * sizeof(double);
-      const size_t chunk = std::min(std::min(list.size(), (size_t)65535), std::max((size_t)1, b->pol_cap / per));
-      if (chunk * per > b->pol_bytes) {
-        if (pl.K) (void)hipFree(pl.K);
-        pl.K = nullptr; b->pol_bytes = 0;
-        void *k = nullptr;
-        if (hipMalloc(&k, chunk * per) != hipSuccess) { (void)hipGetLastError(); return OSQP_MEM_ALLOC_ERROR; }
-        pl.K = static_cast<double *>(k); b->pol_bytes = chunk * per;
-      }
-      BCHK(hipMemcpyAsync(b->d_plist, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
-      const size_t ilds = 4 * (size_t)NPOL * sizeof(double);
-      if (ilds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bp_invert), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ilds);
-      if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bp_polish), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      for (size_t c0 = 0; c0 < list.size(); c0 += chunk) {
-        const unsigned cnt = (unsigned)std::min(chunk, list.size() - c0);
+    BPlan pn;
+    const c_int rc = bp_plan(b, pl, "polish", bp_lds_of, &pn);
+    if (rc) return rc;
+    if (pn.count) {
+      if (pn.lds > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bp_polish), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pn.lds);
+      for (size_t c0 = 0; c0 < pn.count; c0 += pn.chunk) {
+        const unsigned cnt = (unsigned)std::min(pn.chunk, pn.count - c0);
         const int *lp = b->d_plist + c0;
-        hipLaunchKernelGGL(k_bp_form, dim3((unsigned)NPOL, cnt), dim3(256), 0, b->stream, b->pat, b->io, pl, NPOL, b->pol_delta, lp);
-        hipLaunchKernelGGL(k_bp_invert, dim3(cnt), dim3(BS_NTI), ilds, b->stream, n, pl, NPOL, lp);
-        hipLaunchKernelGGL(k_bp_polish, dim3(cnt), dim3(BP_NT), lds, b->stream, b->pat, b->st, b->io, pl, NPOL, b->pol_refine, lp);
+        hipLaunchKernelGGL(k_bp_form, dim3((unsigned)pn.NPOL, cnt), dim3(256), 0, b->stream, b->pat, b->io, pl, pn.NPOL, b->pol_delta, lp);
+        hipLaunchKernelGGL(k_bp_invert, dim3(cnt), dim3(BS_NTI), pn.ilds, b->stream, n, pl, pn.NPOL, lp);
+        hipLaunchKernelGGL(k_bp_polish, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->st, b->io, pl, pn.NPOL, b->pol_refine, lp);
         BCHK(hipGetLastError());
       }
-      BCHK(hipStreamSynchronize(b->stream));   // (list goes out of scope)
+      BCHK(hipStreamSynchronize(b->stream));
     }
     b->polished = true;
   }
   if (status_polish) {
+    std::vector<int> h(B);
     BCHK(hipMemcpyAsync(h.data(), pl.stat, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     BCHK(hipStreamSynchronize(b->stream));
     for (size_t q = 0; q < B; q++) status_polish[q] = h[q];
   }
+  return 0;
+}
+
+// adjoint derivatives for the solved members (batch_adjoint.h): polish's active rows, KKT matrix and inversion on
+// polish's buffers, in the same chunks, with a status array of its own; nothing of the solve state is written
+extern "C" c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, const c_float *dY,
+                                        c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
+                                        c_int *active, c_int *status_adjoint) {
+  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
+  BCHK(hipSetDevice(b->device));
+  const size_t B = (size_t)b->B;
+  const int n = b->n, m = b->m;
+  if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
+  {                          // staging, each buffer once: a call that follows a failed allocation asks only for the rest
+    int rc = 0;
+    if (!b->adj_in) rc |= balloc(b, &b->adj_in, B * (n + m));
+    if (!rc && !b->adj_out) rc |= balloc(b, &b->adj_out, B * (n + 2 * (size_t)m));
+    if (!rc && !b->adj_act) rc |= balloc(b, &b->adj_act, B * m);
+    if (!rc && !b->adj_stat) rc |= balloc(b, &b->adj_stat, B);
+    if (!rc && dPx && !b->adj_dP) rc |= balloc(b, &b->adj_dP, B * b->nnzP);
+    if (!rc && dAx && !b->adj_dA) rc |= balloc(b, &b->adj_dA, B * b->nnzA);
+    if (rc) { (void)hipGetLastError(); return OSQP_MEM_ALLOC_ERROR; }
+  }
+  BPol pl = b->pol;          // polish's buffers; its status array stays polish's
+  pl.stat = b->adj_stat;
+  BAdj ad{};
+  double *gx = b->adj_in, *gy = b->adj_in + B * n;
+  ad.gx = gx; ad.gy = (dY && m) ? gy : nullptr;
+  ad.dQ = b->adj_out; ad.dL = ad.dQ + B * n; ad.dU = ad.dL + B * m;
+  ad.dPx = dPx ? b->adj_dP : nullptr; ad.dAx = dAx ? b->adj_dA : nullptr;
+  ad.active = b->adj_act;
+  BCHK(hipMemcpyAsync(gx, dX, B * n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  if (ad.gy) BCHK(hipMemcpyAsync(gy, dY, B * m * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  // members that are skipped or rejected report zeros
+  BCHK(hipMemsetAsync(b->adj_out, 0, std::max((size_t)1, B * (n + 2 * (size_t)m)) * sizeof(double), b->stream));
+  BCHK(hipMemsetAsync(b->adj_act, 0, std::max((size_t)1, B * m) * sizeof(int), b->stream));
+  if (ad.dPx) BCHK(hipMemsetAsync(ad.dPx, 0, std::max((size_t)1, B * b->nnzP) * sizeof(double), b->stream));
+  if (ad.dAx) BCHK(hipMemsetAsync(ad.dAx, 0, std::max((size_t)1, B * b->nnzA) * sizeof(double), b->stream));
+  BPlan pn;
+  const c_int rc = bp_plan(b, pl, "adjoint", ba_lds_of, &pn);
+  if (rc) return rc;
+  if (pn.count) {
+    if (pn.lds > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ba_adjoint), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pn.lds);
+    for (size_t c0 = 0; c0 < pn.count; c0 += pn.chunk) {
+      const unsigned cnt = (unsigned)std::min(pn.chunk, pn.count - c0);
+      const int *lp = b->d_plist + c0;
+      hipLaunchKernelGGL(k_bp_form, dim3((unsigned)pn.NPOL, cnt), dim3(256), 0, b->stream, b->pat, b->io, pl, pn.NPOL, b->pol_delta, lp);
+      hipLaunchKernelGGL(k_bp_invert, dim3(cnt), dim3(BS_NTI), pn.ilds, b->stream, n, pl, pn.NPOL, lp);
+      hipLaunchKernelGGL(k_ba_adjoint, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
+      BCHK(hipGetLastError());
+    }
+  }
+  BCHK(hipMemcpyAsync(dQ, ad.dQ, B * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  if (m) {
+    BCHK(hipMemcpyAsync(dL, ad.dL, B * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    BCHK(hipMemcpyAsync(dU, ad.dU, B * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  }
+  if (dPx && b->nnzP) BCHK(hipMemcpyAsync(dPx, ad.dPx, B * b->nnzP * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  if (dAx && b->nnzA) BCHK(hipMemcpyAsync(dAx, ad.dAx, B * b->nnzA * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  std::vector<int> ha(active ? B * m : 0), hs(B);
+  if (active && m) BCHK(hipMemcpyAsync(ha.data(), b->adj_act, B * m * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  if (status_adjoint) BCHK(hipMemcpyAsync(hs.data(), b->adj_stat, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  BCHK(hipStreamSynchronize(b->stream));
+  for (size_t k = 0; k < ha.size(); k++) active[k] = ha[k];
+  if (status_adjoint) for (size_t q = 0; q < B; q++) status_adjoint[q] = hs[q];
   return 0;
 }
 
