@@ -101,8 +101,8 @@ int hipeng_upload_matrices(hipeng *e, const csc *P, const csc *A);
  * keep; z is recomputed as A x on the device when x is given. */
 int hipeng_cold_start(hipeng *e);
 int hipeng_set_iterates(hipeng *e, const c_float *x, const c_float *y);
-/* overwrite z (and the PCG's z~ warm-start image) -- used when polish adopts
- * its (x, z, y) (src/polish.c:321-325) */
+/* overwrite z; the PCG's warm-start image z~ = A x~ left by hipeng_set_iterates stays -- used when polish adopts
+ * its (x, z, y) (src/polish.c:321-325) or puts the ADMM iterates back */
 int hipeng_set_z(hipeng *e, const c_float *z);
 
 /* Run `count` ADMM iterations (osqp.c:356-370: swap, update_xz_tilde,

@@ -3932,7 +3932,7 @@ extern "C" int hipeng_set_z(hipeng *e, const c_float *z) {
   const int m = e->m;
   if (m > 0 && z) {
     if (upload_vec(e, e->c.z, z, m)) return HIPENG_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(e->c.zt, e->c.z, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    // (z~ stays A x~: k_pcg_init takes the start vector's m-part for rho A x~0, whatever z is)
     hipLaunchKernelGGL(k_refresh_m, dim3(elem_grid(m)), dim3(TB), 0, e->stream, e->c, 0); e->start_dirty = true;
     HIPCHK(hipGetLastError());
   }

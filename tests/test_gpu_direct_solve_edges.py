@@ -18,158 +18,21 @@ Each solve prints its form, route and ratio (error / bar) for the record (pytest
 The refresh that drives the dense-direct engine off its direct form (cond 9e11, sigma 1e-10) asserts only that it left: the PCG
 kernels it drops to reach no better than a relative residual of 0.3 there, far from the 1e-9 of the fallback bar; that leg is
 left open."""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 from scipy import sparse
 
-from tests._kkt_reference import KKTReference, reduced_matrix
+from tests._hipeng import Engine
+from tests._kkt_reference import reduced_matrix
 
 pytestmark = pytest.mark.gpu
 
 RHO, RHO_MIN, EQ = 0.1, 1e-6, 1e3
-SIGMA = 1e-6
-PCG_STOP = 1e-10
 SWEEP, CHOL = 0, 1
-
-
-class HipengParams(C.Structure):          # include/osqp_amd_engine.h: hipeng_params
-    _fields_ = [("sigma", C.c_double), ("alpha", C.c_double), ("pcg_eps_rel", C.c_double), ("pcg_eps_abs", C.c_double),
-                ("pcg_max_iter", C.c_longlong), ("no_restart", C.c_longlong)]
-
-
-class _env:
-    def __init__(self, **kw): self.kw = kw
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        for k, v in self.kw.items():
-            os.environ[k] = str(v)
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 DD_ENV = dict(OSQP_AMD_RESIDENT=0, OSQP_AMD_DENSE_DIRECT=2)        # dense-direct whatever the size (block forms off)
 BD_ENV = dict(OSQP_AMD_BLOCK_DIRECT=1)
-
-
-def _lib():
-    import osqp_amd
-    from osqp_amd import _abi
-    L = osqp_amd.lib()
-    vp, fp = C.c_void_p, _abi.c_float_p
-    for name, args in (("hipeng_create", [C.POINTER(vp), C.POINTER(_abi.csc), C.POINTER(_abi.csc), fp, fp, fp, fp, C.POINTER(HipengParams), C.c_int]),
-                       ("hipeng_kkt_solve", [vp, fp]), ("hipeng_kkt_solve_unrefined", [vp, fp]), ("hipeng_upload_rho", [vp, fp]),
-                       ("hipeng_upload_matrices", [vp, C.POINTER(_abi.csc), C.POINTER(_abi.csc)]),
-                       ("hipeng_set_params", [vp, C.POINTER(HipengParams)]), ("hipeng_resident_info", [vp, C.POINTER(C.c_longlong)])):
-        f = getattr(L, name)
-        f.restype, f.argtypes = C.c_int, args
-    L.hipeng_destroy.restype, L.hipeng_destroy.argtypes = None, [vp]
-    L.hipeng_elim_count.restype, L.hipeng_elim_count.argtypes = C.c_longlong, [vp]
-    return L
-
-
-class Engine:
-    """One hipeng on device 0 and the refined reference of its current (P, A, sigma, rho)."""
-
-    def __init__(self, Pu, A, rho, sigma=SIGMA, env=None):
-        from osqp_amd import _abi
-        self.L, self.abi = _lib(), _abi
-        self.n, self.m = Pu.shape[0], A.shape[0]
-        self.Pu, self.A, self.rho, self.sigma = sparse.csc_matrix(Pu), sparse.csc_matrix(A), np.asarray(rho, float), sigma
-        self._hold = [_abi.CscHolder(self.Pu), _abi.CscHolder(self.A)]
-        self.prm = HipengParams(sigma, 1.6, PCG_STOP, 1e-15, max(20000, 10 * self.n), 0)
-        r = _abi.as_f64(self.rho)
-        self.h = C.c_void_p()
-        with _env(**(env or {})):
-            rc = self.L.hipeng_create(C.byref(self.h), C.byref(self._hold[0].struct), C.byref(self._hold[1].struct), None, None, None,
-                                      _abi.fptr(r), C.byref(self.prm), 0)
-        assert rc == 0, rc
-        self.ref = None
-
-    def close(self):
-        if self.h:
-            self.L.hipeng_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def info(self):
-        out = (C.c_longlong * 16)()
-        assert self.L.hipeng_resident_info(self.h, out) == 0
-        return list(out)
-
-    def elim(self):
-        return int(self.L.hipeng_elim_count(self.h))
-
-    def set_rho(self, rho):
-        self.rho = np.asarray(rho, float)
-        r = self.abi.as_f64(self.rho)
-        assert self.L.hipeng_upload_rho(self.h, self.abi.fptr(r)) == 0
-        self.ref = None
-
-    def set_sigma(self, sigma):
-        self.sigma = self.prm.sigma = sigma
-        assert self.L.hipeng_set_params(self.h, C.byref(self.prm)) == 0
-        self.ref = None
-
-    def set_matrices(self, Pu, A):
-        Pu, A = sparse.csc_matrix(Pu), sparse.csc_matrix(A)
-        hp, ha = self.abi.CscHolder(Pu), self.abi.CscHolder(A)
-        assert (hp.nnz, ha.nnz) == (self._hold[0].nnz, self._hold[1].nnz)
-        assert self.L.hipeng_upload_matrices(self.h, C.byref(hp.struct), C.byref(ha.struct)) == 0
-        self.Pu, self.A, self._hold = Pu, A, [hp, ha]
-        self.ref = None
-
-    def reference(self):
-        if self.ref is None:
-            self.ref = KKTReference(self.Pu, self.A, self.sigma, self.rho)
-        return self.ref
-
-    def solve(self, b, refined=True):
-        out = self.abi.as_f64(b).copy()
-        f = self.L.hipeng_kkt_solve if refined else self.L.hipeng_kkt_solve_unrefined
-        assert f(self.h, self.abi.fptr(out)) == 0
-        return out
-
-    def check(self, tag, form, route=None, seed=0, nrhs=2):
-        """Assert the form (and, where given, the route) in use, then the bar for it on nrhs right-hand sides; returns the worst
-        ratio.  Where no route is given, which one serves depends on how far the sweeps' inverse is off its probes -- close to the
-        thresholds on well-conditioned systems, and the formation of S sums with atomics -- and the bar holds on either."""
-        inf = self.info()
-        if isinstance(form, (set, tuple)):
-            assert inf[9] in form, (tag, inf)
-        else:
-            assert inf[9] == form, (tag, "form", inf[9], "expected", form, inf)
-        if route is not None and inf[9] == 4:
-            assert inf[5] == route, (tag, "route", inf[5], "expected", route)
-        ref = self.reference()
-        rng = np.random.default_rng(seed)
-        worst = 0.0
-        for k in range(nrhs):
-            b = rng.standard_normal(self.n + self.m) * (1.0 if k == 0 else rng.uniform(0.1, 10.0, self.n + self.m))
-            _, _, plain = ref.solve(b)
-            for refined in (False, True):
-                out = self.solve(b, refined)
-                if inf[9] in (3, 4):
-                    err = ref.forward_error(out)
-                    yard = plain if refined else ref.inverse_error(b)
-                    bar = 10.0 * yard + 1e-14
-                    what = f"fwd {err:.2e} {'numpy' if refined else 'inv(K)'} {yard:.2e}"
-                else:
-                    err = ref.residual(out[: self.n], b)
-                    bar = 10.0 * PCG_STOP
-                    what = f"res {err:.2e}"
-                ratio = err / bar
-                worst = max(worst, ratio)
-                route_s = "" if inf[9] != 4 else (" chol" if inf[5] else " sweep")
-                kind = "refined" if refined else "unrefined"
-                print(f"[direct-edges] {tag}: {kind} form {inf[9]}{route_s} n3={inf[3]} n15={inf[15]} {what} ratio {ratio:.3f}")
-                assert err <= bar, (tag, kind, inf[9], inf[5], err, bar, plain)
-        return worst
 
 
 def _classes(m, rng, eq=0.3, loose=0.2):
