@@ -61,10 +61,26 @@ osqp_amd_rp *osqp_amd_rp_create(void *shard_engine, const double *q, const doubl
  * (osqp_amd_rp_rccl_unique_id), the same on every rank.  Collective: every rank calls it.  (NULL, 0) detaches again. */
 int  osqp_amd_rp_rccl_unique_id(void *out, int cap_bytes);          /* returns the number of bytes written, < 0 on error */
 int  osqp_amd_rp_use_rccl(osqp_amd_rp *rp, const void *unique_id, int id_bytes);
+/* A handle starts from zero iterates and settings->rho.  Every later solve on the same handle continues as the reference's
+ * osqp_solve does on one workspace: from the iterates x, x~, z, y the previous solve left, with the rho that solve ended on
+ * (not settings->rho), and info->rho_updates counts on across solves; rho per row and the preconditioner are built at
+ * the first solve and again only when rho changes.  A PCG solve that meets p'Kp <= 0 (K not positive definite: the problem
+ * is not convex) ends the call with HIPENG_ERR_ARG; the handle can still be freed. */
 int  osqp_amd_rp_solve(osqp_amd_rp *rp, osqp_amd_rp_info *info);
 /* x: n doubles (unscaled, the same on every rank); y_loc: m_loc doubles (unscaled duals of this rank's rows) */
 int  osqp_amd_rp_get_solution(osqp_amd_rp *rp, double *x, double *y_loc);
 void osqp_amd_rp_free(osqp_amd_rp *rp);
+
+/* ---- for the tests ---- */
+/* One array of the handle's state, in the scaled space the loop iterates in: synchronises the engine's stream, copies the
+ * array to out[0, count) and returns count, or a negative HIPENG_ERR_* code (cap < count, unknown `which`).  Nothing is
+ * written on the device.  x, x~, minv, b, r: n doubles (r: the last PCG residual); z, y, rho per row: m_loc doubles;
+ * SC15: the fifteen scalars of the last termination check as the device left them (maxima of the rank's rows first:
+ * pri_u z_u Ax_u pri_s z_s Ax_s | dua_u dua_s q_u q_s Aty_u Aty_s Px_u Px_s x'(Px/2 + q); _u: unscaled with Einv / Dinv);
+ * S: the PCG's device-side record as nine doubles: rz[0] rz[1] rr tol2 bb done iters cap bad. */
+enum { OSQP_AMD_RP_PEEK_X = 0, OSQP_AMD_RP_PEEK_XT, OSQP_AMD_RP_PEEK_Z, OSQP_AMD_RP_PEEK_Y, OSQP_AMD_RP_PEEK_RHO_VEC, OSQP_AMD_RP_PEEK_MINV,
+       OSQP_AMD_RP_PEEK_B, OSQP_AMD_RP_PEEK_R, OSQP_AMD_RP_PEEK_SC15, OSQP_AMD_RP_PEEK_S };
+int  osqp_amd_rp_peek(osqp_amd_rp *rp, int which, double *out, long long cap);
 
 #ifdef __cplusplus
 }

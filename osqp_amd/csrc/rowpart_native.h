@@ -201,6 +201,7 @@ struct osqp_amd_rp {
   double *h15 = nullptr;
   long long collectives = 0, pcg_iters = 0;
   int last_iters = 4, rho_updates = 0;
+  bool rho_set = false;                                                             // rv and minv hold rp->rho (false until the first solve)
   double sc[15];
 };
 
@@ -340,8 +341,13 @@ extern "C" int osqp_amd_rp_solve(osqp_amd_rp *rp, osqp_amd_rp_info *info) {
   if (rp->has_eq) eps_pcg = std::max(1e-13, 1e-3 * eps_pcg);
   const int interval = st.adaptive_rho_interval ? st.adaptive_rho_interval : (st.check_termination ? 4 * st.check_termination : 100);
   const int cap = st.pcg_max_iter ? st.pcg_max_iter : std::max(20000, 10 * n);
-  rp->pcg_iters = 0; rp->collectives = 0; rp->rho_updates = 0;
-  if (int rc = rp_set_rho(rp, st.rho)) return rc;
+  rp->pcg_iters = 0; rp->collectives = 0;
+  // the first solve builds rho per row and the preconditioner from the setting; a later one starts from the kept iterates with the
+  // rho the previous solve ended on, and rho_updates counts on (osqp_solve keeps work->settings->rho and info->rho_updates)
+  if (!rp->rho_set) {
+    if (int rc = rp_set_rho(rp, st.rho)) return rc;
+    rp->rho_set = true;
+  }
   int status = 0, it = 0;
   bool checked = false;
   double pri_res = 0.0, dua_res = 0.0;
@@ -421,6 +427,32 @@ extern "C" int osqp_amd_rp_get_solution(osqp_amd_rp *rp, double *x, double *y_lo
   }
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
+}
+
+// ---- for the tests: one array of the handle's state on the host (reads only) ----
+extern "C" int osqp_amd_rp_peek(osqp_amd_rp *rp, int which, double *out, long long cap) {
+  if (!rp || !out) return HIPENG_ERR_ARG;
+  hipeng *e = rp->e;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const double *nsrc[] = {rp->x, rp->xt, nullptr, nullptr, nullptr, rp->minv, rp->b, rp->r};
+  const double *msrc[] = {nullptr, nullptr, rp->z, rp->y, rp->rv, nullptr, nullptr, nullptr};
+  if (which == OSQP_AMD_RP_PEEK_S) {
+    if (cap < 9) return HIPENG_ERR_ARG;
+    RpS s;
+    HIPCHK(hipMemcpy(&s, rp->S, sizeof(RpS), hipMemcpyDeviceToHost));
+    const double v[9] = {s.rz[0], s.rz[1], s.rr, s.tol2, s.bb, (double)s.done, (double)s.iters, (double)s.cap, (double)s.bad};
+    memcpy(out, v, sizeof(v));
+    return 9;
+  }
+  const double *src = nullptr;
+  long long count = 0;
+  if (which == OSQP_AMD_RP_PEEK_SC15) { src = rp->sc15; count = 15; }
+  else if (which >= 0 && which < 8) { src = nsrc[which] ? nsrc[which] : msrc[which]; count = nsrc[which] ? rp->n : rp->m; }
+  else return HIPENG_ERR_ARG;
+  if (cap < count) return HIPENG_ERR_ARG;
+  if (count > 0) HIPCHK(hipMemcpy(out, src, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+  return (int)count;
 }
 
 extern "C" void osqp_amd_rp_free(osqp_amd_rp *rp) {

@@ -438,6 +438,7 @@ class NativeRowPartitionedOSQP:
         L.osqp_amd_rp_free.restype = None; L.osqp_amd_rp_free.argtypes = [C.c_void_p]
         L.osqp_amd_rp_rccl_unique_id.restype = C.c_int; L.osqp_amd_rp_rccl_unique_id.argtypes = [C.c_void_p, C.c_int]
         L.osqp_amd_rp_use_rccl.restype = C.c_int; L.osqp_amd_rp_use_rccl.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.osqp_amd_rp_peek.restype = C.c_int; L.osqp_amd_rp_peek.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
         L.hipeng_sync.restype = C.c_int; L.hipeng_sync.argtypes = [C.c_void_p]
 
     def _group_allreduce(self, user, buf, count, op, stream):
@@ -555,6 +556,20 @@ class NativeRowPartitionedOSQP:
         ns = SimpleNamespace(status=_STATUS.get(info.status, "unsolved"), iter=info.iter, obj_val=info.obj_val, pri_res=info.pri_res, dua_res=info.dua_res,
                              rho_updates=info.rho_updates, rho_estimate=info.rho_estimate, pcg_iters=info.pcg_iters, collectives=info.collectives)
         return SimpleNamespace(x=x, y=y, info=ns)
+
+    _PEEK = ("x", "xt", "z", "y", "rv", "minv", "b", "r", "sc15", "S")
+    _S_FIELDS = ("rz0", "rz1", "rr", "tol2", "bb", "done", "iters", "cap", "bad")
+
+    def peek(self, name):
+        """For the tests (osqp_amd_rp_peek): one array of the handle's state in the scaled space, copied to the host; nothing
+        is written on the device.  "S": the PCG's device-side record as a dict."""
+        which = self._PEEK.index(name)
+        cap = {"sc15": 15, "S": 9}.get(name, max(self.n, self.r1 - self.r0, 1))
+        out = np.zeros(cap)
+        k = self._L.osqp_amd_rp_peek(self._rp, which, out.ctypes.data_as(C.c_void_p), cap)
+        if k < 0:
+            raise RuntimeError("osqp_amd_rp_peek failed (%d)" % k)
+        return dict(zip(self._S_FIELDS, out[:k])) if name == "S" else out[:k].copy()
 
     def cleanup(self):
         if self._rp:

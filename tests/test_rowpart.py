@@ -46,6 +46,43 @@ def test_row_partition_two_ranks_cpu_matches_oracle(tmp_path, oracle_mod, which)
     assert int(r["collectives"]) <= int(r["pcg_iters"]) + 2 * int(r["iter"]) + 3 * (int(r["iter"]) // 25 + 1) + 3 * (int(r["rho_updates"]) + 2)
 
 
+def _check_edges(tmp_path, oracle_mod, mode):
+    """The edge problems of tests/_rowpart_reference.py in ONE spawn of two ranks (and one of three for the empty shard of P): the bars of
+    the tests above -- status, iter, rho_updates equal to the oracle's, x and y to 1e-6, objective to 1e-8 -- and every rank's x and
+    info record equal to rank 0's bit for bit (the design's claim that all ranks take the same decisions)."""
+    import _rowpart_reference as R
+    for world, names in ((2, R.EDGE_WORLD2), (3, R.EDGE_WORLD3)):
+        r = _run(tmp_path, mode, "list:" + ",".join(names), world=world)
+        for name in names:
+            pb = R.edge_problem(name)
+            ro = oracle_mod.OracleOSQP().setup(**pb, **R.EDGE_SETTINGS).solve()
+            g = lambda k: r[name + "/" + k]
+            rows = [tuple(int(v) for v in ab) for ab in g("rows")]
+            assert int(g("world")) == world and len(rows) == world
+            if name == "dense_last_row":
+                assert rows == [(0, 4), (4, 4)]                                   # rank 1 has no rows
+            if name == "eq_on_rank1":
+                eq = pb["u"] - pb["l"] < 1e-4
+                assert not eq[rows[0][0]:rows[0][1]].any() and eq[rows[1][0]:rows[1][1]].any()
+            assert str(g("status")) == ro.info.status == "solved", name
+            assert int(g("iter")) == ro.info.iter and int(g("rho_updates")) == ro.info.rho_updates, name
+            assert _rel(g("x"), ro.x) < 1e-6 and (ro.y.size == 0 or _rel(g("y"), ro.y) < 1e-6), name
+            assert abs(float(g("obj")) - ro.info.obj_val) <= 1e-8 * max(1.0, abs(ro.info.obj_val)), name
+            assert bool(g("ranks_equal")), name
+
+
+def test_row_partition_edge_shards_cpu(tmp_path, oracle_mod):
+    """A rank with no rows, equality rows on one rank only, no rows at all; three ranks with an empty shard of P: the collective logic
+    with scipy SpMVs."""
+    _check_edges(tmp_path, oracle_mod, "cpu")
+
+
+@pytest.mark.gpu
+def test_native_row_partition_edge_shards_gpu(gpu_lib, tmp_path, oracle_mod):
+    """The same through osqp_amd_rp_solve: shard engines without rows or without entries of P, has_eq_any from the other rank, m_total = 0."""
+    _check_edges(tmp_path, oracle_mod, "native")
+
+
 @pytest.mark.gpu
 def test_row_partition_two_ranks_gpu_matches_oracle(gpu_lib, tmp_path, oracle_mod):
     from osqp_amd.problems import portfolio_qp
