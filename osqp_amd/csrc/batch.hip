@@ -75,11 +75,25 @@ struct BIO {               // per-batch arrays (device)
   double *Wd, *We, *Wc;    // D [B][n], E [B][m], c [B]
   double *Wk;              // [B][NP*NP] K^-1 in per-thread tile order
   int    *Wt;              // [B][m] constraint class
-  int    *flag;            // [B] 1 = K^-1 must be rebuilt (constraint class changed); 2, 4: refinement
-                           // verdict; 8 (setup phase only): K was not positive definite
+  int    *flag;            // [B] BF_* bits
   double *info;            // [B][8]: iter, status, obj, pri, dua, rho_updates, rho_estimate, rho
   const int *order;        // [B] solve phase: workgroup k works on QP order[k] (longest expected first)
 };
+
+// The bits of io.flag[qp].  Every writer stores the whole word, so a bit it does not name is cleared.
+//   BF_REBUILD  K^-1 no longer matches rho or the row classes.  Set by k_batch_update (a class changed),
+//               k_batch_update_rho, the streamed setup (store_workspace) and a streamed member whose rho moved
+//               (StreamedK::leave, k_bs_loop's store_solution); cleared by the rebuild: k_bs_invert, or the tiled
+//               solve phase, which rebuilds on entry and stores the word without it.
+//   BF_REFINE   the member's K solves take a refinement step.  Set or cleared by the probe of admm_loop and stored
+//               by store_solution; kept by k_bs_invert and StreamedK::leave; dropped by whoever sets BF_REBUILD alone.
+//   BF_OPEN     the refinement verdict is still to be taken.  Set with every new K^-1 (tiled setup and
+//               matrix-update phases, k_bs_invert; the tiled solve phase also reads BF_REBUILD as it); cleared
+//               by the first probe of admm_loop.
+//   BF_NOT_PD   a pivot of K was not positive.  Set by the tiled setup and matrix-update phases and by k_bs_invert,
+//               read by the host right after setup or a matrix update; cleared by the next store of the word.
+// osqp_amd_batch_rounds counts BF_REFINE; the values are part of what the tests read.
+enum { BF_REBUILD = 1, BF_REFINE = 2, BF_OPEN = 4, BF_NOT_PD = 8 };
 
 // ---------------------------------------------------------------------------
 // workgroup helpers
@@ -506,8 +520,7 @@ __global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k
     set_rho_vectors<NT>(s, rho);
     __syncthreads();
     const bool notpd = rebuild_kinv<TR, TC, GC>(p.n, s, st.sigma, Wk);
-    // 4: verdict on refinement still open; 8: K not positive definite (read by the host after the launch)
-    store_workspace<NT, false>(s, p, io, qp, cs, rho, notpd ? 4 | 8 : 4);
+    store_workspace<NT, false>(s, p, io, qp, cs, rho, notpd ? BF_OPEN | BF_NOT_PD : BF_OPEN);
     return;
   }
   if (PH == 2) {
@@ -519,7 +532,7 @@ __global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k
     set_rho_vectors<NT>(s, rho);
     __syncthreads();
     const bool notpd = rebuild_kinv<TR, TC, GC>(p.n, s, st.sigma, Wk);
-    store_workspace<NT, false, false>(s, p, io, qp, cs, rho, notpd ? 4 | 8 : 4);
+    store_workspace<NT, false, false>(s, p, io, qp, cs, rho, notpd ? BF_OPEN | BF_NOT_PD : BF_OPEN);
     return;
   }
   TiledK<TR, TC, GC> eng;
@@ -531,17 +544,17 @@ __global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k
   init_iterates<NT>(s, p, io, qp, a.rho, st.warm_start);
   DBG(dbg.tstamp[3] = wall_clock64();)
   // refinement is applied only to QPs whose K^-1 left a relative residual above refine_tol in the
-  // first solves after it was (re)built; the verdict is kept in bit 1 of flag[]
+  // first solves after it was (re)built; the verdict is kept in BF_REFINE
   const int qflag = io.flag[qp];
-  a.need_refine = (qflag & 2) != 0;
-  a.check_pending = (qflag & 5) != 0;
-  if (qflag & 1) rebuild_kinv<TR, TC, GC>(p.n, s, st.sigma, Wk);   // (the verdict on K is dropped: not covered in-loop)
+  a.need_refine = (qflag & BF_REFINE) != 0;
+  a.check_pending = (qflag & (BF_REBUILD | BF_OPEN)) != 0;
+  if (qflag & BF_REBUILD) rebuild_kinv<TR, TC, GC>(p.n, s, st.sigma, Wk);   // (the verdict on K is dropped: not covered in-loop)
   DBG(dbg.tstamp[4] = wall_clock64();)
   load_kinv<NP, NT>(eng.ag, Wk);
   DBG(dbg.tstamp[5] = wall_clock64();)
   admm_loop<NT, true>(s, p, st, io, qp, a, 0, eng, dbg);
   DBG(dbg.tstamp[6] = wall_clock64();)
-  store_solution<NT>(s, p, st, io, qp, a, a.check_pending ? 4 : (a.need_refine ? 2 : 0));
+  store_solution<NT>(s, p, st, io, qp, a, a.check_pending ? BF_OPEN : (a.need_refine ? BF_REFINE : 0));
   DBG(if (st.profile && tid == 0) {
     const int n = p.n;
     dbg.tstamp[7] = wall_clock64();
@@ -577,7 +590,7 @@ __global__ void __launch_bounds__(256) k_batch_update(int n, int m, BIO io, cons
     }
   }
   __syncthreads();
-  if (threadIdx.x == 0 && changed) io.flag[qp] = 1;   // rebuild; the refinement verdict is re-taken after it
+  if (threadIdx.x == 0 && changed) io.flag[qp] = BF_REBUILD;   // the refinement verdict is re-taken after the rebuild
   if (threadIdx.x == 0) io.info[qp * 8 + 5] = 0.0;      // reset_info: rho_updates (src/auxil.c:647)
 }
 
@@ -598,7 +611,7 @@ __global__ void __launch_bounds__(256) k_batch_update_rho(long long B, BIO io, c
   const long long qp = (long long)blockIdx.x * 256 + threadIdx.x;
   if (qp >= B) return;
   io.rho_io[qp] = fmin(fmax(rho[per_member ? qp : 0], 1e-6), 1e6);
-  io.flag[qp] = 1;
+  io.flag[qp] = BF_REBUILD;
 }
 
 // osqp_warm_start / _x / _y for every QP (osqp.c:942-1010): x = D^-1 x, z = A x with the scaled A, y = c E^-1 y.
@@ -729,6 +742,35 @@ static int bupload(osqp_amd_batch *b, const Tp **dst, const std::vector<Tp> &src
   if (!src.empty()) BCHK(hipMemcpyAsync(d, src.data(), src.size() * sizeof(Tp), hipMemcpyHostToDevice, b->stream));
   *dst = d;
   return 0;
+}
+
+// *p once: a call that follows a failed allocation asks only for what is still missing
+template <typename Tp>
+static int balloc_once(osqp_amd_batch *b, Tp **p, size_t cnt) { return *p ? 0 : balloc(b, p, cnt); }
+
+// A kernel may use more than 64 KiB of dynamic LDS only after its limit was raised.  The limit is a property of the
+// kernel function on the current device, not of a batch: another handle of another size may have set it to its own,
+// smaller value since.  So it is set before every launch that needs it.
+static void set_dynamic_lds(const void *fn, size_t bytes) {
+  if (bytes > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+#define KFN(k) reinterpret_cast<const void *>(&k)
+
+// io.flag of every member as the launches queued so far leave it
+static int read_flags(osqp_amd_batch *b, std::vector<int> &h) {
+  h.resize((size_t)b->B);
+  BCHK(hipGetLastError());
+  BCHK(hipMemcpyAsync(h.data(), b->io.flag, h.size() * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  BCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+// the first member whose K was not positive definite (BF_NOT_PD), B when there is none, -1 after a HIP error
+static long long first_not_pd(osqp_amd_batch *b) {
+  std::vector<int> h;
+  if (read_flags(b, h)) return -1;
+  long long q = 0;
+  while (q < b->B && !(h[q] & BF_NOT_PD)) q++;
+  return q;
 }
 
 static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
@@ -927,22 +969,15 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
   // setup phase on the device: Ruiz scaling, rho classes, K^-1 (one workgroup per QP)
   if (streamed) (void)bs_setup_launch(b, false);
   else batch_launch(b, 0);
-  std::vector<int> hflag(B);
-  if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(hflag.data(), io.flag, B * sizeof(int), hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
-      hipStreamSynchronize(b->stream) != hipSuccess) {
-    osqp_amd_batch_cleanup(b);
-    return OSQP_LINSYS_SOLVER_INIT_ERROR;
-  }
   // a non-positive Gauss-Jordan pivot: K = P + sigma I + A' rho A is not positive definite, which
   // the reference's LDL' inertia check rejects at osqp_setup (qdldl_interface.c:93-99)
-  for (size_t q = 0; q < B; q++)
-    if (hflag[q] & 8) {
-      fprintf(stderr, "osqp_amd batch: QP %zu of the batch is non-convex (K = P + sigma I + A' rho A is not "
-                      "positive definite)\n", q);
-      osqp_amd_batch_cleanup(b);
-      return OSQP_NONCVX_ERROR;
-    }
+  const long long bad = first_not_pd(b);
+  if (bad != batch) {
+    if (bad >= 0) fprintf(stderr, "osqp_amd batch: QP %zu of the batch is non-convex (K = P + sigma I + A' rho A is not "
+                                  "positive definite)\n", (size_t)bad);
+    osqp_amd_batch_cleanup(b);
+    return bad < 0 ? OSQP_LINSYS_SOLVER_INIT_ERROR : OSQP_NONCVX_ERROR;
+  }
   *out = b;
   return 0;
 }
@@ -1024,15 +1059,6 @@ static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, cons
   return rc ? OSQP_MEM_ALLOC_ERROR : 0;
 }
 
-// The dynamic-LDS limit of the streamed setup and loop kernels, set on the current device before every launch
-// (a batch of another size may have changed it since).
-static void bs_set_lds(osqp_amd_batch *b) {
-  if (b->lds_bytes <= 64 * 1024) return;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bs_setup<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bs_setup<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bs_loop), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes);
-}
-
 // form and invert K for the members of list[0..count) (the whole batch when list is null) that have a rebuild due
 static void bs_rebuild(osqp_amd_batch *b, const int *list, long long count) {
   hipLaunchKernelGGL(k_bs_form, dim3((unsigned)b->NPs, (unsigned)count), dim3(256), 0, b->stream,
@@ -1042,25 +1068,26 @@ static void bs_rebuild(osqp_amd_batch *b, const int *list, long long count) {
 
 // update = true: the re-equilibration of a matrix update; K is re-formed and re-inverted for every member either way
 static int bs_setup_launch(osqp_amd_batch *b, bool update) {
-  bs_set_lds(b);
-  if (update) hipLaunchKernelGGL(k_bs_setup<true>, dim3((unsigned)b->B), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, b->NPs);
-  else hipLaunchKernelGGL(k_bs_setup<false>, dim3((unsigned)b->B), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, b->NPs);
+  const void *fn = update ? KFN(k_bs_setup<true>) : KFN(k_bs_setup<false>);
+  int NP = b->NPs;
+  void *args[] = {&b->pat, &b->st, &b->io, &NP};
+  set_dynamic_lds(fn, b->lds_bytes);
+  (void)hipLaunchKernel(fn, dim3((unsigned)b->B), dim3(BS_NT), args, b->lds_bytes, b->stream);
   bs_rebuild(b, nullptr, b->B);
   return 0;
 }
 
-// One solve of the streamed engine: rounds of the ADMM loop.  Round 0 runs every member; a member whose rho
+// The streamed engine's part of a solve: rounds of the ADMM loop.  Round 0 runs every member; a member whose rho
 // moves leaves with a rebuild request, and the next round re-forms and re-inverts K for those members and
 // resumes them.  One counter is read back per round; rounds <= rho updates of the slowest member + 1.
 static int bs_solve(osqp_amd_batch *b) {
-  b->io.order = (b->lpt && b->solves > 0) ? b->d_order : nullptr;   // first solve: no history, index order
   bs_rebuild(b, nullptr, b->B);                  // members whose class changed in an update, or rho at max_iter
   const int *list = nullptr;
   long long count = b->B;
   int cur = 0, rounds = 0;
   for (;;) {
     BCHK(hipMemsetAsync(b->d_count, 0, sizeof(int), b->stream));
-    bs_set_lds(b);
+    set_dynamic_lds(KFN(k_bs_loop), b->lds_bytes);
     hipLaunchKernelGGL(k_bs_loop, dim3((unsigned)count), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io,
                        b->NPs, list, b->d_count, b->d_list[cur]);
     BCHK(hipGetLastError());
@@ -1075,26 +1102,19 @@ static int bs_solve(osqp_amd_batch *b) {
     cur ^= 1;
   }
   bs_rebuild(b, nullptr, b->B);                  // rho moved in the last iteration: K^-1 follows it, as in k_batch_solve
-  if (b->lpt) hipLaunchKernelGGL(k_batch_order, dim3(1), dim3(1024), 0, b->stream, b->B, b->io.info, b->d_order);
-  BCHK(hipGetLastError());
-  BCHK(hipStreamSynchronize(b->stream));
   b->last_rounds = rounds;
-  b->solves++;
   return 0;
 }
 
 // the one instantiation of k_batch_solve for (tile, phase)
 static const void *batch_kernel(int tile, int phase) {
-  if (phase == 2) return tile == 8 ? reinterpret_cast<const void *>(&k_batch_solve<8, 4, 32, 2>) : reinterpret_cast<const void *>(&k_batch_solve<4, 2, 32, 2>);
-  if (tile == 8) return phase ? reinterpret_cast<const void *>(&k_batch_solve<8, 4, 32, 1>) : reinterpret_cast<const void *>(&k_batch_solve<8, 4, 32, 0>);
-  return phase ? reinterpret_cast<const void *>(&k_batch_solve<4, 2, 32, 1>) : reinterpret_cast<const void *>(&k_batch_solve<4, 2, 32, 0>);
+  if (phase == 2) return tile == 8 ? KFN((k_batch_solve<8, 4, 32, 2>)) : KFN((k_batch_solve<4, 2, 32, 2>));
+  if (tile == 8) return phase ? KFN((k_batch_solve<8, 4, 32, 1>)) : KFN((k_batch_solve<8, 4, 32, 0>));
+  return phase ? KFN((k_batch_solve<4, 2, 32, 1>)) : KFN((k_batch_solve<4, 2, 32, 0>));
 }
 static void batch_launch(osqp_amd_batch *b, int phase) {
-  // The dynamic-LDS limit is a property of the kernel function, not of this batch: a later batch
-  // of the same tile may have set it to its own, smaller size.  Set it for this one every launch.
   const void *fn = batch_kernel(b->tile, phase);
-  if (b->lds_bytes > 64 * 1024)
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes);
+  set_dynamic_lds(fn, b->lds_bytes);
   void *args[] = {&b->pat, &b->st, &b->io};
   (void)hipLaunchKernel(fn, dim3((unsigned)b->B), dim3(BT), args, b->lds_bytes, b->stream);
 }
@@ -1191,18 +1211,14 @@ extern "C" c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
   // re-equilibrate from the raw data, re-form and re-invert K with each member's current rho and classes
   if (b->engine == OSQP_AMD_BATCH_STREAMED) (void)bs_setup_launch(b, true);
   else batch_launch(b, 2);
-  BCHK(hipGetLastError());
-  std::vector<int> hflag(B);
-  BCHK(hipMemcpyAsync(hflag.data(), b->io.flag, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-  BCHK(hipStreamSynchronize(b->stream));
-  b->noncvx = false;
-  for (size_t q = 0; q < B; q++)
-    if (hflag[q] & 8) {
-      fprintf(stderr, "osqp_amd batch: the new K of QP %zu of the batch is not positive definite (K = P + sigma I + "
-                      "A' rho A with the updated values); solves are refused until a matrix update succeeds\n", q);
-      b->noncvx = true;
-      return OSQP_NONCVX_ERROR;
-    }
+  const long long bad = first_not_pd(b);
+  if (bad < 0) return -102;
+  b->noncvx = bad != b->B;
+  if (b->noncvx) {
+    fprintf(stderr, "osqp_amd batch: the new K of QP %zu of the batch is not positive definite (K = P + sigma I + "
+                    "A' rho A with the updated values); solves are refused until a matrix update succeeds\n", (size_t)bad);
+    return OSQP_NONCVX_ERROR;
+  }
   return 0;
 }
 
@@ -1213,7 +1229,7 @@ extern "C" c_int osqp_amd_batch_update_rho(osqp_amd_batch *b, const c_float *rho
   for (size_t k = 0; k < cnt; k++) if (!(rho[k] > 0)) return 1;   // osqp.c:1288-1293
   BCHK(hipSetDevice(b->device));
   b->solved = false;
-  if (!b->d_rho && balloc(b, &b->d_rho, (size_t)b->B)) return OSQP_MEM_ALLOC_ERROR;
+  if (balloc_once(b, &b->d_rho, (size_t)b->B)) return OSQP_MEM_ALLOC_ERROR;
   BCHK(hipMemcpyAsync(b->d_rho, rho, cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
   hipLaunchKernelGGL(k_batch_update_rho, dim3((unsigned)((b->B + 255) / 256)), dim3(256), 0, b->stream,
                      b->B, b->io, b->d_rho, (int)(per_member != 0));
@@ -1244,13 +1260,9 @@ extern "C" c_int osqp_amd_batch_solve(osqp_amd_batch *b) {
   if (b->noncvx) return OSQP_NONCVX_ERROR;
   BCHK(hipSetDevice(b->device));
   b->solved = b->polished = false;
-  if (b->engine == OSQP_AMD_BATCH_STREAMED) {
-    const int rc = bs_solve(b);
-    b->solved = rc == 0;
-    return rc;
-  }
   b->io.order = (b->lpt && b->solves > 0) ? b->d_order : nullptr;   // first solve: no history, index order
-  batch_launch(b, 1);
+  if (b->engine != OSQP_AMD_BATCH_STREAMED) batch_launch(b, 1);
+  else if (const int rc = bs_solve(b)) return rc;
   if (b->lpt) hipLaunchKernelGGL(k_batch_order, dim3(1), dim3(1024), 0, b->stream, b->B, b->io.info, b->d_order);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
@@ -1264,14 +1276,11 @@ static int bp_reserve_maps(osqp_amd_batch *b) {
   if (b->d_plist) return 0;
   const size_t B = (size_t)b->B, m = (size_t)b->m;
   BPol &pl = b->pol;
-  int rc = 0;                // each buffer once: a call that follows a failed allocation asks only for the rest
-  if (!pl.map) rc |= balloc(b, &pl.map, B * m);
-  if (!rc && !pl.rows) rc |= balloc(b, &pl.rows, B * m);
-  if (!rc && !pl.mred) rc |= balloc(b, &pl.mred, B);
-  if (!rc && !pl.nlow) rc |= balloc(b, &pl.nlow, B);
-  if (!rc && !pl.stat) rc |= balloc(b, &pl.stat, B);
-  if (!rc) rc |= balloc(b, &b->d_plist, B);
-  if (rc) { (void)hipGetLastError(); return -102; }
+  if (balloc_once(b, &pl.map, B * m) || balloc_once(b, &pl.rows, B * m) || balloc_once(b, &pl.mred, B) ||
+      balloc_once(b, &pl.nlow, B) || balloc_once(b, &pl.stat, B) || balloc_once(b, &b->d_plist, B)) {
+    (void)hipGetLastError();
+    return -102;
+  }
   return 0;
 }
 // the KKT buffer of at least `bytes` (it only grows)
@@ -1315,40 +1324,45 @@ static c_int bp_plan(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds
   pl.K = b->pol.K;
   BCHK(hipMemcpyAsync(b->d_plist, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
   BCHK(hipStreamSynchronize(b->stream));         // (list goes out of scope)
-  const size_t ilds = 4 * (size_t)NPOL * sizeof(double);
-  if (ilds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bp_invert), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ilds);
-  out->count = list.size(); out->chunk = chunk; out->lds = lds; out->ilds = ilds; out->NPOL = NPOL;
+  out->count = list.size(); out->chunk = chunk; out->lds = lds; out->ilds = 4 * (size_t)NPOL * sizeof(double); out->NPOL = NPOL;
   return 0;
 }
 static size_t bp_lds_of(int n, int m, int NPOL) { return bp_lds_bytes(n, m, NPOL); }
 static size_t ba_lds_of(int n, int m, int NPOL) { return ba_lds_bytes(n, m, NPOL); }
+
+// The planned chunks of solved members: the KKT matrix of each member of a chunk (k_bp_form), its inverse
+// (k_bp_invert), then the caller's kernel fn, launched by third(members of the chunk, their list) with pn.lds
+// bytes of LDS.  Nothing is waited for.
+template <class Third>
+static int bp_run_chunks(osqp_amd_batch *b, const BPol &pl, const BPlan &pn, const void *fn, Third third) {
+  set_dynamic_lds(KFN(k_bp_invert), pn.ilds);
+  set_dynamic_lds(fn, pn.lds);
+  for (size_t c0 = 0; c0 < pn.count; c0 += pn.chunk) {
+    const unsigned cnt = (unsigned)std::min(pn.chunk, pn.count - c0);
+    const int *lp = b->d_plist + c0;
+    hipLaunchKernelGGL(k_bp_form, dim3((unsigned)pn.NPOL, cnt), dim3(256), 0, b->stream, b->pat, b->io, pl, pn.NPOL, b->pol_delta, lp);
+    hipLaunchKernelGGL(k_bp_invert, dim3(cnt), dim3(BS_NTI), pn.ilds, b->stream, b->n, pl, pn.NPOL, lp);
+    third(cnt, lp);
+    BCHK(hipGetLastError());
+  }
+  return 0;
+}
 
 // polish for the solved members, in chunks of at most pol_cap bytes of KKT matrices (batch_polish.h)
 extern "C" c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish) {
   if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   BCHK(hipSetDevice(b->device));
   const size_t B = (size_t)b->B;
-  const int n = b->n;
   BPol &pl = b->pol;
   if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
   if (!b->polished) {       // (a second call without a solve in between finds the work done and reports it again)
     BPlan pn;
     const c_int rc = bp_plan(b, pl, "polish", bp_lds_of, &pn);
     if (rc) return rc;
-    if (pn.count) {
-      if (pn.lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bp_polish), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pn.lds);
-      for (size_t c0 = 0; c0 < pn.count; c0 += pn.chunk) {
-        const unsigned cnt = (unsigned)std::min(pn.chunk, pn.count - c0);
-        const int *lp = b->d_plist + c0;
-        hipLaunchKernelGGL(k_bp_form, dim3((unsigned)pn.NPOL, cnt), dim3(256), 0, b->stream, b->pat, b->io, pl, pn.NPOL, b->pol_delta, lp);
-        hipLaunchKernelGGL(k_bp_invert, dim3(cnt), dim3(BS_NTI), pn.ilds, b->stream, n, pl, pn.NPOL, lp);
-        hipLaunchKernelGGL(k_bp_polish, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->st, b->io, pl, pn.NPOL, b->pol_refine, lp);
-        BCHK(hipGetLastError());
-      }
-      BCHK(hipStreamSynchronize(b->stream));
-    }
+    if (bp_run_chunks(b, pl, pn, KFN(k_bp_polish), [&](unsigned cnt, const int *lp) {
+          hipLaunchKernelGGL(k_bp_polish, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->st, b->io, pl, pn.NPOL, b->pol_refine, lp);
+        })) return -102;
+    BCHK(hipStreamSynchronize(b->stream));
     b->polished = true;
   }
   if (status_polish) {
@@ -1371,15 +1385,11 @@ extern "C" c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, co
   const size_t B = (size_t)b->B;
   const int n = b->n, m = b->m;
   if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
-  {                          // staging, each buffer once: a call that follows a failed allocation asks only for the rest
-    int rc = 0;
-    if (!b->adj_in) rc |= balloc(b, &b->adj_in, B * (n + m));
-    if (!rc && !b->adj_out) rc |= balloc(b, &b->adj_out, B * (n + 2 * (size_t)m));
-    if (!rc && !b->adj_act) rc |= balloc(b, &b->adj_act, B * m);
-    if (!rc && !b->adj_stat) rc |= balloc(b, &b->adj_stat, B);
-    if (!rc && dPx && !b->adj_dP) rc |= balloc(b, &b->adj_dP, B * b->nnzP);
-    if (!rc && dAx && !b->adj_dA) rc |= balloc(b, &b->adj_dA, B * b->nnzA);
-    if (rc) { (void)hipGetLastError(); return OSQP_MEM_ALLOC_ERROR; }
+  if (balloc_once(b, &b->adj_in, B * (n + m)) || balloc_once(b, &b->adj_out, B * (n + 2 * (size_t)m)) ||
+      balloc_once(b, &b->adj_act, B * m) || balloc_once(b, &b->adj_stat, B) ||
+      (dPx && balloc_once(b, &b->adj_dP, B * b->nnzP)) || (dAx && balloc_once(b, &b->adj_dA, B * b->nnzA))) {
+    (void)hipGetLastError();
+    return OSQP_MEM_ALLOC_ERROR;
   }
   BPol pl = b->pol;          // polish's buffers; its status array stays polish's
   pl.stat = b->adj_stat;
@@ -1399,18 +1409,9 @@ extern "C" c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, co
   BPlan pn;
   const c_int rc = bp_plan(b, pl, "adjoint", ba_lds_of, &pn);
   if (rc) return rc;
-  if (pn.count) {
-    if (pn.lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ba_adjoint), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pn.lds);
-    for (size_t c0 = 0; c0 < pn.count; c0 += pn.chunk) {
-      const unsigned cnt = (unsigned)std::min(pn.chunk, pn.count - c0);
-      const int *lp = b->d_plist + c0;
-      hipLaunchKernelGGL(k_bp_form, dim3((unsigned)pn.NPOL, cnt), dim3(256), 0, b->stream, b->pat, b->io, pl, pn.NPOL, b->pol_delta, lp);
-      hipLaunchKernelGGL(k_bp_invert, dim3(cnt), dim3(BS_NTI), pn.ilds, b->stream, n, pl, pn.NPOL, lp);
-      hipLaunchKernelGGL(k_ba_adjoint, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
-      BCHK(hipGetLastError());
-    }
-  }
+  if (bp_run_chunks(b, pl, pn, KFN(k_ba_adjoint), [&](unsigned cnt, const int *lp) {
+        hipLaunchKernelGGL(k_ba_adjoint, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
+      })) return -102;
   BCHK(hipMemcpyAsync(dQ, ad.dQ, B * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
   if (m) {
     BCHK(hipMemcpyAsync(dL, ad.dL, B * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
@@ -1489,11 +1490,10 @@ extern "C" c_int osqp_amd_batch_rounds(osqp_amd_batch *b, c_int *rounds, c_int *
   if (rounds) *rounds = b->engine == OSQP_AMD_BATCH_STREAMED ? b->last_rounds : (b->solves ? 1 : 0);
   if (refined) {
     BCHK(hipSetDevice(b->device));
-    std::vector<int> f((size_t)b->B);
-    BCHK(hipMemcpyAsync(f.data(), b->io.flag, f.size() * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-    BCHK(hipStreamSynchronize(b->stream));
+    std::vector<int> f;
+    if (read_flags(b, f)) return -102;
     c_int c = 0;
-    for (int v : f) c += (v & 2) ? 1 : 0;
+    for (int v : f) c += (v & BF_REFINE) ? 1 : 0;
     *refined = c;
   }
   return 0;

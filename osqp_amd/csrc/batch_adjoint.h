@@ -14,10 +14,10 @@
 //
 // The route is polish's: k_bp_active, k_bp_form and k_bp_invert as they are (the delta-regularised matrix, inverted
 // in place), on the polish buffers with a status array of its own, then
-//   k_ba_adjoint  one workgroup per member: the right-hand side, the solve with the explicit inverse, exactly
-//                 polish_refine_iter refinement steps against the unregularised M, and the unscaled outputs.
-// The refinement loop is a second copy of k_bp_polish's (another right-hand side), so that kernel's code and
-// register count stay what they were.  Nothing of the handle's solve state is written: X, Y, info, the stored
+//   k_ba_adjoint  one workgroup per member: the right-hand side, polish's solve (kkt_solve_refined: the explicit
+//                 inverse, then exactly polish_refine_iter refinement steps against the unregularised M), and the
+//                 unscaled outputs.
+// Nothing of the handle's solve state is written: X, Y, info, the stored
 // iterates, rho, K^-1, flags and polish's status stay bit-equal.  Every output element has one owner: no atomics.
 
 struct BAdj {              // staging of a handle's adjoint call (device pointers)
@@ -47,16 +47,11 @@ __global__ void __launch_bounds__(BP_NT) k_ba_adjoint(BPattern p, BIO io, BPol p
   double *x = g + NPOL, *D = x + n, *E = D + n, *y = E + m;
   int *map = reinterpret_cast<int *>(y + m), *rows = map + m;
   BL s;
-  s.Pv = io.Wv + qp * ((long long)p.nnzP + p.nnzA); s.Av = s.Pv + p.nnzP;
-  s.Pp = p.Pp; s.Pi = p.Pi; s.Pc = p.Pc; s.Fp = p.Fp; s.Fi = p.Fi; s.Fk = p.Fk;
-  s.Ap = p.Ap; s.Ai = p.Ai; s.Ac = p.Ac; s.Rp = p.Rp; s.Rj = p.Rj; s.Rk = p.Rk;
+  slab_view(s, p, io, qp);
   const double cs = io.Wc[qp], cinv = 1.0 / cs;
   for (int j = tid; j < n; j += BP_NT) { x[j] = io.Xs[qp * n + j]; D[j] = io.Wd[qp * n + j]; }
-  for (int i = tid; i < m; i += BP_NT) {
-    E[i] = io.We[qp * m + i]; y[i] = io.Ys[qp * m + i];
-    map[i] = pl.map[qp * m + i];
-    if (i < mred) rows[i] = pl.rows[qp * m + i];
-  }
+  for (int i = tid; i < m; i += BP_NT) { E[i] = io.We[qp * m + i]; y[i] = io.Ys[qp * m + i]; }
+  load_row_maps(pl, qp, m, mred, map, rows);
   __syncthreads();
   // rhs = [D gx; E gy / c on the active rows], zero in the padding
   for (int k = tid; k < NPOL; k += BP_NT) {
@@ -66,26 +61,7 @@ __global__ void __launch_bounds__(BP_NT) k_ba_adjoint(BPattern p, BIO io, BPol p
     g[k] = v;
   }
   __syncthreads();
-  bs_gemv(Kinv, NPOL, N, g, sol);
-  // iterative refinement against the unregularised KKT matrix, a fixed number of steps (as k_bp_polish)
-  for (int it = 0; it < refine_iter; ++it) {
-    for (int k = tid; k < NPOL; k += BP_NT) {
-      double v = 0.0;
-      if (k < n) {
-        double aty = 0.0;
-        for (int kk = s.Ap[k]; kk < s.Ap[k + 1]; ++kk) {
-          const int a = map[s.Ai[kk]];
-          if (a >= 0) aty += s.Av[kk] * sol[n + a];
-        }
-        v = (g[k] - p_row_dot(s, sol, k)) - aty;
-      } else if (k < N) v = g[k] - a_row_dot(s, sol, rows[k - n]);
-      res[k] = v;
-    }
-    __syncthreads();
-    bs_gemv(Kinv, NPOL, N, res, cor);
-    for (int k = tid; k < N; k += BP_NT) sol[k] += cor[k];
-    __syncthreads();
-  }
+  kkt_solve_refined(s, Kinv, NPOL, n, N, map, rows, refine_iter, [g](int k) { return g[k]; }, sol, res, cor);
   // sol = [rx; rnu] of the scaled problem; the unscaled gradients
   for (int j = tid; j < n; j += BP_NT) ad.dQ[qp * n + j] = 0.0 - (cs * D[j]) * sol[j];
   for (int i = tid; i < m; i += BP_NT) {

@@ -37,7 +37,7 @@ struct BDbg {};
 struct BA {
   double rho, cs;                     // current rho, cost scaling c
   int iter, rho_updates;
-  bool need_refine, check_pending;    // refinement verdict (bit 2 of io.flag) / still to be taken (bit 4)
+  bool need_refine, check_pending;    // refinement verdict (BF_REFINE of io.flag) / still to be taken (BF_OPEN)
 };
 
 // constraint class of a row (auxil.c:76-98): -1 loose, 1 equality, 0 inequality; and its rho
@@ -473,7 +473,7 @@ __device__ __forceinline__ bool admm_loop(const BL &s, const BPattern &p, const 
   return false;
 }
 
-// store_solution (auxil.c:524-562) with the certificates, the warm-start iterates, io.flag and the info record
+// store_solution (auxil.c:524-562) with the certificates, the warm-start iterates, io.flag (BF_* bits) and the info record
 template <int NT>
 __device__ __forceinline__ void store_solution(const BL &s, const BPattern &p, const BSettings &st, const BIO &io, long long qp,
                                                const BA &a, int flag) {

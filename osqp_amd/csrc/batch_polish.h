@@ -13,10 +13,13 @@
 //                row <-> reduced-row maps;
 //   k_bp_form    grid (NPOL rows, members of the chunk): row i of the member's NPOL x NPOL matrix, identity
 //                beyond N; NPOL = n + largest mred of the batch, rounded up to 32;
-//   k_bp_invert  one workgroup per member: k_bs_invert's in-place Gauss-Jordan over N.  A quasi-definite
-//                matrix is strongly factorisable in this order: n positive pivots, then mred negative ones; a
-//                pivot of the wrong sign (zero and NaN included) rejects the member's polish;
+//   k_bp_invert  one workgroup per member: the in-place Gauss-Jordan sweep of the streamed engine (gj_sweep,
+//                batch_streamed.h) over N.  A quasi-definite matrix is strongly factorisable in this order: n
+//                positive pivots, then mred negative ones; a pivot of the wrong sign (zero and NaN included)
+//                rejects the member's polish;
 //   k_bp_polish  one workgroup per member: everything after the inversion.
+// The adjoint (batch_adjoint.h) runs the same route with another right-hand side and shares its pieces: the three
+// kernels above, load_row_maps and kkt_solve_refined.
 // An accepted member's X, Y, info8[2..4] and scaled iterates are overwritten; of a rejected or skipped
 // member nothing is written but its status_polish.  rho, K^-1, io.flag, the row classes and rho_updates are
 // never touched.
@@ -107,36 +110,54 @@ __global__ void __launch_bounds__(256) k_bp_form(BPattern p, BIO io, BPol pl, in
   for (int j = tid; j < NPOL; j += 256) out[j] = row[j];
 }
 
-// k_bs_invert over the order N = n + mred of the member in slot blockIdx.x, with exchange buffers of NPOL
-// doubles (dynamic LDS: 4 * NPOL doubles) and the quasi-definite pivot verdict.
+// gj_sweep over the order N = n + mred of the member in slot blockIdx.x, with exchange buffers of NPOL doubles
+// (dynamic LDS: 4 * NPOL doubles) and the quasi-definite pivot verdict.
 __global__ void __launch_bounds__(BS_NTI) k_bp_invert(int n, BPol pl, int NPOL, const int *list) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const long long qp = list[blockIdx.x];
-  const int N = n + pl.mred[qp];
-  double *Ka = pl.K + (long long)blockIdx.x * NPOL * NPOL;
-  const int tr = threadIdx.x >> 5, tc = threadIdx.x & 31;
-  bool bad = false;
-#pragma unroll 1
-  for (int k = 0; k < N; ++k) {
-    double *rk = lds + (k & 1) * NPOL, *ck = lds + (2 + (k & 1)) * NPOL;
-    if (tr == (k & 31)) for (int j = tc; j < N; j += 32) rk[j] = Ka[(long long)k * NPOL + j];
-    if (tc == (k & 31)) for (int i = tr; i < N; i += 32) ck[i] = Ka[(long long)i * NPOL + k];
-    __syncthreads();
-    const double akk = rk[k];
-    bad |= k < n ? !(akk > 0.0) : !(akk < 0.0);
-    const double piv = 1.0 / akk;
-    for (int i = tr; i < N; i += 32) {
-      const double ci = ck[i];
-      double *Ki = Ka + (long long)i * NPOL;
-      if (i == k) {
-        for (int j = tc; j < N; j += 32) Ki[j] = j == k ? piv : rk[j] * piv;
-      } else {
-        for (int j = tc; j < N; j += 32) Ki[j] = j == k ? 0.0 - ci * piv : __builtin_fma(-ci, rk[j] * piv, Ki[j]);
-      }
-    }
-  }
-  __syncthreads();
+  const bool bad = gj_sweep(pl.K + (long long)blockIdx.x * NPOL * NPOL, n + pl.mred[qp], NPOL, lds, lds + 2 * NPOL, NPOL,
+                            [n](int k, double akk) { return k < n ? !(akk > 0.0) : !(akk < 0.0); });
   if (threadIdx.x == 0 && bad) pl.stat[qp] = -1;
+}
+
+// The member's row maps into LDS: map[0..m) and rows[0..mred) (visible after the next barrier).
+__device__ __forceinline__ void load_row_maps(const BPol &pl, long long qp, int m, int mred, int *map, int *rows) {
+  for (int i = threadIdx.x; i < m; i += BP_NT) {
+    map[i] = pl.map[qp * m + i];
+    if (i < mred) rows[i] = pl.rows[qp * m + i];
+  }
+}
+
+// sol = K^-1 rhs with the explicit inverse of the regularised matrix, then exactly refine_iter steps of
+// res = rhs - M sol, cor = K^-1 res, sol += cor against the unregularised M = [P, Ar'; Ar, 0] (polish.c:134-181).
+// rhs(k): the right-hand side, k in [0, NPOL), zero in the padding [N, NPOL).  sol, res, cor: LDS, NPOL each;
+// s: the member's slab_view; map, rows: LDS (load_row_maps).  Ends on a barrier.
+template <class Rhs>
+__device__ __forceinline__ void kkt_solve_refined(const BL &s, const double *Kinv, int NPOL, int n, int N, const int *map,
+                                                  const int *rows, int refine_iter, Rhs rhs, double *sol, double *res,
+                                                  double *cor) {
+  const int tid = threadIdx.x;
+  for (int k = tid; k < NPOL; k += BP_NT) res[k] = rhs(k);
+  __syncthreads();
+  bs_gemv(Kinv, NPOL, N, res, sol);
+  for (int it = 0; it < refine_iter; ++it) {
+    for (int k = tid; k < NPOL; k += BP_NT) {
+      double v = 0.0;
+      if (k < n) {
+        double aty = 0.0;
+        for (int kk = s.Ap[k]; kk < s.Ap[k + 1]; ++kk) {
+          const int a = map[s.Ai[kk]];
+          if (a >= 0) aty += s.Av[kk] * sol[n + a];
+        }
+        v = (rhs(k) - p_row_dot(s, sol, k)) - aty;
+      } else if (k < N) v = rhs(k) - a_row_dot(s, sol, rows[k - n]);
+      res[k] = v;
+    }
+    __syncthreads();
+    bs_gemv(Kinv, NPOL, N, res, cor);
+    for (int k = tid; k < N; k += BP_NT) sol[k] += cor[k];
+    __syncthreads();
+  }
 }
 
 // LDS of k_bp_polish: three vectors of NPOL (solution, residual, correction), q, D, five m-vectors (l, u, E, z, y),
@@ -158,15 +179,10 @@ __global__ void __launch_bounds__(BP_NT) k_bp_polish(BPattern p, BSettings st, B
   double *q = cor + NPOL, *D = q + n, *l = D + n, *u = l + m, *E = u + m, *z = E + m, *y = z + m, *gp = y + m;
   int *map = reinterpret_cast<int *>(gp + 32), *rows = map + m;
   BL s;
-  s.Pv = io.Wv + qp * ((long long)p.nnzP + p.nnzA); s.Av = s.Pv + p.nnzP;
-  s.Pp = p.Pp; s.Pi = p.Pi; s.Pc = p.Pc; s.Fp = p.Fp; s.Fi = p.Fi; s.Fk = p.Fk;
-  s.Ap = p.Ap; s.Ai = p.Ai; s.Ac = p.Ac; s.Rp = p.Rp; s.Rj = p.Rj; s.Rk = p.Rk;
+  slab_view(s, p, io, qp);
   for (int j = tid; j < n; j += BP_NT) { q[j] = io.Wq[qp * n + j]; D[j] = io.Wd[qp * n + j]; }
-  for (int i = tid; i < m; i += BP_NT) {
-    l[i] = io.Wl[qp * m + i]; u[i] = io.Wu[qp * m + i]; E[i] = io.We[qp * m + i];
-    map[i] = pl.map[qp * m + i];
-    if (i < mred) rows[i] = pl.rows[qp * m + i];
-  }
+  for (int i = tid; i < m; i += BP_NT) { l[i] = io.Wl[qp * m + i]; u[i] = io.Wu[qp * m + i]; E[i] = io.We[qp * m + i]; }
+  load_row_maps(pl, qp, m, mred, map, rows);
   const double cs = io.Wc[qp], pri0 = io.info[qp * 8 + 3], dua0 = io.info[qp * 8 + 4];
   __syncthreads();
   // rhs = [-q; l of the active lows; u of the active upps] (polish.c:226-233), zero in the padding
@@ -176,28 +192,7 @@ __global__ void __launch_bounds__(BP_NT) k_bp_polish(BPattern p, BSettings st, B
     const int r = rows[k - n];
     return k - n < nlow ? l[r] : u[r];
   };
-  for (int k = tid; k < NPOL; k += BP_NT) res[k] = rhs(k);
-  __syncthreads();
-  bs_gemv(Kinv, NPOL, N, res, sol);
-  // iterative refinement against the unregularised KKT matrix (polish.c:134-181): a fixed number of steps
-  for (int it = 0; it < refine_iter; ++it) {
-    for (int k = tid; k < NPOL; k += BP_NT) {
-      double v = 0.0;
-      if (k < n) {
-        double aty = 0.0;
-        for (int kk = s.Ap[k]; kk < s.Ap[k + 1]; ++kk) {
-          const int a = map[s.Ai[kk]];
-          if (a >= 0) aty += s.Av[kk] * sol[n + a];
-        }
-        v = (rhs(k) - p_row_dot(s, sol, k)) - aty;
-      } else if (k < N) v = rhs(k) - a_row_dot(s, sol, rows[k - n]);
-      res[k] = v;
-    }
-    __syncthreads();
-    bs_gemv(Kinv, NPOL, N, res, cor);
-    for (int k = tid; k < N; k += BP_NT) sol[k] += cor[k];
-    __syncthreads();
-  }
+  kkt_solve_refined(s, Kinv, NPOL, n, N, map, rows, refine_iter, rhs, sol, res, cor);
   // z = A x, y from the multipliers of the active rows, (z, y) on the normal cone (polish.c:262-279, proj.c:16-29);
   // then objective and residuals of the polished point as update_info computes them (auxil.c:227-318)
   const bool unscaled = st.scaling && !st.scaled_termination;

@@ -9,14 +9,14 @@
 //                <true>: the re-equilibration of a matrix update, classes, rho and iterates kept);
 //   k_bs_form    grid (NP rows, members): K = P + sigma I + A' diag(rho) A, dense, from a host-built list of
 //                (A slot, A slot, row) triples per entry of triu(K): a fixed summation order, no atomics;
-//   k_bs_invert  one workgroup per member: Gauss-Jordan in place in HBM without pivoting (K is SPD); a
-//                non-positive pivot flags the member (bit 8 of io.flag);
+//   k_bs_invert  one workgroup per member: Gauss-Jordan in place in HBM without pivoting (K is SPD; gj_sweep,
+//                the sweep polish and adjoint run too); a non-positive pivot flags the member (BF_NOT_PD);
 //   k_bs_loop    one workgroup per member: admm_loop of batch_admm.h, the code k_batch_solve runs, with StreamedK
 //                as its K solve.  A member whose rho moves saves its scaled x, z, y, iteration count and rho and
 //                leaves with a rebuild request; the host re-forms and re-inverts those members and relaunches
 //                the loop over them (osqp_amd_batch_solve).
-// form and invert only touch members whose io.flag has bit 1 set (a rebuild is due), so a launch over the
-// whole batch costs nothing for the others.
+// form and invert only touch members whose io.flag has BF_REBUILD, so a launch over the whole batch costs
+// nothing for the others.
 
 #define BS_MAX_N 1024      // largest n (k_bs_form's and k_bs_invert's row buffers)
 #define BS_MAX_TRIPLES (1 << 26)   // A'A row products of the K pattern (4 bytes x 3 each)
@@ -57,6 +57,14 @@ __host__ __device__ __forceinline__ size_t bs_lds_bytes(int NP, int m) {
   return (b + 15) & ~(size_t)15;
 }
 
+// The matrix side of a BL for a member whose scaled values stay in HBM: Pv / Av in its slab io.Wv, the pattern
+// read from global memory.  (Polish and adjoint use nothing else of the BL.)
+__device__ __forceinline__ void slab_view(BL &s, const BPattern &p, const BIO &io, long long qp) {
+  s.Pv = io.Wv + qp * ((long long)p.nnzP + p.nnzA); s.Av = s.Pv + p.nnzP;
+  s.Pp = p.Pp; s.Pi = p.Pi; s.Pc = p.Pc; s.Fp = p.Fp; s.Fi = p.Fi; s.Fk = p.Fk;
+  s.Ap = p.Ap; s.Ai = p.Ai; s.Ac = p.Ac; s.Rp = p.Rp; s.Rj = p.Rj; s.Rk = p.Rk;
+}
+
 __device__ __forceinline__ BL bs_layout(double *lds, const BPattern &p, const BIO &io, long long qp, int NP) {
   BL s;
   double *w = lds;
@@ -65,9 +73,7 @@ __device__ __forceinline__ BL bs_layout(double *lds, const BPattern &p, const BI
   s.red = w; w += 64; s.gp = w; w += 256;
   s.rowk = s.colk = nullptr;
   s.ctype = reinterpret_cast<int *>(w);
-  s.Pv = io.Wv + qp * ((long long)p.nnzP + p.nnzA); s.Av = s.Pv + p.nnzP;
-  s.Pp = p.Pp; s.Pi = p.Pi; s.Pc = p.Pc; s.Fp = p.Fp; s.Fi = p.Fi; s.Fk = p.Fk;
-  s.Ap = p.Ap; s.Ai = p.Ai; s.Ac = p.Ac; s.Rp = p.Rp; s.Rj = p.Rj; s.Rk = p.Rk;
+  slab_view(s, p, io, qp);
   return s;
 }
 
@@ -84,7 +90,7 @@ __global__ void __launch_bounds__(BS_NT) k_bs_setup(BPattern p, BSettings st, BI
   clear_vectors<BS_NT>(s);
   load_problem<BS_NT, true>(s, p, io, qp);
   const double cs = ruiz_scale<BS_NT, true, !UPD>(s, p, st);
-  store_workspace<BS_NT, true, !UPD>(s, p, io, qp, cs, fmin(fmax(st.rho, 1e-6), 1e6), 1);   // 1: K^-1 is due (k_bs_form, k_bs_invert)
+  store_workspace<BS_NT, true, !UPD>(s, p, io, qp, cs, fmin(fmax(st.rho, 1e-6), 1e6), BF_REBUILD);   // K^-1 is due (k_bs_form, k_bs_invert)
 }
 
 // ---------------------------------------------------------------------------
@@ -93,7 +99,7 @@ __global__ void __launch_bounds__(BS_NT) k_bs_setup(BPattern p, BSettings st, BI
 __global__ void __launch_bounds__(256) k_bs_form(BPattern p, BSPattern kp, BIO io, int NP, double sigma, const int *list) {
   __shared__ __attribute__((aligned(16))) double row[1024];
   const long long qp = list ? list[blockIdx.y] : (int)blockIdx.y;
-  if (!(io.flag[qp] & 1)) return;
+  if (!(io.flag[qp] & BF_REBUILD)) return;
   const int i = blockIdx.x, n = p.n, m = p.m;
   for (int j = threadIdx.x; j < NP; j += 256) row[j] = j == i ? 1.0 : 0.0;
   __syncthreads();
@@ -116,50 +122,58 @@ __global__ void __launch_bounds__(256) k_bs_form(BPattern p, BSPattern kp, BIO i
 }
 
 // ---------------------------------------------------------------------------
-// Gauss-Jordan inversion in place in HBM without pivoting (invert_tiles, one pivot per step).  Thread (tr, tc)
-// of a 32 x 32 grid owns the entries (i, j) with i = tr mod 32, j = tc mod 32 for all pivots, so each entry is
-// only ever read and written by its owner; the owners of row k and column k publish them to LDS (double
-// buffered, one barrier per pivot).  Only the n x n block is touched: the padding stays the identity.
+// Gauss-Jordan inversion in place in HBM without pivoting (invert_tiles, one pivot per step) of the N x N block
+// of a matrix of pitch NP.  Thread (tr, tc) of a 32 x 32 grid owns the entries (i, j) with i = tr mod 32,
+// j = tc mod 32 for all pivots, so each entry is only ever read and written by its owner; the owners of row k and
+// column k publish them to LDS (double buffered: row[0..N) and row[stride..stride + N), col likewise; one barrier
+// per pivot).  Only the N x N block is touched: the padding stays the identity.  wrong(k, akk): pivot k has the
+// wrong sign; returns (uniformly: every lane reads every pivot) whether any had.
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(BS_NTI) k_bs_invert(int n, BIO io, int NP, const int *list) {
-  __shared__ double rowk[2][1024], colk[2][1024];
-  const long long qp = list ? list[blockIdx.x] : (int)blockIdx.x;
-  const int fl = io.flag[qp];
-  if (!(fl & 1)) return;
-  double *Ka = io.Wk + qp * (long long)NP * NP;
+template <class Wrong>
+__device__ __forceinline__ bool gj_sweep(double *Ka, int N, int NP, double *row, double *col, int stride, Wrong wrong) {
   const int tr = threadIdx.x >> 5, tc = threadIdx.x & 31;
-  bool notpd = false;
+  bool bad = false;
 #pragma unroll 1
-  for (int k = 0; k < n; ++k) {
-    double *rk = rowk[k & 1], *ck = colk[k & 1];
-    if (tr == (k & 31)) for (int j = tc; j < n; j += 32) rk[j] = Ka[(long long)k * NP + j];
-    if (tc == (k & 31)) for (int i = tr; i < n; i += 32) ck[i] = Ka[(long long)i * NP + k];
+  for (int k = 0; k < N; ++k) {
+    double *rk = row + (k & 1) * stride, *ck = col + (k & 1) * stride;
+    if (tr == (k & 31)) for (int j = tc; j < N; j += 32) rk[j] = Ka[(long long)k * NP + j];
+    if (tc == (k & 31)) for (int i = tr; i < N; i += 32) ck[i] = Ka[(long long)i * NP + k];
     __syncthreads();
     const double akk = rk[k];
-    notpd |= !(akk > 0.0);
+    bad |= wrong(k, akk);
     const double piv = 1.0 / akk;
-    for (int i = tr; i < n; i += 32) {
+    for (int i = tr; i < N; i += 32) {
       const double ci = ck[i];
       double *Ki = Ka + (long long)i * NP;
       if (i == k) {
-        for (int j = tc; j < n; j += 32) Ki[j] = j == k ? piv : rk[j] * piv;
+        for (int j = tc; j < N; j += 32) Ki[j] = j == k ? piv : rk[j] * piv;
       } else {
-        for (int j = tc; j < n; j += 32) Ki[j] = j == k ? 0.0 - ci * piv : __builtin_fma(-ci, rk[j] * piv, Ki[j]);
+        for (int j = tc; j < N; j += 32) Ki[j] = j == k ? 0.0 - ci * piv : __builtin_fma(-ci, rk[j] * piv, Ki[j]);
       }
     }
   }
   __syncthreads();
-  // bit 1 (rebuild due) cleared, refinement verdict kept, 4: the verdict is re-taken, 8: K not positive definite
-  if (threadIdx.x == 0) io.flag[qp] = (fl & 2) | 4 | (notpd ? 8 : 0);
+  return bad;
+}
+
+__global__ void __launch_bounds__(BS_NTI) k_bs_invert(int n, BIO io, int NP, const int *list) {
+  __shared__ double rowk[2][1024], colk[2][1024];
+  const long long qp = list ? list[blockIdx.x] : (int)blockIdx.x;
+  const int fl = io.flag[qp];
+  if (!(fl & BF_REBUILD)) return;
+  const bool notpd = gj_sweep(io.Wk + qp * (long long)NP * NP, n, NP, rowk[0], colk[0], 1024,
+                              [](int, double akk) { return !(akk > 0.0); });
+  // the rebuild is done and the refinement verdict kept, to be taken again on the new K^-1
+  if (threadIdx.x == 0) io.flag[qp] = (fl & BF_REFINE) | BF_OPEN | (notpd ? BF_NOT_PD : 0);
 }
 
 // ---------------------------------------------------------------------------
 // the ADMM loop with K^-1 streamed from HBM
 // ---------------------------------------------------------------------------
 // A rho move cannot be followed inside the kernel (K is re-formed and re-inverted by kernels of their own): before
-// max_iter the member saves its scaled iterates, counters and rho, sets io.flag = 1 | (refinement verdict), appends
-// itself to rb_list (rb_count) and leaves; at max_iter no further solve with K follows, so it finishes and the
-// rebuild is left to the host's last pass.
+// max_iter the member saves its scaled iterates, counters and rho, sets io.flag = BF_REBUILD | (refinement
+// verdict), appends itself to rb_list (rb_count) and leaves; at max_iter no further solve with K follows, so it
+// finishes and the rebuild is left to the host's last pass.
 struct StreamedK {
   const double *Wk;
   int NP, n;
@@ -173,7 +187,7 @@ struct StreamedK {
     for (int i = tid; i < m; i += BS_NT) { io.Zs[qp * m + i] = s_z[i]; io.Ys[qp * m + i] = s_y[i]; }
     if (tid == 0) {
       io.info[qp * 8] = a.iter; io.info[qp * 8 + 5] = a.rho_updates; io.rho_io[qp] = a.rho;
-      io.flag[qp] = 1 | (a.need_refine ? 2 : 0);
+      io.flag[qp] = BF_REBUILD | (a.need_refine ? BF_REFINE : 0);
       rb_list[atomicAdd(rb_count, 1)] = (int)qp;
     }
     return true;
@@ -198,10 +212,10 @@ __global__ void __launch_bounds__(BS_NT) k_bs_loop(BPattern p, BSettings st, BIO
   a.rho = fmin(fmax(io.rho_io[qp], 1e-6), 1e6);
   init_iterates<BS_NT>(s, p, io, qp, a.rho, st.warm_start || resume);
   const int qflag = io.flag[qp];
-  a.need_refine = (qflag & 2) != 0;
-  a.check_pending = (qflag & 4) != 0;
+  a.need_refine = (qflag & BF_REFINE) != 0;
+  a.check_pending = (qflag & BF_OPEN) != 0;
   if (admm_loop<BS_NT, false>(s, p, st, io, qp, a, resume ? (int)io.info[qp * 8] : 0, eng, dbg)) return;
   // a rebuild left for after the loop drops the refinement verdict, as the tiled engine's in-loop rebuild does
-  store_solution<BS_NT>(s, p, st, io, qp, a, eng.rebuild_due ? 1 : (a.check_pending ? 4 : (a.need_refine ? 2 : 0)));
+  store_solution<BS_NT>(s, p, st, io, qp, a, eng.rebuild_due ? BF_REBUILD : (a.check_pending ? BF_OPEN : (a.need_refine ? BF_REFINE : 0)));
   if (threadIdx.x == 0) io.rho_io[qp] = a.rho;
 }
