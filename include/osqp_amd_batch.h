@@ -132,6 +132,49 @@ c_int osqp_amd_batch_get(osqp_amd_batch *b, c_float *X, c_float *Y, c_float *inf
 c_int osqp_amd_batch_device_ptrs(osqp_amd_batch *b, void **X, void **Y, void **info8);
 void  osqp_amd_batch_cleanup(osqp_amd_batch *b);
 
+/* ---- Device arrays in and out -------------------------------------------------------------------------------
+ * The calls below are the calls above with DEVICE pointers in place of host pointers: a caller whose data lives in
+ * HBM (a torch CUDA tensor, an array of its own hipMalloc) updates, warm-starts and reads a handle without a host
+ * copy of any [batch][.] array.  Each has the semantics and the return codes of its twin (the same name without
+ * _dev), runs the twin's kernels on the same workspace and leaves the handle in the state the twin would.
+ * Pointers: every non-NULL device pointer must be device memory (hipMalloc and the like, not managed and not
+ * registered host memory) of the handle's device, known to the HIP runtime this library runs on.  Each is classified
+ * on the host (hipPointerGetAttributes) before any copy or launch; a pointer that does not pass -- a host pointer,
+ * another device's memory, an allocation of a second HIP runtime mapped into the process -- makes the call return
+ * OSQP_DATA_VALIDATION_ERROR with nothing written.  The sizes are the caller's promise, as for host pointers.
+ * Ordering: the work runs on the handle's own stream.  The caller's inputs must be complete when the call is made
+ * (synchronise the stream that produced them first); every _dev call returns with the handle's stream synchronised,
+ * so its outputs are ready on return for any stream.  No stream or event handle crosses this interface. */
+
+/* osqp_amd_batch_update from device arrays (NULL = keep).  The bounds are clamped to +-OSQP_INFTY on the device.
+ * Returns 1 when L and U are both given and some L[k] > U[k] after the clamp; the raw q, l, u of the handle, its
+ * scaled workspace, flags and info8 are then exactly as before the call. */
+c_int osqp_amd_batch_update_dev(osqp_amd_batch *b, const c_float *Q, const c_float *L, const c_float *U);
+/* osqp_amd_batch_update_matrices with the value arrays Px / Ax on the device.  The index lists Px_idx / Ax_idx stay
+ * HOST pointers (they belong to the pattern) and are validated before anything is written, with the twin's codes in
+ * the twin's order: 1, 2, OSQP_DATA_VALIDATION_ERROR; then the device pointers. */
+c_int osqp_amd_batch_update_matrices_dev(osqp_amd_batch *b,
+                                         const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
+                                         const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member);
+/* osqp_amd_batch_warm_start from device arrays X [batch][n], Y [batch][m] (either may be NULL). */
+c_int osqp_amd_batch_warm_start_dev(osqp_amd_batch *b, const c_float *X, const c_float *Y);
+/* osqp_amd_batch_adjoint with every array on the device.  active [batch][m] and status_adjoint [batch] are 32-bit
+ * ints there (int, not c_int), as the kernel writes them. */
+c_int osqp_amd_batch_adjoint_dev(osqp_amd_batch *b, const c_float *dX, const c_float *dY /*NULL = 0*/,
+                                 c_float *dQ, c_float *dL, c_float *dU,
+                                 c_float *dPx /*NULL = skip*/, c_float *dAx /*NULL = skip*/,
+                                 int *active /*NULL = skip*/, int *status_adjoint /*NULL = skip*/);
+/* osqp_amd_batch_get into caller-owned device arrays (NULL = skip): copies, which a later solve does not touch
+ * (the arrays of osqp_amd_batch_device_ptrs are the handle's own and change with the next solve). */
+c_int osqp_amd_batch_get_dev(osqp_amd_batch *b, c_float *X, c_float *Y, c_float *info8, c_float *DX, c_float *DY);
+/* status_polish [batch] (32-bit ints on the device) as osqp_amd_batch_polish reports it; all 0 when polish has not
+ * run since the last solve.  Runs no polish.  OSQP_WORKSPACE_NOT_INIT_ERROR as osqp_amd_batch_polish: no solve has
+ * run on the current problem. */
+c_int osqp_amd_batch_polish_status_dev(osqp_amd_batch *b, int *status_polish);
+/* For the tests: the pointer check of the _dev calls alone.  0 when p passes, OSQP_DATA_VALIDATION_ERROR otherwise
+ * (NULL included).  Asks the runtime about the address; reads and writes no GPU memory. */
+c_int osqp_amd_batch_check_dev_ptr(osqp_amd_batch *b, const void *p);
+
 /* For the tests: member qp's workspace as the last setup / update / solve left it.  NULL = skip.
  * D [n], E [m], c [1], rho [1] (current scalar rho), ctype [m] (-1 free, 0 ineq, 1 eq),
  * Pv [nnzP], Av [nnzA] (scaled values, CSC order), Kinv [NP*NP] row-major, *NP = 64 or 128

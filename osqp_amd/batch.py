@@ -51,10 +51,24 @@ def _bind(L):
     L.osqp_amd_batch_rounds.argtypes = [H, abi.c_int_p, abi.c_int_p]
     L.osqp_amd_batch_member.restype = abi.c_int
     L.osqp_amd_batch_member.argtypes = [H, abi.c_int] + [abi.c_float_p] * 4 + [abi.c_int_p] + [abi.c_float_p] * 3 + [abi.c_int_p]
+    # device arrays in and out: device addresses travel as integers (c_void_p), host index lists as before
+    V = C.c_void_p
+    for name, args in (("update_dev", [V] * 3), ("warm_start_dev", [V] * 2), ("adjoint_dev", [V] * 9),
+                       ("update_matrices_dev", [V, abi.c_int_p, abi.c_int, abi.c_int] * 2),
+                       ("get_dev", [V] * 5), ("polish_status_dev", [V]), ("check_dev_ptr", [V])):
+        f = getattr(L, "osqp_amd_batch_" + name)
+        f.restype = abi.c_int
+        f.argtypes = [H] + args
 
 
 def _p(a):
     return C.cast(None, abi.c_float_p) if a is None else abi.fptr(a)
+
+
+def is_device(a):
+    """True for an object that says where it lives in HBM (`__cuda_array_interface__`: a torch CUDA tensor that needs no
+    gradient, a cupy array, an object of the caller's own)."""
+    return hasattr(a, "__cuda_array_interface__")
 
 
 def check_matrix_update(B, nnzP, nnzA, Px=None, Px_idx=None, Ax=None, Ax_idx=None):
@@ -69,12 +83,16 @@ def check_matrix_update(B, nnzP, nnzA, Px=None, Px_idx=None, Ax=None, Ax_idx=Non
                 raise ValueError("%sx_idx given without %sx" % (name, name))
             out += [None, None, 0]
             continue
-        V = abi.as_f64(V)
-        if V.ndim not in (1, 2):
+        if is_device(V):                         # stays where it is: device_view checks type and strides
+            shape = tuple(V.__cuda_array_interface__["shape"])
+        else:
+            V = abi.as_f64(V)
+            shape = V.shape
+        if len(shape) not in (1, 2):
             raise ValueError("%sx must be [k] (shared) or [B, k] (per member)" % name)
-        if V.ndim == 2 and V.shape[0] != B:
-            raise ValueError("%sx has %d rows, the batch has %d members" % (name, V.shape[0], B))
-        k = V.shape[-1]
+        if len(shape) == 2 and shape[0] != B:
+            raise ValueError("%sx has %d rows, the batch has %d members" % (name, shape[0], B))
+        k = shape[-1]
         if I is None:
             if k != nnz:
                 raise ValueError("%sx has %d values per member, %s has %d non-zeros (pass %sx_idx for a partial update)"
@@ -85,8 +103,45 @@ def check_matrix_update(B, nnzP, nnzA, Px=None, Px_idx=None, Ax=None, Ax_idx=Non
                 raise ValueError("%sx_idx must be a vector as long as a member's %sx" % (name, name))
             if I.size and (I.min() < 0 or I.max() >= nnz):
                 raise ValueError("%sx_idx out of range [0, %d)" % (name, nnz))
-        out += [V, I, int(V.ndim == 2)]
+        out += [V, I, int(len(shape) == 2)]
     return tuple(out)
+
+
+def device_view(a, shape, typestr, writable=False, name="array"):
+    """The device pointer of `a`, an object with `__cuda_array_interface__`, once it is what the C side will read or
+    write: `shape` exactly, `typestr` ("<f8", or "<i4" for the integer outputs), C-contiguous (`strides` None or the
+    contiguous ones) and, for an output (writable=True), not read-only."""
+    cai = getattr(a, "__cuda_array_interface__", None)
+    if cai is None:
+        raise ValueError("%s is not a device array (no __cuda_array_interface__)" % name)
+    shape = tuple(int(d) for d in shape)
+    if tuple(cai["shape"]) != shape:
+        raise ValueError("%s has shape %s, the handle needs %s" % (name, tuple(cai["shape"]), shape))
+    if cai["typestr"] != typestr:
+        raise ValueError("%s has type %s, the handle needs %s" % (name, cai["typestr"], typestr))
+    strides = cai.get("strides")
+    if strides is not None:
+        want, step = [], int(typestr[2:])
+        for d in reversed(shape):
+            want.insert(0, step)
+            step *= max(d, 1)
+        if any(d > 1 and s != w for d, s, w in zip(shape, strides, want)):
+            raise ValueError("%s must be C-contiguous (strides %s, not %s)" % (name, tuple(want), tuple(strides)))
+    ptr, readonly = cai["data"]
+    if writable and readonly:
+        raise ValueError("%s is read-only and the handle writes it" % name)
+    return int(ptr or 0)
+
+
+def io_route(**arrays):
+    """"device" when every given (non-None) array is a device object, "host" when none is; a mix raises."""
+    given = {k: is_device(a) for k, a in arrays.items() if a is not None}
+    if given and all(given.values()):
+        return "device"
+    if any(given.values()):
+        raise ValueError("host and device arrays in one call (%s on the device, %s on the host): pass all of them one way"
+                         % (", ".join(k for k, d in given.items() if d), ", ".join(k for k, d in given.items() if not d)))
+    return "host"
 
 
 def check_adjoint(B, n, m, dX, dY=None):
@@ -97,6 +152,11 @@ def check_adjoint(B, n, m, dX, dY=None):
     if dX.shape != (B, n) or (dY is not None and dY.shape != (B, m)):
         raise ValueError("adjoint arrays must be dX [B, n], dY [B, m]")
     return dX, dY
+
+
+_BAD_POINTER = (": a pointer is not device memory of the handle's device as the library's HIP runtime knows it (a host "
+                "array, another device, or an allocation of a second HIP runtime in this process: import torch before the "
+                "library is first loaded)")
 
 
 class BatchOSQP:
@@ -230,7 +290,25 @@ class BatchOSQP:
             setattr(out, name, col.astype(np.int64) if name in ("iter", "status_val", "rho_updates") else col)
         return out
 
+    def _route(self, **arrays):
+        route = io_route(**arrays)
+        if route == "device" and self._many is not None:
+            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): it takes and returns host arrays; "
+                               "there is no packed device image to read or write" % BATCH_MAX_N)
+        return route
+
+    def _dev(self, a, cols, name, typestr="<f8", writable=False):
+        """Device pointer of a [B, cols] array (None, or nothing to read: NULL)."""
+        if a is None:
+            return None
+        return device_view(a, (self.B, cols), typestr, writable, name) or None
+
     def update(self, Q=None, L=None, U=None):
+        """osqp_update_lin_cost / _bounds for every QP (None = keep).  Host arrays, or device arrays (objects with
+        `__cuda_array_interface__`, complete when the call is made): those are clamped, checked and scaled on the device."""
+        if self._route(Q=Q, L=L, U=U) == "device":
+            return int(self._lib.osqp_amd_batch_update_dev(self._h, self._dev(Q, self.n, "Q"), self._dev(L, self.m, "L"),
+                                                           self._dev(U, self.m, "U")))
         Q = None if Q is None else abi.as_f64(Q)
         L = None if L is None else np.maximum(abi.as_f64(L), -abi.OSQP_INFTY)
         U = None if U is None else np.minimum(abi.as_f64(U), abi.OSQP_INFTY)
@@ -257,7 +335,10 @@ class BatchOSQP:
         """osqp_update_P / _A / _P_A for every QP: new values on the pattern of setup.  Px / Ax: [k] (shared by the
         batch) or [B, k] (per member); k = nnz of triu(P) / A in CSC order, or the length of Px_idx / Ax_idx (slots, one
         list for the batch).  Scaling is recomputed; rho, row classes and iterates stay.  Returns the C return code
-        (5: some member's new K is not positive definite; solve then refuses until an update succeeds)."""
+        (5: some member's new K is not positive definite; solve then refuses until an update succeeds).  Px / Ax may be
+        device arrays; the index lists stay host data."""
+        if self._route(Px=Px, Ax=Ax) == "device":
+            return self._update_matrices_dev(Px, Px_idx, Ax, Ax_idx)
         Px, Px_idx, pper, Ax, Ax_idx, aper = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
         if Px is None and Ax is None:
             return 0
@@ -268,6 +349,19 @@ class BatchOSQP:
         return int(self._lib.osqp_amd_batch_update_matrices(
             self._h, _p(Px), ip(Px_idx), 0 if Px is None else Px.shape[-1], pper,
             _p(Ax), ip(Ax_idx), 0 if Ax is None else Ax.shape[-1], aper))
+
+    def _update_matrices_dev(self, Px, Px_idx, Ax, Ax_idx):
+        Px, Px_idx, pper, Ax, Ax_idx, aper = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
+        shp = lambda a: tuple(a.__cuda_array_interface__["shape"])
+        ip = lambda a: C.cast(None, abi.c_int_p) if a is None else abi.iptr(a)
+        # (a pointer of 0: nothing to write; NULL = keep says the same)
+        pP = None if Px is None else device_view(Px, shp(Px), "<f8", name="Px") or None
+        pA = None if Ax is None else device_view(Ax, shp(Ax), "<f8", name="Ax") or None
+        if pP is None and pA is None:
+            return 0
+        return int(self._lib.osqp_amd_batch_update_matrices_dev(
+            self._h, pP, ip(Px_idx), 0 if Px is None else shp(Px)[-1], pper,
+            pA, ip(Ax_idx), 0 if Ax is None else shp(Ax)[-1], aper))
 
     def update_rho(self, rho):
         """osqp_update_rho for every QP: a scalar, or [B] values.  Returns 1 (nothing changed) when a value is <= 0."""
@@ -283,7 +377,11 @@ class BatchOSQP:
         return int(self._lib.osqp_amd_batch_update_rho(self._h, abi.fptr(rho), per))
 
     def warm_start(self, X=None, Y=None):
-        """osqp_warm_start (_x, _y) for every QP: X [B, n], Y [B, m], unscaled; turns the warm_start setting on."""
+        """osqp_warm_start (_x, _y) for every QP: X [B, n], Y [B, m], unscaled; turns the warm_start setting on.  Host
+        arrays or device arrays."""
+        if self._route(X=X, Y=Y) == "device":
+            return int(self._lib.osqp_amd_batch_warm_start_dev(self._h, self._dev(X, self.n, "X"),
+                                                               self._dev(Y, self.m, "Y") if self.m else None))
         X = None if X is None else abi.as_f64(X)
         Y = None if Y is None else abi.as_f64(Y)
         if (X is not None and X.shape != (self.B, self.n)) or (Y is not None and Y.shape != (self.B, self.m)):
@@ -303,21 +401,23 @@ class BatchOSQP:
             raise RuntimeError("osqp_amd_batch_solve failed (%d)" % rc)
         return self.results() if fetch else None
 
-    def polish(self):
+    def polish(self, fetch=True):
         """Polish (src/polish.c) on the device for every member whose last solve ended `solved`, with the handle's
         `delta` and `polish_refine_iter`.  Returns results() -- x, y, obj_val, pri_res, dua_res of the accepted
         members are the polished ones -- with `status_polish` [B]: 1 accepted, -1 tried and rejected (nothing of
-        that member changed), 0 not tried.  Needs a solve since setup or the last update."""
+        that member changed), 0 not tried.  Needs a solve since setup or the last update.  fetch=False: nothing is
+        copied to the host and None is returned (results_into reads the outcome on the device; a later results() fetches
+        the status then)."""
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): polish is a call of the batch "
                                "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
-        sp = np.zeros(self.B, np.int64)
-        rc = self._lib.osqp_amd_batch_polish(self._h, abi.iptr(sp))
+        sp = np.zeros(self.B, np.int64) if fetch else None
+        rc = self._lib.osqp_amd_batch_polish(self._h, abi.iptr(sp) if fetch else C.cast(None, abi.c_int_p))
         if rc:
             raise RuntimeError("osqp_amd_batch_polish failed (%d)%s" % (rc, ": no solve has run on the current problem"
                                                                         if rc == 7 else ""))
-        self._status_polish = sp
-        return self.results()
+        self._status_polish = sp if fetch else "device"       # results() reads it when it is first asked for
+        return self.results() if fetch else None
 
     def adjoint(self, dX, dY=None, matrices=False):
         """Adjoint derivatives of the solution on the device, for every member whose last solve ended `solved`: from
@@ -354,11 +454,59 @@ class BatchOSQP:
         if rc:
             raise RuntimeError("osqp_amd_batch_get failed (%d)" % rc)
         out = SimpleNamespace(x=X, y=Y[:, :self.m], dual_inf_cert=DX, prim_inf_cert=DY[:, :self.m], info_raw=info)
+        if isinstance(self._status_polish, str):       # polish(fetch=False) ran: the work is done, the call reports it
+            sp = np.zeros(self.B, np.int64)
+            rc = self._lib.osqp_amd_batch_polish(self._h, abi.iptr(sp))
+            if rc and rc != 7:
+                raise RuntimeError("osqp_amd_batch_polish failed (%d)" % rc)
+            self._status_polish = None if rc else sp       # (7: the problem has changed since; nothing was tried on it)
         out.status_polish = np.zeros(self.B, np.int64) if self._status_polish is None else self._status_polish.copy()
         for k, name in enumerate(INFO_FIELDS):
             col = info[:, k]
             setattr(out, name, col.astype(np.int64) if name in ("iter", "status_val", "rho_updates") else col)
         return out
+
+    def results_into(self, X=None, Y=None, info=None, DX=None, DY=None, status_polish=None):
+        """The results into device arrays of the caller's (None = skip): X, DX [B, n], Y, DY [B, m], info [B, 8]
+        (INFO_FIELDS) float64, status_polish [B] int32 (1 accepted, -1 rejected, 0 not tried or no polish since the
+        last solve; needs a solve on the current problem).  Device-to-device copies, ready on return; a later solve
+        does not touch them.  For m = 0 the m-sized arguments may be None."""
+        if self._route(X=X, Y=Y, info=info, DX=DX, DY=DY, status_polish=status_polish) != "device":
+            raise ValueError("results_into writes device arrays (objects with __cuda_array_interface__); results() returns "
+                             "host arrays")
+        d = lambda a, cols, name: self._dev(a, cols, name, writable=True)
+        rc = self._lib.osqp_amd_batch_get_dev(self._h, d(X, self.n, "X"), d(Y, self.m, "Y"), d(info, 8, "info"),
+                                              d(DX, self.n, "DX"), d(DY, self.m, "DY"))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_get_dev failed (%d)%s" % (rc, _BAD_POINTER if rc == 1 else ""))
+        if status_polish is not None:
+            rc = self._lib.osqp_amd_batch_polish_status_dev(
+                self._h, device_view(status_polish, (self.B,), "<i4", True, "status_polish"))
+            if rc:
+                raise RuntimeError("osqp_amd_batch_polish_status_dev failed (%d)%s"
+                                   % (rc, ": no solve has run on the current problem" if rc == 7 else
+                                      _BAD_POINTER if rc == 1 else ""))
+
+    def adjoint_into(self, dX, dY, dq, dl, du, dPx=None, dAx=None, active=None, status_adjoint=None):
+        """adjoint() between device arrays of the caller's: from dX [B, n] and dY [B, m] (None = 0) into dq [B, n], dl, du
+        [B, m] and, where given, dPx [B, nnzP], dAx [B, nnzA] (float64), active [B, m], status_adjoint [B] (int32).
+        For m = 0 the m-sized arguments may be None.  Ready on return."""
+        if self._route(dX=dX, dY=dY, dq=dq, dl=dl, du=du, dPx=dPx, dAx=dAx, active=active,
+                       status_adjoint=status_adjoint) != "device":
+            raise ValueError("adjoint_into reads and writes device arrays (objects with __cuda_array_interface__); adjoint() "
+                             "takes and returns host arrays")
+        if dX is None or dq is None or (self.m and (dl is None or du is None)):
+            raise ValueError("adjoint_into needs dX, dq and, for m > 0, dl and du")
+        d = lambda a, cols, name: self._dev(a, cols, name, writable=True)
+        rc = self._lib.osqp_amd_batch_adjoint_dev(
+            self._h, self._dev(dX, self.n, "dX"), self._dev(dY, self.m, "dY"), d(dq, self.n, "dq"), d(dl, self.m, "dl"),
+            d(du, self.m, "du"), d(dPx, self.Pu.nnz, "dPx"), d(dAx, self.Ah.nnz, "dAx"),
+            self._dev(active, self.m, "active", "<i4", True),
+            None if status_adjoint is None else device_view(status_adjoint, (self.B,), "<i4", True, "status_adjoint"))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_adjoint_dev failed (%d)%s"
+                               % (rc, ": no solve has run on the current problem" if rc == 7 else
+                                  _BAD_POINTER if rc == 1 else ""))
 
     def member_workspace(self, qp):
         """Test hook: member qp's workspace as the last setup / update / solve left it -- D, E, c, rho (scalar),

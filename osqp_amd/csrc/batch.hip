@@ -721,6 +721,7 @@ struct osqp_amd_batch {
   double *adj_out = nullptr;  // [B][n + 2 m] dQ, dL, dU
   double *adj_dP = nullptr, *adj_dA = nullptr;   // [B][nnzP], [B][nnzA]
   int *adj_act = nullptr, *adj_stat = nullptr;   // [B][m], [B]
+  int *d_bad = nullptr;     // device-array updates (batch_devio.h): count of l > u pairs of k_batch_check_bounds
 };
 
 static void batch_launch(osqp_amd_batch *b, int phase);
@@ -1157,9 +1158,11 @@ static int stage_reserve(osqp_amd_batch *b, size_t vals, size_t idx) {
 
 // One of P, A: new values into the raw value array (switched to per-member storage first when the handle holds
 // shared values and the update brings per-member ones).  at / iat: where this matrix's values and indices sit in
-// the staging buffers.
+// the staging buffers.  dev: vals is a device array (osqp_amd_batch_update_matrices_dev): it is copied device to
+// device where the layouts match and read in place by k_batch_scatter otherwise; idx is a host list either way.
 static int patch_values(osqp_amd_batch *b, double **raw, const double **io_raw, long long *stride, int nnz,
-                        const c_float *vals, const c_int *idx, c_int cnt, c_int per_member, size_t at, size_t iat) {
+                        const c_float *vals, const c_int *idx, c_int cnt, c_int per_member, size_t at, size_t iat,
+                        bool dev = false) {
   const long long B = b->B;
   if (per_member && !*stride) {
     double *all = nullptr;
@@ -1171,10 +1174,11 @@ static int patch_values(osqp_amd_batch *b, double **raw, const double **io_raw, 
   if (!cnt) return 0;
   const size_t tot = per_member ? (size_t)B * cnt : (size_t)cnt;
   if (!idx && (per_member || !*stride)) {       // same layout as the raw array: straight in
-    BCHK(hipMemcpyAsync(*raw, vals, tot * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    BCHK(hipMemcpyAsync(*raw, vals, tot * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream));
     return 0;
   }
-  BCHK(hipMemcpyAsync(b->d_vals + at, vals, tot * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  const double *src = dev ? vals : b->d_vals + at;
+  if (!dev) BCHK(hipMemcpyAsync(b->d_vals + at, vals, tot * sizeof(double), hipMemcpyHostToDevice, b->stream));
   if (idx) {
     std::vector<int> h(idx, idx + cnt);
     BCHK(hipMemcpyAsync(b->d_idx + iat, h.data(), (size_t)cnt * sizeof(int), hipMemcpyHostToDevice, b->stream));
@@ -1182,7 +1186,7 @@ static int patch_values(osqp_amd_batch *b, double **raw, const double **io_raw, 
   }
   const long long members = *stride ? B : 1;
   hipLaunchKernelGGL(k_batch_scatter, dim3((unsigned)((members * cnt + 255) / 256)), dim3(256), 0, b->stream,
-                     *raw, *stride, b->d_vals + at, per_member ? (long long)cnt : 0LL,
+                     *raw, *stride, src, per_member ? (long long)cnt : 0LL,
                      idx ? b->d_idx + iat : (const int *)nullptr, (long long)cnt, members);
   return 0;
 }
@@ -1374,33 +1378,32 @@ extern "C" c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish) 
   return 0;
 }
 
-// adjoint derivatives for the solved members (batch_adjoint.h): polish's active rows, KKT matrix and inversion on
-// polish's buffers, in the same chunks, with a status array of its own; nothing of the solve state is written
-extern "C" c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, const c_float *dY,
-                                        c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
-                                        c_int *active, c_int *status_adjoint) {
-  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
-  BCHK(hipSetDevice(b->device));
+// What osqp_amd_batch_adjoint and osqp_amd_batch_adjoint_dev share: the staging, the plan and the launches.  dev: dX
+// and dY are device arrays, which k_ba_adjoint reads in place.  *out: where the outputs sit (dPx / dAx null unless
+// wantP / wantA); nothing is waited for.
+static c_int adjoint_launch(osqp_amd_batch *b, const c_float *dX, const c_float *dY, bool dev, bool wantP, bool wantA,
+                            BAdj *out) {
   const size_t B = (size_t)b->B;
   const int n = b->n, m = b->m;
   if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
-  if (balloc_once(b, &b->adj_in, B * (n + m)) || balloc_once(b, &b->adj_out, B * (n + 2 * (size_t)m)) ||
+  if ((!dev && balloc_once(b, &b->adj_in, B * (n + m))) || balloc_once(b, &b->adj_out, B * (n + 2 * (size_t)m)) ||
       balloc_once(b, &b->adj_act, B * m) || balloc_once(b, &b->adj_stat, B) ||
-      (dPx && balloc_once(b, &b->adj_dP, B * b->nnzP)) || (dAx && balloc_once(b, &b->adj_dA, B * b->nnzA))) {
+      (wantP && balloc_once(b, &b->adj_dP, B * b->nnzP)) || (wantA && balloc_once(b, &b->adj_dA, B * b->nnzA))) {
     (void)hipGetLastError();
     return OSQP_MEM_ALLOC_ERROR;
   }
   BPol pl = b->pol;          // polish's buffers; its status array stays polish's
   pl.stat = b->adj_stat;
   BAdj ad{};
-  double *gx = b->adj_in, *gy = b->adj_in + B * n;
-  ad.gx = gx; ad.gy = (dY && m) ? gy : nullptr;
+  double *gx = b->adj_in, *gy = dev ? nullptr : b->adj_in + B * n;   // (the input staging is the host route's alone)
+  ad.gx = dev ? dX : gx; ad.gy = (dY && m) ? (dev ? dY : gy) : nullptr;
   ad.dQ = b->adj_out; ad.dL = ad.dQ + B * n; ad.dU = ad.dL + B * m;
-  ad.dPx = dPx ? b->adj_dP : nullptr; ad.dAx = dAx ? b->adj_dA : nullptr;
+  ad.dPx = wantP ? b->adj_dP : nullptr; ad.dAx = wantA ? b->adj_dA : nullptr;
   ad.active = b->adj_act;
-  BCHK(hipMemcpyAsync(gx, dX, B * n * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  if (ad.gy) BCHK(hipMemcpyAsync(gy, dY, B * m * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  if (!dev) {
+    BCHK(hipMemcpyAsync(gx, dX, B * n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (ad.gy) BCHK(hipMemcpyAsync(gy, dY, B * m * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  }
   // members that are skipped or rejected report zeros
   BCHK(hipMemsetAsync(b->adj_out, 0, std::max((size_t)1, B * (n + 2 * (size_t)m)) * sizeof(double), b->stream));
   BCHK(hipMemsetAsync(b->adj_act, 0, std::max((size_t)1, B * m) * sizeof(int), b->stream));
@@ -1412,6 +1415,22 @@ extern "C" c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, co
   if (bp_run_chunks(b, pl, pn, KFN(k_ba_adjoint), [&](unsigned cnt, const int *lp) {
         hipLaunchKernelGGL(k_ba_adjoint, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
       })) return -102;
+  *out = ad;
+  return 0;
+}
+
+// adjoint derivatives for the solved members (batch_adjoint.h): polish's active rows, KKT matrix and inversion on
+// polish's buffers, in the same chunks, with a status array of its own; nothing of the solve state is written
+extern "C" c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, const c_float *dY,
+                                        c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
+                                        c_int *active, c_int *status_adjoint) {
+  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
+  BCHK(hipSetDevice(b->device));
+  const size_t B = (size_t)b->B;
+  const int n = b->n, m = b->m;
+  BAdj ad{};
+  if (const c_int rc = adjoint_launch(b, dX, dY, false, dPx != nullptr, dAx != nullptr, &ad)) return rc;
   BCHK(hipMemcpyAsync(dQ, ad.dQ, B * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
   if (m) {
     BCHK(hipMemcpyAsync(dL, ad.dL, B * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
@@ -1507,3 +1526,5 @@ extern "C" c_int osqp_amd_batch_device_ptrs(osqp_amd_batch *b, void **X, void **
   if (info8) *info8 = b->io.info;
   return 0;
 }
+
+#include "batch_devio.h"

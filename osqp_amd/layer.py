@@ -2,18 +2,24 @@
 BatchOSQP handle, the backward pass is BatchOSQP.adjoint (osqp_amd_batch_adjoint: one more solve with the KKT
 matrix of the active rows, on the device).
 
-Inputs and outputs are float64 tensors on the CPU or the GPU.  In this version they are staged through host numpy
-arrays on their way to and from the handle (the C entry points take host pointers); device-pointer inputs are a
-later change.  The solve, the polish and the adjoint themselves run on the device.
-Tensors on the GPU take the same route (`.cpu()` in, `torch.as_tensor(..., device=...)` out); the tests exercise CPU
-tensors only, so that path is untested.
+Inputs and outputs are float64 tensors on the CPU or the GPU, and the route follows Q (`layer.last_route`).
+CPU tensors ("host") are staged through numpy arrays on their way to and from the handle.  CUDA tensors ("device") set
+the handle up once from host copies (setup takes host pointers) on the tensors' device; every later call on the live
+handle hands the tensors' device pointers to the handle (the osqp_amd_batch_*_dev entry points through
+BatchOSQP.update / update_matrices / results_into / adjoint_into): no [B, .] array crosses to the host, forward or
+backward, and the outputs are tensors on that device.  The handle works on a stream of its own, so the layer
+synchronises torch's current stream before each hand-over, and every call returns with the handle's work complete.
+The solve, the polish and the adjoint themselves run on the device on either route.
 
 A torch wheel may carry a HIP runtime of its own.  A process that imports torch before the library is first loaded
-runs both on torch's copy; one that loads the library first maps two runtimes side by side, which host staging
-does not mind, but a later `ctypes.CDLL("libamdhip64.so")` of the caller's then names torch's copy, not the
-library's.  Import torch first (bench.py does) where that matters."""
+runs both on torch's copy; one that loads the library first maps two runtimes side by side.  Host staging does not
+mind that, but the device route does: torch's allocations are then unknown to the library's runtime, the pointer check
+of the _dev calls refuses them (error 1) and the layer raises.  A later `ctypes.CDLL("libamdhip64.so")` of the
+caller's likewise names torch's copy, not the library's.  Import torch first (bench.py does)."""
 import numpy as np
 import torch
+from types import SimpleNamespace
+
 from scipy import sparse
 
 from .batch import BatchOSQP
@@ -23,9 +29,28 @@ def _host(t):
     return None if t is None else np.ascontiguousarray(t.detach().cpu().numpy())
 
 
+def _dev(t):
+    return None if t is None else t.detach().contiguous()
+
+
+def _hand_over(device):
+    """The handle reads and writes on its own stream: what torch has queued for these tensors has to be done first."""
+    torch.cuda.current_stream(device).synchronize()
+
+
 class _BatchQPFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, layer, Q, L, U, Px, Ax):
+        if Q.is_cuda:
+            ctx.layer, ctx.route = layer, "device"
+            ctx.save_for_backward(Q, L, U, Px, Ax)
+            ctx.set_materialize_grads(False)
+            r = layer._solve_device(*(_dev(t) for t in (Q, L, U, Px, Ax)))
+            ctx.serial = layer._serial
+            # (tensor objects of their own, so that last_results stays outside the graph; they share its storage, as the
+            # host route's outputs share the numpy arrays of last_results)
+            return r.x.detach(), r.y.detach()
+        layer.last_route = ctx.route = "host"
         args = tuple(_host(t) for t in (Q, L, U, Px, Ax))
         r = layer._solve(*args)
         ctx.layer, ctx.args, ctx.serial = layer, args, layer._serial
@@ -39,10 +64,29 @@ class _BatchQPFunction(torch.autograd.Function):
         need = ctx.needs_input_grad[1:]
         if not any(need) or (gX is None and gY is None):
             return (None,) * 6
+        ref = gX if gX is not None else gY
+        if ctx.route == "device":
+            if layer._serial != ctx.serial:
+                layer._solve_device(*(_dev(t) for t in ctx.saved_tensors))
+                ctx.serial = layer._serial
+            h, new = layer.h, lambda *shape, **kw: torch.empty(shape, device=ref.device, **{"dtype": torch.float64, **kw})
+            m = h.m > 0
+            # both inputs are made contiguous here, before the hand-over: a copy queued on torch's stream after it
+            # would race with the handle's stream (the gradient of a sum is an expanded, non-contiguous tensor)
+            dX = torch.zeros((h.B, h.n), dtype=torch.float64, device=ref.device) if gX is None else _dev(gX)
+            dY = _dev(gY) if m else None
+            g = dict(dq=new(h.B, h.n), dl=new(h.B, h.m) if m else None, du=new(h.B, h.m) if m else None,
+                     dPx=new(h.B, h.Pu.nnz) if need[3] else None, dAx=new(h.B, h.Ah.nnz) if need[4] else None)
+            sa = new(h.B, dtype=torch.int32)
+            _hand_over(ref.device)
+            h.adjoint_into(dX, dY, status_adjoint=sa, **g)
+            layer.last_status_adjoint = sa
+            zero = lambda w, cols: new(h.B, cols).zero_() if w else None        # (m = 0: the empty gradients of L, U)
+            outs = (g["dq"], g["dl"] if m else zero(need[1], 0), g["du"] if m else zero(need[2], 0), g["dPx"], g["dAx"])
+            return (None,) + tuple(o if w else None for o, w in zip(outs, need))
         if layer._serial != ctx.serial:      # the handle has solved another problem since: bring this one back
             layer._solve(*ctx.args)
             ctx.serial = layer._serial
-        ref = gX if gX is not None else gY
         dX = np.zeros((layer.h.B, layer.h.n)) if gX is None else _host(gX)
         a = layer.h.adjoint(dX, _host(gY), matrices=need[3] or need[4])
         layer.last_status_adjoint = a.status_adjoint
@@ -67,7 +111,11 @@ class BatchQPLayer(torch.nn.Module):
     gradients; `last_status_adjoint` [B] (1 computed, -1 rejected, 0 not tried) and `last_results` say which.  Where active
     rows are linearly dependent or strict complementarity fails, the gradients are those of the guessed active set.
 
-    Tensors are float64, on the CPU or the GPU; they are staged through host numpy arrays in this version."""
+    Tensors are float64, all on the CPU (staged through host numpy arrays) or all on one GPU: CUDA tensors set the handle
+    up on their device, and every later call and every backward pass on the live handle runs without a host copy of
+    any [B, .] array; X, Y and the gradients are then tensors on that device, `last_results` carries device tensors
+    x, y, status_polish (int32) and `last_status_adjoint` is one too.  `last_route` says which route the last call
+    took: "host" or "device"."""
 
     def __init__(self, P, A, engine="auto", polish=True, **settings):
         super().__init__()
@@ -77,13 +125,16 @@ class BatchQPLayer(torch.nn.Module):
         self.h = None
         self._serial = 0
         self._own = [False, False]       # the handle holds per-member values of P / A given by a caller
-        self.last_results = self.last_status_adjoint = None
+        self.last_results = self.last_status_adjoint = self.last_route = None
+        self._device = None              # device route: the device index the handle was set up on
+        self._vals = {}                  # the layer's own P / A values as tensors on the handle's device
 
     def _solve(self, Q, L, U, Px, Ax):
         if self.h is not None and self.h.B != Q.shape[0]:
             self.h.cleanup(); self.h = None
         if self.h is None:
             self.h = BatchOSQP().setup(self.P, self.A, Q, L, U, Px_all=Px, Ax_all=Ax, engine=self.engine, **self.settings)
+            self._device = None
         else:
             rc = self.h.update(Q=Q, L=L, U=U)
             if rc:
@@ -101,6 +152,52 @@ class BatchQPLayer(torch.nn.Module):
         self._serial += 1
         return self.last_results
 
+    def _own_values(self, which, device):
+        if which not in self._vals or self._vals[which].device != device:
+            self._vals[which] = torch.as_tensor((self.P if which == "P" else self.A).data, dtype=torch.float64, device=device)
+        return self._vals[which]
+
+    def _solve_device(self, Q, L, U, Px, Ax):
+        """_solve for contiguous CUDA tensors.  The first call sets the handle up from host copies, on the tensors'
+        device; every later one hands the device pointers over."""
+        dev = Q.device
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        self.last_route = "device"
+        if self.h is not None and (self.h.B != Q.shape[0] or self._device != index):
+            self.h.cleanup(); self.h = None
+        m = self.A.shape[0] > 0
+        _hand_over(dev)
+        if self.h is None:
+            self.h = BatchOSQP().setup(self.P, self.A, *(_host(t) for t in (Q, L, U)), Px_all=_host(Px), Ax_all=_host(Ax),
+                                       engine=self.engine, device=index, **self.settings)
+            self._device = index
+        else:
+            rc = self.h.update(Q=Q, L=L if m else None, U=U if m else None)
+            if rc:
+                raise RuntimeError("BatchOSQP.update failed (%d: some lower bound exceeds its upper bound, or a tensor is "
+                                   "not device memory the library's HIP runtime knows -- import torch before the library "
+                                   "is first loaded)" % rc)
+            vP = Px if Px is not None else (self._own_values("P", dev) if self._own[0] else None)
+            vA = Ax if Ax is not None else (self._own_values("A", dev) if self._own[1] else None)
+            if vP is not None or vA is not None:
+                _hand_over(dev)
+                rc = self.h.update_matrices(Px=vP, Ax=vA)
+                if rc:
+                    raise RuntimeError("BatchOSQP.update_matrices failed (%d)" % rc)
+        self._own = [Px is not None, Ax is not None]
+        self.h.solve(fetch=False)
+        if self.polish:
+            self.h.polish(fetch=False)
+        B = Q.shape[0]
+        X = torch.empty((B, self.h.n), dtype=torch.float64, device=dev)
+        Y = torch.empty((B, self.h.m), dtype=torch.float64, device=dev)
+        sp = torch.empty((B,), dtype=torch.int32, device=dev)
+        _hand_over(dev)
+        self.h.results_into(X=X, Y=Y if m else None, status_polish=sp)
+        self.last_results = SimpleNamespace(x=X, y=Y, status_polish=sp)
+        self._serial += 1
+        return self.last_results
+
     def forward(self, Q, L, U, Px=None, Ax=None, return_y=False):
         B = Q.shape[0] if Q.dim() == 2 else -1
         n, m = self.P.shape[0], self.A.shape[0]
@@ -111,6 +208,8 @@ class BatchQPLayer(torch.nn.Module):
                 raise TypeError("%s must be a float64 tensor, not %s" % (name, t.dtype))
             if tuple(t.shape) != (B, cols):
                 raise ValueError("%s must be [B, %d], not %s" % (name, cols, tuple(t.shape)))
+            if t.device != Q.device:
+                raise ValueError("%s is on %s and Q on %s: every tensor of a call lives on one device" % (name, t.device, Q.device))
         X, Y = _BatchQPFunction.apply(self, Q, L, U, Px, Ax)
         return (X, Y) if return_y else X
 
