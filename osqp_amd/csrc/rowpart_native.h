@@ -10,6 +10,8 @@
 //   PCG iteration:                        t = rho (A_g p);  part = [P_g | A_g'] [p; t];  ALL-REDUCE(part);  Kp = part + sigma p
 //                                         alpha = rz / p'Kp;  x~ += alpha p;  r -= alpha Kp;  z = Minv r;  p = z + (rz'/rz) p
 //   termination check (src/auxil.c:681-740): six maxima (ALL-REDUCE max), [P x; A' y] (ALL-REDUCE of 2n), norms on the device.
+//   with osqp_amd_rp_set_infeasibility (src/auxil.c:361-512):  dx = x - x_prev;  dy = y - y_prev projected on the polar of the
+//                                         recession cone;  ALL-REDUCE([P_g dx; A_g' dy; u'dy+ + l'dy-]);  ALL-REDUCE max([|E dy|; row violation])
 #include <dlfcn.h>
 #include "../../include/osqp_amd_rowpart.h"
 
@@ -163,6 +165,87 @@ __global__ void __launch_bounds__(TB) k_rp_unscale(int n, const double *s, const
   for (int j = blockIdx.x * TB + threadIdx.x; j < n; j += gridDim.x * TB) out[j] = s[j] * v[j] * f;
 }
 
+// ---- infeasibility tests (is_primal_infeasible / is_dual_infeasible, src/auxil.c:361-512), only after osqp_amd_rp_set_infeasibility ----
+// out7 = sc15 + 15:  0 |E dy|  1 row violation (both ALL-REDUCE max)  2 u'dy+ + l'dy- (summed over the ranks)  3 |Dinv A'dy|  4 |D dx|  5 q'dx  6 |Dinv P dx|
+// (E, Einv, D, Dinv: null under scaled_termination or unscaled data).  None of the seven depends on a tolerance, so the host applies
+// eps and 10 eps to the same read-back.
+__global__ void __launch_bounds__(TB) k_rp_delta_x(int n, const double *x, const double *xp, double *dx) {
+  for (int j = blockIdx.x * TB + threadIdx.x; j < n; j += gridDim.x * TB) dx[j] = x[j] - xp[j];
+}
+// dy = y - y_prev projected on the polar of the recession cone of [l, u] (src/auxil.c:374-387)
+__global__ void __launch_bounds__(TB) k_rp_delta_y(int m, const double *y, const double *yp, const double *l, const double *u, double *dy) {
+  for (int i = blockIdx.x * TB + threadIdx.x; i < m; i += gridDim.x * TB) {
+    double d = y[i] - yp[i];
+    if (u[i] > 1e26) d = l[i] < -1e26 ? 0.0 : fmin(d, 0.0);
+    else if (l[i] < -1e26) d = fmax(d, 0.0);
+    dy[i] = d;
+  }
+}
+// replicated side: |D dx| and q'dx, in one workgroup's fixed order on every rank
+__global__ void __launch_bounds__(TB) k_rp_cert_x(int n, const double *dx, const double *q, const double *D, double *out7) {
+  __shared__ double red[16];
+  double nx = 0.0, s = 0.0;
+  for (int j = threadIdx.x; j < n; j += TB) { const double d = dx[j]; nx = fmax(nx, fabs(D ? D[j] * d : d)); s += q[j] * d; }
+  nx = block_max(nx, red);
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) { out7[4] = nx; out7[5] = s; }
+}
+// the rank's rows: |E dy|, the largest (Einv A dx)_i of a row with a finite u and -(Einv A dx)_i of one with a finite l (never below
+// 0: the test is `> eps |dx|` with eps |dx| >= 0), and this rank's share of u'dy+ + l'dy-
+__global__ void __launch_bounds__(TB) k_rp_cert_rows(int m, const double *dy, const double *E, const double *Einv, const double *l, const double *u,
+                                                     const double *adx, double *out7, double *lhs) {
+  __shared__ double red[16];
+  double ny = 0.0, viol = 0.0, s = 0.0;
+  for (int i = threadIdx.x; i < m; i += TB) {
+    const double d = dy[i], a = Einv ? Einv[i] * adx[i] : adx[i];
+    ny = fmax(ny, fabs(E ? E[i] * d : d));
+    s += u[i] * fmax(d, 0.0) + l[i] * fmin(d, 0.0);
+    if (u[i] < 1e26) viol = fmax(viol, a);
+    if (l[i] > -1e26) viol = fmax(viol, -a);
+  }
+  ny = block_max(ny, red);
+  viol = block_max(viol, red);
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) { out7[0] = ny; out7[1] = viol; *lhs = s; }
+}
+// after the all-reduce of cb = [P dx ; A'dy ; lhs]: |Dinv A'dy|, |Dinv P dx|, and lhs beside the other scalars
+__global__ void __launch_bounds__(TB) k_rp_cert_fin(int n, const double *cb, const double *Dinv, double *out7) {
+  __shared__ double red[16];
+  double na = 0.0, np = 0.0;
+  for (int j = threadIdx.x; j < n; j += TB) {
+    const double di = Dinv ? Dinv[j] : 1.0;
+    np = fmax(np, fabs(Dinv ? di * cb[j] : cb[j])); na = fmax(na, fabs(Dinv ? di * cb[n + j] : cb[n + j]));
+  }
+  na = block_max(na, red);
+  np = block_max(np, red);
+  if (threadIdx.x == 0) { out7[2] = cb[2 * n]; out7[3] = na; out7[6] = np; }
+}
+// certificate as store_solution leaves it (src/auxil.c:545-555, 762-780): (s v) / |s v|_inf in place
+__global__ void __launch_bounds__(TB) k_rp_cert_out(int n, const double *s, double f, double *v) {
+  for (int j = blockIdx.x * TB + threadIdx.x; j < n; j += gridDim.x * TB) v[j] = (s ? s[j] * v[j] : v[j]) * f;
+}
+// ---- updates of a live handle ----
+// new bounds of the rank's rows, nothing of the handle written yet: clamp to +-OSQP_INFTY, scale by E into ln / un; flags3 = [l > u on
+// some row, some row changes class (k_rp_rho's three), some row is an equality row]  (one workgroup)
+__global__ void __launch_bounds__(TB) k_rp_bounds(int m, const double *lin, const double *uin, const double *E, const double *l, const double *u,
+                                                  double *ln, double *un, double *flags3) {
+  __shared__ double red[16];
+  double bad = 0.0, chg = 0.0, eq = 0.0;
+  for (int i = threadIdx.x; i < m; i += TB) {
+    const double lo = fmax(lin[i], -1e30), hi = fmin(uin[i], 1e30);
+    if (lo > hi) bad = 1.0;
+    const double a = E[i] * lo, b = E[i] * hi;
+    ln[i] = a; un[i] = b;
+    const int was = (l[i] < -1e26 && u[i] > 1e26) ? -1 : (u[i] - l[i] < 1e-4), now = (a < -1e26 && b > 1e26) ? -1 : (b - a < 1e-4);
+    if (was != now) chg = 1.0;
+    if (now == 1) eq = 1.0;
+  }
+  bad = block_max(bad, red);
+  chg = block_max(chg, red);
+  eq = block_max(eq, red);
+  if (threadIdx.x == 0) { flags3[0] = bad; flags3[1] = chg; flags3[2] = eq; }
+}
+
 // ---- RCCL through dlopen (no link-time dependency; a process that already loaded librccl gets that copy) ----
 struct RpNcclId { char b[128]; };
 struct RpRccl {
@@ -196,13 +279,16 @@ struct osqp_amd_rp {
   bool scaled = false;
   double *x, *xt, *q, *D, *Dinv, *minv, *r, *zz, *Kp, *b, *part, *both, *stage;      // n (both: 2n, stage: n + m)
   double *z, *y, *l, *u, *E, *Einv, *rv, *zt, *ax;                                   // m
-  double *pa, *pb, *pc, *sc15;                                                      // RP_G partials x 3; 6 + 9 check scalars
+  double *pa, *pb, *pc, *sc15;                                                      // RP_G partials x 3; 6 + 9 check scalars (+ 7 of the infeasibility tests)
+  double *xp, *yp, *dxy, *cb, *ln, *un;                                             // x, y before the update (n, m); [dx ; dy] (n + m); [P dx ; A'dy ; lhs] (2n + 1); staged bounds (m)
+  double eps_pinf = 0.0, eps_dinf = 0.0;                                            // 0: that test is off (osqp_amd_rp_set_infeasibility)
+  int last_status = 0;
   RpS *S = nullptr, *hS = nullptr;                                                  // device / pinned host
   double *h15 = nullptr;
   long long collectives = 0, pcg_iters = 0;
   int last_iters = 4, rho_updates = 0;
   bool rho_set = false;                                                             // rv and minv hold rp->rho (false until the first solve)
-  double sc[15];
+  double sc[22];
 };
 
 static int rp_allreduce(osqp_amd_rp *rp, double *buf, long long count, int op) {
@@ -250,8 +336,10 @@ extern "C" osqp_amd_rp *osqp_amd_rp_create(void *shard_engine, const double *q, 
   for (double **p : nv) bad = bad || dev_alloc(e, p, n);
   for (double **p : mv) bad = bad || dev_alloc(e, p, m);
   bad = bad || dev_alloc(e, &rp->both, 2 * n) || dev_alloc(e, &rp->stage, n + m) || dev_alloc(e, &rp->pa, (size_t)RP_G) || dev_alloc(e, &rp->pb, (size_t)RP_G) ||
-        dev_alloc(e, &rp->pc, (size_t)RP_G) || dev_alloc(e, &rp->sc15, (size_t)16) || dev_alloc(e, &rp->S, (size_t)1);
-  if (!bad) bad = hipHostMalloc((void **)&rp->hS, sizeof(RpS)) != hipSuccess || hipHostMalloc((void **)&rp->h15, 16 * sizeof(double)) != hipSuccess;
+        dev_alloc(e, &rp->pc, (size_t)RP_G) || dev_alloc(e, &rp->sc15, (size_t)24) || dev_alloc(e, &rp->S, (size_t)1) ||
+        dev_alloc(e, &rp->xp, n) || dev_alloc(e, &rp->yp, m) || dev_alloc(e, &rp->dxy, n + m) || dev_alloc(e, &rp->cb, 2 * n + 1) ||
+        dev_alloc(e, &rp->ln, m) || dev_alloc(e, &rp->un, m);
+  if (!bad) bad = hipHostMalloc((void **)&rp->hS, sizeof(RpS)) != hipSuccess || hipHostMalloc((void **)&rp->h15, 24 * sizeof(double)) != hipSuccess;
   if (bad) { delete rp; return nullptr; }
   std::vector<double> Dinv(n), Einv(m);
   bool scaled = c != 1.0;
@@ -289,11 +377,12 @@ extern "C" int osqp_amd_rp_use_rccl(osqp_amd_rp *rp, const void *unique_id, int 
   return 0;
 }
 
-// one termination check: fills rp->sc (the fifteen scalars) and pri_res / dua_res
-static int rp_check(osqp_amd_rp *rp, double *pri_res, double *dua_res) {
+// one termination check: fills rp->sc (the fifteen scalars; with cert the seven of the infeasibility tests behind them, two more
+// all-reduces, the same one read-back) and pri_res / dua_res
+static int rp_check(osqp_amd_rp *rp, double *pri_res, double *dua_res, bool cert) {
   hipeng *e = rp->e;
   const int n = rp->n, m = rp->m;
-  HIPCHK(hipMemsetAsync(rp->sc15, 0, 16 * sizeof(double), e->stream));
+  HIPCHK(hipMemsetAsync(rp->sc15, 0, (cert ? 24 : 16) * sizeof(double), e->stream));
   if (m > 0) {
     hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, (const double *)rp->x, rp->ax, 0);
     hipLaunchKernelGGL(k_rp_pri, dim3(1), dim3(TB), 0, e->stream, m, (const double *)rp->ax, (const double *)rp->z, (const double *)rp->Einv, rp->sc15);
@@ -306,10 +395,24 @@ static int rp_check(osqp_amd_rp *rp, double *pri_res, double *dua_res) {
   hipLaunchKernelGGL(k_spmv, gm, dim3(TB), 0, e->stream, e->c.M, (const double *)rp->stage, rp->both + n, 2);        // A_g' y
   if (int rc = rp_allreduce(rp, rp->both, 2ll * n, 0)) return rc;
   hipLaunchKernelGGL(k_rp_dua, dim3(1), dim3(TB), 0, e->stream, n, (const double *)rp->both, (const double *)rp->q, (const double *)rp->Dinv, (const double *)rp->x, rp->sc15 + 6);
-  HIPCHK(hipMemcpyAsync(rp->h15, rp->sc15, 15 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  memcpy(rp->sc, rp->h15, sizeof(rp->sc));
   const bool un = rp->scaled && !rp->st.scaled_termination;
+  if (cert) {
+    double *dx = rp->dxy, *dy = rp->dxy + n, *out7 = rp->sc15 + 15;
+    hipLaunchKernelGGL(k_rp_delta_x, rp_grid(), dim3(TB), 0, e->stream, n, (const double *)rp->x, (const double *)rp->xp, dx);
+    if (m > 0) hipLaunchKernelGGL(k_rp_delta_y, rp_grid(), dim3(TB), 0, e->stream, m, (const double *)rp->y, (const double *)rp->yp, (const double *)rp->l, (const double *)rp->u, dy);
+    hipLaunchKernelGGL(k_rp_cert_x, dim3(1), dim3(TB), 0, e->stream, n, (const double *)dx, (const double *)rp->q, un ? (const double *)rp->D : nullptr, out7);
+    hipLaunchKernelGGL(k_spmv, gm, dim3(TB), 0, e->stream, e->c.M, (const double *)rp->dxy, rp->cb, 1);                // P_g dx
+    hipLaunchKernelGGL(k_spmv, gm, dim3(TB), 0, e->stream, e->c.M, (const double *)rp->dxy, rp->cb + n, 2);            // A_g' dy
+    if (m > 0) hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, (const double *)dx, rp->ax, 0);
+    hipLaunchKernelGGL(k_rp_cert_rows, dim3(1), dim3(TB), 0, e->stream, m, (const double *)dy, un ? (const double *)rp->E : nullptr, un ? (const double *)rp->Einv : nullptr,
+                       (const double *)rp->l, (const double *)rp->u, (const double *)rp->ax, out7, rp->cb + 2 * n);
+    if (int rc = rp_allreduce(rp, rp->cb, 2ll * n + 1, 0)) return rc;
+    if (int rc = rp_allreduce(rp, out7, 2, 1)) return rc;
+    hipLaunchKernelGGL(k_rp_cert_fin, dim3(1), dim3(TB), 0, e->stream, n, (const double *)rp->cb, un ? (const double *)rp->Dinv : nullptr, out7);
+  }
+  HIPCHK(hipMemcpyAsync(rp->h15, rp->sc15, (cert ? 22 : 15) * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  memcpy(rp->sc, rp->h15, (cert ? 22 : 15) * sizeof(double));
   const double *s = rp->sc;             // 0 pri_u 1 z_u 2 Ax_u 3 pri_s 4 z_s 5 Ax_s | 6 dua_u 7 dua_s 8 q_u 9 q_s 10 Aty_u 11 Aty_s 12 Px_u 13 Px_s 14 obj
   *pri_res = rp->m_total == 0 ? 0.0 : (un ? s[0] : s[3]);
   *dua_res = un ? s[6] / rp->c : s[7];
@@ -321,6 +424,30 @@ static bool rp_terminated(const osqp_amd_rp *rp, double pri_res, double dua_res,
   const bool prim_ok = rp->m_total == 0 || pri_res < ea + er * (un ? std::max(s[1], s[2]) : std::max(s[4], s[5]));
   const double nrm = un ? std::max(s[8], std::max(s[10], s[12])) / rp->c : std::max(s[9], std::max(s[11], s[13]));
   return prim_ok && dua_res < ea + er * nrm;
+}
+// check_termination with the infeasibility tests (src/auxil.c:716-783) on a read-back that holds all twenty-two scalars: 0 none, 1 the
+// residuals pass, 3 primal infeasible, 4 dual infeasible.  Only all-reduced and replicated values are looked at: every rank decides alike.
+// (un: the unscaled forms decide; c: the cost scaling; eps4: eps_abs, eps_rel, eps_prim_inf, eps_dual_inf)
+static int rp_verdict_of(const double *s, bool un, double c, int m_total, const double *eps4, double pri_res, double dua_res, bool approximate) {
+  const double k = approximate ? 10.0 : 1.0, ea = k * eps4[0], er = k * eps4[1];
+  const bool prim_ok = m_total == 0 || pri_res < ea + er * (un ? std::max(s[1], s[2]) : std::max(s[4], s[5]));
+  const double nrm = un ? std::max(s[8], std::max(s[10], s[12])) / c : std::max(s[9], std::max(s[11], s[13]));
+  const bool dual_ok = dua_res < ea + er * nrm;
+  if (prim_ok && dual_ok) return 1;
+  // s[15] |E dy|  s[16] row violation  s[17] u'dy+ + l'dy-  s[18] |Dinv A'dy|  s[19] |D dx|  s[20] q'dx  s[21] |Dinv P dx|
+  const double ep = k * eps4[2], ed = k * eps4[3], cs = un ? c : 1.0;
+  if (!prim_ok && ep > 0.0 && s[15] > 1e-30 && s[17] < ep * s[15] && s[18] < ep * s[15]) return 3;
+  if (!dual_ok && ed > 0.0 && s[19] > 1e-30 && s[20] < cs * ed * s[19] && s[21] < cs * ed * s[19] && !(s[16] > ed * s[19])) return 4;
+  return 0;
+}
+static int rp_verdict(const osqp_amd_rp *rp, double pri_res, double dua_res, bool approximate) {
+  const double eps4[4] = {rp->st.eps_abs, rp->st.eps_rel, rp->eps_pinf, rp->eps_dinf};
+  return rp_verdict_of(rp->sc, rp->scaled && !rp->st.scaled_termination, rp->c, rp->m_total, eps4, pri_res, dua_res, approximate);
+}
+// for the tests: the verdict on given scalars, host arithmetic only (no handle, no device)
+extern "C" int osqp_amd_rp_test_verdict(const double *sc22, int unscaled, double c, int m_total, const double *eps4, double pri_res, double dua_res, int approximate) {
+  if (!sc22 || !eps4) return HIPENG_ERR_ARG;
+  return rp_verdict_of(sc22, unscaled != 0, c, m_total, eps4, pri_res, dua_res, approximate != 0);
 }
 static double rp_rho_estimate(const osqp_amd_rp *rp) {
   const double *s = rp->sc;
@@ -348,6 +475,7 @@ extern "C" int osqp_amd_rp_solve(osqp_amd_rp *rp, osqp_amd_rp_info *info) {
     if (int rc = rp_set_rho(rp, st.rho)) return rc;
     rp->rho_set = true;
   }
+  const bool cert = rp->eps_pinf > 0.0 || rp->eps_dinf > 0.0;
   int status = 0, it = 0;
   bool checked = false;
   double pri_res = 0.0, dua_res = 0.0;
@@ -387,16 +515,21 @@ extern "C" int osqp_amd_rp_solve(osqp_amd_rp *rp, osqp_amd_rp_info *info) {
     rp->pcg_iters += rp->hS->iters;
     // x, z, y
     if (m > 0) hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), tb, 0, e->stream, e->c.A, (const double *)rp->xt, rp->zt, 0);
+    checked = st.check_termination && it % st.check_termination == 0;
+    if (cert && (checked || it == st.max_iter)) {          // this iteration ends in a check: x and y as they are now, for dx and dy
+      HIPCHK(hipMemcpyAsync(rp->xp, rp->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      if (m > 0) HIPCHK(hipMemcpyAsync(rp->yp, rp->y, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    }
     hipLaunchKernelGGL(k_rp_admm_x, g, tb, 0, e->stream, n, st.alpha, (const double *)rp->xt, rp->x);
     if (m > 0) hipLaunchKernelGGL(k_rp_admm_z, g, tb, 0, e->stream, m, st.alpha, (const double *)rp->zt, (const double *)rp->rv, (const double *)rp->l, (const double *)rp->u, rp->z, rp->y);
     HIPCHK(hipGetLastError());
-    checked = st.check_termination && it % st.check_termination == 0;
     if (checked) {
-      if (int rc = rp_check(rp, &pri_res, &dua_res)) return rc;
-      if (rp_terminated(rp, pri_res, dua_res, false)) { status = 1; break; }
+      if (int rc = rp_check(rp, &pri_res, &dua_res, cert)) return rc;
+      if (cert) { if ((status = rp_verdict(rp, pri_res, dua_res, false))) break; }
+      else if (rp_terminated(rp, pri_res, dua_res, false)) { status = 1; break; }
     }
     if (st.adaptive_rho && it % interval == 0) {
-      if (!checked) if (int rc = rp_check(rp, &pri_res, &dua_res)) return rc;
+      if (!checked) if (int rc = rp_check(rp, &pri_res, &dua_res, false)) return rc;
       const double nw = rp_rho_estimate(rp);
       if (nw > rp->rho * st.adaptive_rho_tolerance || nw < rp->rho / st.adaptive_rho_tolerance) {
         if (int rc = rp_set_rho(rp, nw)) return rc;
@@ -406,18 +539,132 @@ extern "C" int osqp_amd_rp_solve(osqp_amd_rp *rp, osqp_amd_rp_info *info) {
   }
   if (it > st.max_iter) it = st.max_iter;
   if (!checked) {
-    if (int rc = rp_check(rp, &pri_res, &dua_res)) return rc;
-    if (rp_terminated(rp, pri_res, dua_res, false)) status = 1;
+    if (int rc = rp_check(rp, &pri_res, &dua_res, cert)) return rc;
+    if (cert) status = rp_verdict(rp, pri_res, dua_res, false);
+    else if (rp_terminated(rp, pri_res, dua_res, false)) status = 1;
   }
-  if (!status) status = rp_terminated(rp, pri_res, dua_res, true) ? 2 : -2;
-  info->status = status; info->iter = it; info->rho_updates = rp->rho_updates; info->pcg_iters = rp->pcg_iters; info->collectives = rp->collectives;
+  if (status >= 3) status = -status;        // OSQP_PRIMAL_INFEASIBLE = -3, OSQP_DUAL_INFEASIBLE = -4
+  else if (!status && cert) {              // the approximate branch: 10 x every tolerance on the same scalars
+    const int v = rp_verdict(rp, pri_res, dua_res, true);
+    status = v == 1 ? 2 : (v ? v : -2);     // OSQP_PRIMAL_INFEASIBLE_INACCURATE = 3, OSQP_DUAL_INFEASIBLE_INACCURATE = 4
+  } else if (!status) status = rp_terminated(rp, pri_res, dua_res, true) ? 2 : -2;
+  info->status = status; info->iter = it; info->rho_updates = rp->rho_updates; info->pcg_iters = rp->pcg_iters;
   info->obj_val = rp->sc[14] / rp->c; info->pri_res = pri_res; info->dua_res = dua_res; info->rho_estimate = rp_rho_estimate(rp);
+  rp->last_status = status;
+  if (status == 3 || status == -3 || status == 4 || status == -4) {
+    // store_solution (src/auxil.c:536-560): no solution, the certificate normalised in place, the iterates back to zero
+    const bool un = rp->scaled && !st.scaled_termination, prim = status == 3 || status == -3;
+    info->obj_val = prim ? 1e30 : -1e30;                                           // +-OSQP_INFTY
+    if (prim) { if (m > 0) hipLaunchKernelGGL(k_rp_cert_out, g, tb, 0, e->stream, m, un ? (const double *)rp->E : nullptr, 1.0 / rp->sc[15], rp->dxy + n); }
+    else hipLaunchKernelGGL(k_rp_cert_out, g, tb, 0, e->stream, n, un ? (const double *)rp->D : nullptr, 1.0 / rp->sc[19], rp->dxy);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(rp->x, 0, (size_t)n * sizeof(double), e->stream));
+    HIPCHK(hipMemsetAsync(rp->xt, 0, (size_t)n * sizeof(double), e->stream));
+    if (m > 0) { HIPCHK(hipMemsetAsync(rp->z, 0, (size_t)m * sizeof(double), e->stream)); HIPCHK(hipMemsetAsync(rp->y, 0, (size_t)m * sizeof(double), e->stream)); }
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  info->collectives = rp->collectives;
+  return 0;
+}
+
+static inline bool rp_infeasible(int status) { return status == 3 || status == -3 || status == 4 || status == -4; }
+
+extern "C" int osqp_amd_rp_set_infeasibility(osqp_amd_rp *rp, double eps_prim_inf, double eps_dual_inf) {
+  if (!rp || !(eps_prim_inf >= 0.0) || !(eps_dual_inf >= 0.0)) return HIPENG_ERR_ARG;
+  rp->eps_pinf = eps_prim_inf; rp->eps_dinf = eps_dual_inf;
+  return 0;
+}
+extern "C" int osqp_amd_rp_get_certificates(osqp_amd_rp *rp, double *dual_inf_cert, double *prim_inf_cert_loc) {
+  if (!rp || !dual_inf_cert || (rp->m > 0 && !prim_inf_cert_loc)) return HIPENG_ERR_ARG;
+  hipeng *e = rp->e;
+  const bool prim = rp->last_status == 3 || rp->last_status == -3, dual = rp->last_status == 4 || rp->last_status == -4;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (dual) HIPCHK(hipMemcpy(dual_inf_cert, rp->dxy, (size_t)rp->n * sizeof(double), hipMemcpyDeviceToHost));
+  else std::fill(dual_inf_cert, dual_inf_cert + rp->n, NAN);
+  if (prim && rp->m > 0) HIPCHK(hipMemcpy(prim_inf_cert_loc, rp->dxy + rp->n, (size_t)rp->m * sizeof(double), hipMemcpyDeviceToHost));
+  else if (rp->m > 0) std::fill(prim_inf_cert_loc, prim_inf_cert_loc + rp->m, NAN);
+  return 0;
+}
+
+// ---- a live handle: unscaled host arrays in, scaled on the device with the handle's D, E, c.  Every rank calls each of them. ----
+static int rp_upload(osqp_amd_rp *rp, double *dst, const double *src, size_t k) {
+  if (k) HIPCHK(hipMemcpyAsync(dst, src, k * sizeof(double), hipMemcpyHostToDevice, rp->e->stream));
+  return 0;
+}
+extern "C" int osqp_amd_rp_update_lin_cost(osqp_amd_rp *rp, const double *q) {
+  if (!rp || !q) return HIPENG_ERR_ARG;
+  hipeng *e = rp->e;
+  HIPCHK(hipSetDevice(e->device));
+  if (int rc = rp_upload(rp, rp->part, q, (size_t)rp->n)) return rc;
+  hipLaunchKernelGGL(k_rp_unscale, rp_grid(), dim3(TB), 0, e->stream, rp->n, (const double *)rp->D, (const double *)rp->part, rp->c, rp->q);      // (D q) c
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(e->stream));            // (q is the caller's)
+  rp->rho_updates = 0;                                // reset_info (src/osqp.c:788)
+  return 0;
+}
+extern "C" int osqp_amd_rp_update_bounds(osqp_amd_rp *rp, const double *l_loc, const double *u_loc) {
+  if (!rp || (rp->m > 0 && (!l_loc || !u_loc))) return HIPENG_ERR_ARG;
+  hipeng *e = rp->e;
+  const size_t m = (size_t)rp->m;
+  HIPCHK(hipSetDevice(e->device));
+  if (int rc = rp_upload(rp, rp->zt, l_loc, m)) return rc;
+  if (int rc = rp_upload(rp, rp->ax, u_loc, m)) return rc;
+  hipLaunchKernelGGL(k_rp_bounds, dim3(1), dim3(TB), 0, e->stream, rp->m, (const double *)rp->zt, (const double *)rp->ax, (const double *)rp->E,
+                     (const double *)rp->l, (const double *)rp->u, rp->ln, rp->un, rp->pa);
+  HIPCHK(hipGetLastError());
+  if (int rc = rp_allreduce(rp, rp->pa, 3, 1)) return rc;
+  double f[3];
+  HIPCHK(hipMemcpyAsync(f, rp->pa, sizeof(f), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (f[0] > 0.0) return 1;                           // l > u on some rank: nothing written on any (src/osqp.c:814-821)
+  if (m) {
+    HIPCHK(hipMemcpyAsync(rp->l, rp->ln, m * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(rp->u, rp->un, m * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+  }
+  rp->has_eq = f[2] > 0.0;
+  rp->rho_updates = 0;                                // reset_info (src/osqp.c:834)
+  // a row changed class on some rank: rho per row and the preconditioner again, on every rank (update_rho_vec, src/auxil.c:54-74);
+  // before the first solve there is nothing to rebuild yet
+  if (f[1] > 0.0 && rp->rho_set) return rp_set_rho(rp, rp->rho);
+  return 0;
+}
+extern "C" int osqp_amd_rp_warm_start(osqp_amd_rp *rp, const double *x, const double *y_loc) {
+  if (!rp) return HIPENG_ERR_ARG;
+  hipeng *e = rp->e;
+  const int n = rp->n, m = rp->m;
+  HIPCHK(hipSetDevice(e->device));
+  if (x) {
+    if (int rc = rp_upload(rp, rp->part, x, (size_t)n)) return rc;
+    hipLaunchKernelGGL(k_rp_unscale, rp_grid(), dim3(TB), 0, e->stream, n, (const double *)rp->Dinv, (const double *)rp->part, 1.0, rp->x);      // Dinv x
+    HIPCHK(hipMemcpyAsync(rp->xt, rp->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));                                    // the PCG starts from x~
+    if (m > 0) hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, (const double *)rp->x, rp->z, 0);
+  }
+  if (y_loc && m > 0) {
+    if (int rc = rp_upload(rp, rp->zt, y_loc, (size_t)m)) return rc;
+    hipLaunchKernelGGL(k_rp_unscale, rp_grid(), dim3(TB), 0, e->stream, m, (const double *)rp->Einv, (const double *)rp->zt, rp->c, rp->y);      // (Einv y) c
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+extern "C" int osqp_amd_rp_update_rho(osqp_amd_rp *rp, double rho) {
+  if (!rp) return HIPENG_ERR_ARG;
+  if (!(rho > 0.0)) return 1;
+  HIPCHK(hipSetDevice(rp->e->device));
+  if (int rc = rp_set_rho(rp, rho)) return rc;
+  rp->rho_set = true;
   return 0;
 }
 
 extern "C" int osqp_amd_rp_get_solution(osqp_amd_rp *rp, double *x, double *y_loc) {
   if (!rp || !x) return HIPENG_ERR_ARG;
   hipeng *e = rp->e;
+  if (rp_infeasible(rp->last_status)) {             // no solution (src/auxil.c:537-539)
+    std::fill(x, x + rp->n, NAN);
+    if (y_loc) std::fill(y_loc, y_loc + rp->m, NAN);
+    return 0;
+  }
   HIPCHK(hipSetDevice(e->device));
   hipLaunchKernelGGL(k_rp_unscale, rp_grid(), dim3(TB), 0, e->stream, rp->n, (const double *)rp->D, (const double *)rp->x, 1.0, rp->part);
   HIPCHK(hipMemcpyAsync(x, rp->part, (size_t)rp->n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
@@ -448,6 +695,12 @@ extern "C" int osqp_amd_rp_peek(osqp_amd_rp *rp, int which, double *out, long lo
   const double *src = nullptr;
   long long count = 0;
   if (which == OSQP_AMD_RP_PEEK_SC15) { src = rp->sc15; count = 15; }
+  else if (which == OSQP_AMD_RP_PEEK_DX) { src = rp->dxy; count = rp->n; }
+  else if (which == OSQP_AMD_RP_PEEK_DY) { src = rp->dxy + rp->n; count = rp->m; }
+  else if (which == OSQP_AMD_RP_PEEK_SC7) { src = rp->sc15 + 15; count = 7; }
+  else if (which == OSQP_AMD_RP_PEEK_Q) { src = rp->q; count = rp->n; }
+  else if (which == OSQP_AMD_RP_PEEK_L) { src = rp->l; count = rp->m; }
+  else if (which == OSQP_AMD_RP_PEEK_U) { src = rp->u; count = rp->m; }
   else if (which >= 0 && which < 8) { src = nsrc[which] ? nsrc[which] : msrc[which]; count = nsrc[which] ? rp->n : rp->m; }
   else return HIPENG_ERR_ARG;
   if (cap < count) return HIPENG_ERR_ARG;

@@ -16,7 +16,9 @@ decisions.  The m-vectors z, y, l, u, rho live only on the rank that owns their 
 Algorithm = the reference's ADMM (src/osqp.c:354-532, src/auxil.c:161-225) in the scaled space of scale_data
 (src/scaling.c:44-156) with the indirect KKT solve of engine.hip (Jacobi-PCG on P + sigma I + A' rho A), termination
 and rho adaptation as src/auxil.c:13-74, 240-359, 681-740.  Scope: statuses solved / solved inaccurate / maximum
-iterations reached (no infeasibility certificates, no polish in this variant).
+iterations reached, and with eps_prim_inf / eps_dual_inf > 0 primal / dual infeasible and their inaccurate forms with
+certificates (src/auxil.c:361-512; two more all-reduces per check); q, the bounds, the iterates and rho of a set-up
+solver can be replaced (update, warm_start, update_rho).  No polish and no matrix updates in this variant.
 
 The SpMVs -- the part that touches the matrices -- run in the HIP kernels of the rank's shard engine
 (hipeng_spmv_dev); vectors are torch tensors in HBM and the O(n) vector arithmetic between collectives is
@@ -31,8 +33,36 @@ import numpy as np
 from scipy import sparse
 
 RHO_MIN, RHO_MAX, RHO_TOL, RHO_EQ = 1e-6, 1e6, 1e-4, 1e3
-INF_BOUND = 1e30 * 1e-4
+OSQP_INFTY = 1e30
+INF_BOUND = OSQP_INFTY * 1e-4
 DIV_TOL = 1e-30
+_DEFAULTS = dict(rho=0.1, sigma=1e-6, alpha=1.6, eps_abs=1e-3, eps_rel=1e-3, max_iter=4000, check_termination=25,
+                 adaptive_rho=1, adaptive_rho_interval=0, adaptive_rho_tolerance=5.0, scaled_termination=0,
+                 pcg_eps_rel=1e-9, pcg_max_iter=0, eps_prim_inf=0.0, eps_dual_inf=0.0)
+INFEASIBLE = ("primal infeasible", "primal infeasible inaccurate", "dual infeasible", "dual infeasible inaccurate")
+
+
+def _settings(settings):
+    st = dict(_DEFAULTS)
+    for k, v in settings.items():
+        if k not in st:
+            raise ValueError("unsupported setting %r in the row-partitioned variant" % k)
+        st[k] = v
+    if st["eps_prim_inf"] < 0 or st["eps_dual_inf"] < 0:
+        raise ValueError("eps_prim_inf and eps_dual_inf must not be negative (0 switches the test off)")
+    return st
+
+
+def _row_class(l, u):
+    """-1 free, 1 equality, 0 inequality from the scaled bounds (set_rho_vec, src/auxil.c:28-52)."""
+    return np.where((l < -INF_BOUND) & (u > INF_BOUND), -1, np.where(u - l < RHO_TOL, 1, 0))
+
+
+def _rows_of(v, m, r0, r1, name):
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if v.shape != (m,):
+        raise ValueError("%s must have %d entries" % (name, m))
+    return np.ascontiguousarray(v[r0:r1])
 
 
 def shard_rows(A, world):
@@ -207,13 +237,7 @@ class RowPartitionedOSQP:
     def setup(self, scaled, ops_factory, device=0, **settings):
         """`scaled`: dict(P (triu), q, A, l, u, D, E, c) -- the scaled problem, identical on every rank;
         `ops_factory(Pu_g, A_g, device)` builds the rank's SpMV back end (HipOps on a GPU)."""
-        st = dict(rho=0.1, sigma=1e-6, alpha=1.6, eps_abs=1e-3, eps_rel=1e-3, max_iter=4000, check_termination=25,
-                  adaptive_rho=1, adaptive_rho_interval=0, adaptive_rho_tolerance=5.0, scaled_termination=0,
-                  pcg_eps_rel=1e-9, pcg_max_iter=0)
-        for k, v in settings.items():
-            if k not in st:
-                raise ValueError("unsupported setting %r in the row-partitioned variant" % k)
-            st[k] = v
+        st = _settings(settings)
         self.st = st
         n, m = scaled["P"].shape[0], scaled["A"].shape[0]
         self.n, self.m = n, m
@@ -229,8 +253,7 @@ class RowPartitionedOSQP:
         self.E = o.vec(scaled["E"][r0:r1]); self.Einv = 1.0 / self.E
         self.c = float(scaled["c"]); self.cinv = 1.0 / self.c
         self.scaled_data = bool(np.any(scaled["D"] != 1.0) or np.any(scaled["E"] != 1.0) or scaled["c"] != 1.0)
-        lg, ug = scaled["l"][r0:r1], scaled["u"][r0:r1]
-        self.cls = np.where((lg < -INF_BOUND) & (ug > INF_BOUND), -1, np.where(ug - lg < RHO_TOL, 1, 0))
+        self.cls = _row_class(scaled["l"][r0:r1], scaled["u"][r0:r1])
         self.has_eq = bool(self._allreduce(o.vec([float((self.cls == 1).any())]), "max").item() > 0)
         pd, a2 = o.diag_terms()
         self._pdiag, self._a2 = pd, a2                   # this rank's share of diag(P) and of A.^2 (column sums weighted by rho)
@@ -239,7 +262,62 @@ class RowPartitionedOSQP:
         self.z = t.zeros(r1 - r0, dtype=t.float64, device=o.device); self.y = self.z.clone()
         self._set_rho(st["rho"])
         self.rho_updates = 0
+        self.status = "unsolved"
         return self
+
+    # ---- a live solver: unscaled arrays of full length in, the rank's rows taken here (every rank calls each of these) ----
+    def update(self, q=None, l=None, u=None):
+        """osqp_update_lin_cost / osqp_update_bounds (src/osqp.c:765-846).  l and u come together.  Returns 1 on every rank, with
+        nothing changed on any, when l > u on some row; a row that changes class on some rank rebuilds rho per row and the
+        preconditioner on every rank."""
+        o = self.ops
+        if (l is None) != (u is None):
+            raise ValueError("l and u are updated together in the row-partitioned variant")
+        if q is not None:
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            if q.shape != (self.n,):
+                raise ValueError("q must have %d entries" % self.n)
+        if l is not None:
+            lo = np.maximum(_rows_of(l, self.m, self.r0, self.r1, "l"), -OSQP_INFTY)
+            hi = np.minimum(_rows_of(u, self.m, self.r0, self.r1, "u"), OSQP_INFTY)
+            E = self.E.cpu().numpy()
+            ls, us = E * lo, E * hi
+            cls = _row_class(ls, us)
+            flags = self._allreduce(o.vec([float((lo > hi).any()), float((cls != self.cls).any()), float((cls == 1).any())]), "max")
+            bad, changed, has_eq = (bool(v > 0) for v in flags.cpu().numpy())
+            if bad:
+                return 1
+        if q is not None:
+            self.q = (self.D * o.vec(q)) * self.c
+            self.rho_updates = 0                         # reset_info
+        if l is not None:
+            self.l, self.u, self.cls, self.has_eq = o.vec(ls), o.vec(us), cls, has_eq
+            self.rho_updates = 0
+            if changed:
+                self._set_rho(self.rho)
+        return 0
+
+    def warm_start(self, x=None, y=None):
+        """osqp_warm_start (src/osqp.c:942-1010): x_s = Dinv x, z = A x_s on the rank's rows, y_s = c Einv y; x~ starts from x_s."""
+        o = self.ops
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=np.float64)
+            if x.shape != (self.n,):
+                raise ValueError("x must have %d entries" % self.n)
+            self.x = self.Dinv * o.vec(x)
+            self.xt = self.x.clone()
+            if self.r1 > self.r0:
+                self.z = o.A_mul(self.x)
+        if y is not None:
+            self.y = (self.Einv * o.vec(_rows_of(y, self.m, self.r0, self.r1, "y"))) * self.c
+        return 0
+
+    def update_rho(self, rho):
+        """osqp_update_rho (src/osqp.c:1281-1330): rho <= 0 returns 1 and changes nothing; rho_updates is not reset."""
+        if not rho > 0:
+            return 1
+        self._set_rho(float(rho))
+        return 0
 
     def _set_rho(self, rho):
         rho = min(max(rho, RHO_MIN), RHO_MAX)
@@ -308,6 +386,54 @@ class RowPartitionedOSQP:
         self.dua_res = self.cinv * s["dua_u"] if un else s["dua_s"]
         return un
 
+    def _cert_scalars(self):
+        """The seven scalars of is_primal_infeasible / is_dual_infeasible (src/auxil.c:361-512) from dx, dy: one all-reduce (sum) of
+        [P_g dx ; A_g' dy ; u'dy+ + l'dy-] and one (max) of [|E dy| ; row violation], everything computed every time."""
+        t, o, n = self.torch, self.ops, self.n
+        un = self.scaled_data and not self.st["scaled_termination"]
+        have = self.r1 > self.r0
+        zero = t.zeros((), dtype=t.float64, device=o.device)
+        dx = self.x - self.x_prev
+        dy = self.y - self.y_prev
+        infu, infl = self.u > INF_BOUND, self.l < -INF_BOUND
+        dy = t.where(infu & infl, t.zeros_like(dy), t.where(infu, t.minimum(dy, t.zeros_like(dy)), t.where(infl, t.maximum(dy, t.zeros_like(dy)), dy)))
+        self.dx, self.dy = dx, dy
+        ndy, viol, lhs = zero, zero, zero
+        if have:
+            ndy = ((self.E * dy) if un else dy).abs().max()
+            lhs = (self.u * dy.clamp(min=0.0) + self.l * dy.clamp(max=0.0)).sum()
+            adx = o.A_mul(dx)
+            if un:
+                adx = self.Einv * adx
+            # the largest (A dx)_i of a row with a finite u and -(A dx)_i of one with a finite l; never below 0 (the test is `> eps |dx|`)
+            viol = t.maximum(t.where(~infu, adx, t.zeros_like(adx)).max(), t.where(~infl, -adx, t.zeros_like(adx)).max()).clamp(min=0.0)
+        sums = self._allreduce(t.cat([o.P_mul(dx), o.At_mul(dy) if have else t.zeros_like(dx), lhs.reshape(1)]))
+        mx = self._allreduce(t.stack([ndy, viol]), "max")
+        Pdx, Atdy = sums[:n], sums[n:2 * n]
+        f = lambda v, S: float((S * v if un else v).abs().max())
+        self.cs = dict(ndy=float(mx[0]), viol=float(mx[1]), lhs=float(sums[2 * n]), nAtdy=f(Atdy, self.Dinv),
+                       ndx=f(dx, self.D), qdx=float(self.q @ dx), nPdx=f(Pdx, self.Dinv))
+
+    def _verdict(self, approximate=False):
+        """check_termination with the infeasibility tests (src/auxil.c:716-783): None, "solved", "primal infeasible" or "dual infeasible";
+        only all-reduced and replicated values are looked at, so every rank decides alike."""
+        un = self.scaled_data and not self.st["scaled_termination"]
+        s, st, c = self.sc, self.st, self.cs
+        k = 10.0 if approximate else 1.0
+        eps_abs, eps_rel = k * st["eps_abs"], k * st["eps_rel"]
+        prim_ok = self.m == 0 or self.pri_res < eps_abs + eps_rel * (max(s["z_u"], s["Ax_u"]) if un else max(s["z_s"], s["Ax_s"]))
+        nrm = self.cinv * max(s["q_u"], s["Aty_u"], s["Px_u"]) if un else max(s["q_s"], s["Aty_s"], s["Px_s"])
+        dual_ok = self.dua_res < eps_abs + eps_rel * nrm
+        if prim_ok and dual_ok:
+            return "solved"
+        ep, ed, cost = k * st["eps_prim_inf"], k * st["eps_dual_inf"], (self.c if un else 1.0)
+        if not prim_ok and ep > 0 and c["ndy"] > DIV_TOL and c["lhs"] < ep * c["ndy"] and c["nAtdy"] < ep * c["ndy"]:
+            return "primal infeasible"
+        if (not dual_ok and ed > 0 and c["ndx"] > DIV_TOL and c["qdx"] < cost * ed * c["ndx"] and c["nPdx"] < cost * ed * c["ndx"]
+                and not c["viol"] > ed * c["ndx"]):
+            return "dual infeasible"
+        return None
+
     def _terminated(self, approximate=False):
         un = self.scaled_data and not self.st["scaled_termination"]
         s, st = self.sc, self.st
@@ -335,22 +461,32 @@ class RowPartitionedOSQP:
         interval = st["adaptive_rho_interval"] or (4 * st["check_termination"] if st["check_termination"] else 100)
         self.pcg_iters = 0
         alpha, sigma = st["alpha"], st["sigma"]
+        cert = st["eps_prim_inf"] > 0 or st["eps_dual_inf"] > 0
+
+        def check():             # one termination check; with the infeasibility tests on, the verdict of check_termination
+            self._info()
+            if not cert:
+                return "solved" if self._terminated() else None
+            self._cert_scalars()
+            return self._verdict()
         status, it, checked = "unsolved", 0, False
         for it in range(1, st["max_iter"] + 1):
             w = self.rho_vec * self.z - self.y
             b = sigma * self.x - self.q + self._allreduce(o.At_mul(w) if self.r1 > self.r0 else t.zeros_like(self.x))
             self.xt = self._pcg(b, self.xt, eps_pcg)
             zt = o.A_mul(self.xt) if self.r1 > self.r0 else self.z
+            checked = bool(st["check_termination"]) and it % st["check_termination"] == 0
+            if cert and (checked or it == st["max_iter"]):          # this iteration ends in a check: x and y as they are now
+                self.x_prev, self.y_prev = self.x, self.y
             self.x = alpha * self.xt + (1.0 - alpha) * self.x
             v = alpha * zt + (1.0 - alpha) * self.z
             zn = t.minimum(t.maximum(v + self.y / self.rho_vec, self.l), self.u)
             self.y = self.y + self.rho_vec * (v - zn)
             self.z = zn
-            checked = bool(st["check_termination"]) and it % st["check_termination"] == 0
             if checked:
-                self._info()
-                if self._terminated():
-                    status = "solved"
+                v = check()
+                if v:
+                    status = v
                     break
             if st["adaptive_rho"] and it % interval == 0:
                 if not checked:
@@ -360,29 +496,50 @@ class RowPartitionedOSQP:
                     self._set_rho(new)
                     self.rho_updates += 1
         if not checked:
-            self._info()
-            if self._terminated():
-                status = "solved"
+            status = check() or "unsolved"
         if status == "unsolved":
-            status = "solved inaccurate" if self._terminated(approximate=True) else "maximum iterations reached"
-        # unscale; y is gathered from the row shards
-        x = (self.D * self.x).cpu().numpy()
-        yl = (self.E * self.y * self.cinv)
-        if self.world > 1:
-            per = max(r1 - r0 for r0, r1 in self.rows)
-            pad = t.zeros(per, dtype=t.float64, device=yl.device); pad[:yl.numel()] = yl
-            if pad.is_cuda and self.dist.get_backend(self.group) != "nccl":
-                pad = pad.cpu()
-            out = t.empty(self.world * per, dtype=t.float64, device=pad.device)
-            self.dist.all_gather_into_tensor(out, pad, group=self.group)
-            out = out.cpu().numpy()
-            y = np.concatenate([out[g * per:g * per + (r1 - r0)] for g, (r0, r1) in enumerate(self.rows)])
+            if cert:             # the approximate branch: 10 x every tolerance on the same scalars
+                v = self._verdict(approximate=True)
+                status = v + " inaccurate" if v else "maximum iterations reached"
+            else:
+                status = "solved inaccurate" if self._terminated(approximate=True) else "maximum iterations reached"
+        self.status = status
+        obj, rho_estimate = self.sc["obj"], self._rho_estimate()
+        nan_x, nan_m = np.full(self.n, np.nan), np.full(self.m, np.nan)
+        prim_inf_cert, dual_inf_cert = nan_m, nan_x
+        if status in INFEASIBLE:
+            # store_solution (src/auxil.c:536-560): no solution, the certificate normalised, the iterates back to zero (rho stays)
+            un = self.scaled_data and not st["scaled_termination"]
+            x, y = nan_x, nan_m
+            if status.startswith("primal"):
+                obj = OSQP_INFTY
+                prim_inf_cert = self._gather_rows(((self.E * self.dy) if un else self.dy) * (1.0 / self.cs["ndy"]))
+            else:
+                obj = -OSQP_INFTY
+                dual_inf_cert = (((self.D * self.dx) if un else self.dx) * (1.0 / self.cs["ndx"])).cpu().numpy()
+            self.x, self.xt = t.zeros_like(self.x), t.zeros_like(self.x)
+            self.z, self.y = t.zeros_like(self.z), t.zeros_like(self.z)
         else:
-            y = yl.cpu().numpy()
-        info = SimpleNamespace(status=status, iter=it, obj_val=self.sc["obj"], pri_res=self.pri_res, dua_res=self.dua_res,
-                               rho_updates=self.rho_updates, rho_estimate=self._rho_estimate(), pcg_iters=self.pcg_iters,
+            # unscale; y is gathered from the row shards
+            x = (self.D * self.x).cpu().numpy()
+            y = self._gather_rows(self.E * self.y * self.cinv)
+        info = SimpleNamespace(status=status, iter=it, obj_val=obj, pri_res=self.pri_res, dua_res=self.dua_res,
+                               rho_updates=self.rho_updates, rho_estimate=rho_estimate, pcg_iters=self.pcg_iters,
                                collectives=self.collectives)
-        return SimpleNamespace(x=x, y=y, info=info)
+        return SimpleNamespace(x=x, y=y, info=info, prim_inf_cert=prim_inf_cert, dual_inf_cert=dual_inf_cert)
+
+    def _gather_rows(self, yl):
+        t = self.torch
+        if self.world == 1:
+            return yl.cpu().numpy()
+        per = max(r1 - r0 for r0, r1 in self.rows)
+        pad = t.zeros(per, dtype=t.float64, device=yl.device); pad[:yl.numel()] = yl
+        if pad.is_cuda and self.dist.get_backend(self.group) != "nccl":
+            pad = pad.cpu()
+        out = t.empty(self.world * per, dtype=t.float64, device=pad.device)
+        self.dist.all_gather_into_tensor(out, pad, group=self.group)
+        out = out.cpu().numpy()
+        return np.concatenate([out[g * per:g * per + (r1 - r0)] for g, (r0, r1) in enumerate(self.rows)])
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -401,12 +558,24 @@ class _RpInfo(C.Structure):
 
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p)
-_STATUS = {1: "solved", 2: "solved inaccurate", -2: "maximum iterations reached"}
+_STATUS = {1: "solved", 2: "solved inaccurate", -2: "maximum iterations reached", -3: "primal infeasible", 3: "primal infeasible inaccurate",
+           -4: "dual infeasible", 4: "dual infeasible inaccurate"}
 
 
 class _DevView:
     def __init__(self, ptr, count):
         self.__cuda_array_interface__ = dict(shape=(int(count),), typestr="<f8", data=(int(ptr), False), version=2, strides=None)
+
+
+def bind_live(L):
+    """Signatures of the infeasibility and live-handle entry points (include/osqp_amd_rowpart.h)."""
+    H, P, d = C.c_void_p, C.c_void_p, C.c_double
+    for name, args in (("osqp_amd_rp_set_infeasibility", [H, d, d]), ("osqp_amd_rp_get_certificates", [H, P, P]),
+                       ("osqp_amd_rp_update_lin_cost", [H, P]), ("osqp_amd_rp_update_bounds", [H, P, P]),
+                       ("osqp_amd_rp_warm_start", [H, P, P]), ("osqp_amd_rp_update_rho", [H, d])):
+        f = getattr(L, name)
+        f.restype, f.argtypes = C.c_int, args
+    return L
 
 
 class NativeRowPartitionedOSQP:
@@ -439,6 +608,7 @@ class NativeRowPartitionedOSQP:
         L.osqp_amd_rp_rccl_unique_id.restype = C.c_int; L.osqp_amd_rp_rccl_unique_id.argtypes = [C.c_void_p, C.c_int]
         L.osqp_amd_rp_use_rccl.restype = C.c_int; L.osqp_amd_rp_use_rccl.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.osqp_amd_rp_peek.restype = C.c_int; L.osqp_amd_rp_peek.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
+        bind_live(L)
         L.hipeng_sync.restype = C.c_int; L.hipeng_sync.argtypes = [C.c_void_p]
 
     def _group_allreduce(self, user, buf, count, op, stream):
@@ -463,13 +633,8 @@ class NativeRowPartitionedOSQP:
 
     def setup(self, scaled, device=0, **settings):
         t, d = self.torch, self.dist
-        st = dict(rho=0.1, sigma=1e-6, alpha=1.6, eps_abs=1e-3, eps_rel=1e-3, max_iter=4000, check_termination=25,
-                  adaptive_rho=1, adaptive_rho_interval=0, adaptive_rho_tolerance=5.0, scaled_termination=0,
-                  pcg_eps_rel=1e-9, pcg_max_iter=0)
-        for k, v in settings.items():
-            if k not in st:
-                raise ValueError("unsupported setting %r in the row-partitioned variant" % k)
-            st[k] = v
+        st = _settings(settings)
+        eps_inf = (float(st.pop("eps_prim_inf")), float(st.pop("eps_dual_inf")))
         n, m = scaled["P"].shape[0], scaled["A"].shape[0]
         self.n, self.m = n, m
         self.rows = shard_rows(scaled["A"], self.world)
@@ -504,6 +669,8 @@ class NativeRowPartitionedOSQP:
                                         C.byref(s), self.world, self.rank, self._cb, None)
         if not self._rp:
             raise RuntimeError("osqp_amd_rp_create failed")
+        if eps_inf[0] > 0 or eps_inf[1] > 0:              # (a handle that never makes the call solves as before the tests existed)
+            self.set_infeasibility(*eps_inf)
         if self.collective == "rccl" and self.world > 1:
             idb = t.zeros(128, dtype=t.uint8)
             if self.rank == 0:
@@ -531,9 +698,64 @@ class NativeRowPartitionedOSQP:
             raise RuntimeError("osqp_amd_rp_rccl_unique_id failed")
         return self._L.osqp_amd_rp_use_rccl(self._rp, raw.raw, 128)
 
+    def set_infeasibility(self, eps_prim_inf, eps_dual_inf):
+        """Switch the infeasibility tests on (0: that test off); every rank with the same values."""
+        if self._L.osqp_amd_rp_set_infeasibility(self._rp, float(eps_prim_inf), float(eps_dual_inf)):
+            raise ValueError("eps_prim_inf and eps_dual_inf must not be negative")
+
+    # ---- a live handle: unscaled arrays of full length in, the rank's rows taken here (every rank calls each of these) ----
+    def _checked(self, rc, what):
+        if rc not in (0, 1):
+            raise RuntimeError("%s failed (%d)" % (what, rc))
+        return int(rc)
+
+    def update(self, q=None, l=None, u=None):
+        """New q and / or new bounds (l and u together).  Returns 1 on every rank, with the bounds unchanged on all of them, when l > u
+        on some row."""
+        if (l is None) != (u is None):
+            raise ValueError("l and u are updated together in the row-partitioned variant")
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        if q is not None:
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            if q.shape != (self.n,):
+                raise ValueError("q must have %d entries" % self.n)
+        if l is not None:                                # the bounds first: refused bounds leave q as it was, too
+            lo, hi = _rows_of(l, self.m, self.r0, self.r1, "l"), _rows_of(u, self.m, self.r0, self.r1, "u")
+            if self._checked(self._L.osqp_amd_rp_update_bounds(self._rp, ptr(lo), ptr(hi)), "osqp_amd_rp_update_bounds"):
+                return 1
+        if q is not None:
+            self._checked(self._L.osqp_amd_rp_update_lin_cost(self._rp, ptr(q)), "osqp_amd_rp_update_lin_cost")
+        return 0
+
+    def warm_start(self, x=None, y=None):
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=np.float64)
+            if x.shape != (self.n,):
+                raise ValueError("x must have %d entries" % self.n)
+        yl = _rows_of(y, self.m, self.r0, self.r1, "y") if y is not None else None
+        return self._checked(self._L.osqp_amd_rp_warm_start(self._rp, ptr(x) if x is not None else None, ptr(yl) if yl is not None else None),
+                             "osqp_amd_rp_warm_start")
+
+    def update_rho(self, rho):
+        return self._checked(self._L.osqp_amd_rp_update_rho(self._rp, float(rho)), "osqp_amd_rp_update_rho")
+
+    def _gather_rows(self, yl):
+        """An m-vector from the row shards (once per solve, off the data path)."""
+        t, d = self.torch, self.dist
+        if self.world == 1:
+            return yl
+        per = max(b - a for a, b in self.rows)
+        pad = t.zeros(per, dtype=t.float64); pad[:yl.size] = t.from_numpy(yl)
+        if d.get_backend(self.group) == "nccl":
+            pad = pad.to(self.dev)
+        out = t.empty(self.world * per, dtype=t.float64, device=pad.device)
+        d.all_gather_into_tensor(out, pad, group=self.group)
+        out = out.cpu().numpy()
+        return np.concatenate([out[g * per:g * per + (b - a)] for g, (a, b) in enumerate(self.rows)])
+
     def solve(self):
         from types import SimpleNamespace
-        t, d = self.torch, self.dist
         info = _RpInfo()
         rc = self._L.osqp_amd_rp_solve(self._rp, C.byref(info))
         if rc:
@@ -541,30 +763,26 @@ class NativeRowPartitionedOSQP:
         x = np.zeros(self.n); yl = np.zeros(max(self.r1 - self.r0, 1))
         if self._L.osqp_amd_rp_get_solution(self._rp, x.ctypes.data_as(C.c_void_p), yl.ctypes.data_as(C.c_void_p)):
             raise RuntimeError("osqp_amd_rp_get_solution failed")
-        yl = yl[:self.r1 - self.r0]
-        if self.world > 1:                                  # the duals are gathered from the row shards (once per solve, off the data path)
-            per = max(b - a for a, b in self.rows)
-            pad = t.zeros(per, dtype=t.float64); pad[:yl.size] = t.from_numpy(yl)
-            if d.get_backend(self.group) == "nccl":
-                pad = pad.to(self.dev)
-            out = t.empty(self.world * per, dtype=t.float64, device=pad.device)
-            d.all_gather_into_tensor(out, pad, group=self.group)
-            out = out.cpu().numpy()
-            y = np.concatenate([out[g * per:g * per + (b - a)] for g, (a, b) in enumerate(self.rows)])
-        else:
-            y = yl
+        y = self._gather_rows(yl[:self.r1 - self.r0])
+        dual_inf_cert, prim_inf_cert = np.full(self.n, np.nan), np.full(self.m, np.nan)
+        if info.status in (3, -3, 4, -4):
+            pl = np.full(max(self.r1 - self.r0, 1), np.nan)
+            if self._L.osqp_amd_rp_get_certificates(self._rp, dual_inf_cert.ctypes.data_as(C.c_void_p), pl.ctypes.data_as(C.c_void_p)):
+                raise RuntimeError("osqp_amd_rp_get_certificates failed")
+            if info.status in (3, -3):                   # (the status is the same on every rank: all of them gather, or none)
+                prim_inf_cert = self._gather_rows(pl[:self.r1 - self.r0])
         ns = SimpleNamespace(status=_STATUS.get(info.status, "unsolved"), iter=info.iter, obj_val=info.obj_val, pri_res=info.pri_res, dua_res=info.dua_res,
                              rho_updates=info.rho_updates, rho_estimate=info.rho_estimate, pcg_iters=info.pcg_iters, collectives=info.collectives)
-        return SimpleNamespace(x=x, y=y, info=ns)
+        return SimpleNamespace(x=x, y=y, info=ns, prim_inf_cert=prim_inf_cert, dual_inf_cert=dual_inf_cert)
 
-    _PEEK = ("x", "xt", "z", "y", "rv", "minv", "b", "r", "sc15", "S")
+    _PEEK = ("x", "xt", "z", "y", "rv", "minv", "b", "r", "sc15", "S", "dx", "dy", "sc7", "q", "l", "u")
     _S_FIELDS = ("rz0", "rz1", "rr", "tol2", "bb", "done", "iters", "cap", "bad")
 
     def peek(self, name):
         """For the tests (osqp_amd_rp_peek): one array of the handle's state in the scaled space, copied to the host; nothing
         is written on the device.  "S": the PCG's device-side record as a dict."""
         which = self._PEEK.index(name)
-        cap = {"sc15": 15, "S": 9}.get(name, max(self.n, self.r1 - self.r0, 1))
+        cap = {"sc15": 15, "S": 9, "sc7": 7}.get(name, max(self.n, self.r1 - self.r0, 1))
         out = np.zeros(cap)
         k = self._L.osqp_amd_rp_peek(self._rp, which, out.ctypes.data_as(C.c_void_p), cap)
         if k < 0:
