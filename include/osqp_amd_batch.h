@@ -123,6 +123,41 @@ c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, const c_float
                              c_float *dQ, c_float *dL, c_float *dU,
                              c_float *dPx /*[batch][nnzP], NULL = skip*/, c_float *dAx /*[batch][nnzA], NULL = skip*/,
                              c_int *active /*[batch][m], NULL = skip*/, c_int *status_adjoint /*[batch]*/);
+/* Forward sensitivities of the solution, for every member whose last solve ended OSQP_SOLVED: from ndir tangents per
+ * member of the data -- dQ [batch][ndir][n], dL and dU [batch][ndir][m], dPx [batch][ndir][nnzP] and dAx
+ * [batch][ndir][nnzA] on the pattern of setup (CSC order of triu(P) / A; an off-diagonal slot of triu(P) stands for
+ * both halves of P); any of them NULL = 0 -- the tangents dX [batch][ndir][n] and dY [batch][ndir][m] (NULL = skip)
+ * of the solution: one column of the Jacobian per direction, where osqp_amd_batch_adjoint gives one row per call.
+ * The point differentiated is the one the handle holds: the polished one where osqp_amd_batch_polish was accepted,
+ * the ADMM iterate otherwise.  Per member, in its scaled space: the active rows as polish guesses them (lows first,
+ * then upps), the same regularised KKT matrix inverted on the device once for all ndir directions, and per direction
+ * one solve M [dx; dnu] = [-(dQ + dP x + dA' y_act); db_act - (dA x)_act] with exactly polish_refine_iter refinement
+ * steps against the unregularised M = [P, Ar'; Ar, 0]; dY = dnu on the active rows and 0 elsewhere.  y_act is y on
+ * the active rows and 0 elsewhere; db is dL_i on a row active at its lower bound and dU_i on one active at its upper
+ * bound.  The tangent of the other bound of a row, of an inactive row and of an infinite bound has no effect.  An
+ * equality row (l = u) follows the one bound it is classified active at, by the sign of its multiplier: give dL = dU
+ * there.  Where active rows are linearly dependent the multipliers are not unique and neither is dY (and a tangent
+ * that moves dependent rows apart has no solution: the values are those of the regularised solve); where strict
+ * complementarity fails the solution is not differentiable and the values are those of the guessed active set.
+ * For a loss with gradients gx, gy and the adjoint's outputs for them, gx.dX + gy.dY = dQ_adj.dQ + dL_adj.dL +
+ * dU_adj.dU + dPx_adj.dPx + dAx_adj.dAx.  The results carry no atomics and are reproducible to the bit; a
+ * direction's bits do not depend on the other directions of the call.
+ * active [batch][m] (NULL = skip): as osqp_amd_batch_adjoint reports it.  status_tangent [batch] (NULL = skip): 1
+ * computed; -1 a KKT pivot of the wrong sign (that member's outputs are 0); 0 not tried, the member's last solve did
+ * not end OSQP_SOLVED (outputs 0).  Nothing of the handle changes: X, Y, info8, the stored iterates, rho, K^-1, the
+ * status_polish a later osqp_amd_batch_polish reports and what a later osqp_amd_batch_adjoint returns stay bit-equal.
+ * Memory: polish's KKT buffer with its cap and chunks, plus staging of the vector tangents and the outputs,
+ * allocated at the first call, and of the matrix tangents, allocated at the first call that passes one; the staging
+ * grows when a later call brings a larger ndir and is freed by cleanup.
+ * Returns 0; OSQP_WORKSPACE_NOT_INIT_ERROR for a NULL handle or when no solve has run on the current problem;
+ * OSQP_DATA_VALIDATION_ERROR when ndir < 1, ndir > 65535 or dX is NULL; OSQP_MEM_ALLOC_ERROR (the handle stays
+ * usable); OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line when n + active rows exceeds 2176 or the kernel would
+ * need more than 160 KiB of LDS. */
+c_int osqp_amd_batch_tangent(osqp_amd_batch *b, c_int ndir,
+                             const c_float *dQ /*[batch][ndir][n]*/, const c_float *dL, const c_float *dU /*[batch][ndir][m]*/,
+                             const c_float *dPx /*[batch][ndir][nnzP]*/, const c_float *dAx /*[batch][ndir][nnzA]*/,
+                             c_float *dX /*[batch][ndir][n]*/, c_float *dY /*[batch][ndir][m], NULL = skip*/,
+                             c_int *active /*[batch][m], NULL = skip*/, c_int *status_tangent /*[batch], NULL = skip*/);
 /* Results: X [batch][n], Y [batch][m] (unscaled; OSQP_NAN when infeasible),
  * info8 [batch][8] = {iter, status_val, obj_val, pri_res, dua_res, rho_updates,
  * rho_estimate, rho}; DX / DY infeasibility certificates.  NULL = skip. */
@@ -164,6 +199,13 @@ c_int osqp_amd_batch_adjoint_dev(osqp_amd_batch *b, const c_float *dX, const c_f
                                  c_float *dQ, c_float *dL, c_float *dU,
                                  c_float *dPx /*NULL = skip*/, c_float *dAx /*NULL = skip*/,
                                  int *active /*NULL = skip*/, int *status_adjoint /*NULL = skip*/);
+/* osqp_amd_batch_tangent with every array on the device: the tangents are read in place, the outputs arrive by
+ * device-to-device copies.  active [batch][m] and status_tangent [batch] are 32-bit ints there, as the kernel writes
+ * them. */
+c_int osqp_amd_batch_tangent_dev(osqp_amd_batch *b, c_int ndir,
+                                 const c_float *dQ, const c_float *dL, const c_float *dU,
+                                 const c_float *dPx, const c_float *dAx, c_float *dX, c_float *dY /*NULL = skip*/,
+                                 int *active /*NULL = skip*/, int *status_tangent /*NULL = skip*/);
 /* osqp_amd_batch_get into caller-owned device arrays (NULL = skip): copies, which a later solve does not touch
  * (the arrays of osqp_amd_batch_device_ptrs are the handle's own and change with the next solve). */
 c_int osqp_amd_batch_get_dev(osqp_amd_batch *b, c_float *X, c_float *Y, c_float *info8, c_float *DX, c_float *DY);

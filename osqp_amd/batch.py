@@ -37,6 +37,8 @@ def _bind(L):
     L.osqp_amd_batch_polish.argtypes = [H, abi.c_int_p]
     L.osqp_amd_batch_adjoint.restype = abi.c_int
     L.osqp_amd_batch_adjoint.argtypes = [H] + [abi.c_float_p] * 7 + [abi.c_int_p] * 2
+    L.osqp_amd_batch_tangent.restype = abi.c_int
+    L.osqp_amd_batch_tangent.argtypes = [H, abi.c_int] + [abi.c_float_p] * 7 + [abi.c_int_p] * 2
     L.osqp_amd_batch_get.restype = abi.c_int
     L.osqp_amd_batch_get.argtypes = [H, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p]
     L.osqp_amd_batch_cleanup.restype = None
@@ -54,6 +56,7 @@ def _bind(L):
     # device arrays in and out: device addresses travel as integers (c_void_p), host index lists as before
     V = C.c_void_p
     for name, args in (("update_dev", [V] * 3), ("warm_start_dev", [V] * 2), ("adjoint_dev", [V] * 9),
+                       ("tangent_dev", [abi.c_int] + [V] * 9),
                        ("update_matrices_dev", [V, abi.c_int_p, abi.c_int, abi.c_int] * 2),
                        ("get_dev", [V] * 5), ("polish_status_dev", [V]), ("check_dev_ptr", [V])):
         f = getattr(L, "osqp_amd_batch_" + name)
@@ -152,6 +155,39 @@ def check_adjoint(B, n, m, dX, dY=None):
     if dX.shape != (B, n) or (dY is not None and dY.shape != (B, m)):
         raise ValueError("adjoint arrays must be dX [B, n], dY [B, m]")
     return dX, dY
+
+
+def check_tangent(B, n, m, nnzP, nnzA, dQ=None, dL=None, dU=None, dPx=None, dAx=None, **outputs):
+    """Shape checks of BatchOSQP.tangent / tangent_into, as check_adjoint: every given array is [B, k] (one direction
+    per member) or [B, D, k] (D directions), k = n for dQ, m for dL and dU, nnzP for dPx, nnzA for dAx; all given
+    arrays agree on the form and on D.  outputs: dx / dy of tangent_into, checked the same way with k = n / m.  Host
+    arrays come back as contiguous float64, device arrays as they are (device_view checks type and strides).  Returns
+    (dQ, dL, dU, dPx, dAx, D, flat): flat is True for the [B, k] form (D = 1), and when nothing is given."""
+    cols = dict(dQ=n, dL=m, dU=m, dPx=nnzP, dAx=nnzA, dx=n, dy=m)
+    given = dict(dQ=dQ, dL=dL, dU=dU, dPx=dPx, dAx=dAx, **outputs)
+    out, forms = {}, {}
+    for name, a in given.items():
+        if name not in cols:
+            raise ValueError("unknown tangent array %r" % name)
+        if a is None:
+            out[name] = None
+            continue
+        if is_device(a):
+            shape = tuple(a.__cuda_array_interface__["shape"])
+        else:
+            a = abi.as_f64(a)
+            shape = a.shape
+        if len(shape) not in (2, 3) or shape[0] != B or shape[-1] != cols[name] or (len(shape) == 3 and shape[1] < 1):
+            raise ValueError("%s must be [B, %d] or [B, D, %d] with B = %d, not %s" % (name, cols[name], cols[name], B, shape))
+        forms[name] = None if len(shape) == 2 else shape[1]
+        out[name] = a
+    if len(set(forms.values())) > 1:
+        raise ValueError("tangent arrays must all be [B, k] or all [B, D, k] with one D: %s"
+                         % ", ".join("%s %s" % (k, "[B, k]" if d is None else "D = %d" % d) for k, d in forms.items()))
+    D = next(iter(forms.values()), None)
+    if D is not None and D > 65535:
+        raise ValueError("at most 65535 directions per call, not %d" % D)
+    return tuple(out[k] for k in ("dQ", "dL", "dU", "dPx", "dAx")) + (1 if D is None else int(D), D is None)
 
 
 _BAD_POINTER = (": a pointer is not device memory of the handle's device as the library's HIP runtime knows it (a host "
@@ -445,6 +481,31 @@ class BatchOSQP:
         return SimpleNamespace(dq=dq, dl=dl[:, :m], du=du[:, :m], dPx=None if dPx is None else dPx[:, :self.Pu.nnz],
                                dAx=None if dAx is None else dAx[:, :self.Ah.nnz], active=act[:, :m], status_adjoint=sa)
 
+    def tangent(self, dQ=None, dL=None, dU=None, dPx=None, dAx=None):
+        """Forward sensitivities of the solution on the device, for every member whose last solve ended `solved`: from
+        tangents of the data -- dQ [B, n], dL, dU [B, m], dPx [B, nnzP], dAx [B, nnzA] (CSC order of triu(P) / A; an
+        off-diagonal dPx slot stands for both halves of P), or each of them [B, D, k] for D directions per member
+        that share one KKT inversion; None = 0 -- a namespace with dx [B, n] and dy [B, m] (or [B, D, .]), active
+        [B, m] and status_tangent [B]: 1 computed, -1 a KKT pivot of the wrong sign, 0 not tried; the tangents of
+        members that are not 1 are 0.  Only the tangent of the bound a row is active at counts (dL = dU on an
+        equality row).  The point differentiated is the one the handle holds, as for adjoint().  To first order the
+        solution of the moved problem is r.x + t.dx, r.y + t.dy.  Changes nothing in the handle.  Needs a solve since
+        setup or the last update."""
+        if self._many is not None:
+            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): tangent is a call of the batch "
+                               "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
+        B, n, m = self.B, self.n, self.m
+        dQ, dL, dU, dPx, dAx, D, flat = check_tangent(B, n, m, self.Pu.nnz, self.Ah.nnz, dQ, dL, dU, dPx, dAx)
+        dx = np.zeros((B, D, n)); dy = np.zeros((B, D, max(m, 1)))
+        act = np.zeros((B, max(m, 1)), np.int64); st = np.zeros(B, np.int64)
+        rc = self._lib.osqp_amd_batch_tangent(self._h, D, _p(dQ), _p(dL if m else None), _p(dU if m else None), _p(dPx),
+                                              _p(dAx), abi.fptr(dx), _p(dy if m else None), abi.iptr(act), abi.iptr(st))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_tangent failed (%d)%s" % (rc, ": no solve has run on the current problem"
+                                                                         if rc == 7 else ""))
+        dy = dy[:, :, :m]
+        return SimpleNamespace(dx=dx[:, 0] if flat else dx, dy=dy[:, 0] if flat else dy, active=act[:, :m], status_tangent=st)
+
     def results(self):
         if self._many is not None:
             return self._many_results()
@@ -505,6 +566,32 @@ class BatchOSQP:
             None if status_adjoint is None else device_view(status_adjoint, (self.B,), "<i4", True, "status_adjoint"))
         if rc:
             raise RuntimeError("osqp_amd_batch_adjoint_dev failed (%d)%s"
+                               % (rc, ": no solve has run on the current problem" if rc == 7 else
+                                  _BAD_POINTER if rc == 1 else ""))
+
+    def tangent_into(self, dx, dy, dQ=None, dL=None, dU=None, dPx=None, dAx=None, active=None, status_tangent=None):
+        """tangent() between device arrays of the caller's: from dQ, dL, dU, dPx, dAx (None = 0; [B, k], or [B, D, k] for
+        D directions) into dx [B, n] and dy [B, m] (or [B, D, .], as the tangents; float64) and, where given, active
+        [B, m], status_tangent [B] (int32).  For m = 0 dy may be None.  Ready on return."""
+        if self._route(dx=dx, dy=dy, dQ=dQ, dL=dL, dU=dU, dPx=dPx, dAx=dAx, active=active,
+                       status_tangent=status_tangent) != "device":
+            raise ValueError("tangent_into reads and writes device arrays (objects with __cuda_array_interface__); tangent() "
+                             "takes and returns host arrays")
+        if dx is None or (self.m and dy is None):
+            raise ValueError("tangent_into needs dx and, for m > 0, dy")
+        B, n, m = self.B, self.n, self.m
+        dQ, dL, dU, dPx, dAx, D, flat = check_tangent(B, n, m, self.Pu.nnz, self.Ah.nnz, dQ, dL, dU, dPx, dAx, dx=dx, dy=dy)
+
+        def d(a, cols, name, writable=False):
+            if a is None:
+                return None
+            return device_view(a, (B, cols) if flat else (B, D, cols), "<f8", writable, name) or None
+        rc = self._lib.osqp_amd_batch_tangent_dev(
+            self._h, D, d(dQ, n, "dQ"), d(dL, m, "dL"), d(dU, m, "dU"), d(dPx, self.Pu.nnz, "dPx"), d(dAx, self.Ah.nnz, "dAx"),
+            d(dx, n, "dx", True), d(dy, m, "dy", True), self._dev(active, m, "active", "<i4", True),
+            None if status_tangent is None else device_view(status_tangent, (B,), "<i4", True, "status_tangent"))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_tangent_dev failed (%d)%s"
                                % (rc, ": no solve has run on the current problem" if rc == 7 else
                                   _BAD_POINTER if rc == 1 else ""))
 

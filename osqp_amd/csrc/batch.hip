@@ -681,6 +681,7 @@ __global__ void __launch_bounds__(1024) k_batch_order(long long B, const double 
 #include "batch_streamed.h"
 #include "batch_polish.h"
 #include "batch_adjoint.h"
+#include "batch_tangent.h"
 
 struct osqp_amd_batch {
   int engine = OSQP_AMD_BATCH_TILED;
@@ -721,6 +722,12 @@ struct osqp_amd_batch {
   double *adj_out = nullptr;  // [B][n + 2 m] dQ, dL, dU
   double *adj_dP = nullptr, *adj_dA = nullptr;   // [B][nnzP], [B][nnzA]
   int *adj_act = nullptr, *adj_stat = nullptr;   // [B][m], [B]
+  // tangent (batch_tangent.h): staging that grows with ndir (freed by cleanup), the rest allocated at the first call
+  double *tan_in = nullptr;   // [B][ndir][n], [B][ndir][m], [B][ndir][m] the vector tangents (host route)
+  double *tan_mat = nullptr;  // [B][ndir][nnzP], [B][ndir][nnzA] the matrix tangents (host route)
+  double *tan_out = nullptr;  // [B][ndir][n] dX, then [B][ndir][m] dY
+  size_t tan_in_cap = 0, tan_mat_cap = 0, tan_out_cap = 0;   // in doubles
+  int *tan_act = nullptr, *tan_stat = nullptr, *tan_piv = nullptr;   // [B][m], [B], [B] (the inversion's verdict)
   int *d_bad = nullptr;     // device-array updates (batch_devio.h): count of l > u pairs of k_batch_check_bounds
 };
 
@@ -1126,6 +1133,7 @@ extern "C" void osqp_amd_batch_cleanup(osqp_amd_batch *b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   for (void *p : b->allocs) (void)hipFree(p);
   if (b->pol.K) (void)hipFree(b->pol.K);
+  for (double *p : {b->tan_in, b->tan_mat, b->tan_out}) if (p) (void)hipFree(p);
   if (b->stream) (void)hipStreamDestroy(b->stream);
   delete b;
 }
@@ -1333,6 +1341,7 @@ static c_int bp_plan(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds
 }
 static size_t bp_lds_of(int n, int m, int NPOL) { return bp_lds_bytes(n, m, NPOL); }
 static size_t ba_lds_of(int n, int m, int NPOL) { return ba_lds_bytes(n, m, NPOL); }
+static size_t bt_lds_of(int n, int m, int NPOL) { return bt_lds_bytes(n, m, NPOL); }
 
 // The planned chunks of solved members: the KKT matrix of each member of a chunk (k_bp_form), its inverse
 // (k_bp_invert), then the caller's kernel fn, launched by third(members of the chunk, their list) with pn.lds
@@ -1444,6 +1453,92 @@ extern "C" c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, co
   BCHK(hipStreamSynchronize(b->stream));
   for (size_t k = 0; k < ha.size(); k++) active[k] = ha[k];
   if (status_adjoint) for (size_t q = 0; q < B; q++) status_adjoint[q] = hs[q];
+  return 0;
+}
+
+// a staging buffer of the tangent call of at least cnt doubles (it only grows; nothing is queued on it between calls)
+static int tan_reserve(double **p, size_t *cap, size_t cnt) {
+  if (cnt <= *cap) return 0;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr; *cap = 0;
+  void *q = nullptr;
+  if (hipMalloc(&q, cnt * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return -102; }
+  *p = static_cast<double *>(q); *cap = cnt;
+  return 0;
+}
+
+// What osqp_amd_batch_tangent and osqp_amd_batch_tangent_dev share: the staging, the plan and the launches.  dev: the
+// tangents are device arrays, which k_bt_tangent reads in place.  *out: where the outputs sit; nothing is waited for.
+static c_int tangent_launch(osqp_amd_batch *b, int ndir, const c_float *dQ, const c_float *dL, const c_float *dU,
+                            const c_float *dPx, const c_float *dAx, bool dev, BTan *out) {
+  const size_t B = (size_t)b->B, D = (size_t)ndir;
+  const size_t n = (size_t)b->n, m = (size_t)b->m, nnzP = (size_t)b->nnzP, nnzA = (size_t)b->nnzA;
+  if (!m) dL = dU = nullptr;
+  if (!nnzP) dPx = nullptr;
+  if (!nnzA) dAx = nullptr;
+  if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
+  if (balloc_once(b, &b->tan_act, B * m) || balloc_once(b, &b->tan_stat, B) || balloc_once(b, &b->tan_piv, B)) {
+    (void)hipGetLastError();
+    return OSQP_MEM_ALLOC_ERROR;
+  }
+  const size_t nout = std::max((size_t)1, B * D * (n + m));
+  if (tan_reserve(&b->tan_out, &b->tan_out_cap, nout) ||
+      (!dev && tan_reserve(&b->tan_in, &b->tan_in_cap, std::max((size_t)1, B * D * (n + 2 * m)))) ||
+      (!dev && (dPx || dAx) && tan_reserve(&b->tan_mat, &b->tan_mat_cap, B * D * (nnzP + nnzA))))
+    return OSQP_MEM_ALLOC_ERROR;
+  BPol pl = b->pol;          // polish's buffers; its status array stays polish's
+  pl.stat = b->tan_piv;
+  BTan tg{};
+  tg.ndir = ndir;
+  tg.dQ = dQ; tg.dL = dL; tg.dU = dU; tg.dPx = dPx; tg.dAx = dAx;
+  if (!dev) {                // (the input staging is the host route's alone)
+    double *vq = b->tan_in, *vl = vq + B * D * n, *vu = vl + B * D * m, *vp = b->tan_mat, *va = vp ? vp + B * D * nnzP : nullptr;
+    const struct { const c_float *src; double *dst; size_t cnt; const double **slot; } in[] = {
+        {dQ, vq, B * D * n, &tg.dQ}, {dL, vl, B * D * m, &tg.dL}, {dU, vu, B * D * m, &tg.dU},
+        {dPx, vp, B * D * nnzP, &tg.dPx}, {dAx, va, B * D * nnzA, &tg.dAx}};
+    for (const auto &t : in) {
+      if (!t.src) continue;
+      BCHK(hipMemcpyAsync(t.dst, t.src, t.cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
+      *t.slot = t.dst;
+    }
+  }
+  tg.dX = b->tan_out; tg.dY = tg.dX + B * D * n;
+  tg.active = b->tan_act; tg.stat = b->tan_stat;
+  // members that are skipped or rejected report zeros
+  BCHK(hipMemsetAsync(b->tan_out, 0, nout * sizeof(double), b->stream));
+  BCHK(hipMemsetAsync(b->tan_act, 0, std::max((size_t)1, B * m) * sizeof(int), b->stream));
+  BCHK(hipMemsetAsync(b->tan_stat, 0, B * sizeof(int), b->stream));
+  BPlan pn;
+  const c_int rc = bp_plan(b, pl, "tangent", bt_lds_of, &pn);
+  if (rc) return rc;
+  if (bp_run_chunks(b, pl, pn, KFN(k_bt_tangent), [&](unsigned cnt, const int *lp) {
+        hipLaunchKernelGGL(k_bt_tangent, dim3(cnt, (unsigned)ndir), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, tg, pn.NPOL, b->pol_refine, lp);
+      })) return -102;
+  *out = tg;
+  return 0;
+}
+
+// forward sensitivities for the solved members (batch_tangent.h): polish's active rows, KKT matrix and inversion on
+// polish's buffers, in the same chunks, one inversion for the ndir directions of a member; nothing of the solve state
+// is written
+extern "C" c_int osqp_amd_batch_tangent(osqp_amd_batch *b, c_int ndir, const c_float *dQ, const c_float *dL, const c_float *dU,
+                                        const c_float *dPx, const c_float *dAx, c_float *dX, c_float *dY,
+                                        c_int *active, c_int *status_tangent) {
+  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (ndir < 1 || ndir > 65535 || !dX) return OSQP_DATA_VALIDATION_ERROR;
+  BCHK(hipSetDevice(b->device));
+  const size_t B = (size_t)b->B, D = (size_t)ndir;
+  const int n = b->n, m = b->m;
+  BTan tg{};
+  if (const c_int rc = tangent_launch(b, (int)ndir, dQ, dL, dU, dPx, dAx, false, &tg)) return rc;
+  BCHK(hipMemcpyAsync(dX, tg.dX, B * D * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  if (dY && m) BCHK(hipMemcpyAsync(dY, tg.dY, B * D * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  std::vector<int> ha(active ? B * m : 0), hs(B);
+  if (active && m) BCHK(hipMemcpyAsync(ha.data(), tg.active, B * m * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  if (status_tangent) BCHK(hipMemcpyAsync(hs.data(), tg.stat, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  BCHK(hipStreamSynchronize(b->stream));
+  for (size_t k = 0; k < ha.size(); k++) active[k] = ha[k];
+  if (status_tangent) for (size_t q = 0; q < B; q++) status_tangent[q] = hs[q];
   return 0;
 }
 

@@ -171,6 +171,24 @@ extern "C" c_int osqp_amd_batch_adjoint_dev(osqp_amd_batch *b, const c_float *dX
   return 0;
 }
 
+extern "C" c_int osqp_amd_batch_tangent_dev(osqp_amd_batch *b, c_int ndir, const c_float *dQ, const c_float *dL,
+                                            const c_float *dU, const c_float *dPx, const c_float *dAx, c_float *dX,
+                                            c_float *dY, int *active, int *status_tangent) {
+  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (ndir < 1 || ndir > 65535 || !dX) return OSQP_DATA_VALIDATION_ERROR;
+  BCHK(hipSetDevice(b->device));
+  if (dev_ptrs_check(b, {dQ, dL, dU, dPx, dAx, dX, dY, active, status_tangent})) return OSQP_DATA_VALIDATION_ERROR;
+  const size_t B = (size_t)b->B, D = (size_t)ndir, n = (size_t)b->n, m = (size_t)b->m;
+  BTan tg{};
+  if (const c_int rc = tangent_launch(b, (int)ndir, dQ, dL, dU, dPx, dAx, true, &tg)) return rc;
+  BCHK(give(b, dX, (const double *)tg.dX, B * D * n));
+  BCHK(give(b, dY, (const double *)tg.dY, B * D * m));
+  BCHK(give(b, active, (const int *)tg.active, B * m));
+  BCHK(give(b, status_tangent, (const int *)tg.stat, B));
+  BCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
 extern "C" c_int osqp_amd_batch_get_dev(osqp_amd_batch *b, c_float *X, c_float *Y, c_float *info8,
                                        c_float *DX, c_float *DY) {
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;

@@ -1,6 +1,6 @@
 """A batch of QPs as a differentiable PyTorch layer: the forward pass is update -> solve -> polish on a live
 BatchOSQP handle, the backward pass is BatchOSQP.adjoint (osqp_amd_batch_adjoint: one more solve with the KKT
-matrix of the active rows, on the device).
+matrix of the active rows, on the device), and forward-mode tangents come from BatchOSQP.tangent the same way.
 
 Inputs and outputs are float64 tensors on the CPU or the GPU, and the route follows Q (`layer.last_route`).
 CPU tensors ("host") are staged through numpy arrays on their way to and from the handle.  CUDA tensors ("device") set
@@ -44,6 +44,7 @@ class _BatchQPFunction(torch.autograd.Function):
         if Q.is_cuda:
             ctx.layer, ctx.route = layer, "device"
             ctx.save_for_backward(Q, L, U, Px, Ax)
+            ctx.save_for_forward(Q, L, U, Px, Ax)      # (jvp sees only these)
             ctx.set_materialize_grads(False)
             r = layer._solve_device(*(_dev(t) for t in (Q, L, U, Px, Ax)))
             ctx.serial = layer._serial
@@ -94,6 +95,34 @@ class _BatchQPFunction(torch.autograd.Function):
         return (None,) + tuple(torch.as_tensor(g, dtype=ref.dtype, device=ref.device) if w else None
                                for g, w in zip(outs, need))
 
+    @staticmethod
+    def jvp(ctx, _, tQ, tL, tU, tPx, tAx):
+        """Forward mode (torch.autograd.forward_ad): the tangents of X and Y from those of Q, L, U, Px, Ax (None = 0)
+        by BatchOSQP.tangent on the host route and tangent_into on the device route."""
+        layer = ctx.layer
+        if ctx.route == "device":
+            if layer._serial != ctx.serial:
+                layer._solve_device(*(_dev(t) for t in ctx.saved_tensors))
+                ctx.serial = layer._serial
+            h, dev = layer.h, layer.last_results.x.device
+            m = h.m > 0
+            # made contiguous before the hand-over, as in backward
+            t = dict(dQ=_dev(tQ), dL=_dev(tL) if m else None, dU=_dev(tU) if m else None, dPx=_dev(tPx), dAx=_dev(tAx))
+            tX = torch.empty((h.B, h.n), dtype=torch.float64, device=dev)
+            tY = torch.empty((h.B, h.m), dtype=torch.float64, device=dev)
+            st = torch.empty((h.B,), dtype=torch.int32, device=dev)
+            _hand_over(dev)
+            h.tangent_into(tX, tY if m else None, status_tangent=st, **t)
+            layer.last_status_tangent = st
+            return tX, tY
+        if layer._serial != ctx.serial:      # the handle has solved another problem since: bring this one back
+            layer._solve(*ctx.args)
+            ctx.serial = layer._serial
+        r = layer.h.tangent(*(_host(t) for t in (tQ, tL, tU, tPx, tAx)))
+        layer.last_status_tangent = r.status_tangent
+        like = dict(dtype=torch.float64, device=next((t.device for t in (tQ, tL, tU, tPx, tAx) if t is not None), "cpu"))
+        return torch.as_tensor(r.dx, **like), torch.as_tensor(r.dy, **like)
+
 
 class BatchQPLayer(torch.nn.Module):
     """x*(Q, L, U, Px, Ax) = argmin 1/2 x'Px + q'x  s.t.  l <= Ax <= u for a batch of QPs with the shared sparsity
@@ -110,6 +139,8 @@ class BatchQPLayer(torch.nn.Module):
     halves of the symmetric P.  Members whose solve did not end `solved` (or whose KKT matrix is rejected) get zero
     gradients; `last_status_adjoint` [B] (1 computed, -1 rejected, 0 not tried) and `last_results` say which.  Where active
     rows are linearly dependent or strict complementarity fails, the gradients are those of the guessed active set.
+    Forward mode works too: under `torch.autograd.forward_ad.dual_level()` the tangents of X and Y come from
+    BatchOSQP.tangent (an input without a tangent counts as zero; `last_status_tangent` [B] as `last_status_adjoint`).
 
     Tensors are float64, all on the CPU (staged through host numpy arrays) or all on one GPU: CUDA tensors set the handle
     up on their device, and every later call and every backward pass on the live handle runs without a host copy of
@@ -125,7 +156,7 @@ class BatchQPLayer(torch.nn.Module):
         self.h = None
         self._serial = 0
         self._own = [False, False]       # the handle holds per-member values of P / A given by a caller
-        self.last_results = self.last_status_adjoint = self.last_route = None
+        self.last_results = self.last_status_adjoint = self.last_status_tangent = self.last_route = None
         self._device = None              # device route: the device index the handle was set up on
         self._vals = {}                  # the layer's own P / A values as tensors on the handle's device
 
