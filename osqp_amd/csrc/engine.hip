@@ -180,8 +180,24 @@ struct Ctx {             // static pointers / sizes, passed by value
 #define TL_CAP (1 << 20)
 #define TL_MARK(c, id) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long k_ = atomicAdd((c).tl, 1ull); \
     if (k_ < TL_CAP - 2) (c).tl[1 + k_] = ((unsigned long long)(id) << 56) | (wall_clock64() & 0x00FFFFFFFFFFFFFFull); } } while (0)
+// Stamps inside k_pcg_init / k_admm_finalize (workgroup 0, thread 0): TLK_AT(k, v) reads the clock once v -- the last value a
+// flight of loads brings -- is in its register; the kernel's end writes them out as ids base + k (tools/loop_probe.py,
+// profiles/iter_kernels_chain_timeline.txt).
+// TLK_LAST(k): entry (0) and end (1, after its stores are acknowledged) of the LAST workgroup of the grid, ids base + 20 + k.
+#define TLK_N 10
+#define TLK_DECL long long tlk_[TLK_N], tll_[2] = {0, 0}; for (int q_ = 0; q_ < TLK_N; ++q_) tlk_[q_] = 0
+#define TLK_LAST(k) do { if (k) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) tll_[k] = wall_clock64(); } while (0)
+#define TLK_AT(k, v) do { asm volatile("" :: "v"(v)); if (blockIdx.x == 0 && threadIdx.x == 0) tlk_[k] = wall_clock64(); } while (0)
+#define TLK_FLUSH(c, base, n) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long k_ = atomicAdd((c).tl, (unsigned long long)(n)); \
+    if (k_ + (n) < TL_CAP - 2) for (int q_ = 0; q_ < (n); ++q_) (c).tl[1 + k_ + q_] = ((unsigned long long)((base) + q_) << 56) | ((unsigned long long)tlk_[q_] & 0x00FFFFFFFFFFFFFFull); } \
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) { const unsigned long long k_ = atomicAdd((c).tl, 2ull); \
+    if (k_ + 2 < TL_CAP - 2) for (int q_ = 0; q_ < 2; ++q_) (c).tl[1 + k_ + q_] = ((unsigned long long)((base) + 20 + q_) << 56) | ((unsigned long long)tll_[q_] & 0x00FFFFFFFFFFFFFFull); } } while (0)
 #else
 #define TL_MARK(c, id) do { } while (0)
+#define TLK_DECL do { } while (0)
+#define TLK_AT(k, v) do { } while (0)
+#define TLK_LAST(k) do { } while (0)
+#define TLK_FLUSH(c, base, n) do { } while (0)
 #endif
 
 enum {  // slots of Ctx::scal (max slots are bit patterns of non-negative doubles)
@@ -452,19 +468,64 @@ template <bool DENSE>
 __global__ void __launch_bounds__(TB) k_pcg_init(Ctx c, int bench) {
   State *st = c.st;
   TL_MARK(c, 1);
+  TLK_DECL;
+  TLK_AT(0, 0); TLK_LAST(0);
+  LDS_DECL(2);
+  // rows inside dense diagonal blocks of P: P x~0 by the block product, A' part from the remainder
+  // matrix; all other rows below (Mm = remainder matrix then, M itself otherwise)
+  const DevMat &Mm = DENSE ? c.Mk : c.M;
+  // Loads in three flights, as in k_admm_finalize (see there): the early returns gate stores only, every prefetch is an
+  // unconditional load at a clamped index.  Flight A: the state, the parameters and this workgroup's first stream block (engines without dense
+  // blocks of P; with them the dense rows come first and the stream blocks keep the plain form).
+  const int s_stalled = st->stalled, s_fail = st->res_fail, s_hist = st->hist_r;
+  const long long s_admm = st->admm_done, s_target = st->admm_target;
+  const Params prm = *c.prm;
+  // (the DENSE instantiation loads nothing here: everything below folds to the empty block)
+  RowBlk b = RowBlk{0, 0, 0, 0};
+  if constexpr (!DENSE) {
+    b = Mm.blk[max(min((int)blockIdx.x, Mm.nstream - 1), 0)];
+    if ((int)blockIdx.x >= Mm.nstream) b = RowBlk{0, 0, 0, 0};
+  }
+  TLK_AT(1, b.k1);
+  // what the start-up of one row reads besides its two sums
+  struct RowIn { double base0, base1, vx, minv; int u0, er; };
+  // (u0 and er are looked at only where c.u0pos / c.nelim say so; where their arrays do not exist the load goes to minv instead of
+  // into a branch, whose merge would wait for the whole flight)
+  const unsigned short *u0m = c.u0pos ? c.u0map : reinterpret_cast<const unsigned short *>(c.minv);
+  const int *erw = c.nelim ? c.erow : reinterpret_cast<const int *>(c.minv);
+  auto row_load = [&](int j) {
+    RowIn r;
+    r.base0 = (prm.use_cvec ? c.cvec : c.xy)[j]; r.base1 = c.q[j];
+    r.vx = c.vx[j]; r.minv = c.minv[j];
+    r.u0 = (int)u0m[j]; r.er = erw[j];
+    return r;
+  };
+  // Flight B: the chunk's indices and values, the row pointers of the row this thread helps to sum in the first round, and
+  // that row's scalars in the lane that will start it.
+  constexpr int E = MAX_CHUNK / TB;
+  const int cnt = b.k1 - b.k0;
+  int cc[E] = {}; double vv[E] = {};
+  const int RL = lanes_for(b.r1 - b.r0), rg = threadIdx.x / RL, rlane = threadIdx.x % RL;
+  const int jf = b.r0 + rg, jfc = max(min(jf, b.r1 - 1), 0);
+  int p0 = 0, p1 = 0;
+  RowIn rf = {};
+  if constexpr (!DENSE) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int kc = max(min(b.k0 + (int)threadIdx.x + e * TB, b.k1 - 1), 0);
+      cc[e] = Mm.col[kc]; vv[e] = Mm.val[kc];
+    }
+    p0 = Mm.rowptr[jfc]; p1 = Mm.rowptr[jfc + 1];
+    rf = row_load(jfc);
+  }
   // A solve that ran out of unrolled PCG iterations (`stalled`, raised by k_admm_finalize) is continued by
   // this graph launch: no new right-hand side, the iteration kernels below pick the recurrences up where they
   // stopped (K is even, so the parity of every ping-pong buffer is preserved).
   if (!bench) {
-    if (st->stalled || st->res_fail) return;
-    if (st->admm_done >= st->admm_target) { if (blockIdx.x == 0 && threadIdx.x == 0) st->run = 0; return; }
+    if (s_stalled || s_fail) return;
+    if (s_admm >= s_target) { if (blockIdx.x == 0 && threadIdx.x == 0) st->run = 0; return; }
   }
-  LDS_DECL(2);
-  const Params prm = *c.prm;
   double prz = 0, prr = 0, pbb = 0;
-  // rows inside dense diagonal blocks of P: P x~0 by the block product, A' part from the remainder
-  // matrix; all other rows below (Mm = remainder matrix then, M itself otherwise)
-  const DevMat &Mm = DENSE ? c.Mk : c.M;
   if (DENSE)
   for (int db = blockIdx.x; db < c.dP.nblk; db += gridDim.x) {
     const DenseBlk d = c.dP.blk[db];
@@ -492,29 +553,57 @@ __global__ void __launch_bounds__(TB) k_pcg_init(Ctx c, int bench) {
     __syncthreads();
   }
   // row j of the start-up given sA = (M [x~0 | rho z~0])_j and sB = (M [0 | rho z - y])_j, by one thread
-  auto row_start = [&](int j, double sA, double sB) {
+  auto row_apply = [&](int j, double sA, double sB, const RowIn &r) {
     if (DENSE) for (int k = 0; k < c.nh; ++k) { const double hc = c.hcol[(size_t)k * c.n + j]; sA += hc * c.vx[c.n + c.hrow[k]]; sB += hc * c.vb[c.n + c.hrow[k]]; }
-    const double base = prm.use_cvec ? c.cvec[j] : (prm.sigma * c.xy[j] - c.q[j]);
-    const bool gone = c.nelim && c.erow[j] >= 0;           // eliminated from the system: no residual, no direction
+    const double base = prm.use_cvec ? r.base0 : (prm.sigma * r.base0 - r.base1);
+    const bool gone = c.nelim && r.er >= 0;                // eliminated from the system: no residual, no direction
     const double bj = gone ? 0.0 : base + sB;
-    const double rj = gone ? 0.0 : bj - prm.sigma * c.vx[j] - sA;
-    const double zj = c.minv[j] * rj;
+    const double rj = gone ? 0.0 : bj - prm.sigma * r.vx - sA;
+    const double zj = r.minv * rj;
     c.init_r[(size_t)j * c.init_stride] = rj;
     c.init_z[j] = zj;
-    if (c.u0pos) c.u0pos[c.u0map[j]] = zj;
+    if (c.u0pos) c.u0pos[r.u0] = zj;
     prz += rj * zj; prr += rj * rj; pbb += bj * bj;
   };
-  for (int bi = blockIdx.x; bi < Mm.nstream; bi += gridDim.x) {
-    const RowBlk b = Mm.blk[bi];
-    stage_products<2>(Mm, b, c.vx, c.vb, lprod, lprod + MAX_CHUNK);
+  auto row_start = [&](int j, double sA, double sB) { row_apply(j, sA, sB, row_load(j)); };
+  // this workgroup's first stream block -- Flight C: the two gathers per entry; then the row sums, and the first round of
+  // rows on what flight B brought
+  if (!DENSE) {
+    double xa[E], xb[E];
+    TLK_AT(2, cc[E - 1]);
+#pragma unroll
+    for (int e = 0; e < E; ++e) { xa[e] = c.vx[cc[e]]; xb[e] = c.vb[cc[e]]; }      // (beyond the chunk: the clamped entry's column again)
+    TLK_AT(3, xb[E - 1]);
+#pragma unroll
+    for (int e = 0; e < E; ++e) { const int k = threadIdx.x + e * TB; if (k < cnt) { lprod[k] = vv[e] * xa[e]; lprod[MAX_CHUNK + k] = vv[e] * xb[e]; } }
     __syncthreads();
+    TLK_AT(4, 0);
     // the summation order is free here (PCG-internal): several lanes per row
-    const int RL = lanes_for(b.r1 - b.r0), rg = threadIdx.x / RL, rlane = threadIdx.x % RL;
-    for (int j = b.r0 + rg; j < b.r1; j += TB / RL) {
+    if (jf < b.r1) {
+      const double sA = row_sum_par(lprod, p0 - b.k0, p1 - b.k0, rlane, RL);
+      const double sB = row_sum_par(lprod + MAX_CHUNK, p0 - b.k0, p1 - b.k0, rlane, RL);
+      if (rlane == 0) row_apply(jf, sA, sB, rf);
+    }
+    TLK_AT(5, prz);
+    for (int j = jf + TB / RL; j < b.r1; j += TB / RL) {
       const int a0 = Mm.rowptr[j] - b.k0, a1 = Mm.rowptr[j + 1] - b.k0;
       const double sA = row_sum_par(lprod, a0, a1, rlane, RL);
       const double sB = row_sum_par(lprod + MAX_CHUNK, a0, a1, rlane, RL);
       if (rlane == 0) row_start(j, sA, sB);
+    }
+    __syncthreads();
+  }
+  // ... the blocks beyond the grid (with dense blocks of P: all stream blocks) in the plain form
+  for (int bi = DENSE ? blockIdx.x : blockIdx.x + gridDim.x; bi < Mm.nstream; bi += gridDim.x) {
+    const RowBlk bb = Mm.blk[bi];
+    stage_products<2>(Mm, bb, c.vx, c.vb, lprod, lprod + MAX_CHUNK);
+    __syncthreads();
+    const int RLb = lanes_for(bb.r1 - bb.r0), rgb = threadIdx.x / RLb, rlb = threadIdx.x % RLb;
+    for (int j = bb.r0 + rgb; j < bb.r1; j += TB / RLb) {
+      const int a0 = Mm.rowptr[j] - bb.k0, a1 = Mm.rowptr[j + 1] - bb.k0;
+      const double sA = row_sum_par(lprod, a0, a1, rlb, RLb);
+      const double sB = row_sum_par(lprod + MAX_CHUNK, a0, a1, rlb, RLb);
+      if (rlb == 0) row_start(j, sA, sB);
     }
     __syncthreads();
   }
@@ -550,13 +639,16 @@ __global__ void __launch_bounds__(TB) k_pcg_init(Ctx c, int bench) {
     if (lane == 0) row_start(lb.r0, sA, sB);
   }
   block_sum3(prz, prr, pbb, red);
+  TLK_AT(6, prz);
   if (threadIdx.x == 0) {
     c.part_rz[blockIdx.x] = prz; c.part_rr[blockIdx.x] = prr; c.part_bb[blockIdx.x] = pbb;
     if (blockIdx.x == 0) {
       st->run = 1; st->done = 0; st->neg_curv = 0; st->iters[0] = 0; st->iters[1] = 0;
-      if (st->hist_r < (1 << 20)) st->hist_r += 1;
+      if (s_hist < (1 << 20)) st->hist_r = s_hist + 1;
     }
   }
+  TLK_LAST(1);
+  TLK_FLUSH(c, 100, 7);
 }
 
 // ---------------------------------------------------------------------------
@@ -956,83 +1048,174 @@ __device__ __forceinline__ double elim_vb(const Ctx &c, const Params &prm, int i
 __global__ void __launch_bounds__(TB) k_admm_finalize(Ctx c) {
   State *st = c.st;
   TL_MARK(c, 4);
-  if (!st->run || st->res_fail) return;
+  TLK_DECL;
+  TLK_AT(0, 0); TLK_LAST(0);
   LDS_DECL(1);
+  // A launch starts with cold vector L1 and translation caches, so what this kernel costs at config 2 is not its 2.4 MB but its
+  // chain of dependent round trips.  The loads are therefore issued in three flights, each as soon as its addresses are known, and
+  // the early returns below gate stores only.  The prefetches are unconditional loads at clamped indices (no branch per load: a
+  // use the compiler moves into such a branch would wait there), so they are in bounds in every thread of every workgroup
+  // whatever the verdict turns out to be; every array of the engine holds at least one element.
+  // Flight A (addresses from blockIdx / threadIdx alone): the state, the parameters, this workgroup's first row block, the
+  // partials of ||r||^2 and the first round of the x part (both candidates for x~: the choice needs `iters`).
+  const int s_run = st->run, s_fail = st->res_fail, s_done = st->done, s_neg = st->neg_curv, s_hist = st->hist_r;
+  const int s_it0 = st->iters[0], s_it1 = st->iters[1];
+  const double s_tol2 = st->tol2;
+  const long long s_admm = st->admm_done, s_total = st->iters_total;
+  const int s_max = st->iters_max, s_min = st->iters_min, s_forced = st->forced, s_negseen = st->neg_curv_seen;
   const Params prm = *c.prm;
-  double rr[1];
-  reduce_parts<1>(c.fin_rr, nullptr, nullptr, c.fin_cnt, red, rr);
-  const int iters = st->iters[0] > st->iters[1] ? st->iters[0] : st->iters[1];
-  const bool conv = st->done == 1 || rr[0] <= st->tol2;
-  const bool force = st->done == 2 || iters >= prm.pcg_max_iter || st->neg_curv;
+  const bool ex = c.vx != c.va;
+  const bool have = (int)blockIdx.x < c.A.nstream;
+  RowBlk b = c.A.blk[max(min((int)blockIdx.x, c.A.nstream - 1), 0)];
+  if (!have) b = RowBlk{0, 0, 0, 0};
+  TLK_AT(1, b.k1);
+  constexpr int NP = MAX_PARTS / TB;
+  double fp[NP];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) fp[k] = c.fin_rr[max(min((int)threadIdx.x + k * TB, c.fin_cnt - 1), 0)];
+  double *x = c.xy, *y = c.xy + c.n;
+  const int j0 = blockIdx.x * TB + threadIdx.x, jc = max(min(j0, c.n - 1), 0);
+  const double xo0 = x[jc], xa0 = c.va[jc], xv0 = c.vx[jc], vo0 = c.vold[jc];
+  // what update_z / update_y of one row read besides z~
+  struct RowIn { double rho, rinv, yo, zo, lo, up, vo, ea, edi, rhe; int ye; };
+  auto row_load = [&](int i) {
+    RowIn r;
+    r.rho = c.rho[i]; r.rinv = c.rhoinv[i]; r.yo = y[i]; r.zo = c.z[i]; r.lo = c.l[i]; r.up = c.u[i];
+    r.vo = c.vold[c.n + i];
+    r.ye = -1; r.ea = 0.0; r.edi = 0.0; r.rhe = 0.0;
+    if (c.nelim) { r.ye = c.ecol[i]; r.ea = c.ecoef[i]; r.edi = c.edinv[i]; r.rhe = c.rhoe[i]; }
+    return r;
+  };
+  // Flight B (addresses from the block descriptor): the chunk's indices and values, the row pointers of the row this thread
+  // helps to sum in the first round, and that row's scalars in the lane that will update it.
+  constexpr int E = MAX_CHUNK / TB;
+  const int cnt = b.k1 - b.k0;
+  int cc[E]; double vv[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const int kc = max(min(b.k0 + (int)threadIdx.x + e * TB, b.k1 - 1), 0);
+    cc[e] = c.A.col[kc]; vv[e] = c.A.val[kc];
+  }
+  const int RL = lanes_for(b.r1 - b.r0), rg = threadIdx.x / RL, rlane = threadIdx.x % RL;
+  const int i0 = b.r0 + rg, ic = max(min(i0, b.r1 - 1), 0);
+  const int p0 = c.A.rowptr[ic], p1 = c.A.rowptr[min(ic + 1, c.A.nrows)];
+  const RowIn ri0 = row_load(ic);
+  const int er0 = (c.nelim ? c.erow : reinterpret_cast<const int *>(c.rho))[c.nelim ? jc : 0];   // (looked at only where c.nelim; no branch, whose merge would wait)
+  TLK_AT(2, fp[NP - 1]);
+  if (!s_run || s_fail) return;
+  // A solve that ended converged (done == 1: every resident launch that did, every k_cg_A that saw its stop test pass) has its
+  // verdict already; only done == 0 (the last unrolled iteration's residual is still in the partials) and done == 2 (a forced
+  // stop counts as `forced` only if that residual misses the tolerance) read ||r||^2.  s_done is the same in every thread.
+  double rr[1] = {0.0};
+  if (s_done != 1) {
+    // reduce_parts<1> on the prefetched partials: the same additions in the same order
+    double s0 = 0;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) s0 = (int)threadIdx.x + k * TB < c.fin_cnt ? s0 + fp[k] : s0;
+    for (int i = threadIdx.x + NP * TB; i < c.fin_cnt; i += TB) s0 += c.fin_rr[i];
+    rr[0] = block_sum(s0, red);
+  }
+  TLK_AT(3, rr[0]);
+  const int iters = s_it0 > s_it1 ? s_it0 : s_it1;
+  const bool conv = s_done == 1 || rr[0] <= s_tol2;
+  const bool force = s_done == 2 || iters >= prm.pcg_max_iter || s_neg;
   if (!conv && !force) {
     if (blockIdx.x == 0 && threadIdx.x == 0) st->stalled = 1;
     return;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     st->stalled = 0;
-    st->admm_done += 1;
+    st->admm_done = s_admm + 1;
     st->iters_last = iters;
-    st->iters_total += iters;
-    if (iters > st->iters_max) st->iters_max = iters;
-    if (iters < st->iters_min) st->iters_min = iters;
-    if (!conv) st->forced += 1;
-    if (st->neg_curv) st->neg_curv_seen += 1;
+    st->iters_total = s_total + iters;
+    if (iters > s_max) st->iters_max = iters;
+    if (iters < s_min) st->iters_min = iters;
+    if (!conv) st->forced = s_forced + 1;
+    if (s_neg) st->neg_curv_seen = s_negseen + 1;
   }
   const double alpha = prm.alpha, oma = 1.0 - prm.alpha;
   // start vector of the next PCG solve: [x~ | rho z~] + theta * (change since the previous ADMM
   // iteration).  No extrapolation in the first iterations after a reset (the iterates still jump),
   // half a step for a while, then the full linear step.  hist_r is advanced by k_pcg_init only.
-  const int hist = st->hist_r;
+  const int hist = s_hist;
   const double th = (hist < prm.ex_h0 ? 0.0 : (hist < prm.ex_h1 ? 0.5 : 1.0)) * prm.ex_theta;
-  const bool ex = c.vx != c.va;
   // the start vector itself passed the stop test (no PCG update ran): x~ is the start vector
   const bool from_start = ex && iters == 0;
   const double *xts = from_start ? c.vx : c.va;
-  double *x = c.xy, *y = c.xy + c.n;
-  for (int j = blockIdx.x * TB + threadIdx.x; j < c.n; j += gridDim.x * TB) {
-    if (c.nelim && c.erow[j] >= 0) continue;      // eliminated from the linear system: its row's thread back-substitutes and updates it below
-    const double xo = x[j], xt = xts[j];
+  auto x_update = [&](int j, double xo, double xt, double vo) {
     const double xn = alpha * xt + oma * xo;
     c.dxy[j] = xn - xo;
     x[j] = xn;
-    if (ex) { c.vx[j] = xt + th * (xt - c.vold[j]); c.vold[j] = xt; }
+    // (from_start: the rows below gather x~ from vx in every workgroup while this one runs, so vx must stay what it is -- the next
+    // solve then starts from x~ itself; the iterates have all but stopped moving when a start vector passes the stop test)
+    if (ex) { if (!from_start) c.vx[j] = xt + th * (xt - vo); c.vold[j] = xt; }
     if (from_start) c.va[j] = xt;
+  };
+  // (eliminated from the linear system: its row's thread back-substitutes and updates it below)
+  if (j0 < c.n && !(c.nelim && er0 >= 0)) x_update(j0, xo0, from_start ? xv0 : xa0, vo0);
+  for (int j = j0 + gridDim.x * TB; j < c.n; j += gridDim.x * TB) {
+    if (c.nelim && c.erow[j] >= 0) continue;
+    x_update(j, x[j], xts[j], c.vold[j]);
   }
   // update_z / update_y of row i given z~_i = (A x~)_i (without the eliminated variable's term), by one thread
-  auto row_update = [&](int i, double zt) {
-    const double rho = c.rho[i], rinv = c.rhoinv[i], yo = y[i], zo = c.z[i];
-    const int ye = c.nelim ? c.ecol[i] : -1;
+  auto row_apply = [&](int i, double zt, const RowIn &r) {
+    const double rho = r.rho, rinv = r.rinv, yo = r.yo, zo = r.zo;
+    const int ye = r.ye;
     double rz = rho * zt, xny = 0.0;
     if (ye >= 0) {
       // zt so far is (A_X x~_X)_i: the PCG vector is zero at the eliminated variable.  Back substitution
       // x~_y = (b_y - rho a (A_X x~_X)_i) / D_y with the b_y of the system just solved, then the variable's own update_x.
-      const double a = c.ecoef[i], xoy = x[ye];
+      const double a = r.ea, xoy = x[ye];
       const double by = (prm.use_cvec ? c.cvec[ye] : (prm.sigma * xoy - c.q[ye])) + a * (rho * zo - yo);
-      const double xty = (by - rho * a * zt) * c.edinv[i];
-      rz = c.rhoe[i] * zt;                     // what the operator of the reduced system applies to this row
+      const double xty = (by - rho * a * zt) * r.edi;
+      rz = r.rhe * zt;                         // what the operator of the reduced system applies to this row
       zt += a * xty;
       xny = alpha * xty + oma * xoy;
       c.dxy[ye] = xny - xoy; x[ye] = xny; c.xte[i] = xty;
     }
     double v = alpha * zt + oma * zo + rinv * yo;
-    v = fmax(v, c.l[i]);
-    const double zn = fmin(v, c.u[i]);
+    v = fmax(v, r.lo);
+    const double zn = fmin(v, r.up);
     const double dy = rho * (alpha * zt + oma * zo - zn);
     const double yn = yo + dy;
     c.z[i] = zn; y[i] = yn; c.dy[i] = dy; c.zt[i] = zt;
     c.va[c.n + i] = rz;
-    if (ex) { c.vx[c.n + i] = rz + th * (rz - c.vold[c.n + i]); c.vold[c.n + i] = rz; }
+    if (ex) { c.vx[c.n + i] = rz + th * (rz - r.vo); c.vold[c.n + i] = rz; }
     c.vb[c.n + i] = ye >= 0 ? elim_vb(c, prm, i, rho, rho * zn - yn, xny) : rho * zn - yn;
   };
-  // stream blocks (whole rows staged through LDS)
-  for (int bi = blockIdx.x; bi < c.A.nstream; bi += gridDim.x) {
-    const RowBlk b = c.A.blk[bi];
-    stage_products<1>(c.A, b, xts, nullptr, lprod, nullptr);
+  auto row_update = [&](int i, double zt) { row_apply(i, zt, row_load(i)); };
+  // stream blocks (whole rows staged through LDS).  This workgroup's first block -- Flight C: the gathers from the vector the
+  // verdict selected; then the row sums, and the first round of rows on what flight B brought
+  {
+    double xg[E];
+    TLK_AT(4, cc[E - 1]);
+#pragma unroll
+    for (int e = 0; e < E; ++e) xg[e] = xts[cc[e]];      // (beyond the chunk: the clamped entry's column again)
+    TLK_AT(5, xg[E - 1]);
+#pragma unroll
+    for (int e = 0; e < E; ++e) { const int k = threadIdx.x + e * TB; if (k < cnt) lprod[k] = vv[e] * xg[e]; }
     __syncthreads();
-    const int RL = lanes_for(b.r1 - b.r0), rg = threadIdx.x / RL, rlane = threadIdx.x % RL;
-    for (int i = b.r0 + rg; i < b.r1; i += TB / RL) {
+    TLK_AT(6, 0);
+    if (i0 < b.r1) {
+      const double zt = row_sum_par(lprod, p0 - b.k0, p1 - b.k0, rlane, RL);
+      if (rlane == 0) row_apply(i0, zt, ri0);
+    }
+    TLK_AT(7, 0);
+    for (int i = i0 + TB / RL; i < b.r1; i += TB / RL) {
       const double zt = row_sum_par(lprod, c.A.rowptr[i] - b.k0, c.A.rowptr[i + 1] - b.k0, rlane, RL);
       if (rlane == 0) row_update(i, zt);
+    }
+    __syncthreads();
+  }
+  // ... and the blocks beyond the grid, in the plain form
+  for (int bi = blockIdx.x + gridDim.x; bi < c.A.nstream; bi += gridDim.x) {
+    const RowBlk bb = c.A.blk[bi];
+    stage_products<1>(c.A, bb, xts, nullptr, lprod, nullptr);
+    __syncthreads();
+    const int RLb = lanes_for(bb.r1 - bb.r0), rgb = threadIdx.x / RLb, rlb = threadIdx.x % RLb;
+    for (int i = bb.r0 + rgb; i < bb.r1; i += TB / RLb) {
+      const double zt = row_sum_par(lprod, c.A.rowptr[i] - bb.k0, c.A.rowptr[i + 1] - bb.k0, rlb, RLb);
+      if (rlb == 0) row_update(i, zt);
     }
     __syncthreads();
   }
@@ -1062,6 +1245,8 @@ __global__ void __launch_bounds__(TB) k_admm_finalize(Ctx c) {
     if (threadIdx.x == 0) row_update(c.A.blk[bi].r0, zt);
     __syncthreads();
   }
+  TLK_AT(8, 0); TLK_LAST(1);
+  TLK_FLUSH(c, 110, 9);
 }
 
 

@@ -50,7 +50,30 @@ if hasattr(L, "hipeng_timeline"):      # make TIMELINE=1 build: where the time o
                 v = v[v < 1e4]
                 row.append(v.mean() if v.size else float("nan"))
             print("   phase %d: " % ph + " ".join("%6.2f" % x for x in row))
-    wsel = wsel | w1
+    # stamps inside k_pcg_init (ids 100..) and k_admm_finalize (110..), workgroup 0: us since the kernel's first instruction
+    chain = {100: ("k_pcg_init", ("entry", "state, parameters, block descriptor in", "indices, values, row pointers, row scalars in",
+                                  "gathers in", "products in LDS, barrier passed", "first round of rows started", "partials reduced")),
+             110: ("k_admm_finalize", ("entry", "state, parameters, block descriptor in", "partials of ||r||^2 in", "verdict",
+                                       "indices and values in", "gathers in", "products in LDS, barrier passed", "first round of rows updated",
+                                       "kernel end"))}
+    wc = (ids >= 100) & (ids < 140)
+    for base, (kname, labels) in chain.items():
+        t0 = ts[ids == base]
+        if t0.size == 0: continue
+        print("  %s, workgroup 0, thread 0: us since its first stamp (%d launches)" % (kname, t0.size))
+        for q in range(1, 10):
+            tq = ts[ids == base + q]
+            if tq.size != t0.size: continue
+            d = tq - t0
+            d = d[(d >= 0) & (d < 1e3)]
+            if d.size: print("   %-2d %-52s mean %5.2f  min %5.2f  max %6.2f" % (q, labels[q] if q < len(labels) else "", d.mean(), d.min(), d.max()))
+        for q, what in ((20, "last workgroup of the grid: entry"), (21, "last workgroup of the grid: end, stores acknowledged")):
+            tq = ts[ids == base + q]
+            if tq.size != t0.size: continue
+            d = tq - t0
+            d = d[(d > -1e3) & (d < 1e3)]
+            if d.size: print("   %-55s mean %5.2f  min %5.2f  max %6.2f" % (what, d.mean(), d.min(), d.max()))
+    wsel = wsel | w1 | wc
     ids, ts = ids[~wsel], ts[~wsel]
     order = np.argsort(ts, kind="stable"); ids, ts = ids[order], ts[order]
     per = np.diff(ts)
