@@ -100,6 +100,40 @@ typedef struct {
                             or a resident launch found the GPU shared and the engine fell back) */
 } osqp_amd_stats;
 c_int osqp_amd_get_stats(const OSQPWorkspace *work, osqp_amd_stats *st);
+/* Derivatives of the solution at the point the workspace holds (the polished one where settings->polish ran and was accepted,
+ * the ADMM iterate otherwise), for one QP what osqp_amd_batch_adjoint / osqp_amd_batch_tangent (osqp_amd_batch.h) are for a batch
+ * member, in the CSC order of triu(P) / A as given to osqp_setup.  With the active rows (polish's two tests on the scaled z, y,
+ * l, u; lows first, then upps), Ar those rows of A and M = [P, Ar'; Ar, 0]:
+ *   adjoint  M [rx; rnu] = [dx; dy_act]:  dq = -rx, dl_i (du_i) = rnu at a row active at its lower (upper) bound,
+ *            dA_ij = -(y_i rx_j + rnu_i x_j) on active rows, dP_ij = -(rx_i x_j + rx_j x_i) (an off-diagonal slot of triu(P) stands
+ *            for both halves; -rx_i x_i on the diagonal);
+ *   tangent  M [dx; dnu] = [-(dq + dP x + dA' y_act); db_act - (dA x)_act], dy = dnu on the active rows, ndir directions that share
+ *            the KKT instance (dl = du is expected on an equality row; the tangent of the bound a row is active at is used).
+ * The solve is polish's, in the scaled space with D, E, c as constants: d' = max(delta, 1e-3), at least polish_refine_iter
+ * refinement steps, at most max(polish_refine_iter, 15), the same stop rule.  kkt_res is the last |g - M s|_inf / max(|g|_inf, 1)
+ * of that space, reported and not judged.  active: -1 / +1 / 0 per row.
+ * status: 1 computed; -1 a linear solve failed (negative curvature, a HIP error, a non-finite value), outputs 0; 0 not tried
+ * (info->status_val != OSQP_SOLVED), outputs 0.
+ * Return 0, OSQP_WORKSPACE_NOT_INIT_ERROR (NULL workspace; no osqp_solve since setup, since the last osqp_update_* of data,
+ * matrices or rho, or since an osqp_warm_start*), OSQP_DATA_VALIDATION_ERROR (NULL dx / dq / status, NULL dl / du with m > 0,
+ * ndir < 1 or ndir > OSQP_AMD_MAX_NDIR = 65535: the directions of a call are one dimension of one kernel launch).
+ * The first call after a solve builds the KKT instance (Ared and a polish-mode plugin instance); it is kept until the next
+ * osqp_solve, update, warm start or osqp_cleanup, so a backward pass, a forward pass and all directions share it (it is built with
+ * the delta of that moment: osqp_update_delta drops it, and the next call builds one with the new value; polish_refine_iter is read
+ * by every call).  Nothing of the
+ * workspace changes: x, y, z, solution, info, the engine's iterates, rho and statistics stay bit-equal. */
+#define OSQP_AMD_MAX_NDIR 65535
+c_int osqp_amd_adjoint(OSQPWorkspace *work, const c_float *dx /*[n]*/, const c_float *dy /*[m], NULL = 0*/,
+                       c_float *dq, c_float *dl, c_float *du,
+                       c_float *dPx /*[nnzP], NULL = skip*/, c_float *dAx /*[nnzA], NULL = skip*/,
+                       c_int *active /*[m], NULL = skip*/, c_int *status, c_float *kkt_res /*NULL = skip*/);
+c_int osqp_amd_tangent(OSQPWorkspace *work, c_int ndir,
+                       const c_float *dq /*[ndir][n]*/, const c_float *dl, const c_float *du /*[ndir][m]*/,
+                       const c_float *dPx /*[ndir][nnzP]*/, const c_float *dAx /*[ndir][nnzA]*/,   /* any NULL = 0 */
+                       c_float *dx /*[ndir][n]*/, c_float *dy /*[ndir][m], NULL = skip*/,
+                       c_int *active, c_int *status, c_float *kkt_res /*[ndir], NULL = skip*/);
+/* for the tests: out[0] KKT instances built since setup, [1] one is alive, [2] its active rows, [3] linear solves since setup */
+c_int osqp_amd_sens_info(OSQPWorkspace *work, c_int out[4]);
 /* The options above are the DEFAULTS a new workspace / plugin instance copies at creation; afterwards
  * each instance has its own (no knob is shared between live workspaces).  These two read / change the
  * copy of one workspace (the device cannot be changed after setup). */

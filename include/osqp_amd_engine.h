@@ -180,6 +180,23 @@ long long hipeng_resident_dump(hipeng *e, int *row, int *col, double *val, long 
  * kernel.  Returns 0, 1 when a pivot was not positive, or a HIPENG_ERR_* code. */
 int hipeng_dense_invert_selftest(int n, const double *A, double *Ainv, double *ms);
 
+/* O(nnz) parts of the single-QP engine's solution derivatives (csrc/kkt_sens.h: k_sens_grad, k_sens_tan_rhs).  One hipsens per
+ * workspace, created at its first osqp_amd_adjoint / osqp_amd_tangent call and kept until cleanup; every call runs on the stream
+ * of `pe`, the polish-mode instance's engine whose solves it accompanies.  P, A: the patterns in the caller's CSC order.
+ * hipsens_set_point: the point (x~, y~ on the active rows and 0 elsewhere, act = -1 / +1 / 0 per row, D, E (NULL = ones), c).
+ * hipsens_grad: dPx [nnzP] / dAx [nnzA] (NULL = skip) of the adjoint from rx [n] and rnu scattered to the m rows.
+ * hipsens_tan_rhs: g [ndir][n + m], per direction -(dq~ + dP~ x~ + dA~' y~_act) and, on the rows, db~ - dA~ x~ (0 on an
+ * inactive row); any NULL tangent = 0. */
+typedef struct hipsens hipsens;
+int hipsens_create(hipsens **out, c_int n, c_int m, c_int nnzP, c_int nnzA, int device);
+void hipsens_destroy(hipsens *s);
+int hipsens_set_point(hipsens *s, hipeng *pe, const c_float *x, const c_float *yact, const c_int *act,
+                      const c_float *D, const c_float *E, c_float c);
+int hipsens_grad(hipsens *s, hipeng *pe, const csc *P, const csc *A, const c_float *rx, const c_float *rnu,
+                 c_float *dPx, c_float *dAx);
+int hipsens_tan_rhs(hipsens *s, hipeng *pe, const csc *P, const csc *A, c_int ndir, const c_float *dq, const c_float *dl,
+                    const c_float *du, const c_float *dPx, const c_float *dAx, c_float *g);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ from .interface import SolverHandle, Results
 from .batch import BatchOSQP
 from .multi import solve_many
 
-__all__ = ["OSQP", "BatchOSQP", "BatchQPLayer", "solve_many", "abi", "lib", "build", "engine_options", "set_engine_options"]
+__all__ = ["OSQP", "BatchOSQP", "BatchQPLayer", "QPLayer", "solve_many", "abi", "lib", "build", "engine_options", "set_engine_options"]
 
 
 def __getattr__(name):
@@ -20,6 +20,9 @@ def __getattr__(name):
     if name == "BatchQPLayer":
         from .layer import BatchQPLayer
         return BatchQPLayer
+    if name == "QPLayer":      # ... and the one over the single-QP engine
+        from .layer import QPLayer
+        return QPLayer
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

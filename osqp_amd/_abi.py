@@ -183,4 +183,9 @@ def bind_api(lib, prefix=""):
     api["update_P_A"] = fn("osqp_update_P_A", c_int, W, c_float_p, c_int_p, c_int,
                            c_float_p, c_int_p, c_int)
     api["update_rho"] = fn("osqp_update_rho", c_int, W, c_float)
+    if hasattr(lib, prefix + "osqp_amd_adjoint"):      # the product library; a second library with the reference's ABI alone has none
+        F, I = c_float_p, c_int_p
+        api["adjoint"] = fn("osqp_amd_adjoint", c_int, W, F, F, F, F, F, F, F, I, I, F)
+        api["tangent"] = fn("osqp_amd_tangent", c_int, W, c_int, F, F, F, F, F, F, F, I, I, F)
+        api["sens_info"] = fn("osqp_amd_sens_info", c_int, W, I)
     return api

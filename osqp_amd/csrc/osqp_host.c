@@ -86,6 +86,21 @@ static void fill_params(hipeng_params *p, const osqp_amd_options *o, c_float sig
 /* ------------------------------------------------------------------------ */
 /* the plugin object (vtable prefix + private part)                           */
 /* ------------------------------------------------------------------------ */
+/* Solution derivatives (osqp_amd_adjoint / osqp_amd_tangent): one polish-mode KKT instance per solved problem, built by the first
+ * call after a solve and dropped by the next solve, update or warm start; the device side (hipsens) and the host buffers stay
+ * until cleanup.  Allocated by the first call: a workspace that never asks has none of it. */
+typedef struct {
+  LinSysSolver *ls;       /* the instance: [P + d I, Ared'; Ared, -d I] (NULL: none alive) */
+  csc *Ared;
+  OSQPPolish pol;         /* its active rows (row maps of its own; polish's stay polish's) */
+  hipsens *dev;           /* O(nnz) kernels and their device arrays (csrc/kkt_sens.h) */
+  c_int dev_device;       /* ... and the device they live on: the instance's */
+  c_int built, solves;    /* instances built / linear solves since setup */
+  c_int *act;             /* [m] -1 / +1 / 0 */
+  c_float *yact, *rnu;    /* [m] y on the active rows, 0 elsewhere; rnu scattered to the rows */
+  c_float *rhs, *sol, *res, *tmp;   /* [n + m] */
+} sens_state;
+
 typedef struct {
   enum linsys_solver_type type;
   c_int (*solve)(LinSysSolver *self, c_float *b);
@@ -107,6 +122,8 @@ typedef struct {
   c_int host_syncs;
   c_int forced_warned;    /* the pcg_forced warning has been printed for this workspace */
   osqp_amd_options opt;   /* this instance's engine options (copied from the defaults at creation) */
+  sens_state *sens;       /* workspace view: solution derivatives (NULL until the first call) */
+  c_int sens_ready;       /* an osqp_solve has completed and no data, rho or iterate was changed since */
 } hip_pcg_solver;
 
 #define PCG(work) ((hip_pcg_solver *)((work)->linsys_solver))
@@ -138,9 +155,26 @@ static c_int pcg_solve_polish(LinSysSolver *self, c_float *b) {
   return pcg_solve(self, b);
 }
 
+static void sens_drop_instance(sens_state *ss) {
+  if (!ss) return;
+  if (ss->ls) ss->ls->free(ss->ls);
+  csc_spfree(ss->Ared);
+  ss->ls = NULL; ss->Ared = NULL;
+}
+static void sens_free(sens_state *ss) {
+  if (!ss) return;
+  sens_drop_instance(ss);
+  hipsens_destroy(ss->dev);
+  c_free(ss->pol.Alow_to_A); c_free(ss->pol.Aupp_to_A); c_free(ss->pol.A_to_Alow); c_free(ss->pol.A_to_Aupp);
+  c_free(ss->act); c_free(ss->yact); c_free(ss->rnu);
+  c_free(ss->rhs); c_free(ss->sol); c_free(ss->res); c_free(ss->tmp);
+  c_free(ss);
+}
+
 static void pcg_free(LinSysSolver *self) {
   hip_pcg_solver *s = (hip_pcg_solver *)self;
   if (!s) return;
+  sens_free(s->sens);
   hipeng_destroy(s->eng);
   hipeng_destroy(s->aux);
   c_free(s->rho_tmp);
@@ -689,6 +723,14 @@ static c_int extract_solution(OSQPWorkspace *w) {
 
 static c_int run_polish(OSQPWorkspace *w);
 
+/* the solved point is gone (a new solve starts, or data, rho or the iterates change): so is the KKT instance of its derivatives */
+static void sens_invalidate(OSQPWorkspace *w) {
+  hip_pcg_solver *s = PCG(w);
+  if (!s) return;
+  s->sens_ready = 0;
+  sens_drop_instance(s->sens);
+}
+
 /* ------------------------------------------------------------------------ */
 /* osqp_solve (src/osqp.c:288-654)                                            */
 /* ------------------------------------------------------------------------ */
@@ -699,6 +741,7 @@ c_int osqp_solve(OSQPWorkspace *w) {
   c_int exitflag = 0, iter = 0, can_check = 0, can_print = 0;
   const c_int with_obj = st->verbose;
 
+  sens_invalidate(w);
   if (w->clear_update_time == 1) w->info->update_time = 0.0;
   w->rho_update_from_solve = 1;
   tic(w->timer);
@@ -810,6 +853,7 @@ c_int osqp_solve(OSQPWorkspace *w) {
   if (extract_solution(w)) { exitflag = 1; goto done; }
 
   if (st->polish && w->info->status_val == OSQP_SOLVED) run_polish(w);
+  s->sens_ready = 1;
 
   w->info->run_time = (w->first_run ? w->info->setup_time : w->info->update_time) +
                       w->info->solve_time + w->info->polish_time;
@@ -850,6 +894,7 @@ static void upd_end(OSQPWorkspace *w) { w->info->update_time += toc(w->timer); }
 c_int osqp_update_lin_cost(OSQPWorkspace *w, const c_float *q_new) {
   NEED_WORK(w);
   upd_begin(w);
+  sens_invalidate(w);
   const c_int n = w->data->n;
   memcpy(w->data->q, q_new, (size_t)n * sizeof(c_float));
   if (w->settings->scaling) {
@@ -864,6 +909,7 @@ c_int osqp_update_lin_cost(OSQPWorkspace *w, const c_float *q_new) {
 }
 
 static c_int push_bounds(OSQPWorkspace *w) {
+  sens_invalidate(w);
   if (hipeng_upload_bounds(PCG(w)->eng, w->data->l, w->data->u)) return 1;
   info_reset(w->info);
   return reclassify_rows(w);
@@ -915,6 +961,7 @@ c_int osqp_update_upper_bound(OSQPWorkspace *w, const c_float *u_new) {
 
 static c_int warm(OSQPWorkspace *w, const c_float *x, const c_float *y) {
   const c_int n = w->data->n, m = w->data->m;
+  sens_invalidate(w);
   if (!w->settings->warm_start) w->settings->warm_start = 1;
   if (x) {
     memcpy(w->x, x, (size_t)n * sizeof(c_float));
@@ -939,6 +986,7 @@ static c_int patch(OSQPWorkspace *w, const c_float *Px, const c_int *Pi, c_int P
   hip_pcg_solver *s = PCG(w);
   const c_int nnzP = w->data->P->p[w->data->P->n], nnzA = w->data->A->p[w->data->A->n];
   upd_begin(w);
+  sens_invalidate(w);
   if (doP && Pi && Pn > nnzP) { fprintf(stderr, "ERROR: new number of elements greater than elements in P\n"); return 1; }
   if (doA && Ai && An > nnzA) { fprintf(stderr, "ERROR: new number of elements greater than elements in A\n"); return doP ? 2 : 1; }
   /* the reference trusts the index arrays; an index outside the matrix would write past its values */
@@ -988,6 +1036,7 @@ c_int osqp_update_rho(OSQPWorkspace *w, c_float rho_new) {   /* src/osqp.c:1281-
   NEED_WORK(w);
   if (rho_new <= 0) { fprintf(stderr, "ERROR in osqp_update_rho: rho must be positive\n"); return 1; }
   double t0 = 0;
+  sens_invalidate(w);
   if (!w->rho_update_from_solve) {
     if (w->clear_update_time == 1) { w->clear_update_time = 0; w->info->update_time = 0.0; }
     t0 = now_s();
@@ -1021,22 +1070,24 @@ SETTER(osqp_update_alpha, c_float, alpha, (v > 0. && v < 2.), "alpha must be bet
 SETTER(osqp_update_warm_start, c_int, warm_start, (v == 0 || v == 1), "warm_start should be either 0 or 1")
 SETTER(osqp_update_scaled_termination, c_int, scaled_termination, (v == 0 || v == 1), "scaled_termination should be either 0 or 1")
 SETTER(osqp_update_check_termination, c_int, check_termination, v >= 0, "check_termination should be nonnegative")
-SETTER(osqp_update_delta, c_float, delta, v > 0., "delta must be positive")
+c_int osqp_update_delta(OSQPWorkspace *w, c_float v) {
+  NEED_WORK(w);
+  if (!(v > 0.)) { fprintf(stderr, "ERROR in %s: %s\n", __func__, "delta must be positive"); return 1; }
+  w->settings->delta = v;
+  /* a kept KKT instance of the solution derivatives was built with the old delta: the next call builds one with the new */
+  if (w->linsys_solver) sens_drop_instance(PCG(w)->sens);
+  return 0;
+}
 SETTER(osqp_update_polish, c_int, polish, (v == 0 || v == 1), "polish should be either 0 or 1")
 SETTER(osqp_update_polish_refine_iter, c_int, polish_refine_iter, v >= 0, "polish_refine_iter must be nonnegative")
 SETTER(osqp_update_verbose, c_int, verbose, (v == 0 || v == 1), "verbose should be either 0 or 1")
 SETTER(osqp_update_time_limit, c_float, time_limit, v >= 0., "time_limit must be nonnegative")
 
-/* ------------------------------------------------------------------------ */
-/* polish (src/polish.c:19-350) through the plugin with polish = 1            */
-/* ------------------------------------------------------------------------ */
-static c_int run_polish(OSQPWorkspace *w) {
-  OSQPPolish *p = w->pol;
-  hip_pcg_solver *s = PCG(w);
-  const c_int n = w->data->n, m = w->data->m;
-  const csc *A = w->data->A;
-  tic(w->timer);
-  /* active-set guess from the ADMM (z, y) (polish.c:19-103) */
+/* The route polish and the solution derivatives (osqp_amd_adjoint / osqp_amd_tangent) share: the active-row guess, Ared, the
+ * polish-mode instance and the refined solve. */
+/* active-set guess from the (z, y) the workspace holds (polish.c:19-103); p: row maps of m entries each */
+static void guess_active_rows(const OSQPWorkspace *w, OSQPPolish *p) {
+  const c_int m = w->data->m;
   p->n_low = p->n_upp = 0;
   for (c_int i = 0; i < m; i++) {
     if (w->z[i] - w->data->l[i] < -w->y[i]) { p->Alow_to_A[p->n_low] = i; p->A_to_Alow[i] = p->n_low++; }
@@ -1046,12 +1097,18 @@ static c_int run_polish(OSQPWorkspace *w) {
     if (w->data->u[i] - w->z[i] < w->y[i]) { p->Aupp_to_A[p->n_upp] = i; p->A_to_Aupp[i] = p->n_upp++; }
     else p->A_to_Aupp[i] = -1;
   }
+}
+
+/* the active rows of A, lows first, then upps */
+static csc *form_Ared(const OSQPWorkspace *w, const OSQPPolish *p) {
+  const c_int n = w->data->n;
+  const csc *A = w->data->A;
   const c_int mred = p->n_low + p->n_upp;
   c_int cnt = 0;
   for (c_int k = 0; k < A->p[n]; k++)
     if (p->A_to_Alow[A->i[k]] != -1 || p->A_to_Aupp[A->i[k]] != -1) cnt++;
   csc *Ar = (csc *)c_calloc(1, sizeof(csc));
-  if (!Ar) { w->info->status_polish = -1; return -1; }
+  if (!Ar) return NULL;
   Ar->m = mred; Ar->n = n; Ar->nz = -1; Ar->nzmax = cnt > 0 ? cnt : 1;
   Ar->p = (c_int *)c_calloc((size_t)n + 1, sizeof(c_int));
   Ar->i = (c_int *)c_calloc((size_t)Ar->nzmax, sizeof(c_int));
@@ -1066,29 +1123,33 @@ static c_int run_polish(OSQPWorkspace *w) {
     }
   }
   Ar->p[n] = cnt;
-  p->Ared = Ar;
+  return Ar;
+}
 
-  /* The reference solves [P + dI, Ar'; Ar, -dI] with d = settings->delta (1e-6) by a direct factorisation and
-   * refines against the unregularised KKT matrix (polish.c:134-181, 232-260).  The indirect plugin solves the
-   * equivalent reduced system (P + dI + Ar'Ar/d) x = rhs1 + Ar'rhs2/d and recovers nu = (Ar x - rhs2)/d: that
-   * difference loses log10(1/d) digits, and cond(K) grows like 1/d, so at d = 1e-6 nothing of nu is left.  The
-   * regularisation only has to be small against the KKT matrix for the refinement to contract (error factor
-   * ~ d/sigma_min per step), so the solves use d = max(delta, 1e-3) -- nu keeps ~9 digits -- and the refinement
-   * runs until the true KKT residual (evaluated on the device) stops falling: same limit point, the solution of
-   * the unregularised system, as the reference's 3 steps at 1e-6. */
+/* The reference solves [P + dI, Ar'; Ar, -dI] with d = settings->delta (1e-6) by a direct factorisation and
+ * refines against the unregularised KKT matrix (polish.c:134-181, 232-260).  The indirect plugin solves the
+ * equivalent reduced system (P + dI + Ar'Ar/d) x = rhs1 + Ar'rhs2/d and recovers nu = (Ar x - rhs2)/d: that
+ * difference loses log10(1/d) digits, and cond(K) grows like 1/d, so at d = 1e-6 nothing of nu is left.  The
+ * regularisation only has to be small against the KKT matrix for the refinement to contract (error factor
+ * ~ d/sigma_min per step), so the solves use d = max(delta, 1e-3) -- nu keeps ~9 digits -- and the refinement
+ * runs until the true KKT residual (evaluated on the device) stops falling: same limit point, the solution of
+ * the unregularised system, as the reference's 3 steps at 1e-6. */
+static c_int kkt_instance(const OSQPWorkspace *w, const csc *Ar, LinSysSolver **ls) {
   const c_float delta = HMAX(w->settings->delta, POLISH_DELTA_MIN);
-  LinSysSolver *ls = NULL;
-  if (init_linsys_solver(&ls, w->data->P, Ar, delta, NULL, w->settings->linsys_solver, 1)) {
-    w->info->status_polish = -1; free_csc(Ar); p->Ared = NULL; return 1;
-  }
-  hipeng *pe = ((hip_pcg_solver *)ls)->eng;      /* the polish instance's engine holds P and Ared */
-  const c_int N = n + mred;
-  c_float *rhs = zero_vec(N), *sol = zero_vec(N), *res = zero_vec(N), *tmp = zero_vec(N);
-  for (c_int j = 0; j < n; j++) rhs[j] = -w->data->q[j];
-  for (c_int k = 0; k < p->n_low; k++) rhs[n + k] = w->data->l[p->Alow_to_A[k]];
-  for (c_int k = 0; k < p->n_upp; k++) rhs[n + p->n_low + k] = w->data->u[p->Aupp_to_A[k]];
+  return init_linsys_solver(ls, w->data->P, Ar, delta, NULL, w->settings->linsys_solver, 1);
+}
+
+/* sol = M^-1 rhs, M = [P, Ar'; Ar, 0] of the instance `ls` (N = n + mred unknowns): its regularised solve, then refinement against
+ * M (polish.c:134-181) -- at least polish_refine_iter steps, at most max(polish_refine_iter, POLISH_MAX_REFINE), ended once converged
+ * or no longer contracting.  res, tmp: scratch of N.  kkt_res (NULL = skip): the last |rhs - M sol|_inf / max(|rhs|_inf, 1) evaluated;
+ * nsolves (NULL = skip): counts the linear solves.  Returns nonzero when a solve or a product failed. */
+static c_int kkt_refined_solve(const OSQPWorkspace *w, LinSysSolver *ls, c_int mred, const c_float *rhs, c_float *sol,
+                               c_float *res, c_float *tmp, c_float *kkt_res, c_int *nsolves) {
+  hipeng *pe = ((hip_pcg_solver *)ls)->eng;      /* the instance's engine holds P and Ared */
+  const c_int n = w->data->n, N = n + mred;
   memcpy(sol, rhs, (size_t)N * sizeof(c_float));
   c_int bad = ls->solve(ls, sol);
+  if (nsolves) (*nsolves)++;
   c_float prev = OSQP_INFTY;
   const c_int max_ref = HMAX(w->settings->polish_refine_iter, POLISH_MAX_REFINE);
   for (c_int it = 0; !bad && it < max_ref; it++) {   /* polish.c:134-181 */
@@ -1104,12 +1165,40 @@ static c_int run_polish(OSQPWorkspace *w) {
     }
     if (bad) break;
     const c_float nres = absmax(res, N), scale = HMAX(absmax(rhs, N), 1.0);
+    if (kkt_res) *kkt_res = nres / scale;
     /* at least the reference's polish_refine_iter steps; then stop once converged or no longer contracting */
     if (it >= w->settings->polish_refine_iter && (nres <= 1e-14 * scale || nres > 0.5 * prev)) break;
     prev = nres;
     bad = ls->solve(ls, res);
+    if (nsolves) (*nsolves)++;
     for (c_int k = 0; k < N; k++) sol[k] += res[k];
   }
+  return bad;
+}
+
+/* ------------------------------------------------------------------------ */
+/* polish (src/polish.c:19-350) through the plugin with polish = 1            */
+/* ------------------------------------------------------------------------ */
+static c_int run_polish(OSQPWorkspace *w) {
+  OSQPPolish *p = w->pol;
+  hip_pcg_solver *s = PCG(w);
+  const c_int n = w->data->n, m = w->data->m;
+  tic(w->timer);
+  guess_active_rows(w, p);
+  const c_int mred = p->n_low + p->n_upp;
+  csc *Ar = form_Ared(w, p);
+  if (!Ar) { w->info->status_polish = -1; return -1; }
+  p->Ared = Ar;
+  LinSysSolver *ls = NULL;
+  if (kkt_instance(w, Ar, &ls)) {
+    w->info->status_polish = -1; free_csc(Ar); p->Ared = NULL; return 1;
+  }
+  const c_int N = n + mred;
+  c_float *rhs = zero_vec(N), *sol = zero_vec(N), *res = zero_vec(N), *tmp = zero_vec(N);
+  for (c_int j = 0; j < n; j++) rhs[j] = -w->data->q[j];
+  for (c_int k = 0; k < p->n_low; k++) rhs[n + k] = w->data->l[p->Alow_to_A[k]];
+  for (c_int k = 0; k < p->n_upp; k++) rhs[n + p->n_low + k] = w->data->u[p->Aupp_to_A[k]];
+  const c_int bad = kkt_refined_solve(w, ls, mred, rhs, sol, res, tmp, NULL, NULL);
   if (bad) { w->info->status_polish = -1; goto cleanup; }
   memcpy(p->x, sol, (size_t)n * sizeof(c_float));
   if (m && hipeng_spmv(s->eng, 0, p->x, p->z)) { w->info->status_polish = -1; goto cleanup; }   /* z = A x on the device */
@@ -1245,6 +1334,192 @@ c_int osqp_amd_get_stats(const OSQPWorkspace *w, osqp_amd_stats *out) {
   out->pcg_forced = hs.pcg_forced; out->graph_launches = hs.graph_launches;
   out->host_syncs = s->host_syncs;
   out->resident = hs.resident;
+  return 0;
+}
+
+/* ------------------------------------------------------------------------ */
+/* derivatives of the solution (include/osqp_amd.h): polish's route with      */
+/* another right-hand side, then O(nnz) work on the device (csrc/kkt_sens.h)  */
+/* ------------------------------------------------------------------------ */
+static void fill_zero(c_float *v, c_int k) { if (v && k > 0) memset(v, 0, (size_t)k * sizeof(c_float)); }
+static c_int all_finite(const c_float *v, c_int k) {
+  for (c_int q = 0; q < k; q++) if (!isfinite(v[q])) return 0;
+  return 1;
+}
+
+/* the workspace's state and instance for a derivative call: 0 ready, -1 a failure (status -1), or an OSQP error code to return */
+static c_int sens_prepare(OSQPWorkspace *w, const char *who) {
+  hip_pcg_solver *s = PCG(w);
+  const c_int n = w->data->n, m = w->data->m;
+  sens_state *ss = s->sens;
+  if (!ss) {
+    const size_t mm = (size_t)(m > 0 ? m : 1);
+    ss = (sens_state *)c_calloc(1, sizeof(sens_state));
+    if (!ss) return -1;
+    s->sens = ss;
+    ss->pol.Alow_to_A = (c_int *)c_malloc(mm * sizeof(c_int)); ss->pol.Aupp_to_A = (c_int *)c_malloc(mm * sizeof(c_int));
+    ss->pol.A_to_Alow = (c_int *)c_malloc(mm * sizeof(c_int)); ss->pol.A_to_Aupp = (c_int *)c_malloc(mm * sizeof(c_int));
+    ss->act = (c_int *)c_calloc(mm, sizeof(c_int));
+    ss->yact = zero_vec(m); ss->rnu = zero_vec(m);
+    ss->rhs = zero_vec(n + m); ss->sol = zero_vec(n + m); ss->res = zero_vec(n + m); ss->tmp = zero_vec(n + m);
+    if (!ss->pol.Alow_to_A || !ss->pol.Aupp_to_A || !ss->pol.A_to_Alow || !ss->pol.A_to_Aupp || !ss->act || !ss->yact ||
+        !ss->rnu || !ss->rhs || !ss->sol || !ss->res || !ss->tmp) { sens_free(ss); s->sens = NULL; return -1; }
+  }
+  if (ss->ls) return 0;
+  /* one instance per solved problem: the active rows of the point the workspace holds (scaled z, y, l, u), Ared, the instance */
+  OSQPPolish *p = &ss->pol;
+  guess_active_rows(w, p);
+  ss->Ared = form_Ared(w, p);
+  if (!ss->Ared) return -1;
+  if (kkt_instance(w, ss->Ared, &ss->ls)) { ss->ls = NULL; sens_drop_instance(ss); return -1; }
+  /* the kernels run on the instance's stream, so their arrays live on the instance's device */
+  const c_int device = ((hip_pcg_solver *)ss->ls)->opt.device;
+  if (ss->dev && ss->dev_device != device) { hipsens_destroy(ss->dev); ss->dev = NULL; }
+  if (!ss->dev) {
+    if (hipsens_create(&ss->dev, n, m, w->data->P->p[n], w->data->A->p[n], (int)device)) {
+      fprintf(stderr, "ERROR in %s: device set-up failed\n", who);
+      hipsens_destroy(ss->dev); ss->dev = NULL;
+      sens_drop_instance(ss);
+      return -1;
+    }
+    ss->dev_device = device;
+  }
+  for (c_int i = 0; i < m; i++) {
+    ss->act[i] = p->A_to_Alow[i] != -1 ? -1 : (p->A_to_Aupp[i] != -1 ? 1 : 0);
+    ss->yact[i] = ss->act[i] ? w->y[i] : 0.0;
+  }
+  const OSQPScaling *sc = w->settings->scaling ? w->scaling : NULL;
+  if (hipsens_set_point(ss->dev, ((hip_pcg_solver *)ss->ls)->eng, w->x, ss->yact, ss->act, sc ? sc->D : NULL, sc ? sc->E : NULL,
+                        sc ? sc->c : 1.0)) { sens_drop_instance(ss); return -1; }
+  ss->built++;
+  return 0;
+}
+
+/* position of row i among the instance's unknowns behind x (lows first, then upps), -1: inactive */
+static c_int sens_slot(const OSQPPolish *p, c_int i) {
+  if (p->A_to_Alow[i] != -1) return p->A_to_Alow[i];
+  if (p->A_to_Aupp[i] != -1) return p->n_low + p->A_to_Aupp[i];
+  return -1;
+}
+
+/* the refined solve of ss->rhs into ss->sol; nonzero: a solve failed, met negative curvature or gave a non-finite value */
+static c_int sens_solve(const OSQPWorkspace *w, sens_state *ss, c_float *kkt_res) {
+  const c_int mred = ss->pol.n_low + ss->pol.n_upp;
+  hipeng_stats hs;
+  c_float r = 0.0;
+  if (kkt_refined_solve(w, ss->ls, mred, ss->rhs, ss->sol, ss->res, ss->tmp, &r, &ss->solves)) return 1;
+  if (hipeng_get_stats(((hip_pcg_solver *)ss->ls)->eng, &hs) || hs.neg_curvature > 0) return 1;
+  if (!all_finite(ss->sol, w->data->n + mred) || !isfinite(r)) return 1;
+  if (kkt_res) *kkt_res = r;
+  return 0;
+}
+
+#define SENS_ENTRY(w, who)                                                                                       \
+  NEED_WORK(w);                                                                                                  \
+  if (!(w)->linsys_solver || !PCG(w)->sens_ready) {                                                              \
+    fprintf(stderr, "ERROR in %s: no osqp_solve since setup or since the last update or warm start\n", who);     \
+    return OSQP_WORKSPACE_NOT_INIT_ERROR;                                                                        \
+  }
+
+c_int osqp_amd_adjoint(OSQPWorkspace *w, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl, c_float *du,
+                       c_float *dPx, c_float *dAx, c_int *active, c_int *status, c_float *kkt_res) {
+  SENS_ENTRY(w, "osqp_amd_adjoint");
+  const c_int n = w->data->n, m = w->data->m;
+  if (!dx || !dq || !status || (m > 0 && (!dl || !du))) {
+    fprintf(stderr, "ERROR in osqp_amd_adjoint: missing argument\n");
+    return OSQP_DATA_VALIDATION_ERROR;
+  }
+  const c_int nnzP = w->data->P->p[n], nnzA = w->data->A->p[n];
+  fill_zero(dq, n); fill_zero(dl, m); fill_zero(du, m); fill_zero(dPx, nnzP); fill_zero(dAx, nnzA);
+  if (active) for (c_int i = 0; i < m; i++) active[i] = 0;
+  if (kkt_res) *kkt_res = 0.0;
+  *status = 0;
+  if (w->info->status_val != OSQP_SOLVED) return 0;
+  *status = -1;
+  if (sens_prepare(w, "osqp_amd_adjoint")) return 0;
+  sens_state *ss = PCG(w)->sens;
+  const OSQPPolish *p = &ss->pol;
+  const OSQPScaling *sc = w->settings->scaling ? w->scaling : NULL;
+  const c_float cs = sc ? sc->c : 1.0, cinv = 1.0 / cs;
+  const c_int mred = p->n_low + p->n_upp;
+  /* rhs = [D gx; E gy / c on the active rows] */
+  for (c_int j = 0; j < n; j++) ss->rhs[j] = (sc ? sc->D[j] : 1.0) * dx[j];
+  for (c_int a = 0; a < mred; a++) {
+    const c_int r = a < p->n_low ? p->Alow_to_A[a] : p->Aupp_to_A[a - p->n_low];
+    ss->rhs[n + a] = dy ? ((sc ? sc->E[r] : 1.0) * dy[r]) * cinv : 0.0;
+  }
+  c_float kr = 0.0;
+  if (sens_solve(w, ss, &kr)) return 0;
+  /* sol = [rx; rnu] of the scaled problem */
+  for (c_int i = 0; i < m; i++) { const c_int a = sens_slot(p, i); ss->rnu[i] = a >= 0 ? ss->sol[n + a] : 0.0; }
+  if ((dPx || dAx) && hipsens_grad(ss->dev, ((hip_pcg_solver *)ss->ls)->eng, w->data->P, w->data->A, ss->sol, ss->rnu, dPx, dAx)) {
+    fill_zero(dPx, nnzP); fill_zero(dAx, nnzA);
+    return 0;
+  }
+  if ((dPx && !all_finite(dPx, nnzP)) || (dAx && !all_finite(dAx, nnzA))) { fill_zero(dPx, nnzP); fill_zero(dAx, nnzA); return 0; }
+  for (c_int j = 0; j < n; j++) dq[j] = 0.0 - (cs * (sc ? sc->D[j] : 1.0)) * ss->sol[j];
+  for (c_int i = 0; i < m; i++) {
+    const c_float v = ss->act[i] ? (sc ? sc->E[i] : 1.0) * ss->rnu[i] : 0.0;
+    dl[i] = ss->act[i] < 0 ? v : 0.0;
+    du[i] = ss->act[i] > 0 ? v : 0.0;
+    if (active) active[i] = ss->act[i];
+  }
+  if (kkt_res) *kkt_res = kr;
+  *status = 1;
+  return 0;
+}
+
+c_int osqp_amd_tangent(OSQPWorkspace *w, c_int ndir, const c_float *dq, const c_float *dl, const c_float *du,
+                       const c_float *dPx, const c_float *dAx, c_float *dx, c_float *dy, c_int *active, c_int *status,
+                       c_float *kkt_res) {
+  SENS_ENTRY(w, "osqp_amd_tangent");
+  const c_int n = w->data->n, m = w->data->m;
+  if (!dx || !status || ndir < 1 || ndir > OSQP_AMD_MAX_NDIR) {
+    fprintf(stderr, "ERROR in osqp_amd_tangent: %s\n", !dx || !status ? "missing argument" : "ndir must be in [1, 65535]");
+    return OSQP_DATA_VALIDATION_ERROR;
+  }
+  fill_zero(dx, ndir * n); fill_zero(dy, ndir * m); fill_zero(kkt_res, ndir);
+  if (active) for (c_int i = 0; i < m; i++) active[i] = 0;
+  *status = 0;
+  if (w->info->status_val != OSQP_SOLVED) return 0;
+  *status = -1;
+  if (sens_prepare(w, "osqp_amd_tangent")) return 0;
+  sens_state *ss = PCG(w)->sens;
+  const OSQPPolish *p = &ss->pol;
+  const OSQPScaling *sc = w->settings->scaling ? w->scaling : NULL;
+  const c_float cinv = 1.0 / (sc ? sc->c : 1.0);
+  const c_int mred = p->n_low + p->n_upp;
+  /* the right-hand sides of all directions in one launch: g [ndir][n + m], the row part on all m rows */
+  c_float *g = (c_float *)c_malloc((size_t)ndir * (size_t)(n + m) * sizeof(c_float));
+  if (!g) return 0;
+  c_int bad = hipsens_tan_rhs(ss->dev, ((hip_pcg_solver *)ss->ls)->eng, w->data->P, w->data->A, ndir, dq, dl, du, dPx, dAx, g) ? 1 : 0;
+  for (c_int d = 0; !bad && d < ndir; d++) {
+    const c_float *gd = g + d * (n + m);
+    memcpy(ss->rhs, gd, (size_t)n * sizeof(c_float));
+    for (c_int a = 0; a < mred; a++) ss->rhs[n + a] = gd[n + (a < p->n_low ? p->Alow_to_A[a] : p->Aupp_to_A[a - p->n_low])];
+    if (!all_finite(ss->rhs, n + mred) || sens_solve(w, ss, kkt_res ? kkt_res + d : NULL)) { bad = 1; break; }
+    /* sol = [dx~; dnu~] of the scaled problem */
+    for (c_int j = 0; j < n; j++) dx[d * n + j] = (sc ? sc->D[j] : 1.0) * ss->sol[j];
+    if (dy) for (c_int i = 0; i < m; i++) {
+      const c_int a = sens_slot(p, i);
+      dy[d * m + i] = a >= 0 ? ((sc ? sc->E[i] : 1.0) * ss->sol[n + a]) * cinv : 0.0;
+    }
+  }
+  c_free(g);
+  if (bad) { fill_zero(dx, ndir * n); fill_zero(dy, ndir * m); fill_zero(kkt_res, ndir); return 0; }
+  if (active) for (c_int i = 0; i < m; i++) active[i] = ss->act[i];
+  *status = 1;
+  return 0;
+}
+
+c_int osqp_amd_sens_info(OSQPWorkspace *w, c_int out[4]) {
+  NEED_WORK(w);
+  if (!w->linsys_solver || !out) return OSQP_DATA_VALIDATION_ERROR;
+  const sens_state *ss = PCG(w)->sens;
+  out[0] = ss ? ss->built : 0;
+  out[1] = ss && ss->ls ? 1 : 0;
+  out[2] = ss && ss->ls ? ss->pol.n_low + ss->pol.n_upp : 0;
+  out[3] = ss ? ss->solves : 0;
   return 0;
 }
 

@@ -20,6 +20,43 @@ class Results(SimpleNamespace):
     pass
 
 
+def check_adjoint(n, m, dx, dy=None):
+    """Shape checks of SolverHandle.adjoint: dx [n], dy [m] or None.  Returns the arrays as the C side takes them."""
+    dx = abi.as_f64(dx)
+    dy = None if dy is None else abi.as_f64(dy)
+    if dx.shape != (n,) or (dy is not None and dy.shape != (m,)):
+        raise ValueError("adjoint arrays must be dx [%d], dy [%d]" % (n, m))
+    return dx, dy
+
+
+def check_tangent(n, m, nnzP, nnzA, dq=None, dl=None, du=None, dPx=None, dAx=None):
+    """Shape checks of SolverHandle.tangent: every given array is [k] (one direction) or [D, k] (D directions), k = n for dq,
+    m for dl and du, nnzP for dPx, nnzA for dAx; all given arrays agree on the form and on D.  Returns (dq, dl, du, dPx,
+    dAx, D, flat) with contiguous float64 arrays: flat is True for the [k] form (D = 1), and when nothing is given."""
+    cols = dict(dq=n, dl=m, du=m, dPx=nnzP, dAx=nnzA)
+    out, forms = {}, {}
+    for name, a in dict(dq=dq, dl=dl, du=du, dPx=dPx, dAx=dAx).items():
+        if a is None:
+            out[name] = None
+            continue
+        a = abi.as_f64(a)
+        if a.ndim not in (1, 2) or a.shape[-1] != cols[name] or (a.ndim == 2 and a.shape[0] < 1):
+            raise ValueError("%s must be [%d] or [D, %d], not %s" % (name, cols[name], cols[name], a.shape))
+        forms[name] = None if a.ndim == 1 else a.shape[0]
+        out[name] = a
+    if len(set(forms.values())) > 1:
+        raise ValueError("tangent arrays must all be [k] or all [D, k] with one D: %s"
+                         % ", ".join("%s %s" % (k, "[k]" if d is None else "D = %d" % d) for k, d in forms.items()))
+    D = next(iter(forms.values()), None)
+    if D is not None and D > 65535:
+        raise ValueError("at most 65535 directions per call, not %d" % D)
+    return tuple(out[k] for k in ("dq", "dl", "du", "dPx", "dAx")) + (1 if D is None else int(D), D is None)
+
+
+def _opt(a, ptr=None):
+    return C.cast(None, ptr or abi.c_float_p) if a is None else abi.fptr(a)
+
+
 class SolverHandle:
     def __init__(self, lib, prefix=""):
         self._lib = lib
@@ -201,6 +238,69 @@ class SolverHandle:
             y = abi.as_f64(y)
             return int(self._api["warm_start_y"](w, abi.fptr(y)))
         return 0
+
+    # ------------------------------------------------------------ derivatives
+    def _sens(self, name):
+        if name not in self._api:
+            raise NotImplementedError("this library has no osqp_amd_%s" % name)
+        return self._api[name]
+
+    @staticmethod
+    def _sens_fail(name, rc):
+        raise RuntimeError("%s failed (%d)%s" % (name, rc, ": no solve has run on the current problem" if rc == 7 else ""))
+
+    def adjoint(self, dx, dy=None, matrices=False):
+        """Adjoint derivatives of the solution (osqp_amd_adjoint): from dx = dl/dx [n] and dy = dl/dy [m] (None = 0) of a
+        scalar l, a namespace with dq [n], dl, du [m], dPx [nnzP] and dAx [nnzA] (CSC order of triu(P) / A; None unless
+        matrices=True; an off-diagonal dPx slot stands for both halves of P), active [m] (-1 active at the lower bound, +1
+        at the upper, 0 inactive), status_adjoint (1 computed, -1 a linear solve failed, 0 not tried: the solve did not end
+        `solved`; the gradients are 0 unless it is 1) and kkt_res (the scaled KKT residual the refined solve ended at,
+        relative to its right-hand side).  The point differentiated is the one the handle holds: the polished one where
+        polish ran and was accepted, the ADMM iterate otherwise.  Changes nothing in the handle.  Needs a solve since
+        setup or the last update or warm start; the KKT instance the first call builds serves every later adjoint() and
+        tangent() until then."""
+        n, m = self.n, self.m
+        dx, dy = check_adjoint(n, m, dx, dy)
+        f = self._sens("adjoint")
+        dq = np.zeros(n); dl = np.zeros(max(m, 1)); du = np.zeros(max(m, 1))
+        dPx = np.zeros(max(self.nnzP, 1)) if matrices else None
+        dAx = np.zeros(max(self.nnzA, 1)) if matrices else None
+        act = np.zeros(max(m, 1), np.int64); st = np.zeros(1, np.int64); kr = np.zeros(1)
+        rc = f(self._work, abi.fptr(dx), _opt(dy if m else None), abi.fptr(dq), abi.fptr(dl), abi.fptr(du), _opt(dPx), _opt(dAx),
+               abi.iptr(act), abi.iptr(st), abi.fptr(kr))
+        if rc:
+            self._sens_fail("osqp_amd_adjoint", rc)
+        return SimpleNamespace(dq=dq, dl=dl[:m], du=du[:m], dPx=None if dPx is None else dPx[:self.nnzP],
+                               dAx=None if dAx is None else dAx[:self.nnzA], active=act[:m], status_adjoint=int(st[0]),
+                               kkt_res=float(kr[0]))
+
+    def tangent(self, dq=None, dl=None, du=None, dPx=None, dAx=None):
+        """Forward sensitivities of the solution (osqp_amd_tangent): from tangents of the data -- dq [n], dl, du [m], dPx
+        [nnzP], dAx [nnzA] (CSC order of triu(P) / A; an off-diagonal dPx slot stands for both halves of P), or each of
+        them [D, k] for D directions that share the KKT instance; None = 0 -- a namespace with dx [n] and dy [m] (or
+        [D, .]), active [m], status_tangent (as adjoint()'s status) and kkt_res [D] (a float for the [k] form).  Only the
+        tangent of the bound a row is active at counts (dl = du on an equality row).  The point, the instance and what the
+        call needs are adjoint()'s.  Changes nothing in the handle."""
+        n, m = self.n, self.m
+        dq, dl, du, dPx, dAx, D, flat = check_tangent(n, m, self.nnzP, self.nnzA, dq, dl, du, dPx, dAx)
+        f = self._sens("tangent")
+        dx = np.zeros((D, n)); dy = np.zeros((D, max(m, 1)))
+        act = np.zeros(max(m, 1), np.int64); st = np.zeros(1, np.int64); kr = np.zeros(D)
+        rc = f(self._work, D, _opt(dq), _opt(dl if m else None), _opt(du if m else None), _opt(dPx), _opt(dAx), abi.fptr(dx),
+               _opt(dy if m else None), abi.iptr(act), abi.iptr(st), abi.fptr(kr))
+        if rc:
+            self._sens_fail("osqp_amd_tangent", rc)
+        dy = dy[:, :m]
+        return SimpleNamespace(dx=dx[0] if flat else dx, dy=dy[0] if flat else dy, active=act[:m], status_tangent=int(st[0]),
+                               kkt_res=float(kr[0]) if flat else kr)
+
+    def sens_info(self):
+        """For the tests: KKT instances built since setup, whether one is alive, its active rows, linear solves since setup."""
+        out = np.zeros(4, np.int64)
+        rc = self._sens("sens_info")(self._work, abi.iptr(out))
+        if rc:
+            self._sens_fail("osqp_amd_sens_info", rc)
+        return dict(built=int(out[0]), alive=int(out[1]), active_rows=int(out[2]), solves=int(out[3]))
 
     # -------------------------------------------------------------- accessors
     @property

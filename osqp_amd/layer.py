@@ -1,4 +1,7 @@
-"""A batch of QPs as a differentiable PyTorch layer: the forward pass is update -> solve -> polish on a live
+"""QPs as differentiable PyTorch layers: BatchQPLayer over the batch engines and, at the end of the file, QPLayer over the
+single-QP engine (OSQP.adjoint / OSQP.tangent).
+
+A batch of QPs as a differentiable PyTorch layer: the forward pass is update -> solve -> polish on a live
 BatchOSQP handle, the backward pass is BatchOSQP.adjoint (osqp_amd_batch_adjoint: one more solve with the KKT
 matrix of the active rows, on the device), and forward-mode tangents come from BatchOSQP.tangent the same way.
 
@@ -243,6 +246,112 @@ class BatchQPLayer(torch.nn.Module):
                 raise ValueError("%s is on %s and Q on %s: every tensor of a call lives on one device" % (name, t.device, Q.device))
         X, Y = _BatchQPFunction.apply(self, Q, L, U, Px, Ax)
         return (X, Y) if return_y else X
+
+    def cleanup(self):
+        if self.h is not None:
+            self.h.cleanup(); self.h = None
+
+
+class _QPFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, layer, q, l, u, Px, Ax):
+        args = tuple(_host(t) for t in (q, l, u, Px, Ax))
+        r = layer._solve(*args)
+        ctx.layer, ctx.args, ctx.serial = layer, args, layer._serial
+        ctx.set_materialize_grads(False)
+        like = dict(dtype=q.dtype, device=q.device)
+        return torch.as_tensor(r.x, **like), torch.as_tensor(r.y, **like)
+
+    @staticmethod
+    def _bring_back(ctx):
+        layer = ctx.layer
+        if layer._serial != ctx.serial:      # the handle has solved another problem since: bring this one back
+            layer._solve(*ctx.args)
+            ctx.serial = layer._serial
+        return layer
+
+    @staticmethod
+    def backward(ctx, gx, gy):
+        need = ctx.needs_input_grad[1:]
+        if not any(need) or (gx is None and gy is None):
+            return (None,) * 6
+        ref = gx if gx is not None else gy
+        layer = _QPFunction._bring_back(ctx)
+        a = layer.h.adjoint(np.zeros(layer.h.n) if gx is None else _host(gx), _host(gy), matrices=need[3] or need[4])
+        layer.last_status_adjoint, layer.last_kkt_res = a.status_adjoint, a.kkt_res
+        outs = (a.dq, a.dl, a.du, a.dPx, a.dAx)
+        return (None,) + tuple(torch.as_tensor(g, dtype=ref.dtype, device=ref.device) if w else None for g, w in zip(outs, need))
+
+    @staticmethod
+    def jvp(ctx, _, tq, tl, tu, tPx, tAx):
+        layer = _QPFunction._bring_back(ctx)
+        r = layer.h.tangent(*(_host(t) for t in (tq, tl, tu, tPx, tAx)))
+        layer.last_status_tangent, layer.last_kkt_res = r.status_tangent, r.kkt_res
+        like = dict(dtype=torch.float64, device=next((t.device for t in (tq, tl, tu, tPx, tAx) if t is not None), "cpu"))
+        return torch.as_tensor(r.dx, **like), torch.as_tensor(r.dy, **like)
+
+
+class QPLayer(torch.nn.Module):
+    """x*(q, l, u, Px, Ax) = argmin 1/2 x'Px + q'x  s.t.  l <= Ax <= u for ONE sparse QP on the single-QP engine (the
+    engine of the large problems: no limit on n), differentiable in every argument.
+
+        layer = QPLayer(P, A, eps_abs=1e-6, eps_rel=1e-6)
+        x = layer(q, l, u)                            # [n]; q [n], l, u [m]
+        x, y = layer(q, l, u, Ax=Ax, return_y=True)   # Px [nnz(triu P)], Ax [nnz(A)] in CSC order; None = P's, A's
+
+    The forward pass is update -> solve on one live `OSQP` handle (set up at the first call and kept; **settings are
+    OSQP.setup's, with polish=1 unless given), so the point differentiated is the polished one where polish is accepted.
+    The backward pass is OSQP.adjoint, forward-mode tangents (`torch.autograd.forward_ad`) are OSQP.tangent; both share
+    the KKT instance of the solved problem.  Gradients come back for exactly the inputs that require them; a gradient
+    with respect to an off-diagonal Px slot counts both halves of the symmetric P.  A solve that did not end `solved`
+    (or a failed KKT solve) gives zero gradients: `last_status_adjoint` / `last_status_tangent` (1 computed, -1 failed,
+    0 not tried), `last_kkt_res` and `last_results` say which.
+
+    Tensors are float64 on the CPU or on a GPU.  Tensors of either device are staged through host numpy arrays on their
+    way to and from the handle (the single-QP engine's C ABI takes host pointers; a device-array route exists for the
+    batch engines only, BatchQPLayer): the outputs and gradients come back on the inputs' device."""
+
+    def __init__(self, P, A, **settings):
+        super().__init__()
+        self.P = sparse.triu(sparse.csc_matrix(P), format="csc"); self.P.sort_indices()
+        self.A = sparse.csc_matrix(A); self.A.sort_indices()
+        self.settings = dict(polish=1, **settings) if "polish" not in settings else dict(settings)
+        self.h = None
+        self._serial = 0
+        self._own = [False, False]       # the handle holds values of P / A given by a caller
+        self.last_results = self.last_status_adjoint = self.last_status_tangent = self.last_kkt_res = None
+
+    def _solve(self, q, l, u, Px, Ax):
+        from . import OSQP
+        if self.h is None:
+            P = self.P if Px is None else sparse.csc_matrix((Px, self.P.indices, self.P.indptr), shape=self.P.shape)
+            A = self.A if Ax is None else sparse.csc_matrix((Ax, self.A.indices, self.A.indptr), shape=self.A.shape)
+            self.h = OSQP().setup(P=P, q=q, A=A, l=l, u=u, **self.settings)
+        else:
+            # values a caller gave last time and not this time go back to the layer's own
+            vP = Px if Px is not None else (self.P.data if self._own[0] else None)
+            vA = Ax if Ax is not None else (self.A.data if self._own[1] else None)
+            rc = self.h.update(q=q, l=l, u=u, Px=vP, Ax=vA)
+            if rc:
+                raise RuntimeError("OSQP.update failed (%d)" % rc)
+        self._own = [Px is not None, Ax is not None]
+        self.last_results = self.h.solve()
+        self._serial += 1
+        return self.last_results
+
+    def forward(self, q, l, u, Px=None, Ax=None, return_y=False):
+        n, m = self.P.shape[0], self.A.shape[0]
+        for name, t, k in (("q", q, n), ("l", l, m), ("u", u, m), ("Px", Px, self.P.nnz), ("Ax", Ax, self.A.nnz)):
+            if t is None:
+                continue
+            if t.dtype != torch.float64:
+                raise TypeError("%s must be a float64 tensor, not %s" % (name, t.dtype))
+            if tuple(t.shape) != (k,):
+                raise ValueError("%s must be [%d], not %s" % (name, k, tuple(t.shape)))
+            if t.device != q.device:
+                raise ValueError("%s is on %s and q on %s: every tensor of a call lives on one device" % (name, t.device, q.device))
+        x, y = _QPFunction.apply(self, q, l, u, Px, Ax)
+        return (x, y) if return_y else x
 
     def cleanup(self):
         if self.h is not None:
