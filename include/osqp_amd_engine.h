@@ -149,6 +149,11 @@ int hipeng_time_kernel(hipeng *e, int which, int reps, double *usec);
 /* Algorithmic bytes of one launch of the kernels above. */
 int hipeng_kernel_bytes(hipeng *e, int which, double *bytes);
 int hipeng_is_split(hipeng *e);   /* k_cg_A as two launches (update-only + apply-only)? */
+/* For the tests: how the PCG kernels see (P, A).  Copies host-side fields only (no kernel, no launch): out[0] dense diagonal
+ * blocks of P, [1] rows inside them, [2] stream blocks of A, [3] long (one-wavefront) rows of A, [4] huge rows of A, [5] huge
+ * rows folded into k_cg_B, [6] split, [7] A has 16-bit column ids, [8] M = [P | A'] has them, [9] the matrix k_cg_B streams
+ * (the remainder Mr when it exists, else M) has them, [10] long rows of that matrix, [11] gridA, [12] gridM; the rest 0. */
+int hipeng_pcg_layout(hipeng *e, long long out[16]);
 /* Slack-like variables (one entry in their column of A, no coupling in P) are eliminated from the linear system exactly
  * (engine.hip, k_elim_refresh; launch-per-step engines).  hipeng_row_eliminated: does row i of A carry such a variable?
  * hipeng_elim_count: how many variables are eliminated. */

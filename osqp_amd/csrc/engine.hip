@@ -4657,6 +4657,22 @@ extern "C" long long hipeng_timeline(hipeng *e, unsigned long long *out, long lo
 
 // 1 if the vector update and the operator apply of k_cg_A run as two launches (A dominated by long rows)
 extern "C" int hipeng_is_split(hipeng *e) { return e && e->split ? 1 : 0; }
+// For the tests: how the PCG kernels see (P, A) -- host-side fields only, nothing is launched.  out[0] dense blocks of P,
+// [1] rows inside them, [2] stream blocks of A, [3] long (one-wavefront) rows of A, [4] huge rows of A, [5] huge rows folded
+// into k_cg_B, [6] split, [7] A / [8] M / [9] the matrix k_cg_B streams (Mr when it exists, else M) has 16-bit column ids,
+// [10] long rows of the matrix k_cg_B streams, [11] gridA, [12] gridM; the rest 0.
+extern "C" int hipeng_pcg_layout(hipeng *e, long long out[16]) {
+  if (!e || !out) return HIPENG_ERR_ARG;
+  for (int k = 0; k < 16; k++) out[k] = 0;
+  const HostMat &B = (!e->dP_blks.empty() || !e->hrows.empty()) ? e->Mr : e->M;
+  out[0] = (long long)e->dP_blks.size();
+  for (const DenseBlk &d : e->dP_blks) out[1] += d.b;
+  out[2] = e->A.nstream; out[3] = e->A.nwave - e->A.nstream; out[4] = (long long)e->A.blk.size() - e->A.nwave;
+  out[5] = (long long)e->hrows.size(); out[6] = e->split ? 1 : 0;
+  out[7] = e->A.d_col16 != nullptr; out[8] = e->M.d_col16 != nullptr; out[9] = B.d_col16 != nullptr;
+  out[10] = B.nwave - B.nstream; out[11] = e->c.gridA; out[12] = e->c.gridM;
+  return 0;
+}
 extern "C" int hipeng_row_eliminated(hipeng *e, c_int i) { return e && !e->ecol.empty() && i >= 0 && i < (c_int)e->ecol.size() && e->ecol[(size_t)i] >= 0 ? 1 : 0; }
 extern "C" c_int hipeng_elim_count(hipeng *e) { return e ? e->c.nelim : 0; }
 

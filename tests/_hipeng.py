@@ -60,11 +60,13 @@ def _lib():
                        ("hipeng_residuals", [vp, C.POINTER(HipengScalars)]),
                        ("hipeng_certificates", [vp, C.c_double, C.c_int, C.POINTER(HipengScalars)]),
                        ("hipeng_download", [vp, fp, fp, fp, fp, fp, C.c_int]), ("hipeng_spmv", [vp, C.c_int, fp, fp]),
-                       ("hipeng_get_stats", [vp, C.POINTER(HipengStats)])):
+                       ("hipeng_get_stats", [vp, C.POINTER(HipengStats)]), ("hipeng_pcg_layout", [vp, C.POINTER(C.c_longlong)]),
+                       ("hipeng_is_split", [vp])):
         f = getattr(L, name)
         f.restype, f.argtypes = C.c_int, args
     L.hipeng_destroy.restype, L.hipeng_destroy.argtypes = None, [vp]
     L.hipeng_elim_count.restype, L.hipeng_elim_count.argtypes = C.c_longlong, [vp]
+    L.hipeng_resident_dump.restype, L.hipeng_resident_dump.argtypes = C.c_longlong, [vp, vp, vp, vp, ll]
     return L
 
 
@@ -97,6 +99,25 @@ class Engine:
         out = (C.c_longlong * 16)()
         assert self.L.hipeng_resident_info(self.h, out) == 0
         return list(out)
+
+    def layout(self):
+        """hipeng_pcg_layout: [0] dense blocks of P, [1] rows inside them, [2] stream blocks, [3] long rows, [4] huge rows of A,
+        [5] huge rows folded into k_cg_B, [6] split, [7] A / [8] M / [9] the matrix k_cg_B streams has 16-bit column ids,
+        [10] long rows of that matrix, [11] gridA, [12] gridM."""
+        out = (C.c_longlong * 16)()
+        assert self.L.hipeng_pcg_layout(self.h, out) == 0
+        return list(out)
+
+    def is_split(self):
+        return int(self.L.hipeng_is_split(self.h))
+
+    def resident_dump(self):
+        """hipeng_resident_dump: K as k_pcg_resident holds it, as a dense array."""
+        nnz = int(self.info()[4])
+        row, col, val = np.zeros(nnz, dtype=np.int32), np.zeros(nnz, dtype=np.int32), np.zeros(nnz)
+        assert self.L.hipeng_resident_dump(self.h, row.ctypes.data, col.ctypes.data, val.ctypes.data, nnz) == nnz
+        assert len(set(zip(row.tolist(), col.tolist()))) == nnz
+        return sparse.coo_matrix((val, (row, col)), shape=(self.n, self.n)).toarray()
 
     def elim(self):
         return int(self.L.hipeng_elim_count(self.h))
