@@ -123,6 +123,36 @@ c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, const c_float
                              c_float *dQ, c_float *dL, c_float *dU,
                              c_float *dPx /*[batch][nnzP], NULL = skip*/, c_float *dAx /*[batch][nnzA], NULL = skip*/,
                              c_int *active /*[batch][m], NULL = skip*/, c_int *status_adjoint /*[batch]*/);
+/* osqp_amd_batch_adjoint for ncot cotangents per member in one call -- ncot rows of the Jacobian, where one call of
+ * osqp_amd_batch_adjoint gives one: dX [batch][ncot][n] and dY [batch][ncot][m] (NULL = 0) in, dQ [batch][ncot][n], dL
+ * and dU [batch][ncot][m] and, where asked for, dPx [batch][ncot][nnzP] and dAx [batch][ncot][nnzA] out.  Cotangent d of
+ * a member gets exactly what osqp_amd_batch_adjoint gives for (dX[.][d], dY[.][d]), to the bit: the same point, the same
+ * scaled-space solve with exactly polish_refine_iter refinement steps, the same formulas, zeros for members whose status
+ * is not 1, and nothing of the handle's solve state written.  The ncot cotangents of a member share one formation and
+ * one inversion of its KKT matrix; a cotangent's bits depend neither on ncot, nor on the other cotangents, nor on the
+ * chunking.  active [batch][m] and status_adjoint [batch] (NULL = skip) are per member, as osqp_amd_batch_adjoint
+ * reports them.
+ * Memory: as osqp_amd_batch_adjoint, with staging of its own that grows when a later call brings a larger ncot and is
+ * freed by cleanup; a handle that never makes this call allocates nothing for it.
+ * Returns as osqp_amd_batch_adjoint, plus OSQP_DATA_VALIDATION_ERROR when ncot < 1 or ncot > 65535. */
+c_int osqp_amd_batch_adjoint_multi(osqp_amd_batch *b, c_int ncot,
+                                   const c_float *dX /*[batch][ncot][n]*/, const c_float *dY /*[batch][ncot][m], NULL = 0*/,
+                                   c_float *dQ /*[batch][ncot][n]*/, c_float *dL, c_float *dU /*[batch][ncot][m]*/,
+                                   c_float *dPx /*[batch][ncot][nnzP], NULL = skip*/, c_float *dAx /*[batch][ncot][nnzA], NULL = skip*/,
+                                   c_int *active /*[batch][m], NULL = skip*/, c_int *status_adjoint /*[batch], NULL = skip*/);
+/* One KKT inversion per solve.  osqp_amd_batch_adjoint, _adjoint_multi, _tangent and their _dev twins all need the
+ * active rows and the inverted KKT matrix of every solved member at the point the handle holds.  When all of them fit
+ * the KKT buffer at once (one chunk under OSQP_AMD_BATCH_POLISH_CAP_BYTES), the first such call after a solve keeps what
+ * it built -- with the pivot verdicts -- and the later ones run only their own kernel, with the same results and
+ * statuses to the bit.  The kept inversion is dropped by osqp_amd_batch_solve, by every update and warm start that
+ * withdraws the permission to call, by an osqp_amd_batch_polish that does work (polish neither reads nor leaves one; a
+ * repeated polish that finds the work done drops nothing), by a regrowth of the KKT buffer and by cleanup.  With more
+ * than one chunk nothing is kept.  OSQP_AMD_BATCH_KKT_CACHE=0 in the environment at setup switches the sharing off.
+ * osqp_amd_batch_kkt_info, for the tests and tools: out[0] builds since setup (one pass of formation and inversion over
+ * the solved members; polish's passes included), out[1] 1 when an inversion is currently kept, out[2] its padded order
+ * NPOL, out[3] the members in it (0, 0 when none is kept).  Touches no GPU memory.  Returns 0,
+ * OSQP_WORKSPACE_NOT_INIT_ERROR for a NULL handle, OSQP_DATA_VALIDATION_ERROR for a NULL out. */
+c_int osqp_amd_batch_kkt_info(osqp_amd_batch *b, c_int out[4]);
 /* Forward sensitivities of the solution, for every member whose last solve ended OSQP_SOLVED: from ndir tangents per
  * member of the data -- dQ [batch][ndir][n], dL and dU [batch][ndir][m], dPx [batch][ndir][nnzP] and dAx
  * [batch][ndir][nnzA] on the pattern of setup (CSC order of triu(P) / A; an off-diagonal slot of triu(P) stands for
@@ -199,6 +229,13 @@ c_int osqp_amd_batch_adjoint_dev(osqp_amd_batch *b, const c_float *dX, const c_f
                                  c_float *dQ, c_float *dL, c_float *dU,
                                  c_float *dPx /*NULL = skip*/, c_float *dAx /*NULL = skip*/,
                                  int *active /*NULL = skip*/, int *status_adjoint /*NULL = skip*/);
+/* osqp_amd_batch_adjoint_multi with every array on the device: the cotangents are read in place, the outputs arrive by
+ * device-to-device copies.  active [batch][m] and status_adjoint [batch] are 32-bit ints there.  Every non-NULL pointer
+ * is classified before any copy or launch, after the checks of ncot and of the NULL arguments. */
+c_int osqp_amd_batch_adjoint_multi_dev(osqp_amd_batch *b, c_int ncot, const c_float *dX, const c_float *dY /*NULL = 0*/,
+                                       c_float *dQ, c_float *dL, c_float *dU,
+                                       c_float *dPx /*NULL = skip*/, c_float *dAx /*NULL = skip*/,
+                                       int *active /*NULL = skip*/, int *status_adjoint /*NULL = skip*/);
 /* osqp_amd_batch_tangent with every array on the device: the tangents are read in place, the outputs arrive by
  * device-to-device copies.  active [batch][m] and status_tangent [batch] are 32-bit ints there, as the kernel writes
  * them. */

@@ -2,6 +2,7 @@
 BASELINE config 4) -- ctypes plumbing over include/osqp_amd_batch.h.  One
 workgroup per QP on the GPU; see osqp_amd/csrc/batch.hip."""
 import ctypes as C
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -13,6 +14,7 @@ from ._lib import lib
 BATCH_MAX_N = 128     # register-tiled K^-1 of the batch kernel (batch.hip)
 STREAMED_MAX_N = 1024  # streamed-inverse engine (batch_streamed.h)
 ENGINES = {"tiled": 0, "streamed": 1}   # OSQP_AMD_BATCH_TILED / _STREAMED
+KktInfo = namedtuple("KktInfo", "builds kept npol members")     # BatchOSQP.kkt_info()
 INFO_FIELDS = ["iter", "status_val", "obj_val", "pri_res", "dua_res", "rho_updates", "rho_estimate", "rho"]
 
 
@@ -37,6 +39,10 @@ def _bind(L):
     L.osqp_amd_batch_polish.argtypes = [H, abi.c_int_p]
     L.osqp_amd_batch_adjoint.restype = abi.c_int
     L.osqp_amd_batch_adjoint.argtypes = [H] + [abi.c_float_p] * 7 + [abi.c_int_p] * 2
+    L.osqp_amd_batch_adjoint_multi.restype = abi.c_int
+    L.osqp_amd_batch_adjoint_multi.argtypes = [H, abi.c_int] + [abi.c_float_p] * 7 + [abi.c_int_p] * 2
+    L.osqp_amd_batch_kkt_info.restype = abi.c_int
+    L.osqp_amd_batch_kkt_info.argtypes = [H, abi.c_int_p]
     L.osqp_amd_batch_tangent.restype = abi.c_int
     L.osqp_amd_batch_tangent.argtypes = [H, abi.c_int] + [abi.c_float_p] * 7 + [abi.c_int_p] * 2
     L.osqp_amd_batch_get.restype = abi.c_int
@@ -56,6 +62,7 @@ def _bind(L):
     # device arrays in and out: device addresses travel as integers (c_void_p), host index lists as before
     V = C.c_void_p
     for name, args in (("update_dev", [V] * 3), ("warm_start_dev", [V] * 2), ("adjoint_dev", [V] * 9),
+                       ("adjoint_multi_dev", [abi.c_int] + [V] * 9),
                        ("tangent_dev", [abi.c_int] + [V] * 9),
                        ("update_matrices_dev", [V, abi.c_int_p, abi.c_int, abi.c_int] * 2),
                        ("get_dev", [V] * 5), ("polish_status_dev", [V]), ("check_dev_ptr", [V])):
@@ -155,6 +162,36 @@ def check_adjoint(B, n, m, dX, dY=None):
     if dX.shape != (B, n) or (dY is not None and dY.shape != (B, m)):
         raise ValueError("adjoint arrays must be dX [B, n], dY [B, m]")
     return dX, dY
+
+
+def check_adjoint_multi(B, n, m, dX, dY=None, **outputs):
+    """Shape checks of the [B, D, .] form of BatchOSQP.adjoint / adjoint_into: dX [B, D, n], dY [B, D, m] or None, D >= 1
+    cotangents per member that share one KKT inversion; both agree on D, and D <= 65535.  outputs: dq / dl / du / dPx /
+    dAx of adjoint_into as (array, k) pairs, checked the same way with their own k.  Host arrays come back as contiguous
+    float64, device arrays as they are (device_view checks type and strides).  Returns (dX, dY, D)."""
+    given = dict(dX=(dX, n), dY=(dY, m), **outputs)
+    out, Ds = {}, {}
+    for name, (a, k) in given.items():
+        if a is None:
+            out[name] = None
+            continue
+        if is_device(a):
+            shape = tuple(a.__cuda_array_interface__["shape"])
+        else:
+            a = abi.as_f64(a)
+            shape = a.shape
+        if len(shape) != 3 or shape[0] != B or shape[2] != k or shape[1] < 1:
+            raise ValueError("%s must be [B, D, %d] with B = %d and D >= 1, not %s" % (name, k, B, shape))
+        Ds[name] = shape[1]
+        out[name] = a
+    if out["dX"] is None:
+        raise ValueError("adjoint arrays must be dX [B, D, n], dY [B, D, m]")
+    if len(set(Ds.values())) > 1:
+        raise ValueError("adjoint arrays must agree on D: %s" % ", ".join("%s D = %d" % kv for kv in Ds.items()))
+    D = int(Ds["dX"])
+    if D > 65535:
+        raise ValueError("at most 65535 cotangents per call, not %d" % D)
+    return out["dX"], out["dY"], D
 
 
 def check_tangent(B, n, m, nnzP, nnzA, dQ=None, dL=None, dU=None, dPx=None, dAx=None, **outputs):
@@ -463,11 +500,16 @@ class BatchOSQP:
         status_adjoint [B]: 1 computed, -1 a KKT pivot of the wrong sign, 0 not tried (the member did not end
         `solved`); the gradients of members that are not 1 are 0.  The point differentiated is the one the handle
         holds: the polished one where polish() was accepted, the ADMM iterate otherwise.  Changes nothing in the
-        handle.  Needs a solve since setup or the last update."""
+        handle.  Needs a solve since setup or the last update.
+        dX [B, D, n] with dY [B, D, m] (or None): D cotangents per member in one call, on one KKT inversion; the five
+        gradients come back [B, D, .], active and status_adjoint per member (_adjoint_multi).
+        On one solve, adjoint() and tangent() share the KKT inversion the first of them builds (kkt_info)."""
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): adjoint is a call of the batch "
                                "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
         B, n, m = self.B, self.n, self.m
+        if np.ndim(dX) == 3:
+            return self._adjoint_multi(dX, dY, matrices)
         dX, dY = check_adjoint(B, n, m, dX, dY)
         dq = np.zeros((B, n)); dl = np.zeros((B, max(m, 1))); du = np.zeros((B, max(m, 1)))
         dPx = np.zeros((B, max(self.Pu.nnz, 1))) if matrices else None
@@ -480,6 +522,37 @@ class BatchOSQP:
                                                                          if rc == 7 else ""))
         return SimpleNamespace(dq=dq, dl=dl[:, :m], du=du[:, :m], dPx=None if dPx is None else dPx[:, :self.Pu.nnz],
                                dAx=None if dAx is None else dAx[:, :self.Ah.nnz], active=act[:, :m], status_adjoint=sa)
+
+    def _adjoint_multi(self, dX, dY, matrices):
+        """adjoint() for dX [B, D, n], dY [B, D, m] (None = 0): D cotangents per member -- D rows of the Jacobian -- that
+        share one KKT inversion.  dq [B, D, n], dl, du [B, D, m], dPx [B, D, nnzP], dAx [B, D, nnzA]; active [B, m] and
+        status_adjoint [B] are per member.  Slice d carries the bits adjoint(dX[:, d], dY[:, d]) returns."""
+        B, n, m, nP, nA = self.B, self.n, self.m, self.Pu.nnz, self.Ah.nnz
+        dX, dY, D = check_adjoint_multi(B, n, m, dX, dY)
+        dq = np.zeros((B, D, n)); dl = np.zeros((B, D, max(m, 1))); du = np.zeros((B, D, max(m, 1)))
+        dPx = np.zeros((B, D, max(nP, 1))) if matrices else None
+        dAx = np.zeros((B, D, max(nA, 1))) if matrices else None
+        act = np.zeros((B, max(m, 1)), np.int64); sa = np.zeros(B, np.int64)
+        rc = self._lib.osqp_amd_batch_adjoint_multi(self._h, D, abi.fptr(dX), _p(dY if m else None), abi.fptr(dq),
+                                                    abi.fptr(dl), abi.fptr(du), _p(dPx), _p(dAx), abi.iptr(act), abi.iptr(sa))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_adjoint_multi failed (%d)%s"
+                               % (rc, ": no solve has run on the current problem" if rc == 7 else ""))
+        return SimpleNamespace(dq=dq, dl=dl[:, :, :m], du=du[:, :, :m], dPx=None if dPx is None else dPx[:, :, :nP],
+                               dAx=None if dAx is None else dAx[:, :, :nA], active=act[:, :m], status_adjoint=sa)
+
+    def kkt_info(self):
+        """For the tests and tools: (builds, kept, npol, members) -- passes of KKT formation and inversion over the solved
+        members since setup (polish's included), whether an inversion is kept for the next adjoint() / tangent() on this
+        solve, its padded order and the members in it.  Touches no GPU memory."""
+        if self._many is not None:
+            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): there is no batch KKT buffer"
+                               % BATCH_MAX_N)
+        out = np.zeros(4, np.int64)
+        rc = self._lib.osqp_amd_batch_kkt_info(self._h, abi.iptr(out))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_kkt_info failed (%d)" % rc)
+        return KktInfo(*(int(v) for v in out))
 
     def tangent(self, dQ=None, dL=None, dU=None, dPx=None, dAx=None):
         """Forward sensitivities of the solution on the device, for every member whose last solve ended `solved`: from
@@ -551,13 +624,16 @@ class BatchOSQP:
     def adjoint_into(self, dX, dY, dq, dl, du, dPx=None, dAx=None, active=None, status_adjoint=None):
         """adjoint() between device arrays of the caller's: from dX [B, n] and dY [B, m] (None = 0) into dq [B, n], dl, du
         [B, m] and, where given, dPx [B, nnzP], dAx [B, nnzA] (float64), active [B, m], status_adjoint [B] (int32).
-        For m = 0 the m-sized arguments may be None.  Ready on return."""
+        For m = 0 the m-sized arguments may be None.  Ready on return.  With dX [B, D, n] every float array is [B, D, .]
+        (D cotangents per member, as adjoint() takes them); active and status_adjoint stay per member."""
         if self._route(dX=dX, dY=dY, dq=dq, dl=dl, du=du, dPx=dPx, dAx=dAx, active=active,
                        status_adjoint=status_adjoint) != "device":
             raise ValueError("adjoint_into reads and writes device arrays (objects with __cuda_array_interface__); adjoint() "
                              "takes and returns host arrays")
         if dX is None or dq is None or (self.m and (dl is None or du is None)):
             raise ValueError("adjoint_into needs dX, dq and, for m > 0, dl and du")
+        if len(dX.__cuda_array_interface__["shape"]) == 3:
+            return self._adjoint_multi_into(dX, dY, dq, dl, du, dPx, dAx, active, status_adjoint)
         d = lambda a, cols, name: self._dev(a, cols, name, writable=True)
         rc = self._lib.osqp_amd_batch_adjoint_dev(
             self._h, self._dev(dX, self.n, "dX"), self._dev(dY, self.m, "dY"), d(dq, self.n, "dq"), d(dl, self.m, "dl"),
@@ -566,6 +642,24 @@ class BatchOSQP:
             None if status_adjoint is None else device_view(status_adjoint, (self.B,), "<i4", True, "status_adjoint"))
         if rc:
             raise RuntimeError("osqp_amd_batch_adjoint_dev failed (%d)%s"
+                               % (rc, ": no solve has run on the current problem" if rc == 7 else
+                                  _BAD_POINTER if rc == 1 else ""))
+
+    def _adjoint_multi_into(self, dX, dY, dq, dl, du, dPx, dAx, active, status_adjoint):
+        """adjoint_into for dX [B, D, n]: every float array is [B, D, .]; active [B, m] and status_adjoint [B] stay per member."""
+        B, n, m, nP, nA = self.B, self.n, self.m, self.Pu.nnz, self.Ah.nnz
+        dX, dY, D = check_adjoint_multi(B, n, m, dX, dY, dq=(dq, n), dl=(dl, m), du=(du, m), dPx=(dPx, nP), dAx=(dAx, nA))
+
+        def d(a, cols, name, writable=True):
+            if a is None:
+                return None
+            return device_view(a, (B, D, cols), "<f8", writable, name) or None
+        rc = self._lib.osqp_amd_batch_adjoint_multi_dev(
+            self._h, D, d(dX, n, "dX", False), d(dY, m, "dY", False), d(dq, n, "dq"), d(dl, m, "dl"), d(du, m, "du"),
+            d(dPx, nP, "dPx"), d(dAx, nA, "dAx"), self._dev(active, m, "active", "<i4", True),
+            None if status_adjoint is None else device_view(status_adjoint, (B,), "<i4", True, "status_adjoint"))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_adjoint_multi_dev failed (%d)%s"
                                % (rc, ": no solve has run on the current problem" if rc == 7 else
                                   _BAD_POINTER if rc == 1 else ""))
 

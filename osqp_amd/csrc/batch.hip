@@ -729,6 +729,21 @@ struct osqp_amd_batch {
   size_t tan_in_cap = 0, tan_mat_cap = 0, tan_out_cap = 0;   // in doubles
   int *tan_act = nullptr, *tan_stat = nullptr, *tan_piv = nullptr;   // [B][m], [B], [B] (the inversion's verdict)
   int *d_bad = nullptr;     // device-array updates (batch_devio.h): count of l > u pairs of k_batch_check_bounds
+  // adjoint_multi (batch_adjoint.h): staging that grows with ncot (freed by cleanup), the rest allocated at the first call
+  double *adjm_in = nullptr;   // [B][ncot][n] dl/dx, then [B][ncot][m] dl/dy (host route)
+  double *adjm_out = nullptr;  // [B][ncot][n] dQ, then [B][ncot][m] dL and dU
+  double *adjm_mat = nullptr;  // [B][ncot][nnzP] dPx, then [B][ncot][nnzA] dAx
+  size_t adjm_in_cap = 0, adjm_out_cap = 0, adjm_mat_cap = 0;   // in doubles
+  int *adjm_act = nullptr, *adjm_stat = nullptr, *adjm_piv = nullptr;   // [B][m], [B], [B] (the inversion's verdict)
+  // the kept KKT inversion (bd_run): what a one-chunk adjoint / adjoint_multi / tangent call built -- pol.map, rows,
+  // mred, nlow, d_plist, the inverses in pol.K and the pivot verdicts -- stays for the later calls on the same solve
+  int kkt_cache = 1;        // OSQP_AMD_BATCH_KKT_CACHE (0: every call builds its own)
+  bool kkt_valid = false;   // dropped by a polish that does work and by a regrowth of pol.K
+  int kkt_epoch = 0;        // b->solves when it was built: a later solve outdates it (kkt_kept)
+  int kkt_NPOL = 0;
+  size_t kkt_count = 0;     // the members in it
+  int *kkt_piv = nullptr;   // [B] 0, or -1 where k_bp_invert met a pivot of the wrong sign
+  long long kkt_builds = 0; // passes of k_bp_form + k_bp_invert over the solved members since setup, polish's included
 };
 
 static void batch_launch(osqp_amd_batch *b, int phase);
@@ -811,6 +826,10 @@ static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
   // read here, once per handle
   e = getenv("OSQP_AMD_BATCH_POLISH_CAP_BYTES");
   b->pol_cap = e ? (size_t)strtoull(e, nullptr, 10) : (size_t)8 << 30;
+  // 0: adjoint, adjoint_multi and tangent build the KKT inversion anew in every call (the two routes give the same
+  // bits; the switch exists to compare them)
+  e = getenv("OSQP_AMD_BATCH_KKT_CACHE");
+  b->kkt_cache = e ? atoi(e) : 1;
 }
 
 static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, const std::vector<int> &Pi,
@@ -1133,7 +1152,8 @@ extern "C" void osqp_amd_batch_cleanup(osqp_amd_batch *b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   for (void *p : b->allocs) (void)hipFree(p);
   if (b->pol.K) (void)hipFree(b->pol.K);
-  for (double *p : {b->tan_in, b->tan_mat, b->tan_out}) if (p) (void)hipFree(p);
+  for (double *p : {b->tan_in, b->tan_mat, b->tan_out, b->adjm_in, b->adjm_mat, b->adjm_out}) if (p) (void)hipFree(p);
+  b->kkt_valid = false;
   if (b->stream) (void)hipStreamDestroy(b->stream);
   delete b;
 }
@@ -1301,6 +1321,7 @@ static int bp_reserve_K(osqp_amd_batch *b, size_t bytes) {
   if (bytes <= b->pol_bytes) return 0;
   if (pl.K) (void)hipFree(pl.K);
   pl.K = nullptr; b->pol_bytes = 0;
+  b->kkt_valid = false;                          // a kept inversion went with the buffer
   void *k = nullptr;
   if (hipMalloc(&k, bytes) != hipSuccess) { (void)hipGetLastError(); return -102; }
   pl.K = static_cast<double *>(k); b->pol_bytes = bytes;
@@ -1350,6 +1371,7 @@ template <class Third>
 static int bp_run_chunks(osqp_amd_batch *b, const BPol &pl, const BPlan &pn, const void *fn, Third third) {
   set_dynamic_lds(KFN(k_bp_invert), pn.ilds);
   set_dynamic_lds(fn, pn.lds);
+  if (pn.count) b->kkt_builds++;
   for (size_t c0 = 0; c0 < pn.count; c0 += pn.chunk) {
     const unsigned cnt = (unsigned)std::min(pn.chunk, pn.count - c0);
     const int *lp = b->d_plist + c0;
@@ -1358,6 +1380,47 @@ static int bp_run_chunks(osqp_amd_batch *b, const BPol &pl, const BPlan &pn, con
     third(cnt, lp);
     BCHK(hipGetLastError());
   }
+  return 0;
+}
+
+// Whether the inversion a derivative call left in pol.K still belongs to the handle's point.  Every call that reads
+// it has passed `b->solved`, which only osqp_amd_batch_solve sets, together with b->solves; every update and warm
+// start that withdraws the permission to call clears it until the next solve.  So the epoch outdates what a solve,
+// or an update followed by a solve, has overtaken.
+static bool kkt_kept(const osqp_amd_batch *b) { return b->kkt_valid && b->solved && b->kkt_epoch == b->solves; }
+
+// What adjoint, adjoint_multi and tangent share around their own kernel fn, which third(plan, members, their list)
+// launches with pn.lds bytes of LDS; pl.stat is the call's array of pivot verdicts.  While an inversion is kept,
+// only the verdicts are copied and fn launched.  Otherwise bp_plan and bp_run_chunks as polish runs them; when the
+// plan is one chunk (and OSQP_AMD_BATCH_KKT_CACHE is not 0) the verdicts are saved after k_bp_invert and what was
+// built is kept.  Either way fn sees the same maps, list, inverses and verdicts: the same bits.  Nothing is waited for.
+template <class Third>
+static c_int bd_run(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_of)(int, int, int), const void *fn, Third third) {
+  const size_t B = (size_t)b->B;
+  BPlan pn;
+  if (kkt_kept(b)) {
+    pn.count = pn.chunk = b->kkt_count; pn.NPOL = b->kkt_NPOL; pn.lds = lds_of(b->n, b->m, pn.NPOL);
+    if (pn.lds > 160 * 1024) {
+      fprintf(stderr, "osqp_amd batch: %s needs %zu B of LDS (> 160 KiB) for some member\n", what, pn.lds);
+      return OSQP_LINSYS_SOLVER_INIT_ERROR;
+    }
+    pl.K = b->pol.K;
+    BCHK(hipMemcpyAsync(pl.stat, b->kkt_piv, B * sizeof(int), hipMemcpyDeviceToDevice, b->stream));
+    set_dynamic_lds(fn, pn.lds);
+    third(pn, (unsigned)pn.count, (const int *)b->d_plist);
+    BCHK(hipGetLastError());
+    return 0;
+  }
+  b->kkt_valid = false;                          // k_bp_active rewrites the maps
+  const c_int rc = bp_plan(b, pl, what, lds_of, &pn);
+  if (rc) return rc;
+  const bool keep = b->kkt_cache && pn.count && pn.count <= pn.chunk;
+  if (keep && balloc_once(b, &b->kkt_piv, B)) { (void)hipGetLastError(); return OSQP_MEM_ALLOC_ERROR; }
+  if (bp_run_chunks(b, pl, pn, fn, [&](unsigned cnt, const int *lp) {
+        if (keep) (void)hipMemcpyAsync(b->kkt_piv, pl.stat, B * sizeof(int), hipMemcpyDeviceToDevice, b->stream);
+        third(pn, cnt, lp);
+      })) return -102;
+  if (keep) { b->kkt_valid = true; b->kkt_epoch = b->solves; b->kkt_NPOL = pn.NPOL; b->kkt_count = pn.count; }
   return 0;
 }
 
@@ -1370,6 +1433,7 @@ extern "C" c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish) 
   if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
   if (!b->polished) {       // (a second call without a solve in between finds the work done and reports it again)
     BPlan pn;
+    b->kkt_valid = false;   // polish overwrites pol.K and may move the point: it neither reads nor leaves a kept inversion
     const c_int rc = bp_plan(b, pl, "polish", bp_lds_of, &pn);
     if (rc) return rc;
     if (bp_run_chunks(b, pl, pn, KFN(k_bp_polish), [&](unsigned cnt, const int *lp) {
@@ -1418,12 +1482,9 @@ static c_int adjoint_launch(osqp_amd_batch *b, const c_float *dX, const c_float 
   BCHK(hipMemsetAsync(b->adj_act, 0, std::max((size_t)1, B * m) * sizeof(int), b->stream));
   if (ad.dPx) BCHK(hipMemsetAsync(ad.dPx, 0, std::max((size_t)1, B * b->nnzP) * sizeof(double), b->stream));
   if (ad.dAx) BCHK(hipMemsetAsync(ad.dAx, 0, std::max((size_t)1, B * b->nnzA) * sizeof(double), b->stream));
-  BPlan pn;
-  const c_int rc = bp_plan(b, pl, "adjoint", ba_lds_of, &pn);
-  if (rc) return rc;
-  if (bp_run_chunks(b, pl, pn, KFN(k_ba_adjoint), [&](unsigned cnt, const int *lp) {
+  if (const c_int rc = bd_run(b, pl, "adjoint", ba_lds_of, KFN(k_ba_adjoint), [&](const BPlan &pn, unsigned cnt, const int *lp) {
         hipLaunchKernelGGL(k_ba_adjoint, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
-      })) return -102;
+      })) return rc;
   *out = ad;
   return 0;
 }
@@ -1456,7 +1517,8 @@ extern "C" c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, co
   return 0;
 }
 
-// a staging buffer of the tangent call of at least cnt doubles (it only grows; nothing is queued on it between calls)
+// a staging buffer of the tangent or adjoint_multi call of at least cnt doubles (it only grows; nothing is queued on
+// it between calls)
 static int tan_reserve(double **p, size_t *cap, size_t cnt) {
   if (cnt <= *cap) return 0;
   if (*p) (void)hipFree(*p);
@@ -1464,6 +1526,90 @@ static int tan_reserve(double **p, size_t *cap, size_t cnt) {
   void *q = nullptr;
   if (hipMalloc(&q, cnt * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return -102; }
   *p = static_cast<double *>(q); *cap = cnt;
+  return 0;
+}
+
+// What osqp_amd_batch_adjoint_multi and osqp_amd_batch_adjoint_multi_dev share: the staging, the plan and the
+// launches.  dev: dX and dY are device arrays, which k_ba_adjoint_multi reads in place.  *out: where the outputs sit
+// (dPx / dAx null unless wantP / wantA); nothing is waited for.
+static c_int adjoint_multi_launch(osqp_amd_batch *b, int ncot, const c_float *dX, const c_float *dY, bool dev, bool wantP,
+                                  bool wantA, BAdjM *out) {
+  const size_t B = (size_t)b->B, D = (size_t)ncot;
+  const size_t n = (size_t)b->n, m = (size_t)b->m, nnzP = (size_t)b->nnzP, nnzA = (size_t)b->nnzA;
+  if (!m) dY = nullptr;
+  if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
+  if (balloc_once(b, &b->adjm_act, B * m) || balloc_once(b, &b->adjm_stat, B) || balloc_once(b, &b->adjm_piv, B)) {
+    (void)hipGetLastError();
+    return OSQP_MEM_ALLOC_ERROR;
+  }
+  const size_t nout = std::max((size_t)1, B * D * (n + 2 * m)), nmat = std::max((size_t)1, B * D * (nnzP + nnzA));
+  if (tan_reserve(&b->adjm_out, &b->adjm_out_cap, nout) ||
+      (!dev && tan_reserve(&b->adjm_in, &b->adjm_in_cap, std::max((size_t)1, B * D * (n + m)))) ||
+      ((wantP || wantA) && tan_reserve(&b->adjm_mat, &b->adjm_mat_cap, nmat)))
+    return OSQP_MEM_ALLOC_ERROR;
+  BPol pl = b->pol;          // polish's buffers; its status array stays polish's
+  pl.stat = b->adjm_piv;
+  BAdjM ad{};
+  ad.ncot = ncot;
+  ad.gx = dX; ad.gy = dY;
+  if (!dev) {                // (the input staging is the host route's alone)
+    double *gx = b->adjm_in, *gy = gx + B * D * n;
+    BCHK(hipMemcpyAsync(gx, dX, B * D * n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (dY) BCHK(hipMemcpyAsync(gy, dY, B * D * m * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    ad.gx = gx; ad.gy = dY ? gy : nullptr;
+  }
+  ad.dQ = b->adjm_out; ad.dL = ad.dQ + B * D * n; ad.dU = ad.dL + B * D * m;
+  ad.dPx = wantP ? b->adjm_mat : nullptr; ad.dAx = wantA ? b->adjm_mat + B * D * nnzP : nullptr;
+  ad.active = b->adjm_act; ad.stat = b->adjm_stat;
+  // members that are skipped or rejected report zeros, in every one of the ncot slices
+  BCHK(hipMemsetAsync(b->adjm_out, 0, nout * sizeof(double), b->stream));
+  BCHK(hipMemsetAsync(b->adjm_act, 0, std::max((size_t)1, B * m) * sizeof(int), b->stream));
+  BCHK(hipMemsetAsync(b->adjm_stat, 0, B * sizeof(int), b->stream));
+  if (wantP || wantA) BCHK(hipMemsetAsync(b->adjm_mat, 0, nmat * sizeof(double), b->stream));
+  if (const c_int rc = bd_run(b, pl, "adjoint_multi", ba_lds_of, KFN(k_ba_adjoint_multi), [&](const BPlan &pn, unsigned cnt, const int *lp) {
+        hipLaunchKernelGGL(k_ba_adjoint_multi, dim3(cnt, (unsigned)ncot), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
+      })) return rc;
+  *out = ad;
+  return 0;
+}
+
+// ncot cotangents per member in one call (batch_adjoint.h): osqp_amd_batch_adjoint's route, with one inversion for the
+// ncot cotangents of a member; nothing of the solve state is written
+extern "C" c_int osqp_amd_batch_adjoint_multi(osqp_amd_batch *b, c_int ncot, const c_float *dX, const c_float *dY,
+                                              c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
+                                              c_int *active, c_int *status_adjoint) {
+  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (ncot < 1 || ncot > 65535) return OSQP_DATA_VALIDATION_ERROR;
+  if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
+  BCHK(hipSetDevice(b->device));
+  const size_t B = (size_t)b->B, D = (size_t)ncot;
+  const size_t n = (size_t)b->n, m = (size_t)b->m, nnzP = (size_t)b->nnzP, nnzA = (size_t)b->nnzA;
+  BAdjM ad{};
+  if (const c_int rc = adjoint_multi_launch(b, (int)ncot, dX, dY, false, dPx != nullptr, dAx != nullptr, &ad)) return rc;
+  BCHK(hipMemcpyAsync(dQ, ad.dQ, B * D * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  if (m) {
+    BCHK(hipMemcpyAsync(dL, ad.dL, B * D * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    BCHK(hipMemcpyAsync(dU, ad.dU, B * D * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  }
+  if (dPx && nnzP) BCHK(hipMemcpyAsync(dPx, ad.dPx, B * D * nnzP * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  if (dAx && nnzA) BCHK(hipMemcpyAsync(dAx, ad.dAx, B * D * nnzA * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  std::vector<int> ha(active ? B * m : 0), hs(B);
+  if (active && m) BCHK(hipMemcpyAsync(ha.data(), ad.active, B * m * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  if (status_adjoint) BCHK(hipMemcpyAsync(hs.data(), ad.stat, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  BCHK(hipStreamSynchronize(b->stream));
+  for (size_t k = 0; k < ha.size(); k++) active[k] = ha[k];
+  if (status_adjoint) for (size_t q = 0; q < B; q++) status_adjoint[q] = hs[q];
+  return 0;
+}
+
+// For the tests and tools: builds of the KKT inversion since setup, whether one is kept, its NPOL and its members.
+// Touches no GPU memory.
+extern "C" c_int osqp_amd_batch_kkt_info(osqp_amd_batch *b, c_int out[4]) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!out) return OSQP_DATA_VALIDATION_ERROR;
+  const bool kept = kkt_kept(b);
+  out[0] = (c_int)b->kkt_builds; out[1] = kept ? 1 : 0;
+  out[2] = kept ? b->kkt_NPOL : 0; out[3] = kept ? (c_int)b->kkt_count : 0;
   return 0;
 }
 
@@ -1508,12 +1654,9 @@ static c_int tangent_launch(osqp_amd_batch *b, int ndir, const c_float *dQ, cons
   BCHK(hipMemsetAsync(b->tan_out, 0, nout * sizeof(double), b->stream));
   BCHK(hipMemsetAsync(b->tan_act, 0, std::max((size_t)1, B * m) * sizeof(int), b->stream));
   BCHK(hipMemsetAsync(b->tan_stat, 0, B * sizeof(int), b->stream));
-  BPlan pn;
-  const c_int rc = bp_plan(b, pl, "tangent", bt_lds_of, &pn);
-  if (rc) return rc;
-  if (bp_run_chunks(b, pl, pn, KFN(k_bt_tangent), [&](unsigned cnt, const int *lp) {
+  if (const c_int rc = bd_run(b, pl, "tangent", bt_lds_of, KFN(k_bt_tangent), [&](const BPlan &pn, unsigned cnt, const int *lp) {
         hipLaunchKernelGGL(k_bt_tangent, dim3(cnt, (unsigned)ndir), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, tg, pn.NPOL, b->pol_refine, lp);
-      })) return -102;
+      })) return rc;
   *out = tg;
   return 0;
 }

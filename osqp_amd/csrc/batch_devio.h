@@ -171,6 +171,28 @@ extern "C" c_int osqp_amd_batch_adjoint_dev(osqp_amd_batch *b, const c_float *dX
   return 0;
 }
 
+extern "C" c_int osqp_amd_batch_adjoint_multi_dev(osqp_amd_batch *b, c_int ncot, const c_float *dX, const c_float *dY,
+                                                  c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
+                                                  int *active, int *status_adjoint) {
+  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (ncot < 1 || ncot > 65535) return OSQP_DATA_VALIDATION_ERROR;
+  if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
+  BCHK(hipSetDevice(b->device));
+  if (dev_ptrs_check(b, {dX, dY, dQ, dL, dU, dPx, dAx, active, status_adjoint})) return OSQP_DATA_VALIDATION_ERROR;
+  const size_t B = (size_t)b->B, D = (size_t)ncot, n = (size_t)b->n, m = (size_t)b->m;
+  BAdjM ad{};
+  if (const c_int rc = adjoint_multi_launch(b, (int)ncot, dX, dY, true, dPx != nullptr, dAx != nullptr, &ad)) return rc;
+  BCHK(give(b, dQ, (const double *)ad.dQ, B * D * n));
+  BCHK(give(b, dL, (const double *)ad.dL, B * D * m));
+  BCHK(give(b, dU, (const double *)ad.dU, B * D * m));
+  BCHK(give(b, dPx, (const double *)ad.dPx, B * D * b->nnzP));
+  BCHK(give(b, dAx, (const double *)ad.dAx, B * D * b->nnzA));
+  BCHK(give(b, active, (const int *)ad.active, B * m));
+  BCHK(give(b, status_adjoint, (const int *)ad.stat, B));
+  BCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
 extern "C" c_int osqp_amd_batch_tangent_dev(osqp_amd_batch *b, c_int ndir, const c_float *dQ, const c_float *dL,
                                             const c_float *dU, const c_float *dPx, const c_float *dAx, c_float *dX,
                                             c_float *dY, int *active, int *status_tangent) {
