@@ -169,6 +169,13 @@ c_int hipeng_elim_count(hipeng *e);
  * [13] flags / granules stored again by a workgroup whose own wait went on, [14] give-ups in a row (the third ends the mode
  * for this engine; a run_admm call without one starts the count again), [15] block-direct form: coupling rows of A carried as the low-rank term (0: the plain form, huge rows only).  [1] stays 1 until that third one. */
 int hipeng_resident_info(hipeng *e, long long out[16]);
+/* k_pcg_resident since create: out[0] vector trips of its launches (a pipelined solve of N iterations makes N + 3: the
+ * start-up product, N iterations, one trip that only learns "converged", the true-residual check; N + 2 when the trip
+ * predicted to be the last carried x - x0 and was the last, N + 4 when it was not), [1] launches that ran a solve,
+ * [2] predicted last trips whose products served the check (hits), [3] predicted last trips that were not the last
+ * (misses), [4] predicted trips switched off for the current K (misses outnumbered hits over a window of 16 solves),
+ * [5] the switch OSQP_AMD_RESIDENT_PREDICT as the engine read it, [6] solves and [7] misses minus hits of the current window. */
+int hipeng_resident_trips(hipeng *e, long long out[8]);
 /* For the CPU tests (needs no device): the host side of the resident set-up -- symbolic K, row partition, positions in
  * the exchanged vector, register layout -- for a grid of exactly `nwg` workgroups (nwg > 0) or, nwg < 0, with the grid sized
  * to the problem as the engine does on a machine of -nwg CUs (stats[4] then tells the grid).  stats: [0] qualifies, [1] entries of K per thread,

@@ -125,6 +125,11 @@ struct State {
   int    res_slow_hist[4]; // ... slow waits by length: 50-200 us, 200-500 us, 0.5-2 ms, longer
   unsigned res_slow_xcc;   // ... bit k: a wavefront on XCC k had one
   int    res_slow_last[4]; // ... the latest: exchange number, workgroup, first workgroup it had missed at its 16th round, wait kind (1 flags, 2 granules)
+  // k_pcg_resident, since create (hipeng_resident_trips): vector trips of its launches, launches that ran a solve, predicted last
+  // trips whose products served the true-residual check (hits), predicted last trips that were not the last (misses)
+  long long res_trips, res_solves, res_pred_hit, res_pred_miss;
+  int    res_pred_win[3];  // the current window of RES_PRED_WINDOW solves on this K: solves, hits, misses
+  int    res_pred_off;     // misses outnumbered hits over a window: no predicted trips until K changes (k_form_K clears it)
 };
 
 struct Params {          // mutable scalars (host writes, kernels read)
@@ -1285,6 +1290,7 @@ __global__ void __launch_bounds__(TB) k_admm_finalize(Ctx c) {
 #define AUX_SC1 16
 #define AUX_VOL ((int)0x80000000)     // volatile: a poll load the compiler must neither hoist out of its loop nor merge
 #define RES_DBG 16                    // ints per workgroup in ResCtx::dbg
+#define RES_PRED_WINDOW 16            // solves after which the predicted last trip is judged for this K: more misses than hits switch it off
 #define RES_FSTRIDE 32   // 4-byte words between two workgroups' flags: a 128-byte line each
 #define RES_GSTRIDE 16   // doubles between two workgroups' granule slots: a 128-byte line each (no line is written by two CUs)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -1296,6 +1302,8 @@ struct ResCtx {
   int npw;                           // wavefronts of each workgroup that poll: ceil(nwg / 64), one flag (or one workgroup's granules) per lane
   const unsigned short *rowpos;      // position of row j in that vector
   int pipe;                          // 1: pipelined recurrences where they pass their checks (OSQP_AMD_RESIDENT_PIPE=0: never)
+  int predict;                       // 1: the pipelined phase predicts its last trip and sends x - x0 in it (OSQP_AMD_RESIDENT_PREDICT=0: never)
+  double pred_margin;                // ... when the extrapolated ||r||^2 is <= pred_margin * tol2 (OSQP_AMD_RESIDENT_PREDICT_MARGIN, default 1)
   int u0_direct;                     // 1: the first product reads u0 from global memory instead of exchanging it
   int inject;                        // test hook (OSQP_AMD_RESIDENT_INJECT=k): in the launch of ADMM iteration k one workgroup walks away,
                                      // the others' waits time out -- the give-up path on demand
@@ -1364,7 +1372,10 @@ __device__ __forceinline__ void res_slow_note(State *st, long long t0, int nx, i
 __device__ __forceinline__ int lane_int(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 __global__ void __launch_bounds__(TB) k_form_K(Ctx c, ResCtx rc) {
   const double sigma = c.prm->sigma;
-  if (blockIdx.x == 0 && threadIdx.x == 0) c.st->res_pipe_off = 0;     // a new K: the pipelined recurrences get another chance
+  if (blockIdx.x == 0 && threadIdx.x == 0) {     // a new K: the pipelined recurrences and the predicted last trip get another chance
+    c.st->res_pipe_off = 0;
+    c.st->res_pred_off = 0; c.st->res_pred_win[0] = 0; c.st->res_pred_win[1] = 0; c.st->res_pred_win[2] = 0;
+  }
   const int lane = threadIdx.x & 63, nwaves = gridDim.x * (TB / 64);
   for (int i = blockIdx.x * (TB / 64) + (threadIdx.x >> 6); i < c.n; i += nwaves) {
     const int e0 = rc.krp[i], e1 = rc.krp[i + 1];
@@ -1447,6 +1458,8 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
   const bool sabotage = rc.inject > 0 && g == rc.nwg - 1 && st->admm_done + 1 == rc.inject;
   // pipelined recurrences only where a drift would be caught: not in the convexity probe, not after a failed check
   bool pipe = rc.pipe && !st->res_pipe_off && !prm.no_restart;
+  // the predicted last trip (see the loop): wavefront 0 decides, from sums that are the same in every workgroup
+  bool predict = pipe && rc.predict && !st->res_pred_off;
   // ---- own slice of K into registers (issued first: in flight under everything below) ----
   // (wavefronts 1..7; wavefront 0 holds no entries: its loads are the small ones the start-up and the exchanges wait for)
   const bool prod = wv != 0;
@@ -1481,8 +1494,16 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
   // rows of this workgroup live in the lanes of wavefront 0
   const bool own = wv == 0 && lane < w.nr;
   const int j = w.r0 + lane;
-  double r_ = 0, u_ = 0, w_ = 0, p_ = 0, s_ = 0, x_ = 0, mi = 0, x0_ = 0, r0_ = 0;
-  double z_ = 0, q_ = 0;               // pipelined recurrences: z = K q, q = Minv s
+  // The eleven doubles of the row state are wavefront 0's alone, and wavefront 0 holds no entries of K: they live in the
+  // registers of kv[0..10] (zero in wavefront 0), so that they cost wavefronts 1..7 nothing beside kv[E].  For E < 11 as
+  // many as fit, the rest in registers of their own.  EVERY write to one of these names is wavefront 0's (`own`, or
+  // `!prod`): in wavefronts 1..7 the same registers are entries of K.
+  double rs_rest[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#define RES_ROWSTATE(i) (*((i) < E ? &kv[(i) < E ? (i) : 0] : &rs_rest[i]))
+  double &r_ = RES_ROWSTATE(0), &u_ = RES_ROWSTATE(1), &w_ = RES_ROWSTATE(2), &p_ = RES_ROWSTATE(3), &s_ = RES_ROWSTATE(4), &x_ = RES_ROWSTATE(5);
+  double &mi = RES_ROWSTATE(6), &x0_ = RES_ROWSTATE(7), &r0_ = RES_ROWSTATE(8);
+  double &z_ = RES_ROWSTATE(9), &q_ = RES_ROWSTATE(10);     // pipelined recurrences: z = K q, q = Minv s
+#undef RES_ROWSTATE
   if (own) {
     r_ = c.init_r[(size_t)j * c.init_stride]; u_ = c.init_z[j]; x_ = c.vx[j]; mi = c.minv[j];
     x0_ = x_; r0_ = r_;
@@ -1712,13 +1733,27 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
   // The pipelined recurrences drift on ill-conditioned systems, so: out after 64 iterations, out on any breakdown, and
   // every solve that claims convergence is checked against the true residual.  A failed check hands the solve to
   // mode 3 and switches the pipelined phase off until K changes.
+  // The predicted last trip.  A pipelined solve of N iterations makes a trip N + 1 whose exchange only delivers the
+  // ||r||^2 that says "converged" and whose products nobody uses, and then the check's trip.  When the two latest ||r||^2
+  // extrapolate (rr^2 / rr_prev: linear convergence; CG does a little better here, so this errs on the late side) to
+  // <= pred_margin * tol2, trip N + 1 sends x - x0 instead of m, with the same three partials riding along:
+  //   converged      the products are K (x - x0): straight on to the check's tail -- one trip saved (a hit)
+  //   some other stop (breakdown, cap): the check that mode 2 would now run has its product too
+  //   goes on        the products are thrown away and NOTHING is touched, neither the row state nor gam_old / alp_old;
+  //                  the next trip is an ordinary one with the same partials (a miss: one trip more), and the solve
+  //                  predicts no more
+  // The iterates are the same bit for bit with or without, hit or miss.  When misses outnumber hits over
+  // RES_PRED_WINDOW solves, State::res_pred_off ends it until K changes.
+  double rr_prev = 0.0;                // wavefront 0: ||r||^2 of the trip before
+  bool pred = false;                   // wavefront 0: the coming trip carries x - x0
+  int pred_hit = 0, pred_miss = 0;
   int mode = pipe ? 0 : 3;
   int check_why = 0;                   // 0: the pipelined recurrence says converged, 1: its breakdown / iteration cap, 2: long solve, 3: mode 3 says converged
   int checks3 = 0;                     // failed checks of mode-3 verdicts in this solve
   bool have_u0 = rc.u0_direct;         // the vector k_pcg_init left in global memory is still the u of the recurrences
   while (true) {
     double val = u_, m_ = 0.0;
-    if (mode == 1) { m_ = mi * w_; val = m_; }
+    if (mode == 1) { m_ = mi * w_; val = pred ? x_ - x0_ : m_; }
     else if (mode == 2) val = x_ - x0_;
     if (have_u0) { ++nx; tag = ep0 + (unsigned)nx; par = (int)(tag & 1u); load_u0(); have_u0 = false; }   // (a fresh tag for the granules of exchange (2))
     else if (!vec_exchange(val, mode == 1)) { failed = true; break; }
@@ -1732,16 +1767,30 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
       for (int q = 0; q < 4; ++q) if (lane + 64 * q < nwg) { a0 += uv[ppos[q]]; a1 += uv[ppos[q] + 1]; a2 += uv[ppos[q] + 2]; }
       const double gam = wave_sum(a0), del = wave_sum(a1), rr = wave_sum(a2);
       cs = cg_step(rr, gam, del, gam_old, alp_old, tol2, iters, 0, prm, false);
-      gam_old = gam; alp_old = cs.alpha;
-      if (lane == 0) sc[4] = cs.stop ? (cs.conv ? 1.0 : 2.0) : 0.0;
+      // (+ 4: this was the predicted trip)
+      if (lane == 0) sc[4] = (cs.stop ? (cs.conv ? 1.0 : 2.0) : 0.0) + (pred ? 4.0 : 0.0);
+      if (pred) { pred = false; predict = false; }        // one prediction per solve; the scalars stay as they are
+      else {
+        gam_old = gam; alp_old = cs.alpha;
+        // i >= 2: two ||r||^2 on record
+        pred = predict && !cs.stop && iters >= 1 && rr * rr <= rc.pred_margin * tol2 * rr_prev;
+        rr_prev = rr;
+      }
     }
     WTL(2);
     const double kx = products_finish();       // own row of K times the exchanged vector
     WTL(3);
-    if (mode == 0) { w_ = kx; mode = 1; continue; }
+    if (mode == 0) { if (!prod) w_ = kx; mode = 1; continue; }
     if (mode == 1) {
-      const double verdict = sc[4];
-      if (verdict != 0.0) { check_why = verdict == 1.0 ? 0 : 1; mode = 2; continue; }   // (the products of this trip are wasted)
+      const int verdict = (int)sc[4];
+      if (verdict == 4) { ++pred_miss; continue; }             // predicted, and the solve goes on: this trip did not happen
+      if (verdict != 0) {
+        check_why = (verdict & 3) == 1 ? 0 : 1; mode = 2;
+        if (verdict < 4) continue;                             // (the products of this trip are wasted)
+        ++pred_hit;                                            // kx is a row of K (x - x0): on to the tail of mode 2
+      }
+    }
+    if (mode == 1) {
       ++iters;
       if (own) {
         z_ = cs.first ? kx : (kx + cs.beta * z_);
@@ -1754,7 +1803,7 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
         w_ -= cs.alpha * z_;
       }
       WTL(4);
-      if (iters >= 64) { check_why = 2; mode = 2; }
+      if (iters >= 64) { check_why = 2; mode = 2; pred = false; }
       continue;
     }
     if (mode == 2) {
@@ -1771,7 +1820,7 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
       mode = 3;
       continue;
     }
-    w_ = kx;
+    if (!prod) w_ = kx;
     if (!scal_exchange(own ? r_ * u_ : 0.0, own ? w_ * u_ : 0.0, own ? r_ * r_ : 0.0)) { failed = true; break; }
     const double gam = sc[0], del = sc[1], rr = sc[2];
     cs = cg_step(rr, gam, del, gam_old, alp_old, tol2, iters, 0, prm, false);
@@ -1823,6 +1872,13 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
     if (bad) st->neg_curv = 1;
     st->tol2 = tol2;
     st->res_epoch = ep0 + (unsigned)nx;
+    st->res_trips += nx; st->res_solves += 1; st->res_pred_hit += pred_hit; st->res_pred_miss += pred_miss;
+    if (rc.predict && !st->res_pred_off) {
+      const int ws = st->res_pred_win[0] + 1, wh = st->res_pred_win[1] + pred_hit, wm = st->res_pred_win[2] + pred_miss;
+      const bool full = ws >= RES_PRED_WINDOW;
+      if (full && wm > wh) st->res_pred_off = 1;
+      st->res_pred_win[0] = full ? 0 : ws; st->res_pred_win[1] = full ? 0 : wh; st->res_pred_win[2] = full ? 0 : wm;
+    }
   }
 }
 
@@ -3409,6 +3465,9 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
   rc.npw = (nwg + 63) / 64;
   rc.pipe = 1;
   if (const char *x = getenv("OSQP_AMD_RESIDENT_PIPE")) rc.pipe = atoi(x) != 0;
+  rc.predict = 1; rc.pred_margin = 1.0;
+  if (const char *x = getenv("OSQP_AMD_RESIDENT_PREDICT")) rc.predict = atoi(x) != 0;
+  if (const char *x = getenv("OSQP_AMD_RESIDENT_PREDICT_MARGIN")) { const double v = atof(x); if (v > 0.0) rc.pred_margin = v; }
   rc.u0_direct = 1;
   rc.inject = 0;
   if (const char *x = getenv("OSQP_AMD_RESIDENT_INJECT")) rc.inject = atoi(x);
@@ -4691,6 +4750,20 @@ extern "C" int hipeng_resident_info(hipeng *e, long long out[16]) {
   if (e->res_kind == 2) { out[2] = 64; out[3] = e->bc.nwg; out[4] = 0; out[5] = 0; }
   if (e->res_kind == 3) { out[2] = 0; out[3] = e->c.dP.nblk; out[4] = 0; out[5] = 0; }
   if (e->res_kind == 4) { out[2] = 0; out[3] = e->dd.na; out[4] = (long long)e->dd.nap * e->dd.nap; out[5] = e->dd_chol ? 1 : 0; out[15] = e->dd.nb2; }
+  return 0;
+}
+
+// k_pcg_resident since create: out[0] vector trips of its launches (start-up product, iterations, predicted / wasted trip, check),
+// [1] launches that ran a solve, [2] predicted last trips whose products served the true-residual check, [3] predicted last trips
+// that were not the last, [4] predicted trips switched off for the current K, [5] the switch (OSQP_AMD_RESIDENT_PREDICT), [6] solves /
+// [7] misses minus hits of the current window of RES_PRED_WINDOW solves.
+extern "C" int hipeng_resident_trips(hipeng *e, long long out[8]) {
+  if (!e || !out) return HIPENG_ERR_ARG;
+  HIPCHK(hipSetDevice(e->device));
+  State s;
+  if (read_state(e, &s)) return HIPENG_ERR_HIP;
+  out[0] = s.res_trips; out[1] = s.res_solves; out[2] = s.res_pred_hit; out[3] = s.res_pred_miss;
+  out[4] = s.res_pred_off; out[5] = e->res_kind == 1 ? e->rc.predict : 0; out[6] = s.res_pred_win[0]; out[7] = s.res_pred_win[2] - s.res_pred_win[1];
   return 0;
 }
 
