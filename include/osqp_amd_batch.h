@@ -43,6 +43,49 @@ c_int osqp_amd_batch_setup_engine(osqp_amd_batch **out, c_int engine, c_int batc
                                   const c_float *Px_all, const c_float *Ax_all,
                                   const c_float *Q, const c_float *L, const c_float *U,
                                   const OSQPSettings *settings, c_int device);
+/* The common-K engine: one model, many right-hand sides.  Every member shares P and A (there are no per-member
+ * matrix values: that is the point of this entry), so the batch has ONE K^-1, and the B linear solves of an ADMM
+ * iteration are one product K^-1 R (NP x B) on the matrix cores instead of B streamed GEMVs.  osqp_amd_batch_shape
+ * reports OSQP_AMD_BATCH_COMMON for such a handle; osqp_amd_batch_setup_engine does not take the id (it keeps
+ * returning OSQP_SETTINGS_VALIDATION_ERROR for it).
+ * A member is what osqp_setup + osqp_solve make of its own problem (P, Q[b], A, L[b], U[b]), with three things held
+ * in common:
+ *  1. Scaling.  D, E and c are what the reference's scale_data gives for (P, q^, A) with q^_j = max_b |Q[b][j]|.
+ *     They are computed once at setup and kept across osqp_amd_batch_update, as the reference keeps its scaling
+ *     across osqp_update_lin_cost.  scaling = 0: the identity.  For one member, or identical members, this is the
+ *     reference's own scaling to the bit (Ruiz sees norms only).
+ *  2. Row classes.  Every row has one class (loose, inequality or equality: src/auxil.c:76-98, on the scaled
+ *     bounds) in every member; setup returns OSQP_DATA_VALIDATION_ERROR otherwise and stderr names the first
+ *     (member, row).  osqp_amd_batch_update (and _update_dev) with bounds after which the members would no longer
+ *     agree returns 1, names member and row and writes nothing; bounds that move a row to the same new class in
+ *     every member are accepted, and K is re-formed and re-inverted before the next solve.  L > U: 1, as ever.
+ *  3. rho.  One rho for the batch.  adaptive_rho = 0: it never moves.  adaptive_rho = 1: at the multiples of
+ *     adaptive_rho_interval (0: the deterministic stand-in of the other engines) every member still running forms
+ *     the reference's compute_rho_estimate from its own residuals; the host takes, in member order, that value
+ *     itself when all running members agree and exp(mean(log .)) otherwise, clips it to [1e-6, 1e6] and adopts it
+ *     under the reference's adaptive_rho_tolerance rule.  On adoption the one K is re-formed and re-inverted and
+ *     rho_updates of every running member goes up by one; a finished member keeps the rho, count and estimate it
+ *     finished with.  For one member, or identical members, this is the reference's adaptation exactly.
+ *     osqp_amd_batch_update_rho takes a scalar only: per_member = 1 returns 1 and changes nothing.
+ * Everything else is per member as in the other engines: the iteration, update_info, check_termination with both
+ * infeasibility tests and certificates, scaled_termination, check_termination = 0, max_iter, store_solution, warm
+ * start from the kept scaled iterates.  A finished member is frozen: later iterations change nothing of it.
+ * The explicit-inverse solve is probed in the first iterations after each inversion (refine_tol) as in the streamed
+ * engine, with one verdict for the batch: osqp_amd_batch_rounds reports rounds = 1 + inversions during the solve
+ * and refined = batch or 0.  Solves carry no floating-point atomics and are reproducible to the bit; a member's
+ * bits do not depend on its position in the batch or on the batch's size as long as rho is fixed.
+ * Limits, each OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line naming the limit: 1 <= n <= 1024; a member's vectors
+ * fit 160 KiB of LDS (the streamed engine's limit).  polish / time_limit > 0: OSQP_SETTINGS_VALIDATION_ERROR.
+ * OSQP_NONCVX_ERROR when K is not positive definite.
+ * Served: _update, _warm_start, _update_rho, _solve, _get, _device_ptrs, _shape, _rounds, _cleanup, _update_dev,
+ * _warm_start_dev, _get_dev, _check_dev_ptr, _member (the common D, E, c, rho, classes, Pv, Av and the one K^-1,
+ * NP x NP, for any qp).  Not served: _update_matrices(_dev), _polish, _polish_status_dev, _adjoint*, _tangent*,
+ * _kkt_info: each returns OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line naming the engine and leaves the handle
+ * untouched and usable. */
+#define OSQP_AMD_BATCH_COMMON 2   /* what osqp_amd_batch_shape reports for such a handle; setup_engine does not take it */
+c_int osqp_amd_batch_setup_common(osqp_amd_batch **out, c_int batch, const csc *P, const csc *A,
+                                  const c_float *Q, const c_float *L, const c_float *U,
+                                  const OSQPSettings *settings, c_int device);
 /* The engine of a handle and the padded order NP of its K^-1 (the Kinv buffer of osqp_amd_batch_member is
  * NP x NP).  NULL = skip. */
 c_int osqp_amd_batch_shape(osqp_amd_batch *b, c_int *engine, c_int *NP);

@@ -13,7 +13,7 @@ from ._lib import lib
 
 BATCH_MAX_N = 128     # register-tiled K^-1 of the batch kernel (batch.hip)
 STREAMED_MAX_N = 1024  # streamed-inverse engine (batch_streamed.h)
-ENGINES = {"tiled": 0, "streamed": 1}   # OSQP_AMD_BATCH_TILED / _STREAMED
+ENGINES = {"tiled": 0, "streamed": 1, "common": 2}   # OSQP_AMD_BATCH_TILED / _STREAMED / _COMMON
 KktInfo = namedtuple("KktInfo", "builds kept npol members")     # BatchOSQP.kkt_info()
 INFO_FIELDS = ["iter", "status_val", "obj_val", "pri_res", "dua_res", "rho_updates", "rho_estimate", "rho"]
 
@@ -53,6 +53,10 @@ def _bind(L):
     L.osqp_amd_batch_setup_engine.argtypes = [C.POINTER(H), abi.c_int, abi.c_int, C.POINTER(abi.csc), C.POINTER(abi.csc),
                                               abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p,
                                               abi.c_float_p, C.POINTER(abi.OSQPSettings), abi.c_int]
+    L.osqp_amd_batch_setup_common.restype = abi.c_int
+    L.osqp_amd_batch_setup_common.argtypes = [C.POINTER(H), abi.c_int, C.POINTER(abi.csc), C.POINTER(abi.csc),
+                                              abi.c_float_p, abi.c_float_p, abi.c_float_p,
+                                              C.POINTER(abi.OSQPSettings), abi.c_int]
     L.osqp_amd_batch_shape.restype = abi.c_int
     L.osqp_amd_batch_shape.argtypes = [H, abi.c_int_p, abi.c_int_p]
     L.osqp_amd_batch_rounds.restype = abi.c_int
@@ -244,10 +248,14 @@ class BatchOSQP:
         pattern/values.  Q [B, n], L, U [B, m].  Px_all / Ax_all [B, nnz] optional
         per-QP values in CSC order of triu(P) / A.  engine: "auto" (the register-tiled kernel for
         n <= 128, one single-QP engine per member above) or "streamed" (the streamed-inverse batch
-        engine, K^-1 in HBM, any n <= 1024)."""
+        engine, K^-1 in HBM, any n <= 1024) or "common" (the common-K engine: one model, many right-hand sides --
+        the members share P, A, one scaling, one class per row and one rho, so one K^-1 serves the batch and an ADMM
+        iteration is one GEMM; no Px_all / Ax_all, n <= 1024; see include/osqp_amd_batch.h)."""
         from . import engine_options
-        if engine not in ("auto", "streamed"):
-            raise ValueError("engine must be 'auto' or 'streamed', not %r" % (engine,))
+        if engine not in ("auto", "streamed", "common"):
+            raise ValueError("engine must be 'auto', 'streamed' or 'common', not %r" % (engine,))
+        if engine == "common" and (Px_all is not None or Ax_all is not None):
+            raise ValueError("engine='common' shares P and A over the batch: it takes no Px_all / Ax_all")
         self.engine = engine
         # neither path may hand back an unpolished or unclocked answer to a caller who asked for one: the batch
         # kernel implements neither, so both paths refuse them (OSQP_SETTINGS_VALIDATION_ERROR = 2)
@@ -311,7 +319,15 @@ class BatchOSQP:
             self._last = None
             return self
         h = C.c_void_p()
-        if engine == "streamed":
+        if engine == "common":
+            rc = self._lib.osqp_amd_batch_setup_common(C.byref(h), self.B, C.byref(self.Pu.struct), C.byref(self.Ah.struct),
+                                                       abi.fptr(Q), _p(L if self.m else None), _p(U if self.m else None),
+                                                       C.byref(st), device)
+            if rc:
+                raise ValueError("osqp_amd_batch_setup_common failed with error %d%s"
+                                 % (rc, ": a row has different classes (loose / inequality / equality) in two members"
+                                    if rc == 1 else ""))
+        elif engine == "streamed":
             rc = self._lib.osqp_amd_batch_setup_engine(C.byref(h), ENGINES["streamed"], self.B, C.byref(self.Pu.struct),
                                                        C.byref(self.Ah.struct), _p(Px_all), _p(Ax_all), abi.fptr(Q),
                                                        _p(L if self.m else None), _p(U if self.m else None), C.byref(st),
@@ -327,8 +343,14 @@ class BatchOSQP:
         self._h = h
         return self
 
+    def _unserved(self, call):
+        """The calls the common-K engine does not serve (the C side refuses them too, with the same words)."""
+        if getattr(self, "engine", None) == "common":
+            raise RuntimeError("%s is not served by the common-K engine (engine=\"common\"); set the batch up with "
+                               "engine=\"auto\" or engine=\"streamed\"" % call)
+
     def shape(self):
-        """(engine, NP) of a kernel batch: engine 0 = tiled, 1 = streamed; K^-1 is NP x NP (padded)."""
+        """(engine, NP) of a kernel batch: engine 0 = tiled, 1 = streamed, 2 = common-K; K^-1 is NP x NP (padded)."""
         e = np.zeros(1, np.int64); npo = np.zeros(1, np.int64)
         if self._lib.osqp_amd_batch_shape(self._h, abi.iptr(e), abi.iptr(npo)):
             raise RuntimeError("osqp_amd_batch_shape failed")
@@ -410,6 +432,7 @@ class BatchOSQP:
         list for the batch).  Scaling is recomputed; rho, row classes and iterates stay.  Returns the C return code
         (5: some member's new K is not positive definite; solve then refuses until an update succeeds).  Px / Ax may be
         device arrays; the index lists stay host data."""
+        self._unserved("update_matrices")
         if self._route(Px=Px, Ax=Ax) == "device":
             return self._update_matrices_dev(Px, Px_idx, Ax, Ax_idx)
         Px, Px_idx, pper, Ax, Ax_idx, aper = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
@@ -442,6 +465,8 @@ class BatchOSQP:
         if rho.shape not in ((), (self.B,)):
             raise ValueError("rho must be a scalar or [B]")
         per = int(rho.ndim == 1)
+        if per and getattr(self, "engine", None) == "common":
+            raise ValueError("engine='common' has one rho for the batch: update_rho takes a scalar")
         rho = np.ascontiguousarray(rho.reshape(-1))
         if self._many is not None:
             if np.any(rho <= 0):
@@ -481,6 +506,7 @@ class BatchOSQP:
         that member changed), 0 not tried.  Needs a solve since setup or the last update.  fetch=False: nothing is
         copied to the host and None is returned (results_into reads the outcome on the device; a later results() fetches
         the status then)."""
+        self._unserved("polish")
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): polish is a call of the batch "
                                "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
@@ -504,6 +530,7 @@ class BatchOSQP:
         dX [B, D, n] with dY [B, D, m] (or None): D cotangents per member in one call, on one KKT inversion; the five
         gradients come back [B, D, .], active and status_adjoint per member (_adjoint_multi).
         On one solve, adjoint() and tangent() share the KKT inversion the first of them builds (kkt_info)."""
+        self._unserved("adjoint")
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): adjoint is a call of the batch "
                                "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
@@ -545,6 +572,7 @@ class BatchOSQP:
         """For the tests and tools: (builds, kept, npol, members) -- passes of KKT formation and inversion over the solved
         members since setup (polish's included), whether an inversion is kept for the next adjoint() / tangent() on this
         solve, its padded order and the members in it.  Touches no GPU memory."""
+        self._unserved("kkt_info")
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): there is no batch KKT buffer"
                                % BATCH_MAX_N)
@@ -564,6 +592,7 @@ class BatchOSQP:
         equality row).  The point differentiated is the one the handle holds, as for adjoint().  To first order the
         solution of the moved problem is r.x + t.dx, r.y + t.dy.  Changes nothing in the handle.  Needs a solve since
         setup or the last update."""
+        self._unserved("tangent")
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): tangent is a call of the batch "
                                "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
@@ -614,6 +643,7 @@ class BatchOSQP:
         if rc:
             raise RuntimeError("osqp_amd_batch_get_dev failed (%d)%s" % (rc, _BAD_POINTER if rc == 1 else ""))
         if status_polish is not None:
+            self._unserved("results_into(status_polish=...)")
             rc = self._lib.osqp_amd_batch_polish_status_dev(
                 self._h, device_view(status_polish, (self.B,), "<i4", True, "status_polish"))
             if rc:
@@ -626,6 +656,7 @@ class BatchOSQP:
         [B, m] and, where given, dPx [B, nnzP], dAx [B, nnzA] (float64), active [B, m], status_adjoint [B] (int32).
         For m = 0 the m-sized arguments may be None.  Ready on return.  With dX [B, D, n] every float array is [B, D, .]
         (D cotangents per member, as adjoint() takes them); active and status_adjoint stay per member."""
+        self._unserved("adjoint_into")
         if self._route(dX=dX, dY=dY, dq=dq, dl=dl, du=du, dPx=dPx, dAx=dAx, active=active,
                        status_adjoint=status_adjoint) != "device":
             raise ValueError("adjoint_into reads and writes device arrays (objects with __cuda_array_interface__); adjoint() "
@@ -667,6 +698,7 @@ class BatchOSQP:
         """tangent() between device arrays of the caller's: from dQ, dL, dU, dPx, dAx (None = 0; [B, k], or [B, D, k] for
         D directions) into dx [B, n] and dy [B, m] (or [B, D, .], as the tangents; float64) and, where given, active
         [B, m], status_tangent [B] (int32).  For m = 0 dy may be None.  Ready on return."""
+        self._unserved("tangent_into")
         if self._route(dx=dx, dy=dy, dQ=dQ, dL=dL, dU=dU, dPx=dPx, dAx=dAx, active=active,
                        status_tangent=status_tangent) != "device":
             raise ValueError("tangent_into reads and writes device arrays (objects with __cuda_array_interface__); tangent() "

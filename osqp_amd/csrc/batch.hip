@@ -679,6 +679,7 @@ __global__ void __launch_bounds__(1024) k_batch_order(long long B, const double 
 }
 
 #include "batch_streamed.h"
+#include "batch_common.h"
 #include "batch_polish.h"
 #include "batch_adjoint.h"
 #include "batch_tangent.h"
@@ -689,6 +690,13 @@ struct osqp_amd_batch {
   BSPattern kpat{};         // streamed engine: pattern of K for k_bs_form
   int *d_count = nullptr, *d_list[2] = {nullptr, nullptr};   // streamed engine: rebuild requests of a round
   int last_rounds = 0;
+  // common-K engine (batch_common.h): one K^-1 (io.Wk), one rho and one refinement verdict, kept on the host
+  BCT ct{};
+  double bc_rho = 0.0;      // the batch's rho
+  double *bc_wk2 = nullptr; // the second NP x NP buffer of the inversion (k_bc_pivot); io.Wk and it swap roles
+  bool bc_rebuild = false;  // K^-1 no longer matches rho or the row classes
+  bool bc_refine = false;   // the K^-1 solves take the refinement step (the verdict of the last probe)
+  bool bc_open = false;     // the verdict is to be taken again: K^-1 is new
   int device = 0, tile = 8, threads = 512;
   long long B = 0;
   int n = 0, m = 0, nnzP = 0, nnzA = 0;
@@ -835,14 +843,20 @@ static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
 static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, const std::vector<int> &Pi,
                              const std::vector<int> &Rp, const std::vector<int> &Rc, const std::vector<int> &Rk);
 static int bs_setup_launch(osqp_amd_batch *b, bool update);
+static int bc_alloc(osqp_amd_batch *b);
+static int stage_reserve(osqp_amd_batch *b, size_t vals, size_t idx);
+static int bc_setup_launch(osqp_amd_batch *b, const c_float *Q);
 
 static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const csc *P, const csc *A,
                          const c_float *Px_all, const c_float *Ax_all,
                          const c_float *Q, const c_float *L, const c_float *U,
                          const OSQPSettings *settings, c_int device) {
   if (!out || !P || !A || !Q || !settings || batch <= 0) return OSQP_DATA_VALIDATION_ERROR;
-  if (engine != OSQP_AMD_BATCH_TILED && engine != OSQP_AMD_BATCH_STREAMED) return OSQP_SETTINGS_VALIDATION_ERROR;
-  const bool streamed = engine == OSQP_AMD_BATCH_STREAMED;
+  if (engine != OSQP_AMD_BATCH_TILED && engine != OSQP_AMD_BATCH_STREAMED && engine != OSQP_AMD_BATCH_COMMON)
+    return OSQP_SETTINGS_VALIDATION_ERROR;
+  const bool common = engine == OSQP_AMD_BATCH_COMMON;
+  const bool streamed = engine == OSQP_AMD_BATCH_STREAMED || common;   // K^-1 dense in HBM, formed by k_bs_form
+  const char *ename = common ? "common-K" : "streamed";
   *out = nullptr;
   const int n = (int)P->n, m = (int)A->m;
   if (P->m != P->n || A->n != P->n || n <= 0 || (m > 0 && (!L || !U))) return OSQP_DATA_VALIDATION_ERROR;
@@ -865,17 +879,17 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
     return OSQP_LINSYS_SOLVER_INIT_ERROR;
   }
   if (streamed && n > BS_MAX_N) {
-    fprintf(stderr, "osqp_amd batch: n = %d > %d is not supported by the streamed engine\n", n, BS_MAX_N);
+    fprintf(stderr, "osqp_amd batch: n = %d > %d is not supported by the %s engine\n", n, BS_MAX_N, ename);
     return OSQP_LINSYS_SOLVER_INIT_ERROR;
   }
-  if (streamed && batch > 65535) {   // k_bs_form's grid: y = members
+  if (streamed && !common && batch > 65535) {   // k_bs_form's grid: y = members
     fprintf(stderr, "osqp_amd batch: %lld members > 65535 are not supported by the streamed engine\n", (long long)batch);
     return OSQP_LINSYS_SOLVER_INIT_ERROR;
   }
   const int NPs = (n + 31) & ~31;
   if (streamed && bs_lds_bytes(NPs, m) > 160 * 1024) {
-    fprintf(stderr, "osqp_amd batch: problem needs %zu B of LDS per QP (> 160 KiB) in the streamed engine\n",
-            bs_lds_bytes(NPs, m));
+    fprintf(stderr, "osqp_amd batch: problem needs %zu B of LDS per QP (> 160 KiB) in the %s engine\n",
+            bs_lds_bytes(NPs, m), ename);
     return OSQP_LINSYS_SOLVER_INIT_ERROR;
   }
   if (streamed && m > 0) {   // products of the A'A term of K: sum over rows of c (c + 1) / 2, c entries per row
@@ -884,8 +898,8 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
     size_t ntri = 0;
     for (size_t c : rc_) ntri += c * (c + 1) / 2;
     if (ntri > (size_t)BS_MAX_TRIPLES) {
-      fprintf(stderr, "osqp_amd batch: A'A has %zu row products (> %d) -- A's rows are too dense for the streamed "
-                      "engine\n", ntri, BS_MAX_TRIPLES);
+      fprintf(stderr, "osqp_amd batch: A'A has %zu row products (> %d) -- A's rows are too dense for the %s "
+                      "engine\n", ntri, BS_MAX_TRIPLES, ename);
       return OSQP_LINSYS_SOLVER_INIT_ERROR;
     }
   }
@@ -962,11 +976,13 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
   { int *ord = nullptr; rc |= balloc(b, &ord, B); b->d_order = ord; }
   {
     const size_t NPk = streamed ? (size_t)b->NPs : (size_t)16 * b->tile;
-    rc |= balloc(b, &io.Wv, B * ((size_t)b->nnzP + b->nnzA));
+    const size_t Bk = common ? 1 : B;            // the common-K engine: one slab of scaled values, one K^-1
+    rc |= balloc(b, &io.Wv, Bk * ((size_t)b->nnzP + b->nnzA));
     rc |= balloc(b, &io.Wq, B * n); rc |= balloc(b, &io.Wl, B * m); rc |= balloc(b, &io.Wu, B * m);
     rc |= balloc(b, &io.Wd, B * n); rc |= balloc(b, &io.We, B * m); rc |= balloc(b, &io.Wc, B);
-    rc |= balloc(b, &io.Wk, B * NPk * NPk); rc |= balloc(b, &io.Wt, B * m); rc |= balloc(b, &io.flag, B);
-    if (streamed) { rc |= balloc(b, &b->d_count, 1); rc |= balloc(b, &b->d_list[0], B); rc |= balloc(b, &b->d_list[1], B); }
+    rc |= balloc(b, &io.Wk, Bk * NPk * NPk); rc |= balloc(b, &io.Wt, B * m); rc |= balloc(b, &io.flag, B);
+    if (common) rc |= bc_alloc(b);
+    else if (streamed) { rc |= balloc(b, &b->d_count, 1); rc |= balloc(b, &b->d_list[0], B); rc |= balloc(b, &b->d_list[1], B); }
   }
   if (rc) { osqp_amd_batch_cleanup(b); return OSQP_MEM_ALLOC_ERROR; }
   io.Px = dPx; io.Ax = dAx; io.Q = dQ; io.L = dL; io.U = dU;
@@ -994,7 +1010,10 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
   }
   b->h_info.assign(B * 8, 0.0);
   // setup phase on the device: Ruiz scaling, rho classes, K^-1 (one workgroup per QP)
-  if (streamed) (void)bs_setup_launch(b, false);
+  if (common) {
+    const int crc = bc_setup_launch(b, Q);
+    if (crc) { osqp_amd_batch_cleanup(b); return crc; }
+  } else if (streamed) (void)bs_setup_launch(b, false);
   else batch_launch(b, 0);
   // a non-positive Gauss-Jordan pivot: K = P + sigma I + A' rho A is not positive definite, which
   // the reference's LDL' inertia check rejects at osqp_setup (qdldl_interface.c:93-99)
@@ -1021,6 +1040,7 @@ extern "C" c_int osqp_amd_batch_setup_engine(osqp_amd_batch **out, c_int engine,
                                             const c_float *Q, const c_float *L, const c_float *U,
                                             const OSQPSettings *settings, c_int device) {
   if (out) *out = nullptr;
+  if (engine == OSQP_AMD_BATCH_COMMON) engine = -1;   // that engine has an entry of its own (no per-member values): unknown here
   return batch_setup(out, engine, batch, P, A, Px_all, Ax_all, Q, L, U, settings, device);
 }
 
@@ -1133,6 +1153,187 @@ static int bs_solve(osqp_amd_batch *b) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// common-K engine: host side (kernels: batch_common.h)
+// ---------------------------------------------------------------------------
+static int bc_alloc(osqp_amd_batch *b) {
+  BCT &t = b->ct;
+  const size_t B = (size_t)b->B, Bp = (B + 15) & ~(size_t)15, NP = (size_t)b->NPs, m = (size_t)b->m;
+  t.Bp = (int)Bp;
+  int rc = 0;
+  for (double **v : {&t.q, &t.x, &t.dx, &t.R, &t.Xt, &t.Rr}) rc |= balloc(b, v, NP * Bp);
+  for (double **v : {&t.l, &t.u, &t.z, &t.y, &t.w, &t.dy, &t.T}) rc |= balloc(b, v, m * Bp);
+  rc |= balloc(b, &t.done, B); rc |= balloc(b, &t.verdict, B); rc |= balloc(b, &t.est, B);
+  rc |= balloc(b, &t.count, 1); rc |= balloc(b, &t.bad, B + 1);
+  rc |= balloc(b, &b->bc_wk2, NP * NP);
+  return rc;
+}
+
+// form and invert the one K with the batch's rho; the refinement verdict is taken again on the new K^-1
+static void bc_rebuild(osqp_amd_batch *b) {
+  const int NP = b->NPs;
+  hipLaunchKernelGGL(k_bc_mark, dim3(1), dim3(64), 0, b->stream, b->io, b->bc_rho);
+  hipLaunchKernelGGL(k_bs_form, dim3((unsigned)NP, 1), dim3(256), 0, b->stream, b->pat, b->kpat, b->io, NP, b->st.sigma,
+                     (const int *)nullptr);
+  // Gauss-Jordan, one launch per pivot between the two buffers; K^-1 ends in whichever the last pivot wrote
+  for (int k = 0; k < b->n; k++) {
+    hipLaunchKernelGGL(k_bc_pivot, dim3((unsigned)((NP + 63) / 64), (unsigned)((NP + 15) / 16)), dim3(64, 4), 0, b->stream,
+                       (const double *)b->io.Wk, b->bc_wk2, b->n, NP, k, b->io);
+    std::swap(b->io.Wk, b->bc_wk2);
+  }
+  b->bc_rebuild = false;
+  b->bc_open = true;
+}
+
+// Do the bounds L, U (device, raw, [B][m]; null = keep) leave every row with one class over the batch?  0: yes
+// (*moved: some row's common class changes); 1: no, stderr names the first member and row; nothing is written.
+static int bc_check_classes(osqp_amd_batch *b, const double *L, const double *U, int clamp, bool *moved, const char *what) {
+  const size_t B = (size_t)b->B;
+  std::vector<int> h(B + 1);
+  BCHK(hipMemsetAsync(b->ct.bad, 0, (B + 1) * sizeof(int), b->stream));
+  hipLaunchKernelGGL(k_bc_classes, dim3((unsigned)B), dim3(256), 0, b->stream, b->m, b->B, b->io, L, U, clamp,
+                     (double)RHO_TOL, b->ct.bad);
+  BCHK(hipGetLastError());
+  BCHK(hipMemcpyAsync(h.data(), b->ct.bad, (B + 1) * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  BCHK(hipStreamSynchronize(b->stream));
+  for (size_t q = 0; q < B; q++)
+    if (h[q] >= 0) {
+      fprintf(stderr, "osqp_amd batch: %s: row %d of member %zu has another class (loose / inequality / equality) than in "
+                      "member 0 -- the common-K engine needs one class per row over the batch\n", what, h[q], q);
+      return 1;
+    }
+  if (moved) *moved = h[B] != 0;
+  return 0;
+}
+
+// Setup: k_bs_setup on the one-member image (q^, L[0], U[0]), q^_j = max_b |Q[b][j]| -- D, E, c, the scaled values and
+// the row classes --, the same for every member (k_bc_spread), the class agreement (k_bc_classes), every member's
+// scaled q, l, u (k_batch_update: the reference's osqp_update_lin_cost / _bounds with the kept scaling), the one K^-1.
+static int bc_setup_launch(osqp_amd_batch *b, const c_float *Q) {
+  const size_t B = (size_t)b->B, n = (size_t)b->n;
+  std::vector<double> qhat(n, 0.0);
+  for (size_t q = 0; q < B; q++)
+    for (size_t j = 0; j < n; j++) qhat[j] = std::max(qhat[j], std::fabs((double)Q[q * n + j]));
+  const double *d_qhat = nullptr;
+  if (bupload(b, &d_qhat, qhat)) return OSQP_MEM_ALLOC_ERROR;
+  if (hipStreamSynchronize(b->stream) != hipSuccess) return OSQP_LINSYS_SOLVER_INIT_ERROR;   // qhat leaves scope
+  BIO io1 = b->io;
+  io1.Q = d_qhat;
+  int NP = b->NPs;
+  void *args[] = {&b->pat, &b->st, &io1, &NP};
+  set_dynamic_lds(KFN(k_bs_setup<false>), b->lds_bytes);
+  (void)hipLaunchKernel(KFN(k_bs_setup<false>), dim3(1), dim3(BS_NT), args, b->lds_bytes, b->stream);
+  if (B > 1) hipLaunchKernelGGL(k_bc_spread, dim3((unsigned)(B - 1)), dim3(256), 0, b->stream, b->n, b->m, b->io);
+  const int crc = bc_check_classes(b, b->dL, b->dU, 0, nullptr, "setup");
+  if (crc) return crc == 1 ? OSQP_DATA_VALIDATION_ERROR : OSQP_LINSYS_SOLVER_INIT_ERROR;
+  hipLaunchKernelGGL(k_batch_update, dim3((unsigned)B), dim3(256), 0, b->stream, b->n, b->m, b->io,
+                     (const double *)b->dQ, (const double *)b->dL, (const double *)b->dU, (double)RHO_TOL);
+  b->bc_rho = fmin(fmax(b->st.rho, 1e-6), 1e6);
+  bc_rebuild(b);
+  return 0;
+}
+
+// The batch's rho estimate from the running members' (est > 0; a finished member carries -1), in member order: the
+// value itself when all agree, the geometric mean otherwise; clipped as the reference clips.  0: nobody is running.
+static double bc_batch_estimate(const std::vector<double> &est) {
+  double first = 0.0, sumlog = 0.0;
+  size_t cnt = 0;
+  bool equal = true;
+  for (double e : est) {
+    if (!(e > 0.0)) continue;
+    if (!cnt) first = e; else if (e != first) equal = false;
+    sumlog += std::log(e); cnt++;
+  }
+  if (!cnt) return 0.0;
+  const double v = equal ? first : std::exp(sumlog / (double)cnt);
+  return fmin(fmax(v, 1e-6), 1e6);
+}
+
+// The common-K engine's part of a solve: the ADMM loop of admm_loop, an iteration = a few launches over the batch.
+static int bc_solve(osqp_amd_batch *b) {
+  const BSettings &st = b->st;
+  const BCT &t = b->ct;
+  const long long B = b->B;
+  const int n = b->n, m = b->m, NP = b->NPs, Bp = t.Bp;
+  const dim3 eb(BC_TX, BC_TY);
+  const unsigned gx = (unsigned)((B + BC_TX - 1) / BC_TX);
+  auto ey = [](int cnt) { return (unsigned)((cnt + BC_TY - 1) / BC_TY); };
+  const dim3 gg((unsigned)((Bp + BC_TILE - 1) / BC_TILE), (unsigned)((NP + BC_TILE - 1) / BC_TILE));
+  if (b->bc_rebuild) bc_rebuild(b);              // a class changed in an update, rho was set, or rho moved at max_iter
+  BCHK(hipMemsetAsync(t.count, 0, sizeof(int), b->stream));
+  hipLaunchKernelGGL(k_bc_load, dim3(gx, ey(std::max(std::max(n, m), 1))), eb, 0, b->stream, n, m, B, b->io, t, b->bc_rho,
+                     st.warm_start);
+  std::vector<double> est((size_t)B);
+  std::vector<int> verdict((size_t)B);
+  bool verdict_pending = false;
+  auto take_verdict = [&]() -> int {
+    BCHK(hipMemcpyAsync(verdict.data(), t.verdict, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    BCHK(hipStreamSynchronize(b->stream));
+    for (int v : verdict) if (v) b->bc_refine = true;
+    verdict_pending = false;
+    return 0;
+  };
+  set_dynamic_lds(KFN(k_bc_check), b->lds_bytes);
+  long long running = B;
+  int iter = 0, rounds = 1, probe_until = 0;
+  while (running > 0) {
+    ++iter;
+    const double rho = b->bc_rho;
+    hipLaunchKernelGGL(k_bc_rhs, dim3(gx, ey(n)), eb, 0, b->stream, b->pat, B, b->io, t, st.sigma);
+    hipLaunchKernelGGL(k_bc_gemm, gg, dim3(256), 0, b->stream, (const double *)b->io.Wk, (const double *)t.R, t.Xt,
+                       (const double *)nullptr, NP, Bp);
+    // the refinement rule of admm_loop with one verdict for the batch: probed in the first four iterations after an
+    // inversion (refinement is applied while probing), one hit of any running member turns it on for good
+    const bool probe = !b->bc_refine && (b->bc_open || iter <= probe_until);
+    if (st.refine && (st.refine == 2 || b->bc_refine || probe)) {
+      if (m) hipLaunchKernelGGL(k_bc_rows, dim3(gx, ey(m)), eb, 0, b->stream, b->pat, B, b->io, t, rho);
+      hipLaunchKernelGGL(k_bc_resid, dim3(gx, ey(n)), eb, 0, b->stream, b->pat, B, b->io, t, st.sigma);
+      if (probe) {
+        hipLaunchKernelGGL(k_bc_probe, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, b->stream, n, B, t, st.refine_tol);
+        verdict_pending = true;
+        if (b->bc_open) { b->bc_open = false; probe_until = iter + 3; }
+      }
+      hipLaunchKernelGGL(k_bc_gemm, gg, dim3(256), 0, b->stream, (const double *)b->io.Wk, (const double *)t.Rr, t.Xt,
+                         (const double *)t.Xt, NP, Bp);
+      if (verdict_pending && iter == probe_until) if (const int rc = take_verdict()) return rc;
+    }
+    hipLaunchKernelGGL(k_bc_step, dim3(gx, ey(n + m)), eb, 0, b->stream, b->pat, B, b->io, t, rho, st.alpha);
+    const int checked = st.check_termination && (iter % st.check_termination == 0);
+    const int adapt = st.adaptive_rho && st.rho_interval && (iter % st.rho_interval == 0);
+    const bool last = iter >= st.max_iter;
+    if (checked || adapt) {
+      hipLaunchKernelGGL(k_bc_check, dim3((unsigned)B), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, t, NP,
+                         rho, iter, checked, adapt, 0);
+      BCHK(hipGetLastError());
+      int done = 0;
+      BCHK(hipMemcpyAsync(&done, t.count, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+      if (adapt) BCHK(hipMemcpyAsync(est.data(), t.est, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+      BCHK(hipStreamSynchronize(b->stream));
+      running = B - done;
+      const double rn = (adapt && running > 0) ? bc_batch_estimate(est) : 0.0;
+      if (rn > 0.0 && (rn > rho * st.adapt_tol || rn < rho / st.adapt_tol)) {     // adapt_rho (auxil.c:13-74)
+        b->bc_rho = rn;
+        hipLaunchKernelGGL(k_bc_adopt, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, b->stream, B, b->io, t);
+        b->bc_rebuild = true;
+        if (!last) {                             // (at max_iter no solve with K follows: the rebuild ends the solve)
+          if (verdict_pending) if (const int rc = take_verdict()) return rc;
+          bc_rebuild(b); rounds++;
+          hipLaunchKernelGGL(k_bc_load_w, dim3(gx, ey(std::max(m, 1))), eb, 0, b->stream, m, B, b->io, t, rn);
+        }
+      }
+    }
+    if (last && running > 0) {
+      hipLaunchKernelGGL(k_bc_check, dim3((unsigned)B), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, t, NP,
+                         b->bc_rho, iter, checked, 0, 1);
+      running = 0;
+    }
+  }
+  if (verdict_pending) if (const int rc = take_verdict()) return rc;
+  if (b->bc_rebuild) bc_rebuild(b);              // rho moved in the last iteration: K^-1 follows it
+  b->last_rounds = rounds;
+  return 0;
+}
+
 // the one instantiation of k_batch_solve for (tile, phase)
 static const void *batch_kernel(int tile, int phase) {
   if (phase == 2) return tile == 8 ? KFN((k_batch_solve<8, 4, 32, 2>)) : KFN((k_batch_solve<4, 2, 32, 2>));
@@ -1144,6 +1345,21 @@ static void batch_launch(osqp_amd_batch *b, int phase) {
   set_dynamic_lds(fn, b->lds_bytes);
   void *args[] = {&b->pat, &b->st, &b->io};
   (void)hipLaunchKernel(fn, dim3((unsigned)b->B), dim3(BT), args, b->lds_bytes, b->stream);
+}
+
+// the calls the common-K engine does not serve: the handle is left untouched and usable
+static c_int bc_refuse(const char *call) {
+  fprintf(stderr, "osqp_amd batch: %s is not served by the common-K engine (OSQP_AMD_BATCH_COMMON); use the tiled or "
+                  "the streamed engine\n", call);
+  return OSQP_LINSYS_SOLVER_INIT_ERROR;
+}
+#define BC_UNSERVED(b, call) do { if ((b) && (b)->engine == OSQP_AMD_BATCH_COMMON) return bc_refuse(call); } while (0)
+
+extern "C" c_int osqp_amd_batch_setup_common(osqp_amd_batch **out, c_int batch, const csc *P, const csc *A,
+                                            const c_float *Q, const c_float *L, const c_float *U,
+                                            const OSQPSettings *settings, c_int device) {
+  if (out) *out = nullptr;
+  return batch_setup(out, OSQP_AMD_BATCH_COMMON, batch, P, A, nullptr, nullptr, Q, L, U, settings, device);
 }
 
 extern "C" void osqp_amd_batch_cleanup(osqp_amd_batch *b) {
@@ -1164,6 +1380,15 @@ extern "C" c_int osqp_amd_batch_update(osqp_amd_batch *b, const c_float *Q, cons
   const size_t B = (size_t)b->B;
   if (L && U)
     for (size_t k = 0; k < B * (size_t)b->m; k++) if (L[k] > U[k]) return 1;   // osqp.c:815-822
+  if (b->engine == OSQP_AMD_BATCH_COMMON && (L || U) && b->m) {   // one class per row over the batch, before any write
+    const size_t cnt = B * (size_t)b->m;
+    if (stage_reserve(b, 2 * cnt, 0)) return OSQP_MEM_ALLOC_ERROR;
+    if (L) BCHK(hipMemcpyAsync(b->d_vals, L, cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (U) BCHK(hipMemcpyAsync(b->d_vals + cnt, U, cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    bool moved = false;
+    if (const int rc = bc_check_classes(b, L ? b->d_vals : nullptr, U ? b->d_vals + cnt : nullptr, 0, &moved, "update")) return rc;
+    if (moved) b->bc_rebuild = true;
+  }
   b->solved = false;
   if (Q) BCHK(hipMemcpyAsync(b->dQ, Q, B * b->n * sizeof(double), hipMemcpyHostToDevice, b->stream));
   if (L) BCHK(hipMemcpyAsync(b->dL, L, B * b->m * sizeof(double), hipMemcpyHostToDevice, b->stream));
@@ -1222,6 +1447,7 @@ static int patch_values(osqp_amd_batch *b, double **raw, const double **io_raw, 
 extern "C" c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
                                                 const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
                                                 const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
+  BC_UNSERVED(b, "osqp_amd_batch_update_matrices");
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   // nothing is written before every argument has passed (osqp.c:1197-1222; the index range is this project's check)
   if (Px && Px_idx && P_n > b->nnzP) return 1;
@@ -1259,6 +1485,15 @@ extern "C" c_int osqp_amd_batch_update_rho(osqp_amd_batch *b, const c_float *rho
   if (!rho) return OSQP_DATA_VALIDATION_ERROR;
   const size_t cnt = per_member ? (size_t)b->B : 1;
   for (size_t k = 0; k < cnt; k++) if (!(rho[k] > 0)) return 1;   // osqp.c:1288-1293
+  if (b->engine == OSQP_AMD_BATCH_COMMON) {
+    if (per_member) {
+      fprintf(stderr, "osqp_amd batch: the common-K engine has one rho for the batch: osqp_amd_batch_update_rho takes a "
+                      "scalar (per_member = 0)\n");
+      return 1;
+    }
+    b->bc_rho = fmin(fmax(rho[0], 1e-6), 1e6);
+    b->bc_rebuild = true;
+  }
   BCHK(hipSetDevice(b->device));
   b->solved = false;
   if (balloc_once(b, &b->d_rho, (size_t)b->B)) return OSQP_MEM_ALLOC_ERROR;
@@ -1280,8 +1515,12 @@ extern "C" c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, 
   if (stage_reserve(b, nx + ny, 0)) return OSQP_MEM_ALLOC_ERROR;
   if (nx) BCHK(hipMemcpyAsync(b->d_vals, X, nx * sizeof(double), hipMemcpyHostToDevice, b->stream));
   if (ny) BCHK(hipMemcpyAsync(b->d_vals + nx, Y, ny * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  hipLaunchKernelGGL(k_batch_warm_start, dim3((unsigned)B), dim3(256), 0, b->stream, b->pat, b->io,
-                     X ? b->d_vals : (const double *)nullptr, Y ? b->d_vals + nx : (const double *)nullptr);
+  if (b->engine == OSQP_AMD_BATCH_COMMON)
+    hipLaunchKernelGGL(k_bc_warm_start, dim3((unsigned)B), dim3(256), 0, b->stream, b->pat, b->io,
+                       X ? b->d_vals : (const double *)nullptr, Y ? b->d_vals + nx : (const double *)nullptr);
+  else
+    hipLaunchKernelGGL(k_batch_warm_start, dim3((unsigned)B), dim3(256), 0, b->stream, b->pat, b->io,
+                       X ? b->d_vals : (const double *)nullptr, Y ? b->d_vals + nx : (const double *)nullptr);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   return 0;
@@ -1293,9 +1532,10 @@ extern "C" c_int osqp_amd_batch_solve(osqp_amd_batch *b) {
   BCHK(hipSetDevice(b->device));
   b->solved = b->polished = false;
   b->io.order = (b->lpt && b->solves > 0) ? b->d_order : nullptr;   // first solve: no history, index order
-  if (b->engine != OSQP_AMD_BATCH_STREAMED) batch_launch(b, 1);
+  if (b->engine == OSQP_AMD_BATCH_COMMON) { if (const int rc = bc_solve(b)) return rc; }
+  else if (b->engine != OSQP_AMD_BATCH_STREAMED) batch_launch(b, 1);
   else if (const int rc = bs_solve(b)) return rc;
-  if (b->lpt) hipLaunchKernelGGL(k_batch_order, dim3(1), dim3(1024), 0, b->stream, b->B, b->io.info, b->d_order);
+  if (b->lpt && b->engine != OSQP_AMD_BATCH_COMMON) hipLaunchKernelGGL(k_batch_order, dim3(1), dim3(1024), 0, b->stream, b->B, b->io.info, b->d_order);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   b->solves++;
@@ -1426,6 +1666,7 @@ static c_int bd_run(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_
 
 // polish for the solved members, in chunks of at most pol_cap bytes of KKT matrices (batch_polish.h)
 extern "C" c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish) {
+  BC_UNSERVED(b, "osqp_amd_batch_polish");
   if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   BCHK(hipSetDevice(b->device));
   const size_t B = (size_t)b->B;
@@ -1494,6 +1735,7 @@ static c_int adjoint_launch(osqp_amd_batch *b, const c_float *dX, const c_float 
 extern "C" c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, const c_float *dY,
                                         c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
                                         c_int *active, c_int *status_adjoint) {
+  BC_UNSERVED(b, "osqp_amd_batch_adjoint");
   if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
   BCHK(hipSetDevice(b->device));
@@ -1578,6 +1820,7 @@ static c_int adjoint_multi_launch(osqp_amd_batch *b, int ncot, const c_float *dX
 extern "C" c_int osqp_amd_batch_adjoint_multi(osqp_amd_batch *b, c_int ncot, const c_float *dX, const c_float *dY,
                                               c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
                                               c_int *active, c_int *status_adjoint) {
+  BC_UNSERVED(b, "osqp_amd_batch_adjoint_multi");
   if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (ncot < 1 || ncot > 65535) return OSQP_DATA_VALIDATION_ERROR;
   if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
@@ -1605,6 +1848,7 @@ extern "C" c_int osqp_amd_batch_adjoint_multi(osqp_amd_batch *b, c_int ncot, con
 // For the tests and tools: builds of the KKT inversion since setup, whether one is kept, its NPOL and its members.
 // Touches no GPU memory.
 extern "C" c_int osqp_amd_batch_kkt_info(osqp_amd_batch *b, c_int out[4]) {
+  BC_UNSERVED(b, "osqp_amd_batch_kkt_info");
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (!out) return OSQP_DATA_VALIDATION_ERROR;
   const bool kept = kkt_kept(b);
@@ -1667,6 +1911,7 @@ static c_int tangent_launch(osqp_amd_batch *b, int ndir, const c_float *dQ, cons
 extern "C" c_int osqp_amd_batch_tangent(osqp_amd_batch *b, c_int ndir, const c_float *dQ, const c_float *dL, const c_float *dU,
                                         const c_float *dPx, const c_float *dAx, c_float *dX, c_float *dY,
                                         c_int *active, c_int *status_tangent) {
+  BC_UNSERVED(b, "osqp_amd_batch_tangent");
   if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (ndir < 1 || ndir > 65535 || !dX) return OSQP_DATA_VALIDATION_ERROR;
   BCHK(hipSetDevice(b->device));
@@ -1706,9 +1951,10 @@ extern "C" c_int osqp_amd_batch_member(osqp_amd_batch *b, c_int qp, c_float *D, 
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (qp < 0 || qp >= b->B) return OSQP_DATA_VALIDATION_ERROR;
   BCHK(hipSetDevice(b->device));
-  const bool streamed = b->engine == OSQP_AMD_BATCH_STREAMED;
+  const bool common = b->engine == OSQP_AMD_BATCH_COMMON;     // one slab of values, one K^-1, one rho: for any qp
+  const bool streamed = b->engine == OSQP_AMD_BATCH_STREAMED || common;
   const int n = b->n, m = b->m, NP = streamed ? b->NPs : 16 * b->tile;
-  const long long q = qp, nv = (long long)b->nnzP + b->nnzA;
+  const long long q = qp, qk = common ? 0 : qp, nv = (long long)b->nnzP + b->nnzA;
   std::vector<int> t(m);
   std::vector<double> wk(Kinv ? (size_t)NP * NP : 0);
   auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
@@ -1717,11 +1963,12 @@ extern "C" c_int osqp_amd_batch_member(osqp_amd_batch *b, c_int qp, c_float *D, 
   if (D) BCHK(get(D, b->io.Wd + q * n, n * sizeof(double)));
   if (E) BCHK(get(E, b->io.We + q * m, m * sizeof(double)));
   if (c) BCHK(get(c, b->io.Wc + q, sizeof(double)));
-  if (rho) BCHK(get(rho, b->io.rho_io + q, sizeof(double)));
+  if (rho && common) *rho = b->bc_rho;
+  else if (rho) BCHK(get(rho, b->io.rho_io + q, sizeof(double)));
   if (ctype) BCHK(get(t.data(), b->io.Wt + q * m, m * sizeof(int)));
-  if (Pv) BCHK(get(Pv, b->io.Wv + q * nv, b->nnzP * sizeof(double)));
-  if (Av) BCHK(get(Av, b->io.Wv + q * nv + b->nnzP, b->nnzA * sizeof(double)));
-  if (Kinv) BCHK(get(wk.data(), b->io.Wk + q * NP * NP, wk.size() * sizeof(double)));
+  if (Pv) BCHK(get(Pv, b->io.Wv + qk * nv, b->nnzP * sizeof(double)));
+  if (Av) BCHK(get(Av, b->io.Wv + qk * nv + b->nnzP, b->nnzA * sizeof(double)));
+  if (Kinv) BCHK(get(wk.data(), b->io.Wk + qk * NP * NP, wk.size() * sizeof(double)));
   BCHK(hipStreamSynchronize(b->stream));
   if (ctype) for (int i = 0; i < m; i++) ctype[i] = t[i];
   if (Kinv && streamed) {
@@ -1738,14 +1985,15 @@ extern "C" c_int osqp_amd_batch_member(osqp_amd_batch *b, c_int qp, c_float *D, 
 extern "C" c_int osqp_amd_batch_shape(osqp_amd_batch *b, c_int *engine, c_int *NP) {
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (engine) *engine = b->engine;
-  if (NP) *NP = b->engine == OSQP_AMD_BATCH_STREAMED ? b->NPs : 16 * b->tile;
+  if (NP) *NP = b->engine != OSQP_AMD_BATCH_TILED ? b->NPs : 16 * b->tile;
   return 0;
 }
 
 extern "C" c_int osqp_amd_batch_rounds(osqp_amd_batch *b, c_int *rounds, c_int *refined) {
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (rounds) *rounds = b->engine == OSQP_AMD_BATCH_STREAMED ? b->last_rounds : (b->solves ? 1 : 0);
-  if (refined) {
+  if (rounds) *rounds = b->engine != OSQP_AMD_BATCH_TILED ? b->last_rounds : (b->solves ? 1 : 0);
+  if (refined && b->engine == OSQP_AMD_BATCH_COMMON) *refined = b->bc_refine ? b->B : 0;   // one verdict for the batch
+  else if (refined) {
     BCHK(hipSetDevice(b->device));
     std::vector<int> f;
     if (read_flags(b, f)) return -102;

@@ -85,6 +85,11 @@ extern "C" c_int osqp_amd_batch_update_dev(osqp_amd_batch *b, const c_float *Q, 
     BCHK(hipStreamSynchronize(b->stream));
     if (bad) return 1;                             // nothing of the handle has been written
   }
+  if (b->engine == OSQP_AMD_BATCH_COMMON && (L || U) && cnt) {   // one class per row over the batch, before any write
+    bool moved = false;
+    if (const int rc = bc_check_classes(b, L, U, 1, &moved, "update")) return rc;
+    if (moved) b->bc_rebuild = true;
+  }
   b->solved = false;
   if (Q) BCHK(hipMemcpyAsync(b->dQ, Q, B * b->n * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
   if ((L || U) && cnt)
@@ -99,6 +104,7 @@ extern "C" c_int osqp_amd_batch_update_dev(osqp_amd_batch *b, const c_float *Q, 
 extern "C" c_int osqp_amd_batch_update_matrices_dev(osqp_amd_batch *b,
                                                     const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
                                                     const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
+  BC_UNSERVED(b, "osqp_amd_batch_update_matrices_dev");
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   // the twin's refusals in the twin's order, on the host lists; then the device pointers; then the first write
   if (Px && Px_idx && P_n > b->nnzP) return 1;
@@ -138,7 +144,10 @@ extern "C" c_int osqp_amd_batch_warm_start_dev(osqp_amd_batch *b, const c_float 
   b->st.warm_start = 1;                          // osqp.c:948
   if (!X && !Y) return 0;
   b->solved = false;
-  hipLaunchKernelGGL(k_batch_warm_start, dim3((unsigned)b->B), dim3(256), 0, b->stream, b->pat, b->io, X, Y);
+  if (b->engine == OSQP_AMD_BATCH_COMMON)
+    hipLaunchKernelGGL(k_bc_warm_start, dim3((unsigned)b->B), dim3(256), 0, b->stream, b->pat, b->io, X, Y);
+  else
+    hipLaunchKernelGGL(k_batch_warm_start, dim3((unsigned)b->B), dim3(256), 0, b->stream, b->pat, b->io, X, Y);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   return 0;
@@ -153,6 +162,7 @@ static hipError_t give(osqp_amd_batch *b, Tp *dst, const Tp *src, size_t cnt) {
 extern "C" c_int osqp_amd_batch_adjoint_dev(osqp_amd_batch *b, const c_float *dX, const c_float *dY,
                                             c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
                                             int *active, int *status_adjoint) {
+  BC_UNSERVED(b, "osqp_amd_batch_adjoint_dev");
   if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
   BCHK(hipSetDevice(b->device));
@@ -174,6 +184,7 @@ extern "C" c_int osqp_amd_batch_adjoint_dev(osqp_amd_batch *b, const c_float *dX
 extern "C" c_int osqp_amd_batch_adjoint_multi_dev(osqp_amd_batch *b, c_int ncot, const c_float *dX, const c_float *dY,
                                                   c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
                                                   int *active, int *status_adjoint) {
+  BC_UNSERVED(b, "osqp_amd_batch_adjoint_multi_dev");
   if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (ncot < 1 || ncot > 65535) return OSQP_DATA_VALIDATION_ERROR;
   if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
@@ -196,6 +207,7 @@ extern "C" c_int osqp_amd_batch_adjoint_multi_dev(osqp_amd_batch *b, c_int ncot,
 extern "C" c_int osqp_amd_batch_tangent_dev(osqp_amd_batch *b, c_int ndir, const c_float *dQ, const c_float *dL,
                                             const c_float *dU, const c_float *dPx, const c_float *dAx, c_float *dX,
                                             c_float *dY, int *active, int *status_tangent) {
+  BC_UNSERVED(b, "osqp_amd_batch_tangent_dev");
   if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (ndir < 1 || ndir > 65535 || !dX) return OSQP_DATA_VALIDATION_ERROR;
   BCHK(hipSetDevice(b->device));
@@ -229,6 +241,7 @@ extern "C" c_int osqp_amd_batch_get_dev(osqp_amd_batch *b, c_float *X, c_float *
 // status_polish as osqp_amd_batch_polish reports it, without running polish: all 0 (not tried) when polish has not
 // run since the last solve
 extern "C" c_int osqp_amd_batch_polish_status_dev(osqp_amd_batch *b, int *status_polish) {
+  BC_UNSERVED(b, "osqp_amd_batch_polish_status_dev");
   if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (!status_polish) return 0;
   BCHK(hipSetDevice(b->device));

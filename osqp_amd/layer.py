@@ -153,6 +153,9 @@ class BatchQPLayer(torch.nn.Module):
 
     def __init__(self, P, A, engine="auto", polish=True, **settings):
         super().__init__()
+        if engine == "common":
+            raise ValueError("BatchQPLayer needs polish and adjoint, which the common-K engine (engine='common') does not "
+                             "serve: use engine='auto' or 'streamed'")
         self.P = sparse.triu(sparse.csc_matrix(P), format="csc"); self.P.sort_indices()
         self.A = sparse.csc_matrix(A); self.A.sort_indices()
         self.engine, self.polish, self.settings = engine, polish, settings
