@@ -1,0 +1,297 @@
+"""The batch loop of the common-K engine (`bc_solve`, osqp_amd/csrc/batch.hip) in long double: a plain numpy statement of
+what the engine is defined to compute for a batch that shares P, A, the scaling, the row classes and ONE rho.
+
+It works in the common scaled space: `ws = oracle_ws(common_oracle(...))` gives D, E, c, the scaled P and A and the
+row classes; every member's q, l, u come through `_common_cases.prescaled`.  All arithmetic is `np.longdouble`
+(64-bit significand on x86-64; unless `dtype` says otherwise, see the end).
+
+  linear solve   K = P + sigma I + A' diag(rho_class) A; K^-1 = np.linalg.inv, then two Newton-Schulz steps in long
+                 double (as `_batch_parity.kinv_reference`, one step more); re-formed at every rho move
+  iteration      (k_bc_rhs / k_bc_step, auxil.c:185-225)  R = sigma x - q + A'(rho.z - y); x~ = K^-1 R; z~ = A x~;
+                 x <- alpha x~ + (1 - alpha) x; z <- clip(alpha z~ + (1 - alpha) z + y / rho, l, u);
+                 y <- y + rho.(alpha z~ + (1 - alpha) z - z_new); a finished member is not touched
+  check points   iter % check_termination == 0: the residuals and norms of update_info, the prim_ok && dual_ok test of
+                 check_termination; scaled_termination = 1, or the default 0 with E^-1, D^-1 and 1 / c where update_info
+                 has them.  Infeasibility certificates are NOT modelled: the cases are chosen so that every member ends
+                 solved or at max_iter, and a false verdict of the engine shows as a status mismatch.
+  adaptation     iter % adaptive_rho_interval == 0, after the check: rho_estimate (scaled norms) of every member still
+                 running; the batch value is that estimate itself when all agree bit for bit, exp(mean(log est)) in
+                 member order otherwise; clipped to [1e-6, 1e6]; adopted only outside [rho / tol, rho tol]; on adoption
+                 every running member's rho_updates rises by one
+  at max_iter    the check (if due), the adaptation (if due), the final exact test (unless already made), the
+                 approximate test, then status -2; the reported rho is the batch's after that last adaptation
+  warm start     a second `solve()` continues from each member's final x, z, y with the rho the first ended with;
+                 rho_updates goes on counting (only `update` resets it, which the reference does not model)
+
+Per member it returns status_val, iter, rho_updates, rho (the rho in force when the member finished: info[7],
+`store_solution`'s a.rho) and x, y, obj_val unscaled as `_common_cases.unscale` does.  `decisions` is the log of what was
+decided and by how much: at every adaptation point the number running, the batch value, whether rho moved and the
+distance of log(value / rho) from +-log(tol); at every check point per running member the ratios of the two residuals
+to their tolerances and the margin of the verdict (1 - max ratio when it passed, max ratio - 1 when it did not).
+
+The reference's own accuracy, measured by tests/test_common_reference_host.py against the oracle (double, LDL') at
+B = 1, where the "mean" is the member's own estimate -- members 0-2 of both ADAPTIVE_CASES families, both termination
+settings, full runs and max_iter = 20 followed by a warm second solve: status, iter and rho_updates identical,
+|x - x_oracle| <= 3.9e-12, |y - y_oracle| <= 3.0e-11, objective <= 6.9e-12 (relative, `_batch_parity.rel`), and the final
+rho (the oracle's settings().rho after the solve) within 5.9e-9 relative -- the largest in the 1100 iterations and five
+moves of member 1 of (129, 258) under the default termination; all other runs stay below 3.1e-10.  The host test holds
+x, y and the objective under ANCHOR_BAR = 1e-8 and the rho difference under RHO_DIFF_MEASURED = 6e-9.
+RHO_BAR, what the GPU tests allow between the engine's rho and this reference's, is 100 x that measured difference (the
+margin over the reference's own arithmetic) and never looser than the project's parity bar of 1e-6: RHO_BAR = 6e-7.
+
+dtype=np.float64 runs the same loop in plain double with numpy's inverse as it comes (no Newton-Schulz step).  It is no
+yardstick: the host test uses it to show that a case is well-conditioned, that is, that double arithmetic cruder than
+the engine's still decides as the long-double run does and ends within the bars."""
+from types import SimpleNamespace
+
+import numpy as np
+from scipy import sparse
+
+from _common_cases import prescaled
+
+ANCHOR_BAR = 1e-8
+RHO_DIFF_MEASURED = 6e-9
+RHO_BAR = min(1e-6, 100.0 * RHO_DIFF_MEASURED)
+
+DEFAULTS = dict(alpha=1.6, eps_abs=1e-3, eps_rel=1e-3, max_iter=4000, check_termination=25, adaptive_rho=1,
+                adaptive_rho_interval=0, adaptive_rho_tolerance=5.0, scaled_termination=0)
+RHO_MIN, RHO_MAX = 1e-6, 1e6
+
+
+def _inf(v):
+    """|v|_inf per member of a [B, k] array (0 for k = 0)."""
+    return np.abs(v).max(axis=1, initial=0)
+
+
+class CommonReference:
+    def __init__(self, ws, Q, L, U, keep_status=False, dtype=np.longdouble, **settings):
+        """keep_status: the reference's osqp_solve does not reset info->status_val (osqp.c:577 asks for OSQP_UNSOLVED,
+        which only setup and an update restore), so a solve that follows one without an update in between makes no
+        approximate test at max_iter and ends with the earlier status.  The engines start every solve unsolved
+        (batch_admm.h `sc[S_STATUS] = OSQP_UNSOLVED`, k_bc_check likewise), which is the order written above; the host
+        anchor turns this on to compare the status of a second solve with the oracle's."""
+        LD = self.ld = dtype
+        unknown = set(settings) - set(DEFAULTS)
+        assert not unknown, unknown
+        self.keep_status = keep_status
+        self.status = np.zeros(Q.shape[0], np.int64)
+        self.st = dict(DEFAULTS, **settings)
+        assert not self.st["adaptive_rho"] or self.st["adaptive_rho_interval"] > 0, "the interval is given, not timed"
+        self.ws = ws
+        B = self.B = Q.shape[0]
+        self.P = (ws["Pu"] + sparse.triu(ws["Pu"], 1).T).toarray().astype(LD)
+        self.A = ws["A"].toarray().astype(LD)
+        self.m, self.n = self.A.shape
+        data = [prescaled(ws, Q, L, U, b) for b in range(B)]
+        self.q = np.array([d[1] for d in data], dtype=LD).reshape(B, self.n)
+        self.l = np.array([d[3] for d in data], dtype=LD).reshape(B, self.m)
+        self.u = np.array([d[4] for d in data], dtype=LD).reshape(B, self.m)
+        self.D, self.E, self.c = ws["D"].astype(LD), ws["E"].astype(LD), LD(ws["c"])
+        self.sigma = LD(ws["sigma"])
+        self.ctype = ws["ctype"]
+        self.x = np.zeros((B, self.n), LD); self.z = np.zeros((B, self.m), LD); self.y = np.zeros((B, self.m), LD)
+        self.rho_updates = np.zeros(B, np.int64)
+        self.calls = 0
+        self.decisions = []
+        self.conds = []                                  # cond(K) of every K formed
+        self._set_rho(min(max(LD(ws["rho"]), RHO_MIN), RHO_MAX))
+
+    # ---- the linear solve ---------------------------------------------------------------------------------------
+    def _set_rho(self, rho):
+        LD = self.ld
+        self.rho = LD(rho)
+        self.rho_vec = np.where(self.ctype == -1, LD(1e-6), np.where(self.ctype == 1, LD(1e3) * self.rho, self.rho)).astype(LD)
+        self.K = self.P + self.sigma * np.eye(self.n, dtype=LD) + self.A.T @ (self.rho_vec[:, None] * self.A)
+        X = np.linalg.inv(self.K.astype(np.float64)).astype(LD)
+        I = np.eye(self.n, dtype=LD)
+        for _ in range(2 if LD is np.longdouble else 0):
+            X = X + X @ (I - self.K @ X)
+        self.Kinv = X
+        self.conds.append(float(np.linalg.cond(self.K.astype(np.float64))))
+
+    def update_rho(self, rho):
+        """osqp_update_rho: the clipped value; iterates and rho_updates stay."""
+        self._set_rho(min(max(self.ld(rho), RHO_MIN), RHO_MAX))
+
+    # ---- update_info (auxil.c:227-318) on the scaled iterates ---------------------------------------------------
+    def _info(self):
+        LD = self.ld
+        x, z, y = self.x, self.z, self.y
+        ax = x @ self.A.T; px = x @ self.P; aty = y @ self.A
+        pr = ax - z
+        dr = self.q + px + (aty if self.m else 0)
+        s = SimpleNamespace()
+        s.npri_s, s.nz_s, s.nax_s = _inf(pr), _inf(z), _inf(ax)
+        s.ndua_s, s.nq_s, s.naty_s, s.npx_s = _inf(dr), _inf(self.q), _inf(aty), _inf(px)
+        if self.st["scaled_termination"]:
+            s.pri, s.nz, s.nax = s.npri_s, s.nz_s, s.nax_s
+            s.dua, s.nq, s.naty, s.npx = s.ndua_s, s.nq_s, s.naty_s, s.npx_s
+        else:
+            ei, di, ci = 1 / self.E, 1 / self.D, 1 / self.c
+            s.pri, s.nz, s.nax = _inf(ei * pr), _inf(ei * z), _inf(ei * ax)
+            s.dua, s.nq, s.naty, s.npx = _inf(di * dr) * ci, _inf(di * self.q) * ci, _inf(di * aty) * ci, _inf(di * px) * ci
+        if self.m == 0:
+            s.pri = np.zeros(self.B, LD)
+        s.obj = (LD(0.5) * np.einsum("bi,bi->b", x, px) + np.einsum("bi,bi->b", self.q, x)) / self.c
+        return s
+
+    def _test(self, s, b, iter_, approximate):
+        """prim_ok && dual_ok of check_termination for member b, logged with its margin."""
+        LD = self.ld
+        f = 10 if approximate else 1
+        ea, er = LD(self.st["eps_abs"]) * f, LD(self.st["eps_rel"]) * f
+        rp = LD(0) if self.m == 0 else s.pri[b] / (ea + er * max(s.nz[b], s.nax[b]))
+        rd = s.dua[b] / (ea + er * max(s.nq[b], s.naty[b], s.npx[b]))
+        ok = bool(rp < 1 and rd < 1)
+        worst = max(rp, rd)
+        self.decisions.append(dict(kind="check", call=self.calls, iter=iter_, member=b, approximate=approximate, passed=ok,
+                                   pri_ratio=float(rp), dua_ratio=float(rd), margin=float(1 - worst if ok else worst - 1)))
+        return ok
+
+    def _estimate(self, s, b):
+        """rho_estimate (auxil.c:13-74) from the scaled norms."""
+        LD = self.ld
+        pr = (s.npri_s[b] if self.m else LD(0)) / (max(s.nz_s[b], s.nax_s[b]) + LD(1e-30))
+        du = s.ndua_s[b] / (max(s.nq_s[b], s.naty_s[b], s.npx_s[b]) + LD(1e-30))
+        return min(max(self.rho * np.sqrt(pr / du), RHO_MIN), RHO_MAX)
+
+    # ---- the loop -----------------------------------------------------------------------------------------------
+    def solve(self):
+        LD = self.ld
+        st, B = self.st, self.B
+        alpha, oma = LD(st["alpha"]), 1 - LD(st["alpha"])
+        tol = LD(st["adaptive_rho_tolerance"])
+        self.calls += 1
+        done = np.zeros(B, bool)
+        status = np.zeros(B, np.int64); iters = np.zeros(B, np.int64); rho_at = np.zeros(B, LD); obj = np.zeros(B, LD)
+        moves = []
+
+        def finish(b, code, s, it):
+            done[b] = True
+            status[b], iters[b], rho_at[b], obj[b] = code, it, self.rho, s.obj[b]
+
+        it = 0
+        while not done.all():
+            it += 1
+            run = ~done
+            w = self.rho_vec * self.z - self.y
+            R = self.sigma * self.x - self.q + w @ self.A
+            xt = R @ self.Kinv.T
+            zt = xt @ self.A.T
+            v = alpha * zt + oma * self.z
+            zn = np.minimum(np.maximum(v + self.y / self.rho_vec, self.l), self.u)
+            self.x[run] = (alpha * xt + oma * self.x)[run]
+            self.y[run] = (self.y + self.rho_vec * (v - zn))[run]
+            self.z[run] = zn[run]
+            checked = bool(st["check_termination"]) and it % st["check_termination"] == 0
+            adapt = bool(st["adaptive_rho"]) and it % st["adaptive_rho_interval"] == 0
+            last = it >= st["max_iter"]
+            if not (checked or adapt or last):
+                continue
+            s = self._info()
+            if checked:
+                for b in np.flatnonzero(~done):
+                    if self._test(s, b, it, False):
+                        finish(b, 1, s, it)
+            running = np.flatnonzero(~done)
+            if adapt and running.size:
+                est = [self._estimate(s, b) for b in running]
+                if all(e == est[0] for e in est):
+                    value = est[0]
+                else:
+                    value = np.exp(sum(np.log(e) for e in est) / LD(len(est)))
+                value = min(max(value, RHO_MIN), RHO_MAX)
+                moved = bool(value > self.rho * tol or value < self.rho / tol)
+                lr = np.log(value / self.rho)
+                self.decisions.append(dict(kind="adapt", call=self.calls, iter=it, running=int(running.size), done=int(done.sum()),
+                                           value=float(value), rho=float(self.rho), moved=moved,
+                                           margin=float(min(abs(lr - np.log(tol)), abs(lr + np.log(tol))))))
+                if moved:
+                    self.rho_updates[running] += 1
+                    self._set_rho(value)
+                    moves.append(it)
+            if last:
+                for b in running:
+                    if not checked and self._test(s, b, it, False):
+                        finish(b, 1, s, it)
+                    elif self.keep_status and self.status[b] != 0:
+                        finish(b, self.status[b], s, it)
+                    elif self._test(s, b, it, True):
+                        finish(b, 2, s, it)
+                    else:
+                        finish(b, -2, s, it)
+        self.status = status.copy()
+        x = (self.D * self.x).astype(np.float64)
+        y = (self.E * self.y / self.c).astype(np.float64)
+        return SimpleNamespace(x=x, y=y, status_val=status, iter=iters, rho_updates=self.rho_updates.copy(),
+                               rho=rho_at.astype(np.float64), obj_val=obj.astype(np.float64), final_rho=float(self.rho),
+                               moves=moves)
+
+
+def margins(ref, call=None):
+    """(smallest adaptation margin, smallest termination margin) of the decisions logged so far (inf: none made)."""
+    d = [e for e in ref.decisions if call is None or e["call"] == call]
+    return (min([e["margin"] for e in d if e["kind"] == "adapt"], default=np.inf),
+            min([e["margin"] for e in d if e["kind"] == "check"], default=np.inf))
+
+
+def reference_for(orc, P, A, Q, L, U, keep_status=False, dtype=np.longdouble, **kw):
+    from _batch_parity import oracle_ws
+    from _common_cases import common_oracle
+    ws = oracle_ws(common_oracle(orc, P, A, Q, L, U, **kw))
+    return CommonReference(ws, Q, L, U, keep_status=keep_status, dtype=dtype, **kw)
+
+
+# ---- the cases of tests/test_gpu_batch_common_loop.py, checked on the host by tests/test_common_reference_host.py ----------
+# name: (n, m, qscale, B, seed, settings beyond ADAPTIVE, what follows the first solve).  The seed is `adaptive_family`'s
+# (1000 + n + m) unless the case missed an input condition with it.  "A2-default": with seed 1099 one member runs to
+# max_iter = 4000 through 28 rho moves and comes within 0.007 of an adaptation threshold.  With seed 1103 the margins
+# hold, but the case is ill-conditioned: rho moves at 650 ... 890 on the estimate of the last one or two running members,
+# a ratio of two nearly converged residuals, and this loop in plain double (dtype=np.float64) ends 4e-4 from the
+# long-double rho -- no double-precision engine can be held to 6e-7 there (the engine came to 1.1e-6).  Seed 1100 meets
+# the margins and the conditioning bar of test_cases_are_well_conditioned; its late moves (470, 500) have 62 and 63
+# members frozen.
+# "then": "rho 0.3" = update_rho(0.3) and a second solve; "solve" = a second solve.
+# "D-wide": case A1's matrices with q ten times smaller and the equality rows widened to inequalities
+# (l - 0.5, u + 0.5): no row weighs 1e3 rho in K, so cond(K) stays small and an unrefined explicit inverse is accurate.
+LOOP_CASES = {
+    "A1": (33, 66, 100.0, 5, 1099, dict(scaled_termination=1), "rho 0.3"),
+    "A2-scaled": (33, 66, 100.0, 65, 1099, dict(scaled_termination=1), None),
+    "A2-default": (33, 66, 100.0, 65, 1100, dict(), None),
+    "A3": (129, 258, 100.0, 5, 1387, dict(), None),
+    "C20": (33, 66, 100.0, 5, 1099, dict(scaled_termination=1, max_iter=20), "solve"),
+    "C40": (33, 66, 100.0, 5, 1099, dict(scaled_termination=1, max_iter=40), None),
+    "D-wide": (33, 66, 10.0, 5, 1099, dict(scaled_termination=1), None),
+}
+MARGIN_ADAPT, MARGIN_CHECK = 1e-2, 1e-3
+COND_WIDE = 1e4
+
+
+def loop_case(name):
+    """(P, A, Q, L, U, settings) of a named case."""
+    from _common_cases import ADAPTIVE, common_family
+    n, m, qscale, B, seed, extra, _ = LOOP_CASES[name]
+    P, A, Q, L, U, _ = common_family(n, m, B, seed)
+    if name == "D-wide":
+        eq = L == U
+        L, U = np.where(eq, L - 0.5, L), np.where(eq, U + 0.5, U)
+    return P, A, Q * qscale, L, U, dict(ADAPTIVE, **extra)
+
+
+_RUNS = {}
+
+
+def case_reference(orc, name, dtype=np.longdouble):
+    """(the reference after its run, [result of every solve]) of a named case; computed once per process and shared --
+    callers leave both unchanged."""
+    if (name, dtype) not in _RUNS:
+        P, A, Q, L, U, kw = loop_case(name)
+        ref = reference_for(orc, P, A, Q, L, U, dtype=dtype, **kw)
+        out = [ref.solve()]
+        then = LOOP_CASES[name][6]
+        if then == "rho 0.3":
+            ref.update_rho(0.3)
+        if then:
+            out.append(ref.solve())
+        _RUNS[name, dtype] = (ref, out)
+    return _RUNS[name, dtype]

@@ -19,7 +19,8 @@ from _common_cases import (ADAPTIVE, ADAPTIVE_CASES, CASES_UNSCALED, FIXED, MIXE
 pytestmark = pytest.mark.gpu
 
 # n: the edges of the 32-padding of K^-1 and of the GEMM's 4-deep k step and 64-row tile; B: the edges of the 16-column
-# MFMA tile and of the 64-member workgroups
+# MFMA tile.  No B here reaches the 64-member workgroups of the element-wise kernels, the 256-member ones of k_bc_probe
+# / k_bc_adopt or a second 64-column tile of the GEMM: B = 63, 64, 65 and 257 are in tests/test_gpu_batch_common_loop.py
 SHAPES = [(1, 33), (17, 15), (32, 16), (33, 17), (128, 33), (129, 1), (1024, 17)]
 
 
