@@ -159,6 +159,10 @@ int hipeng_pcg_layout(hipeng *e, long long out[16]);
  * hipeng_elim_count: how many variables are eliminated. */
 int hipeng_row_eliminated(hipeng *e, c_int i);
 c_int hipeng_elim_count(hipeng *e);
+/* For the tests: copies one per-row array of the elimination to out[m] (reads only, no kernel).  which = 0: rhoe (the row's
+ * effective rho), 1: ecoef (A(i, y)), 2: edinv (1 / D_y), 3: xte (x~ of the row's eliminated variable); rows without an
+ * eliminated variable hold rho, 0, 0 and whatever was there.  An error when no variable is eliminated (the arrays do not exist). */
+int hipeng_elim_peek(hipeng *e, int which, c_float *out);
 /* Resident PCG (the reduced matrix K = P + sigma I + A' rho A held in registers, one launch per linear
  * solve; engine.hip, k_pcg_resident).  out[0] structures built, [1] in use, [2] entries of K per thread,
  * [3] workgroups, [4] nnz(K), [5] LDS bytes per workgroup, [6] PCG iterations of the most recent linear

@@ -3976,7 +3976,12 @@ extern "C" int hipeng_set_params(hipeng *e, const hipeng_params *prm) {
   // slightly larger error: plain warm start below 1e-12 (the stop equality-row problems get by default).
   e->prm.ex_theta = prm->pcg_eps_rel >= 0.5e-12 ? e->ex_theta0 : 0.0;
   if (push_params(e)) return HIPENG_ERR_HIP;
-  if (sigma_changed) refresh_operator(e);
+  if (sigma_changed) {
+    refresh_operator(e);
+    // rho~ depends on sigma: the m-part of the start vector (rho~ A_X x~0, which k_pcg_init takes as it stands) is formed again by
+    // hipeng_run_admm's k_refresh_m into va; vx must follow it, or the first residual is that of another operator
+    if (e->c.nelim) e->start_dirty = true;
+  }
   return 0;
 }
 
@@ -4734,6 +4739,15 @@ extern "C" int hipeng_pcg_layout(hipeng *e, long long out[16]) {
 }
 extern "C" int hipeng_row_eliminated(hipeng *e, c_int i) { return e && !e->ecol.empty() && i >= 0 && i < (c_int)e->ecol.size() && e->ecol[(size_t)i] >= 0 ? 1 : 0; }
 extern "C" c_int hipeng_elim_count(hipeng *e) { return e ? e->c.nelim : 0; }
+// ---- for the tests: one of the per-row arrays of the elimination on the host (reads only) ----
+extern "C" int hipeng_elim_peek(hipeng *e, int which, c_float *out) {
+  if (!e || !out || which < 0 || which > 3 || !e->c.nelim) return HIPENG_ERR_ARG;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const double *src[] = {e->c.rhoe, e->c.ecoef, e->c.edinv, e->c.xte};
+  HIPCHK(hipMemcpy(out, src[which], (size_t)e->m * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
 
 // Resident PCG: out[0] structures built, [1] in use, [2] entries of K per thread, [3] workgroups, [4] nnz(K),
 // [5] LDS bytes per workgroup, [6] PCG iterations of the most recent linear solve, [7] pipelined phase switched off for this K,

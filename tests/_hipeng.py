@@ -1,5 +1,5 @@
 """ctypes view of the C shim include/osqp_amd_engine.h, shared by the kernel-level GPU tests (test_gpu_direct_solve_edges.py,
-test_gpu_engine_kernels.py).  Nothing here computes a reference; Engine.reference() only hands the current (P, A, sigma, rho) to
+test_gpu_engine_kernels.py, test_gpu_pcg_edges.py, test_gpu_elim_edges.py).  Nothing here computes a reference; Engine.reference() only hands the current (P, A, sigma, rho) to
 tests/_kkt_reference.py."""
 import ctypes as C
 import os
@@ -61,7 +61,8 @@ def _lib():
                        ("hipeng_certificates", [vp, C.c_double, C.c_int, C.POINTER(HipengScalars)]),
                        ("hipeng_download", [vp, fp, fp, fp, fp, fp, C.c_int]), ("hipeng_spmv", [vp, C.c_int, fp, fp]),
                        ("hipeng_get_stats", [vp, C.POINTER(HipengStats)]), ("hipeng_pcg_layout", [vp, C.POINTER(C.c_longlong)]),
-                       ("hipeng_is_split", [vp])):
+                       ("hipeng_is_split", [vp]), ("hipeng_upload_q", [vp, fp]), ("hipeng_upload_bounds", [vp, fp, fp]),
+                       ("hipeng_cold_start", [vp]), ("hipeng_row_eliminated", [vp, ll]), ("hipeng_elim_peek", [vp, C.c_int, fp])):
         f = getattr(L, name)
         f.restype, f.argtypes = C.c_int, args
     L.hipeng_destroy.restype, L.hipeng_destroy.argtypes = None, [vp]
@@ -121,6 +122,26 @@ class Engine:
 
     def elim(self):
         return int(self.L.hipeng_elim_count(self.h))
+
+    def row_eliminated(self, i):
+        return int(self.L.hipeng_row_eliminated(self.h, int(i)))
+
+    def elim_peek(self, which):
+        """hipeng_elim_peek: "rhoe", "ecoef", "edinv" or "xte", one value per row of A."""
+        out = np.zeros(max(self.m, 1))
+        assert self.L.hipeng_elim_peek(self.h, ("rhoe", "ecoef", "edinv", "xte").index(which), self._p(out)) == 0
+        return out[: self.m]
+
+    def upload_q(self, q):
+        q = self.abi.as_f64(q)
+        assert self.L.hipeng_upload_q(self.h, self._p(q)) == 0
+
+    def upload_bounds(self, l, u):
+        l, u = self.abi.as_f64(l), self.abi.as_f64(u)
+        assert self.L.hipeng_upload_bounds(self.h, self._p(l), self._p(u)) == 0
+
+    def cold_start(self):
+        assert self.L.hipeng_cold_start(self.h) == 0
 
     def set_rho(self, rho):
         self.rho = np.asarray(rho, float)
