@@ -156,8 +156,10 @@ c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish);
  * [batch] (NULL = skip): 1 computed; -1 a KKT pivot of the wrong sign (that member's outputs are 0); 0 not tried, the
  * member's last solve did not end OSQP_SOLVED (outputs 0).  Nothing of the handle changes: X, Y, info8, the stored
  * iterates, rho, K^-1 and the status_polish a later osqp_amd_batch_polish reports stay bit-equal.
- * Memory: polish's KKT buffer with its cap and chunks, plus staging of the inputs and outputs, allocated at the first
- * call (dPx / dAx at the first call that asks for them) and freed by cleanup.
+ * Memory: polish's KKT buffer with its cap and chunks, plus the one staging set of the derivative calls (this one,
+ * osqp_amd_batch_adjoint_multi, osqp_amd_batch_tangent and their _dev twins share it: each returns with the handle's
+ * stream synchronised, so nothing is queued on it between calls): inputs and outputs at the first call, room for
+ * dPx / dAx at the first call that asks for them; it grows when a later call needs more and is freed by cleanup.
  * Returns as osqp_amd_batch_polish: 0; OSQP_WORKSPACE_NOT_INIT_ERROR when no solve has run on the current problem;
  * OSQP_MEM_ALLOC_ERROR (the handle stays usable); OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line when
  * n + active rows exceeds 2176 or the LDS does not fit; OSQP_DATA_VALIDATION_ERROR when dX, dQ (or, with m > 0,
@@ -175,8 +177,8 @@ c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, const c_float
  * one inversion of its KKT matrix; a cotangent's bits depend neither on ncot, nor on the other cotangents, nor on the
  * chunking.  active [batch][m] and status_adjoint [batch] (NULL = skip) are per member, as osqp_amd_batch_adjoint
  * reports them.
- * Memory: as osqp_amd_batch_adjoint, with staging of its own that grows when a later call brings a larger ncot and is
- * freed by cleanup; a handle that never makes this call allocates nothing for it.
+ * Memory: as osqp_amd_batch_adjoint, of which this is the general form (that call is ncot = 1): the same staging set,
+ * which grows when a later call brings a larger ncot and is freed by cleanup.
  * Returns as osqp_amd_batch_adjoint, plus OSQP_DATA_VALIDATION_ERROR when ncot < 1 or ncot > 65535. */
 c_int osqp_amd_batch_adjoint_multi(osqp_amd_batch *b, c_int ncot,
                                    const c_float *dX /*[batch][ncot][n]*/, const c_float *dY /*[batch][ncot][m], NULL = 0*/,
@@ -219,9 +221,9 @@ c_int osqp_amd_batch_kkt_info(osqp_amd_batch *b, c_int out[4]);
  * computed; -1 a KKT pivot of the wrong sign (that member's outputs are 0); 0 not tried, the member's last solve did
  * not end OSQP_SOLVED (outputs 0).  Nothing of the handle changes: X, Y, info8, the stored iterates, rho, K^-1, the
  * status_polish a later osqp_amd_batch_polish reports and what a later osqp_amd_batch_adjoint returns stay bit-equal.
- * Memory: polish's KKT buffer with its cap and chunks, plus staging of the vector tangents and the outputs,
- * allocated at the first call, and of the matrix tangents, allocated at the first call that passes one; the staging
- * grows when a later call brings a larger ndir and is freed by cleanup.
+ * Memory: polish's KKT buffer with its cap and chunks, plus the staging set it shares with osqp_amd_batch_adjoint:
+ * room for the tangents that are passed (host route) and for the outputs; it grows when a later call brings a larger
+ * ndir and is freed by cleanup.
  * Returns 0; OSQP_WORKSPACE_NOT_INIT_ERROR for a NULL handle or when no solve has run on the current problem;
  * OSQP_DATA_VALIDATION_ERROR when ndir < 1, ndir > 65535 or dX is NULL; OSQP_MEM_ALLOC_ERROR (the handle stays
  * usable); OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line when n + active rows exceeds 2176 or the kernel would

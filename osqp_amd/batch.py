@@ -528,45 +528,32 @@ class BatchOSQP:
         holds: the polished one where polish() was accepted, the ADMM iterate otherwise.  Changes nothing in the
         handle.  Needs a solve since setup or the last update.
         dX [B, D, n] with dY [B, D, m] (or None): D cotangents per member in one call, on one KKT inversion; the five
-        gradients come back [B, D, .], active and status_adjoint per member (_adjoint_multi).
+        gradients come back [B, D, .], active and status_adjoint per member -- D rows of the Jacobian; slice d carries
+        the bits adjoint(dX[:, d], dY[:, d]) returns.
         On one solve, adjoint() and tangent() share the KKT inversion the first of them builds (kkt_info)."""
         self._unserved("adjoint")
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): adjoint is a call of the batch "
                                "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
-        B, n, m = self.B, self.n, self.m
-        if np.ndim(dX) == 3:
-            return self._adjoint_multi(dX, dY, matrices)
-        dX, dY = check_adjoint(B, n, m, dX, dY)
-        dq = np.zeros((B, n)); dl = np.zeros((B, max(m, 1))); du = np.zeros((B, max(m, 1)))
-        dPx = np.zeros((B, max(self.Pu.nnz, 1))) if matrices else None
-        dAx = np.zeros((B, max(self.Ah.nnz, 1))) if matrices else None
-        act = np.zeros((B, max(m, 1)), np.int64); sa = np.zeros(B, np.int64)
-        rc = self._lib.osqp_amd_batch_adjoint(self._h, abi.fptr(dX), _p(dY if m else None), abi.fptr(dq), abi.fptr(dl),
-                                              abi.fptr(du), _p(dPx), _p(dAx), abi.iptr(act), abi.iptr(sa))
-        if rc:
-            raise RuntimeError("osqp_amd_batch_adjoint failed (%d)%s" % (rc, ": no solve has run on the current problem"
-                                                                         if rc == 7 else ""))
-        return SimpleNamespace(dq=dq, dl=dl[:, :m], du=du[:, :m], dPx=None if dPx is None else dPx[:, :self.Pu.nnz],
-                               dAx=None if dAx is None else dAx[:, :self.Ah.nnz], active=act[:, :m], status_adjoint=sa)
-
-    def _adjoint_multi(self, dX, dY, matrices):
-        """adjoint() for dX [B, D, n], dY [B, D, m] (None = 0): D cotangents per member -- D rows of the Jacobian -- that
-        share one KKT inversion.  dq [B, D, n], dl, du [B, D, m], dPx [B, D, nnzP], dAx [B, D, nnzA]; active [B, m] and
-        status_adjoint [B] are per member.  Slice d carries the bits adjoint(dX[:, d], dY[:, d]) returns."""
         B, n, m, nP, nA = self.B, self.n, self.m, self.Pu.nnz, self.Ah.nnz
-        dX, dY, D = check_adjoint_multi(B, n, m, dX, dY)
+        flat = np.ndim(dX) != 3       # [B, n] takes the single-cotangent entry point, [B, D, n] the _multi one
+        if flat:
+            dX, dY = check_adjoint(B, n, m, dX, dY)
+            D, call, lead = 1, "osqp_amd_batch_adjoint", ()
+        else:
+            dX, dY, D = check_adjoint_multi(B, n, m, dX, dY)
+            call, lead = "osqp_amd_batch_adjoint_multi", (D,)
         dq = np.zeros((B, D, n)); dl = np.zeros((B, D, max(m, 1))); du = np.zeros((B, D, max(m, 1)))
         dPx = np.zeros((B, D, max(nP, 1))) if matrices else None
         dAx = np.zeros((B, D, max(nA, 1))) if matrices else None
         act = np.zeros((B, max(m, 1)), np.int64); sa = np.zeros(B, np.int64)
-        rc = self._lib.osqp_amd_batch_adjoint_multi(self._h, D, abi.fptr(dX), _p(dY if m else None), abi.fptr(dq),
-                                                    abi.fptr(dl), abi.fptr(du), _p(dPx), _p(dAx), abi.iptr(act), abi.iptr(sa))
+        rc = getattr(self._lib, call)(self._h, *lead, abi.fptr(dX), _p(dY if m else None), abi.fptr(dq), abi.fptr(dl),
+                                      abi.fptr(du), _p(dPx), _p(dAx), abi.iptr(act), abi.iptr(sa))
         if rc:
-            raise RuntimeError("osqp_amd_batch_adjoint_multi failed (%d)%s"
-                               % (rc, ": no solve has run on the current problem" if rc == 7 else ""))
-        return SimpleNamespace(dq=dq, dl=dl[:, :, :m], du=du[:, :, :m], dPx=None if dPx is None else dPx[:, :, :nP],
-                               dAx=None if dAx is None else dAx[:, :, :nA], active=act[:, :m], status_adjoint=sa)
+            raise RuntimeError("%s failed (%d)%s" % (call, rc, ": no solve has run on the current problem" if rc == 7 else ""))
+        cut = lambda a, k: None if a is None else (a[:, 0, :k] if flat else a[:, :, :k])
+        return SimpleNamespace(dq=cut(dq, n), dl=cut(dl, m), du=cut(du, m), dPx=cut(dPx, nP), dAx=cut(dAx, nA),
+                               active=act[:, :m], status_adjoint=sa)
 
     def kkt_info(self):
         """For the tests and tools: (builds, kept, npol, members) -- passes of KKT formation and inversion over the solved
@@ -663,36 +650,24 @@ class BatchOSQP:
                              "takes and returns host arrays")
         if dX is None or dq is None or (self.m and (dl is None or du is None)):
             raise ValueError("adjoint_into needs dX, dq and, for m > 0, dl and du")
-        if len(dX.__cuda_array_interface__["shape"]) == 3:
-            return self._adjoint_multi_into(dX, dY, dq, dl, du, dPx, dAx, active, status_adjoint)
-        d = lambda a, cols, name: self._dev(a, cols, name, writable=True)
-        rc = self._lib.osqp_amd_batch_adjoint_dev(
-            self._h, self._dev(dX, self.n, "dX"), self._dev(dY, self.m, "dY"), d(dq, self.n, "dq"), d(dl, self.m, "dl"),
-            d(du, self.m, "du"), d(dPx, self.Pu.nnz, "dPx"), d(dAx, self.Ah.nnz, "dAx"),
-            self._dev(active, self.m, "active", "<i4", True),
-            None if status_adjoint is None else device_view(status_adjoint, (self.B,), "<i4", True, "status_adjoint"))
-        if rc:
-            raise RuntimeError("osqp_amd_batch_adjoint_dev failed (%d)%s"
-                               % (rc, ": no solve has run on the current problem" if rc == 7 else
-                                  _BAD_POINTER if rc == 1 else ""))
-
-    def _adjoint_multi_into(self, dX, dY, dq, dl, du, dPx, dAx, active, status_adjoint):
-        """adjoint_into for dX [B, D, n]: every float array is [B, D, .]; active [B, m] and status_adjoint [B] stay per member."""
         B, n, m, nP, nA = self.B, self.n, self.m, self.Pu.nnz, self.Ah.nnz
-        dX, dY, D = check_adjoint_multi(B, n, m, dX, dY, dq=(dq, n), dl=(dl, m), du=(du, m), dPx=(dPx, nP), dAx=(dAx, nA))
+        flat = len(dX.__cuda_array_interface__["shape"]) != 3     # as adjoint(): [B, n] takes the single-cotangent entry point
+        D, call, lead = 1, "osqp_amd_batch_adjoint_dev", ()
+        if not flat:
+            dX, dY, D = check_adjoint_multi(B, n, m, dX, dY, dq=(dq, n), dl=(dl, m), du=(du, m), dPx=(dPx, nP), dAx=(dAx, nA))
+            call, lead = "osqp_amd_batch_adjoint_multi_dev", (D,)
 
         def d(a, cols, name, writable=True):
             if a is None:
                 return None
-            return device_view(a, (B, D, cols), "<f8", writable, name) or None
-        rc = self._lib.osqp_amd_batch_adjoint_multi_dev(
-            self._h, D, d(dX, n, "dX", False), d(dY, m, "dY", False), d(dq, n, "dq"), d(dl, m, "dl"), d(du, m, "du"),
+            return device_view(a, (B, cols) if flat else (B, D, cols), "<f8", writable, name) or None
+        rc = getattr(self._lib, call)(
+            self._h, *lead, d(dX, n, "dX", False), d(dY, m, "dY", False), d(dq, n, "dq"), d(dl, m, "dl"), d(du, m, "du"),
             d(dPx, nP, "dPx"), d(dAx, nA, "dAx"), self._dev(active, m, "active", "<i4", True),
             None if status_adjoint is None else device_view(status_adjoint, (B,), "<i4", True, "status_adjoint"))
         if rc:
-            raise RuntimeError("osqp_amd_batch_adjoint_multi_dev failed (%d)%s"
-                               % (rc, ": no solve has run on the current problem" if rc == 7 else
-                                  _BAD_POINTER if rc == 1 else ""))
+            raise RuntimeError("%s failed (%d)%s" % (call, rc, ": no solve has run on the current problem" if rc == 7 else
+                                                     _BAD_POINTER if rc == 1 else ""))
 
     def tangent_into(self, dx, dy, dQ=None, dL=None, dU=None, dPx=None, dAx=None, active=None, status_tangent=None):
         """tangent() between device arrays of the caller's: from dQ, dL, dU, dPx, dAx (None = 0; [B, k], or [B, D, k] for

@@ -725,24 +725,17 @@ struct osqp_amd_batch {
   int *d_plist = nullptr;   // [B] the solved members, in index order
   bool solved = false;      // the iterates and info on the device are those of a solve of the current problem
   bool polished = false;    // ... and polish has already run on them
-  // adjoint (batch_adjoint.h): staging of the inputs and outputs, allocated at the first call that needs them
-  double *adj_in = nullptr;   // [B][n + m] dl/dx, then dl/dy
-  double *adj_out = nullptr;  // [B][n + 2 m] dQ, dL, dU
-  double *adj_dP = nullptr, *adj_dA = nullptr;   // [B][nnzP], [B][nnzA]
-  int *adj_act = nullptr, *adj_stat = nullptr;   // [B][m], [B]
-  // tangent (batch_tangent.h): staging that grows with ndir (freed by cleanup), the rest allocated at the first call
-  double *tan_in = nullptr;   // [B][ndir][n], [B][ndir][m], [B][ndir][m] the vector tangents (host route)
-  double *tan_mat = nullptr;  // [B][ndir][nnzP], [B][ndir][nnzA] the matrix tangents (host route)
-  double *tan_out = nullptr;  // [B][ndir][n] dX, then [B][ndir][m] dY
-  size_t tan_in_cap = 0, tan_mat_cap = 0, tan_out_cap = 0;   // in doubles
-  int *tan_act = nullptr, *tan_stat = nullptr, *tan_piv = nullptr;   // [B][m], [B], [B] (the inversion's verdict)
+  // adjoint and tangent (batch_adjoint.h, batch_tangent.h): the one staging set of the derivative calls.  Each of
+  // them returns with the stream synchronised, so nothing is queued on it between calls.  in, out and mat grow with
+  // ncot / ndir (freed by cleanup); the rest is allocated at the first call.
+  struct {
+    double *in = nullptr;    // the vector inputs of the host route: dl/dx, dl/dy, or the tangents dQ, dL, dU
+    double *out = nullptr;   // dQ, dL, dU of the adjoint, or dX, dY of the tangent
+    double *mat = nullptr;   // the matrix slab: dPx, dAx the adjoint returns, or the tangent's on the host route
+    size_t in_cap = 0, out_cap = 0, mat_cap = 0;   // in doubles
+    int *act = nullptr, *stat = nullptr, *piv = nullptr;   // [B][m], [B], [B] (the inversion's verdict)
+  } bd;
   int *d_bad = nullptr;     // device-array updates (batch_devio.h): count of l > u pairs of k_batch_check_bounds
-  // adjoint_multi (batch_adjoint.h): staging that grows with ncot (freed by cleanup), the rest allocated at the first call
-  double *adjm_in = nullptr;   // [B][ncot][n] dl/dx, then [B][ncot][m] dl/dy (host route)
-  double *adjm_out = nullptr;  // [B][ncot][n] dQ, then [B][ncot][m] dL and dU
-  double *adjm_mat = nullptr;  // [B][ncot][nnzP] dPx, then [B][ncot][nnzA] dAx
-  size_t adjm_in_cap = 0, adjm_out_cap = 0, adjm_mat_cap = 0;   // in doubles
-  int *adjm_act = nullptr, *adjm_stat = nullptr, *adjm_piv = nullptr;   // [B][m], [B], [B] (the inversion's verdict)
   // the kept KKT inversion (bd_run): what a one-chunk adjoint / adjoint_multi / tangent call built -- pol.map, rows,
   // mred, nlow, d_plist, the inverses in pol.K and the pivot verdicts -- stays for the later calls on the same solve
   int kkt_cache = 1;        // OSQP_AMD_BATCH_KKT_CACHE (0: every call builds its own)
@@ -1368,7 +1361,7 @@ extern "C" void osqp_amd_batch_cleanup(osqp_amd_batch *b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   for (void *p : b->allocs) (void)hipFree(p);
   if (b->pol.K) (void)hipFree(b->pol.K);
-  for (double *p : {b->tan_in, b->tan_mat, b->tan_out, b->adjm_in, b->adjm_mat, b->adjm_out}) if (p) (void)hipFree(p);
+  for (double *p : {b->bd.in, b->bd.mat, b->bd.out}) if (p) (void)hipFree(p);
   b->kkt_valid = false;
   if (b->stream) (void)hipStreamDestroy(b->stream);
   delete b;
@@ -1601,8 +1594,7 @@ static c_int bp_plan(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds
   return 0;
 }
 static size_t bp_lds_of(int n, int m, int NPOL) { return bp_lds_bytes(n, m, NPOL); }
-static size_t ba_lds_of(int n, int m, int NPOL) { return ba_lds_bytes(n, m, NPOL); }
-static size_t bt_lds_of(int n, int m, int NPOL) { return bt_lds_bytes(n, m, NPOL); }
+static size_t bd_lds_of(int n, int m, int NPOL) { return bd_lds_bytes(n, m, NPOL); }
 
 // The planned chunks of solved members: the KKT matrix of each member of a chunk (k_bp_form), its inverse
 // (k_bp_invert), then the caller's kernel fn, launched by third(members of the chunk, their list) with pn.lds
@@ -1692,159 +1684,6 @@ extern "C" c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish) 
   return 0;
 }
 
-// What osqp_amd_batch_adjoint and osqp_amd_batch_adjoint_dev share: the staging, the plan and the launches.  dev: dX
-// and dY are device arrays, which k_ba_adjoint reads in place.  *out: where the outputs sit (dPx / dAx null unless
-// wantP / wantA); nothing is waited for.
-static c_int adjoint_launch(osqp_amd_batch *b, const c_float *dX, const c_float *dY, bool dev, bool wantP, bool wantA,
-                            BAdj *out) {
-  const size_t B = (size_t)b->B;
-  const int n = b->n, m = b->m;
-  if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
-  if ((!dev && balloc_once(b, &b->adj_in, B * (n + m))) || balloc_once(b, &b->adj_out, B * (n + 2 * (size_t)m)) ||
-      balloc_once(b, &b->adj_act, B * m) || balloc_once(b, &b->adj_stat, B) ||
-      (wantP && balloc_once(b, &b->adj_dP, B * b->nnzP)) || (wantA && balloc_once(b, &b->adj_dA, B * b->nnzA))) {
-    (void)hipGetLastError();
-    return OSQP_MEM_ALLOC_ERROR;
-  }
-  BPol pl = b->pol;          // polish's buffers; its status array stays polish's
-  pl.stat = b->adj_stat;
-  BAdj ad{};
-  double *gx = b->adj_in, *gy = dev ? nullptr : b->adj_in + B * n;   // (the input staging is the host route's alone)
-  ad.gx = dev ? dX : gx; ad.gy = (dY && m) ? (dev ? dY : gy) : nullptr;
-  ad.dQ = b->adj_out; ad.dL = ad.dQ + B * n; ad.dU = ad.dL + B * m;
-  ad.dPx = wantP ? b->adj_dP : nullptr; ad.dAx = wantA ? b->adj_dA : nullptr;
-  ad.active = b->adj_act;
-  if (!dev) {
-    BCHK(hipMemcpyAsync(gx, dX, B * n * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (ad.gy) BCHK(hipMemcpyAsync(gy, dY, B * m * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  }
-  // members that are skipped or rejected report zeros
-  BCHK(hipMemsetAsync(b->adj_out, 0, std::max((size_t)1, B * (n + 2 * (size_t)m)) * sizeof(double), b->stream));
-  BCHK(hipMemsetAsync(b->adj_act, 0, std::max((size_t)1, B * m) * sizeof(int), b->stream));
-  if (ad.dPx) BCHK(hipMemsetAsync(ad.dPx, 0, std::max((size_t)1, B * b->nnzP) * sizeof(double), b->stream));
-  if (ad.dAx) BCHK(hipMemsetAsync(ad.dAx, 0, std::max((size_t)1, B * b->nnzA) * sizeof(double), b->stream));
-  if (const c_int rc = bd_run(b, pl, "adjoint", ba_lds_of, KFN(k_ba_adjoint), [&](const BPlan &pn, unsigned cnt, const int *lp) {
-        hipLaunchKernelGGL(k_ba_adjoint, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
-      })) return rc;
-  *out = ad;
-  return 0;
-}
-
-// adjoint derivatives for the solved members (batch_adjoint.h): polish's active rows, KKT matrix and inversion on
-// polish's buffers, in the same chunks, with a status array of its own; nothing of the solve state is written
-extern "C" c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, const c_float *dY,
-                                        c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
-                                        c_int *active, c_int *status_adjoint) {
-  BC_UNSERVED(b, "osqp_amd_batch_adjoint");
-  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
-  BCHK(hipSetDevice(b->device));
-  const size_t B = (size_t)b->B;
-  const int n = b->n, m = b->m;
-  BAdj ad{};
-  if (const c_int rc = adjoint_launch(b, dX, dY, false, dPx != nullptr, dAx != nullptr, &ad)) return rc;
-  BCHK(hipMemcpyAsync(dQ, ad.dQ, B * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (m) {
-    BCHK(hipMemcpyAsync(dL, ad.dL, B * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    BCHK(hipMemcpyAsync(dU, ad.dU, B * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  }
-  if (dPx && b->nnzP) BCHK(hipMemcpyAsync(dPx, ad.dPx, B * b->nnzP * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (dAx && b->nnzA) BCHK(hipMemcpyAsync(dAx, ad.dAx, B * b->nnzA * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  std::vector<int> ha(active ? B * m : 0), hs(B);
-  if (active && m) BCHK(hipMemcpyAsync(ha.data(), b->adj_act, B * m * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-  if (status_adjoint) BCHK(hipMemcpyAsync(hs.data(), b->adj_stat, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-  BCHK(hipStreamSynchronize(b->stream));
-  for (size_t k = 0; k < ha.size(); k++) active[k] = ha[k];
-  if (status_adjoint) for (size_t q = 0; q < B; q++) status_adjoint[q] = hs[q];
-  return 0;
-}
-
-// a staging buffer of the tangent or adjoint_multi call of at least cnt doubles (it only grows; nothing is queued on
-// it between calls)
-static int tan_reserve(double **p, size_t *cap, size_t cnt) {
-  if (cnt <= *cap) return 0;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr; *cap = 0;
-  void *q = nullptr;
-  if (hipMalloc(&q, cnt * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return -102; }
-  *p = static_cast<double *>(q); *cap = cnt;
-  return 0;
-}
-
-// What osqp_amd_batch_adjoint_multi and osqp_amd_batch_adjoint_multi_dev share: the staging, the plan and the
-// launches.  dev: dX and dY are device arrays, which k_ba_adjoint_multi reads in place.  *out: where the outputs sit
-// (dPx / dAx null unless wantP / wantA); nothing is waited for.
-static c_int adjoint_multi_launch(osqp_amd_batch *b, int ncot, const c_float *dX, const c_float *dY, bool dev, bool wantP,
-                                  bool wantA, BAdjM *out) {
-  const size_t B = (size_t)b->B, D = (size_t)ncot;
-  const size_t n = (size_t)b->n, m = (size_t)b->m, nnzP = (size_t)b->nnzP, nnzA = (size_t)b->nnzA;
-  if (!m) dY = nullptr;
-  if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
-  if (balloc_once(b, &b->adjm_act, B * m) || balloc_once(b, &b->adjm_stat, B) || balloc_once(b, &b->adjm_piv, B)) {
-    (void)hipGetLastError();
-    return OSQP_MEM_ALLOC_ERROR;
-  }
-  const size_t nout = std::max((size_t)1, B * D * (n + 2 * m)), nmat = std::max((size_t)1, B * D * (nnzP + nnzA));
-  if (tan_reserve(&b->adjm_out, &b->adjm_out_cap, nout) ||
-      (!dev && tan_reserve(&b->adjm_in, &b->adjm_in_cap, std::max((size_t)1, B * D * (n + m)))) ||
-      ((wantP || wantA) && tan_reserve(&b->adjm_mat, &b->adjm_mat_cap, nmat)))
-    return OSQP_MEM_ALLOC_ERROR;
-  BPol pl = b->pol;          // polish's buffers; its status array stays polish's
-  pl.stat = b->adjm_piv;
-  BAdjM ad{};
-  ad.ncot = ncot;
-  ad.gx = dX; ad.gy = dY;
-  if (!dev) {                // (the input staging is the host route's alone)
-    double *gx = b->adjm_in, *gy = gx + B * D * n;
-    BCHK(hipMemcpyAsync(gx, dX, B * D * n * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (dY) BCHK(hipMemcpyAsync(gy, dY, B * D * m * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    ad.gx = gx; ad.gy = dY ? gy : nullptr;
-  }
-  ad.dQ = b->adjm_out; ad.dL = ad.dQ + B * D * n; ad.dU = ad.dL + B * D * m;
-  ad.dPx = wantP ? b->adjm_mat : nullptr; ad.dAx = wantA ? b->adjm_mat + B * D * nnzP : nullptr;
-  ad.active = b->adjm_act; ad.stat = b->adjm_stat;
-  // members that are skipped or rejected report zeros, in every one of the ncot slices
-  BCHK(hipMemsetAsync(b->adjm_out, 0, nout * sizeof(double), b->stream));
-  BCHK(hipMemsetAsync(b->adjm_act, 0, std::max((size_t)1, B * m) * sizeof(int), b->stream));
-  BCHK(hipMemsetAsync(b->adjm_stat, 0, B * sizeof(int), b->stream));
-  if (wantP || wantA) BCHK(hipMemsetAsync(b->adjm_mat, 0, nmat * sizeof(double), b->stream));
-  if (const c_int rc = bd_run(b, pl, "adjoint_multi", ba_lds_of, KFN(k_ba_adjoint_multi), [&](const BPlan &pn, unsigned cnt, const int *lp) {
-        hipLaunchKernelGGL(k_ba_adjoint_multi, dim3(cnt, (unsigned)ncot), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
-      })) return rc;
-  *out = ad;
-  return 0;
-}
-
-// ncot cotangents per member in one call (batch_adjoint.h): osqp_amd_batch_adjoint's route, with one inversion for the
-// ncot cotangents of a member; nothing of the solve state is written
-extern "C" c_int osqp_amd_batch_adjoint_multi(osqp_amd_batch *b, c_int ncot, const c_float *dX, const c_float *dY,
-                                              c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
-                                              c_int *active, c_int *status_adjoint) {
-  BC_UNSERVED(b, "osqp_amd_batch_adjoint_multi");
-  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (ncot < 1 || ncot > 65535) return OSQP_DATA_VALIDATION_ERROR;
-  if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
-  BCHK(hipSetDevice(b->device));
-  const size_t B = (size_t)b->B, D = (size_t)ncot;
-  const size_t n = (size_t)b->n, m = (size_t)b->m, nnzP = (size_t)b->nnzP, nnzA = (size_t)b->nnzA;
-  BAdjM ad{};
-  if (const c_int rc = adjoint_multi_launch(b, (int)ncot, dX, dY, false, dPx != nullptr, dAx != nullptr, &ad)) return rc;
-  BCHK(hipMemcpyAsync(dQ, ad.dQ, B * D * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (m) {
-    BCHK(hipMemcpyAsync(dL, ad.dL, B * D * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    BCHK(hipMemcpyAsync(dU, ad.dU, B * D * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  }
-  if (dPx && nnzP) BCHK(hipMemcpyAsync(dPx, ad.dPx, B * D * nnzP * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (dAx && nnzA) BCHK(hipMemcpyAsync(dAx, ad.dAx, B * D * nnzA * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  std::vector<int> ha(active ? B * m : 0), hs(B);
-  if (active && m) BCHK(hipMemcpyAsync(ha.data(), ad.active, B * m * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-  if (status_adjoint) BCHK(hipMemcpyAsync(hs.data(), ad.stat, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-  BCHK(hipStreamSynchronize(b->stream));
-  for (size_t k = 0; k < ha.size(); k++) active[k] = ha[k];
-  if (status_adjoint) for (size_t q = 0; q < B; q++) status_adjoint[q] = hs[q];
-  return 0;
-}
-
 // For the tests and tools: builds of the KKT inversion since setup, whether one is kept, its NPOL and its members.
 // Touches no GPU memory.
 extern "C" c_int osqp_amd_batch_kkt_info(osqp_amd_batch *b, c_int out[4]) {
@@ -1857,77 +1696,180 @@ extern "C" c_int osqp_amd_batch_kkt_info(osqp_amd_batch *b, c_int out[4]) {
   return 0;
 }
 
-// What osqp_amd_batch_tangent and osqp_amd_batch_tangent_dev share: the staging, the plan and the launches.  dev: the
-// tangents are device arrays, which k_bt_tangent reads in place.  *out: where the outputs sit; nothing is waited for.
-static c_int tangent_launch(osqp_amd_batch *b, int ndir, const c_float *dQ, const c_float *dL, const c_float *dU,
-                            const c_float *dPx, const c_float *dAx, bool dev, BTan *out) {
+// a staging buffer of the derivative calls of at least cnt doubles (it only grows; nothing is queued on it between
+// calls)
+static int bd_reserve(double **p, size_t *cap, size_t cnt) {
+  if (cnt <= *cap) return 0;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr; *cap = 0;
+  void *q = nullptr;
+  if (hipMalloc(&q, cnt * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return -102; }
+  *p = static_cast<double *>(q); *cap = cnt;
+  return 0;
+}
+
+// What the adjoint and the tangent do before bd_run.  The handle's staging for this call: nout doubles of output and
+// nmat of matrix output, both zeroed with `active` and the status (members that are skipped or rejected report
+// zeros), and room for the inputs.  *pl: polish's buffers with the call's own pivot verdicts; polish's status array
+// stays polish's.  ins: the inputs (null = none); *slot is where the kernel reads each -- in place on the device
+// route, from the staging (vectors in `in`, matrices in `mat`) on the host route.
+struct BDIn { const c_float *src; size_t cnt; const double **slot; bool mat; };
+static c_int bd_stage(osqp_amd_batch *b, BPol *pl, bool dev, std::initializer_list<BDIn> ins, size_t nout, size_t nmat) {
+  const size_t B = (size_t)b->B, m = (size_t)b->m;
+  auto &sg = b->bd;
+  if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
+  if (balloc_once(b, &sg.act, B * m) || balloc_once(b, &sg.stat, B) || balloc_once(b, &sg.piv, B)) {
+    (void)hipGetLastError();
+    return OSQP_MEM_ALLOC_ERROR;
+  }
+  size_t nin = 0, nmat_in = 0;                   // (the input staging is the host route's alone)
+  if (!dev) for (const BDIn &t : ins) if (t.src) (t.mat ? nmat_in : nin) += t.cnt;
+  nout = std::max((size_t)1, nout);
+  if (bd_reserve(&sg.out, &sg.out_cap, nout) || bd_reserve(&sg.in, &sg.in_cap, nin) ||
+      bd_reserve(&sg.mat, &sg.mat_cap, std::max(nmat, nmat_in)))
+    return OSQP_MEM_ALLOC_ERROR;
+  *pl = b->pol;
+  pl->stat = sg.piv;
+  double *vec = sg.in, *mat = sg.mat;
+  for (const BDIn &t : ins) {
+    *t.slot = t.src;
+    if (dev || !t.src) continue;
+    double *&dst = t.mat ? mat : vec;
+    BCHK(hipMemcpyAsync(dst, t.src, t.cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    *t.slot = dst;
+    dst += t.cnt;
+  }
+  BCHK(hipMemsetAsync(sg.out, 0, nout * sizeof(double), b->stream));
+  BCHK(hipMemsetAsync(sg.act, 0, std::max((size_t)1, B * m) * sizeof(int), b->stream));
+  BCHK(hipMemsetAsync(sg.stat, 0, B * sizeof(int), b->stream));
+  if (nmat) BCHK(hipMemsetAsync(sg.mat, 0, nmat * sizeof(double), b->stream));
+  return 0;
+}
+
+// What a derivative call hands back, each a (destination, staging, count) with null or 0 skipped, and the wait for the
+// stream.  dev: device-to-device copies.  Otherwise to the host, where the ints arrive as int and are widened to
+// c_int after the wait.
+struct BDOut { void *dst; const void *src; size_t cnt; };
+static c_int bd_deliver(osqp_amd_batch *b, bool dev, std::initializer_list<BDOut> floats, std::initializer_list<BDOut> ints) {
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  for (const BDOut &t : floats)
+    if (t.dst && t.cnt) BCHK(hipMemcpyAsync(t.dst, t.src, t.cnt * sizeof(double), kind, b->stream));
+  size_t total = 0;
+  for (const BDOut &t : ints) if (t.dst) total += t.cnt;
+  std::vector<int> h(dev ? 0 : total);
+  int *hp = h.data();
+  for (const BDOut &t : ints) {
+    if (!t.dst || !t.cnt) continue;
+    BCHK(hipMemcpyAsync(dev ? t.dst : (void *)hp, t.src, t.cnt * sizeof(int), kind, b->stream));
+    if (!dev) hp += t.cnt;
+  }
+  BCHK(hipStreamSynchronize(b->stream));
+  if (dev) return 0;
+  hp = h.data();
+  for (const BDOut &t : ints) {
+    if (!t.dst) continue;
+    for (size_t k = 0; k < t.cnt; k++) static_cast<c_int *>(t.dst)[k] = hp[k];
+    hp += t.cnt;
+  }
+  return 0;
+}
+
+static c_int dev_ptrs_check(const osqp_amd_batch *b, std::initializer_list<const void *> ps);   // batch_devio.h
+
+// adjoint derivatives for the solved members (batch_adjoint.h), ncot cotangents per member: polish's active rows, KKT
+// matrix and inversion on polish's buffers, in the same chunks, one inversion for the ncot cotangents of a member;
+// nothing of the solve state is written.  What the four entry points below share; dev: every array is on the device,
+// dX and dY are read in place.
+static c_int adjoint_call(osqp_amd_batch *b, bool dev, const char *what, c_int ncot, const c_float *dX, const c_float *dY,
+                          c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx, void *active, void *status) {
+  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (ncot < 1 || ncot > 65535) return OSQP_DATA_VALIDATION_ERROR;
+  if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
+  BCHK(hipSetDevice(b->device));
+  if (dev && dev_ptrs_check(b, {dX, dY, dQ, dL, dU, dPx, dAx, active, status})) return OSQP_DATA_VALIDATION_ERROR;
+  const size_t B = (size_t)b->B, D = (size_t)ncot;
+  const size_t n = (size_t)b->n, m = (size_t)b->m, nnzP = (size_t)b->nnzP, nnzA = (size_t)b->nnzA;
+  const size_t nP = dPx ? B * D * nnzP : 0, nA = dAx ? B * D * nnzA : 0;   // only what the call asked for
+  if (!m) dY = nullptr;
+  BPol pl;
+  BAdj ad{};
+  ad.ncot = (int)ncot;
+  if (const c_int rc = bd_stage(b, &pl, dev, {{dX, B * D * n, &ad.gx, false}, {dY, B * D * m, &ad.gy, false}},
+                                B * D * (n + 2 * m), nP + nA)) return rc;
+  ad.dQ = b->bd.out; ad.dL = ad.dQ + B * D * n; ad.dU = ad.dL + B * D * m;
+  ad.dPx = nP ? b->bd.mat : nullptr; ad.dAx = nA ? b->bd.mat + nP : nullptr;
+  ad.active = b->bd.act; ad.stat = b->bd.stat;
+  if (const c_int rc = bd_run(b, pl, what, bd_lds_of, KFN(k_ba_adjoint), [&](const BPlan &pn, unsigned cnt, const int *lp) {
+        hipLaunchKernelGGL(k_ba_adjoint, dim3(cnt, (unsigned)ncot), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
+      })) return rc;
+  return bd_deliver(b, dev, {{dQ, ad.dQ, B * D * n}, {dL, ad.dL, B * D * m}, {dU, ad.dU, B * D * m}, {dPx, ad.dPx, nP}, {dAx, ad.dAx, nA}},
+                    {{active, ad.active, B * m}, {status, ad.stat, B}});
+}
+
+extern "C" c_int osqp_amd_batch_adjoint(osqp_amd_batch *b, const c_float *dX, const c_float *dY,
+                                        c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
+                                        c_int *active, c_int *status_adjoint) {
+  BC_UNSERVED(b, "osqp_amd_batch_adjoint");
+  return adjoint_call(b, false, "adjoint", 1, dX, dY, dQ, dL, dU, dPx, dAx, active, status_adjoint);
+}
+extern "C" c_int osqp_amd_batch_adjoint_dev(osqp_amd_batch *b, const c_float *dX, const c_float *dY,
+                                            c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
+                                            int *active, int *status_adjoint) {
+  BC_UNSERVED(b, "osqp_amd_batch_adjoint_dev");
+  return adjoint_call(b, true, "adjoint", 1, dX, dY, dQ, dL, dU, dPx, dAx, active, status_adjoint);
+}
+extern "C" c_int osqp_amd_batch_adjoint_multi(osqp_amd_batch *b, c_int ncot, const c_float *dX, const c_float *dY,
+                                              c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
+                                              c_int *active, c_int *status_adjoint) {
+  BC_UNSERVED(b, "osqp_amd_batch_adjoint_multi");
+  return adjoint_call(b, false, "adjoint_multi", ncot, dX, dY, dQ, dL, dU, dPx, dAx, active, status_adjoint);
+}
+extern "C" c_int osqp_amd_batch_adjoint_multi_dev(osqp_amd_batch *b, c_int ncot, const c_float *dX, const c_float *dY,
+                                                  c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
+                                                  int *active, int *status_adjoint) {
+  BC_UNSERVED(b, "osqp_amd_batch_adjoint_multi_dev");
+  return adjoint_call(b, true, "adjoint_multi", ncot, dX, dY, dQ, dL, dU, dPx, dAx, active, status_adjoint);
+}
+
+// forward sensitivities for the solved members (batch_tangent.h): the adjoint's route, one inversion for the ndir
+// directions of a member; nothing of the solve state is written.  dev: every array is on the device, the tangents
+// are read in place.
+static c_int tangent_call(osqp_amd_batch *b, bool dev, c_int ndir, const c_float *dQ, const c_float *dL, const c_float *dU,
+                          const c_float *dPx, const c_float *dAx, c_float *dX, c_float *dY, void *active, void *status) {
+  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (ndir < 1 || ndir > 65535 || !dX) return OSQP_DATA_VALIDATION_ERROR;
+  BCHK(hipSetDevice(b->device));
+  if (dev && dev_ptrs_check(b, {dQ, dL, dU, dPx, dAx, dX, dY, active, status})) return OSQP_DATA_VALIDATION_ERROR;
   const size_t B = (size_t)b->B, D = (size_t)ndir;
   const size_t n = (size_t)b->n, m = (size_t)b->m, nnzP = (size_t)b->nnzP, nnzA = (size_t)b->nnzA;
   if (!m) dL = dU = nullptr;
   if (!nnzP) dPx = nullptr;
   if (!nnzA) dAx = nullptr;
-  if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
-  if (balloc_once(b, &b->tan_act, B * m) || balloc_once(b, &b->tan_stat, B) || balloc_once(b, &b->tan_piv, B)) {
-    (void)hipGetLastError();
-    return OSQP_MEM_ALLOC_ERROR;
-  }
-  const size_t nout = std::max((size_t)1, B * D * (n + m));
-  if (tan_reserve(&b->tan_out, &b->tan_out_cap, nout) ||
-      (!dev && tan_reserve(&b->tan_in, &b->tan_in_cap, std::max((size_t)1, B * D * (n + 2 * m)))) ||
-      (!dev && (dPx || dAx) && tan_reserve(&b->tan_mat, &b->tan_mat_cap, B * D * (nnzP + nnzA))))
-    return OSQP_MEM_ALLOC_ERROR;
-  BPol pl = b->pol;          // polish's buffers; its status array stays polish's
-  pl.stat = b->tan_piv;
+  BPol pl;
   BTan tg{};
-  tg.ndir = ndir;
-  tg.dQ = dQ; tg.dL = dL; tg.dU = dU; tg.dPx = dPx; tg.dAx = dAx;
-  if (!dev) {                // (the input staging is the host route's alone)
-    double *vq = b->tan_in, *vl = vq + B * D * n, *vu = vl + B * D * m, *vp = b->tan_mat, *va = vp ? vp + B * D * nnzP : nullptr;
-    const struct { const c_float *src; double *dst; size_t cnt; const double **slot; } in[] = {
-        {dQ, vq, B * D * n, &tg.dQ}, {dL, vl, B * D * m, &tg.dL}, {dU, vu, B * D * m, &tg.dU},
-        {dPx, vp, B * D * nnzP, &tg.dPx}, {dAx, va, B * D * nnzA, &tg.dAx}};
-    for (const auto &t : in) {
-      if (!t.src) continue;
-      BCHK(hipMemcpyAsync(t.dst, t.src, t.cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
-      *t.slot = t.dst;
-    }
-  }
-  tg.dX = b->tan_out; tg.dY = tg.dX + B * D * n;
-  tg.active = b->tan_act; tg.stat = b->tan_stat;
-  // members that are skipped or rejected report zeros
-  BCHK(hipMemsetAsync(b->tan_out, 0, nout * sizeof(double), b->stream));
-  BCHK(hipMemsetAsync(b->tan_act, 0, std::max((size_t)1, B * m) * sizeof(int), b->stream));
-  BCHK(hipMemsetAsync(b->tan_stat, 0, B * sizeof(int), b->stream));
-  if (const c_int rc = bd_run(b, pl, "tangent", bt_lds_of, KFN(k_bt_tangent), [&](const BPlan &pn, unsigned cnt, const int *lp) {
+  tg.ndir = (int)ndir;
+  if (const c_int rc = bd_stage(b, &pl, dev, {{dQ, B * D * n, &tg.dQ, false}, {dL, B * D * m, &tg.dL, false}, {dU, B * D * m, &tg.dU, false},
+                                              {dPx, B * D * nnzP, &tg.dPx, true}, {dAx, B * D * nnzA, &tg.dAx, true}},
+                                B * D * (n + m), 0)) return rc;
+  tg.dX = b->bd.out; tg.dY = tg.dX + B * D * n;
+  tg.active = b->bd.act; tg.stat = b->bd.stat;
+  if (const c_int rc = bd_run(b, pl, "tangent", bd_lds_of, KFN(k_bt_tangent), [&](const BPlan &pn, unsigned cnt, const int *lp) {
         hipLaunchKernelGGL(k_bt_tangent, dim3(cnt, (unsigned)ndir), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, tg, pn.NPOL, b->pol_refine, lp);
       })) return rc;
-  *out = tg;
-  return 0;
+  return bd_deliver(b, dev, {{dX, tg.dX, B * D * n}, {dY, tg.dY, B * D * m}}, {{active, tg.active, B * m}, {status, tg.stat, B}});
 }
 
-// forward sensitivities for the solved members (batch_tangent.h): polish's active rows, KKT matrix and inversion on
-// polish's buffers, in the same chunks, one inversion for the ndir directions of a member; nothing of the solve state
-// is written
 extern "C" c_int osqp_amd_batch_tangent(osqp_amd_batch *b, c_int ndir, const c_float *dQ, const c_float *dL, const c_float *dU,
                                         const c_float *dPx, const c_float *dAx, c_float *dX, c_float *dY,
                                         c_int *active, c_int *status_tangent) {
   BC_UNSERVED(b, "osqp_amd_batch_tangent");
-  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (ndir < 1 || ndir > 65535 || !dX) return OSQP_DATA_VALIDATION_ERROR;
-  BCHK(hipSetDevice(b->device));
-  const size_t B = (size_t)b->B, D = (size_t)ndir;
-  const int n = b->n, m = b->m;
-  BTan tg{};
-  if (const c_int rc = tangent_launch(b, (int)ndir, dQ, dL, dU, dPx, dAx, false, &tg)) return rc;
-  BCHK(hipMemcpyAsync(dX, tg.dX, B * D * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (dY && m) BCHK(hipMemcpyAsync(dY, tg.dY, B * D * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  std::vector<int> ha(active ? B * m : 0), hs(B);
-  if (active && m) BCHK(hipMemcpyAsync(ha.data(), tg.active, B * m * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-  if (status_tangent) BCHK(hipMemcpyAsync(hs.data(), tg.stat, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-  BCHK(hipStreamSynchronize(b->stream));
-  for (size_t k = 0; k < ha.size(); k++) active[k] = ha[k];
-  if (status_tangent) for (size_t q = 0; q < B; q++) status_tangent[q] = hs[q];
-  return 0;
+  return tangent_call(b, false, ndir, dQ, dL, dU, dPx, dAx, dX, dY, active, status_tangent);
+}
+extern "C" c_int osqp_amd_batch_tangent_dev(osqp_amd_batch *b, c_int ndir, const c_float *dQ, const c_float *dL,
+                                            const c_float *dU, const c_float *dPx, const c_float *dAx, c_float *dX,
+                                            c_float *dY, int *active, int *status_tangent) {
+  BC_UNSERVED(b, "osqp_amd_batch_tangent_dev");
+  return tangent_call(b, true, ndir, dQ, dL, dU, dPx, dAx, dX, dY, active, status_tangent);
 }
 
 extern "C" c_int osqp_amd_batch_get(osqp_amd_batch *b, c_float *X, c_float *Y, c_float *info8,

@@ -14,82 +14,16 @@
 //
 // The route is polish's: k_bp_active, k_bp_form and k_bp_invert as they are (the delta-regularised matrix, inverted
 // in place), on the polish buffers with a status array of its own, then
-//   k_ba_adjoint  one workgroup per member: the right-hand side, polish's solve (kkt_solve_refined: the explicit
-//                 inverse, then exactly polish_refine_iter refinement steps against the unregularised M), and the
-//                 unscaled outputs.
-//   k_ba_adjoint_multi  grid (members of the chunk, ncot): k_ba_adjoint for ncot cotangents per member that share
-//                 the one inversion, one workgroup per member and cotangent, the shape of k_bt_tangent's launch.  The
-//                 same expressions in the same order: cotangent d of a member carries the bits k_ba_adjoint gives for
-//                 (dX[:, d], dY[:, d]), whatever ncot, the other cotangents and the chunking are.
+//   k_ba_adjoint  grid (members of the chunk, ncot): one workgroup per member and cotangent, the shape of
+//                 k_bt_tangent's launch, so the ncot cotangents of a member share the one inversion.  The right-hand
+//                 side, polish's solve (kkt_solve_refined: the explicit inverse, then exactly polish_refine_iter
+//                 refinement steps against the unregularised M), and the unscaled outputs.  Cotangent d of a member
+//                 carries the same bits whatever ncot, the other cotangents and the chunking are; the single-cotangent
+//                 entry points are the ncot = 1 call.
 // Nothing of the handle's solve state is written: X, Y, info, the stored
 // iterates, rho, K^-1, flags and polish's status stay bit-equal.  Every output element has one owner: no atomics.
 
 struct BAdj {              // staging of a handle's adjoint call (device pointers)
-  const double *gx, *gy;   // [B][n] dl/dx, [B][m] dl/dy (null = 0)
-  double *dQ, *dL, *dU;    // [B][n], [B][m], [B][m]
-  double *dPx, *dAx;       // [B][nnzP], [B][nnzA]; null = not requested
-  int *active;             // [B][m] -1 active at the lower bound, +1 at the upper, 0 inactive
-};
-
-// LDS of k_ba_adjoint: four vectors of NPOL (solution, residual, correction, right-hand side), x and D, E and y,
-// and the two row maps.
-__host__ __device__ __forceinline__ size_t ba_lds_bytes(int n, int m, int NPOL) {
-  const size_t b = sizeof(double) * (4 * (size_t)NPOL + 2 * (size_t)n + 2 * (size_t)m) + sizeof(int) * 2 * (size_t)m;
-  return (b + 15) & ~(size_t)15;
-}
-
-// pl.stat is the adjoint's status here (1 computed, -1 pivot of the wrong sign, 0 not tried), not polish's.
-__global__ void __launch_bounds__(BP_NT) k_ba_adjoint(BPattern p, BIO io, BPol pl, BAdj ad, int NPOL, int refine_iter,
-                                                      const int *list) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  const long long qp = list[blockIdx.x];
-  if (pl.stat[qp] == -1) return;                 // the inversion met a pivot of the wrong sign: the outputs stay 0
-  const int n = p.n, m = p.m, tid = threadIdx.x;
-  const int mred = pl.mred[qp], nlow = pl.nlow[qp], N = n + mred;
-  const double *Kinv = pl.K + (long long)blockIdx.x * NPOL * NPOL;
-  double *sol = lds, *res = sol + NPOL, *cor = res + NPOL, *g = cor + NPOL;
-  double *x = g + NPOL, *D = x + n, *E = D + n, *y = E + m;
-  int *map = reinterpret_cast<int *>(y + m), *rows = map + m;
-  BL s;
-  slab_view(s, p, io, qp);
-  const double cs = io.Wc[qp], cinv = 1.0 / cs;
-  for (int j = tid; j < n; j += BP_NT) { x[j] = io.Xs[qp * n + j]; D[j] = io.Wd[qp * n + j]; }
-  for (int i = tid; i < m; i += BP_NT) { E[i] = io.We[qp * m + i]; y[i] = io.Ys[qp * m + i]; }
-  load_row_maps(pl, qp, m, mred, map, rows);
-  __syncthreads();
-  // rhs = [D gx; E gy / c on the active rows], zero in the padding
-  for (int k = tid; k < NPOL; k += BP_NT) {
-    double v = 0.0;
-    if (k < n) v = D[k] * ad.gx[qp * n + k];
-    else if (k < N && ad.gy) { const int r = rows[k - n]; v = (E[r] * ad.gy[qp * m + r]) * cinv; }
-    g[k] = v;
-  }
-  __syncthreads();
-  kkt_solve_refined(s, Kinv, NPOL, n, N, map, rows, refine_iter, [g](int k) { return g[k]; }, sol, res, cor);
-  // sol = [rx; rnu] of the scaled problem; the unscaled gradients
-  for (int j = tid; j < n; j += BP_NT) ad.dQ[qp * n + j] = 0.0 - (cs * D[j]) * sol[j];
-  for (int i = tid; i < m; i += BP_NT) {
-    const int a = map[i];
-    const double v = a >= 0 ? E[i] * sol[n + a] : 0.0;
-    ad.dL[qp * m + i] = (a >= 0 && a < nlow) ? v : 0.0;
-    ad.dU[qp * m + i] = a >= nlow ? v : 0.0;
-    if (ad.active) ad.active[qp * m + i] = a < 0 ? 0 : (a < nlow ? -1 : 1);
-  }
-  if (ad.dAx)
-    for (int k = tid; k < p.nnzA; k += BP_NT) {
-      const int i = s.Ai[k], j = s.Ac[k], a = map[i];
-      ad.dAx[qp * p.nnzA + k] = a >= 0 ? 0.0 - (E[i] * D[j]) * (y[i] * sol[j] + sol[n + a] * x[j]) : 0.0;
-    }
-  if (ad.dPx)
-    for (int k = tid; k < p.nnzP; k += BP_NT) {
-      const int i = s.Pi[k], j = s.Pc[k];
-      const double w = i == j ? sol[i] * x[i] : sol[i] * x[j] + sol[j] * x[i];
-      ad.dPx[qp * p.nnzP + k] = 0.0 - ((cs * D[i]) * D[j]) * w;
-    }
-  if (tid == 0) pl.stat[qp] = 1;
-}
-
-struct BAdjM {             // staging of a handle's adjoint_multi call (device pointers)
   const double *gx, *gy;   // [B][ncot][n] dl/dx, [B][ncot][m] dl/dy (null = 0)
   double *dQ, *dL, *dU;    // [B][ncot][n], [B][ncot][m], [B][ncot][m]
   double *dPx, *dAx;       // [B][ncot][nnzP], [B][ncot][nnzA]; null = not requested
@@ -98,31 +32,21 @@ struct BAdjM {             // staging of a handle's adjoint_multi call (device p
   int ncot;
 };
 
-// pl.stat is the pivot verdict of the inversion (0, or -1 from k_bp_invert) and is only read here, as in k_bt_tangent;
-// the status the caller sees is ad.stat, which cotangent 0 of a member alone writes (with `active`): the cotangents
-// of a member neither read what another writes nor write the same word.  LDS: ba_lds_bytes.
-__global__ void __launch_bounds__(BP_NT) k_ba_adjoint_multi(BPattern p, BIO io, BPol pl, BAdjM ad, int NPOL, int refine_iter,
-                                                            const int *list) {
+// Opening, close and LDS as k_bt_tangent (bd_open, bd_close, bd_lds_bytes in batch_polish.h): pl.stat is the pivot
+// verdict of the inversion and is only read here; the status the caller sees is ad.stat.
+__global__ void __launch_bounds__(BP_NT) k_ba_adjoint(BPattern p, BIO io, BPol pl, BAdj ad, int NPOL, int refine_iter,
+                                                      const int *list) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  const long long qp = list[blockIdx.x];
-  const int tid = threadIdx.x;
-  if (pl.stat[qp] == -1) {                       // the inversion met a pivot of the wrong sign: the outputs stay 0
-    if (blockIdx.y == 0 && tid == 0) ad.stat[qp] = -1;
-    return;
-  }
-  const int n = p.n, m = p.m;
-  const int mred = pl.mred[qp], nlow = pl.nlow[qp], N = n + mred;
-  const long long slot = qp * ad.ncot + blockIdx.y;       // this workgroup's (member, cotangent)
-  const double *Kinv = pl.K + (long long)blockIdx.x * NPOL * NPOL;
-  double *sol = lds, *res = sol + NPOL, *cor = res + NPOL, *g = cor + NPOL;
-  double *x = g + NPOL, *D = x + n, *E = D + n, *y = E + m;
-  int *map = reinterpret_cast<int *>(y + m), *rows = map + m;
+  BDView mv;
+  if (!bd_open(p, io, pl, ad.stat, ad.ncot, NPOL, list, lds, mv)) return;
+  const int n = mv.n, m = mv.m, N = mv.N, nlow = mv.nlow, tid = threadIdx.x;
+  const long long slot = mv.slot;                          // this workgroup's (member, cotangent)
+  const double cs = mv.cs, cinv = mv.cinv;
+  const double *x = mv.x, *D = mv.D, *E = mv.E, *y = mv.y;
+  const int *map = mv.map, *rows = mv.rows;
+  double *sol = mv.sol, *g = mv.g;
   BL s;
-  slab_view(s, p, io, qp);
-  const double cs = io.Wc[qp], cinv = 1.0 / cs;
-  for (int j = tid; j < n; j += BP_NT) { x[j] = io.Xs[qp * n + j]; D[j] = io.Wd[qp * n + j]; }
-  for (int i = tid; i < m; i += BP_NT) { E[i] = io.We[qp * m + i]; y[i] = io.Ys[qp * m + i]; }
-  load_row_maps(pl, qp, m, mred, map, rows);
+  slab_view(s, p, io, mv.qp);
   __syncthreads();
   const double *gx = ad.gx + slot * n, *gy = ad.gy ? ad.gy + slot * m : nullptr;
   // rhs = [D gx; E gy / c on the active rows], zero in the padding
@@ -133,7 +57,7 @@ __global__ void __launch_bounds__(BP_NT) k_ba_adjoint_multi(BPattern p, BIO io, 
     g[k] = v;
   }
   __syncthreads();
-  kkt_solve_refined(s, Kinv, NPOL, n, N, map, rows, refine_iter, [g](int k) { return g[k]; }, sol, res, cor);
+  kkt_solve_refined(s, mv.Kinv, NPOL, n, N, map, rows, refine_iter, [g](int k) { return g[k]; }, sol, mv.res, mv.cor);
   // sol = [rx; rnu] of the scaled problem; the unscaled gradients into this cotangent's slices
   for (int j = tid; j < n; j += BP_NT) ad.dQ[slot * n + j] = 0.0 - (cs * D[j]) * sol[j];
   for (int i = tid; i < m; i += BP_NT) {
@@ -141,7 +65,6 @@ __global__ void __launch_bounds__(BP_NT) k_ba_adjoint_multi(BPattern p, BIO io, 
     const double v = a >= 0 ? E[i] * sol[n + a] : 0.0;
     ad.dL[slot * m + i] = (a >= 0 && a < nlow) ? v : 0.0;
     ad.dU[slot * m + i] = a >= nlow ? v : 0.0;
-    if (blockIdx.y == 0) ad.active[qp * m + i] = a < 0 ? 0 : (a < nlow ? -1 : 1);
   }
   if (ad.dAx)
     for (int k = tid; k < p.nnzA; k += BP_NT) {
@@ -154,5 +77,5 @@ __global__ void __launch_bounds__(BP_NT) k_ba_adjoint_multi(BPattern p, BIO io, 
       const double w = i == j ? sol[i] * x[i] : sol[i] * x[j] + sol[j] * x[i];
       ad.dPx[slot * p.nnzP + k] = 0.0 - ((cs * D[i]) * D[j]) * w;
     }
-  if (blockIdx.y == 0 && tid == 0) ad.stat[qp] = 1;
+  bd_close(mv, ad.active, ad.stat);
 }

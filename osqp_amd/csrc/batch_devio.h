@@ -7,6 +7,8 @@
 //   k_batch_stage_bounds   writes the clamped bounds into the raw l, u of the handle (what setup read and matrix
 //                          updates re-read), where k_batch_update, unchanged, then finds them.
 // Everything else is a device-to-device copy or an existing kernel reading the caller's array in place.
+// The _dev twins of adjoint, adjoint_multi and tangent are not here: each shares one body with its host twin in
+// batch.hip (adjoint_call, tangent_call), which asks dev_ptrs_check below.
 //
 // Every non-NULL device pointer of a call passes dev_ptr_check before any copy or launch.  The calls run on the
 // handle's stream and return with it synchronised; no stream or event of the caller's crosses the ABI, so the
@@ -157,70 +159,6 @@ extern "C" c_int osqp_amd_batch_warm_start_dev(osqp_amd_batch *b, const c_float 
 template <typename Tp>
 static hipError_t give(osqp_amd_batch *b, Tp *dst, const Tp *src, size_t cnt) {
   return (dst && cnt) ? hipMemcpyAsync(dst, src, cnt * sizeof(Tp), hipMemcpyDeviceToDevice, b->stream) : hipSuccess;
-}
-
-extern "C" c_int osqp_amd_batch_adjoint_dev(osqp_amd_batch *b, const c_float *dX, const c_float *dY,
-                                            c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
-                                            int *active, int *status_adjoint) {
-  BC_UNSERVED(b, "osqp_amd_batch_adjoint_dev");
-  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
-  BCHK(hipSetDevice(b->device));
-  if (dev_ptrs_check(b, {dX, dY, dQ, dL, dU, dPx, dAx, active, status_adjoint})) return OSQP_DATA_VALIDATION_ERROR;
-  const size_t B = (size_t)b->B, n = (size_t)b->n, m = (size_t)b->m;
-  BAdj ad{};
-  if (const c_int rc = adjoint_launch(b, dX, dY, true, dPx != nullptr, dAx != nullptr, &ad)) return rc;
-  BCHK(give(b, dQ, ad.dQ, B * n));
-  BCHK(give(b, dL, ad.dL, B * m));
-  BCHK(give(b, dU, ad.dU, B * m));
-  BCHK(give(b, dPx, ad.dPx, B * b->nnzP));
-  BCHK(give(b, dAx, ad.dAx, B * b->nnzA));
-  BCHK(give(b, active, ad.active, B * m));
-  BCHK(give(b, status_adjoint, b->adj_stat, B));
-  BCHK(hipStreamSynchronize(b->stream));
-  return 0;
-}
-
-extern "C" c_int osqp_amd_batch_adjoint_multi_dev(osqp_amd_batch *b, c_int ncot, const c_float *dX, const c_float *dY,
-                                                  c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx,
-                                                  int *active, int *status_adjoint) {
-  BC_UNSERVED(b, "osqp_amd_batch_adjoint_multi_dev");
-  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (ncot < 1 || ncot > 65535) return OSQP_DATA_VALIDATION_ERROR;
-  if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
-  BCHK(hipSetDevice(b->device));
-  if (dev_ptrs_check(b, {dX, dY, dQ, dL, dU, dPx, dAx, active, status_adjoint})) return OSQP_DATA_VALIDATION_ERROR;
-  const size_t B = (size_t)b->B, D = (size_t)ncot, n = (size_t)b->n, m = (size_t)b->m;
-  BAdjM ad{};
-  if (const c_int rc = adjoint_multi_launch(b, (int)ncot, dX, dY, true, dPx != nullptr, dAx != nullptr, &ad)) return rc;
-  BCHK(give(b, dQ, (const double *)ad.dQ, B * D * n));
-  BCHK(give(b, dL, (const double *)ad.dL, B * D * m));
-  BCHK(give(b, dU, (const double *)ad.dU, B * D * m));
-  BCHK(give(b, dPx, (const double *)ad.dPx, B * D * b->nnzP));
-  BCHK(give(b, dAx, (const double *)ad.dAx, B * D * b->nnzA));
-  BCHK(give(b, active, (const int *)ad.active, B * m));
-  BCHK(give(b, status_adjoint, (const int *)ad.stat, B));
-  BCHK(hipStreamSynchronize(b->stream));
-  return 0;
-}
-
-extern "C" c_int osqp_amd_batch_tangent_dev(osqp_amd_batch *b, c_int ndir, const c_float *dQ, const c_float *dL,
-                                            const c_float *dU, const c_float *dPx, const c_float *dAx, c_float *dX,
-                                            c_float *dY, int *active, int *status_tangent) {
-  BC_UNSERVED(b, "osqp_amd_batch_tangent_dev");
-  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (ndir < 1 || ndir > 65535 || !dX) return OSQP_DATA_VALIDATION_ERROR;
-  BCHK(hipSetDevice(b->device));
-  if (dev_ptrs_check(b, {dQ, dL, dU, dPx, dAx, dX, dY, active, status_tangent})) return OSQP_DATA_VALIDATION_ERROR;
-  const size_t B = (size_t)b->B, D = (size_t)ndir, n = (size_t)b->n, m = (size_t)b->m;
-  BTan tg{};
-  if (const c_int rc = tangent_launch(b, (int)ndir, dQ, dL, dU, dPx, dAx, true, &tg)) return rc;
-  BCHK(give(b, dX, (const double *)tg.dX, B * D * n));
-  BCHK(give(b, dY, (const double *)tg.dY, B * D * m));
-  BCHK(give(b, active, (const int *)tg.active, B * m));
-  BCHK(give(b, status_tangent, (const int *)tg.stat, B));
-  BCHK(hipStreamSynchronize(b->stream));
-  return 0;
 }
 
 extern "C" c_int osqp_amd_batch_get_dev(osqp_amd_batch *b, c_float *X, c_float *Y, c_float *info8,

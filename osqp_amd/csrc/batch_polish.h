@@ -18,8 +18,10 @@
 //                positive pivots, then mred negative ones; a pivot of the wrong sign (zero and NaN included)
 //                rejects the member's polish;
 //   k_bp_polish  one workgroup per member: everything after the inversion.
-// The adjoint (batch_adjoint.h) runs the same route with another right-hand side and shares its pieces: the three
-// kernels above, load_row_maps and kkt_solve_refined.
+// The adjoint and the tangent (batch_adjoint.h, batch_tangent.h) run the same route with other right-hand sides and
+// share its pieces: the three kernels above, load_row_maps and kkt_solve_refined.  What those two kernels have in
+// common beyond that -- opening, close and LDS layout -- is bd_open, bd_close and bd_lds_bytes below; k_bp_polish's
+// layout and tail differ and stay its own.
 // An accepted member's X, Y, info8[2..4] and scaled iterates are overwritten; of a rejected or skipped
 // member nothing is written but its status_polish.  rho, K^-1, io.flag, the row classes and rho_updates are
 // never touched.
@@ -158,6 +160,65 @@ __device__ __forceinline__ void kkt_solve_refined(const BL &s, const double *Kin
     for (int k = tid; k < N; k += BP_NT) sol[k] += cor[k];
     __syncthreads();
   }
+}
+
+// What k_ba_adjoint and k_bt_tangent hold of their workgroup's member once bd_open has run: its scalars and the
+// carve-up of the LDS (bd_lds_bytes).  The member's slab_view stays a local of the kernel: held in here it cost the
+// two kernels some 25 VGPRs.
+struct BDView {
+  long long qp, slot;      // the member; its slice blockIdx.y of the call's [B][slices][.] arrays
+  int n, m, nlow, N;       // nlow of the N - n active rows sit at their lower bound
+  double cs, cinv;         // the member's cost scaling c and 1 / c
+  const double *Kinv;      // the inverse of the regularised KKT matrix, slot blockIdx.x of the chunk
+  double *sol, *res, *cor, *g;   // NPOL each: solution, residual, correction, right-hand side
+  double *x, *D, *E, *y;   // n, n, m, m: the stored scaled iterates and the scaling
+  int *map, *rows;         // m each (load_row_maps)
+};
+
+// LDS of k_ba_adjoint and k_bt_tangent: four vectors of NPOL (solution, residual, correction, right-hand side), x and
+// D, E and y, and the two row maps.
+__host__ __device__ __forceinline__ size_t bd_lds_bytes(int n, int m, int NPOL) {
+  const size_t b = sizeof(double) * (4 * (size_t)NPOL + 2 * (size_t)n + 2 * (size_t)m) + sizeof(int) * 2 * (size_t)m;
+  return (b + 15) & ~(size_t)15;
+}
+
+// The opening of a derivative kernel, grid (members of the chunk, slices).  pl.stat is the pivot verdict of the call's
+// inversion (0, or -1 from k_bp_invert) and is only read; stat is the status the caller sees.  False (for the whole
+// workgroup): the inversion met a pivot of the wrong sign, slice 0 has reported -1 and the outputs stay 0.  True: v is
+// filled and x, D, E, y and the row maps are on their way into LDS (visible after the next barrier).
+__device__ __forceinline__ bool bd_open(const BPattern &p, const BIO &io, const BPol &pl, int *stat, int slices, int NPOL,
+                                        const int *list, double *lds, BDView &v) {
+  const long long qp = list[blockIdx.x];
+  const int tid = threadIdx.x;
+  if (pl.stat[qp] == -1) {
+    if (blockIdx.y == 0 && tid == 0) stat[qp] = -1;
+    return false;
+  }
+  const int n = p.n, m = p.m;
+  const int mred = pl.mred[qp];
+  v.qp = qp; v.slot = qp * slices + blockIdx.y;
+  v.n = n; v.m = m; v.nlow = pl.nlow[qp]; v.N = n + mred;
+  v.Kinv = pl.K + (long long)blockIdx.x * NPOL * NPOL;
+  v.sol = lds; v.res = v.sol + NPOL; v.cor = v.res + NPOL; v.g = v.cor + NPOL;
+  v.x = v.g + NPOL; v.D = v.x + n; v.E = v.D + n; v.y = v.E + m;
+  v.map = reinterpret_cast<int *>(v.y + m); v.rows = v.map + m;
+  v.cs = io.Wc[qp]; v.cinv = 1.0 / v.cs;
+  for (int j = tid; j < n; j += BP_NT) { v.x[j] = io.Xs[qp * n + j]; v.D[j] = io.Wd[qp * n + j]; }
+  for (int i = tid; i < m; i += BP_NT) { v.E[i] = io.We[qp * m + i]; v.y[i] = io.Ys[qp * m + i]; }
+  load_row_maps(pl, qp, m, mred, v.map, v.rows);
+  return true;
+}
+
+// The close of a derivative kernel: slice 0 of a member alone writes what is per member, `active` (-1 active at the
+// lower bound, +1 at the upper, 0 inactive) and the status, so the slices of a member neither read what another
+// writes nor write the same word.
+__device__ __forceinline__ void bd_close(const BDView &v, int *active, int *stat) {
+  if (blockIdx.y != 0) return;
+  for (int i = threadIdx.x; i < v.m; i += BP_NT) {
+    const int a = v.map[i];
+    active[v.qp * v.m + i] = a < 0 ? 0 : (a < v.nlow ? -1 : 1);
+  }
+  if (threadIdx.x == 0) stat[v.qp] = 1;
 }
 
 // LDS of k_bp_polish: three vectors of NPOL (solution, residual, correction), q, D, five m-vectors (l, u, E, z, y),

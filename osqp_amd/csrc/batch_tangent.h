@@ -36,38 +36,21 @@ struct BTan {              // staging of a handle's tangent call (device pointer
   int ndir;
 };
 
-// LDS of k_bt_tangent: four vectors of NPOL (solution, residual, correction, right-hand side), x and D, E and y,
-// and the two row maps.
-__host__ __device__ __forceinline__ size_t bt_lds_bytes(int n, int m, int NPOL) {
-  const size_t b = sizeof(double) * (4 * (size_t)NPOL + 2 * (size_t)n + 2 * (size_t)m) + sizeof(int) * 2 * (size_t)m;
-  return (b + 15) & ~(size_t)15;
-}
-
-// pl.stat is the pivot verdict of this call's inversion (0, or -1 from k_bp_invert) and is only read here; the
-// status the caller sees is tg.stat, which direction 0 of a member alone writes (with `active`): the directions of
-// a member neither read what another writes nor write the same word.
+// Opening, close and LDS as k_ba_adjoint (bd_open, bd_close, bd_lds_bytes in batch_polish.h): pl.stat is the pivot
+// verdict of this call's inversion and is only read here; the status the caller sees is tg.stat.
 __global__ void __launch_bounds__(BP_NT) k_bt_tangent(BPattern p, BIO io, BPol pl, BTan tg, int NPOL, int refine_iter,
                                                       const int *list) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  const long long qp = list[blockIdx.x];
-  const int tid = threadIdx.x;
-  if (pl.stat[qp] == -1) {                       // the inversion met a pivot of the wrong sign: the outputs stay 0
-    if (blockIdx.y == 0 && tid == 0) tg.stat[qp] = -1;
-    return;
-  }
-  const int n = p.n, m = p.m;
-  const int mred = pl.mred[qp], nlow = pl.nlow[qp], N = n + mred;
-  const long long slot = qp * tg.ndir + blockIdx.y;       // this workgroup's (member, direction)
-  const double *Kinv = pl.K + (long long)blockIdx.x * NPOL * NPOL;
-  double *sol = lds, *res = sol + NPOL, *cor = res + NPOL, *g = cor + NPOL;
-  double *x = g + NPOL, *D = x + n, *E = D + n, *y = E + m;
-  int *map = reinterpret_cast<int *>(y + m), *rows = map + m;
+  BDView mv;
+  if (!bd_open(p, io, pl, tg.stat, tg.ndir, NPOL, list, lds, mv)) return;
+  const int n = mv.n, m = mv.m, N = mv.N, nlow = mv.nlow, tid = threadIdx.x;
+  const long long slot = mv.slot;                         // this workgroup's (member, direction)
+  const double cs = mv.cs, cinv = mv.cinv;
+  const double *x = mv.x, *D = mv.D, *E = mv.E, *y = mv.y;
+  const int *map = mv.map, *rows = mv.rows;
+  double *sol = mv.sol, *g = mv.g;
   BL s;
-  slab_view(s, p, io, qp);
-  const double cs = io.Wc[qp], cinv = 1.0 / cs;
-  for (int j = tid; j < n; j += BP_NT) { x[j] = io.Xs[qp * n + j]; D[j] = io.Wd[qp * n + j]; }
-  for (int i = tid; i < m; i += BP_NT) { E[i] = io.We[qp * m + i]; y[i] = io.Ys[qp * m + i]; }
-  load_row_maps(pl, qp, m, mred, map, rows);
+  slab_view(s, p, io, mv.qp);
   __syncthreads();
   const double *dq = tg.dQ ? tg.dQ + slot * n : nullptr;
   const double *dl = tg.dL ? tg.dL + slot * m : nullptr, *du = tg.dU ? tg.dU + slot * m : nullptr;
@@ -98,13 +81,12 @@ __global__ void __launch_bounds__(BP_NT) k_bt_tangent(BPattern p, BIO io, BPol p
     g[k] = v;
   }
   __syncthreads();
-  kkt_solve_refined(s, Kinv, NPOL, n, N, map, rows, refine_iter, [g](int k) { return g[k]; }, sol, res, cor);
+  kkt_solve_refined(s, mv.Kinv, NPOL, n, N, map, rows, refine_iter, [g](int k) { return g[k]; }, sol, mv.res, mv.cor);
   // sol = [dx~; dnu~] of the scaled problem; the unscaled tangents
   for (int j = tid; j < n; j += BP_NT) tg.dX[slot * n + j] = D[j] * sol[j];
   for (int i = tid; i < m; i += BP_NT) {
     const int a = map[i];
     tg.dY[slot * m + i] = a >= 0 ? (E[i] * sol[n + a]) * cinv : 0.0;
-    if (blockIdx.y == 0) tg.active[qp * m + i] = a < 0 ? 0 : (a < nlow ? -1 : 1);
   }
-  if (blockIdx.y == 0 && tid == 0) tg.stat[qp] = 1;
+  bd_close(mv, tg.active, tg.stat);
 }

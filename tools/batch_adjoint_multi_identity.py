@@ -1,8 +1,9 @@
 """adjoint() and tangent() of the batch engines, bit for bit, between two builds (the kept KKT inversion and the shared
 runner around the three derivative kernels must not move a bit of the existing entry points): on the shapes of
 tests/test_gpu_batch_adjoint.py (TILED_SHAPES on the tiled engine, STREAMED_SHAPES on the streamed one, M0_SHAPE on both),
-solve -> polish -> adjoint(dX, dY, matrices=True) -> tangent(D = 1, all five tangents) -> tangent(D = 3) -> adjoint again;
-the five gradients, dx, dy, active and the statuses are recorded.
+solve -> polish -> adjoint(dX, dY, matrices=True) -> tangent(D = 1, all five tangents) -> tangent(D = 3) -> adjoint again ->
+adjoint with [B, 3, .] cotangents (matrices=True) -> adjoint with its [B, 1, .] slice 1; the five gradients, dx, dy, active and
+the statuses are recorded.
   python tools/batch_adjoint_multi_identity.py --tree DIR --dump a.npz     (one process per built tree; DIR defaults to this one)
   python tools/batch_adjoint_multi_identity.py --compare a.npz b.npz"""
 import argparse
@@ -35,12 +36,17 @@ def dump(tree, out):
             t1 = h.tangent(**{k: np.ascontiguousarray(v[:, 0]) for k, v in tan.items()})
             t3 = h.tangent(**tan)
             a2 = h.adjoint(dX, dY, matrices=True)
+            dX3, dY3 = rng.standard_normal((B, 3, n)), rng.standard_normal((B, 3, m))
+            a3 = h.adjoint(dX3, dY3, matrices=True)
+            a31 = h.adjoint(np.ascontiguousarray(dX3[:, 1:2]), np.ascontiguousarray(dY3[:, 1:2]), matrices=True)
             key = "%s %s" % (engine, shape)
             rec[key + " x"], rec[key + " status_polish"] = r.x, r.status_polish
             for tag, res, names in (("adjoint", a, ("dq", "dl", "du", "dPx", "dAx", "active", "status_adjoint")),
                                     ("tangent1", t1, ("dx", "dy", "active", "status_tangent")),
                                     ("tangent3", t3, ("dx", "dy", "active", "status_tangent")),
-                                    ("adjoint again", a2, ("dq", "dl", "du", "dPx", "dAx", "active", "status_adjoint"))):
+                                    ("adjoint again", a2, ("dq", "dl", "du", "dPx", "dAx", "active", "status_adjoint")),
+                                    ("adjoint3", a3, ("dq", "dl", "du", "dPx", "dAx", "active", "status_adjoint")),
+                                    ("adjoint3 slice", a31, ("dq", "dl", "du", "dPx", "dAx", "active", "status_adjoint"))):
                 for k in names:
                     rec["%s %s %s" % (key, tag, k)] = getattr(res, k)
             h.cleanup()
