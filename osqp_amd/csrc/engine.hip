@@ -3764,8 +3764,13 @@ static void refresh_operator(hipeng *e) {
 // The PCG start vector history is void (cold/warm start from the host, new rho, new matrices):
 // start from [x~ | rho z~] as it stands and extrapolate again once a few iterations are on record.
 static int reset_start(hipeng *e) {
-  if (e->c.vx != e->c.va)
+  if (e->c.vx != e->c.va) {
     HIPCHK(hipMemcpyAsync(e->c.vx, e->c.va, (size_t)std::max(1, e->n + e->m) * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    // ... and the "previous" vector with it: what vold held was formed with the rho and A from before the call, so a schedule that
+    // extrapolates at the first k_admm_finalize after a reset (OSQP_AMD_EXTRAP_SCHED with ex_h0 <= 1) would mix two operators into
+    // the m-part of the next start vector.  The default schedule multiplies that difference by theta = 0 and is not changed by this.
+    HIPCHK(hipMemcpyAsync(e->c.vold, e->c.va, (size_t)std::max(1, e->n + e->m) * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+  }
   HIPCHK(hipMemsetAsync(&e->c.st->hist_r, 0, sizeof(int), e->stream));
   return 0;
 }

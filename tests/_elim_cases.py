@@ -131,15 +131,19 @@ def rhs(pb, sigma, rho, x, z, y):
     return b + pb.AT @ (np.asarray(rho, float).astype(LD) * z - y) if pb.m else b
 
 
-def xtilde_bars(pb, red, erow, rho, pcg_eps_rel, xt, norm_xt, base_abs, vbn_abs):
+def xtilde_bars(pb, red, erow, rho, pcg_eps_rel, xt, norm_xt, base_abs, vbn_abs, direct_err=None):
     """(bxt, per-variable bar on x~, per-row bar on z~) of one linear solve on the reduced system, as step_bars_elim derives them;
-    base_abs [n]: |sigma x| + |q| (a plugin solve: |b1|), vbn_abs [m]: |rho z| + |y| (a plugin solve: |rho b2|)."""
+    base_abs [n]: |sigma x| + |q| (a plugin solve: |b1|), vbn_abs [m]: |rho z| + |y| (a plugin solve: |rho b2|).  direct_err: the
+    2-norm error of an unrefined float64 LU solve of the same system -- the direct forms' term 10 x direct_err of
+    _engine_reference.step_bars then stands in place of the PCG term."""
     erow = np.asarray(erow)
     rho = np.asarray(rho, float)
     X, Y = red["X"], red["Y"]
     assert red["lam_min"] > 0.0, red["lam_min"]
     nb = float(np.sqrt((red["bX"] * red["bX"]).sum())) if X.size else 0.0
     bxt = (pcg_eps_rel * nb / red["lam_min"] if X.size else 0.0) + 50 * U * norm_xt
+    if direct_err is not None:
+        bxt = 10.0 * direct_err + 50 * U * norm_xt
     mask = np.zeros(pb.n)
     mask[X] = 1.0
     a1X = np.asarray(pb.Aa @ mask.astype(LD)).astype(float) if pb.m else np.zeros(0)
@@ -156,7 +160,7 @@ def xtilde_bars(pb, red, erow, rho, pcg_eps_rel, xt, norm_xt, base_abs, vbn_abs)
     return bxt, bar_xt, bar_zt
 
 
-def step_bars_elim(pb, st, red, erow, sigma, alpha, rho, pcg_eps_rel, x, z, y):
+def step_bars_elim(pb, st, red, erow, sigma, alpha, rho, pcg_eps_rel, x, z, y, direct=False):
     """Bars of x+, z+, y+ per element for a step whose linear solve ran on the reduced system.
 
     The engine stops on ||r||_2 <= pcg_eps_rel ||b||_2 of the system it iterates: k_pcg_init sums pbb += bj * bj with bj = 0 on
@@ -172,10 +176,12 @@ def step_bars_elim(pb, st, red, erow, sigma, alpha, rho, pcg_eps_rel, x, z, y):
     most 4 before the subtraction).
     z~_i = zt + a x~_y then carries ||A_iX||_1 bxt + |a| err(x~_y) (+ one more rounding of |a x~_y|), and x+, z+, y+ follow as in
     _engine_reference.step_bars: alpha times the bar for x, alpha times that of z~_i for z, rho_i times that for y, each plus the
-    rounding of its own update formula (st['rnd_*']).  Nothing here is tuned on device output."""
+    rounding of its own update formula (st['rnd_*']).  direct: the engine applied an explicit inverse (dense-direct form) -- the
+    direct term of _engine_reference.step_bars in place of the PCG term.  Nothing here is tuned on device output."""
     xa, za, ya, qa = (np.abs(np.asarray(v, dtype=float)) for v in (x, z, y, pb.q))
     rho = np.asarray(rho, float)
-    bxt, bar_xt, bar_zt = xtilde_bars(pb, red, erow, rho, pcg_eps_rel, st["x_tilde"], st["norm_xt"], sigma * xa + qa, rho * za + ya)
+    bxt, bar_xt, bar_zt = xtilde_bars(pb, red, erow, rho, pcg_eps_rel, st["x_tilde"], st["norm_xt"], sigma * xa + qa, rho * za + ya,
+                                       st["plain_err"] if direct else None)
     al = abs(alpha)
     return dict(x_tilde=bxt, x_tilde_each=bar_xt, x=al * bar_xt + st["rnd_x"].astype(float),
                 z=al * bar_zt + st["rnd_z"].astype(float), y=rho * al * bar_zt + st["rnd_y"].astype(float))

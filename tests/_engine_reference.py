@@ -253,9 +253,11 @@ class _DenseKKT:
 DENSE_MAX = 3000
 
 
-def admm_step(pb, sigma, alpha, rho, x, z, y):
+def admm_step(pb, sigma, alpha, rho, x, z, y, reuse=None):
     """One ADMM iteration from (x, z, y):  K x~ = sigma x - q + A'(rho z - y), K = P + sigma I + A' rho A (a float64 LU solve --
     dense up to DENSE_MAX variables, sparse above -- with one refinement step whose residual is formed in long double),
+    `reuse`: a dict the caller keeps while pb's matrices, rho and sigma are unchanged; the factorisation and lam_min are stored in
+    it by the first call and taken from it by the later ones (the same objects: the results do not change).
     z~ = A x~;  x+ = alpha x~ + (1 - alpha) x;  z+ = clip(alpha z~ + (1 - alpha) z + y / rho, l, u);
     y+ = y + rho (alpha z~ + (1 - alpha) z - z+).  Returns a dict of the long-double x_tilde, x, z, y, dx, dy, v (the unclipped z+),
     lam_min of K, norm_b (2-norm of the right-hand side), plain_err (2-norm error of the unrefined float64 solve) and the rounding
@@ -264,7 +266,13 @@ def admm_step(pb, sigma, alpha, rho, x, z, y):
     x, z, y = (np.asarray(v, dtype=LD) for v in (x, z, y))
     rho = np.asarray(rho, dtype=float)
     rl, sg, al = rho.astype(LD), LD(sigma), LD(alpha)
-    kkt = (_DenseKKT if n <= DENSE_MAX else _SparseKKT)(pb, float(sigma), rho)
+    if reuse is not None and "kkt" in reuse:
+        kkt, lam_min = reuse["kkt"], reuse["lam_min"]
+    else:
+        kkt = (_DenseKKT if n <= DENSE_MAX else _SparseKKT)(pb, float(sigma), rho)
+        lam_min = kkt.lam_min()
+        if reuse is not None:
+            reuse["kkt"], reuse["lam_min"] = kkt, lam_min
 
     def K(v):
         out = pb.P @ v + sg * v
@@ -284,7 +292,7 @@ def admm_step(pb, sigma, alpha, rho, x, z, y):
     dy = rl * (w - zn)
     rowlen = np.diff(pb.A.indptr) if m else np.zeros(0)
     rnd_z = U * ((rowlen + 4) * np.abs(al) * zta + 4 * (np.abs((1 - al) * z) + np.abs(y / rl)))
-    return dict(x_tilde=xt, x=xn, z=zn, y=y + dy, dx=xn - x, dy=dy, v=v, lam_min=kkt.lam_min(),
+    return dict(x_tilde=xt, x=xn, z=zn, y=y + dy, dx=xn - x, dy=dy, v=v, lam_min=lam_min,
                 norm_b=float(np.sqrt((b * b).sum())), plain_err=float(np.sqrt(((plain - xt) ** 2).sum())),
                 norm_xt=float(np.sqrt((xt * xt).sum())),
                 rnd_x=4 * U * (np.abs(al * xt) + np.abs((1 - al) * x)), rnd_z=rnd_z,
