@@ -79,13 +79,38 @@ c_int osqp_amd_batch_setup_engine(osqp_amd_batch **out, c_int engine, c_int batc
  * OSQP_NONCVX_ERROR when K is not positive definite.
  * Served: _update, _warm_start, _update_rho, _solve, _get, _device_ptrs, _shape, _rounds, _cleanup, _update_dev,
  * _warm_start_dev, _get_dev, _check_dev_ptr, _member (the common D, E, c, rho, classes, Pv, Av and the one K^-1,
- * NP x NP, for any qp).  Not served: _update_matrices(_dev), _polish, _polish_status_dev, _adjoint*, _tangent*,
- * _kkt_info: each returns OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line naming the engine and leaves the handle
+ * NP x NP, for any qp).  Served once osqp_amd_batch_common_kkt(b, 1) has built the shared KKT pieces, and refused
+ * without them: _polish, _polish_status_dev, _adjoint*, _tangent*, _kkt_info.  Never served: _update_matrices(_dev).
+ * A refused call returns OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line naming the engine and leaves the handle
  * untouched and usable. */
 #define OSQP_AMD_BATCH_COMMON 2   /* what osqp_amd_batch_shape reports for such a handle; setup_engine does not take it */
 c_int osqp_amd_batch_setup_common(osqp_amd_batch **out, c_int batch, const csc *P, const csc *A,
                                   const c_float *Q, const c_float *L, const c_float *U,
                                   const OSQPSettings *settings, c_int device);
+/* Polish, adjoint and tangent of a common-K handle, on a shared Hessian inverse.  The (1,1) block of the regularised
+ * KKT matrix [P~ + delta I, Ar'; Ar, -delta I] (P~, A~: the handle's scaled values) is the same for every member and
+ * for the handle's life, so the calls below eliminate it once: H = (P~ + delta I)^-1, Wt = A~ H, and per member only
+ * S = Ar H Ar' + delta I of order mred is formed and inverted; t = H g1, nu = S^-1 (Ar t - g2), x = t - Wt[rows]' nu
+ * is the same regularised solve, followed by the same polish_refine_iter refinement steps against [P, Ar'; Ar, 0].
+ * on = 1: build (once; a second call is a no-op returning 0) the shared KKT pieces of a common-K handle -- H = (P~ + delta I)^-1,
+ * NP x NP, and Wt = A~ H, m x NP -- with delta as given at setup; from then on osqp_amd_batch_polish, _polish_status_dev,
+ * _adjoint, _adjoint_multi, _tangent, their _dev twins and _kkt_info are served on the handle, with the semantics, statuses and
+ * return codes written below for the other engines.  on = 0: free them; the calls are refused again as before.
+ * Returns 0; OSQP_LINSYS_SOLVER_INIT_ERROR (stderr line) for a handle of another engine; OSQP_NONCVX_ERROR when a pivot of
+ * P~ + delta I is not positive (nothing is kept, the handle stays usable for solves); OSQP_MEM_ALLOC_ERROR likewise;
+ * OSQP_WORKSPACE_NOT_INIT_ERROR for NULL; -102 when a HIP call fails: nothing is kept
+ * then either.  Solves, updates and warm starts neither read nor invalidate H and Wt.
+ * On such a handle the KKT buffer holds NS x NS doubles per member, NS = the largest number of active rows in the batch
+ * rounded up to 32 (at least 32); osqp_amd_batch_kkt_info reports out[0] = passes of formation and inversion of the
+ * members' S (H does not count), out[2] = NS, out[3] = the members kept.  The limits n + active rows <= 2176 and
+ * 160 KiB of LDS hold as for the other engines.  Either switch drops a kept inversion. */
+c_int osqp_amd_batch_common_kkt(osqp_amd_batch *b, c_int on);
+/* For the tests: H [NP*NP], Wt [m*NP] (NULL = skip), and of member qp of the inversion currently kept (osqp_amd_batch_kkt_info
+ * out[1] = 1): mred, NS and Sinv [NS*NS] as stored (each NULL = skip).  OSQP_WORKSPACE_NOT_INIT_ERROR for NULL, for a
+ * handle without the pieces, and when nothing is kept and something of a member is asked for;
+ * OSQP_DATA_VALIDATION_ERROR for a qp outside the batch or one whose last solve did not end OSQP_SOLVED; -102 when a
+ * HIP call fails. */
+c_int osqp_amd_batch_common_kkt_peek(osqp_amd_batch *b, c_float *H, c_float *Wt, c_int qp, c_int *mred, c_int *NS, c_float *Sinv);
 /* The engine of a handle and the padded order NP of its K^-1 (the Kinv buffer of osqp_amd_batch_member is
  * NP x NP).  NULL = skip. */
 c_int osqp_amd_batch_shape(osqp_amd_batch *b, c_int *engine, c_int *NP);

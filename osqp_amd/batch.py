@@ -57,6 +57,10 @@ def _bind(L):
     L.osqp_amd_batch_setup_common.argtypes = [C.POINTER(H), abi.c_int, C.POINTER(abi.csc), C.POINTER(abi.csc),
                                               abi.c_float_p, abi.c_float_p, abi.c_float_p,
                                               C.POINTER(abi.OSQPSettings), abi.c_int]
+    L.osqp_amd_batch_common_kkt.restype = abi.c_int
+    L.osqp_amd_batch_common_kkt.argtypes = [H, abi.c_int]
+    L.osqp_amd_batch_common_kkt_peek.restype = abi.c_int
+    L.osqp_amd_batch_common_kkt_peek.argtypes = [H, abi.c_float_p, abi.c_float_p, abi.c_int, abi.c_int_p, abi.c_int_p, abi.c_float_p]
     L.osqp_amd_batch_shape.restype = abi.c_int
     L.osqp_amd_batch_shape.argtypes = [H, abi.c_int_p, abi.c_int_p]
     L.osqp_amd_batch_rounds.restype = abi.c_int
@@ -243,20 +247,26 @@ class BatchOSQP:
         self._h = None
         self._status_polish = None
 
-    def setup(self, P, A, Q, L, U, Px_all=None, Ax_all=None, device=None, engine="auto", **settings):
+    def setup(self, P, A, Q, L, U, Px_all=None, Ax_all=None, device=None, engine="auto", shared_kkt=False, **settings):
         """P (n x n, any triangle content; upper triangle is used), A (m x n): shared
         pattern/values.  Q [B, n], L, U [B, m].  Px_all / Ax_all [B, nnz] optional
         per-QP values in CSC order of triu(P) / A.  engine: "auto" (the register-tiled kernel for
         n <= 128, one single-QP engine per member above) or "streamed" (the streamed-inverse batch
         engine, K^-1 in HBM, any n <= 1024) or "common" (the common-K engine: one model, many right-hand sides --
         the members share P, A, one scaling, one class per row and one rho, so one K^-1 serves the batch and an ADMM
-        iteration is one GEMM; no Px_all / Ax_all, n <= 1024; see include/osqp_amd_batch.h)."""
+        iteration is one GEMM; no Px_all / Ax_all, n <= 1024; see include/osqp_amd_batch.h).  shared_kkt=True
+        (engine="common" only): build the shared KKT pieces after setup (shared_kkt()), so that polish, adjoint and
+        tangent are served on the handle."""
         from . import engine_options
         if engine not in ("auto", "streamed", "common"):
             raise ValueError("engine must be 'auto', 'streamed' or 'common', not %r" % (engine,))
         if engine == "common" and (Px_all is not None or Ax_all is not None):
             raise ValueError("engine='common' shares P and A over the batch: it takes no Px_all / Ax_all")
+        if shared_kkt and engine != "common":
+            raise ValueError("shared_kkt=True is an option of engine='common': the other engines serve polish, adjoint and "
+                             "tangent as they are")
         self.engine = engine
+        self._shared_kkt = False
         # neither path may hand back an unpolished or unclocked answer to a caller who asked for one: the batch
         # kernel implements neither, so both paths refuse them (OSQP_SETTINGS_VALIDATION_ERROR = 2)
         for k in ("polish", "time_limit"):
@@ -341,13 +351,56 @@ class BatchOSQP:
             if rc:
                 raise ValueError("osqp_amd_batch_setup failed with error %d" % rc)
         self._h = h
+        if shared_kkt:
+            try:
+                self.shared_kkt(True)
+            except RuntimeError as e:
+                self.cleanup()
+                raise ValueError(str(e)) from None
         return self
 
-    def _unserved(self, call):
-        """The calls the common-K engine does not serve (the C side refuses them too, with the same words)."""
-        if getattr(self, "engine", None) == "common":
-            raise RuntimeError("%s is not served by the common-K engine (engine=\"common\"); set the batch up with "
-                               "engine=\"auto\" or engine=\"streamed\"" % call)
+    def _unserved(self, call, never=False):
+        """The calls the common-K engine does not serve (the C side refuses them too, with the same words): every one of
+        them without the shared KKT pieces (shared_kkt), update_matrices (never=True) with them too."""
+        if getattr(self, "engine", None) == "common" and (never or not getattr(self, "_shared_kkt", False)):
+            raise RuntimeError("%s is not served by the common-K engine (engine=\"common\")%s; set the batch up with "
+                               "engine=\"auto\" or engine=\"streamed\""
+                               % (call, "" if never else " without its shared KKT pieces (shared_kkt=True)"))
+
+    def shared_kkt(self, on=True):
+        """The shared KKT pieces of a common-K handle (osqp_amd_batch_common_kkt): on=True builds H = (P~ + delta I)^-1 and
+        Wt = A~ H once (a second call does nothing), and polish, adjoint, tangent, kkt_info, adjoint_into, tangent_into
+        and results_into(status_polish=) are served from then on; on=False frees them and the calls are refused again.
+        Raises RuntimeError with the C return code (4: not a common-K handle, 5: a pivot of P + delta I is not positive,
+        6: out of memory)."""
+        if getattr(self, "_many", None) is not None or self._h is None:
+            raise RuntimeError("shared_kkt is a call of a live common-K handle (engine=\"common\")")
+        rc = int(self._lib.osqp_amd_batch_common_kkt(self._h, 1 if on else 0))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_common_kkt failed (%d)" % rc)
+        self._shared_kkt = bool(on)
+
+    def shared_kkt_peek(self, qp=None):
+        """Test hook: H [NP, NP] and Wt [m, NP] of a handle with the shared pieces and, with qp given, mred, NS and Sinv
+        [NS, NS] of member qp in the inversion currently kept (kkt_info().kept)."""
+        NP = self.shape()[1]
+        H = np.zeros((NP, NP)); Wt = np.zeros((max(self.m, 1), NP))
+        no_i, no_f = C.cast(None, abi.c_int_p), C.cast(None, abi.c_float_p)
+        rc = self._lib.osqp_amd_batch_common_kkt_peek(self._h, abi.fptr(H), abi.fptr(Wt), 0, no_i, no_i, no_f)
+        if rc:
+            raise RuntimeError("osqp_amd_batch_common_kkt_peek failed (%d)" % rc)
+        out = dict(H=H, Wt=Wt[:self.m], NP=NP)
+        if qp is not None:
+            mred = np.zeros(1, np.int64); NS = np.zeros(1, np.int64)
+            rc = self._lib.osqp_amd_batch_common_kkt_peek(self._h, no_f, no_f, int(qp), abi.iptr(mred), abi.iptr(NS), no_f)
+            if rc:
+                raise RuntimeError("osqp_amd_batch_common_kkt_peek failed (%d)" % rc)
+            S = np.zeros((int(NS[0]), int(NS[0])))
+            rc = self._lib.osqp_amd_batch_common_kkt_peek(self._h, no_f, no_f, int(qp), no_i, no_i, abi.fptr(S))
+            if rc:
+                raise RuntimeError("osqp_amd_batch_common_kkt_peek failed (%d)" % rc)
+            out.update(mred=int(mred[0]), NS=int(NS[0]), Sinv=S)
+        return out
 
     def shape(self):
         """(engine, NP) of a kernel batch: engine 0 = tiled, 1 = streamed, 2 = common-K; K^-1 is NP x NP (padded)."""
@@ -432,7 +485,7 @@ class BatchOSQP:
         list for the batch).  Scaling is recomputed; rho, row classes and iterates stay.  Returns the C return code
         (5: some member's new K is not positive definite; solve then refuses until an update succeeds).  Px / Ax may be
         device arrays; the index lists stay host data."""
-        self._unserved("update_matrices")
+        self._unserved("update_matrices", never=True)
         if self._route(Px=Px, Ax=Ax) == "device":
             return self._update_matrices_dev(Px, Px_idx, Ax, Ax_idx)
         Px, Px_idx, pper, Ax, Ax_idx, aper = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)

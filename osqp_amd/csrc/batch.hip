@@ -683,6 +683,7 @@ __global__ void __launch_bounds__(1024) k_batch_order(long long B, const double 
 #include "batch_polish.h"
 #include "batch_adjoint.h"
 #include "batch_tangent.h"
+#include "batch_common_kkt.h"
 
 struct osqp_amd_batch {
   int engine = OSQP_AMD_BATCH_TILED;
@@ -697,6 +698,7 @@ struct osqp_amd_batch {
   bool bc_rebuild = false;  // K^-1 no longer matches rho or the row classes
   bool bc_refine = false;   // the K^-1 solves take the refinement step (the verdict of the last probe)
   bool bc_open = false;     // the verdict is to be taken again: K^-1 is new
+  BKkt bk{};                // the shared KKT pieces (batch_common_kkt.h), built by osqp_amd_batch_common_kkt
   int device = 0, tile = 8, threads = 512;
   long long B = 0;
   int n = 0, m = 0, nnzP = 0, nnzA = 0;
@@ -741,7 +743,7 @@ struct osqp_amd_batch {
   int kkt_cache = 1;        // OSQP_AMD_BATCH_KKT_CACHE (0: every call builds its own)
   bool kkt_valid = false;   // dropped by a polish that does work and by a regrowth of pol.K
   int kkt_epoch = 0;        // b->solves when it was built: a later solve outdates it (kkt_kept)
-  int kkt_NPOL = 0;
+  int kkt_NPOL = 0, kkt_NS = 0;   // (NS: the order of the per-member S^-1 on a common-K handle with the shared pieces)
   size_t kkt_count = 0;     // the members in it
   int *kkt_piv = nullptr;   // [B] 0, or -1 where k_bp_invert met a pivot of the wrong sign
   long long kkt_builds = 0; // passes of k_bp_form + k_bp_invert over the solved members since setup, polish's included
@@ -778,7 +780,7 @@ static int balloc_once(osqp_amd_batch *b, Tp **p, size_t cnt) { return *p ? 0 : 
 static void set_dynamic_lds(const void *fn, size_t bytes) {
   if (bytes > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
-#define KFN(k) reinterpret_cast<const void *>(&k)
+#define KFN(...) reinterpret_cast<const void *>(&__VA_ARGS__)   // (variadic: a template-id carries commas)
 
 // io.flag of every member as the launches queued so far leave it
 static int read_flags(osqp_amd_batch *b, std::vector<int> &h) {
@@ -1341,12 +1343,14 @@ static void batch_launch(osqp_amd_batch *b, int phase) {
 }
 
 // the calls the common-K engine does not serve: the handle is left untouched and usable
-static c_int bc_refuse(const char *call) {
-  fprintf(stderr, "osqp_amd batch: %s is not served by the common-K engine (OSQP_AMD_BATCH_COMMON); use the tiled or "
-                  "the streamed engine\n", call);
+static c_int bc_refuse(const char *call, bool hint) {
+  fprintf(stderr, "osqp_amd batch: %s is not served by the common-K engine (OSQP_AMD_BATCH_COMMON)%s; use the tiled or "
+                  "the streamed engine\n", call, hint ? " without its shared KKT pieces (osqp_amd_batch_common_kkt)" : "");
   return OSQP_LINSYS_SOLVER_INIT_ERROR;
 }
-#define BC_UNSERVED(b, call) do { if ((b) && (b)->engine == OSQP_AMD_BATCH_COMMON) return bc_refuse(call); } while (0)
+// BC_UNSERVED: a common-K handle without the shared KKT pieces; BC_NEVER: any common-K handle
+#define BC_UNSERVED(b, call) do { if ((b) && (b)->engine == OSQP_AMD_BATCH_COMMON && !(b)->bk.H) return bc_refuse(call, true); } while (0)
+#define BC_NEVER(b, call) do { if ((b) && (b)->engine == OSQP_AMD_BATCH_COMMON) return bc_refuse(call, false); } while (0)
 
 extern "C" c_int osqp_amd_batch_setup_common(osqp_amd_batch **out, c_int batch, const csc *P, const csc *A,
                                             const c_float *Q, const c_float *L, const c_float *U,
@@ -1361,6 +1365,7 @@ extern "C" void osqp_amd_batch_cleanup(osqp_amd_batch *b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   for (void *p : b->allocs) (void)hipFree(p);
   if (b->pol.K) (void)hipFree(b->pol.K);
+  for (double *p : {b->bk.H, b->bk.Wt}) if (p) (void)hipFree(p);
   for (double *p : {b->bd.in, b->bd.mat, b->bd.out}) if (p) (void)hipFree(p);
   b->kkt_valid = false;
   if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -1440,7 +1445,7 @@ static int patch_values(osqp_amd_batch *b, double **raw, const double **io_raw, 
 extern "C" c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
                                                 const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
                                                 const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
-  BC_UNSERVED(b, "osqp_amd_batch_update_matrices");
+  BC_NEVER(b, "osqp_amd_batch_update_matrices");
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   // nothing is written before every argument has passed (osqp.c:1197-1222; the index range is this project's check)
   if (Px && Px_idx && P_n > b->nnzP) return 1;
@@ -1564,7 +1569,10 @@ static int bp_reserve_K(osqp_amd_batch *b, size_t bytes) {
 // What polish and adjoint share before their own kernel: the active rows of every solved member (k_bp_active with
 // pl, whose stat is the caller's status array), the list of solved members on the device, the padded order NPOL,
 // the refusals, the KKT buffer and the members per chunk.  lds_of: the caller's kernel's LDS for (n, m, NPOL).
-struct BPlan { size_t count = 0, chunk = 0, lds = 0, ilds = 0; int NPOL = 0; };
+// On a common-K handle with the shared pieces the buffer holds S^-1 of order NS per member, not the whole matrix of
+// order NPOL; NPOL stays the length of the kernels' LDS vectors [x; nu], and lds includes BlockK's scratch.
+struct BPlan { size_t count = 0, chunk = 0, lds = 0, ilds = 0; int NPOL = 0, NS = 0; };
+static BlockK bk_solver(const osqp_amd_batch *b, int NS) { return BlockK{b->bk.H, b->bk.Wt, b->NPs, NS}; }
 static c_int bp_plan(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_of)(int, int, int), BPlan *out) {
   const size_t B = (size_t)b->B;
   const int n = b->n, m = b->m;
@@ -1578,19 +1586,21 @@ static c_int bp_plan(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds
   *out = BPlan{};
   if (list.empty()) return 0;
   const int NPOL = (n + mmax + 31) & ~31;
-  const size_t lds = lds_of(n, m, NPOL);
+  const bool blk = b->bk.H != nullptr;
+  const int NS = blk ? std::max(32, (mmax + 31) & ~31) : 0, KN = blk ? NS : NPOL;
+  const size_t lds = lds_of(n, m, NPOL) + (blk ? bk_scratch_bytes(b->NPs, NS) : 0);
   if (NPOL > BP_MAX_N || lds > 160 * 1024) {
     fprintf(stderr, "osqp_amd batch: %s needs a KKT matrix of order n + active rows = %d (> %d) or %zu B of LDS "
                     "(> 160 KiB) for some member\n", what, n + mmax, BP_MAX_N, lds);
     return OSQP_LINSYS_SOLVER_INIT_ERROR;
   }
-  const size_t per = (size_t)NPOL * NPOL * sizeof(double);
+  const size_t per = (size_t)KN * KN * sizeof(double);
   const size_t chunk = std::min(std::min(list.size(), (size_t)65535), std::max((size_t)1, b->pol_cap / per));
   if (bp_reserve_K(b, chunk * per)) return OSQP_MEM_ALLOC_ERROR;
   pl.K = b->pol.K;
   BCHK(hipMemcpyAsync(b->d_plist, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
   BCHK(hipStreamSynchronize(b->stream));         // (list goes out of scope)
-  out->count = list.size(); out->chunk = chunk; out->lds = lds; out->ilds = 4 * (size_t)NPOL * sizeof(double); out->NPOL = NPOL;
+  out->count = list.size(); out->chunk = chunk; out->lds = lds; out->ilds = 4 * (size_t)KN * sizeof(double); out->NPOL = NPOL; out->NS = NS;
   return 0;
 }
 static size_t bp_lds_of(int n, int m, int NPOL) { return bp_lds_bytes(n, m, NPOL); }
@@ -1601,14 +1611,20 @@ static size_t bd_lds_of(int n, int m, int NPOL) { return bd_lds_bytes(n, m, NPOL
 // bytes of LDS.  Nothing is waited for.
 template <class Third>
 static int bp_run_chunks(osqp_amd_batch *b, const BPol &pl, const BPlan &pn, const void *fn, Third third) {
-  set_dynamic_lds(KFN(k_bp_invert), pn.ilds);
+  const bool blk = b->bk.H != nullptr;
+  set_dynamic_lds(blk ? KFN(k_bk_invert) : KFN(k_bp_invert), pn.ilds);
   set_dynamic_lds(fn, pn.lds);
   if (pn.count) b->kkt_builds++;
   for (size_t c0 = 0; c0 < pn.count; c0 += pn.chunk) {
     const unsigned cnt = (unsigned)std::min(pn.chunk, pn.count - c0);
     const int *lp = b->d_plist + c0;
-    hipLaunchKernelGGL(k_bp_form, dim3((unsigned)pn.NPOL, cnt), dim3(256), 0, b->stream, b->pat, b->io, pl, pn.NPOL, b->pol_delta, lp);
-    hipLaunchKernelGGL(k_bp_invert, dim3(cnt), dim3(BS_NTI), pn.ilds, b->stream, b->n, pl, pn.NPOL, lp);
+    if (blk) {
+      hipLaunchKernelGGL(k_bk_form, dim3((unsigned)pn.NS, cnt), dim3(256), 0, b->stream, b->pat, b->io, pl, b->bk, b->NPs, pn.NS, b->pol_delta, lp);
+      hipLaunchKernelGGL(k_bk_invert, dim3(cnt), dim3(BS_NTI), pn.ilds, b->stream, pl, pn.NS, lp);
+    } else {
+      hipLaunchKernelGGL(k_bp_form, dim3((unsigned)pn.NPOL, cnt), dim3(256), 0, b->stream, b->pat, b->io, pl, pn.NPOL, b->pol_delta, lp);
+      hipLaunchKernelGGL(k_bp_invert, dim3(cnt), dim3(BS_NTI), pn.ilds, b->stream, b->n, pl, pn.NPOL, lp);
+    }
     third(cnt, lp);
     BCHK(hipGetLastError());
   }
@@ -1631,7 +1647,8 @@ static c_int bd_run(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_
   const size_t B = (size_t)b->B;
   BPlan pn;
   if (kkt_kept(b)) {
-    pn.count = pn.chunk = b->kkt_count; pn.NPOL = b->kkt_NPOL; pn.lds = lds_of(b->n, b->m, pn.NPOL);
+    pn.count = pn.chunk = b->kkt_count; pn.NPOL = b->kkt_NPOL; pn.NS = b->kkt_NS;
+    pn.lds = lds_of(b->n, b->m, pn.NPOL) + (b->bk.H ? bk_scratch_bytes(b->NPs, pn.NS) : 0);
     if (pn.lds > 160 * 1024) {
       fprintf(stderr, "osqp_amd batch: %s needs %zu B of LDS (> 160 KiB) for some member\n", what, pn.lds);
       return OSQP_LINSYS_SOLVER_INIT_ERROR;
@@ -1652,7 +1669,7 @@ static c_int bd_run(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_
         if (keep) (void)hipMemcpyAsync(b->kkt_piv, pl.stat, B * sizeof(int), hipMemcpyDeviceToDevice, b->stream);
         third(pn, cnt, lp);
       })) return -102;
-  if (keep) { b->kkt_valid = true; b->kkt_epoch = b->solves; b->kkt_NPOL = pn.NPOL; b->kkt_count = pn.count; }
+  if (keep) { b->kkt_valid = true; b->kkt_epoch = b->solves; b->kkt_NPOL = pn.NPOL; b->kkt_NS = pn.NS; b->kkt_count = pn.count; }
   return 0;
 }
 
@@ -1669,8 +1686,10 @@ extern "C" c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish) 
     b->kkt_valid = false;   // polish overwrites pol.K and may move the point: it neither reads nor leaves a kept inversion
     const c_int rc = bp_plan(b, pl, "polish", bp_lds_of, &pn);
     if (rc) return rc;
-    if (bp_run_chunks(b, pl, pn, KFN(k_bp_polish), [&](unsigned cnt, const int *lp) {
-          hipLaunchKernelGGL(k_bp_polish, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->st, b->io, pl, pn.NPOL, b->pol_refine, lp);
+    const bool blk = b->bk.H != nullptr;
+    if (bp_run_chunks(b, pl, pn, blk ? KFN(k_bp_polish<BlockK, BlockK>) : KFN(k_bp_polish<FullK>), [&](unsigned cnt, const int *lp) {
+          if (blk) hipLaunchKernelGGL((k_bp_polish<BlockK, BlockK>), dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->st, b->io, pl, pn.NPOL, b->pol_refine, lp, bk_solver(b, pn.NS));
+          else hipLaunchKernelGGL(k_bp_polish<FullK>, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->st, b->io, pl, pn.NPOL, b->pol_refine, lp);
         })) return -102;
     BCHK(hipStreamSynchronize(b->stream));
     b->polished = true;
@@ -1692,7 +1711,84 @@ extern "C" c_int osqp_amd_batch_kkt_info(osqp_amd_batch *b, c_int out[4]) {
   if (!out) return OSQP_DATA_VALIDATION_ERROR;
   const bool kept = kkt_kept(b);
   out[0] = (c_int)b->kkt_builds; out[1] = kept ? 1 : 0;
-  out[2] = kept ? b->kkt_NPOL : 0; out[3] = kept ? (c_int)b->kkt_count : 0;
+  out[2] = kept ? (b->bk.H ? b->kkt_NS : b->kkt_NPOL) : 0; out[3] = kept ? (c_int)b->kkt_count : 0;
+  return 0;
+}
+
+// The shared KKT pieces of a common-K handle (batch_common_kkt.h).  on: H = (P~ + delta I)^-1 by k_bk_hform and the
+// k_bc_pivot sequence of bc_rebuild between two buffers of the call's own -- the pivot kernel sees a BIO whose flag is
+// the call's own word, so io.flag[0] and io.Wk stay as they are -- then Wt = A~ H.  off: both are freed.  Either way a
+// kept inversion is dropped: it belongs to the route that built it.
+static void bk_free(osqp_amd_batch *b) {
+  for (double **p : {&b->bk.H, &b->bk.Wt}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+}
+extern "C" c_int osqp_amd_batch_common_kkt(osqp_amd_batch *b, c_int on) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (b->engine != OSQP_AMD_BATCH_COMMON) {
+    fprintf(stderr, "osqp_amd batch: osqp_amd_batch_common_kkt is a call of the common-K engine (OSQP_AMD_BATCH_COMMON); the "
+                    "tiled and the streamed engine serve polish, adjoint and tangent as they are\n");
+    return OSQP_LINSYS_SOLVER_INIT_ERROR;
+  }
+  if (on && b->bk.H) return 0;
+  BCHK(hipSetDevice(b->device));
+  BCHK(hipStreamSynchronize(b->stream));
+  b->kkt_valid = false;
+  if (!on) { bk_free(b); return 0; }
+  const int n = b->n, m = b->m, NP = b->NPs;
+  const size_t sq = (size_t)NP * NP * sizeof(double);
+  // word: the pivots' verdict.  It is not cleared here: pivot 0 of k_bc_pivot stores the whole word (BF_OPEN) before any
+  // pivot ORs BF_NOT_PD into it, and n >= 1 on every handle, so it is written before it is read.
+  void *h2 = nullptr, *word = nullptr;
+  auto fail = [&](c_int rc) { bk_free(b); if (h2) (void)hipFree(h2); if (word) (void)hipFree(word); (void)hipGetLastError(); return rc; };
+  if (hipMalloc((void **)&b->bk.H, sq) != hipSuccess || hipMalloc(&h2, sq) != hipSuccess || hipMalloc(&word, sizeof(int)) != hipSuccess ||
+      (m > 0 && hipMalloc((void **)&b->bk.Wt, (size_t)m * NP * sizeof(double)) != hipSuccess))
+    return fail(OSQP_MEM_ALLOC_ERROR);
+  BIO io = b->io;
+  io.flag = static_cast<int *>(word);
+  double *cur = b->bk.H, *other = static_cast<double *>(h2);
+  hipLaunchKernelGGL(k_bk_hform, dim3((unsigned)NP), dim3(256), 0, b->stream, b->pat, b->io, NP, b->pol_delta, cur);
+  for (int k = 0; k < n; k++) {
+    hipLaunchKernelGGL(k_bc_pivot, dim3((unsigned)((NP + 63) / 64), (unsigned)((NP + 15) / 16)), dim3(64, 4), 0, b->stream,
+                       (const double *)cur, other, n, NP, k, io);
+    std::swap(cur, other);
+  }
+  int verdict = 0;
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&verdict, word, sizeof(int), hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
+      hipStreamSynchronize(b->stream) != hipSuccess) return fail(-102);
+  b->bk.H = cur; h2 = other;                     // the inverse is in whichever buffer the last pivot wrote
+  if (verdict & BF_NOT_PD) {
+    fprintf(stderr, "osqp_amd batch: osqp_amd_batch_common_kkt: a pivot of P + delta I is not positive\n");
+    return fail(OSQP_NONCVX_ERROR);
+  }
+  if (m > 0) hipLaunchKernelGGL(k_bk_wt, dim3((unsigned)m), dim3(256), 0, b->stream, b->pat, b->io, NP, (const double *)b->bk.H, b->bk.Wt);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) return fail(-102);
+  (void)hipFree(h2); (void)hipFree(word);
+  return 0;
+}
+
+// For the tests: the shared pieces and, of the kept inversion, member qp's S^-1 as stored.
+extern "C" c_int osqp_amd_batch_common_kkt_peek(osqp_amd_batch *b, c_float *H, c_float *Wt, c_int qp, c_int *mred, c_int *NS, c_float *Sinv) {
+  if (!b || !b->bk.H) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  const size_t B = (size_t)b->B, NP = (size_t)b->NPs;
+  const bool member = mred || NS || Sinv;
+  if (member && (qp < 0 || (size_t)qp >= B)) return OSQP_DATA_VALIDATION_ERROR;
+  if (member && !kkt_kept(b)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  BCHK(hipSetDevice(b->device));
+  if (H) BCHK(hipMemcpyAsync(H, b->bk.H, NP * NP * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  if (Wt && b->m) BCHK(hipMemcpyAsync(Wt, b->bk.Wt, (size_t)b->m * NP * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  if (member) {
+    std::vector<int> h(B);
+    BCHK(hipMemcpyAsync(h.data(), b->pol.mred, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    BCHK(hipStreamSynchronize(b->stream));
+    if (h[(size_t)qp] < 0) return OSQP_DATA_VALIDATION_ERROR;   // not a solved member: it has no slot
+    size_t slot = 0;                             // the solved members sit in the buffer in index order
+    for (size_t q = 0; q < (size_t)qp; q++) if (h[q] >= 0) slot++;
+    const size_t ns = (size_t)b->kkt_NS;
+    if (mred) *mred = h[(size_t)qp];
+    if (NS) *NS = (c_int)ns;
+    if (Sinv) BCHK(hipMemcpyAsync(Sinv, b->pol.K + slot * ns * ns, ns * ns * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  }
+  BCHK(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -1799,8 +1895,10 @@ static c_int adjoint_call(osqp_amd_batch *b, bool dev, const char *what, c_int n
   ad.dQ = b->bd.out; ad.dL = ad.dQ + B * D * n; ad.dU = ad.dL + B * D * m;
   ad.dPx = nP ? b->bd.mat : nullptr; ad.dAx = nA ? b->bd.mat + nP : nullptr;
   ad.active = b->bd.act; ad.stat = b->bd.stat;
-  if (const c_int rc = bd_run(b, pl, what, bd_lds_of, KFN(k_ba_adjoint), [&](const BPlan &pn, unsigned cnt, const int *lp) {
-        hipLaunchKernelGGL(k_ba_adjoint, dim3(cnt, (unsigned)ncot), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
+  const bool blk = b->bk.H != nullptr;
+  if (const c_int rc = bd_run(b, pl, what, bd_lds_of, blk ? KFN(k_ba_adjoint<BlockK, BlockK>) : KFN(k_ba_adjoint<FullK>), [&](const BPlan &pn, unsigned cnt, const int *lp) {
+        if (blk) hipLaunchKernelGGL((k_ba_adjoint<BlockK, BlockK>), dim3(cnt, (unsigned)ncot), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp, bk_solver(b, pn.NS));
+        else hipLaunchKernelGGL(k_ba_adjoint<FullK>, dim3(cnt, (unsigned)ncot), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
       })) return rc;
   return bd_deliver(b, dev, {{dQ, ad.dQ, B * D * n}, {dL, ad.dL, B * D * m}, {dU, ad.dU, B * D * m}, {dPx, ad.dPx, nP}, {dAx, ad.dAx, nA}},
                     {{active, ad.active, B * m}, {status, ad.stat, B}});
@@ -1853,8 +1951,10 @@ static c_int tangent_call(osqp_amd_batch *b, bool dev, c_int ndir, const c_float
                                 B * D * (n + m), 0)) return rc;
   tg.dX = b->bd.out; tg.dY = tg.dX + B * D * n;
   tg.active = b->bd.act; tg.stat = b->bd.stat;
-  if (const c_int rc = bd_run(b, pl, "tangent", bd_lds_of, KFN(k_bt_tangent), [&](const BPlan &pn, unsigned cnt, const int *lp) {
-        hipLaunchKernelGGL(k_bt_tangent, dim3(cnt, (unsigned)ndir), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, tg, pn.NPOL, b->pol_refine, lp);
+  const bool blk = b->bk.H != nullptr;
+  if (const c_int rc = bd_run(b, pl, "tangent", bd_lds_of, blk ? KFN(k_bt_tangent<BlockK, BlockK>) : KFN(k_bt_tangent<FullK>), [&](const BPlan &pn, unsigned cnt, const int *lp) {
+        if (blk) hipLaunchKernelGGL((k_bt_tangent<BlockK, BlockK>), dim3(cnt, (unsigned)ndir), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, tg, pn.NPOL, b->pol_refine, lp, bk_solver(b, pn.NS));
+        else hipLaunchKernelGGL(k_bt_tangent<FullK>, dim3(cnt, (unsigned)ndir), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, tg, pn.NPOL, b->pol_refine, lp);
       })) return rc;
   return bd_deliver(b, dev, {{dX, tg.dX, B * D * n}, {dY, tg.dY, B * D * m}}, {{active, tg.active, B * m}, {status, tg.stat, B}});
 }

@@ -34,11 +34,13 @@ struct BAdj {              // staging of a handle's adjoint call (device pointer
 
 // Opening, close and LDS as k_bt_tangent (bd_open, bd_close, bd_lds_bytes in batch_polish.h): pl.stat is the pivot
 // verdict of the inversion and is only read here; the status the caller sees is ad.stat.
+template <class KS, class... KSArg>
 __global__ void __launch_bounds__(BP_NT) k_ba_adjoint(BPattern p, BIO io, BPol pl, BAdj ad, int NPOL, int refine_iter,
-                                                      const int *list) {
+                                                      const int *list, KSArg... ksarg) {
+  const KS ks{ksarg...};
   extern __shared__ __attribute__((aligned(16))) double lds[];
   BDView mv;
-  if (!bd_open(p, io, pl, ad.stat, ad.ncot, NPOL, list, lds, mv)) return;
+  if (!bd_open(p, io, pl, ad.stat, ad.ncot, NPOL, list, lds, ks, mv)) return;
   const int n = mv.n, m = mv.m, N = mv.N, nlow = mv.nlow, tid = threadIdx.x;
   const long long slot = mv.slot;                          // this workgroup's (member, cotangent)
   const double cs = mv.cs, cinv = mv.cinv;
@@ -46,7 +48,7 @@ __global__ void __launch_bounds__(BP_NT) k_ba_adjoint(BPattern p, BIO io, BPol p
   const int *map = mv.map, *rows = mv.rows;
   double *sol = mv.sol, *g = mv.g;
   BL s;
-  slab_view(s, p, io, mv.qp);
+  slab_view(s, p, io, ks.slab(mv.qp));
   __syncthreads();
   const double *gx = ad.gx + slot * n, *gy = ad.gy ? ad.gy + slot * m : nullptr;
   // rhs = [D gx; E gy / c on the active rows], zero in the padding
@@ -57,7 +59,8 @@ __global__ void __launch_bounds__(BP_NT) k_ba_adjoint(BPattern p, BIO io, BPol p
     g[k] = v;
   }
   __syncthreads();
-  kkt_solve_refined(s, mv.Kinv, NPOL, n, N, map, rows, refine_iter, [g](int k) { return g[k]; }, sol, mv.res, mv.cor);
+  ks.solve(s, mv.Kinv, NPOL, n, N, map, rows, refine_iter, [g](int k) { return g[k]; }, sol, mv.res, mv.cor,
+           lds + bd_lds_bytes(n, m, NPOL) / sizeof(double));
   // sol = [rx; rnu] of the scaled problem; the unscaled gradients into this cotangent's slices
   for (int j = tid; j < n; j += BP_NT) ad.dQ[slot * n + j] = 0.0 - (cs * D[j]) * sol[j];
   for (int i = tid; i < m; i += BP_NT) {

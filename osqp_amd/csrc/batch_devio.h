@@ -106,7 +106,7 @@ extern "C" c_int osqp_amd_batch_update_dev(osqp_amd_batch *b, const c_float *Q, 
 extern "C" c_int osqp_amd_batch_update_matrices_dev(osqp_amd_batch *b,
                                                     const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
                                                     const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
-  BC_UNSERVED(b, "osqp_amd_batch_update_matrices_dev");
+  BC_NEVER(b, "osqp_amd_batch_update_matrices_dev");
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   // the twin's refusals in the twin's order, on the host lists; then the device pointers; then the first write
   if (Px && Px_idx && P_n > b->nnzP) return 1;

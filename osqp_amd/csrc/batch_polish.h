@@ -22,6 +22,9 @@
 // share its pieces: the three kernels above, load_row_maps and kkt_solve_refined.  What those two kernels have in
 // common beyond that -- opening, close and LDS layout -- is bd_open, bd_close and bd_lds_bytes below; k_bp_polish's
 // layout and tail differ and stay its own.
+// The solve itself is a template parameter of the three kernels (FullK below: the inverse of the whole matrix, as
+// described here; BlockK, batch_common_kkt.h: the common-K engine's block elimination on a shared Hessian inverse, which
+// replaces k_bp_form and k_bp_invert by k_bk_form and k_bk_invert on the Schur complement of the active rows).
 // An accepted member's X, Y, info8[2..4] and scaled iterates are overwritten; of a rejected or skipped
 // member nothing is written but its status_polish.  rho, K^-1, io.flag, the row classes and rho_updates are
 // never touched.
@@ -35,7 +38,7 @@ struct BPol {              // polish workspace of a handle (device pointers)
   int *mred;               // [B] active rows; -1: the member's last solve did not end OSQP_SOLVED (skipped)
   int *nlow;               // [B] how many of them are active at the lower bound
   int *stat;               // [B] status_polish: 1 accepted, -1 tried and rejected, 0 not tried
-  double *K;               // [members of a chunk][NPOL * NPOL] the KKT matrix, then its inverse
+  double *K;               // [members of a chunk][NPOL * NPOL] the KKT matrix, then its inverse (BlockK: [NS * NS], S and S^-1)
 };
 
 // Active rows from the stored scaled iterates and bounds (polish.c:19-100): low z - l < -y, upp u - z < y.
@@ -130,18 +133,18 @@ __device__ __forceinline__ void load_row_maps(const BPol &pl, long long qp, int 
   }
 }
 
-// sol = K^-1 rhs with the explicit inverse of the regularised matrix, then exactly refine_iter steps of
-// res = rhs - M sol, cor = K^-1 res, sol += cor against the unregularised M = [P, Ar'; Ar, 0] (polish.c:134-181).
-// rhs(k): the right-hand side, k in [0, NPOL), zero in the padding [N, NPOL).  sol, res, cor: LDS, NPOL each;
-// s: the member's slab_view; map, rows: LDS (load_row_maps).  Ends on a barrier.
-template <class Rhs>
-__device__ __forceinline__ void kkt_solve_refined(const BL &s, const double *Kinv, int NPOL, int n, int N, const int *map,
-                                                  const int *rows, int refine_iter, Rhs rhs, double *sol, double *res,
-                                                  double *cor) {
+// sol = K^-1 rhs, then exactly refine_iter steps of res = rhs - M sol, cor = K^-1 res, sol += cor against the
+// unregularised M = [P, Ar'; Ar, 0] (polish.c:134-181), K^-1 being whatever apply(in, out) applies: out = K^-1 in on
+// LDS vectors in the [x; nu] layout, ending on a barrier.  What kkt_solve_refined and kkt_solve_block
+// (batch_common_kkt.h) share.  rhs(k): the right-hand side, k in [0, NPOL), zero in the padding [N, NPOL).  sol, res,
+// cor: LDS, NPOL each; s: the member's slab_view; map, rows: LDS (load_row_maps).  Ends on a barrier.
+template <class Apply, class Rhs>
+__device__ __forceinline__ void kkt_refine(const BL &s, int NPOL, int n, int N, const int *map, const int *rows,
+                                           int refine_iter, Rhs rhs, double *sol, double *res, double *cor, Apply apply) {
   const int tid = threadIdx.x;
   for (int k = tid; k < NPOL; k += BP_NT) res[k] = rhs(k);
   __syncthreads();
-  bs_gemv(Kinv, NPOL, N, res, sol);
+  apply(res, sol);
   for (int it = 0; it < refine_iter; ++it) {
     for (int k = tid; k < NPOL; k += BP_NT) {
       double v = 0.0;
@@ -156,11 +159,34 @@ __device__ __forceinline__ void kkt_solve_refined(const BL &s, const double *Kin
       res[k] = v;
     }
     __syncthreads();
-    bs_gemv(Kinv, NPOL, N, res, cor);
+    apply(res, cor);
     for (int k = tid; k < N; k += BP_NT) sol[k] += cor[k];
     __syncthreads();
   }
 }
+
+// kkt_refine with the explicit inverse Kinv (NPOL x NPOL) of the whole regularised matrix
+template <class Rhs>
+__device__ __forceinline__ void kkt_solve_refined(const BL &s, const double *Kinv, int NPOL, int n, int N, const int *map,
+                                                  const int *rows, int refine_iter, Rhs rhs, double *sol, double *res,
+                                                  double *cor) {
+  kkt_refine(s, NPOL, n, N, map, rows, refine_iter, rhs, sol, res, cor,
+             [=](const double *in, double *out) { bs_gemv(Kinv, NPOL, N, in, out); });
+}
+
+// The KKT solver of k_bp_polish, k_ba_adjoint and k_bt_tangent, a template parameter of theirs as StreamedK is of the
+// ADMM loop.  FullK: the tiled and the streamed engine -- every member has its own slab of values and the inverse of
+// its whole regularised matrix, NPOL x NPOL, in slot blockIdx.x of the chunk's buffer.  (BlockK, the common-K engine's:
+// batch_common_kkt.h.)  The last argument of solve is LDS scratch behind the kernel's own, which only BlockK uses.
+struct FullK {
+  __device__ __forceinline__ long long slab(long long qp) const { return qp; }
+  __device__ __forceinline__ const double *inverse(const double *K, int NPOL) const { return K + (long long)blockIdx.x * NPOL * NPOL; }
+  template <class Rhs>
+  __device__ __forceinline__ void solve(const BL &s, const double *Kinv, int NPOL, int n, int N, const int *map, const int *rows,
+                                        int refine_iter, Rhs rhs, double *sol, double *res, double *cor, double *) const {
+    kkt_solve_refined(s, Kinv, NPOL, n, N, map, rows, refine_iter, rhs, sol, res, cor);
+  }
+};
 
 // What k_ba_adjoint and k_bt_tangent hold of their workgroup's member once bd_open has run: its scalars and the
 // carve-up of the LDS (bd_lds_bytes).  The member's slab_view stays a local of the kernel: held in here it cost the
@@ -169,7 +195,7 @@ struct BDView {
   long long qp, slot;      // the member; its slice blockIdx.y of the call's [B][slices][.] arrays
   int n, m, nlow, N;       // nlow of the N - n active rows sit at their lower bound
   double cs, cinv;         // the member's cost scaling c and 1 / c
-  const double *Kinv;      // the inverse of the regularised KKT matrix, slot blockIdx.x of the chunk
+  const double *Kinv;      // the solver's inverse of this member, slot blockIdx.x of the chunk (KS::inverse)
   double *sol, *res, *cor, *g;   // NPOL each: solution, residual, correction, right-hand side
   double *x, *D, *E, *y;   // n, n, m, m: the stored scaled iterates and the scaling
   int *map, *rows;         // m each (load_row_maps)
@@ -186,8 +212,9 @@ __host__ __device__ __forceinline__ size_t bd_lds_bytes(int n, int m, int NPOL) 
 // inversion (0, or -1 from k_bp_invert) and is only read; stat is the status the caller sees.  False (for the whole
 // workgroup): the inversion met a pivot of the wrong sign, slice 0 has reported -1 and the outputs stay 0.  True: v is
 // filled and x, D, E, y and the row maps are on their way into LDS (visible after the next barrier).
+template <class KS>
 __device__ __forceinline__ bool bd_open(const BPattern &p, const BIO &io, const BPol &pl, int *stat, int slices, int NPOL,
-                                        const int *list, double *lds, BDView &v) {
+                                        const int *list, double *lds, const KS &ks, BDView &v) {
   const long long qp = list[blockIdx.x];
   const int tid = threadIdx.x;
   if (pl.stat[qp] == -1) {
@@ -198,7 +225,7 @@ __device__ __forceinline__ bool bd_open(const BPattern &p, const BIO &io, const 
   const int mred = pl.mred[qp];
   v.qp = qp; v.slot = qp * slices + blockIdx.y;
   v.n = n; v.m = m; v.nlow = pl.nlow[qp]; v.N = n + mred;
-  v.Kinv = pl.K + (long long)blockIdx.x * NPOL * NPOL;
+  v.Kinv = ks.inverse(pl.K, NPOL);
   v.sol = lds; v.res = v.sol + NPOL; v.cor = v.res + NPOL; v.g = v.cor + NPOL;
   v.x = v.g + NPOL; v.D = v.x + n; v.E = v.D + n; v.y = v.E + m;
   v.map = reinterpret_cast<int *>(v.y + m); v.rows = v.map + m;
@@ -228,19 +255,21 @@ __host__ __device__ __forceinline__ size_t bp_lds_bytes(int n, int m, int NPOL) 
   return (b + 15) & ~(size_t)15;
 }
 
+template <class KS, class... KSArg>
 __global__ void __launch_bounds__(BP_NT) k_bp_polish(BPattern p, BSettings st, BIO io, BPol pl, int NPOL, int refine_iter,
-                                                     const int *list) {
+                                                     const int *list, KSArg... ksarg) {
+  const KS ks{ksarg...};
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const long long qp = list[blockIdx.x];
   if (pl.stat[qp] == -1) return;                 // the inversion met a pivot of the wrong sign
   const int n = p.n, m = p.m, tid = threadIdx.x;
   const int mred = pl.mred[qp], nlow = pl.nlow[qp], N = n + mred;
-  const double *Kinv = pl.K + (long long)blockIdx.x * NPOL * NPOL;
+  const double *Kinv = ks.inverse(pl.K, NPOL);
   double *sol = lds, *res = sol + NPOL, *cor = res + NPOL;
   double *q = cor + NPOL, *D = q + n, *l = D + n, *u = l + m, *E = u + m, *z = E + m, *y = z + m, *gp = y + m;
   int *map = reinterpret_cast<int *>(gp + 32), *rows = map + m;
   BL s;
-  slab_view(s, p, io, qp);
+  slab_view(s, p, io, ks.slab(qp));
   for (int j = tid; j < n; j += BP_NT) { q[j] = io.Wq[qp * n + j]; D[j] = io.Wd[qp * n + j]; }
   for (int i = tid; i < m; i += BP_NT) { l[i] = io.Wl[qp * m + i]; u[i] = io.Wu[qp * m + i]; E[i] = io.We[qp * m + i]; }
   load_row_maps(pl, qp, m, mred, map, rows);
@@ -253,7 +282,7 @@ __global__ void __launch_bounds__(BP_NT) k_bp_polish(BPattern p, BSettings st, B
     const int r = rows[k - n];
     return k - n < nlow ? l[r] : u[r];
   };
-  kkt_solve_refined(s, Kinv, NPOL, n, N, map, rows, refine_iter, rhs, sol, res, cor);
+  ks.solve(s, Kinv, NPOL, n, N, map, rows, refine_iter, rhs, sol, res, cor, lds + bp_lds_bytes(n, m, NPOL) / sizeof(double));
   // z = A x, y from the multipliers of the active rows, (z, y) on the normal cone (polish.c:262-279, proj.c:16-29);
   // then objective and residuals of the polished point as update_info computes them (auxil.c:227-318)
   const bool unscaled = st.scaling && !st.scaled_termination;

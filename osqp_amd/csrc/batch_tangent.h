@@ -38,11 +38,13 @@ struct BTan {              // staging of a handle's tangent call (device pointer
 
 // Opening, close and LDS as k_ba_adjoint (bd_open, bd_close, bd_lds_bytes in batch_polish.h): pl.stat is the pivot
 // verdict of this call's inversion and is only read here; the status the caller sees is tg.stat.
+template <class KS, class... KSArg>
 __global__ void __launch_bounds__(BP_NT) k_bt_tangent(BPattern p, BIO io, BPol pl, BTan tg, int NPOL, int refine_iter,
-                                                      const int *list) {
+                                                      const int *list, KSArg... ksarg) {
+  const KS ks{ksarg...};
   extern __shared__ __attribute__((aligned(16))) double lds[];
   BDView mv;
-  if (!bd_open(p, io, pl, tg.stat, tg.ndir, NPOL, list, lds, mv)) return;
+  if (!bd_open(p, io, pl, tg.stat, tg.ndir, NPOL, list, lds, ks, mv)) return;
   const int n = mv.n, m = mv.m, N = mv.N, nlow = mv.nlow, tid = threadIdx.x;
   const long long slot = mv.slot;                         // this workgroup's (member, direction)
   const double cs = mv.cs, cinv = mv.cinv;
@@ -50,7 +52,7 @@ __global__ void __launch_bounds__(BP_NT) k_bt_tangent(BPattern p, BIO io, BPol p
   const int *map = mv.map, *rows = mv.rows;
   double *sol = mv.sol, *g = mv.g;
   BL s;
-  slab_view(s, p, io, mv.qp);
+  slab_view(s, p, io, ks.slab(mv.qp));
   __syncthreads();
   const double *dq = tg.dQ ? tg.dQ + slot * n : nullptr;
   const double *dl = tg.dL ? tg.dL + slot * m : nullptr, *du = tg.dU ? tg.dU + slot * m : nullptr;
@@ -81,7 +83,8 @@ __global__ void __launch_bounds__(BP_NT) k_bt_tangent(BPattern p, BIO io, BPol p
     g[k] = v;
   }
   __syncthreads();
-  kkt_solve_refined(s, mv.Kinv, NPOL, n, N, map, rows, refine_iter, [g](int k) { return g[k]; }, sol, mv.res, mv.cor);
+  ks.solve(s, mv.Kinv, NPOL, n, N, map, rows, refine_iter, [g](int k) { return g[k]; }, sol, mv.res, mv.cor,
+           lds + bd_lds_bytes(n, m, NPOL) / sizeof(double));
   // sol = [dx~; dnu~] of the scaled problem; the unscaled tangents
   for (int j = tid; j < n; j += BP_NT) tg.dX[slot * n + j] = D[j] * sol[j];
   for (int i = tid; i < m; i += BP_NT) {

@@ -137,7 +137,9 @@ class BatchQPLayer(torch.nn.Module):
 
     polish=True polishes the solved members after every solve (BatchOSQP.polish), so the point differentiated is the
     polished one where polish is accepted.  engine and **settings are BatchOSQP.setup's (the handle is set up at the
-    first call and kept: later calls update it, and solves are warm-started unless warm_start=0).  Gradients come
+    first call and kept: later calls update it, and solves are warm-started unless warm_start=0).  engine="common" (one
+    model, many right-hand sides) needs shared_kkt=True, takes no Px / Ax, and raises RuntimeError naming member and
+    row when the bounds of a call give a row different classes in two members.  Gradients come
     back for exactly the inputs that require them.  A gradient with respect to an off-diagonal Px slot counts both
     halves of the symmetric P.  Members whose solve did not end `solved` (or whose KKT matrix is rejected) get zero
     gradients; `last_status_adjoint` [B] (1 computed, -1 rejected, 0 not tried) and `last_results` say which.  Where active
@@ -153,9 +155,9 @@ class BatchQPLayer(torch.nn.Module):
 
     def __init__(self, P, A, engine="auto", polish=True, **settings):
         super().__init__()
-        if engine == "common":
+        if engine == "common" and not settings.get("shared_kkt"):
             raise ValueError("BatchQPLayer needs polish and adjoint, which the common-K engine (engine='common') does not "
-                             "serve: use engine='auto' or 'streamed'")
+                             "serve without its shared KKT pieces: pass shared_kkt=True, or use engine='auto' or 'streamed'")
         self.P = sparse.triu(sparse.csc_matrix(P), format="csc"); self.P.sort_indices()
         self.A = sparse.csc_matrix(A); self.A.sort_indices()
         self.engine, self.polish, self.settings = engine, polish, settings
@@ -175,7 +177,7 @@ class BatchQPLayer(torch.nn.Module):
         else:
             rc = self.h.update(Q=Q, L=L, U=U)
             if rc:
-                raise RuntimeError("BatchOSQP.update failed (%d)" % rc)
+                raise RuntimeError("BatchOSQP.update failed (%d)%s" % (rc, self._class_clash(L, U)))
             # values a caller gave last time and not this time go back to the layer's own
             vP = Px if Px is not None else (self.P.data if self._own[0] else None)
             vA = Ax if Ax is not None else (self.A.data if self._own[1] else None)
@@ -188,6 +190,21 @@ class BatchQPLayer(torch.nn.Module):
         self.last_results = self.h.polish() if self.polish else self.h.results()
         self._serial += 1
         return self.last_results
+
+    def _class_clash(self, L, U):
+        """Why a common-K handle refused the bounds L, U [B, m] (host arrays): the first member and row whose class
+        (loose / inequality / equality, on the scaled bounds as src/auxil.c:76-98 takes it) differs from member 0's;
+        "" when the classes agree or the handle is of another engine."""
+        if self.engine != "common" or L is None or U is None or not L.shape[1]:
+            return ""
+        E = self.h.member_workspace(0)["E"]
+        ls, us = np.maximum(L, -1e30) * E, np.minimum(U, 1e30) * E
+        cls = np.where((ls < -1e26) & (us > 1e26), -1, np.where(us - ls < 1e-4, 1, 0))
+        bad = np.argwhere(cls != cls[0])
+        if not bad.size:
+            return ""
+        return (": row %d of member %d has another class (loose / inequality / equality) than in member 0 -- the common-K "
+                "engine needs one class per row over the batch" % (bad[0][1], bad[0][0]))
 
     def _own_values(self, which, device):
         if which not in self._vals or self._vals[which].device != device:
@@ -213,7 +230,7 @@ class BatchQPLayer(torch.nn.Module):
             if rc:
                 raise RuntimeError("BatchOSQP.update failed (%d: some lower bound exceeds its upper bound, or a tensor is "
                                    "not device memory the library's HIP runtime knows -- import torch before the library "
-                                   "is first loaded)" % rc)
+                                   "is first loaded)%s" % (rc, self._class_clash(_host(L), _host(U)) if m else ""))
             vP = Px if Px is not None else (self._own_values("P", dev) if self._own[0] else None)
             vA = Ax if Ax is not None else (self._own_values("A", dev) if self._own[1] else None)
             if vP is not None or vA is not None:
@@ -247,6 +264,8 @@ class BatchQPLayer(torch.nn.Module):
                 raise ValueError("%s must be [B, %d], not %s" % (name, cols, tuple(t.shape)))
             if t.device != Q.device:
                 raise ValueError("%s is on %s and Q on %s: every tensor of a call lives on one device" % (name, t.device, Q.device))
+        if self.engine == "common" and (Px is not None or Ax is not None):
+            raise ValueError("engine='common' shares P and A over the batch: the layer takes no Px / Ax")
         X, Y = _BatchQPFunction.apply(self, Q, L, U, Px, Ax)
         return (X, Y) if return_y else X
 
