@@ -80,16 +80,40 @@ c_int osqp_amd_batch_setup_engine(osqp_amd_batch **out, c_int engine, c_int batc
  * Served: _update, _warm_start, _update_rho, _solve, _get, _device_ptrs, _shape, _rounds, _cleanup, _update_dev,
  * _warm_start_dev, _get_dev, _check_dev_ptr, _member (the common D, E, c, rho, classes, Pv, Av and the one K^-1,
  * NP x NP, for any qp).  Served once osqp_amd_batch_common_kkt(b, 1) has built the shared KKT pieces, and refused
- * without them: _polish, _polish_status_dev, _adjoint*, _tangent*, _kkt_info.  Never served: _update_matrices(_dev).
+ * without them: _polish, _polish_status_dev, _adjoint*, _tangent*, _kkt_info.  Never served: _update_matrices(_dev)
+ * (its per-member value flags contradict the engine; new values of the one model go through
+ * osqp_amd_batch_common_update_model below).
  * A refused call returns OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line naming the engine and leaves the handle
  * untouched and usable. */
 #define OSQP_AMD_BATCH_COMMON 2   /* what osqp_amd_batch_shape reports for such a handle; setup_engine does not take it */
 c_int osqp_amd_batch_setup_common(osqp_amd_batch **out, c_int batch, const csc *P, const csc *A,
                                   const c_float *Q, const c_float *L, const c_float *U,
                                   const OSQPSettings *settings, c_int device);
+/* New values for the shared model of a live common-K handle: osqp_update_P / _A / _P_A (src/osqp.c:1012-1279) applied
+ * to the one model.  One value array [k] serves the batch.  Px / Ax NULL = keep.  Px_idx / Ax_idx NULL: all nnzP / nnzA
+ * values in CSC order of triu(P) / A; otherwise P_n / A_n values for the listed slots.
+ * The equilibration is recomputed from scratch on the new raw values and q^_j = max_b |Q[b][j]| over the raw Q the
+ * handle holds now (as last given by setup or _update) -- the scale_data of setup -- and every member's scaled q, l, u
+ * are rewritten from its stored raw ones with the new D, E, c.  The row classes stay as stored (the reference does not
+ * re-run set_rho_vec in a matrix update), so the call has no class-clash outcome; a later _update with bounds classifies
+ * under the new E as ever.  rho stays the adapted value of the last solve.  The scaled iterates x, z, y of every member
+ * stay; rho_updates of every member is reset; the handle counts as unsolved and a kept KKT inversion is dropped.  K is
+ * re-formed and re-inverted inside the call and the refinement verdict is taken again.  Where the handle carries the
+ * shared KKT pieces, H and Wt are rebuilt from the new scaled values.
+ * Returns, in this order and with nothing written: OSQP_WORKSPACE_NOT_INIT_ERROR for NULL;
+ * OSQP_LINSYS_SOLVER_INIT_ERROR (stderr names osqp_amd_batch_update_matrices) for a handle of another engine; 1 when
+ * P_n > nnzP; 2 when A_n > nnzA; OSQP_DATA_VALIDATION_ERROR for a negative count or an index outside [0, nnz); 0 when
+ * both Px and Ax are NULL (nothing changes).  After the values are written: OSQP_NONCVX_ERROR when a pivot of the new K
+ * is not positive -- the handle stays alive, osqp_amd_batch_solve returns OSQP_NONCVX_ERROR until a later call of this
+ * function succeeds, and H and Wt are rebuilt by that call; OSQP_NONCVX_ERROR, with the stderr line of
+ * osqp_amd_batch_common_kkt, when K passes but a pivot of P~ + delta I does not -- the shared pieces are freed, the
+ * handle is a common-K handle without them and solves are served; OSQP_MEM_ALLOC_ERROR; -102 when a HIP call fails. */
+c_int osqp_amd_batch_common_update_model(osqp_amd_batch *b,
+                                         const c_float *Px, const c_int *Px_idx, c_int P_n,
+                                         const c_float *Ax, const c_int *Ax_idx, c_int A_n);
 /* Polish, adjoint and tangent of a common-K handle, on a shared Hessian inverse.  The (1,1) block of the regularised
- * KKT matrix [P~ + delta I, Ar'; Ar, -delta I] (P~, A~: the handle's scaled values) is the same for every member and
- * for the handle's life, so the calls below eliminate it once: H = (P~ + delta I)^-1, Wt = A~ H, and per member only
+ * KKT matrix [P~ + delta I, Ar'; Ar, -delta I] (P~, A~: the handle's scaled values) is the same for every member
+ * until osqp_amd_batch_common_update_model brings new values, so the calls below eliminate it once: H = (P~ + delta I)^-1, Wt = A~ H, and per member only
  * S = Ar H Ar' + delta I of order mred is formed and inverted; t = H g1, nu = S^-1 (Ar t - g2), x = t - Wt[rows]' nu
  * is the same regularised solve, followed by the same polish_refine_iter refinement steps against [P, Ar'; Ar, 0].
  * on = 1: build (once; a second call is a no-op returning 0) the shared KKT pieces of a common-K handle -- H = (P~ + delta I)^-1,
@@ -291,6 +315,12 @@ c_int osqp_amd_batch_update_dev(osqp_amd_batch *b, const c_float *Q, const c_flo
 c_int osqp_amd_batch_update_matrices_dev(osqp_amd_batch *b,
                                          const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
                                          const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member);
+/* osqp_amd_batch_common_update_model with the value arrays Px / Ax on the device; the index lists stay HOST pointers.
+ * The twin's refusals in the twin's order, then OSQP_DATA_VALIDATION_ERROR for a pointer that is not device memory of
+ * the handle's device, then 0 for both NULL. */
+c_int osqp_amd_batch_common_update_model_dev(osqp_amd_batch *b,
+                                             const c_float *Px, const c_int *Px_idx, c_int P_n,
+                                             const c_float *Ax, const c_int *Ax_idx, c_int A_n);
 /* osqp_amd_batch_warm_start from device arrays X [batch][n], Y [batch][m] (either may be NULL). */
 c_int osqp_amd_batch_warm_start_dev(osqp_amd_batch *b, const c_float *X, const c_float *Y);
 /* osqp_amd_batch_adjoint with every array on the device.  active [batch][m] and status_adjoint [batch] are 32-bit

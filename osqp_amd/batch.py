@@ -59,6 +59,8 @@ def _bind(L):
                                               C.POINTER(abi.OSQPSettings), abi.c_int]
     L.osqp_amd_batch_common_kkt.restype = abi.c_int
     L.osqp_amd_batch_common_kkt.argtypes = [H, abi.c_int]
+    L.osqp_amd_batch_common_update_model.restype = abi.c_int
+    L.osqp_amd_batch_common_update_model.argtypes = [H] + [abi.c_float_p, abi.c_int_p, abi.c_int] * 2
     L.osqp_amd_batch_common_kkt_peek.restype = abi.c_int
     L.osqp_amd_batch_common_kkt_peek.argtypes = [H, abi.c_float_p, abi.c_float_p, abi.c_int, abi.c_int_p, abi.c_int_p, abi.c_float_p]
     L.osqp_amd_batch_shape.restype = abi.c_int
@@ -73,6 +75,7 @@ def _bind(L):
                        ("adjoint_multi_dev", [abi.c_int] + [V] * 9),
                        ("tangent_dev", [abi.c_int] + [V] * 9),
                        ("update_matrices_dev", [V, abi.c_int_p, abi.c_int, abi.c_int] * 2),
+                       ("common_update_model_dev", [V, abi.c_int_p, abi.c_int] * 2),
                        ("get_dev", [V] * 5), ("polish_status_dev", [V]), ("check_dev_ptr", [V])):
         f = getattr(L, "osqp_amd_batch_" + name)
         f.restype = abi.c_int
@@ -365,7 +368,8 @@ class BatchOSQP:
         if getattr(self, "engine", None) == "common" and (never or not getattr(self, "_shared_kkt", False)):
             raise RuntimeError("%s is not served by the common-K engine (engine=\"common\")%s; set the batch up with "
                                "engine=\"auto\" or engine=\"streamed\""
-                               % (call, "" if never else " without its shared KKT pieces (shared_kkt=True)"))
+                               % (call, " (use update_model for new values of the shared model)" if never else
+                                  " without its shared KKT pieces (shared_kkt=True)"))
 
     def shared_kkt(self, on=True):
         """The shared KKT pieces of a common-K handle (osqp_amd_batch_common_kkt): on=True builds H = (P~ + delta I)^-1 and
@@ -511,6 +515,40 @@ class BatchOSQP:
         return int(self._lib.osqp_amd_batch_update_matrices_dev(
             self._h, pP, ip(Px_idx), 0 if Px is None else shp(Px)[-1], pper,
             pA, ip(Ax_idx), 0 if Ax is None else shp(Ax)[-1], aper))
+
+    def update_model(self, Px=None, Px_idx=None, Ax=None, Ax_idx=None):
+        """New values for the shared model of a common-K handle (osqp_amd_batch_common_update_model): osqp_update_P / _A /
+        _P_A applied to the one model.  Px / Ax: [k] -- k = nnz of triu(P) / A in CSC order, or the length of Px_idx /
+        Ax_idx (slots) -- host arrays or device arrays; the index lists stay host data.  The common scaling is recomputed
+        (q^ over the Q the handle holds now), every member's q, l, u are rescaled, the one K^-1 and, where the handle has
+        them, the shared KKT pieces are rebuilt inside the call; rho, the row classes and the iterates stay, rho_updates
+        restarts.  Returns the C return code (5: the new K is not positive definite and solve refuses until a call
+        succeeds -- or, on a handle with the shared pieces whose K is fine, P + delta I is not: the pieces are freed and
+        polish, adjoint and tangent are refused again)."""
+        if getattr(self, "engine", None) != "common" or self._h is None:
+            raise RuntimeError("update_model is a call of the common-K engine (engine=\"common\"); the other engines take new "
+                               "matrix values through update_matrices")
+        for name, V in (("Px", Px), ("Ax", Ax)):
+            if V is not None and len(V.__cuda_array_interface__["shape"] if is_device(V) else np.shape(V)) != 1:
+                raise ValueError("engine='common' shares P and A over the batch: update_model takes %s as one [k] array, not "
+                                 "[B, k]" % name)
+        dev = self._route(Px=Px, Ax=Ax) == "device"
+        Px, Px_idx, _, Ax, Ax_idx, _ = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
+        ip = lambda a: C.cast(None, abi.c_int_p) if a is None else abi.iptr(a)
+        if dev:
+            shp = lambda a: tuple(a.__cuda_array_interface__["shape"])
+            # (a pointer of 0: nothing to write; NULL = keep says the same)
+            vals = [None if V is None else device_view(V, shp(V), "<f8", name=nm) or None for nm, V in (("Px", Px), ("Ax", Ax))]
+            cnt = [0 if V is None else shp(V)[0] for V in (Px, Ax)]
+            call = self._lib.osqp_amd_batch_common_update_model_dev
+        else:
+            vals, cnt = [_p(Px), _p(Ax)], [0 if V is None else V.shape[0] for V in (Px, Ax)]
+            call = self._lib.osqp_amd_batch_common_update_model
+        rc = int(call(self._h, vals[0], ip(Px_idx), cnt[0], vals[1], ip(Ax_idx), cnt[1]))
+        if rc == 5 and self._shared_kkt:                 # did the shared pieces go?  (NULL outputs: nothing is copied)
+            no_i, no_f = C.cast(None, abi.c_int_p), C.cast(None, abi.c_float_p)
+            self._shared_kkt = self._lib.osqp_amd_batch_common_kkt_peek(self._h, no_f, no_f, 0, no_i, no_i, no_f) == 0
+        return rc
 
     def update_rho(self, rho):
         """osqp_update_rho for every QP: a scalar, or [B] values.  Returns 1 (nothing changed) when a value is <= 0."""

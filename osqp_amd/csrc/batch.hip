@@ -695,6 +695,8 @@ struct osqp_amd_batch {
   BCT ct{};
   double bc_rho = 0.0;      // the batch's rho
   double *bc_wk2 = nullptr; // the second NP x NP buffer of the inversion (k_bc_pivot); io.Wk and it swap roles
+  double *bc_qhat = nullptr; // [n] q^ of a model update (k_bc_qhat), allocated by the first one
+  int bc_pivot2 = 1;        // OSQP_AMD_BATCH_MODEL_PIVOT2 (0: a model update inverts K, then H, with k_bc_pivot)
   bool bc_rebuild = false;  // K^-1 no longer matches rho or the row classes
   bool bc_refine = false;   // the K^-1 solves take the refinement step (the verdict of the last probe)
   bool bc_open = false;     // the verdict is to be taken again: K^-1 is new
@@ -833,6 +835,10 @@ static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
   // bits; the switch exists to compare them)
   e = getenv("OSQP_AMD_BATCH_KKT_CACHE");
   b->kkt_cache = e ? atoi(e) : 1;
+  // 0: a model update of a common-K handle with the shared pieces runs the two pivot sequences one after the other (the
+  // same bits; the switch exists to time them against k_bc_pivot2)
+  e = getenv("OSQP_AMD_BATCH_MODEL_PIVOT2");
+  b->bc_pivot2 = e ? atoi(e) : 1;
 }
 
 static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, const std::vector<int> &Pi,
@@ -1722,26 +1728,18 @@ extern "C" c_int osqp_amd_batch_kkt_info(osqp_amd_batch *b, c_int out[4]) {
 static void bk_free(osqp_amd_batch *b) {
   for (double **p : {&b->bk.H, &b->bk.Wt}) { if (*p) (void)hipFree(*p); *p = nullptr; }
 }
-extern "C" c_int osqp_amd_batch_common_kkt(osqp_amd_batch *b, c_int on) {
-  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (b->engine != OSQP_AMD_BATCH_COMMON) {
-    fprintf(stderr, "osqp_amd batch: osqp_amd_batch_common_kkt is a call of the common-K engine (OSQP_AMD_BATCH_COMMON); the "
-                    "tiled and the streamed engine serve polish, adjoint and tangent as they are\n");
-    return OSQP_LINSYS_SOLVER_INIT_ERROR;
-  }
-  if (on && b->bk.H) return 0;
-  BCHK(hipSetDevice(b->device));
-  BCHK(hipStreamSynchronize(b->stream));
-  b->kkt_valid = false;
-  if (!on) { bk_free(b); return 0; }
+// H and Wt from the scaled values the handle holds now, into b->bk's allocations where it has them (a model update)
+// and into new ones otherwise (osqp_amd_batch_common_kkt).  On any failure both are freed.
+static c_int bk_build(osqp_amd_batch *b) {
   const int n = b->n, m = b->m, NP = b->NPs;
   const size_t sq = (size_t)NP * NP * sizeof(double);
   // word: the pivots' verdict.  It is not cleared here: pivot 0 of k_bc_pivot stores the whole word (BF_OPEN) before any
   // pivot ORs BF_NOT_PD into it, and n >= 1 on every handle, so it is written before it is read.
   void *h2 = nullptr, *word = nullptr;
   auto fail = [&](c_int rc) { bk_free(b); if (h2) (void)hipFree(h2); if (word) (void)hipFree(word); (void)hipGetLastError(); return rc; };
-  if (hipMalloc((void **)&b->bk.H, sq) != hipSuccess || hipMalloc(&h2, sq) != hipSuccess || hipMalloc(&word, sizeof(int)) != hipSuccess ||
-      (m > 0 && hipMalloc((void **)&b->bk.Wt, (size_t)m * NP * sizeof(double)) != hipSuccess))
+  if ((!b->bk.H && hipMalloc((void **)&b->bk.H, sq) != hipSuccess) || hipMalloc(&h2, sq) != hipSuccess ||
+      hipMalloc(&word, sizeof(int)) != hipSuccess ||
+      (m > 0 && !b->bk.Wt && hipMalloc((void **)&b->bk.Wt, (size_t)m * NP * sizeof(double)) != hipSuccess))
     return fail(OSQP_MEM_ALLOC_ERROR);
   BIO io = b->io;
   io.flag = static_cast<int *>(word);
@@ -1764,6 +1762,127 @@ extern "C" c_int osqp_amd_batch_common_kkt(osqp_amd_batch *b, c_int on) {
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) return fail(-102);
   (void)hipFree(h2); (void)hipFree(word);
   return 0;
+}
+extern "C" c_int osqp_amd_batch_common_kkt(osqp_amd_batch *b, c_int on) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (b->engine != OSQP_AMD_BATCH_COMMON) {
+    fprintf(stderr, "osqp_amd batch: osqp_amd_batch_common_kkt is a call of the common-K engine (OSQP_AMD_BATCH_COMMON); the "
+                    "tiled and the streamed engine serve polish, adjoint and tangent as they are\n");
+    return OSQP_LINSYS_SOLVER_INIT_ERROR;
+  }
+  if (on && b->bk.H) return 0;
+  BCHK(hipSetDevice(b->device));
+  BCHK(hipStreamSynchronize(b->stream));
+  b->kkt_valid = false;
+  if (!on) { bk_free(b); return 0; }
+  return bk_build(b);
+}
+
+// bc_rebuild and bk_build of a model update on a handle with the shared pieces, side by side: k_bc_pivot2 advances K and
+// P~ + delta I in one launch per pivot.  *kflag: K's flag word.  Where K fails, H's verdict is not read and the pieces
+// stay allocated (the call that repairs K rebuilds them); where only H fails, bk_build's outcome.
+static c_int bc_rebuild_pair(osqp_amd_batch *b, int *kflag) {
+  const int n = b->n, m = b->m, NP = b->NPs;
+  const size_t sq = (size_t)NP * NP * sizeof(double);
+  void *h2 = nullptr, *word = nullptr;
+  auto fail = [&](c_int rc) { bk_free(b); if (h2) (void)hipFree(h2); if (word) (void)hipFree(word); (void)hipGetLastError(); return rc; };
+  if (hipMalloc(&h2, sq) != hipSuccess || hipMalloc(&word, sizeof(int)) != hipSuccess) return fail(OSQP_MEM_ALLOC_ERROR);
+  hipLaunchKernelGGL(k_bc_mark, dim3(1), dim3(64), 0, b->stream, b->io, b->bc_rho);
+  hipLaunchKernelGGL(k_bs_form, dim3((unsigned)NP, 1), dim3(256), 0, b->stream, b->pat, b->kpat, b->io, NP, b->st.sigma,
+                     (const int *)nullptr);
+  hipLaunchKernelGGL(k_bk_hform, dim3((unsigned)NP), dim3(256), 0, b->stream, b->pat, b->io, NP, b->pol_delta, b->bk.H);
+  BCPair a;
+  a.in[0] = b->io.Wk; a.out[0] = b->bc_wk2; a.flag[0] = b->io.flag;
+  a.in[1] = b->bk.H; a.out[1] = static_cast<double *>(h2); a.flag[1] = static_cast<int *>(word);
+  for (int k = 0; k < n; k++) {
+    hipLaunchKernelGGL(k_bc_pivot2, dim3((unsigned)((NP + 63) / 64), (unsigned)((NP + 15) / 16), 2), dim3(64, 4), 0, b->stream,
+                       a, n, NP, k);
+    for (int s = 0; s < 2; s++) { double *t = const_cast<double *>(a.in[s]); a.in[s] = a.out[s]; a.out[s] = t; }
+  }
+  b->io.Wk = const_cast<double *>(a.in[0]); b->bc_wk2 = a.out[0];
+  b->bk.H = const_cast<double *>(a.in[1]); h2 = a.out[1];      // each inverse is in whichever buffer the last pivot wrote
+  b->bc_rebuild = false;
+  b->bc_open = true;
+  int verdict = 0;
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(kflag, b->io.flag, sizeof(int), hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
+      hipMemcpyAsync(&verdict, word, sizeof(int), hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
+      hipStreamSynchronize(b->stream) != hipSuccess) return fail(-102);
+  if (!(*kflag & BF_NOT_PD)) {
+    if (verdict & BF_NOT_PD) {
+      fprintf(stderr, "osqp_amd batch: osqp_amd_batch_common_kkt: a pivot of P + delta I is not positive\n");
+      return fail(OSQP_NONCVX_ERROR);
+    }
+    if (m > 0) hipLaunchKernelGGL(k_bk_wt, dim3((unsigned)m), dim3(256), 0, b->stream, b->pat, b->io, NP, (const double *)b->bk.H, b->bk.Wt);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) return fail(-102);
+  }
+  (void)hipFree(h2); (void)hipFree(word);
+  return 0;
+}
+
+// New values for the one model of a common-K handle: osqp_update_P / _A / _P_A on the shared raw arrays, then
+// setup's scale_data on the one-member image (q^, L[0], U[0]) with the classes kept (k_bs_setup<true>), D, E, c for
+// every member (k_bc_spread), every member's scaled q, l, u from its stored raw ones (k_bc_rescale), the one K^-1 with
+// the batch's rho as it stands, and H / Wt where the handle carries them.  dev: Px / Ax are device arrays.
+static c_int dev_ptrs_check(const osqp_amd_batch *b, std::initializer_list<const void *> ps);   // batch_devio.h
+static c_int bc_update_model(osqp_amd_batch *b, bool dev, const char *call, const c_float *Px, const c_int *Px_idx, c_int P_n,
+                             const c_float *Ax, const c_int *Ax_idx, c_int A_n) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (b->engine != OSQP_AMD_BATCH_COMMON) {
+    fprintf(stderr, "osqp_amd batch: %s is a call of the common-K engine (OSQP_AMD_BATCH_COMMON); the tiled and the streamed "
+                    "engine take new matrix values through osqp_amd_batch_update_matrices\n", call);
+    return OSQP_LINSYS_SOLVER_INIT_ERROR;
+  }
+  // nothing is written before every argument has passed: osqp_amd_batch_update_matrices' refusals in its order
+  if (Px && Px_idx && P_n > b->nnzP) return 1;
+  if (Ax && Ax_idx && A_n > b->nnzA) return 2;
+  if ((Px && Px_idx && P_n < 0) || (Ax && Ax_idx && A_n < 0)) return OSQP_DATA_VALIDATION_ERROR;
+  if (Px && Px_idx) for (c_int k = 0; k < P_n; k++) if (Px_idx[k] < 0 || Px_idx[k] >= b->nnzP) return OSQP_DATA_VALIDATION_ERROR;
+  if (Ax && Ax_idx) for (c_int k = 0; k < A_n; k++) if (Ax_idx[k] < 0 || Ax_idx[k] >= b->nnzA) return OSQP_DATA_VALIDATION_ERROR;
+  BCHK(hipSetDevice(b->device));
+  if (dev && dev_ptrs_check(b, {Px, Ax})) return OSQP_DATA_VALIDATION_ERROR;
+  if (!Px && !Ax) return 0;
+  b->solved = false;                             // (a kept KKT inversion goes with it: kkt_kept)
+  b->kkt_valid = false;
+  const c_int pc = Px ? (Px_idx ? P_n : (c_int)b->nnzP) : 0, ac = Ax ? (Ax_idx ? A_n : (c_int)b->nnzA) : 0;
+  const size_t n = (size_t)b->n, B = (size_t)b->B;
+  if (stage_reserve(b, dev ? 0 : (size_t)pc + ac, (size_t)pc + ac) || balloc_once(b, &b->bc_qhat, n)) return OSQP_MEM_ALLOC_ERROR;
+  if (Px && patch_values(b, &b->dPx, &b->io.Px, &b->io.strideP, b->nnzP, Px, Px_idx, pc, 0, 0, 0, dev)) return OSQP_MEM_ALLOC_ERROR;
+  if (Ax && patch_values(b, &b->dAx, &b->io.Ax, &b->io.strideA, b->nnzA, Ax, Ax_idx, ac, 0, (size_t)pc, (size_t)pc, dev))
+    return OSQP_MEM_ALLOC_ERROR;
+  hipLaunchKernelGGL(k_bc_qhat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, b->n, b->B, (const double *)b->dQ,
+                     b->bc_qhat);
+  BIO io1 = b->io;
+  io1.Q = b->bc_qhat;
+  int NP = b->NPs;
+  void *args[] = {&b->pat, &b->st, &io1, &NP};
+  set_dynamic_lds(KFN(k_bs_setup<true>), b->lds_bytes);
+  (void)hipLaunchKernel(KFN(k_bs_setup<true>), dim3(1), dim3(BS_NT), args, b->lds_bytes, b->stream);
+  if (B > 1) hipLaunchKernelGGL(k_bc_spread, dim3((unsigned)(B - 1)), dim3(256), 0, b->stream, b->n, b->m, b->io);
+  hipLaunchKernelGGL(k_bc_rescale, dim3((unsigned)B), dim3(256), 0, b->stream, b->n, b->m, b->io);
+  b->bc_refine = false;                          // the verdict belonged to the old K; the rebuild re-opens it
+  int flag = 0;
+  c_int hrc = 0;
+  const bool pair = b->bk.H && b->bc_pivot2;
+  if (pair) hrc = bc_rebuild_pair(b, &flag);
+  else {
+    bc_rebuild(b);
+    BCHK(hipGetLastError());
+    BCHK(hipMemcpyAsync(&flag, b->io.flag, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    BCHK(hipStreamSynchronize(b->stream));
+  }
+  if (hrc && hrc != OSQP_NONCVX_ERROR) return hrc;
+  b->noncvx = (flag & BF_NOT_PD) != 0;
+  if (b->noncvx) {                               // (H and Wt wait for the call that repairs K)
+    fprintf(stderr, "osqp_amd batch: the new K of the batch is not positive definite (K = P + sigma I + A' rho A with the "
+                    "updated values); solves are refused until a matrix update succeeds\n");
+    return OSQP_NONCVX_ERROR;
+  }
+  if (pair) return hrc;
+  return b->bk.H ? bk_build(b) : 0;
+}
+extern "C" c_int osqp_amd_batch_common_update_model(osqp_amd_batch *b, const c_float *Px, const c_int *Px_idx, c_int P_n,
+                                                    const c_float *Ax, const c_int *Ax_idx, c_int A_n) {
+  return bc_update_model(b, false, "osqp_amd_batch_common_update_model", Px, Px_idx, P_n, Ax, Ax_idx, A_n);
 }
 
 // For the tests: the shared pieces and, of the kept inversion, member qp's S^-1 as stored.

@@ -53,6 +53,33 @@ __global__ void __launch_bounds__(256) k_bc_spread(int n, int m, BIO io) {
   if (threadIdx.x == 0) io.Wc[qp] = io.Wc[0];
 }
 
+// q^_j = max_b |Q[b][j]| of the raw [B][n] Q the handle holds (osqp_amd_batch_common_update_model): one thread per
+// column walks the members, so a wavefront reads 64 contiguous doubles of each member.  A max is exact: q^ carries
+// the bits of setup's host loop (bc_setup_launch), whatever the order.
+__global__ void __launch_bounds__(256) k_bc_qhat(int n, long long B, const double *__restrict__ Q, double *__restrict__ qhat) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  double v = 0.0;
+#pragma unroll 8                                  // (eight members' loads in flight: the walk is latency-bound)
+  for (long long b = 0; b < B; ++b) v = fmax(v, fabs(Q[b * n + j]));
+  qhat[j] = v;
+}
+
+// Every member's scaled q, l, u from its stored raw Q, L, U with the D, E, c the model update has just spread:
+// k_batch_update's expressions without its re-classification -- the row classes (io.Wt) and io.flag stay as they are,
+// as in the reference's matrix update -- and reset_info's rho_updates = 0.  One workgroup per member.
+__global__ void __launch_bounds__(256) k_bc_rescale(int n, int m, BIO io) {
+  const long long qp = blockIdx.x;
+  const double c = io.Wc[qp];
+  for (int j = threadIdx.x; j < n; j += 256) io.Wq[qp * n + j] = (io.Q[qp * n + j] * io.Wd[qp * n + j]) * c;
+  for (int i = threadIdx.x; i < m; i += 256) {
+    const double e = io.We[qp * m + i];
+    io.Wl[qp * m + i] = io.L[qp * m + i] * e;
+    io.Wu[qp * m + i] = io.U[qp * m + i] * e;
+  }
+  if (threadIdx.x == 0) io.info[qp * 8 + 5] = 0.0;
+}
+
 // Would the bounds L, U (raw, [B][m]; null = the member's scaled bound as stored) leave every row with one class over
 // the batch?  bad[qp] = the first row whose class differs from member 0's (-1: none); bad[B] = 1 when the class of
 // some row of member 0 differs from the stored one (K is then due).  Writes nothing of the workspace.
@@ -110,6 +137,40 @@ __global__ void __launch_bounds__(256) k_bc_pivot(const double *__restrict__ in,
       const double ci = in[(size_t)i * NP + k];
       if (i == k) v = j == k ? piv : rkj;
       else v = j == k ? 0.0 - ci * piv : __builtin_fma(-ci, rkj, a);
+    }
+    out[(size_t)i * NP + j] = v;
+  }
+}
+
+// k_bc_pivot for two matrices in one launch: blockIdx.z chooses (in, out, flag word) of K or of H = (P~ + delta I)^-1, which
+// a model update on a handle with the shared KKT pieces inverts side by side -- the 2n pivot launches are launch-bound and
+// the two sequences independent.  The same expression per entry as k_bc_pivot, hence the same bits.
+struct BCPair { const double *in[2]; double *out[2]; int *flag[2]; };
+__global__ void __launch_bounds__(256) k_bc_pivot2(BCPair a, int n, int NP, int k) {
+  const bool h = blockIdx.z != 0;                   // (selects, not an index: the argument stays in scalar registers)
+  const double *__restrict__ in = h ? a.in[1] : a.in[0];
+  double *__restrict__ out = h ? a.out[1] : a.out[0];
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  const double akk = in[(size_t)k * NP + k];
+  const double piv = 1.0 / akk;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) {
+    int *flag = h ? a.flag[1] : a.flag[0];
+    int f = k == 0 ? BF_OPEN : flag[0];
+    if (!(akk > 0.0)) f |= BF_NOT_PD;
+    flag[0] = f;
+  }
+  if (j >= NP) return;
+  const double rkj = j < n ? in[(size_t)k * NP + j] * piv : 0.0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = blockIdx.y * 16 + threadIdx.y + 4 * r;
+    if (i >= NP) continue;
+    const double v0 = in[(size_t)i * NP + j];
+    double v = v0;
+    if (i < n && j < n) {
+      const double ci = in[(size_t)i * NP + k];
+      if (i == k) v = j == k ? piv : rkj;
+      else v = j == k ? 0.0 - ci * piv : __builtin_fma(-ci, rkj, v0);
     }
     out[(size_t)i * NP + j] = v;
   }

@@ -137,6 +137,12 @@ extern "C" c_int osqp_amd_batch_update_matrices_dev(osqp_amd_batch *b,
   return 0;
 }
 
+// (one body with its host twin, bc_update_model in batch.hip: the device pointers are checked after the host lists)
+extern "C" c_int osqp_amd_batch_common_update_model_dev(osqp_amd_batch *b, const c_float *Px, const c_int *Px_idx, c_int P_n,
+                                                        const c_float *Ax, const c_int *Ax_idx, c_int A_n) {
+  return bc_update_model(b, true, "osqp_amd_batch_common_update_model_dev", Px, Px_idx, P_n, Ax, Ax_idx, A_n);
+}
+
 extern "C" c_int osqp_amd_batch_warm_start_dev(osqp_amd_batch *b, const c_float *X, const c_float *Y) {
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (X || Y) {

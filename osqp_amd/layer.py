@@ -86,7 +86,8 @@ class _BatchQPFunction(torch.autograd.Function):
             h.adjoint_into(dX, dY, status_adjoint=sa, **g)
             layer.last_status_adjoint = sa
             zero = lambda w, cols: new(h.B, cols).zero_() if w else None        # (m = 0: the empty gradients of L, U)
-            outs = (g["dq"], g["dl"] if m else zero(need[1], 0), g["du"] if m else zero(need[2], 0), g["dPx"], g["dAx"])
+            outs = (g["dq"], g["dl"] if m else zero(need[1], 0), g["du"] if m else zero(need[2], 0),
+                    layer._shared_grad(g["dPx"]), layer._shared_grad(g["dAx"]))
             return (None,) + tuple(o if w else None for o, w in zip(outs, need))
         if layer._serial != ctx.serial:      # the handle has solved another problem since: bring this one back
             layer._solve(*ctx.args)
@@ -95,14 +96,15 @@ class _BatchQPFunction(torch.autograd.Function):
         a = layer.h.adjoint(dX, _host(gY), matrices=need[3] or need[4])
         layer.last_status_adjoint = a.status_adjoint
         outs = (a.dq, a.dl, a.du, a.dPx, a.dAx)
-        return (None,) + tuple(torch.as_tensor(g, dtype=ref.dtype, device=ref.device) if w else None
-                               for g, w in zip(outs, need))
+        outs = tuple(torch.as_tensor(g, dtype=ref.dtype, device=ref.device) if w else None for g, w in zip(outs, need))
+        return (None,) + outs[:3] + (layer._shared_grad(outs[3]), layer._shared_grad(outs[4]))
 
     @staticmethod
     def jvp(ctx, _, tQ, tL, tU, tPx, tAx):
         """Forward mode (torch.autograd.forward_ad): the tangents of X and Y from those of Q, L, U, Px, Ax (None = 0)
         by BatchOSQP.tangent on the host route and tangent_into on the device route."""
         layer = ctx.layer
+        tPx, tAx = layer._shared_tangent(tPx), layer._shared_tangent(tAx)
         if ctx.route == "device":
             if layer._serial != ctx.serial:
                 layer._solve_device(*(_dev(t) for t in ctx.saved_tensors))
@@ -138,8 +140,10 @@ class BatchQPLayer(torch.nn.Module):
     polish=True polishes the solved members after every solve (BatchOSQP.polish), so the point differentiated is the
     polished one where polish is accepted.  engine and **settings are BatchOSQP.setup's (the handle is set up at the
     first call and kept: later calls update it, and solves are warm-started unless warm_start=0).  engine="common" (one
-    model, many right-hand sides) needs shared_kkt=True, takes no Px / Ax, and raises RuntimeError naming member and
-    row when the bounds of a call give a row different classes in two members.  Gradients come
+    model, many right-hand sides) needs shared_kkt=True, takes Px [nnz(triu P)] and Ax [nnz(A)] as the values of the one
+    shared model (1-D; later calls bring them to the live handle through BatchOSQP.update_model, their gradient is the
+    sum over the members and a tangent counts for every member) and no per-member [B, k] values, and raises RuntimeError
+    naming member and row when the bounds of a call give a row different classes in two members.  Gradients come
     back for exactly the inputs that require them.  A gradient with respect to an off-diagonal Px slot counts both
     halves of the symmetric P.  Members whose solve did not end `solved` (or whose KKT matrix is rejected) get zero
     gradients; `last_status_adjoint` [B] (1 computed, -1 rejected, 0 not tried) and `last_results` say which.  Where active
@@ -168,11 +172,35 @@ class BatchQPLayer(torch.nn.Module):
         self._device = None              # device route: the device index the handle was set up on
         self._vals = {}                  # the layer's own P / A values as tensors on the handle's device
 
+    def _shared_grad(self, g):
+        """engine="common": the gradient of a shared value is the sum over the members of the adjoint's [B, k] rows."""
+        return g.sum(0) if self.engine == "common" and g is not None else g
+
+    def _shared_tangent(self, t):
+        """engine="common": the tangent of a shared value, [k], as the [B, k] array tangent / tangent_into take."""
+        return t.expand(self.h.B, -1) if self.engine == "common" and t is not None else t
+
+    def _setup(self, Q, L, U, Px, Ax, **where):
+        """The handle from host arrays.  engine="common": Px / Ax are the shared model's values, [k]."""
+        if self.engine != "common":
+            return BatchOSQP().setup(self.P, self.A, Q, L, U, Px_all=Px, Ax_all=Ax, engine=self.engine, **where, **self.settings)
+        with_values = lambda M, v: M if v is None else sparse.csc_matrix((v, M.indices, M.indptr), shape=M.shape)
+        return BatchOSQP().setup(with_values(self.P, Px), with_values(self.A, Ax), Q, L, U, engine=self.engine, **where,
+                                 **self.settings)
+
+    def _update_values(self, vP, vA):
+        if self.engine == "common":
+            rc, call = self.h.update_model(Px=vP, Ax=vA), "update_model"
+        else:
+            rc, call = self.h.update_matrices(Px=vP, Ax=vA), "update_matrices"
+        if rc:
+            raise RuntimeError("BatchOSQP.%s failed (%d)" % (call, rc))
+
     def _solve(self, Q, L, U, Px, Ax):
         if self.h is not None and self.h.B != Q.shape[0]:
             self.h.cleanup(); self.h = None
         if self.h is None:
-            self.h = BatchOSQP().setup(self.P, self.A, Q, L, U, Px_all=Px, Ax_all=Ax, engine=self.engine, **self.settings)
+            self.h = self._setup(Q, L, U, Px, Ax)
             self._device = None
         else:
             rc = self.h.update(Q=Q, L=L, U=U)
@@ -182,9 +210,7 @@ class BatchQPLayer(torch.nn.Module):
             vP = Px if Px is not None else (self.P.data if self._own[0] else None)
             vA = Ax if Ax is not None else (self.A.data if self._own[1] else None)
             if vP is not None or vA is not None:
-                rc = self.h.update_matrices(Px=vP, Ax=vA)
-                if rc:
-                    raise RuntimeError("BatchOSQP.update_matrices failed (%d)" % rc)
+                self._update_values(vP, vA)
         self._own = [Px is not None, Ax is not None]
         self.h.solve(fetch=False)
         self.last_results = self.h.polish() if self.polish else self.h.results()
@@ -222,8 +248,7 @@ class BatchQPLayer(torch.nn.Module):
         m = self.A.shape[0] > 0
         _hand_over(dev)
         if self.h is None:
-            self.h = BatchOSQP().setup(self.P, self.A, *(_host(t) for t in (Q, L, U)), Px_all=_host(Px), Ax_all=_host(Ax),
-                                       engine=self.engine, device=index, **self.settings)
+            self.h = self._setup(*(_host(t) for t in (Q, L, U, Px, Ax)), device=index)
             self._device = index
         else:
             rc = self.h.update(Q=Q, L=L if m else None, U=U if m else None)
@@ -235,9 +260,7 @@ class BatchQPLayer(torch.nn.Module):
             vA = Ax if Ax is not None else (self._own_values("A", dev) if self._own[1] else None)
             if vP is not None or vA is not None:
                 _hand_over(dev)
-                rc = self.h.update_matrices(Px=vP, Ax=vA)
-                if rc:
-                    raise RuntimeError("BatchOSQP.update_matrices failed (%d)" % rc)
+                self._update_values(vP, vA)
         self._own = [Px is not None, Ax is not None]
         self.h.solve(fetch=False)
         if self.polish:
@@ -255,17 +278,22 @@ class BatchQPLayer(torch.nn.Module):
     def forward(self, Q, L, U, Px=None, Ax=None, return_y=False):
         B = Q.shape[0] if Q.dim() == 2 else -1
         n, m = self.P.shape[0], self.A.shape[0]
+        common = self.engine == "common"
         for name, t, cols in (("Q", Q, n), ("L", L, m), ("U", U, m), ("Px", Px, self.P.nnz), ("Ax", Ax, self.A.nnz)):
             if t is None:
                 continue
             if t.dtype != torch.float64:
                 raise TypeError("%s must be a float64 tensor, not %s" % (name, t.dtype))
-            if tuple(t.shape) != (B, cols):
+            if common and name in ("Px", "Ax") and t.dim() == 1:       # the shared model's values
+                if tuple(t.shape) != (cols,):
+                    raise ValueError("%s must be [%d] (the shared model of engine='common'), not %s" % (name, cols, tuple(t.shape)))
+            elif tuple(t.shape) != (B, cols):
                 raise ValueError("%s must be [B, %d], not %s" % (name, cols, tuple(t.shape)))
             if t.device != Q.device:
                 raise ValueError("%s is on %s and Q on %s: every tensor of a call lives on one device" % (name, t.device, Q.device))
-        if self.engine == "common" and (Px is not None or Ax is not None):
-            raise ValueError("engine='common' shares P and A over the batch: the layer takes no Px / Ax")
+        if common and any(t is not None and t.dim() != 1 for t in (Px, Ax)):
+            raise ValueError("engine='common' shares P and A over the batch: the layer takes no Px / Ax per member ([B, k]); "
+                             "pass the shared model's values as [k]")
         X, Y = _BatchQPFunction.apply(self, Q, L, U, Px, Ax)
         return (X, Y) if return_y else X
 
