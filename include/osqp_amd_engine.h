@@ -187,6 +187,16 @@ int hipeng_resident_trips(hipeng *e, long long out[8]);
  * workgroup, [7] threads that hold entries (448).  Optional outputs may be NULL. */
 int hipeng_resident_plan(const csc *P, const csc *A, int nwg, long long stats[8], int *Kptr, int *Kcol, int *kdst, long long cap,
                          unsigned short *rowpos, unsigned short *slotcol, int *wg4);
+/* The contribution lists of that plan, from which k_form_K_lists forms the values of K: entry e of K (in the order of the
+ * plan's Kcol) is P_ij + sigma [i == j] plus the terms Kcp[e] .. Kcp[e + 1]; term q is rho_k a_ki a_kj with a_ki at slot Kcm[q] of
+ * M = [P | A'] (its column there is n + k) and a_kj at slot Kca[q] of the CSR copy of A, rows k ascending.  Kcp: nnz(K) + 1, Kcm /
+ * Kca: cap terms at most; outputs may be NULL.  Returns the number of terms (the sum over the rows of A of nnz^2), -1 when the
+ * problem does not qualify, -2 when the lists are switched off (OSQP_AMD_FORM_K_LISTS=0) or over their budget
+ * (OSQP_AMD_FORM_K_LIST_MB, default 128; more than 2^31 - 1 terms count as over), or a HIPENG_ERR_* code. */
+long long hipeng_resident_plan_lists(const csc *P, const csc *A, int nwg, int *Kcp, int *Kcm, int *Kca, long long cap);
+/* How the resident PCG forms K: out[0] 1 from contribution lists (k_form_K_lists), 0 by the merge on the device (k_form_K);
+ * [1] terms, [2] bytes of the list arrays on the device, [3] their budget in bytes. */
+int hipeng_form_k_info(hipeng *e, long long out[4]);
 /* For the tests: K as the resident kernel holds it, as triplets; returns nnz(K) or a negative code. */
 long long hipeng_resident_dump(hipeng *e, int *row, int *col, double *val, long long cap);
 

@@ -1319,6 +1319,8 @@ struct ResCtx {
   unsigned *flags;                   // nwg x RES_FSTRIDE words (one 128-byte line each)
   int *dbg;                          // nwg x RES_DBG, written by a launch that gives up: see res_note()
   double *sbuf;                      // 2 x nwg x RES_GSTRIDE 8-byte words: six granules {32 bits of a double, tag} per workgroup, one line each
+  const int *kcp, *kcm, *kca;        // contribution lists of k_form_K_lists (null: k_form_K forms K): entry e of K (the order of kcj) sums the terms
+                                     // kcp[e] .. kcp[e + 1], term q = rhoe[M.col[kcm[q]] - n] * (M.val[kcm[q]] * A.val[kca[q]]), rows of A ascending
 };
 
 static __device__ __forceinline__ __amdgpu_buffer_rsrc_t res_rsrc(const void *p, size_t bytes) {
@@ -1426,6 +1428,91 @@ __global__ void __launch_bounds__(TB) k_form_K(Ctx c, ResCtx rc) {
           rc.val[rc.kdst[idx]] = gone ? (j[q] == i ? 1.0 : 0.0) : v[q];
         }
       }
+    }
+  }
+}
+
+// The same values from contribution lists (build_resident): which rows k of A reach entry (i, j), and where a_ki and a_kj
+// sit, depends on the patterns alone, so the merge above is done once on the host and this kernel only streams its result:
+// every entry adds its terms in list order (ascending k: the order, the operands and the association of k_form_K, so the
+// bits are the same).  The kernel is a chain of dependent loads (offsets -> slots -> values -> weight), so it is laid out for
+// few links and many loads per link.  One wavefront per row i of K, four entries per lane.  Nearly every entry has one
+// term or none: the first FKL_T terms of all four entries are gathered in one flight per link and added by the lane itself
+// (a term the list does not have reads term 0 -- a real slot, one line for all such lanes -- and is not added).  An entry
+// with more (the diagonal: as many as column i of A has rows) is finished by the whole wavefront: lane t gathers term t,
+// then the products are added in order through readlane.
+#define FKL_T 2
+__global__ void __launch_bounds__(TB) k_form_K_lists(Ctx c, ResCtx rc) {
+  const double sigma = c.prm->sigma;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {     // a new K: the pipelined recurrences and the predicted last trip get another chance
+    c.st->res_pipe_off = 0;
+    c.st->res_pred_off = 0; c.st->res_pred_win[0] = 0; c.st->res_pred_win[1] = 0; c.st->res_pred_win[2] = 0;
+  }
+  const int lane = threadIdx.x & 63, nwaves = gridDim.x * (TB / 64);
+  for (int i = blockIdx.x * (TB / 64) + (threadIdx.x >> 6); i < c.n; i += nwaves) {
+    const int e0 = rc.krp[i], e1 = rc.krp[i + 1];
+    const bool igone = c.nelim && c.erow[i] >= 0;
+    for (int eb = e0; eb < e1; eb += 256) {
+      int j[4], ps[4], dst[4], q0[4], len[4]; double v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int idx = min(eb + q * 64 + lane, e1 - 1);          // (lanes past the row read its last entry and store nothing)
+        j[q] = rc.kcj[idx]; ps[q] = rc.kps[idx]; dst[q] = rc.kdst[idx];
+        q0[q] = rc.kcp[idx]; len[q] = eb + q * 64 + lane < e1 ? rc.kcp[idx + 1] - q0[q] : 0;
+      }
+      bool any = false;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        v[q] = (ps[q] >= 0 ? c.M.val[ps[q]] : 0.0) + (j[q] == i ? sigma : 0.0);
+        any = any || len[q] > 0;
+      }
+      if (__ballot(any)) {                       // (some entry of this pass has a term: the lists are not empty, term 0 exists)
+        int pm[4][FKL_T], pa[4][FKL_T], kk[4][FKL_T];
+        double am[4][FKL_T], aa[4][FKL_T], rk[4][FKL_T];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int t = 0; t < FKL_T; ++t) { const int s = t < len[q] ? q0[q] + t : 0; pm[q][t] = rc.kcm[s]; pa[q][t] = rc.kca[s]; }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int t = 0; t < FKL_T; ++t) { kk[q][t] = c.M.col[pm[q][t]] - c.n; am[q][t] = c.M.val[pm[q][t]]; aa[q][t] = c.A.val[pa[q][t]]; }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int t = 0; t < FKL_T; ++t) rk[q][t] = c.rhoe[kk[q][t]];     // (rhoe: the rows' effective weights when variables are eliminated, rho itself otherwise)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int t = 0; t < FKL_T; ++t) if (t < len[q]) v[q] += rk[q][t] * (am[q][t] * aa[q][t]);
+        // the longer lists, one after the other
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          unsigned long long pend = __ballot(len[q] > FKL_T);
+          while (pend) {
+            const int l = __ffsll((long long)pend) - 1;
+            pend &= pend - 1;
+            const int s0 = lane_int(q0[q], l) + FKL_T, s1 = s0 - FKL_T + lane_int(len[q], l);
+            double acc = lane_value(v[q], l);
+            for (int sb = s0; sb < s1; sb += 64) {
+              const int s = sb + lane < s1 ? sb + lane : 0;
+              const int m_ = rc.kcm[s], a_ = rc.kca[s];
+              const int k_ = c.M.col[m_] - c.n;
+              const double prod = c.rhoe[k_] * (c.M.val[m_] * c.A.val[a_]);
+              const int cnt = min(64, s1 - sb);
+              for (int t = 0; t < cnt; ++t) acc += lane_value(prod, t);
+            }
+            if (lane == l) v[q] = acc;
+          }
+        }
+      }
+      // eliminated variables: see k_form_K
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (eb + q * 64 + lane < e1) {
+          const bool gone = c.nelim && (igone || c.erow[j[q]] >= 0);
+          rc.val[dst[q]] = gone ? (j[q] == i ? 1.0 : 0.0) : v[q];
+        }
     }
   }
 }
@@ -2921,6 +3008,8 @@ struct hipeng {
   std::vector<int> erow, ecol, epos;   // host images of Ctx::erow / ecol / epos (empty: no variable is eliminated)
   size_t res_lds = 0;
   long long res_nnz = 0;
+  bool fk_lists = false;     // resident PCG: k_form_K_lists forms K (else k_form_K); terms, bytes of the lists, their budget in bytes
+  long long fk_terms = 0, fk_bytes = 0, fk_budget = 0;
 };
 
 template <typename T>
@@ -3249,6 +3338,7 @@ static void parallel_chunks(int count, int min_chunk, F fn) {
 struct ResPlanOut {
   bool ok = false; int nwg = 0, E = 0, npad = 0; long long nnzK = 0;
   std::vector<ResWG> wg; std::vector<int> Kptr, Kcol, kdst; std::vector<unsigned short> rowpos, col; std::vector<unsigned long long> brk;
+  bool lists = false; std::vector<int> Kcp, Kcm, Kca;     // the contribution lists of k_form_K_lists, where they are in use
 };
 static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr) {
   e->res_on = e->res_use = false;
@@ -3281,15 +3371,28 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
   // pattern of K, row by row (sorted), with the slot of P(i,j) in M
   const size_t cap_total = (size_t)nwg * RES_PT * 64;
   std::vector<int> Kptr(n + 1, 0), Kcol, Kps;
+  // Contribution lists for k_form_K_lists: for entry e of K, in the order of Kcol, the terms Kcp[e] .. Kcp[e + 1]; term q is row
+  // k of A with a_ki at slot Kcm[q] of M and a_kj at slot Kca[q] of A, rows ascending (the order of column i in M).  Every pair
+  // of entries of a row of A is one term: sum_k nnz(A_k)^2 of them, known before the pass, so that the budget
+  // (OSQP_AMD_FORM_K_LIST_MB, 8 bytes per term + 4 per entry of K) decides the same for any number of threads.
+  std::vector<int> Kcp, Kcm, Kca;
+  long long fk_terms = 0, fk_budget = 128LL << 20;
+  bool fk_lists = true;
+  if (const char *x = getenv("OSQP_AMD_FORM_K_LISTS")) fk_lists = atoi(x) != 0;
+  if (const char *x = getenv("OSQP_AMD_FORM_K_LIST_MB")) fk_budget = (long long)std::max(0.0, std::min(1e6, atof(x))) << 20;
+  for (int k = 0; k < e->m; k++) { const long long len = A.rowptr[k + 1] - A.rowptr[k]; fk_terms += len * len; }
+  auto fk_bytes = [&](long long entries) { return 8 * fk_terms + 4 * (entries + 1); };
+  if (fk_terms > 0x7fffffffLL || fk_bytes(n) > fk_budget) fk_lists = false;      // (K has n entries at least: the diagonal)
   {
     // rows in contiguous chunks, one thread each with its own scratch; the chunks' lists are joined in order afterwards
-    std::vector<std::vector<int>> cKcol(64), cKps(64), cLen(64);
+    std::vector<std::vector<int>> cKcol(64), cKps(64), cLen(64), cCnt(64), cCm(64), cCa(64);
     std::atomic<int> bad{0};
     int used = 1;
     parallel_chunks(n, 256, [&](int lo, int hi, int tid, int T) {
       if (tid == 0) used = T;
       std::vector<int> mark(n, -1), pslot(n, -1);
-      std::vector<int> &kc = cKcol[tid], &kp = cKps[tid], &ln = cLen[tid];
+      std::vector<int> &kc = cKcol[tid], &kp = cKps[tid], &ln = cLen[tid], &cn = cCnt[tid], &cm = cCm[tid], &ca = cCa[tid];
+      std::vector<size_t> fill;
       kc.reserve((size_t)(hi - lo) * 64); ln.reserve(hi - lo);
       for (int i = lo; i < hi && !bad.load(std::memory_order_relaxed); i++) {
         const size_t start = kc.size();
@@ -3310,6 +3413,26 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
         kp.resize(kc.size());
         for (size_t q = start; q < kc.size(); q++) kp[q] = pslot[kc[q]];
         ln.push_back((int)(kc.size() - start));
+        if (fk_lists) {
+          // the terms of this row's entries: counted per entry, then filled in the order of column i (ascending k)
+          const size_t len = kc.size() - start, cstart = cn.size(), tstart = cm.size();
+          for (size_t q = start; q < kc.size(); q++) pslot[kc[q]] = (int)(q - start);      // (pslot has served: now the entry's place in the row)
+          cn.resize(cstart + len, 0);
+          size_t terms = 0;
+          for (int k = M.split[i]; k < M.rowptr[i + 1]; k++) {
+            const int row = M.col[k] - n;
+            for (int q = A.rowptr[row]; q < A.rowptr[row + 1]; q++) cn[cstart + pslot[A.col[q]]]++;
+            terms += A.rowptr[row + 1] - A.rowptr[row];
+          }
+          fill.resize(len);
+          size_t at = tstart;
+          for (size_t q = 0; q < len; q++) { fill[q] = at; at += cn[cstart + q]; }
+          cm.resize(tstart + terms); ca.resize(tstart + terms);
+          for (int k = M.split[i]; k < M.rowptr[i + 1]; k++) {
+            const int row = M.col[k] - n;
+            for (int q = A.rowptr[row]; q < A.rowptr[row + 1]; q++) { const size_t d = fill[pslot[A.col[q]]]++; cm[d] = k; ca[d] = q; }
+          }
+        }
       }
     });
     if (bad.load() == 1) RES_NO("P repeats an entry");
@@ -3322,6 +3445,16 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
       Kcol.insert(Kcol.end(), cKcol[k].begin(), cKcol[k].end());
       Kps.insert(Kps.end(), cKps[k].begin(), cKps[k].end());
       for (int len : cLen[k]) { Kptr[row + 1] = Kptr[row] + len; row++; }
+    }
+    if (fk_lists && fk_bytes((long long)tot) > fk_budget) fk_lists = false;
+    if (fk_lists) {
+      Kcp.reserve(tot + 1); Kcm.reserve((size_t)fk_terms); Kca.reserve((size_t)fk_terms);
+      Kcp.push_back(0);
+      for (int k = 0; k < used; k++) {
+        for (int cnt : cCnt[k]) Kcp.push_back(Kcp.back() + cnt);
+        Kcm.insert(Kcm.end(), cCm[k].begin(), cCm[k].end());
+        Kca.insert(Kca.end(), cCa[k].begin(), cCa[k].end());
+      }
     }
   }
   const long long nnzK = Kptr[n];
@@ -3458,6 +3591,7 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
   if (po) {                      // plan only (no device): hand the layout out
     po->ok = true; po->nwg = nwg; po->E = E; po->npad = npad; po->nnzK = nnzK;
     po->wg = wg; po->Kptr = Kptr; po->Kcol = Kcol; po->kdst = kdst; po->rowpos = rowpos; po->col = col; po->brk = brk;
+    po->lists = fk_lists; po->Kcp = Kcp; po->Kcm = Kcm; po->Kca = Kca;
     return 0;
   }
   ResCtx rc{};
@@ -3481,6 +3615,13 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
       dev_alloc(e, &d_segrow, segrow.size()) || dev_alloc(e, &d_rowpos, rowpos.size()) || dev_alloc(e, &rc.ubuf, (size_t)2 * rc.npad) ||
       dev_alloc_polled(e, &rc.flags, (size_t)nwg * RES_FSTRIDE) || dev_alloc(e, &rc.dbg, (size_t)nwg * RES_DBG) || dev_alloc_polled(e, &rc.sbuf, (size_t)2 * nwg * RES_GSTRIDE)) return HIPENG_ERR_HIP;
 #define UP(dst, src) HIPCHK(hipMemcpyAsync(dst, (src).data(), (src).size() * sizeof((src)[0]), hipMemcpyHostToDevice, e->stream))
+  if (fk_lists) {
+    int *d_kcp = nullptr, *d_kcm = nullptr, *d_kca = nullptr;
+    if (dev_alloc(e, &d_kcp, Kcp.size()) || dev_alloc(e, &d_kcm, Kcm.size()) || dev_alloc(e, &d_kca, Kca.size())) return HIPENG_ERR_HIP;
+    UP(d_kcp, Kcp); UP(d_kcm, Kcm); UP(d_kca, Kca);
+    rc.kcp = d_kcp; rc.kcm = d_kcm; rc.kca = d_kca;
+  }
+  e->fk_lists = fk_lists; e->fk_terms = fk_terms; e->fk_bytes = fk_lists ? fk_bytes(nnzK) : 0; e->fk_budget = fk_budget;
   UP(d_wg, wg); UP(d_rowpos, rowpos); UP(d_col, col); UP(d_rowl, rowl); UP(d_krp, Kptr); UP(d_kcj, Kcol); UP(d_kps, Kps); UP(d_kdst, kdst); UP(d_brk, brk); UP(d_slot0, slot0); UP(d_segrow, segrow);
 #undef UP
   HIPCHK(hipStreamSynchronize(e->stream));       // the sources are locals
@@ -3756,7 +3897,10 @@ static void refresh_operator(hipeng *e) {
   // (the Jacobi preconditioner: one thread per column -- 1.3 ms on the Lasso's 1 500-entry columns -- and of no use to a dense-direct
   // engine; direct_disable forms it when such an engine goes back to the PCG kernels)
   if (e->res_kind != 4) hipLaunchKernelGGL(k_precond, dim3(elem_grid(e->n)), dim3(TB), 0, e->stream, e->c);
-  if (e->res_kind == 1) hipLaunchKernelGGL(k_form_K, dim3(std::min(2048, (e->n + 3) / 4)), dim3(TB), 0, e->stream, e->c, e->rc);
+  if (e->res_kind == 1) {
+    if (e->rc.kcp) hipLaunchKernelGGL(k_form_K_lists, dim3((e->n + 3) / 4), dim3(TB), 0, e->stream, e->c, e->rc);
+    else hipLaunchKernelGGL(k_form_K, dim3(std::min(2048, (e->n + 3) / 4)), dim3(TB), 0, e->stream, e->c, e->rc);
+  }
   if (e->res_kind == 3 && blk_refresh(e)) fprintf(stderr, "osqp_amd: the block-direct solve could not be refreshed\n");
   if (e->res_kind == 4 && dd_refresh(e)) fprintf(stderr, "osqp_amd: the dense-direct solve could not be refreshed\n");
 }
@@ -4710,6 +4854,26 @@ extern "C" int hipeng_resident_plan(const csc *P, const csc *A, int nwg, long lo
   return 0;
 }
 
+// The contribution lists of that plan (k_form_K_lists), for the CPU tests: Kcp (nnz(K) + 1 offsets, entries in the order of the
+// plan's Kcol), Kcm / Kca (slot in M of a_ki, slot in the CSR copy of A of a_kj; cap terms at most).  Outputs may be NULL.
+// Returns the number of terms, -1 when the problem does not qualify for the resident PCG, -2 when it does but the lists are
+// switched off or over their budget (OSQP_AMD_FORM_K_LISTS, OSQP_AMD_FORM_K_LIST_MB), or a HIPENG_ERR_* code.
+extern "C" long long hipeng_resident_plan_lists(const csc *P, const csc *A, int nwg, int *Kcp, int *Kcm, int *Kca, long long cap) {
+  if (!P || !A || P->n > 0x7ffffff0LL || A->m > 0x7ffffff0LL) return HIPENG_ERR_ARG;
+  hipeng tmp;
+  tmp.n = (int)P->n; tmp.m = (int)A->m;
+  build_A(&tmp, A); build_M(&tmp, P, A); build_dense(&tmp, P);
+  ResPlanOut po;
+  if (const int rc = build_resident(&tmp, nwg, &po)) return rc;
+  if (!po.ok) return -1;
+  if (!po.lists) return -2;
+  const long long terms = (long long)po.Kcm.size();
+  if (Kcp) std::copy(po.Kcp.begin(), po.Kcp.end(), Kcp);
+  if (terms <= cap) { if (Kcm) std::copy(po.Kcm.begin(), po.Kcm.end(), Kcm); if (Kca) std::copy(po.Kca.begin(), po.Kca.end(), Kca); }
+  else if (Kcm || Kca) return HIPENG_ERR_ARG;
+  return terms;
+}
+
 #ifdef OSQP_AMD_TIMELINE
 // make TIMELINE=1 builds only: copy out (and reset) the kernel start marks; returns their number
 extern "C" long long hipeng_timeline(hipeng *e, unsigned long long *out, long long cap) {
@@ -4769,6 +4933,16 @@ extern "C" int hipeng_resident_info(hipeng *e, long long out[16]) {
   if (e->res_kind == 2) { out[2] = 64; out[3] = e->bc.nwg; out[4] = 0; out[5] = 0; }
   if (e->res_kind == 3) { out[2] = 0; out[3] = e->c.dP.nblk; out[4] = 0; out[5] = 0; }
   if (e->res_kind == 4) { out[2] = 0; out[3] = e->dd.na; out[4] = (long long)e->dd.nap * e->dd.nap; out[5] = e->dd_chol ? 1 : 0; out[15] = e->dd.nb2; }
+  return 0;
+}
+
+// How the resident PCG forms K: out[0] 1 k_form_K_lists (contribution lists built at set-up), 0 k_form_K; [1] terms of the
+// lists (sum over the rows of A of nnz^2, whether or not they were built), [2] bytes of the list arrays on the device (0: none),
+// [3] their budget in bytes (OSQP_AMD_FORM_K_LIST_MB).  All 0 for an engine on another form.
+extern "C" int hipeng_form_k_info(hipeng *e, long long out[4]) {
+  if (!e || !out) return HIPENG_ERR_ARG;
+  const bool res = e->res_kind == 1;
+  out[0] = res && e->fk_lists; out[1] = res ? e->fk_terms : 0; out[2] = res ? e->fk_bytes : 0; out[3] = res ? e->fk_budget : 0;
   return 0;
 }
 
