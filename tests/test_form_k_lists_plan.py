@@ -10,6 +10,7 @@ from scipy import sparse
 import osqp_amd
 from osqp_amd import _abi as abi
 from tests import _form_k_cases as FC
+from tests._form_k_reference import _slots
 from tests.test_resident_plan import _plan, _qp
 
 
@@ -26,24 +27,6 @@ def _lists(P, A, nwg=256):
     Kcp = np.zeros(st[3] + 1, dtype=np.int32); Kcm = np.zeros(max(terms, 1), dtype=np.int32); Kca = np.zeros(max(terms, 1), dtype=np.int32)
     assert f(C.byref(Pu.struct), C.byref(Ah.struct), nwg, Kcp.ctypes.data, Kcm.ctypes.data, Kca.ctypes.data, terms) == terms
     return terms, Kcp, Kcm[:terms], Kca[:terms]
-
-
-def _slots(P, A):
-    """Where the engine keeps the entries of A (build_A, build_M): for every entry of the CSR copy of A (columns ascending in a
-    row) its row, its column and its slot in M -- row i of M holds the stored entries of row i of P (both triangles), then
-    column i of A with rows ascending."""
-    n = P.shape[0]
-    Pu = sparse.triu(P, format="coo")
-    per_row = np.bincount(Pu.row, minlength=n) + np.bincount(Pu.col[Pu.row != Pu.col], minlength=n)
-    Ac = sparse.csc_matrix(A); Ac.sort_indices()
-    acol = np.diff(Ac.indptr)
-    rowptr = np.concatenate([[0], np.cumsum(per_row + acol)])
-    split = rowptr[:-1] + per_row
-    in_m = np.repeat(split - Ac.indptr[:-1], acol) + np.arange(Ac.nnz)          # slot in M of every entry in CSC order
-    tag = sparse.csc_matrix((np.arange(Ac.nnz) + 1.0, Ac.indices, Ac.indptr), shape=Ac.shape).tocsr()
-    tag.sort_indices()
-    csc_of_csr = tag.data.astype(np.int64) - 1
-    return np.repeat(np.arange(A.shape[0]), np.diff(tag.indptr)), tag.indices.astype(np.int64), in_m[csc_of_csr], Ac
 
 
 def _check(P, A, nwg=256):
@@ -98,6 +81,9 @@ def test_lists_against_scipy_at_the_edges(name, monkeypatch):
         assert terms >= 65 * 65
     if name == "m0":
         assert terms == 0 and not Kcp.any()
+    # the new cases say themselves what they are there for (the turns of k_form_K_lists's own loops)
+    pl = _plan(P, A)[1]
+    FC.check_premise(name, pl["Kptr"], pl["Kcol"], lens)
 
 
 def test_lists_of_a_mid_size_problem_do_not_depend_on_the_setup_threads(monkeypatch):
