@@ -77,12 +77,12 @@ c_int osqp_amd_batch_setup_engine(osqp_amd_batch **out, c_int engine, c_int batc
  * Limits, each OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line naming the limit: 1 <= n <= 1024; a member's vectors
  * fit 160 KiB of LDS (the streamed engine's limit).  polish / time_limit > 0: OSQP_SETTINGS_VALIDATION_ERROR.
  * OSQP_NONCVX_ERROR when K is not positive definite.
- * Served: _update, _warm_start, _update_rho, _solve, _get, _device_ptrs, _shape, _rounds, _cleanup, _update_dev,
- * _warm_start_dev, _get_dev, _check_dev_ptr, _member (the common D, E, c, rho, classes, Pv, Av and the one K^-1,
- * NP x NP, for any qp).  Served once osqp_amd_batch_common_kkt(b, 1) has built the shared KKT pieces, and refused
- * without them: _polish, _polish_status_dev, _adjoint*, _tangent*, _kkt_info.  Never served: _update_matrices(_dev)
- * (its per-member value flags contradict the engine; new values of the one model go through
- * osqp_amd_batch_common_update_model below).
+ * Served: _update, _warm_start, _update_rho, _solve, _solve_members, _common_columns, _get, _device_ptrs, _shape,
+ * _rounds, _cleanup, _update_dev, _warm_start_dev, _get_dev, _check_dev_ptr, _member (the common D, E, c, rho,
+ * classes, Pv, Av and the one K^-1, NP x NP, for any qp).  Served once osqp_amd_batch_common_kkt(b, 1) has built the
+ * shared KKT pieces, and refused without them: _polish, _polish_status_dev, _adjoint*, _tangent*, _kkt_info.  Never
+ * served: _update_matrices(_dev) (its per-member value flags contradict the engine; new values of the one model go
+ * through osqp_amd_batch_common_update_model below).
  * A refused call returns OSQP_LINSYS_SOLVER_INIT_ERROR with a stderr line naming the engine and leaves the handle
  * untouched and usable. */
 #define OSQP_AMD_BATCH_COMMON 2   /* what osqp_amd_batch_shape reports for such a handle; setup_engine does not take it */
@@ -169,6 +169,32 @@ c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, const c_flo
 /* osqp_solve for every QP; iterates persist on the device between calls
  * (warm start, settings->warm_start). */
 c_int osqp_amd_batch_solve(osqp_amd_batch *b);
+/* osqp_solve for `count` chosen members of a common-K handle: members [count], strictly ascending, each in [0, batch).
+ * Only the listed members are loaded, iterated, checked, counted in the rho estimate (in member order) and stored: the
+ * columns of the solve are the listed members, so the GEMM and every other kernel shrink with the list.  Of a member
+ * that is not listed nothing changes: X, Y, info8 (all eight, its rho and rho_updates among them), both certificates
+ * and the stored scaled iterates keep their bits.  The listed members get the bits a handle set up on them alone would
+ * give as long as the scaling and rho agree (rho fixed, or adapted from the same members).  Where rho is adopted it is
+ * the batch's one rho from then on: K is re-formed and re-inverted as in a full solve and rho_updates of the running
+ * listed members goes up.
+ * It counts as a solve: a kept KKT inversion is dropped and a polish is forgotten.  The handle keeps one flag per member,
+ * "solved on the current problem": every update and warm start that makes polish, adjoint and tangent return
+ * OSQP_WORKSPACE_NOT_INIT_ERROR clears all of them, osqp_amd_batch_solve sets all, this call sets the listed ones, and
+ * those calls are served once every member's flag is set -- after update, solve_members(S) they are refused, after
+ * solve_members(the rest) they are served.
+ * Returns, in this order and with nothing of the handle changed: OSQP_WORKSPACE_NOT_INIT_ERROR for a NULL handle;
+ * OSQP_LINSYS_SOLVER_INIT_ERROR, with a stderr line naming the call and the engine, for a tiled or streamed handle;
+ * OSQP_DATA_VALIDATION_ERROR for NULL members, count < 1, count > batch, an index outside [0, batch) or a list that is
+ * not strictly ascending; OSQP_NONCVX_ERROR as osqp_amd_batch_solve.  count == batch is osqp_amd_batch_solve, to the bit. */
+c_int osqp_amd_batch_solve_members(osqp_amd_batch *b, const c_int *members, c_int count);
+/* Of the last solve of a common-K handle (either call): out[0] = the columns it started with (batch, or count),
+ * out[1] = packs, out[2] = the columns in use when it ended.  Whenever the members still running fit fewer groups of
+ * 64 columns than the columns in use, the solve moves them to the front, in member order, and every kernel runs on
+ * the shorter range from then on (a pack); results do not depend on it.  OSQP_AMD_BATCH_COMMON_PACK=0 in the
+ * environment when the handle is set up switches packing off.  Touches no GPU memory.  OSQP_WORKSPACE_NOT_INIT_ERROR
+ * for a NULL handle, OSQP_DATA_VALIDATION_ERROR for NULL out, OSQP_LINSYS_SOLVER_INIT_ERROR (stderr line) for a handle
+ * of another engine. */
+c_int osqp_amd_batch_common_columns(osqp_amd_batch *b, c_int out[3]);
 /* polish (src/polish.c:19-350) for every member whose last solve ended OSQP_SOLVED; the others are skipped.
  * Polish is this call on a solved handle, with settings->delta and settings->polish_refine_iter as given at setup;
  * settings->polish != 0 itself stays refused by the setup functions.  Per member, in its scaled space: the active

@@ -15,6 +15,7 @@ BATCH_MAX_N = 128     # register-tiled K^-1 of the batch kernel (batch.hip)
 STREAMED_MAX_N = 1024  # streamed-inverse engine (batch_streamed.h)
 ENGINES = {"tiled": 0, "streamed": 1, "common": 2}   # OSQP_AMD_BATCH_TILED / _STREAMED / _COMMON
 KktInfo = namedtuple("KktInfo", "builds kept npol members")     # BatchOSQP.kkt_info()
+Columns = namedtuple("Columns", "started packs ended")          # BatchOSQP.columns()
 INFO_FIELDS = ["iter", "status_val", "obj_val", "pri_res", "dua_res", "rho_updates", "rho_estimate", "rho"]
 
 
@@ -35,6 +36,10 @@ def _bind(L):
     L.osqp_amd_batch_warm_start.argtypes = [H, abi.c_float_p, abi.c_float_p]
     L.osqp_amd_batch_solve.restype = abi.c_int
     L.osqp_amd_batch_solve.argtypes = [H]
+    L.osqp_amd_batch_solve_members.restype = abi.c_int
+    L.osqp_amd_batch_solve_members.argtypes = [H, abi.c_int_p, abi.c_int]
+    L.osqp_amd_batch_common_columns.restype = abi.c_int
+    L.osqp_amd_batch_common_columns.argtypes = [H, abi.c_int_p]
     L.osqp_amd_batch_polish.restype = abi.c_int
     L.osqp_amd_batch_polish.argtypes = [H, abi.c_int_p]
     L.osqp_amd_batch_adjoint.restype = abi.c_int
@@ -126,6 +131,28 @@ def check_matrix_update(B, nnzP, nnzA, Px=None, Px_idx=None, Ax=None, Ax_idx=Non
                 raise ValueError("%sx_idx out of range [0, %d)" % (name, nnz))
         out += [V, I, int(len(shape) == 2)]
     return tuple(out)
+
+
+def check_members(B, members):
+    """The list checks of BatchOSQP.solve(members=...), as the C entry point makes them: an integer sequence, strictly
+    ascending, every index in [0, B), at least one; or a boolean mask of length B with at least one member set.
+    Returns the indices as the C side takes them."""
+    a = np.asarray(members)
+    if a.dtype == np.bool_:
+        if a.shape != (B,):
+            raise ValueError("a members mask must have length B = %d, not shape %s" % (B, a.shape))
+        a = np.flatnonzero(a)
+    elif a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("members must be an ascending integer sequence or a boolean mask of length B = %d" % B)
+    if a.size < 1:
+        raise ValueError("members is empty: a solve needs at least one member")
+    if a.size > B:
+        raise ValueError("members lists %d indices, the batch has %d members" % (a.size, B))
+    if a.min() < 0 or a.max() >= B:
+        raise ValueError("members out of range [0, %d)" % B)
+    if np.any(np.diff(a) <= 0):
+        raise ValueError("members must be strictly ascending (sorted, no duplicates)")
+    return abi.as_i64(a)
 
 
 def device_view(a, shape, typestr, writable=False, name="array"):
@@ -579,7 +606,22 @@ class BatchOSQP:
             return self._many_each(lambda b, s: s.warm_start(x=None if X is None else X[b], y=None if Y is None else Y[b]))
         return int(self._lib.osqp_amd_batch_warm_start(self._h, _p(X), _p(Y if self.m else None)))
 
-    def solve(self, fetch=True):
+    def solve(self, fetch=True, members=None):
+        """osqp_solve for every member, or (engine="common" only) for the listed ones: members is a strictly ascending
+        integer sequence or a boolean mask of length B.  Only the listed members are loaded, iterated and stored; of the
+        others nothing changes, and results() returns them as they were.  polish, adjoint and tangent are served once every
+        member has been solved on the current problem, by one call or by several."""
+        if members is not None:
+            if getattr(self, "engine", None) != "common" or self._many is not None or self._h is None:
+                raise RuntimeError("solve(members=...) is not served by the %s; it is a call of the common-K engine "
+                                   "(engine=\"common\")" % ("one-engine-per-member path (n > %d)" % BATCH_MAX_N
+                                                            if self._many is not None else "tiled or the streamed engine"))
+            members = check_members(self.B, members)
+            self._status_polish = None
+            rc = self._lib.osqp_amd_batch_solve_members(self._h, abi.iptr(members), members.size)
+            if rc:
+                raise RuntimeError("osqp_amd_batch_solve_members failed (%d)" % rc)
+            return self.results() if fetch else None
         if self._many is not None:
             from .multi import solve_many
             self._last = solve_many(self._many, max_workers=8)
@@ -589,6 +631,18 @@ class BatchOSQP:
         if rc:
             raise RuntimeError("osqp_amd_batch_solve failed (%d)" % rc)
         return self.results() if fetch else None
+
+    def columns(self):
+        """Of the last solve of a common-K handle: (started, packs, ended) -- the columns it started with (B, or the
+        number of listed members), how often it packed the running columns to the front, and the columns in use when it
+        ended.  Touches no GPU memory."""
+        if getattr(self, "engine", None) != "common" or self._h is None:
+            raise RuntimeError("columns is a call of the common-K engine (engine=\"common\")")
+        out = np.zeros(3, np.int64)
+        rc = self._lib.osqp_amd_batch_common_columns(self._h, abi.iptr(out))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_common_columns failed (%d)" % rc)
+        return Columns(*(int(v) for v in out))
 
     def polish(self, fetch=True):
         """Polish (src/polish.c) on the device for every member whose last solve ended `solved`, with the handle's

@@ -700,6 +700,8 @@ struct osqp_amd_batch {
   bool bc_rebuild = false;  // K^-1 no longer matches rho or the row classes
   bool bc_refine = false;   // the K^-1 solves take the refinement step (the verdict of the last probe)
   bool bc_open = false;     // the verdict is to be taken again: K^-1 is new
+  int bc_pack = 1;          // OSQP_AMD_BATCH_COMMON_PACK (0: the columns of a solve stay where they started)
+  int bc_cols[3] = {0, 0, 0};   // of the last solve: columns it started with, packs, columns in use when it ended
   BKkt bk{};                // the shared KKT pieces (batch_common_kkt.h), built by osqp_amd_batch_common_kkt
   int device = 0, tile = 8, threads = 512;
   long long B = 0;
@@ -728,6 +730,7 @@ struct osqp_amd_batch {
   BPol pol{};
   int *d_plist = nullptr;   // [B] the solved members, in index order
   bool solved = false;      // the iterates and info on the device are those of a solve of the current problem
+  std::vector<char> member_solved;   // ... per member (a solve of chosen members sets its own); solved = all of them
   bool polished = false;    // ... and polish has already run on them
   // adjoint and tangent (batch_adjoint.h, batch_tangent.h): the one staging set of the derivative calls.  Each of
   // them returns with the stream synchronised, so nothing is queued on it between calls.  in, out and mat grow with
@@ -752,6 +755,12 @@ struct osqp_amd_batch {
 };
 
 static void batch_launch(osqp_amd_batch *b, int phase);
+
+// the problem or the stored iterates have changed: no member's results are those of a solve of what the handle holds
+static void mark_unsolved(osqp_amd_batch *b) {
+  b->solved = false;
+  std::fill(b->member_solved.begin(), b->member_solved.end(), (char)0);
+}
 
 template <typename Tp>
 static int balloc(osqp_amd_batch *b, Tp **p, size_t cnt) {
@@ -839,6 +848,10 @@ static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
   // same bits; the switch exists to time them against k_bc_pivot2)
   e = getenv("OSQP_AMD_BATCH_MODEL_PIVOT2");
   b->bc_pivot2 = e ? atoi(e) : 1;
+  // 0: a solve of a common-K handle never packs its running columns (the same bits; the switch exists to compare and
+  // to time the two)
+  e = getenv("OSQP_AMD_BATCH_COMMON_PACK");
+  b->bc_pack = e ? atoi(e) : 1;
 }
 
 static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, const std::vector<int> &Pi,
@@ -912,6 +925,7 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
   osqp_amd_batch *b = new (std::nothrow) osqp_amd_batch();
   if (!b) return OSQP_MEM_ALLOC_ERROR;
   b->device = (int)device; b->B = batch; b->n = n; b->m = m;
+  b->member_solved.assign((size_t)batch, (char)0);
   b->engine = (int)engine; b->NPs = streamed ? NPs : 0;
   b->nnzP = (int)P->p[n]; b->nnzA = (int)A->p[n];
   b->tile = n <= 64 ? 4 : 8;
@@ -1166,6 +1180,7 @@ static int bc_alloc(osqp_amd_batch *b) {
   for (double **v : {&t.l, &t.u, &t.z, &t.y, &t.w, &t.dy, &t.T}) rc |= balloc(b, v, m * Bp);
   rc |= balloc(b, &t.done, B); rc |= balloc(b, &t.verdict, B); rc |= balloc(b, &t.est, B);
   rc |= balloc(b, &t.count, 1); rc |= balloc(b, &t.bad, B + 1);
+  rc |= balloc(b, &t.mem, Bp); rc |= balloc(b, &t.src, B);
   rc |= balloc(b, &b->bc_wk2, NP * NP);
   return rc;
 }
@@ -1234,13 +1249,15 @@ static int bc_setup_launch(osqp_amd_batch *b, const c_float *Q) {
   return 0;
 }
 
-// The batch's rho estimate from the running members' (est > 0; a finished member carries -1), in member order: the
-// value itself when all agree, the geometric mean otherwise; clipped as the reference clips.  0: nobody is running.
-static double bc_batch_estimate(const std::vector<double> &est) {
+// The batch's rho estimate from the running columns' (est > 0; a finished one carries -1), in column order -- which is
+// member order, before and after a pack --: the value itself when all agree, the geometric mean otherwise; clipped as
+// the reference clips.  0: nobody is running.
+static double bc_batch_estimate(const std::vector<double> &est, size_t cols) {
   double first = 0.0, sumlog = 0.0;
   size_t cnt = 0;
   bool equal = true;
-  for (double e : est) {
+  for (size_t c = 0; c < cols; c++) {
+    const double e = est[c];
     if (!(e > 0.0)) continue;
     if (!cnt) first = e; else if (e != first) equal = false;
     sumlog += std::log(e); cnt++;
@@ -1250,87 +1267,117 @@ static double bc_batch_estimate(const std::vector<double> &est) {
   return fmin(fmax(v, 1e-6), 1e6);
 }
 
-// The common-K engine's part of a solve: the ADMM loop of admm_loop, an iteration = a few launches over the batch.
-static int bc_solve(osqp_amd_batch *b) {
+// The common-K engine's part of a solve: the ADMM loop of admm_loop, an iteration = a few launches over the columns.
+// members: the `count` members to solve, ascending (null: all B, column = member).  Column c starts as member
+// members[c]; C, the columns in use, starts at count and falls at every pack (batch_common.h).
+static int bc_solve(osqp_amd_batch *b, const c_int *members, long long count) {
   const BSettings &st = b->st;
-  const BCT &t = b->ct;
-  const long long B = b->B;
+  BCT t = b->ct;
   const int n = b->n, m = b->m, NP = b->NPs, Bp = t.Bp;
   const dim3 eb(BC_TX, BC_TY);
-  const unsigned gx = (unsigned)((B + BC_TX - 1) / BC_TX);
   auto ey = [](int cnt) { return (unsigned)((cnt + BC_TY - 1) / BC_TY); };
-  const dim3 gg((unsigned)((Bp + BC_TILE - 1) / BC_TILE), (unsigned)((NP + BC_TILE - 1) / BC_TILE));
+  auto groups = [](long long cols) { return (unsigned)((cols + BC_TX - 1) / BC_TX); };   // (BC_TX = BC_TILE = 64)
+  t.C = (int)count;
+  unsigned gx = groups(t.C), g256 = (unsigned)((t.C + 255) / 256);
+  dim3 gg((unsigned)((((t.C + 15) & ~15) + BC_TILE - 1) / BC_TILE), (unsigned)((NP + BC_TILE - 1) / BC_TILE));
+  b->bc_cols[0] = b->bc_cols[2] = t.C; b->bc_cols[1] = 0;
   if (b->bc_rebuild) bc_rebuild(b);              // a class changed in an update, rho was set, or rho moved at max_iter
   BCHK(hipMemsetAsync(t.count, 0, sizeof(int), b->stream));
-  hipLaunchKernelGGL(k_bc_load, dim3(gx, ey(std::max(std::max(n, m), 1))), eb, 0, b->stream, n, m, B, b->io, t, b->bc_rho,
-                     st.warm_start);
-  std::vector<double> est((size_t)B);
-  std::vector<int> verdict((size_t)B);
+  // the one host list behind t.src: the members first, the source columns of every pack later -- rewritten only after a
+  // synchronisation that follows the copy of its last content
+  std::vector<int> list;
+  if (members) {
+    list.assign(members, members + count);
+    BCHK(hipMemcpyAsync(t.src, list.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, b->stream));
+  }
+  hipLaunchKernelGGL(k_bc_load, dim3(gx, ey(std::max(std::max(n, m), 1))), eb, 0, b->stream, n, m, b->io, t,
+                     members ? (const int *)t.src : (const int *)nullptr, b->bc_rho, st.warm_start);
+  std::vector<double> est((size_t)count);
+  std::vector<int> verdict((size_t)count), flags((size_t)count);
   bool verdict_pending = false;
   auto take_verdict = [&]() -> int {
-    BCHK(hipMemcpyAsync(verdict.data(), t.verdict, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    BCHK(hipMemcpyAsync(verdict.data(), t.verdict, (size_t)t.C * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     BCHK(hipStreamSynchronize(b->stream));
-    for (int v : verdict) if (v) b->bc_refine = true;
+    for (int c = 0; c < t.C; c++) if (verdict[(size_t)c]) b->bc_refine = true;
     verdict_pending = false;
     return 0;
   };
   set_dynamic_lds(KFN(k_bc_check), b->lds_bytes);
-  long long running = B;
+  long long running = count;
   int iter = 0, rounds = 1, probe_until = 0;
   while (running > 0) {
     ++iter;
     const double rho = b->bc_rho;
-    hipLaunchKernelGGL(k_bc_rhs, dim3(gx, ey(n)), eb, 0, b->stream, b->pat, B, b->io, t, st.sigma);
+    hipLaunchKernelGGL(k_bc_rhs, dim3(gx, ey(n)), eb, 0, b->stream, b->pat, b->io, t, st.sigma);
     hipLaunchKernelGGL(k_bc_gemm, gg, dim3(256), 0, b->stream, (const double *)b->io.Wk, (const double *)t.R, t.Xt,
-                       (const double *)nullptr, NP, Bp);
+                       (const double *)nullptr, NP, Bp, t.C);
     // the refinement rule of admm_loop with one verdict for the batch: probed in the first four iterations after an
     // inversion (refinement is applied while probing), one hit of any running member turns it on for good
     const bool probe = !b->bc_refine && (b->bc_open || iter <= probe_until);
     if (st.refine && (st.refine == 2 || b->bc_refine || probe)) {
-      if (m) hipLaunchKernelGGL(k_bc_rows, dim3(gx, ey(m)), eb, 0, b->stream, b->pat, B, b->io, t, rho);
-      hipLaunchKernelGGL(k_bc_resid, dim3(gx, ey(n)), eb, 0, b->stream, b->pat, B, b->io, t, st.sigma);
+      if (m) hipLaunchKernelGGL(k_bc_rows, dim3(gx, ey(m)), eb, 0, b->stream, b->pat, b->io, t, rho);
+      hipLaunchKernelGGL(k_bc_resid, dim3(gx, ey(n)), eb, 0, b->stream, b->pat, b->io, t, st.sigma);
       if (probe) {
-        hipLaunchKernelGGL(k_bc_probe, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, b->stream, n, B, t, st.refine_tol);
+        hipLaunchKernelGGL(k_bc_probe, dim3(g256), dim3(256), 0, b->stream, n, t, st.refine_tol);
         verdict_pending = true;
         if (b->bc_open) { b->bc_open = false; probe_until = iter + 3; }
       }
       hipLaunchKernelGGL(k_bc_gemm, gg, dim3(256), 0, b->stream, (const double *)b->io.Wk, (const double *)t.Rr, t.Xt,
-                         (const double *)t.Xt, NP, Bp);
+                         (const double *)t.Xt, NP, Bp, t.C);
       if (verdict_pending && iter == probe_until) if (const int rc = take_verdict()) return rc;
     }
-    hipLaunchKernelGGL(k_bc_step, dim3(gx, ey(n + m)), eb, 0, b->stream, b->pat, B, b->io, t, rho, st.alpha);
+    hipLaunchKernelGGL(k_bc_step, dim3(gx, ey(n + m)), eb, 0, b->stream, b->pat, b->io, t, rho, st.alpha);
     const int checked = st.check_termination && (iter % st.check_termination == 0);
     const int adapt = st.adaptive_rho && st.rho_interval && (iter % st.rho_interval == 0);
     const bool last = iter >= st.max_iter;
     if (checked || adapt) {
-      hipLaunchKernelGGL(k_bc_check, dim3((unsigned)B), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, t, NP,
+      hipLaunchKernelGGL(k_bc_check, dim3((unsigned)t.C), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, t, NP,
                          rho, iter, checked, adapt, 0);
       BCHK(hipGetLastError());
+      // a pack needs more than one group of columns; the flags it is made from come over with the count
+      const bool may_pack = b->bc_pack && !last && groups(t.C) > 1;
       int done = 0;
       BCHK(hipMemcpyAsync(&done, t.count, sizeof(int), hipMemcpyDeviceToHost, b->stream));
-      if (adapt) BCHK(hipMemcpyAsync(est.data(), t.est, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+      if (adapt) BCHK(hipMemcpyAsync(est.data(), t.est, (size_t)t.C * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+      if (may_pack) BCHK(hipMemcpyAsync(flags.data(), t.done, (size_t)t.C * sizeof(int), hipMemcpyDeviceToHost, b->stream));
       BCHK(hipStreamSynchronize(b->stream));
-      running = B - done;
-      const double rn = (adapt && running > 0) ? bc_batch_estimate(est) : 0.0;
+      running = count - done;
+      const double rn = (adapt && running > 0) ? bc_batch_estimate(est, (size_t)t.C) : 0.0;
       if (rn > 0.0 && (rn > rho * st.adapt_tol || rn < rho / st.adapt_tol)) {     // adapt_rho (auxil.c:13-74)
         b->bc_rho = rn;
-        hipLaunchKernelGGL(k_bc_adopt, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, b->stream, B, b->io, t);
+        hipLaunchKernelGGL(k_bc_adopt, dim3(g256), dim3(256), 0, b->stream, b->io, t);
         b->bc_rebuild = true;
         if (!last) {                             // (at max_iter no solve with K follows: the rebuild ends the solve)
           if (verdict_pending) if (const int rc = take_verdict()) return rc;
           bc_rebuild(b); rounds++;
-          hipLaunchKernelGGL(k_bc_load_w, dim3(gx, ey(std::max(m, 1))), eb, 0, b->stream, m, B, b->io, t, rn);
+          hipLaunchKernelGGL(k_bc_load_w, dim3(gx, ey(std::max(m, 1))), eb, 0, b->stream, m, b->io, t, rn);
         }
+      }
+      // Pack once a whole group of 64 columns -- a workgroup column of every kernel -- is saved.  A verdict still open
+      // is taken first: it is read by column.  (Taking it early changes no iterate: refinement is applied while probing.)
+      if (may_pack && running > 0 && groups(running) < groups(t.C)) {
+        if (verdict_pending) if (const int rc = take_verdict()) return rc;
+        list.clear();
+        for (int c = 0; c < t.C; c++) if (!flags[(size_t)c]) list.push_back(c);
+        if ((long long)list.size() != running) return -102;
+        BCHK(hipMemcpyAsync(t.src, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+        hipLaunchKernelGGL(k_bc_pack, dim3((unsigned)std::max(std::max(n, m), 1), 10), dim3(256), 0, b->stream, n, m, t,
+                           (int)running);
+        t.C = (int)running;
+        gx = groups(t.C); g256 = (unsigned)((t.C + 255) / 256);
+        gg.x = (unsigned)((((t.C + 15) & ~15) + BC_TILE - 1) / BC_TILE);
+        b->bc_cols[1]++; b->bc_cols[2] = t.C;
       }
     }
     if (last && running > 0) {
-      hipLaunchKernelGGL(k_bc_check, dim3((unsigned)B), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, t, NP,
+      hipLaunchKernelGGL(k_bc_check, dim3((unsigned)t.C), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, t, NP,
                          b->bc_rho, iter, checked, 0, 1);
       running = 0;
     }
   }
   if (verdict_pending) if (const int rc = take_verdict()) return rc;
   if (b->bc_rebuild) bc_rebuild(b);              // rho moved in the last iteration: K^-1 follows it
+  BCHK(hipStreamSynchronize(b->stream));         // (`list` leaves scope: its last copy has been made)
   b->last_rounds = rounds;
   return 0;
 }
@@ -1393,7 +1440,7 @@ extern "C" c_int osqp_amd_batch_update(osqp_amd_batch *b, const c_float *Q, cons
     if (const int rc = bc_check_classes(b, L ? b->d_vals : nullptr, U ? b->d_vals + cnt : nullptr, 0, &moved, "update")) return rc;
     if (moved) b->bc_rebuild = true;
   }
-  b->solved = false;
+  mark_unsolved(b);
   if (Q) BCHK(hipMemcpyAsync(b->dQ, Q, B * b->n * sizeof(double), hipMemcpyHostToDevice, b->stream));
   if (L) BCHK(hipMemcpyAsync(b->dL, L, B * b->m * sizeof(double), hipMemcpyHostToDevice, b->stream));
   if (U) BCHK(hipMemcpyAsync(b->dU, U, B * b->m * sizeof(double), hipMemcpyHostToDevice, b->stream));
@@ -1461,7 +1508,7 @@ extern "C" c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
   if (Ax && Ax_idx) for (c_int k = 0; k < A_n; k++) if (Ax_idx[k] < 0 || Ax_idx[k] >= b->nnzA) return OSQP_DATA_VALIDATION_ERROR;
   if (!Px && !Ax) return 0;
   BCHK(hipSetDevice(b->device));
-  b->solved = false;
+  mark_unsolved(b);
   const c_int pc = Px ? (Px_idx ? P_n : (c_int)b->nnzP) : 0, ac = Ax ? (Ax_idx ? A_n : (c_int)b->nnzA) : 0;
   const size_t B = (size_t)b->B;
   const size_t pv = (size_t)pc * (Px_per_member ? B : 1), av = (size_t)ac * (Ax_per_member ? B : 1);
@@ -1499,7 +1546,7 @@ extern "C" c_int osqp_amd_batch_update_rho(osqp_amd_batch *b, const c_float *rho
     b->bc_rebuild = true;
   }
   BCHK(hipSetDevice(b->device));
-  b->solved = false;
+  mark_unsolved(b);
   if (balloc_once(b, &b->d_rho, (size_t)b->B)) return OSQP_MEM_ALLOC_ERROR;
   BCHK(hipMemcpyAsync(b->d_rho, rho, cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
   hipLaunchKernelGGL(k_batch_update_rho, dim3((unsigned)((b->B + 255) / 256)), dim3(256), 0, b->stream,
@@ -1514,7 +1561,7 @@ extern "C" c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, 
   b->st.warm_start = 1;                          // osqp.c:948
   if (!X && !Y) return 0;
   BCHK(hipSetDevice(b->device));
-  b->solved = false;                             // the stored iterates are the caller's now, not a solve's
+  mark_unsolved(b);                             // the stored iterates are the caller's now, not a solve's
   const size_t B = (size_t)b->B, nx = X ? B * b->n : 0, ny = Y ? B * b->m : 0;
   if (stage_reserve(b, nx + ny, 0)) return OSQP_MEM_ALLOC_ERROR;
   if (nx) BCHK(hipMemcpyAsync(b->d_vals, X, nx * sizeof(double), hipMemcpyHostToDevice, b->stream));
@@ -1530,20 +1577,60 @@ extern "C" c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, 
   return 0;
 }
 
-extern "C" c_int osqp_amd_batch_solve(osqp_amd_batch *b) {
-  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  if (b->noncvx) return OSQP_NONCVX_ERROR;
+// A solve of all members (members = null) or of `count` chosen ones: what osqp_amd_batch_solve and
+// osqp_amd_batch_solve_members share once their arguments have passed.  The solved flags of the members it is about to
+// solve are cleared first and set when it has ended; `solved` is all of them.
+static c_int batch_solve_run(osqp_amd_batch *b, const c_int *members, long long count) {
   BCHK(hipSetDevice(b->device));
   b->solved = b->polished = false;
+  if (!members) std::fill(b->member_solved.begin(), b->member_solved.end(), (char)0);
+  else for (long long k = 0; k < count; k++) b->member_solved[(size_t)members[k]] = 0;
   b->io.order = (b->lpt && b->solves > 0) ? b->d_order : nullptr;   // first solve: no history, index order
-  if (b->engine == OSQP_AMD_BATCH_COMMON) { if (const int rc = bc_solve(b)) return rc; }
+  if (b->engine == OSQP_AMD_BATCH_COMMON) { if (const int rc = bc_solve(b, members, count)) return rc; }
   else if (b->engine != OSQP_AMD_BATCH_STREAMED) batch_launch(b, 1);
   else if (const int rc = bs_solve(b)) return rc;
   if (b->lpt && b->engine != OSQP_AMD_BATCH_COMMON) hipLaunchKernelGGL(k_batch_order, dim3(1), dim3(1024), 0, b->stream, b->B, b->io.info, b->d_order);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
-  b->solves++;
-  b->solved = true;
+  b->solves++;                                   // (a kept KKT inversion is of an earlier solve now: kkt_kept)
+  if (!members) std::fill(b->member_solved.begin(), b->member_solved.end(), (char)1);
+  else for (long long k = 0; k < count; k++) b->member_solved[(size_t)members[k]] = 1;
+  b->solved = std::find(b->member_solved.begin(), b->member_solved.end(), (char)0) == b->member_solved.end();
+  return 0;
+}
+
+extern "C" c_int osqp_amd_batch_solve(osqp_amd_batch *b) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (b->noncvx) return OSQP_NONCVX_ERROR;
+  return batch_solve_run(b, nullptr, b->B);
+}
+
+extern "C" c_int osqp_amd_batch_solve_members(osqp_amd_batch *b, const c_int *members, c_int count) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (b->engine != OSQP_AMD_BATCH_COMMON) {
+    fprintf(stderr, "osqp_amd batch: osqp_amd_batch_solve_members is a call of the common-K engine (OSQP_AMD_BATCH_COMMON); "
+                    "the %s engine solves all members (osqp_amd_batch_solve)\n",
+            b->engine == OSQP_AMD_BATCH_STREAMED ? "streamed" : "tiled");
+    return OSQP_LINSYS_SOLVER_INIT_ERROR;
+  }
+  if (!members || count < 1 || count > b->B) return OSQP_DATA_VALIDATION_ERROR;
+  for (c_int k = 0; k < count; k++)
+    if (members[k] < 0 || members[k] >= b->B || (k && members[k] <= members[k - 1])) return OSQP_DATA_VALIDATION_ERROR;
+  if (b->noncvx) return OSQP_NONCVX_ERROR;
+  // all B members, ascending: the identity, and the full solve to the bit
+  return batch_solve_run(b, count == b->B ? nullptr : members, count);
+}
+
+// Of the last solve of a common-K handle: the columns it started with, its packs, the columns in use when it ended.
+// Touches no GPU memory.
+extern "C" c_int osqp_amd_batch_common_columns(osqp_amd_batch *b, c_int out[3]) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!out) return OSQP_DATA_VALIDATION_ERROR;
+  if (b->engine != OSQP_AMD_BATCH_COMMON) {
+    fprintf(stderr, "osqp_amd batch: osqp_amd_batch_common_columns is a call of the common-K engine (OSQP_AMD_BATCH_COMMON)\n");
+    return OSQP_LINSYS_SOLVER_INIT_ERROR;
+  }
+  for (int k = 0; k < 3; k++) out[k] = b->bc_cols[k];
   return 0;
 }
 
@@ -1841,7 +1928,7 @@ static c_int bc_update_model(osqp_amd_batch *b, bool dev, const char *call, cons
   BCHK(hipSetDevice(b->device));
   if (dev && dev_ptrs_check(b, {Px, Ax})) return OSQP_DATA_VALIDATION_ERROR;
   if (!Px && !Ax) return 0;
-  b->solved = false;                             // (a kept KKT inversion goes with it: kkt_kept)
+  mark_unsolved(b);                             // (a kept KKT inversion goes with it: kkt_kept)
   b->kkt_valid = false;
   const c_int pc = Px ? (Px_idx ? P_n : (c_int)b->nnzP) : 0, ac = Ax ? (Ax_idx ? A_n : (c_int)b->nnzA) : 0;
   const size_t n = (size_t)b->n, B = (size_t)b->B;

@@ -32,12 +32,15 @@ struct BCT {               // the index-major arrays of a solve (device), pitch 
   double *q, *x, *dx;      // [NP][Bp]
   double *l, *u, *z, *y, *w, *dy, *T;   // [m][Bp]; T = rho .* (A x~) of the refinement
   double *R, *Xt, *Rr;     // [NP][Bp] right-hand side, x~, residual of the refinement; rows [n, NP) stay zero
-  int *done;               // [B] 1 once the member has finished
-  int *verdict;            // [B] 1 when a probe found the member's relative residual above refine_tol
-  double *est;             // [B] rho estimate of a running member at an adaptation point, -1 once it has finished
+  int *done;               // [B] per column: 1 once its member has finished
+  int *verdict;            // [B] per column: 1 when a probe found the member's relative residual above refine_tol
+  double *est;             // [B] per column: rho estimate of a running member at an adaptation point, -1 once it has finished
   int *count;              // [1] finished members
   int *bad;                // [B + 1] class check: first disagreeing row per member (-1: none); [B]: a common class moved
-  int Bp;
+  int *mem;                // [Bp] the member that owns a column (written by k_bc_load, moved by k_bc_pack)
+  int *src;                // [B] host-written lists: the members of a subset solve, then the source columns of a pack
+  int Bp;                  // the pitch of the allocation: B rounded up to 16
+  int C;                   // the columns in use
 };
 
 typedef double bc_d4 __attribute__((ext_vector_type(4)));
@@ -201,33 +204,35 @@ __global__ void __launch_bounds__(256) k_bc_warm_start(BPattern p, BIO io, const
 }
 
 // ---------------------------------------------------------------------------
-// the solve: element-wise kernels, thread (tx, ty) = member blockIdx.x * 64 + tx, index blockIdx.y * 4 + ty
+// the solve: element-wise kernels, thread (tx, ty) = column blockIdx.x * 64 + tx, index blockIdx.y * 4 + ty
 // ---------------------------------------------------------------------------
 #define BC_MEMBER_INDEX \
   const long long b = (long long)blockIdx.x * BC_TX + threadIdx.x; \
   const int idx = blockIdx.y * BC_TY + threadIdx.y;                \
-  if (b >= B) return;
+  if (b >= t.C) return;
 
-// the member-major workspace into the index-major arrays of the solve; cold: zero iterates
-__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_load(int n, int m, long long B, BIO io, BCT t, double rho, int warm) {
+// the member-major workspace into the index-major arrays of the solve, member members[b] (null: member b) into column b;
+// cold: zero iterates
+__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_load(int n, int m, BIO io, BCT t, const int *__restrict__ members,
+                                                           double rho, int warm) {
   BC_MEMBER_INDEX
-  const long long Bp = t.Bp;
+  const long long Bp = t.Bp, qp = members ? members[b] : b;
   if (idx < n) {
-    t.q[idx * Bp + b] = io.Wq[b * n + idx];
-    t.x[idx * Bp + b] = warm ? io.Xs[b * n + idx] : 0.0;
+    t.q[idx * Bp + b] = io.Wq[qp * n + idx];
+    t.x[idx * Bp + b] = warm ? io.Xs[qp * n + idx] : 0.0;
     t.dx[idx * Bp + b] = 0.0;
   }
   if (idx < m) {
-    const double z = warm ? io.Zs[b * m + idx] : 0.0, y = warm ? io.Ys[b * m + idx] : 0.0;
-    t.l[idx * Bp + b] = io.Wl[b * m + idx]; t.u[idx * Bp + b] = io.Wu[b * m + idx];
+    const double z = warm ? io.Zs[qp * m + idx] : 0.0, y = warm ? io.Ys[qp * m + idx] : 0.0;
+    t.l[idx * Bp + b] = io.Wl[qp * m + idx]; t.u[idx * Bp + b] = io.Wu[qp * m + idx];
     t.z[idx * Bp + b] = z; t.y[idx * Bp + b] = y; t.dy[idx * Bp + b] = 0.0;
     t.w[idx * Bp + b] = rho_of_class(io.Wt[idx], rho) * z - y;
   }
-  if (idx == 0) { t.done[b] = 0; t.est[b] = 0.0; t.verdict[b] = 0; }
+  if (idx == 0) { t.mem[b] = (int)qp; t.done[b] = 0; t.est[b] = 0.0; t.verdict[b] = 0; }
 }
 
 // R = sigma x - q + A' w
-__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_rhs(BPattern p, long long B, BIO io, BCT t, double sigma) {
+__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_rhs(BPattern p, BIO io, BCT t, double sigma) {
   BC_MEMBER_INDEX
   if (idx >= p.n) return;
   const long long Bp = t.Bp;
@@ -238,7 +243,7 @@ __global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_rhs(BPattern p, long long 
 }
 
 // T = rho .* (A X~)
-__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_rows(BPattern p, long long B, BIO io, BCT t, double rho) {
+__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_rows(BPattern p, BIO io, BCT t, double rho) {
   BC_MEMBER_INDEX
   if (idx >= p.m) return;
   const long long Bp = t.Bp;
@@ -249,7 +254,7 @@ __global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_rows(BPattern p, long long
 }
 
 // Rr = R - K X~ through the sparse operator: K X~ = P X~ + sigma X~ + A' T
-__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_resid(BPattern p, long long B, BIO io, BCT t, double sigma) {
+__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_resid(BPattern p, BIO io, BCT t, double sigma) {
   BC_MEMBER_INDEX
   if (idx >= p.n) return;
   const long long Bp = t.Bp;
@@ -260,10 +265,10 @@ __global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_resid(BPattern p, long lon
   t.Rr[idx * Bp + b] = t.R[idx * Bp + b] - (px + sigma * t.Xt[idx * Bp + b] + at);
 }
 
-// the probe of the explicit-inverse solve: one thread per running member, |Rr|_inf against refine_tol |R|_inf
-__global__ void __launch_bounds__(256) k_bc_probe(int n, long long B, BCT t, double refine_tol) {
+// the probe of the explicit-inverse solve: one thread per running column, |Rr|_inf against refine_tol |R|_inf
+__global__ void __launch_bounds__(256) k_bc_probe(int n, BCT t, double refine_tol) {
   const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (b >= B || t.done[b]) return;
+  if (b >= t.C || t.done[b]) return;
   const long long Bp = t.Bp;
   double rmax = 0.0, bmax = 0.0;
   for (int j = 0; j < n; ++j) { rmax = fmax(rmax, fabs(t.Rr[j * Bp + b])); bmax = fmax(bmax, fabs(t.R[j * Bp + b])); }
@@ -271,7 +276,7 @@ __global__ void __launch_bounds__(256) k_bc_probe(int n, long long B, BCT t, dou
 }
 
 // z~ = A x~ and the x, z, y updates (auxil.c:185-225, proj.c:4-14), as admm_loop; rows first, then columns
-__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_step(BPattern p, long long B, BIO io, BCT t, double rho, double alpha) {
+__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_step(BPattern p, BIO io, BCT t, double rho, double alpha) {
   BC_MEMBER_INDEX
   if (t.done[b]) return;                     // a finished member is frozen
   const long long Bp = t.Bp;
@@ -299,7 +304,7 @@ __global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_step(BPattern p, long long
 }
 
 // rho has moved: w = rho z - y of the running members with the new rho (refresh_w)
-__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_load_w(int m, long long B, BIO io, BCT t, double rho) {
+__global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_load_w(int m, BIO io, BCT t, double rho) {
   BC_MEMBER_INDEX
   if (idx >= m || t.done[b]) return;
   const long long e = idx * (long long)t.Bp + b;
@@ -307,9 +312,9 @@ __global__ void __launch_bounds__(BC_TX * BC_TY) k_bc_load_w(int m, long long B,
 }
 
 // rho has moved: every running member counts the update
-__global__ void __launch_bounds__(256) k_bc_adopt(long long B, BIO io, BCT t) {
+__global__ void __launch_bounds__(256) k_bc_adopt(BIO io, BCT t) {
   const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (b < B && !t.done[b]) io.info[b * 8 + 5] += 1.0;
+  if (b < t.C && !t.done[b]) io.info[(long long)t.mem[b] * 8 + 5] += 1.0;
 }
 
 // ---------------------------------------------------------------------------
@@ -318,10 +323,13 @@ __global__ void __launch_bounds__(256) k_bc_adopt(long long B, BIO io, BCT t) {
 // 64 x 64 tile (a wavefront: 32 x 32, 2 x 2 MFMA tiles); both operands go through LDS in chunks of BC_KC k rows, the
 // next chunk's global loads in flight while the current one is multiplied.  Every output element accumulates k = 0,
 // 4, 8, ... NP - 4 in this order whatever its tile, so a member's bits depend neither on its column nor on B.
-// NP is a multiple of 32 and Bp of 16: the double2 loads are aligned and guarded by the even index alone.
+// Bp is the pitch, C the columns in use: the grid and the guards cover Cp = C rounded up to 16 (the columns of [C, Cp)
+// hold whatever earlier columns left there; nobody reads their product).  NP is a multiple of 32 and Cp of 16: the
+// double2 loads are aligned and guarded by the even index alone.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_bc_gemm(const double *__restrict__ Kinv, const double *__restrict__ Rin, double *out,
-                                                 const double *add, int NP, int Bp) {
+                                                 const double *add, int NP, int Bp, int C) {
+  const int Cp = (C + 15) & ~15;
   __shared__ __attribute__((aligned(16))) double As[BC_KC * BC_LP], Bs[BC_KC * BC_LP];
   const int row0 = blockIdx.y * BC_TILE, col0 = blockIdx.x * BC_TILE;
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6, li = lane & 15, lk = lane >> 4;
@@ -338,7 +346,7 @@ __global__ void __launch_bounds__(256) k_bc_gemm(const double *__restrict__ Kinv
     for (int u = 0; u < 2; ++u) {
       const int p = t + 256 * u, kk = k0 + (p >> 5), c2 = (p & 31) * 2;
       ga[u] = row0 + c2 < NP ? *reinterpret_cast<const double2 *>(Kinv + (size_t)kk * NP + row0 + c2) : double2{0.0, 0.0};
-      gb[u] = col0 + c2 < Bp ? *reinterpret_cast<const double2 *>(Rin + (size_t)kk * Bp + col0 + c2) : double2{0.0, 0.0};
+      gb[u] = col0 + c2 < Cp ? *reinterpret_cast<const double2 *>(Rin + (size_t)kk * Bp + col0 + c2) : double2{0.0, 0.0};
     }
   };
   gload(0);
@@ -371,7 +379,7 @@ __global__ void __launch_bounds__(256) k_bc_gemm(const double *__restrict__ Kinv
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = row0 + wr + 16 * i + lk + 4 * r, col = col0 + wc + 16 * j + li;
-        if (row < NP && col < Bp) {
+        if (row < NP && col < Cp) {
           const size_t e = (size_t)row * Bp + col;
           out[e] = add ? acc[i][j][r] + add[e] : acc[i][j][r];
         }
@@ -379,7 +387,7 @@ __global__ void __launch_bounds__(256) k_bc_gemm(const double *__restrict__ Kinv
 }
 
 // ---------------------------------------------------------------------------
-// check and adaptation points: one workgroup per running member, the member's vectors in LDS, batch_admm.h's code.
+// check and adaptation points: one workgroup per running column, its member's vectors in LDS, batch_admm.h's code.
 // checked / adapt: what admm_loop does after iteration `iter` (check_termination, then the rho estimate of a member
 // that goes on).  final: the solve ends here (iter >= max_iter; the host has dealt with rho): the stage machine's
 // tail -- the exact test unless `checked` already made it, then the approximate one, then OSQP_MAX_ITER_REACHED.
@@ -387,8 +395,9 @@ __global__ void __launch_bounds__(256) k_bc_gemm(const double *__restrict__ Kinv
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(BS_NT) k_bc_check(BPattern p, BSettings st, BIO io, BCT t, int NP, double rho, int iter,
                                                     int checked, int adapt, int final) {
-  const long long qp = blockIdx.x;
-  if (t.done[qp]) return;
+  const long long col = blockIdx.x;
+  if (t.done[col]) return;
+  const long long qp = t.mem[col];                     // the member: the workspace and the results are addressed by it
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const BL s = bs_layout(lds, p, io, 0, NP);           // the one slab of scaled values
   const int n = p.n, m = p.m, tid = threadIdx.x;
@@ -399,15 +408,15 @@ __global__ void __launch_bounds__(BS_NT) k_bc_check(BPattern p, BSettings st, BI
   a.cs = load_workspace<BS_NT, true>(s, p, io, qp);
   a.rho = rho; a.iter = iter; a.rho_updates = (int)io.info[qp * 8 + 5];
   a.need_refine = a.check_pending = false;
-  for (int j = tid; j < n; j += BS_NT) { s_x[j] = t.x[j * Bp + qp]; s_dx[j] = t.dx[j * Bp + qp]; }
-  for (int i = tid; i < m; i += BS_NT) { s_z[i] = t.z[i * Bp + qp]; s_y[i] = t.y[i * Bp + qp]; s_dy[i] = t.dy[i * Bp + qp]; }
+  for (int j = tid; j < n; j += BS_NT) { s_x[j] = t.x[j * Bp + col]; s_dx[j] = t.dx[j * Bp + col]; }
+  for (int i = tid; i < m; i += BS_NT) { s_z[i] = t.z[i * Bp + col]; s_y[i] = t.y[i * Bp + col]; s_dy[i] = t.dy[i * Bp + col]; }
   if (tid == 0) { for (int k = 0; k < S_COUNT_; ++k) sc[k] = 0.0; sc[S_STATUS] = OSQP_UNSOLVED; sc[S_RHO] = rho; }
   __syncthreads();
   update_info<BS_NT, false>(s, p, st, a.cs);
   bool fin = false;
   if (!final) {
     if (checked) fin = check_termination<BS_NT>(s, p, st, a.cs, false);
-    if (!fin && adapt && tid == 0) t.est[qp] = rho_estimate(sc, m, rho);
+    if (!fin && adapt && tid == 0) t.est[col] = rho_estimate(sc, m, rho);
   } else {
     if (!checked) fin = check_termination<BS_NT>(s, p, st, a.cs, false);
     if (!fin && !check_termination<BS_NT>(s, p, st, a.cs, true)) {
@@ -418,5 +427,41 @@ __global__ void __launch_bounds__(BS_NT) k_bc_check(BPattern p, BSettings st, BI
   }
   if (!fin) return;
   store_solution<BS_NT>(s, p, st, io, qp, a, 0);
-  if (tid == 0) { t.done[qp] = 1; t.est[qp] = -1.0; atomicAdd(t.count, 1); }
+  if (tid == 0) { t.done[col] = 1; t.est[col] = -1.0; atomicAdd(t.count, 1); }
+}
+
+// ---------------------------------------------------------------------------
+// Stable compaction of the running columns: column c takes column t.src[c], c < Rn, with src increasing and
+// src[c] >= c, in the nine state arrays (q, x, dx; l, u, z, y, w, dy) and in mem, est, verdict, done.  R, Xt, Rr and T
+// are re-formed in every iteration before they are read and are not moved (rows [n, NP) of R are never written: they
+// stay zero in every column).  In place: workgroup (row, array) owns one row of one array and walks it in ascending
+// chunks of 256 columns, reading a chunk's sources, then -- after the barrier -- writing its destinations.  A chunk's
+// sources lie at or beyond its first destination, hence beyond every destination of the chunks before it; its
+// destinations are written only after the barrier every thread reaches once it has read the chunk, and a thread
+// reaches the next barrier only after it has read the next chunk, so no source is overwritten before it is read.
+// Array 9 is the four per-column words, moved by workgroup (0, 9) the same way.  Copies only: no arithmetic.
+// ---------------------------------------------------------------------------
+template <typename Tp>
+__device__ __forceinline__ void bc_pack_row(Tp *row, const int *__restrict__ src, int Rn) {
+  for (int c0 = 0; c0 < Rn; c0 += 256) {
+    const int c = c0 + threadIdx.x;
+    Tp v{};
+    if (c < Rn) v = row[src[c]];
+    __syncthreads();
+    if (c < Rn) row[c] = v;
+  }
+}
+__global__ void __launch_bounds__(256) k_bc_pack(int n, int m, BCT t, int Rn) {
+  const int a = blockIdx.y;
+  const long long r = blockIdx.x;
+  if (a == 9) {
+    if (r) return;
+    bc_pack_row(t.mem, t.src, Rn); bc_pack_row(t.est, t.src, Rn);
+    bc_pack_row(t.verdict, t.src, Rn); bc_pack_row(t.done, t.src, Rn);
+    return;
+  }
+  if (r >= (a < 3 ? n : m)) return;
+  double *const v = a == 0 ? t.q : a == 1 ? t.x : a == 2 ? t.dx : a == 3 ? t.l : a == 4 ? t.u : a == 5 ? t.z :
+                    a == 6 ? t.y : a == 7 ? t.w : t.dy;
+  bc_pack_row(v + r * t.Bp, t.src, Rn);
 }

@@ -92,7 +92,7 @@ extern "C" c_int osqp_amd_batch_update_dev(osqp_amd_batch *b, const c_float *Q, 
     if (const int rc = bc_check_classes(b, L, U, 1, &moved, "update")) return rc;
     if (moved) b->bc_rebuild = true;
   }
-  b->solved = false;
+  mark_unsolved(b);
   if (Q) BCHK(hipMemcpyAsync(b->dQ, Q, B * b->n * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
   if ((L || U) && cnt)
     hipLaunchKernelGGL(k_batch_stage_bounds, dim3(bd_blocks(cnt)), dim3(BD_NT), 0, b->stream, cnt, L, U, b->dL, b->dU);
@@ -117,7 +117,7 @@ extern "C" c_int osqp_amd_batch_update_matrices_dev(osqp_amd_batch *b,
   if (!Px && !Ax) return 0;
   BCHK(hipSetDevice(b->device));
   if (dev_ptrs_check(b, {Px, Ax})) return OSQP_DATA_VALIDATION_ERROR;
-  b->solved = false;
+  mark_unsolved(b);
   const c_int pc = Px ? (Px_idx ? P_n : (c_int)b->nnzP) : 0, ac = Ax ? (Ax_idx ? A_n : (c_int)b->nnzA) : 0;
   if (stage_reserve(b, 0, (size_t)pc + ac)) return OSQP_MEM_ALLOC_ERROR;      // the index lists only
   if (Px && patch_values(b, &b->dPx, &b->io.Px, &b->io.strideP, b->nnzP, Px, Px_idx, pc, Px_per_member, 0, 0, true))
@@ -151,7 +151,7 @@ extern "C" c_int osqp_amd_batch_warm_start_dev(osqp_amd_batch *b, const c_float 
   }
   b->st.warm_start = 1;                          // osqp.c:948
   if (!X && !Y) return 0;
-  b->solved = false;
+  mark_unsolved(b);
   if (b->engine == OSQP_AMD_BATCH_COMMON)
     hipLaunchKernelGGL(k_bc_warm_start, dim3((unsigned)b->B), dim3(256), 0, b->stream, b->pat, b->io, X, Y);
   else
