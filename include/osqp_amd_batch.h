@@ -177,6 +177,13 @@ c_int osqp_amd_batch_solve(osqp_amd_batch *b);
  * give as long as the scaling and rho agree (rho fixed, or adapted from the same members).  Where rho is adopted it is
  * the batch's one rho from then on: K is re-formed and re-inverted as in a full solve and rho_updates of the running
  * listed members goes up.
+ * The refinement verdict (osqp_amd_batch_rounds) is the batch's, but "off" binds only members that were probed under the
+ * current K^-1: a call that lists a member no solve has probed since the last inversion probes through its first four
+ * iterations, so solve_members(S) then solve_members(the rest) refines the rest exactly when a handle of their own
+ * would.  The flags are kept per listed member, not per probed column: after a rho move in mid-solve the new window
+ * counts for every member of that call's list, those that had finished before the move included -- what a full solve
+ * has always done.  "On" stays through every later inversion (a rho move, osqp_amd_batch_update_rho, a class change in an
+ * update); only osqp_amd_batch_common_update_model clears it.
  * It counts as a solve: a kept KKT inversion is dropped and a polish is forgotten.  The handle keeps one flag per member,
  * "solved on the current problem": every update and warm start that makes polish, adjoint and tangent return
  * OSQP_WORKSPACE_NOT_INIT_ERROR clears all of them, osqp_amd_batch_solve sets all, this call sets the listed ones, and

@@ -700,6 +700,7 @@ struct osqp_amd_batch {
   bool bc_rebuild = false;  // K^-1 no longer matches rho or the row classes
   bool bc_refine = false;   // the K^-1 solves take the refinement step (the verdict of the last probe)
   bool bc_open = false;     // the verdict is to be taken again: K^-1 is new
+  std::vector<char> bc_probed;   // [B] the member was listed in a solve that probed this K^-1 (cleared with every new K^-1)
   int bc_pack = 1;          // OSQP_AMD_BATCH_COMMON_PACK (0: the columns of a solve stay where they started)
   int bc_cols[3] = {0, 0, 0};   // of the last solve: columns it started with, packs, columns in use when it ended
   BKkt bk{};                // the shared KKT pieces (batch_common_kkt.h), built by osqp_amd_batch_common_kkt
@@ -1199,6 +1200,7 @@ static void bc_rebuild(osqp_amd_batch *b) {
   }
   b->bc_rebuild = false;
   b->bc_open = true;
+  b->bc_probed.assign((size_t)b->B, 0);
 }
 
 // Do the bounds L, U (device, raw, [B][m]; null = keep) leave every row with one class over the batch?  0: yes
@@ -1282,6 +1284,13 @@ static int bc_solve(osqp_amd_batch *b, const c_int *members, long long count) {
   dim3 gg((unsigned)((((t.C + 15) & ~15) + BC_TILE - 1) / BC_TILE), (unsigned)((NP + BC_TILE - 1) / BC_TILE));
   b->bc_cols[0] = b->bc_cols[2] = t.C; b->bc_cols[1] = 0;
   if (b->bc_rebuild) bc_rebuild(b);              // a class changed in an update, rho was set, or rho moved at max_iter
+  // A verdict of "off" binds only the members that were probed under this K^-1: a solve that lists one that was not
+  // probes through its first four iterations, as the first solve after the inversion does.  A window counts for every
+  // member of the list, finished columns included (k_bc_probe skips them): full solves keep the launches they had.
+  auto member_of = [&](long long c) { return (size_t)(members ? members[c] : c); };
+  if (!b->bc_refine && !b->bc_open)
+    for (long long c = 0; c < count; c++) if (!b->bc_probed[member_of(c)]) { b->bc_open = true; break; }
+  auto mark_probed = [&]() { for (long long c = 0; c < count; c++) b->bc_probed[member_of(c)] = 1; };
   BCHK(hipMemsetAsync(t.count, 0, sizeof(int), b->stream));
   // the one host list behind t.src: the members first, the source columns of every pack later -- rewritten only after a
   // synchronisation that follows the copy of its last content
@@ -1320,7 +1329,7 @@ static int bc_solve(osqp_amd_batch *b, const c_int *members, long long count) {
       if (probe) {
         hipLaunchKernelGGL(k_bc_probe, dim3(g256), dim3(256), 0, b->stream, n, t, st.refine_tol);
         verdict_pending = true;
-        if (b->bc_open) { b->bc_open = false; probe_until = iter + 3; }
+        if (b->bc_open) { b->bc_open = false; probe_until = iter + 3; mark_probed(); }
       }
       hipLaunchKernelGGL(k_bc_gemm, gg, dim3(256), 0, b->stream, (const double *)b->io.Wk, (const double *)t.Rr, t.Xt,
                          (const double *)t.Xt, NP, Bp, t.C);
@@ -1890,6 +1899,7 @@ static c_int bc_rebuild_pair(osqp_amd_batch *b, int *kflag) {
   b->bk.H = const_cast<double *>(a.in[1]); h2 = a.out[1];      // each inverse is in whichever buffer the last pivot wrote
   b->bc_rebuild = false;
   b->bc_open = true;
+  b->bc_probed.assign((size_t)b->B, 0);
   int verdict = 0;
   if (hipGetLastError() != hipSuccess || hipMemcpyAsync(kflag, b->io.flag, sizeof(int), hipMemcpyDeviceToHost, b->stream) != hipSuccess ||
       hipMemcpyAsync(&verdict, word, sizeof(int), hipMemcpyDeviceToHost, b->stream) != hipSuccess ||

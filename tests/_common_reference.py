@@ -21,7 +21,16 @@ row classes; every member's q, l, u come through `_common_cases.prescaled`.  All
   at max_iter    the check (if due), the adaptation (if due), the final exact test (unless already made), the
                  approximate test, then status -2; the reported rho is the batch's after that last adaptation
   warm start     a second `solve()` continues from each member's final x, z, y with the rho the first ended with;
-                 rho_updates goes on counting (only `update` resets it, which the reference does not model)
+                 rho_updates goes on counting (only `update` resets it); with the setting warm_start = 0 every solve
+                 starts its members from x = z = y = 0 instead, with the rho the handle holds
+  a handle's life  `solve(members=S)` iterates, tests, counts in the estimate (in member order), counts rho_updates for
+                 and stores the listed members only -- every other member keeps x, z, y, status, iter, rho, rho_updates
+                 and its stored result; rho and K are the batch's, so a move made on S binds everybody afterwards.
+                 `update(Q, L, U)` scales the new q, l, u with the D, E, c held (`prescaled`), sets rho_updates = 0 and
+                 the status unsolved for all members, asserts that the row classes stay common and, where the common
+                 class of a row moved, re-forms K with the current rho (`bc_rebuild` at the next solve).
+                 `warm_start(X, Y)` sets x = D^-1 X, z = A x, y = c E^-1 Y (`k_bc_warm_start`) and turns the setting
+                 warm_start on, as the reference's osqp_warm_start does
 
 Per member it returns status_val, iter, rho_updates, rho (the rho in force when the member finished: info[7],
 `store_solution`'s a.rho) and x, y, obj_val unscaled as `_common_cases.unscale` does.  `decisions` is the log of what was
@@ -36,6 +45,9 @@ settings, full runs and max_iter = 20 followed by a warm second solve: status, i
 rho (the oracle's settings().rho after the solve) within 5.9e-9 relative -- the largest in the 1100 iterations and five
 moves of member 1 of (129, 258) under the default termination; all other runs stay below 3.1e-10.  The host test holds
 x, y and the objective under ANCHOR_BAR = 1e-8 and the rho difference under RHO_DIFF_MEASURED = 6e-9.
+`update` and `warm_start` are anchored the same way by tests/test_common_session_cases_host.py (a solve cut at 20
+iterations, an update of q, l, u, optionally a warm start, a solve to the end): |x - x_oracle| <= 6.3e-12, y <= 7.3e-11,
+objective <= 3.1e-12, rho within 3.0e-9.
 RHO_BAR, what the GPU tests allow between the engine's rho and this reference's, is 100 x that measured difference (the
 margin over the reference's own arithmetic) and never looser than the project's parity bar of 1e-6: RHO_BAR = 6e-7.
 
@@ -54,7 +66,7 @@ RHO_DIFF_MEASURED = 6e-9
 RHO_BAR = min(1e-6, 100.0 * RHO_DIFF_MEASURED)
 
 DEFAULTS = dict(alpha=1.6, eps_abs=1e-3, eps_rel=1e-3, max_iter=4000, check_termination=25, adaptive_rho=1,
-                adaptive_rho_interval=0, adaptive_rho_tolerance=5.0, scaled_termination=0)
+                adaptive_rho_interval=0, adaptive_rho_tolerance=5.0, scaled_termination=0, warm_start=1)
 RHO_MIN, RHO_MAX = 1e-6, 1e6
 
 
@@ -79,22 +91,30 @@ class CommonReference:
         assert not self.st["adaptive_rho"] or self.st["adaptive_rho_interval"] > 0, "the interval is given, not timed"
         self.ws = ws
         B = self.B = Q.shape[0]
+        self.Qr, self.Lr, self.Ur = (np.array(v, dtype=np.float64) for v in (Q, L, U))     # raw, for `update`
         self.P = (ws["Pu"] + sparse.triu(ws["Pu"], 1).T).toarray().astype(LD)
         self.A = ws["A"].toarray().astype(LD)
         self.m, self.n = self.A.shape
-        data = [prescaled(ws, Q, L, U, b) for b in range(B)]
-        self.q = np.array([d[1] for d in data], dtype=LD).reshape(B, self.n)
-        self.l = np.array([d[3] for d in data], dtype=LD).reshape(B, self.m)
-        self.u = np.array([d[4] for d in data], dtype=LD).reshape(B, self.m)
+        self._scale_data()
         self.D, self.E, self.c = ws["D"].astype(LD), ws["E"].astype(LD), LD(ws["c"])
         self.sigma = LD(ws["sigma"])
         self.ctype = ws["ctype"]
         self.x = np.zeros((B, self.n), LD); self.z = np.zeros((B, self.m), LD); self.y = np.zeros((B, self.m), LD)
         self.rho_updates = np.zeros(B, np.int64)
+        # what the last solve that listed the member stored for it
+        self.iters = np.zeros(B, np.int64); self.rho_at = np.zeros(B, LD); self.obj = np.zeros(B, LD)
+        self.out_x = np.zeros((B, self.n)); self.out_y = np.zeros((B, self.m))
         self.calls = 0
         self.decisions = []
         self.conds = []                                  # cond(K) of every K formed
         self._set_rho(min(max(LD(ws["rho"]), RHO_MIN), RHO_MAX))
+
+    def _scale_data(self):
+        LD, B = self.ld, self.B
+        data = [prescaled(self.ws, self.Qr, self.Lr, self.Ur, b) for b in range(B)]
+        self.q = np.array([d[1] for d in data], dtype=LD).reshape(B, self.n)
+        self.l = np.array([d[3] for d in data], dtype=LD).reshape(B, self.m)
+        self.u = np.array([d[4] for d in data], dtype=LD).reshape(B, self.m)
 
     # ---- the linear solve ---------------------------------------------------------------------------------------
     def _set_rho(self, rho):
@@ -112,6 +132,37 @@ class CommonReference:
     def update_rho(self, rho):
         """osqp_update_rho: the clipped value; iterates and rho_updates stay."""
         self._set_rho(min(max(self.ld(rho), RHO_MIN), RHO_MAX))
+
+    def update(self, Q=None, L=None, U=None):
+        """osqp_update_lin_cost / _bounds for every member with the scaling kept (None = keep)."""
+        from _common_cases import row_classes
+        for name, v in (("Qr", Q), ("Lr", L), ("Ur", U)):
+            if v is not None:
+                assert np.shape(v) == getattr(self, name).shape, name
+                setattr(self, name, np.array(v, dtype=np.float64))
+        assert np.all(self.Lr <= self.Ur)
+        self._scale_data()
+        self.rho_updates[:] = 0
+        self.status[:] = 0
+        if self.m and (L is not None or U is not None):
+            cls = row_classes(self.Lr[0], self.Ur[0], self.ws["E"])
+            for b in range(self.B):
+                assert np.array_equal(row_classes(self.Lr[b], self.Ur[b], self.ws["E"]), cls), "member %d: classes not common" % b
+            if not np.array_equal(cls, self.ctype):
+                self.ctype = cls
+                self._set_rho(self.rho)
+
+    def warm_start(self, X=None, Y=None):
+        """osqp_warm_start (_x, _y) for every member: unscaled X [B, n], Y [B, m]; either may be None."""
+        LD = self.ld
+        if X is not None:
+            assert np.shape(X) == (self.B, self.n)
+            self.x = np.asarray(X, dtype=np.float64).astype(LD) / self.D
+            self.z = self.x @ self.A.T
+        if Y is not None:
+            assert np.shape(Y) == (self.B, self.m)
+            self.y = np.asarray(Y, dtype=np.float64).astype(LD) / self.E * self.c
+        self.st["warm_start"] = 1
 
     # ---- update_info (auxil.c:227-318) on the scaled iterates ---------------------------------------------------
     def _info(self):
@@ -156,15 +207,20 @@ class CommonReference:
         return min(max(self.rho * np.sqrt(pr / du), RHO_MIN), RHO_MAX)
 
     # ---- the loop -----------------------------------------------------------------------------------------------
-    def solve(self):
+    def solve(self, members=None):
         LD = self.ld
         st, B = self.st, self.B
+        listed = np.arange(B) if members is None else np.asarray(members, dtype=np.int64)
+        assert listed.ndim == 1 and listed.size and np.all(np.diff(listed) > 0) and listed[0] >= 0 and listed[-1] < B
         alpha, oma = LD(st["alpha"]), 1 - LD(st["alpha"])
         tol = LD(st["adaptive_rho_tolerance"])
         self.calls += 1
-        done = np.zeros(B, bool)
+        done = np.ones(B, bool)                          # a member that is not listed is never touched
+        done[listed] = False
         status = np.zeros(B, np.int64); iters = np.zeros(B, np.int64); rho_at = np.zeros(B, LD); obj = np.zeros(B, LD)
         moves = []
+        if not st["warm_start"]:
+            self.x[listed] = 0; self.z[listed] = 0; self.y[listed] = 0
 
         def finish(b, code, s, it):
             done[b] = True
@@ -220,12 +276,13 @@ class CommonReference:
                         finish(b, 2, s, it)
                     else:
                         finish(b, -2, s, it)
-        self.status = status.copy()
-        x = (self.D * self.x).astype(np.float64)
-        y = (self.E * self.y / self.c).astype(np.float64)
-        return SimpleNamespace(x=x, y=y, status_val=status, iter=iters, rho_updates=self.rho_updates.copy(),
-                               rho=rho_at.astype(np.float64), obj_val=obj.astype(np.float64), final_rho=float(self.rho),
-                               moves=moves)
+        self.status[listed] = status[listed]
+        self.iters[listed], self.rho_at[listed], self.obj[listed] = iters[listed], rho_at[listed], obj[listed]
+        self.out_x[listed] = (self.D * self.x).astype(np.float64)[listed]
+        self.out_y[listed] = (self.E * self.y / self.c).astype(np.float64)[listed]
+        return SimpleNamespace(x=self.out_x.copy(), y=self.out_y.copy(), status_val=self.status.copy(), iter=self.iters.copy(),
+                               rho_updates=self.rho_updates.copy(), rho=self.rho_at.astype(np.float64),
+                               obj_val=self.obj.astype(np.float64), final_rho=float(self.rho), moves=moves, listed=listed.copy())
 
 
 def margins(ref, call=None):
@@ -239,6 +296,7 @@ def reference_for(orc, P, A, Q, L, U, keep_status=False, dtype=np.longdouble, **
     from _batch_parity import oracle_ws
     from _common_cases import common_oracle
     ws = oracle_ws(common_oracle(orc, P, A, Q, L, U, **kw))
+    kw.pop("scaling", None); kw.pop("rho", None)         # (they have done their work: D, E, c and rho of `ws`)
     return CommonReference(ws, Q, L, U, keep_status=keep_status, dtype=dtype, **kw)
 
 
