@@ -1308,6 +1308,7 @@ struct ResCtx {
   int inject;                        // test hook (OSQP_AMD_RESIDENT_INJECT=k): in the launch of ADMM iteration k one workgroup walks away,
                                      // the others' waits time out -- the give-up path on demand
   const ResWG *wg;
+  const int *ppos;                   // [nwg]: wg[o].pos + wg[o].nr, where workgroup o's three riding partials sit in the exchanged vector
   double *val;                       // [nwg][E][RES_PT]: entry t*E + k of the workgroup's row-major list at (k, t)
   const unsigned short *col;         // same layout: POSITION of the entry's column in the exchanged vector
   const unsigned char *rowl;         // same layout: local row of the entry
@@ -1522,10 +1523,17 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
   extern __shared__ __attribute__((aligned(16))) double rlds[];
   State *st = c.st;
   TL_MARK(c, 5);
-  if (st->stalled || !st->run || st->res_fail) return;
+  // ---- entry: every field of the state, the parameters and the own descriptor in one flight, the returns after one wait ----
+  // (none of these loads depends on another; `a || b || c` on three loads is three round trips)
+  const int s_stalled = st->stalled, s_run = st->run, s_fail = st->res_fail;
+  const unsigned ep0 = st->res_epoch;
+  const int s_pipe_off = st->res_pipe_off, s_pred_off = st->res_pred_off, s_admm_done = st->admm_done;
+  const Params prm = *c.prm;
+  const ResWG w = rc.wg[blockIdx.x];
+  if ((s_stalled != 0) | (s_run == 0) | (s_fail != 0)) return;
   double *uv = rlds;                              // npad doubles: the exchanged vector (rows and riding partials of every workgroup)
   double *seg = uv + rc.npad;                     // RES_TB + RES_MAXROWS row-segment sums
-  double *sc = seg + RES_TB + RES_MAXROWS;        // 8 doubles: gamma, delta, rr, fail word, verdict
+  double *sc = seg + RES_TB + RES_MAXROWS;        // 8 doubles: gamma, delta, rr, fail word, verdict; [5] tol2, [6] "the start vector passes" (written once, before the loop)
   double *sval = sc + 8;                          // 3 x 256: the workgroups' dot partials during exchange (2)
 #ifdef OSQP_AMD_TIMELINE
   long long *tls = reinterpret_cast<long long *>(sval + 768);   // phase stamps of the first 64 exchanges (workgroup 0)
@@ -1539,14 +1547,11 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
 #endif
   const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int nwg = rc.nwg, npad = rc.npad;
-  const ResWG w = rc.wg[g];
-  const Params prm = *c.prm;
-  const unsigned ep0 = st->res_epoch;
-  const bool sabotage = rc.inject > 0 && g == rc.nwg - 1 && st->admm_done + 1 == rc.inject;
+  const bool sabotage = rc.inject > 0 && g == rc.nwg - 1 && s_admm_done + 1 == rc.inject;
   // pipelined recurrences only where a drift would be caught: not in the convexity probe, not after a failed check
-  bool pipe = rc.pipe && !st->res_pipe_off && !prm.no_restart;
+  bool pipe = rc.pipe && !s_pipe_off && !prm.no_restart;
   // the predicted last trip (see the loop): wavefront 0 decides, from sums that are the same in every workgroup
-  bool predict = pipe && rc.predict && !st->res_pred_off;
+  bool predict = pipe && rc.predict && !s_pred_off;
   // ---- own slice of K into registers (issued first: in flight under everything below) ----
   // (wavefronts 1..7; wavefront 0 holds no entries: its loads are the small ones the start-up and the exchanges wait for)
   const bool prod = wv != 0;
@@ -1556,7 +1561,20 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
   for (int k = 0; k < E; ++k) { kv[k] = 0.0; kc[k] = 0; }
   unsigned long long brk = 0ull;
   int slot0 = 0;
+  // u0 = Minv r0 was left in global memory by k_pcg_init (an earlier launch: plain loads see it), in the layout of the exchanged
+  // vector: no exchange needed, one coalesced sweep in the form of the exchange's own (every 16-byte load of a thread in flight at
+  // once: the register peak the kernel pays there anyway).  It needs nothing but kernel arguments, so wavefronts 1..7 issue it
+  // ahead of their entries of K and wavefront 0 behind its start-up sums; a load past the vector's end is dropped by the
+  // descriptor's range check.  It lands in LDS before the barrier in front of the loop (uv has no earlier reader).
+  const bool u0_direct = rc.u0_direct != 0;
+  u32x4 u0v[RES_MAXLD];
+  auto u0_issue = [&]() __attribute__((always_inline)) {
+    const __amdgpu_buffer_rsrc_t ru = res_rsrc(c.u0pos, (size_t)npad * 8);
+#pragma unroll
+    for (int q = 0; q < RES_MAXLD; ++q) u0v[q] = __builtin_amdgcn_raw_buffer_load_b128(ru, (q * RES_TB + t) * 16, 0, 0);
+  };
   if (prod) {
+    if (u0_direct) u0_issue();
 #pragma unroll
     for (int k = 0; k < E; ++k) {
       const size_t idx = ((size_t)g * E + k) * RES_PT + tt;
@@ -1566,17 +1584,35 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
     slot0 = rc.slot0[(size_t)g * RES_PT + tt];
   }
   int sr0 = 0, sr1 = 0;
-  int ppos[4];                         // where the partials of workgroups lane, lane + 64, ... sit in the exchanged vector
+  // where the partials of workgroups lane, lane + 64, ... sit in the exchanged vector: wavefront 0 alone reads them (mode 1), so
+  // it alone loads them, four loads in one flight at clamped indices (an entry past nwg is never used)
+  int ppos[4] = {0, 0, 0, 0};
+  // ---- start-up scalars: ||r0||^2, ||b||^2 from k_pcg_init's partials, by wavefront 0 alone ----
+  // Wavefront 0 holds no entries of K, so none of these loads queues behind K's.  A lane's partials (lane, lane + 64, ...: at most
+  // MAX_PARTS / 64 of each sum) are all in flight at once, at clamped indices, and are added in ascending order from 0.0 (a slot
+  // past gridM adds +0.0, which changes no bit of a sum that started at +0.0), then wave_sum: the order the sum has always had.
+  // tol2 and the verdict "the start vector already passes" reach the other wavefronts through sc[5], sc[6] at the barrier below.
+  constexpr int NPL = MAX_PARTS / 64;
+  static_assert(NPL == 16 && NPL * 64 == MAX_PARTS, "k_pcg_resident: a lane of wavefront 0 holds MAX_PARTS / 64 partials of each start-up sum");
+  double own_r = 0.0, own_u = 0.0, own_x = 0.0, own_mi = 0.0;
+  if (!prod) {
+    const int gm = c.gridM;
+    double pr[NPL], pb[NPL];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) { const int o = lane + 64 * q; ppos[q] = 0; if (o < rc.nwg) { const ResWG wo = rc.wg[o]; ppos[q] = wo.pos + wo.nr; } }
-  // ---- start-up scalars: ||r0||^2, ||b||^2 from k_pcg_init's partials (every wavefront, same order) ----
-  double rr0 = 0.0, bb = 0.0;
-  for (int i = lane; i < c.gridM; i += 64) { rr0 += c.part_rr[i]; bb += c.part_bb[i]; }
-  rr0 = wave_sum(rr0); bb = wave_sum(bb);
-  const double tol2 = fmax(prm.eps_rel * prm.eps_rel * bb, prm.eps_abs * prm.eps_abs);
-  if (rr0 <= tol2) {
-    if (g == 0 && t == 0) { st->done = 1; st->tol2 = tol2; }
-    return;
+    for (int q = 0; q < NPL; ++q) { const int i = min(lane + 64 * q, gm - 1); pr[q] = c.part_rr[i]; pb[q] = c.part_bb[i]; }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) ppos[q] = rc.ppos[min(lane + 64 * q, nwg - 1)];
+    // the own rows in the same flight (clamped: a lane past the workgroup's rows loads a valid element and drops it below)
+    const int jc = min(w.r0 + lane, c.n - 1);
+    own_r = c.init_r[(size_t)jc * c.init_stride]; own_u = c.init_z[jc]; own_x = c.vx[jc]; own_mi = c.minv[jc];
+    sr0 = rc.segrow[(size_t)g * (RES_MAXROWS + 1) + min(lane, RES_MAXROWS)]; sr1 = rc.segrow[(size_t)g * (RES_MAXROWS + 1) + min(lane + 1, RES_MAXROWS)];
+    double rr0 = 0.0, bb = 0.0;
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) { const bool in = lane + 64 * q < gm; rr0 += in ? pr[q] : 0.0; bb += in ? pb[q] : 0.0; }
+    rr0 = wave_sum(rr0); bb = wave_sum(bb);
+    const double tl2 = fmax(prm.eps_rel * prm.eps_rel * bb, prm.eps_abs * prm.eps_abs);
+    if (lane == 0) { sc[3] = 0.0; sc[5] = tl2; sc[6] = rr0 <= tl2 ? 1.0 : 0.0; }
+    if (u0_direct) u0_issue();
   }
   // rows of this workgroup live in the lanes of wavefront 0
   const bool own = wv == 0 && lane < w.nr;
@@ -1591,13 +1627,22 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
   double &mi = RES_ROWSTATE(6), &x0_ = RES_ROWSTATE(7), &r0_ = RES_ROWSTATE(8);
   double &z_ = RES_ROWSTATE(9), &q_ = RES_ROWSTATE(10);     // pipelined recurrences: z = K q, q = Minv s
 #undef RES_ROWSTATE
-  if (own) {
-    r_ = c.init_r[(size_t)j * c.init_stride]; u_ = c.init_z[j]; x_ = c.vx[j]; mi = c.minv[j];
-    x0_ = x_; r0_ = r_;
-    sr0 = rc.segrow[(size_t)g * (RES_MAXROWS + 1) + lane]; sr1 = rc.segrow[(size_t)g * (RES_MAXROWS + 1) + lane + 1];
+  if (own) { r_ = own_r; u_ = own_u; x_ = own_x; mi = own_mi; x0_ = own_x; r0_ = own_r; }
+  else { sr0 = 0; sr1 = 0; }
+  if (u0_direct) {
+    const int half = npad >> 1;
+#pragma unroll
+    for (int q = 0; q < RES_MAXLD; ++q) {
+      const int i2 = q * RES_TB + t;
+      if (i2 < half) { uv[2 * i2] = __hiloint2double((int)u0v[q].y, (int)u0v[q].x); uv[2 * i2 + 1] = __hiloint2double((int)u0v[q].w, (int)u0v[q].z); }
+    }
   }
-  if (t == 0) sc[3] = 0.0;
   __syncthreads();
+  const double tol2 = sc[5];
+  if (sc[6] != 0.0) {                  // the start vector already passes the stop test: all eight wavefronts leave together
+    if (g == 0 && t == 0) { st->done = 1; st->tol2 = tol2; }
+    return;
+  }
   int nx = 0;                          // vector exchanges so far; exchange k carries the tag ep0 + k
   unsigned tag = ep0;
   int par = 0;
@@ -1683,22 +1728,6 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
   };
   // rows of K times the vector in LDS: E products per thread, row segments through LDS; the own-row value
   // in the lanes of wavefront 0 (ends with the barrier that makes the segments visible)
-  // u0 = Minv r0 was left in global memory by k_pcg_init (an earlier launch: plain loads see it): no exchange needed
-  auto load_u0 = [&]() __attribute__((always_inline)) {
-    // (k_pcg_init left it in the layout of the exchanged vector: one coalesced sweep, every load in flight at once)
-    const double2 *src = reinterpret_cast<const double2 *>(c.u0pos);
-    const int half = npad >> 1;
-#pragma unroll
-    for (int h8 = 0; h8 < RES_MAXLD; h8 += 4) {          // four loads in flight per thread and round (registers are the entries of K's)
-      if (h8 * RES_TB >= half) break;
-      double2 v[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { const int i2 = (h8 + q) * RES_TB + t; if (i2 < half) v[q] = src[i2]; }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { const int i2 = (h8 + q) * RES_TB + t; if (i2 < half) { uv[2 * i2] = v[q].x; uv[2 * i2 + 1] = v[q].y; } }
-    }
-    __syncthreads();
-  };
   auto products_issue = [&]() __attribute__((always_inline)) {
     if (prod) {
       // gathers first (all in flight together; the segment writes below could alias them as far as the compiler knows),
@@ -1837,12 +1866,12 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
   int mode = pipe ? 0 : 3;
   int check_why = 0;                   // 0: the pipelined recurrence says converged, 1: its breakdown / iteration cap, 2: long solve, 3: mode 3 says converged
   int checks3 = 0;                     // failed checks of mode-3 verdicts in this solve
-  bool have_u0 = rc.u0_direct;         // the vector k_pcg_init left in global memory is still the u of the recurrences
+  bool have_u0 = u0_direct;            // the vector k_pcg_init left in global memory, in LDS since the barrier above, is still the u of the recurrences
   while (true) {
     double val = u_, m_ = 0.0;
     if (mode == 1) { m_ = mi * w_; val = pred ? x_ - x0_ : m_; }
     else if (mode == 2) val = x_ - x0_;
-    if (have_u0) { ++nx; tag = ep0 + (unsigned)nx; par = (int)(tag & 1u); load_u0(); have_u0 = false; }   // (a fresh tag for the granules of exchange (2))
+    if (have_u0) { ++nx; tag = ep0 + (unsigned)nx; par = (int)(tag & 1u); have_u0 = false; }   // (a fresh tag for the granules of exchange (2))
     else if (!vec_exchange(val, mode == 1)) { failed = true; break; }
     WTL(0);
     products_issue();
@@ -3607,9 +3636,12 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
   if (const char *x = getenv("OSQP_AMD_RESIDENT_INJECT")) rc.inject = atoi(x);
   if (const char *x = getenv("OSQP_AMD_RESIDENT_U0")) rc.u0_direct = atoi(x) != 0;
   unsigned short *d_rowpos = nullptr;
+  std::vector<int> ppos(wg.size());
+  for (size_t o = 0; o < wg.size(); o++) ppos[o] = wg[o].pos + wg[o].nr;
+  int *d_ppos = nullptr;
   ResWG *d_wg = nullptr; unsigned short *d_col = nullptr, *d_slot0 = nullptr, *d_segrow = nullptr; unsigned char *d_rowl = nullptr;
   int *d_krp = nullptr, *d_kcj = nullptr, *d_kps = nullptr, *d_kdst = nullptr; unsigned long long *d_brk = nullptr;
-  if (dev_alloc(e, &d_wg, wg.size()) || dev_alloc(e, &rc.val, slots) || dev_alloc(e, &d_col, slots) || dev_alloc(e, &d_rowl, slots) ||
+  if (dev_alloc(e, &d_wg, wg.size()) || dev_alloc(e, &d_ppos, ppos.size()) || dev_alloc(e, &rc.val, slots) || dev_alloc(e, &d_col, slots) || dev_alloc(e, &d_rowl, slots) ||
       dev_alloc(e, &d_krp, Kptr.size()) || dev_alloc(e, &d_kcj, Kcol.size()) || dev_alloc(e, &d_kps, Kps.size()) || dev_alloc(e, &d_kdst, kdst.size()) ||
       dev_alloc(e, &d_brk, brk.size()) || dev_alloc(e, &d_slot0, slot0.size()) ||
       dev_alloc(e, &d_segrow, segrow.size()) || dev_alloc(e, &d_rowpos, rowpos.size()) || dev_alloc(e, &rc.ubuf, (size_t)2 * rc.npad) ||
@@ -3622,7 +3654,7 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
     rc.kcp = d_kcp; rc.kcm = d_kcm; rc.kca = d_kca;
   }
   e->fk_lists = fk_lists; e->fk_terms = fk_terms; e->fk_bytes = fk_lists ? fk_bytes(nnzK) : 0; e->fk_budget = fk_budget;
-  UP(d_wg, wg); UP(d_rowpos, rowpos); UP(d_col, col); UP(d_rowl, rowl); UP(d_krp, Kptr); UP(d_kcj, Kcol); UP(d_kps, Kps); UP(d_kdst, kdst); UP(d_brk, brk); UP(d_slot0, slot0); UP(d_segrow, segrow);
+  UP(d_wg, wg); UP(d_ppos, ppos); UP(d_rowpos, rowpos); UP(d_col, col); UP(d_rowl, rowl); UP(d_krp, Kptr); UP(d_kcj, Kcol); UP(d_kps, Kps); UP(d_kdst, kdst); UP(d_brk, brk); UP(d_slot0, slot0); UP(d_segrow, segrow);
 #undef UP
   HIPCHK(hipStreamSynchronize(e->stream));       // the sources are locals
   {
@@ -3630,7 +3662,7 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
     if (dev_alloc(e, &d_u0pos, (size_t)rc.npad)) return HIPENG_ERR_HIP;       // (zeroed: the padding positions are read, never written)
     e->c.u0map = d_rowpos; e->c.u0pos = d_u0pos;
   }
-  rc.wg = d_wg; rc.rowpos = d_rowpos; rc.col = d_col; rc.rowl = d_rowl; rc.krp = d_krp; rc.kcj = d_kcj; rc.kps = d_kps; rc.kdst = d_kdst; rc.brk = d_brk; rc.slot0 = d_slot0; rc.segrow = d_segrow;
+  rc.wg = d_wg; rc.ppos = d_ppos; rc.rowpos = d_rowpos; rc.col = d_col; rc.rowl = d_rowl; rc.krp = d_krp; rc.kcj = d_kcj; rc.kps = d_kps; rc.kdst = d_kdst; rc.brk = d_brk; rc.slot0 = d_slot0; rc.segrow = d_segrow;
   e->rc = rc;
   e->res_lds = ((size_t)rc.npad + RES_TB + RES_MAXROWS + 3 + 16 + 768 + 5 * 64 + 96) * sizeof(double);   // + phase stamps of the TIMELINE build
   int rcode = 0;
@@ -4958,6 +4990,19 @@ extern "C" int hipeng_resident_trips(hipeng *e, long long out[8]) {
   out[0] = s.res_trips; out[1] = s.res_solves; out[2] = s.res_pred_hit; out[3] = s.res_pred_miss;
   out[4] = s.res_pred_off; out[5] = e->res_kind == 1 ? e->rc.predict : 0; out[6] = s.res_pred_win[0]; out[7] = s.res_pred_win[2] - s.res_pred_win[1];
   return 0;
+}
+
+// Resident PCG, for the tests: what the start-up of the last launch summed.  Returns gridM (or a negative code); part_bb receives
+// min(gridM, cap) partials of ||b||^2 as the last k_pcg_init left them, *tol2 State::tol2 as the last launch stored it.
+extern "C" long long hipeng_resident_start_peek(hipeng *e, double *part_bb, long long cap, double *tol2) {
+  if (!e || e->res_kind != 1 || !part_bb || !tol2 || cap < 0) return HIPENG_ERR_ARG;
+  if (hipSetDevice(e->device) != hipSuccess) return HIPENG_ERR_HIP;
+  State s;
+  if (read_state(e, &s)) return HIPENG_ERR_HIP;       // (synchronises the stream)
+  const long long cnt = std::min<long long>(e->c.gridM, cap);
+  if (cnt > 0 && hipMemcpy(part_bb, e->c.part_bb, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return HIPENG_ERR_HIP;
+  *tol2 = s.tol2;
+  return e->c.gridM;
 }
 
 // Resident PCG, for the tests: the rows of K as the resident kernel holds them.  row/col/val receive nnz(K) triplets
