@@ -387,6 +387,81 @@ c_int osqp_amd_batch_polish_status_dev(osqp_amd_batch *b, int *status_polish);
  * (NULL included).  Asks the runtime about the address; reads and writes no GPU memory. */
 c_int osqp_amd_batch_check_dev_ptr(osqp_amd_batch *b, const void *p);
 
+/* ---- Chosen members: the calls around the solve -----------------------------------------------------------------
+ * Each call below is the twin named in its comment "for the listed members": `members [count]`, a HOST list (in the
+ * _dev forms too: it belongs to the call, not to the data), strictly ascending, every index in [0, batch) -- the checks
+ * of osqp_amd_batch_solve_members -- in front of the twin's arguments, and every per-member array COMPACT: [count][.],
+ * row k belongs to member members[k].  All three engines serve them.  Of a member that is not listed nothing changes:
+ * its raw and scaled q, l, u, its row classes and flags, X, Y, info8, both certificates, the stored iterates, its solved
+ * flag and its status_polish keep their bits.  count == batch is the whole-batch twin to the bit, in every output and
+ * in every piece of handle state: it runs the twin's own code.
+ * Refusals come first, in this order, with nothing written:
+ *   1. OSQP_WORKSPACE_NOT_INIT_ERROR   handle is NULL;
+ *   2. OSQP_DATA_VALIDATION_ERROR      the list: NULL, count < 1, count > batch, an index out of range, not strictly
+ *                                      ascending;
+ *   3. the twin's own refusals, in the twin's order (a common-K handle without its shared KKT pieces refuses the polish,
+ *      adjoint and tangent forms with OSQP_LINSYS_SOLVER_INIT_ERROR and the twin's line on stderr, naming the call).
+ * The handle keeps one solved flag and one polished flag per member.  A member's solved flag is set by a solve that
+ * lists it (or a whole solve) and cleared by every update or warm start that touches it; its polished flag is set when
+ * polish has run on it, by either polish call, and cleared with the solved flag and by the member's next solve. */
+
+/* osqp_amd_batch_update for the listed members: Q [count][n], L, U [count][m] (NULL = keep).  The raw rows of the listed
+ * members are replaced, scaled with the stored D, E, c and re-classified; a class change requests the member's K^-1
+ * again; rho_updates of the listed members restarts.  Clears the solved flag of the listed members only and drops a kept
+ * KKT inversion.  Returns 1, with nothing of the handle changed, when some listed row has L > U (_dev: after the clamp
+ * to +-OSQP_INFTY) or, on a common-K handle with count < batch, when a listed member's new bounds would give a row
+ * another class than the handle holds for it (stderr names member and row): the unlisted members keep that class. */
+c_int osqp_amd_batch_update_members(osqp_amd_batch *b, const c_int *members, c_int count,
+                                    const c_float *Q, const c_float *L, const c_float *U);
+c_int osqp_amd_batch_update_members_dev(osqp_amd_batch *b, const c_int *members, c_int count,
+                                        const c_float *Q, const c_float *L, const c_float *U);
+/* osqp_amd_batch_warm_start for the listed members: X [count][n], Y [count][m], unscaled (NULL = keep).  Turns the
+ * warm_start setting on; with arrays it rewrites the listed members' scaled x, z = A x and y, clears their solved flags
+ * and drops a kept KKT inversion.  Both NULL: 0 after the argument checks, no GPU work. */
+c_int osqp_amd_batch_warm_start_members(osqp_amd_batch *b, const c_int *members, c_int count,
+                                        const c_float *X, const c_float *Y);
+c_int osqp_amd_batch_warm_start_members_dev(osqp_amd_batch *b, const c_int *members, c_int count,
+                                            const c_float *X, const c_float *Y);
+/* osqp_amd_batch_polish for the listed members; status_polish [count].  Needs every LISTED member solved on the current
+ * problem (OSQP_WORKSPACE_NOT_INIT_ERROR otherwise, nothing changed).  The work is done for the listed members whose
+ * polished flag is unset, with the padded orders of their largest active set; a repeat does no work and reports the
+ * same values.  A call that does work drops a kept KKT inversion.  osqp_amd_batch_polish keeps its own rule: it works
+ * once per solve on every member, whatever the member calls have done, and sets every member's polished flag. */
+c_int osqp_amd_batch_polish_members(osqp_amd_batch *b, const c_int *members, c_int count, c_int *status_polish);
+/* osqp_amd_batch_adjoint_multi for the listed members: ncot >= 1 cotangents per member, dX [count][ncot][n], dY
+ * [count][ncot][m] (NULL = 0), dQ, dL, dU, dPx, dAx [count][ncot][.], active [count][m], status_adjoint [count].  Needs
+ * every listed member solved on the current problem.  Plan, buffer cap, chunks, statuses and the zero outputs of members
+ * whose solve did not end OSQP_SOLVED are the twin's; the bits of a listed member are those of the whole-batch call on
+ * the same state.  A one-chunk build is kept together with its list: a later _members call on the same solve reuses it
+ * exactly when its list is identical, a whole-batch call reuses only a whole-batch build (osqp_amd_batch_kkt_info:
+ * out[3] = the members kept). */
+c_int osqp_amd_batch_adjoint_members(osqp_amd_batch *b, const c_int *members, c_int count, c_int ncot,
+                                     const c_float *dX, const c_float *dY /*NULL = 0*/,
+                                     c_float *dQ, c_float *dL, c_float *dU, c_float *dPx /*NULL = skip*/,
+                                     c_float *dAx /*NULL = skip*/, c_int *active /*NULL = skip*/, c_int *status_adjoint);
+c_int osqp_amd_batch_adjoint_members_dev(osqp_amd_batch *b, const c_int *members, c_int count, c_int ncot,
+                                         const c_float *dX, const c_float *dY, c_float *dQ, c_float *dL, c_float *dU,
+                                         c_float *dPx, c_float *dAx, int *active, int *status_adjoint);
+/* osqp_amd_batch_tangent for the listed members: tangents [count][ndir][.] in, dX [count][ndir][n], dY [count][ndir][m],
+ * active [count][m], status_tangent [count] out; precondition and kept inversion as osqp_amd_batch_adjoint_members. */
+c_int osqp_amd_batch_tangent_members(osqp_amd_batch *b, const c_int *members, c_int count, c_int ndir,
+                                     const c_float *dQ, const c_float *dL, const c_float *dU, const c_float *dPx,
+                                     const c_float *dAx, c_float *dX, c_float *dY /*NULL = skip*/,
+                                     c_int *active /*NULL = skip*/, c_int *status_tangent);
+c_int osqp_amd_batch_tangent_members_dev(osqp_amd_batch *b, const c_int *members, c_int count, c_int ndir,
+                                         const c_float *dQ, const c_float *dL, const c_float *dU, const c_float *dPx,
+                                         const c_float *dAx, c_float *dX, c_float *dY, int *active, int *status_tangent);
+/* osqp_amd_batch_get for the listed members: a gather of their rows into X, DX [count][n], Y, DY [count][m], info8
+ * [count][8] (NULL = skip).  The _dev form writes caller-owned device arrays, exactly count rows of each. */
+c_int osqp_amd_batch_get_members(osqp_amd_batch *b, const c_int *members, c_int count, c_float *X, c_float *Y,
+                                 c_float *info8, c_float *DX, c_float *DY);
+c_int osqp_amd_batch_get_members_dev(osqp_amd_batch *b, const c_int *members, c_int count, c_float *X, c_float *Y,
+                                     c_float *info8, c_float *DX, c_float *DY);
+/* out [batch]: 1 where the member's results are those of a solve of the problem the handle holds now (what the polish,
+ * adjoint and tangent forms above require of the members they list), 0 otherwise.  OSQP_DATA_VALIDATION_ERROR for a
+ * NULL out.  Touches no GPU memory. */
+c_int osqp_amd_batch_solved_members(osqp_amd_batch *b, c_int *out);
+
 /* For the tests: member qp's workspace as the last setup / update / solve left it.  NULL = skip.
  * D [n], E [m], c [1], rho [1] (current scalar rho), ctype [m] (-1 free, 0 ineq, 1 eq),
  * Pv [nnzP], Av [nnzA] (scaled values, CSC order), Kinv [NP*NP] row-major, *NP = 64 or 128

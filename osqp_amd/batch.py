@@ -85,6 +85,26 @@ def _bind(L):
         f = getattr(L, "osqp_amd_batch_" + name)
         f.restype = abi.c_int
         f.argtypes = [H] + args
+    # the member-list forms: (members, count) -- a host list in the _dev forms too -- in front of the twin's arguments
+    F, I = abi.c_float_p, abi.c_int_p
+    for name, args in MEMBER_CALLS.items():
+        f = getattr(L, "osqp_amd_batch_" + name)
+        f.restype = abi.c_int
+        f.argtypes = [H, I, abi.c_int] + [dict(f=F, i=I, v=V, n=abi.c_int)[k] for k in args]
+    L.osqp_amd_batch_solved_members.restype = abi.c_int
+    L.osqp_amd_batch_solved_members.argtypes = [H, I]
+
+
+# the arguments of each osqp_amd_batch_<name> after (handle, members, count): f = float array, i = c_int array,
+# v = device address, n = c_int
+MEMBER_CALLS = {
+    "update_members": "fff", "update_members_dev": "vvv",
+    "warm_start_members": "ff", "warm_start_members_dev": "vv",
+    "polish_members": "i",
+    "adjoint_members": "n" + "f" * 7 + "ii", "adjoint_members_dev": "n" + "v" * 9,
+    "tangent_members": "n" + "f" * 7 + "ii", "tangent_members_dev": "n" + "v" * 9,
+    "get_members": "fffff", "get_members_dev": "vvvvv",
+}
 
 
 def _p(a):
@@ -476,15 +496,41 @@ class BatchOSQP:
                                "there is no packed device image to read or write" % BATCH_MAX_N)
         return route
 
-    def _dev(self, a, cols, name, typestr="<f8", writable=False):
-        """Device pointer of a [B, cols] array (None, or nothing to read: NULL)."""
+    def _dev(self, a, cols, name, typestr="<f8", writable=False, rows=None):
+        """Device pointer of a [B, cols] array -- [rows, cols] in a members= call -- (None, or nothing to read: NULL)."""
         if a is None:
             return None
-        return device_view(a, (self.B, cols), typestr, writable, name) or None
+        return device_view(a, (self.B if rows is None else rows, cols), typestr, writable, name) or None
 
-    def update(self, Q=None, L=None, U=None):
+    def _members(self, members, call):
+        """The list of a members= call as the C side takes it (check_members), once the handle can serve one: the
+        one-engine-per-member route keeps no packed batch to address by member."""
+        if self._many is not None:
+            raise RuntimeError("%s(members=...) is not served by the one-engine-per-member route (engine=\"auto\", n > %d); "
+                               "set the batch up with engine=\"streamed\" or engine=\"common\"" % (call, BATCH_MAX_N))
+        return check_members(self.B, members)
+
+    def solved_members(self):
+        """Boolean [B]: True where the member's results are those of a solve of the problem the handle holds now -- what
+        polish, adjoint and tangent with members= require of the members they list.  Touches no GPU memory."""
+        if self._many is not None:
+            raise RuntimeError("solved_members is not served by the one-engine-per-member route (engine=\"auto\", n > %d)"
+                               % BATCH_MAX_N)
+        out = np.zeros(self.B, np.int64)
+        rc = self._lib.osqp_amd_batch_solved_members(self._h, abi.iptr(out))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_solved_members failed (%d)" % rc)
+        return out != 0
+
+    def update(self, Q=None, L=None, U=None, members=None):
         """osqp_update_lin_cost / _bounds for every QP (None = keep).  Host arrays, or device arrays (objects with
-        `__cuda_array_interface__`, complete when the call is made): those are clamped, checked and scaled on the device."""
+        `__cuda_array_interface__`, complete when the call is made): those are clamped, checked and scaled on the device.
+        members= (an ascending index list or a boolean mask of length B): for the listed members only, with compact
+        arrays Q [count, n], L, U [count, m], row k for the k-th listed member; the others keep their data, their results
+        and their solved flag (solved_members).  engine="common": returns 1, with nothing changed, when a listed member's
+        new bounds would give a row another class than the batch holds for it."""
+        if members is not None:
+            return self._update_members(self._members(members, "update"), Q, L, U)
         if self._route(Q=Q, L=L, U=U) == "device":
             return int(self._lib.osqp_amd_batch_update_dev(self._h, self._dev(Q, self.n, "Q"), self._dev(L, self.m, "L"),
                                                            self._dev(U, self.m, "U")))
@@ -499,6 +545,27 @@ class BatchOSQP:
         if self._many is not None:
             return self._many_update(Q, L, U)
         return int(self._lib.osqp_amd_batch_update(self._h, _p(Q), _p(L), _p(U)))
+
+    def _update_members(self, mem, Q, L, U):
+        R, n, m = int(mem.size), self.n, self.m
+        want = "update arrays with members= must be compact: Q [%d, %d], L [%d, %d], U [%d, %d] for the %d listed members" \
+               % (R, n, R, m, R, m, R)
+        if self._route(Q=Q, L=L, U=U) == "device":
+            for a, k in ((Q, n), (L, m), (U, m)):
+                if a is not None and tuple(a.__cuda_array_interface__["shape"]) != (R, k):
+                    raise ValueError(want)
+            return int(self._lib.osqp_amd_batch_update_members_dev(
+                self._h, abi.iptr(mem), R, self._dev(Q, n, "Q", rows=R), self._dev(L, m, "L", rows=R),
+                self._dev(U, m, "U", rows=R)))
+        Q = None if Q is None else abi.as_f64(Q)
+        L = None if L is None else np.maximum(abi.as_f64(L), -abi.OSQP_INFTY)
+        U = None if U is None else np.minimum(abi.as_f64(U), abi.OSQP_INFTY)
+        if (Q is not None and Q.shape != (R, n)) or (L is not None and L.shape != (R, m)) or \
+           (U is not None and U.shape != (R, m)):
+            raise ValueError(want)
+        if L is not None and U is not None and np.any(L > U):
+            raise ValueError("lower bound greater than upper bound")
+        return int(self._lib.osqp_amd_batch_update_members(self._h, abi.iptr(mem), R, _p(Q), _p(L), _p(U)))
 
     def _many_each(self, call):
         # as _many_update: the first failing member's code comes back
@@ -592,9 +659,26 @@ class BatchOSQP:
             return self._many_each(lambda b, s: s.update_rho(rho[b if per else 0]))
         return int(self._lib.osqp_amd_batch_update_rho(self._h, abi.fptr(rho), per))
 
-    def warm_start(self, X=None, Y=None):
+    def warm_start(self, X=None, Y=None, members=None):
         """osqp_warm_start (_x, _y) for every QP: X [B, n], Y [B, m], unscaled; turns the warm_start setting on.  Host
-        arrays or device arrays."""
+        arrays or device arrays.  members=: for the listed members only, X [count, n], Y [count, m]; the others keep their
+        iterates and their solved flag."""
+        if members is not None:
+            mem = self._members(members, "warm_start")
+            R, n, m = int(mem.size), self.n, self.m
+            want = "warm start arrays with members= must be compact: X [%d, %d], Y [%d, %d] for the %d listed members" \
+                   % (R, n, R, m, R)
+            if self._route(X=X, Y=Y) == "device":
+                for a, k in ((X, n), (Y, m)):
+                    if a is not None and tuple(a.__cuda_array_interface__["shape"]) != (R, k):
+                        raise ValueError(want)
+                return int(self._lib.osqp_amd_batch_warm_start_members_dev(
+                    self._h, abi.iptr(mem), R, self._dev(X, n, "X", rows=R), self._dev(Y, m, "Y", rows=R) if m else None))
+            X = None if X is None else abi.as_f64(X)
+            Y = None if Y is None else abi.as_f64(Y)
+            if (X is not None and X.shape != (R, n)) or (Y is not None and Y.shape != (R, m)):
+                raise ValueError(want)
+            return int(self._lib.osqp_amd_batch_warm_start_members(self._h, abi.iptr(mem), R, _p(X), _p(Y if m else None)))
         if self._route(X=X, Y=Y) == "device":
             return int(self._lib.osqp_amd_batch_warm_start_dev(self._h, self._dev(X, self.n, "X"),
                                                                self._dev(Y, self.m, "Y") if self.m else None))
@@ -644,14 +728,30 @@ class BatchOSQP:
             raise RuntimeError("osqp_amd_batch_common_columns failed (%d)" % rc)
         return Columns(*(int(v) for v in out))
 
-    def polish(self, fetch=True):
+    def polish(self, fetch=True, members=None):
         """Polish (src/polish.c) on the device for every member whose last solve ended `solved`, with the handle's
         `delta` and `polish_refine_iter`.  Returns results() -- x, y, obj_val, pri_res, dua_res of the accepted
         members are the polished ones -- with `status_polish` [B]: 1 accepted, -1 tried and rejected (nothing of
         that member changed), 0 not tried.  Needs a solve since setup or the last update.  fetch=False: nothing is
         copied to the host and None is returned (results_into reads the outcome on the device; a later results() fetches
-        the status then)."""
+        the status then).
+        members=: polish for the listed members only, each of which must be solved on the current problem
+        (solved_members); the work is done once per member and solve.  Returns results(members=) -- compact rows -- with
+        `status_polish` [count]."""
         self._unserved("polish")
+        if members is not None:
+            mem = self._members(members, "polish")
+            sp = np.zeros(mem.size, np.int64) if fetch else None
+            rc = self._lib.osqp_amd_batch_polish_members(self._h, abi.iptr(mem), mem.size,
+                                                         abi.iptr(sp) if fetch else C.cast(None, abi.c_int_p))
+            if rc:
+                raise RuntimeError("osqp_amd_batch_polish_members failed (%d)%s"
+                                   % (rc, ": a listed member has not been solved on the current problem" if rc == 7 else ""))
+            if not fetch:
+                return None
+            out = self.results(members=mem)
+            out.status_polish = sp
+            return out
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): polish is a call of the batch "
                                "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
@@ -663,7 +763,7 @@ class BatchOSQP:
         self._status_polish = sp if fetch else "device"       # results() reads it when it is first asked for
         return self.results() if fetch else None
 
-    def adjoint(self, dX, dY=None, matrices=False):
+    def adjoint(self, dX, dY=None, matrices=False, members=None):
         """Adjoint derivatives of the solution on the device, for every member whose last solve ended `solved`: from
         dX = dl/dx [B, n] and dY = dl/dy [B, m] (None = 0) of a scalar l, a namespace with dq [B, n], dl, du [B, m],
         dPx [B, nnzP] and dAx [B, nnzA] (CSC order of triu(P) / A; None unless matrices=True; an off-diagonal dPx slot
@@ -675,8 +775,13 @@ class BatchOSQP:
         dX [B, D, n] with dY [B, D, m] (or None): D cotangents per member in one call, on one KKT inversion; the five
         gradients come back [B, D, .], active and status_adjoint per member -- D rows of the Jacobian; slice d carries
         the bits adjoint(dX[:, d], dY[:, d]) returns.
-        On one solve, adjoint() and tangent() share the KKT inversion the first of them builds (kkt_info)."""
+        On one solve, adjoint() and tangent() share the KKT inversion the first of them builds (kkt_info).
+        members=: for the listed members only, each solved on the current problem; every array is compact, [count, .] or
+        [count, D, .], and the KKT inversion is built for the listed members alone (and shared by later members= calls
+        with the same list)."""
         self._unserved("adjoint")
+        if members is not None:
+            return self._adjoint_members(self._members(members, "adjoint"), dX, dY, matrices)
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): adjoint is a call of the batch "
                                "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
@@ -700,6 +805,39 @@ class BatchOSQP:
         return SimpleNamespace(dq=cut(dq, n), dl=cut(dl, m), du=cut(du, m), dPx=cut(dPx, nP), dAx=cut(dAx, nA),
                                active=act[:, :m], status_adjoint=sa)
 
+    @staticmethod
+    def _compact(e, B, R):
+        """The message of a shape check made with R rows, worded for a members= call."""
+        return ValueError("with members= the arrays are compact (%d listed members): %s"
+                          % (R, str(e).replace("B = %d" % R, "count = %d" % R).replace("[B,", "[count,")))
+
+    def _adjoint_members(self, mem, dX, dY, matrices):
+        R, n, m, nP, nA = int(mem.size), self.n, self.m, self.Pu.nnz, self.Ah.nnz
+        flat = np.ndim(dX) != 3
+        try:
+            if flat:
+                dX, dY = check_adjoint(R, n, m, dX, dY)
+                dX = dX[:, None, :]; dY = None if dY is None else dY[:, None, :]
+                D = 1
+            else:
+                dX, dY, D = check_adjoint_multi(R, n, m, dX, dY)
+        except ValueError as e:
+            raise self._compact(e, self.B, R) from None
+        dX = abi.as_f64(dX); dY = None if dY is None else abi.as_f64(dY)
+        dq = np.zeros((R, D, n)); dl = np.zeros((R, D, max(m, 1))); du = np.zeros((R, D, max(m, 1)))
+        dPx = np.zeros((R, D, max(nP, 1))) if matrices else None
+        dAx = np.zeros((R, D, max(nA, 1))) if matrices else None
+        act = np.zeros((R, max(m, 1)), np.int64); sa = np.zeros(R, np.int64)
+        rc = self._lib.osqp_amd_batch_adjoint_members(self._h, abi.iptr(mem), R, D, abi.fptr(dX), _p(dY if m else None),
+                                                      abi.fptr(dq), abi.fptr(dl), abi.fptr(du), _p(dPx), _p(dAx),
+                                                      abi.iptr(act), abi.iptr(sa))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_adjoint_members failed (%d)%s"
+                               % (rc, ": a listed member has not been solved on the current problem" if rc == 7 else ""))
+        cut = lambda a, k: None if a is None else (a[:, 0, :k] if flat else a[:, :, :k])
+        return SimpleNamespace(dq=cut(dq, n), dl=cut(dl, m), du=cut(du, m), dPx=cut(dPx, nP), dAx=cut(dAx, nA),
+                               active=act[:, :m], status_adjoint=sa)
+
     def kkt_info(self):
         """For the tests and tools: (builds, kept, npol, members) -- passes of KKT formation and inversion over the solved
         members since setup (polish's included), whether an inversion is kept for the next adjoint() / tangent() on this
@@ -714,7 +852,7 @@ class BatchOSQP:
             raise RuntimeError("osqp_amd_batch_kkt_info failed (%d)" % rc)
         return KktInfo(*(int(v) for v in out))
 
-    def tangent(self, dQ=None, dL=None, dU=None, dPx=None, dAx=None):
+    def tangent(self, dQ=None, dL=None, dU=None, dPx=None, dAx=None, members=None):
         """Forward sensitivities of the solution on the device, for every member whose last solve ended `solved`: from
         tangents of the data -- dQ [B, n], dL, dU [B, m], dPx [B, nnzP], dAx [B, nnzA] (CSC order of triu(P) / A; an
         off-diagonal dPx slot stands for both halves of P), or each of them [B, D, k] for D directions per member
@@ -723,8 +861,27 @@ class BatchOSQP:
         members that are not 1 are 0.  Only the tangent of the bound a row is active at counts (dL = dU on an
         equality row).  The point differentiated is the one the handle holds, as for adjoint().  To first order the
         solution of the moved problem is r.x + t.dx, r.y + t.dy.  Changes nothing in the handle.  Needs a solve since
-        setup or the last update."""
+        setup or the last update.
+        members=: for the listed members only, as adjoint(members=): compact arrays, [count, k] or [count, D, k]."""
         self._unserved("tangent")
+        if members is not None:
+            mem = self._members(members, "tangent")
+            R, n, m = int(mem.size), self.n, self.m
+            try:
+                dQ, dL, dU, dPx, dAx, D, flat = check_tangent(R, n, m, self.Pu.nnz, self.Ah.nnz, dQ, dL, dU, dPx, dAx)
+            except ValueError as e:
+                raise self._compact(e, self.B, R) from None
+            dx = np.zeros((R, D, n)); dy = np.zeros((R, D, max(m, 1)))
+            act = np.zeros((R, max(m, 1)), np.int64); st = np.zeros(R, np.int64)
+            rc = self._lib.osqp_amd_batch_tangent_members(
+                self._h, abi.iptr(mem), R, D, _p(dQ), _p(dL if m else None), _p(dU if m else None), _p(dPx), _p(dAx),
+                abi.fptr(dx), _p(dy if m else None), abi.iptr(act), abi.iptr(st))
+            if rc:
+                raise RuntimeError("osqp_amd_batch_tangent_members failed (%d)%s"
+                                   % (rc, ": a listed member has not been solved on the current problem" if rc == 7 else ""))
+            dy = dy[:, :, :m]
+            return SimpleNamespace(dx=dx[:, 0] if flat else dx, dy=dy[:, 0] if flat else dy, active=act[:, :m],
+                                   status_tangent=st)
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): tangent is a call of the batch "
                                "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
@@ -740,7 +897,25 @@ class BatchOSQP:
         dy = dy[:, :, :m]
         return SimpleNamespace(dx=dx[:, 0] if flat else dx, dy=dy[:, 0] if flat else dy, active=act[:, :m], status_tangent=st)
 
-    def results(self):
+    def results(self, members=None):
+        """The results of every member, or with members= the compact rows of the listed ones (status_polish: of the last
+        whole-batch polish)."""
+        if members is not None:
+            mem = self._members(members, "results")
+            R, n, m = int(mem.size), self.n, self.m
+            X = np.zeros((R, n)); Y = np.zeros((R, max(m, 1)))
+            info = np.zeros((R, 8)); DX = np.zeros((R, n)); DY = np.zeros((R, max(m, 1)))
+            rc = self._lib.osqp_amd_batch_get_members(self._h, abi.iptr(mem), R, abi.fptr(X), _p(Y if m else None),
+                                                      abi.fptr(info), abi.fptr(DX), _p(DY if m else None))
+            if rc:
+                raise RuntimeError("osqp_amd_batch_get_members failed (%d)" % rc)
+            out = SimpleNamespace(x=X, y=Y[:, :m], dual_inf_cert=DX, prim_inf_cert=DY[:, :m], info_raw=info)
+            sp = self._status_polish
+            out.status_polish = sp[mem].copy() if isinstance(sp, np.ndarray) else np.zeros(R, np.int64)
+            for k, name in enumerate(INFO_FIELDS):
+                col = info[:, k]
+                setattr(out, name, col.astype(np.int64) if name in ("iter", "status_val", "rho_updates") else col)
+            return out
         if self._many is not None:
             return self._many_results()
         X = np.zeros((self.B, self.n)); Y = np.zeros((self.B, max(self.m, 1)))
@@ -761,14 +936,27 @@ class BatchOSQP:
             setattr(out, name, col.astype(np.int64) if name in ("iter", "status_val", "rho_updates") else col)
         return out
 
-    def results_into(self, X=None, Y=None, info=None, DX=None, DY=None, status_polish=None):
+    def results_into(self, X=None, Y=None, info=None, DX=None, DY=None, status_polish=None, members=None):
         """The results into device arrays of the caller's (None = skip): X, DX [B, n], Y, DY [B, m], info [B, 8]
         (INFO_FIELDS) float64, status_polish [B] int32 (1 accepted, -1 rejected, 0 not tried or no polish since the
         last solve; needs a solve on the current problem).  Device-to-device copies, ready on return; a later solve
-        does not touch them.  For m = 0 the m-sized arguments may be None."""
+        does not touch them.  For m = 0 the m-sized arguments may be None.
+        members=: the listed members' rows into compact arrays [count, .]; exactly count rows are written.  status_polish
+        is a whole-batch array and is not taken together with members=."""
         if self._route(X=X, Y=Y, info=info, DX=DX, DY=DY, status_polish=status_polish) != "device":
             raise ValueError("results_into writes device arrays (objects with __cuda_array_interface__); results() returns "
                              "host arrays")
+        if members is not None:
+            mem = self._members(members, "results_into")
+            if status_polish is not None:
+                raise ValueError("results_into(members=...) takes no status_polish: it is a [B] array of the whole-batch polish")
+            R = int(mem.size)
+            d = lambda a, cols, name: self._dev(a, cols, name, writable=True, rows=R)
+            rc = self._lib.osqp_amd_batch_get_members_dev(self._h, abi.iptr(mem), R, d(X, self.n, "X"), d(Y, self.m, "Y"),
+                                                          d(info, 8, "info"), d(DX, self.n, "DX"), d(DY, self.m, "DY"))
+            if rc:
+                raise RuntimeError("osqp_amd_batch_get_members_dev failed (%d)%s" % (rc, _BAD_POINTER if rc == 1 else ""))
+            return
         d = lambda a, cols, name: self._dev(a, cols, name, writable=True)
         rc = self._lib.osqp_amd_batch_get_dev(self._h, d(X, self.n, "X"), d(Y, self.m, "Y"), d(info, 8, "info"),
                                               d(DX, self.n, "DX"), d(DY, self.m, "DY"))
@@ -783,7 +971,7 @@ class BatchOSQP:
                                    % (rc, ": no solve has run on the current problem" if rc == 7 else
                                       _BAD_POINTER if rc == 1 else ""))
 
-    def adjoint_into(self, dX, dY, dq, dl, du, dPx=None, dAx=None, active=None, status_adjoint=None):
+    def adjoint_into(self, dX, dY, dq, dl, du, dPx=None, dAx=None, active=None, status_adjoint=None, members=None):
         """adjoint() between device arrays of the caller's: from dX [B, n] and dY [B, m] (None = 0) into dq [B, n], dl, du
         [B, m] and, where given, dPx [B, nnzP], dAx [B, nnzA] (float64), active [B, m], status_adjoint [B] (int32).
         For m = 0 the m-sized arguments may be None.  Ready on return.  With dX [B, D, n] every float array is [B, D, .]
@@ -798,9 +986,17 @@ class BatchOSQP:
         B, n, m, nP, nA = self.B, self.n, self.m, self.Pu.nnz, self.Ah.nnz
         flat = len(dX.__cuda_array_interface__["shape"]) != 3     # as adjoint(): [B, n] takes the single-cotangent entry point
         D, call, lead = 1, "osqp_amd_batch_adjoint_dev", ()
+        mem = None if members is None else self._members(members, "adjoint_into")
+        if mem is not None:                       # compact arrays: B stands for the listed members from here on
+            B = int(mem.size)
         if not flat:
-            dX, dY, D = check_adjoint_multi(B, n, m, dX, dY, dq=(dq, n), dl=(dl, m), du=(du, m), dPx=(dPx, nP), dAx=(dAx, nA))
+            try:
+                dX, dY, D = check_adjoint_multi(B, n, m, dX, dY, dq=(dq, n), dl=(dl, m), du=(du, m), dPx=(dPx, nP), dAx=(dAx, nA))
+            except ValueError as e:
+                raise (e if mem is None else self._compact(e, self.B, B)) from None
             call, lead = "osqp_amd_batch_adjoint_multi_dev", (D,)
+        if mem is not None:
+            call, lead = "osqp_amd_batch_adjoint_members_dev", (abi.iptr(mem), B, D)
 
         def d(a, cols, name, writable=True):
             if a is None:
@@ -808,13 +1004,14 @@ class BatchOSQP:
             return device_view(a, (B, cols) if flat else (B, D, cols), "<f8", writable, name) or None
         rc = getattr(self._lib, call)(
             self._h, *lead, d(dX, n, "dX", False), d(dY, m, "dY", False), d(dq, n, "dq"), d(dl, m, "dl"), d(du, m, "du"),
-            d(dPx, nP, "dPx"), d(dAx, nA, "dAx"), self._dev(active, m, "active", "<i4", True),
+            d(dPx, nP, "dPx"), d(dAx, nA, "dAx"), self._dev(active, m, "active", "<i4", True, rows=B),
             None if status_adjoint is None else device_view(status_adjoint, (B,), "<i4", True, "status_adjoint"))
         if rc:
             raise RuntimeError("%s failed (%d)%s" % (call, rc, ": no solve has run on the current problem" if rc == 7 else
                                                      _BAD_POINTER if rc == 1 else ""))
 
-    def tangent_into(self, dx, dy, dQ=None, dL=None, dU=None, dPx=None, dAx=None, active=None, status_tangent=None):
+    def tangent_into(self, dx, dy, dQ=None, dL=None, dU=None, dPx=None, dAx=None, active=None, status_tangent=None,
+                     members=None):
         """tangent() between device arrays of the caller's: from dQ, dL, dU, dPx, dAx (None = 0; [B, k], or [B, D, k] for
         D directions) into dx [B, n] and dy [B, m] (or [B, D, .], as the tangents; float64) and, where given, active
         [B, m], status_tangent [B] (int32).  For m = 0 dy may be None.  Ready on return."""
@@ -826,19 +1023,27 @@ class BatchOSQP:
         if dx is None or (self.m and dy is None):
             raise ValueError("tangent_into needs dx and, for m > 0, dy")
         B, n, m = self.B, self.n, self.m
-        dQ, dL, dU, dPx, dAx, D, flat = check_tangent(B, n, m, self.Pu.nnz, self.Ah.nnz, dQ, dL, dU, dPx, dAx, dx=dx, dy=dy)
+        mem = None if members is None else self._members(members, "tangent_into")
+        if mem is not None:                       # compact arrays: B stands for the listed members from here on
+            B = int(mem.size)
+        try:
+            dQ, dL, dU, dPx, dAx, D, flat = check_tangent(B, n, m, self.Pu.nnz, self.Ah.nnz, dQ, dL, dU, dPx, dAx, dx=dx, dy=dy)
+        except ValueError as e:
+            raise (e if mem is None else self._compact(e, self.B, B)) from None
 
         def d(a, cols, name, writable=False):
             if a is None:
                 return None
             return device_view(a, (B, cols) if flat else (B, D, cols), "<f8", writable, name) or None
-        rc = self._lib.osqp_amd_batch_tangent_dev(
-            self._h, D, d(dQ, n, "dQ"), d(dL, m, "dL"), d(dU, m, "dU"), d(dPx, self.Pu.nnz, "dPx"), d(dAx, self.Ah.nnz, "dAx"),
-            d(dx, n, "dx", True), d(dy, m, "dy", True), self._dev(active, m, "active", "<i4", True),
+        call, lead = ("osqp_amd_batch_tangent_dev", ()) if mem is None else \
+                     ("osqp_amd_batch_tangent_members_dev", (abi.iptr(mem), B))
+        rc = getattr(self._lib, call)(
+            self._h, *lead, D, d(dQ, n, "dQ"), d(dL, m, "dL"), d(dU, m, "dU"), d(dPx, self.Pu.nnz, "dPx"), d(dAx, self.Ah.nnz, "dAx"),
+            d(dx, n, "dx", True), d(dy, m, "dy", True), self._dev(active, m, "active", "<i4", True, rows=B),
             None if status_tangent is None else device_view(status_tangent, (B,), "<i4", True, "status_tangent"))
         if rc:
-            raise RuntimeError("osqp_amd_batch_tangent_dev failed (%d)%s"
-                               % (rc, ": no solve has run on the current problem" if rc == 7 else
+            raise RuntimeError("%s failed (%d)%s"
+                               % (call, rc, ": no solve has run on the current problem" if rc == 7 else
                                   _BAD_POINTER if rc == 1 else ""))
 
     def member_workspace(self, qp):

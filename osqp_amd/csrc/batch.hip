@@ -570,20 +570,36 @@ __global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k
 // (src/osqp.c:765-846): new raw vectors are scaled with the stored D, E, c; rows
 // are re-classified and a changed class requests a rebuild of K^-1
 // (update_rho_vec, src/auxil.c:100-142).
+// list (null: every member, Q, L, U are the handle's raw [B][.] arrays): one workgroup per listed member,
+// qp = list[blockIdx.x]; Q, L, U are compact, row blockIdx.x belongs to that member, and the raw row -- clamped to
+// +-OSQP_INFTY where clamp is set, the device route's -- goes into rawQ, rawL, rawU of the member first.
 __global__ void __launch_bounds__(256) k_batch_update(int n, int m, BIO io, const double *Q, const double *L,
-                                                      const double *U, double rho_tol) {
-  const long long qp = blockIdx.x;
+                                                      const double *U, double rho_tol, const int *list, double *rawQ,
+                                                      double *rawL, double *rawU, int clamp) {
+  const long long qp = list ? list[blockIdx.x] : blockIdx.x, src = blockIdx.x;
   __shared__ int changed;
   if (threadIdx.x == 0) changed = 0;
   __syncthreads();
   if (Q) {
     const double c = io.Wc[qp];
-    for (int j = threadIdx.x; j < n; j += blockDim.x) io.Wq[qp * n + j] = (Q[qp * n + j] * io.Wd[qp * n + j]) * c;
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+      const double v = Q[src * n + j];
+      if (list) rawQ[qp * n + j] = v;
+      io.Wq[qp * n + j] = (v * io.Wd[qp * n + j]) * c;
+    }
   }
   for (int i = threadIdx.x; i < m; i += blockDim.x) {
     const double e = io.We[qp * m + i];
-    if (L) io.Wl[qp * m + i] = L[qp * m + i] * e;
-    if (U) io.Wu[qp * m + i] = U[qp * m + i] * e;
+    if (L) {
+      double v = L[src * m + i];
+      if (list) { if (clamp) v = v < -OSQP_INFTY ? -OSQP_INFTY : v; rawL[qp * m + i] = v; }
+      io.Wl[qp * m + i] = v * e;
+    }
+    if (U) {
+      double v = U[src * m + i];
+      if (list) { if (clamp) v = v > OSQP_INFTY ? OSQP_INFTY : v; rawU[qp * m + i] = v; }
+      io.Wu[qp * m + i] = v * e;
+    }
     if (L || U) {
       const int t = row_class(io.Wl[qp * m + i], io.Wu[qp * m + i], rho_tol);
       if (t != io.Wt[qp * m + i]) { io.Wt[qp * m + i] = t; changed = 1; }
@@ -592,6 +608,16 @@ __global__ void __launch_bounds__(256) k_batch_update(int n, int m, BIO io, cons
   __syncthreads();
   if (threadIdx.x == 0 && changed) io.flag[qp] = BF_REBUILD;   // the refinement verdict is re-taken after the rebuild
   if (threadIdx.x == 0) io.info[qp * 8 + 5] = 0.0;      // reset_info: rho_updates (src/auxil.c:647)
+}
+
+// Rows of a member-major array into a compact one: dst[k][j] = src[list[k]][j], k < count, j < width.  One thread per
+// (k, j), j fastest, as k_batch_scatter: the reads run along a member's row and the writes are contiguous.
+__global__ void __launch_bounds__(256) k_batch_gather(double *dst, const double *src, long long width, const int *list,
+                                                      long long count) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= width * count) return;
+  const long long k = t / width, j = t - k * width;
+  dst[t] = src[(long long)list[k] * width + j];
 }
 
 // New matrix values into the raw value array of the batch: slot idx[k] (k itself when idx is null) of every member
@@ -617,13 +643,14 @@ __global__ void __launch_bounds__(256) k_batch_update_rho(long long B, BIO io, c
 // osqp_warm_start / _x / _y for every QP (osqp.c:942-1010): x = D^-1 x, z = A x with the scaled A, y = c E^-1 y.
 // One workgroup per QP; the scaled x is handed from its writers to the row sums through LDS.
 #define BW_MAX_N 1024      // largest n of either engine
-__global__ void __launch_bounds__(256) k_batch_warm_start(BPattern p, BIO io, const double *X, const double *Y) {
+// list (null: every member): one workgroup per listed member, X and Y compact (row blockIdx.x).
+__global__ void __launch_bounds__(256) k_batch_warm_start(BPattern p, BIO io, const double *X, const double *Y, const int *list) {
   __shared__ double xs[BW_MAX_N];
-  const long long qp = blockIdx.x;
+  const long long qp = list ? list[blockIdx.x] : blockIdx.x, src = blockIdx.x;
   const int n = p.n, m = p.m;
   if (X) {
     for (int j = threadIdx.x; j < n; j += 256) {
-      const double v = (1.0 / io.Wd[qp * n + j]) * X[qp * n + j];
+      const double v = (1.0 / io.Wd[qp * n + j]) * X[src * n + j];
       xs[j] = v; io.Xs[qp * n + j] = v;
     }
     __syncthreads();
@@ -636,7 +663,7 @@ __global__ void __launch_bounds__(256) k_batch_warm_start(BPattern p, BIO io, co
   }
   if (Y) {
     const double c = io.Wc[qp];
-    for (int i = threadIdx.x; i < m; i += 256) io.Ys[qp * m + i] = ((1.0 / io.We[qp * m + i]) * Y[qp * m + i]) * c;
+    for (int i = threadIdx.x; i < m; i += 256) io.Ys[qp * m + i] = ((1.0 / io.We[qp * m + i]) * Y[src * m + i]) * c;
   }
 }
 
@@ -733,6 +760,9 @@ struct osqp_amd_batch {
   bool solved = false;      // the iterates and info on the device are those of a solve of the current problem
   std::vector<char> member_solved;   // ... per member (a solve of chosen members sets its own); solved = all of them
   bool polished = false;    // ... and polish has already run on them
+  std::vector<char> member_polished;   // polish has run on the member since its last solve, by osqp_amd_batch_polish or _polish_members
+  // the _members calls: the call's list on the device, uploaded once per call, and each listed member's place in it
+  int *d_mlist = nullptr, *d_mpos = nullptr;   // [B], [B]
   // adjoint and tangent (batch_adjoint.h, batch_tangent.h): the one staging set of the derivative calls.  Each of
   // them returns with the stream synchronised, so nothing is queued on it between calls.  in, out and mat grow with
   // ncot / ndir (freed by cleanup); the rest is allocated at the first call.
@@ -751,6 +781,7 @@ struct osqp_amd_batch {
   int kkt_epoch = 0;        // b->solves when it was built: a later solve outdates it (kkt_kept)
   int kkt_NPOL = 0, kkt_NS = 0;   // (NS: the order of the per-member S^-1 on a common-K handle with the shared pieces)
   size_t kkt_count = 0;     // the members in it
+  std::vector<int> kkt_members;   // the list of the _members call that built it (empty: a whole-batch call)
   int *kkt_piv = nullptr;   // [B] 0, or -1 where k_bp_invert met a pivot of the wrong sign
   long long kkt_builds = 0; // passes of k_bp_form + k_bp_invert over the solved members since setup, polish's included
 };
@@ -761,6 +792,13 @@ static void batch_launch(osqp_amd_batch *b, int phase);
 static void mark_unsolved(osqp_amd_batch *b) {
   b->solved = false;
   std::fill(b->member_solved.begin(), b->member_solved.end(), (char)0);
+  std::fill(b->member_polished.begin(), b->member_polished.end(), (char)0);
+}
+// ... of the listed members only (the _members form of an update or a warm start); a kept KKT inversion goes with them
+static void mark_members_unsolved(osqp_amd_batch *b, const c_int *members, c_int count) {
+  b->solved = false;
+  b->kkt_valid = false;
+  for (c_int k = 0; k < count; k++) b->member_solved[(size_t)members[k]] = b->member_polished[(size_t)members[k]] = 0;
 }
 
 template <typename Tp>
@@ -927,6 +965,7 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
   if (!b) return OSQP_MEM_ALLOC_ERROR;
   b->device = (int)device; b->B = batch; b->n = n; b->m = m;
   b->member_solved.assign((size_t)batch, (char)0);
+  b->member_polished.assign((size_t)batch, (char)0);
   b->engine = (int)engine; b->NPs = streamed ? NPs : 0;
   b->nnzP = (int)P->p[n]; b->nnzA = (int)A->p[n];
   b->tile = n <= 64 ? 4 : 8;
@@ -1205,16 +1244,26 @@ static void bc_rebuild(osqp_amd_batch *b) {
 
 // Do the bounds L, U (device, raw, [B][m]; null = keep) leave every row with one class over the batch?  0: yes
 // (*moved: some row's common class changes); 1: no, stderr names the first member and row; nothing is written.
-static int bc_check_classes(osqp_amd_batch *b, const double *L, const double *U, int clamp, bool *moved, const char *what) {
+// members (with d_list, the same list on the device; null: every member): L, U are compact [count][m], and a listed
+// member's rows must keep the class the handle holds, which the unlisted members keep.
+static int bc_check_classes(osqp_amd_batch *b, const double *L, const double *U, int clamp, bool *moved, const char *what,
+                            const c_int *members = nullptr, size_t count = 0, const int *d_list = nullptr) {
   const size_t B = (size_t)b->B;
   std::vector<int> h(B + 1);
   BCHK(hipMemsetAsync(b->ct.bad, 0, (B + 1) * sizeof(int), b->stream));
-  hipLaunchKernelGGL(k_bc_classes, dim3((unsigned)B), dim3(256), 0, b->stream, b->m, b->B, b->io, L, U, clamp,
-                     (double)RHO_TOL, b->ct.bad);
+  hipLaunchKernelGGL(k_bc_classes, dim3((unsigned)(members ? count : B)), dim3(256), 0, b->stream, b->m, b->B, b->io, L, U,
+                     clamp, (double)RHO_TOL, b->ct.bad, d_list);
   BCHK(hipGetLastError());
   BCHK(hipMemcpyAsync(h.data(), b->ct.bad, (B + 1) * sizeof(int), hipMemcpyDeviceToHost, b->stream));
   BCHK(hipStreamSynchronize(b->stream));
-  for (size_t q = 0; q < B; q++)
+  for (size_t k = 0; members && k < count; k++)
+    if (h[k] >= 0) {
+      fprintf(stderr, "osqp_amd batch: %s: row %d of member %zu would get another class (loose / inequality / equality) "
+                      "than the handle holds for it -- the common-K engine needs one class per row over the batch\n",
+              what, h[k], (size_t)members[k]);
+      return 1;
+    }
+  for (size_t q = 0; !members && q < B; q++)
     if (h[q] >= 0) {
       fprintf(stderr, "osqp_amd batch: %s: row %d of member %zu has another class (loose / inequality / equality) than in "
                       "member 0 -- the common-K engine needs one class per row over the batch\n", what, h[q], q);
@@ -1245,7 +1294,8 @@ static int bc_setup_launch(osqp_amd_batch *b, const c_float *Q) {
   const int crc = bc_check_classes(b, b->dL, b->dU, 0, nullptr, "setup");
   if (crc) return crc == 1 ? OSQP_DATA_VALIDATION_ERROR : OSQP_LINSYS_SOLVER_INIT_ERROR;
   hipLaunchKernelGGL(k_batch_update, dim3((unsigned)B), dim3(256), 0, b->stream, b->n, b->m, b->io,
-                     (const double *)b->dQ, (const double *)b->dL, (const double *)b->dU, (double)RHO_TOL);
+                     (const double *)b->dQ, (const double *)b->dL, (const double *)b->dU, (double)RHO_TOL, (const int *)nullptr,
+                     (double *)nullptr, (double *)nullptr, (double *)nullptr, 0);
   b->bc_rho = fmin(fmax(b->st.rho, 1e-6), 1e6);
   bc_rebuild(b);
   return 0;
@@ -1454,7 +1504,8 @@ extern "C" c_int osqp_amd_batch_update(osqp_amd_batch *b, const c_float *Q, cons
   if (L) BCHK(hipMemcpyAsync(b->dL, L, B * b->m * sizeof(double), hipMemcpyHostToDevice, b->stream));
   if (U) BCHK(hipMemcpyAsync(b->dU, U, B * b->m * sizeof(double), hipMemcpyHostToDevice, b->stream));
   hipLaunchKernelGGL(k_batch_update, dim3((unsigned)B), dim3(256), 0, b->stream, b->n, b->m, b->io,
-                     Q ? b->dQ : nullptr, L ? b->dL : nullptr, U ? b->dU : nullptr, (double)RHO_TOL);
+                     Q ? b->dQ : nullptr, L ? b->dL : nullptr, U ? b->dU : nullptr, (double)RHO_TOL, (const int *)nullptr,
+                     (double *)nullptr, (double *)nullptr, (double *)nullptr, 0);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   return 0;
@@ -1577,10 +1628,10 @@ extern "C" c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, 
   if (ny) BCHK(hipMemcpyAsync(b->d_vals + nx, Y, ny * sizeof(double), hipMemcpyHostToDevice, b->stream));
   if (b->engine == OSQP_AMD_BATCH_COMMON)
     hipLaunchKernelGGL(k_bc_warm_start, dim3((unsigned)B), dim3(256), 0, b->stream, b->pat, b->io,
-                       X ? b->d_vals : (const double *)nullptr, Y ? b->d_vals + nx : (const double *)nullptr);
+                       X ? b->d_vals : (const double *)nullptr, Y ? b->d_vals + nx : (const double *)nullptr, (const int *)nullptr);
   else
     hipLaunchKernelGGL(k_batch_warm_start, dim3((unsigned)B), dim3(256), 0, b->stream, b->pat, b->io,
-                       X ? b->d_vals : (const double *)nullptr, Y ? b->d_vals + nx : (const double *)nullptr);
+                       X ? b->d_vals : (const double *)nullptr, Y ? b->d_vals + nx : (const double *)nullptr, (const int *)nullptr);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   return 0;
@@ -1592,8 +1643,8 @@ extern "C" c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, 
 static c_int batch_solve_run(osqp_amd_batch *b, const c_int *members, long long count) {
   BCHK(hipSetDevice(b->device));
   b->solved = b->polished = false;
-  if (!members) std::fill(b->member_solved.begin(), b->member_solved.end(), (char)0);
-  else for (long long k = 0; k < count; k++) b->member_solved[(size_t)members[k]] = 0;
+  if (!members) mark_unsolved(b);
+  else for (long long k = 0; k < count; k++) b->member_solved[(size_t)members[k]] = b->member_polished[(size_t)members[k]] = 0;
   b->io.order = (b->lpt && b->solves > 0) ? b->d_order : nullptr;   // first solve: no history, index order
   if (b->engine == OSQP_AMD_BATCH_COMMON) { if (const int rc = bc_solve(b, members, count)) return rc; }
   else if (b->engine != OSQP_AMD_BATCH_STREAMED) batch_launch(b, 1);
@@ -1675,16 +1726,24 @@ static int bp_reserve_K(osqp_amd_batch *b, size_t bytes) {
 // order NPOL; NPOL stays the length of the kernels' LDS vectors [x; nu], and lds includes BlockK's scratch.
 struct BPlan { size_t count = 0, chunk = 0, lds = 0, ilds = 0; int NPOL = 0, NS = 0; };
 static BlockK bk_solver(const osqp_amd_batch *b, int NS) { return BlockK{b->bk.H, b->bk.Wt, b->NPs, NS}; }
-static c_int bp_plan(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_of)(int, int, int), BPlan *out) {
+// sel (null: every member): the members the call is about, ascending, already on the device in b->d_mlist
+// (members_upload); k_bp_active runs over them alone, and NPOL and NS come from their largest mred.
+static c_int bp_plan(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_of)(int, int, int), BPlan *out,
+                     const std::vector<int> *sel = nullptr) {
   const size_t B = (size_t)b->B;
   const int n = b->n, m = b->m;
-  hipLaunchKernelGGL(k_bp_active, dim3((unsigned)B), dim3(256), 0, b->stream, m, b->io, pl);
+  hipLaunchKernelGGL(k_bp_active, dim3((unsigned)(sel ? sel->size() : B)), dim3(256), 0, b->stream, m, b->io, pl,
+                     sel ? (const int *)b->d_mlist : (const int *)nullptr);
   BCHK(hipGetLastError());
   std::vector<int> h(B), list;
   BCHK(hipMemcpyAsync(h.data(), pl.mred, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
   BCHK(hipStreamSynchronize(b->stream));
   int mmax = 0;
-  for (size_t q = 0; q < B; q++) if (h[q] >= 0) { list.push_back((int)q); mmax = std::max(mmax, h[q]); }
+  for (size_t q = 0; !sel && q < B; q++) if (h[q] >= 0) { list.push_back((int)q); mmax = std::max(mmax, h[q]); }
+  for (size_t k = 0; sel && k < sel->size(); k++) {
+    const int q = (*sel)[k];
+    if (h[(size_t)q] >= 0) { list.push_back(q); mmax = std::max(mmax, h[(size_t)q]); }
+  }
   *out = BPlan{};
   if (list.empty()) return 0;
   const int NPOL = (n + mmax + 31) & ~31;
@@ -1737,7 +1796,34 @@ static int bp_run_chunks(osqp_amd_batch *b, const BPol &pl, const BPlan &pn, con
 // it has passed `b->solved`, which only osqp_amd_batch_solve sets, together with b->solves; every update and warm
 // start that withdraws the permission to call clears it until the next solve.  So the epoch outdates what a solve,
 // or an update followed by a solve, has overtaken.
-static bool kkt_kept(const osqp_amd_batch *b) { return b->kkt_valid && b->solved && b->kkt_epoch == b->solves; }
+// An inversion built by a _members call is kept with its list (kkt_members) and belongs to a later _members call with
+// the identical list, whose members have all passed their solved flags; a whole-batch call reuses only a whole-batch
+// build.  kkt_kept: something is kept and still belongs to the handle's point (osqp_amd_batch_kkt_info);
+// kkt_kept_for: ... and to the asking call, whose list is sel (null: a whole-batch call).
+static bool kkt_kept(const osqp_amd_batch *b) {
+  if (!b->kkt_valid || b->kkt_epoch != b->solves) return false;
+  if (b->kkt_members.empty()) return b->solved;
+  for (int q : b->kkt_members) if (!b->member_solved[(size_t)q]) return false;
+  return true;
+}
+static bool kkt_kept_for(const osqp_amd_batch *b, const std::vector<int> *sel) {
+  return kkt_kept(b) && (sel ? b->kkt_members == *sel : b->kkt_members.empty());
+}
+// The list of a _members call on the device: d_mlist[k] = list[k] and, with pos, d_mpos[list[k]] = k.  One upload per
+// call; the wait is for the host vectors.
+static int members_upload(osqp_amd_batch *b, const int *list, size_t count, bool pos) {
+  const size_t B = (size_t)b->B;
+  if (balloc_once(b, &b->d_mlist, B) || balloc_once(b, &b->d_mpos, B)) { (void)hipGetLastError(); return -102; }
+  BCHK(hipMemcpyAsync(b->d_mlist, list, count * sizeof(int), hipMemcpyHostToDevice, b->stream));
+  std::vector<int> at;
+  if (pos) {
+    at.assign(B, 0);
+    for (size_t k = 0; k < count; k++) at[(size_t)list[k]] = (int)k;
+    BCHK(hipMemcpyAsync(b->d_mpos, at.data(), B * sizeof(int), hipMemcpyHostToDevice, b->stream));
+  }
+  BCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
 
 // What adjoint, adjoint_multi and tangent share around their own kernel fn, which third(plan, members, their list)
 // launches with pn.lds bytes of LDS; pl.stat is the call's array of pivot verdicts.  While an inversion is kept,
@@ -1745,10 +1831,11 @@ static bool kkt_kept(const osqp_amd_batch *b) { return b->kkt_valid && b->solved
 // plan is one chunk (and OSQP_AMD_BATCH_KKT_CACHE is not 0) the verdicts are saved after k_bp_invert and what was
 // built is kept.  Either way fn sees the same maps, list, inverses and verdicts: the same bits.  Nothing is waited for.
 template <class Third>
-static c_int bd_run(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_of)(int, int, int), const void *fn, Third third) {
+static c_int bd_run(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_of)(int, int, int), const void *fn, Third third,
+                    const std::vector<int> *sel = nullptr) {
   const size_t B = (size_t)b->B;
   BPlan pn;
-  if (kkt_kept(b)) {
+  if (kkt_kept_for(b, sel)) {
     pn.count = pn.chunk = b->kkt_count; pn.NPOL = b->kkt_NPOL; pn.NS = b->kkt_NS;
     pn.lds = lds_of(b->n, b->m, pn.NPOL) + (b->bk.H ? bk_scratch_bytes(b->NPs, pn.NS) : 0);
     if (pn.lds > 160 * 1024) {
@@ -1763,7 +1850,7 @@ static c_int bd_run(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_
     return 0;
   }
   b->kkt_valid = false;                          // k_bp_active rewrites the maps
-  const c_int rc = bp_plan(b, pl, what, lds_of, &pn);
+  const c_int rc = bp_plan(b, pl, what, lds_of, &pn, sel);
   if (rc) return rc;
   const bool keep = b->kkt_cache && pn.count && pn.count <= pn.chunk;
   if (keep && balloc_once(b, &b->kkt_piv, B)) { (void)hipGetLastError(); return OSQP_MEM_ALLOC_ERROR; }
@@ -1771,7 +1858,26 @@ static c_int bd_run(osqp_amd_batch *b, BPol &pl, const char *what, size_t (*lds_
         if (keep) (void)hipMemcpyAsync(b->kkt_piv, pl.stat, B * sizeof(int), hipMemcpyDeviceToDevice, b->stream);
         third(pn, cnt, lp);
       })) return -102;
-  if (keep) { b->kkt_valid = true; b->kkt_epoch = b->solves; b->kkt_NPOL = pn.NPOL; b->kkt_NS = pn.NS; b->kkt_count = pn.count; }
+  if (keep) {
+    b->kkt_valid = true; b->kkt_epoch = b->solves; b->kkt_NPOL = pn.NPOL; b->kkt_NS = pn.NS; b->kkt_count = pn.count;
+    if (sel) b->kkt_members = *sel; else b->kkt_members.clear();
+  }
+  return 0;
+}
+
+// polish's plan and chunks for every member (sel null) or the members of sel (bp_plan), and the wait for them
+static c_int bp_polish_run(osqp_amd_batch *b, const std::vector<int> *sel) {
+  BPol &pl = b->pol;
+  BPlan pn;
+  b->kkt_valid = false;   // polish overwrites pol.K and may move the point: it neither reads nor leaves a kept inversion
+  const c_int rc = bp_plan(b, pl, "polish", bp_lds_of, &pn, sel);
+  if (rc) return rc;
+  const bool blk = b->bk.H != nullptr;
+  if (bp_run_chunks(b, pl, pn, blk ? KFN(k_bp_polish<BlockK, BlockK>) : KFN(k_bp_polish<FullK>), [&](unsigned cnt, const int *lp) {
+        if (blk) hipLaunchKernelGGL((k_bp_polish<BlockK, BlockK>), dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->st, b->io, pl, pn.NPOL, b->pol_refine, lp, bk_solver(b, pn.NS));
+        else hipLaunchKernelGGL(k_bp_polish<FullK>, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->st, b->io, pl, pn.NPOL, b->pol_refine, lp);
+      })) return -102;
+  BCHK(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -1784,17 +1890,9 @@ extern "C" c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish) 
   BPol &pl = b->pol;
   if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
   if (!b->polished) {       // (a second call without a solve in between finds the work done and reports it again)
-    BPlan pn;
-    b->kkt_valid = false;   // polish overwrites pol.K and may move the point: it neither reads nor leaves a kept inversion
-    const c_int rc = bp_plan(b, pl, "polish", bp_lds_of, &pn);
-    if (rc) return rc;
-    const bool blk = b->bk.H != nullptr;
-    if (bp_run_chunks(b, pl, pn, blk ? KFN(k_bp_polish<BlockK, BlockK>) : KFN(k_bp_polish<FullK>), [&](unsigned cnt, const int *lp) {
-          if (blk) hipLaunchKernelGGL((k_bp_polish<BlockK, BlockK>), dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->st, b->io, pl, pn.NPOL, b->pol_refine, lp, bk_solver(b, pn.NS));
-          else hipLaunchKernelGGL(k_bp_polish<FullK>, dim3(cnt), dim3(BP_NT), pn.lds, b->stream, b->pat, b->st, b->io, pl, pn.NPOL, b->pol_refine, lp);
-        })) return -102;
-    BCHK(hipStreamSynchronize(b->stream));
+    if (const c_int rc = bp_polish_run(b, nullptr)) return rc;
     b->polished = true;
+    std::fill(b->member_polished.begin(), b->member_polished.end(), (char)1);
   }
   if (status_polish) {
     std::vector<int> h(B);
@@ -2026,7 +2124,8 @@ static int bd_reserve(double **p, size_t *cap, size_t cnt) {
 // stays polish's.  ins: the inputs (null = none); *slot is where the kernel reads each -- in place on the device
 // route, from the staging (vectors in `in`, matrices in `mat`) on the host route.
 struct BDIn { const c_float *src; size_t cnt; const double **slot; bool mat; };
-static c_int bd_stage(osqp_amd_batch *b, BPol *pl, bool dev, std::initializer_list<BDIn> ins, size_t nout, size_t nmat) {
+// R: the rows of the call's arrays -- B, or the listed members of a _members call -- which size what is zeroed.
+static c_int bd_stage(osqp_amd_batch *b, BPol *pl, bool dev, std::initializer_list<BDIn> ins, size_t nout, size_t nmat, size_t R) {
   const size_t B = (size_t)b->B, m = (size_t)b->m;
   auto &sg = b->bd;
   if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
@@ -2052,8 +2151,8 @@ static c_int bd_stage(osqp_amd_batch *b, BPol *pl, bool dev, std::initializer_li
     dst += t.cnt;
   }
   BCHK(hipMemsetAsync(sg.out, 0, nout * sizeof(double), b->stream));
-  BCHK(hipMemsetAsync(sg.act, 0, std::max((size_t)1, B * m) * sizeof(int), b->stream));
-  BCHK(hipMemsetAsync(sg.stat, 0, B * sizeof(int), b->stream));
+  BCHK(hipMemsetAsync(sg.act, 0, std::max((size_t)1, R * m) * sizeof(int), b->stream));
+  BCHK(hipMemsetAsync(sg.stat, 0, R * sizeof(int), b->stream));
   if (nmat) BCHK(hipMemsetAsync(sg.mat, 0, nmat * sizeof(double), b->stream));
   return 0;
 }
@@ -2092,22 +2191,35 @@ static c_int dev_ptrs_check(const osqp_amd_batch *b, std::initializer_list<const
 // matrix and inversion on polish's buffers, in the same chunks, one inversion for the ncot cotangents of a member;
 // nothing of the solve state is written.  What the four entry points below share; dev: every array is on the device,
 // dX and dY are read in place.
+// the precondition of polish, adjoint and tangent: every member (members null), or every listed one, is solved on the
+// current problem
+static bool members_solved(const osqp_amd_batch *b, const c_int *members, c_int count) {
+  if (!members) return b->solved;
+  for (c_int k = 0; k < count; k++) if (!b->member_solved[(size_t)members[k]]) return false;
+  return true;
+}
+// members (null: every member; a list the caller has checked): the _members form -- every array is compact, [count][.],
+// the listed members must be solved on the current problem, and the staging is sized by count.
 static c_int adjoint_call(osqp_amd_batch *b, bool dev, const char *what, c_int ncot, const c_float *dX, const c_float *dY,
-                          c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx, void *active, void *status) {
-  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+                          c_float *dQ, c_float *dL, c_float *dU, c_float *dPx, c_float *dAx, void *active, void *status,
+                          const c_int *members = nullptr, c_int count = 0) {
+  if (!b || !members_solved(b, members, count)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (ncot < 1 || ncot > 65535) return OSQP_DATA_VALIDATION_ERROR;
   if (!dX || !dQ || (b->m > 0 && (!dL || !dU))) return OSQP_DATA_VALIDATION_ERROR;
   BCHK(hipSetDevice(b->device));
   if (dev && dev_ptrs_check(b, {dX, dY, dQ, dL, dU, dPx, dAx, active, status})) return OSQP_DATA_VALIDATION_ERROR;
-  const size_t B = (size_t)b->B, D = (size_t)ncot;
+  const size_t B = members ? (size_t)count : (size_t)b->B, D = (size_t)ncot;   // (B: the rows of the call's arrays)
   const size_t n = (size_t)b->n, m = (size_t)b->m, nnzP = (size_t)b->nnzP, nnzA = (size_t)b->nnzA;
   const size_t nP = dPx ? B * D * nnzP : 0, nA = dAx ? B * D * nnzA : 0;   // only what the call asked for
   if (!m) dY = nullptr;
+  const std::vector<int> sel(members, members + (members ? count : 0));
+  if (members && members_upload(b, sel.data(), sel.size(), true)) return OSQP_MEM_ALLOC_ERROR;
   BPol pl;
   BAdj ad{};
   ad.ncot = (int)ncot;
   if (const c_int rc = bd_stage(b, &pl, dev, {{dX, B * D * n, &ad.gx, false}, {dY, B * D * m, &ad.gy, false}},
-                                B * D * (n + 2 * m), nP + nA)) return rc;
+                                B * D * (n + 2 * m), nP + nA, B)) return rc;
+  if (members) pl.pos = b->d_mpos;
   ad.dQ = b->bd.out; ad.dL = ad.dQ + B * D * n; ad.dU = ad.dL + B * D * m;
   ad.dPx = nP ? b->bd.mat : nullptr; ad.dAx = nA ? b->bd.mat + nP : nullptr;
   ad.active = b->bd.act; ad.stat = b->bd.stat;
@@ -2115,7 +2227,7 @@ static c_int adjoint_call(osqp_amd_batch *b, bool dev, const char *what, c_int n
   if (const c_int rc = bd_run(b, pl, what, bd_lds_of, blk ? KFN(k_ba_adjoint<BlockK, BlockK>) : KFN(k_ba_adjoint<FullK>), [&](const BPlan &pn, unsigned cnt, const int *lp) {
         if (blk) hipLaunchKernelGGL((k_ba_adjoint<BlockK, BlockK>), dim3(cnt, (unsigned)ncot), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp, bk_solver(b, pn.NS));
         else hipLaunchKernelGGL(k_ba_adjoint<FullK>, dim3(cnt, (unsigned)ncot), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, ad, pn.NPOL, b->pol_refine, lp);
-      })) return rc;
+      }, members ? &sel : nullptr)) return rc;
   return bd_deliver(b, dev, {{dQ, ad.dQ, B * D * n}, {dL, ad.dL, B * D * m}, {dU, ad.dU, B * D * m}, {dPx, ad.dPx, nP}, {dAx, ad.dAx, nA}},
                     {{active, ad.active, B * m}, {status, ad.stat, B}});
 }
@@ -2149,29 +2261,33 @@ extern "C" c_int osqp_amd_batch_adjoint_multi_dev(osqp_amd_batch *b, c_int ncot,
 // directions of a member; nothing of the solve state is written.  dev: every array is on the device, the tangents
 // are read in place.
 static c_int tangent_call(osqp_amd_batch *b, bool dev, c_int ndir, const c_float *dQ, const c_float *dL, const c_float *dU,
-                          const c_float *dPx, const c_float *dAx, c_float *dX, c_float *dY, void *active, void *status) {
-  if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+                          const c_float *dPx, const c_float *dAx, c_float *dX, c_float *dY, void *active, void *status,
+                          const c_int *members = nullptr, c_int count = 0) {
+  if (!b || !members_solved(b, members, count)) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   if (ndir < 1 || ndir > 65535 || !dX) return OSQP_DATA_VALIDATION_ERROR;
   BCHK(hipSetDevice(b->device));
   if (dev && dev_ptrs_check(b, {dQ, dL, dU, dPx, dAx, dX, dY, active, status})) return OSQP_DATA_VALIDATION_ERROR;
-  const size_t B = (size_t)b->B, D = (size_t)ndir;
+  const size_t B = members ? (size_t)count : (size_t)b->B, D = (size_t)ndir;   // (B: the rows of the call's arrays)
   const size_t n = (size_t)b->n, m = (size_t)b->m, nnzP = (size_t)b->nnzP, nnzA = (size_t)b->nnzA;
   if (!m) dL = dU = nullptr;
   if (!nnzP) dPx = nullptr;
   if (!nnzA) dAx = nullptr;
+  const std::vector<int> sel(members, members + (members ? count : 0));
+  if (members && members_upload(b, sel.data(), sel.size(), true)) return OSQP_MEM_ALLOC_ERROR;
   BPol pl;
   BTan tg{};
   tg.ndir = (int)ndir;
   if (const c_int rc = bd_stage(b, &pl, dev, {{dQ, B * D * n, &tg.dQ, false}, {dL, B * D * m, &tg.dL, false}, {dU, B * D * m, &tg.dU, false},
                                               {dPx, B * D * nnzP, &tg.dPx, true}, {dAx, B * D * nnzA, &tg.dAx, true}},
-                                B * D * (n + m), 0)) return rc;
+                                B * D * (n + m), 0, B)) return rc;
+  if (members) pl.pos = b->d_mpos;
   tg.dX = b->bd.out; tg.dY = tg.dX + B * D * n;
   tg.active = b->bd.act; tg.stat = b->bd.stat;
   const bool blk = b->bk.H != nullptr;
   if (const c_int rc = bd_run(b, pl, "tangent", bd_lds_of, blk ? KFN(k_bt_tangent<BlockK, BlockK>) : KFN(k_bt_tangent<FullK>), [&](const BPlan &pn, unsigned cnt, const int *lp) {
         if (blk) hipLaunchKernelGGL((k_bt_tangent<BlockK, BlockK>), dim3(cnt, (unsigned)ndir), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, tg, pn.NPOL, b->pol_refine, lp, bk_solver(b, pn.NS));
         else hipLaunchKernelGGL(k_bt_tangent<FullK>, dim3(cnt, (unsigned)ndir), dim3(BP_NT), pn.lds, b->stream, b->pat, b->io, pl, tg, pn.NPOL, b->pol_refine, lp);
-      })) return rc;
+      }, members ? &sel : nullptr)) return rc;
   return bd_deliver(b, dev, {{dX, tg.dX, B * D * n}, {dY, tg.dY, B * D * m}}, {{active, tg.active, B * m}, {status, tg.stat, B}});
 }
 
@@ -2272,3 +2388,4 @@ extern "C" c_int osqp_amd_batch_device_ptrs(osqp_amd_batch *b, void **X, void **
 }
 
 #include "batch_devio.h"
+#include "batch_members.h"

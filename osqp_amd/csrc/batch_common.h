@@ -86,25 +86,28 @@ __global__ void __launch_bounds__(256) k_bc_rescale(int n, int m, BIO io) {
 // Would the bounds L, U (raw, [B][m]; null = the member's scaled bound as stored) leave every row with one class over
 // the batch?  bad[qp] = the first row whose class differs from member 0's (-1: none); bad[B] = 1 when the class of
 // some row of member 0 differs from the stored one (K is then due).  Writes nothing of the workspace.
+// list (null: every member): one workgroup per listed member, L and U compact (row blockIdx.x); the class to agree
+// with is the one the handle holds (io.Wt of member 0: the unlisted members keep it), bad[blockIdx.x] the verdict, and
+// bad[B] is not written.
 __global__ void __launch_bounds__(256) k_bc_classes(int m, long long B, BIO io, const double *L, const double *U,
-                                                    int clamp, double rho_tol, int *bad) {
+                                                    int clamp, double rho_tol, int *bad, const int *list) {
   __shared__ int first;
-  const long long qp = blockIdx.x;
+  const long long qp = list ? list[blockIdx.x] : blockIdx.x, src = blockIdx.x;
   if (threadIdx.x == 0) first = m;
   __syncthreads();
   for (int i = threadIdx.x; i < m; i += 256) {
     const double e = io.We[i];
     double lb, ub, l0, u0;
-    if (L) { lb = L[qp * m + i]; l0 = L[i]; if (clamp) { lb = lb < -OSQP_INFTY ? -OSQP_INFTY : lb; l0 = l0 < -OSQP_INFTY ? -OSQP_INFTY : l0; } lb *= e; l0 *= e; }
+    if (L) { lb = L[src * m + i]; l0 = L[i]; if (clamp) { lb = lb < -OSQP_INFTY ? -OSQP_INFTY : lb; l0 = l0 < -OSQP_INFTY ? -OSQP_INFTY : l0; } lb *= e; l0 *= e; }
     else { lb = io.Wl[qp * m + i]; l0 = io.Wl[i]; }
-    if (U) { ub = U[qp * m + i]; u0 = U[i]; if (clamp) { ub = ub > OSQP_INFTY ? OSQP_INFTY : ub; u0 = u0 > OSQP_INFTY ? OSQP_INFTY : u0; } ub *= e; u0 *= e; }
+    if (U) { ub = U[src * m + i]; u0 = U[i]; if (clamp) { ub = ub > OSQP_INFTY ? OSQP_INFTY : ub; u0 = u0 > OSQP_INFTY ? OSQP_INFTY : u0; } ub *= e; u0 *= e; }
     else { ub = io.Wu[qp * m + i]; u0 = io.Wu[i]; }
-    const int t0 = row_class(l0, u0, rho_tol);
+    const int t0 = list ? io.Wt[i] : row_class(l0, u0, rho_tol);
     if (row_class(lb, ub, rho_tol) != t0) atomicMin(&first, i);
-    if (qp == 0 && t0 != io.Wt[i]) bad[B] = 1;
+    if (!list && qp == 0 && t0 != io.Wt[i]) bad[B] = 1;
   }
   __syncthreads();
-  if (threadIdx.x == 0) bad[qp] = first < m ? first : -1;
+  if (threadIdx.x == 0) bad[src] = first < m ? first : -1;
 }
 
 // the common K is due: k_bs_form reads member 0's flag and rho
@@ -180,13 +183,13 @@ __global__ void __launch_bounds__(256) k_bc_pivot2(BCPair a, int n, int NP, int 
 }
 
 // k_batch_warm_start with the one slab of scaled values
-__global__ void __launch_bounds__(256) k_bc_warm_start(BPattern p, BIO io, const double *X, const double *Y) {
+__global__ void __launch_bounds__(256) k_bc_warm_start(BPattern p, BIO io, const double *X, const double *Y, const int *list) {
   __shared__ double xs[BW_MAX_N];
-  const long long qp = blockIdx.x;
+  const long long qp = list ? list[blockIdx.x] : blockIdx.x, src = blockIdx.x;
   const int n = p.n, m = p.m;
   if (X) {
     for (int j = threadIdx.x; j < n; j += 256) {
-      const double v = (1.0 / io.Wd[qp * n + j]) * X[qp * n + j];
+      const double v = (1.0 / io.Wd[qp * n + j]) * X[src * n + j];
       xs[j] = v; io.Xs[qp * n + j] = v;
     }
     __syncthreads();
@@ -199,7 +202,7 @@ __global__ void __launch_bounds__(256) k_bc_warm_start(BPattern p, BIO io, const
   }
   if (Y) {
     const double c = io.Wc[qp];
-    for (int i = threadIdx.x; i < m; i += 256) io.Ys[qp * m + i] = ((1.0 / io.We[qp * m + i]) * Y[qp * m + i]) * c;
+    for (int i = threadIdx.x; i < m; i += 256) io.Ys[qp * m + i] = ((1.0 / io.We[qp * m + i]) * Y[src * m + i]) * c;
   }
 }
 

@@ -97,7 +97,8 @@ extern "C" c_int osqp_amd_batch_update_dev(osqp_amd_batch *b, const c_float *Q, 
   if ((L || U) && cnt)
     hipLaunchKernelGGL(k_batch_stage_bounds, dim3(bd_blocks(cnt)), dim3(BD_NT), 0, b->stream, cnt, L, U, b->dL, b->dU);
   hipLaunchKernelGGL(k_batch_update, dim3((unsigned)B), dim3(256), 0, b->stream, b->n, b->m, b->io,
-                     Q ? b->dQ : nullptr, L ? b->dL : nullptr, U ? b->dU : nullptr, (double)RHO_TOL);
+                     Q ? b->dQ : nullptr, L ? b->dL : nullptr, U ? b->dU : nullptr, (double)RHO_TOL, (const int *)nullptr,
+                     (double *)nullptr, (double *)nullptr, (double *)nullptr, 0);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   return 0;
@@ -153,9 +154,9 @@ extern "C" c_int osqp_amd_batch_warm_start_dev(osqp_amd_batch *b, const c_float 
   if (!X && !Y) return 0;
   mark_unsolved(b);
   if (b->engine == OSQP_AMD_BATCH_COMMON)
-    hipLaunchKernelGGL(k_bc_warm_start, dim3((unsigned)b->B), dim3(256), 0, b->stream, b->pat, b->io, X, Y);
+    hipLaunchKernelGGL(k_bc_warm_start, dim3((unsigned)b->B), dim3(256), 0, b->stream, b->pat, b->io, X, Y, (const int *)nullptr);
   else
-    hipLaunchKernelGGL(k_batch_warm_start, dim3((unsigned)b->B), dim3(256), 0, b->stream, b->pat, b->io, X, Y);
+    hipLaunchKernelGGL(k_batch_warm_start, dim3((unsigned)b->B), dim3(256), 0, b->stream, b->pat, b->io, X, Y, (const int *)nullptr);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   return 0;

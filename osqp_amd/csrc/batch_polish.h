@@ -39,14 +39,16 @@ struct BPol {              // polish workspace of a handle (device pointers)
   int *nlow;               // [B] how many of them are active at the lower bound
   int *stat;               // [B] status_polish: 1 accepted, -1 tried and rejected, 0 not tried
   double *K;               // [members of a chunk][NPOL * NPOL] the KKT matrix, then its inverse (BlockK: [NS * NS], S and S^-1)
+  const int *pos;          // [B] a member's row in the compact arrays of a _members call (null: its own index)
 };
 
 // Active rows from the stored scaled iterates and bounds (polish.c:19-100): low z - l < -y, upp u - z < y.
 // (Both cannot hold for l <= u; a row that passed the low test is not tested again.)
-__global__ void __launch_bounds__(256) k_bp_active(int m, BIO io, BPol pl) {
+// list (null: every member): one workgroup per listed member; of the others nothing is written.
+__global__ void __launch_bounds__(256) k_bp_active(int m, BIO io, BPol pl, const int *list) {
   __shared__ int sc[256];
   __shared__ int base;
-  const long long qp = blockIdx.x;
+  const long long qp = list ? list[blockIdx.x] : blockIdx.x;
   const int tid = threadIdx.x;
   if (tid == 0) pl.stat[qp] = 0;
   if ((int)io.info[qp * 8 + 1] != OSQP_SOLVED) {
@@ -192,7 +194,7 @@ struct FullK {
 // carve-up of the LDS (bd_lds_bytes).  The member's slab_view stays a local of the kernel: held in here it cost the
 // two kernels some 25 VGPRs.
 struct BDView {
-  long long qp, slot;      // the member; its slice blockIdx.y of the call's [B][slices][.] arrays
+  long long qp, row, slot; // the member; its row of the call's arrays (pl.pos); its slice blockIdx.y of their [.][slices][.]
   int n, m, nlow, N;       // nlow of the N - n active rows sit at their lower bound
   double cs, cinv;         // the member's cost scaling c and 1 / c
   const double *Kinv;      // the solver's inverse of this member, slot blockIdx.x of the chunk (KS::inverse)
@@ -217,13 +219,14 @@ __device__ __forceinline__ bool bd_open(const BPattern &p, const BIO &io, const 
                                         const int *list, double *lds, const KS &ks, BDView &v) {
   const long long qp = list[blockIdx.x];
   const int tid = threadIdx.x;
+  const long long row = pl.pos ? pl.pos[qp] : qp;
   if (pl.stat[qp] == -1) {
-    if (blockIdx.y == 0 && tid == 0) stat[qp] = -1;
+    if (blockIdx.y == 0 && tid == 0) stat[row] = -1;
     return false;
   }
   const int n = p.n, m = p.m;
   const int mred = pl.mred[qp];
-  v.qp = qp; v.slot = qp * slices + blockIdx.y;
+  v.qp = qp; v.row = row; v.slot = row * slices + blockIdx.y;
   v.n = n; v.m = m; v.nlow = pl.nlow[qp]; v.N = n + mred;
   v.Kinv = ks.inverse(pl.K, NPOL);
   v.sol = lds; v.res = v.sol + NPOL; v.cor = v.res + NPOL; v.g = v.cor + NPOL;
@@ -243,9 +246,9 @@ __device__ __forceinline__ void bd_close(const BDView &v, int *active, int *stat
   if (blockIdx.y != 0) return;
   for (int i = threadIdx.x; i < v.m; i += BP_NT) {
     const int a = v.map[i];
-    active[v.qp * v.m + i] = a < 0 ? 0 : (a < v.nlow ? -1 : 1);
+    active[v.row * v.m + i] = a < 0 ? 0 : (a < v.nlow ? -1 : 1);
   }
-  if (threadIdx.x == 0) stat[v.qp] = 1;
+  if (threadIdx.x == 0) stat[v.row] = 1;
 }
 
 // LDS of k_bp_polish: three vectors of NPOL (solution, residual, correction), q, D, five m-vectors (l, u, E, z, y),
