@@ -25,6 +25,11 @@ D = E = 1, c = 1 for unscaled data), unscaled afterwards: with T = diag(D, E_act
     M~ = T [c P, Ar'; Ar, 0] T,   so   M [x; nu] = [g1; g2]   <=>   [x; c nu] = T M~^-1 T [c g1; g2].
 Polish also projects (z, y) on the normal cone in the scaled space, as polish.c does.
 
+The wrong-pivot verdict: the case "wrongpivot" (VERDICT_CASES, not in CASES) has one member whose KKT inversion must
+meet the pivot 0.0 on the device -- see _build -- and `gj_verdict`, a float64 model of the device's Gauss-Jordan sweep
+on the matrix `device_kkt` forms, says which pivot that is (tests/test_planted_verdict_host.py,
+tests/test_gpu_batch_pivot_verdict.py).
+
 Bar (one function, `bar`): err <= 10 err_model + 1e-14 max|truth| per output array; the factor and the floor are
 the project's (check_member_kinv, Engine.check) and cover another summation order.  Two-sided where asked
 (k in {0, 1}): also err >= err_model / 10 -- there the error is the deterministic regularisation error."""
@@ -42,9 +47,11 @@ NDIR = 2
 
 
 # ------------------------------------------------------------------------------------------------ generator
-def _p_pattern(rng, n, empty=False, dense_row=None, no_p=()):
+def _p_pattern(rng, n, empty=False, dense_row=None, no_p=(), pair=None):
     """triu(P), CSC, sorted.  dense_row: that row of the full P couples to every variable that has a P row at all.
-    no_p: variables whose row and column of P are empty, the diagonal included (P stays positive semidefinite)."""
+    no_p: variables whose row and column of P are empty, the diagonal included (P stays positive semidefinite).
+    pair = (j0, j1), j0 < j1: the two variables are coupled to each other and to no other variable -- rows and columns
+    j0, j1 of P hold (j0, j0), (j0, j1), (j1, j1) alone."""
     if empty:
         return sparse.csc_matrix((n, n))
     off = sparse.triu(sparse.random(n, n, density=min(1.0, 3.0 / n), random_state=rng, format="csc"), 1)
@@ -57,6 +64,11 @@ def _p_pattern(rng, n, empty=False, dense_row=None, no_p=()):
     F = F + F.T
     no_p = np.asarray(no_p, np.int64)
     F[no_p, :] = 0.0; F[:, no_p] = 0.0
+    if pair is not None:
+        j0, j1 = pair
+        assert 0 <= j0 < j1 < n
+        F[[j0, j1], :] = 0.0; F[:, [j0, j1]] = 0.0
+        F[j0, j1] = F[j1, j0] = 0.3
     d = 1.0 + np.abs(F).sum(axis=1) + rng.uniform(0, 2, n)
     d[no_p] = 0.0
     F[np.arange(n), np.arange(n)] = d
@@ -144,12 +156,23 @@ def _plant(rng, P, A, rows, sign, kinds=None):
     return q, l, u, x, y, act
 
 
-def _assemble(name, engines, seed, n, m, members, p_kw=None, a_kw=None, settings=None):
-    """members: per member (rows or a function of the rng giving them, sign[, kinds])."""
+def pair_slots(P, pair):
+    """The slots of (j0, j0), (j0, j1), (j1, j1) in the values of triu(P) (CSC, sorted)."""
+    j0, j1 = pair
+    at = lambda i, j: int(P.indptr[j] + np.searchsorted(P.indices[P.indptr[j]:P.indptr[j + 1]], i))
+    slots = np.array([at(j0, j0), at(j0, j1), at(j1, j1)], np.int64)
+    assert np.array_equal(P.indices[slots], [j0, j0, j1])
+    return slots
+
+
+def _assemble(name, engines, seed, n, m, members, p_kw=None, a_kw=None, settings=None, singular=None):
+    """members: per member (rows or a function of the rng giving them, sign[, kinds]).  singular: the member whose
+    pair of P (p_kw["pair"]) holds [[1, 1], [1, 1]] -- set before its q is planted, so the planted point solves it."""
     rng = np.random.default_rng(seed)
     P = _p_pattern(rng, n, **(p_kw or {}))
     A = _a_pattern(rng, n, m, **(a_kw or {}))
     B = len(members)
+    pair = (p_kw or {}).get("pair")
     Px_all = np.empty((B, P.nnz)); Ax_all = np.empty((B, A.nnz))
     Q = np.empty((B, n)); L = np.empty((B, m)); U = np.empty((B, m))
     X = np.empty((B, n)); Y = np.empty((B, m)); act = np.empty((B, m), np.int64)
@@ -158,6 +181,8 @@ def _assemble(name, engines, seed, n, m, members, p_kw=None, a_kw=None, settings
         rows = rows(rng) if callable(rows) else np.asarray(rows, np.int64)
         Px_all[b] = rng.uniform(0.5, 2.0) * P.data
         Ax_all[b] = 10.0 ** rng.uniform(-1.0, 1.0) * A.data
+        if b == singular:
+            Px_all[b][pair_slots(P, pair)] = 1.0
         Pb = sparse.csc_matrix((Px_all[b], P.indices, P.indptr), shape=(n, n))
         Ab = sparse.csc_matrix((Ax_all[b], A.indices, A.indptr), shape=(m, n))
         Q[b], L[b], U[b], X[b], Y[b], act[b] = _plant(rng, Pb, Ab, rows, sign, spec[2] if len(spec) > 2 else None)
@@ -166,7 +191,7 @@ def _assemble(name, engines, seed, n, m, members, p_kw=None, a_kw=None, settings
     inc = SimpleNamespace(gx=draw(B, n), gy=draw(B, m), dQ=draw(B, NDIR, n), dL=draw(B, NDIR, m), dU=draw(B, NDIR, m),
                           dPx=draw(B, NDIR, P.nnz), dAx=draw(B, NDIR, A.nnz))
     return SimpleNamespace(name=name, engines=engines, n=n, m=m, B=B, P=P, A=A, Px_all=Px_all, Ax_all=Ax_all, Q=Q, L=L, U=U,
-                           x=X, y=Y, act=act, inc=inc, settings=dict(settings or {}))
+                           x=X, y=Y, act=act, inc=inc, settings=dict(settings or {}), pair=pair, singular=singular)
 
 
 BOTH, STREAMED = ("auto", "streamed"), ("streamed",)
@@ -174,6 +199,11 @@ CASES = ("one", "pad", "pad_exact", "scan", "scan2", "rows", "lp", "lds64k", "ma
 ENGINES = dict(one=BOTH, pad=BOTH, pad_exact=BOTH, scan=BOTH, scan2=STREAMED, rows=STREAMED, lp=BOTH, lds64k=STREAMED,
                max=STREAMED)          # (n <= 128: the tiled engine too)
 ROWS_DENSE_A, ROWS_EMPTY_COL, ROWS_NO_P = (3, 17), 150, (5, 7, 200)
+# Cases with a member whose KKT inversion meets a pivot of the wrong sign: not in CASES, whose every member is served.
+VERDICT_CASES = ("wrongpivot",)
+ENGINES["wrongpivot"] = BOTH
+PAIR = (9, 23)                         # j0 < j1, the decoupled pair of "wrongpivot"
+VERDICT_DELTA = 2.0 ** -60             # > 0, and below half an ulp of 1.0: 1.0 + delta == 1.0
 _cases = {}
 
 
@@ -214,6 +244,17 @@ def _build(name, variant):
     if name == "max":        # N == NPOL == 1408, every row of the KKT matrix a real one; m at the streamed engine's limit
         n, m = 704, 1129     # (n = 1024, N = 2048 passed too but spends 9 s in the three inversions: DESIGN section 4)
         return _assemble(name, STREAMED, 19 + s, n, m, [(pick(n, m, n), "mixed")])
+    if name == "wrongpivot":
+        # One member's P holds [[1, 1], [1, 1]] on the pair PAIR, which P couples to nothing else.  Without scaling and
+        # with delta below half an ulp of 1 the device forms these very bits, pivot j0 is 1 and leaves
+        # K[j1][j1] = fma(-1, 1 * (1 / 1), 1) = 0 exactly: pivot j1 is 0.0, the wrong sign (gj_verdict).  P is positive
+        # semidefinite and the active rows j0, j1 -- their dominant entries sit in those columns -- pin x_j0 - x_j1, so
+        # the QP is convex with a unique solution.  NPOL = 96 with four different paddings; variant 1 moves the
+        # singular pair from member 1 to member 2.
+        n, m = 40, 56
+        counts = (5, 24, 25, 40) if variant == 0 else (40, 7, 25, 31)
+        return _assemble(name, BOTH, 20 + s, n, m, [(pick(n, m, c, must=PAIR), "mixed") for c in counts],
+                         p_kw=dict(pair=PAIR), settings=dict(scaling=0, delta=VERDICT_DELTA), singular=1 if variant == 0 else 2)
     raise KeyError(name)
 
 
@@ -242,6 +283,8 @@ def _rebase(c, c0):
     for b in range(c0.B):
         out.Px_all[b] = rng.uniform(0.5, 2.0) * P.data
         out.Ax_all[b] = 10.0 ** rng.uniform(-1.0, 1.0) * A.data
+        if b == c.singular:
+            out.Px_all[b][pair_slots(P, c.pair)] = 1.0
         Pb = sparse.csc_matrix((out.Px_all[b], P.indices, P.indptr), shape=(n, n))
         Ab = sparse.csc_matrix((out.Ax_all[b], A.indices, A.indptr), shape=(m, n))
         rows = np.flatnonzero(c.act[b])
@@ -447,6 +490,36 @@ def truth_at(c, b, x, y):
 def accepts(pri, dua, pri0, dua0):
     """The acceptance rule of polish (polish.c:301-311) for polished residuals pri, dua after ADMM's pri0, dua0."""
     return bool((pri < pri0 and dua < dua0) or (pri < pri0 and dua0 < 1e-10) or (dua < dua0 and pri0 < 1e-10))
+
+
+def device_kkt(mem, delta):
+    """[P + delta I, Ar'; Ar, -delta I] of a member as k_bp_form forms it: the planted rows, lows first."""
+    M = Route(mem).M.copy()
+    i = np.arange(M.shape[0])
+    M[i, i] = np.where(i < mem.n, M[i, i] + delta, 0.0 - delta)
+    return M
+
+
+def gj_verdict(K, n):
+    """A float64 model of gj_sweep (batch_streamed.h) as k_bp_invert runs it: Gauss-Jordan in place in the natural
+    order, no pivoting, and the quasi-definite verdict -- pivot k must be > 0 for k < n and < 0 beyond; zero and NaN
+    are wrong.  Returns the first wrong pivot as (k, value), or None.  (The device fuses the update of an entry into
+    one fma; here the product is rounded first.  Where the update is exact -- the singular pair -- both give the same
+    bits; elsewhere the verdict rests on pivots far from zero.)"""
+    K = np.array(K, float)
+    N = K.shape[0]
+    for k in range(N):
+        akk = K[k, k]
+        if not (akk > 0.0 if k < n else akk < 0.0):
+            return k, float(akk)
+        piv = 1.0 / akk
+        rk = K[k] * piv
+        ck = K[:, k].copy()
+        K -= np.outer(ck, rk)
+        K[:, k] = 0.0 - ck * piv
+        K[k] = rk
+        K[k, k] = piv
+    return None
 
 
 # ------------------------------------------------------------------------------------------------ the bar

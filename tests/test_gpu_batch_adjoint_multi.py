@@ -8,8 +8,9 @@ the first comes from _references; that of the second is the same function (adjoi
 x, y, from _oracle_runs) kept under a key of its own, because _references files every explicit gradient under one
 key.  tests/test_batch_adjoint_multi_host.py shows the reference linear in the cotangent.
 
-No existing test has a recipe for a member whose inversion meets a pivot of the wrong sign (status -1), so that verdict
-on a kept inversion is not exercised here."""
+A member whose inversion meets a pivot of the wrong sign (status -1) needs a recipe of its own: that verdict on a kept
+inversion is exercised by tests/test_gpu_batch_pivot_verdict.py (test_kept_inversion) on the case "wrongpivot" of
+tests/_planted_qp.py, which tests/test_planted_verdict_host.py proves on the CPU."""
 import os
 import subprocess
 import sys
