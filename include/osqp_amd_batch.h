@@ -23,8 +23,8 @@ typedef struct osqp_amd_batch osqp_amd_batch;
  * Returns 0 or an osqp_error_type code (include/constants.h:42-50 numbering):
  * OSQP_NONCVX_ERROR when some member's K = P + sigma I + A' rho A is not positive definite
  * (stderr names the first such member), OSQP_SETTINGS_VALIDATION_ERROR for settings->polish != 0
- * (polish is a call on a solved handle: osqp_amd_batch_polish) or time_limit > 0, which the batched
- * kernel does not implement. */
+ * (polish is a call on a solved handle: osqp_amd_batch_polish) or time_limit > 0 (still refused at setup: a time
+ * limit is given per call, osqp_amd_batch_solve_limited). */
 c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int batch, const csc *P, const csc *A,
                            const c_float *Px_all, const c_float *Ax_all,
                            const c_float *Q, const c_float *L, const c_float *U,
@@ -202,6 +202,32 @@ c_int osqp_amd_batch_solve_members(osqp_amd_batch *b, const c_int *members, c_in
  * for a NULL handle, OSQP_DATA_VALIDATION_ERROR for NULL out, OSQP_LINSYS_SOLVER_INIT_ERROR (stderr line) for a handle
  * of another engine. */
 c_int osqp_amd_batch_common_columns(osqp_amd_batch *b, c_int out[3]);
+/* osqp_amd_batch_solve / _solve_members with two limits that hold for this call only.
+ * members NULL (count ignored): every member, on any engine.  members non-NULL: the checks, refusals and
+ * semantics of osqp_amd_batch_solve_members (common-K only).
+ * max_iter   0: settings->max_iter of setup;  > 0: the cap of this call.  The call leaves the results and the whole
+ *            handle state that a handle set up with that max_iter leaves after a solve, to the bit; the next plain solve
+ *            runs with the setup's value again.
+ * time_limit 0: none;  > 0: seconds, counted from the start of the call's device work.  The clock is looked at only
+ *            at clock iterations -- those of a termination check or, with check_termination == 0, every 25th -- and
+ *            after that check: a member that passes it leaves as ever.  Every other member then ends as it ends at
+ *            max_iter (which wins when both hold) -- the approximate test, then OSQP_TIME_LIMIT_REACHED -- with x, y,
+ *            info8 and the stored iterates of its last iteration; polish, adjoint and tangent skip it (status 0).
+ *            A member runs at most one clock interval of iterations past the deadline; with more members than the
+ *            device runs workgroups at once, each later wave of workgroups adds that interval again.  On the tiled
+ *            and streamed engines the deadline is a device word that one thread of each workgroup compares with
+ *            wall_clock64(); the common-K engine, whose members move in lockstep, compares a host clock.
+ * Refusals, in this order, with nothing of the handle changed: OSQP_WORKSPACE_NOT_INIT_ERROR for a NULL handle;
+ * OSQP_SETTINGS_VALIDATION_ERROR for max_iter < 0 (or beyond INT_MAX), time_limit < 0 or not finite; the refusals of
+ * osqp_amd_batch_solve_members when members is given; OSQP_NONCVX_ERROR as osqp_amd_batch_solve.
+ * (NULL, ., 0, 0) is osqp_amd_batch_solve to the bit, with the same launches. */
+c_int osqp_amd_batch_solve_limited(osqp_amd_batch *b, const c_int *members, c_int count,
+                                   c_int max_iter, c_float time_limit);
+/* Of the last solve by any call: out[0] max_iter in force, out[1] time_limit in force (0 = none),
+ * out[2] seconds between the two device stamps of a clocked solve (0 when time_limit was 0),
+ * out[3] members that the clock cut.  Before the first solve: settings->max_iter, 0, 0, 0.  Touches no GPU memory.
+ * OSQP_WORKSPACE_NOT_INIT_ERROR for a NULL handle, OSQP_DATA_VALIDATION_ERROR for NULL out. */
+c_int osqp_amd_batch_solve_report(osqp_amd_batch *b, c_float out[4]);
 /* polish (src/polish.c:19-350) for every member whose last solve ended OSQP_SOLVED; the others are skipped.
  * Polish is this call on a solved handle, with settings->delta and settings->polish_refine_iter as given at setup;
  * settings->polish != 0 itself stays refused by the setup functions.  Per member, in its scaled space: the active

@@ -16,6 +16,7 @@ STREAMED_MAX_N = 1024  # streamed-inverse engine (batch_streamed.h)
 ENGINES = {"tiled": 0, "streamed": 1, "common": 2}   # OSQP_AMD_BATCH_TILED / _STREAMED / _COMMON
 KktInfo = namedtuple("KktInfo", "builds kept npol members")     # BatchOSQP.kkt_info()
 Columns = namedtuple("Columns", "started packs ended")          # BatchOSQP.columns()
+SolveReport = namedtuple("SolveReport", "max_iter time_limit elapsed cut")   # BatchOSQP.solve_report()
 INFO_FIELDS = ["iter", "status_val", "obj_val", "pri_res", "dua_res", "rho_updates", "rho_estimate", "rho"]
 
 
@@ -40,6 +41,10 @@ def _bind(L):
     L.osqp_amd_batch_solve_members.argtypes = [H, abi.c_int_p, abi.c_int]
     L.osqp_amd_batch_common_columns.restype = abi.c_int
     L.osqp_amd_batch_common_columns.argtypes = [H, abi.c_int_p]
+    L.osqp_amd_batch_solve_limited.restype = abi.c_int
+    L.osqp_amd_batch_solve_limited.argtypes = [H, abi.c_int_p, abi.c_int, abi.c_int, abi.c_float]
+    L.osqp_amd_batch_solve_report.restype = abi.c_int
+    L.osqp_amd_batch_solve_report.argtypes = [H, abi.c_float_p]
     L.osqp_amd_batch_polish.restype = abi.c_int
     L.osqp_amd_batch_polish.argtypes = [H, abi.c_int_p]
     L.osqp_amd_batch_adjoint.restype = abi.c_int
@@ -317,8 +322,9 @@ class BatchOSQP:
                              "tangent as they are")
         self.engine = engine
         self._shared_kkt = False
-        # neither path may hand back an unpolished or unclocked answer to a caller who asked for one: the batch
-        # kernel implements neither, so both paths refuse them (OSQP_SETTINGS_VALIDATION_ERROR = 2)
+        # neither path may hand back an unpolished or unclocked answer to a caller who asked for one: polish is a call
+        # on a solved handle and a time limit an argument of solve(), so both paths refuse the settings
+        # (OSQP_SETTINGS_VALIDATION_ERROR = 2)
         for k in ("polish", "time_limit"):
             if settings.get(k, 0) and settings[k] > 0:
                 raise ValueError("osqp_amd_batch_setup failed with error 2: %s is not implemented by the batched engine" % k)
@@ -690,11 +696,28 @@ class BatchOSQP:
             return self._many_each(lambda b, s: s.warm_start(x=None if X is None else X[b], y=None if Y is None else Y[b]))
         return int(self._lib.osqp_amd_batch_warm_start(self._h, _p(X), _p(Y if self.m else None)))
 
-    def solve(self, fetch=True, members=None):
+    def solve(self, fetch=True, members=None, max_iter=None, time_limit=None):
         """osqp_solve for every member, or (engine="common" only) for the listed ones: members is a strictly ascending
         integer sequence or a boolean mask of length B.  Only the listed members are loaded, iterated and stored; of the
         others nothing changes, and results() returns them as they were.  polish, adjoint and tangent are served once every
-        member has been solved on the current problem, by one call or by several."""
+        member has been solved on the current problem, by one call or by several.
+        max_iter (an integer >= 1) and time_limit (seconds, > 0) hold for this call only (osqp_amd_batch_solve_limited):
+        the call ends as a handle set up with that max_iter would, to the bit; a member the clock stops ends with status
+        -6 (OSQP_TIME_LIMIT_REACHED), or 2 where the approximate test passes, and keeps its last iterate.  The clock is
+        looked at only where termination is checked (every 25th iteration with check_termination=0); solve_report()
+        tells what the call ran with."""
+        limited = max_iter is not None or time_limit is not None
+        if max_iter is not None:
+            if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+                raise ValueError("max_iter must be an integer >= 1, not %r" % (max_iter,))
+        if time_limit is not None:
+            if isinstance(time_limit, bool) or not isinstance(time_limit, (int, float, np.integer, np.floating)) \
+                    or not np.isfinite(time_limit) or time_limit <= 0:
+                raise ValueError("time_limit must be a finite number of seconds > 0, not %r" % (time_limit,))
+        if limited and self._many is not None:
+            raise RuntimeError("solve(%s=...) is not served by the one-engine-per-member route (engine=\"auto\", n > %d); "
+                               "set the batch up with engine=\"streamed\" or engine=\"common\""
+                               % ("max_iter" if max_iter is not None else "time_limit", BATCH_MAX_N))
         if members is not None:
             if getattr(self, "engine", None) != "common" or self._many is not None or self._h is None:
                 raise RuntimeError("solve(members=...) is not served by the %s; it is a call of the common-K engine "
@@ -702,19 +725,40 @@ class BatchOSQP:
                                                             if self._many is not None else "tiled or the streamed engine"))
             members = check_members(self.B, members)
             self._status_polish = None
-            rc = self._lib.osqp_amd_batch_solve_members(self._h, abi.iptr(members), members.size)
+            if limited:
+                rc = self._lib.osqp_amd_batch_solve_limited(self._h, abi.iptr(members), members.size, int(max_iter or 0),
+                                                            float(time_limit or 0.0))
+            else:
+                rc = self._lib.osqp_amd_batch_solve_members(self._h, abi.iptr(members), members.size)
             if rc:
-                raise RuntimeError("osqp_amd_batch_solve_members failed (%d)" % rc)
+                raise RuntimeError("osqp_amd_batch_solve_%s failed (%d)" % ("limited" if limited else "members", rc))
             return self.results() if fetch else None
         if self._many is not None:
             from .multi import solve_many
             self._last = solve_many(self._many, max_workers=8)
             return self._many_results() if fetch else None
         self._status_polish = None
-        rc = self._lib.osqp_amd_batch_solve(self._h)
+        if limited:
+            rc = self._lib.osqp_amd_batch_solve_limited(self._h, C.cast(None, abi.c_int_p), 0, int(max_iter or 0),
+                                                        float(time_limit or 0.0))
+        else:
+            rc = self._lib.osqp_amd_batch_solve(self._h)
         if rc:
-            raise RuntimeError("osqp_amd_batch_solve failed (%d)" % rc)
+            raise RuntimeError("osqp_amd_batch_solve%s failed (%d)" % ("_limited" if limited else "", rc))
         return self.results() if fetch else None
+
+    def solve_report(self):
+        """Of the last solve by any call: (max_iter, time_limit, elapsed, cut) -- the iteration cap and the time limit in
+        force (0: none), the seconds between the two device stamps of a solve with a time limit (0 without one) and the
+        members the clock stopped.  Touches no GPU memory."""
+        if self._many is not None:
+            raise RuntimeError("solve_report is not served by the one-engine-per-member route (engine=\"auto\", n > %d)"
+                               % BATCH_MAX_N)
+        out = np.zeros(4)
+        rc = self._lib.osqp_amd_batch_solve_report(self._h, abi.fptr(out))
+        if rc:
+            raise RuntimeError("osqp_amd_batch_solve_report failed (%d)" % rc)
+        return SolveReport(int(out[0]), float(out[1]), float(out[2]), int(out[3]))
 
     def columns(self):
         """Of the last solve of a common-K handle: (started, packs, ended) -- the columns it started with (B, or the

@@ -27,6 +27,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <chrono>
+#include <climits>
+#include <cmath>
 #include <vector>
 #include <algorithm>
 #include "../../include/osqp_amd.h"
@@ -496,18 +499,21 @@ struct TiledK {
 // PH = 0: setup phase (scale, classify, build K^-1, store the workspace);
 // PH = 1: solve phase (load the workspace, ADMM loop, store the solution);
 // PH = 2: matrix-update phase (osqp_update_P_A, osqp.c:1171-1279): the setup phase on the current raw data with
-//         the member's row classes, rho and iterates kept.
+//         the member's row classes, rho and iterates kept;
+// PH = 3: the solve phase of a solve with a time limit (admm_loop<.., CLOCK = true>): an instantiation of its own, so
+//         that PH = 1 -- 256 registers and spills at tile 8 -- carries no clock statement.  clk: the clock words (PH = 3).
 #ifndef BATCH_WAVES_PER_SIMD
 #define BATCH_WAVES_PER_SIMD 2   // 4 (two workgroups per CU, <= 128 registers) was measured slower: spills lengthen the slowest QP
 #endif
 template <int TR, int TC, int GC, int PH>
-__global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k_batch_solve(BPattern p, BSettings st, BIO io) {
+__global__ void __launch_bounds__(16 * GC, PH == 1 || PH == 3 ? BATCH_WAVES_PER_SIMD : 2)
+k_batch_solve(BPattern p, BSettings st, BIO io, unsigned long long *clk) {
   constexpr int NP = 16 * TR, NT = 16 * GC;
   static_assert(GC * TC == NP, "tile shape");
   static_assert(4 * NP <= NT, "the GEMV reduction and the column dots use four lanes per row/column");
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x;
-  const long long qp = (PH == 1 && io.order) ? io.order[blockIdx.x] : (int)blockIdx.x;
+  const long long qp = ((PH == 1 || PH == 3) && io.order) ? io.order[blockIdx.x] : (int)blockIdx.x;
   const BL s = bt_layout<NP, NT>(lds, p);
   double *Wk = io.Wk + qp * (long long)(NP * NP);
   BDbg dbg;
@@ -552,7 +558,7 @@ __global__ void __launch_bounds__(16 * GC, PH == 1 ? BATCH_WAVES_PER_SIMD : 2) k
   DBG(dbg.tstamp[4] = wall_clock64();)
   load_kinv<NP, NT>(eng.ag, Wk);
   DBG(dbg.tstamp[5] = wall_clock64();)
-  admm_loop<NT, true>(s, p, st, io, qp, a, 0, eng, dbg);
+  admm_loop<NT, true, PH == 3>(s, p, st, io, qp, a, 0, eng, dbg, clk);
   DBG(dbg.tstamp[6] = wall_clock64();)
   store_solution<NT>(s, p, st, io, qp, a, a.check_pending ? BF_OPEN : (a.need_refine ? BF_REFINE : 0));
   DBG(if (st.profile && tid == 0) {
@@ -705,6 +711,15 @@ __global__ void __launch_bounds__(1024) k_batch_order(long long B, const double 
   for (long long b = tid; b < B; b += 1024) order[atomicAdd(&hist[1023 - (int)(info[b * 8] * sc)], 1)] = (int)b;
 }
 
+// The clock of a solve with a time limit, one thread each on the handle's stream: k_clock_start, first in the solve,
+// writes the absolute deadline, the start stamp and a zero count of cut members; k_clock_end, after the last loop
+// kernel, the end stamp.
+__global__ void k_clock_start(unsigned long long *clk, unsigned long long ticks) {
+  const unsigned long long now = wall_clock64();
+  clk[CK_DEADLINE] = now + ticks; clk[CK_START] = now; clk[CK_END] = now; clk[CK_CUT] = 0;
+}
+__global__ void k_clock_end(unsigned long long *clk) { clk[CK_END] = wall_clock64(); }
+
 #include "batch_streamed.h"
 #include "batch_common.h"
 #include "batch_polish.h"
@@ -750,6 +765,11 @@ struct osqp_amd_batch {
   bool noncvx = false;      // the last matrix update left some member's K indefinite: solve refuses
   int *d_order = nullptr;   // dispatch order for the next solve (k_batch_order)
   int lpt = 1;
+  // the limits of a solve (osqp_amd_batch_solve_limited)
+  unsigned long long *d_clock = nullptr;   // [CK_COUNT_] the clock words, allocated by the first solve with a time limit
+  int clock_khz = 0;        // hipDeviceAttributeWallClockRate, read with them
+  double report[4] = {0, 0, 0, 0};   // osqp_amd_batch_solve_report of the last solve
+  std::chrono::steady_clock::time_point clock_t0;   // when k_clock_start was enqueued (the common-K engine's clock)
   // polish (batch_polish.h)
   double pol_delta = 0.0;   // settings->delta
   int pol_refine = 0;       // settings->polish_refine_iter
@@ -786,7 +806,7 @@ struct osqp_amd_batch {
   long long kkt_builds = 0; // passes of k_bp_form + k_bp_invert over the solved members since setup, polish's included
 };
 
-static void batch_launch(osqp_amd_batch *b, int phase);
+static void batch_launch(osqp_amd_batch *b, int phase, const BSettings *st = nullptr, unsigned long long *clk = nullptr);
 
 // the problem or the stored iterates have changed: no member's results are those of a solve of what the handle holds
 static void mark_unsolved(osqp_amd_batch *b) {
@@ -859,6 +879,7 @@ static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
   if (t.adaptive_rho && !t.rho_interval)   // deterministic stand-in for the timing rule (osqp.c:267-279)
     t.rho_interval = s->check_termination ? 4 * (int)s->check_termination : 100;
   t.max_iter = (int)s->max_iter; t.check_termination = (int)s->check_termination;
+  b->report[0] = t.max_iter;                     // (before the first solve: the cap a plain one will run with)
   t.scaled_termination = (int)s->scaled_termination; t.warm_start = (int)s->warm_start;
   const char *e = getenv("OSQP_AMD_BATCH_REFINE");
   t.refine = e ? atoi(e) : 1;
@@ -919,8 +940,8 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
   if (settings->rho <= 0 || settings->sigma <= 0 || settings->alpha <= 0 || settings->alpha >= 2 ||
       settings->max_iter <= 0 || settings->scaling < 0 || settings->check_termination < 0)
     return OSQP_SETTINGS_VALIDATION_ERROR;
-  // the solve has no polish step (polish is a call of its own on a solved handle, osqp_amd_batch_polish) and no
-  // clock: refusing beats an answer the caller did not ask for
+  // the solve has no polish step (polish is a call of its own on a solved handle, osqp_amd_batch_polish) and a clock
+  // only per call (osqp_amd_batch_solve_limited): refusing beats an answer the caller did not ask for
   if (settings->polish || settings->time_limit > 0) {
     fprintf(stderr, "osqp_amd batch: %s is not implemented by the batched engine\n",
             settings->polish ? "polish" : "time_limit");
@@ -1182,16 +1203,21 @@ static int bs_setup_launch(osqp_amd_batch *b, bool update) {
 // The streamed engine's part of a solve: rounds of the ADMM loop.  Round 0 runs every member; a member whose rho
 // moves leaves with a rebuild request, and the next round re-forms and re-inverts K for those members and
 // resumes them.  One counter is read back per round; rounds <= rho updates of the slowest member + 1.
-static int bs_solve(osqp_amd_batch *b) {
+// st: the settings of this call (b->st, or a copy with the call's max_iter); clk: the clock words of a solve with a
+// time limit (k_bs_loop<true>), null without one.
+static int bs_solve(osqp_amd_batch *b, const BSettings &st, unsigned long long *clk) {
   bs_rebuild(b, nullptr, b->B);                  // members whose class changed in an update, or rho at max_iter
   const int *list = nullptr;
   long long count = b->B;
   int cur = 0, rounds = 0;
   for (;;) {
     BCHK(hipMemsetAsync(b->d_count, 0, sizeof(int), b->stream));
-    set_dynamic_lds(KFN(k_bs_loop), b->lds_bytes);
-    hipLaunchKernelGGL(k_bs_loop, dim3((unsigned)count), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io,
-                       b->NPs, list, b->d_count, b->d_list[cur]);
+    const void *fn = clk ? KFN(k_bs_loop<true>) : KFN(k_bs_loop<false>);
+    int NP = b->NPs;
+    int *rb_list = b->d_list[cur];
+    void *args[] = {&b->pat, const_cast<BSettings *>(&st), &b->io, &NP, &list, &b->d_count, &rb_list, &clk};
+    set_dynamic_lds(fn, b->lds_bytes);
+    (void)hipLaunchKernel(fn, dim3((unsigned)count), dim3(BS_NT), args, b->lds_bytes, b->stream);
     BCHK(hipGetLastError());
     int h = 0;
     BCHK(hipMemcpyAsync(&h, b->d_count, sizeof(int), hipMemcpyDeviceToHost, b->stream));
@@ -1203,6 +1229,7 @@ static int bs_solve(osqp_amd_batch *b) {
     bs_rebuild(b, list, count);
     cur ^= 1;
   }
+  if (clk) hipLaunchKernelGGL(k_clock_end, dim3(1), dim3(1), 0, b->stream, clk);
   bs_rebuild(b, nullptr, b->B);                  // rho moved in the last iteration: K^-1 follows it, as in k_batch_solve
   b->last_rounds = rounds;
   return 0;
@@ -1322,8 +1349,11 @@ static double bc_batch_estimate(const std::vector<double> &est, size_t cols) {
 // The common-K engine's part of a solve: the ADMM loop of admm_loop, an iteration = a few launches over the columns.
 // members: the `count` members to solve, ascending (null: all B, column = member).  Column c starts as member
 // members[c]; C, the columns in use, starts at count and falls at every pack (batch_common.h).
-static int bc_solve(osqp_amd_batch *b, const c_int *members, long long count) {
-  const BSettings &st = b->st;
+// st: the settings of this call.  limit > 0: the call's time limit in seconds, the host's to watch -- the columns move in
+// lockstep --: at a clock iteration (BATCH_CLOCK_INTERVAL), once the stream is synchronised and the termination check
+// has been made, the time since k_clock_start was enqueued (b->clock_t0) is compared with it, and an expiry makes the
+// iteration the last; *cut: the members running then.
+static int bc_solve(osqp_amd_batch *b, const BSettings &st, const c_int *members, long long count, double limit, long long *cut) {
   BCT t = b->ct;
   const int n = b->n, m = b->m, NP = b->NPs, Bp = t.Bp;
   const dim3 eb(BC_TX, BC_TY);
@@ -1388,9 +1418,14 @@ static int bc_solve(osqp_amd_batch *b, const c_int *members, long long count) {
     hipLaunchKernelGGL(k_bc_step, dim3(gx, ey(n + m)), eb, 0, b->stream, b->pat, b->io, t, rho, st.alpha);
     const int checked = st.check_termination && (iter % st.check_termination == 0);
     const int adapt = st.adaptive_rho && st.rho_interval && (iter % st.rho_interval == 0);
-    const bool last = iter >= st.max_iter;
+    bool last = iter >= st.max_iter, expired = false;
+    const bool clock_iter = limit > 0 && !last && (checked || (!st.check_termination && iter % BATCH_CLOCK_INTERVAL == 0));
+    auto read_clock = [&]() {
+      if (clock_iter && std::chrono::duration<double>(std::chrono::steady_clock::now() - b->clock_t0).count() >= limit)
+        last = expired = true;
+    };
     if (checked || adapt) {
-      hipLaunchKernelGGL(k_bc_check, dim3((unsigned)t.C), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, t, NP,
+      hipLaunchKernelGGL(k_bc_check, dim3((unsigned)t.C), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, st, b->io, t, NP,
                          rho, iter, checked, adapt, 0);
       BCHK(hipGetLastError());
       // a pack needs more than one group of columns; the flags it is made from come over with the count
@@ -1401,12 +1436,13 @@ static int bc_solve(osqp_amd_batch *b, const c_int *members, long long count) {
       if (may_pack) BCHK(hipMemcpyAsync(flags.data(), t.done, (size_t)t.C * sizeof(int), hipMemcpyDeviceToHost, b->stream));
       BCHK(hipStreamSynchronize(b->stream));
       running = count - done;
+      read_clock();
       const double rn = (adapt && running > 0) ? bc_batch_estimate(est, (size_t)t.C) : 0.0;
       if (rn > 0.0 && (rn > rho * st.adapt_tol || rn < rho / st.adapt_tol)) {     // adapt_rho (auxil.c:13-74)
         b->bc_rho = rn;
         hipLaunchKernelGGL(k_bc_adopt, dim3(g256), dim3(256), 0, b->stream, b->io, t);
         b->bc_rebuild = true;
-        if (!last) {                             // (at max_iter no solve with K follows: the rebuild ends the solve)
+        if (!last) {                             // (after the last iteration no solve with K follows: the rebuild ends the solve)
           if (verdict_pending) if (const int rc = take_verdict()) return rc;
           bc_rebuild(b); rounds++;
           hipLaunchKernelGGL(k_bc_load_w, dim3(gx, ey(std::max(m, 1))), eb, 0, b->stream, m, b->io, t, rn);
@@ -1414,7 +1450,7 @@ static int bc_solve(osqp_amd_batch *b, const c_int *members, long long count) {
       }
       // Pack once a whole group of 64 columns -- a workgroup column of every kernel -- is saved.  A verdict still open
       // is taken first: it is read by column.  (Taking it early changes no iterate: refinement is applied while probing.)
-      if (may_pack && running > 0 && groups(running) < groups(t.C)) {
+      if (may_pack && !last && running > 0 && groups(running) < groups(t.C)) {
         if (verdict_pending) if (const int rc = take_verdict()) return rc;
         list.clear();
         for (int c = 0; c < t.C; c++) if (!flags[(size_t)c]) list.push_back(c);
@@ -1427,13 +1463,18 @@ static int bc_solve(osqp_amd_batch *b, const c_int *members, long long count) {
         gg.x = (unsigned)((((t.C + 15) & ~15) + BC_TILE - 1) / BC_TILE);
         b->bc_cols[1]++; b->bc_cols[2] = t.C;
       }
+    } else if (clock_iter) {
+      BCHK(hipStreamSynchronize(b->stream));
+      read_clock();
     }
     if (last && running > 0) {
-      hipLaunchKernelGGL(k_bc_check, dim3((unsigned)t.C), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, b->st, b->io, t, NP,
-                         b->bc_rho, iter, checked, 0, 1);
+      hipLaunchKernelGGL(k_bc_check, dim3((unsigned)t.C), dim3(BS_NT), b->lds_bytes, b->stream, b->pat, st, b->io, t, NP,
+                         b->bc_rho, iter, checked, 0, expired ? 2 : 1);
+      if (expired) *cut = running;
       running = 0;
     }
   }
+  if (limit > 0) hipLaunchKernelGGL(k_clock_end, dim3(1), dim3(1), 0, b->stream, b->d_clock);
   if (verdict_pending) if (const int rc = take_verdict()) return rc;
   if (b->bc_rebuild) bc_rebuild(b);              // rho moved in the last iteration: K^-1 follows it
   BCHK(hipStreamSynchronize(b->stream));         // (`list` leaves scope: its last copy has been made)
@@ -1444,13 +1485,15 @@ static int bc_solve(osqp_amd_batch *b, const c_int *members, long long count) {
 // the one instantiation of k_batch_solve for (tile, phase)
 static const void *batch_kernel(int tile, int phase) {
   if (phase == 2) return tile == 8 ? KFN((k_batch_solve<8, 4, 32, 2>)) : KFN((k_batch_solve<4, 2, 32, 2>));
+  if (phase == 3) return tile == 8 ? KFN((k_batch_solve<8, 4, 32, 3>)) : KFN((k_batch_solve<4, 2, 32, 3>));
   if (tile == 8) return phase ? KFN((k_batch_solve<8, 4, 32, 1>)) : KFN((k_batch_solve<8, 4, 32, 0>));
   return phase ? KFN((k_batch_solve<4, 2, 32, 1>)) : KFN((k_batch_solve<4, 2, 32, 0>));
 }
-static void batch_launch(osqp_amd_batch *b, int phase) {
+// st: the settings of a solve phase's call (null: b->st); clk: the clock words of phase 3
+static void batch_launch(osqp_amd_batch *b, int phase, const BSettings *st, unsigned long long *clk) {
   const void *fn = batch_kernel(b->tile, phase);
   set_dynamic_lds(fn, b->lds_bytes);
-  void *args[] = {&b->pat, &b->st, &b->io};
+  void *args[] = {&b->pat, st ? const_cast<BSettings *>(st) : &b->st, &b->io, &clk};
   (void)hipLaunchKernel(fn, dim3((unsigned)b->B), dim3(BT), args, b->lds_bytes, b->stream);
 }
 
@@ -1640,19 +1683,48 @@ extern "C" c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, 
 // A solve of all members (members = null) or of `count` chosen ones: what osqp_amd_batch_solve and
 // osqp_amd_batch_solve_members share once their arguments have passed.  The solved flags of the members it is about to
 // solve are cleared first and set when it has ended; `solved` is all of them.
-static c_int batch_solve_run(osqp_amd_batch *b, const c_int *members, long long count) {
+// max_iter > 0: the iteration cap of this call -- it runs with a copy of b->st, so everything max_iter does follows;
+// time_limit > 0: its time limit in seconds, counted from k_clock_start (osqp_amd_batch_solve_limited).
+static c_int batch_solve_run(osqp_amd_batch *b, const c_int *members, long long count, int max_iter = 0, double time_limit = 0.0) {
   BCHK(hipSetDevice(b->device));
+  BSettings st = b->st;
+  if (max_iter > 0) st.max_iter = max_iter;
+  unsigned long long *clk = nullptr;
+  long long cut = 0;
+  if (time_limit > 0) {
+    if (!b->d_clock) {
+      BCHK(hipDeviceGetAttribute(&b->clock_khz, hipDeviceAttributeWallClockRate, b->device));
+      if (b->clock_khz <= 0) return -102;
+      if (balloc_once(b, &b->d_clock, (size_t)CK_COUNT_)) return OSQP_MEM_ALLOC_ERROR;
+    }
+    clk = b->d_clock;
+  }
   b->solved = b->polished = false;
   if (!members) mark_unsolved(b);
   else for (long long k = 0; k < count; k++) b->member_solved[(size_t)members[k]] = b->member_polished[(size_t)members[k]] = 0;
   b->io.order = (b->lpt && b->solves > 0) ? b->d_order : nullptr;   // first solve: no history, index order
-  if (b->engine == OSQP_AMD_BATCH_COMMON) { if (const int rc = bc_solve(b, members, count)) return rc; }
-  else if (b->engine != OSQP_AMD_BATCH_STREAMED) batch_launch(b, 1);
-  else if (const int rc = bs_solve(b)) return rc;
+  if (clk) {
+    const double ticks = time_limit * 1e3 * (double)b->clock_khz;
+    hipLaunchKernelGGL(k_clock_start, dim3(1), dim3(1), 0, b->stream, clk, ticks < 0x1p62 ? (unsigned long long)ticks : 1ULL << 62);
+    b->clock_t0 = std::chrono::steady_clock::now();
+  }
+  if (b->engine == OSQP_AMD_BATCH_COMMON) { if (const int rc = bc_solve(b, st, members, count, time_limit, &cut)) return rc; }
+  else if (b->engine != OSQP_AMD_BATCH_STREAMED) {
+    batch_launch(b, clk ? 3 : 1, &st, clk);
+    if (clk) hipLaunchKernelGGL(k_clock_end, dim3(1), dim3(1), 0, b->stream, clk);
+  }
+  else if (const int rc = bs_solve(b, st, clk)) return rc;
   if (b->lpt && b->engine != OSQP_AMD_BATCH_COMMON) hipLaunchKernelGGL(k_batch_order, dim3(1), dim3(1024), 0, b->stream, b->B, b->io.info, b->d_order);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   b->solves++;                                   // (a kept KKT inversion is of an earlier solve now: kkt_kept)
+  b->report[0] = st.max_iter; b->report[1] = time_limit; b->report[2] = b->report[3] = 0.0;
+  if (clk) {                                     // the stamps and the count, once (a plain solve reads nothing extra)
+    unsigned long long w[CK_COUNT_];
+    BCHK(hipMemcpy(w, clk, sizeof(w), hipMemcpyDeviceToHost));
+    b->report[2] = (double)(w[CK_END] - w[CK_START]) / (1e3 * (double)b->clock_khz);
+    b->report[3] = b->engine == OSQP_AMD_BATCH_COMMON ? (double)cut : (double)w[CK_CUT];
+  }
   if (!members) std::fill(b->member_solved.begin(), b->member_solved.end(), (char)1);
   else for (long long k = 0; k < count; k++) b->member_solved[(size_t)members[k]] = 1;
   b->solved = std::find(b->member_solved.begin(), b->member_solved.end(), (char)0) == b->member_solved.end();
@@ -1665,8 +1737,8 @@ extern "C" c_int osqp_amd_batch_solve(osqp_amd_batch *b) {
   return batch_solve_run(b, nullptr, b->B);
 }
 
-extern "C" c_int osqp_amd_batch_solve_members(osqp_amd_batch *b, const c_int *members, c_int count) {
-  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+// the refusals of a member list given to a solve
+static c_int solve_members_check(osqp_amd_batch *b, const c_int *members, c_int count) {
   if (b->engine != OSQP_AMD_BATCH_COMMON) {
     fprintf(stderr, "osqp_amd batch: osqp_amd_batch_solve_members is a call of the common-K engine (OSQP_AMD_BATCH_COMMON); "
                     "the %s engine solves all members (osqp_amd_batch_solve)\n",
@@ -1676,9 +1748,32 @@ extern "C" c_int osqp_amd_batch_solve_members(osqp_amd_batch *b, const c_int *me
   if (!members || count < 1 || count > b->B) return OSQP_DATA_VALIDATION_ERROR;
   for (c_int k = 0; k < count; k++)
     if (members[k] < 0 || members[k] >= b->B || (k && members[k] <= members[k - 1])) return OSQP_DATA_VALIDATION_ERROR;
+  return 0;
+}
+
+extern "C" c_int osqp_amd_batch_solve_members(osqp_amd_batch *b, const c_int *members, c_int count) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (const c_int rc = solve_members_check(b, members, count)) return rc;
   if (b->noncvx) return OSQP_NONCVX_ERROR;
   // all B members, ascending: the identity, and the full solve to the bit
   return batch_solve_run(b, count == b->B ? nullptr : members, count);
+}
+
+extern "C" c_int osqp_amd_batch_solve_limited(osqp_amd_batch *b, const c_int *members, c_int count, c_int max_iter,
+                                             c_float time_limit) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (max_iter < 0 || max_iter > INT_MAX || !std::isfinite(time_limit) || time_limit < 0) return OSQP_SETTINGS_VALIDATION_ERROR;
+  if (members) if (const c_int rc = solve_members_check(b, members, count)) return rc;
+  if (b->noncvx) return OSQP_NONCVX_ERROR;
+  const bool all = !members || count == b->B;
+  return batch_solve_run(b, all ? nullptr : members, all ? b->B : count, (int)max_iter, time_limit);
+}
+
+extern "C" c_int osqp_amd_batch_solve_report(osqp_amd_batch *b, c_float out[4]) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!out) return OSQP_DATA_VALIDATION_ERROR;
+  for (int k = 0; k < 4; k++) out[k] = b->report[k];
+  return 0;
 }
 
 // Of the last solve of a common-K handle: the columns it started with, its packs, the columns in use when it ended.

@@ -18,6 +18,12 @@
 enum { S_PRI, S_DUA, S_OBJ, S_NPRI_S, S_NDUA_S, S_NZ_S, S_NAX_S, S_NQ_S, S_NATY_S, S_NPX_S,
        S_NZ, S_NAX, S_NQ, S_NATY, S_NPX, S_STATUS, S_RHO, S_ND, S_LHS, S_NDX, S_QDX, S_COUNT_ };
 enum { F_NORMS = 1, F_STATUS = 2, F_APPROX = 4 };
+// The clock of a solve with a time limit (admm_loop<.., CLOCK = true>, bc_solve).  It is looked at only at clock
+// iterations: those of a termination check or, with check_termination == 0, every BATCH_CLOCK_INTERVAL-th (the
+// reference's default check interval).  The device words of a handle's clock, written by k_clock_start / k_clock_end:
+#define BATCH_CLOCK_INTERVAL 25
+enum { CK_DEADLINE, CK_START, CK_END, CK_CUT, CK_COUNT_ };   // wall_clock64 ticks: deadline, first and last stamp; members cut
+#define S_EXPIRED 40       // s.red slot of the clock's verdict (beyond the reductions' [0, 13) and the scalars from 13)
 
 // Phase time stamps / per-phase accumulators exist only in -DOSQP_AMD_BATCH_DEBUG builds
 // (make BATCH_DEBUG=1): they cost ~26 registers and a 2 us s_memrealtime each.
@@ -38,6 +44,8 @@ struct BA {
   double rho, cs;                     // current rho, cost scaling c
   int iter, rho_updates;
   bool need_refine, check_pending;    // refinement verdict (BF_REFINE of io.flag) / still to be taken (BF_OPEN)
+  int end_iter;                       // the loop ends with this iteration: max_iter, or the clock iteration that
+                                      // found the deadline passed (set before adapt_rho, read by K::leave)
 };
 
 // constraint class of a row (auxil.c:76-98): -1 loose, 1 equality, 0 inequality; and its rho
@@ -356,9 +364,13 @@ __device__ __forceinline__ double rho_estimate(const double *sc, int m, double r
 // residual/termination code has ONE call site: a small stage machine replaces the reference's
 // in-loop / post-loop / approximate calls of update_info + check_termination (osqp.c:411-437, 537-581).
 // Returns true when the member left for a rebuild of K^-1 (K::leave): the kernel returns at once.
-template <int NT, bool SINGLE_PASS, class K>
+// CLOCK: the solve has a time limit, clk are the handle's clock words.  At a clock iteration, after the termination
+// check, ONE thread compares wall_clock64() with the deadline and publishes the verdict through LDS -- wavefronts that
+// read the clock themselves could disagree across the deadline and part ways at a barrier.  An expired clock ends the
+// loop as max_iter does (which wins when both hold): the approximate test, then OSQP_TIME_LIMIT_REACHED.
+template <int NT, bool SINGLE_PASS, bool CLOCK = false, class K>
 __device__ __forceinline__ bool admm_loop(const BL &s, const BPattern &p, const BSettings &st, const BIO &io, long long qp,
-                                          BA &a, int iter0, K &eng, BDbg &dbg) {
+                                          BA &a, int iter0, K &eng, BDbg &dbg, unsigned long long *clk = nullptr) {
   constexpr int NW = NT / 64;
   const int n = p.n, m = p.m, tid = threadIdx.x;
   const double alpha = st.alpha, oma = 1.0 - st.alpha, sigma = st.sigma;
@@ -371,8 +383,10 @@ __device__ __forceinline__ bool admm_loop(const BL &s, const BPattern &p, const 
   // (set to 0 by osqp_setup and by reset_info in every osqp_update_*, src/auxil.c:632-649)
   int &iter = a.iter, &rho_updates = a.rho_updates;
   iter = iter0; rho_updates = (int)io.info[qp * 8 + 5];
+  a.end_iter = st.max_iter;
   int stage = 0, probe_until = 0;
   bool norms_fresh = false;
+  bool cut = false;        // (CLOCK) the clock ended the loop
 
   while (stage != 3) {
     int flags = 0;
@@ -452,6 +466,17 @@ __device__ __forceinline__ bool admm_loop(const BL &s, const BPattern &p, const 
     if (flags & F_STATUS) term = check_termination<NT>(s, p, st, a.cs, flags & F_APPROX);
     if (stage == 0) {
       if (checked && term) { stage = 3; continue; }
+      if constexpr (CLOCK) {
+        if (checked || (!st.check_termination && iter % BATCH_CLOCK_INTERVAL == 0)) {
+          // the deadline is loaded here, not before the loop: it holds no register across the K solve
+          if (tid == 0) s.red[S_EXPIRED] = wall_clock64() >= *(volatile unsigned long long *)(clk + CK_DEADLINE) ? 1.0 : 0.0;
+          __syncthreads();
+          if (s.red[S_EXPIRED] != 0.0 && iter < a.end_iter) {
+            a.end_iter = iter; cut = true;
+            if (tid == 0) atomicAdd(clk + CK_CUT, 1ULL);
+          }
+        }
+      }
       if (adapt_due) {     // adapt_rho (auxil.c:13-74)
         const double rn = rho_estimate(sc, m, rho);
         if (rn > rho * st.adapt_tol || rn < rho / st.adapt_tol) {
@@ -462,10 +487,10 @@ __device__ __forceinline__ bool admm_loop(const BL &s, const BPattern &p, const 
           eng.rho_moved(s, p, st, a);
         }
       }
-      if (iter >= st.max_iter) stage = checked ? 2 : 1;
+      if (iter >= a.end_iter) stage = checked ? 2 : 1;
     } else if (stage == 1) stage = term ? 3 : 2;
     else {
-      if (!term && tid == 0) sc[S_STATUS] = OSQP_MAX_ITER_REACHED;
+      if (!term && tid == 0) sc[S_STATUS] = (CLOCK && cut) ? OSQP_TIME_LIMIT_REACHED : OSQP_MAX_ITER_REACHED;
       __syncthreads();
       stage = 3;
     }

@@ -393,7 +393,8 @@ __global__ void __launch_bounds__(256) k_bc_gemm(const double *__restrict__ Kinv
 // check and adaptation points: one workgroup per running column, its member's vectors in LDS, batch_admm.h's code.
 // checked / adapt: what admm_loop does after iteration `iter` (check_termination, then the rho estimate of a member
 // that goes on).  final: the solve ends here (iter >= max_iter; the host has dealt with rho): the stage machine's
-// tail -- the exact test unless `checked` already made it, then the approximate one, then OSQP_MAX_ITER_REACHED.
+// tail -- the exact test unless `checked` already made it, then the approximate one, then OSQP_MAX_ITER_REACHED;
+// final = 2: the same where the host's clock ended the solve (bc_solve), with OSQP_TIME_LIMIT_REACHED.
 // A member that finishes stores its solution (store_solution), sets done, est = -1 and counts itself.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(BS_NT) k_bc_check(BPattern p, BSettings st, BIO io, BCT t, int NP, double rho, int iter,
@@ -423,7 +424,7 @@ __global__ void __launch_bounds__(BS_NT) k_bc_check(BPattern p, BSettings st, BI
   } else {
     if (!checked) fin = check_termination<BS_NT>(s, p, st, a.cs, false);
     if (!fin && !check_termination<BS_NT>(s, p, st, a.cs, true)) {
-      if (tid == 0) sc[S_STATUS] = OSQP_MAX_ITER_REACHED;
+      if (tid == 0) sc[S_STATUS] = final == 2 ? OSQP_TIME_LIMIT_REACHED : OSQP_MAX_ITER_REACHED;
       __syncthreads();
     }
     fin = true;

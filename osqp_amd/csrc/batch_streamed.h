@@ -171,9 +171,10 @@ __global__ void __launch_bounds__(BS_NTI) k_bs_invert(int n, BIO io, int NP, con
 // the ADMM loop with K^-1 streamed from HBM
 // ---------------------------------------------------------------------------
 // A rho move cannot be followed inside the kernel (K is re-formed and re-inverted by kernels of their own): before
-// max_iter the member saves its scaled iterates, counters and rho, sets io.flag = BF_REBUILD | (refinement
-// verdict), appends itself to rb_list (rb_count) and leaves; at max_iter no further solve with K follows, so it
-// finishes and the rebuild is left to the host's last pass.
+// the loop's last iteration the member saves its scaled iterates, counters and rho, sets io.flag = BF_REBUILD |
+// (refinement verdict), appends itself to rb_list (rb_count) and leaves; in the last iteration (BA::end_iter: max_iter,
+// or the clock of a solve with a time limit) no further solve with K follows, so it finishes and the rebuild is left
+// to the host's last pass.
 struct StreamedK {
   const double *Wk;
   int NP, n;
@@ -181,7 +182,7 @@ struct StreamedK {
   bool rebuild_due;
   __device__ __forceinline__ void solve(const BL &, const double *in, double *out) const { bs_gemv(Wk, NP, n, in, out); }
   __device__ __forceinline__ bool leave(const BL &s, const BPattern &p, const BSettings &st, const BIO &io, long long qp, const BA &a) const {
-    if (a.iter >= st.max_iter) return false;
+    if (a.iter >= a.end_iter) return false;
     const int m = p.m, tid = threadIdx.x;
     for (int j = tid; j < n; j += BS_NT) io.Xs[qp * n + j] = s_x[j];
     for (int i = tid; i < m; i += BS_NT) { io.Zs[qp * m + i] = s_z[i]; io.Ys[qp * m + i] = s_y[i]; }
@@ -197,9 +198,11 @@ struct StreamedK {
 
 // list == nullptr: the first round, over the whole batch (in io.order when set), from the stored iterates
 // when warm starting; otherwise a resumed round over list[0..gridDim.x): the members continue from the state
-// they saved when their rho moved.
+// they saved when their rho moved.  CLOCK: a solve with a time limit (admm_loop), clk the handle's clock words; the
+// deadline persists across rounds, so a resumed member meets it at its next clock iteration.
+template <bool CLOCK>
 __global__ void __launch_bounds__(BS_NT) k_bs_loop(BPattern p, BSettings st, BIO io, int NP, const int *list,
-                                                   int *rb_count, int *rb_list) {
+                                                   int *rb_count, int *rb_list, unsigned long long *clk) {
   const bool resume = list != nullptr;
   const long long qp = resume ? list[blockIdx.x] : (io.order ? io.order[blockIdx.x] : (int)blockIdx.x);
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -214,7 +217,7 @@ __global__ void __launch_bounds__(BS_NT) k_bs_loop(BPattern p, BSettings st, BIO
   const int qflag = io.flag[qp];
   a.need_refine = (qflag & BF_REFINE) != 0;
   a.check_pending = (qflag & BF_OPEN) != 0;
-  if (admm_loop<BS_NT, false>(s, p, st, io, qp, a, resume ? (int)io.info[qp * 8] : 0, eng, dbg)) return;
+  if (admm_loop<BS_NT, false, CLOCK>(s, p, st, io, qp, a, resume ? (int)io.info[qp * 8] : 0, eng, dbg, clk)) return;
   // a rebuild left for after the loop drops the refinement verdict, as the tiled engine's in-loop rebuild does
   store_solution<BS_NT>(s, p, st, io, qp, a, eng.rebuild_due ? BF_REBUILD : (a.check_pending ? BF_OPEN : (a.need_refine ? BF_REFINE : 0)));
   if (threadIdx.x == 0) io.rho_io[qp] = a.rho;
