@@ -116,6 +116,31 @@ def _p(a):
     return C.cast(None, abi.c_float_p) if a is None else abi.fptr(a)
 
 
+def _ip(a):
+    return C.cast(None, abi.c_int_p) if a is None else abi.iptr(a)
+
+
+def _shape(a):
+    return tuple(a.__cuda_array_interface__["shape"])
+
+
+def _outputs(R, D, **cols):
+    """The float outputs of a derivative call, zeroed: name -> [R, D, max(k, 1)], or None where k is None (not asked for)."""
+    return {name: None if k is None else np.zeros((R, D, max(k, 1))) for name, k in cols.items()}
+
+
+def _trim(a, k, flat):
+    """An output of _outputs as the caller gets it: its k columns, [R, k] for the flat form of the call."""
+    return None if a is None else (a[:, 0, :k] if flat else a[:, :, :k])
+
+
+def _info_columns(out, info):
+    for k, name in enumerate(INFO_FIELDS):
+        col = info[:, k]
+        setattr(out, name, col.astype(np.int64) if name in ("iter", "status_val", "rho_updates") else col)
+    return out
+
+
 def is_device(a):
     """True for an object that says where it lives in HBM (`__cuda_array_interface__`: a torch CUDA tensor that needs no
     gradient, a cupy array, an object of the caller's own)."""
@@ -490,10 +515,7 @@ class BatchOSQP:
                           r.info.rho_estimate, s.settings().rho] for r, s in zip(rs, self._many)], dtype=np.float64)
         out = SimpleNamespace(x=X, y=Y, dual_inf_cert=np.array([r.dual_inf_cert for r in rs]),
                               prim_inf_cert=np.array([r.prim_inf_cert for r in rs]).reshape(self.B, self.m), info_raw=info)
-        for k, name in enumerate(INFO_FIELDS):
-            col = info[:, k]
-            setattr(out, name, col.astype(np.int64) if name in ("iter", "status_val", "rho_updates") else col)
-        return out
+        return _info_columns(out, info)
 
     def _route(self, **arrays):
         route = io_route(**arrays)
@@ -528,6 +550,26 @@ class BatchOSQP:
             raise RuntimeError("osqp_amd_batch_solved_members failed (%d)" % rc)
         return out != 0
 
+    def _entry(self, name, mem=None, dev=False):
+        """The C entry of a call in the form asked for -- osqp_amd_batch_<name>[_members][_dev] -- as (its name, the
+        function, the arguments that follow the handle: the list and its length for a members= call)."""
+        call = "osqp_amd_batch_%s%s%s" % (name, "" if mem is None else "_members", "_dev" if dev else "")
+        return call, getattr(self._lib, call), () if mem is None else (abi.iptr(mem), int(mem.size))
+
+    def _given(self, dev, mem, want, *arrays):
+        """The given arrays of update / warm_start, each (a, k, name, view), are [R, k] -- R = B, or the number of listed
+        members --, or ValueError(want).  Returns them as the C side takes them: contiguous float64 on the host route,
+        device pointers on the device route (None where view is False: an array the call does not read)."""
+        R = self.B if mem is None else int(mem.size)
+        if dev:
+            if mem is not None and any(a is not None and _shape(a) != (R, k) for a, k, _, _ in arrays):
+                raise ValueError(want)               # (the whole-batch form leaves the shape to device_view's own words)
+            return [self._dev(a, k, name, rows=R) if view else None for a, k, name, view in arrays]
+        out = [None if a is None else abi.as_f64(a) for a, _, _, _ in arrays]
+        if any(a is not None and a.shape != (R, k) for a, (_, k, _, _) in zip(out, arrays)):
+            raise ValueError(want)
+        return out
+
     def update(self, Q=None, L=None, U=None, members=None):
         """osqp_update_lin_cost / _bounds for every QP (None = keep).  Host arrays, or device arrays (objects with
         `__cuda_array_interface__`, complete when the call is made): those are clamped, checked and scaled on the device.
@@ -535,43 +577,22 @@ class BatchOSQP:
         arrays Q [count, n], L, U [count, m], row k for the k-th listed member; the others keep their data, their results
         and their solved flag (solved_members).  engine="common": returns 1, with nothing changed, when a listed member's
         new bounds would give a row another class than the batch holds for it."""
-        if members is not None:
-            return self._update_members(self._members(members, "update"), Q, L, U)
-        if self._route(Q=Q, L=L, U=U) == "device":
-            return int(self._lib.osqp_amd_batch_update_dev(self._h, self._dev(Q, self.n, "Q"), self._dev(L, self.m, "L"),
-                                                           self._dev(U, self.m, "U")))
-        Q = None if Q is None else abi.as_f64(Q)
-        L = None if L is None else np.maximum(abi.as_f64(L), -abi.OSQP_INFTY)
-        U = None if U is None else np.minimum(abi.as_f64(U), abi.OSQP_INFTY)
-        if (Q is not None and Q.shape != (self.B, self.n)) or (L is not None and L.shape != (self.B, self.m)) or \
-           (U is not None and U.shape != (self.B, self.m)):
-            raise ValueError("update arrays must be Q [B, n], L [B, m], U [B, m]")
-        if L is not None and U is not None and np.any(L > U):
-            raise ValueError("lower bound greater than upper bound")
-        if self._many is not None:
-            return self._many_update(Q, L, U)
-        return int(self._lib.osqp_amd_batch_update(self._h, _p(Q), _p(L), _p(U)))
-
-    def _update_members(self, mem, Q, L, U):
-        R, n, m = int(mem.size), self.n, self.m
-        want = "update arrays with members= must be compact: Q [%d, %d], L [%d, %d], U [%d, %d] for the %d listed members" \
-               % (R, n, R, m, R, m, R)
-        if self._route(Q=Q, L=L, U=U) == "device":
-            for a, k in ((Q, n), (L, m), (U, m)):
-                if a is not None and tuple(a.__cuda_array_interface__["shape"]) != (R, k):
-                    raise ValueError(want)
-            return int(self._lib.osqp_amd_batch_update_members_dev(
-                self._h, abi.iptr(mem), R, self._dev(Q, n, "Q", rows=R), self._dev(L, m, "L", rows=R),
-                self._dev(U, m, "U", rows=R)))
-        Q = None if Q is None else abi.as_f64(Q)
-        L = None if L is None else np.maximum(abi.as_f64(L), -abi.OSQP_INFTY)
-        U = None if U is None else np.minimum(abi.as_f64(U), abi.OSQP_INFTY)
-        if (Q is not None and Q.shape != (R, n)) or (L is not None and L.shape != (R, m)) or \
-           (U is not None and U.shape != (R, m)):
-            raise ValueError(want)
-        if L is not None and U is not None and np.any(L > U):
-            raise ValueError("lower bound greater than upper bound")
-        return int(self._lib.osqp_amd_batch_update_members(self._h, abi.iptr(mem), R, _p(Q), _p(L), _p(U)))
+        mem = None if members is None else self._members(members, "update")
+        n, m = self.n, self.m
+        want = "update arrays must be Q [B, n], L [B, m], U [B, m]" if mem is None else \
+               "update arrays with members= must be compact: Q [%d, %d], L [%d, %d], U [%d, %d] for the %d listed members" \
+               % (mem.size, n, mem.size, m, mem.size, m, mem.size)
+        dev = self._route(Q=Q, L=L, U=U) == "device"
+        Q, L, U = self._given(dev, mem, want, (Q, n, "Q", True), (L, m, "L", True), (U, m, "U", True))
+        if not dev:
+            L = None if L is None else np.maximum(L, -abi.OSQP_INFTY)
+            U = None if U is None else np.minimum(U, abi.OSQP_INFTY)
+            if L is not None and U is not None and np.any(L > U):
+                raise ValueError("lower bound greater than upper bound")
+            if self._many is not None:
+                return self._many_update(Q, L, U)
+        _, f, lead = self._entry("update", mem, dev)
+        return int(f(self._h, *lead, *((Q, L, U) if dev else (_p(Q), _p(L), _p(U)))))
 
     def _many_each(self, call):
         # as _many_update: the first failing member's code comes back
@@ -598,23 +619,20 @@ class BatchOSQP:
         if self._many is not None:
             return self._many_each(lambda b, s: s.update(Px=None if Px is None else (Px[b] if pper else Px), Px_idx=Px_idx,
                                                          Ax=None if Ax is None else (Ax[b] if aper else Ax), Ax_idx=Ax_idx))
-        ip = lambda a: C.cast(None, abi.c_int_p) if a is None else abi.iptr(a)
         return int(self._lib.osqp_amd_batch_update_matrices(
-            self._h, _p(Px), ip(Px_idx), 0 if Px is None else Px.shape[-1], pper,
-            _p(Ax), ip(Ax_idx), 0 if Ax is None else Ax.shape[-1], aper))
+            self._h, _p(Px), _ip(Px_idx), 0 if Px is None else Px.shape[-1], pper,
+            _p(Ax), _ip(Ax_idx), 0 if Ax is None else Ax.shape[-1], aper))
 
     def _update_matrices_dev(self, Px, Px_idx, Ax, Ax_idx):
         Px, Px_idx, pper, Ax, Ax_idx, aper = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
-        shp = lambda a: tuple(a.__cuda_array_interface__["shape"])
-        ip = lambda a: C.cast(None, abi.c_int_p) if a is None else abi.iptr(a)
         # (a pointer of 0: nothing to write; NULL = keep says the same)
-        pP = None if Px is None else device_view(Px, shp(Px), "<f8", name="Px") or None
-        pA = None if Ax is None else device_view(Ax, shp(Ax), "<f8", name="Ax") or None
+        pP = None if Px is None else device_view(Px, _shape(Px), "<f8", name="Px") or None
+        pA = None if Ax is None else device_view(Ax, _shape(Ax), "<f8", name="Ax") or None
         if pP is None and pA is None:
             return 0
         return int(self._lib.osqp_amd_batch_update_matrices_dev(
-            self._h, pP, ip(Px_idx), 0 if Px is None else shp(Px)[-1], pper,
-            pA, ip(Ax_idx), 0 if Ax is None else shp(Ax)[-1], aper))
+            self._h, pP, _ip(Px_idx), 0 if Px is None else _shape(Px)[-1], pper,
+            pA, _ip(Ax_idx), 0 if Ax is None else _shape(Ax)[-1], aper))
 
     def update_model(self, Px=None, Px_idx=None, Ax=None, Ax_idx=None):
         """New values for the shared model of a common-K handle (osqp_amd_batch_common_update_model): osqp_update_P / _A /
@@ -634,17 +652,15 @@ class BatchOSQP:
                                  "[B, k]" % name)
         dev = self._route(Px=Px, Ax=Ax) == "device"
         Px, Px_idx, _, Ax, Ax_idx, _ = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
-        ip = lambda a: C.cast(None, abi.c_int_p) if a is None else abi.iptr(a)
         if dev:
-            shp = lambda a: tuple(a.__cuda_array_interface__["shape"])
             # (a pointer of 0: nothing to write; NULL = keep says the same)
-            vals = [None if V is None else device_view(V, shp(V), "<f8", name=nm) or None for nm, V in (("Px", Px), ("Ax", Ax))]
-            cnt = [0 if V is None else shp(V)[0] for V in (Px, Ax)]
+            vals = [None if V is None else device_view(V, _shape(V), "<f8", name=nm) or None for nm, V in (("Px", Px), ("Ax", Ax))]
+            cnt = [0 if V is None else _shape(V)[0] for V in (Px, Ax)]
             call = self._lib.osqp_amd_batch_common_update_model_dev
         else:
             vals, cnt = [_p(Px), _p(Ax)], [0 if V is None else V.shape[0] for V in (Px, Ax)]
             call = self._lib.osqp_amd_batch_common_update_model
-        rc = int(call(self._h, vals[0], ip(Px_idx), cnt[0], vals[1], ip(Ax_idx), cnt[1]))
+        rc = int(call(self._h, vals[0], _ip(Px_idx), cnt[0], vals[1], _ip(Ax_idx), cnt[1]))
         if rc == 5 and self._shared_kkt:                 # did the shared pieces go?  (NULL outputs: nothing is copied)
             no_i, no_f = C.cast(None, abi.c_int_p), C.cast(None, abi.c_float_p)
             self._shared_kkt = self._lib.osqp_amd_batch_common_kkt_peek(self._h, no_f, no_f, 0, no_i, no_i, no_f) == 0
@@ -669,32 +685,18 @@ class BatchOSQP:
         """osqp_warm_start (_x, _y) for every QP: X [B, n], Y [B, m], unscaled; turns the warm_start setting on.  Host
         arrays or device arrays.  members=: for the listed members only, X [count, n], Y [count, m]; the others keep their
         iterates and their solved flag."""
-        if members is not None:
-            mem = self._members(members, "warm_start")
-            R, n, m = int(mem.size), self.n, self.m
-            want = "warm start arrays with members= must be compact: X [%d, %d], Y [%d, %d] for the %d listed members" \
-                   % (R, n, R, m, R)
-            if self._route(X=X, Y=Y) == "device":
-                for a, k in ((X, n), (Y, m)):
-                    if a is not None and tuple(a.__cuda_array_interface__["shape"]) != (R, k):
-                        raise ValueError(want)
-                return int(self._lib.osqp_amd_batch_warm_start_members_dev(
-                    self._h, abi.iptr(mem), R, self._dev(X, n, "X", rows=R), self._dev(Y, m, "Y", rows=R) if m else None))
-            X = None if X is None else abi.as_f64(X)
-            Y = None if Y is None else abi.as_f64(Y)
-            if (X is not None and X.shape != (R, n)) or (Y is not None and Y.shape != (R, m)):
-                raise ValueError(want)
-            return int(self._lib.osqp_amd_batch_warm_start_members(self._h, abi.iptr(mem), R, _p(X), _p(Y if m else None)))
-        if self._route(X=X, Y=Y) == "device":
-            return int(self._lib.osqp_amd_batch_warm_start_dev(self._h, self._dev(X, self.n, "X"),
-                                                               self._dev(Y, self.m, "Y") if self.m else None))
-        X = None if X is None else abi.as_f64(X)
-        Y = None if Y is None else abi.as_f64(Y)
-        if (X is not None and X.shape != (self.B, self.n)) or (Y is not None and Y.shape != (self.B, self.m)):
-            raise ValueError("warm start arrays must be X [B, n], Y [B, m]")
-        if self._many is not None:
-            return self._many_each(lambda b, s: s.warm_start(x=None if X is None else X[b], y=None if Y is None else Y[b]))
-        return int(self._lib.osqp_amd_batch_warm_start(self._h, _p(X), _p(Y if self.m else None)))
+        mem = None if members is None else self._members(members, "warm_start")
+        n, m = self.n, self.m
+        want = "warm start arrays must be X [B, n], Y [B, m]" if mem is None else \
+               "warm start arrays with members= must be compact: X [%d, %d], Y [%d, %d] for the %d listed members" \
+               % (mem.size, n, mem.size, m, mem.size)
+        dev = self._route(X=X, Y=Y) == "device"
+        X, Y = self._given(dev, mem, want, (X, n, "X", True), (Y, m, "Y", bool(m)))
+        if not dev:
+            if self._many is not None:
+                return self._many_each(lambda b, s: s.warm_start(x=None if X is None else X[b], y=None if Y is None else Y[b]))
+        _, f, lead = self._entry("warm_start", mem, dev)
+        return int(f(self._h, *lead, *((X, Y) if dev else (_p(X), _p(Y if m else None)))))
 
     def solve(self, fetch=True, members=None, max_iter=None, time_limit=None):
         """osqp_solve for every member, or (engine="common" only) for the listed ones: members is a strictly ascending
@@ -824,63 +826,46 @@ class BatchOSQP:
         [count, D, .], and the KKT inversion is built for the listed members alone (and shared by later members= calls
         with the same list)."""
         self._unserved("adjoint")
-        if members is not None:
-            return self._adjoint_members(self._members(members, "adjoint"), dX, dY, matrices)
+        mem = None if members is None else self._members(members, "adjoint")
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): adjoint is a call of the batch "
                                "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
-        B, n, m, nP, nA = self.B, self.n, self.m, self.Pu.nnz, self.Ah.nnz
-        flat = np.ndim(dX) != 3       # [B, n] takes the single-cotangent entry point, [B, D, n] the _multi one
-        if flat:
-            dX, dY = check_adjoint(B, n, m, dX, dY)
-            D, call, lead = 1, "osqp_amd_batch_adjoint", ()
-        else:
-            dX, dY, D = check_adjoint_multi(B, n, m, dX, dY)
-            call, lead = "osqp_amd_batch_adjoint_multi", (D,)
-        dq = np.zeros((B, D, n)); dl = np.zeros((B, D, max(m, 1))); du = np.zeros((B, D, max(m, 1)))
-        dPx = np.zeros((B, D, max(nP, 1))) if matrices else None
-        dAx = np.zeros((B, D, max(nA, 1))) if matrices else None
-        act = np.zeros((B, max(m, 1)), np.int64); sa = np.zeros(B, np.int64)
-        rc = getattr(self._lib, call)(self._h, *lead, abi.fptr(dX), _p(dY if m else None), abi.fptr(dq), abi.fptr(dl),
-                                      abi.fptr(du), _p(dPx), _p(dAx), abi.iptr(act), abi.iptr(sa))
+        R, n, m, nP, nA = self._rows(mem), self.n, self.m, self.Pu.nnz, self.Ah.nnz
+        flat = np.ndim(dX) != 3       # whole batch: [B, n] takes the single-cotangent entry point, [B, D, n] the _multi one
+        try:
+            dX, dY, D = check_adjoint(R, n, m, dX, dY) + (1,) if flat else check_adjoint_multi(R, n, m, dX, dY)
+        except ValueError as e:
+            raise self._compact(e, mem) from None
+        o = _outputs(R, D, dq=n, dl=m, du=m, dPx=nP if matrices else None, dAx=nA if matrices else None)
+        act = np.zeros((R, max(m, 1)), np.int64); sa = np.zeros(R, np.int64)
+        call, f, lead = self._entry("adjoint" if flat or mem is not None else "adjoint_multi", mem)
+        if mem is not None or not flat:
+            lead += (D,)
+        rc = f(self._h, *lead, abi.fptr(dX), _p(dY if m else None), abi.fptr(o["dq"]), abi.fptr(o["dl"]), abi.fptr(o["du"]),
+               _p(o["dPx"]), _p(o["dAx"]), abi.iptr(act), abi.iptr(sa))
         if rc:
-            raise RuntimeError("%s failed (%d)%s" % (call, rc, ": no solve has run on the current problem" if rc == 7 else ""))
-        cut = lambda a, k: None if a is None else (a[:, 0, :k] if flat else a[:, :, :k])
-        return SimpleNamespace(dq=cut(dq, n), dl=cut(dl, m), du=cut(du, m), dPx=cut(dPx, nP), dAx=cut(dAx, nA),
-                               active=act[:, :m], status_adjoint=sa)
+            raise RuntimeError("%s failed (%d)%s" % (call, rc, self._unsolved(mem) if rc == 7 else ""))
+        return SimpleNamespace(dq=_trim(o["dq"], n, flat), dl=_trim(o["dl"], m, flat), du=_trim(o["du"], m, flat),
+                               dPx=_trim(o["dPx"], nP, flat), dAx=_trim(o["dAx"], nA, flat), active=act[:, :m],
+                               status_adjoint=sa)
+
+    def _rows(self, mem):
+        """The rows of a call's per-member arrays: B, or the number of listed members."""
+        return self.B if mem is None else int(mem.size)
 
     @staticmethod
-    def _compact(e, B, R):
-        """The message of a shape check made with R rows, worded for a members= call."""
+    def _unsolved(mem):
+        """What return code 7 of polish, adjoint and tangent says."""
+        return ": no solve has run on the current problem" if mem is None else \
+               ": a listed member has not been solved on the current problem"
+
+    def _compact(self, e, mem):
+        """The error of a shape check made with the rows of the call, worded for a members= call where it is one."""
+        if mem is None:
+            return e
+        R = int(mem.size)
         return ValueError("with members= the arrays are compact (%d listed members): %s"
                           % (R, str(e).replace("B = %d" % R, "count = %d" % R).replace("[B,", "[count,")))
-
-    def _adjoint_members(self, mem, dX, dY, matrices):
-        R, n, m, nP, nA = int(mem.size), self.n, self.m, self.Pu.nnz, self.Ah.nnz
-        flat = np.ndim(dX) != 3
-        try:
-            if flat:
-                dX, dY = check_adjoint(R, n, m, dX, dY)
-                dX = dX[:, None, :]; dY = None if dY is None else dY[:, None, :]
-                D = 1
-            else:
-                dX, dY, D = check_adjoint_multi(R, n, m, dX, dY)
-        except ValueError as e:
-            raise self._compact(e, self.B, R) from None
-        dX = abi.as_f64(dX); dY = None if dY is None else abi.as_f64(dY)
-        dq = np.zeros((R, D, n)); dl = np.zeros((R, D, max(m, 1))); du = np.zeros((R, D, max(m, 1)))
-        dPx = np.zeros((R, D, max(nP, 1))) if matrices else None
-        dAx = np.zeros((R, D, max(nA, 1))) if matrices else None
-        act = np.zeros((R, max(m, 1)), np.int64); sa = np.zeros(R, np.int64)
-        rc = self._lib.osqp_amd_batch_adjoint_members(self._h, abi.iptr(mem), R, D, abi.fptr(dX), _p(dY if m else None),
-                                                      abi.fptr(dq), abi.fptr(dl), abi.fptr(du), _p(dPx), _p(dAx),
-                                                      abi.iptr(act), abi.iptr(sa))
-        if rc:
-            raise RuntimeError("osqp_amd_batch_adjoint_members failed (%d)%s"
-                               % (rc, ": a listed member has not been solved on the current problem" if rc == 7 else ""))
-        cut = lambda a, k: None if a is None else (a[:, 0, :k] if flat else a[:, :, :k])
-        return SimpleNamespace(dq=cut(dq, n), dl=cut(dl, m), du=cut(du, m), dPx=cut(dPx, nP), dAx=cut(dAx, nA),
-                               active=act[:, :m], status_adjoint=sa)
 
     def kkt_info(self):
         """For the tests and tools: (builds, kept, npol, members) -- passes of KKT formation and inversion over the solved
@@ -908,77 +893,47 @@ class BatchOSQP:
         setup or the last update.
         members=: for the listed members only, as adjoint(members=): compact arrays, [count, k] or [count, D, k]."""
         self._unserved("tangent")
-        if members is not None:
-            mem = self._members(members, "tangent")
-            R, n, m = int(mem.size), self.n, self.m
-            try:
-                dQ, dL, dU, dPx, dAx, D, flat = check_tangent(R, n, m, self.Pu.nnz, self.Ah.nnz, dQ, dL, dU, dPx, dAx)
-            except ValueError as e:
-                raise self._compact(e, self.B, R) from None
-            dx = np.zeros((R, D, n)); dy = np.zeros((R, D, max(m, 1)))
-            act = np.zeros((R, max(m, 1)), np.int64); st = np.zeros(R, np.int64)
-            rc = self._lib.osqp_amd_batch_tangent_members(
-                self._h, abi.iptr(mem), R, D, _p(dQ), _p(dL if m else None), _p(dU if m else None), _p(dPx), _p(dAx),
-                abi.fptr(dx), _p(dy if m else None), abi.iptr(act), abi.iptr(st))
-            if rc:
-                raise RuntimeError("osqp_amd_batch_tangent_members failed (%d)%s"
-                                   % (rc, ": a listed member has not been solved on the current problem" if rc == 7 else ""))
-            dy = dy[:, :, :m]
-            return SimpleNamespace(dx=dx[:, 0] if flat else dx, dy=dy[:, 0] if flat else dy, active=act[:, :m],
-                                   status_tangent=st)
+        mem = None if members is None else self._members(members, "tangent")
         if self._many is not None:
             raise RuntimeError("this batch runs one single-QP engine per member (n > %d): tangent is a call of the batch "
                                "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
-        B, n, m = self.B, self.n, self.m
-        dQ, dL, dU, dPx, dAx, D, flat = check_tangent(B, n, m, self.Pu.nnz, self.Ah.nnz, dQ, dL, dU, dPx, dAx)
-        dx = np.zeros((B, D, n)); dy = np.zeros((B, D, max(m, 1)))
-        act = np.zeros((B, max(m, 1)), np.int64); st = np.zeros(B, np.int64)
-        rc = self._lib.osqp_amd_batch_tangent(self._h, D, _p(dQ), _p(dL if m else None), _p(dU if m else None), _p(dPx),
-                                              _p(dAx), abi.fptr(dx), _p(dy if m else None), abi.iptr(act), abi.iptr(st))
+        R, n, m = self._rows(mem), self.n, self.m
+        try:
+            dQ, dL, dU, dPx, dAx, D, flat = check_tangent(R, n, m, self.Pu.nnz, self.Ah.nnz, dQ, dL, dU, dPx, dAx)
+        except ValueError as e:
+            raise self._compact(e, mem) from None
+        o = _outputs(R, D, dx=n, dy=m)
+        act = np.zeros((R, max(m, 1)), np.int64); st = np.zeros(R, np.int64)
+        call, f, lead = self._entry("tangent", mem)
+        rc = f(self._h, *lead, D, _p(dQ), _p(dL if m else None), _p(dU if m else None), _p(dPx), _p(dAx),
+               abi.fptr(o["dx"]), _p(o["dy"] if m else None), abi.iptr(act), abi.iptr(st))
         if rc:
-            raise RuntimeError("osqp_amd_batch_tangent failed (%d)%s" % (rc, ": no solve has run on the current problem"
-                                                                         if rc == 7 else ""))
-        dy = dy[:, :, :m]
-        return SimpleNamespace(dx=dx[:, 0] if flat else dx, dy=dy[:, 0] if flat else dy, active=act[:, :m], status_tangent=st)
+            raise RuntimeError("%s failed (%d)%s" % (call, rc, self._unsolved(mem) if rc == 7 else ""))
+        return SimpleNamespace(dx=_trim(o["dx"], n, flat), dy=_trim(o["dy"], m, flat), active=act[:, :m], status_tangent=st)
 
     def results(self, members=None):
         """The results of every member, or with members= the compact rows of the listed ones (status_polish: of the last
         whole-batch polish)."""
-        if members is not None:
-            mem = self._members(members, "results")
-            R, n, m = int(mem.size), self.n, self.m
-            X = np.zeros((R, n)); Y = np.zeros((R, max(m, 1)))
-            info = np.zeros((R, 8)); DX = np.zeros((R, n)); DY = np.zeros((R, max(m, 1)))
-            rc = self._lib.osqp_amd_batch_get_members(self._h, abi.iptr(mem), R, abi.fptr(X), _p(Y if m else None),
-                                                      abi.fptr(info), abi.fptr(DX), _p(DY if m else None))
-            if rc:
-                raise RuntimeError("osqp_amd_batch_get_members failed (%d)" % rc)
-            out = SimpleNamespace(x=X, y=Y[:, :m], dual_inf_cert=DX, prim_inf_cert=DY[:, :m], info_raw=info)
-            sp = self._status_polish
-            out.status_polish = sp[mem].copy() if isinstance(sp, np.ndarray) else np.zeros(R, np.int64)
-            for k, name in enumerate(INFO_FIELDS):
-                col = info[:, k]
-                setattr(out, name, col.astype(np.int64) if name in ("iter", "status_val", "rho_updates") else col)
-            return out
+        mem = None if members is None else self._members(members, "results")
         if self._many is not None:
             return self._many_results()
-        X = np.zeros((self.B, self.n)); Y = np.zeros((self.B, max(self.m, 1)))
-        info = np.zeros((self.B, 8)); DX = np.zeros((self.B, self.n)); DY = np.zeros((self.B, max(self.m, 1)))
-        rc = self._lib.osqp_amd_batch_get(self._h, abi.fptr(X), abi.fptr(Y), abi.fptr(info), abi.fptr(DX), abi.fptr(DY))
+        R, n, m = self._rows(mem), self.n, self.m
+        X = np.zeros((R, n)); Y = np.zeros((R, max(m, 1)))
+        info = np.zeros((R, 8)); DX = np.zeros((R, n)); DY = np.zeros((R, max(m, 1)))
+        call, f, lead = self._entry("get", mem)
+        rc = f(self._h, *lead, abi.fptr(X), _p(Y if m else None), abi.fptr(info), abi.fptr(DX), _p(DY if m else None))
         if rc:
-            raise RuntimeError("osqp_amd_batch_get failed (%d)" % rc)
-        out = SimpleNamespace(x=X, y=Y[:, :self.m], dual_inf_cert=DX, prim_inf_cert=DY[:, :self.m], info_raw=info)
-        if isinstance(self._status_polish, str):       # polish(fetch=False) ran: the work is done, the call reports it
+            raise RuntimeError("%s failed (%d)" % (call, rc))
+        out = SimpleNamespace(x=X, y=Y[:, :m], dual_inf_cert=DX, prim_inf_cert=DY[:, :m], info_raw=info)
+        if mem is None and isinstance(self._status_polish, str):   # polish(fetch=False) ran: the work is done, the call reports it
             sp = np.zeros(self.B, np.int64)
             rc = self._lib.osqp_amd_batch_polish(self._h, abi.iptr(sp))
             if rc and rc != 7:
                 raise RuntimeError("osqp_amd_batch_polish failed (%d)" % rc)
             self._status_polish = None if rc else sp       # (7: the problem has changed since; nothing was tried on it)
-        out.status_polish = np.zeros(self.B, np.int64) if self._status_polish is None else self._status_polish.copy()
-        for k, name in enumerate(INFO_FIELDS):
-            col = info[:, k]
-            setattr(out, name, col.astype(np.int64) if name in ("iter", "status_val", "rho_updates") else col)
-        return out
+        sp = self._status_polish
+        out.status_polish = np.zeros(R, np.int64) if not isinstance(sp, np.ndarray) else sp[slice(None) if mem is None else mem].copy()
+        return _info_columns(out, info)
 
     def results_into(self, X=None, Y=None, info=None, DX=None, DY=None, status_polish=None, members=None):
         """The results into device arrays of the caller's (None = skip): X, DX [B, n], Y, DY [B, m], info [B, 8]
@@ -990,22 +945,14 @@ class BatchOSQP:
         if self._route(X=X, Y=Y, info=info, DX=DX, DY=DY, status_polish=status_polish) != "device":
             raise ValueError("results_into writes device arrays (objects with __cuda_array_interface__); results() returns "
                              "host arrays")
-        if members is not None:
-            mem = self._members(members, "results_into")
-            if status_polish is not None:
-                raise ValueError("results_into(members=...) takes no status_polish: it is a [B] array of the whole-batch polish")
-            R = int(mem.size)
-            d = lambda a, cols, name: self._dev(a, cols, name, writable=True, rows=R)
-            rc = self._lib.osqp_amd_batch_get_members_dev(self._h, abi.iptr(mem), R, d(X, self.n, "X"), d(Y, self.m, "Y"),
-                                                          d(info, 8, "info"), d(DX, self.n, "DX"), d(DY, self.m, "DY"))
-            if rc:
-                raise RuntimeError("osqp_amd_batch_get_members_dev failed (%d)%s" % (rc, _BAD_POINTER if rc == 1 else ""))
-            return
-        d = lambda a, cols, name: self._dev(a, cols, name, writable=True)
-        rc = self._lib.osqp_amd_batch_get_dev(self._h, d(X, self.n, "X"), d(Y, self.m, "Y"), d(info, 8, "info"),
-                                              d(DX, self.n, "DX"), d(DY, self.m, "DY"))
+        mem = None if members is None else self._members(members, "results_into")
+        if mem is not None and status_polish is not None:
+            raise ValueError("results_into(members=...) takes no status_polish: it is a [B] array of the whole-batch polish")
+        d = lambda a, cols, name: self._dev(a, cols, name, writable=True, rows=self._rows(mem))
+        call, f, lead = self._entry("get", mem, dev=True)
+        rc = f(self._h, *lead, d(X, self.n, "X"), d(Y, self.m, "Y"), d(info, 8, "info"), d(DX, self.n, "DX"), d(DY, self.m, "DY"))
         if rc:
-            raise RuntimeError("osqp_amd_batch_get_dev failed (%d)%s" % (rc, _BAD_POINTER if rc == 1 else ""))
+            raise RuntimeError("%s failed (%d)%s" % (call, rc, _BAD_POINTER if rc == 1 else ""))
         if status_polish is not None:
             self._unserved("results_into(status_polish=...)")
             rc = self._lib.osqp_amd_batch_polish_status_dev(
@@ -1037,7 +984,7 @@ class BatchOSQP:
             try:
                 dX, dY, D = check_adjoint_multi(B, n, m, dX, dY, dq=(dq, n), dl=(dl, m), du=(du, m), dPx=(dPx, nP), dAx=(dAx, nA))
             except ValueError as e:
-                raise (e if mem is None else self._compact(e, self.B, B)) from None
+                raise self._compact(e, mem) from None
             call, lead = "osqp_amd_batch_adjoint_multi_dev", (D,)
         if mem is not None:
             call, lead = "osqp_amd_batch_adjoint_members_dev", (abi.iptr(mem), B, D)
@@ -1073,7 +1020,7 @@ class BatchOSQP:
         try:
             dQ, dL, dU, dPx, dAx, D, flat = check_tangent(B, n, m, self.Pu.nnz, self.Ah.nnz, dQ, dL, dU, dPx, dAx, dx=dx, dy=dy)
         except ValueError as e:
-            raise (e if mem is None else self._compact(e, self.B, B)) from None
+            raise self._compact(e, mem) from None
 
         def d(a, cols, name, writable=False):
             if a is None:

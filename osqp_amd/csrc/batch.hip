@@ -572,13 +572,36 @@ k_batch_solve(BPattern p, BSettings st, BIO io, unsigned long long *clk) {
   if (tid == 0 && io.rho_io) io.rho_io[qp] = a.rho;
 }
 
+// the clamp of BatchOSQP.update (np.maximum(L, -OSQP_INFTY), np.minimum(U, OSQP_INFTY)); a NaN stays a NaN
+__device__ __forceinline__ double clamp_lower(double v) { return v < -OSQP_INFTY ? -OSQP_INFTY : v; }
+__device__ __forceinline__ double clamp_upper(double v) { return v > OSQP_INFTY ? OSQP_INFTY : v; }
+
+#define BD_NT 256
+#define BD_MAX_BLOCKS 1024
+// *bad += the number of k in [0, cnt) with clamp(L[k]) > clamp(U[k]) (osqp.c:815-822 for every QP).  Grid-stride;
+// the workgroup's count meets in LDS and at most one atomicAdd per workgroup leaves it.
+__global__ void __launch_bounds__(BD_NT) k_batch_check_bounds(long long cnt, const double *L, const double *U, int *bad) {
+  __shared__ int wsum[BD_NT / 64];
+  int c = 0;
+  for (long long k = (long long)blockIdx.x * BD_NT + threadIdx.x; k < cnt; k += (long long)gridDim.x * BD_NT)
+    c += clamp_lower(L[k]) > clamp_upper(U[k]) ? 1 : 0;
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    if (t) atomicAdd(bad, t);
+  }
+}
+
 // osqp_update_lin_cost / osqp_update_bounds for every QP of the batch
 // (src/osqp.c:765-846): new raw vectors are scaled with the stored D, E, c; rows
 // are re-classified and a changed class requests a rebuild of K^-1
 // (update_rho_vec, src/auxil.c:100-142).
-// list (null: every member, Q, L, U are the handle's raw [B][.] arrays): one workgroup per listed member,
-// qp = list[blockIdx.x]; Q, L, U are compact, row blockIdx.x belongs to that member, and the raw row -- clamped to
-// +-OSQP_INFTY where clamp is set, the device route's -- goes into rawQ, rawL, rawU of the member first.
+// One workgroup per member of the call: qp = list[blockIdx.x], or blockIdx.x itself without a list; Q, L, U hold that
+// member's new row at blockIdx.x.  With rawQ, rawL, rawU (every form of osqp_amd_batch_update) the raw row -- clamped to
+// +-OSQP_INFTY where clamp is set, the device route's -- goes into the handle's raw arrays first; without them (setup of
+// the common-K engine) Q, L, U are those arrays.
 __global__ void __launch_bounds__(256) k_batch_update(int n, int m, BIO io, const double *Q, const double *L,
                                                       const double *U, double rho_tol, const int *list, double *rawQ,
                                                       double *rawL, double *rawU, int clamp) {
@@ -590,7 +613,7 @@ __global__ void __launch_bounds__(256) k_batch_update(int n, int m, BIO io, cons
     const double c = io.Wc[qp];
     for (int j = threadIdx.x; j < n; j += blockDim.x) {
       const double v = Q[src * n + j];
-      if (list) rawQ[qp * n + j] = v;
+      if (rawQ) rawQ[qp * n + j] = v;
       io.Wq[qp * n + j] = (v * io.Wd[qp * n + j]) * c;
     }
   }
@@ -598,12 +621,12 @@ __global__ void __launch_bounds__(256) k_batch_update(int n, int m, BIO io, cons
     const double e = io.We[qp * m + i];
     if (L) {
       double v = L[src * m + i];
-      if (list) { if (clamp) v = v < -OSQP_INFTY ? -OSQP_INFTY : v; rawL[qp * m + i] = v; }
+      if (rawL) { if (clamp) v = clamp_lower(v); rawL[qp * m + i] = v; }
       io.Wl[qp * m + i] = v * e;
     }
     if (U) {
       double v = U[src * m + i];
-      if (list) { if (clamp) v = v > OSQP_INFTY ? OSQP_INFTY : v; rawU[qp * m + i] = v; }
+      if (rawU) { if (clamp) v = clamp_upper(v); rawU[qp * m + i] = v; }
       io.Wu[qp * m + i] = v * e;
     }
     if (L || U) {
@@ -793,7 +816,7 @@ struct osqp_amd_batch {
     size_t in_cap = 0, out_cap = 0, mat_cap = 0;   // in doubles
     int *act = nullptr, *stat = nullptr, *piv = nullptr;   // [B][m], [B], [B] (the inversion's verdict)
   } bd;
-  int *d_bad = nullptr;     // device-array updates (batch_devio.h): count of l > u pairs of k_batch_check_bounds
+  int *d_bad = nullptr;     // device-array updates (bounds_cross_dev): count of l > u pairs of k_batch_check_bounds
   // the kept KKT inversion (bd_run): what a one-chunk adjoint / adjoint_multi / tangent call built -- pol.map, rows,
   // mred, nlow, d_plist, the inverses in pol.K and the pivot verdicts -- stays for the later calls on the same solve
   int kkt_cache = 1;        // OSQP_AMD_BATCH_KKT_CACHE (0: every call builds its own)
@@ -843,6 +866,60 @@ static int bupload(osqp_amd_batch *b, const Tp **dst, const std::vector<Tp> &src
 // *p once: a call that follows a failed allocation asks only for what is still missing
 template <typename Tp>
 static int balloc_once(osqp_amd_batch *b, Tp **p, size_t cnt) { return *p ? 0 : balloc(b, p, cnt); }
+
+// The forms of a call: host arrays or device arrays (dev), every member or the listed ones (members, count).  Each call
+// has one body, <name>_call(b, dev, members /*null: every member*/, count, ...); its entry points are wrappers that
+// check the handle and the list and hand a list of all B members on as null, so count == B runs the whole-batch code.
+
+// OSQP_DATA_VALIDATION_ERROR unless p is device memory of the handle's device as this process's HIP runtime knows it:
+// a host pointer, managed or registered host memory, another device's memory and an address of another runtime's
+// allocation (two HIP runtimes mapped side by side) are all refused.  Only asks the runtime; touches no GPU memory.
+static c_int dev_ptr_check(const osqp_amd_batch *b, const void *p) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return OSQP_DATA_VALIDATION_ERROR;
+  }
+  return (at.type == hipMemoryTypeDevice && at.device == b->device) ? 0 : OSQP_DATA_VALIDATION_ERROR;
+}
+static c_int dev_ptrs_check(const osqp_amd_batch *b, std::initializer_list<const void *> ps) {
+  for (const void *p : ps) if (p && dev_ptr_check(b, p)) return OSQP_DATA_VALIDATION_ERROR;
+  return 0;
+}
+
+// a member list: host, `count` in [1, B] indices, strictly ascending, each in [0, B)
+static c_int members_check(const osqp_amd_batch *b, const c_int *members, c_int count) {
+  if (!members || count < 1 || count > b->B) return OSQP_DATA_VALIDATION_ERROR;
+  for (c_int k = 0; k < count; k++)
+    if (members[k] < 0 || members[k] >= b->B || (k && members[k] <= members[k - 1])) return OSQP_DATA_VALIDATION_ERROR;
+  return 0;
+}
+// The list of a _members call on the device: d_mlist[k] = list[k] and, with pos, d_mpos[list[k]] = k.  One upload per
+// call; the wait is for the host vectors.
+static int members_upload(osqp_amd_batch *b, const int *list, size_t count, bool pos) {
+  const size_t B = (size_t)b->B;
+  if (balloc_once(b, &b->d_mlist, B) || balloc_once(b, &b->d_mpos, B)) { (void)hipGetLastError(); return -102; }
+  BCHK(hipMemcpyAsync(b->d_mlist, list, count * sizeof(int), hipMemcpyHostToDevice, b->stream));
+  std::vector<int> at;
+  if (pos) {
+    at.assign(B, 0);
+    for (size_t k = 0; k < count; k++) at[(size_t)list[k]] = (int)k;
+    BCHK(hipMemcpyAsync(b->d_mpos, at.data(), B * sizeof(int), hipMemcpyHostToDevice, b->stream));
+  }
+  BCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+// the list of a call's body on the device (null: nothing to do, the kernels take every member)
+static int members_put(osqp_amd_batch *b, const c_int *members, c_int count) {
+  if (!members) return 0;
+  const std::vector<int> sel(members, members + count);
+  return members_upload(b, sel.data(), sel.size(), false);
+}
+// the solved and polished flags of the members of a call that changes their data or their stored iterates
+static void mark_call_unsolved(osqp_amd_batch *b, const c_int *members, c_int count) {
+  if (members) mark_members_unsolved(b, members, count);
+  else mark_unsolved(b);
+}
 
 // A kernel may use more than 64 KiB of dynamic LDS only after its limit was raised.  The limit is a property of the
 // kernel function on the current device, not of a batch: another handle of another size may have set it to its own,
@@ -1527,31 +1604,64 @@ extern "C" void osqp_amd_batch_cleanup(osqp_amd_batch *b) {
   delete b;
 }
 
-extern "C" c_int osqp_amd_batch_update(osqp_amd_batch *b, const c_float *Q, const c_float *L, const c_float *U) {
-  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+// 1 when some pair of the cnt device pairs has l > u after the clamp to +-OSQP_INFTY, 0 when none has: k_batch_check_bounds
+// and one 4-byte read-back, before anything of the handle is written
+static c_int bounds_cross_dev(osqp_amd_batch *b, const double *L, const double *U, size_t cnt) {
+  if (balloc_once(b, &b->d_bad, 1)) { (void)hipGetLastError(); return OSQP_MEM_ALLOC_ERROR; }
+  int bad = 0;
+  BCHK(hipMemsetAsync(b->d_bad, 0, sizeof(int), b->stream));
+  const unsigned blocks = (unsigned)std::min<size_t>((cnt + BD_NT - 1) / BD_NT, BD_MAX_BLOCKS);
+  hipLaunchKernelGGL(k_batch_check_bounds, dim3(blocks), dim3(BD_NT), 0, b->stream, (long long)cnt, L, U, b->d_bad);
+  BCHK(hipGetLastError());
+  BCHK(hipMemcpyAsync(&bad, b->d_bad, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  BCHK(hipStreamSynchronize(b->stream));
+  return bad ? 1 : 0;
+}
+
+// osqp_amd_batch_update in its four forms; Q, L, U are [R][.], R = count with a list and B without (null = keep).  The
+// rows are read in place on the device route and go through the staging on the host route; k_batch_update writes the
+// raw rows of the call's members (clamped on the device route) and scales them.
+static c_int update_call(osqp_amd_batch *b, bool dev, const c_int *members, c_int count, const c_float *Q, const c_float *L,
+                         const c_float *U) {
   BCHK(hipSetDevice(b->device));
-  const size_t B = (size_t)b->B;
-  if (L && U)
-    for (size_t k = 0; k < B * (size_t)b->m; k++) if (L[k] > U[k]) return 1;   // osqp.c:815-822
-  if (b->engine == OSQP_AMD_BATCH_COMMON && (L || U) && b->m) {   // one class per row over the batch, before any write
-    const size_t cnt = B * (size_t)b->m;
-    if (stage_reserve(b, 2 * cnt, 0)) return OSQP_MEM_ALLOC_ERROR;
-    if (L) BCHK(hipMemcpyAsync(b->d_vals, L, cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (U) BCHK(hipMemcpyAsync(b->d_vals + cnt, U, cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  if (dev && dev_ptrs_check(b, {Q, L, U})) return OSQP_DATA_VALIDATION_ERROR;
+  const size_t R = members ? (size_t)count : (size_t)b->B, n = (size_t)b->n, m = (size_t)b->m, cnt = R * m;
+  if (!m) L = U = nullptr;
+  if (dev && L && U) { if (const c_int rc = bounds_cross_dev(b, L, U, cnt)) return rc; }
+  if (!dev && L && U)
+    for (size_t k = 0; k < cnt; k++) if (L[k] > U[k]) return 1;   // osqp.c:815-822
+  if (members_put(b, members, count)) return OSQP_MEM_ALLOC_ERROR;
+  const int *list = members ? b->d_mlist : nullptr;
+  const double *sQ = Q, *sL = L, *sU = U;
+  if (!dev) {
+    if (stage_reserve(b, (Q ? R * n : 0) + (L ? cnt : 0) + (U ? cnt : 0), 0)) return OSQP_MEM_ALLOC_ERROR;
+    double *at = b->d_vals;
+    for (const double **v : {&sQ, &sL, &sU}) {
+      if (!*v) continue;
+      const size_t len = v == &sQ ? R * n : cnt;
+      BCHK(hipMemcpyAsync(at, *v, len * sizeof(double), hipMemcpyHostToDevice, b->stream));
+      *v = at; at += len;
+    }
+  }
+  // common-K, one class per row over the batch, before any write: a whole-batch update may move a row's class in every
+  // member (the one K^-1 is rebuilt); the unlisted members of a list keep theirs, so the listed ones must too
+  if (b->engine == OSQP_AMD_BATCH_COMMON && (sL || sU)) {
     bool moved = false;
-    if (const int rc = bc_check_classes(b, L ? b->d_vals : nullptr, U ? b->d_vals + cnt : nullptr, 0, &moved, "update")) return rc;
+    if (const int rc = bc_check_classes(b, sL, sU, dev ? 1 : 0, members ? nullptr : &moved, members ? "update_members" : "update",
+                                        members, R, list)) return rc;
     if (moved) b->bc_rebuild = true;
   }
-  mark_unsolved(b);
-  if (Q) BCHK(hipMemcpyAsync(b->dQ, Q, B * b->n * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  if (L) BCHK(hipMemcpyAsync(b->dL, L, B * b->m * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  if (U) BCHK(hipMemcpyAsync(b->dU, U, B * b->m * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  hipLaunchKernelGGL(k_batch_update, dim3((unsigned)B), dim3(256), 0, b->stream, b->n, b->m, b->io,
-                     Q ? b->dQ : nullptr, L ? b->dL : nullptr, U ? b->dU : nullptr, (double)RHO_TOL, (const int *)nullptr,
-                     (double *)nullptr, (double *)nullptr, (double *)nullptr, 0);
+  mark_call_unsolved(b, members, count);
+  hipLaunchKernelGGL(k_batch_update, dim3((unsigned)R), dim3(256), 0, b->stream, b->n, b->m, b->io, sQ, sL, sU, (double)RHO_TOL,
+                     list, b->dQ, b->dL, b->dU, dev ? 1 : 0);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   return 0;
+}
+
+extern "C" c_int osqp_amd_batch_update(osqp_amd_batch *b, const c_float *Q, const c_float *L, const c_float *U) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  return update_call(b, false, nullptr, 0, Q, L, U);
 }
 
 // ---------------------------------------------------------------------------
@@ -1598,11 +1708,11 @@ static int patch_values(osqp_amd_batch *b, double **raw, const double **io_raw, 
   return 0;
 }
 
-extern "C" c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
-                                                const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
-                                                const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
-  BC_NEVER(b, "osqp_amd_batch_update_matrices");
-  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+// osqp_amd_batch_update_matrices, and with dev its _dev twin: the value arrays are device arrays then, the index lists
+// host lists either way
+static c_int update_matrices_call(osqp_amd_batch *b, bool dev,
+                                  const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
+                                  const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
   // nothing is written before every argument has passed (osqp.c:1197-1222; the index range is this project's check)
   if (Px && Px_idx && P_n > b->nnzP) return 1;
   if (Ax && Ax_idx && A_n > b->nnzA) return 2;
@@ -1611,14 +1721,15 @@ extern "C" c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
   if (Ax && Ax_idx) for (c_int k = 0; k < A_n; k++) if (Ax_idx[k] < 0 || Ax_idx[k] >= b->nnzA) return OSQP_DATA_VALIDATION_ERROR;
   if (!Px && !Ax) return 0;
   BCHK(hipSetDevice(b->device));
+  if (dev && dev_ptrs_check(b, {Px, Ax})) return OSQP_DATA_VALIDATION_ERROR;
   mark_unsolved(b);
   const c_int pc = Px ? (Px_idx ? P_n : (c_int)b->nnzP) : 0, ac = Ax ? (Ax_idx ? A_n : (c_int)b->nnzA) : 0;
-  const size_t B = (size_t)b->B;
-  const size_t pv = (size_t)pc * (Px_per_member ? B : 1), av = (size_t)ac * (Ax_per_member ? B : 1);
+  const size_t B = (size_t)b->B;                // (the device route stages the index lists only)
+  const size_t pv = dev ? 0 : (size_t)pc * (Px_per_member ? B : 1), av = dev ? 0 : (size_t)ac * (Ax_per_member ? B : 1);
   if (stage_reserve(b, pv + av, (size_t)pc + ac)) return OSQP_MEM_ALLOC_ERROR;
-  if (Px && patch_values(b, &b->dPx, &b->io.Px, &b->io.strideP, b->nnzP, Px, Px_idx, pc, Px_per_member, 0, 0))
+  if (Px && patch_values(b, &b->dPx, &b->io.Px, &b->io.strideP, b->nnzP, Px, Px_idx, pc, Px_per_member, 0, 0, dev))
     return OSQP_MEM_ALLOC_ERROR;
-  if (Ax && patch_values(b, &b->dAx, &b->io.Ax, &b->io.strideA, b->nnzA, Ax, Ax_idx, ac, Ax_per_member, pv, (size_t)pc))
+  if (Ax && patch_values(b, &b->dAx, &b->io.Ax, &b->io.strideA, b->nnzA, Ax, Ax_idx, ac, Ax_per_member, pv, (size_t)pc, dev))
     return OSQP_MEM_ALLOC_ERROR;
   // re-equilibrate from the raw data, re-form and re-invert K with each member's current rho and classes
   if (b->engine == OSQP_AMD_BATCH_STREAMED) (void)bs_setup_launch(b, true);
@@ -1632,6 +1743,14 @@ extern "C" c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
     return OSQP_NONCVX_ERROR;
   }
   return 0;
+}
+
+extern "C" c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
+                                                const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
+                                                const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
+  BC_NEVER(b, "osqp_amd_batch_update_matrices");
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  return update_matrices_call(b, false, Px, Px_idx, P_n, Px_per_member, Ax, Ax_idx, A_n, Ax_per_member);
 }
 
 extern "C" c_int osqp_amd_batch_update_rho(osqp_amd_batch *b, const c_float *rho, c_int per_member) {
@@ -1659,25 +1778,33 @@ extern "C" c_int osqp_amd_batch_update_rho(osqp_amd_batch *b, const c_float *rho
   return 0;
 }
 
-extern "C" c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, const c_float *Y) {
-  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+// osqp_amd_batch_warm_start in its four forms; X, Y are [R][.], R = count with a list and B without (null = keep)
+static c_int warm_start_call(osqp_amd_batch *b, bool dev, const c_int *members, c_int count, const c_float *X, const c_float *Y) {
+  if (X || Y) BCHK(hipSetDevice(b->device));
+  if (dev && dev_ptrs_check(b, {X, Y})) return OSQP_DATA_VALIDATION_ERROR;
   b->st.warm_start = 1;                          // osqp.c:948
   if (!X && !Y) return 0;
-  BCHK(hipSetDevice(b->device));
-  mark_unsolved(b);                             // the stored iterates are the caller's now, not a solve's
-  const size_t B = (size_t)b->B, nx = X ? B * b->n : 0, ny = Y ? B * b->m : 0;
-  if (stage_reserve(b, nx + ny, 0)) return OSQP_MEM_ALLOC_ERROR;
-  if (nx) BCHK(hipMemcpyAsync(b->d_vals, X, nx * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  if (ny) BCHK(hipMemcpyAsync(b->d_vals + nx, Y, ny * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  if (b->engine == OSQP_AMD_BATCH_COMMON)
-    hipLaunchKernelGGL(k_bc_warm_start, dim3((unsigned)B), dim3(256), 0, b->stream, b->pat, b->io,
-                       X ? b->d_vals : (const double *)nullptr, Y ? b->d_vals + nx : (const double *)nullptr, (const int *)nullptr);
-  else
-    hipLaunchKernelGGL(k_batch_warm_start, dim3((unsigned)B), dim3(256), 0, b->stream, b->pat, b->io,
-                       X ? b->d_vals : (const double *)nullptr, Y ? b->d_vals + nx : (const double *)nullptr, (const int *)nullptr);
+  const size_t R = members ? (size_t)count : (size_t)b->B, nx = X ? R * b->n : 0, ny = Y ? R * b->m : 0;
+  if (members_put(b, members, count)) return OSQP_MEM_ALLOC_ERROR;
+  const int *list = members ? b->d_mlist : nullptr;
+  const double *sX = X, *sY = Y;
+  if (!dev) {
+    if (stage_reserve(b, nx + ny, 0)) return OSQP_MEM_ALLOC_ERROR;
+    if (nx) BCHK(hipMemcpyAsync(b->d_vals, X, nx * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (ny) BCHK(hipMemcpyAsync(b->d_vals + nx, Y, ny * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    sX = X ? b->d_vals : nullptr; sY = Y ? b->d_vals + nx : nullptr;
+  }
+  mark_call_unsolved(b, members, count);         // the stored iterates are the caller's now, not a solve's
+  const auto fn = b->engine == OSQP_AMD_BATCH_COMMON ? k_bc_warm_start : k_batch_warm_start;
+  hipLaunchKernelGGL(fn, dim3((unsigned)R), dim3(256), 0, b->stream, b->pat, b->io, sX, sY, list);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   return 0;
+}
+
+extern "C" c_int osqp_amd_batch_warm_start(osqp_amd_batch *b, const c_float *X, const c_float *Y) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  return warm_start_call(b, false, nullptr, 0, X, Y);
 }
 
 // A solve of all members (members = null) or of `count` chosen ones: what osqp_amd_batch_solve and
@@ -1737,7 +1864,7 @@ extern "C" c_int osqp_amd_batch_solve(osqp_amd_batch *b) {
   return batch_solve_run(b, nullptr, b->B);
 }
 
-// the refusals of a member list given to a solve
+// the refusals of a member list given to a solve: the engine's, then the list's
 static c_int solve_members_check(osqp_amd_batch *b, const c_int *members, c_int count) {
   if (b->engine != OSQP_AMD_BATCH_COMMON) {
     fprintf(stderr, "osqp_amd batch: osqp_amd_batch_solve_members is a call of the common-K engine (OSQP_AMD_BATCH_COMMON); "
@@ -1745,10 +1872,7 @@ static c_int solve_members_check(osqp_amd_batch *b, const c_int *members, c_int 
             b->engine == OSQP_AMD_BATCH_STREAMED ? "streamed" : "tiled");
     return OSQP_LINSYS_SOLVER_INIT_ERROR;
   }
-  if (!members || count < 1 || count > b->B) return OSQP_DATA_VALIDATION_ERROR;
-  for (c_int k = 0; k < count; k++)
-    if (members[k] < 0 || members[k] >= b->B || (k && members[k] <= members[k - 1])) return OSQP_DATA_VALIDATION_ERROR;
-  return 0;
+  return members_check(b, members, count);
 }
 
 extern "C" c_int osqp_amd_batch_solve_members(osqp_amd_batch *b, const c_int *members, c_int count) {
@@ -1904,22 +2028,6 @@ static bool kkt_kept(const osqp_amd_batch *b) {
 static bool kkt_kept_for(const osqp_amd_batch *b, const std::vector<int> *sel) {
   return kkt_kept(b) && (sel ? b->kkt_members == *sel : b->kkt_members.empty());
 }
-// The list of a _members call on the device: d_mlist[k] = list[k] and, with pos, d_mpos[list[k]] = k.  One upload per
-// call; the wait is for the host vectors.
-static int members_upload(osqp_amd_batch *b, const int *list, size_t count, bool pos) {
-  const size_t B = (size_t)b->B;
-  if (balloc_once(b, &b->d_mlist, B) || balloc_once(b, &b->d_mpos, B)) { (void)hipGetLastError(); return -102; }
-  BCHK(hipMemcpyAsync(b->d_mlist, list, count * sizeof(int), hipMemcpyHostToDevice, b->stream));
-  std::vector<int> at;
-  if (pos) {
-    at.assign(B, 0);
-    for (size_t k = 0; k < count; k++) at[(size_t)list[k]] = (int)k;
-    BCHK(hipMemcpyAsync(b->d_mpos, at.data(), B * sizeof(int), hipMemcpyHostToDevice, b->stream));
-  }
-  BCHK(hipStreamSynchronize(b->stream));
-  return 0;
-}
-
 // What adjoint, adjoint_multi and tangent share around their own kernel fn, which third(plan, members, their list)
 // launches with pn.lds bytes of LDS; pl.stat is the call's array of pivot verdicts.  While an inversion is kept,
 // only the verdicts are copied and fn launched.  Otherwise bp_plan and bp_run_chunks as polish runs them; when the
@@ -1976,26 +2084,28 @@ static c_int bp_polish_run(osqp_amd_batch *b, const std::vector<int> *sel) {
   return 0;
 }
 
+// status_polish[k] (null: not asked for) of member members[k], or of member k without a list, as polish left it
+static c_int polish_status_out(osqp_amd_batch *b, const c_int *members, c_int count, c_int *status_polish) {
+  if (!status_polish) return 0;
+  std::vector<int> h((size_t)b->B);
+  BCHK(hipMemcpyAsync(h.data(), b->pol.stat, h.size() * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  BCHK(hipStreamSynchronize(b->stream));
+  for (c_int k = 0; k < count; k++) status_polish[k] = h[(size_t)(members ? members[k] : k)];
+  return 0;
+}
+
 // polish for the solved members, in chunks of at most pol_cap bytes of KKT matrices (batch_polish.h)
 extern "C" c_int osqp_amd_batch_polish(osqp_amd_batch *b, c_int *status_polish) {
   BC_UNSERVED(b, "osqp_amd_batch_polish");
   if (!b || !b->solved) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   BCHK(hipSetDevice(b->device));
-  const size_t B = (size_t)b->B;
-  BPol &pl = b->pol;
   if (bp_reserve_maps(b)) return OSQP_MEM_ALLOC_ERROR;
   if (!b->polished) {       // (a second call without a solve in between finds the work done and reports it again)
     if (const c_int rc = bp_polish_run(b, nullptr)) return rc;
     b->polished = true;
     std::fill(b->member_polished.begin(), b->member_polished.end(), (char)1);
   }
-  if (status_polish) {
-    std::vector<int> h(B);
-    BCHK(hipMemcpyAsync(h.data(), pl.stat, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-    BCHK(hipStreamSynchronize(b->stream));
-    for (size_t q = 0; q < B; q++) status_polish[q] = h[q];
-  }
-  return 0;
+  return polish_status_out(b, nullptr, b->B, status_polish);
 }
 
 // For the tests and tools: builds of the KKT inversion since setup, whether one is kept, its NPOL and its members.
@@ -2113,7 +2223,6 @@ static c_int bc_rebuild_pair(osqp_amd_batch *b, int *kflag) {
 // setup's scale_data on the one-member image (q^, L[0], U[0]) with the classes kept (k_bs_setup<true>), D, E, c for
 // every member (k_bc_spread), every member's scaled q, l, u from its stored raw ones (k_bc_rescale), the one K^-1 with
 // the batch's rho as it stands, and H / Wt where the handle carries them.  dev: Px / Ax are device arrays.
-static c_int dev_ptrs_check(const osqp_amd_batch *b, std::initializer_list<const void *> ps);   // batch_devio.h
 static c_int bc_update_model(osqp_amd_batch *b, bool dev, const char *call, const c_float *Px, const c_int *Px_idx, c_int P_n,
                              const c_float *Ax, const c_int *Ax_idx, c_int A_n) {
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
@@ -2280,7 +2389,6 @@ static c_int bd_deliver(osqp_amd_batch *b, bool dev, std::initializer_list<BDOut
   return 0;
 }
 
-static c_int dev_ptrs_check(const osqp_amd_batch *b, std::initializer_list<const void *> ps);   // batch_devio.h
 
 // adjoint derivatives for the solved members (batch_adjoint.h), ncot cotangents per member: polish's active rows, KKT
 // matrix and inversion on polish's buffers, in the same chunks, one inversion for the ncot cotangents of a member;
@@ -2399,18 +2507,43 @@ extern "C" c_int osqp_amd_batch_tangent_dev(osqp_amd_batch *b, c_int ndir, const
   return tangent_call(b, true, ndir, dQ, dL, dU, dPx, dAx, dX, dY, active, status_tangent);
 }
 
+// osqp_amd_batch_get in its four forms; the arrays are [R][.], R = count with a list and B without (null = not asked
+// for).  Without a list: one copy per array.  With one: k_batch_gather writes the listed rows into the caller's device
+// array, or into the staging, from where one copy per array takes them to the host.
+static c_int get_call(osqp_amd_batch *b, bool dev, const c_int *members, c_int count, c_float *X, c_float *Y, c_float *info8,
+                      c_float *DX, c_float *DY) {
+  BCHK(hipSetDevice(b->device));
+  if (dev && dev_ptrs_check(b, {X, Y, info8, DX, DY})) return OSQP_DATA_VALIDATION_ERROR;
+  const size_t R = members ? (size_t)count : (size_t)b->B, n = (size_t)b->n, m = (size_t)b->m;
+  const struct { c_float *dst; const double *src; size_t width; } rows[] = {
+      {X, b->io.Xo, n}, {Y, b->io.Yo, m}, {info8, b->io.info, 8}, {DX, b->io.DXo, n}, {DY, b->io.DYo, m}};
+  size_t total = 0;
+  for (const auto &r : rows) if (r.dst) total += R * r.width;
+  if (!total) return 0;
+  if (members_put(b, members, count)) return OSQP_MEM_ALLOC_ERROR;
+  if (members && !dev && stage_reserve(b, total, 0)) return OSQP_MEM_ALLOC_ERROR;
+  const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  double *at = b->d_vals;
+  for (const auto &r : rows) {
+    const size_t len = R * r.width;
+    if (!r.dst || !len) continue;
+    const double *src = r.src;
+    if (members) {
+      hipLaunchKernelGGL(k_batch_gather, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, b->stream, dev ? r.dst : at, r.src,
+                         (long long)r.width, (const int *)b->d_mlist, (long long)R);
+      BCHK(hipGetLastError());
+      src = at; at += len;
+    }
+    if (!members || !dev) BCHK(hipMemcpyAsync(r.dst, src, len * sizeof(double), out, b->stream));
+  }
+  BCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
 extern "C" c_int osqp_amd_batch_get(osqp_amd_batch *b, c_float *X, c_float *Y, c_float *info8,
                                    c_float *DX, c_float *DY) {
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  BCHK(hipSetDevice(b->device));
-  const size_t B = (size_t)b->B;
-  if (X) BCHK(hipMemcpyAsync(X, b->io.Xo, B * b->n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (Y && b->m) BCHK(hipMemcpyAsync(Y, b->io.Yo, B * b->m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (info8) BCHK(hipMemcpyAsync(info8, b->io.info, B * 8 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (DX) BCHK(hipMemcpyAsync(DX, b->io.DXo, B * b->n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (DY && b->m) BCHK(hipMemcpyAsync(DY, b->io.DYo, B * b->m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  BCHK(hipStreamSynchronize(b->stream));
-  return 0;
+  return get_call(b, false, nullptr, 0, X, Y, info8, DX, DY);
 }
 
 // Test hook: one member's workspace as the last setup / update / solve left it (K^-1 un-permuted
