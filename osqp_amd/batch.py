@@ -20,86 +20,6 @@ SolveReport = namedtuple("SolveReport", "max_iter time_limit elapsed cut")   # B
 INFO_FIELDS = ["iter", "status_val", "obj_val", "pri_res", "dua_res", "rho_updates", "rho_estimate", "rho"]
 
 
-def _bind(L):
-    H = C.c_void_p
-    L.osqp_amd_batch_setup.restype = abi.c_int
-    L.osqp_amd_batch_setup.argtypes = [C.POINTER(H), abi.c_int, C.POINTER(abi.csc), C.POINTER(abi.csc),
-                                       abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p,
-                                       abi.c_float_p, C.POINTER(abi.OSQPSettings), abi.c_int]
-    L.osqp_amd_batch_update.restype = abi.c_int
-    L.osqp_amd_batch_update.argtypes = [H, abi.c_float_p, abi.c_float_p, abi.c_float_p]
-    L.osqp_amd_batch_update_matrices.restype = abi.c_int
-    L.osqp_amd_batch_update_matrices.argtypes = [H, abi.c_float_p, abi.c_int_p, abi.c_int, abi.c_int,
-                                                 abi.c_float_p, abi.c_int_p, abi.c_int, abi.c_int]
-    L.osqp_amd_batch_update_rho.restype = abi.c_int
-    L.osqp_amd_batch_update_rho.argtypes = [H, abi.c_float_p, abi.c_int]
-    L.osqp_amd_batch_warm_start.restype = abi.c_int
-    L.osqp_amd_batch_warm_start.argtypes = [H, abi.c_float_p, abi.c_float_p]
-    L.osqp_amd_batch_solve.restype = abi.c_int
-    L.osqp_amd_batch_solve.argtypes = [H]
-    L.osqp_amd_batch_solve_members.restype = abi.c_int
-    L.osqp_amd_batch_solve_members.argtypes = [H, abi.c_int_p, abi.c_int]
-    L.osqp_amd_batch_common_columns.restype = abi.c_int
-    L.osqp_amd_batch_common_columns.argtypes = [H, abi.c_int_p]
-    L.osqp_amd_batch_solve_limited.restype = abi.c_int
-    L.osqp_amd_batch_solve_limited.argtypes = [H, abi.c_int_p, abi.c_int, abi.c_int, abi.c_float]
-    L.osqp_amd_batch_solve_report.restype = abi.c_int
-    L.osqp_amd_batch_solve_report.argtypes = [H, abi.c_float_p]
-    L.osqp_amd_batch_polish.restype = abi.c_int
-    L.osqp_amd_batch_polish.argtypes = [H, abi.c_int_p]
-    L.osqp_amd_batch_adjoint.restype = abi.c_int
-    L.osqp_amd_batch_adjoint.argtypes = [H] + [abi.c_float_p] * 7 + [abi.c_int_p] * 2
-    L.osqp_amd_batch_adjoint_multi.restype = abi.c_int
-    L.osqp_amd_batch_adjoint_multi.argtypes = [H, abi.c_int] + [abi.c_float_p] * 7 + [abi.c_int_p] * 2
-    L.osqp_amd_batch_kkt_info.restype = abi.c_int
-    L.osqp_amd_batch_kkt_info.argtypes = [H, abi.c_int_p]
-    L.osqp_amd_batch_tangent.restype = abi.c_int
-    L.osqp_amd_batch_tangent.argtypes = [H, abi.c_int] + [abi.c_float_p] * 7 + [abi.c_int_p] * 2
-    L.osqp_amd_batch_get.restype = abi.c_int
-    L.osqp_amd_batch_get.argtypes = [H, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p]
-    L.osqp_amd_batch_cleanup.restype = None
-    L.osqp_amd_batch_cleanup.argtypes = [H]
-    L.osqp_amd_batch_setup_engine.restype = abi.c_int
-    L.osqp_amd_batch_setup_engine.argtypes = [C.POINTER(H), abi.c_int, abi.c_int, C.POINTER(abi.csc), C.POINTER(abi.csc),
-                                              abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_float_p,
-                                              abi.c_float_p, C.POINTER(abi.OSQPSettings), abi.c_int]
-    L.osqp_amd_batch_setup_common.restype = abi.c_int
-    L.osqp_amd_batch_setup_common.argtypes = [C.POINTER(H), abi.c_int, C.POINTER(abi.csc), C.POINTER(abi.csc),
-                                              abi.c_float_p, abi.c_float_p, abi.c_float_p,
-                                              C.POINTER(abi.OSQPSettings), abi.c_int]
-    L.osqp_amd_batch_common_kkt.restype = abi.c_int
-    L.osqp_amd_batch_common_kkt.argtypes = [H, abi.c_int]
-    L.osqp_amd_batch_common_update_model.restype = abi.c_int
-    L.osqp_amd_batch_common_update_model.argtypes = [H] + [abi.c_float_p, abi.c_int_p, abi.c_int] * 2
-    L.osqp_amd_batch_common_kkt_peek.restype = abi.c_int
-    L.osqp_amd_batch_common_kkt_peek.argtypes = [H, abi.c_float_p, abi.c_float_p, abi.c_int, abi.c_int_p, abi.c_int_p, abi.c_float_p]
-    L.osqp_amd_batch_shape.restype = abi.c_int
-    L.osqp_amd_batch_shape.argtypes = [H, abi.c_int_p, abi.c_int_p]
-    L.osqp_amd_batch_rounds.restype = abi.c_int
-    L.osqp_amd_batch_rounds.argtypes = [H, abi.c_int_p, abi.c_int_p]
-    L.osqp_amd_batch_member.restype = abi.c_int
-    L.osqp_amd_batch_member.argtypes = [H, abi.c_int] + [abi.c_float_p] * 4 + [abi.c_int_p] + [abi.c_float_p] * 3 + [abi.c_int_p]
-    # device arrays in and out: device addresses travel as integers (c_void_p), host index lists as before
-    V = C.c_void_p
-    for name, args in (("update_dev", [V] * 3), ("warm_start_dev", [V] * 2), ("adjoint_dev", [V] * 9),
-                       ("adjoint_multi_dev", [abi.c_int] + [V] * 9),
-                       ("tangent_dev", [abi.c_int] + [V] * 9),
-                       ("update_matrices_dev", [V, abi.c_int_p, abi.c_int, abi.c_int] * 2),
-                       ("common_update_model_dev", [V, abi.c_int_p, abi.c_int] * 2),
-                       ("get_dev", [V] * 5), ("polish_status_dev", [V]), ("check_dev_ptr", [V])):
-        f = getattr(L, "osqp_amd_batch_" + name)
-        f.restype = abi.c_int
-        f.argtypes = [H] + args
-    # the member-list forms: (members, count) -- a host list in the _dev forms too -- in front of the twin's arguments
-    F, I = abi.c_float_p, abi.c_int_p
-    for name, args in MEMBER_CALLS.items():
-        f = getattr(L, "osqp_amd_batch_" + name)
-        f.restype = abi.c_int
-        f.argtypes = [H, I, abi.c_int] + [dict(f=F, i=I, v=V, n=abi.c_int)[k] for k in args]
-    L.osqp_amd_batch_solved_members.restype = abi.c_int
-    L.osqp_amd_batch_solved_members.argtypes = [H, I]
-
-
 # the arguments of each osqp_amd_batch_<name> after (handle, members, count): f = float array, i = c_int array,
 # v = device address, n = c_int
 MEMBER_CALLS = {
@@ -110,6 +30,36 @@ MEMBER_CALLS = {
     "tangent_members": "n" + "f" * 7 + "ii", "tangent_members_dev": "n" + "v" * 9,
     "get_members": "fffff", "get_members_dev": "vvvvv",
 }
+# ... and of every other osqp_amd_batch_<name>, in the same letters and h = the handle, H = a place for a handle or a
+# device address, c = csc matrix, s = settings, d = c_float.  Device addresses travel as integers (c_void_p); index
+# lists are host data in the _dev forms too.
+_CALLS = {
+    "setup": "Hnccfffffsn", "setup_engine": "Hnnccfffffsn", "setup_common": "Hnccfffsn", "cleanup": "h",
+    "update": "hfff", "update_dev": "hvvv", "warm_start": "hff", "warm_start_dev": "hvv", "update_rho": "hfn",
+    "update_matrices": "h" + "finn" * 2, "update_matrices_dev": "h" + "vinn" * 2,
+    "common_update_model": "h" + "fin" * 2, "common_update_model_dev": "h" + "vin" * 2,
+    "solve": "h", "solve_members": "hin", "solve_limited": "hinnd", "solve_report": "hf", "common_columns": "hi",
+    "polish": "hi", "polish_status_dev": "hv", "kkt_info": "hi", "common_kkt": "hn", "common_kkt_peek": "hffniif",
+    "adjoint": "h" + "f" * 7 + "ii", "adjoint_multi": "hn" + "f" * 7 + "ii", "tangent": "hn" + "f" * 7 + "ii",
+    "adjoint_dev": "h" + "v" * 9, "adjoint_multi_dev": "hn" + "v" * 9, "tangent_dev": "hn" + "v" * 9,
+    "get": "hfffff", "get_dev": "hvvvvv", "solved_members": "hi", "shape": "hii", "rounds": "hii",
+    "member": "hnffffifffi", "device_ptrs": "hHHH", "check_dev_ptr": "hv",
+}
+
+
+def _bind(L):
+    """Declares the batch entry points on the library object L, once per object (a second call does nothing)."""
+    if getattr(L, "_osqp_amd_batch_bound", False):
+        return
+    kinds = dict(h=C.c_void_p, H=C.POINTER(C.c_void_p), v=C.c_void_p, f=abi.c_float_p, i=abi.c_int_p, n=abi.c_int,
+                 d=abi.c_float, c=C.POINTER(abi.csc), s=C.POINTER(abi.OSQPSettings))
+    L.osqp_set_default_settings.restype = None
+    L.osqp_set_default_settings.argtypes = [kinds["s"]]
+    for name, args in list(_CALLS.items()) + [(name, "hin" + args) for name, args in MEMBER_CALLS.items()]:
+        f = getattr(L, "osqp_amd_batch_" + name)
+        f.restype = None if name == "cleanup" else abi.c_int
+        f.argtypes = [kinds[k] for k in args]
+    L._osqp_amd_batch_bound = True
 
 
 def _p(a):
@@ -141,6 +91,14 @@ def _info_columns(out, info):
     return out
 
 
+def _checked(a):
+    """(a, its shape): a host array as contiguous float64, a device array as it is (device_view checks type and strides)."""
+    if is_device(a):
+        return a, _shape(a)
+    a = abi.as_f64(a)
+    return a, a.shape
+
+
 def is_device(a):
     """True for an object that says where it lives in HBM (`__cuda_array_interface__`: a torch CUDA tensor that needs no
     gradient, a cupy array, an object of the caller's own)."""
@@ -159,11 +117,7 @@ def check_matrix_update(B, nnzP, nnzA, Px=None, Px_idx=None, Ax=None, Ax_idx=Non
                 raise ValueError("%sx_idx given without %sx" % (name, name))
             out += [None, None, 0]
             continue
-        if is_device(V):                         # stays where it is: device_view checks type and strides
-            shape = tuple(V.__cuda_array_interface__["shape"])
-        else:
-            V = abi.as_f64(V)
-            shape = V.shape
+        V, shape = _checked(V)
         if len(shape) not in (1, 2):
             raise ValueError("%sx must be [k] (shared) or [B, k] (per member)" % name)
         if len(shape) == 2 and shape[0] != B:
@@ -263,11 +217,7 @@ def check_adjoint_multi(B, n, m, dX, dY=None, **outputs):
         if a is None:
             out[name] = None
             continue
-        if is_device(a):
-            shape = tuple(a.__cuda_array_interface__["shape"])
-        else:
-            a = abi.as_f64(a)
-            shape = a.shape
+        a, shape = _checked(a)
         if len(shape) != 3 or shape[0] != B or shape[2] != k or shape[1] < 1:
             raise ValueError("%s must be [B, D, %d] with B = %d and D >= 1, not %s" % (name, k, B, shape))
         Ds[name] = shape[1]
@@ -297,11 +247,7 @@ def check_tangent(B, n, m, nnzP, nnzA, dQ=None, dL=None, dU=None, dPx=None, dAx=
         if a is None:
             out[name] = None
             continue
-        if is_device(a):
-            shape = tuple(a.__cuda_array_interface__["shape"])
-        else:
-            a = abi.as_f64(a)
-            shape = a.shape
+        a, shape = _checked(a)
         if len(shape) not in (2, 3) or shape[0] != B or shape[-1] != cols[name] or (len(shape) == 3 and shape[1] < 1):
             raise ValueError("%s must be [B, %d] or [B, D, %d] with B = %d, not %s" % (name, cols[name], cols[name], B, shape))
         forms[name] = None if len(shape) == 2 else shape[1]
@@ -368,8 +314,6 @@ class BatchOSQP:
             if V is not None and np.shape(V) != (self.B, nnz):
                 raise ValueError("%s must be [B, %d]" % (nm, nnz))
         st = abi.OSQPSettings()
-        self._lib.osqp_set_default_settings.restype = None
-        self._lib.osqp_set_default_settings.argtypes = [C.POINTER(abi.OSQPSettings)]
         self._lib.osqp_set_default_settings(C.byref(st))
         st.verbose = 0
         for k, v in settings.items():
@@ -386,51 +330,18 @@ class BatchOSQP:
         if engine == "auto" and self.n > BATCH_MAX_N:
             # The one-workgroup-per-QP kernel keeps K^-1 in registers (n <= 128).  Larger members of a batch go
             # one QP per HIP stream through the single-QP engine (osqp_amd/multi.py): same results, the PCG path.
-            from . import OSQP, set_engine_options
-            old = engine_options()["device"]
-            set_engine_options(device=device)
-            try:
-                Pf, Af = sparse.csc_matrix(P), sparse.csc_matrix(A)
-                self._many = []
-                for b in range(self.B):
-                    Pb, Ab = Pf.copy(), Af.copy()
-                    if Px_all is not None:
-                        Pb = sparse.triu(Pf, format="csc"); Pb.sort_indices(); Pb.data = Px_all[b].copy()
-                    if Ax_all is not None:
-                        Ab.sort_indices(); Ab.data = Ax_all[b].copy()
-                    try:
-                        self._many.append(OSQP().setup(P=Pb, q=Q[b], A=Ab, l=L[b], u=U[b], **settings))
-                    except ValueError as e:       # e.g. error 5 (non-convex member), as the kernel path reports it
-                        for s in self._many:
-                            s.cleanup()
-                        self._many = None
-                        raise ValueError("%s (QP %d of the batch)" % (e, b)) from None
-            finally:
-                set_engine_options(device=old)
-            self._last = None
+            from .multi import PerMemberBatch
+            self._many = PerMemberBatch(P, A, Q, L, U, Px_all, Ax_all, device, settings)
             return self
         h = C.c_void_p()
-        if engine == "common":
-            rc = self._lib.osqp_amd_batch_setup_common(C.byref(h), self.B, C.byref(self.Pu.struct), C.byref(self.Ah.struct),
-                                                       abi.fptr(Q), _p(L if self.m else None), _p(U if self.m else None),
-                                                       C.byref(st), device)
-            if rc:
-                raise ValueError("osqp_amd_batch_setup_common failed with error %d%s"
-                                 % (rc, ": a row has different classes (loose / inequality / equality) in two members"
-                                    if rc == 1 else ""))
-        elif engine == "streamed":
-            rc = self._lib.osqp_amd_batch_setup_engine(C.byref(h), ENGINES["streamed"], self.B, C.byref(self.Pu.struct),
-                                                       C.byref(self.Ah.struct), _p(Px_all), _p(Ax_all), abi.fptr(Q),
-                                                       _p(L if self.m else None), _p(U if self.m else None), C.byref(st),
-                                                       device)
-            if rc:
-                raise ValueError("osqp_amd_batch_setup_engine failed with error %d" % rc)
-        else:
-            rc = self._lib.osqp_amd_batch_setup(C.byref(h), self.B, C.byref(self.Pu.struct), C.byref(self.Ah.struct),
-                                                _p(Px_all), _p(Ax_all), abi.fptr(Q), _p(L if self.m else None),
-                                                _p(U if self.m else None), C.byref(st), device)
-            if rc:
-                raise ValueError("osqp_amd_batch_setup failed with error %d" % rc)
+        call = "osqp_amd_batch_setup" + dict(auto="", streamed="_engine", common="_common")[engine]
+        rc = getattr(self._lib, call)(
+            C.byref(h), *((ENGINES["streamed"],) if engine == "streamed" else ()), self.B, C.byref(self.Pu.struct),
+            C.byref(self.Ah.struct), *(() if engine == "common" else (_p(Px_all), _p(Ax_all))), abi.fptr(Q),
+            _p(L if self.m else None), _p(U if self.m else None), C.byref(st), device)
+        if rc:
+            raise ValueError("%s failed with error %d%s" % (call, rc, ": a row has different classes (loose / inequality / "
+                                                            "equality) in two members" if engine == "common" and rc == 1 else ""))
         self._h = h
         if shared_kkt:
             try:
@@ -448,6 +359,20 @@ class BatchOSQP:
                                "engine=\"auto\" or engine=\"streamed\""
                                % (call, " (use update_model for new values of the shared model)" if never else
                                   " without its shared KKT pieces (shared_kkt=True)"))
+
+    def _kernel_batch(self, call, option=None, why=None):
+        """Refuses what the one-engine-per-member route (osqp_amd/multi.py, `_many`) does not serve -- it keeps no packed
+        batch on the device -- in one of its three sentences: `why` (what the caller meets instead; True: `call` is a
+        call of the batch engines), `call(option=...)`, or `call` alone."""
+        if self._many is None:
+            return
+        if why is not None:
+            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): %s" % (BATCH_MAX_N, (
+                "%s is a call of the batch engines; set the batch up with engine=\"streamed\"" % call) if why is True else why))
+        if option is not None:
+            raise RuntimeError("%s(%s=...) is not served by the one-engine-per-member route (engine=\"auto\", n > %d); "
+                               "set the batch up with engine=\"streamed\" or engine=\"common\"" % (call, option, BATCH_MAX_N))
+        raise RuntimeError("%s is not served by the one-engine-per-member route (engine=\"auto\", n > %d)" % (call, BATCH_MAX_N))
 
     def shared_kkt(self, on=True):
         """The shared KKT pieces of a common-K handle (osqp_amd_batch_common_kkt): on=True builds H = (P~ + delta I)^-1 and
@@ -498,30 +423,16 @@ class BatchOSQP:
             raise RuntimeError("osqp_amd_batch_rounds failed")
         return int(r[0]), int(f[0])
 
-    def _many_update(self, Q, L, U):
-        # the first failing member's code comes back (and which member it was stays readable in `last_update_failed`)
-        self.last_update_failed = None
-        for b, s in enumerate(self._many):
-            rc = s.update(q=None if Q is None else Q[b], l=None if L is None else L[b], u=None if U is None else U[b])
-            if rc:
-                self.last_update_failed = b
-                return rc
-        return 0
-
-    def _many_results(self):
-        rs = self._last
-        X = np.array([r.x for r in rs]); Y = np.array([r.y for r in rs]).reshape(self.B, self.m)
-        info = np.array([[r.info.iter, r.info.status_val, r.info.obj_val, r.info.pri_res, r.info.dua_res, r.info.rho_updates,
-                          r.info.rho_estimate, s.settings().rho] for r, s in zip(rs, self._many)], dtype=np.float64)
-        out = SimpleNamespace(x=X, y=Y, dual_inf_cert=np.array([r.dual_inf_cert for r in rs]),
-                              prim_inf_cert=np.array([r.prim_inf_cert for r in rs]).reshape(self.B, self.m), info_raw=info)
-        return _info_columns(out, info)
+    @property
+    def last_update_failed(self):
+        """One-engine-per-member route: the member whose non-zero code the last update, update_matrices, update_rho or
+        warm_start returned (None: every member took the call)."""
+        return self._many.last_update_failed
 
     def _route(self, **arrays):
         route = io_route(**arrays)
-        if route == "device" and self._many is not None:
-            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): it takes and returns host arrays; "
-                               "there is no packed device image to read or write" % BATCH_MAX_N)
+        if route == "device":
+            self._kernel_batch(None, why="it takes and returns host arrays; there is no packed device image to read or write")
         return route
 
     def _dev(self, a, cols, name, typestr="<f8", writable=False, rows=None):
@@ -533,17 +444,13 @@ class BatchOSQP:
     def _members(self, members, call):
         """The list of a members= call as the C side takes it (check_members), once the handle can serve one: the
         one-engine-per-member route keeps no packed batch to address by member."""
-        if self._many is not None:
-            raise RuntimeError("%s(members=...) is not served by the one-engine-per-member route (engine=\"auto\", n > %d); "
-                               "set the batch up with engine=\"streamed\" or engine=\"common\"" % (call, BATCH_MAX_N))
+        self._kernel_batch(call, option="members")
         return check_members(self.B, members)
 
     def solved_members(self):
         """Boolean [B]: True where the member's results are those of a solve of the problem the handle holds now -- what
         polish, adjoint and tangent with members= require of the members they list.  Touches no GPU memory."""
-        if self._many is not None:
-            raise RuntimeError("solved_members is not served by the one-engine-per-member route (engine=\"auto\", n > %d)"
-                               % BATCH_MAX_N)
+        self._kernel_batch("solved_members")
         out = np.zeros(self.B, np.int64)
         rc = self._lib.osqp_amd_batch_solved_members(self._h, abi.iptr(out))
         if rc:
@@ -590,19 +497,9 @@ class BatchOSQP:
             if L is not None and U is not None and np.any(L > U):
                 raise ValueError("lower bound greater than upper bound")
             if self._many is not None:
-                return self._many_update(Q, L, U)
+                return self._many.update(Q, L, U)
         _, f, lead = self._entry("update", mem, dev)
         return int(f(self._h, *lead, *((Q, L, U) if dev else (_p(Q), _p(L), _p(U)))))
-
-    def _many_each(self, call):
-        # as _many_update: the first failing member's code comes back
-        self.last_update_failed = None
-        for b, s in enumerate(self._many):
-            rc = call(b, s)
-            if rc:
-                self.last_update_failed = b
-                return rc
-        return 0
 
     def update_matrices(self, Px=None, Px_idx=None, Ax=None, Ax_idx=None):
         """osqp_update_P / _A / _P_A for every QP: new values on the pattern of setup.  Px / Ax: [k] (shared by the
@@ -611,28 +508,31 @@ class BatchOSQP:
         (5: some member's new K is not positive definite; solve then refuses until an update succeeds).  Px / Ax may be
         device arrays; the index lists stay host data."""
         self._unserved("update_matrices", never=True)
-        if self._route(Px=Px, Ax=Ax) == "device":
-            return self._update_matrices_dev(Px, Px_idx, Ax, Ax_idx)
+        dev = self._route(Px=Px, Ax=Ax) == "device"
         Px, Px_idx, pper, Ax, Ax_idx, aper = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
         if Px is None and Ax is None:
             return 0
         if self._many is not None:
-            return self._many_each(lambda b, s: s.update(Px=None if Px is None else (Px[b] if pper else Px), Px_idx=Px_idx,
-                                                         Ax=None if Ax is None else (Ax[b] if aper else Ax), Ax_idx=Ax_idx))
-        return int(self._lib.osqp_amd_batch_update_matrices(
-            self._h, _p(Px), _ip(Px_idx), 0 if Px is None else Px.shape[-1], pper,
-            _p(Ax), _ip(Ax_idx), 0 if Ax is None else Ax.shape[-1], aper))
-
-    def _update_matrices_dev(self, Px, Px_idx, Ax, Ax_idx):
-        Px, Px_idx, pper, Ax, Ax_idx, aper = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
-        # (a pointer of 0: nothing to write; NULL = keep says the same)
-        pP = None if Px is None else device_view(Px, _shape(Px), "<f8", name="Px") or None
-        pA = None if Ax is None else device_view(Ax, _shape(Ax), "<f8", name="Ax") or None
-        if pP is None and pA is None:
+            return self._many.update_matrices(Px, Px_idx, pper, Ax, Ax_idx, aper)
+        (pP, iP, kP), (pA, iA, kA) = self._matrix_values(dev, Px, Px_idx, Ax, Ax_idx)
+        if dev and pP is None and pA is None:
             return 0
-        return int(self._lib.osqp_amd_batch_update_matrices_dev(
-            self._h, pP, _ip(Px_idx), 0 if Px is None else _shape(Px)[-1], pper,
-            pA, _ip(Ax_idx), 0 if Ax is None else _shape(Ax)[-1], aper))
+        f = self._lib.osqp_amd_batch_update_matrices_dev if dev else self._lib.osqp_amd_batch_update_matrices
+        return int(f(self._h, pP, iP, kP, pper, pA, iA, kA, aper))
+
+    @staticmethod
+    def _matrix_values(dev, Px, Px_idx, Ax, Ax_idx):
+        """New matrix values that check_matrix_update has passed, as update_matrices and update_model hand them to the C
+        side: (values, index list, values per member) of P and of A -- host pointers or, on the device route, device
+        addresses (a pointer of 0: nothing to write; NULL = keep says the same); the index lists are host data."""
+        out = []
+        for name, V, I in (("Px", Px, Px_idx), ("Ax", Ax, Ax_idx)):
+            if dev:
+                out.append((None if V is None else device_view(V, _shape(V), "<f8", name=name) or None, _ip(I),
+                            0 if V is None else _shape(V)[-1]))
+            else:
+                out.append((_p(V), _ip(I), 0 if V is None else V.shape[-1]))
+        return out
 
     def update_model(self, Px=None, Px_idx=None, Ax=None, Ax_idx=None):
         """New values for the shared model of a common-K handle (osqp_amd_batch_common_update_model): osqp_update_P / _A /
@@ -652,15 +552,8 @@ class BatchOSQP:
                                  "[B, k]" % name)
         dev = self._route(Px=Px, Ax=Ax) == "device"
         Px, Px_idx, _, Ax, Ax_idx, _ = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
-        if dev:
-            # (a pointer of 0: nothing to write; NULL = keep says the same)
-            vals = [None if V is None else device_view(V, _shape(V), "<f8", name=nm) or None for nm, V in (("Px", Px), ("Ax", Ax))]
-            cnt = [0 if V is None else _shape(V)[0] for V in (Px, Ax)]
-            call = self._lib.osqp_amd_batch_common_update_model_dev
-        else:
-            vals, cnt = [_p(Px), _p(Ax)], [0 if V is None else V.shape[0] for V in (Px, Ax)]
-            call = self._lib.osqp_amd_batch_common_update_model
-        rc = int(call(self._h, vals[0], _ip(Px_idx), cnt[0], vals[1], _ip(Ax_idx), cnt[1]))
+        f = self._lib.osqp_amd_batch_common_update_model_dev if dev else self._lib.osqp_amd_batch_common_update_model
+        rc = int(f(self._h, *(v for of in self._matrix_values(dev, Px, Px_idx, Ax, Ax_idx) for v in of)))
         if rc == 5 and self._shared_kkt:                 # did the shared pieces go?  (NULL outputs: nothing is copied)
             no_i, no_f = C.cast(None, abi.c_int_p), C.cast(None, abi.c_float_p)
             self._shared_kkt = self._lib.osqp_amd_batch_common_kkt_peek(self._h, no_f, no_f, 0, no_i, no_i, no_f) == 0
@@ -676,9 +569,7 @@ class BatchOSQP:
             raise ValueError("engine='common' has one rho for the batch: update_rho takes a scalar")
         rho = np.ascontiguousarray(rho.reshape(-1))
         if self._many is not None:
-            if np.any(rho <= 0):
-                return 1
-            return self._many_each(lambda b, s: s.update_rho(rho[b if per else 0]))
+            return self._many.update_rho(rho, per)
         return int(self._lib.osqp_amd_batch_update_rho(self._h, abi.fptr(rho), per))
 
     def warm_start(self, X=None, Y=None, members=None):
@@ -692,9 +583,8 @@ class BatchOSQP:
                % (mem.size, n, mem.size, m, mem.size)
         dev = self._route(X=X, Y=Y) == "device"
         X, Y = self._given(dev, mem, want, (X, n, "X", True), (Y, m, "Y", bool(m)))
-        if not dev:
-            if self._many is not None:
-                return self._many_each(lambda b, s: s.warm_start(x=None if X is None else X[b], y=None if Y is None else Y[b]))
+        if not dev and self._many is not None:
+            return self._many.warm_start(X, Y)
         _, f, lead = self._entry("warm_start", mem, dev)
         return int(f(self._h, *lead, *((X, Y) if dev else (_p(X), _p(Y if m else None)))))
 
@@ -716,46 +606,38 @@ class BatchOSQP:
             if isinstance(time_limit, bool) or not isinstance(time_limit, (int, float, np.integer, np.floating)) \
                     or not np.isfinite(time_limit) or time_limit <= 0:
                 raise ValueError("time_limit must be a finite number of seconds > 0, not %r" % (time_limit,))
-        if limited and self._many is not None:
-            raise RuntimeError("solve(%s=...) is not served by the one-engine-per-member route (engine=\"auto\", n > %d); "
-                               "set the batch up with engine=\"streamed\" or engine=\"common\""
-                               % ("max_iter" if max_iter is not None else "time_limit", BATCH_MAX_N))
+        if limited:
+            self._kernel_batch("solve", option="max_iter" if max_iter is not None else "time_limit")
+        mem = None
         if members is not None:
             if getattr(self, "engine", None) != "common" or self._many is not None or self._h is None:
                 raise RuntimeError("solve(members=...) is not served by the %s; it is a call of the common-K engine "
                                    "(engine=\"common\")" % ("one-engine-per-member path (n > %d)" % BATCH_MAX_N
                                                             if self._many is not None else "tiled or the streamed engine"))
-            members = check_members(self.B, members)
-            self._status_polish = None
-            if limited:
-                rc = self._lib.osqp_amd_batch_solve_limited(self._h, abi.iptr(members), members.size, int(max_iter or 0),
-                                                            float(time_limit or 0.0))
-            else:
-                rc = self._lib.osqp_amd_batch_solve_members(self._h, abi.iptr(members), members.size)
-            if rc:
-                raise RuntimeError("osqp_amd_batch_solve_%s failed (%d)" % ("limited" if limited else "members", rc))
+            mem = check_members(self.B, members)
+        elif self._many is not None:
+            self._many.solve()
             return self.results() if fetch else None
-        if self._many is not None:
-            from .multi import solve_many
-            self._last = solve_many(self._many, max_workers=8)
-            return self._many_results() if fetch else None
         self._status_polish = None
         if limited:
-            rc = self._lib.osqp_amd_batch_solve_limited(self._h, C.cast(None, abi.c_int_p), 0, int(max_iter or 0),
+            call = "osqp_amd_batch_solve_limited"
+            rc = self._lib.osqp_amd_batch_solve_limited(self._h, _ip(mem), 0 if mem is None else mem.size, int(max_iter or 0),
                                                         float(time_limit or 0.0))
+        elif mem is not None:
+            call = "osqp_amd_batch_solve_members"
+            rc = self._lib.osqp_amd_batch_solve_members(self._h, abi.iptr(mem), mem.size)
         else:
+            call = "osqp_amd_batch_solve"
             rc = self._lib.osqp_amd_batch_solve(self._h)
         if rc:
-            raise RuntimeError("osqp_amd_batch_solve%s failed (%d)" % ("_limited" if limited else "", rc))
+            raise RuntimeError("%s failed (%d)" % (call, rc))
         return self.results() if fetch else None
 
     def solve_report(self):
         """Of the last solve by any call: (max_iter, time_limit, elapsed, cut) -- the iteration cap and the time limit in
         force (0: none), the seconds between the two device stamps of a solve with a time limit (0 without one) and the
         members the clock stopped.  Touches no GPU memory."""
-        if self._many is not None:
-            raise RuntimeError("solve_report is not served by the one-engine-per-member route (engine=\"auto\", n > %d)"
-                               % BATCH_MAX_N)
+        self._kernel_batch("solve_report")
         out = np.zeros(4)
         rc = self._lib.osqp_amd_batch_solve_report(self._h, abi.fptr(out))
         if rc:
@@ -785,29 +667,21 @@ class BatchOSQP:
         (solved_members); the work is done once per member and solve.  Returns results(members=) -- compact rows -- with
         `status_polish` [count]."""
         self._unserved("polish")
-        if members is not None:
-            mem = self._members(members, "polish")
-            sp = np.zeros(mem.size, np.int64) if fetch else None
-            rc = self._lib.osqp_amd_batch_polish_members(self._h, abi.iptr(mem), mem.size,
-                                                         abi.iptr(sp) if fetch else C.cast(None, abi.c_int_p))
-            if rc:
-                raise RuntimeError("osqp_amd_batch_polish_members failed (%d)%s"
-                                   % (rc, ": a listed member has not been solved on the current problem" if rc == 7 else ""))
-            if not fetch:
-                return None
-            out = self.results(members=mem)
-            out.status_polish = sp
-            return out
-        if self._many is not None:
-            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): polish is a call of the batch "
-                               "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
-        sp = np.zeros(self.B, np.int64) if fetch else None
-        rc = self._lib.osqp_amd_batch_polish(self._h, abi.iptr(sp) if fetch else C.cast(None, abi.c_int_p))
+        mem = None if members is None else self._members(members, "polish")
+        self._kernel_batch("polish", why=True)
+        sp = np.zeros(self._rows(mem), np.int64) if fetch else None
+        call, f, lead = self._entry("polish", mem)
+        rc = f(self._h, *lead, _ip(sp))
         if rc:
-            raise RuntimeError("osqp_amd_batch_polish failed (%d)%s" % (rc, ": no solve has run on the current problem"
-                                                                        if rc == 7 else ""))
-        self._status_polish = sp if fetch else "device"       # results() reads it when it is first asked for
-        return self.results() if fetch else None
+            raise RuntimeError("%s failed (%d)%s" % (call, rc, self._unsolved(mem) if rc == 7 else ""))
+        if mem is None:
+            self._status_polish = sp if fetch else "device"       # results() reads it when it is first asked for
+        if not fetch:
+            return None
+        out = self.results(members=mem)
+        if mem is not None:
+            out.status_polish = sp
+        return out
 
     def adjoint(self, dX, dY=None, matrices=False, members=None):
         """Adjoint derivatives of the solution on the device, for every member whose last solve ended `solved`: from
@@ -826,28 +700,54 @@ class BatchOSQP:
         [count, D, .], and the KKT inversion is built for the listed members alone (and shared by later members= calls
         with the same list)."""
         self._unserved("adjoint")
-        mem = None if members is None else self._members(members, "adjoint")
-        if self._many is not None:
-            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): adjoint is a call of the batch "
-                               "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
-        R, n, m, nP, nA = self._rows(mem), self.n, self.m, self.Pu.nnz, self.Ah.nnz
-        flat = np.ndim(dX) != 3       # whole batch: [B, n] takes the single-cotangent entry point, [B, D, n] the _multi one
+        return self._adjoint("adjoint", False, members, dX, dY, matrices=matrices)
+
+    def _adjoint(self, call, dev, members, dX, dY, into=None, active=None, status=None, matrices=False):
+        """The one body of adjoint (dev=False: host arrays in, a namespace of new host arrays out) and adjoint_into
+        (dev=True: between the caller's device arrays, `into` = dict(dq, dl, du, dPx, dAx), active, status): the list of a
+        members= call, the shape checks with the rows of the call, [R, n] or [R, D, n], and the entry that serves the form."""
+        mem = None if members is None else self._members(members, call)
+        self._kernel_batch(call, why=True)
+        R, n, m = self._rows(mem), self.n, self.m
+        cols = dict(dq=n, dl=m, du=m, dPx=self.Pu.nnz, dAx=self.Ah.nnz)
+        # whole batch: [B, n] takes the single-cotangent entry point, [B, D, n] the _multi one
+        flat, D = len(_shape(dX) if dev else np.shape(dX)) != 3, 1
         try:
-            dX, dY, D = check_adjoint(R, n, m, dX, dY) + (1,) if flat else check_adjoint_multi(R, n, m, dX, dY)
+            if not flat:
+                dX, dY, D = check_adjoint_multi(R, n, m, dX, dY, **({k: (into[k], c) for k, c in cols.items()} if dev else {}))
+            elif not dev:                            # (flat device arrays: device_view says what is wrong with which)
+                dX, dY = check_adjoint(R, n, m, dX, dY)
         except ValueError as e:
             raise self._compact(e, mem) from None
-        o = _outputs(R, D, dq=n, dl=m, du=m, dPx=nP if matrices else None, dAx=nA if matrices else None)
-        act = np.zeros((R, max(m, 1)), np.int64); sa = np.zeros(R, np.int64)
-        call, f, lead = self._entry("adjoint" if flat or mem is not None else "adjoint_multi", mem)
-        if mem is not None or not flat:
-            lead += (D,)
-        rc = f(self._h, *lead, abi.fptr(dX), _p(dY if m else None), abi.fptr(o["dq"]), abi.fptr(o["dl"]), abi.fptr(o["du"]),
-               _p(o["dPx"]), _p(o["dAx"]), abi.iptr(act), abi.iptr(sa))
+        if not dev:
+            into = _outputs(R, D, **{k: c if matrices or k not in ("dPx", "dAx") else None for k, c in cols.items()})
+            active, status = np.zeros((R, max(m, 1)), np.int64), np.zeros(R, np.int64)
+        self._sens("adjoint", "adjoint" if flat or mem is not None else "adjoint_multi", dev, mem, flat, D,
+                   () if flat and mem is None else (D,),
+                   [(dX, n, "dX", False), (dY if dev or m else None, m, "dY", False)] + [(into[k], c, k, True) for k, c in cols.items()],
+                   active, status)
+        if not dev:
+            return SimpleNamespace(**{k: _trim(into[k], c, flat) for k, c in cols.items()}, active=active[:, :m],
+                                   status_adjoint=status)
+
+    def _sens(self, kind, entry, dev, mem, flat, D, scalars, floats, active, status):
+        """The library call of the derivative bodies (kind: "adjoint" or "tangent"), marshalled and worded in one place.
+        floats: the float arrays in the entry's order, each (a, cols, name, writable): host arrays go as pointers, device
+        arrays as the address device_view gives once the array is [R, cols] (flat) or [R, D, cols], float64, contiguous
+        and, for an output, writable; active [R, m] and status [R]: int64 on the host, int32 on the device."""
+        R = self._rows(mem)
+        call, f, lead = self._entry(entry, mem, dev)
+        if dev:
+            args = [None if a is None else device_view(a, (R, k) if flat else (R, D, k), "<f8", w, name) or None
+                    for a, k, name, w in floats]
+            args += [self._dev(active, self.m, "active", "<i4", True, rows=R),
+                     None if status is None else device_view(status, (R,), "<i4", True, "status_" + kind)]
+        else:
+            args = [_p(a) for a, _, _, _ in floats] + [abi.iptr(active), abi.iptr(status)]
+        rc = f(self._h, *lead, *scalars, *args)
         if rc:
-            raise RuntimeError("%s failed (%d)%s" % (call, rc, self._unsolved(mem) if rc == 7 else ""))
-        return SimpleNamespace(dq=_trim(o["dq"], n, flat), dl=_trim(o["dl"], m, flat), du=_trim(o["du"], m, flat),
-                               dPx=_trim(o["dPx"], nP, flat), dAx=_trim(o["dAx"], nA, flat), active=act[:, :m],
-                               status_adjoint=sa)
+            raise RuntimeError("%s failed (%d)%s" % (call, rc, self._unsolved(mem) if rc == 7 else
+                                                     _BAD_POINTER if dev and rc == 1 else ""))
 
     def _rows(self, mem):
         """The rows of a call's per-member arrays: B, or the number of listed members."""
@@ -872,9 +772,7 @@ class BatchOSQP:
         members since setup (polish's included), whether an inversion is kept for the next adjoint() / tangent() on this
         solve, its padded order and the members in it.  Touches no GPU memory."""
         self._unserved("kkt_info")
-        if self._many is not None:
-            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): there is no batch KKT buffer"
-                               % BATCH_MAX_N)
+        self._kernel_batch("kkt_info", why="there is no batch KKT buffer")
         out = np.zeros(4, np.int64)
         rc = self._lib.osqp_amd_batch_kkt_info(self._h, abi.iptr(out))
         if rc:
@@ -893,37 +791,39 @@ class BatchOSQP:
         setup or the last update.
         members=: for the listed members only, as adjoint(members=): compact arrays, [count, k] or [count, D, k]."""
         self._unserved("tangent")
-        mem = None if members is None else self._members(members, "tangent")
-        if self._many is not None:
-            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): tangent is a call of the batch "
-                               "engines; set the batch up with engine=\"streamed\"" % BATCH_MAX_N)
-        R, n, m = self._rows(mem), self.n, self.m
+        return self._tangent("tangent", False, members, (dQ, dL, dU, dPx, dAx))
+
+    def _tangent(self, call, dev, members, given, into=None, active=None, status=None):
+        """The one body of tangent and tangent_into, as _adjoint: given = (dQ, dL, dU, dPx, dAx), into = dict(dx, dy)."""
+        mem = None if members is None else self._members(members, call)
+        self._kernel_batch(call, why=True)
+        R, n, m, nP, nA = self._rows(mem), self.n, self.m, self.Pu.nnz, self.Ah.nnz
         try:
-            dQ, dL, dU, dPx, dAx, D, flat = check_tangent(R, n, m, self.Pu.nnz, self.Ah.nnz, dQ, dL, dU, dPx, dAx)
+            dQ, dL, dU, dPx, dAx, D, flat = check_tangent(R, n, m, nP, nA, *given, **(into if dev else {}))
         except ValueError as e:
             raise self._compact(e, mem) from None
-        o = _outputs(R, D, dx=n, dy=m)
-        act = np.zeros((R, max(m, 1)), np.int64); st = np.zeros(R, np.int64)
-        call, f, lead = self._entry("tangent", mem)
-        rc = f(self._h, *lead, D, _p(dQ), _p(dL if m else None), _p(dU if m else None), _p(dPx), _p(dAx),
-               abi.fptr(o["dx"]), _p(o["dy"] if m else None), abi.iptr(act), abi.iptr(st))
-        if rc:
-            raise RuntimeError("%s failed (%d)%s" % (call, rc, self._unsolved(mem) if rc == 7 else ""))
-        return SimpleNamespace(dx=_trim(o["dx"], n, flat), dy=_trim(o["dy"], m, flat), active=act[:, :m], status_tangent=st)
+        if not dev:
+            into = _outputs(R, D, dx=n, dy=m)
+            active, status = np.zeros((R, max(m, 1)), np.int64), np.zeros(R, np.int64)
+        rows = (lambda a: a) if dev or m else (lambda a: None)      # host arrays of m = 0 columns go as NULL
+        self._sens("tangent", "tangent", dev, mem, flat, D, (D,),
+                   [(dQ, n, "dQ", False), (rows(dL), m, "dL", False), (rows(dU), m, "dU", False), (dPx, nP, "dPx", False),
+                    (dAx, nA, "dAx", False), (into["dx"], n, "dx", True), (rows(into["dy"]), m, "dy", True)], active, status)
+        if not dev:
+            return SimpleNamespace(dx=_trim(into["dx"], n, flat), dy=_trim(into["dy"], m, flat), active=active[:, :m],
+                                   status_tangent=status)
 
     def results(self, members=None):
         """The results of every member, or with members= the compact rows of the listed ones (status_polish: of the last
         whole-batch polish)."""
         mem = None if members is None else self._members(members, "results")
         if self._many is not None:
-            return self._many_results()
+            out = self._many.results()
+            return _info_columns(out, out.info_raw)
         R, n, m = self._rows(mem), self.n, self.m
         X = np.zeros((R, n)); Y = np.zeros((R, max(m, 1)))
         info = np.zeros((R, 8)); DX = np.zeros((R, n)); DY = np.zeros((R, max(m, 1)))
-        call, f, lead = self._entry("get", mem)
-        rc = f(self._h, *lead, abi.fptr(X), _p(Y if m else None), abi.fptr(info), abi.fptr(DX), _p(DY if m else None))
-        if rc:
-            raise RuntimeError("%s failed (%d)" % (call, rc))
+        self._get(False, mem, X, Y if m else None, info, DX, DY if m else None)
         out = SimpleNamespace(x=X, y=Y[:, :m], dual_inf_cert=DX, prim_inf_cert=DY[:, :m], info_raw=info)
         if mem is None and isinstance(self._status_polish, str):   # polish(fetch=False) ran: the work is done, the call reports it
             sp = np.zeros(self.B, np.int64)
@@ -934,6 +834,14 @@ class BatchOSQP:
         sp = self._status_polish
         out.status_polish = np.zeros(R, np.int64) if not isinstance(sp, np.ndarray) else sp[slice(None) if mem is None else mem].copy()
         return _info_columns(out, info)
+
+    def _get(self, dev, mem, X, Y, info, DX, DY):
+        """The one body of results and results_into: X, DX [R, n], Y, DY [R, m], info [R, 8] from the handle (None = skip)."""
+        arrays = ((X, self.n, "X"), (Y, self.m, "Y"), (info, 8, "info"), (DX, self.n, "DX"), (DY, self.m, "DY"))
+        call, f, lead = self._entry("get", mem, dev)
+        rc = f(self._h, *lead, *((self._dev(a, k, name, writable=True, rows=self._rows(mem)) if dev else _p(a)) for a, k, name in arrays))
+        if rc:
+            raise RuntimeError("%s failed (%d)%s" % (call, rc, _BAD_POINTER if dev and rc == 1 else ""))
 
     def results_into(self, X=None, Y=None, info=None, DX=None, DY=None, status_polish=None, members=None):
         """The results into device arrays of the caller's (None = skip): X, DX [B, n], Y, DY [B, m], info [B, 8]
@@ -948,19 +856,14 @@ class BatchOSQP:
         mem = None if members is None else self._members(members, "results_into")
         if mem is not None and status_polish is not None:
             raise ValueError("results_into(members=...) takes no status_polish: it is a [B] array of the whole-batch polish")
-        d = lambda a, cols, name: self._dev(a, cols, name, writable=True, rows=self._rows(mem))
-        call, f, lead = self._entry("get", mem, dev=True)
-        rc = f(self._h, *lead, d(X, self.n, "X"), d(Y, self.m, "Y"), d(info, 8, "info"), d(DX, self.n, "DX"), d(DY, self.m, "DY"))
-        if rc:
-            raise RuntimeError("%s failed (%d)%s" % (call, rc, _BAD_POINTER if rc == 1 else ""))
+        self._get(True, mem, X, Y, info, DX, DY)
         if status_polish is not None:
             self._unserved("results_into(status_polish=...)")
             rc = self._lib.osqp_amd_batch_polish_status_dev(
                 self._h, device_view(status_polish, (self.B,), "<i4", True, "status_polish"))
             if rc:
                 raise RuntimeError("osqp_amd_batch_polish_status_dev failed (%d)%s"
-                                   % (rc, ": no solve has run on the current problem" if rc == 7 else
-                                      _BAD_POINTER if rc == 1 else ""))
+                                   % (rc, self._unsolved(None) if rc == 7 else _BAD_POINTER if rc == 1 else ""))
 
     def adjoint_into(self, dX, dY, dq, dl, du, dPx=None, dAx=None, active=None, status_adjoint=None, members=None):
         """adjoint() between device arrays of the caller's: from dX [B, n] and dY [B, m] (None = 0) into dq [B, n], dl, du
@@ -974,32 +877,7 @@ class BatchOSQP:
                              "takes and returns host arrays")
         if dX is None or dq is None or (self.m and (dl is None or du is None)):
             raise ValueError("adjoint_into needs dX, dq and, for m > 0, dl and du")
-        B, n, m, nP, nA = self.B, self.n, self.m, self.Pu.nnz, self.Ah.nnz
-        flat = len(dX.__cuda_array_interface__["shape"]) != 3     # as adjoint(): [B, n] takes the single-cotangent entry point
-        D, call, lead = 1, "osqp_amd_batch_adjoint_dev", ()
-        mem = None if members is None else self._members(members, "adjoint_into")
-        if mem is not None:                       # compact arrays: B stands for the listed members from here on
-            B = int(mem.size)
-        if not flat:
-            try:
-                dX, dY, D = check_adjoint_multi(B, n, m, dX, dY, dq=(dq, n), dl=(dl, m), du=(du, m), dPx=(dPx, nP), dAx=(dAx, nA))
-            except ValueError as e:
-                raise self._compact(e, mem) from None
-            call, lead = "osqp_amd_batch_adjoint_multi_dev", (D,)
-        if mem is not None:
-            call, lead = "osqp_amd_batch_adjoint_members_dev", (abi.iptr(mem), B, D)
-
-        def d(a, cols, name, writable=True):
-            if a is None:
-                return None
-            return device_view(a, (B, cols) if flat else (B, D, cols), "<f8", writable, name) or None
-        rc = getattr(self._lib, call)(
-            self._h, *lead, d(dX, n, "dX", False), d(dY, m, "dY", False), d(dq, n, "dq"), d(dl, m, "dl"), d(du, m, "du"),
-            d(dPx, nP, "dPx"), d(dAx, nA, "dAx"), self._dev(active, m, "active", "<i4", True, rows=B),
-            None if status_adjoint is None else device_view(status_adjoint, (B,), "<i4", True, "status_adjoint"))
-        if rc:
-            raise RuntimeError("%s failed (%d)%s" % (call, rc, ": no solve has run on the current problem" if rc == 7 else
-                                                     _BAD_POINTER if rc == 1 else ""))
+        self._adjoint("adjoint_into", True, members, dX, dY, dict(dq=dq, dl=dl, du=du, dPx=dPx, dAx=dAx), active, status_adjoint)
 
     def tangent_into(self, dx, dy, dQ=None, dL=None, dU=None, dPx=None, dAx=None, active=None, status_tangent=None,
                      members=None):
@@ -1013,37 +891,13 @@ class BatchOSQP:
                              "takes and returns host arrays")
         if dx is None or (self.m and dy is None):
             raise ValueError("tangent_into needs dx and, for m > 0, dy")
-        B, n, m = self.B, self.n, self.m
-        mem = None if members is None else self._members(members, "tangent_into")
-        if mem is not None:                       # compact arrays: B stands for the listed members from here on
-            B = int(mem.size)
-        try:
-            dQ, dL, dU, dPx, dAx, D, flat = check_tangent(B, n, m, self.Pu.nnz, self.Ah.nnz, dQ, dL, dU, dPx, dAx, dx=dx, dy=dy)
-        except ValueError as e:
-            raise self._compact(e, mem) from None
-
-        def d(a, cols, name, writable=False):
-            if a is None:
-                return None
-            return device_view(a, (B, cols) if flat else (B, D, cols), "<f8", writable, name) or None
-        call, lead = ("osqp_amd_batch_tangent_dev", ()) if mem is None else \
-                     ("osqp_amd_batch_tangent_members_dev", (abi.iptr(mem), B))
-        rc = getattr(self._lib, call)(
-            self._h, *lead, D, d(dQ, n, "dQ"), d(dL, m, "dL"), d(dU, m, "dU"), d(dPx, self.Pu.nnz, "dPx"), d(dAx, self.Ah.nnz, "dAx"),
-            d(dx, n, "dx", True), d(dy, m, "dy", True), self._dev(active, m, "active", "<i4", True, rows=B),
-            None if status_tangent is None else device_view(status_tangent, (B,), "<i4", True, "status_tangent"))
-        if rc:
-            raise RuntimeError("%s failed (%d)%s"
-                               % (call, rc, ": no solve has run on the current problem" if rc == 7 else
-                                  _BAD_POINTER if rc == 1 else ""))
+        self._tangent("tangent_into", True, members, (dQ, dL, dU, dPx, dAx), dict(dx=dx, dy=dy), active, status_tangent)
 
     def member_workspace(self, qp):
         """Test hook: member qp's workspace as the last setup / update / solve left it -- D, E, c, rho (scalar),
         ctype (-1 free, 0 inequality, 1 equality), scaled Pv / Av (CSC order of triu(P) / A) and the kernel's
         K^-1 as an NP x NP matrix (padded with identity to NP = 64 or 128; the streamed engine: n rounded up to 32)."""
-        if self._many is not None:
-            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): there is no packed batch "
-                               "workspace to read" % BATCH_MAX_N)
+        self._kernel_batch("member_workspace", why="there is no packed batch workspace to read")
         NP = self.shape()[1]
         D = np.zeros(self.n); E = np.zeros(max(self.m, 1)); c = np.zeros(1); rho = np.zeros(1)
         ct = np.zeros(max(self.m, 1), np.int64); Pv = np.zeros(max(self.Pu.nnz, 1)); Av = np.zeros(max(self.Ah.nnz, 1))
@@ -1060,14 +914,9 @@ class BatchOSQP:
         """The result arrays as they sit in HBM -- X [B, n], Y [B, m], info8 [B, 8] -- as objects carrying
         `__cuda_array_interface__` (no copy; `torch.as_tensor(a, device="cuda")` wraps them for a device-side
         gather).  Valid until the next solve / cleanup."""
-        if self._many is not None:
-            raise RuntimeError("this batch runs one single-QP engine per member (n > %d): its results are host arrays "
-                               "(results()); there is no packed device image to wrap" % BATCH_MAX_N)
-        f = self._lib.osqp_amd_batch_device_ptrs
-        f.restype = abi.c_int
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        self._kernel_batch("device_arrays", why="its results are host arrays (results()); there is no packed device image to wrap")
         px, py, pi = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        if f(self._h, C.byref(px), C.byref(py), C.byref(pi)):
+        if self._lib.osqp_amd_batch_device_ptrs(self._h, C.byref(px), C.byref(py), C.byref(pi)):
             raise RuntimeError("osqp_amd_batch_device_ptrs failed")
 
         class _Dev:
@@ -1077,8 +926,7 @@ class BatchOSQP:
 
     def cleanup(self):
         if getattr(self, "_many", None):
-            for s in self._many:
-                s.cleanup()
+            self._many.cleanup()
             self._many = None
         if self._h is not None:
             self._lib.osqp_amd_batch_cleanup(self._h)

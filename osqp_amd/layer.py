@@ -41,95 +41,237 @@ def _hand_over(device):
     torch.cuda.current_stream(device).synchronize()
 
 
-class _BatchQPFunction(torch.autograd.Function):
+class _HostSide:
+    """The array adapter of the host route: what a layer does with tensors on their way to and from a handle that takes
+    and returns host numpy arrays (BatchOSQP's host forms, OSQP).  `like`: the dtype and device the outputs take."""
+    route, index, where = "host", None, {}
+    update_failed = "BatchOSQP.update failed (%d)%s"
+    take = staticmethod(_host)                   # a tensor as the handle takes it
+    host = staticmethod(lambda a: a)             # ... and what take() gave as setup and _class_clash take it
+    hand_over = staticmethod(lambda: None)       # (numpy arrays are complete when they are made)
+    bounds = staticmethod(lambda L, U, m: (L, U))
+
+    def __init__(self, like):
+        self.like = dict(dtype=like.dtype, device=like.device)
+
+    def save(self, ctx, tensors, args):
+        ctx.args = args
+
+    def saved(self, ctx):
+        return ctx.args
+
+    def outputs(self, r):
+        return torch.as_tensor(r.x, **self.like), torch.as_tensor(r.y, **self.like)
+
+    def own(self, layer, which):
+        return (layer.P if which == "P" else layer.A).data
+
+    def results(self, h, polish):
+        return h.polish() if polish else h.results()
+
+    def adjoint(self, layer, gX, gY, need, ref):
+        """(dq, dl, du, dPx, dAx) -- None where not needed --, and the call's result for the layer's status attributes."""
+        h = layer.h
+        dX = np.zeros(((h.B,) if layer.batched else ()) + (h.n,)) if gX is None else _host(gX)
+        a = h.adjoint(dX, _host(gY), matrices=need[3] or need[4])
+        return [torch.as_tensor(g, dtype=ref.dtype, device=ref.device) if w else None
+                for g, w in zip((a.dq, a.dl, a.du, a.dPx, a.dAx), need)], a
+
+    def tangent(self, layer, tangents):
+        r = layer.h.tangent(*(_host(t) for t in tangents))
+        like = dict(dtype=torch.float64, device=next((t.device for t in tangents if t is not None), "cpu"))
+        return torch.as_tensor(r.dx, **like), torch.as_tensor(r.dy, **like), r
+
+
+class _DeviceSide:
+    """The array adapter of the device route (BatchQPLayer on CUDA tensors): contiguous tensors go to the handle's _dev
+    forms as they are, outputs are torch.empty on the device and filled by the _into calls, and torch's current stream is
+    synchronised before every hand-over (the handle works on a stream of its own)."""
+    route, take = "device", staticmethod(_dev)
+    host = staticmethod(_host)
+    update_failed = ("BatchOSQP.update failed (%d: some lower bound exceeds its upper bound, or a tensor is not device memory "
+                     "the library's HIP runtime knows -- import torch before the library is first loaded)%s")
+
+    def __init__(self, like):
+        self.device = like.device
+        self.index = like.device.index if like.device.index is not None else torch.cuda.current_device()
+        self.where = dict(device=self.index)
+
+    def hand_over(self):
+        _hand_over(self.device)
+
+    def new(self, *shape, dtype=torch.float64):
+        return torch.empty(shape, dtype=dtype, device=self.device)
+
+    def save(self, ctx, tensors, args):
+        ctx.save_for_backward(*tensors)
+        ctx.save_for_forward(*tensors)           # (jvp sees only these)
+
+    def saved(self, ctx):
+        return tuple(_dev(t) for t in ctx.saved_tensors)
+
+    def outputs(self, r):
+        # (tensor objects of their own, so that last_results stays outside the graph; they share its storage, as the
+        # host route's outputs share the numpy arrays of last_results)
+        return r.x.detach(), r.y.detach()
+
+    def bounds(self, L, U, m):
+        return (L, U) if m else (None, None)
+
+    def own(self, layer, which):
+        if which not in layer._vals or layer._vals[which].device != self.device:
+            layer._vals[which] = torch.as_tensor((layer.P if which == "P" else layer.A).data, dtype=torch.float64,
+                                                 device=self.device)
+        return layer._vals[which]
+
+    def results(self, h, polish):
+        if polish:
+            h.polish(fetch=False)
+        X, Y, sp = self.new(h.B, h.n), self.new(h.B, h.m), self.new(h.B, dtype=torch.int32)
+        self.hand_over()
+        h.results_into(X=X, Y=Y if h.m else None, status_polish=sp)
+        return SimpleNamespace(x=X, y=Y, status_polish=sp)
+
+    def adjoint(self, layer, gX, gY, need, ref):
+        h, m = layer.h, layer.h.m > 0
+        # both inputs are made contiguous here, before the hand-over: a copy queued on torch's stream after it
+        # would race with the handle's stream (the gradient of a sum is an expanded, non-contiguous tensor)
+        dX = torch.zeros((h.B, h.n), dtype=torch.float64, device=self.device) if gX is None else _dev(gX)
+        dY = _dev(gY) if m else None
+        g = dict(dq=self.new(h.B, h.n), dl=self.new(h.B, h.m) if m else None, du=self.new(h.B, h.m) if m else None,
+                 dPx=self.new(h.B, h.Pu.nnz) if need[3] else None, dAx=self.new(h.B, h.Ah.nnz) if need[4] else None)
+        sa = self.new(h.B, dtype=torch.int32)
+        self.hand_over()
+        h.adjoint_into(dX, dY, status_adjoint=sa, **g)
+        zero = lambda w: self.new(h.B, 0).zero_() if w else None        # (m = 0: the empty gradients of L, U)
+        return [g["dq"], g["dl"] if m else zero(need[1]), g["du"] if m else zero(need[2]), g["dPx"], g["dAx"]], \
+            SimpleNamespace(status_adjoint=sa)
+
+    def tangent(self, layer, tangents):
+        h, m = layer.h, layer.h.m > 0
+        tQ, tL, tU, tPx, tAx = tangents
+        # made contiguous before the hand-over, as in adjoint
+        t = dict(dQ=_dev(tQ), dL=_dev(tL) if m else None, dU=_dev(tU) if m else None, dPx=_dev(tPx), dAx=_dev(tAx))
+        tX, tY, st = self.new(h.B, h.n), self.new(h.B, h.m), self.new(h.B, dtype=torch.int32)
+        self.hand_over()
+        h.tangent_into(tX, tY if m else None, status_tangent=st, **t)
+        return tX, tY, SimpleNamespace(status_tangent=st)
+
+
+def _bring_back(ctx):
+    """The layer of a graph, its handle holding the graph's problem: where the handle has solved another one since, this
+    one is solved again."""
+    layer = ctx.layer
+    if layer._serial != ctx.serial:
+        layer._solve(ctx.side, *ctx.side.saved(ctx))
+        ctx.serial = layer._serial
+    return layer
+
+
+class _QPFunction(torch.autograd.Function):
+    """Both layers' autograd function: the route of a call is the adapter the layer chooses for its first input."""
+
     @staticmethod
     def forward(ctx, layer, Q, L, U, Px, Ax):
-        if Q.is_cuda:
-            ctx.layer, ctx.route = layer, "device"
-            ctx.save_for_backward(Q, L, U, Px, Ax)
-            ctx.save_for_forward(Q, L, U, Px, Ax)      # (jvp sees only these)
-            ctx.set_materialize_grads(False)
-            r = layer._solve_device(*(_dev(t) for t in (Q, L, U, Px, Ax)))
-            ctx.serial = layer._serial
-            # (tensor objects of their own, so that last_results stays outside the graph; they share its storage, as the
-            # host route's outputs share the numpy arrays of last_results)
-            return r.x.detach(), r.y.detach()
-        layer.last_route = ctx.route = "host"
-        args = tuple(_host(t) for t in (Q, L, U, Px, Ax))
-        r = layer._solve(*args)
-        ctx.layer, ctx.args, ctx.serial = layer, args, layer._serial
+        ctx.layer, ctx.side = layer, layer._side(Q)
+        args = tuple(ctx.side.take(t) for t in (Q, L, U, Px, Ax))
+        ctx.side.save(ctx, (Q, L, U, Px, Ax), args)
         ctx.set_materialize_grads(False)
-        like = dict(dtype=Q.dtype, device=Q.device)
-        return torch.as_tensor(r.x, **like), torch.as_tensor(r.y, **like)
+        r = layer._solve(ctx.side, *args)
+        ctx.serial = layer._serial
+        return ctx.side.outputs(r)
 
     @staticmethod
     def backward(ctx, gX, gY):
-        layer = ctx.layer
         need = ctx.needs_input_grad[1:]
         if not any(need) or (gX is None and gY is None):
             return (None,) * 6
-        ref = gX if gX is not None else gY
-        if ctx.route == "device":
-            if layer._serial != ctx.serial:
-                layer._solve_device(*(_dev(t) for t in ctx.saved_tensors))
-                ctx.serial = layer._serial
-            h, new = layer.h, lambda *shape, **kw: torch.empty(shape, device=ref.device, **{"dtype": torch.float64, **kw})
-            m = h.m > 0
-            # both inputs are made contiguous here, before the hand-over: a copy queued on torch's stream after it
-            # would race with the handle's stream (the gradient of a sum is an expanded, non-contiguous tensor)
-            dX = torch.zeros((h.B, h.n), dtype=torch.float64, device=ref.device) if gX is None else _dev(gX)
-            dY = _dev(gY) if m else None
-            g = dict(dq=new(h.B, h.n), dl=new(h.B, h.m) if m else None, du=new(h.B, h.m) if m else None,
-                     dPx=new(h.B, h.Pu.nnz) if need[3] else None, dAx=new(h.B, h.Ah.nnz) if need[4] else None)
-            sa = new(h.B, dtype=torch.int32)
-            _hand_over(ref.device)
-            h.adjoint_into(dX, dY, status_adjoint=sa, **g)
-            layer.last_status_adjoint = sa
-            zero = lambda w, cols: new(h.B, cols).zero_() if w else None        # (m = 0: the empty gradients of L, U)
-            outs = (g["dq"], g["dl"] if m else zero(need[1], 0), g["du"] if m else zero(need[2], 0),
-                    layer._shared_grad(g["dPx"]), layer._shared_grad(g["dAx"]))
-            return (None,) + tuple(o if w else None for o, w in zip(outs, need))
-        if layer._serial != ctx.serial:      # the handle has solved another problem since: bring this one back
-            layer._solve(*ctx.args)
-            ctx.serial = layer._serial
-        dX = np.zeros((layer.h.B, layer.h.n)) if gX is None else _host(gX)
-        a = layer.h.adjoint(dX, _host(gY), matrices=need[3] or need[4])
-        layer.last_status_adjoint = a.status_adjoint
-        outs = (a.dq, a.dl, a.du, a.dPx, a.dAx)
-        outs = tuple(torch.as_tensor(g, dtype=ref.dtype, device=ref.device) if w else None for g, w in zip(outs, need))
-        return (None,) + outs[:3] + (layer._shared_grad(outs[3]), layer._shared_grad(outs[4]))
+        layer = _bring_back(ctx)
+        outs, a = ctx.side.adjoint(layer, gX, gY, need, gX if gX is not None else gY)
+        layer._note("adjoint", a)
+        outs = outs[:3] + [layer._shared_grad(g) for g in outs[3:]]
+        return (None,) + tuple(g if w else None for g, w in zip(outs, need))
 
     @staticmethod
     def jvp(ctx, _, tQ, tL, tU, tPx, tAx):
         """Forward mode (torch.autograd.forward_ad): the tangents of X and Y from those of Q, L, U, Px, Ax (None = 0)
-        by BatchOSQP.tangent on the host route and tangent_into on the device route."""
+        by the handle's tangent on the host route and tangent_into on the device route."""
         layer = ctx.layer
         tPx, tAx = layer._shared_tangent(tPx), layer._shared_tangent(tAx)
-        if ctx.route == "device":
-            if layer._serial != ctx.serial:
-                layer._solve_device(*(_dev(t) for t in ctx.saved_tensors))
-                ctx.serial = layer._serial
-            h, dev = layer.h, layer.last_results.x.device
-            m = h.m > 0
-            # made contiguous before the hand-over, as in backward
-            t = dict(dQ=_dev(tQ), dL=_dev(tL) if m else None, dU=_dev(tU) if m else None, dPx=_dev(tPx), dAx=_dev(tAx))
-            tX = torch.empty((h.B, h.n), dtype=torch.float64, device=dev)
-            tY = torch.empty((h.B, h.m), dtype=torch.float64, device=dev)
-            st = torch.empty((h.B,), dtype=torch.int32, device=dev)
-            _hand_over(dev)
-            h.tangent_into(tX, tY if m else None, status_tangent=st, **t)
-            layer.last_status_tangent = st
-            return tX, tY
-        if layer._serial != ctx.serial:      # the handle has solved another problem since: bring this one back
-            layer._solve(*ctx.args)
-            ctx.serial = layer._serial
-        r = layer.h.tangent(*(_host(t) for t in (tQ, tL, tU, tPx, tAx)))
-        layer.last_status_tangent = r.status_tangent
-        like = dict(dtype=torch.float64, device=next((t.device for t in (tQ, tL, tU, tPx, tAx) if t is not None), "cpu"))
-        return torch.as_tensor(r.dx, **like), torch.as_tensor(r.dy, **like)
+        _bring_back(ctx)
+        tX, tY, r = ctx.side.tangent(layer, (tQ, tL, tU, tPx, tAx))
+        layer._note("tangent", r)
+        return tX, tY
 
 
-class BatchQPLayer(torch.nn.Module):
+_BatchQPFunction = _QPFunction       # (the name it had while each layer had a function of its own)
+
+
+class _Layer(torch.nn.Module):
+    """What BatchQPLayer and QPLayer share: the pattern of P and A, one live handle `h`, which of P / A hold values a
+    caller gave (`_own`), the count of solves (`_serial`: a graph whose count is not the layer's has to bring its problem
+    back before it is differentiated) and the checks of forward.  `batched`: shapes carry a leading B."""
+    batched = True
+
+    def __init__(self, P, A):
+        super().__init__()
+        self.P = sparse.triu(sparse.csc_matrix(P), format="csc"); self.P.sort_indices()
+        self.A = sparse.csc_matrix(A); self.A.sort_indices()
+        self.h = None
+        self._serial = 0
+        self._own = [False, False]       # the handle holds values of P / A given by a caller
+        self.last_results = self.last_status_adjoint = self.last_status_tangent = None
+
+    def _side(self, Q):
+        return _HostSide(Q)
+
+    def _shared_grad(self, g):
+        return g
+
+    def _shared_tangent(self, t):
+        return t
+
+    def _note(self, which, r):
+        setattr(self, "last_status_" + which, getattr(r, "status_" + which))
+
+    def _values(self, side, Px, Ax):
+        """The values to bring to a live handle: the caller's, or -- where a caller gave some last time and none this
+        time -- the layer's own again; None: the handle holds the right ones."""
+        return (Px if Px is not None else (side.own(self, "P") if self._own[0] else None),
+                Ax if Ax is not None else (side.own(self, "A") if self._own[1] else None))
+
+    def _solved(self, results, Px, Ax):
+        self._own = [Px is not None, Ax is not None]
+        self.last_results = results
+        self._serial += 1
+        return results
+
+    def _check(self, tensors, shared=False):
+        """dtype, shape and device of the inputs of forward; shared: Px / Ax may be the [k] values of one shared model."""
+        names = ("Q", "L", "U", "Px", "Ax") if self.batched else ("q", "l", "u", "Px", "Ax")
+        first = tensors[0]
+        lead = (first.shape[0] if first.dim() == 2 else -1,) if self.batched else ()
+        n, m = self.P.shape[0], self.A.shape[0]
+        for name, t, cols in zip(names, tensors, (n, m, m, self.P.nnz, self.A.nnz)):
+            if t is None:
+                continue
+            if t.dtype != torch.float64:
+                raise TypeError("%s must be a float64 tensor, not %s" % (name, t.dtype))
+            if shared and name in ("Px", "Ax") and t.dim() == 1:       # the shared model's values
+                if tuple(t.shape) != (cols,):
+                    raise ValueError("%s must be [%d] (the shared model of engine='common'), not %s" % (name, cols, tuple(t.shape)))
+            elif tuple(t.shape) != lead + (cols,):
+                raise ValueError("%s must be [%s%d], not %s" % (name, "B, " if self.batched else "", cols, tuple(t.shape)))
+            if t.device != first.device:
+                raise ValueError("%s is on %s and %s on %s: every tensor of a call lives on one device"
+                                 % (name, t.device, names[0], first.device))
+
+    def cleanup(self):
+        if self.h is not None:
+            self.h.cleanup(); self.h = None
+
+
+class BatchQPLayer(_Layer):
     """x*(Q, L, U, Px, Ax) = argmin 1/2 x'Px + q'x  s.t.  l <= Ax <= u for a batch of QPs with the shared sparsity
     pattern of P (n x n; the upper triangle is used) and A (m x n), differentiable in every argument.
 
@@ -158,19 +300,17 @@ class BatchQPLayer(torch.nn.Module):
     took: "host" or "device"."""
 
     def __init__(self, P, A, engine="auto", polish=True, **settings):
-        super().__init__()
         if engine == "common" and not settings.get("shared_kkt"):
             raise ValueError("BatchQPLayer needs polish and adjoint, which the common-K engine (engine='common') does not "
                              "serve without its shared KKT pieces: pass shared_kkt=True, or use engine='auto' or 'streamed'")
-        self.P = sparse.triu(sparse.csc_matrix(P), format="csc"); self.P.sort_indices()
-        self.A = sparse.csc_matrix(A); self.A.sort_indices()
+        super().__init__(P, A)
         self.engine, self.polish, self.settings = engine, polish, settings
-        self.h = None
-        self._serial = 0
-        self._own = [False, False]       # the handle holds per-member values of P / A given by a caller
-        self.last_results = self.last_status_adjoint = self.last_status_tangent = self.last_route = None
+        self.last_route = None
         self._device = None              # device route: the device index the handle was set up on
         self._vals = {}                  # the layer's own P / A values as tensors on the handle's device
+
+    def _side(self, Q):
+        return _DeviceSide(Q) if Q.is_cuda else _HostSide(Q)
 
     def _shared_grad(self, g):
         """engine="common": the gradient of a shared value is the sum over the members of the adjoint's [B, k] rows."""
@@ -196,26 +336,28 @@ class BatchQPLayer(torch.nn.Module):
         if rc:
             raise RuntimeError("BatchOSQP.%s failed (%d)" % (call, rc))
 
-    def _solve(self, Q, L, U, Px, Ax):
-        if self.h is not None and self.h.B != Q.shape[0]:
+    def _solve(self, side, Q, L, U, Px, Ax):
+        """update -> solve -> polish -> results on the live handle, from what side.take() made of the inputs.  The first
+        call, and one with another B or (device route) on another device, sets the handle up from host copies."""
+        self.last_route = side.route
+        if self.h is not None and (self.h.B != Q.shape[0] or (side.index is not None and self._device != side.index)):
             self.h.cleanup(); self.h = None
+        m = self.A.shape[0] > 0
+        side.hand_over()
         if self.h is None:
-            self.h = self._setup(Q, L, U, Px, Ax)
-            self._device = None
+            self.h = self._setup(*(side.host(t) for t in (Q, L, U, Px, Ax)), **side.where)
+            self._device = side.index
         else:
-            rc = self.h.update(Q=Q, L=L, U=U)
+            Lb, Ub = side.bounds(L, U, m)
+            rc = self.h.update(Q=Q, L=Lb, U=Ub)
             if rc:
-                raise RuntimeError("BatchOSQP.update failed (%d)%s" % (rc, self._class_clash(L, U)))
-            # values a caller gave last time and not this time go back to the layer's own
-            vP = Px if Px is not None else (self.P.data if self._own[0] else None)
-            vA = Ax if Ax is not None else (self.A.data if self._own[1] else None)
+                raise RuntimeError(side.update_failed % (rc, self._class_clash(side.host(L), side.host(U)) if m else ""))
+            vP, vA = self._values(side, Px, Ax)
             if vP is not None or vA is not None:
+                side.hand_over()
                 self._update_values(vP, vA)
-        self._own = [Px is not None, Ax is not None]
         self.h.solve(fetch=False)
-        self.last_results = self.h.polish() if self.polish else self.h.results()
-        self._serial += 1
-        return self.last_results
+        return self._solved(side.results(self.h, self.polish), Px, Ax)
 
     def _class_clash(self, L, U):
         """Why a common-K handle refused the bounds L, U [B, m] (host arrays): the first member and row whose class
@@ -232,116 +374,17 @@ class BatchQPLayer(torch.nn.Module):
         return (": row %d of member %d has another class (loose / inequality / equality) than in member 0 -- the common-K "
                 "engine needs one class per row over the batch" % (bad[0][1], bad[0][0]))
 
-    def _own_values(self, which, device):
-        if which not in self._vals or self._vals[which].device != device:
-            self._vals[which] = torch.as_tensor((self.P if which == "P" else self.A).data, dtype=torch.float64, device=device)
-        return self._vals[which]
-
-    def _solve_device(self, Q, L, U, Px, Ax):
-        """_solve for contiguous CUDA tensors.  The first call sets the handle up from host copies, on the tensors'
-        device; every later one hands the device pointers over."""
-        dev = Q.device
-        index = dev.index if dev.index is not None else torch.cuda.current_device()
-        self.last_route = "device"
-        if self.h is not None and (self.h.B != Q.shape[0] or self._device != index):
-            self.h.cleanup(); self.h = None
-        m = self.A.shape[0] > 0
-        _hand_over(dev)
-        if self.h is None:
-            self.h = self._setup(*(_host(t) for t in (Q, L, U, Px, Ax)), device=index)
-            self._device = index
-        else:
-            rc = self.h.update(Q=Q, L=L if m else None, U=U if m else None)
-            if rc:
-                raise RuntimeError("BatchOSQP.update failed (%d: some lower bound exceeds its upper bound, or a tensor is "
-                                   "not device memory the library's HIP runtime knows -- import torch before the library "
-                                   "is first loaded)%s" % (rc, self._class_clash(_host(L), _host(U)) if m else ""))
-            vP = Px if Px is not None else (self._own_values("P", dev) if self._own[0] else None)
-            vA = Ax if Ax is not None else (self._own_values("A", dev) if self._own[1] else None)
-            if vP is not None or vA is not None:
-                _hand_over(dev)
-                self._update_values(vP, vA)
-        self._own = [Px is not None, Ax is not None]
-        self.h.solve(fetch=False)
-        if self.polish:
-            self.h.polish(fetch=False)
-        B = Q.shape[0]
-        X = torch.empty((B, self.h.n), dtype=torch.float64, device=dev)
-        Y = torch.empty((B, self.h.m), dtype=torch.float64, device=dev)
-        sp = torch.empty((B,), dtype=torch.int32, device=dev)
-        _hand_over(dev)
-        self.h.results_into(X=X, Y=Y if m else None, status_polish=sp)
-        self.last_results = SimpleNamespace(x=X, y=Y, status_polish=sp)
-        self._serial += 1
-        return self.last_results
-
     def forward(self, Q, L, U, Px=None, Ax=None, return_y=False):
-        B = Q.shape[0] if Q.dim() == 2 else -1
-        n, m = self.P.shape[0], self.A.shape[0]
         common = self.engine == "common"
-        for name, t, cols in (("Q", Q, n), ("L", L, m), ("U", U, m), ("Px", Px, self.P.nnz), ("Ax", Ax, self.A.nnz)):
-            if t is None:
-                continue
-            if t.dtype != torch.float64:
-                raise TypeError("%s must be a float64 tensor, not %s" % (name, t.dtype))
-            if common and name in ("Px", "Ax") and t.dim() == 1:       # the shared model's values
-                if tuple(t.shape) != (cols,):
-                    raise ValueError("%s must be [%d] (the shared model of engine='common'), not %s" % (name, cols, tuple(t.shape)))
-            elif tuple(t.shape) != (B, cols):
-                raise ValueError("%s must be [B, %d], not %s" % (name, cols, tuple(t.shape)))
-            if t.device != Q.device:
-                raise ValueError("%s is on %s and Q on %s: every tensor of a call lives on one device" % (name, t.device, Q.device))
+        self._check((Q, L, U, Px, Ax), shared=common)
         if common and any(t is not None and t.dim() != 1 for t in (Px, Ax)):
             raise ValueError("engine='common' shares P and A over the batch: the layer takes no Px / Ax per member ([B, k]); "
                              "pass the shared model's values as [k]")
-        X, Y = _BatchQPFunction.apply(self, Q, L, U, Px, Ax)
+        X, Y = _QPFunction.apply(self, Q, L, U, Px, Ax)
         return (X, Y) if return_y else X
 
-    def cleanup(self):
-        if self.h is not None:
-            self.h.cleanup(); self.h = None
 
-
-class _QPFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, layer, q, l, u, Px, Ax):
-        args = tuple(_host(t) for t in (q, l, u, Px, Ax))
-        r = layer._solve(*args)
-        ctx.layer, ctx.args, ctx.serial = layer, args, layer._serial
-        ctx.set_materialize_grads(False)
-        like = dict(dtype=q.dtype, device=q.device)
-        return torch.as_tensor(r.x, **like), torch.as_tensor(r.y, **like)
-
-    @staticmethod
-    def _bring_back(ctx):
-        layer = ctx.layer
-        if layer._serial != ctx.serial:      # the handle has solved another problem since: bring this one back
-            layer._solve(*ctx.args)
-            ctx.serial = layer._serial
-        return layer
-
-    @staticmethod
-    def backward(ctx, gx, gy):
-        need = ctx.needs_input_grad[1:]
-        if not any(need) or (gx is None and gy is None):
-            return (None,) * 6
-        ref = gx if gx is not None else gy
-        layer = _QPFunction._bring_back(ctx)
-        a = layer.h.adjoint(np.zeros(layer.h.n) if gx is None else _host(gx), _host(gy), matrices=need[3] or need[4])
-        layer.last_status_adjoint, layer.last_kkt_res = a.status_adjoint, a.kkt_res
-        outs = (a.dq, a.dl, a.du, a.dPx, a.dAx)
-        return (None,) + tuple(torch.as_tensor(g, dtype=ref.dtype, device=ref.device) if w else None for g, w in zip(outs, need))
-
-    @staticmethod
-    def jvp(ctx, _, tq, tl, tu, tPx, tAx):
-        layer = _QPFunction._bring_back(ctx)
-        r = layer.h.tangent(*(_host(t) for t in (tq, tl, tu, tPx, tAx)))
-        layer.last_status_tangent, layer.last_kkt_res = r.status_tangent, r.kkt_res
-        like = dict(dtype=torch.float64, device=next((t.device for t in (tq, tl, tu, tPx, tAx) if t is not None), "cpu"))
-        return torch.as_tensor(r.dx, **like), torch.as_tensor(r.dy, **like)
-
-
-class QPLayer(torch.nn.Module):
+class QPLayer(_Layer):
     """x*(q, l, u, Px, Ax) = argmin 1/2 x'Px + q'x  s.t.  l <= Ax <= u for ONE sparse QP on the single-QP engine (the
     engine of the large problems: no limit on n), differentiable in every argument.
 
@@ -361,48 +404,31 @@ class QPLayer(torch.nn.Module):
     way to and from the handle (the single-QP engine's C ABI takes host pointers; a device-array route exists for the
     batch engines only, BatchQPLayer): the outputs and gradients come back on the inputs' device."""
 
-    def __init__(self, P, A, **settings):
-        super().__init__()
-        self.P = sparse.triu(sparse.csc_matrix(P), format="csc"); self.P.sort_indices()
-        self.A = sparse.csc_matrix(A); self.A.sort_indices()
-        self.settings = dict(polish=1, **settings) if "polish" not in settings else dict(settings)
-        self.h = None
-        self._serial = 0
-        self._own = [False, False]       # the handle holds values of P / A given by a caller
-        self.last_results = self.last_status_adjoint = self.last_status_tangent = self.last_kkt_res = None
+    batched = False
 
-    def _solve(self, q, l, u, Px, Ax):
+    def __init__(self, P, A, **settings):
+        super().__init__(P, A)
+        self.settings = dict(polish=1, **settings) if "polish" not in settings else dict(settings)
+        self.last_kkt_res = None
+
+    def _note(self, which, r):
+        super()._note(which, r)
+        self.last_kkt_res = r.kkt_res
+
+    def _solve(self, side, q, l, u, Px, Ax):
         from . import OSQP
         if self.h is None:
             P = self.P if Px is None else sparse.csc_matrix((Px, self.P.indices, self.P.indptr), shape=self.P.shape)
             A = self.A if Ax is None else sparse.csc_matrix((Ax, self.A.indices, self.A.indptr), shape=self.A.shape)
             self.h = OSQP().setup(P=P, q=q, A=A, l=l, u=u, **self.settings)
         else:
-            # values a caller gave last time and not this time go back to the layer's own
-            vP = Px if Px is not None else (self.P.data if self._own[0] else None)
-            vA = Ax if Ax is not None else (self.A.data if self._own[1] else None)
+            vP, vA = self._values(side, Px, Ax)
             rc = self.h.update(q=q, l=l, u=u, Px=vP, Ax=vA)
             if rc:
                 raise RuntimeError("OSQP.update failed (%d)" % rc)
-        self._own = [Px is not None, Ax is not None]
-        self.last_results = self.h.solve()
-        self._serial += 1
-        return self.last_results
+        return self._solved(self.h.solve(), Px, Ax)
 
     def forward(self, q, l, u, Px=None, Ax=None, return_y=False):
-        n, m = self.P.shape[0], self.A.shape[0]
-        for name, t, k in (("q", q, n), ("l", l, m), ("u", u, m), ("Px", Px, self.P.nnz), ("Ax", Ax, self.A.nnz)):
-            if t is None:
-                continue
-            if t.dtype != torch.float64:
-                raise TypeError("%s must be a float64 tensor, not %s" % (name, t.dtype))
-            if tuple(t.shape) != (k,):
-                raise ValueError("%s must be [%d], not %s" % (name, k, tuple(t.shape)))
-            if t.device != q.device:
-                raise ValueError("%s is on %s and q on %s: every tensor of a call lives on one device" % (name, t.device, q.device))
+        self._check((q, l, u, Px, Ax))
         x, y = _QPFunction.apply(self, q, l, u, Px, Ax)
         return (x, y) if return_y else x
-
-    def cleanup(self):
-        if self.h is not None:
-            self.h.cleanup(); self.h = None
