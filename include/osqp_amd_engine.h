@@ -127,7 +127,7 @@ int hipeng_sync(hipeng *e);
  * qdldl_interface.c:350-376): b = [sigma x - q ; z - y/rho] on the host is
  * overwritten by [x_tilde ; z_tilde]. */
 int hipeng_kkt_solve(hipeng *e, c_float *b);
-/* The same solve without the refinement step hipeng_kkt_solve takes on the direct forms (res_kind 3 / 4): one application of
+/* The same solve without the refinement step hipeng_kkt_solve takes on the direct forms (form 3 / 4): one application of
  * the inverse the engine iterates with.  Used by the setup-time convexity probe and the direct-solve tests. */
 int hipeng_kkt_solve_unrefined(hipeng *e, c_float *b);
 
@@ -200,7 +200,7 @@ int hipeng_form_k_info(hipeng *e, long long out[4]);
 /* For the tests: K as the resident kernel holds it, as triplets; returns nnz(K) or a negative code. */
 long long hipeng_resident_dump(hipeng *e, int *row, int *col, double *val, long long cap);
 
-/* Dense-direct solve (engine.hip res_kind 4, csrc/dense_direct.h): test / measurement hook for its blocked inversion.
+/* Dense-direct solve (engine.hip FORM_DENSE_DIRECT, csrc/dense_direct.h): test / measurement hook for its blocked inversion.
  * A: n x n row-major symmetric positive definite host matrix, n a multiple of 128; Ainv: its inverse (explicit, by blocked
  * Gauss-Jordan on v_mfma_f64_16x16x4_f64); ms[0]: device time of the inversion, ms[1]: of one n x n x n GEMM of the same
  * kernel.  Returns 0, 1 when a pivot was not positive, or a HIPENG_ERR_* code. */

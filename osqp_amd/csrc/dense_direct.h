@@ -1,6 +1,6 @@
 // dense_direct.h -- included by engine.hip after the elimination and block forms (it uses Ctx, State, k_blk-style helpers).
 //
-// Dense-direct solve (res_kind 4): problems whose reduced matrix K = P + sigma I + A' rho~ A is SMALL AND DENSE -- BASELINE
+// Dense-direct solve (FORM_DENSE_DIRECT): problems whose reduced matrix K = P + sigma I + A' rho~ A is SMALL AND DENSE -- BASELINE
 // config 3, the Lasso QP: 5 000 feature variables tied together by 10 000 data rows of 750 entries.  There the PCG streams the
 // 90 MB of A twice per iteration, 22 times per ADMM iteration; the matrix it inverts piecemeal is only 5 000 x 5 000.
 // So K is formed as a dense matrix, inverted explicitly on the matrix cores whenever rho / sigma / the matrices change, and one

@@ -10,7 +10,7 @@ static int build_dense_direct(hipeng *e, const csc *P, const csc *A, bool small_
   if (const char *x = getenv("OSQP_AMD_DENSE_SMALL")) small_max = std::max(0, atoi(x));
   if (small_only && small_max == 0) return 0;
   const int n = e->n, m = e->m;
-  if (!want || e->res_on || e->res_kind != 0 || n == 0 || m == 0) return 0;
+  if (!want || e->form != FORM_STEPS || n == 0 || m == 0) return 0;
   auto gone = [&](int j) { return !e->erow.empty() && e->erow[j] >= 0; };
   // rows of A over the unknowns of the reduced system: dense (>= DD_DENSE_ROW entries: a row of R) or short (scattered)
   std::vector<char> isdense(m, 0), indense(n, 0), coupledP(n, 0);
@@ -110,7 +110,7 @@ static int build_dense_direct(hipeng *e, const csc *P, const csc *A, bool small_
     // (only where k_pcg_init's pass over [P | A'] is more than a launch: on small problems k_vd's own launch would cost more than it saves)
     if (one_gather && nnzA >= 2e5 && dev_alloc(e, &e->c.vd, (size_t)(n + m))) return HIPENG_ERR_HIP;
   }
-  e->res_kind = 4; e->res_on = e->res_use = true;
+  e->form = FORM_DENSE_DIRECT; e->res_use = true;
   if (e->trace) fprintf(stderr, "[osqp_amd] dense-direct solve: %d dense unknowns (%d x %d inverse, %.0f MB), %d sparse unknowns by Schur complement, %d dense rows of A\n",
                         na, nap, nap, 8e-6 * nap * nap, nb2, nd);
   return 0;

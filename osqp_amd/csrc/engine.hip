@@ -2981,6 +2981,9 @@ struct HostMat {         // host image of a device CSR matrix
   RowBlk *d_blk = nullptr;
 };
 
+// How an engine solves the linear system of an ADMM iteration (the values are hipeng_resident_info [9]): launch-per-step PCG kernels only,
+// k_pcg_resident, k_pcg_blockres, block-direct solve (k_blk_apply / k_blk_finish), dense-direct solve (dense_direct.h)
+enum SolveForm : int { FORM_STEPS = 0, FORM_RESIDENT = 1, FORM_BLOCKRES = 2, FORM_BLOCK_DIRECT = 3, FORM_DENSE_DIRECT = 4 };
 struct hipeng {
   int device = 0;
   int n = 0, m = 0;
@@ -3004,12 +3007,12 @@ struct hipeng {
   std::vector<void *> allocs;
   std::map<int, hipGraphExec_t> graphs;
   int K = 8;
-  int spec_lo = 0;           // unrolled slots below this prefetch without a look at the flags (smallest count of the last window)
+  int spec_lo = 0;           // unrolled slots below this prefetch without a look at the flags (smallest count of the last window); pcg_count_will_jump()
   bool split = false;     // large A: vector update and operator apply as two launches (plain 8-byte gathers)
   int rlA = 8, rlM = 8;   // lanes per row segment in the PCG kernels
-  bool calibrated = false;
+  bool calibrated = false;   // a window has sized K since the PCG iteration count last jumped: pcg_count_will_jump() (the host-call table)
   double ex_theta0 = 1.0;    // OSQP_AMD_EXTRAP (0 disables the extrapolated PCG start)
-  bool start_dirty = true;   // [x~ | rho z~] was rewritten from outside the loop: PCG start history is void
+  bool start_dirty = true;   // the PCG start history is void: start_history_void(), hipeng_run_admm consumes it (the host-call table)
   long long admm_total = 0;            // host copy of State::admm_done
   State *h_state = nullptr;            // pinned staging for the state read-back and the target upload
   long long *h_target = nullptr;
@@ -3017,8 +3020,8 @@ struct hipeng {
   hipeng_stats stats{};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   long long admm_done_seen = 0;
-  bool res_on = false;       // resident PCG structures built (problem fits the register files)
-  bool res_use = false;      // ... and in use
+  SolveForm form = FORM_STEPS;   // what set-up built (direct_disable takes an engine back to FORM_STEPS for good)
+  bool res_use = false;      // ... and in use (a launch that gave up suspends it)
   int res_fails = 0;         // launches that gave up waiting, in a row (one sends the rest of the run_admm call to the launch-per-step
                              // kernels; the third in a row sends the engine there for good; a call without one starts the count again)
   long long res_gave_up = 0; // ... since create
@@ -3026,20 +3029,41 @@ struct hipeng {
   long long res_slow = 0, res_slow_max = 0, res_repub = 0;   // State::res_slow / res_slow_max / res_repub added up over the windows
   long long res_slow_hist[4] = {0, 0, 0, 0}; unsigned res_slow_xcc = 0; int res_slow_last[4] = {0, 0, 0, 0};
   ResCtx rc{};
-  BrCtx bc{};                // block-resident form (res_kind 2)
-  int res_kind = 0;          // 0: launch-per-step only, 1: k_pcg_resident, 2: k_pcg_blockres, 3: block-direct solve (k_blk_apply / k_blk_finish), 4: dense-direct solve (dense_direct.h)
-  BdCtx bd{};                // block-direct form (res_kind 3)
-  DdCtx dd{};                // dense-direct form (res_kind 4)
+  BrCtx bc{};                // FORM_BLOCKRES
+  BdCtx bd{};                // FORM_BLOCK_DIRECT
+  DdCtx dd{};                // FORM_DENSE_DIRECT
   double *dd_init_r = nullptr; int dd_init_stride = 4; double dd_check = 0.0; bool dd_chol = false;   // what direct_disable restores; the last inverse's check; the Cholesky route was needed
-  bool elim_rhs_dirty = false;   // q, the scaling, the matrices or the iterates changed since the m-part of the right-hand side was formed: with
-                             // eliminated variables it carries their q_y and coefficients (elim_vb), so hipeng_run_admm forms it again first
+  bool elim_rhs_dirty = false;   // the m-part of the right-hand side (with eliminated variables: their q_y and coefficients, elim_vb) must be formed again: rhs_m_stale(), the host-call table
   std::vector<double> h_rho; // host copy of rho (the capacitance matrix of the block-direct form needs the huge rows' entries)
   std::vector<int> erow, ecol, epos;   // host images of Ctx::erow / ecol / epos (empty: no variable is eliminated)
   size_t res_lds = 0;
   long long res_nnz = 0;
   bool fk_lists = false;     // resident PCG: k_form_K_lists forms K (else k_form_K); terms, bytes of the lists, their budget in bytes
   long long fk_terms = 0, fk_bytes = 0, fk_budget = 0;
+  bool explicit_inverse() const { return form == FORM_BLOCK_DIRECT || form == FORM_DENSE_DIRECT; }
+  bool one_launch() const { return form == FORM_RESIDENT || form == FORM_BLOCKRES; }      // one launch per solve: it needs the CU lease
+  bool resident_available() const { return form != FORM_STEPS && res_fails < 3; }         // (a launch that gave up suspends the mode for the rest of that call only)
+  int one_launch_grid() const { return form == FORM_BLOCKRES ? bc.nwg : rc.nwg; }         // grid, debug buffer and exchange buffer of the one-launch forms
+  int *one_launch_dbg() const { return form == FORM_BLOCKRES ? bc.dbg : rc.dbg; }
+  const double *one_launch_sbuf() const { return form == FORM_BLOCKRES ? bc.sbuf : rc.sbuf; }
 };
+
+static int elem_grid(int cnt) { return std::max(1, std::min((cnt + TB - 1) / TB, MAX_PARTS)); }
+// ---- the launches that several host calls share ----
+static void launch_spmv(hipeng *e, const DevMat &Mx, const double *in, double *out, int sel) { hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, Mx.nblk))), dim3(TB), 0, e->stream, Mx, in, out, sel); }
+static void launch_precond(hipeng *e) { hipLaunchKernelGGL(k_precond, dim3(elem_grid(e->n)), dim3(TB), 0, e->stream, e->c); }
+static void launch_elim_refresh(hipeng *e) { if (e->c.nelim) hipLaunchKernelGGL(k_elim_refresh, dim3(elem_grid(e->m)), dim3(TB), 0, e->stream, e->c); }
+// ---- what a host call leaves to do: each function is the only writer of its fields (hipeng_run_admm, the consumer, clears them);
+// which entry point calls which is the host-call table of DESIGN 2 ----
+static void pcg_count_will_jump(hipeng *e) { e->calibrated = false; e->spec_lo = 0; }   // two iterations to see where it lands, then whole windows
+static void start_history_void(hipeng *e) { e->start_dirty = true; }                    // [x~ | rho z~] was rewritten from outside the loop: reset_start
+static void rhs_m_stale(hipeng *e) { e->elim_rhs_dirty = true; }
+// k_refresh_m forms the m-parts of the PCG input vectors again; a caller that rewrites the start vector's m-part with it voids the history
+enum StartHistory { START_HISTORY_KEPT, START_HISTORY_VOID };
+static void launch_refresh_m(hipeng *e, int zt_partial, StartHistory h) {
+  hipLaunchKernelGGL(k_refresh_m, dim3(elem_grid(e->m)), dim3(TB), 0, e->stream, e->c, zt_partial);
+  if (h == START_HISTORY_VOID) start_history_void(e);
+}
 
 template <typename T>
 static int dev_alloc(hipeng *e, T **p, size_t count) {
@@ -3313,39 +3337,39 @@ template <int E> static int res_set_lds(size_t lds) {
 }
 static void launch_dense_direct(hipeng *e);
 static void launch_resident(hipeng *e) {
-  if (e->res_kind == 4) { launch_dense_direct(e); return; }
-  if (e->res_kind == 3) {
-    const int gb = std::max(1, std::min(1024, e->c.dP.nblk));
-    hipLaunchKernelGGL(k_blk_apply, dim3(gb), dim3(TB), 0, e->stream, e->c, e->bd, (const double *)e->c.init_r, e->bd.t, 1);
-    if (e->bd.kc) {
-      hipLaunchKernelGGL(k_cpl_dot, dim3(e->bd.kc), dim3(TB), 0, e->stream, e->c, e->bd, (const double *)e->bd.t, e->bd.cs, 1, 1, 0ll, 0ll, 1);
-      hipLaunchKernelGGL(k_cpl_solve, dim3((e->bd.kc + TB / 64 - 1) / (TB / 64)), dim3(TB), 0, e->stream, e->c, e->bd);
-      hipLaunchKernelGGL(k_blk_apply_back, dim3(gb), dim3(TB), 0, e->stream, e->c, e->bd);
+  const dim3 g(e->one_launch_grid()), b(RES_TB);
+  const int gb = std::max(1, std::min(1024, e->c.dP.nblk));       // (block-direct)
+  switch (e->form) {
+    case FORM_STEPS: return;       // (no caller: get_graph asks for K = 0 only while res_use holds, which a FORM_STEPS engine never sets)
+    case FORM_BLOCKRES:       // (ahead of FORM_RESIDENT: the instantiations of the two kernel templates keep their order in the code object)
+      switch (e->c.nh) {
+        case 0: hipLaunchKernelGGL(k_pcg_blockres<0>, g, b, 0, e->stream, e->c, e->bc); break;
+        case 1: hipLaunchKernelGGL(k_pcg_blockres<1>, g, b, 0, e->stream, e->c, e->bc); break;
+        case 2: hipLaunchKernelGGL(k_pcg_blockres<2>, g, b, 0, e->stream, e->c, e->bc); break;
+        case 3: hipLaunchKernelGGL(k_pcg_blockres<3>, g, b, 0, e->stream, e->c, e->bc); break;
+        default: hipLaunchKernelGGL(k_pcg_blockres<4>, g, b, 0, e->stream, e->c, e->bc); break;
+      }
       return;
-    }
-    hipLaunchKernelGGL(k_blk_finish, dim3(std::max(1, std::min(256, (e->n + TB - 1) / TB))), dim3(TB), 0, e->stream, e->c, e->bd);
-    return;
-  }
-  if (e->res_kind == 2) {
-    const dim3 g2(e->bc.nwg), b2(RES_TB);
-    switch (e->c.nh) {
-      case 0: hipLaunchKernelGGL(k_pcg_blockres<0>, g2, b2, 0, e->stream, e->c, e->bc); break;
-      case 1: hipLaunchKernelGGL(k_pcg_blockres<1>, g2, b2, 0, e->stream, e->c, e->bc); break;
-      case 2: hipLaunchKernelGGL(k_pcg_blockres<2>, g2, b2, 0, e->stream, e->c, e->bc); break;
-      case 3: hipLaunchKernelGGL(k_pcg_blockres<3>, g2, b2, 0, e->stream, e->c, e->bc); break;
-      default: hipLaunchKernelGGL(k_pcg_blockres<4>, g2, b2, 0, e->stream, e->c, e->bc); break;
-    }
-    return;
-  }
-  const dim3 g(e->rc.nwg), b(RES_TB);
-  switch (e->rc.E) {
-    case 8:  hipLaunchKernelGGL(k_pcg_resident<8>,  g, b, e->res_lds, e->stream, e->c, e->rc); break;
-    case 16: hipLaunchKernelGGL(k_pcg_resident<16>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
-    case 20: hipLaunchKernelGGL(k_pcg_resident<20>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
-    case 24: hipLaunchKernelGGL(k_pcg_resident<24>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
-    case 32: hipLaunchKernelGGL(k_pcg_resident<32>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
-    case 48: hipLaunchKernelGGL(k_pcg_resident<48>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
-    default: hipLaunchKernelGGL(k_pcg_resident<64>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
+    case FORM_RESIDENT:
+      switch (e->rc.E) {
+        case 8:  hipLaunchKernelGGL(k_pcg_resident<8>,  g, b, e->res_lds, e->stream, e->c, e->rc); break;
+        case 16: hipLaunchKernelGGL(k_pcg_resident<16>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
+        case 20: hipLaunchKernelGGL(k_pcg_resident<20>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
+        case 24: hipLaunchKernelGGL(k_pcg_resident<24>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
+        case 32: hipLaunchKernelGGL(k_pcg_resident<32>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
+        case 48: hipLaunchKernelGGL(k_pcg_resident<48>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
+        default: hipLaunchKernelGGL(k_pcg_resident<64>, g, b, e->res_lds, e->stream, e->c, e->rc); break;
+      }
+      return;
+    case FORM_BLOCK_DIRECT:
+      hipLaunchKernelGGL(k_blk_apply, dim3(gb), dim3(TB), 0, e->stream, e->c, e->bd, (const double *)e->c.init_r, e->bd.t, 1);
+      if (e->bd.kc) {
+        hipLaunchKernelGGL(k_cpl_dot, dim3(e->bd.kc), dim3(TB), 0, e->stream, e->c, e->bd, (const double *)e->bd.t, e->bd.cs, 1, 1, 0ll, 0ll, 1);
+        hipLaunchKernelGGL(k_cpl_solve, dim3((e->bd.kc + TB / 64 - 1) / (TB / 64)), dim3(TB), 0, e->stream, e->c, e->bd);
+        hipLaunchKernelGGL(k_blk_apply_back, dim3(gb), dim3(TB), 0, e->stream, e->c, e->bd);
+      } else hipLaunchKernelGGL(k_blk_finish, dim3(std::max(1, std::min(256, (e->n + TB - 1) / TB))), dim3(TB), 0, e->stream, e->c, e->bd);
+      return;
+    case FORM_DENSE_DIRECT: launch_dense_direct(e); return;
   }
 }
 
@@ -3361,7 +3385,7 @@ static void parallel_chunks(int count, int min_chunk, F fn) {
   for (auto &t : th) t.join();
 }
 
-// Returns 0 (with e->res_on set when the problem qualifies) or a HIPENG error.  Not qualifying is not an error.
+// Returns 0 (with e->form = FORM_RESIDENT when the problem qualifies) or a HIPENG error.  Not qualifying is not an error.
 #define RES_NO(why) do { if (e->trace) fprintf(stderr, "[osqp_amd] resident PCG not used: %s\n", why); return 0; } while (0)
 // What build_resident works out on the host before anything is uploaded (hipeng_resident_plan hands it to the CPU tests).
 struct ResPlanOut {
@@ -3370,8 +3394,7 @@ struct ResPlanOut {
   bool lists = false; std::vector<int> Kcp, Kcm, Kca;     // the contribution lists of k_form_K_lists, where they are in use
 };
 static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr) {
-  e->res_on = e->res_use = false;
-  const int n = e->n;
+  const int n = e->n;       // (called on an engine that is still FORM_STEPS)
   int want = 1, min_n = 256;
   if (const char *x = getenv("OSQP_AMD_RESIDENT")) want = atoi(x);
   if (const char *x = getenv("OSQP_AMD_RESIDENT_MIN_N")) min_n = atoi(x);
@@ -3674,7 +3697,7 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
   }
   if (rcode) RES_NO("the launch's LDS request was refused");
   e->res_nnz = nnzK;
-  e->res_on = e->res_use = true;
+  e->form = FORM_RESIDENT; e->res_use = true;
   if (e->trace) {
     const auto tb3 = std::chrono::steady_clock::now();
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -3778,22 +3801,20 @@ static int build_blockdirect(hipeng *e) {
   // the solve kernels read the residual as a plain n-vector
   e->dd_init_r = e->c.init_r; e->dd_init_stride = e->c.init_stride;       // (what the launch-per-step kernels use: direct_disable puts them back)
   e->c.init_r = e->c.r; e->c.init_stride = 1;
-  e->res_kind = 3; e->res_on = e->res_use = true;
+  e->form = FORM_BLOCK_DIRECT; e->res_use = true;
   if (e->trace) fprintf(stderr, "[osqp_amd] block-direct solve: %zu dense blocks inverted explicitly, %d %s of A as a Woodbury term\n", nb,
                         bd.kc ? bd.kc : (int)e->hrows.size(), bd.kc ? "coupling rows" : "huge rows");
   return 0;
 }
-static int elem_grid(int count);
 // A direct form whose fresh inverse cannot be trusted leaves: this engine goes on with the launch-per-step PCG kernels for good.
 static void direct_disable(hipeng *e, const char *what, const char *why, double err) {
   if (e->trace) fprintf(stderr, "[osqp_amd] %s solve dropped (%s, check %.2e): the PCG kernels take over\n", what, why, err);
   for (auto &g : e->graphs) (void)hipGraphExecDestroy(g.second);      // (they hold the Ctx by value)
   e->graphs.clear();
   e->c.init_r = e->dd_init_r; e->c.init_stride = e->dd_init_stride; e->c.fin_wave_rows = 0; e->c.plain_rhs = 0; e->c.plain_skip = nullptr; e->c.vd = nullptr;
-  const bool was_dense = e->res_kind == 4;
-  e->res_kind = 0; e->res_on = e->res_use = false;
-  e->calibrated = false; e->spec_lo = 0; e->start_dirty = true;
-  if (was_dense) hipLaunchKernelGGL(k_precond, dim3(elem_grid(e->n)), dim3(TB), 0, e->stream, e->c);
+  if (e->form == FORM_DENSE_DIRECT) launch_precond(e);       // (refresh_operator leaves it out on a dense-direct engine)
+  e->form = FORM_STEPS; e->res_use = false;
+  pcg_count_will_jump(e); start_history_void(e);
 }
 // The verdict on the inverses blk_refresh has just formed (k_blk_check, k_cap_check): Gauss-Jordan has an error ~ cond^2 eps; fine on
 // the blocks this form was built for (cond ~ 20), not on every block-diagonal P.  A pivot that was not positive stays what it was: the
@@ -3911,30 +3932,28 @@ static int build_blockres(hipeng *e) {
   HIPCHK(hipStreamSynchronize(e->stream));
   bc.blk0 = d_blk0;
   e->bc = bc;
-  e->res_kind = 2; e->res_on = e->res_use = true;
+  e->form = FORM_BLOCKRES; e->res_use = true;
   if (e->trace) fprintf(stderr, "[osqp_amd] block-resident PCG: %d dense blocks over %d workgroups, %d huge rows of A as rank-one terms\n", nb, nwg, (int)e->hrows.size());
   return 0;
-}
-
-static int elem_grid(int cnt) {
-  int g = (cnt + TB - 1) / TB;
-  return std::max(1, std::min(g, MAX_PARTS));
 }
 
 // Everything derived from (P, A, rho, sigma): the Jacobi preconditioner.
 static int dd_refresh(hipeng *e);
 static void refresh_operator(hipeng *e) {
-  e->elim_rhs_dirty = true;
-  if (e->c.nelim) hipLaunchKernelGGL(k_elim_refresh, dim3(elem_grid(e->m)), dim3(TB), 0, e->stream, e->c);
+  rhs_m_stale(e);
+  launch_elim_refresh(e);
   // (the Jacobi preconditioner: one thread per column -- 1.3 ms on the Lasso's 1 500-entry columns -- and of no use to a dense-direct
   // engine; direct_disable forms it when such an engine goes back to the PCG kernels)
-  if (e->res_kind != 4) hipLaunchKernelGGL(k_precond, dim3(elem_grid(e->n)), dim3(TB), 0, e->stream, e->c);
-  if (e->res_kind == 1) {
-    if (e->rc.kcp) hipLaunchKernelGGL(k_form_K_lists, dim3((e->n + 3) / 4), dim3(TB), 0, e->stream, e->c, e->rc);
-    else hipLaunchKernelGGL(k_form_K, dim3(std::min(2048, (e->n + 3) / 4)), dim3(TB), 0, e->stream, e->c, e->rc);
+  switch (e->form) {
+    case FORM_STEPS: case FORM_BLOCKRES: launch_precond(e); break;
+    case FORM_RESIDENT:
+      launch_precond(e);
+      if (e->rc.kcp) hipLaunchKernelGGL(k_form_K_lists, dim3((e->n + 3) / 4), dim3(TB), 0, e->stream, e->c, e->rc);
+      else hipLaunchKernelGGL(k_form_K, dim3(std::min(2048, (e->n + 3) / 4)), dim3(TB), 0, e->stream, e->c, e->rc);
+      break;
+    case FORM_BLOCK_DIRECT: launch_precond(e); if (blk_refresh(e)) fprintf(stderr, "osqp_amd: the block-direct solve could not be refreshed\n"); break;
+    case FORM_DENSE_DIRECT: if (dd_refresh(e)) fprintf(stderr, "osqp_amd: the dense-direct solve could not be refreshed\n"); break;
   }
-  if (e->res_kind == 3 && blk_refresh(e)) fprintf(stderr, "osqp_amd: the block-direct solve could not be refreshed\n");
-  if (e->res_kind == 4 && dd_refresh(e)) fprintf(stderr, "osqp_amd: the dense-direct solve could not be refreshed\n");
 }
 
 // The PCG start vector history is void (cold/warm start from the host, new rho, new matrices):
@@ -3972,7 +3991,7 @@ static int build_elim(hipeng *e, const csc *P, const csc *A) {
   c.nelim = 0; c.erow = c.ecol = c.epos = nullptr; c.rhoe = c.rho; c.ecoef = c.edinv = c.xte = nullptr;
   const int n = e->n, m = e->m;
   if (const char *x = getenv("OSQP_AMD_ELIM")) if (!atoi(x)) return 0;
-  if (e->res_kind >= 2 || m == 0 || n == 0) return 0;      // (the block forms of the portfolio family hold their own operator)
+  if (e->form == FORM_BLOCKRES || e->form == FORM_BLOCK_DIRECT || m == 0 || n == 0) return 0;      // (the block forms of the portfolio family hold their own operator; the other forms are built after this)
   std::vector<char> coupled(n, 0);
   for (int j = 0; j < n; j++)
     for (long long k = P->p[j]; k < P->p[j + 1]; k++) if (P->i[k] != j) { coupled[j] = 1; coupled[(int)P->i[k]] = 1; }
@@ -4114,10 +4133,10 @@ extern "C" int hipeng_create(hipeng **out, const csc *P, const csc *A, const c_f
   e->stats.kernels_per_pcg_iter = 2;
   *out = e;
   if (int rc = build_blockdirect(e)) return rc;
-  if (!e->res_on) if (int rc = build_blockres(e)) return rc;
+  if (e->form == FORM_STEPS) if (int rc = build_blockres(e)) return rc;
   if (int rc = build_elim(e, P, A)) return rc;
   if (int rc = build_dense_direct(e, P, A, true)) return rc;          // small reduced systems: ahead of the resident PCG
-  if (!e->res_on) { if (int rc = build_resident(e)) return rc; if (e->res_on) e->res_kind = 1; }
+  if (e->form == FORM_STEPS) if (int rc = build_resident(e)) return rc;
   if (int rc = build_dense_direct(e, P, A, false)) return rc;
   if (rho_vec) { int rc = hipeng_upload_rho(e, rho_vec); if (rc) return rc; }
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -4161,7 +4180,7 @@ extern "C" int hipeng_set_params(hipeng *e, const hipeng_params *prm) {
     refresh_operator(e);
     // rho~ depends on sigma: the m-part of the start vector (rho~ A_X x~0, which k_pcg_init takes as it stands) is formed again by
     // hipeng_run_admm's k_refresh_m into va; vx must follow it, or the first residual is that of another operator
-    if (e->c.nelim) e->start_dirty = true;
+    if (e->c.nelim) start_history_void(e);
   }
   return 0;
 }
@@ -4230,7 +4249,7 @@ extern "C" int hipeng_ruiz_scale(hipeng *e, c_int passes, c_float *D, c_float *E
   if (upload_vec(e, c.pdiag, e->pdiag.data(), n)) return HIPENG_ERR_HIP;
   e->prm.has_scaling = passes > 0 ? 1 : 0; e->prm.cinv = 1.0 / cc;
   if (push_params(e)) return HIPENG_ERR_HIP;
-  e->elim_rhs_dirty = true;
+  rhs_m_stale(e);
   return 0;
 }
 
@@ -4239,7 +4258,7 @@ extern "C" int hipeng_upload_q(hipeng *e, const c_float *q) {
   HIPCHK(hipSetDevice(e->device));
   if (upload_vec(e, e->c.q, q, e->n)) return HIPENG_ERR_HIP;
   HIPCHK(hipStreamSynchronize(e->stream));
-  e->elim_rhs_dirty = true;
+  rhs_m_stale(e);
   return 0;
 }
 
@@ -4258,13 +4277,27 @@ extern "C" int hipeng_upload_rho(hipeng *e, const c_float *rho_vec) {
     if (!rho_vec) return HIPENG_ERR_ARG;
     if (upload_vec(e, e->c.rho, rho_vec, e->m)) return HIPENG_ERR_HIP;
     e->h_rho.assign(rho_vec, rho_vec + e->m);
-    if (e->c.nelim) hipLaunchKernelGGL(k_elim_refresh, dim3(elem_grid(e->m)), dim3(TB), 0, e->stream, e->c);
-    hipLaunchKernelGGL(k_refresh_m, dim3(elem_grid(e->m)), dim3(TB), 0, e->stream, e->c, 0); e->start_dirty = true;
+    launch_elim_refresh(e);          // (refresh_operator below launches it once more: DESIGN 2, the oddities under the host-call table)
+    launch_refresh_m(e, 0, START_HISTORY_VOID);
   }
   refresh_operator(e);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(e->stream));
-  e->calibrated = false; e->spec_lo = 0;   // the PCG iteration count usually jumps after a rho change
+  pcg_count_will_jump(e);            // (usually, after a rho change)
+  return 0;
+}
+
+// The operator's values changed under a set-up engine (new P, A from the host, or a device-side rescale in place): everything derived
+// from them, then z~ = A x~ for the new A and the m-parts of the PCG input vectors, so that the PCG warm start stays consistent; error check, sync.
+static int operator_values_changed(hipeng *e) {
+  if (repack_dense(e)) return HIPENG_ERR_HIP;
+  refresh_operator(e);
+  if (e->m > 0) {
+    launch_spmv(e, e->c.A, e->c.va, e->c.zt, 0);
+    launch_refresh_m(e, 1, START_HISTORY_VOID);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 }
 
@@ -4289,32 +4322,14 @@ extern "C" int hipeng_upload_matrices(hipeng *e, const csc *P, const csc *A) {
   if (upload_vec(e, e->M.d_val, e->M.val.data(), e->M.val.size()) ||
       upload_vec(e, e->A.d_val, e->A.val.data(), e->A.val.size()) ||
       upload_vec(e, e->c.pdiag, e->pdiag.data(), n)) return HIPENG_ERR_HIP;
-  if (repack_dense(e)) return HIPENG_ERR_HIP;
-  refresh_operator(e);
-  // z~ = A x~ for the new A so that the PCG warm start stays consistent
-  if (e->m > 0) {
-    hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, e->c.va, e->c.zt, 0);
-    hipLaunchKernelGGL(k_refresh_m, dim3(elem_grid(e->m)), dim3(TB), 0, e->stream, e->c, 1); e->start_dirty = true;
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return operator_values_changed(e);
 }
 
-// The resident matrix values changed in place (device-side rescaling): rebuild what depends
-// on them -- Jacobi preconditioner, z~ = A x~ and the m-parts of the PCG input vectors.
+// The resident matrix values changed in place (device-side rescaling).
 extern "C" int hipeng_matrices_changed(hipeng *e) {
   if (!e) return HIPENG_ERR_ARG;
   HIPCHK(hipSetDevice(e->device));
-  if (repack_dense(e)) return HIPENG_ERR_HIP;
-  refresh_operator(e);
-  if (e->m > 0) {
-    hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, e->c.va, e->c.zt, 0);
-    hipLaunchKernelGGL(k_refresh_m, dim3(elem_grid(e->m)), dim3(TB), 0, e->stream, e->c, 1); e->start_dirty = true;
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return operator_values_changed(e);
 }
 
 extern "C" int hipeng_cold_start(hipeng *e) {
@@ -4327,9 +4342,8 @@ extern "C" int hipeng_cold_start(hipeng *e) {
   HIPCHK(hipMemsetAsync(e->c.z, 0, std::max<size_t>(e->m, 1) * sizeof(double), e->stream));
   HIPCHK(hipMemsetAsync(e->c.zt, 0, std::max<size_t>(e->m, 1) * sizeof(double), e->stream));
   if (e->c.nelim) HIPCHK(hipMemsetAsync(e->c.xte, 0, (size_t)e->m * sizeof(double), e->stream));
-  e->calibrated = false; e->spec_lo = 0;   // the first solve from zero needs far more PCG iterations than the steady state
-  e->start_dirty = true;
-  e->elim_rhs_dirty = true;                // (vb = rho z - y = 0 is NOT the whole m-part when a row carries an eliminated variable: -rho a (-q_y) / D_y)
+  pcg_count_will_jump(e); start_history_void(e);     // the first solve from zero needs far more PCG iterations than the steady state
+  rhs_m_stale(e);                          // (vb = rho z - y = 0 is NOT the whole m-part when a row carries an eliminated variable: -rho a (-q_y) / D_y)
   return 0;
 }
 
@@ -4343,14 +4357,13 @@ extern "C" int hipeng_set_iterates(hipeng *e, const c_float *x, const c_float *y
     // PCG warm start x~ = x ; z = A x ; z~ = z   (osqp_warm_start, osqp.c:960-963)
     HIPCHK(hipMemcpyAsync(e->c.va, e->c.xy, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
     if (e->c.nelim) hipLaunchKernelGGL(k_elim_split, dim3(elem_grid(n)), dim3(TB), 0, e->stream, e->c);
-    e->start_dirty = true;
     if (m > 0) {
-      hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, e->c.xy, e->c.z, 0);
+      launch_spmv(e, e->c.A, e->c.xy, e->c.z, 0);
       HIPCHK(hipMemcpyAsync(e->c.zt, e->c.z, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
     }
   }
-  if (m > 0) hipLaunchKernelGGL(k_refresh_m, dim3(elem_grid(m)), dim3(TB), 0, e->stream, e->c, 0);
-  e->start_dirty = true;
+  if (m > 0) launch_refresh_m(e, 0, START_HISTORY_VOID);
+  start_history_void(e);             // (without constraints too: x~ was rewritten)
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
@@ -4363,7 +4376,7 @@ extern "C" int hipeng_set_z(hipeng *e, const c_float *z) {
   if (m > 0 && z) {
     if (upload_vec(e, e->c.z, z, m)) return HIPENG_ERR_HIP;
     // (z~ stays A x~: k_pcg_init takes the start vector's m-part for rho A x~0, whatever z is)
-    hipLaunchKernelGGL(k_refresh_m, dim3(elem_grid(m)), dim3(TB), 0, e->stream, e->c, 0); e->start_dirty = true;
+    launch_refresh_m(e, 0, START_HISTORY_VOID);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -4416,7 +4429,7 @@ static int get_graph(hipeng *e, int K, int R, int spec_lo, hipGraphExec_t *out) 
     if (K == 0) launch_resident(e);                   // the whole linear solve in one launch (K in registers)
     else { launch_cg_A(e, -1, 8); launch_cg_B(e, -1, 0); }   // operator apply on u0 (+ first convergence test), then w0 and the first dots
     for (int it = 0; it < K; it++) launch_pcg_iter(e, it, 0, spec_lo);
-    if (e->c.A.nblk > e->c.A.nwave && !(K == 0 && e->res_kind == 3 && e->bd.fin_dots))      // (block-direct: the kernel that wrote x~ left the partials)
+    if (e->c.A.nblk > e->c.A.nwave && !(K == 0 && e->form == FORM_BLOCK_DIRECT && e->bd.fin_dots))      // (block-direct: the kernel that wrote x~ left the partials)
       hipLaunchKernelGGL(k_huge_dot, dim3(e->c.gridA), dim3(TB), 0, e->stream, e->c, (const double *)nullptr, 0);
     {
       // dense-direct engines (one wavefront per long row in this kernel): enough workgroups that a wavefront has one or two rows --
@@ -4458,11 +4471,10 @@ static int next_K(int want, int cap) {
 // when it published (its give-up clock minus the ticks it had waited) and both XCC ids -- "store landed but was never seen",
 // "store never landed" and "the other one was late" read differently.
 static int resident_gave_up(hipeng *e, const State &s, bool quiet) {
-  const int nwg = e->res_kind == 2 ? e->bc.nwg : e->rc.nwg;
-  int *ddbg = e->res_kind == 2 ? e->bc.dbg : e->rc.dbg;
+  const int nwg = e->one_launch_grid(); int *ddbg = e->one_launch_dbg();
   std::vector<int> d((size_t)nwg * RES_DBG, 0);
   bool have = ddbg && hipMemcpy(d.data(), ddbg, d.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
-  const bool injected = have && e->res_kind == 1 && e->rc.inject > 0 && d[(size_t)RES_DBG * (nwg - 1) + 3] == 4;
+  const bool injected = have && e->form == FORM_RESIDENT && e->rc.inject > 0 && d[(size_t)RES_DBG * (nwg - 1) + 3] == 4;
   if (!quiet || !injected) {
     fprintf(stderr, "osqp_amd: a resident PCG launch gave up waiting for its workgroups%s; %s with the launch-per-step kernels "
                     "[wait %d (1 flags, 2 granules) of exchange %d: workgroup %d missed workgroup %d]\n",
@@ -4482,9 +4494,9 @@ static int resident_gave_up(hipeng *e, const State &s, bool quiet) {
         if (ow >= 0 && ow < nwg) {
           const int *o = &d[(size_t)RES_DBG * ow];
           unsigned long long memword = 0; bool got = false;
-          if (s.res_dbg[0] == 1 && e->res_kind == 1) { unsigned f = 0; got = hipMemcpy(&f, e->rc.flags + (size_t)ow * RES_FSTRIDE, 4, hipMemcpyDeviceToHost) == hipSuccess; memword = f; }
+          if (s.res_dbg[0] == 1 && e->form == FORM_RESIDENT) { unsigned f = 0; got = hipMemcpy(&f, e->rc.flags + (size_t)ow * RES_FSTRIDE, 4, hipMemcpyDeviceToHost) == hipSuccess; memword = f; }
           else {
-            const double *sb = e->res_kind == 2 ? e->bc.sbuf : e->rc.sbuf;
+            const double *sb = e->one_launch_sbuf();
             const unsigned tag = s.res_epoch + (unsigned)w[0];
             int gi = 0; while (gi < 15 && !((w[10] >> gi) & 1)) gi++;
             got = hipMemcpy(&memword, reinterpret_cast<const unsigned long long *>(sb) + ((size_t)(tag & 1u) * nwg + ow) * RES_GSTRIDE + gi, 8, hipMemcpyDeviceToHost) == hipSuccess;
@@ -4530,13 +4542,13 @@ extern "C" int hipeng_run_admm(hipeng *e, c_int count) {
   // without a device round trip.  The device stops starting iterations at admm_target.
   if (count == 0) return 0;
   if (e->elim_rhs_dirty) {
-    if (e->c.nelim && e->m > 0) hipLaunchKernelGGL(k_refresh_m, dim3(elem_grid(e->m)), dim3(TB), 0, e->stream, e->c, 0);
+    if (e->c.nelim && e->m > 0) launch_refresh_m(e, 0, START_HISTORY_KEPT);      // (a host call that needs the history void says so itself, as hipeng_set_params does)
     e->elim_rhs_dirty = false;
   }
   // A launch that gave up (a wait timed out) took the rest of that call to the launch-per-step kernels.  Apart from a GPU
   // that is shared for good, there is a rare transient (about one exchange in 1e5 on small, fast problems: a workgroup's
   // flag or granule stays invisible to some CUs): the next call tries resident launches again, three strikes end that.
-  if (e->res_on && !e->res_use && e->res_fails < 3) e->res_use = true;
+  if (!e->res_use && e->resident_available()) e->res_use = true;
   bool had_fail = false;
   const long long start = e->admm_total, target = start + (long long)count;
   *e->h_target = target;
@@ -4558,7 +4570,7 @@ extern "C" int hipeng_run_admm(hipeng *e, c_int count) {
     // different engines of this process on one device take turns.  (Across processes there is no such lock: a
     // launch that finds CUs taken times out and the engine falls back, see k_pcg_resident.)
     CuLease lease;
-    if (resident && e->res_kind < 3) lease.take(e->device, e->res_cus, e->res_kind == 2 ? e->bc.nwg : e->rc.nwg);
+    if (resident && e->one_launch()) lease.take(e->device, e->res_cus, e->one_launch_grid());
     const long long burst = std::min<long long>(remaining, (e->calibrated || resident) ? 128 : 2);
     TR2(e, "launch burst=%lld K=%d", burst, e->K);
     // `burst` ADMM iterations = burst / segs graphs of `segs` segments + single-segment graphs for the rest
@@ -4625,15 +4637,14 @@ extern "C" int hipeng_reset_stats(hipeng *e) {
   HIPCHK(hipStreamSynchronize(e->stream));
   e->stats = hipeng_stats{};
   e->stats.kernels_per_pcg_iter = 2;
-  e->calibrated = false;
-  e->K = 8; e->spec_lo = 0;
+  pcg_count_will_jump(e); e->K = 8;
   return 0;
 }
 
 extern "C" int hipeng_get_stats(hipeng *e, hipeng_stats *st) {
   if (!e || !st) return HIPENG_ERR_ARG;
   *st = e->stats;
-  st->resident = (e->res_on && e->res_fails < 3) ? 1 : 0;     // (a launch that gave up suspends the mode for the rest of that call only)
+  st->resident = e->resident_available() ? 1 : 0;
   return 0;
 }
 
@@ -4712,7 +4723,7 @@ extern "C" int hipeng_kkt_solve_unrefined(hipeng *e, c_float *b) {
   if (m > 0) {
     // stage b2 in z, y = 0  =>  k_refresh_m writes vb = rho*z - y = rho.b2
     if (upload_vec(e, e->c.z, b + n, m)) return HIPENG_ERR_HIP;
-    hipLaunchKernelGGL(k_refresh_m, dim3(elem_grid(m)), dim3(TB), 0, e->stream, e->c, 0); e->start_dirty = true;
+    launch_refresh_m(e, 0, START_HISTORY_VOID);
   }
   int rc = hipeng_run_admm(e, 1);
   e->prm.use_cvec = 0;
@@ -4737,11 +4748,11 @@ extern "C" int hipeng_kkt_solve(hipeng *e, c_float *b) {
   // right-hand side, where even an exact inverse leaves an error of cond(K) eps relative to |K^-1| |b| -- 15x that of an LU solve at
   // cond 500.  So one step of refinement: r = b1 + A'(rho . b2) - K x~ from the host copies of [P | A'] (long double sums), then
   // x~ += K^-1 r, z~ += A K^-1 r.
-  const bool direct = e->res_use && (e->res_kind == 3 || e->res_kind == 4) && (m == 0 || e->h_rho.size() == (size_t)m);
+  const bool direct = e->res_use && e->explicit_inverse() && (m == 0 || e->h_rho.size() == (size_t)m);
   std::vector<double> b0;
   if (direct) b0.assign(b, b + n + m);
   if (int rc = hipeng_kkt_solve_unrefined(e, b)) return rc;
-  if (!direct || !(e->res_use && (e->res_kind == 3 || e->res_kind == 4))) return 0;
+  if (!direct || !(e->res_use && e->explicit_inverse())) return 0;
   const HostMat &M = e->M;
   const long double sigma = e->prm.sigma;
   std::vector<long double> w((size_t)m, 0.0L);            // rho . (b2 - A x~)
@@ -4767,17 +4778,11 @@ extern "C" int hipeng_spmv(hipeng *e, int which, const c_float *x, c_float *y) {
   const int n = e->n, m = e->m;
   double *in = e->c.pt0, *out = e->c.pt1;   // scratch of n+m doubles each
   HIPCHK(hipMemsetAsync(in, 0, (size_t)std::max(1, n + m) * sizeof(double), e->stream));
-  if (which == 0) {
-    if (upload_vec(e, in, x, n)) return HIPENG_ERR_HIP;
-    hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, in, out, 0);
-    HIPCHK(hipMemcpyAsync(y, out, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  } else {
-    if (which == 1) { if (upload_vec(e, in + n, x, m)) return HIPENG_ERR_HIP; }
-    else if (upload_vec(e, in, x, n)) return HIPENG_ERR_HIP;
-    hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.M.nblk))), dim3(TB), 0, e->stream, e->c.M, in, out,
-                       which == 1 ? 2 : 1);
-    HIPCHK(hipMemcpyAsync(y, out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  }
+  // A x from x in [0, n); A' y (selector 2) from y behind n unused slots, P x (selector 1) from x in [0, n), both through the fused rows of M
+  if (which == 1 ? upload_vec(e, in + n, x, m) : upload_vec(e, in, x, n)) return HIPENG_ERR_HIP;
+  if (which == 0) launch_spmv(e, e->c.A, in, out, 0);
+  else launch_spmv(e, e->c.M, in, out, which == 1 ? 2 : 1);
+  HIPCHK(hipMemcpyAsync(y, out, (size_t)(which == 0 ? m : n) * sizeof(double), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
@@ -4791,18 +4796,13 @@ extern "C" int hipeng_spmv_dev(hipeng *e, int which, const double *d_x, double *
   HIPCHK(hipSetDevice(e->device));
   const int n = e->n, m = e->m;
   if (which == 0) {
-    if (m > 0) hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, d_x, d_y, 0);
-  } else if (which == 1) {
-    // the fused row matrix reads y at column ids n + i: stage it behind n unused slots
-    double *in = e->c.pt0;
-    if (m > 0) HIPCHK(hipMemcpyAsync(in + n, d_x, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-    hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.M.nblk))), dim3(TB), 0, e->stream, e->c.M, (const double *)in, d_y, 2);
+    if (m > 0) launch_spmv(e, e->c.A, d_x, d_y, 0);
   } else {
-    // k_spmv stages the products of whole rows of [P | A'] (the A' entries gather at column ids up to n + m - 1)
-    // before it sums the P part: the input must be n + m long, so x is staged too
+    // the fused row matrix reads y at column ids n + i: stage it behind n unused slots.  x is staged too: k_spmv stages the products of whole
+    // rows of [P | A'] (the A' entries gather at column ids up to n + m - 1) before it sums the P part, so the input must be n + m long
     double *in = e->c.pt0;
-    HIPCHK(hipMemcpyAsync(in, d_x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-    hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.M.nblk))), dim3(TB), 0, e->stream, e->c.M, (const double *)in, d_y, 1);
+    if (which == 2 || m > 0) HIPCHK(hipMemcpyAsync(which == 1 ? in + n : in, d_x, (size_t)(which == 1 ? m : n) * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    launch_spmv(e, e->c.M, in, d_y, which == 1 ? 2 : 1);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -4810,10 +4810,10 @@ extern "C" int hipeng_spmv_dev(hipeng *e, int which, const double *d_x, double *
 
 extern "C" int hipeng_time_kernel(hipeng *e, int which, int reps, double *usec) {
   if (!e || !usec || reps <= 0 || which < 0 || which > 8) return HIPENG_ERR_ARG;
-  if (which == 8 && !(e->res_on && e->res_fails < 3)) return HIPENG_ERR_ARG;
+  if (which == 8 && !e->resident_available()) return HIPENG_ERR_ARG;
   HIPCHK(hipSetDevice(e->device));
   CuLease lease;
-  if (which == 8 && e->res_kind < 3) lease.take(e->device, e->res_cus, e->res_kind == 2 ? e->bc.nwg : e->rc.nwg);
+  if (which == 8 && e->one_launch()) lease.take(e->device, e->res_cus, e->one_launch_grid());
   auto one = [&](int it) {
     // the first two kernels of a resident ADMM iteration: right-hand side + start residual, then the whole linear solve
     // (without k_admm_finalize the iterates do not move: every repetition solves the same system from the same start)
@@ -4959,12 +4959,12 @@ extern "C" int hipeng_resident_info(hipeng *e, long long out[16]) {
   HIPCHK(hipSetDevice(e->device));
   State s;
   if (read_state(e, &s)) return HIPENG_ERR_HIP;
-  out[0] = e->res_on; out[1] = e->res_on && e->res_fails < 3; out[2] = e->rc.E; out[3] = e->rc.nwg; out[4] = e->res_nnz; out[5] = (long long)e->res_lds;
-  out[6] = std::max(s.iters[0], s.iters[1]); out[7] = s.res_pipe_off; out[8] = s.res_chk_fail; out[9] = e->res_kind; out[10] = e->res_gave_up; out[11] = e->res_slow + s.res_slow;
-  out[12] = std::max<long long>(e->res_slow_max, s.res_slow_max); out[13] = e->res_repub + s.res_repub; out[14] = e->res_fails; out[15] = e->res_kind == 3 ? e->bd.kc : 0;
-  if (e->res_kind == 2) { out[2] = 64; out[3] = e->bc.nwg; out[4] = 0; out[5] = 0; }
-  if (e->res_kind == 3) { out[2] = 0; out[3] = e->c.dP.nblk; out[4] = 0; out[5] = 0; }
-  if (e->res_kind == 4) { out[2] = 0; out[3] = e->dd.na; out[4] = (long long)e->dd.nap * e->dd.nap; out[5] = e->dd_chol ? 1 : 0; out[15] = e->dd.nb2; }
+  out[0] = e->form != FORM_STEPS; out[1] = e->resident_available(); out[2] = e->rc.E; out[3] = e->rc.nwg; out[4] = e->res_nnz; out[5] = (long long)e->res_lds;
+  out[6] = std::max(s.iters[0], s.iters[1]); out[7] = s.res_pipe_off; out[8] = s.res_chk_fail; out[9] = e->form; out[10] = e->res_gave_up; out[11] = e->res_slow + s.res_slow;
+  out[12] = std::max<long long>(e->res_slow_max, s.res_slow_max); out[13] = e->res_repub + s.res_repub; out[14] = e->res_fails; out[15] = 0;
+  if (e->form == FORM_BLOCKRES) { out[2] = 64; out[3] = e->bc.nwg; out[4] = 0; out[5] = 0; }
+  if (e->form == FORM_BLOCK_DIRECT) { out[2] = 0; out[3] = e->c.dP.nblk; out[4] = 0; out[5] = 0; out[15] = e->bd.kc; }
+  if (e->form == FORM_DENSE_DIRECT) { out[2] = 0; out[3] = e->dd.na; out[4] = (long long)e->dd.nap * e->dd.nap; out[5] = e->dd_chol ? 1 : 0; out[15] = e->dd.nb2; }
   return 0;
 }
 
@@ -4973,7 +4973,7 @@ extern "C" int hipeng_resident_info(hipeng *e, long long out[16]) {
 // [3] their budget in bytes (OSQP_AMD_FORM_K_LIST_MB).  All 0 for an engine on another form.
 extern "C" int hipeng_form_k_info(hipeng *e, long long out[4]) {
   if (!e || !out) return HIPENG_ERR_ARG;
-  const bool res = e->res_kind == 1;
+  const bool res = e->form == FORM_RESIDENT;
   out[0] = res && e->fk_lists; out[1] = res ? e->fk_terms : 0; out[2] = res ? e->fk_bytes : 0; out[3] = res ? e->fk_budget : 0;
   return 0;
 }
@@ -4988,14 +4988,14 @@ extern "C" int hipeng_resident_trips(hipeng *e, long long out[8]) {
   State s;
   if (read_state(e, &s)) return HIPENG_ERR_HIP;
   out[0] = s.res_trips; out[1] = s.res_solves; out[2] = s.res_pred_hit; out[3] = s.res_pred_miss;
-  out[4] = s.res_pred_off; out[5] = e->res_kind == 1 ? e->rc.predict : 0; out[6] = s.res_pred_win[0]; out[7] = s.res_pred_win[2] - s.res_pred_win[1];
+  out[4] = s.res_pred_off; out[5] = e->form == FORM_RESIDENT ? e->rc.predict : 0; out[6] = s.res_pred_win[0]; out[7] = s.res_pred_win[2] - s.res_pred_win[1];
   return 0;
 }
 
 // Resident PCG, for the tests: what the start-up of the last launch summed.  Returns gridM (or a negative code); part_bb receives
 // min(gridM, cap) partials of ||b||^2 as the last k_pcg_init left them, *tol2 State::tol2 as the last launch stored it.
 extern "C" long long hipeng_resident_start_peek(hipeng *e, double *part_bb, long long cap, double *tol2) {
-  if (!e || e->res_kind != 1 || !part_bb || !tol2 || cap < 0) return HIPENG_ERR_ARG;
+  if (!e || e->form != FORM_RESIDENT || !part_bb || !tol2 || cap < 0) return HIPENG_ERR_ARG;
   if (hipSetDevice(e->device) != hipSuccess) return HIPENG_ERR_HIP;
   State s;
   if (read_state(e, &s)) return HIPENG_ERR_HIP;       // (synchronises the stream)
@@ -5008,7 +5008,7 @@ extern "C" long long hipeng_resident_start_peek(hipeng *e, double *part_bb, long
 // Resident PCG, for the tests: the rows of K as the resident kernel holds them.  row/col/val receive nnz(K) triplets
 // (row by row, columns ascending; values read from the slots the threads load them from); returns the count or a negative code.
 extern "C" long long hipeng_resident_dump(hipeng *e, int *row, int *col, double *val, long long cap) {
-  if (!e || e->res_kind != 1 || !row || !col || !val) return HIPENG_ERR_ARG;
+  if (!e || e->form != FORM_RESIDENT || !row || !col || !val) return HIPENG_ERR_ARG;
   if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return HIPENG_ERR_HIP;
   const ResCtx &rc = e->rc;
   const size_t slots = (size_t)rc.nwg * rc.E * RES_PT;

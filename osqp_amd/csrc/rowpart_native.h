@@ -303,10 +303,10 @@ static void rp_apply_local(osqp_amd_rp *rp) {
   hipeng *e = rp->e;
   const int n = rp->n, m = rp->m;
   if (m > 0) {
-    hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, (const double *)rp->stage, rp->stage + n, 0);
+    launch_spmv(e, e->c.A, rp->stage, rp->stage + n, 0);
     hipLaunchKernelGGL(k_rp_scale, rp_grid(), dim3(TB), 0, e->stream, m, (const double *)rp->rv, rp->stage + n);
   }
-  hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.M.nblk))), dim3(TB), 0, e->stream, e->c.M, (const double *)rp->stage, rp->part, 0);
+  launch_spmv(e, e->c.M, rp->stage, rp->part, 0);
 }
 static int rp_set_rho(osqp_amd_rp *rp, double rho) {
   hipeng *e = rp->e;
@@ -384,15 +384,14 @@ static int rp_check(osqp_amd_rp *rp, double *pri_res, double *dua_res, bool cert
   const int n = rp->n, m = rp->m;
   HIPCHK(hipMemsetAsync(rp->sc15, 0, (cert ? 24 : 16) * sizeof(double), e->stream));
   if (m > 0) {
-    hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, (const double *)rp->x, rp->ax, 0);
+    launch_spmv(e, e->c.A, rp->x, rp->ax, 0);
     hipLaunchKernelGGL(k_rp_pri, dim3(1), dim3(TB), 0, e->stream, m, (const double *)rp->ax, (const double *)rp->z, (const double *)rp->Einv, rp->sc15);
   }
   if (int rc = rp_allreduce(rp, rp->sc15, 6, 1)) return rc;
   HIPCHK(hipMemcpyAsync(rp->stage, rp->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
   if (m > 0) HIPCHK(hipMemcpyAsync(rp->stage + n, rp->y, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-  const dim3 gm(std::min(MAX_PARTS, std::max(1, e->c.M.nblk)));
-  hipLaunchKernelGGL(k_spmv, gm, dim3(TB), 0, e->stream, e->c.M, (const double *)rp->stage, rp->both, 1);            // P_g x
-  hipLaunchKernelGGL(k_spmv, gm, dim3(TB), 0, e->stream, e->c.M, (const double *)rp->stage, rp->both + n, 2);        // A_g' y
+  launch_spmv(e, e->c.M, rp->stage, rp->both, 1);            // P_g x
+  launch_spmv(e, e->c.M, rp->stage, rp->both + n, 2);        // A_g' y
   if (int rc = rp_allreduce(rp, rp->both, 2ll * n, 0)) return rc;
   hipLaunchKernelGGL(k_rp_dua, dim3(1), dim3(TB), 0, e->stream, n, (const double *)rp->both, (const double *)rp->q, (const double *)rp->Dinv, (const double *)rp->x, rp->sc15 + 6);
   const bool un = rp->scaled && !rp->st.scaled_termination;
@@ -401,9 +400,9 @@ static int rp_check(osqp_amd_rp *rp, double *pri_res, double *dua_res, bool cert
     hipLaunchKernelGGL(k_rp_delta_x, rp_grid(), dim3(TB), 0, e->stream, n, (const double *)rp->x, (const double *)rp->xp, dx);
     if (m > 0) hipLaunchKernelGGL(k_rp_delta_y, rp_grid(), dim3(TB), 0, e->stream, m, (const double *)rp->y, (const double *)rp->yp, (const double *)rp->l, (const double *)rp->u, dy);
     hipLaunchKernelGGL(k_rp_cert_x, dim3(1), dim3(TB), 0, e->stream, n, (const double *)dx, (const double *)rp->q, un ? (const double *)rp->D : nullptr, out7);
-    hipLaunchKernelGGL(k_spmv, gm, dim3(TB), 0, e->stream, e->c.M, (const double *)rp->dxy, rp->cb, 1);                // P_g dx
-    hipLaunchKernelGGL(k_spmv, gm, dim3(TB), 0, e->stream, e->c.M, (const double *)rp->dxy, rp->cb + n, 2);            // A_g' dy
-    if (m > 0) hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, (const double *)dx, rp->ax, 0);
+    launch_spmv(e, e->c.M, rp->dxy, rp->cb, 1);                // P_g dx
+    launch_spmv(e, e->c.M, rp->dxy, rp->cb + n, 2);            // A_g' dy
+    if (m > 0) launch_spmv(e, e->c.A, dx, rp->ax, 0);
     hipLaunchKernelGGL(k_rp_cert_rows, dim3(1), dim3(TB), 0, e->stream, m, (const double *)dy, un ? (const double *)rp->E : nullptr, un ? (const double *)rp->Einv : nullptr,
                        (const double *)rp->l, (const double *)rp->u, (const double *)rp->ax, out7, rp->cb + 2 * n);
     if (int rc = rp_allreduce(rp, rp->cb, 2ll * n + 1, 0)) return rc;
@@ -483,7 +482,7 @@ extern "C" int osqp_amd_rp_solve(osqp_amd_rp *rp, osqp_amd_rp_info *info) {
     // right-hand side
     HIPCHK(hipMemsetAsync(rp->stage, 0, (size_t)n * sizeof(double), e->stream));
     if (m > 0) hipLaunchKernelGGL(k_rp_w, g, tb, 0, e->stream, m, (const double *)rp->rv, (const double *)rp->z, (const double *)rp->y, rp->stage + n);
-    hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.M.nblk))), tb, 0, e->stream, e->c.M, (const double *)rp->stage, rp->part, 2);   // A_g' w
+    launch_spmv(e, e->c.M, rp->stage, rp->part, 2);   // A_g' w
     if (int rc = rp_allreduce(rp, rp->part, n, 0)) return rc;
     hipLaunchKernelGGL(k_rp_b, g, tb, 0, e->stream, n, st.sigma, (const double *)rp->x, (const double *)rp->q, (const double *)rp->part, rp->b, rp->pa);
     // PCG from the previous x~
@@ -514,7 +513,7 @@ extern "C" int osqp_amd_rp_solve(osqp_amd_rp *rp, osqp_amd_rp_info *info) {
     rp->last_iters = rp->hS->iters;
     rp->pcg_iters += rp->hS->iters;
     // x, z, y
-    if (m > 0) hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), tb, 0, e->stream, e->c.A, (const double *)rp->xt, rp->zt, 0);
+    if (m > 0) launch_spmv(e, e->c.A, rp->xt, rp->zt, 0);
     checked = st.check_termination && it % st.check_termination == 0;
     if (cert && (checked || it == st.max_iter)) {          // this iteration ends in a check: x and y as they are now, for dx and dy
       HIPCHK(hipMemcpyAsync(rp->xp, rp->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
@@ -638,7 +637,7 @@ extern "C" int osqp_amd_rp_warm_start(osqp_amd_rp *rp, const double *x, const do
     if (int rc = rp_upload(rp, rp->part, x, (size_t)n)) return rc;
     hipLaunchKernelGGL(k_rp_unscale, rp_grid(), dim3(TB), 0, e->stream, n, (const double *)rp->Dinv, (const double *)rp->part, 1.0, rp->x);      // Dinv x
     HIPCHK(hipMemcpyAsync(rp->xt, rp->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));                                    // the PCG starts from x~
-    if (m > 0) hipLaunchKernelGGL(k_spmv, dim3(std::min(MAX_PARTS, std::max(1, e->c.A.nblk))), dim3(TB), 0, e->stream, e->c.A, (const double *)rp->x, rp->z, 0);
+    if (m > 0) launch_spmv(e, e->c.A, rp->x, rp->z, 0);
   }
   if (y_loc && m > 0) {
     if (int rc = rp_upload(rp, rp->zt, y_loc, (size_t)m)) return rc;
