@@ -203,8 +203,26 @@ long long hipeng_resident_dump(hipeng *e, int *row, int *col, double *val, long 
 /* Dense-direct solve (engine.hip FORM_DENSE_DIRECT, csrc/dense_direct.h): test / measurement hook for its blocked inversion.
  * A: n x n row-major symmetric positive definite host matrix, n a multiple of 128; Ainv: its inverse (explicit, by blocked
  * Gauss-Jordan on v_mfma_f64_16x16x4_f64); ms[0]: device time of the inversion, ms[1]: of one n x n x n GEMM of the same
- * kernel.  Returns 0, 1 when a pivot was not positive, or a HIPENG_ERR_* code. */
+ * kernel.  Returns 0, 1 when a pivot was not positive, or a HIPENG_ERR_* code.  The route is the blocked Cholesky one unless
+ * OSQP_AMD_DENSE_CHOL=0 (then the block sweeps); the GEMM kernel is the one the engines of this process use. */
 int hipeng_dense_invert_selftest(int n, const double *A, double *Ainv, double *ms);
+/* The same inversion with both choices explicit: route 0 block sweeps (dd_invert_sweep), 1 blocked Cholesky (dd_invert_chol);
+ * gemm 0 k_dd_gemm_tn (operands from global memory), 1 k_dd_gemm_tn_lds.  What the process's engines have latched from
+ * OSQP_AMD_DENSE_GEMM_LDS is as it was afterwards.  Returns 0, 1 when a pivot was not positive, or a HIPENG_ERR_* code. */
+int hipeng_dense_invert_route(int n, const double *A, double *Ainv, int route, int gemm);
+/* The two once-per-process switches of the dense-direct solve as this process has latched them: out[0] the LDS-staged GEMM kernel
+ * (OSQP_AMD_DENSE_GEMM_LDS), out[1] Cholesky before the sweeps (OSQP_AMD_DENSE_CHOL); 0 / 1, or -1 while no engine has read it. */
+int hipeng_dense_switches(int out[2]);
+/* One launch of one of its GEMM kernels by name (kernel 0: k_dd_gemm_tn, 1: k_dd_gemm_tn_lds), grid (ceil(N / 128), ceil(M / 128),
+ * slices):  C = beta C + alpha T' diag(w) B.  T: [K][ldt] (T' is M x K), B: [K][ldb], w: [K] or NULL, all row-major on the host.
+ * C: [Mp][ldc] with Mp = M rounded up to a multiple of 128, in: C0, out: the result -- rows M.. and columns N.. are uploaded and
+ * downloaded too, so that the caller can see they were left alone.  Masks as the kernels have them: 128 x 128 tiles whose rows start in
+ * [sr0, sr1) or columns in [sc0, sc1) and, with `lower`, tiles above the diagonal are not written; kmode 1 / 2 starts k at the tile's first
+ * column / row.  ksl > 0: split K -- ceil(K / ksl) slices into a scratch, summed into C by k_dd_sum_slices (M = 128, beta = 0 and no
+ * masked tile: that kernel sums 128 rows and overwrites).  HIPENG_ERR_ARG and no launch for an odd ld, an ld below its extent (ldt < M,
+ * ldb < N, ldc < N) or a split K outside those limits.  Returns 0 or a HIPENG_ERR_* code. */
+int hipeng_dense_gemm_selftest(int kernel, int M, int N, int K, const double *T, int ldt, const double *B, int ldb, const double *w,
+                               double *C, int ldc, double alpha, double beta, int sr0, int sr1, int sc0, int sc1, int lower, int kmode, int ksl);
 
 /* O(nnz) parts of the single-QP engine's solution derivatives (csrc/kkt_sens.h: k_sens_grad, k_sens_tan_rhs).  One hipsens per
  * workspace, created at its first osqp_amd_adjoint / osqp_amd_tangent call and kept until cleanup; every call runs on the stream

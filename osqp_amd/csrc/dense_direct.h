@@ -191,14 +191,23 @@ __global__ void __launch_bounds__(TB, 2) k_dd_gemm_tn_lds(double *C, int ldc, co
 }
 
 // every product of this file goes through here: the LDS-staged kernel, or (OSQP_AMD_DENSE_GEMM_LDS=0) the one that feeds the MFMAs from global memory
+// (dd_gemm_lds: -1 until the first product of the process reads the switch; file scope so that the test hooks of dense_direct_host.h
+// can report it and run an inversion on either kernel)
+static int dd_gemm_lds = -1;
+constexpr size_t DD_GEMM_LDS_BYTES = (size_t)4 * DD_KC * DD_LP * sizeof(double);
+static bool dd_gemm_lds_attr() {
+  if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dd_gemm_tn_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DD_GEMM_LDS_BYTES) == hipSuccess) return true;
+  (void)hipGetLastError();
+  return false;
+}
 static void dd_gemm(hipStream_t stream, dim3 grid, double *C, int ldc, const double *T, int ldt, const double *B, int ldb, const double *w,
                     int M, int N, int K, double alpha, double beta, int sr0, int sr1, int sc0, int sc1, int lower, int kmode, int ksl = 0, long long cz = 0) {
-  static int lds = -1;
-  constexpr size_t bytes = (size_t)4 * DD_KC * DD_LP * sizeof(double);
+  int &lds = dd_gemm_lds;
+  constexpr size_t bytes = DD_GEMM_LDS_BYTES;
   if (lds < 0) {
     lds = 1;
     if (const char *x = getenv("OSQP_AMD_DENSE_GEMM_LDS")) lds = atoi(x) != 0;
-    if (lds && hipFuncSetAttribute(reinterpret_cast<const void *>(k_dd_gemm_tn_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) { (void)hipGetLastError(); lds = 0; }
+    if (lds && !dd_gemm_lds_attr()) lds = 0;
   }
   if (lds) hipLaunchKernelGGL(k_dd_gemm_tn_lds, grid, dim3(TB), bytes, stream, C, ldc, T, ldt, B, ldb, w, M, N, K, alpha, beta, sr0, sr1, sc0, sc1, lower, kmode, ksl, cz);
   else hipLaunchKernelGGL(k_dd_gemm_tn, grid, dim3(TB), 0, stream, C, ldc, T, ldt, B, ldb, w, M, N, K, alpha, beta, sr0, sr1, sc0, sc1, lower, kmode, ksl, cz);

@@ -123,6 +123,7 @@ static int build_dense_direct(hipeng *e, const csc *P, const csc *A, bool small_
 // was not positive) and the inverse is computed again by the Cholesky route; if that fails too the engine drops the dense solve.
 #define DD_CHECK 1e-6
 #define DD_FWD 8.0
+static int dd_chol_first = -1;            // OSQP_AMD_DENSE_CHOL as the first refresh of the process read it (-1: not read yet; hipeng_dense_switches)
 static int dd_refresh(hipeng *e) {
   const DdCtx &dd = e->dd;
   const int nap = dd.nap;
@@ -146,7 +147,7 @@ static int dd_refresh(hipeng *e) {
   //   y = S^-1 u (into vv), z = S0 y (into Bp), err = max |z - u|.
   // Failed (or a pivot was not positive): the matrix as formed goes through the blocked Cholesky route (cond eps; five times slower
   // until its triangular inversion is parallelised better) and is checked again.  OSQP_AMD_DENSE_CHOL=1 takes that route at once.
-  static int chol_first = -1;
+  int &chol_first = dd_chol_first;
   if (chol_first < 0) { chol_first = 0; if (const char *x = getenv("OSQP_AMD_DENSE_CHOL")) chol_first = atoi(x) != 0; }
   const dim3 gg(std::min(1024, nap / 4));
   const size_t lds = (size_t)nap * sizeof(double);
@@ -200,29 +201,102 @@ static void launch_dense_direct(hipeng *e) {
   hipLaunchKernelGGL(k_dd_finish, dim3(elem_grid(e->n)), dim3(TB), 0, e->stream, e->c, dd);
 }
 
-// Test / measurement hook: the blocked inversion alone.  A: n x n row-major symmetric positive definite on the host (n a multiple
-// of 128); Ainv receives the inverse, ms[0] the time of the inversion on the device, ms[1] that of one n x n x n TN GEMM
-// (C = A' A on the matrix cores: the kernel's rate).  Returns 0, or 1 when a pivot was not positive.
-extern "C" int hipeng_dense_invert_selftest(int n, const double *A, double *Ainv, double *ms) {
+// ---- test / measurement hooks (include/osqp_amd_engine.h): each allocates, uploads, launches on stream 0, downloads and frees ----------------
+struct DdHookMem {                        // the device buffers and events of one hook call, released on every way out
+  std::vector<void *> bufs;
+  std::vector<hipEvent_t> evs;
+  template <class T> bool alloc(T **p, size_t count) {
+    void *q = nullptr;
+    if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return true; }
+    bufs.push_back(q); *p = static_cast<T *>(q);
+    return false;
+  }
+  bool event(hipEvent_t *ev) {
+    if (hipEventCreate(ev) != hipSuccess) { (void)hipGetLastError(); return true; }
+    evs.push_back(*ev);
+    return false;
+  }
+  ~DdHookMem() { for (void *q : bufs) (void)hipFree(q); for (hipEvent_t ev : evs) (void)hipEventDestroy(ev); }
+};
+
+// The blocked inversion alone, on the route and the GEMM kernel named (gemm < 0: the kernel dd_gemm has latched or will latch from the
+// environment, as in an engine).  timed: one n x n x n TN GEMM ahead of it, for the kernel's rate (ms[1]; ms[0]: the inversion).
+static int dd_hook_invert(int n, const double *A, double *Ainv, int route, int gemm, bool timed, double *ms) {
   if (n <= 0 || n % DD_NB || !A || !Ainv) return HIPENG_ERR_ARG;
+  DdHookMem mem;
   double *dA = nullptr, *dC = nullptr, *D = nullptr, *Bp = nullptr, *T = nullptr, *Tp = nullptr; int *flag = nullptr;
   const size_t nn = (size_t)n * n;
-  HIPCHK(hipMalloc(&dA, nn * 8)); HIPCHK(hipMalloc(&dC, nn * 8)); HIPCHK(hipMalloc(&D, DD_NB * DD_NB * 8)); HIPCHK(hipMalloc(&Bp, (size_t)DD_NB * n * 8));
-  HIPCHK(hipMalloc(&T, (size_t)DD_NB * n * 8)); HIPCHK(hipMalloc(&Tp, (size_t)DD_NB * n * 8)); HIPCHK(hipMalloc(&flag, 16));
+  if (mem.alloc(&dA, nn) || mem.alloc(&dC, nn) || mem.alloc(&D, (size_t)DD_NB * DD_NB) || mem.alloc(&Bp, (size_t)DD_NB * n) ||
+      mem.alloc(&T, (size_t)DD_NB * n) || mem.alloc(&Tp, (size_t)DD_NB * n) || mem.alloc(&flag, (size_t)4)) return HIPENG_ERR_HIP;
   HIPCHK(hipMemcpy(dA, A, nn * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemset(flag, 0, 16));
-  hipEvent_t e0, e1, e2; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventCreate(&e2));
+  hipEvent_t e0, e1, e2;
+  if (mem.event(&e0) || mem.event(&e1) || mem.event(&e2)) return HIPENG_ERR_HIP;
   HIPCHK(hipEventRecord(e0, 0));
-  dd_gemm(0, dim3(n / 128, n / 128), dC, n, (const double *)dA, n, (const double *)dA, n, (const double *)nullptr, n, n, n, 1.0, 0.0, -1, -1, -1, -1, 0, 0);
+  if (timed) dd_gemm(0, dim3(n / 128, n / 128), dC, n, (const double *)dA, n, (const double *)dA, n, (const double *)nullptr, n, n, n, 1.0, 0.0, -1, -1, -1, -1, 0, 0);
   HIPCHK(hipEventRecord(e1, 0));
-  int chol = 1;
-  if (const char *x = getenv("OSQP_AMD_DENSE_CHOL")) chol = atoi(x) != 0;
-  if (int rc = chol ? dd_invert_chol(0, dA, n, Bp, T, Tp, dC, flag) : dd_invert_sweep(0, dA, n, D, Bp, T, flag)) return rc;
+  const int keep = dd_gemm_lds;
+  if (gemm >= 0) {
+    if (gemm && !dd_gemm_lds_attr()) return HIPENG_ERR_HIP;
+    dd_gemm_lds = gemm != 0;
+  }
+  const int rc = route ? dd_invert_chol(0, dA, n, Bp, T, Tp, dC, flag) : dd_invert_sweep(0, dA, n, D, Bp, T, flag);
+  if (gemm >= 0) dd_gemm_lds = keep;        // (what production has latched, or has not yet, is as it was)
+  if (rc) return rc;
   HIPCHK(hipEventRecord(e2, 0)); HIPCHK(hipEventSynchronize(e2));
   float t0 = 0, t1 = 0; HIPCHK(hipEventElapsedTime(&t0, e0, e1)); HIPCHK(hipEventElapsedTime(&t1, e1, e2));
   if (ms) { ms[0] = t1; ms[1] = t0; }
   int hf = 0;
   HIPCHK(hipMemcpy(Ainv, dA, nn * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&hf, flag, 4, hipMemcpyDeviceToHost));
-  (void)hipFree(dA); (void)hipFree(dC); (void)hipFree(D); (void)hipFree(Bp); (void)hipFree(T); (void)hipFree(Tp); (void)hipFree(flag);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
   return hf ? 1 : 0;
+}
+
+// A: n x n row-major symmetric positive definite on the host (n a multiple of 128); Ainv receives the inverse, ms[0] the time of the
+// inversion on the device, ms[1] that of one n x n x n TN GEMM (C = A' A on the matrix cores: the kernel's rate).  The Cholesky route
+// unless OSQP_AMD_DENSE_CHOL=0, the GEMM kernel of the engines.  Returns 0, or 1 when a pivot was not positive.
+extern "C" int hipeng_dense_invert_selftest(int n, const double *A, double *Ainv, double *ms) {
+  int chol = 1;
+  if (const char *x = getenv("OSQP_AMD_DENSE_CHOL")) chol = atoi(x) != 0;
+  return dd_hook_invert(n, A, Ainv, chol, -1, true, ms);
+}
+// The same inversion with both choices explicit: route 0 block sweeps / 1 blocked Cholesky, gemm 0 k_dd_gemm_tn / 1 k_dd_gemm_tn_lds.
+extern "C" int hipeng_dense_invert_route(int n, const double *A, double *Ainv, int route, int gemm) {
+  if ((route != 0 && route != 1) || (gemm != 0 && gemm != 1)) return HIPENG_ERR_ARG;
+  return dd_hook_invert(n, A, Ainv, route, gemm, false, nullptr);
+}
+// What this process has latched: out[0] the LDS-staged GEMM (dd_gemm), out[1] Cholesky first (dd_refresh); 0 / 1, -1: not read yet.
+extern "C" int hipeng_dense_switches(int out[2]) {
+  if (!out) return HIPENG_ERR_ARG;
+  out[0] = dd_gemm_lds; out[1] = dd_chol_first;
+  return 0;
+}
+
+// One launch of a GEMM kernel by name (kernel 0: k_dd_gemm_tn, 1: k_dd_gemm_tn_lds), not through dd_gemm's switch:
+// C = beta C + alpha T' diag(w) B with the kernel's own masks.  T: [K][ldt], B: [K][ldb], w: [K] or NULL; C: [Mp][ldc], Mp = M rounded up
+// to a multiple of 128 -- the rows the grid covers: rows M.. and columns N.. go up and come back so that a caller sees them left alone.
+// ksl > 0: split K as step (b) of dd_invert_chol has it -- slice z of ceil(K / ksl) writes its product to plane z of a scratch (cz =
+// M ldc) and k_dd_sum_slices adds the planes into C; that kernel sums 128 rows and overwrites, so M = 128, beta = 0 and no masked tile.
+extern "C" int hipeng_dense_gemm_selftest(int kernel, int M, int N, int K, const double *T, int ldt, const double *B, int ldb, const double *w,
+                                          double *C, int ldc, double alpha, double beta, int sr0, int sr1, int sc0, int sc1, int lower, int kmode, int ksl) {
+  if ((kernel != 0 && kernel != 1) || M <= 0 || N <= 0 || K <= 0 || !T || !B || !C || kmode < 0 || kmode > 2 || ksl < 0) return HIPENG_ERR_ARG;
+  if ((ldt & 1) || (ldb & 1) || (ldc & 1) || ldt < M || ldb < N || ldc < N) return HIPENG_ERR_ARG;      // (odd strides: the double2 loads of the LDS kernel)
+  if (ksl > 0 && (M != DD_NB || beta != 0.0 || lower || sr1 > sr0 || sc1 > sc0)) return HIPENG_ERR_ARG;
+  const int Mp = (M + DD_NB - 1) / DD_NB * DD_NB, nz = ksl > 0 ? (K + ksl - 1) / ksl : 1;
+  const long long cz = (long long)M * ldc;
+  DdHookMem mem;
+  double *dT = nullptr, *dB = nullptr, *dw = nullptr, *dC = nullptr, *part = nullptr;
+  if (mem.alloc(&dT, (size_t)K * ldt) || mem.alloc(&dB, (size_t)K * ldb) || mem.alloc(&dw, (size_t)K) || mem.alloc(&dC, (size_t)Mp * ldc) ||
+      mem.alloc(&part, ksl > 0 ? (size_t)nz * cz : 1)) return HIPENG_ERR_HIP;
+  HIPCHK(hipMemcpy(dT, T, (size_t)K * ldt * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dB, B, (size_t)K * ldb * 8, hipMemcpyHostToDevice));
+  if (w) HIPCHK(hipMemcpy(dw, w, (size_t)K * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dC, C, (size_t)Mp * ldc * 8, hipMemcpyHostToDevice));
+  if (kernel == 1 && !dd_gemm_lds_attr()) return HIPENG_ERR_HIP;
+  const dim3 grid((N + 127) / 128, (M + 127) / 128, nz);
+  double *out = ksl > 0 ? part : dC;
+  const double *wd = w ? dw : nullptr;
+  if (kernel) hipLaunchKernelGGL(k_dd_gemm_tn_lds, grid, dim3(TB), DD_GEMM_LDS_BYTES, 0, out, ldc, (const double *)dT, ldt, (const double *)dB, ldb, wd, M, N, K, alpha, beta, sr0, sr1, sc0, sc1, lower, kmode, ksl, cz);
+  else hipLaunchKernelGGL(k_dd_gemm_tn, grid, dim3(TB), 0, 0, out, ldc, (const double *)dT, ldt, (const double *)dB, ldb, wd, M, N, K, alpha, beta, sr0, sr1, sc0, sc1, lower, kmode, ksl, cz);
+  if (ksl > 0) hipLaunchKernelGGL(k_dd_sum_slices, dim3(std::min(1024, (DD_NB * N + TB - 1) / TB)), dim3(TB), 0, 0, dC, ldc, (const double *)part, cz, nz, N);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(C, dC, (size_t)Mp * ldc * 8, hipMemcpyDeviceToHost));
+  return 0;
 }

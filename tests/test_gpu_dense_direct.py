@@ -43,23 +43,29 @@ def _rel(a, b):
 
 
 def test_blocked_inversion_against_numpy(gpu_lib):
-    """hipeng_dense_invert_selftest: explicit inverse of a symmetric positive definite matrix by blocked Gauss-Jordan, every
-    flop outside the 128 x 128 pivot blocks in the MFMA GEMM kernel."""
+    """hipeng_dense_invert_route: explicit inverse of a symmetric positive definite matrix by BOTH blocked routes -- the symmetric
+    block sweeps (blocked Gauss-Jordan; route 0: k_dd_pivot, the panels, k_dd_mirror negating) and the blocked Cholesky route
+    (route 1: k_dd_chol, k_dd_trsm, X'X) --, every flop outside the 128 x 128 diagonal blocks in the MFMA GEMM kernel (the
+    LDS-staged one, as an engine uses by default).  A pivot that is not positive is reported by k_dd_pivot and by k_dd_chol.
+    (hipeng_dense_invert_selftest, which this test called before, takes the Cholesky route unless told otherwise: the sweeps
+    had no stand-alone test.  tests/test_gpu_dense_kernels.py holds both routes to a derived bar.)"""
     import osqp_amd
-    f = osqp_amd.lib().hipeng_dense_invert_selftest
+    f = osqp_amd.lib().hipeng_dense_invert_route
     f.restype = C.c_int
-    f.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    f.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     for n in (128, 384, 1280):
         rng = np.random.default_rng(n)
         G = rng.standard_normal((n, n + 50))
         A = G @ G.T / n + 0.1 * np.eye(n)
-        Ainv = np.zeros((n, n)); ms = (C.c_double * 2)()
-        assert f(n, A.ctypes.data_as(C.c_void_p), Ainv.ctypes.data_as(C.c_void_p), ms) == 0
-        assert np.abs(Ainv @ A - np.eye(n)).max() < 1e-10
-        assert np.abs(Ainv - np.linalg.inv(A)).max() <= 1e-10 * np.abs(Ainv).max()
+        for route in (0, 1):
+            Ainv = np.zeros((n, n))
+            assert f(n, A.ctypes.data_as(C.c_void_p), Ainv.ctypes.data_as(C.c_void_p), route, 1) == 0
+            assert np.abs(Ainv @ A - np.eye(n)).max() < 1e-10
+            assert np.abs(Ainv - np.linalg.inv(A)).max() <= 1e-10 * np.abs(Ainv).max()
     A = np.eye(256); A[200, 200] = -1.0                       # a pivot that is not positive is reported
-    Ainv = np.zeros((256, 256))
-    assert f(256, A.ctypes.data_as(C.c_void_p), Ainv.ctypes.data_as(C.c_void_p), None) == 1
+    for route in (0, 1):
+        Ainv = np.zeros((256, 256))
+        assert f(256, A.ctypes.data_as(C.c_void_p), Ainv.ctypes.data_as(C.c_void_p), route, 1) == 1
 
 
 @pytest.mark.parametrize("nf,md", [(60, 150), (300, 700), (700, 1500)])
