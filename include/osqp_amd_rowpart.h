@@ -48,8 +48,8 @@ typedef struct {
 } osqp_amd_rp_settings;                 /* meaning and defaults of the fields: OSQPSettings (include/osqp_amd_types.h) */
 
 typedef struct {
-  int status;                           /* OSQP_SOLVED = 1, OSQP_SOLVED_INACCURATE = 2, OSQP_MAX_ITER_REACHED = -2; with the infeasibility tests on
-                                           also OSQP_PRIMAL_INFEASIBLE = -3, OSQP_DUAL_INFEASIBLE = -4 and their inaccurate forms 3, 4 */
+  int status;                           /* OSQP_SOLVED, OSQP_SOLVED_INACCURATE or OSQP_MAX_ITER_REACHED (include/osqp_amd_types.h); with the infeasibility
+                                           tests on also OSQP_PRIMAL_INFEASIBLE, OSQP_DUAL_INFEASIBLE and their _INACCURATE forms */
   int iter, rho_updates;
   long long pcg_iters, collectives;
   double obj_val, pri_res, dua_res, rho_estimate;
@@ -113,20 +113,19 @@ int  osqp_amd_rp_update_rho(osqp_amd_rp *rp, double rho);
 /* One array of the handle's state, in the scaled space the loop iterates in: synchronises the engine's stream, copies the
  * array to out[0, count) and returns count, or a negative HIPENG_ERR_* code (cap < count, unknown `which`).  Nothing is
  * written on the device.  x, x~, minv, b, r: n doubles (r: the last PCG residual); z, y, rho per row: m_loc doubles;
- * SC15: the fifteen scalars of the last termination check as the device left them (maxima of the rank's rows first:
- * pri_u z_u Ax_u pri_s z_s Ax_s | dua_u dua_s q_u q_s Aty_u Aty_s Px_u Px_s x'(Px/2 + q); _u: unscaled with Einv / Dinv);
  * S: the PCG's device-side record as nine doubles: rz[0] rz[1] rr tol2 bb done iters cap bad.
- * DX, DY: dx (n) and the projected dy (m_loc) of the last check with the infeasibility tests on (after an infeasible status:
- * the certificates); SC7: that check's seven scalars  |E dy|  row violation  u'dy+ + l'dy-  |Dinv A'dy|  |D dx|  q'dx
- * |Dinv P dx|  (the first three as the all-reduces left them; E, D, Dinv only where the fifteen's _u forms use them).
+ * SC15: the fifteen scalars of the last termination check as the device left them; SC7: the seven of the last check with the
+ * infeasibility tests on (the first three as the all-reduces left them); DESIGN.md section 7 has the table of the twenty-two slots.
+ * DX, DY: dx (n) and the projected dy (m_loc) of that check (after an infeasible status: the certificates).
  * Q, L, U: the scaled q (n) and bounds (m_loc) the loop reads, as osqp_amd_rp_update_lin_cost / _bounds left them. */
 enum { OSQP_AMD_RP_PEEK_X = 0, OSQP_AMD_RP_PEEK_XT, OSQP_AMD_RP_PEEK_Z, OSQP_AMD_RP_PEEK_Y, OSQP_AMD_RP_PEEK_RHO_VEC, OSQP_AMD_RP_PEEK_MINV,
        OSQP_AMD_RP_PEEK_B, OSQP_AMD_RP_PEEK_R, OSQP_AMD_RP_PEEK_SC15, OSQP_AMD_RP_PEEK_S,
        OSQP_AMD_RP_PEEK_DX, OSQP_AMD_RP_PEEK_DY, OSQP_AMD_RP_PEEK_SC7, OSQP_AMD_RP_PEEK_Q, OSQP_AMD_RP_PEEK_L, OSQP_AMD_RP_PEEK_U };
 int  osqp_amd_rp_peek(osqp_amd_rp *rp, int which, double *out, long long cap);
-/* The host's decision at a termination check with the infeasibility tests on, on given scalars (no handle, no device): sc22 = the
- * fifteen + the seven; unscaled: the _u forms decide (scaled data without scaled_termination); eps4 = eps_abs, eps_rel,
- * eps_prim_inf, eps_dual_inf; approximate: 10 x each.  Returns 0 none, 1 the residuals pass, 3 primal infeasible, 4 dual infeasible. */
+/* The host's decision at a termination check on given scalars (no handle, no device): sc22 = the fifteen + the seven;
+ * unscaled: the _u forms decide (scaled data without scaled_termination); eps4 = eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
+ * approximate: 10 x each.  Returns the verdict as rowpart_native.h names it: RP_GO_ON = 0, RP_RESIDUALS_PASS = 1, RP_PRIMAL_INF = 3,
+ * RP_DUAL_INF = 4.  A test whose tolerance is 0 reads none of its scalars. */
 int  osqp_amd_rp_test_verdict(const double *sc22, int unscaled, double c, int m_total, const double *eps4,
                               double pri_res, double dua_res, int approximate);
 

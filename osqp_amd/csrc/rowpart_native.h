@@ -13,9 +13,25 @@
 //   with osqp_amd_rp_set_infeasibility (src/auxil.c:361-512):  dx = x - x_prev;  dy = y - y_prev projected on the polar of the
 //                                         recession cone;  ALL-REDUCE([P_g dx; A_g' dy; u'dy+ + l'dy-]);  ALL-REDUCE max([|E dy|; row violation])
 #include <dlfcn.h>
+#include "../../include/osqp_amd_types.h"
 #include "../../include/osqp_amd_rowpart.h"
 
 #define RP_G 128                 // workgroups (= partials per dot product) of the n- and m-vector kernels
+#define RP_DIV_TOL 1e-30         // the literal, not OSQP_DIVISION_TOL: 1.0 / 1e30 is another double
+// The scalars of a termination check, in the order the device holds them (rp->sc15), the read-back carries them and the host keeps
+// them (rp->sc); DESIGN.md section 7 has the table.  _U: unscaled with Einv / Dinv, _S: in the space the loop iterates in.
+enum RpScalar {
+  RSC_PRI_U, RSC_Z_U, RSC_AX_U, RSC_PRI_S, RSC_Z_S, RSC_AX_S,                               // k_rp_pri: |Ax - z|, |z|, |Ax| over the rows (ALL-REDUCE max)
+  RSC_DUA_U, RSC_DUA_S, RSC_Q_U, RSC_Q_S, RSC_ATY_U, RSC_ATY_S, RSC_PX_U, RSC_PX_S, RSC_OBJ,   // k_rp_dua: |Px + q + A'y|, |q|, |A'y|, |Px|, x'(Px/2 + q)
+  // the seven of the infeasibility tests, written only by a check with a test on: |E dy|, row violation (both ALL-REDUCE max),
+  // u'dy+ + l'dy- (summed over the ranks), |Dinv A'dy|, |D dx|, q'dx, |Dinv P dx|
+  RSC_NDY, RSC_VIOL, RSC_LHS, RSC_NATDY, RSC_NDX, RSC_QDX, RSC_NPDX,
+  RSC_ALL, RSC_CHECK = RSC_NDY, RSC_CERT = RSC_ALL - RSC_CHECK,                           // 22 = 15 + 7
+  RSC_CHECK_PAD = 16, RSC_ALL_PAD = 24                                                  // what a check zeroes and the buffers hold: padded to eight doubles
+};
+static_assert(RSC_CHECK == 15 && RSC_CERT == 7, "osqp_amd_rp_peek and osqp_amd_rp_test_verdict promise these counts");
+// what a termination check finds (rp_verdict_of; osqp_amd_rp_test_verdict exports the values)
+enum { RP_GO_ON = 0, RP_RESIDUALS_PASS = 1, RP_PRIMAL_INF = 3, RP_DUAL_INF = 4 };
 struct RpS { double rz[2]; double rr, tol2, bb; int done, iters, cap, bad; };
 
 // sum of RP_G partials, the same order in every workgroup and on every rank
@@ -54,7 +70,7 @@ __global__ void __launch_bounds__(TB) k_rp_s0(RpS *S, const double *pbb, const d
   __shared__ double red[16];
   const double bb = rp_total(pbb, red), rz = rp_total(prz, red), rr = rp_total(prr, red);
   if (threadIdx.x == 0) {
-    S->bb = bb; S->rz[0] = rz; S->rr = rr; S->tol2 = fmax(eps * eps * bb, 1e-30);
+    S->bb = bb; S->rz[0] = rz; S->rr = rr; S->tol2 = fmax(eps * eps * bb, RP_DIV_TOL);
     S->iters = 0; S->cap = cap; S->bad = 0; S->done = !(rr > S->tol2);
   }
 }
@@ -113,7 +129,7 @@ __global__ void __launch_bounds__(TB) k_rp_admm_z(int m, double alpha, const dou
 __global__ void __launch_bounds__(TB) k_rp_rho(int m, double rho, const double *l, const double *u, double *rv) {
   for (int i = blockIdx.x * TB + threadIdx.x; i < m; i += gridDim.x * TB) {
     const double lo = l[i], hi = u[i];
-    rv[i] = (lo < -1e26 && hi > 1e26) ? 1e-6 : ((hi - lo < 1e-4) ? 1e3 * rho : rho);
+    rv[i] = (lo < -INF_BOUND && hi > INF_BOUND) ? RHO_MIN : ((hi - lo < RHO_TOL) ? RHO_EQ_OVER_RHO_INEQ * rho : rho);
   }
 }
 // this rank's share of diag(P) + sum_i rho_i A_ij^2 (the Jacobi preconditioner before the all-reduce), from the rows of [P_g | A_g']
@@ -166,9 +182,8 @@ __global__ void __launch_bounds__(TB) k_rp_unscale(int n, const double *s, const
 }
 
 // ---- infeasibility tests (is_primal_infeasible / is_dual_infeasible, src/auxil.c:361-512), only after osqp_amd_rp_set_infeasibility ----
-// out7 = sc15 + 15:  0 |E dy|  1 row violation (both ALL-REDUCE max)  2 u'dy+ + l'dy- (summed over the ranks)  3 |Dinv A'dy|  4 |D dx|  5 q'dx  6 |Dinv P dx|
-// (E, Einv, D, Dinv: null under scaled_termination or unscaled data).  None of the seven depends on a tolerance, so the host applies
-// eps and 10 eps to the same read-back.
+// out7 = sc15 + RSC_NDY: the seven of enum RpScalar, by their distance from RSC_NDY (E, Einv, D, Dinv: null under scaled_termination
+// or unscaled data).  None of the seven depends on a tolerance, so the host applies eps and 10 eps to the same read-back.
 __global__ void __launch_bounds__(TB) k_rp_delta_x(int n, const double *x, const double *xp, double *dx) {
   for (int j = blockIdx.x * TB + threadIdx.x; j < n; j += gridDim.x * TB) dx[j] = x[j] - xp[j];
 }
@@ -176,8 +191,8 @@ __global__ void __launch_bounds__(TB) k_rp_delta_x(int n, const double *x, const
 __global__ void __launch_bounds__(TB) k_rp_delta_y(int m, const double *y, const double *yp, const double *l, const double *u, double *dy) {
   for (int i = blockIdx.x * TB + threadIdx.x; i < m; i += gridDim.x * TB) {
     double d = y[i] - yp[i];
-    if (u[i] > 1e26) d = l[i] < -1e26 ? 0.0 : fmin(d, 0.0);
-    else if (l[i] < -1e26) d = fmax(d, 0.0);
+    if (u[i] > INF_BOUND) d = l[i] < -INF_BOUND ? 0.0 : fmin(d, 0.0);
+    else if (l[i] < -INF_BOUND) d = fmax(d, 0.0);
     dy[i] = d;
   }
 }
@@ -200,8 +215,8 @@ __global__ void __launch_bounds__(TB) k_rp_cert_rows(int m, const double *dy, co
     const double d = dy[i], a = Einv ? Einv[i] * adx[i] : adx[i];
     ny = fmax(ny, fabs(E ? E[i] * d : d));
     s += u[i] * fmax(d, 0.0) + l[i] * fmin(d, 0.0);
-    if (u[i] < 1e26) viol = fmax(viol, a);
-    if (l[i] > -1e26) viol = fmax(viol, -a);
+    if (u[i] < INF_BOUND) viol = fmax(viol, a);
+    if (l[i] > -INF_BOUND) viol = fmax(viol, -a);
   }
   ny = block_max(ny, red);
   viol = block_max(viol, red);
@@ -232,11 +247,11 @@ __global__ void __launch_bounds__(TB) k_rp_bounds(int m, const double *lin, cons
   __shared__ double red[16];
   double bad = 0.0, chg = 0.0, eq = 0.0;
   for (int i = threadIdx.x; i < m; i += TB) {
-    const double lo = fmax(lin[i], -1e30), hi = fmin(uin[i], 1e30);
+    const double lo = fmax(lin[i], -OSQP_INFTY), hi = fmin(uin[i], OSQP_INFTY);
     if (lo > hi) bad = 1.0;
     const double a = E[i] * lo, b = E[i] * hi;
     ln[i] = a; un[i] = b;
-    const int was = (l[i] < -1e26 && u[i] > 1e26) ? -1 : (u[i] - l[i] < 1e-4), now = (a < -1e26 && b > 1e26) ? -1 : (b - a < 1e-4);
+    const int was = (l[i] < -INF_BOUND && u[i] > INF_BOUND) ? -1 : (u[i] - l[i] < RHO_TOL), now = (a < -INF_BOUND && b > INF_BOUND) ? -1 : (b - a < RHO_TOL);
     if (was != now) chg = 1.0;
     if (now == 1) eq = 1.0;
   }
@@ -279,7 +294,7 @@ struct osqp_amd_rp {
   bool scaled = false;
   double *x, *xt, *q, *D, *Dinv, *minv, *r, *zz, *Kp, *b, *part, *both, *stage;      // n (both: 2n, stage: n + m)
   double *z, *y, *l, *u, *E, *Einv, *rv, *zt, *ax;                                   // m
-  double *pa, *pb, *pc, *sc15;                                                      // RP_G partials x 3; 6 + 9 check scalars (+ 7 of the infeasibility tests)
+  double *pa, *pb, *pc, *sc15;                                                      // RP_G partials x 3; the check scalars (enum RpScalar, RSC_ALL_PAD doubles)
   double *xp, *yp, *dxy, *cb, *ln, *un;                                             // x, y before the update (n, m); [dx ; dy] (n + m); [P dx ; A'dy ; lhs] (2n + 1); staged bounds (m)
   double eps_pinf = 0.0, eps_dinf = 0.0;                                            // 0: that test is off (osqp_amd_rp_set_infeasibility)
   int last_status = 0;
@@ -288,8 +303,14 @@ struct osqp_amd_rp {
   long long collectives = 0, pcg_iters = 0;
   int last_iters = 4, rho_updates = 0;
   bool rho_set = false;                                                             // rv and minv hold rp->rho (false until the first solve)
-  double sc[22];
+  double sc[RSC_ALL];
 };
+
+// the unscaled forms of residuals, norms and certificates decide (scaled data without scaled_termination)
+static inline bool rp_unscaled(const osqp_amd_rp *rp) { return rp->scaled && !rp->st.scaled_termination; }
+static inline bool rp_primal(int status) { return status == OSQP_PRIMAL_INFEASIBLE || status == OSQP_PRIMAL_INFEASIBLE_INACCURATE; }
+static inline bool rp_dual(int status) { return status == OSQP_DUAL_INFEASIBLE || status == OSQP_DUAL_INFEASIBLE_INACCURATE; }
+static inline bool rp_infeasible(int status) { return rp_primal(status) || rp_dual(status); }
 
 static int rp_allreduce(osqp_amd_rp *rp, double *buf, long long count, int op) {
   if (rp->world <= 1 && !rp->rccl.comm) return 0;
@@ -310,7 +331,7 @@ static void rp_apply_local(osqp_amd_rp *rp) {
 }
 static int rp_set_rho(osqp_amd_rp *rp, double rho) {
   hipeng *e = rp->e;
-  rho = std::min(std::max(rho, 1e-6), 1e6);
+  rho = std::min(std::max(rho, RHO_MIN), RHO_MAX);
   rp->rho = rho;
   if (rp->m > 0) hipLaunchKernelGGL(k_rp_rho, rp_grid(), dim3(TB), 0, e->stream, rp->m, rho, (const double *)rp->l, (const double *)rp->u, rp->rv);
   hipLaunchKernelGGL(k_rp_diag, rp_grid(), dim3(TB), 0, e->stream, e->c.M, rp->n, (const double *)rp->rv, rp->part);
@@ -336,10 +357,10 @@ extern "C" osqp_amd_rp *osqp_amd_rp_create(void *shard_engine, const double *q, 
   for (double **p : nv) bad = bad || dev_alloc(e, p, n);
   for (double **p : mv) bad = bad || dev_alloc(e, p, m);
   bad = bad || dev_alloc(e, &rp->both, 2 * n) || dev_alloc(e, &rp->stage, n + m) || dev_alloc(e, &rp->pa, (size_t)RP_G) || dev_alloc(e, &rp->pb, (size_t)RP_G) ||
-        dev_alloc(e, &rp->pc, (size_t)RP_G) || dev_alloc(e, &rp->sc15, (size_t)24) || dev_alloc(e, &rp->S, (size_t)1) ||
+        dev_alloc(e, &rp->pc, (size_t)RP_G) || dev_alloc(e, &rp->sc15, (size_t)RSC_ALL_PAD) || dev_alloc(e, &rp->S, (size_t)1) ||
         dev_alloc(e, &rp->xp, n) || dev_alloc(e, &rp->yp, m) || dev_alloc(e, &rp->dxy, n + m) || dev_alloc(e, &rp->cb, 2 * n + 1) ||
         dev_alloc(e, &rp->ln, m) || dev_alloc(e, &rp->un, m);
-  if (!bad) bad = hipHostMalloc((void **)&rp->hS, sizeof(RpS)) != hipSuccess || hipHostMalloc((void **)&rp->h15, 24 * sizeof(double)) != hipSuccess;
+  if (!bad) bad = hipHostMalloc((void **)&rp->hS, sizeof(RpS)) != hipSuccess || hipHostMalloc((void **)&rp->h15, RSC_ALL_PAD * sizeof(double)) != hipSuccess;
   if (bad) { delete rp; return nullptr; }
   std::vector<double> Dinv(n), Einv(m);
   bool scaled = c != 1.0;
@@ -382,21 +403,21 @@ extern "C" int osqp_amd_rp_use_rccl(osqp_amd_rp *rp, const void *unique_id, int 
 static int rp_check(osqp_amd_rp *rp, double *pri_res, double *dua_res, bool cert) {
   hipeng *e = rp->e;
   const int n = rp->n, m = rp->m;
-  HIPCHK(hipMemsetAsync(rp->sc15, 0, (cert ? 24 : 16) * sizeof(double), e->stream));
+  HIPCHK(hipMemsetAsync(rp->sc15, 0, (cert ? RSC_ALL_PAD : RSC_CHECK_PAD) * sizeof(double), e->stream));
   if (m > 0) {
     launch_spmv(e, e->c.A, rp->x, rp->ax, 0);
-    hipLaunchKernelGGL(k_rp_pri, dim3(1), dim3(TB), 0, e->stream, m, (const double *)rp->ax, (const double *)rp->z, (const double *)rp->Einv, rp->sc15);
+    hipLaunchKernelGGL(k_rp_pri, dim3(1), dim3(TB), 0, e->stream, m, (const double *)rp->ax, (const double *)rp->z, (const double *)rp->Einv, rp->sc15 + RSC_PRI_U);
   }
-  if (int rc = rp_allreduce(rp, rp->sc15, 6, 1)) return rc;
+  if (int rc = rp_allreduce(rp, rp->sc15 + RSC_PRI_U, RSC_DUA_U - RSC_PRI_U, 1)) return rc;
   HIPCHK(hipMemcpyAsync(rp->stage, rp->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
   if (m > 0) HIPCHK(hipMemcpyAsync(rp->stage + n, rp->y, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
   launch_spmv(e, e->c.M, rp->stage, rp->both, 1);            // P_g x
   launch_spmv(e, e->c.M, rp->stage, rp->both + n, 2);        // A_g' y
   if (int rc = rp_allreduce(rp, rp->both, 2ll * n, 0)) return rc;
-  hipLaunchKernelGGL(k_rp_dua, dim3(1), dim3(TB), 0, e->stream, n, (const double *)rp->both, (const double *)rp->q, (const double *)rp->Dinv, (const double *)rp->x, rp->sc15 + 6);
-  const bool un = rp->scaled && !rp->st.scaled_termination;
+  hipLaunchKernelGGL(k_rp_dua, dim3(1), dim3(TB), 0, e->stream, n, (const double *)rp->both, (const double *)rp->q, (const double *)rp->Dinv, (const double *)rp->x, rp->sc15 + RSC_DUA_U);
+  const bool un = rp_unscaled(rp);
   if (cert) {
-    double *dx = rp->dxy, *dy = rp->dxy + n, *out7 = rp->sc15 + 15;
+    double *dx = rp->dxy, *dy = rp->dxy + n, *out7 = rp->sc15 + RSC_NDY;
     hipLaunchKernelGGL(k_rp_delta_x, rp_grid(), dim3(TB), 0, e->stream, n, (const double *)rp->x, (const double *)rp->xp, dx);
     if (m > 0) hipLaunchKernelGGL(k_rp_delta_y, rp_grid(), dim3(TB), 0, e->stream, m, (const double *)rp->y, (const double *)rp->yp, (const double *)rp->l, (const double *)rp->u, dy);
     hipLaunchKernelGGL(k_rp_cert_x, dim3(1), dim3(TB), 0, e->stream, n, (const double *)dx, (const double *)rp->q, un ? (const double *)rp->D : nullptr, out7);
@@ -406,42 +427,45 @@ static int rp_check(osqp_amd_rp *rp, double *pri_res, double *dua_res, bool cert
     hipLaunchKernelGGL(k_rp_cert_rows, dim3(1), dim3(TB), 0, e->stream, m, (const double *)dy, un ? (const double *)rp->E : nullptr, un ? (const double *)rp->Einv : nullptr,
                        (const double *)rp->l, (const double *)rp->u, (const double *)rp->ax, out7, rp->cb + 2 * n);
     if (int rc = rp_allreduce(rp, rp->cb, 2ll * n + 1, 0)) return rc;
-    if (int rc = rp_allreduce(rp, out7, 2, 1)) return rc;
+    if (int rc = rp_allreduce(rp, out7, RSC_LHS - RSC_NDY, 1)) return rc;          // |E dy| and the row violation
     hipLaunchKernelGGL(k_rp_cert_fin, dim3(1), dim3(TB), 0, e->stream, n, (const double *)rp->cb, un ? (const double *)rp->Dinv : nullptr, out7);
   }
-  HIPCHK(hipMemcpyAsync(rp->h15, rp->sc15, (cert ? 22 : 15) * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  const size_t got = (cert ? RSC_ALL : RSC_CHECK) * sizeof(double);
+  HIPCHK(hipMemcpyAsync(rp->h15, rp->sc15, got, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  memcpy(rp->sc, rp->h15, (cert ? 22 : 15) * sizeof(double));
-  const double *s = rp->sc;             // 0 pri_u 1 z_u 2 Ax_u 3 pri_s 4 z_s 5 Ax_s | 6 dua_u 7 dua_s 8 q_u 9 q_s 10 Aty_u 11 Aty_s 12 Px_u 13 Px_s 14 obj
-  *pri_res = rp->m_total == 0 ? 0.0 : (un ? s[0] : s[3]);
-  *dua_res = un ? s[6] / rp->c : s[7];
+  memcpy(rp->sc, rp->h15, got);
+  const double *s = rp->sc;
+  *pri_res = rp->m_total == 0 ? 0.0 : (un ? s[RSC_PRI_U] : s[RSC_PRI_S]);
+  *dua_res = un ? s[RSC_DUA_U] / rp->c : s[RSC_DUA_S];
   return 0;
 }
-static bool rp_terminated(const osqp_amd_rp *rp, double pri_res, double dua_res, bool approximate) {
-  const bool un = rp->scaled && !rp->st.scaled_termination;
-  const double *s = rp->sc, k = approximate ? 10.0 : 1.0, ea = k * rp->st.eps_abs, er = k * rp->st.eps_rel;
-  const bool prim_ok = rp->m_total == 0 || pri_res < ea + er * (un ? std::max(s[1], s[2]) : std::max(s[4], s[5]));
-  const double nrm = un ? std::max(s[8], std::max(s[10], s[12])) / rp->c : std::max(s[9], std::max(s[11], s[13]));
-  return prim_ok && dua_res < ea + er * nrm;
-}
-// check_termination with the infeasibility tests (src/auxil.c:716-783) on a read-back that holds all twenty-two scalars: 0 none, 1 the
-// residuals pass, 3 primal infeasible, 4 dual infeasible.  Only all-reduced and replicated values are looked at: every rank decides alike.
-// (un: the unscaled forms decide; c: the cost scaling; eps4: eps_abs, eps_rel, eps_prim_inf, eps_dual_inf)
+// check_termination with the infeasibility tests (src/auxil.c:716-783) on the scalars of a check: RP_GO_ON, RP_RESIDUALS_PASS,
+// RP_PRIMAL_INF or RP_DUAL_INF.  Only all-reduced and replicated values are looked at: every rank decides alike.  A test whose
+// tolerance is 0 is off before any of its scalars is read, so with both off (a check without cert leaves s[RSC_NDY..] as they were)
+// this is the residual test alone.  (un: the unscaled forms decide; c: the cost scaling; eps4: eps_abs, eps_rel, eps_prim_inf, eps_dual_inf)
 static int rp_verdict_of(const double *s, bool un, double c, int m_total, const double *eps4, double pri_res, double dua_res, bool approximate) {
   const double k = approximate ? 10.0 : 1.0, ea = k * eps4[0], er = k * eps4[1];
-  const bool prim_ok = m_total == 0 || pri_res < ea + er * (un ? std::max(s[1], s[2]) : std::max(s[4], s[5]));
-  const double nrm = un ? std::max(s[8], std::max(s[10], s[12])) / c : std::max(s[9], std::max(s[11], s[13]));
+  const bool prim_ok = m_total == 0 || pri_res < ea + er * (un ? std::max(s[RSC_Z_U], s[RSC_AX_U]) : std::max(s[RSC_Z_S], s[RSC_AX_S]));
+  const double nrm = un ? std::max(s[RSC_Q_U], std::max(s[RSC_ATY_U], s[RSC_PX_U])) / c : std::max(s[RSC_Q_S], std::max(s[RSC_ATY_S], s[RSC_PX_S]));
   const bool dual_ok = dua_res < ea + er * nrm;
-  if (prim_ok && dual_ok) return 1;
-  // s[15] |E dy|  s[16] row violation  s[17] u'dy+ + l'dy-  s[18] |Dinv A'dy|  s[19] |D dx|  s[20] q'dx  s[21] |Dinv P dx|
+  if (prim_ok && dual_ok) return RP_RESIDUALS_PASS;
   const double ep = k * eps4[2], ed = k * eps4[3], cs = un ? c : 1.0;
-  if (!prim_ok && ep > 0.0 && s[15] > 1e-30 && s[17] < ep * s[15] && s[18] < ep * s[15]) return 3;
-  if (!dual_ok && ed > 0.0 && s[19] > 1e-30 && s[20] < cs * ed * s[19] && s[21] < cs * ed * s[19] && !(s[16] > ed * s[19])) return 4;
-  return 0;
+  if (!prim_ok && ep > 0.0 && s[RSC_NDY] > RP_DIV_TOL && s[RSC_LHS] < ep * s[RSC_NDY] && s[RSC_NATDY] < ep * s[RSC_NDY]) return RP_PRIMAL_INF;
+  if (!dual_ok && ed > 0.0 && s[RSC_NDX] > RP_DIV_TOL && s[RSC_QDX] < cs * ed * s[RSC_NDX] && s[RSC_NPDX] < cs * ed * s[RSC_NDX] && !(s[RSC_VIOL] > ed * s[RSC_NDX])) return RP_DUAL_INF;
+  return RP_GO_ON;
 }
 static int rp_verdict(const osqp_amd_rp *rp, double pri_res, double dua_res, bool approximate) {
   const double eps4[4] = {rp->st.eps_abs, rp->st.eps_rel, rp->eps_pinf, rp->eps_dinf};
-  return rp_verdict_of(rp->sc, rp->scaled && !rp->st.scaled_termination, rp->c, rp->m_total, eps4, pri_res, dua_res, approximate);
+  return rp_verdict_of(rp->sc, rp_unscaled(rp), rp->c, rp->m_total, eps4, pri_res, dua_res, approximate);
+}
+// the status a verdict ends the solve with: at a check within the budget, or in the approximate branch once the budget is spent
+static int rp_status_of(int verdict, bool approximate) {
+  switch (verdict) {
+    case RP_RESIDUALS_PASS: return approximate ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED;
+    case RP_PRIMAL_INF:     return approximate ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE;
+    case RP_DUAL_INF:       return approximate ? OSQP_DUAL_INFEASIBLE_INACCURATE : OSQP_DUAL_INFEASIBLE;
+    default:                return OSQP_MAX_ITER_REACHED;
+  }
 }
 // for the tests: the verdict on given scalars, host arithmetic only (no handle, no device)
 extern "C" int osqp_amd_rp_test_verdict(const double *sc22, int unscaled, double c, int m_total, const double *eps4, double pri_res, double dua_res, int approximate) {
@@ -450,9 +474,15 @@ extern "C" int osqp_amd_rp_test_verdict(const double *sc22, int unscaled, double
 }
 static double rp_rho_estimate(const osqp_amd_rp *rp) {
   const double *s = rp->sc;
-  const double pri = (rp->m_total ? s[3] : 0.0) / (std::max(s[4], s[5]) + 1e-30);
-  const double dua = s[7] / (std::max(s[9], std::max(s[11], s[13])) + 1e-30);
-  return std::min(std::max(rp->rho * std::sqrt(pri / dua), 1e-6), 1e6);
+  const double pri = (rp->m_total ? s[RSC_PRI_S] : 0.0) / (std::max(s[RSC_Z_S], s[RSC_AX_S]) + RP_DIV_TOL);
+  const double dua = s[RSC_DUA_S] / (std::max(s[RSC_Q_S], std::max(s[RSC_ATY_S], s[RSC_PX_S])) + RP_DIV_TOL);
+  return std::min(std::max(rp->rho * std::sqrt(pri / dua), RHO_MIN), RHO_MAX);
+}
+// cold_start (src/auxil.c:536-560 ends in it): the iterates x, x~, z, y back to zero; rho and rho_updates stay
+static int rp_cold_start(osqp_amd_rp *rp) {
+  for (double *v : {rp->x, rp->xt}) HIPCHK(hipMemsetAsync(v, 0, (size_t)rp->n * sizeof(double), rp->e->stream));
+  if (rp->m > 0) for (double *v : {rp->z, rp->y}) HIPCHK(hipMemsetAsync(v, 0, (size_t)rp->m * sizeof(double), rp->e->stream));
+  return 0;
 }
 
 extern "C" int osqp_amd_rp_solve(osqp_amd_rp *rp, osqp_amd_rp_info *info) {
@@ -475,7 +505,7 @@ extern "C" int osqp_amd_rp_solve(osqp_amd_rp *rp, osqp_amd_rp_info *info) {
     rp->rho_set = true;
   }
   const bool cert = rp->eps_pinf > 0.0 || rp->eps_dinf > 0.0;
-  int status = 0, it = 0;
+  int verdict = RP_GO_ON, it = 0;
   bool checked = false;
   double pri_res = 0.0, dua_res = 0.0;
   for (it = 1; it <= st.max_iter; it++) {
@@ -524,8 +554,7 @@ extern "C" int osqp_amd_rp_solve(osqp_amd_rp *rp, osqp_amd_rp_info *info) {
     HIPCHK(hipGetLastError());
     if (checked) {
       if (int rc = rp_check(rp, &pri_res, &dua_res, cert)) return rc;
-      if (cert) { if ((status = rp_verdict(rp, pri_res, dua_res, false))) break; }
-      else if (rp_terminated(rp, pri_res, dua_res, false)) { status = 1; break; }
+      if ((verdict = rp_verdict(rp, pri_res, dua_res, false)) != RP_GO_ON) break;
     }
     if (st.adaptive_rho && it % interval == 0) {
       if (!checked) if (int rc = rp_check(rp, &pri_res, &dua_res, false)) return rc;
@@ -539,34 +568,26 @@ extern "C" int osqp_amd_rp_solve(osqp_amd_rp *rp, osqp_amd_rp_info *info) {
   if (it > st.max_iter) it = st.max_iter;
   if (!checked) {
     if (int rc = rp_check(rp, &pri_res, &dua_res, cert)) return rc;
-    if (cert) status = rp_verdict(rp, pri_res, dua_res, false);
-    else if (rp_terminated(rp, pri_res, dua_res, false)) status = 1;
+    verdict = rp_verdict(rp, pri_res, dua_res, false);
   }
-  if (status >= 3) status = -status;        // OSQP_PRIMAL_INFEASIBLE = -3, OSQP_DUAL_INFEASIBLE = -4
-  else if (!status && cert) {              // the approximate branch: 10 x every tolerance on the same scalars
-    const int v = rp_verdict(rp, pri_res, dua_res, true);
-    status = v == 1 ? 2 : (v ? v : -2);     // OSQP_PRIMAL_INFEASIBLE_INACCURATE = 3, OSQP_DUAL_INFEASIBLE_INACCURATE = 4
-  } else if (!status) status = rp_terminated(rp, pri_res, dua_res, true) ? 2 : -2;
+  // nothing within the budget: the approximate branch, 10 x every tolerance on the same scalars
+  const int status = verdict != RP_GO_ON ? rp_status_of(verdict, false) : rp_status_of(rp_verdict(rp, pri_res, dua_res, true), true);
   info->status = status; info->iter = it; info->rho_updates = rp->rho_updates; info->pcg_iters = rp->pcg_iters;
-  info->obj_val = rp->sc[14] / rp->c; info->pri_res = pri_res; info->dua_res = dua_res; info->rho_estimate = rp_rho_estimate(rp);
+  info->obj_val = rp->sc[RSC_OBJ] / rp->c; info->pri_res = pri_res; info->dua_res = dua_res; info->rho_estimate = rp_rho_estimate(rp);
   rp->last_status = status;
-  if (status == 3 || status == -3 || status == 4 || status == -4) {
+  if (rp_infeasible(status)) {
     // store_solution (src/auxil.c:536-560): no solution, the certificate normalised in place, the iterates back to zero
-    const bool un = rp->scaled && !st.scaled_termination, prim = status == 3 || status == -3;
-    info->obj_val = prim ? 1e30 : -1e30;                                           // +-OSQP_INFTY
-    if (prim) { if (m > 0) hipLaunchKernelGGL(k_rp_cert_out, g, tb, 0, e->stream, m, un ? (const double *)rp->E : nullptr, 1.0 / rp->sc[15], rp->dxy + n); }
-    else hipLaunchKernelGGL(k_rp_cert_out, g, tb, 0, e->stream, n, un ? (const double *)rp->D : nullptr, 1.0 / rp->sc[19], rp->dxy);
+    const bool un = rp_unscaled(rp), prim = rp_primal(status);
+    info->obj_val = prim ? OSQP_INFTY : -OSQP_INFTY;
+    if (prim) { if (m > 0) hipLaunchKernelGGL(k_rp_cert_out, g, tb, 0, e->stream, m, un ? (const double *)rp->E : nullptr, 1.0 / rp->sc[RSC_NDY], rp->dxy + n); }
+    else hipLaunchKernelGGL(k_rp_cert_out, g, tb, 0, e->stream, n, un ? (const double *)rp->D : nullptr, 1.0 / rp->sc[RSC_NDX], rp->dxy);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(rp->x, 0, (size_t)n * sizeof(double), e->stream));
-    HIPCHK(hipMemsetAsync(rp->xt, 0, (size_t)n * sizeof(double), e->stream));
-    if (m > 0) { HIPCHK(hipMemsetAsync(rp->z, 0, (size_t)m * sizeof(double), e->stream)); HIPCHK(hipMemsetAsync(rp->y, 0, (size_t)m * sizeof(double), e->stream)); }
+    if (int rc = rp_cold_start(rp)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
   }
   info->collectives = rp->collectives;
   return 0;
 }
-
-static inline bool rp_infeasible(int status) { return status == 3 || status == -3 || status == 4 || status == -4; }
 
 extern "C" int osqp_amd_rp_set_infeasibility(osqp_amd_rp *rp, double eps_prim_inf, double eps_dual_inf) {
   if (!rp || !(eps_prim_inf >= 0.0) || !(eps_dual_inf >= 0.0)) return HIPENG_ERR_ARG;
@@ -576,7 +597,7 @@ extern "C" int osqp_amd_rp_set_infeasibility(osqp_amd_rp *rp, double eps_prim_in
 extern "C" int osqp_amd_rp_get_certificates(osqp_amd_rp *rp, double *dual_inf_cert, double *prim_inf_cert_loc) {
   if (!rp || !dual_inf_cert || (rp->m > 0 && !prim_inf_cert_loc)) return HIPENG_ERR_ARG;
   hipeng *e = rp->e;
-  const bool prim = rp->last_status == 3 || rp->last_status == -3, dual = rp->last_status == 4 || rp->last_status == -4;
+  const bool prim = rp_primal(rp->last_status), dual = rp_dual(rp->last_status);
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
   if (dual) HIPCHK(hipMemcpy(dual_inf_cert, rp->dxy, (size_t)rp->n * sizeof(double), hipMemcpyDeviceToHost));
@@ -681,29 +702,19 @@ extern "C" int osqp_amd_rp_peek(osqp_amd_rp *rp, int which, double *out, long lo
   hipeng *e = rp->e;
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
-  const double *nsrc[] = {rp->x, rp->xt, nullptr, nullptr, nullptr, rp->minv, rp->b, rp->r};
-  const double *msrc[] = {nullptr, nullptr, rp->z, rp->y, rp->rv, nullptr, nullptr, nullptr};
-  if (which == OSQP_AMD_RP_PEEK_S) {
-    if (cap < 9) return HIPENG_ERR_ARG;
+  const int n = rp->n, m = rp->m;
+  const struct { const double *src; long long count; } tab[] = {          // by OSQP_AMD_RP_PEEK_*
+      {rp->x, n}, {rp->xt, n}, {rp->z, m}, {rp->y, m}, {rp->rv, m}, {rp->minv, n}, {rp->b, n}, {rp->r, n}, {rp->sc15, RSC_CHECK}, {nullptr, 9},
+      {rp->dxy, n}, {rp->dxy + n, m}, {rp->sc15 + RSC_NDY, RSC_CERT}, {rp->q, n}, {rp->l, m}, {rp->u, m}};
+  static_assert(sizeof(tab) / sizeof(tab[0]) == OSQP_AMD_RP_PEEK_U + 1, "one entry per selector");
+  if (which < 0 || which > OSQP_AMD_RP_PEEK_U || cap < tab[which].count) return HIPENG_ERR_ARG;
+  const long long count = tab[which].count;
+  if (which == OSQP_AMD_RP_PEEK_S) {                  // a struct, not doubles: converted here
     RpS s;
     HIPCHK(hipMemcpy(&s, rp->S, sizeof(RpS), hipMemcpyDeviceToHost));
     const double v[9] = {s.rz[0], s.rz[1], s.rr, s.tol2, s.bb, (double)s.done, (double)s.iters, (double)s.cap, (double)s.bad};
     memcpy(out, v, sizeof(v));
-    return 9;
-  }
-  const double *src = nullptr;
-  long long count = 0;
-  if (which == OSQP_AMD_RP_PEEK_SC15) { src = rp->sc15; count = 15; }
-  else if (which == OSQP_AMD_RP_PEEK_DX) { src = rp->dxy; count = rp->n; }
-  else if (which == OSQP_AMD_RP_PEEK_DY) { src = rp->dxy + rp->n; count = rp->m; }
-  else if (which == OSQP_AMD_RP_PEEK_SC7) { src = rp->sc15 + 15; count = 7; }
-  else if (which == OSQP_AMD_RP_PEEK_Q) { src = rp->q; count = rp->n; }
-  else if (which == OSQP_AMD_RP_PEEK_L) { src = rp->l; count = rp->m; }
-  else if (which == OSQP_AMD_RP_PEEK_U) { src = rp->u; count = rp->m; }
-  else if (which >= 0 && which < 8) { src = nsrc[which] ? nsrc[which] : msrc[which]; count = nsrc[which] ? rp->n : rp->m; }
-  else return HIPENG_ERR_ARG;
-  if (cap < count) return HIPENG_ERR_ARG;
-  if (count > 0) HIPCHK(hipMemcpy(out, src, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+  } else if (count > 0) HIPCHK(hipMemcpy(out, tab[which].src, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
   return (int)count;
 }
 

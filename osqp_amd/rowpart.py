@@ -28,9 +28,12 @@ against ~26 us for a whole single-GPU PCG iteration at config 5 -- the partition
 apply is well above that, i.e. for P blocks / A shards of several hundred MB per GPU.
 """
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 from scipy import sparse
+
+from . import _abi
 
 RHO_MIN, RHO_MAX, RHO_TOL, RHO_EQ = 1e-6, 1e6, 1e-4, 1e3
 OSQP_INFTY = 1e30
@@ -58,33 +61,57 @@ def _row_class(l, u):
     return np.where((l < -INF_BOUND) & (u > INF_BOUND), -1, np.where(u - l < RHO_TOL, 1, 0))
 
 
-def _rows_of(v, m, r0, r1, name):
+def _full(v, count, name):
     v = np.ascontiguousarray(v, dtype=np.float64)
-    if v.shape != (m,):
-        raise ValueError("%s must have %d entries" % (name, m))
-    return np.ascontiguousarray(v[r0:r1])
+    if v.shape != (count,):
+        raise ValueError("%s must have %d entries" % (name, count))
+    return v
+
+
+def _rows_of(v, m, r0, r1, name):
+    return np.ascontiguousarray(_full(v, m, name)[r0:r1])
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+
+
+def _engine_on(device, **setup_kw):
+    """A single-GPU solver set up on `device`; the device option is as before afterwards."""
+    import osqp_amd
+    old = osqp_amd.engine_options()["device"]
+    osqp_amd.set_engine_options(device=device)
+    try:
+        return osqp_amd.OSQP().setup(**setup_kw)
+    finally:
+        osqp_amd.set_engine_options(device=old)
+
+
+def _shard_engine(Pu_g, A_g, device):
+    """The rank's shard (P_g, A_g) resident in an ordinary engine: scaling = 0 on already scaled data (a shard with no rows still
+    needs one for its part of P).  Returns the solver, its library with the signatures bound, and the engine."""
+    n, m = Pu_g.shape[0], A_g.shape[0]
+    solver = _engine_on(device, P=Pu_g, q=np.zeros(n), A=A_g, l=-np.ones(m), u=np.ones(m), scaling=0, sigma=1.0)
+    return solver, bind_live(solver._lib), solver.engine()
+
+
+def _ranges(indptr, world):
+    """Contiguous ranges of the rows (columns) behind a CSR (CSC) indptr with about equal numbers of non-zeros."""
+    cuts = [0] + [int(np.searchsorted(indptr, indptr[-1] * g / world)) for g in range(1, world)] + [len(indptr) - 1]
+    return [(cuts[g], max(cuts[g], cuts[g + 1])) for g in range(world)]
 
 
 def shard_rows(A, world):
     """Contiguous row ranges of A with about equal numbers of non-zeros."""
-    Ar = sparse.csr_matrix(A)
-    nnz = Ar.indptr
-    cuts = [0]
-    for g in range(1, world):
-        cuts.append(int(np.searchsorted(nnz, nnz[-1] * g / world)))
-    cuts.append(Ar.shape[0])
-    return [(cuts[g], max(cuts[g], cuts[g + 1])) for g in range(world)]
+    return _ranges(sparse.csr_matrix(A).indptr, world)
 
 
 def shard_triu(Pu, world):
     """Split the stored upper triangle of P by contiguous column ranges: P = sum_g sym(P_g)."""
     Pc = sparse.csc_matrix(Pu)
     n = Pc.shape[0]
-    nnz = Pc.indptr
-    cuts = [0] + [int(np.searchsorted(nnz, nnz[-1] * g / world)) for g in range(1, world)] + [n]
     out = []
-    for g in range(world):
-        j0, j1 = cuts[g], max(cuts[g], cuts[g + 1])
+    for j0, j1 in _ranges(Pc.indptr, world):
         part = sparse.csc_matrix(Pc[:, j0:j1])
         M = sparse.hstack([sparse.csc_matrix((n, j0)), part, sparse.csc_matrix((n, n - j1))], format="csc")
         out.append(sparse.triu(M, format="csc"))
@@ -124,26 +151,12 @@ class HipOps:
 
     def __init__(self, Pu_g, A_g, device=0):
         import torch
-        import osqp_amd
         self.torch = torch
         self.device = torch.device("cuda", device)
-        n, m = Pu_g.shape[0], A_g.shape[0]
-        self.n, self.m = n, m
+        self.n, self.m = Pu_g.shape[0], A_g.shape[0]
         self._A = sparse.csr_matrix(A_g)
         self._P = Pu_g
-        # a shard with no rows still needs an engine for its part of P
-        old = osqp_amd.engine_options()["device"]
-        osqp_amd.set_engine_options(device=device)
-        try:
-            self.solver = osqp_amd.OSQP().setup(P=Pu_g, q=np.zeros(n), A=A_g, l=-np.ones(m), u=np.ones(m), scaling=0, sigma=1.0)
-        finally:
-            osqp_amd.set_engine_options(device=old)
-        L = self.solver._lib
-        L.hipeng_spmv_dev.restype = C.c_int
-        L.hipeng_spmv_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.hipeng_sync.restype = C.c_int
-        L.hipeng_sync.argtypes = [C.c_void_p]
-        self._L, self._e = L, self.solver.engine()
+        self.solver, self._L, self._e = _shard_engine(Pu_g, A_g, device)
 
     def vec(self, a):
         return self.torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64))).to(self.device)
@@ -198,28 +211,75 @@ def scaled_problem_from_handle(s):
 def scaled_problem_from_engine(P, q, A, l, u, scaling=10, device=0):
     """scale_data as the single-GPU engine performs it (hipeng_ruiz_scale), so that the row-partitioned variant
     iterates in exactly the scaled space of the single-GPU path."""
-    import osqp_amd
-    old = osqp_amd.engine_options()["device"]
-    osqp_amd.set_engine_options(device=device)
-    try:
-        s = osqp_amd.OSQP().setup(P=P, q=q, A=A, l=l, u=u, scaling=scaling)
-    finally:
-        osqp_amd.set_engine_options(device=old)
+    s = _engine_on(device, P=P, q=q, A=A, l=l, u=u, scaling=scaling)
     out = scaled_problem_from_handle(s)
     s.cleanup()
     return out
 
 
-class RowPartitionedOSQP:
+class _RowPartitioned:
+    """What the torch-driven and the C-driven solver share: the rank's place in the group, its shard, the checks of full-length
+    arguments, the gather of an m-vector and the shape of a result.  `self.dev`: where the rank's tensors live (set by setup)."""
+
+    def __init__(self, group=None, world=None):
+        # world=1: no process group and no torch at all (a plain C caller's situation; tools/rccl_world1_probe.py)
+        self.torch = self.dist = None
+        self.group, self.world, self.rank = group, 1, 0
+        if world != 1:
+            import torch
+            import torch.distributed as dist
+            self.torch, self.dist = torch, dist
+            if dist.is_initialized():
+                self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
+
+    def _shard(self, scaled):
+        """Sets n, m, rows and the rank's [r0, r1); returns the rank's (P_g, A_g)."""
+        self.n, self.m = scaled["P"].shape[0], scaled["A"].shape[0]
+        self.rows = shard_rows(scaled["A"], self.world)
+        self.r0, self.r1 = self.rows[self.rank]
+        return shard_triu(scaled["P"], self.world)[self.rank], sparse.csr_matrix(scaled["A"])[self.r0:self.r1]
+
+    def _rows(self, v, name):
+        return _rows_of(v, self.m, self.r0, self.r1, name)
+
+    def _update_args(self, q, l, u):
+        """The arguments of update(): q of full length, the rank's rows of l and u (None: not given)."""
+        if (l is None) != (u is None):
+            raise ValueError("l and u are updated together in the row-partitioned variant")
+        q = None if q is None else _full(q, self.n, "q")
+        return (q, None, None) if l is None else (q, self._rows(l, "l"), self._rows(u, "u"))
+
+    def _gather_rows(self, yl):
+        """An m-vector from the row shards (once per solve, off the data path): the rank's rows as a numpy array or a tensor in,
+        the full numpy vector out; gathered device to device with nccl, on the host otherwise."""
+        if self.world == 1:
+            return yl if isinstance(yl, np.ndarray) else yl.cpu().numpy()
+        t, d = self.torch, self.dist
+        yl = t.from_numpy(yl) if isinstance(yl, np.ndarray) else yl
+        per = max(b - a for a, b in self.rows)
+        pad = t.zeros(per, dtype=t.float64, device=self.dev if d.get_backend(self.group) == "nccl" else "cpu")
+        pad[:yl.numel()] = yl
+        out = t.empty(self.world * per, dtype=t.float64, device=pad.device)
+        d.all_gather_into_tensor(out, pad, group=self.group)
+        out = out.cpu().numpy()
+        return np.concatenate([out[g * per:g * per + (b - a)] for g, (a, b) in enumerate(self.rows)])
+
+    @staticmethod
+    def _result(x, y, prim_inf_cert, dual_inf_cert, **info):
+        return SimpleNamespace(x=x, y=y, info=SimpleNamespace(**info), prim_inf_cert=prim_inf_cert, dual_inf_cert=dual_inf_cert)
+
+
+class RowPartitionedOSQP(_RowPartitioned):
     """osqp_setup / osqp_solve for ONE QP whose matrices are sharded over the ranks of a torch.distributed group."""
 
     def __init__(self, group=None):
-        import torch
-        import torch.distributed as dist
-        self.torch, self.dist, self.group = torch, dist, group
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        super().__init__(group)
         self.collectives = 0
+
+    @property
+    def _unscaled(self):
+        """The unscaled forms of residuals, norms and certificates decide (scaled data without scaled_termination)."""
+        return self.scaled_data and not self.st["scaled_termination"]
 
     # ---- collectives (device to device with nccl; staged through the host for a gloo rehearsal) ----
     def _allreduce(self, t, op="sum"):
@@ -237,17 +297,11 @@ class RowPartitionedOSQP:
     def setup(self, scaled, ops_factory, device=0, **settings):
         """`scaled`: dict(P (triu), q, A, l, u, D, E, c) -- the scaled problem, identical on every rank;
         `ops_factory(Pu_g, A_g, device)` builds the rank's SpMV back end (HipOps on a GPU)."""
-        st = _settings(settings)
-        self.st = st
-        n, m = scaled["P"].shape[0], scaled["A"].shape[0]
-        self.n, self.m = n, m
-        self.rows = shard_rows(scaled["A"], self.world)
-        r0, r1 = self.rows[self.rank]
-        self.r0, self.r1 = r0, r1
-        Pg = shard_triu(scaled["P"], self.world)[self.rank]
-        Ag = sparse.csr_matrix(scaled["A"])[r0:r1]
-        self.ops = ops_factory(Pg, Ag, device)
-        o = self.ops
+        st = self.st = _settings(settings)
+        Pg, Ag = self._shard(scaled)
+        n, r0, r1 = self.n, self.r0, self.r1
+        o = self.ops = ops_factory(Pg, Ag, device)
+        self.dev = o.device
         self.q = o.vec(scaled["q"]); self.l = o.vec(scaled["l"][r0:r1]); self.u = o.vec(scaled["u"][r0:r1])
         self.D = o.vec(scaled["D"]); self.Dinv = 1.0 / self.D
         self.E = o.vec(scaled["E"][r0:r1]); self.Einv = 1.0 / self.E
@@ -255,8 +309,7 @@ class RowPartitionedOSQP:
         self.scaled_data = bool(np.any(scaled["D"] != 1.0) or np.any(scaled["E"] != 1.0) or scaled["c"] != 1.0)
         self.cls = _row_class(scaled["l"][r0:r1], scaled["u"][r0:r1])
         self.has_eq = bool(self._allreduce(o.vec([float((self.cls == 1).any())]), "max").item() > 0)
-        pd, a2 = o.diag_terms()
-        self._pdiag, self._a2 = pd, a2                   # this rank's share of diag(P) and of A.^2 (column sums weighted by rho)
+        self._pdiag, self._a2 = o.diag_terms()           # this rank's share of diag(P) and of A.^2 (column sums weighted by rho)
         t = self.torch
         self.x = t.zeros(n, dtype=t.float64, device=o.device); self.xt = self.x.clone()
         self.z = t.zeros(r1 - r0, dtype=t.float64, device=o.device); self.y = self.z.clone()
@@ -271,15 +324,9 @@ class RowPartitionedOSQP:
         nothing changed on any, when l > u on some row; a row that changes class on some rank rebuilds rho per row and the
         preconditioner on every rank."""
         o = self.ops
-        if (l is None) != (u is None):
-            raise ValueError("l and u are updated together in the row-partitioned variant")
-        if q is not None:
-            q = np.ascontiguousarray(q, dtype=np.float64)
-            if q.shape != (self.n,):
-                raise ValueError("q must have %d entries" % self.n)
+        q, lo, hi = self._update_args(q, l, u)
         if l is not None:
-            lo = np.maximum(_rows_of(l, self.m, self.r0, self.r1, "l"), -OSQP_INFTY)
-            hi = np.minimum(_rows_of(u, self.m, self.r0, self.r1, "u"), OSQP_INFTY)
+            lo, hi = np.maximum(lo, -OSQP_INFTY), np.minimum(hi, OSQP_INFTY)
             E = self.E.cpu().numpy()
             ls, us = E * lo, E * hi
             cls = _row_class(ls, us)
@@ -301,15 +348,12 @@ class RowPartitionedOSQP:
         """osqp_warm_start (src/osqp.c:942-1010): x_s = Dinv x, z = A x_s on the rank's rows, y_s = c Einv y; x~ starts from x_s."""
         o = self.ops
         if x is not None:
-            x = np.ascontiguousarray(x, dtype=np.float64)
-            if x.shape != (self.n,):
-                raise ValueError("x must have %d entries" % self.n)
-            self.x = self.Dinv * o.vec(x)
+            self.x = self.Dinv * o.vec(_full(x, self.n, "x"))
             self.xt = self.x.clone()
             if self.r1 > self.r0:
                 self.z = o.A_mul(self.x)
         if y is not None:
-            self.y = (self.Einv * o.vec(_rows_of(y, self.m, self.r0, self.r1, "y"))) * self.c
+            self.y = (self.Einv * o.vec(self._rows(y, "y"))) * self.c
         return 0
 
     def update_rho(self, rho):
@@ -342,7 +386,7 @@ class RowPartitionedOSQP:
         cap = self.st["pcg_max_iter"] or max(20000, 10 * n)
         x = x0.clone()
         r = b - self._K(x)
-        tol2 = max(eps_rel * eps_rel * float(b @ b), 1e-30)
+        tol2 = max(eps_rel * eps_rel * float(b @ b), DIV_TOL)
         z = self.minv * r
         p = z.clone()
         rz = float(r @ z)
@@ -365,12 +409,8 @@ class RowPartitionedOSQP:
         t, o = self.torch, self.ops
         Ax = o.A_mul(self.x) if self.r1 > self.r0 else self.z
         pri = Ax - self.z
-        loc = t.stack([(self.Einv * pri).abs().max() if pri.numel() else t.zeros((), dtype=t.float64, device=o.device),
-                       (self.Einv * self.z).abs().max() if pri.numel() else t.zeros((), dtype=t.float64, device=o.device),
-                       (self.Einv * Ax).abs().max() if pri.numel() else t.zeros((), dtype=t.float64, device=o.device),
-                       pri.abs().max() if pri.numel() else t.zeros((), dtype=t.float64, device=o.device),
-                       self.z.abs().max() if pri.numel() else t.zeros((), dtype=t.float64, device=o.device),
-                       Ax.abs().max() if pri.numel() else t.zeros((), dtype=t.float64, device=o.device)])
+        mx = lambda v: v.abs().max() if v.numel() else t.zeros((), dtype=t.float64, device=o.device)       # (a rank without rows)
+        loc = t.stack([mx(self.Einv * pri), mx(self.Einv * self.z), mx(self.Einv * Ax), mx(pri), mx(self.z), mx(Ax)])
         pri_u, z_u, Ax_u, pri_s, z_s, Ax_s = (float(v) for v in self._allreduce(loc, "max"))
         both = t.cat([o.P_mul(self.x), o.At_mul(self.y) if self.r1 > self.r0 else t.zeros_like(self.x)])
         both = self._allreduce(both)
@@ -381,16 +421,14 @@ class RowPartitionedOSQP:
                  dua_u=f(dua, self.Dinv), dua_s=f(dua), q_u=f(self.q, self.Dinv), q_s=f(self.q), Aty_u=f(Aty, self.Dinv), Aty_s=f(Aty),
                  Px_u=f(Px, self.Dinv), Px_s=f(Px), obj=float(self.x @ (0.5 * Px + self.q)) * self.cinv)
         self.sc = s
-        un = self.scaled_data and not self.st["scaled_termination"]
+        un = self._unscaled
         self.pri_res = 0.0 if self.m == 0 else (s["pri_u"] if un else s["pri_s"])
         self.dua_res = self.cinv * s["dua_u"] if un else s["dua_s"]
-        return un
 
     def _cert_scalars(self):
         """The seven scalars of is_primal_infeasible / is_dual_infeasible (src/auxil.c:361-512) from dx, dy: one all-reduce (sum) of
         [P_g dx ; A_g' dy ; u'dy+ + l'dy-] and one (max) of [|E dy| ; row violation], everything computed every time."""
-        t, o, n = self.torch, self.ops, self.n
-        un = self.scaled_data and not self.st["scaled_termination"]
+        t, o, n, un = self.torch, self.ops, self.n, self._unscaled
         have = self.r1 > self.r0
         zero = t.zeros((), dtype=t.float64, device=o.device)
         dx = self.x - self.x_prev
@@ -416,9 +454,9 @@ class RowPartitionedOSQP:
 
     def _verdict(self, approximate=False):
         """check_termination with the infeasibility tests (src/auxil.c:716-783): None, "solved", "primal infeasible" or "dual infeasible";
-        only all-reduced and replicated values are looked at, so every rank decides alike."""
-        un = self.scaled_data and not self.st["scaled_termination"]
-        s, st, c = self.sc, self.st, self.cs
+        only all-reduced and replicated values are looked at, so every rank decides alike.  A test whose tolerance is 0 is off before its
+        scalars are looked up: with both off there is no self.cs, and this is the residual test alone."""
+        un, s, st = self._unscaled, self.sc, self.st
         k = 10.0 if approximate else 1.0
         eps_abs, eps_rel = k * st["eps_abs"], k * st["eps_rel"]
         prim_ok = self.m == 0 or self.pri_res < eps_abs + eps_rel * (max(s["z_u"], s["Ax_u"]) if un else max(s["z_s"], s["Ax_s"]))
@@ -427,22 +465,15 @@ class RowPartitionedOSQP:
         if prim_ok and dual_ok:
             return "solved"
         ep, ed, cost = k * st["eps_prim_inf"], k * st["eps_dual_inf"], (self.c if un else 1.0)
-        if not prim_ok and ep > 0 and c["ndy"] > DIV_TOL and c["lhs"] < ep * c["ndy"] and c["nAtdy"] < ep * c["ndy"]:
-            return "primal infeasible"
-        if (not dual_ok and ed > 0 and c["ndx"] > DIV_TOL and c["qdx"] < cost * ed * c["ndx"] and c["nPdx"] < cost * ed * c["ndx"]
-                and not c["viol"] > ed * c["ndx"]):
-            return "dual infeasible"
+        if not prim_ok and ep > 0:
+            c = self.cs
+            if c["ndy"] > DIV_TOL and c["lhs"] < ep * c["ndy"] and c["nAtdy"] < ep * c["ndy"]:
+                return "primal infeasible"
+        if not dual_ok and ed > 0:
+            c = self.cs
+            if c["ndx"] > DIV_TOL and c["qdx"] < cost * ed * c["ndx"] and c["nPdx"] < cost * ed * c["ndx"] and not c["viol"] > ed * c["ndx"]:
+                return "dual infeasible"
         return None
-
-    def _terminated(self, approximate=False):
-        un = self.scaled_data and not self.st["scaled_termination"]
-        s, st = self.sc, self.st
-        k = 10.0 if approximate else 1.0
-        eps_abs, eps_rel = k * st["eps_abs"], k * st["eps_rel"]
-        prim_ok = self.m == 0 or self.pri_res < eps_abs + eps_rel * (max(s["z_u"], s["Ax_u"]) if un else max(s["z_s"], s["Ax_s"]))
-        nrm = self.cinv * max(s["q_u"], s["Aty_u"], s["Px_u"]) if un else max(s["q_s"], s["Aty_s"], s["Px_s"])
-        dual_ok = self.dua_res < eps_abs + eps_rel * nrm
-        return prim_ok and dual_ok
 
     def _rho_estimate(self):
         s = self.sc
@@ -452,7 +483,6 @@ class RowPartitionedOSQP:
 
     # ---- solve ---------------------------------------------------------------------------------------
     def solve(self):
-        from types import SimpleNamespace
         st, o, t = self.st, self.ops, self.torch
         e = min(st["eps_abs"] or st["eps_rel"], st["eps_rel"] or st["eps_abs"])
         eps_pcg = max(1e-13, min(st["pcg_eps_rel"], 1e-5 * e))      # the rule of osqp_solve (osqp_host.c)
@@ -463,11 +493,10 @@ class RowPartitionedOSQP:
         alpha, sigma = st["alpha"], st["sigma"]
         cert = st["eps_prim_inf"] > 0 or st["eps_dual_inf"] > 0
 
-        def check():             # one termination check; with the infeasibility tests on, the verdict of check_termination
+        def check():             # one termination check: the verdict of check_termination, on seven more scalars with a test on
             self._info()
-            if not cert:
-                return "solved" if self._terminated() else None
-            self._cert_scalars()
+            if cert:
+                self._cert_scalars()
             return self._verdict()
         status, it, checked = "unsolved", 0, False
         for it in range(1, st["max_iter"] + 1):
@@ -497,19 +526,16 @@ class RowPartitionedOSQP:
                     self.rho_updates += 1
         if not checked:
             status = check() or "unsolved"
-        if status == "unsolved":
-            if cert:             # the approximate branch: 10 x every tolerance on the same scalars
-                v = self._verdict(approximate=True)
-                status = v + " inaccurate" if v else "maximum iterations reached"
-            else:
-                status = "solved inaccurate" if self._terminated(approximate=True) else "maximum iterations reached"
+        if status == "unsolved":     # the approximate branch: 10 x every tolerance on the same scalars
+            v = self._verdict(approximate=True)
+            status = v + " inaccurate" if v else "maximum iterations reached"
         self.status = status
         obj, rho_estimate = self.sc["obj"], self._rho_estimate()
         nan_x, nan_m = np.full(self.n, np.nan), np.full(self.m, np.nan)
         prim_inf_cert, dual_inf_cert = nan_m, nan_x
         if status in INFEASIBLE:
             # store_solution (src/auxil.c:536-560): no solution, the certificate normalised, the iterates back to zero (rho stays)
-            un = self.scaled_data and not st["scaled_termination"]
+            un = self._unscaled
             x, y = nan_x, nan_m
             if status.startswith("primal"):
                 obj = OSQP_INFTY
@@ -523,23 +549,8 @@ class RowPartitionedOSQP:
             # unscale; y is gathered from the row shards
             x = (self.D * self.x).cpu().numpy()
             y = self._gather_rows(self.E * self.y * self.cinv)
-        info = SimpleNamespace(status=status, iter=it, obj_val=obj, pri_res=self.pri_res, dua_res=self.dua_res,
-                               rho_updates=self.rho_updates, rho_estimate=rho_estimate, pcg_iters=self.pcg_iters,
-                               collectives=self.collectives)
-        return SimpleNamespace(x=x, y=y, info=info, prim_inf_cert=prim_inf_cert, dual_inf_cert=dual_inf_cert)
-
-    def _gather_rows(self, yl):
-        t = self.torch
-        if self.world == 1:
-            return yl.cpu().numpy()
-        per = max(r1 - r0 for r0, r1 in self.rows)
-        pad = t.zeros(per, dtype=t.float64, device=yl.device); pad[:yl.numel()] = yl
-        if pad.is_cuda and self.dist.get_backend(self.group) != "nccl":
-            pad = pad.cpu()
-        out = t.empty(self.world * per, dtype=t.float64, device=pad.device)
-        self.dist.all_gather_into_tensor(out, pad, group=self.group)
-        out = out.cpu().numpy()
-        return np.concatenate([out[g * per:g * per + (r1 - r0)] for g, (r0, r1) in enumerate(self.rows)])
+        return self._result(x, y, prim_inf_cert, dual_inf_cert, status=status, iter=it, obj_val=obj, pri_res=self.pri_res, dua_res=self.dua_res,
+                            rho_updates=self.rho_updates, rho_estimate=rho_estimate, pcg_iters=self.pcg_iters, collectives=self.collectives)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -558,8 +569,38 @@ class _RpInfo(C.Structure):
 
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p)
-_STATUS = {1: "solved", 2: "solved inaccurate", -2: "maximum iterations reached", -3: "primal infeasible", 3: "primal infeasible inaccurate",
-           -4: "dual infeasible", 4: "dual infeasible inaccurate"}
+_PRIMAL = (_abi.OSQP_PRIMAL_INFEASIBLE, _abi.OSQP_PRIMAL_INFEASIBLE_INACCURATE)
+_DUAL = (_abi.OSQP_DUAL_INFEASIBLE, _abi.OSQP_DUAL_INFEASIBLE_INACCURATE)
+_STATUS = {v: _abi.STATUS[v] for v in (_abi.OSQP_SOLVED, _abi.OSQP_SOLVED_INACCURATE, _abi.OSQP_MAX_ITER_REACHED) + _PRIMAL + _DUAL}
+
+# every entry point this module calls (include/osqp_amd_engine.h, include/osqp_amd_rowpart.h): result type, argument types
+_H = _P = C.c_void_p
+_SIGNATURES = {
+    "hipeng_spmv_dev": (C.c_int, [_H, C.c_int, _P, _P]),
+    "hipeng_sync": (C.c_int, [_H]),
+    "osqp_amd_rp_create": (_H, [_H, _P, _P, _P, _P, _P, C.c_double, C.c_int, C.c_int, C.POINTER(_RpSettings), C.c_int, C.c_int, _ALLREDUCE_FN, _P]),
+    "osqp_amd_rp_solve": (C.c_int, [_H, C.POINTER(_RpInfo)]),
+    "osqp_amd_rp_get_solution": (C.c_int, [_H, _P, _P]),
+    "osqp_amd_rp_free": (None, [_H]),
+    "osqp_amd_rp_rccl_unique_id": (C.c_int, [_P, C.c_int]),
+    "osqp_amd_rp_use_rccl": (C.c_int, [_H, _P, C.c_int]),
+    "osqp_amd_rp_peek": (C.c_int, [_H, C.c_int, _P, C.c_longlong]),
+    "osqp_amd_rp_test_verdict": (C.c_int, [_P, C.c_int, C.c_double, C.c_int, _P, C.c_double, C.c_double, C.c_int]),
+    "osqp_amd_rp_set_infeasibility": (C.c_int, [_H, C.c_double, C.c_double]),
+    "osqp_amd_rp_get_certificates": (C.c_int, [_H, _P, _P]),
+    "osqp_amd_rp_update_lin_cost": (C.c_int, [_H, _P]),
+    "osqp_amd_rp_update_bounds": (C.c_int, [_H, _P, _P]),
+    "osqp_amd_rp_warm_start": (C.c_int, [_H, _P, _P]),
+    "osqp_amd_rp_update_rho": (C.c_int, [_H, C.c_double]),
+}
+
+
+def bind_live(L):
+    """Declares the signatures of _SIGNATURES on the library L and returns it."""
+    for name, (res, args) in _SIGNATURES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = res, args
+    return L
 
 
 class _DevView:
@@ -567,49 +608,19 @@ class _DevView:
         self.__cuda_array_interface__ = dict(shape=(int(count),), typestr="<f8", data=(int(ptr), False), version=2, strides=None)
 
 
-def bind_live(L):
-    """Signatures of the infeasibility and live-handle entry points (include/osqp_amd_rowpart.h)."""
-    H, P, d = C.c_void_p, C.c_void_p, C.c_double
-    for name, args in (("osqp_amd_rp_set_infeasibility", [H, d, d]), ("osqp_amd_rp_get_certificates", [H, P, P]),
-                       ("osqp_amd_rp_update_lin_cost", [H, P]), ("osqp_amd_rp_update_bounds", [H, P, P]),
-                       ("osqp_amd_rp_warm_start", [H, P, P]), ("osqp_amd_rp_update_rho", [H, d])):
-        f = getattr(L, name)
-        f.restype, f.argtypes = C.c_int, args
-    return L
-
-
-class NativeRowPartitionedOSQP:
+class NativeRowPartitionedOSQP(_RowPartitioned):
     """osqp_setup / osqp_solve of ONE row-partitioned QP through the C entry points osqp_amd_rp_*.
     collective = "rccl": ncclAllReduce of librccl on the engine's stream (the production path, one GPU per rank);
                  "group": the torch.distributed group as a callback (any backend; gloo stages through the host);
                  "auto": rccl when the group's backend is nccl, else group."""
 
     def __init__(self, group=None, collective="auto", world=None):
-        # world=1: no process group and no torch at all (a plain C caller's situation; tools/rccl_world1_probe.py)
-        self.torch = self.dist = None
-        self.group, self.world, self.rank = group, 1, 0
-        if world != 1:
-            import torch
-            import torch.distributed as dist
-            self.torch, self.dist = torch, dist
-            self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-            self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-            if collective == "auto":
-                collective = "rccl" if (dist.is_initialized() and dist.get_backend(group) == "nccl") else "group"
-        self.collective = "group" if collective == "auto" else collective
+        super().__init__(group, world)
+        d = self.dist
+        if collective == "auto":
+            collective = "rccl" if (d is not None and d.is_initialized() and d.get_backend(group) == "nccl") else "group"
+        self.collective = collective
         self._rp = None
-
-    def _bind(self, L):
-        L.osqp_amd_rp_create.restype = C.c_void_p
-        L.osqp_amd_rp_create.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_double, C.c_int, C.c_int, C.POINTER(_RpSettings), C.c_int, C.c_int, _ALLREDUCE_FN, C.c_void_p]
-        L.osqp_amd_rp_solve.restype = C.c_int; L.osqp_amd_rp_solve.argtypes = [C.c_void_p, C.POINTER(_RpInfo)]
-        L.osqp_amd_rp_get_solution.restype = C.c_int; L.osqp_amd_rp_get_solution.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.osqp_amd_rp_free.restype = None; L.osqp_amd_rp_free.argtypes = [C.c_void_p]
-        L.osqp_amd_rp_rccl_unique_id.restype = C.c_int; L.osqp_amd_rp_rccl_unique_id.argtypes = [C.c_void_p, C.c_int]
-        L.osqp_amd_rp_use_rccl.restype = C.c_int; L.osqp_amd_rp_use_rccl.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.osqp_amd_rp_peek.restype = C.c_int; L.osqp_amd_rp_peek.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
-        bind_live(L)
-        L.hipeng_sync.restype = C.c_int; L.hipeng_sync.argtypes = [C.c_void_p]
 
     def _group_allreduce(self, user, buf, count, op, stream):
         # the callback form of the collective: everything queued on the engine's stream first, then the group's all-reduce on
@@ -635,25 +646,13 @@ class NativeRowPartitionedOSQP:
         t, d = self.torch, self.dist
         st = _settings(settings)
         eps_inf = (float(st.pop("eps_prim_inf")), float(st.pop("eps_dual_inf")))
-        n, m = scaled["P"].shape[0], scaled["A"].shape[0]
-        self.n, self.m = n, m
-        self.rows = shard_rows(scaled["A"], self.world)
-        r0, r1 = self.rows[self.rank]
-        self.r0, self.r1 = r0, r1
-        # the rank's shard (P_g, A_g) in an ordinary engine: scaling = 0 on already scaled data
-        import osqp_amd
-        Pg, Ag = shard_triu(scaled["P"], self.world)[self.rank], sparse.csr_matrix(scaled["A"])[r0:r1]
-        old = osqp_amd.engine_options()["device"]
-        osqp_amd.set_engine_options(device=device)
-        try:
-            self.shard = osqp_amd.OSQP().setup(P=Pg, q=np.zeros(n), A=Ag, l=-np.ones(r1 - r0), u=np.ones(r1 - r0), scaling=0, sigma=1.0)
-        finally:
-            osqp_amd.set_engine_options(device=old)
+        Pg, Ag = self._shard(scaled)
+        r0, r1 = self.r0, self.r1
+        self.shard, self._L, self._e = _shard_engine(Pg, Ag, device)
+        L = self._L
         self.dev = t.device("cuda", device) if t is not None else None
-        L = self.shard._lib
-        self._bind(L)
-        self._L, self._e = L, self.shard.engine()
-        lg, ug = np.ascontiguousarray(scaled["l"][r0:r1], dtype=np.float64), np.ascontiguousarray(scaled["u"][r0:r1], dtype=np.float64)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        lg, ug = f64(scaled["l"][r0:r1]), f64(scaled["u"][r0:r1])
         has_eq = float(np.any(ug - lg < RHO_TOL))
         if self.world > 1:
             flag = t.tensor([has_eq], dtype=t.float64, device=self.dev if d.get_backend(self.group) == "nccl" else "cpu")
@@ -662,10 +661,8 @@ class NativeRowPartitionedOSQP:
         kinds = dict(_RpSettings._fields_)
         s = _RpSettings(**{k: (float(v) if kinds[k] is C.c_double else int(v)) for k, v in st.items()})
         self._cb = _ALLREDUCE_FN(self._group_allreduce)              # kept alive with the object
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
         q, D, E = f64(scaled["q"]), f64(scaled["D"]), f64(scaled["E"][r0:r1])
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
-        self._rp = L.osqp_amd_rp_create(self._e, ptr(q), ptr(lg), ptr(ug), ptr(D), ptr(E), float(scaled["c"]), int(m), int(has_eq > 0),
+        self._rp = L.osqp_amd_rp_create(self._e, _ptr(q), _ptr(lg), _ptr(ug), _ptr(D), _ptr(E), float(scaled["c"]), int(self.m), int(has_eq > 0),
                                         C.byref(s), self.world, self.rank, self._cb, None)
         if not self._rp:
             raise RuntimeError("osqp_amd_rp_create failed")
@@ -674,10 +671,7 @@ class NativeRowPartitionedOSQP:
         if self.collective == "rccl" and self.world > 1:
             idb = t.zeros(128, dtype=t.uint8)
             if self.rank == 0:
-                raw = (C.c_char * 128)()
-                if L.osqp_amd_rp_rccl_unique_id(raw, 128) != 128:
-                    raise RuntimeError("osqp_amd_rp_rccl_unique_id failed")
-                idb = t.frombuffer(bytearray(raw.raw), dtype=t.uint8).clone()
+                idb = t.frombuffer(bytearray(self._rccl_id()), dtype=t.uint8).clone()
             on = self.dev if d.get_backend(self.group) == "nccl" else "cpu"
             idb = idb.to(on)
             d.broadcast(idb, src=0, group=self.group)
@@ -691,12 +685,15 @@ class NativeRowPartitionedOSQP:
                 self.collective = "group"
         return self
 
-    def use_rccl_world1(self):
-        """Test hook: the built-in RCCL provider on a one-rank communicator (dlopen, ncclCommInitRank, the stream-ordered call)."""
+    def _rccl_id(self):
         raw = (C.c_char * 128)()
         if self._L.osqp_amd_rp_rccl_unique_id(raw, 128) != 128:
             raise RuntimeError("osqp_amd_rp_rccl_unique_id failed")
-        return self._L.osqp_amd_rp_use_rccl(self._rp, raw.raw, 128)
+        return raw.raw
+
+    def use_rccl_world1(self):
+        """Test hook: the built-in RCCL provider on a one-rank communicator (dlopen, ncclCommInitRank, the stream-ordered call)."""
+        return self._L.osqp_amd_rp_use_rccl(self._rp, self._rccl_id(), 128)
 
     def set_infeasibility(self, eps_prim_inf, eps_dual_inf):
         """Switch the infeasibility tests on (0: that test off); every rank with the same values."""
@@ -704,76 +701,49 @@ class NativeRowPartitionedOSQP:
             raise ValueError("eps_prim_inf and eps_dual_inf must not be negative")
 
     # ---- a live handle: unscaled arrays of full length in, the rank's rows taken here (every rank calls each of these) ----
-    def _checked(self, rc, what):
+    def _call(self, name, *args):
+        rc = getattr(self._L, name)(self._rp, *args)
         if rc not in (0, 1):
-            raise RuntimeError("%s failed (%d)" % (what, rc))
+            raise RuntimeError("%s failed (%d)" % (name, rc))
         return int(rc)
 
     def update(self, q=None, l=None, u=None):
         """New q and / or new bounds (l and u together).  Returns 1 on every rank, with the bounds unchanged on all of them, when l > u
         on some row."""
-        if (l is None) != (u is None):
-            raise ValueError("l and u are updated together in the row-partitioned variant")
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        q, lo, hi = self._update_args(q, l, u)
+        # the bounds first: refused bounds leave q as it was, too
+        if l is not None and self._call("osqp_amd_rp_update_bounds", _ptr(lo), _ptr(hi)):
+            return 1
         if q is not None:
-            q = np.ascontiguousarray(q, dtype=np.float64)
-            if q.shape != (self.n,):
-                raise ValueError("q must have %d entries" % self.n)
-        if l is not None:                                # the bounds first: refused bounds leave q as it was, too
-            lo, hi = _rows_of(l, self.m, self.r0, self.r1, "l"), _rows_of(u, self.m, self.r0, self.r1, "u")
-            if self._checked(self._L.osqp_amd_rp_update_bounds(self._rp, ptr(lo), ptr(hi)), "osqp_amd_rp_update_bounds"):
-                return 1
-        if q is not None:
-            self._checked(self._L.osqp_amd_rp_update_lin_cost(self._rp, ptr(q)), "osqp_amd_rp_update_lin_cost")
+            self._call("osqp_amd_rp_update_lin_cost", _ptr(q))
         return 0
 
     def warm_start(self, x=None, y=None):
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
-        if x is not None:
-            x = np.ascontiguousarray(x, dtype=np.float64)
-            if x.shape != (self.n,):
-                raise ValueError("x must have %d entries" % self.n)
-        yl = _rows_of(y, self.m, self.r0, self.r1, "y") if y is not None else None
-        return self._checked(self._L.osqp_amd_rp_warm_start(self._rp, ptr(x) if x is not None else None, ptr(yl) if yl is not None else None),
-                             "osqp_amd_rp_warm_start")
+        x = None if x is None else _full(x, self.n, "x")
+        yl = None if y is None else self._rows(y, "y")
+        return self._call("osqp_amd_rp_warm_start", _ptr(x), _ptr(yl))
 
     def update_rho(self, rho):
-        return self._checked(self._L.osqp_amd_rp_update_rho(self._rp, float(rho)), "osqp_amd_rp_update_rho")
-
-    def _gather_rows(self, yl):
-        """An m-vector from the row shards (once per solve, off the data path)."""
-        t, d = self.torch, self.dist
-        if self.world == 1:
-            return yl
-        per = max(b - a for a, b in self.rows)
-        pad = t.zeros(per, dtype=t.float64); pad[:yl.size] = t.from_numpy(yl)
-        if d.get_backend(self.group) == "nccl":
-            pad = pad.to(self.dev)
-        out = t.empty(self.world * per, dtype=t.float64, device=pad.device)
-        d.all_gather_into_tensor(out, pad, group=self.group)
-        out = out.cpu().numpy()
-        return np.concatenate([out[g * per:g * per + (b - a)] for g, (a, b) in enumerate(self.rows)])
+        return self._call("osqp_amd_rp_update_rho", float(rho))
 
     def solve(self):
-        from types import SimpleNamespace
-        info = _RpInfo()
+        info, k = _RpInfo(), self.r1 - self.r0
         rc = self._L.osqp_amd_rp_solve(self._rp, C.byref(info))
         if rc:
             raise RuntimeError("osqp_amd_rp_solve failed (%d)" % rc)
-        x = np.zeros(self.n); yl = np.zeros(max(self.r1 - self.r0, 1))
-        if self._L.osqp_amd_rp_get_solution(self._rp, x.ctypes.data_as(C.c_void_p), yl.ctypes.data_as(C.c_void_p)):
+        x, yl = np.zeros(self.n), np.zeros(max(k, 1))
+        if self._L.osqp_amd_rp_get_solution(self._rp, _ptr(x), _ptr(yl)):
             raise RuntimeError("osqp_amd_rp_get_solution failed")
-        y = self._gather_rows(yl[:self.r1 - self.r0])
+        y = self._gather_rows(yl[:k])
         dual_inf_cert, prim_inf_cert = np.full(self.n, np.nan), np.full(self.m, np.nan)
-        if info.status in (3, -3, 4, -4):
-            pl = np.full(max(self.r1 - self.r0, 1), np.nan)
-            if self._L.osqp_amd_rp_get_certificates(self._rp, dual_inf_cert.ctypes.data_as(C.c_void_p), pl.ctypes.data_as(C.c_void_p)):
+        if info.status in _PRIMAL + _DUAL:
+            pl = np.full(max(k, 1), np.nan)
+            if self._L.osqp_amd_rp_get_certificates(self._rp, _ptr(dual_inf_cert), _ptr(pl)):
                 raise RuntimeError("osqp_amd_rp_get_certificates failed")
-            if info.status in (3, -3):                   # (the status is the same on every rank: all of them gather, or none)
-                prim_inf_cert = self._gather_rows(pl[:self.r1 - self.r0])
-        ns = SimpleNamespace(status=_STATUS.get(info.status, "unsolved"), iter=info.iter, obj_val=info.obj_val, pri_res=info.pri_res, dua_res=info.dua_res,
-                             rho_updates=info.rho_updates, rho_estimate=info.rho_estimate, pcg_iters=info.pcg_iters, collectives=info.collectives)
-        return SimpleNamespace(x=x, y=y, info=ns, prim_inf_cert=prim_inf_cert, dual_inf_cert=dual_inf_cert)
+            if info.status in _PRIMAL:                   # (the status is the same on every rank: all of them gather, or none)
+                prim_inf_cert = self._gather_rows(pl[:k])
+        return self._result(x, y, prim_inf_cert, dual_inf_cert, status=_STATUS.get(info.status, "unsolved"),
+                            **{f: getattr(info, f) for f, _ in _RpInfo._fields_ if f != "status"})
 
     _PEEK = ("x", "xt", "z", "y", "rv", "minv", "b", "r", "sc15", "S", "dx", "dy", "sc7", "q", "l", "u")
     _S_FIELDS = ("rz0", "rz1", "rr", "tol2", "bb", "done", "iters", "cap", "bad")
@@ -784,7 +754,7 @@ class NativeRowPartitionedOSQP:
         which = self._PEEK.index(name)
         cap = {"sc15": 15, "S": 9, "sc7": 7}.get(name, max(self.n, self.r1 - self.r0, 1))
         out = np.zeros(cap)
-        k = self._L.osqp_amd_rp_peek(self._rp, which, out.ctypes.data_as(C.c_void_p), cap)
+        k = self._L.osqp_amd_rp_peek(self._rp, which, _ptr(out), cap)
         if k < 0:
             raise RuntimeError("osqp_amd_rp_peek failed (%d)" % k)
         return dict(zip(self._S_FIELDS, out[:k])) if name == "S" else out[:k].copy()

@@ -88,6 +88,42 @@ def test_c_verdict_is_strict_on_the_thresholds(lib):
     assert f(None, 0, 1.0, 1, None, 0.0, 0.0, 0) == HIPENG_ERR_ARG
 
 
+def test_verdict_with_both_tests_off_is_the_residual_test_alone(lib):
+    """With eps4 = (ea, er, 0, 0) osqp_amd_rp_test_verdict returns 1 or 0 exactly as the residual test dictates and consults none of the
+    seven certificate scalars (NaN here); the torch class's _verdict agrees on an object that has no `cs` at all.  This is what lets one
+    verdict serve a solve with the infeasibility tests off."""
+    from osqp_amd import rowpart
+    f = lib.osqp_amd_rp_test_verdict
+    f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int]
+    order = ("pri_u", "z_u", "Ax_u", "pri_s", "z_s", "Ax_s", "dua_u", "dua_s", "q_u", "q_s", "Aty_u", "Aty_s", "Px_u", "Px_s", "obj")
+    ea, er = 1e-3, 1e-2
+
+    def both(pri_res, dua_res, approximate=0, un=0, c=1.0, m_total=5, **norms):
+        s15 = dict(dict.fromkeys(order, 0.0), **norms)
+        sc = np.full(22, np.nan); sc[:15] = [s15[k] for k in order]
+        e4 = np.array([ea, er, 0.0, 0.0])
+        got = f(sc.ctypes.data_as(C.c_void_p), un, c, m_total, e4.ctypes.data_as(C.c_void_p), pri_res, dua_res, approximate)
+        s = rowpart.RowPartitionedOSQP.__new__(rowpart.RowPartitionedOSQP)
+        s.scaled_data, s.m, s.c, s.cinv = bool(un), m_total, c, 1.0 / c
+        s.st = dict(rowpart._DEFAULTS, eps_abs=ea, eps_rel=er)
+        s.sc, s.pri_res, s.dua_res = s15, pri_res, dua_res
+        assert not hasattr(s, "cs") and s._verdict(approximate=bool(approximate)) == {0: None, 1: "solved"}[got]
+        return got
+    below = lambda v: np.nextafter(v, 0.0)
+    assert both(0.0, 0.0) == 1 and both(below(ea), below(ea)) == 1                                    # pass
+    assert both(ea, 0.0) == 0 and both(0.0, ea) == 0                                                 # exactly on eps_abs: no pass
+    pt, dt = ea + er * 3.0, ea + er * 7.0                                                            # with the relative terms (scaled forms)
+    nrm = dict(z_s=2.0, Ax_s=3.0, q_s=5.0, Aty_s=7.0, Px_s=6.0, z_u=90.0, Ax_u=90.0, q_u=90.0, Aty_u=90.0, Px_u=90.0)
+    assert both(below(pt), below(dt), **nrm) == 1 and both(pt, below(dt), **nrm) == 0 and both(below(pt), dt, **nrm) == 0
+    assert both(1e9, 0.0, m_total=0) == 1 and both(1e9, ea, m_total=0) == 0                          # no rows: no primal test
+    assert both(ea, ea) == 0 and both(ea, ea, approximate=1) == 1                                    # approximate: 10 x each
+    assert both(below(10.0 * ea), below(10.0 * ea), approximate=1) == 1 and both(10.0 * ea, 0.0, approximate=1) == 0
+    # the unscaled forms with c = 2: the _u norms decide, the dual one divided by c
+    nu = dict(z_u=2.0, Ax_u=3.0, q_u=10.0, Aty_u=14.0, Px_u=12.0, z_s=90.0, Ax_s=90.0, q_s=90.0, Aty_s=90.0, Px_s=90.0)
+    assert both(below(pt), below(dt), un=1, c=2.0, **nu) == 1 and both(pt, 0.0, un=1, c=2.0, **nu) == 0
+    assert both(0.0, dt, un=1, c=2.0, **nu) == 0 and both(0.0, below(ea + er * 14.0), un=0, c=2.0, **dict(nu, q_s=0.0, Aty_s=14.0, Px_s=0.0, z_s=0.0, Ax_s=0.0)) == 1
+
+
 def test_python_classes_carry_the_settings_and_the_calls():
     from osqp_amd import rowpart
     for cls in (rowpart.RowPartitionedOSQP, rowpart.NativeRowPartitionedOSQP):
