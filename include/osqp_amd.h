@@ -134,6 +134,10 @@ c_int osqp_amd_tangent(OSQPWorkspace *work, c_int ndir,
                        c_int *active, c_int *status, c_float *kkt_res /*[ndir], NULL = skip*/);
 /* for the tests: out[0] KKT instances built since setup, [1] one is alive, [2] its active rows, [3] linear solves since setup */
 c_int osqp_amd_sens_info(OSQPWorkspace *work, c_int out[4]);
+/* for the tests: the KKT instance of the last polish, recorded before polish freed it.  out[0] polish instances run since setup,
+ * [1] the linear-solve form the last one took (hipeng_resident_info [9]; -1: none yet, or it could not be read), [2] its active
+ * rows, [3] its resident launches that gave up plus its negative-curvature stops (0: the form served every solve; -1 unread) */
+c_int osqp_amd_polish_info(OSQPWorkspace *work, c_int out[4]);
 /* The options above are the DEFAULTS a new workspace / plugin instance copies at creation; afterwards
  * each instance has its own (no knob is shared between live workspaces).  These two read / change the
  * copy of one workspace (the device cannot be changed after setup). */
@@ -147,6 +151,9 @@ c_int osqp_amd_read_problem(const char *path, OSQPData **data);
 void  osqp_amd_free_problem(OSQPData *data);
 /* Raw engine handle of a workspace (for the kernel-level tests / bench). */
 void *osqp_amd_engine(const OSQPWorkspace *work);
+/* ... and of the live KKT instance of the solution derivatives (NULL: none alive).  The instance chooses its linear-solve form
+ * from (P, Ared) on its own: hipeng_resident_info / hipeng_pcg_layout / hipeng_elim_count on this handle say which. */
+void *osqp_amd_sens_engine(const OSQPWorkspace *work);
 
 #ifdef __cplusplus
 }

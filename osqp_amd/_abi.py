@@ -188,4 +188,6 @@ def bind_api(lib, prefix=""):
         api["adjoint"] = fn("osqp_amd_adjoint", c_int, W, F, F, F, F, F, F, F, I, I, F)
         api["tangent"] = fn("osqp_amd_tangent", c_int, W, c_int, F, F, F, F, F, F, F, I, I, F)
         api["sens_info"] = fn("osqp_amd_sens_info", c_int, W, I)
+        api["polish_info"] = fn("osqp_amd_polish_info", c_int, W, I)
+        api["sens_engine"] = fn("osqp_amd_sens_engine", C.c_void_p, W)
     return api

@@ -124,6 +124,7 @@ typedef struct {
   osqp_amd_options opt;   /* this instance's engine options (copied from the defaults at creation) */
   sens_state *sens;       /* workspace view: solution derivatives (NULL until the first call) */
   c_int sens_ready;       /* an osqp_solve has completed and no data, rho or iterate was changed since */
+  c_int pol_info[4];      /* workspace view: run_polish's last instance, as osqp_amd_polish_info reports it */
 } hip_pcg_solver;
 
 #define PCG(work) ((hip_pcg_solver *)((work)->linsys_solver))
@@ -1114,12 +1115,17 @@ static csc *form_Ared(const OSQPWorkspace *w, const OSQPPolish *p) {
   Ar->i = (c_int *)c_calloc((size_t)Ar->nzmax, sizeof(c_int));
   Ar->x = (c_float *)c_calloc((size_t)Ar->nzmax, sizeof(c_float));
   cnt = 0;
+  /* a column's lows, then its upps: the reduced row indices ascend within the column whenever A's do (the resident PCG asks for
+   * sorted columns and refuses the instance otherwise; in A's own order an upp row ahead of a low row breaks it) */
   for (c_int j = 0; j < n; j++) {
     Ar->p[j] = cnt;
     for (c_int k = A->p[j]; k < A->p[j + 1]; k++) {
       c_int r = A->i[k];
-      if (p->A_to_Alow[r] != -1)      { Ar->i[cnt] = p->A_to_Alow[r];            Ar->x[cnt++] = A->x[k]; }
-      else if (p->A_to_Aupp[r] != -1) { Ar->i[cnt] = p->A_to_Aupp[r] + p->n_low; Ar->x[cnt++] = A->x[k]; }
+      if (p->A_to_Alow[r] != -1) { Ar->i[cnt] = p->A_to_Alow[r]; Ar->x[cnt++] = A->x[k]; }
+    }
+    for (c_int k = A->p[j]; k < A->p[j + 1]; k++) {
+      c_int r = A->i[k];
+      if (p->A_to_Alow[r] == -1 && p->A_to_Aupp[r] != -1) { Ar->i[cnt] = p->A_to_Aupp[r] + p->n_low; Ar->x[cnt++] = A->x[k]; }
     }
   }
   Ar->p[n] = cnt;
@@ -1247,6 +1253,16 @@ restore:   /* put the ADMM iterates back on the device */
   hipeng_set_z(s->eng, w->z);
 cleanup:
   w->info->polish_time = toc(w->timer);
+  {   /* what the instance was, for osqp_amd_polish_info: read before it goes */
+    long long ri[16];
+    hipeng_stats hs;
+    hipeng *pe = ((hip_pcg_solver *)ls)->eng;
+    const c_int known = !hipeng_resident_info(pe, ri) && !hipeng_get_stats(pe, &hs);
+    s->pol_info[0]++;
+    s->pol_info[1] = known ? (c_int)ri[9] : -1;
+    s->pol_info[2] = mred;
+    s->pol_info[3] = known ? (c_int)ri[10] + (c_int)hs.neg_curvature : -1;
+  }
   ls->free(ls);
   free_csc(Ar); p->Ared = NULL;
   c_free(rhs); c_free(sol); c_free(res); c_free(tmp);
@@ -1523,6 +1539,17 @@ c_int osqp_amd_sens_info(OSQPWorkspace *w, c_int out[4]) {
   return 0;
 }
 
+c_int osqp_amd_polish_info(OSQPWorkspace *w, c_int out[4]) {
+  NEED_WORK(w);
+  if (!w->linsys_solver || !out) return OSQP_DATA_VALIDATION_ERROR;
+  const hip_pcg_solver *s = PCG(w);
+  out[0] = s->pol_info[0];
+  out[1] = s->pol_info[0] ? s->pol_info[1] : -1;
+  out[2] = s->pol_info[2];
+  out[3] = s->pol_info[3];
+  return 0;
+}
+
 /* per-workspace engine options (device excluded: the engine lives where it was created) */
 c_int osqp_amd_get_workspace_options(const OSQPWorkspace *w, osqp_amd_options *o) {
   if (!w || !w->linsys_solver || !o) return 1;
@@ -1540,4 +1567,10 @@ c_int osqp_amd_set_workspace_options(OSQPWorkspace *w, const osqp_amd_options *o
 void *osqp_amd_engine(const OSQPWorkspace *w) {
   if (!w || !w->linsys_solver) return NULL;
   return PCG(w)->eng;
+}
+
+void *osqp_amd_sens_engine(const OSQPWorkspace *w) {
+  if (!w || !w->linsys_solver) return NULL;
+  const sens_state *ss = PCG(w)->sens;
+  return ss && ss->ls ? ((hip_pcg_solver *)ss->ls)->eng : NULL;
 }

@@ -302,6 +302,20 @@ class SolverHandle:
             self._sens_fail("osqp_amd_sens_info", rc)
         return dict(built=int(out[0]), alive=int(out[1]), active_rows=int(out[2]), solves=int(out[3]))
 
+    def polish_info(self):
+        """For the tests: polish instances run since setup, the linear-solve form the last one took (hipeng_resident_info [9];
+        -1: none yet), its active rows, and its give-ups plus negative-curvature stops (0: the form served every solve)."""
+        out = np.zeros(4, np.int64)
+        rc = self._sens("polish_info")(self._work, abi.iptr(out))
+        if rc:
+            self._sens_fail("osqp_amd_polish_info", rc)
+        return dict(runs=int(out[0]), form=int(out[1]), active_rows=int(out[2]), troubles=int(out[3]))
+
+    def sens_engine(self):
+        """Raw engine handle of the live KKT instance of adjoint() / tangent() (None: none alive), as OSQP.engine() is of
+        the handle's own engine."""
+        return self._sens("sens_engine")(self._work)
+
     # -------------------------------------------------------------- accessors
     @property
     def work(self):

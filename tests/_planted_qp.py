@@ -324,27 +324,37 @@ class Route:
         self._lu = self._Ml = None
         self._inv = {}
 
-    def solve_true(self, g):
-        """float64 LU, then refinement with the residual in long double until it stops falling; the best iterate."""
+    # the three pieces of solve_true that depend on how M is stored (tests/_kkt_instance_cases.py holds M sparse at n = 8192)
+    def _factor(self):
         if self._lu is None:
             self._lu = sla.lu_factor(self.M, check_finite=False)
             self._Ml = self.M.astype(LD)
+
+    def _lu_solve(self, v):
+        return sla.lu_solve(self._lu, v, check_finite=False)
+
+    def _residual(self, gl, x):
+        return gl - self._Ml @ x
+
+    def solve_true(self, g):
+        """float64 LU, then refinement with the residual in long double until it stops falling; the best iterate."""
+        self._factor()
         gl = np.asarray(g, LD)
-        x = sla.lu_solve(self._lu, np.asarray(g, float), check_finite=False).astype(LD)
+        x = self._lu_solve(np.asarray(g, float)).astype(LD)
         best, xbest = np.inf, x
         for _ in range(12):
-            r = gl - self._Ml @ x
+            r = self._residual(gl, x)
             nr = float(np.abs(r).max()) if r.size else 0.0
             if not nr < best:
                 break
             best, xbest = nr, x
             if nr == 0.0:
                 break
-            x = x + sla.lu_solve(self._lu, r.astype(float), check_finite=False).astype(LD)
+            x = x + self._lu_solve(r.astype(float)).astype(LD)
         return xbest.astype(float)
 
     def residual_ld(self, x, g):
-        """g - M x in long double (self.M must have been factored: call solve_true first, or this builds the copy)."""
+        """g - M x in long double."""
         if self._Ml is None:
             self._Ml = self.M.astype(LD)
         return np.asarray(g, LD) - self._Ml @ np.asarray(x, LD)
@@ -390,14 +400,17 @@ def adjoint_from(mem, x, y, gx, gy, solve):
 
 
 def tangent_from(mem, x, y, inc, solve):
-    """_tangent_reference.py's formulas over solve(g) = M^-1 g, for the NDIR directions inc.dQ[d], ...: dx, dy [NDIR, .]."""
+    """_tangent_reference.py's formulas over solve(g) = M^-1 g, for the NDIR directions inc.dQ[d], ...: dx, dy [NDIR, .].
+    A member that holds its matrices sparse (mem.sparse, tests/_kkt_instance_cases.py at n = 8192) keeps dP, dA sparse."""
     n, m = mem.n, mem.m
     dx = np.zeros((NDIR, n)); dy = np.zeros((NDIR, m))
     y_act = np.where(mem.act != 0, y, 0.0)
+    keep = getattr(mem, "sparse", False)
     for d in range(NDIR):
         dPu = sparse.csc_matrix((inc.dPx[d], mem.Pu.indices, mem.Pu.indptr), shape=(n, n))
-        dP = (dPu + sparse.triu(dPu, 1).T).toarray()
-        dA = sparse.csc_matrix((inc.dAx[d], mem.Ac.indices, mem.Ac.indptr), shape=(m, n)).toarray().reshape(m, n)
+        dP = dPu + sparse.triu(dPu, 1).T
+        dA = sparse.csc_matrix((inc.dAx[d], mem.Ac.indices, mem.Ac.indptr), shape=(m, n))
+        dP, dA = (dP.tocsr(), dA.tocsr()) if keep else (dP.toarray(), dA.toarray().reshape(m, n))
         db = np.concatenate([inc.dL[d][mem.low], inc.dU[d][mem.upp]])
         g = np.concatenate([-(inc.dQ[d] + dP @ x + dA.T @ y_act), db - (dA @ x)[mem.rows]])
         r = solve(g)

@@ -15,11 +15,16 @@ Scaling (P~ = c D P D, A~ = E A D, q~ = c D q, x = D x~, y = E y~ / c; D, E, c c
               (-c D_i^2 rx~_i x~_i on the diagonal);
     tangent   rhs = [-(c D dq + (c D dP D) x~ + (E dA D)' y~_act); E db_act - ((E dA D) x~)_act];  dx = D dx~,
               dy = E dnu~ / c on the active rows.
-`scaled_adjoint` / `scaled_tangent` evaluate exactly these formulas over any solve of M~ that is handed to them."""
+`scaled_adjoint` / `scaled_tangent` evaluate exactly these formulas over any solve of M~ that is handed to them.
+
+Sparse matrices (tests/_kkt_instance_cases.py at n = 8192): `scaled_problem(..., dense=False)` returns them, `route_solve` then
+takes the reduced solve from a sparse LU of [P~ + d I, Ar~'; Ar~, -d I] -- the same x and nu in exact arithmetic -- and
+`scaled_tangent(..., keep_sparse=True)` keeps dP~, dA~ sparse."""
 from types import SimpleNamespace
 
 import numpy as np
 from scipy import sparse
+from scipy.sparse import linalg as spla
 
 DELTA_MIN, MAX_REFINE = 1e-3, 15
 
@@ -28,13 +33,20 @@ def route_solve(Pf, Ar, g, delta=1e-6, refine_iter=3):
     """(s, kkt_res, steps): the model of one refined solve of M s = g, M = [Pf, Ar'; Ar, 0]."""
     n, k = Pf.shape[0], Ar.shape[0]
     d = max(delta, DELTA_MIN)
-    M = np.zeros((n + k, n + k))
-    M[:n, :n] = Pf; M[:n, n:] = Ar.T; M[n:, :n] = Ar
-    K = Pf + d * np.eye(n) + Ar.T @ Ar / d
+    if sparse.issparse(Pf):
+        Pf, Ar = sparse.csr_matrix(Pf), sparse.csr_matrix(Ar)
+        M = sparse.bmat([[Pf, Ar.T], [Ar, None]], format="csr") if k else Pf
+        lu = spla.splu(sparse.bmat([[Pf + d * sparse.eye(n), Ar.T], [Ar, -d * sparse.eye(k)]], format="csc") if k
+                       else sparse.csc_matrix(Pf + d * sparse.eye(n)))
+        reduced = lu.solve                       # [x; nu] with Ar x - d nu = b2: nu = (Ar x - b2) / d
+    else:
+        M = np.zeros((n + k, n + k))
+        M[:n, :n] = Pf; M[:n, n:] = Ar.T; M[n:, :n] = Ar
+        K = Pf + d * np.eye(n) + Ar.T @ Ar / d
 
-    def reduced(b):
-        x = np.linalg.solve(K, b[:n] + Ar.T @ b[n:] / d)
-        return np.concatenate([x, (Ar @ x - b[n:]) / d])
+        def reduced(b):
+            x = np.linalg.solve(K, b[:n] + Ar.T @ b[n:] / d)
+            return np.concatenate([x, (Ar @ x - b[n:]) / d])
     g = np.asarray(g, float)
     s = reduced(g)
     prev, kkt_res, steps = np.inf, 0.0, 0
@@ -51,13 +63,17 @@ def route_solve(Pf, Ar, g, delta=1e-6, refine_iter=3):
     return s, kkt_res, steps
 
 
-def scaled_problem(Pu, Ac, act, D, E, c):
-    """The scaled matrices and the active rows of a member: Pf~ (full, dense), Ad~ (dense), rows (lows first, then upps)."""
+def scaled_problem(Pu, Ac, act, D, E, c, dense=True):
+    """The scaled matrices and the active rows of a member: Pf~ (full, dense), Ad~ (dense), rows (lows first, then upps).
+    dense=False: both as CSR."""
     n, m = Pu.shape[0], Ac.shape[0]
+    rows = np.concatenate([np.flatnonzero(act < 0), np.flatnonzero(act > 0)]).astype(np.int64)
+    if not dense:
+        Pf = sparse.csr_matrix(Pu + sparse.triu(Pu, 1).T)
+        return sparse.csr_matrix(c * (sparse.diags(D) @ Pf @ sparse.diags(D))), sparse.csr_matrix(sparse.diags(E) @ Ac @ sparse.diags(D)), rows
     Pf = (Pu + sparse.triu(Pu, 1).T).toarray()
     Pfs = c * (D[:, None] * Pf * D[None, :])
     Ads = E[:, None] * Ac.toarray().reshape(m, n) * D[None, :]
-    rows = np.concatenate([np.flatnonzero(act < 0), np.flatnonzero(act > 0)]).astype(np.int64)
     return Pfs, Ads, rows
 
 
@@ -80,7 +96,7 @@ def scaled_adjoint(Pu, Ac, act, D, E, c, x, y, gx, gy, solve):
     return SimpleNamespace(dq=-(c * D) * rx, dl=np.where(act < 0, v, 0.0), du=np.where(act > 0, v, 0.0), dPx=dPx, dAx=dAx)
 
 
-def scaled_tangent(Pu, Ac, act, D, E, c, x, y, dQ, dL, dU, dPx, dAx, solve):
+def scaled_tangent(Pu, Ac, act, D, E, c, x, y, dQ, dL, dU, dPx, dAx, solve, keep_sparse=False):
     """The tangent as the C side computes it, for the directions dQ [ndir, n], ...: dx [ndir, n], dy [ndir, m]."""
     n, m = Pu.shape[0], Ac.shape[0]
     low, upp = np.flatnonzero(act < 0), np.flatnonzero(act > 0)
@@ -91,8 +107,13 @@ def scaled_tangent(Pu, Ac, act, D, E, c, x, y, dQ, dL, dU, dPx, dAx, solve):
     dx = np.zeros((ndir, n)); dy = np.zeros((ndir, m))
     for d in range(ndir):
         dPu = sparse.csc_matrix((dPx[d], Pu.indices, Pu.indptr), shape=(n, n))
-        dPs = c * (D[:, None] * (dPu + sparse.triu(dPu, 1).T).toarray() * D[None, :])
-        dAs = E[:, None] * sparse.csc_matrix((dAx[d], Ac.indices, Ac.indptr), shape=(m, n)).toarray().reshape(m, n) * D[None, :]
+        dAu = sparse.csc_matrix((dAx[d], Ac.indices, Ac.indptr), shape=(m, n))
+        if keep_sparse:
+            dPs = sparse.csr_matrix(c * (sparse.diags(D) @ (dPu + sparse.triu(dPu, 1).T) @ sparse.diags(D)))
+            dAs = sparse.csr_matrix(sparse.diags(E) @ dAu @ sparse.diags(D))
+        else:
+            dPs = c * (D[:, None] * (dPu + sparse.triu(dPu, 1).T).toarray() * D[None, :])
+            dAs = E[:, None] * dAu.toarray().reshape(m, n) * D[None, :]
         db = np.concatenate([(E * dL[d])[low], (E * dU[d])[upp]])
         g = np.concatenate([-(c * D * dQ[d] + dPs @ xs + dAs.T @ yact), db - (dAs @ xs)[rows]])
         s = solve(g)
