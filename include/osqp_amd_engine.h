@@ -108,6 +108,13 @@ int hipeng_set_z(hipeng *e, const c_float *z);
 /* Run `count` ADMM iterations (osqp.c:356-370: swap, update_xz_tilde,
  * update_x, update_z, update_y) entirely on the device. */
 int hipeng_run_admm(hipeng *e, c_int count);
+/* hipeng_run_admm followed by hipeng_residuals for a window that ends where the residuals are looked at: the residual pass
+ * is enqueued directly behind the window and both come back after one wait.  *have = 1: *out holds the scalars of the
+ * iterate the call ended on.  *have = 0 (the window needed a continuation, a resident launch gave up, a slow-wait record
+ * was cleared, or OSQP_AMD_FUSED_CHECK=0): *out is untouched and the caller asks hipeng_residuals. */
+int hipeng_run_admm_check(hipeng *e, c_int count, hipeng_scalars *out, int *have);
+/* the rule behind *have, on the fields of the window's read-back (no device needed) */
+int hipeng_early_scalars_usable(c_int remaining, int res_fail, int res_slow, int res_repub);
 /* Evaluate all residual scalars for the current iterates (device reductions,
  * one small D2H copy). */
 int hipeng_residuals(hipeng *e, hipeng_scalars *out);

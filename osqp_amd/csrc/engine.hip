@@ -469,8 +469,12 @@ __device__ __forceinline__ double dense_block_mv(const DenseP &dP, const DenseBl
 __global__ void __launch_bounds__(TB) k_vd(Ctx c) {
   for (int k = blockIdx.x * TB + threadIdx.x; k < c.n + c.m; k += gridDim.x * TB) c.vd[k] = c.vb[k] - c.vx[k];
 }
-template <bool DENSE>
-__global__ void __launch_bounds__(TB) k_pcg_init(Ctx c, int bench) {
+// RESFORM (the K == 0 graphs of a k_pcg_resident engine, launch_init): the only reader of r0 and u0 = Minv r0 is the resident launch,
+// which wants its own rows of both, and they sit side by side in the exchanged vector's layout.  This form stores r0 at
+// r0pos[u0map[j]] and u0 at u0pos[u0map[j]] -- whole lines per workgroup of the resident launch -- and leaves out init_r (one
+// double in every 32-byte record) and init_z.  Same arithmetic, same partials, same returns.
+template <bool DENSE, bool RESFORM>
+__global__ void __launch_bounds__(TB) k_pcg_init(Ctx c, int bench, double *r0pos) {
   State *st = c.st;
   TL_MARK(c, 1);
   TLK_DECL;
@@ -550,9 +554,12 @@ __global__ void __launch_bounds__(TB) k_pcg_init(Ctx c, int bench) {
       const double bj = base + sB;
       const double rj = c.plain_rhs ? bj : bj - prm.sigma * c.vx[j] - sA;
       const double zj = c.minv[j] * rj;
-      c.init_r[(size_t)j * c.init_stride] = rj;
-      c.init_z[j] = zj;
-      if (c.u0pos) c.u0pos[c.u0map[j]] = zj;
+      if constexpr (RESFORM) { const int p = (int)c.u0map[j]; r0pos[p] = rj; c.u0pos[p] = zj; }
+      else {
+        c.init_r[(size_t)j * c.init_stride] = rj;
+        c.init_z[j] = zj;
+        if (c.u0pos) c.u0pos[c.u0map[j]] = zj;
+      }
       prz += rj * zj; prr += rj * rj; pbb += bj * bj;
     }
     __syncthreads();
@@ -565,9 +572,12 @@ __global__ void __launch_bounds__(TB) k_pcg_init(Ctx c, int bench) {
     const double bj = gone ? 0.0 : base + sB;
     const double rj = gone ? 0.0 : bj - prm.sigma * r.vx - sA;
     const double zj = r.minv * rj;
-    c.init_r[(size_t)j * c.init_stride] = rj;
-    c.init_z[j] = zj;
-    if (c.u0pos) c.u0pos[r.u0] = zj;
+    if constexpr (RESFORM) { r0pos[r.u0] = rj; c.u0pos[r.u0] = zj; }
+    else {
+      c.init_r[(size_t)j * c.init_stride] = rj;
+      c.init_z[j] = zj;
+      if (c.u0pos) c.u0pos[r.u0] = zj;
+    }
     prz += rj * zj; prr += rj * rj; pbb += bj * bj;
   };
   auto row_start = [&](int j, double sA, double sB) { row_apply(j, sA, sB, row_load(j)); };
@@ -1320,6 +1330,8 @@ struct ResCtx {
   unsigned *flags;                   // nwg x RES_FSTRIDE words (one 128-byte line each)
   int *dbg;                          // nwg x RES_DBG, written by a launch that gives up: see res_note()
   double *sbuf;                      // 2 x nwg x RES_GSTRIDE 8-byte words: six granules {32 bits of a double, tag} per workgroup, one line each
+  double *r0pos;                     // npad doubles: r0 in the exchanged vector's layout, left by k_pcg_init<*, true> (null: r0 and u0 come from
+                                     // init_r / init_z, OSQP_AMD_INIT_RESIDENT_STORES=0)
   const int *kcp, *kcm, *kca;        // contribution lists of k_form_K_lists (null: k_form_K forms K): entry e of K (the order of kcj) sums the terms
                                      // kcp[e] .. kcp[e + 1], term q = rhoe[M.col[kcm[q]] - n] * (M.val[kcm[q]] * A.val[kca[q]]), rows of A ascending
 };
@@ -1603,8 +1615,12 @@ __global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) ppos[q] = rc.ppos[min(lane + 64 * q, nwg - 1)];
     // the own rows in the same flight (clamped: a lane past the workgroup's rows loads a valid element and drops it below)
-    const int jc = min(w.r0 + lane, c.n - 1);
-    own_r = c.init_r[(size_t)jc * c.init_stride]; own_u = c.init_z[jc]; own_x = c.vx[jc]; own_mi = c.minv[jc];
+    // (r0 and u0: from the exchanged vector's layout, where the own rows are w.pos .. w.pos + nr - 1, when k_pcg_init left them there;
+    // pointer and index are chosen from kernel arguments alone, so the loads stay in this flight either way)
+    const int jc = min(w.r0 + lane, c.n - 1), pc = min(w.pos + lane, npad - 1);
+    const bool rpos = rc.r0pos != nullptr;
+    const double *rsrc = rpos ? rc.r0pos : c.init_r, *usrc = rpos ? c.u0pos : c.init_z;
+    own_r = rsrc[rpos ? (size_t)pc : (size_t)jc * c.init_stride]; own_u = usrc[rpos ? pc : jc]; own_x = c.vx[jc]; own_mi = c.minv[jc];
     sr0 = rc.segrow[(size_t)g * (RES_MAXROWS + 1) + min(lane, RES_MAXROWS)]; sr1 = rc.segrow[(size_t)g * (RES_MAXROWS + 1) + min(lane + 1, RES_MAXROWS)];
     double rr0 = 0.0, bb = 0.0;
 #pragma unroll
@@ -2959,6 +2975,31 @@ __global__ void __launch_bounds__(TB) k_fill(double *p, double v, int cnt) {
   for (int i = blockIdx.x * TB + threadIdx.x; i < cnt; i += gridDim.x * TB) p[i] = v;
 }
 
+// Up to FILL_RANGES arrays set to zero in one launch (hipeng_cold_start: one launch instead of one memset per array).
+#define FILL_RANGES 6
+struct FillRanges { double *p[FILL_RANGES]; int cnt[FILL_RANGES]; };
+__global__ void __launch_bounds__(TB) k_fill_ranges(FillRanges f) {
+  for (int k = 0; k < FILL_RANGES; k++) {
+    double *p = f.p[k];
+    const int cnt = f.cnt[k];
+    for (int i = blockIdx.x * TB + threadIdx.x; i < cnt; i += gridDim.x * TB) p[i] = 0.0;
+  }
+}
+
+// reset_start in one launch: vx = vold = va over all n + m entries, and the history count back to zero.
+__global__ void __launch_bounds__(TB) k_start_reset(Ctx c, int cnt) {
+  for (int i = blockIdx.x * TB + threadIdx.x; i < cnt; i += gridDim.x * TB) {
+    const double v = c.va[i];
+    c.vx[i] = v; c.vold[i] = v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) c.st->hist_r = 0;
+}
+
+// What a window of hipeng_run_admm starts from: the target and the window's extremes of the PCG iteration count.
+__global__ void k_window_begin(State *st, long long target) {
+  if (threadIdx.x == 0) { st->admm_target = target; st->iters_max = 0; st->iters_min = 0x7f7f7f7f; }
+}
+
 // dst[k] = src_val[map[k]] (map < 0: structural zero inside a dense block)
 __global__ void __launch_bounds__(TB) k_repack(const double *src, const int *map, double *dst, long long cnt) {
   for (long long k = (long long)blockIdx.x * TB + threadIdx.x; k < cnt; k += (long long)gridDim.x * TB) {
@@ -3016,6 +3057,10 @@ struct hipeng {
   long long admm_total = 0;            // host copy of State::admm_done
   State *h_state = nullptr;            // pinned staging for the state read-back and the target upload
   long long *h_target = nullptr;
+  // OSQP_AMD_FUSED_CHECK (default 1): a window that ends in a check enqueues the residual pass behind its graphs and waits once
+  // (hipeng_run_admm_check); the window's prologue, hipeng_cold_start and reset_start are one launch each.  0: one operation per field / array.
+  bool fused_check = true;
+  double *h_check = nullptr;           // pinned: the scalars' lines followed by State, as they lie on the device (one D2H copy)
   int trace = 0;            // OSQP_AMD_TRACE: 1 = one line per window, 2 = every HIP call of the run loop
   hipeng_stats stats{};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -3684,6 +3729,11 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
     double *d_u0pos = nullptr;
     if (dev_alloc(e, &d_u0pos, (size_t)rc.npad)) return HIPENG_ERR_HIP;       // (zeroed: the padding positions are read, never written)
     e->c.u0map = d_rowpos; e->c.u0pos = d_u0pos;
+    // OSQP_AMD_INIT_RESIDENT_STORES (default 1): k_pcg_init of the resident graphs stores r0 beside u0 in this layout and nothing else
+    bool rform = true;
+    if (const char *x = getenv("OSQP_AMD_INIT_RESIDENT_STORES")) rform = atoi(x) != 0;
+    rc.r0pos = nullptr;
+    if (rform && dev_alloc(e, &rc.r0pos, (size_t)rc.npad)) return HIPENG_ERR_HIP;
   }
   rc.wg = d_wg; rc.ppos = d_ppos; rc.rowpos = d_rowpos; rc.col = d_col; rc.rowl = d_rowl; rc.krp = d_krp; rc.kcj = d_kcj; rc.kps = d_kps; rc.kdst = d_kdst; rc.brk = d_brk; rc.slot0 = d_slot0; rc.segrow = d_segrow;
   e->rc = rc;
@@ -3959,6 +4009,11 @@ static void refresh_operator(hipeng *e) {
 // The PCG start vector history is void (cold/warm start from the host, new rho, new matrices):
 // start from [x~ | rho z~] as it stands and extrapolate again once a few iterations are on record.
 static int reset_start(hipeng *e) {
+  if (e->c.vx != e->c.va && e->fused_check && e->n + e->m > 0) {      // (both copies and the count in one launch)
+    hipLaunchKernelGGL(k_start_reset, dim3(elem_grid(e->n + e->m)), dim3(TB), 0, e->stream, e->c, e->n + e->m);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   if (e->c.vx != e->c.va) {
     HIPCHK(hipMemcpyAsync(e->c.vx, e->c.va, (size_t)std::max(1, e->n + e->m) * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
     // ... and the "previous" vector with it: what vold held was formed with the rho and A from before the call, so a schedule that
@@ -4103,9 +4158,10 @@ extern "C" int hipeng_create(hipeng **out, const csc *P, const csc *A, const c_f
   const int np = std::max(std::max(c.gridM, c.gridA), 2048);   // also scratch for the scaling kernels
   DA(part_rz, np); DA(part_rr, np); DA(part_bb, np); DA(part_pkp, np);
   DA(part_s0, np); DA(part_s1, np); DA(part_s2, np); DA(part_gam, np); DA(part_del, np);
-  DA(scal, SC_COUNT * 16);
+  // the residual scalars' lines and State lie back to back, so that a check reads both with one copy (hipeng_run_admm_check)
+  DA(scal, SC_COUNT * 16 + (sizeof(State) + sizeof(double) - 1) / sizeof(double));
+  c.st = reinterpret_cast<State *>(c.scal + SC_COUNT * 16);
   DA(part_h, (size_t)std::max(1, c.A.nblk - c.A.nwave) * c.gridA);
-  DA(st, 1);
 #ifdef OSQP_AMD_TIMELINE
   DA(tl, TL_CAP);
 #endif
@@ -4114,6 +4170,8 @@ extern "C" int hipeng_create(hipeng **out, const csc *P, const csc *A, const c_f
     c.init_r = &c.g4[n].r; c.init_stride = 4; c.init_z = c.ut; c.fin_rr = c.part_rr; c.fin_cnt = c.gridM;
     HIPCHK(hipHostMalloc((void **)&e->h_state, sizeof(State), hipHostMallocDefault));
     HIPCHK(hipHostMalloc((void **)&e->h_target, sizeof(long long), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void **)&e->h_check, SC_COUNT * 16 * sizeof(double) + sizeof(State), hipHostMallocDefault));
+    if (const char *x = getenv("OSQP_AMD_FUSED_CHECK")) e->fused_check = atoi(x) != 0;
   }
   if (dev_alloc(e, &e->d_prm, 1)) return HIPENG_ERR_HIP;
   c.prm = e->d_prm;
@@ -4153,6 +4211,7 @@ extern "C" void hipeng_destroy(hipeng *e) {
   if (e->ev1) (void)hipEventDestroy(e->ev1);
   if (e->h_state) (void)hipHostFree(e->h_state);
   if (e->h_target) (void)hipHostFree(e->h_target);
+  if (e->h_check) (void)hipHostFree(e->h_check);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -4336,12 +4395,19 @@ extern "C" int hipeng_cold_start(hipeng *e) {
   if (!e) return HIPENG_ERR_ARG;
   HIPCHK(hipSetDevice(e->device));
   const size_t nm = (size_t)(e->n + e->m) * sizeof(double);
-  HIPCHK(hipMemsetAsync(e->c.xy, 0, std::max<size_t>(nm, 8), e->stream));
-  HIPCHK(hipMemsetAsync(e->c.va, 0, std::max<size_t>(nm, 8), e->stream));
-  HIPCHK(hipMemsetAsync(e->c.vb, 0, std::max<size_t>(nm, 8), e->stream));
-  HIPCHK(hipMemsetAsync(e->c.z, 0, std::max<size_t>(e->m, 1) * sizeof(double), e->stream));
-  HIPCHK(hipMemsetAsync(e->c.zt, 0, std::max<size_t>(e->m, 1) * sizeof(double), e->stream));
-  if (e->c.nelim) HIPCHK(hipMemsetAsync(e->c.xte, 0, (size_t)e->m * sizeof(double), e->stream));
+  if (e->fused_check) {
+    const int cnm = std::max(1, e->n + e->m), cm = std::max(1, e->m);
+    FillRanges f{{e->c.xy, e->c.va, e->c.vb, e->c.z, e->c.zt, e->c.nelim ? e->c.xte : nullptr}, {cnm, cnm, cnm, cm, cm, e->c.nelim ? e->m : 0}};
+    hipLaunchKernelGGL(k_fill_ranges, dim3(elem_grid(cnm)), dim3(TB), 0, e->stream, f);
+    HIPCHK(hipGetLastError());
+  } else {
+    HIPCHK(hipMemsetAsync(e->c.xy, 0, std::max<size_t>(nm, 8), e->stream));
+    HIPCHK(hipMemsetAsync(e->c.va, 0, std::max<size_t>(nm, 8), e->stream));
+    HIPCHK(hipMemsetAsync(e->c.vb, 0, std::max<size_t>(nm, 8), e->stream));
+    HIPCHK(hipMemsetAsync(e->c.z, 0, std::max<size_t>(e->m, 1) * sizeof(double), e->stream));
+    HIPCHK(hipMemsetAsync(e->c.zt, 0, std::max<size_t>(e->m, 1) * sizeof(double), e->stream));
+    if (e->c.nelim) HIPCHK(hipMemsetAsync(e->c.xte, 0, (size_t)e->m * sizeof(double), e->stream));
+  }
   pcg_count_will_jump(e); start_history_void(e);     // the first solve from zero needs far more PCG iterations than the steady state
   rhs_m_stale(e);                          // (vb = rho z - y = 0 is NOT the whole m-part when a row carries an eliminated variable: -rho a (-q_y) / D_y)
   return 0;
@@ -4385,10 +4451,21 @@ extern "C" int hipeng_set_z(hipeng *e, const c_float *z) {
 
 // ---- graphs ---------------------------------------------------------------
 #define TR2(e, ...) do { if ((e)->trace >= 2) { fprintf(stderr, "[osqp_amd:t2] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
-static void launch_init(hipeng *e, int bench = 0) {
+// for_resident: the launch that follows is k_pcg_resident and nothing else reads r0 and u0 before the next k_pcg_init (the K == 0
+// graphs of a FORM_RESIDENT engine, and the timing hook of that pair).  Every other caller gets the default form: a launch-per-step
+// graph that takes over after a launch gave up starts with its own k_pcg_init (k_admm_finalize leaves the iteration untouched then).
+static bool init_resident_form(const hipeng *e) { return e->form == FORM_RESIDENT && e->rc.r0pos != nullptr; }
+static void launch_init(hipeng *e, int bench = 0, bool for_resident = false) {
   if (e->c.vd) hipLaunchKernelGGL(k_vd, dim3(elem_grid(e->n + e->m)), dim3(TB), 0, e->stream, e->c);
-  if (e->c.dP.nblk) hipLaunchKernelGGL(k_pcg_init<true>, dim3(e->c.gridM), dim3(TB), 0, e->stream, e->c, bench);
-  else hipLaunchKernelGGL(k_pcg_init<false>, dim3(e->c.gridM), dim3(TB), 0, e->stream, e->c, bench);
+  double *const none = nullptr;
+  const dim3 g(e->c.gridM), b(TB);
+  if (for_resident && init_resident_form(e)) {
+    if (e->c.dP.nblk) hipLaunchKernelGGL((k_pcg_init<true, true>), g, b, 0, e->stream, e->c, bench, e->rc.r0pos);
+    else hipLaunchKernelGGL((k_pcg_init<false, true>), g, b, 0, e->stream, e->c, bench, e->rc.r0pos);
+  } else {
+    if (e->c.dP.nblk) hipLaunchKernelGGL((k_pcg_init<true, false>), g, b, 0, e->stream, e->c, bench, none);
+    else hipLaunchKernelGGL((k_pcg_init<false, false>), g, b, 0, e->stream, e->c, bench, none);
+  }
 }
 
 static void launch_cg_A(hipeng *e, int it, int flags) {
@@ -4425,7 +4502,7 @@ static int get_graph(hipeng *e, int K, int R, int spec_lo, hipGraphExec_t *out) 
   TR2(e, "get_graph K=%d R=%d: begin capture", K, R);
   HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
   for (int seg = 0; seg < R; seg++) {
-    launch_init(e);
+    launch_init(e, 0, K == 0);
     if (K == 0) launch_resident(e);                   // the whole linear solve in one launch (K in registers)
     else { launch_cg_A(e, -1, 8); launch_cg_B(e, -1, 0); }   // operator apply on u0 (+ first convergence test), then w0 and the first dots
     for (int it = 0; it < K; it++) launch_pcg_iter(e, it, 0, spec_lo);
@@ -4522,7 +4599,19 @@ static int resident_gave_up(hipeng *e, const State &s, bool quiet) {
   return 0;
 }
 
-extern "C" int hipeng_run_admm(hipeng *e, c_int count) {
+static void fill_scalars(const double *h, hipeng_scalars *o);
+static int enqueue_residuals(hipeng *e);
+
+// Whether the residual scalars taken directly behind a window's graphs belong to the iterate the call ends on: the window did all
+// it was asked for (no stall continuation is left to run), no resident launch gave up, and no slow-wait record had to be cleared in
+// between.  Anything else and the caller takes the residuals again, as hipeng_residuals does.
+extern "C" int hipeng_early_scalars_usable(c_int remaining, int res_fail, int res_slow, int res_repub) {
+  return remaining == 0 && !res_fail && !res_slow && !res_repub;
+}
+
+// hipeng_run_admm (early == null) and hipeng_run_admm_check
+static int run_admm(hipeng *e, c_int count, hipeng_scalars *early, int *have) {
+  if (have) *have = 0;
   if (!e || count < 0) return HIPENG_ERR_ARG;
   HIPCHK(hipSetDevice(e->device));
   State s;
@@ -4551,10 +4640,14 @@ extern "C" int hipeng_run_admm(hipeng *e, c_int count) {
   if (!e->res_use && e->resident_available()) e->res_use = true;
   bool had_fail = false;
   const long long start = e->admm_total, target = start + (long long)count;
-  *e->h_target = target;
-  HIPCHK(hipMemcpyAsync(&e->c.st->admm_target, e->h_target, sizeof(long long), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemsetAsync(&e->c.st->iters_max, 0, sizeof(int), e->stream));
-  HIPCHK(hipMemsetAsync(&e->c.st->iters_min, 0x7f, sizeof(int), e->stream));
+  if (e->fused_check) {
+    hipLaunchKernelGGL(k_window_begin, dim3(1), dim3(64), 0, e->stream, e->c.st, target);      // (the three fields in one launch)
+  } else {
+    *e->h_target = target;
+    HIPCHK(hipMemcpyAsync(&e->c.st->admm_target, e->h_target, sizeof(long long), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(&e->c.st->iters_max, 0, sizeof(int), e->stream));
+    HIPCHK(hipMemsetAsync(&e->c.st->iters_min, 0x7f, sizeof(int), e->stream));
+  }
   if (e->start_dirty) { if (reset_start(e)) return HIPENG_ERR_HIP; e->start_dirty = false; }
   long long remaining = count;
   const int cap = std::max(2, e->prm.pcg_max_iter);
@@ -4583,7 +4676,16 @@ extern "C" int hipeng_run_admm(hipeng *e, c_int count) {
     long long left = burst;
     for (; gR && left >= R; left -= R) { HIPCHK(hipGraphLaunch(gR, e->stream)); e->stats.graph_launches += 1; }
     for (; left > 0; left--) { HIPCHK(hipGraphLaunch(g1, e->stream)); e->stats.graph_launches += 1; }
-    if (read_state(e, &s)) return HIPENG_ERR_HIP;
+    // A window that should be the call's last carries the residual pass behind its graphs: scalars and State come back in one
+    // copy, after one wait.  Nothing the iterations read is written by that pass, so a window that turns out not to be the last
+    // (a stall continuation, a launch that gave up) goes on as it would have, and the scalars are dropped.
+    const bool fused = early && e->fused_check && burst == remaining;
+    if (fused) {
+      if (enqueue_residuals(e)) return HIPENG_ERR_HIP;
+      HIPCHK(hipMemcpyAsync(e->h_check, e->c.scal, SC_COUNT * 16 * sizeof(double) + sizeof(State), hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipStreamSynchronize(e->stream));
+      memcpy(&s, e->h_check + SC_COUNT * 16, sizeof(State));
+    } else if (read_state(e, &s)) return HIPENG_ERR_HIP;
     lease.give();
     e->res_slow += s.res_slow; e->res_slow_max = std::max<long long>(e->res_slow_max, s.res_slow_max); e->res_repub += s.res_repub;
     if (s.res_slow || s.res_repub) {
@@ -4598,6 +4700,7 @@ extern "C" int hipeng_run_admm(hipeng *e, c_int count) {
     const long long done_now = s.admm_done - start;
     const bool stalls = count - done_now > remaining - burst;       // some launches were continuations
     remaining = count - done_now;
+    if (fused && hipeng_early_scalars_usable((c_int)remaining, s.res_fail, s.res_slow, s.res_repub)) { fill_scalars(e->h_check, early); *have = 1; }
     call_max = std::max(call_max, s.iters_max);
     const int in_flight = s.stalled ? std::max(s.iters[0], s.iters[1]) : 0;
     if (e->trace) fprintf(stderr, "[osqp_amd] window: K=%d burst=%lld done=%lld iters_max=%d last=%d stalled=%d(%d) launches=%lld\n", e->K, burst, done_now, s.iters_max, s.iters_last, s.stalled, in_flight, (long long)e->stats.graph_launches);
@@ -4627,6 +4730,15 @@ extern "C" int hipeng_run_admm(hipeng *e, c_int count) {
   return 0;
 }
 
+extern "C" int hipeng_run_admm(hipeng *e, c_int count) { return run_admm(e, count, nullptr, nullptr); }
+
+// hipeng_run_admm followed by hipeng_residuals, with one wait between them where the window allows it: *have = 1 and *out holds the
+// scalars of the iterate the call ended on; *have = 0 and the caller asks hipeng_residuals.
+extern "C" int hipeng_run_admm_check(hipeng *e, c_int count, hipeng_scalars *out, int *have) {
+  if (!out || !have) return HIPENG_ERR_ARG;
+  return run_admm(e, count, out, have);
+}
+
 extern "C" int hipeng_reset_stats(hipeng *e) {
   if (!e) return HIPENG_ERR_ARG;
   HIPCHK(hipSetDevice(e->device));
@@ -4649,7 +4761,7 @@ extern "C" int hipeng_get_stats(hipeng *e, hipeng_stats *st) {
 }
 
 // ---- residual scalars -----------------------------------------------------
-static void fill_scalars(const double *h, hipeng_scalars *o) {
+static void fill_scalars(const double *h, hipeng_scalars *o) {   // (every field of *o is written)
   o->pri_res_u = h[SCI(SC_PRI_U)]; o->pri_res_s = h[SCI(SC_PRI_S)];
   o->z_u = h[SCI(SC_Z_U)]; o->z_s = h[SCI(SC_Z_S)]; o->Ax_u = h[SCI(SC_AX_U)]; o->Ax_s = h[SCI(SC_AX_S)];
   o->dua_res_u = h[SCI(SC_DUA_U)]; o->dua_res_s = h[SCI(SC_DUA_S)];
@@ -4663,14 +4775,20 @@ static void fill_scalars(const double *h, hipeng_scalars *o) {
   o->Adx_viol = h[SCI(SC_ADX_VIOL)];
 }
 
-extern "C" int hipeng_residuals(hipeng *e, hipeng_scalars *out) {
-  if (!e || !out) return HIPENG_ERR_ARG;
-  HIPCHK(hipSetDevice(e->device));
+// what one residual evaluation enqueues (hipeng_residuals, and hipeng_run_admm_check behind a window's graphs)
+static int enqueue_residuals(hipeng *e) {
   HIPCHK(hipMemsetAsync(e->c.scal, 0, SC_COUNT * 16 * sizeof(double), e->stream));
   if (e->c.A.nblk > e->c.A.nwave) hipLaunchKernelGGL(k_huge_dot, dim3(e->c.gridA), dim3(TB), 0, e->stream, e->c, (const double *)e->c.xy, 1);
   hipLaunchKernelGGL(k_residuals, dim3(e->c.gridA + e->c.gridM), dim3(TB), 0, e->stream, e->c);
   hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(TB), 0, e->stream, e->c);
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int hipeng_residuals(hipeng *e, hipeng_scalars *out) {
+  if (!e || !out) return HIPENG_ERR_ARG;
+  HIPCHK(hipSetDevice(e->device));
+  if (enqueue_residuals(e)) return HIPENG_ERR_HIP;
   double h[SCI(SC_COUNT)];
   HIPCHK(hipMemcpyAsync(h, e->c.scal, sizeof(h), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -4817,7 +4935,7 @@ extern "C" int hipeng_time_kernel(hipeng *e, int which, int reps, double *usec) 
   auto one = [&](int it) {
     // the first two kernels of a resident ADMM iteration: right-hand side + start residual, then the whole linear solve
     // (without k_admm_finalize the iterates do not move: every repetition solves the same system from the same start)
-    if (which == 8) { launch_init(e, 1); launch_resident(e); return; }
+    if (which == 8) { launch_init(e, 1, true); launch_resident(e); return; }
     if (which == 5) { launch_init(e, 1); return; }   // first kernel of an ADMM iteration
     if (which == 6) { launch_pcg_iter(e, it, 4); return; }   // one whole PCG iteration (all its launches, in loop order)
 

@@ -119,6 +119,8 @@ typedef struct {
   c_float *rawq, *rawl, *rawu;
   hipeng_scalars sc;      /* last residual scalars                                */
   c_int sc_iter;          /* iteration they belong to (-1 = stale)                */
+  hipeng_scalars early;   /* scalars that came back with a window's own wait (hipeng_run_admm_check) */
+  c_int early_iter;       /* iteration they belong to (-1 = none): refresh_info takes them once */
   c_int host_syncs;
   c_int forced_warned;    /* the pcg_forced warning has been printed for this workspace */
   osqp_amd_options opt;   /* this instance's engine options (copied from the defaults at creation) */
@@ -206,7 +208,7 @@ static hip_pcg_solver *pcg_alloc(c_int n, c_int m, c_float sigma, c_int polish) 
   s->solve = polish ? pcg_solve_polish : pcg_solve;
   s->free = pcg_free;
   s->update_matrices = pcg_update_matrices; s->update_rho_vec = pcg_update_rho_vec;
-  s->n = n; s->m = m; s->sigma = sigma; s->polish = polish; s->sc_iter = -1;
+  s->n = n; s->m = m; s->sigma = sigma; s->polish = polish; s->sc_iter = -1; s->early_iter = -1;
   opt_init();
   s->opt = g_opt;
   return s;
@@ -588,8 +590,12 @@ static c_int use_unscaled(const OSQPWorkspace *w) {
 
 static c_int refresh_info(OSQPWorkspace *w, c_int iter, c_int with_obj) {
   hip_pcg_solver *s = PCG(w);
-  if (hipeng_residuals(s->eng, &s->sc)) return 1;
-  s->host_syncs++;
+  if (s->early_iter == iter) s->sc = s->early;      /* the window's own wait brought them (hipeng_run_admm_check): used once */
+  else {
+    if (hipeng_residuals(s->eng, &s->sc)) return 1;
+    s->host_syncs++;
+  }
+  s->early_iter = -1;
   s->sc_iter = iter;
   w->info->iter = iter;
   if (with_obj) w->info->obj_val = s->sc.obj_scaled * (w->settings->scaling ? w->scaling->cinv : 1.0);
@@ -787,6 +793,7 @@ c_int osqp_solve(OSQPWorkspace *w) {
 
   if (!st->warm_start) cold_start(w);
   s->sc_iter = -1;
+  s->early_iter = -1;
 
   while (iter < st->max_iter) {
     /* next iteration count at which the reference would look at the iterates */
@@ -795,8 +802,20 @@ c_int osqp_solve(OSQPWorkspace *w) {
     if (st->adaptive_rho && rho_interval) next = HMIN(next, (iter / rho_interval + 1) * rho_interval);
     if (st->verbose) next = HMIN(next, iter == 0 ? 1 : (iter / PRINT_INTERVAL + 1) * PRINT_INTERVAL);
     next = HMIN(next, iter + (st->time_limit ? 8 : 128));
-    if (hipeng_run_admm(s->eng, next - iter)) { exitflag = 1; goto done; }
-    s->host_syncs++;
+    /* a window that ends where the residuals are looked at (a check, a printed line, a rho-interval check, the last iteration)
+     * takes them behind its own iterations: one wait instead of two */
+    {
+      const c_int will_check = st->check_termination && (next % st->check_termination == 0);
+      const c_int will_print = st->verbose && ((next % PRINT_INTERVAL == 0) || (next == 1));
+      const c_int will_rho = st->adaptive_rho && rho_interval && (next % rho_interval == 0);
+      int have = 0;
+      s->early_iter = -1;
+      if (will_check || will_print || will_rho || next == st->max_iter) {
+        if (hipeng_run_admm_check(s->eng, next - iter, &s->early, &have)) { exitflag = 1; goto done; }
+      } else if (hipeng_run_admm(s->eng, next - iter)) { exitflag = 1; goto done; }
+      s->host_syncs++;
+      if (have) s->early_iter = next;
+    }
     iter = next;
 
     if (st->time_limit) {

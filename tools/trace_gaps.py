@@ -8,7 +8,7 @@ with open(f) as fh:
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0]))
 rows.sort()
 # keep only the last third of the single-QP engine kernels (steady-state steps)
-eng = [r for r in rows if r[2].replace("void ", "").startswith(("k_cg", "k_pcg", "k_admm", "k_resid", "k_final", "k_precond", "k_refresh", "k_form", "__amd_rocclr"))]
+eng = [r for r in rows if r[2].replace("void ", "").startswith(("k_cg", "k_pcg", "k_admm", "k_resid", "k_final", "k_precond", "k_refresh", "k_form", "k_fill", "k_start_reset", "k_window", "k_huge", "__amd_rocclr"))]
 print("engine kernels:", len(eng))
 busy = collections.Counter(); cnt = collections.Counter(); noop = collections.Counter(); noop_t = collections.Counter()
 gaps = []
