@@ -231,6 +231,16 @@ int hipeng_dense_switches(int out[2]);
 int hipeng_dense_gemm_selftest(int kernel, int M, int N, int K, const double *T, int ldt, const double *B, int ldb, const double *w,
                                double *C, int ldc, double alpha, double beta, int sr0, int sr1, int sc0, int sc1, int lower, int kmode, int ksl);
 
+/* The OSQP_AMD_* switches of the single-QP engine (the table ahead of struct hipeng in csrc/engine.hip), for the tests: neither call
+ * needs a device.  hipeng_switch_row: row `index` -- name, kind (0 flag: atoi != 0, 1 int: atoi, 2 double: atof, 3 pair of ints: "a,b",
+ * 4 text), default as text ("unset" where an unset variable is a value of its own: the engine then works the default out from the
+ * problem or the caller), that bit, a one-line description; outputs may be NULL, def_text holds def_cap bytes.  Returns the number of rows.
+ * hipeng_switch_values: what the engine's reader makes of the current environment, two doubles per row for `rows` rows at most --
+ * out[2 i] the value (-1 where unset is distinct and the variable is not set; the length of a text), out[2 i + 1] the second
+ * number of a pair, else 0.  Returns the number of rows. */
+int hipeng_switch_row(int index, const char **name, int *kind, char *def_text, int def_cap, int *unset_distinct, const char **what);
+int hipeng_switch_values(double *out, int rows);
+
 /* O(nnz) parts of the single-QP engine's solution derivatives (csrc/kkt_sens.h: k_sens_grad, k_sens_tan_rhs).  One hipsens per
  * workspace, created at its first osqp_amd_adjoint / osqp_amd_tangent call and kept until cleanup; every call runs on the stream
  * of `pe`, the polish-mode instance's engine whose solves it accompanies.  P, A: the patterns in the caller's CSC order.

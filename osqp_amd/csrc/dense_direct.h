@@ -191,8 +191,8 @@ __global__ void __launch_bounds__(TB, 2) k_dd_gemm_tn_lds(double *C, int ldc, co
 }
 
 // every product of this file goes through here: the LDS-staged kernel, or (OSQP_AMD_DENSE_GEMM_LDS=0) the one that feeds the MFMAs from global memory
-// (dd_gemm_lds: -1 until the first product of the process reads the switch; file scope so that the test hooks of dense_direct_host.h
-// can report it and run an inversion on either kernel)
+// (dd_gemm_lds: -1 until dd_gemm_latch, ahead of the first product of the process, takes the switch from its caller's Switches; process-wide
+// and at file scope so that the test hooks of dense_direct_host.h can report it and run an inversion on either kernel)
 static int dd_gemm_lds = -1;
 constexpr size_t DD_GEMM_LDS_BYTES = (size_t)4 * DD_KC * DD_LP * sizeof(double);
 static bool dd_gemm_lds_attr() {
@@ -200,16 +200,15 @@ static bool dd_gemm_lds_attr() {
   (void)hipGetLastError();
   return false;
 }
+static void dd_gemm_latch(int want_lds) {
+  if (dd_gemm_lds >= 0) return;
+  dd_gemm_lds = want_lds != 0;
+  if (dd_gemm_lds && !dd_gemm_lds_attr()) dd_gemm_lds = 0;
+}
 static void dd_gemm(hipStream_t stream, dim3 grid, double *C, int ldc, const double *T, int ldt, const double *B, int ldb, const double *w,
                     int M, int N, int K, double alpha, double beta, int sr0, int sr1, int sc0, int sc1, int lower, int kmode, int ksl = 0, long long cz = 0) {
-  int &lds = dd_gemm_lds;
   constexpr size_t bytes = DD_GEMM_LDS_BYTES;
-  if (lds < 0) {
-    lds = 1;
-    if (const char *x = getenv("OSQP_AMD_DENSE_GEMM_LDS")) lds = atoi(x) != 0;
-    if (lds && !dd_gemm_lds_attr()) lds = 0;
-  }
-  if (lds) hipLaunchKernelGGL(k_dd_gemm_tn_lds, grid, dim3(TB), bytes, stream, C, ldc, T, ldt, B, ldb, w, M, N, K, alpha, beta, sr0, sr1, sc0, sc1, lower, kmode, ksl, cz);
+  if (dd_gemm_lds > 0) hipLaunchKernelGGL(k_dd_gemm_tn_lds, grid, dim3(TB), bytes, stream, C, ldc, T, ldt, B, ldb, w, M, N, K, alpha, beta, sr0, sr1, sc0, sc1, lower, kmode, ksl, cz);
   else hipLaunchKernelGGL(k_dd_gemm_tn, grid, dim3(TB), 0, stream, C, ldc, T, ldt, B, ldb, w, M, N, K, alpha, beta, sr0, sr1, sc0, sc1, lower, kmode, ksl, cz);
 }
 
@@ -372,11 +371,6 @@ __global__ void __launch_bounds__(TB) k_dd_mirror(double *A, int n, int neg) {
 // two parts -- look-ahead.  21.6 -> 24.9 ms at n = 5120, 3.5 -> 14.5 ms at n = 1280: two event hand-overs per step and the stream's
 // creation cost more than the 0.25 ms pivot kernels they were to hide.)
 static int dd_invert_sweep(hipStream_t stream, double *A, int n, double *D, double *Wt, double *Vt, int *flag) {
-  static bool lds_set = false;
-  if (!lds_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dd_pivot), hipFuncAttributeMaxDynamicSharedMemorySize, DD_NB * DD_NB * (int)sizeof(double)) != hipSuccess) return HIPENG_ERR_HIP;
-    lds_set = true;
-  }
   const int nb = n / DD_NB;
   for (int kb = 0; kb < nb; kb++) {
     const int p0 = kb * DD_NB, p1 = p0 + DD_NB;
@@ -500,16 +494,11 @@ __global__ void __launch_bounds__(TB) k_dd_rowT(const double *A, int lda, int kb
   for (int q = threadIdx.x; q < 64 * DD_NB; q += TB) { const int k = q / DD_NB, r = q % DD_NB; Tp[(size_t)(k0 + k) * DD_NB + r] = tile[r][k]; }
 }
 
+constexpr size_t DD_TRSM_LDS_BYTES = ((size_t)DD_NB * (DD_NB + 1) / 2 + (size_t)DD_NB * 64) * sizeof(double);
 // A (n x n, n a multiple of 128, symmetric positive definite, lower tiles valid) <- A^-1 (both triangles) on `stream`.
 // Wt, Yt: [128][n] panels; Tp: [n][128]; X2: n x n scratch.
 static int dd_invert_chol(hipStream_t stream, double *A, int n, double *Wt, double *Yt, double *Tp, double *X2, int *flag) {
-  static bool lds_set = false;
-  const size_t trsm_lds = ((size_t)DD_NB * (DD_NB + 1) / 2 + (size_t)DD_NB * 64) * sizeof(double);
-  if (!lds_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dd_chol), hipFuncAttributeMaxDynamicSharedMemorySize, DD_NB * DD_NB * (int)sizeof(double)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k_dd_trsm), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trsm_lds) != hipSuccess) return HIPENG_ERR_HIP;
-    lds_set = true;
-  }
+  constexpr size_t trsm_lds = DD_TRSM_LDS_BYTES;
   const int nb = n / DD_NB;
   const double *nul = nullptr;
   // (a) A = L L': per block column the diagonal factor, the panel solved against it, the trailing lower tiles updated
@@ -733,4 +722,28 @@ __global__ void __launch_bounds__(TB) k_dd_finish(Ctx c, DdCtx dd) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     st->iters[0] = 1; st->iters[1] = 0; st->done = 1;      // (a pivot that was not positive never gets here: dd_refresh drops the inverse)
   }
+}
+
+// The dynamic-LDS limits of this file's kernels are an attribute per DEVICE: set on the current one by whoever is about to launch
+// there (build_dense_direct once per engine, the test hooks per call), each at the most any launch asks for -- k_dd_gemv's at DD_MAX
+// unknowns, so that a later, smaller engine does not lower it under an earlier one.  The launches themselves touch no attribute.
+// Five attribute calls cost a dense-direct set-up of 150 unknowns 0.2 of its 5.3 ms, so a device that has its limits is remembered
+// (bit d of `done`; the calls are idempotent: two threads that race set them twice).
+// k_dd_gemm_tn_lds's is not required: dd_gemm_latch sends the process to k_dd_gemm_tn where it cannot be set.
+static bool dd_set_kernel_limits() {
+  static std::atomic<unsigned long long> done{0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
+  const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
+  if (done.load(std::memory_order_acquire) & bit) return true;
+  const auto set = [](const void *kernel, size_t bytes) {
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+  };
+  (void)dd_gemm_lds_attr();
+  if (!(set(reinterpret_cast<const void *>(k_dd_pivot), DD_NB * DD_NB * sizeof(double)) && set(reinterpret_cast<const void *>(k_dd_chol), DD_NB * DD_NB * sizeof(double)) &&
+        set(reinterpret_cast<const void *>(k_dd_trsm), DD_TRSM_LDS_BYTES) && set(reinterpret_cast<const void *>(k_dd_gemv), DD_MAX * sizeof(double)))) return false;
+  done.fetch_or(bit, std::memory_order_release);
+  return true;
 }

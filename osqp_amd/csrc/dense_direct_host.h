@@ -4,10 +4,7 @@
 // 90 us) nor launch-per-step PCG iterations come near (tools/small_paths.py: 125-iteration solves in 3.6 / 4.1 / 4.9 / 6.1 ms at
 // n = 150 / 300 / 600 / 1000 against 18 / 11.3 / 11.1 / 11.2 ms; at n = 2000 the 5.6 ms refresh of every rho update eats the gain).
 static int build_dense_direct(hipeng *e, const csc *P, const csc *A, bool small_only) {
-  int want = 1;
-  if (const char *x = getenv("OSQP_AMD_DENSE_DIRECT")) want = atoi(x);
-  int small_max = 1024;
-  if (const char *x = getenv("OSQP_AMD_DENSE_SMALL")) small_max = std::max(0, atoi(x));
+  const int want = e->sw.dense_direct, small_max = e->sw.dense_small;
   if (small_only && small_max == 0) return 0;
   const int n = e->n, m = e->m;
   if (!want || e->form != FORM_STEPS || n == 0 || m == 0) return 0;
@@ -56,7 +53,7 @@ static int build_dense_direct(hipeng *e, const csc *P, const csc *A, bool small_
   const double nnzA = (double)e->A.val.size(), nnzP = 2.0 * (double)e->P_toM_up.size();
   const double bytes_pcg = 8.0 * (2.0 * nnzA + nnzP) * 12.0, bytes_dd = 3.0 * 8.0 * (double)nap * nap;
   bool pays = (small_only || bytes_pcg > bytes_dd) && (double)nd * nap * 8.0 < 6e9;
-  if (const char *x = getenv("OSQP_AMD_DENSE_DIRECT")) if (atoi(x) == 2) pays = (double)nd * nap * 8.0 < 6e9;      // 2: whenever it fits (tests)
+  if (want == 2) pays = (double)nd * nap * 8.0 < 6e9;      // 2: whenever it fits (tests)
   if (!pays) return 0;
   std::vector<int> bnbr(bnbr_var.size());
   for (size_t q = 0; q < bnbr_var.size(); q++) bnbr[q] = bnbr_var[q] < 0 ? -1 : vidx[bnbr_var[q]];
@@ -87,8 +84,7 @@ static int build_dense_direct(hipeng *e, const csc *P, const csc *A, bool small_
       dev_alloc(e, &dd.flag, (size_t)4)) return HIPENG_ERR_HIP;
 #define DDUP(dst, src) if (!(src).empty()) HIPCHK(hipMemcpyAsync(dst, (src).data(), (src).size() * sizeof((src)[0]), hipMemcpyHostToDevice, e->stream))
   {
-    int symv = nap >= 2048;
-    if (const char *x = getenv("OSQP_AMD_DENSE_SYMV")) symv = atoi(x) != 0;
+    const int symv = e->sw.dense_symv != SW_UNSET ? e->sw.dense_symv : nap >= 2048;
     const size_t tiles = (size_t)(nap / DD_NB) * (nap / DD_NB + 1) / 2;
     if (symv && (dev_alloc(e, &dd.rowpart, tiles * DD_NB) || dev_alloc(e, &dd.colpart, tiles * DD_NB))) return HIPENG_ERR_HIP;
   }
@@ -96,22 +92,17 @@ static int build_dense_direct(hipeng *e, const csc *P, const csc *A, bool small_
 #undef DDUP
   HIPCHK(hipStreamSynchronize(e->stream));        // (the sources are locals)
   dd.vidx = d_vidx; dd.alist = d_alist; dd.blist = d_blist; dd.bnbr = d_bnbr; dd.drow = d_drow; dd.isdense = d_isdense; dd.aptr = d_aptr; dd.aadj = d_aadj; dd.sptr = d_sptr; dd.spos = d_spos;
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dd_gemv), hipFuncAttributeMaxDynamicSharedMemorySize, nap * (int)sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
+  if (!dd_set_kernel_limits()) return 0;          // (not an error: the form is not taken)
   e->dd = dd;
   e->dd_init_r = e->c.init_r; e->dd_init_stride = e->c.init_stride;       // (what the launch-per-step kernels use: direct_disable puts them back)
   e->c.init_r = e->c.r; e->c.init_stride = 1;
   e->c.fin_wave_rows = 1;
   {
-    int one_gather = 1;
-    if (const char *x = getenv("OSQP_AMD_DENSE_ONE_GATHER")) one_gather = atoi(x) != 0;
     // (only where k_pcg_init's pass over [P | A'] is more than a launch: on small problems k_vd's own launch would cost more than it saves)
-    if (one_gather && nnzA >= 2e5 && dev_alloc(e, &e->c.vd, (size_t)(n + m))) return HIPENG_ERR_HIP;
+    if (e->sw.dense_one_gather && nnzA >= 2e5 && dev_alloc(e, &e->c.vd, (size_t)(n + m))) return HIPENG_ERR_HIP;
   }
   e->form = FORM_DENSE_DIRECT; e->res_use = true;
-  if (e->trace) fprintf(stderr, "[osqp_amd] dense-direct solve: %d dense unknowns (%d x %d inverse, %.0f MB), %d sparse unknowns by Schur complement, %d dense rows of A\n",
+  if (e->sw.trace) fprintf(stderr, "[osqp_amd] dense-direct solve: %d dense unknowns (%d x %d inverse, %.0f MB), %d sparse unknowns by Schur complement, %d dense rows of A\n",
                         na, nap, nap, 8e-6 * nap * nap, nb2, nd);
   return 0;
 }
@@ -123,10 +114,11 @@ static int build_dense_direct(hipeng *e, const csc *P, const csc *A, bool small_
 // was not positive) and the inverse is computed again by the Cholesky route; if that fails too the engine drops the dense solve.
 #define DD_CHECK 1e-6
 #define DD_FWD 8.0
-static int dd_chol_first = -1;            // OSQP_AMD_DENSE_CHOL as the first refresh of the process read it (-1: not read yet; hipeng_dense_switches)
+static int dd_chol_first = -1;            // OSQP_AMD_DENSE_CHOL as the first refresh of the process found it in its engine's switches (-1: none yet; hipeng_dense_switches)
 static int dd_refresh(hipeng *e) {
   const DdCtx &dd = e->dd;
   const int nap = dd.nap;
+  dd_gemm_latch(e->sw.dense_gemm_lds);
   HIPCHK(hipMemsetAsync(dd.flag, 0, 4 * sizeof(int), e->stream));
   if (dd.nd) HIPCHK(hipMemsetAsync(dd.R, 0, (size_t)dd.nd * nap * sizeof(double), e->stream));
   else HIPCHK(hipMemsetAsync(dd.S, 0, (size_t)nap * nap * sizeof(double), e->stream));
@@ -148,7 +140,7 @@ static int dd_refresh(hipeng *e) {
   // Failed (or a pivot was not positive): the matrix as formed goes through the blocked Cholesky route (cond eps; five times slower
   // until its triangular inversion is parallelised better) and is checked again.  OSQP_AMD_DENSE_CHOL=1 takes that route at once.
   int &chol_first = dd_chol_first;
-  if (chol_first < 0) { chol_first = 0; if (const char *x = getenv("OSQP_AMD_DENSE_CHOL")) chol_first = atoi(x) != 0; }
+  if (chol_first < 0) chol_first = e->sw.dense_chol != SW_UNSET ? e->sw.dense_chol : 0;
   const dim3 gg(std::min(1024, nap / 4));
   const size_t lds = (size_t)nap * sizeof(double);
   double err = 0.0; int flag = 0;
@@ -179,7 +171,7 @@ static int dd_refresh(hipeng *e) {
     HIPCHK(hipMemcpyAsync(&flag, dd.flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (!flag && err <= DD_CHECK && fwd <= DD_FWD * nap * 0x1p-52) break;
-    if (e->trace) fprintf(stderr, "[osqp_amd] dense-direct: the %s inverse failed its check (%.2e, forward %.2e%s)\n", attempt ? "Cholesky" : "block-sweep", err, fwd,
+    if (e->sw.trace) fprintf(stderr, "[osqp_amd] dense-direct: the %s inverse failed its check (%.2e, forward %.2e%s)\n", attempt ? "Cholesky" : "block-sweep", err, fwd,
                           flag ? ", a pivot was not positive" : "");
   }
   e->dd_chol = attempt >= 1;                // (the inverse in use came from the Cholesky route)
@@ -223,6 +215,8 @@ struct DdHookMem {                        // the device buffers and events of on
 // environment, as in an engine).  timed: one n x n x n TN GEMM ahead of it, for the kernel's rate (ms[1]; ms[0]: the inversion).
 static int dd_hook_invert(int n, const double *A, double *Ainv, int route, int gemm, bool timed, double *ms) {
   if (n <= 0 || n % DD_NB || !A || !Ainv) return HIPENG_ERR_ARG;
+  if (!dd_set_kernel_limits()) return HIPENG_ERR_HIP;
+  if (gemm < 0) dd_gemm_latch(read_switches().dense_gemm_lds);
   DdHookMem mem;
   double *dA = nullptr, *dC = nullptr, *D = nullptr, *Bp = nullptr, *T = nullptr, *Tp = nullptr; int *flag = nullptr;
   const size_t nn = (size_t)n * n;
@@ -254,9 +248,8 @@ static int dd_hook_invert(int n, const double *A, double *Ainv, int route, int g
 // inversion on the device, ms[1] that of one n x n x n TN GEMM (C = A' A on the matrix cores: the kernel's rate).  The Cholesky route
 // unless OSQP_AMD_DENSE_CHOL=0, the GEMM kernel of the engines.  Returns 0, or 1 when a pivot was not positive.
 extern "C" int hipeng_dense_invert_selftest(int n, const double *A, double *Ainv, double *ms) {
-  int chol = 1;
-  if (const char *x = getenv("OSQP_AMD_DENSE_CHOL")) chol = atoi(x) != 0;
-  return dd_hook_invert(n, A, Ainv, chol, -1, true, ms);
+  const int chol = read_switches().dense_chol;
+  return dd_hook_invert(n, A, Ainv, chol != SW_UNSET ? chol : 1, -1, true, ms);
 }
 // The same inversion with both choices explicit: route 0 block sweeps / 1 blocked Cholesky, gemm 0 k_dd_gemm_tn / 1 k_dd_gemm_tn_lds.
 extern "C" int hipeng_dense_invert_route(int n, const double *A, double *Ainv, int route, int gemm) {
@@ -289,7 +282,7 @@ extern "C" int hipeng_dense_gemm_selftest(int kernel, int M, int N, int K, const
   HIPCHK(hipMemcpy(dT, T, (size_t)K * ldt * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dB, B, (size_t)K * ldb * 8, hipMemcpyHostToDevice));
   if (w) HIPCHK(hipMemcpy(dw, w, (size_t)K * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(dC, C, (size_t)Mp * ldc * 8, hipMemcpyHostToDevice));
-  if (kernel == 1 && !dd_gemm_lds_attr()) return HIPENG_ERR_HIP;
+  if (!dd_set_kernel_limits() || (kernel == 1 && !dd_gemm_lds_attr())) return HIPENG_ERR_HIP;
   const dim3 grid((N + 127) / 128, (M + 127) / 128, nz);
   double *out = ksl > 0 ? part : dC;
   const double *wd = w ? dw : nullptr;

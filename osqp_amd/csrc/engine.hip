@@ -33,6 +33,9 @@
 #include <new>
 #include <cstdlib>
 #include <cstring>
+#include <cstddef>
+#include <climits>
+#include <limits>
 #include <cmath>
 #include <vector>
 #include <map>
@@ -3022,10 +3025,108 @@ struct HostMat {         // host image of a device CSR matrix
   RowBlk *d_blk = nullptr;
 };
 
+// ---- the OSQP_AMD_* switches of the single-QP engine: one row each, one reader, one struct ----
+// read_switches() is the only place of this translation unit that looks at the environment, and a pure function of it.  Every hipeng
+// takes its values when it is made (hipeng::sw, a member initialiser: the plan temporaries of the CPU hooks have them too), and
+// every use site reads e->sw.  A clamp that depends on the problem (RESIDENT_NWG, BLOCK_FIN_DOTS) stays at its use site.
+enum SwKind : int { SW_FLAG = 0, SW_INT = 1, SW_DOUBLE = 2, SW_INT_PAIR = 3, SW_TEXT = 4 };   // atoi != 0 / atoi / atof / sscanf "%d,%d" / the string itself
+enum SwRange : int { SW_ANY = 0, SW_CLAMP = 1, SW_IGNORE = 2 };    // a value outside [lo, hi] is taken as it is / clamped / ignored (the switch then reads as not set)
+constexpr int SW_UNSET = -1;     // what the field of an `unset is distinct` row holds while its variable is not set: the use site works out the default
+struct Switches {
+  int resident, resident_min_n, resident_all_cus, resident_nwg, resident_banks, resident_pipe, resident_predict;
+  double resident_predict_margin;
+  int resident_inject, resident_u0, resident_fine, resident_blocks, init_resident_stores, form_k_lists;
+  double form_k_list_mb;
+  int setup_threads, block_direct, block_coupled_max, block_fin_dots, block_plain;
+  int dense_p, dense_direct, dense_small, dense_symv, dense_one_gather, dense_chol, dense_gemm_lds;
+  int elim, hfold, split, chunk, fin_grid, fused_check;
+  double extrap;
+  int extrap_sched[2];
+  int khead, graph_segs, trace;
+  char trace_maps[PATH_MAX];
+};
+struct SwRow { const char *name; SwKind kind; size_t field; double def, def2; SwRange range; double lo, hi; bool unset_distinct; const char *what; };
+#define SW(field) offsetof(Switches, field)
+#define SW_NAME(x) "OSQP_AMD_" x
+constexpr double SW_INF = std::numeric_limits<double>::infinity(), SW_TINY = std::numeric_limits<double>::denorm_min();    // [SW_TINY, SW_INF]: v > 0
+static const SwRow SW_TABLE[] = {
+  // name                                  kind         field                         default  range      lo   hi         unset distinct
+  {SW_NAME("RESIDENT"),                    SW_FLAG,     SW(resident),                 1, 0,    SW_ANY,    0, 0,           false, "0: never a one-launch form (resident PCG, block-resident PCG, block-direct solve)"},
+  {SW_NAME("RESIDENT_MIN_N"),              SW_INT,      SW(resident_min_n),           256, 0,  SW_ANY,    0, 0,           false, "smallest n that takes the resident PCG"},
+  {SW_NAME("RESIDENT_ALL_CUS"),            SW_FLAG,     SW(resident_all_cus),         0, 0,    SW_ANY,    0, 0,           false, "1: a resident grid may take every CU (default: one per XCD stays free)"},
+  {SW_NAME("RESIDENT_NWG"),                SW_INT,      SW(resident_nwg),             0, 0,    SW_ANY,    0, 0,           false, "> 0: at least this many workgroups per resident launch, at most the plan's CUs (0: sized to the problem)"},
+  {SW_NAME("RESIDENT_BANKS"),              SW_FLAG,     SW(resident_banks),           1, 0,    SW_ANY,    0, 0,           false, "0: a thread's entries of K in row order instead of spread over the LDS bank pairs"},
+  {SW_NAME("RESIDENT_PIPE"),               SW_FLAG,     SW(resident_pipe),            1, 0,    SW_ANY,    0, 0,           false, "0: Chronopoulos-Gear recurrences only, never the pipelined ones"},
+  {SW_NAME("RESIDENT_PREDICT"),            SW_FLAG,     SW(resident_predict),         1, 0,    SW_ANY,    0, 0,           false, "0: no predicted last trip in the pipelined phase"},
+  {SW_NAME("RESIDENT_PREDICT_MARGIN"),     SW_DOUBLE,   SW(resident_predict_margin),  1.0, 0,  SW_IGNORE, SW_TINY, SW_INF, false, "last trip predicted at |r|^2 <= margin x tol^2; taken only if > 0"},
+  {SW_NAME("RESIDENT_INJECT"),             SW_INT,      SW(resident_inject),          0, 0,    SW_ANY,    0, 0,           false, "test hook: the resident launch of ADMM iteration k gives up"},
+  {SW_NAME("RESIDENT_U0"),                 SW_FLAG,     SW(resident_u0),              1, 0,    SW_ANY,    0, 0,           false, "0: exchange the first vector instead of reading it from memory"},
+  {SW_NAME("RESIDENT_FINE"),               SW_INT,      SW(resident_fine),            2, 0,    SW_ANY,    0, 0,           false, "polled words in uncached (2), fine-grained (1) or ordinary (0) device memory"},
+  {SW_NAME("RESIDENT_BLOCKS"),             SW_FLAG,     SW(resident_blocks),          1, 0,    SW_ANY,    0, 0,           false, "0: neither block form"},
+  {SW_NAME("INIT_RESIDENT_STORES"),        SW_FLAG,     SW(init_resident_stores),     1, 0,    SW_ANY,    0, 0,           false, "0: k_pcg_init of the resident graphs also stores r0 and u0 where the launch-per-step kernels want them"},
+  {SW_NAME("FORM_K_LISTS"),                SW_FLAG,     SW(form_k_lists),             1, 0,    SW_ANY,    0, 0,           false, "0: k_form_K (merge on the device) instead of k_form_K_lists"},
+  {SW_NAME("FORM_K_LIST_MB"),              SW_DOUBLE,   SW(form_k_list_mb),           128.0, 0, SW_CLAMP, 0.0, 1e6,       false, "budget of the contribution lists in MiB"},
+  {SW_NAME("SETUP_THREADS"),               SW_INT,      SW(setup_threads),            0, 0,    SW_CLAMP,  1, 64,          true,  "host threads of the resident set-up (unset: min(8, cores))"},
+  {SW_NAME("BLOCK_DIRECT"),                SW_FLAG,     SW(block_direct),             1, 0,    SW_ANY,    0, 0,           false, "0: the block-resident PCG instead of the block-direct solve"},
+  {SW_NAME("BLOCK_COUPLED_MAX"),           SW_INT,      SW(block_coupled_max),        CPL_MAX, 0, SW_CLAMP, 0, CPL_MAX,   false, "most coupling rows of A the block-direct solve carries as its low-rank term"},
+  {SW_NAME("BLOCK_FIN_DOTS"),              SW_FLAG,     SW(block_fin_dots),           1, 0,    SW_ANY,    0, 0,           false, "0: a k_huge_dot launch per iteration even where the block-direct kernels could leave the partials"},
+  {SW_NAME("BLOCK_PLAIN"),                 SW_FLAG,     SW(block_plain),              0, 0,    SW_ANY,    0, 0,           false, "1: block-direct solve on the right-hand side with the low-rank rows' terms split off"},
+  {SW_NAME("DENSE_P"),                     SW_FLAG,     SW(dense_p),                  1, 0,    SW_ANY,    0, 0,           false, "0: no kernel path of their own for dense diagonal blocks of P"},
+  {SW_NAME("DENSE_DIRECT"),                SW_INT,      SW(dense_direct),             1, 0,    SW_ANY,    0, 0,           false, "dense-direct solve: 0 never, 1 where it pays, 2 whenever it fits"},
+  {SW_NAME("DENSE_SMALL"),                 SW_INT,      SW(dense_small),              1024, 0, SW_CLAMP,  0, INT_MAX,     false, "most dense unknowns that take the dense-direct solve ahead of the resident PCG (0: none)"},
+  {SW_NAME("DENSE_SYMV"),                  SW_FLAG,     SW(dense_symv),               0, 0,    SW_ANY,    0, 0,           true,  "dense-direct solve from the inverse's lower tiles (1) or all its entries (0) (unset: tiles from 2048 unknowns up)"},
+  {SW_NAME("DENSE_ONE_GATHER"),            SW_FLAG,     SW(dense_one_gather),         1, 0,    SW_ANY,    0, 0,           false, "0: dense-direct engines gather vb and vx separately in k_pcg_init"},
+  {SW_NAME("DENSE_CHOL"),                  SW_FLAG,     SW(dense_chol),               0, 0,    SW_ANY,    0, 0,           true,  "1: blocked Cholesky inversion at once (unset: the caller's default -- 0 in an engine's refresh, 1 in hipeng_dense_invert_selftest)"},
+  {SW_NAME("DENSE_GEMM_LDS"),              SW_FLAG,     SW(dense_gemm_lds),           1, 0,    SW_ANY,    0, 0,           false, "0: the dense-direct GEMM kernel that feeds the MFMAs from global memory"},
+  {SW_NAME("ELIM"),                        SW_FLAG,     SW(elim),                     1, 0,    SW_ANY,    0, 0,           false, "0: no slack-like variable is eliminated from the linear system"},
+  {SW_NAME("HFOLD"),                       SW_FLAG,     SW(hfold),                    1, 0,    SW_ANY,    0, 0,           false, "0: huge rows of A finish their sums in k_huge_reduce instead of inside k_cg_B"},
+  {SW_NAME("SPLIT"),                       SW_FLAG,     SW(split),                    0, 0,    SW_ANY,    0, 0,           true,  "vector update and operator apply as two launches (unset: when most of A sits in long rows)"},
+  {SW_NAME("CHUNK"),                       SW_INT,      SW(chunk),                    0, 0,    SW_IGNORE, 64, MAX_CHUNK,  true,  "products per row block (unset or outside [64, 2048]: pick_chunk)"},
+  {SW_NAME("FIN_GRID"),                    SW_INT,      SW(fin_grid),                 0, 0,    SW_CLAMP,  1, INT_MAX,     true,  "workgroups of k_admm_finalize (unset: computed from the problem)"},
+  {SW_NAME("FUSED_CHECK"),                 SW_FLAG,     SW(fused_check),              1, 0,    SW_ANY,    0, 0,           false, "0: a window that ends in a check waits twice; prologue and resets one operation per field"},
+  {SW_NAME("EXTRAP"),                      SW_DOUBLE,   SW(extrap),                   1.0, 0,  SW_ANY,    0, 0,           false, "theta of the extrapolated PCG start (0: plain warm start)"},
+  {SW_NAME("EXTRAP_SCHED"),                SW_INT_PAIR, SW(extrap_sched),             5, 12,   SW_ANY,    0, 0,           false, "h0,h1: history lengths of the extrapolated start"},
+  {SW_NAME("KHEAD"),                       SW_INT,      SW(khead),                    1, 0,    SW_ANY,    0, 0,           false, "unrolled PCG slots beyond the last window's maximum"},
+  {SW_NAME("GRAPH_SEGS"),                  SW_INT,      SW(graph_segs),               5, 0,    SW_CLAMP,  1, 32,          false, "ADMM iterations captured per hipGraph"},
+  {SW_NAME("TRACE"),                       SW_INT,      SW(trace),                    0, 0,    SW_CLAMP,  1, INT_MAX,     false, "set: 1 = one line per window, 2 = every HIP call of the run loop"},
+  {SW_NAME("TRACE_MAPS"),                  SW_TEXT,     SW(trace_maps),               0, 0,    SW_ANY,    0, 0,           false, "with TRACE >= 2: file that receives /proc/self/maps once per process"},
+};
+#undef SW_NAME
+#undef SW
+constexpr int SW_COUNT = (int)(sizeof(SW_TABLE) / sizeof(SW_TABLE[0]));
+static Switches read_switches() {
+  Switches sw{};
+  for (const SwRow &r : SW_TABLE) {
+    char *at = reinterpret_cast<char *>(&sw) + r.field;
+    int *iv = reinterpret_cast<int *>(at);
+    double *dv = reinterpret_cast<double *>(at);
+    const char *x = getenv(r.name);
+    if (r.kind == SW_TEXT) { if (x) snprintf(at, PATH_MAX, "%s", x); continue; }
+    if (r.kind == SW_INT_PAIR) { iv[0] = (int)r.def; iv[1] = (int)r.def2; if (x) sscanf(x, "%d,%d", &iv[0], &iv[1]); continue; }
+    if (r.kind == SW_DOUBLE) {
+      double v = x ? atof(x) : r.def;
+      if (x && r.range == SW_CLAMP) v = std::max(r.lo, std::min(r.hi, v));
+      if (x && r.range == SW_IGNORE && !(v >= r.lo && v <= r.hi)) v = r.def;
+      *dv = v;
+      continue;
+    }
+    const int unset = r.unset_distinct ? SW_UNSET : (int)r.def;
+    int v = unset;
+    if (x) {
+      v = r.kind == SW_FLAG ? atoi(x) != 0 : atoi(x);
+      if (r.range == SW_CLAMP) v = std::max((int)r.lo, std::min((int)r.hi, v));
+      if (r.range == SW_IGNORE && (v < (int)r.lo || v > (int)r.hi)) v = unset;
+    }
+    *iv = v;
+  }
+  return sw;
+}
+
 // How an engine solves the linear system of an ADMM iteration (the values are hipeng_resident_info [9]): launch-per-step PCG kernels only,
 // k_pcg_resident, k_pcg_blockres, block-direct solve (k_blk_apply / k_blk_finish), dense-direct solve (dense_direct.h)
 enum SolveForm : int { FORM_STEPS = 0, FORM_RESIDENT = 1, FORM_BLOCKRES = 2, FORM_BLOCK_DIRECT = 3, FORM_DENSE_DIRECT = 4 };
 struct hipeng {
+  Switches sw = read_switches();       // the environment as it was when this engine was made
   int device = 0;
   int n = 0, m = 0;
   hipStream_t stream = nullptr;
@@ -3057,11 +3158,9 @@ struct hipeng {
   long long admm_total = 0;            // host copy of State::admm_done
   State *h_state = nullptr;            // pinned staging for the state read-back and the target upload
   long long *h_target = nullptr;
-  // OSQP_AMD_FUSED_CHECK (default 1): a window that ends in a check enqueues the residual pass behind its graphs and waits once
+  // sw.fused_check (default 1): a window that ends in a check enqueues the residual pass behind its graphs and waits once
   // (hipeng_run_admm_check); the window's prologue, hipeng_cold_start and reset_start are one launch each.  0: one operation per field / array.
-  bool fused_check = true;
   double *h_check = nullptr;           // pinned: the scalars' lines followed by State, as they lie on the device (one D2H copy)
-  int trace = 0;            // OSQP_AMD_TRACE: 1 = one line per window, 2 = every HIP call of the run loop
   hipeng_stats stats{};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   long long admm_done_seen = 0;
@@ -3128,7 +3227,7 @@ static int dev_alloc(hipeng *e, T **p, size_t count) {
 // OSQP_AMD_RESIDENT_FINE=1: fine-grained (coherent) but cacheable; =0: like everything else.
 template <typename T>
 static int dev_alloc_polled(hipeng *e, T **p, size_t count) {
-  static const int fine = getenv("OSQP_AMD_RESIDENT_FINE") ? atoi(getenv("OSQP_AMD_RESIDENT_FINE")) : 2;
+  const int fine = e->sw.resident_fine;
   if (!fine) return dev_alloc(e, p, count);
   void *q = nullptr;
   if (count == 0) count = 1;
@@ -3166,14 +3265,13 @@ static void build_blocks(HostMat &H, int chunk, bool huge_ok, const std::vector<
   H.blk.insert(H.blk.end(), huges.begin(), huges.end());
 }
 
-static int pick_chunk(long long nnz, int nrows) {
+static int pick_chunk(const Switches &sw, long long nnz) {
   // about one to two workgroups per CU on small problems (every workgroup of a
   // consumer kernel re-reduces one dot partial per producer workgroup, so the
   // grid is kept near the CU count), full 2048-product chunks on large ones
   int chunk = 256;
   while (chunk < MAX_CHUNK && nnz / chunk > 640) chunk <<= 1;
-  (void)nrows;
-  if (const char *x = getenv("OSQP_AMD_CHUNK")) { const int v = atoi(x); if (v >= 64 && v <= MAX_CHUNK) chunk = v; }   // tuning experiments
+  if (sw.chunk != SW_UNSET) chunk = sw.chunk;   // tuning experiments
   return chunk;
 }
 
@@ -3228,7 +3326,7 @@ static void build_A(hipeng *e, const csc *A) {
       H.col[dst] = j; H.val[dst] = A->x[k];
       e->A_csc2csr[k] = dst;
     }
-  build_blocks(H, pick_chunk(nnz, m), true);     // k_cg_A slices huge rows over the grid
+  build_blocks(H, pick_chunk(e->sw, nnz), true);     // k_cg_A slices huge rows over the grid
 }
 
 // Fused row matrix M = [P_full | A'] with the reference's summation order.
@@ -3272,7 +3370,7 @@ static void build_M(hipeng *e, const csc *P, const csc *A) {
       H.col[d] = n + (int)A->i[k]; H.val[d] = A->x[k]; e->A_toM[k] = d;
     }
   }
-  build_blocks(H, pick_chunk(tot, n), false);    // rows of M need their full sum inside k_cg_B
+  build_blocks(H, pick_chunk(e->sw, tot), false);    // rows of M need their full sum inside k_cg_B
 }
 
 // Dense diagonal blocks of P (BASELINE config 5: block-diagonal covariance).  Column j
@@ -3286,7 +3384,7 @@ static void build_dense(hipeng *e, const csc *P) {
   std::vector<char> dense(n, 0);
   const HostMat &M = e->M;
   long long off = 0;
-  if (const char *v = getenv("OSQP_AMD_DENSE_P")) if (atoi(v) == 0) goto build_remainder;
+  if (!e->sw.dense_p) goto build_remainder;
   {
   std::vector<int> lo(n), smin(n + 1, n);
   for (int j = 0; j < n; j++) {
@@ -3315,7 +3413,7 @@ build_remainder:
   e->hrows.clear();
   for (int q = e->A.nwave; q < (int)e->A.blk.size(); q++) e->hrows.push_back(e->A.blk[q].r0);
   if ((int)e->hrows.size() > MAX_HUGE_FOLD) e->hrows.clear();        // many huge rows: keep the k_huge_reduce path
-  if (const char *v = getenv("OSQP_AMD_HFOLD")) if (atoi(v) == 0) e->hrows.clear();   // tuning experiments
+  if (!e->sw.hfold) e->hrows.clear();   // tuning experiments
   if (e->dP_blks.empty() && e->hrows.empty()) return;
   std::vector<int> hidx(e->m > 0 ? e->m : 1, -1);
   for (size_t k = 0; k < e->hrows.size(); k++) hidx[e->hrows[k]] = (int)k;
@@ -3336,7 +3434,7 @@ build_remainder:
     }
     R.rowptr[i + 1] = (int)R.col.size();
   }
-  build_blocks(R, pick_chunk(std::max(1, R.rowptr[n]), n), false, e->dP_blks.empty() ? nullptr : &dense);
+  build_blocks(R, pick_chunk(e->sw, std::max(1, R.rowptr[n])), false, e->dP_blks.empty() ? nullptr : &dense);
 }
 
 // refresh the dense rows and the remainder matrix from the values of M (device side)
@@ -3420,9 +3518,8 @@ static void launch_resident(hipeng *e) {
 
 // Host-side set-up work of the resident PCG (symbolic K, register layout) is independent per row / per workgroup: a few threads.
 template <class F>
-static void parallel_chunks(int count, int min_chunk, F fn) {
-  int T = (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency()));
-  if (const char *x = getenv("OSQP_AMD_SETUP_THREADS")) T = std::max(1, std::min(64, atoi(x)));
+static void parallel_chunks(const Switches &sw, int count, int min_chunk, F fn) {
+  int T = sw.setup_threads != SW_UNSET ? sw.setup_threads : (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency()));
   T = std::min(T, std::max(1, count / min_chunk));
   if (T <= 1) { fn(0, count, 0, 1); return; }
   std::vector<std::thread> th;
@@ -3431,7 +3528,7 @@ static void parallel_chunks(int count, int min_chunk, F fn) {
 }
 
 // Returns 0 (with e->form = FORM_RESIDENT when the problem qualifies) or a HIPENG error.  Not qualifying is not an error.
-#define RES_NO(why) do { if (e->trace) fprintf(stderr, "[osqp_amd] resident PCG not used: %s\n", why); return 0; } while (0)
+#define RES_NO(why) do { if (e->sw.trace) fprintf(stderr, "[osqp_amd] resident PCG not used: %s\n", why); return 0; } while (0)
 // What build_resident works out on the host before anything is uploaded (hipeng_resident_plan hands it to the CPU tests).
 struct ResPlanOut {
   bool ok = false; int nwg = 0, E = 0, npad = 0; long long nnzK = 0;
@@ -3440,11 +3537,8 @@ struct ResPlanOut {
 };
 static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr) {
   const int n = e->n;       // (called on an engine that is still FORM_STEPS)
-  int want = 1, min_n = 256;
-  if (const char *x = getenv("OSQP_AMD_RESIDENT")) want = atoi(x);
-  if (const char *x = getenv("OSQP_AMD_RESIDENT_MIN_N")) min_n = atoi(x);
-  if (!want) RES_NO("OSQP_AMD_RESIDENT=0");
-  if (n < min_n || n > RES_MAXN) RES_NO("n outside [OSQP_AMD_RESIDENT_MIN_N, 15616]");
+  if (!e->sw.resident) RES_NO("OSQP_AMD_RESIDENT=0");
+  if (n < e->sw.resident_min_n || n > RES_MAXN) RES_NO("n outside [OSQP_AMD_RESIDENT_MIN_N, 15616]");
   if (!e->hrows.empty() || e->A.nwave < (int)e->A.blk.size()) RES_NO("A has rows of 8192 or more entries");   // (their outer products alone overflow the register files)
   int nwg = plan_nwg < 0 ? -plan_nwg : plan_nwg;      // (plan mode: nwg > 0 keeps that grid, nwg < 0 sizes the grid for a machine of -nwg CUs)
   const bool fixed_grid = po && plan_nwg > 0;
@@ -3456,7 +3550,7 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
     // about once per 20-30 s of 256-workgroup launches and never with a smaller grid -- the time it takes to save and
     // restore an XCD's 32 x 570 KB of registers and LDS.  (Round 2's 1 ms wait limit turned each of them into a give-up.)
     nwg = std::min(256, prop.multiProcessorCount) - 8;
-    if (const char *x = getenv("OSQP_AMD_RESIDENT_ALL_CUS")) if (atoi(x)) nwg += 8;
+    if (e->sw.resident_all_cus) nwg += 8;
     e->res_cus = nwg;
     if (prop.sharedMemPerBlock < 64 * 1024) RES_NO("too little LDS");
   }
@@ -3473,10 +3567,9 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
   // of entries of a row of A is one term: sum_k nnz(A_k)^2 of them, known before the pass, so that the budget
   // (OSQP_AMD_FORM_K_LIST_MB, 8 bytes per term + 4 per entry of K) decides the same for any number of threads.
   std::vector<int> Kcp, Kcm, Kca;
-  long long fk_terms = 0, fk_budget = 128LL << 20;
-  bool fk_lists = true;
-  if (const char *x = getenv("OSQP_AMD_FORM_K_LISTS")) fk_lists = atoi(x) != 0;
-  if (const char *x = getenv("OSQP_AMD_FORM_K_LIST_MB")) fk_budget = (long long)std::max(0.0, std::min(1e6, atof(x))) << 20;
+  long long fk_terms = 0;
+  const long long fk_budget = (long long)e->sw.form_k_list_mb << 20;
+  bool fk_lists = e->sw.form_k_lists != 0;
   for (int k = 0; k < e->m; k++) { const long long len = A.rowptr[k + 1] - A.rowptr[k]; fk_terms += len * len; }
   auto fk_bytes = [&](long long entries) { return 8 * fk_terms + 4 * (entries + 1); };
   if (fk_terms > 0x7fffffffLL || fk_bytes(n) > fk_budget) fk_lists = false;      // (K has n entries at least: the diagonal)
@@ -3485,7 +3578,7 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
     std::vector<std::vector<int>> cKcol(64), cKps(64), cLen(64), cCnt(64), cCm(64), cCa(64);
     std::atomic<int> bad{0};
     int used = 1;
-    parallel_chunks(n, 256, [&](int lo, int hi, int tid, int T) {
+    parallel_chunks(e->sw, n, 256, [&](int lo, int hi, int tid, int T) {
       if (tid == 0) used = T;
       std::vector<int> mark(n, -1), pslot(n, -1);
       std::vector<int> &kc = cKcol[tid], &kp = cKps[tid], &ln = cLen[tid], &cn = cCnt[tid], &cm = cCm[tid], &ca = cCa[tid];
@@ -3578,8 +3671,7 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
   if (packs(std::max<long long>(nnzK, 1)) > nwg_max) RES_NO("more than 61 rows per workgroup");
   int E = 0;
   long long C = 0;
-  int force_nwg = 0;
-  if (const char *x = getenv("OSQP_AMD_RESIDENT_NWG")) force_nwg = std::max(0, std::min(nwg_max, atoi(x)));
+  const int force_nwg = std::max(0, std::min(nwg_max, e->sw.resident_nwg));
   for (int cand : RES_E_LIST) {
     const long long cap = (long long)cand * RES_PT;
     if (cap < maxrow) continue;
@@ -3622,14 +3714,13 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
   }
   if (npad > RES_MAXPAD) RES_NO("the exchanged vector (rows padded to whole lines) exceeds 16384 doubles");
   const size_t slots = (size_t)nwg * E * RES_PT;
-  bool bank_sched = true;
-  if (const char *x = getenv("OSQP_AMD_RESIDENT_BANKS")) bank_sched = atoi(x) != 0;
+  const bool bank_sched = e->sw.resident_banks != 0;
   std::vector<unsigned short> col(slots, 0), slot0((size_t)nwg * RES_PT, 0), segrow((size_t)nwg * (RES_MAXROWS + 1), 0);
   std::vector<unsigned char> rowl(slots, 0);
   std::vector<int> kdst((size_t)nnzK, 0);
   std::vector<unsigned long long> brk((size_t)nwg * RES_PT, 0ull);
   std::atomic<int> seg_over{0};
-  parallel_chunks(nwg, 4, [&](int g_lo, int g_hi, int, int) {        // workgroups write disjoint parts of every array
+  parallel_chunks(e->sw, nwg, 4, [&](int g_lo, int g_hi, int, int) {        // workgroups write disjoint parts of every array
   for (int g = g_lo; g < g_hi; g++) {
     const ResWG &w = wg[g];
     if (w.nr == 0) continue;
@@ -3694,15 +3785,10 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
   ResCtx rc{};
   rc.nwg = nwg; rc.E = E; rc.npad = npad;
   rc.npw = (nwg + 63) / 64;
-  rc.pipe = 1;
-  if (const char *x = getenv("OSQP_AMD_RESIDENT_PIPE")) rc.pipe = atoi(x) != 0;
-  rc.predict = 1; rc.pred_margin = 1.0;
-  if (const char *x = getenv("OSQP_AMD_RESIDENT_PREDICT")) rc.predict = atoi(x) != 0;
-  if (const char *x = getenv("OSQP_AMD_RESIDENT_PREDICT_MARGIN")) { const double v = atof(x); if (v > 0.0) rc.pred_margin = v; }
-  rc.u0_direct = 1;
-  rc.inject = 0;
-  if (const char *x = getenv("OSQP_AMD_RESIDENT_INJECT")) rc.inject = atoi(x);
-  if (const char *x = getenv("OSQP_AMD_RESIDENT_U0")) rc.u0_direct = atoi(x) != 0;
+  rc.pipe = e->sw.resident_pipe;
+  rc.predict = e->sw.resident_predict; rc.pred_margin = e->sw.resident_predict_margin;
+  rc.u0_direct = e->sw.resident_u0;
+  rc.inject = e->sw.resident_inject;
   unsigned short *d_rowpos = nullptr;
   std::vector<int> ppos(wg.size());
   for (size_t o = 0; o < wg.size(); o++) ppos[o] = wg[o].pos + wg[o].nr;
@@ -3730,10 +3816,8 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
     if (dev_alloc(e, &d_u0pos, (size_t)rc.npad)) return HIPENG_ERR_HIP;       // (zeroed: the padding positions are read, never written)
     e->c.u0map = d_rowpos; e->c.u0pos = d_u0pos;
     // OSQP_AMD_INIT_RESIDENT_STORES (default 1): k_pcg_init of the resident graphs stores r0 beside u0 in this layout and nothing else
-    bool rform = true;
-    if (const char *x = getenv("OSQP_AMD_INIT_RESIDENT_STORES")) rform = atoi(x) != 0;
     rc.r0pos = nullptr;
-    if (rform && dev_alloc(e, &rc.r0pos, (size_t)rc.npad)) return HIPENG_ERR_HIP;
+    if (e->sw.init_resident_stores && dev_alloc(e, &rc.r0pos, (size_t)rc.npad)) return HIPENG_ERR_HIP;
   }
   rc.wg = d_wg; rc.ppos = d_ppos; rc.rowpos = d_rowpos; rc.col = d_col; rc.rowl = d_rowl; rc.krp = d_krp; rc.kcj = d_kcj; rc.kps = d_kps; rc.kdst = d_kdst; rc.brk = d_brk; rc.slot0 = d_slot0; rc.segrow = d_segrow;
   e->rc = rc;
@@ -3748,7 +3832,7 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
   if (rcode) RES_NO("the launch's LDS request was refused");
   e->res_nnz = nnzK;
   e->form = FORM_RESIDENT; e->res_use = true;
-  if (e->trace) {
+  if (e->sw.trace) {
     const auto tb3 = std::chrono::steady_clock::now();
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     fprintf(stderr, "[osqp_amd] resident PCG: nnz(K)=%lld, %d workgroups x %d threads x %d entries, %zu B LDS; host: pattern %.0f ms, layout %.0f ms, upload %.0f ms\n",
@@ -3778,18 +3862,13 @@ static bool blocks_coupled_eligible(hipeng *e, std::vector<int> &rows) {
   int next = 0;
   for (const DenseBlk &d : e->dP_blks) { if (d.c0 != next || d.b > DENSE_MAX) return false; next += d.b; }
   if (next != e->n) return false;
-  int cap = CPL_MAX;
-  if (const char *x = getenv("OSQP_AMD_BLOCK_COUPLED_MAX")) cap = std::max(0, std::min(CPL_MAX, atoi(x)));
+  const int cap = e->sw.block_coupled_max;
   rows.clear();
   for (int i = 0; i < e->m; i++) if (e->A.rowptr[i + 1] - e->A.rowptr[i] >= 2) { if ((int)rows.size() >= cap) return false; rows.push_back(i); }
   return !rows.empty();
 }
 static int build_blockdirect(hipeng *e) {
-  int want = 1;
-  if (const char *x = getenv("OSQP_AMD_RESIDENT")) want = atoi(x);
-  if (const char *x = getenv("OSQP_AMD_RESIDENT_BLOCKS")) want = want && atoi(x);
-  if (const char *x = getenv("OSQP_AMD_BLOCK_DIRECT")) want = want && atoi(x);
-  if (!want) return 0;
+  if (!e->sw.resident || !e->sw.resident_blocks || !e->sw.block_direct) return 0;
   std::vector<int> crows;
   const bool plain = blocks_eligible(e);
   if (!plain && !blocks_coupled_eligible(e, crows)) return 0;
@@ -3835,15 +3914,14 @@ static int build_blockdirect(hipeng *e) {
     // huge row folded, and that kernel's grid within the gridA partial slots k_admm_finalize sums
     const int fin_grid = bd.kc ? std::max(1, std::min(1024, (int)nb)) : std::max(1, std::min(256, (e->n + TB - 1) / TB));
     bd.fin_dots = !e->hrows.empty() && (int)e->A.blk.size() - e->A.nwave == (int)e->hrows.size() && fin_grid <= e->c.gridA;
-    if (const char *x = getenv("OSQP_AMD_BLOCK_FIN_DOTS")) bd.fin_dots = bd.fin_dots && atoi(x) != 0;
+    bd.fin_dots = bd.fin_dots && e->sw.block_fin_dots;
   }
   {
     // Opt-in (OSQP_AMD_BLOCK_PLAIN=1), not the default: exact algebra, 46 -> 37 us per ADMM iteration at config 5, and x~ as accurate
     // entry by entry -- but a' x~ = a' t0 - c a' W is then a difference of two numbers of size 1e4: 1e-12 of noise in the budget row's
     // constraint value, times rho_h in y_h (1e-10), which moves the dual residual norm by 1e-7 relative, the next rho estimate with
     // it, and the trajectory by 1e-7: config 5's golden objective is then off by 2.4e-6 (bar 1e-6).  tools/plain_check.py.
-    int plain = 0;
-    if (const char *x = getenv("OSQP_AMD_BLOCK_PLAIN")) plain = atoi(x) != 0;
+    const int plain = e->sw.block_plain;
     e->c.plain_rhs = plain;
     e->c.plain_skip = (plain && bd.kc) ? bd.cidx : nullptr;
   }
@@ -3852,13 +3930,13 @@ static int build_blockdirect(hipeng *e) {
   e->dd_init_r = e->c.init_r; e->dd_init_stride = e->c.init_stride;       // (what the launch-per-step kernels use: direct_disable puts them back)
   e->c.init_r = e->c.r; e->c.init_stride = 1;
   e->form = FORM_BLOCK_DIRECT; e->res_use = true;
-  if (e->trace) fprintf(stderr, "[osqp_amd] block-direct solve: %zu dense blocks inverted explicitly, %d %s of A as a Woodbury term\n", nb,
+  if (e->sw.trace) fprintf(stderr, "[osqp_amd] block-direct solve: %zu dense blocks inverted explicitly, %d %s of A as a Woodbury term\n", nb,
                         bd.kc ? bd.kc : (int)e->hrows.size(), bd.kc ? "coupling rows" : "huge rows");
   return 0;
 }
 // A direct form whose fresh inverse cannot be trusted leaves: this engine goes on with the launch-per-step PCG kernels for good.
 static void direct_disable(hipeng *e, const char *what, const char *why, double err) {
-  if (e->trace) fprintf(stderr, "[osqp_amd] %s solve dropped (%s, check %.2e): the PCG kernels take over\n", what, why, err);
+  if (e->sw.trace) fprintf(stderr, "[osqp_amd] %s solve dropped (%s, check %.2e): the PCG kernels take over\n", what, why, err);
   for (auto &g : e->graphs) (void)hipGraphExecDestroy(g.second);      // (they hold the Ctx by value)
   e->graphs.clear();
   e->c.init_r = e->dd_init_r; e->c.init_stride = e->dd_init_stride; e->c.fin_wave_rows = 0; e->c.plain_rhs = 0; e->c.plain_skip = nullptr; e->c.vd = nullptr;
@@ -3876,7 +3954,7 @@ static int blk_check(hipeng *e) {
   HIPCHK(hipMemcpyAsync(&flag, e->bd.flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   e->dd_check = std::max(chk[0], chk[1]);
-  if (e->trace) fprintf(stderr, "[osqp_amd] block-direct refresh: inverse blocks off by %.2e, capacitance inverse by %.2e (probe vector of size 1..2)\n", chk[0], chk[1]);
+  if (e->sw.trace) fprintf(stderr, "[osqp_amd] block-direct refresh: inverse blocks off by %.2e, capacitance inverse by %.2e (probe vector of size 1..2)\n", chk[0], chk[1]);
   if (!flag && !(e->dd_check <= BLK_CHECK)) direct_disable(e, "block-direct", chk[0] > BLK_CHECK ? "the inverse blocks failed their check" : "the capacitance inverse failed its check", e->dd_check);
   return 0;
 }
@@ -3942,10 +4020,7 @@ static int blk_refresh(hipeng *e) {
 // Block-resident form (k_pcg_blockres): P = dense diagonal blocks only, rows of A single-entry or folded huge rows.
 static int build_blockres(hipeng *e) {
   const int n = e->n;
-  int want = 1;
-  if (const char *x = getenv("OSQP_AMD_RESIDENT")) want = atoi(x);
-  if (const char *x = getenv("OSQP_AMD_RESIDENT_BLOCKS")) want = want && atoi(x);
-  if (!want || e->dP_blks.empty()) return 0;
+  if (!e->sw.resident || !e->sw.resident_blocks || e->dP_blks.empty()) return 0;
   // the blocks tile 0..n
   int next = 0;
   for (const DenseBlk &d : e->dP_blks) { if (d.c0 != next || d.b > DENSE_MAX) return 0; next += d.b; }
@@ -3983,7 +4058,7 @@ static int build_blockres(hipeng *e) {
   bc.blk0 = d_blk0;
   e->bc = bc;
   e->form = FORM_BLOCKRES; e->res_use = true;
-  if (e->trace) fprintf(stderr, "[osqp_amd] block-resident PCG: %d dense blocks over %d workgroups, %d huge rows of A as rank-one terms\n", nb, nwg, (int)e->hrows.size());
+  if (e->sw.trace) fprintf(stderr, "[osqp_amd] block-resident PCG: %d dense blocks over %d workgroups, %d huge rows of A as rank-one terms\n", nb, nwg, (int)e->hrows.size());
   return 0;
 }
 
@@ -4009,7 +4084,7 @@ static void refresh_operator(hipeng *e) {
 // The PCG start vector history is void (cold/warm start from the host, new rho, new matrices):
 // start from [x~ | rho z~] as it stands and extrapolate again once a few iterations are on record.
 static int reset_start(hipeng *e) {
-  if (e->c.vx != e->c.va && e->fused_check && e->n + e->m > 0) {      // (both copies and the count in one launch)
+  if (e->c.vx != e->c.va && e->sw.fused_check && e->n + e->m > 0) {      // (both copies and the count in one launch)
     hipLaunchKernelGGL(k_start_reset, dim3(elem_grid(e->n + e->m)), dim3(TB), 0, e->stream, e->c, e->n + e->m);
     HIPCHK(hipGetLastError());
     return 0;
@@ -4045,7 +4120,7 @@ static int build_elim(hipeng *e, const csc *P, const csc *A) {
   Ctx &c = e->c;
   c.nelim = 0; c.erow = c.ecol = c.epos = nullptr; c.rhoe = c.rho; c.ecoef = c.edinv = c.xte = nullptr;
   const int n = e->n, m = e->m;
-  if (const char *x = getenv("OSQP_AMD_ELIM")) if (!atoi(x)) return 0;
+  if (!e->sw.elim) return 0;
   if (e->form == FORM_BLOCKRES || e->form == FORM_BLOCK_DIRECT || m == 0 || n == 0) return 0;      // (the block forms of the portfolio family hold their own operator; the other forms are built after this)
   std::vector<char> coupled(n, 0);
   for (int j = 0; j < n; j++)
@@ -4070,7 +4145,7 @@ static int build_elim(hipeng *e, const csc *P, const csc *A) {
   HIPCHK(hipStreamSynchronize(e->stream));
   c.erow = d_erow; c.ecol = d_ecol; c.epos = d_epos; c.nelim = cnt;
   e->erow = erow; e->ecol = ecol; e->epos = epos;
-  if (e->trace) fprintf(stderr, "[osqp_amd] %d of %d variables eliminated from the linear system (one row of A each, no coupling in P)\n", cnt, n);
+  if (e->sw.trace) fprintf(stderr, "[osqp_amd] %d of %d variables eliminated from the linear system (one row of A each, no coupling in P)\n", cnt, n);
   return 0;
 }
 
@@ -4115,7 +4190,7 @@ extern "C" int hipeng_create(hipeng **out, const csc *P, const csc *A, const c_f
     for (size_t q = (size_t)e->A.nstream; q < (size_t)e->A.nwave; q++) lnnz += e->A.blk[q].k1 - e->A.blk[q].k0;
     e->split = 2 * lnnz >= (long long)e->A.val.size() && !e->A.val.empty();
   }
-  if (const char *sp = getenv("OSQP_AMD_SPLIT")) e->split = atoi(sp) != 0;
+  if (e->sw.split != SW_UNSET) e->split = e->sw.split != 0;
   if (upload_mat(e, e->A) || upload_mat(e, e->M)) return HIPENG_ERR_HIP;
   Ctx &c = e->c;
   c.n = n; c.m = m;
@@ -4139,9 +4214,6 @@ extern "C" int hipeng_create(hipeng **out, const csc *P, const csc *A, const c_f
     c.nh = (int)e->hrows.size(); c.hcol = e->d_hcol;
     for (int k = 0; k < MAX_HUGE_FOLD; k++) c.hrow[k] = k < c.nh ? e->hrows[k] : 0;
     if (repack_dense(e)) return HIPENG_ERR_HIP;
-  }
-  {
-    if (const char *t = getenv("OSQP_AMD_TRACE")) e->trace = std::max(1, atoi(t));
   }
   const int cap = MAX_PARTS;
   c.gridM = std::min(cap, std::max(1, c.M.nblk));
@@ -4171,7 +4243,6 @@ extern "C" int hipeng_create(hipeng **out, const csc *P, const csc *A, const c_f
     HIPCHK(hipHostMalloc((void **)&e->h_state, sizeof(State), hipHostMallocDefault));
     HIPCHK(hipHostMalloc((void **)&e->h_target, sizeof(long long), hipHostMallocDefault));
     HIPCHK(hipHostMalloc((void **)&e->h_check, SC_COUNT * 16 * sizeof(double) + sizeof(State), hipHostMallocDefault));
-    if (const char *x = getenv("OSQP_AMD_FUSED_CHECK")) e->fused_check = atoi(x) != 0;
   }
   if (dev_alloc(e, &e->d_prm, 1)) return HIPENG_ERR_HIP;
   c.prm = e->d_prm;
@@ -4179,9 +4250,7 @@ extern "C" int hipeng_create(hipeng **out, const csc *P, const csc *A, const c_f
   e->prm.eps_rel = prm->pcg_eps_rel; e->prm.eps_abs = prm->pcg_eps_abs;
   e->prm.pcg_max_iter = (int)prm->pcg_max_iter; e->prm.cinv = 1.0;
   e->prm.use_cvec = 0; e->prm.has_scaling = 0; e->prm.pad0 = 0;
-  e->prm.ex_theta = 1.0; e->prm.ex_h0 = 5; e->prm.ex_h1 = 12; e->prm.no_restart = 0;
-  if (const char *x = getenv("OSQP_AMD_EXTRAP_SCHED")) sscanf(x, "%d,%d", &e->prm.ex_h0, &e->prm.ex_h1);
-  if (const char *x = getenv("OSQP_AMD_EXTRAP")) e->prm.ex_theta = atof(x);
+  e->prm.ex_theta = e->sw.extrap; e->prm.ex_h0 = e->sw.extrap_sched[0]; e->prm.ex_h1 = e->sw.extrap_sched[1]; e->prm.no_restart = 0;
   if (e->prm.ex_theta == 0.0) c.vx = c.va;   // plain warm start
   e->ex_theta0 = e->prm.ex_theta;
   if (prm->pcg_eps_rel < 0.5e-12) e->prm.ex_theta = 0.0;
@@ -4395,7 +4464,7 @@ extern "C" int hipeng_cold_start(hipeng *e) {
   if (!e) return HIPENG_ERR_ARG;
   HIPCHK(hipSetDevice(e->device));
   const size_t nm = (size_t)(e->n + e->m) * sizeof(double);
-  if (e->fused_check) {
+  if (e->sw.fused_check) {
     const int cnm = std::max(1, e->n + e->m), cm = std::max(1, e->m);
     FillRanges f{{e->c.xy, e->c.va, e->c.vb, e->c.z, e->c.zt, e->c.nelim ? e->c.xte : nullptr}, {cnm, cnm, cnm, cm, cm, e->c.nelim ? e->m : 0}};
     hipLaunchKernelGGL(k_fill_ranges, dim3(elem_grid(cnm)), dim3(TB), 0, e->stream, f);
@@ -4450,7 +4519,7 @@ extern "C" int hipeng_set_z(hipeng *e, const c_float *z) {
 }
 
 // ---- graphs ---------------------------------------------------------------
-#define TR2(e, ...) do { if ((e)->trace >= 2) { fprintf(stderr, "[osqp_amd:t2] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
+#define TR2(e, ...) do { if ((e)->sw.trace >= 2) { fprintf(stderr, "[osqp_amd:t2] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
 // for_resident: the launch that follows is k_pcg_resident and nothing else reads r0 and u0 before the next k_pcg_init (the K == 0
 // graphs of a FORM_RESIDENT engine, and the timing hook of that pair).  Every other caller gets the default form: a launch-per-step
 // graph that takes over after a launch gave up starts with its own k_pcg_init (k_admm_finalize leaves the iteration untouched then).
@@ -4513,7 +4582,7 @@ static int get_graph(hipeng *e, int K, int R, int spec_lo, hipGraphExec_t *out) 
       // a row is a chain of dependent round trips (the dot, then the row's own scalars), and at gridA <= 1024 each wavefront walked three
       int fg = e->c.gridA;
       if (e->c.fin_wave_rows) fg = std::max(fg, std::min(4096, (e->c.A.nwave - e->c.A.nstream + 3) / 4 + 1));
-      if (const char *x = getenv("OSQP_AMD_FIN_GRID")) fg = std::max(1, atoi(x));
+      if (e->sw.fin_grid != SW_UNSET) fg = e->sw.fin_grid;
       hipLaunchKernelGGL(k_admm_finalize, dim3(fg), dim3(TB), 0, e->stream, e->c);
     }
   }
@@ -4615,8 +4684,8 @@ static int run_admm(hipeng *e, c_int count, hipeng_scalars *early, int *have) {
   if (!e || count < 0) return HIPENG_ERR_ARG;
   HIPCHK(hipSetDevice(e->device));
   State s;
-  if (e->trace >= 2) {
-    if (const char *mp = getenv("OSQP_AMD_TRACE_MAPS")) {     // address map, to read a crash stack
+  if (e->sw.trace >= 2) {
+    if (const char *mp = e->sw.trace_maps[0] ? e->sw.trace_maps : nullptr) {     // address map, to read a crash stack
       static bool dumped = false;
       if (!dumped) {
         dumped = true;
@@ -4640,7 +4709,7 @@ static int run_admm(hipeng *e, c_int count, hipeng_scalars *early, int *have) {
   if (!e->res_use && e->resident_available()) e->res_use = true;
   bool had_fail = false;
   const long long start = e->admm_total, target = start + (long long)count;
-  if (e->fused_check) {
+  if (e->sw.fused_check) {
     hipLaunchKernelGGL(k_window_begin, dim3(1), dim3(64), 0, e->stream, e->c.st, target);      // (the three fields in one launch)
   } else {
     *e->h_target = target;
@@ -4651,10 +4720,10 @@ static int run_admm(hipeng *e, c_int count, hipeng_scalars *early, int *have) {
   if (e->start_dirty) { if (reset_start(e)) return HIPENG_ERR_HIP; e->start_dirty = false; }
   long long remaining = count;
   const int cap = std::max(2, e->prm.pcg_max_iter);
-  static const int khead = getenv("OSQP_AMD_KHEAD") ? atoi(getenv("OSQP_AMD_KHEAD")) : 1;   // unrolled iterations beyond the last window's maximum
+  const int khead = e->sw.khead;   // unrolled iterations beyond the last window's maximum
   int guard = 0, call_max = 0;
   s.admm_done = start; s.iters_last = 0; s.iters_total = 0; s.forced = 0; s.neg_curv_seen = 0;
-  static const int segs = getenv("OSQP_AMD_GRAPH_SEGS") ? std::max(1, std::min(32, atoi(getenv("OSQP_AMD_GRAPH_SEGS")))) : 5;
+  const int segs = e->sw.graph_segs;
   while (remaining > 0) {
     // after a reset (cold start, new rho, new matrices) the PCG iteration count jumps: two
     // iterations to see where it lands, then whole windows
@@ -4679,7 +4748,7 @@ static int run_admm(hipeng *e, c_int count, hipeng_scalars *early, int *have) {
     // A window that should be the call's last carries the residual pass behind its graphs: scalars and State come back in one
     // copy, after one wait.  Nothing the iterations read is written by that pass, so a window that turns out not to be the last
     // (a stall continuation, a launch that gave up) goes on as it would have, and the scalars are dropped.
-    const bool fused = early && e->fused_check && burst == remaining;
+    const bool fused = early && e->sw.fused_check && burst == remaining;
     if (fused) {
       if (enqueue_residuals(e)) return HIPENG_ERR_HIP;
       HIPCHK(hipMemcpyAsync(e->h_check, e->c.scal, SC_COUNT * 16 * sizeof(double) + sizeof(State), hipMemcpyDeviceToHost, e->stream));
@@ -4691,19 +4760,19 @@ static int run_admm(hipeng *e, c_int count, hipeng_scalars *early, int *have) {
     if (s.res_slow || s.res_repub) {
       for (int k = 0; k < 4; k++) { e->res_slow_hist[k] += s.res_slow_hist[k]; e->res_slow_last[k] = s.res_slow_last[k]; }
       e->res_slow_xcc |= s.res_slow_xcc;
-      if (e->trace) fprintf(stderr, "[osqp_amd] resident waits of this window: %d took more than 50 us (50-200 us: %d, 200-500: %d, 0.5-2 ms: %d, longer: %d; longest %.1f us; XCC mask 0x%02x; "
+      if (e->sw.trace) fprintf(stderr, "[osqp_amd] resident waits of this window: %d took more than 50 us (50-200 us: %d, 200-500: %d, 0.5-2 ms: %d, longer: %d; longest %.1f us; XCC mask 0x%02x; "
                                     "latest: exchange %d, workgroup %d missed workgroup %d, wait %d), %d re-publications\n", s.res_slow, s.res_slow_hist[0], s.res_slow_hist[1], s.res_slow_hist[2],
                             s.res_slow_hist[3], s.res_slow_max * 0.01, s.res_slow_xcc, s.res_slow_last[0], s.res_slow_last[1], s.res_slow_last[2], s.res_slow_last[3], s.res_repub);
       HIPCHK(hipMemsetAsync(&e->c.st->res_slow, 0, 12 * sizeof(int), e->stream));
     }
-    if (s.res_fail) { had_fail = true; if (resident_gave_up(e, s, !e->trace)) return HIPENG_ERR_HIP; }
+    if (s.res_fail) { had_fail = true; if (resident_gave_up(e, s, !e->sw.trace)) return HIPENG_ERR_HIP; }
     const long long done_now = s.admm_done - start;
     const bool stalls = count - done_now > remaining - burst;       // some launches were continuations
     remaining = count - done_now;
     if (fused && hipeng_early_scalars_usable((c_int)remaining, s.res_fail, s.res_slow, s.res_repub)) { fill_scalars(e->h_check, early); *have = 1; }
     call_max = std::max(call_max, s.iters_max);
     const int in_flight = s.stalled ? std::max(s.iters[0], s.iters[1]) : 0;
-    if (e->trace) fprintf(stderr, "[osqp_amd] window: K=%d burst=%lld done=%lld iters_max=%d last=%d stalled=%d(%d) launches=%lld\n", e->K, burst, done_now, s.iters_max, s.iters_last, s.stalled, in_flight, (long long)e->stats.graph_launches);
+    if (e->sw.trace) fprintf(stderr, "[osqp_amd] window: K=%d burst=%lld done=%lld iters_max=%d last=%d stalled=%d(%d) launches=%lld\n", e->K, burst, done_now, s.iters_max, s.iters_last, s.stalled, in_flight, (long long)e->stats.graph_launches);
     // next unroll count: the last window's maximum (the last solve's count right after a reset,
     // where the counts are still falling) plus a little head-room; a solve that needs more simply
     // takes a second graph launch
@@ -5022,6 +5091,40 @@ extern "C" long long hipeng_resident_plan_lists(const csc *P, const csc *A, int 
   if (terms <= cap) { if (Kcm) std::copy(po.Kcm.begin(), po.Kcm.end(), Kcm); if (Kca) std::copy(po.Kca.begin(), po.Kca.end(), Kca); }
   else if (Kcm || Kca) return HIPENG_ERR_ARG;
   return terms;
+}
+
+// The switch table from outside, for the tests and the documentation check (no device, no HIP call).  Row `index` of SW_TABLE: its name,
+// kind (SwKind), default as text ("unset" where unset is distinct: the use site works it out), that bit, and the one-line description;
+// outputs may be NULL.  Returns the number of rows, whatever the index.
+extern "C" int hipeng_switch_row(int index, const char **name, int *kind, char *def_text, int def_cap, int *unset_distinct, const char **what) {
+  if (index < 0 || index >= SW_COUNT) return SW_COUNT;
+  const SwRow &r = SW_TABLE[index];
+  if (name) *name = r.name;
+  if (kind) *kind = r.kind;
+  if (unset_distinct) *unset_distinct = r.unset_distinct;
+  if (what) *what = r.what;
+  if (def_text && def_cap > 0) {
+    if (r.unset_distinct) snprintf(def_text, (size_t)def_cap, "unset");
+    else if (r.kind == SW_TEXT) def_text[0] = 0;
+    else if (r.kind == SW_INT_PAIR) snprintf(def_text, (size_t)def_cap, "%d,%d", (int)r.def, (int)r.def2);
+    else if (r.kind == SW_DOUBLE) snprintf(def_text, (size_t)def_cap, "%g", r.def);
+    else snprintf(def_text, (size_t)def_cap, "%d", (int)r.def);
+  }
+  return SW_COUNT;
+}
+// What read_switches() makes of the current environment: two doubles per row, rows at most of them (out[2 i]: the value -- SW_UNSET where
+// unset is distinct and the variable is not set, the length of a text; out[2 i + 1]: the second number of a pair, else 0).  Returns the number of rows.
+extern "C" int hipeng_switch_values(double *out, int rows) {
+  if (!out) return SW_COUNT;
+  const Switches sw = read_switches();
+  for (int i = 0; i < std::min(rows, SW_COUNT); i++) {
+    const SwRow &r = SW_TABLE[i];
+    const char *at = reinterpret_cast<const char *>(&sw) + r.field;
+    const int *iv = reinterpret_cast<const int *>(at);
+    out[2 * i + 1] = r.kind == SW_INT_PAIR ? (double)iv[1] : 0.0;
+    out[2 * i] = r.kind == SW_TEXT ? (double)strlen(at) : r.kind == SW_DOUBLE ? *reinterpret_cast<const double *>(at) : (double)iv[0];
+  }
+  return SW_COUNT;
 }
 
 #ifdef OSQP_AMD_TIMELINE

@@ -55,6 +55,9 @@ static double toc(const OSQPTimer *t) { return now_s() - t->t0; }
 /* ------------------------------------------------------------------------ */
 static osqp_amd_options g_opt;
 static int g_opt_init = 0;
+/* OSQP_AMD_PCG_EPS_FACTOR: experiment knob for tools/pcg_tol_sweep.py -- the 1e-5 of osqp_solve's PCG stop.  Read with the others, kept
+ * beside them: osqp_amd_options is ABI and does not grow. */
+static double g_pcg_eps_factor = 1e-5;
 
 static void opt_init(void) {
   if (g_opt_init) return;
@@ -67,6 +70,7 @@ static void opt_init(void) {
   if ((s = getenv("OSQP_AMD_PCG_MAX_ITER"))) g_opt.pcg_max_iter = atoll(s);
   if ((s = getenv("OSQP_AMD_DEVICE")))       g_opt.device = atoll(s);
   else if ((s = getenv("LOCAL_RANK")))       g_opt.device = atoll(s);   /* one process per GPU */
+  if ((s = getenv("OSQP_AMD_PCG_EPS_FACTOR")) && atof(s) > 0) g_pcg_eps_factor = atof(s);
   g_opt_init = 1;
 }
 void osqp_amd_get_options(osqp_amd_options *o) { opt_init(); *o = g_opt; }
@@ -769,8 +773,7 @@ c_int osqp_solve(OSQPWorkspace *w) {
    * used 1e-6 * eps: 2.4 more PCG iterations per solve at config 2 for digits nothing looks at). */
   {
     const c_float e = HMIN(st->eps_abs > 0 ? st->eps_abs : st->eps_rel, st->eps_rel > 0 ? st->eps_rel : st->eps_abs);
-    static double factor = 0.0;          /* OSQP_AMD_PCG_EPS_FACTOR: experiment knob for tools/pcg_tol_sweep.py (default 1e-5) */
-    if (factor == 0.0) { const char *x = getenv("OSQP_AMD_PCG_EPS_FACTOR"); factor = x && atof(x) > 0 ? atof(x) : 1e-5; }
+    const double factor = g_pcg_eps_factor;
     prm.pcg_eps_rel = s->opt.pcg_eps_rel;
     if (e > 0) prm.pcg_eps_rel = HMAX(1e-13, HMIN(prm.pcg_eps_rel, factor * e));
     /* Equality rows carry rho_eq = 1e3 rho (constants.h:70): ||b|| is then dominated by their terms and a stop

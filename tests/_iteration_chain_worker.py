@@ -1,5 +1,6 @@
 """Shared set-up of tests/test_gpu_iteration_chain.py, and the child process of its segment test: the number of segments per
-graph (OSQP_AMD_GRAPH_SEGS) is read once per process, so the single-segment run needs a process of its own.
+graph (OSQP_AMD_GRAPH_SEGS) is read when an engine is created; the single-segment run has a process of its own, with the variable
+set for all of it.
 
   python tests/_iteration_chain_worker.py CASE ENV COUNT OUT.npz      (ENV: steps | default | resident)
 runs COUNT ADMM iterations in one hipeng_run_admm call and saves x, y, z."""

@@ -106,6 +106,11 @@ def _as_case(Pu, A):
     return dict(Pu=Pu, A=A, n=Pu.shape[0], m=A.shape[0])
 
 
+# the engine's defaults of the switches the rule below reads (tests/test_engine_switches_host.py holds them to the engine's table)
+SWITCH_DEFAULTS = dict(OSQP_AMD_RESIDENT=1, OSQP_AMD_RESIDENT_BLOCKS=1, OSQP_AMD_BLOCK_DIRECT=1, OSQP_AMD_ELIM=1, OSQP_AMD_DENSE_DIRECT=1,
+                       OSQP_AMD_DENSE_SMALL=1024, OSQP_AMD_RESIDENT_MIN_N=256)
+
+
 def instance_claims(Pu, A, env):
     """Form, info slots, layout slots and eliminated count of an engine created on (triu(P), A) under `env`, in the order of
     hipeng_create: block-direct, block-resident, the elimination, dense-direct for at most OSQP_AMD_DENSE_SMALL (1024) dense
@@ -114,7 +119,7 @@ def instance_claims(Pu, A, env):
     Whether the resident plan holds K is the device's own (hipeng_resident_plan): where the rule reaches it, form 1 is claimed."""
     c = _as_case(Pu, A)
     n, m = c["n"], c["m"]
-    on = lambda k, d=1: int(env.get(k, d))
+    on = lambda k: int(env.get(k, SWITCH_DEFAULTS[k]))
     res, blocks = on("OSQP_AMD_RESIDENT") != 0, on("OSQP_AMD_RESIDENT") != 0 and on("OSQP_AMD_RESIDENT_BLOCKS") != 0
     bd = FC.bd_structure(c)
     st = PC.structure(c)
@@ -128,9 +133,9 @@ def instance_claims(Pu, A, env):
     elim = int((erow >= 0).sum())
     dd = FC.dd_structure(c) if m and on("OSQP_AMD_DENSE_DIRECT") != 0 else None
     d4 = lambda: dict(form=4, info={3: dd["na"], 15: dd["nb2"]}, layout=layout, elim=elim, nd=dd["nd"])
-    if dd is not None and 0 < dd["na"] <= on("OSQP_AMD_DENSE_SMALL", 1024):
+    if dd is not None and 0 < dd["na"] <= on("OSQP_AMD_DENSE_SMALL"):
         return d4()
-    if res and on("OSQP_AMD_RESIDENT_MIN_N", 256) <= n <= 15616 and not st["huge"]:
+    if res and on("OSQP_AMD_RESIDENT_MIN_N") <= n <= 15616 and not st["huge"]:
         return dict(form=1, info={}, layout=layout, elim=elim)
     if dd is not None and on("OSQP_AMD_DENSE_DIRECT") == 2 and 0 < dd["na"] <= 8192:
         return d4()

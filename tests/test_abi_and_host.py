@@ -295,9 +295,12 @@ def test_bench_dump_outputs(tmp_path):
 
 
 def test_every_environment_variable_is_documented():
-    """Every OSQP_AMD_* variable the sources read appears in INTEGRATION.md (section F or the diagnostics paragraph)."""
+    """Every OSQP_AMD_* variable the sources read appears in INTEGRATION.md (section F or the diagnostics paragraph).  The single-QP
+    engine reads its variables by the names of its switch table (one getenv, no literal names): they come from the table itself."""
     import glob
-    names = set()
+    from tests.test_engine_switches_host import table
+    names = {row[0] for row in table()}
+    assert len(names) == 39
     for pat in ("osqp_amd/csrc/*.c", "osqp_amd/csrc/*.hip", "osqp_amd/*.py"):
         for f in glob.glob(os.path.join(ROOT, pat)):
             txt = open(f, errors="ignore").read()
