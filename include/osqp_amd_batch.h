@@ -417,7 +417,8 @@ c_int osqp_amd_batch_check_dev_ptr(osqp_amd_batch *b, const void *p);
  * Each call below is the twin named in its comment "for the listed members": `members [count]`, a HOST list (in the
  * _dev forms too: it belongs to the call, not to the data), strictly ascending, every index in [0, batch) -- the checks
  * of osqp_amd_batch_solve_members -- in front of the twin's arguments, and every per-member array COMPACT: [count][.],
- * row k belongs to member members[k].  All three engines serve them.  Of a member that is not listed nothing changes:
+ * row k belongs to member members[k].  All three engines serve them (osqp_amd_batch_update_matrices_members: the tiled and
+ * the streamed engine, as its twin).  Of a member that is not listed nothing changes:
  * its raw and scaled q, l, u, its row classes and flags, X, Y, info8, both certificates, the stored iterates, its solved
  * flag and its status_polish keep their bits.  count == batch is the whole-batch twin to the bit, in every output and
  * in every piece of handle state: it runs the twin's own code.
@@ -448,6 +449,38 @@ c_int osqp_amd_batch_warm_start_members(osqp_amd_batch *b, const c_int *members,
                                         const c_float *X, const c_float *Y);
 c_int osqp_amd_batch_warm_start_members_dev(osqp_amd_batch *b, const c_int *members, c_int count,
                                             const c_float *X, const c_float *Y);
+/* osqp_amd_batch_update_matrices for the listed members.  *_per_member = 0: one value array [k], written to every listed
+ * member; 1: COMPACT [count][k], row r for member members[r].  The index lists belong to the pattern, as in the twin.  A
+ * handle that holds shared raw values switches to per-member storage on the first such call with count < batch, whatever
+ * *_per_member says; the unlisted members' rows then hold the values that were shared.  A listed member gets what the twin
+ * does to a member: the new raw values, the equilibration from scratch on its raw data (q, l, u as last given), K re-formed
+ * and re-inverted inside the call with its current rho and row classes, the scaled iterates kept, rho_updates reset, the
+ * refinement verdict taken again; its solved and polished flags are cleared and a kept KKT inversion is dropped.  Its bits
+ * are those of the twin given [batch][k] arrays.  Of an unlisted member nothing changes: not its scaling (the twin would
+ * recompute it from the q it holds now), not its rho_updates, K^-1, flags or results.
+ * Refusals after the list's, with nothing written: OSQP_LINSYS_SOLVER_INIT_ERROR on a common-K handle (the twin's line on
+ * stderr, naming this call), then the twin's in the twin's order -- 1 for P_n > nnzP, 2 for A_n > nnzA,
+ * OSQP_DATA_VALIDATION_ERROR for an index outside [0, nnz), in the _dev form for a value pointer that is not device memory
+ * of the handle's device -- and 0 for both NULL.
+ * OSQP_NONCVX_ERROR exactly when, after the values are written, SOME member of the batch has a K with a non-positive pivot,
+ * listed or not (stderr names the first such member): a call that repairs other members while a bad one stays bad still
+ * returns it, and osqp_amd_batch_solve refuses until a matrix update returns 0.  So 0 means solves are served.  The handle
+ * keeps the verdict per member, and only a matrix update that lists the member (or a whole-batch one) takes it again:
+ * osqp_amd_batch_update, _update_rho and _warm_start, in any form, leave it. */
+c_int osqp_amd_batch_update_matrices_members(osqp_amd_batch *b, const c_int *members, c_int count,
+                                             const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
+                                             const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member);
+/* ... with the value arrays Px / Ax on the device; the index lists and members stay HOST lists. */
+c_int osqp_amd_batch_update_matrices_members_dev(osqp_amd_batch *b, const c_int *members, c_int count,
+                                                 const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
+                                                 const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member);
+/* osqp_amd_batch_update_rho for the listed members: rho points at one value (per_member = 0) or at COMPACT [count].  Each
+ * listed member's rho becomes min(max(rho, 1e-6), 1e6) and its K^-1 is rebuilt at the start of the next solve;
+ * rho_updates is not reset; its solved and polished flags are cleared and a kept KKT inversion is dropped.  The unlisted
+ * members keep every bit.  OSQP_DATA_VALIDATION_ERROR for a NULL rho; any value <= 0: returns 1 and changes nothing; on a
+ * common-K handle (one rho for the batch) count < batch returns 1 with a line on stderr and changes nothing. */
+c_int osqp_amd_batch_update_rho_members(osqp_amd_batch *b, const c_int *members, c_int count,
+                                        const c_float *rho, c_int per_member);
 /* osqp_amd_batch_polish for the listed members; status_polish [count].  Needs every LISTED member solved on the current
  * problem (OSQP_WORKSPACE_NOT_INIT_ERROR otherwise, nothing changed).  The work is done for the listed members whose
  * polished flag is unset, with the padded orders of their largest active set; a repeat does no work and reports the

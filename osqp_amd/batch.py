@@ -37,6 +37,7 @@ _CALLS = {
     "setup": "Hnccfffffsn", "setup_engine": "Hnnccfffffsn", "setup_common": "Hnccfffsn", "cleanup": "h",
     "update": "hfff", "update_dev": "hvvv", "warm_start": "hff", "warm_start_dev": "hvv", "update_rho": "hfn",
     "update_matrices": "h" + "finn" * 2, "update_matrices_dev": "h" + "vinn" * 2,
+    "update_matrices_members": "hin" + "finn" * 2, "update_matrices_members_dev": "hin" + "vinn" * 2, "update_rho_members": "hinfn",
     "common_update_model": "h" + "fin" * 2, "common_update_model_dev": "h" + "vin" * 2,
     "solve": "h", "solve_members": "hin", "solve_limited": "hinnd", "solve_report": "hf", "common_columns": "hi",
     "polish": "hi", "polish_status_dev": "hv", "kkt_info": "hi", "common_kkt": "hn", "common_kkt_peek": "hffniif",
@@ -108,7 +109,8 @@ def is_device(a):
 def check_matrix_update(B, nnzP, nnzA, Px=None, Px_idx=None, Ax=None, Ax_idx=None):
     """Shape and index checks of BatchOSQP.update_matrices, as interface.py: update makes them for one QP (the C
     entry point reads what the shapes promise).  A 1-D value array is shared by the batch, a 2-D one is [B, k];
-    without an index list k is the matrix's nnz, with one it is the list's length.  Returns the arrays as the C
+    without an index list k is the matrix's nnz, with one it is the list's length.  B is the row count of the call: the
+    batch, or the number of listed members of a members= call (compact [count, k]).  Returns the arrays as the C
     side takes them: (Px, Px_idx, P per-member flag, Ax, Ax_idx, A per-member flag)."""
     out = []
     for name, V, I, nnz in (("P", Px, Px_idx, nnzP), ("A", Ax, Ax_idx, nnzA)):
@@ -501,15 +503,27 @@ class BatchOSQP:
         _, f, lead = self._entry("update", mem, dev)
         return int(f(self._h, *lead, *((Q, L, U) if dev else (_p(Q), _p(L), _p(U)))))
 
-    def update_matrices(self, Px=None, Px_idx=None, Ax=None, Ax_idx=None):
+    def update_matrices(self, Px=None, Px_idx=None, Ax=None, Ax_idx=None, members=None):
         """osqp_update_P / _A / _P_A for every QP: new values on the pattern of setup.  Px / Ax: [k] (shared by the
         batch) or [B, k] (per member); k = nnz of triu(P) / A in CSC order, or the length of Px_idx / Ax_idx (slots, one
         list for the batch).  Scaling is recomputed; rho, row classes and iterates stay.  Returns the C return code
         (5: some member's new K is not positive definite; solve then refuses until an update succeeds).  Px / Ax may be
-        device arrays; the index lists stay host data."""
+        device arrays; the index lists stay host data.
+        members= (an ascending index list or a boolean mask of length B): for the listed members only.  Px / Ax are [k]
+        (written to every listed member) or compact [count, k], row r for the r-th listed member.  Only the listed
+        members are re-equilibrated and get a new K^-1; the others keep their data, scaling, rho, K^-1, results and solved
+        flag.  A handle with shared values keeps one row per member from then on.  5 is returned as long as any member
+        of the batch, listed or not, has a K that is not positive definite."""
         self._unserved("update_matrices", never=True)
+        mem = None if members is None else self._members(members, "update_matrices")
         dev = self._route(Px=Px, Ax=Ax) == "device"
-        Px, Px_idx, pper, Ax, Ax_idx, aper = check_matrix_update(self.B, self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
+        try:
+            Px, Px_idx, pper, Ax, Ax_idx, aper = check_matrix_update(self._rows(mem), self.Pu.nnz, self.Ah.nnz, Px, Px_idx, Ax, Ax_idx)
+        except ValueError as e:
+            if mem is None:
+                raise
+            raise ValueError("with members= the values are [k] or compact [count, k] (%d listed members): %s"
+                             % (mem.size, e)) from None
         if Px is None and Ax is None:
             return 0
         if self._many is not None:
@@ -517,8 +531,8 @@ class BatchOSQP:
         (pP, iP, kP), (pA, iA, kA) = self._matrix_values(dev, Px, Px_idx, Ax, Ax_idx)
         if dev and pP is None and pA is None:
             return 0
-        f = self._lib.osqp_amd_batch_update_matrices_dev if dev else self._lib.osqp_amd_batch_update_matrices
-        return int(f(self._h, pP, iP, kP, pper, pA, iA, kA, aper))
+        _, f, lead = self._entry("update_matrices", mem, dev)
+        return int(f(self._h, *lead, pP, iP, kP, pper, pA, iA, kA, aper))
 
     @staticmethod
     def _matrix_values(dev, Px, Px_idx, Ax, Ax_idx):
@@ -559,18 +573,24 @@ class BatchOSQP:
             self._shared_kkt = self._lib.osqp_amd_batch_common_kkt_peek(self._h, no_f, no_f, 0, no_i, no_i, no_f) == 0
         return rc
 
-    def update_rho(self, rho):
-        """osqp_update_rho for every QP: a scalar, or [B] values.  Returns 1 (nothing changed) when a value is <= 0."""
+    def update_rho(self, rho, members=None):
+        """osqp_update_rho for every QP: a scalar, or [B] values.  Returns 1 (nothing changed) when a value is <= 0.
+        members=: for the listed members only, a scalar or [count] values; the others keep rho, K^-1, results and solved
+        flag.  engine="common" has one rho for the batch: it returns 1, with nothing changed, for a list short of all B."""
+        mem = None if members is None else self._members(members, "update_rho")
+        R = self._rows(mem)
         rho = np.asarray(rho, dtype=np.float64)
-        if rho.shape not in ((), (self.B,)):
-            raise ValueError("rho must be a scalar or [B]")
+        if rho.shape not in ((), (R,)):
+            raise ValueError("rho must be a scalar or [B]" if mem is None else
+                             "rho with members= must be a scalar or [%d], one value per listed member" % R)
         per = int(rho.ndim == 1)
         if per and getattr(self, "engine", None) == "common":
             raise ValueError("engine='common' has one rho for the batch: update_rho takes a scalar")
         rho = np.ascontiguousarray(rho.reshape(-1))
         if self._many is not None:
             return self._many.update_rho(rho, per)
-        return int(self._lib.osqp_amd_batch_update_rho(self._h, abi.fptr(rho), per))
+        _, f, lead = self._entry("update_rho", mem)
+        return int(f(self._h, *lead, abi.fptr(rho), per))
 
     def warm_start(self, X=None, Y=None, members=None):
         """osqp_warm_start (_x, _y) for every QP: X [B, n], Y [B, m], unscaled; turns the warm_start setting on.  Host

@@ -94,7 +94,9 @@ struct BIO {               // per-batch arrays (device)
 //               matrix-update phases, k_bs_invert; the tiled solve phase also reads BF_REBUILD as it); cleared
 //               by the first probe of admm_loop.
 //   BF_NOT_PD   a pivot of K was not positive.  Set by the tiled setup and matrix-update phases and by k_bs_invert,
-//               read by the host right after setup or a matrix update; cleared by the next store of the word.
+//               read by the host right after setup or a matrix update, for the members that call touched, and kept
+//               there per member (member_not_pd): the next store of the word -- an update_rho, a class-changing
+//               update -- clears the bit, not the host's record.
 // osqp_amd_batch_rounds counts BF_REFINE; the values are part of what the tests read.
 enum { BF_REBUILD = 1, BF_REFINE = 2, BF_OPEN = 4, BF_NOT_PD = 8 };
 
@@ -499,7 +501,8 @@ struct TiledK {
 // PH = 0: setup phase (scale, classify, build K^-1, store the workspace);
 // PH = 1: solve phase (load the workspace, ADMM loop, store the solution);
 // PH = 2: matrix-update phase (osqp_update_P_A, osqp.c:1171-1279): the setup phase on the current raw data with
-//         the member's row classes, rho and iterates kept;
+//         the member's row classes, rho and iterates kept; one workgroup per listed member with `list` (qp = list[blockIdx.x],
+//         osqp_amd_batch_update_matrices_members), which no other phase reads;
 // PH = 3: the solve phase of a solve with a time limit (admm_loop<.., CLOCK = true>): an instantiation of its own, so
 //         that PH = 1 -- 256 registers and spills at tile 8 -- carries no clock statement.  clk: the clock words (PH = 3).
 #ifndef BATCH_WAVES_PER_SIMD
@@ -507,13 +510,14 @@ struct TiledK {
 #endif
 template <int TR, int TC, int GC, int PH>
 __global__ void __launch_bounds__(16 * GC, PH == 1 || PH == 3 ? BATCH_WAVES_PER_SIMD : 2)
-k_batch_solve(BPattern p, BSettings st, BIO io, unsigned long long *clk) {
+k_batch_solve(BPattern p, BSettings st, BIO io, unsigned long long *clk, const int *list) {
   constexpr int NP = 16 * TR, NT = 16 * GC;
   static_assert(GC * TC == NP, "tile shape");
   static_assert(4 * NP <= NT, "the GEMV reduction and the column dots use four lanes per row/column");
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x;
-  const long long qp = ((PH == 1 || PH == 3) && io.order) ? io.order[blockIdx.x] : (int)blockIdx.x;
+  const long long qp = ((PH == 1 || PH == 3) && io.order) ? io.order[blockIdx.x]
+                       : (PH == 2 && list) ? list[blockIdx.x] : (int)blockIdx.x;
   const BL s = bt_layout<NP, NT>(lds, p);
   double *Wk = io.Wk + qp * (long long)(NP * NP);
   BDbg dbg;
@@ -652,20 +656,24 @@ __global__ void __launch_bounds__(256) k_batch_gather(double *dst, const double 
 // New matrix values into the raw value array of the batch: slot idx[k] (k itself when idx is null) of every member
 // receives src[k] (shared values) or src[member][k].  dstride = 0: the raw array is shared and so is src.  One
 // thread per (member, k), k fastest: the reads are coalesced, and so are the writes of a full update.
+// list (null: every member): `members` listed ones, row b of src -- or its one row -- goes to member list[b].
 __global__ void __launch_bounds__(256) k_batch_scatter(double *dst, long long dstride, const double *src, long long sstride,
-                                                       const int *idx, long long cnt, long long members) {
+                                                       const int *idx, long long cnt, long long members, const int *list) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t >= cnt * members) return;
   const long long b = t / cnt, k = t - b * cnt;
-  dst[b * dstride + (idx ? idx[k] : k)] = src[b * sstride + k];
+  dst[(list ? list[b] : b) * dstride + (idx ? idx[k] : k)] = src[b * sstride + k];
 }
 
 // osqp_update_rho for every QP (osqp.c:1281-1332): the clipped value, and a rebuild of K^-1 at the start of the next
 // solve, after which the refinement verdict is re-taken (as after a class change in k_batch_update)
-__global__ void __launch_bounds__(256) k_batch_update_rho(long long B, BIO io, const double *rho, int per_member) {
-  const long long qp = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (qp >= B) return;
-  io.rho_io[qp] = fmin(fmax(rho[per_member ? qp : 0], 1e-6), 1e6);
+// list (null: every member): the B listed members only, rho compact (rho[k] for member list[k]).
+__global__ void __launch_bounds__(256) k_batch_update_rho(long long B, BIO io, const double *rho, int per_member,
+                                                          const int *list) {
+  const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= B) return;
+  const long long qp = list ? list[k] : k;
+  io.rho_io[qp] = fmin(fmax(rho[per_member ? k : 0], 1e-6), 1e6);
   io.flag[qp] = BF_REBUILD;
 }
 
@@ -785,7 +793,8 @@ struct osqp_amd_batch {
   double *d_vals = nullptr, *d_rho = nullptr;           // staging of update_matrices / update_rho / warm_start
   int *d_idx = nullptr;
   size_t vals_cap = 0, idx_cap = 0;
-  bool noncvx = false;      // the last matrix update left some member's K indefinite: solve refuses
+  bool noncvx = false;      // some member's K is indefinite since its last matrix update: solve refuses
+  std::vector<char> member_not_pd;   // ... per member: written by a matrix update for the members it re-inverts, and by nothing else
   int *d_order = nullptr;   // dispatch order for the next solve (k_batch_order)
   int lpt = 1;
   // the limits of a solve (osqp_amd_batch_solve_limited)
@@ -829,7 +838,8 @@ struct osqp_amd_batch {
   long long kkt_builds = 0; // passes of k_bp_form + k_bp_invert over the solved members since setup, polish's included
 };
 
-static void batch_launch(osqp_amd_batch *b, int phase, const BSettings *st = nullptr, unsigned long long *clk = nullptr);
+static void batch_launch(osqp_amd_batch *b, int phase, const BSettings *st = nullptr, unsigned long long *clk = nullptr,
+                         const int *list = nullptr, long long count = 0);
 
 // the problem or the stored iterates have changed: no member's results are those of a solve of what the handle holds
 static void mark_unsolved(osqp_amd_batch *b) {
@@ -993,7 +1003,7 @@ static void fill_settings(osqp_amd_batch *b, const OSQPSettings *s) {
 
 static int bs_build_kpattern(osqp_amd_batch *b, const std::vector<int> &Pp, const std::vector<int> &Pi,
                              const std::vector<int> &Rp, const std::vector<int> &Rc, const std::vector<int> &Rk);
-static int bs_setup_launch(osqp_amd_batch *b, bool update);
+static int bs_setup_launch(osqp_amd_batch *b, bool update, const int *list = nullptr, long long count = 0);
 static int bc_alloc(osqp_amd_batch *b);
 static int stage_reserve(osqp_amd_batch *b, size_t vals, size_t idx);
 static int bc_setup_launch(osqp_amd_batch *b, const c_float *Q);
@@ -1064,6 +1074,7 @@ static c_int batch_setup(osqp_amd_batch **out, c_int engine, c_int batch, const 
   b->device = (int)device; b->B = batch; b->n = n; b->m = m;
   b->member_solved.assign((size_t)batch, (char)0);
   b->member_polished.assign((size_t)batch, (char)0);
+  b->member_not_pd.assign((size_t)batch, (char)0);
   b->engine = (int)engine; b->NPs = streamed ? NPs : 0;
   b->nnzP = (int)P->p[n]; b->nnzA = (int)A->p[n];
   b->tile = n <= 64 ? 4 : 8;
@@ -1266,14 +1277,16 @@ static void bs_rebuild(osqp_amd_batch *b, const int *list, long long count) {
   hipLaunchKernelGGL(k_bs_invert, dim3((unsigned)count), dim3(BS_NTI), 0, b->stream, b->n, b->io, b->NPs, list);
 }
 
-// update = true: the re-equilibration of a matrix update; K is re-formed and re-inverted for every member either way
-static int bs_setup_launch(osqp_amd_batch *b, bool update) {
+// update = true: the re-equilibration of a matrix update; K is re-formed and re-inverted for every member either way.
+// list (device, with update only; null: every member): for the `count` listed members alone.
+static int bs_setup_launch(osqp_amd_batch *b, bool update, const int *list, long long count) {
   const void *fn = update ? KFN(k_bs_setup<true>) : KFN(k_bs_setup<false>);
   int NP = b->NPs;
-  void *args[] = {&b->pat, &b->st, &b->io, &NP};
+  if (!list) count = b->B;
+  void *args[] = {&b->pat, &b->st, &b->io, &NP, &list};
   set_dynamic_lds(fn, b->lds_bytes);
-  (void)hipLaunchKernel(fn, dim3((unsigned)b->B), dim3(BS_NT), args, b->lds_bytes, b->stream);
-  bs_rebuild(b, nullptr, b->B);
+  (void)hipLaunchKernel(fn, dim3((unsigned)count), dim3(BS_NT), args, b->lds_bytes, b->stream);
+  bs_rebuild(b, list, count);
   return 0;
 }
 
@@ -1391,7 +1404,8 @@ static int bc_setup_launch(osqp_amd_batch *b, const c_float *Q) {
   BIO io1 = b->io;
   io1.Q = d_qhat;
   int NP = b->NPs;
-  void *args[] = {&b->pat, &b->st, &io1, &NP};
+  const int *every = nullptr;
+  void *args[] = {&b->pat, &b->st, &io1, &NP, &every};
   set_dynamic_lds(KFN(k_bs_setup<false>), b->lds_bytes);
   (void)hipLaunchKernel(KFN(k_bs_setup<false>), dim3(1), dim3(BS_NT), args, b->lds_bytes, b->stream);
   if (B > 1) hipLaunchKernelGGL(k_bc_spread, dim3((unsigned)(B - 1)), dim3(256), 0, b->stream, b->n, b->m, b->io);
@@ -1566,12 +1580,14 @@ static const void *batch_kernel(int tile, int phase) {
   if (tile == 8) return phase ? KFN((k_batch_solve<8, 4, 32, 1>)) : KFN((k_batch_solve<8, 4, 32, 0>));
   return phase ? KFN((k_batch_solve<4, 2, 32, 1>)) : KFN((k_batch_solve<4, 2, 32, 0>));
 }
-// st: the settings of a solve phase's call (null: b->st); clk: the clock words of phase 3
-static void batch_launch(osqp_amd_batch *b, int phase, const BSettings *st, unsigned long long *clk) {
+// st: the settings of a solve phase's call (null: b->st); clk: the clock words of phase 3; list (device, phase 2 only;
+// null: every member): the `count` listed members of a matrix update
+static void batch_launch(osqp_amd_batch *b, int phase, const BSettings *st, unsigned long long *clk, const int *list,
+                         long long count) {
   const void *fn = batch_kernel(b->tile, phase);
   set_dynamic_lds(fn, b->lds_bytes);
-  void *args[] = {&b->pat, st ? const_cast<BSettings *>(st) : &b->st, &b->io, &clk};
-  (void)hipLaunchKernel(fn, dim3((unsigned)b->B), dim3(BT), args, b->lds_bytes, b->stream);
+  void *args[] = {&b->pat, st ? const_cast<BSettings *>(st) : &b->st, &b->io, &clk, &list};
+  (void)hipLaunchKernel(fn, dim3((unsigned)(list ? count : b->B)), dim3(BT), args, b->lds_bytes, b->stream);
 }
 
 // the calls the common-K engine does not serve: the handle is left untouched and usable
@@ -1674,23 +1690,25 @@ static int stage_reserve(osqp_amd_batch *b, size_t vals, size_t idx) {
 }
 
 // One of P, A: new values into the raw value array (switched to per-member storage first when the handle holds
-// shared values and the update brings per-member ones).  at / iat: where this matrix's values and indices sit in
-// the staging buffers.  dev: vals is a device array (osqp_amd_batch_update_matrices_dev): it is copied device to
-// device where the layouts match and read in place by k_batch_scatter otherwise; idx is a host list either way.
+// shared values and the update brings per-member ones, or values for a list of members).  at / iat: where this
+// matrix's values and indices sit in the staging buffers.  dev: vals is a device array
+// (osqp_amd_batch_update_matrices_dev): it is copied device to device where the layouts match and read in place by
+// k_batch_scatter otherwise; idx is a host list either way.  list (device; null: every member): vals is one [cnt] array
+// for each of the `count` listed members, or with per_member compact [count][cnt]; the other members' rows stay.
 static int patch_values(osqp_amd_batch *b, double **raw, const double **io_raw, long long *stride, int nnz,
                         const c_float *vals, const c_int *idx, c_int cnt, c_int per_member, size_t at, size_t iat,
-                        bool dev = false) {
+                        bool dev = false, const int *list = nullptr, long long count = 0) {
   const long long B = b->B;
-  if (per_member && !*stride) {
+  if ((per_member || list) && !*stride) {
     double *all = nullptr;
     if (balloc(b, &all, (size_t)B * nnz)) return -102;
     if (nnz) hipLaunchKernelGGL(k_batch_scatter, dim3((unsigned)((B * nnz + 255) / 256)), dim3(256), 0, b->stream,
-                                all, (long long)nnz, *raw, 0LL, (const int *)nullptr, (long long)nnz, B);
+                                all, (long long)nnz, *raw, 0LL, (const int *)nullptr, (long long)nnz, B, (const int *)nullptr);
     *raw = all; *io_raw = all; *stride = nnz;   // (the shared array stays in b->allocs until cleanup)
   }
   if (!cnt) return 0;
-  const size_t tot = per_member ? (size_t)B * cnt : (size_t)cnt;
-  if (!idx && (per_member || !*stride)) {       // same layout as the raw array: straight in
+  const size_t tot = per_member ? (size_t)(list ? count : B) * cnt : (size_t)cnt;
+  if (!list && !idx && (per_member || !*stride)) {       // same layout as the raw array: straight in
     BCHK(hipMemcpyAsync(*raw, vals, tot * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream));
     return 0;
   }
@@ -1701,16 +1719,17 @@ static int patch_values(osqp_amd_batch *b, double **raw, const double **io_raw, 
     BCHK(hipMemcpyAsync(b->d_idx + iat, h.data(), (size_t)cnt * sizeof(int), hipMemcpyHostToDevice, b->stream));
     BCHK(hipStreamSynchronize(b->stream));      // h goes out of scope
   }
-  const long long members = *stride ? B : 1;
+  const long long members = list ? count : (*stride ? B : 1);
   hipLaunchKernelGGL(k_batch_scatter, dim3((unsigned)((members * cnt + 255) / 256)), dim3(256), 0, b->stream,
                      *raw, *stride, src, per_member ? (long long)cnt : 0LL,
-                     idx ? b->d_idx + iat : (const int *)nullptr, (long long)cnt, members);
+                     idx ? b->d_idx + iat : (const int *)nullptr, (long long)cnt, members, list);
   return 0;
 }
 
-// osqp_amd_batch_update_matrices, and with dev its _dev twin: the value arrays are device arrays then, the index lists
-// host lists either way
-static c_int update_matrices_call(osqp_amd_batch *b, bool dev,
+// osqp_amd_batch_update_matrices in its four forms: with dev the value arrays are device arrays (the index lists are
+// host lists either way); with members the values go to the `count` listed members -- one [k] array for each of them,
+// or with *_per_member compact [count][k] -- and only they are re-equilibrated, re-formed and re-inverted.
+static c_int update_matrices_call(osqp_amd_batch *b, bool dev, const c_int *members, c_int count,
                                   const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
                                   const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
   // nothing is written before every argument has passed (osqp.c:1197-1222; the index range is this project's check)
@@ -1722,20 +1741,30 @@ static c_int update_matrices_call(osqp_amd_batch *b, bool dev,
   if (!Px && !Ax) return 0;
   BCHK(hipSetDevice(b->device));
   if (dev && dev_ptrs_check(b, {Px, Ax})) return OSQP_DATA_VALIDATION_ERROR;
-  mark_unsolved(b);
+  if (members_put(b, members, count)) return OSQP_MEM_ALLOC_ERROR;
+  const int *list = members ? b->d_mlist : nullptr;
+  mark_call_unsolved(b, members, count);
   const c_int pc = Px ? (Px_idx ? P_n : (c_int)b->nnzP) : 0, ac = Ax ? (Ax_idx ? A_n : (c_int)b->nnzA) : 0;
-  const size_t B = (size_t)b->B;                // (the device route stages the index lists only)
-  const size_t pv = dev ? 0 : (size_t)pc * (Px_per_member ? B : 1), av = dev ? 0 : (size_t)ac * (Ax_per_member ? B : 1);
+  const size_t R = members ? (size_t)count : (size_t)b->B;   // (the device route stages the index lists only)
+  const size_t pv = dev ? 0 : (size_t)pc * (Px_per_member ? R : 1), av = dev ? 0 : (size_t)ac * (Ax_per_member ? R : 1);
   if (stage_reserve(b, pv + av, (size_t)pc + ac)) return OSQP_MEM_ALLOC_ERROR;
-  if (Px && patch_values(b, &b->dPx, &b->io.Px, &b->io.strideP, b->nnzP, Px, Px_idx, pc, Px_per_member, 0, 0, dev))
+  if (Px && patch_values(b, &b->dPx, &b->io.Px, &b->io.strideP, b->nnzP, Px, Px_idx, pc, Px_per_member, 0, 0, dev, list, count))
     return OSQP_MEM_ALLOC_ERROR;
-  if (Ax && patch_values(b, &b->dAx, &b->io.Ax, &b->io.strideA, b->nnzA, Ax, Ax_idx, ac, Ax_per_member, pv, (size_t)pc, dev))
+  if (Ax && patch_values(b, &b->dAx, &b->io.Ax, &b->io.strideA, b->nnzA, Ax, Ax_idx, ac, Ax_per_member, pv, (size_t)pc, dev, list,
+                         count))
     return OSQP_MEM_ALLOC_ERROR;
   // re-equilibrate from the raw data, re-form and re-invert K with each member's current rho and classes
-  if (b->engine == OSQP_AMD_BATCH_STREAMED) (void)bs_setup_launch(b, true);
-  else batch_launch(b, 2);
-  const long long bad = first_not_pd(b);
-  if (bad < 0) return -102;
+  if (b->engine == OSQP_AMD_BATCH_STREAMED) (void)bs_setup_launch(b, true, list, count);
+  else batch_launch(b, 2, nullptr, nullptr, list, count);
+  // the verdict of the members this call re-inverted goes into the host's record; an unlisted member that an earlier
+  // call left non-convex still is, whatever has stored its flag word since
+  std::vector<int> fl;
+  if (read_flags(b, fl)) return -102;
+  for (size_t k = 0; k < R; k++) {
+    const size_t q = members ? (size_t)members[k] : k;
+    b->member_not_pd[q] = (fl[q] & BF_NOT_PD) ? 1 : 0;
+  }
+  const long long bad = std::find(b->member_not_pd.begin(), b->member_not_pd.end(), (char)1) - b->member_not_pd.begin();
   b->noncvx = bad != b->B;
   if (b->noncvx) {
     fprintf(stderr, "osqp_amd batch: the new K of QP %zu of the batch is not positive definite (K = P + sigma I + "
@@ -1750,32 +1779,39 @@ extern "C" c_int osqp_amd_batch_update_matrices(osqp_amd_batch *b,
                                                 const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
   BC_NEVER(b, "osqp_amd_batch_update_matrices");
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  return update_matrices_call(b, false, Px, Px_idx, P_n, Px_per_member, Ax, Ax_idx, A_n, Ax_per_member);
+  return update_matrices_call(b, false, nullptr, 0, Px, Px_idx, P_n, Px_per_member, Ax, Ax_idx, A_n, Ax_per_member);
 }
 
-extern "C" c_int osqp_amd_batch_update_rho(osqp_amd_batch *b, const c_float *rho, c_int per_member) {
-  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+// osqp_amd_batch_update_rho and its _members form: rho is one value, or with per_member [R], R = count with a list and B
+// without
+static c_int update_rho_call(osqp_amd_batch *b, const c_int *members, c_int count, const c_float *rho, c_int per_member) {
   if (!rho) return OSQP_DATA_VALIDATION_ERROR;
-  const size_t cnt = per_member ? (size_t)b->B : 1;
+  const size_t R = members ? (size_t)count : (size_t)b->B, cnt = per_member ? R : 1;
   for (size_t k = 0; k < cnt; k++) if (!(rho[k] > 0)) return 1;   // osqp.c:1288-1293
   if (b->engine == OSQP_AMD_BATCH_COMMON) {
-    if (per_member) {
-      fprintf(stderr, "osqp_amd batch: the common-K engine has one rho for the batch: osqp_amd_batch_update_rho takes a "
-                      "scalar (per_member = 0)\n");
+    if (per_member || members) {
+      fprintf(stderr, "osqp_amd batch: the common-K engine has one rho for the batch: osqp_amd_batch_update_rho%s\n",
+              members ? "_members takes all of its members (count = batch)" : " takes a scalar (per_member = 0)");
       return 1;
     }
     b->bc_rho = fmin(fmax(rho[0], 1e-6), 1e6);
     b->bc_rebuild = true;
   }
   BCHK(hipSetDevice(b->device));
-  mark_unsolved(b);
+  if (members_put(b, members, count)) return OSQP_MEM_ALLOC_ERROR;
+  mark_call_unsolved(b, members, count);
   if (balloc_once(b, &b->d_rho, (size_t)b->B)) return OSQP_MEM_ALLOC_ERROR;
   BCHK(hipMemcpyAsync(b->d_rho, rho, cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  hipLaunchKernelGGL(k_batch_update_rho, dim3((unsigned)((b->B + 255) / 256)), dim3(256), 0, b->stream,
-                     b->B, b->io, b->d_rho, (int)(per_member != 0));
+  hipLaunchKernelGGL(k_batch_update_rho, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, b->stream,
+                     (long long)R, b->io, b->d_rho, (int)(per_member != 0), members ? b->d_mlist : (const int *)nullptr);
   BCHK(hipGetLastError());
   BCHK(hipStreamSynchronize(b->stream));
   return 0;
+}
+
+extern "C" c_int osqp_amd_batch_update_rho(osqp_amd_batch *b, const c_float *rho, c_int per_member) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  return update_rho_call(b, nullptr, 0, rho, per_member);
 }
 
 // osqp_amd_batch_warm_start in its four forms; X, Y are [R][.], R = count with a list and B without (null = keep)
@@ -2253,7 +2289,8 @@ static c_int bc_update_model(osqp_amd_batch *b, bool dev, const char *call, cons
   BIO io1 = b->io;
   io1.Q = b->bc_qhat;
   int NP = b->NPs;
-  void *args[] = {&b->pat, &b->st, &io1, &NP};
+  const int *every = nullptr;
+  void *args[] = {&b->pat, &b->st, &io1, &NP, &every};
   set_dynamic_lds(KFN(k_bs_setup<true>), b->lds_bytes);
   (void)hipLaunchKernel(KFN(k_bs_setup<true>), dim3(1), dim3(BS_NT), args, b->lds_bytes, b->stream);
   if (B > 1) hipLaunchKernelGGL(k_bc_spread, dim3((unsigned)(B - 1)), dim3(256), 0, b->stream, b->n, b->m, b->io);

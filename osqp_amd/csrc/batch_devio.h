@@ -31,7 +31,7 @@ extern "C" c_int osqp_amd_batch_update_matrices_dev(osqp_amd_batch *b,
                                                     const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
   BC_NEVER(b, "osqp_amd_batch_update_matrices_dev");
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
-  return update_matrices_call(b, true, Px, Px_idx, P_n, Px_per_member, Ax, Ax_idx, A_n, Ax_per_member);
+  return update_matrices_call(b, true, nullptr, 0, Px, Px_idx, P_n, Px_per_member, Ax, Ax_idx, A_n, Ax_per_member);
 }
 
 // (one body with its host twin, bc_update_model in batch.hip: the device pointers are checked after the host lists)

@@ -5,14 +5,16 @@
 // not listed nothing changes: its raw and scaled q, l, u, classes, io.flag, results, certificates, stored iterates,
 // solved flag and status_polish keep their bits.
 //
-// A form shares the twin's body in batch.hip (update_call, warm_start_call, get_call, adjoint_call, tangent_call),
+// A form shares the twin's body in batch.hip (update_call, update_matrices_call, update_rho_call, warm_start_call,
+// get_call, adjoint_call, tangent_call),
 // which takes the list; an entry point here is MEMBERS_OPEN -- the NULL handle (OSQP_WORKSPACE_NOT_INIT_ERROR), the
 // list (OSQP_DATA_VALIDATION_ERROR), the engine's refusal where the twin has one, in this order and with nothing
 // written -- and that call, after which the twin's own refusals come in the twin's order.  A list of all B members
 // goes on as no list, so count == B runs the twin's code and nothing else.
 //
 // The kernels are the twins', given the list (k_batch_update, k_batch_warm_start, k_bc_warm_start, k_bc_classes,
-// k_bp_active: one workgroup per listed member, compact inputs read at blockIdx.x) or already taking one (k_bp_form,
+// k_bp_active, the matrix-update phase of k_batch_solve, k_bs_setup<true>: one workgroup per listed member, compact
+// inputs read at blockIdx.x; k_batch_scatter, k_batch_update_rho: one thread per listed entry) or already taking one (k_bp_form,
 // k_bk_form, the inversions, k_bp_polish, k_ba_adjoint, k_bt_tangent, whose compact outputs go through BPol::pos).
 // The list is uploaded once per call (members_upload).
 
@@ -42,6 +44,27 @@ extern "C" c_int osqp_amd_batch_warm_start_members_dev(osqp_amd_batch *b, const 
                                                        const c_float *Y) {
   MEMBERS_OPEN()
   return warm_start_call(b, true, list, count, X, Y);
+}
+
+// New matrix values and rho for the listed members: update_matrices_call and update_rho_call of batch.hip with the list.
+// The values are one [k] array written to every listed member (*_per_member = 0) or compact [count][k]; a handle with
+// shared raw values switches to per-member storage (patch_values) and the unlisted rows hold what was shared.
+extern "C" c_int osqp_amd_batch_update_matrices_members(osqp_amd_batch *b, const c_int *members, c_int count,
+                                                        const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
+                                                        const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
+  MEMBERS_OPEN(BC_NEVER(b, "osqp_amd_batch_update_matrices_members"))
+  return update_matrices_call(b, false, list, count, Px, Px_idx, P_n, Px_per_member, Ax, Ax_idx, A_n, Ax_per_member);
+}
+extern "C" c_int osqp_amd_batch_update_matrices_members_dev(osqp_amd_batch *b, const c_int *members, c_int count,
+                                                            const c_float *Px, const c_int *Px_idx, c_int P_n, c_int Px_per_member,
+                                                            const c_float *Ax, const c_int *Ax_idx, c_int A_n, c_int Ax_per_member) {
+  MEMBERS_OPEN(BC_NEVER(b, "osqp_amd_batch_update_matrices_members_dev"))
+  return update_matrices_call(b, true, list, count, Px, Px_idx, P_n, Px_per_member, Ax, Ax_idx, A_n, Ax_per_member);
+}
+extern "C" c_int osqp_amd_batch_update_rho_members(osqp_amd_batch *b, const c_int *members, c_int count, const c_float *rho,
+                                                   c_int per_member) {
+  MEMBERS_OPEN()
+  return update_rho_call(b, list, count, rho, per_member);
 }
 
 // polish for the listed members: the work is done for those on which polish has not run since their last solve

@@ -81,10 +81,11 @@ __device__ __forceinline__ BL bs_layout(double *lds, const BPattern &p, const BI
 // setup: the tiled engine's setup phase with the matrix values in the member's HBM slab (SLAB: the slab is
 // written and re-read by different lanes of this workgroup, so its hand-offs are fenced).
 // UPD: the same on the current raw data for a matrix update (osqp.c:1171-1279): row classes, rho and iterates stay.
+// list (null: every member): one workgroup per listed member, qp = list[blockIdx.x].
 // ---------------------------------------------------------------------------
 template <bool UPD>
-__global__ void __launch_bounds__(BS_NT) k_bs_setup(BPattern p, BSettings st, BIO io, int NP) {
-  const long long qp = blockIdx.x;
+__global__ void __launch_bounds__(BS_NT) k_bs_setup(BPattern p, BSettings st, BIO io, int NP, const int *list) {
+  const long long qp = list ? list[blockIdx.x] : blockIdx.x;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const BL s = bs_layout(lds, p, io, qp, NP);
   clear_vectors<BS_NT>(s);
