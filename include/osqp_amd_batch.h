@@ -346,6 +346,34 @@ c_int osqp_amd_batch_tangent(osqp_amd_batch *b, c_int ndir,
  * rho_estimate, rho}; DX / DY infeasibility certificates.  NULL = skip. */
 c_int osqp_amd_batch_get(osqp_amd_batch *b, c_float *X, c_float *Y, c_float *info8,
                          c_float *DX, c_float *DY);
+/* The verdict on a point against the RAW problem the handle holds now (osqp_amd/csrc/batch_verify.h): the values on the
+ * setup pattern (shared, per member, or the common-K engine's one model), q, l, u as setup read them and every update
+ * has rewritten them.  It reads nothing of the scaling, rho, K^-1 or the stored iterates, needs no solve and writes
+ * nothing of the handle; all three engines serve it.  The point is X [batch][n], Y [batch][m], unscaled, the
+ * certificates DX [batch][n], DY [batch][m]; NULL = the handle's own (what osqp_amd_batch_get returns).  P is the full
+ * symmetric matrix of the stored triangle.  With ax = A x, z = clamp(ax, l, u), px = P x, aty = A'y, yp = max(y, 0),
+ * ym = max(-y, 0), V [batch][16] receives per member
+ *    0 obj = x'px / 2 + q'x         1 pri_res = |ax - z|oo         2 dua_res = |px + q + aty|oo
+ *    3 |ax|oo    4 |z|oo    5 |px|oo    6 |aty|oo    7 |q|oo
+ *    8 eps_pri = eps_abs + eps_rel max(3, 4)         9 eps_dua = eps_abs + eps_rel max(5, 6, 7)
+ *   10 comp = max_i max(yp_i (u_i - z_i), ym_i (z_i - l_i))
+ *   11 dual_obj = -x'px / 2 - sum_i (u_i yp_i - l_i ym_i)          12 gap = obj - dual_obj
+ *   13 optimal   1.0 when pri_res < eps_pri and dua_res < eps_dua (strict), else 0.0
+ *   14 prim_inf  the reference's is_primal_infeasible on DY, 15 dual_inf its is_dual_infeasible on DX, with identity
+ *                scaling on the raw data and the handle's eps_prim_inf / eps_dual_inf, its inequalities as coded.
+ * eps_abs, eps_rel: of this call; a negative value means the handle's setting.
+ * A bound is infinite as in the reference without scaling: u > 1e26, l < -1e26 (OSQP_INFTY * MIN_SCALING).  In 10 and 11
+ * a term whose multiplier part (yp_i, ym_i) is 0 counts 0; a nonzero multiplier part on an infinite bound makes 10
+ * +OSQP_INFTY, 11 -OSQP_INFTY and 12 +OSQP_INFTY.
+ * "NaN" is an IEEE NaN or the number OSQP_NAN, which the handle stores in X and Y of a member without a solution.  One
+ * in a member's x or y: slots 0-12 are OSQP_NAN and 13 is 0.0, 14 and 15 are computed all the same.  One in its dy (dx):
+ * 14 (15) is 0.0.
+ * A member's record is reproducible to the bit and does not depend on the batch around it or on the form of the call.
+ * Refusals, in this order, with nothing written: OSQP_WORKSPACE_NOT_INIT_ERROR for a NULL handle; in the _members forms
+ * the list's (OSQP_DATA_VALIDATION_ERROR); OSQP_DATA_VALIDATION_ERROR for a NULL V, a non-finite eps_abs or eps_rel and,
+ * in the _dev forms, a non-NULL pointer that is not device memory of the handle's device; -102 for a HIP failure. */
+c_int osqp_amd_batch_verify(osqp_amd_batch *b, const c_float *X, const c_float *Y, const c_float *DX, const c_float *DY,
+                            c_float eps_abs, c_float eps_rel, c_float *V /*[batch][16]*/);
 /* Device pointers of the result arrays, for device-side gathers (RCCL). */
 c_int osqp_amd_batch_device_ptrs(osqp_amd_batch *b, void **X, void **Y, void **info8);
 void  osqp_amd_batch_cleanup(osqp_amd_batch *b);
@@ -405,6 +433,10 @@ c_int osqp_amd_batch_tangent_dev(osqp_amd_batch *b, c_int ndir,
 /* osqp_amd_batch_get into caller-owned device arrays (NULL = skip): copies, which a later solve does not touch
  * (the arrays of osqp_amd_batch_device_ptrs are the handle's own and change with the next solve). */
 c_int osqp_amd_batch_get_dev(osqp_amd_batch *b, c_float *X, c_float *Y, c_float *info8, c_float *DX, c_float *DY);
+/* osqp_amd_batch_verify with every array on the device: the given X, Y, DX, DY are read in place, V [batch][16] arrives
+ * by a device-to-device copy.  The records carry the bits of the host form. */
+c_int osqp_amd_batch_verify_dev(osqp_amd_batch *b, const c_float *X, const c_float *Y, const c_float *DX,
+                                const c_float *DY, c_float eps_abs, c_float eps_rel, c_float *V /*[batch][16]*/);
 /* status_polish [batch] (32-bit ints on the device) as osqp_amd_batch_polish reports it; all 0 when polish has not
  * run since the last solve.  Runs no polish.  OSQP_WORKSPACE_NOT_INIT_ERROR as osqp_amd_batch_polish: no solve has
  * run on the current problem. */
@@ -516,6 +548,14 @@ c_int osqp_amd_batch_get_members(osqp_amd_batch *b, const c_int *members, c_int 
                                  c_float *info8, c_float *DX, c_float *DY);
 c_int osqp_amd_batch_get_members_dev(osqp_amd_batch *b, const c_int *members, c_int count, c_float *X, c_float *Y,
                                      c_float *info8, c_float *DX, c_float *DY);
+/* osqp_amd_batch_verify for the listed members: X, DX [count][n], Y, DY [count][m] (NULL = the handle's own rows of the
+ * listed members), V [count][16].  A listed member's record carries the bits of the whole-batch call on the same point. */
+c_int osqp_amd_batch_verify_members(osqp_amd_batch *b, const c_int *members, c_int count,
+                                    const c_float *X, const c_float *Y, const c_float *DX, const c_float *DY,
+                                    c_float eps_abs, c_float eps_rel, c_float *V /*[count][16]*/);
+c_int osqp_amd_batch_verify_members_dev(osqp_amd_batch *b, const c_int *members, c_int count,
+                                        const c_float *X, const c_float *Y, const c_float *DX, const c_float *DY,
+                                        c_float eps_abs, c_float eps_rel, c_float *V /*[count][16]*/);
 /* out [batch]: 1 where the member's results are those of a solve of the problem the handle holds now (what the polish,
  * adjoint and tangent forms above require of the members they list), 0 otherwise.  OSQP_DATA_VALIDATION_ERROR for a
  * NULL out.  Touches no GPU memory. */

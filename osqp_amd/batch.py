@@ -18,6 +18,9 @@ KktInfo = namedtuple("KktInfo", "builds kept npol members")     # BatchOSQP.kkt_
 Columns = namedtuple("Columns", "started packs ended")          # BatchOSQP.columns()
 SolveReport = namedtuple("SolveReport", "max_iter time_limit elapsed cut")   # BatchOSQP.solve_report()
 INFO_FIELDS = ["iter", "status_val", "obj_val", "pri_res", "dua_res", "rho_updates", "rho_estimate", "rho"]
+# the 16 slots of a record of BatchOSQP.verify (osqp_amd_batch_verify); the last three are verdicts
+VERIFY_FIELDS = ["obj", "pri_res", "dua_res", "norm_ax", "norm_z", "norm_px", "norm_aty", "norm_q", "eps_pri", "eps_dua", "comp",
+                 "dual_obj", "gap", "optimal", "prim_inf", "dual_inf"]
 
 
 # the arguments of each osqp_amd_batch_<name> after (handle, members, count): f = float array, i = c_int array,
@@ -45,6 +48,7 @@ _CALLS = {
     "adjoint_dev": "h" + "v" * 9, "adjoint_multi_dev": "hn" + "v" * 9, "tangent_dev": "hn" + "v" * 9,
     "get": "hfffff", "get_dev": "hvvvvv", "solved_members": "hi", "shape": "hii", "rounds": "hii",
     "member": "hnffffifffi", "device_ptrs": "hHHH", "check_dev_ptr": "hv",
+    "verify": "hffffddf", "verify_dev": "hvvvvddv", "verify_members": "hinffffddf", "verify_members_dev": "hinvvvvddv",
 }
 
 
@@ -912,6 +916,57 @@ class BatchOSQP:
         if dx is None or (self.m and dy is None):
             raise ValueError("tangent_into needs dx and, for m > 0, dy")
         self._tangent("tangent_into", True, members, (dQ, dL, dU, dPx, dAx), dict(dx=dx, dy=dy), active, status_tangent)
+
+    def verify(self, X=None, Y=None, DX=None, DY=None, eps_abs=None, eps_rel=None, members=None):
+        """The verdict on a point against the raw problem the handle holds now, computed on the device from P, q, A, l, u
+        alone -- nothing of the scaling, rho, K^-1 or the stored iterates (include/osqp_amd_batch.h: osqp_amd_batch_verify).
+        X [B, n], Y [B, m]: the point, unscaled; DX [B, n], DY [B, m]: certificates; None = the handle's own (what
+        results() returns).  Needs no solve and changes nothing in the handle.  Returns a namespace with one [B] array per
+        slot (VERIFY_FIELDS): obj, pri_res, dua_res, norm_ax, norm_z, norm_px, norm_aty, norm_q, eps_pri, eps_dua, comp,
+        dual_obj, gap (float) and optimal, prim_inf, dual_inf (bool), and V [B, 16], the records as the device wrote them.
+        eps_abs, eps_rel: the tolerances of eps_pri and eps_dua (None: the handle's settings).
+        members=: for the listed members only, with compact arrays [count, .]."""
+        V = self._verify("verify", False, members, None, X, Y, DX, DY, eps_abs, eps_rel)
+        out = SimpleNamespace(V=V)
+        for k, name in enumerate(VERIFY_FIELDS):
+            setattr(out, name, V[:, k] != 0.0 if k >= 13 else V[:, k].copy())
+        return out
+
+    def verify_into(self, V, X=None, Y=None, DX=None, DY=None, eps_abs=None, eps_rel=None, members=None):
+        """verify() between device arrays of the caller's: X, Y, DX, DY (None = the handle's own) are read in place, V
+        [B, 16] float64 ([count, 16] with members=) receives the records (VERIFY_FIELDS).  Ready on return."""
+        self._kernel_batch("verify_into", why=True)
+        if V is None or self._route(V=V, X=X, Y=Y, DX=DX, DY=DY) != "device":
+            raise ValueError("verify_into reads and writes device arrays (objects with __cuda_array_interface__); verify() "
+                             "takes and returns host arrays")
+        self._verify("verify_into", True, members, V, X, Y, DX, DY, eps_abs, eps_rel)
+
+    def _verify(self, call, dev, members, V, X, Y, DX, DY, eps_abs, eps_rel):
+        """The one body of verify (dev=False: host arrays in, the records [R, 16] out) and verify_into (dev=True)."""
+        self._kernel_batch(call, why=True)
+        mem = None if members is None else self._members(members, call)
+        if not dev and self._route(X=X, Y=Y, DX=DX, DY=DY) != "host":
+            raise ValueError("verify takes host arrays; verify_into reads and writes device arrays")
+        eps = []
+        for name, e in (("eps_abs", eps_abs), ("eps_rel", eps_rel)):
+            if e is not None and (isinstance(e, bool) or not isinstance(e, (int, float, np.integer, np.floating))
+                                  or not np.isfinite(e) or e < 0):
+                raise ValueError("%s must be a finite number >= 0 or None (the handle's setting), not %r" % (name, e))
+            eps.append(-1.0 if e is None else float(e))
+        R, n, m = self._rows(mem), self.n, self.m
+        want = "verify arrays must be X, DX [%s, %d], Y, DY [%s, %d]%s" % (
+            ("B", n, "B", m, "") if mem is None else (R, n, R, m, ": compact, for the %d listed members" % R))
+        arrays = self._given(dev, mem, want, (X, n, "X", True), (Y, m, "Y", bool(m)), (DX, n, "DX", True), (DY, m, "DY", bool(m)))
+        name, f, lead = self._entry("verify", mem, dev)
+        if dev:
+            out = device_view(V, (R, 16), "<f8", True, "V")
+        else:
+            V = np.zeros((R, 16))
+            arrays, out = [_p(a if a is None or a.shape[1] else None) for a in arrays], abi.fptr(V)
+        rc = f(self._h, *lead, *arrays, *eps, out)
+        if rc:
+            raise RuntimeError("%s failed (%d)%s" % (name, rc, _BAD_POINTER if dev and rc == 1 else ""))
+        return V
 
     def member_workspace(self, qp):
         """Test hook: member qp's workspace as the last setup / update / solve left it -- D, E, c, rho (scalar),

@@ -757,6 +757,7 @@ __global__ void k_clock_end(unsigned long long *clk) { clk[CK_END] = wall_clock6
 #include "batch_adjoint.h"
 #include "batch_tangent.h"
 #include "batch_common_kkt.h"
+#include "batch_verify.h"
 
 struct osqp_amd_batch {
   int engine = OSQP_AMD_BATCH_TILED;
@@ -2581,6 +2582,53 @@ extern "C" c_int osqp_amd_batch_get(osqp_amd_batch *b, c_float *X, c_float *Y, c
                                    c_float *DX, c_float *DY) {
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   return get_call(b, false, nullptr, 0, X, Y, info8, DX, DY);
+}
+
+// osqp_amd_batch_verify in its four forms (batch_verify.h): the 16-slot record of every member, or of the listed ones,
+// on the raw data the handle holds now.  X, Y, DX, DY are [R][.], R = count with a list and B without; NULL = the
+// handle's own io.Xo, io.Yo, io.DXo, io.DYo at the member's row.  The given arrays are read in place on the device route
+// and go through the staging of the derivative calls on the host route; k_batch_verify writes the records into that
+// staging, from where one copy takes them to V.  Needs no solve and writes nothing of the handle.
+static c_int verify_call(osqp_amd_batch *b, bool dev, const c_int *members, c_int count, const c_float *X, const c_float *Y,
+                         const c_float *DX, const c_float *DY, c_float eps_abs, c_float eps_rel, c_float *V) {
+  if (!V || !std::isfinite(eps_abs) || !std::isfinite(eps_rel)) return OSQP_DATA_VALIDATION_ERROR;
+  BCHK(hipSetDevice(b->device));
+  if (dev && dev_ptrs_check(b, {X, Y, DX, DY, V})) return OSQP_DATA_VALIDATION_ERROR;
+  const size_t R = members ? (size_t)count : (size_t)b->B, n = (size_t)b->n, m = (size_t)b->m;
+  if (members_put(b, members, count)) return OSQP_MEM_ALLOC_ERROR;
+  BVer v{};
+  v.eps_abs = eps_abs < 0 ? b->st.eps_abs : eps_abs; v.eps_rel = eps_rel < 0 ? b->st.eps_rel : eps_rel;
+  v.eps_pinf = b->st.eps_pinf; v.eps_dinf = b->st.eps_dinf;
+  const struct { const c_float *given; const double *own; const double **slot; size_t width; } ins[] = {
+      {X, b->io.Xo, &v.X, n}, {m ? Y : nullptr, b->io.Yo, &v.Y, m}, {DX, b->io.DXo, &v.DX, n}, {m ? DY : nullptr, b->io.DYo, &v.DY, m}};
+  size_t nin = 0;
+  if (!dev) for (const auto &t : ins) if (t.given) nin += R * t.width;
+  auto &sg = b->bd;
+  if (bd_reserve(&sg.in, &sg.in_cap, nin) || bd_reserve(&sg.out, &sg.out_cap, R * BV_SLOTS)) return OSQP_MEM_ALLOC_ERROR;
+  double *at = sg.in;
+  for (int k = 0; k < 4; k++) {
+    const auto &t = ins[k];
+    *t.slot = t.given;
+    if (!t.given) { *t.slot = t.own; v.own |= 1 << k; continue; }
+    if (dev || !t.width) continue;
+    BCHK(hipMemcpyAsync(at, t.given, R * t.width * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    *t.slot = at; at += R * t.width;
+  }
+  v.V = sg.out;
+  const size_t lds = bv_lds_bytes(b->n, b->m);
+  const int *list = members ? b->d_mlist : nullptr;
+  set_dynamic_lds(KFN(k_batch_verify), lds);
+  hipLaunchKernelGGL(k_batch_verify, dim3((unsigned)R), dim3(BV_NT), lds, b->stream, b->pat, b->io, v, list);
+  BCHK(hipGetLastError());
+  BCHK(hipMemcpyAsync(V, sg.out, R * BV_SLOTS * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, b->stream));
+  BCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+extern "C" c_int osqp_amd_batch_verify(osqp_amd_batch *b, const c_float *X, const c_float *Y, const c_float *DX,
+                                       const c_float *DY, c_float eps_abs, c_float eps_rel, c_float *V) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  return verify_call(b, false, nullptr, 0, X, Y, DX, DY, eps_abs, eps_rel, V);
 }
 
 // Test hook: one member's workspace as the last setup / update / solve left it (K^-1 un-permuted

@@ -1,8 +1,8 @@
 // batch_devio.h -- the entry points of a batch handle that take and return DEVICE arrays (osqp_amd_batch_*_dev),
 // included at the end of batch.hip.  Each one is its host twin with the host copies taken out, and shares the twin's
 // body in batch.hip, called with dev set (update_call, update_matrices_call, warm_start_call, get_call, adjoint_call,
-// tangent_call, bc_update_model): the same checks in the same order, the same kernels on the same workspace, the same
-// b->solved / b->polished / noncvx bookkeeping.  An entry point here is the NULL-handle check, the engine's refusal
+// tangent_call, verify_call, bc_update_model): the same checks in the same order, the same kernels on the same workspace,
+// the same b->solved / b->polished / noncvx bookkeeping.  An entry point here is the NULL-handle check, the engine's refusal
 // where the twin has one, and that call.  What a twin does on the host before it copies happens on the device:
 //   k_batch_check_bounds   counts the pairs l > u (after the clamp to +-OSQP_INFTY) of an update; one 4-byte read-back
 //                          decides whether the update is refused, before anything of the handle is written;
@@ -49,6 +49,12 @@ extern "C" c_int osqp_amd_batch_get_dev(osqp_amd_batch *b, c_float *X, c_float *
                                        c_float *DX, c_float *DY) {
   if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
   return get_call(b, true, nullptr, 0, X, Y, info8, DX, DY);
+}
+
+extern "C" c_int osqp_amd_batch_verify_dev(osqp_amd_batch *b, const c_float *X, const c_float *Y, const c_float *DX,
+                                           const c_float *DY, c_float eps_abs, c_float eps_rel, c_float *V) {
+  if (!b) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  return verify_call(b, true, nullptr, 0, X, Y, DX, DY, eps_abs, eps_rel, V);
 }
 
 // status_polish as osqp_amd_batch_polish reports it, without running polish: all 0 (not tried) when polish has not

@@ -6,7 +6,7 @@
 // solved flag and status_polish keep their bits.
 //
 // A form shares the twin's body in batch.hip (update_call, update_matrices_call, update_rho_call, warm_start_call,
-// get_call, adjoint_call, tangent_call),
+// get_call, adjoint_call, tangent_call, verify_call),
 // which takes the list; an entry point here is MEMBERS_OPEN -- the NULL handle (OSQP_WORKSPACE_NOT_INIT_ERROR), the
 // list (OSQP_DATA_VALIDATION_ERROR), the engine's refusal where the twin has one, in this order and with nothing
 // written -- and that call, after which the twin's own refusals come in the twin's order.  A list of all B members
@@ -120,6 +120,19 @@ extern "C" c_int osqp_amd_batch_get_members_dev(osqp_amd_batch *b, const c_int *
                                                 c_float *info8, c_float *DX, c_float *DY) {
   MEMBERS_OPEN()
   return get_call(b, true, list, count, X, Y, info8, DX, DY);
+}
+// the records of the listed members: X, DX [count][n], Y, DY [count][m] (NULL = the handle's own rows of them), V [count][16]
+extern "C" c_int osqp_amd_batch_verify_members(osqp_amd_batch *b, const c_int *members, c_int count, const c_float *X,
+                                               const c_float *Y, const c_float *DX, const c_float *DY, c_float eps_abs,
+                                               c_float eps_rel, c_float *V) {
+  MEMBERS_OPEN()
+  return verify_call(b, false, list, count, X, Y, DX, DY, eps_abs, eps_rel, V);
+}
+extern "C" c_int osqp_amd_batch_verify_members_dev(osqp_amd_batch *b, const c_int *members, c_int count, const c_float *X,
+                                                   const c_float *Y, const c_float *DX, const c_float *DY, c_float eps_abs,
+                                                   c_float eps_rel, c_float *V) {
+  MEMBERS_OPEN()
+  return verify_call(b, true, list, count, X, Y, DX, DY, eps_abs, eps_rel, V);
 }
 #undef MEMBERS_OPEN
 
