@@ -138,6 +138,36 @@ c_int osqp_amd_sens_info(OSQPWorkspace *work, c_int out[4]);
  * [1] the linear-solve form the last one took (hipeng_resident_info [9]; -1: none yet, or it could not be read), [2] its active
  * rows, [3] its resident launches that gave up plus its negative-curvature stops (0: the form served every solve; -1 unread) */
 c_int osqp_amd_polish_info(OSQPWorkspace *work, c_int out[4]);
+/* The verdict on a point against the RAW problem the workspace holds now, computed on the device from P, q, A, l, u as the caller gave
+ * and last updated them and from the unscaled point alone -- nothing of D, E, c, rho, the linear-solve form or the engine's iterates:
+ * for one QP what osqp_amd_batch_verify (osqp_amd_batch.h) is for a batch member.  V receives the same 16 slots with the same
+ * definitions:
+ *    0 obj = x'Px / 2 + q'x      1 pri_res = |Ax - z|oo, z = clamp(Ax, l, u)      2 dua_res = |Px + q + A'y|oo
+ *    3 |Ax|oo   4 |z|oo   5 |Px|oo   6 |A'y|oo   7 |q|oo     8 eps_pri = eps_abs + eps_rel max(3, 4)
+ *    9 eps_dua = eps_abs + eps_rel max(5, 6, 7)      10 comp = max_i max(y+_i (u_i - z_i), y-_i (z_i - l_i))
+ *   11 dual_obj = -x'Px / 2 - sum_i (u_i y+_i - l_i y-_i)      12 gap = obj - dual_obj
+ *   13 optimal: 1 < 8 and 2 < 9      14 prim_inf: is_primal_infeasible on dy      15 dual_inf: is_dual_infeasible on dx
+ * (13-15 are 1.0 or 0.0; the two tests are auxil.c:361-512 with D = E = I, c = 1 and settings->eps_prim_inf / eps_dual_inf).  A bound
+ * with |bound| > 1e26 is infinite: a term of 10 or 11 whose multiplier part is 0 counts 0, a nonzero multiplier part on an infinite
+ * bound makes 10 +OSQP_INFTY, 11 -OSQP_INFTY, 12 +OSQP_INFTY.  "NaN" is an IEEE NaN or the number OSQP_NAN: one in x or y makes 0-12
+ * OSQP_NAN and 13 0, one in dy / dx makes 14 / 15 0.
+ * x, dx [n], y, dy [m]: unscaled host arrays; NULL = the workspace's own at the moment of the call -- work->solution->x,
+ * work->solution->y, work->delta_x, work->delta_y.  eps_abs, eps_rel: negative = settings->eps_abs / eps_rel.  Needs no solve; m = 0 is
+ * served; returns with the engine's stream synchronised.
+ * Returns, in this order and with nothing done: OSQP_WORKSPACE_NOT_INIT_ERROR for a NULL workspace or one without an engine;
+ * OSQP_DATA_VALIDATION_ERROR for a NULL V or a non-finite eps_abs / eps_rel; OSQP_MEM_ALLOC_ERROR when the host or the device has no room
+ * for the call's arrays (the workspace stays usable); -102 when a HIP call fails.
+ * The first call builds the device side (patterns, copies of the raw values); each osqp_update_lin_cost, _bounds, _lower_bound,
+ * _upper_bound, _P, _A, _P_A marks what it changes and the next call copies those parts again, nothing else.  osqp_update_rho, the warm
+ * starts and the osqp_update_<setting> calls mark nothing; a workspace that never calls this allocates and launches nothing for it.
+ * Nothing of the workspace changes: x, y, z, solution, info, the engine's iterates, rho, the statistics and a live KKT instance of the
+ * derivatives keep their bits.  A record is reproducible to the bit: it depends on the pattern, the values and the point, not on the
+ * linear-solve form, the device or earlier calls. */
+c_int osqp_amd_verify(OSQPWorkspace *work, const c_float *x, const c_float *y, const c_float *dx, const c_float *dy,
+                      c_float eps_abs, c_float eps_rel, c_float V[16]);
+/* for the tests: out[0] osqp_amd_verify calls served since setup, [1] uploads of P values, [2] of A values, [3] of q / l / u (one
+ * counter, each vector counts one).  OSQP_WORKSPACE_NOT_INIT_ERROR / OSQP_DATA_VALIDATION_ERROR as above (NULL out). */
+c_int osqp_amd_verify_info(OSQPWorkspace *work, c_int out[4]);
 /* The options above are the DEFAULTS a new workspace / plugin instance copies at creation; afterwards
  * each instance has its own (no knob is shared between live workspaces).  These two read / change the
  * copy of one workspace (the device cannot be changed after setup). */

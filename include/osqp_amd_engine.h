@@ -258,6 +258,27 @@ int hipsens_grad(hipsens *s, hipeng *pe, const csc *P, const csc *A, const c_flo
 int hipsens_tan_rhs(hipsens *s, hipeng *pe, const csc *P, const csc *A, c_int ndir, const c_float *dq, const c_float *dl,
                     const c_float *du, const c_float *dPx, const c_float *dAx, c_float *g);
 
+/* The device side of osqp_amd_verify (csrc/verify.h: k_ver_point, k_ver_cert, k_ver_combine).  One hipver per workspace, created at its
+ * first osqp_amd_verify call and kept until cleanup; every call runs on the stream of `e`, the workspace's engine, and returns with it
+ * synchronised.  It holds the patterns of triu(P) and A (hipver_create reads the CSC pointers and indices only, and refuses arrays
+ * that are not a pattern with HIPENG_ERR_ARG), device copies of the raw values and the partial records; nothing of `e` is read or
+ * written.  HIPENG_ERR_ALLOC: the host or the device has no room (the caller destroys what was made).
+ * hipver_upload: the raw values named by `parts` (bit 0 Px [nnzP], 1 Ax [nnzA], 2 q [n], 3 l [m], 4 u [m]) from host arrays.
+ * hipver_run: the record V [16] of the host arrays x, dx [n], y, dy [m] against the values last uploaded.
+ * hipver_info (no device, no object): the kernels' constants -- out[0] threads per workgroup, [1] rows (or columns) a workgroup takes
+ * per sweep, [2] the most workgroups of a launch, [3] the number of entries above which a row or column is taken by a whole workgroup.
+ * The grid of a launch is min(out[2], ceil(max(n, m) / out[1])): it follows from the sizes and these constants alone.
+ * hipver_uploads: uploads since create of P values, of A values, of q / l / u (one counter: each vector counts one). */
+typedef struct hipver hipver;
+int hipver_create(hipver **out, const csc *P, const csc *A, int device);
+void hipver_destroy(hipver *v);
+int hipver_upload(hipver *v, hipeng *e, int parts, const c_float *Px, const c_float *Ax, const c_float *q, const c_float *l,
+                  const c_float *u);
+int hipver_run(hipver *v, hipeng *e, const c_float *x, const c_float *y, const c_float *dx, const c_float *dy, c_float eps_abs,
+               c_float eps_rel, c_float eps_prim_inf, c_float eps_dual_inf, c_float *V);
+int hipver_info(int out[4]);
+int hipver_uploads(const hipver *v, c_int out[3]);
+
 #ifdef __cplusplus
 }
 #endif

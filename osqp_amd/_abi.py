@@ -190,4 +190,8 @@ def bind_api(lib, prefix=""):
         api["sens_info"] = fn("osqp_amd_sens_info", c_int, W, I)
         api["polish_info"] = fn("osqp_amd_polish_info", c_int, W, I)
         api["sens_engine"] = fn("osqp_amd_sens_engine", C.c_void_p, W)
+    if hasattr(lib, prefix + "osqp_amd_verify"):
+        F, I = c_float_p, c_int_p
+        api["verify"] = fn("osqp_amd_verify", c_int, W, F, F, F, F, c_float, c_float, F)
+        api["verify_info"] = fn("osqp_amd_verify_info", c_int, W, I)
     return api

@@ -5265,4 +5265,5 @@ extern "C" int hipeng_kernel_bytes(hipeng *e, int which, double *bytes) {
 
 // ---- ONE QP over several GPUs by rows, driven from C (include/osqp_amd_rowpart.h) ----
 #include "kkt_sens.h"
+#include "verify.h"
 #include "rowpart_native.h"

@@ -131,9 +131,16 @@ typedef struct {
   sens_state *sens;       /* workspace view: solution derivatives (NULL until the first call) */
   c_int sens_ready;       /* an osqp_solve has completed and no data, rho or iterate was changed since */
   c_int pol_info[4];      /* workspace view: run_polish's last instance, as osqp_amd_polish_info reports it */
+  hipver *ver;            /* workspace view: the device side of osqp_amd_verify (csrc/verify.h; NULL until the first call) */
+  c_int ver_stale;        /* VER_P .. VER_U: parts of the raw problem changed since that side copied them (ver_mark) */
+  c_int ver_calls;        /* osqp_amd_verify calls served */
 } hip_pcg_solver;
 
 #define PCG(work) ((hip_pcg_solver *)((work)->linsys_solver))
+
+/* the parts of the raw problem osqp_amd_verify keeps on the device (the bits of hipver_upload) and their one writer */
+enum { VER_P = 1, VER_A = 2, VER_Q = 4, VER_L = 8, VER_U = 16, VER_ALL = 31 };
+static void ver_mark(OSQPWorkspace *w, c_int parts) { PCG(w)->ver_stale |= parts; }
 
 static c_int pcg_solve(LinSysSolver *self, c_float *b) {
   hip_pcg_solver *s = (hip_pcg_solver *)self;
@@ -182,6 +189,7 @@ static void pcg_free(LinSysSolver *self) {
   hip_pcg_solver *s = (hip_pcg_solver *)self;
   if (!s) return;
   sens_free(s->sens);
+  hipver_destroy(s->ver);
   hipeng_destroy(s->eng);
   hipeng_destroy(s->aux);
   c_free(s->rho_tmp);
@@ -918,6 +926,7 @@ c_int osqp_update_lin_cost(OSQPWorkspace *w, const c_float *q_new) {
   NEED_WORK(w);
   upd_begin(w);
   sens_invalidate(w);
+  ver_mark(w, VER_Q);
   const c_int n = w->data->n;
   memcpy(w->data->q, q_new, (size_t)n * sizeof(c_float));
   if (w->settings->scaling) {
@@ -944,6 +953,7 @@ c_int osqp_update_bounds(OSQPWorkspace *w, const c_float *l_new, const c_float *
   const c_int m = w->data->m;
   for (c_int i = 0; i < m; i++)
     if (l_new[i] > u_new[i]) { fprintf(stderr, "ERROR in osqp_update_bounds: lower bound must be lower than or equal to upper bound\n"); return 1; }
+  ver_mark(w, VER_L | VER_U);
   memcpy(w->data->l, l_new, (size_t)m * sizeof(c_float));
   memcpy(w->data->u, u_new, (size_t)m * sizeof(c_float));
   if (w->settings->scaling) { memcpy(PCG(w)->rawl, l_new, (size_t)m * sizeof(c_float)); memcpy(PCG(w)->rawu, u_new, (size_t)m * sizeof(c_float)); }
@@ -958,6 +968,7 @@ c_int osqp_update_lower_bound(OSQPWorkspace *w, const c_float *l_new) {
   NEED_WORK(w);
   upd_begin(w);
   const c_int m = w->data->m;
+  ver_mark(w, VER_L);
   memcpy(w->data->l, l_new, (size_t)m * sizeof(c_float));
   if (w->settings->scaling) memcpy(PCG(w)->rawl, l_new, (size_t)m * sizeof(c_float));
   if (w->settings->scaling) for (c_int i = 0; i < m; i++) w->data->l[i] = w->data->l[i] * w->scaling->E[i];
@@ -972,6 +983,7 @@ c_int osqp_update_upper_bound(OSQPWorkspace *w, const c_float *u_new) {
   NEED_WORK(w);
   upd_begin(w);
   const c_int m = w->data->m;
+  ver_mark(w, VER_U);
   memcpy(w->data->u, u_new, (size_t)m * sizeof(c_float));
   if (w->settings->scaling) memcpy(PCG(w)->rawu, u_new, (size_t)m * sizeof(c_float));
   if (w->settings->scaling) for (c_int i = 0; i < m; i++) w->data->u[i] = w->data->u[i] * w->scaling->E[i];
@@ -1019,6 +1031,7 @@ static c_int patch(OSQPWorkspace *w, const c_float *Px, const c_int *Pi, c_int P
    * the unscaled problem is kept as given, patched, uploaded and re-equilibrated on the GPU. */
   csc *P = w->settings->scaling ? s->rawP : w->data->P;
   csc *A = w->settings->scaling ? s->rawA : w->data->A;
+  ver_mark(w, (doP ? VER_P : 0) | (doA ? VER_A : 0));
   if (doP) {
     if (Pi) for (c_int k = 0; k < Pn; k++) P->x[Pi[k]] = Px[k];
     else    for (c_int k = 0; k < nnzP; k++) P->x[k] = Px[k];
@@ -1558,6 +1571,54 @@ c_int osqp_amd_sens_info(OSQPWorkspace *w, c_int out[4]) {
   out[1] = ss && ss->ls ? 1 : 0;
   out[2] = ss && ss->ls ? ss->pol.n_low + ss->pol.n_upp : 0;
   out[3] = ss ? ss->solves : 0;
+  return 0;
+}
+
+/* ------------------------------------------------------------------------ */
+/* osqp_amd_verify (include/osqp_amd.h): a point against the raw problem, on   */
+/* the device (csrc/verify.h).  Reads the workspace, writes nothing of it.     */
+/* ------------------------------------------------------------------------ */
+c_int osqp_amd_verify(OSQPWorkspace *w, const c_float *x, const c_float *y, const c_float *dx, const c_float *dy,
+                      c_float eps_abs, c_float eps_rel, c_float V[16]) {
+  NEED_WORK(w);
+  if (!w->linsys_solver || !PCG(w)->eng) {
+    fprintf(stderr, "ERROR in osqp_amd_verify: the workspace has no engine\n");
+    return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  }
+  if (!V || !isfinite(eps_abs) || !isfinite(eps_rel)) {
+    fprintf(stderr, "ERROR in osqp_amd_verify: %s\n", !V ? "missing argument" : "eps_abs and eps_rel must be finite");
+    return OSQP_DATA_VALIDATION_ERROR;
+  }
+  hip_pcg_solver *s = PCG(w);
+  int rc = 0;
+  if (!s->ver) {
+    rc = hipver_create(&s->ver, w->data->P, w->data->A, (int)s->opt.device);
+    if (rc) { hipver_destroy(s->ver); s->ver = NULL; }
+    s->ver_stale = VER_ALL;
+  }
+  /* the raw problem as the caller last gave it: the copies kept beside the scaled data, or the data itself */
+  const c_int raw = w->settings->scaling != 0;
+  if (!rc && s->ver_stale) {
+    rc = hipver_upload(s->ver, s->eng, (int)s->ver_stale, raw ? s->rawP->x : w->data->P->x, raw ? s->rawA->x : w->data->A->x,
+                       raw ? s->rawq : w->data->q, raw ? s->rawl : w->data->l, raw ? s->rawu : w->data->u);
+    if (!rc) s->ver_stale = 0;
+  }
+  if (!rc)
+    rc = hipver_run(s->ver, s->eng, x ? x : w->solution->x, y ? y : w->solution->y, dx ? dx : w->delta_x, dy ? dy : w->delta_y,
+                    eps_abs < 0 ? w->settings->eps_abs : eps_abs, eps_rel < 0 ? w->settings->eps_rel : eps_rel,
+                    w->settings->eps_prim_inf, w->settings->eps_dual_inf, V);
+  if (rc == HIPENG_ERR_ALLOC) return OSQP_MEM_ALLOC_ERROR;
+  if (rc) return HIPENG_ERR_HIP;
+  s->ver_calls++;
+  return 0;
+}
+
+c_int osqp_amd_verify_info(OSQPWorkspace *w, c_int out[4]) {
+  NEED_WORK(w);
+  if (!w->linsys_solver || !PCG(w)->eng) return OSQP_WORKSPACE_NOT_INIT_ERROR;
+  if (!out) return OSQP_DATA_VALIDATION_ERROR;
+  out[0] = PCG(w)->ver_calls; out[1] = out[2] = out[3] = 0;
+  if (PCG(w)->ver) hipver_uploads(PCG(w)->ver, out + 1);
   return 0;
 }
 

@@ -14,6 +14,7 @@ import numpy as np
 from scipy import sparse
 
 from . import _abi as abi
+from .batch import VERIFY_FIELDS
 
 
 class Results(SimpleNamespace):
@@ -315,6 +316,53 @@ class SolverHandle:
         """Raw engine handle of the live KKT instance of adjoint() / tangent() (None: none alive), as OSQP.engine() is of
         the handle's own engine."""
         return self._sens("sens_engine")(self._work)
+
+    # ----------------------------------------------------------------- verify
+    def verify(self, x=None, y=None, dx=None, dy=None, eps_abs=None, eps_rel=None):
+        """The verdict on a point against the raw problem the handle holds now, computed on the device from P, q, A, l, u as
+        given and last updated -- nothing of the scaling, rho, the linear-solve form or the engine's iterates
+        (include/osqp_amd.h: osqp_amd_verify).  x [n], y [m]: the point, unscaled; dx [n], dy [m]: certificates; None = the
+        handle's own, what solve() returned as x, y, dual_inf_cert, prim_inf_cert.  eps_abs, eps_rel: the tolerances of
+        eps_pri and eps_dua (None: the handle's settings).  Needs no solve and changes nothing in the handle.  Returns a
+        namespace with one scalar per slot (batch.VERIFY_FIELDS): obj, pri_res, dua_res, norm_ax, norm_z, norm_px, norm_aty,
+        norm_q, eps_pri, eps_dua, comp, dual_obj, gap (float) and optimal, prim_inf, dual_inf (bool), and V [16], the record
+        as the device wrote it."""
+        if "verify" not in self._api:
+            raise NotImplementedError("this library has no osqp_amd_verify")
+        arr = {}
+        for name, a, k in (("x", x, self.n), ("y", y, self.m), ("dx", dx, self.n), ("dy", dy, self.m)):
+            if a is not None:
+                a = abi.as_f64(a)
+                if a.shape != (k,):
+                    raise ValueError("%s must have %d entries, not shape %s" % (name, k, a.shape))
+                if k == 0:
+                    a = np.zeros(1)      # (a pointer that is not NULL: the array is the caller's, empty as it is)
+            arr[name] = a
+        eps = []
+        for name, e in (("eps_abs", eps_abs), ("eps_rel", eps_rel)):
+            if e is not None and not (np.isfinite(e) and e >= 0):
+                raise ValueError("%s must be a finite number >= 0 or None (the handle's setting), not %r" % (name, e))
+            eps.append(-1.0 if e is None else float(e))
+        V = np.zeros(len(VERIFY_FIELDS))
+        rc = self._api["verify"](self._work, _opt(arr["x"]), _opt(arr["y"]), _opt(arr["dx"]), _opt(arr["dy"]), eps[0], eps[1],
+                                 abi.fptr(V))
+        if rc:
+            raise RuntimeError("osqp_amd_verify failed (%d)" % rc)
+        out = SimpleNamespace(V=V)
+        for k, name in enumerate(VERIFY_FIELDS):
+            setattr(out, name, bool(V[k] != 0.0) if k >= 13 else float(V[k]))
+        return out
+
+    def verify_info(self):
+        """For the tests: verify() calls served since setup and, since the first of them, uploads of P values, of A values
+        and of q / l / u (one counter; each vector counts one)."""
+        if "verify_info" not in self._api:
+            raise NotImplementedError("this library has no osqp_amd_verify_info")
+        out = np.zeros(4, np.int64)
+        rc = self._api["verify_info"](self._work, abi.iptr(out))
+        if rc:
+            raise RuntimeError("osqp_amd_verify_info failed (%d)" % rc)
+        return dict(calls=int(out[0]), uploads_P=int(out[1]), uploads_A=int(out[2]), uploads_qlu=int(out[3]))
 
     # -------------------------------------------------------------- accessors
     @property
