@@ -95,7 +95,7 @@ typedef struct {
   c_int pcg_forced;
   c_int graph_launches;
   c_int host_syncs;
-  c_int resident;        /* 1: the linear solves run as one resident launch each (K in registers, engine.hip k_pcg_resident);
+  c_int resident;        /* 1: the linear solves run as one resident launch each (K in registers, engine_pcg_resident.h k_pcg_resident);
                             0: launch-per-step PCG kernels (problem too large for the register files, OSQP_AMD_RESIDENT=0,
                             or a resident launch found the GPU shared and the engine fell back) */
 } osqp_amd_stats;

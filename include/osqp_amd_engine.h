@@ -171,7 +171,7 @@ c_int hipeng_elim_count(hipeng *e);
  * eliminated variable hold rho, 0, 0 and whatever was there.  An error when no variable is eliminated (the arrays do not exist). */
 int hipeng_elim_peek(hipeng *e, int which, c_float *out);
 /* Resident PCG (the reduced matrix K = P + sigma I + A' rho A held in registers, one launch per linear
- * solve; engine.hip, k_pcg_resident).  out[0] structures built, [1] in use, [2] entries of K per thread,
+ * solve; engine_pcg_resident.h, k_pcg_resident).  out[0] structures built, [1] in use, [2] entries of K per thread,
  * [3] workgroups, [4] nnz(K), [5] LDS bytes per workgroup, [6] PCG iterations of the most recent linear
  * solve, [7] pipelined recurrences switched off for the current K, [8] true-residual checks that failed since create
  * (each continued its solve from the true residual), [9] form (1: k_pcg_resident, 2: k_pcg_blockres), [10] launches that

@@ -28,6 +28,25 @@
 // per workgroup and re-reduced in a fixed order by every workgroup of the next
 // kernel, so results are bitwise reproducible and PCG scalars never visit the
 // host.
+//
+// What stays in this file: the shared descriptors and device building blocks, the launch-per-step PCG with k_pcg_init and
+// k_admm_finalize, the kernels that belong to no single form, and the host side.  The device code of the one-launch forms and
+// the test hooks stand in fragments, each included exactly once at the place where its text belongs.  They are pieces of this
+// file, not headers that compile alone; each opens with what it holds and what must stand before it.  In include order:
+//   engine_pcg_resident.h   resident PCG: ResCtx, the bounded waits, k_form_K, k_form_K_lists, k_pcg_resident
+//   engine_pcg_blockres.h   block-resident PCG: BrCtx, k_pcg_blockres
+//   engine_block_direct.h   block-direct solve: BdCtx, k_blk_*, k_cpl_*, k_cap_diag, k_cap_step
+//   dense_direct.h          dense-direct solve: DdCtx, k_dd_*
+//   engine_block_check.h    block-direct solve: k_blk_check, k_cap_check (they use dense_direct.h's probe vector)
+//   dense_direct_host.h     build_dense_direct, dd_refresh, launch_dense_direct, the dense-direct test hooks
+//   engine_hooks.h          entry points for tests and measurements
+//   kkt_sens.h              derivatives of the solution (k_sens_*)
+//   verify.h                a point against the raw problem (k_ver_*)
+//   rowpart_native.h        one QP over several GPUs by rows (k_rp_*)
+// The order is pinned: the kernels, and the instantiations of the kernel templates, stand in the code object in the order of
+// the text, the hand-tuned kernels are sensitive to their place there, and the check of a change that only moves text is that
+// the device assembly of this translation unit stays what it was.  A new fragment goes where its text would have gone.
+
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <new>
@@ -1266,1346 +1285,12 @@ __global__ void __launch_bounds__(TB) k_admm_finalize(Ctx c) {
   TLK_AT(8, 0); TLK_LAST(1);
   TLK_FLUSH(c, 110, 9);
 }
-
-
-// ---------------------------------------------------------------------------
-// Resident PCG: the whole linear solve of one ADMM iteration in ONE launch.
-//
-// For problems whose reduced matrix K = P + sigma I + A' diag(rho) A fits the chip's register files
-// (n <= 15616, nnz(K) <= 256 workgroups x 448 threads x 64 entries) every workgroup keeps a block of
-// rows of K -- values and 16-bit column positions -- in registers for the whole solve, one workgroup per CU:
-// wavefronts 1..7 hold the entries and multiply, wavefront 0 owns the rows' vector elements, decides and talks.
-// The workgroups exchange vectors through memory INSIDE the launch instead of ending a kernel:
-//   (1) an n-vector: every workgroup stores its rows write-through (sc1), drains, raises its flag; wavefront 0
-//       polls the 256 flags; then all wavefronts read the vector into LDS with L1-bypassing (sc1) loads -- no
-//       fence (MI355X_MICROARCH.md, visibility: the flag/sc1 row).  3.5 us alone (tools/exchange_probe.hip),
-//       4.6 us in the loop, against 12.2 us for a k_cg_A/k_cg_B pair;
-//   (2) three scalars per workgroup as 8-byte {32 bits, tag} granules, stored and polled with agent-scope atomics.
-// Rules the protocol learned the hard way: no 128-byte line of an exchange buffer is written by two
-// CUs; a tag never shares a 16-byte store with data it vouches for in the other half; polls are 4- or 8-byte atomic
-// loads, never 16-byte buffer loads.
-// Recurrences: pipelined CG (Ghysels-Vanroose, ONE exchange per iteration) as long as its true-residual checks
-// pass, else Chronopoulos-Gear with a fresh product (the recurrences, scalars and stop rule of k_cg_A / k_cg_B:
-// cg_step).  The operator is the explicit K (k_form_K re-forms its values whenever rho, sigma or the matrices change).
-// Every wait is bounded in time: if the grid is not co-resident (another process or stream holds CUs) the
-// launch gives up, sets State::res_fail, and the host continues with the launch-per-step kernels.
-// ---------------------------------------------------------------------------
-#define RES_TB 512
-#define RES_PT (RES_TB - 64)   // threads that hold entries of K (wavefronts 1..7); wavefront 0 owns the rows and talks
-#define RES_MAXROWS 61    // rows per workgroup: they and the three riding partials are stored by the 64 lanes of wavefront 0
-#define RES_MAXN (RES_MAXROWS * 256)
-#define RES_MAXPAD 16384  // longest exchanged vector (doubles, lines padded)
-#define RES_MAXLD (RES_MAXPAD / 2 / RES_TB)   // 16-byte loads per thread that sweep the exchanged vector
-#define RES_WAIT_TICKS 2000000LL      // 20 ms of the 100 MHz wall clock: the limit of every wait inside a resident launch (the grid may still be
-                                      // arriving in the first one; a later one that long means a workgroup is gone).  Two readings 16 rounds apart
-                                      // must both say so, and a reading that cannot be (negative, or hours) restarts the wait's clock.
-#define RES_SLOW_TICKS 5000LL         // a wait that ended well after more than 50 us is counted (State::res_slow)
-#define AUX_SC1 16
-#define AUX_VOL ((int)0x80000000)     // volatile: a poll load the compiler must neither hoist out of its loop nor merge
-#define RES_DBG 16                    // ints per workgroup in ResCtx::dbg
-#define RES_PRED_WINDOW 16            // solves after which the predicted last trip is judged for this K: more misses than hits switch it off
-#define RES_FSTRIDE 32   // 4-byte words between two workgroups' flags: a 128-byte line each
-#define RES_GSTRIDE 16   // doubles between two workgroups' granule slots: a 128-byte line each (no line is written by two CUs)
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-struct ResWG { int r0, nr, cnt, pos; };   // first row, rows (<= RES_MAXROWS), entries of K, first position in the exchanged vector
-struct ResCtx {
-  int nwg, E, npad;                  // workgroups, entries per thread, length of the exchanged vector: every workgroup's rows + its three
-                                     // dot partials, padded to whole 128-byte lines (a line written by two CUs can lose one of the writes)
-  int npw;                           // wavefronts of each workgroup that poll: ceil(nwg / 64), one flag (or one workgroup's granules) per lane
-  const unsigned short *rowpos;      // position of row j in that vector
-  int pipe;                          // 1: pipelined recurrences where they pass their checks (OSQP_AMD_RESIDENT_PIPE=0: never)
-  int predict;                       // 1: the pipelined phase predicts its last trip and sends x - x0 in it (OSQP_AMD_RESIDENT_PREDICT=0: never)
-  double pred_margin;                // ... when the extrapolated ||r||^2 is <= pred_margin * tol2 (OSQP_AMD_RESIDENT_PREDICT_MARGIN, default 1)
-  int u0_direct;                     // 1: the first product reads u0 from global memory instead of exchanging it
-  int inject;                        // test hook (OSQP_AMD_RESIDENT_INJECT=k): in the launch of ADMM iteration k one workgroup walks away,
-                                     // the others' waits time out -- the give-up path on demand
-  const ResWG *wg;
-  const int *ppos;                   // [nwg]: wg[o].pos + wg[o].nr, where workgroup o's three riding partials sit in the exchanged vector
-  double *val;                       // [nwg][E][RES_PT]: entry t*E + k of the workgroup's row-major list at (k, t)
-  const unsigned short *col;         // same layout: POSITION of the entry's column in the exchanged vector
-  const unsigned char *rowl;         // same layout: local row of the entry
-  const int *krp, *kcj, *kps, *kdst; // K row by row for k_form_K: row pointers (n + 1), column, slot in M of P(i,j) (-1: none), slot in val
-  const unsigned long long *brk;     // [nwg][RES_PT]: bit k set = entry k ends a row segment of this thread
-  const unsigned short *slot0;       // [nwg][RES_PT]: first segment slot of the thread
-  const unsigned short *segrow;      // [nwg][RES_MAXROWS + 1]: first segment slot of each local row
-  double *ubuf;                      // 2 x npad doubles (parity of the tag)
-  unsigned *flags;                   // nwg x RES_FSTRIDE words (one 128-byte line each)
-  int *dbg;                          // nwg x RES_DBG, written by a launch that gives up: see res_note()
-  double *sbuf;                      // 2 x nwg x RES_GSTRIDE 8-byte words: six granules {32 bits of a double, tag} per workgroup, one line each
-  double *r0pos;                     // npad doubles: r0 in the exchanged vector's layout, left by k_pcg_init<*, true> (null: r0 and u0 come from
-                                     // init_r / init_z, OSQP_AMD_INIT_RESIDENT_STORES=0)
-  const int *kcp, *kcm, *kca;        // contribution lists of k_form_K_lists (null: k_form_K forms K): entry e of K (the order of kcj) sums the terms
-                                     // kcp[e] .. kcp[e + 1], term q = rhoe[M.col[kcm[q]] - n] * (M.val[kcm[q]] * A.val[kca[q]]), rows of A ascending
-};
-
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t res_rsrc(const void *p, size_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-
-// ---- waits inside a resident launch (k_pcg_resident, k_pcg_blockres) ----
-// Every wait is a bounded spin of ceil(nwg / 64) wavefronts, one polled workgroup per lane, re-loading only what is still
-// missing.  Every 16th round the wave looks at the clock and at the give-up word; every 64th the workgroup stores its own
-// flag / granules again (idempotent: should a store ever go missing, the others do not hang on it) -- counted in
-// State::res_repub; a wait that ends well after more than 50 us is counted in State::res_slow.
-// res_spin_check: 0 = keep polling, 1 = this wait has timed out, 2 = another workgroup gave up.
-__device__ __forceinline__ int res_spin_check(State *st, long long &t0, int &late) {
-  const long long now = wall_clock64();
-  const long long el = now - t0;
-  if (el < 0 || el > (1LL << 40)) { t0 = now; late = 0; return 0; }      // not a time: start this wait's clock again
-  if (__hip_atomic_load(&st->res_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return 2;
-  if (el > RES_WAIT_TICKS) { if (late) return 1; late = 1; } else late = 0;
-  return 0;
-}
-// What a workgroup leaves for the host when it gives up (ResCtx::dbg, RES_DBG ints per workgroup):
-//   [0] exchange number  [1] mode  [2] PCG iterations          (written at the kernel's exit)
-//   [3] 1 / 2: its flag / granule wait timed out, 3: it left because another workgroup had given up
-//   [4] first workgroup it still missed (-1: none)   [5] the word it last read from that workgroup (flag, or a granule's tag)
-//   [6] ticks it had waited (100 MHz)   [7] XCC id   [8] clock at the give-up (low 32 bits)   [9] rounds   [10] granule index
-// Publishing time of a workgroup's last flag = [8] - [6]: its wait started right behind its own store.
-__device__ __forceinline__ void res_note(State *st, int *dbg, int g, int verdict, int kind, int nx, int first, unsigned seen, long long t0, unsigned rounds, int gidx) {
-  if (verdict == 1 && atomicCAS(&st->res_dbg[0], 0, kind) == 0) { st->res_dbg[1] = nx; st->res_dbg[2] = g; st->res_dbg[3] = first; }
-  int *d = dbg + (size_t)RES_DBG * g;
-  const long long now = wall_clock64();
-  d[3] = verdict == 1 ? kind : 3; d[4] = first; d[5] = (int)seen; d[6] = (int)(now - t0);
-  d[7] = (int)__builtin_amdgcn_s_getreg((3 << 11) | 20);        // HW_REG_XCC_ID, bits 3:0
-  d[8] = (int)(unsigned)now; d[9] = (int)rounds; d[10] = gidx;
-}
-__device__ __forceinline__ void res_slow_note(State *st, long long t0, int nx, int g, int missed, int kind) {
-  const long long el = wall_clock64() - t0;
-  if (el > RES_SLOW_TICKS && el < (1LL << 40)) {
-    atomicAdd(&st->res_slow, 1); atomicMax(&st->res_slow_max, (int)(el > 0x7fffffffLL ? 0x7fffffffLL : el));
-    atomicAdd(&st->res_slow_hist[el < 20000 ? 0 : (el < 50000 ? 1 : (el < 200000 ? 2 : 3))], 1);
-    atomicOr(&st->res_slow_xcc, 1u << (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15));
-    st->res_slow_last[0] = nx; st->res_slow_last[1] = g; st->res_slow_last[2] = missed; st->res_slow_last[3] = kind;
-  }
-}
-
-// K values in the resident layout.  K_ij = P_ij + sigma [i == j] + sum_k rho_k (A_ki A_kj): the sum runs over the rows k
-// of A that column i reaches, in ascending k -- the same order and the same products for (i,j) and (j,i), so K is
-// symmetric to the bit.  One wavefront per row i of K: each lane keeps up to four entries (i, j) of the row; the
-// wavefront walks the rows k of A that column i touches (the A' part of row i of M) and broadcasts their entries
-// (k, j') lane by lane; a lane whose j equals j' adds rho_k A_ki A_kj'.  All loads are wavefront-uniform or coalesced:
-// 25 us for the 2.09 M entries of config 2 (a two-list merge per entry took 390 us on dependent scattered loads).
-__device__ __forceinline__ int lane_int(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__global__ void __launch_bounds__(TB) k_form_K(Ctx c, ResCtx rc) {
-  const double sigma = c.prm->sigma;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {     // a new K: the pipelined recurrences and the predicted last trip get another chance
-    c.st->res_pipe_off = 0;
-    c.st->res_pred_off = 0; c.st->res_pred_win[0] = 0; c.st->res_pred_win[1] = 0; c.st->res_pred_win[2] = 0;
-  }
-  const int lane = threadIdx.x & 63, nwaves = gridDim.x * (TB / 64);
-  for (int i = blockIdx.x * (TB / 64) + (threadIdx.x >> 6); i < c.n; i += nwaves) {
-    const int e0 = rc.krp[i], e1 = rc.krp[i + 1];
-    const int ka = c.M.split[i], kb = c.M.rowptr[i + 1];
-    for (int eb = e0; eb < e1; eb += 256) {
-      int j[4]; double v[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int idx = eb + q * 64 + lane;
-        j[q] = -1; v[q] = 0.0;
-        if (idx < e1) {
-          j[q] = rc.kcj[idx];
-          const int ps = rc.kps[idx];
-          v[q] = (ps >= 0 ? c.M.val[ps] : 0.0) + (j[q] == i ? sigma : 0.0);
-        }
-      }
-      for (int kc = ka; kc < kb; kc += 64) {
-        const bool on = kc + lane < kb;
-        const int kk = on ? c.M.col[kc + lane] - c.n : 0;
-        const double ai = on ? c.M.val[kc + lane] : 0.0, rk = on ? c.rhoe[kk] : 0.0;     // (rhoe: the rows' effective weights when variables are eliminated, rho itself otherwise)
-        const int p0 = on ? c.A.rowptr[kk] : 0, p1 = on ? c.A.rowptr[kk + 1] : 0;
-        const int cnt = min(64, kb - kc);
-        for (int q = 0; q < cnt; ++q) {
-          const double a_i = lane_value(ai, q), r = lane_value(rk, q);
-          const int s0 = lane_int(p0, q), s1 = lane_int(p1, q);
-          for (int ec = s0; ec < s1; ec += 64) {
-            const bool eon = ec + lane < s1;
-            const int cj = eon ? c.A.col[ec + lane] : -1;
-            const double av = eon ? c.A.val[ec + lane] : 0.0;
-            const int len = min(64, s1 - ec);
-            for (int e = 0; e < len; ++e) {
-              const int cjb = lane_int(cj, e);
-              const double t = r * (a_i * lane_value(av, e));
-#pragma unroll
-              for (int q4 = 0; q4 < 4; ++q4) if (j[q4] == cjb) v[q4] += t;
-            }
-          }
-        }
-      }
-      // eliminated variables (k_elim_refresh) are not part of the system the launch solves: their rows and columns of K hold
-      // nothing but a diagonal entry (the PCG vectors are zero there, so its value never enters a product)
-      const bool igone = c.nelim && c.erow[i] >= 0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int idx = eb + q * 64 + lane;
-        if (idx < e1) {
-          const bool gone = c.nelim && (igone || c.erow[j[q]] >= 0);
-          rc.val[rc.kdst[idx]] = gone ? (j[q] == i ? 1.0 : 0.0) : v[q];
-        }
-      }
-    }
-  }
-}
-
-// The same values from contribution lists (build_resident): which rows k of A reach entry (i, j), and where a_ki and a_kj
-// sit, depends on the patterns alone, so the merge above is done once on the host and this kernel only streams its result:
-// every entry adds its terms in list order (ascending k: the order, the operands and the association of k_form_K, so the
-// bits are the same).  The kernel is a chain of dependent loads (offsets -> slots -> values -> weight), so it is laid out for
-// few links and many loads per link.  One wavefront per row i of K, four entries per lane.  Nearly every entry has one
-// term or none: the first FKL_T terms of all four entries are gathered in one flight per link and added by the lane itself
-// (a term the list does not have reads term 0 -- a real slot, one line for all such lanes -- and is not added).  An entry
-// with more (the diagonal: as many as column i of A has rows) is finished by the whole wavefront: lane t gathers term t,
-// then the products are added in order through readlane.
-#define FKL_T 2
-__global__ void __launch_bounds__(TB) k_form_K_lists(Ctx c, ResCtx rc) {
-  const double sigma = c.prm->sigma;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {     // a new K: the pipelined recurrences and the predicted last trip get another chance
-    c.st->res_pipe_off = 0;
-    c.st->res_pred_off = 0; c.st->res_pred_win[0] = 0; c.st->res_pred_win[1] = 0; c.st->res_pred_win[2] = 0;
-  }
-  const int lane = threadIdx.x & 63, nwaves = gridDim.x * (TB / 64);
-  for (int i = blockIdx.x * (TB / 64) + (threadIdx.x >> 6); i < c.n; i += nwaves) {
-    const int e0 = rc.krp[i], e1 = rc.krp[i + 1];
-    const bool igone = c.nelim && c.erow[i] >= 0;
-    for (int eb = e0; eb < e1; eb += 256) {
-      int j[4], ps[4], dst[4], q0[4], len[4]; double v[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int idx = min(eb + q * 64 + lane, e1 - 1);          // (lanes past the row read its last entry and store nothing)
-        j[q] = rc.kcj[idx]; ps[q] = rc.kps[idx]; dst[q] = rc.kdst[idx];
-        q0[q] = rc.kcp[idx]; len[q] = eb + q * 64 + lane < e1 ? rc.kcp[idx + 1] - q0[q] : 0;
-      }
-      bool any = false;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        v[q] = (ps[q] >= 0 ? c.M.val[ps[q]] : 0.0) + (j[q] == i ? sigma : 0.0);
-        any = any || len[q] > 0;
-      }
-      if (__ballot(any)) {                       // (some entry of this pass has a term: the lists are not empty, term 0 exists)
-        int pm[4][FKL_T], pa[4][FKL_T], kk[4][FKL_T];
-        double am[4][FKL_T], aa[4][FKL_T], rk[4][FKL_T];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int t = 0; t < FKL_T; ++t) { const int s = t < len[q] ? q0[q] + t : 0; pm[q][t] = rc.kcm[s]; pa[q][t] = rc.kca[s]; }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int t = 0; t < FKL_T; ++t) { kk[q][t] = c.M.col[pm[q][t]] - c.n; am[q][t] = c.M.val[pm[q][t]]; aa[q][t] = c.A.val[pa[q][t]]; }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int t = 0; t < FKL_T; ++t) rk[q][t] = c.rhoe[kk[q][t]];     // (rhoe: the rows' effective weights when variables are eliminated, rho itself otherwise)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int t = 0; t < FKL_T; ++t) if (t < len[q]) v[q] += rk[q][t] * (am[q][t] * aa[q][t]);
-        // the longer lists, one after the other
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          unsigned long long pend = __ballot(len[q] > FKL_T);
-          while (pend) {
-            const int l = __ffsll((long long)pend) - 1;
-            pend &= pend - 1;
-            const int s0 = lane_int(q0[q], l) + FKL_T, s1 = s0 - FKL_T + lane_int(len[q], l);
-            double acc = lane_value(v[q], l);
-            for (int sb = s0; sb < s1; sb += 64) {
-              const int s = sb + lane < s1 ? sb + lane : 0;
-              const int m_ = rc.kcm[s], a_ = rc.kca[s];
-              const int k_ = c.M.col[m_] - c.n;
-              const double prod = c.rhoe[k_] * (c.M.val[m_] * c.A.val[a_]);
-              const int cnt = min(64, s1 - sb);
-              for (int t = 0; t < cnt; ++t) acc += lane_value(prod, t);
-            }
-            if (lane == l) v[q] = acc;
-          }
-        }
-      }
-      // eliminated variables: see k_form_K
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (eb + q * 64 + lane < e1) {
-          const bool gone = c.nelim && (igone || c.erow[j[q]] >= 0);
-          rc.val[dst[q]] = gone ? (j[q] == i ? 1.0 : 0.0) : v[q];
-        }
-    }
-  }
-}
-
-template <int E>
-__global__ void __launch_bounds__(RES_TB) k_pcg_resident(Ctx c, ResCtx rc) {
-  extern __shared__ __attribute__((aligned(16))) double rlds[];
-  State *st = c.st;
-  TL_MARK(c, 5);
-  // ---- entry: every field of the state, the parameters and the own descriptor in one flight, the returns after one wait ----
-  // (none of these loads depends on another; `a || b || c` on three loads is three round trips)
-  const int s_stalled = st->stalled, s_run = st->run, s_fail = st->res_fail;
-  const unsigned ep0 = st->res_epoch;
-  const int s_pipe_off = st->res_pipe_off, s_pred_off = st->res_pred_off, s_admm_done = st->admm_done;
-  const Params prm = *c.prm;
-  const ResWG w = rc.wg[blockIdx.x];
-  if ((s_stalled != 0) | (s_run == 0) | (s_fail != 0)) return;
-  double *uv = rlds;                              // npad doubles: the exchanged vector (rows and riding partials of every workgroup)
-  double *seg = uv + rc.npad;                     // RES_TB + RES_MAXROWS row-segment sums
-  double *sc = seg + RES_TB + RES_MAXROWS;        // 8 doubles: gamma, delta, rr, fail word, verdict; [5] tol2, [6] "the start vector passes" (written once, before the loop)
-  double *sval = sc + 8;                          // 3 x 256: the workgroups' dot partials during exchange (2)
-#ifdef OSQP_AMD_TIMELINE
-  long long *tls = reinterpret_cast<long long *>(sval + 768);   // phase stamps of the first 64 exchanges (workgroup 0)
-#define RTL(k) do { if (blockIdx.x == 0 && threadIdx.x == 0 && nx >= 1 && nx <= 64) tls[(nx - 1) * 5 + (k)] = wall_clock64(); } while (0)
-  long long *wtl = tls + 5 * 64;                             // [phase][wavefront] stamps of exchange 8 (workgroup 0), then the same of exchange 1
-#define WTL(k) do { if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && (nx == 8 || nx == 1)) wtl[(nx == 1 ? 40 : 0) + (k) * 8 + (threadIdx.x >> 6)] = wall_clock64(); } while (0)
-  if (blockIdx.x == 0 && threadIdx.x == 0) wtl[80] = wall_clock64();       // kernel entry
-#else
-#define RTL(k) do { } while (0)
-#define WTL(k) do { } while (0)
-#endif
-  const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int nwg = rc.nwg, npad = rc.npad;
-  const bool sabotage = rc.inject > 0 && g == rc.nwg - 1 && s_admm_done + 1 == rc.inject;
-  // pipelined recurrences only where a drift would be caught: not in the convexity probe, not after a failed check
-  bool pipe = rc.pipe && !s_pipe_off && !prm.no_restart;
-  // the predicted last trip (see the loop): wavefront 0 decides, from sums that are the same in every workgroup
-  bool predict = pipe && rc.predict && !s_pred_off;
-  // ---- own slice of K into registers (issued first: in flight under everything below) ----
-  // (wavefronts 1..7; wavefront 0 holds no entries: its loads are the small ones the start-up and the exchanges wait for)
-  const bool prod = wv != 0;
-  const int tt = t - 64;
-  double kv[E]; unsigned short kc[E];
-#pragma unroll
-  for (int k = 0; k < E; ++k) { kv[k] = 0.0; kc[k] = 0; }
-  unsigned long long brk = 0ull;
-  int slot0 = 0;
-  // u0 = Minv r0 was left in global memory by k_pcg_init (an earlier launch: plain loads see it), in the layout of the exchanged
-  // vector: no exchange needed, one coalesced sweep in the form of the exchange's own (every 16-byte load of a thread in flight at
-  // once: the register peak the kernel pays there anyway).  It needs nothing but kernel arguments, so wavefronts 1..7 issue it
-  // ahead of their entries of K and wavefront 0 behind its start-up sums; a load past the vector's end is dropped by the
-  // descriptor's range check.  It lands in LDS before the barrier in front of the loop (uv has no earlier reader).
-  const bool u0_direct = rc.u0_direct != 0;
-  u32x4 u0v[RES_MAXLD];
-  auto u0_issue = [&]() __attribute__((always_inline)) {
-    const __amdgpu_buffer_rsrc_t ru = res_rsrc(c.u0pos, (size_t)npad * 8);
-#pragma unroll
-    for (int q = 0; q < RES_MAXLD; ++q) u0v[q] = __builtin_amdgcn_raw_buffer_load_b128(ru, (q * RES_TB + t) * 16, 0, 0);
-  };
-  if (prod) {
-    if (u0_direct) u0_issue();
-#pragma unroll
-    for (int k = 0; k < E; ++k) {
-      const size_t idx = ((size_t)g * E + k) * RES_PT + tt;
-      kv[k] = rc.val[idx]; kc[k] = rc.col[idx];
-    }
-    brk = rc.brk[(size_t)g * RES_PT + tt];
-    slot0 = rc.slot0[(size_t)g * RES_PT + tt];
-  }
-  int sr0 = 0, sr1 = 0;
-  // where the partials of workgroups lane, lane + 64, ... sit in the exchanged vector: wavefront 0 alone reads them (mode 1), so
-  // it alone loads them, four loads in one flight at clamped indices (an entry past nwg is never used)
-  int ppos[4] = {0, 0, 0, 0};
-  // ---- start-up scalars: ||r0||^2, ||b||^2 from k_pcg_init's partials, by wavefront 0 alone ----
-  // Wavefront 0 holds no entries of K, so none of these loads queues behind K's.  A lane's partials (lane, lane + 64, ...: at most
-  // MAX_PARTS / 64 of each sum) are all in flight at once, at clamped indices, and are added in ascending order from 0.0 (a slot
-  // past gridM adds +0.0, which changes no bit of a sum that started at +0.0), then wave_sum: the order the sum has always had.
-  // tol2 and the verdict "the start vector already passes" reach the other wavefronts through sc[5], sc[6] at the barrier below.
-  constexpr int NPL = MAX_PARTS / 64;
-  static_assert(NPL == 16 && NPL * 64 == MAX_PARTS, "k_pcg_resident: a lane of wavefront 0 holds MAX_PARTS / 64 partials of each start-up sum");
-  double own_r = 0.0, own_u = 0.0, own_x = 0.0, own_mi = 0.0;
-  if (!prod) {
-    const int gm = c.gridM;
-    double pr[NPL], pb[NPL];
-#pragma unroll
-    for (int q = 0; q < NPL; ++q) { const int i = min(lane + 64 * q, gm - 1); pr[q] = c.part_rr[i]; pb[q] = c.part_bb[i]; }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ppos[q] = rc.ppos[min(lane + 64 * q, nwg - 1)];
-    // the own rows in the same flight (clamped: a lane past the workgroup's rows loads a valid element and drops it below)
-    // (r0 and u0: from the exchanged vector's layout, where the own rows are w.pos .. w.pos + nr - 1, when k_pcg_init left them there;
-    // pointer and index are chosen from kernel arguments alone, so the loads stay in this flight either way)
-    const int jc = min(w.r0 + lane, c.n - 1), pc = min(w.pos + lane, npad - 1);
-    const bool rpos = rc.r0pos != nullptr;
-    const double *rsrc = rpos ? rc.r0pos : c.init_r, *usrc = rpos ? c.u0pos : c.init_z;
-    own_r = rsrc[rpos ? (size_t)pc : (size_t)jc * c.init_stride]; own_u = usrc[rpos ? pc : jc]; own_x = c.vx[jc]; own_mi = c.minv[jc];
-    sr0 = rc.segrow[(size_t)g * (RES_MAXROWS + 1) + min(lane, RES_MAXROWS)]; sr1 = rc.segrow[(size_t)g * (RES_MAXROWS + 1) + min(lane + 1, RES_MAXROWS)];
-    double rr0 = 0.0, bb = 0.0;
-#pragma unroll
-    for (int q = 0; q < NPL; ++q) { const bool in = lane + 64 * q < gm; rr0 += in ? pr[q] : 0.0; bb += in ? pb[q] : 0.0; }
-    rr0 = wave_sum(rr0); bb = wave_sum(bb);
-    const double tl2 = fmax(prm.eps_rel * prm.eps_rel * bb, prm.eps_abs * prm.eps_abs);
-    if (lane == 0) { sc[3] = 0.0; sc[5] = tl2; sc[6] = rr0 <= tl2 ? 1.0 : 0.0; }
-    if (u0_direct) u0_issue();
-  }
-  // rows of this workgroup live in the lanes of wavefront 0
-  const bool own = wv == 0 && lane < w.nr;
-  const int j = w.r0 + lane;
-  // The eleven doubles of the row state are wavefront 0's alone, and wavefront 0 holds no entries of K: they live in the
-  // registers of kv[0..10] (zero in wavefront 0), so that they cost wavefronts 1..7 nothing beside kv[E].  For E < 11 as
-  // many as fit, the rest in registers of their own.  EVERY write to one of these names is wavefront 0's (`own`, or
-  // `!prod`): in wavefronts 1..7 the same registers are entries of K.
-  double rs_rest[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define RES_ROWSTATE(i) (*((i) < E ? &kv[(i) < E ? (i) : 0] : &rs_rest[i]))
-  double &r_ = RES_ROWSTATE(0), &u_ = RES_ROWSTATE(1), &w_ = RES_ROWSTATE(2), &p_ = RES_ROWSTATE(3), &s_ = RES_ROWSTATE(4), &x_ = RES_ROWSTATE(5);
-  double &mi = RES_ROWSTATE(6), &x0_ = RES_ROWSTATE(7), &r0_ = RES_ROWSTATE(8);
-  double &z_ = RES_ROWSTATE(9), &q_ = RES_ROWSTATE(10);     // pipelined recurrences: z = K q, q = Minv s
-#undef RES_ROWSTATE
-  if (own) { r_ = own_r; u_ = own_u; x_ = own_x; mi = own_mi; x0_ = own_x; r0_ = own_r; }
-  else { sr0 = 0; sr1 = 0; }
-  if (u0_direct) {
-    const int half = npad >> 1;
-#pragma unroll
-    for (int q = 0; q < RES_MAXLD; ++q) {
-      const int i2 = q * RES_TB + t;
-      if (i2 < half) { uv[2 * i2] = __hiloint2double((int)u0v[q].y, (int)u0v[q].x); uv[2 * i2 + 1] = __hiloint2double((int)u0v[q].w, (int)u0v[q].z); }
-    }
-  }
-  __syncthreads();
-  const double tol2 = sc[5];
-  if (sc[6] != 0.0) {                  // the start vector already passes the stop test: all eight wavefronts leave together
-    if (g == 0 && t == 0) { st->done = 1; st->tol2 = tol2; }
-    return;
-  }
-  int nx = 0;                          // vector exchanges so far; exchange k carries the tag ep0 + k
-  unsigned tag = ep0;
-  int par = 0;
-
-  // Exchange (1): every workgroup's rows of one vector (+ 3 doubles riding along) to every workgroup's LDS.
-  // Write-through stores, drain, flag; wavefront 0 polls the flags; sc1 sweep.  False when a wait timed out.
-  auto vec_exchange = [&](double val, bool ride) __attribute__((always_inline)) -> bool {
-    double e0 = 0.0, e1 = 0.0, e2 = 0.0;     // riding partials of (r,u), (w,u), (r,r) when `ride`
-    ++nx; tag = ep0 + (unsigned)nx; par = (int)(tag & 1u);
-    if (sabotage && nx == 3) return false;     // (test hook: this workgroup walks away without a word)
-    RTL(0);
-    const __amdgpu_buffer_rsrc_t rs = res_rsrc(rc.ubuf + (size_t)par * npad, (size_t)npad * 8);
-    if (wv == 0) {
-      // rows at pos .. pos + nr - 1, the three riding partials right behind them: all inside this workgroup's own lines
-      if (lane < w.nr) {
-        u32x2 d; d.x = (unsigned)__double2loint(val); d.y = (unsigned)__double2hiint(val);
-        __builtin_amdgcn_raw_buffer_store_b64(d, rs, (w.pos + lane) * 8, 0, AUX_SC1);
-      }
-      // (the partials are reduced while the rows are on their way)
-      if (ride) { e0 = wave_sum(own ? r_ * u_ : 0.0); e1 = wave_sum(own ? w_ * u_ : 0.0); e2 = wave_sum(own ? r_ * r_ : 0.0); }
-      if (lane < 3) {
-        const double v = lane == 0 ? e0 : (lane == 1 ? e1 : e2);
-        u32x2 d; d.x = (unsigned)__double2loint(v); d.y = (unsigned)__double2hiint(v);
-        __builtin_amdgcn_raw_buffer_store_b64(d, rs, (w.pos + w.nr + lane) * 8, 0, AUX_SC1);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0) __hip_atomic_store(rc.flags + (size_t)g * RES_FSTRIDE, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (wv < rc.npw) {
-      // ceil(nwg / 64) wavefronts poll, ONE flag per lane (a lane that polled four flags with atomic loads waited for each
-      // before it issued the next), and only until that flag has been seen; the own flag is not polled
-      const int o = t;                         // flag of workgroup t
-      bool pend = o < nwg && o != g;
-      int miss16 = -1;
-      unsigned seen = 0, rounds = 0;
-      long long t0 = wall_clock64();
-      int late = 0;
-      bool gave = false;
-      while (true) {
-        if (pend) {
-          seen = __hip_atomic_load(rc.flags + (size_t)o * RES_FSTRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          pend = (int)(seen - tag) < 0;
-        }
-        if (!__any(pend)) break;
-        if (++rounds & 15u) { __builtin_amdgcn_s_sleep(1); continue; }     // clock and give-up word only every 16th round
-        const int verdict = res_spin_check(st, t0, late);
-        if (verdict) {
-          const unsigned long long miss = __ballot(pend);
-          const int fl = miss ? (int)__ffsll((long long)miss) - 1 : 0;
-          const unsigned sv = (unsigned)__builtin_amdgcn_readlane((int)seen, fl);
-          if (lane == 0) { res_note(st, rc.dbg, g, verdict, 1, nx, miss ? 64 * wv + fl : -1, sv, t0, rounds, 0); sc[3] = 1.0; }
-          gave = true;
-          break;
-        }
-        if (rounds == 16u) { const unsigned long long ms = __ballot(pend); miss16 = ms ? 64 * wv + (int)__ffsll((long long)ms) - 1 : -1; }
-        if ((rounds & 63u) == 0 && wv == 0 && lane == 0) {       // a long wait: say it again
-          __hip_atomic_store(rc.flags + (size_t)g * RES_FSTRIDE, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          atomicAdd(&st->res_repub, 1);
-        }
-        if ((rounds & 255u) == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        __builtin_amdgcn_s_sleep(1);
-      }
-      if (rounds >= 16u && lane == 0 && !gave) res_slow_note(st, t0, nx, g, miss16, 1);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    __syncthreads();
-    RTL(1);
-    if (sc[3] != 0.0) return false;
-    {
-      const int half = npad >> 1;
-      u32x4 v[RES_MAXLD];              // every load of the sweep in flight at once
-#pragma unroll
-      for (int q = 0; q < RES_MAXLD; ++q) { const int i2 = q * RES_TB + t; if (i2 < half) v[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, i2 * 16, 0, AUX_SC1); }
-#pragma unroll
-      for (int q = 0; q < RES_MAXLD; ++q) {
-        const int i2 = q * RES_TB + t;
-        if (i2 < half) { uv[2 * i2] = __hiloint2double((int)v[q].y, (int)v[q].x); uv[2 * i2 + 1] = __hiloint2double((int)v[q].w, (int)v[q].z); }
-      }
-    }
-    __syncthreads();
-    RTL(2);
-    return true;
-  };
-  // rows of K times the vector in LDS: E products per thread, row segments through LDS; the own-row value
-  // in the lanes of wavefront 0 (ends with the barrier that makes the segments visible)
-  auto products_issue = [&]() __attribute__((always_inline)) {
-    if (prod) {
-      // gathers first (all in flight together; the segment writes below could alias them as far as the compiler knows),
-      // half of the entries at a time to stay inside the register budget
-      double s = 0.0; int slot = slot0;
-      constexpr int H = (E + 1) / 2;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        double xv[H];
-#pragma unroll
-        for (int k = 0; k < H; ++k) if (h * H + k < E) xv[k] = uv[kc[h * H + k]];
-#pragma unroll
-        for (int k = 0; k < H; ++k)
-          if (h * H + k < E) {
-            s += kv[h * H + k] * xv[k];
-            if ((brk >> (h * H + k)) & 1ull) { seg[slot++] = s; s = 0.0; }
-          }
-      }
-    }
-  };
-  auto products_finish = [&]() __attribute__((always_inline)) -> double {
-    __syncthreads();
-    RTL(3);
-    double a = 0.0;
-    if (own)
-      for (int q0 = sr0; q0 < sr1; q0 += 16) {       // 16 independent LDS reads in flight, summed in slot order
-        double sv[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) sv[q] = seg[min(q0 + q, sr1 - 1)];     // unconditional: no branch per read
-#pragma unroll
-        for (int q = 0; q < 16; ++q) a += q0 + q < sr1 ? sv[q] : 0.0;
-      }
-    return a;
-  };
-  // Exchange (2): three dot partials per workgroup as tagged granules (the data is the flag); totals in sc[0..2].
-  auto scal_exchange = [&](double pg, double pd, double prr) __attribute__((always_inline)) -> bool {
-    // granules of 8 bytes {32 bits of data, tag}: six per workgroup, in a line of the workgroup's own, stored with
-    // agent-scope atomic stores
-    unsigned long long *gb = reinterpret_cast<unsigned long long *>(rc.sbuf) + (size_t)par * nwg * RES_GSTRIDE;
-    if (wv == 0) {
-      pg = wave_sum(pg); pd = wave_sum(pd); prr = wave_sum(prr);
-      if (lane < 6) {
-        const double v = lane < 2 ? pg : (lane < 4 ? pd : prr);
-        const unsigned half = (lane & 1) ? (unsigned)__double2hiint(v) : (unsigned)__double2loint(v);
-        __hip_atomic_store(gb + (size_t)g * RES_GSTRIDE + lane, ((unsigned long long)tag << 32) | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    if (wv < rc.npw) {
-      // ceil(nwg / 64) wavefronts poll, ONE workgroup's six granules per lane, all six loads in flight together
-      // (buffer_load_dwordx2 sc1, volatile; six atomic loads went one after the other: 1.9-2.2 us per exchange against
-      // 1.5-1.75 at up to 64 workgroups, tools/exchange_probe2.hip), and only the granules still missing.  Each granule vouches
-      // for itself; a half arrives in LDS as soon as its tag matches.
-      const int o = t;                         // the workgroup whose granules this thread fetches
-      const __amdgpu_buffer_rsrc_t rg = res_rsrc(gb, (size_t)nwg * RES_GSTRIDE * 8);
-      unsigned pend = o < nwg ? 63u : 0u;
-      int miss16 = -1;
-      unsigned *svw = reinterpret_cast<unsigned *>(sval) + 6 * o;
-      unsigned seen = 0, rounds = 0;
-      long long t0 = wall_clock64();
-      int late = 0;
-      bool gave = false;
-      while (true) {
-        u32x2 gv[6];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) if (pend & (1u << q)) gv[q] = __builtin_amdgcn_raw_buffer_load_b64(rg, (o * RES_GSTRIDE + q) * 8, 0, AUX_SC1 | AUX_VOL);
-#pragma unroll
-        for (int q = 0; q < 6; ++q)
-          if (pend & (1u << q)) { if (gv[q].y == tag) { svw[q] = gv[q].x; pend &= ~(1u << q); } else seen = gv[q].y; }
-        if (!__any(pend != 0)) break;
-        asm volatile("" ::: "memory");
-        if (++rounds & 15u) { __builtin_amdgcn_s_sleep(1); continue; }
-        const int verdict = res_spin_check(st, t0, late);
-        if (verdict) {
-          const unsigned long long miss = __ballot(pend != 0);
-          const int fl = miss ? (int)__ffsll((long long)miss) - 1 : 0;
-          const unsigned sv = (unsigned)__builtin_amdgcn_readlane((int)seen, fl);
-          const int gi = __builtin_amdgcn_readlane((int)pend, fl);
-          if (lane == 0) { res_note(st, rc.dbg, g, verdict, 2, nx, miss ? 64 * wv + fl : -1, sv, t0, rounds, gi); sc[3] = 1.0; }
-          gave = true;
-          break;
-        }
-        if (rounds == 16u) { const unsigned long long ms = __ballot(pend != 0); miss16 = ms ? 64 * wv + (int)__ffsll((long long)ms) - 1 : -1; }
-        if ((rounds & 63u) == 0 && wv == 0) {          // a long wait: say it again
-          if (lane < 6) {
-            const double v = lane < 2 ? pg : (lane < 4 ? pd : prr);
-            const unsigned half = (lane & 1) ? (unsigned)__double2hiint(v) : (unsigned)__double2loint(v);
-            __hip_atomic_store(gb + (size_t)g * RES_GSTRIDE + lane, ((unsigned long long)tag << 32) | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          if (lane == 0) atomicAdd(&st->res_repub, 1);
-        }
-        if ((rounds & 255u) == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // a poll that stays unanswered this long: drop whatever this CU still caches
-        __builtin_amdgcn_s_sleep(1);
-      }
-      if (rounds >= 16u && lane == 0 && !gave) res_slow_note(st, t0, nx, g, miss16, 2);
-    }
-    __syncthreads();
-    if (wv == 0) {
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (lane + 64 * q < nwg) { a0 += sval[3 * (lane + 64 * q)]; a1 += sval[3 * (lane + 64 * q) + 1]; a2 += sval[3 * (lane + 64 * q) + 2]; }
-      a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
-      if (lane == 0) { sc[0] = a0; sc[1] = a1; sc[2] = a2; }
-    }
-    __syncthreads();
-    RTL(4);
-    return sc[3] == 0.0;
-  };
-
-  double gam_old = 0.0, alp_old = 0.0;
-  int iters = 0;
-  bool conv = false, bad = false, failed = false;
-  // One loop, one copy of each exchange (four inlined copies cost 88 spilled registers).  Modes:
-  //   0  w = K u0 for the pipelined phase           1  pipelined iteration (Ghysels-Vanroose): ONE exchange -- m = Minv w
-  //   2  true-residual check r0 - K (x - x0) of        travels with the partials of (r,u), (w,u), (r,r); wavefront 0 forms
-  //      EVERY solve that claims convergence           the scalars while the others multiply; w and u follow recurrences
-  //   3  Chronopoulos-Gear iteration with a fresh
-  //      product (the recurrences of k_cg_A/k_cg_B)
-  // The pipelined recurrences drift on ill-conditioned systems, so: out after 64 iterations, out on any breakdown, and
-  // every solve that claims convergence is checked against the true residual.  A failed check hands the solve to
-  // mode 3 and switches the pipelined phase off until K changes.
-  // The predicted last trip.  A pipelined solve of N iterations makes a trip N + 1 whose exchange only delivers the
-  // ||r||^2 that says "converged" and whose products nobody uses, and then the check's trip.  When the two latest ||r||^2
-  // extrapolate (rr^2 / rr_prev: linear convergence; CG does a little better here, so this errs on the late side) to
-  // <= pred_margin * tol2, trip N + 1 sends x - x0 instead of m, with the same three partials riding along:
-  //   converged      the products are K (x - x0): straight on to the check's tail -- one trip saved (a hit)
-  //   some other stop (breakdown, cap): the check that mode 2 would now run has its product too
-  //   goes on        the products are thrown away and NOTHING is touched, neither the row state nor gam_old / alp_old;
-  //                  the next trip is an ordinary one with the same partials (a miss: one trip more), and the solve
-  //                  predicts no more
-  // The iterates are the same bit for bit with or without, hit or miss.  When misses outnumber hits over
-  // RES_PRED_WINDOW solves, State::res_pred_off ends it until K changes.
-  double rr_prev = 0.0;                // wavefront 0: ||r||^2 of the trip before
-  bool pred = false;                   // wavefront 0: the coming trip carries x - x0
-  int pred_hit = 0, pred_miss = 0;
-  int mode = pipe ? 0 : 3;
-  int check_why = 0;                   // 0: the pipelined recurrence says converged, 1: its breakdown / iteration cap, 2: long solve, 3: mode 3 says converged
-  int checks3 = 0;                     // failed checks of mode-3 verdicts in this solve
-  bool have_u0 = u0_direct;            // the vector k_pcg_init left in global memory, in LDS since the barrier above, is still the u of the recurrences
-  while (true) {
-    double val = u_, m_ = 0.0;
-    if (mode == 1) { m_ = mi * w_; val = pred ? x_ - x0_ : m_; }
-    else if (mode == 2) val = x_ - x0_;
-    if (have_u0) { ++nx; tag = ep0 + (unsigned)nx; par = (int)(tag & 1u); have_u0 = false; }   // (a fresh tag for the granules of exchange (2))
-    else if (!vec_exchange(val, mode == 1)) { failed = true; break; }
-    WTL(0);
-    products_issue();
-    WTL(1);
-    CgStep cs{};
-    if (mode == 1 && wv == 0) {
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) if (lane + 64 * q < nwg) { a0 += uv[ppos[q]]; a1 += uv[ppos[q] + 1]; a2 += uv[ppos[q] + 2]; }
-      const double gam = wave_sum(a0), del = wave_sum(a1), rr = wave_sum(a2);
-      cs = cg_step(rr, gam, del, gam_old, alp_old, tol2, iters, 0, prm, false);
-      // (+ 4: this was the predicted trip)
-      if (lane == 0) sc[4] = (cs.stop ? (cs.conv ? 1.0 : 2.0) : 0.0) + (pred ? 4.0 : 0.0);
-      if (pred) { pred = false; predict = false; }        // one prediction per solve; the scalars stay as they are
-      else {
-        gam_old = gam; alp_old = cs.alpha;
-        // i >= 2: two ||r||^2 on record
-        pred = predict && !cs.stop && iters >= 1 && rr * rr <= rc.pred_margin * tol2 * rr_prev;
-        rr_prev = rr;
-      }
-    }
-    WTL(2);
-    const double kx = products_finish();       // own row of K times the exchanged vector
-    WTL(3);
-    if (mode == 0) { if (!prod) w_ = kx; mode = 1; continue; }
-    if (mode == 1) {
-      const int verdict = (int)sc[4];
-      if (verdict == 4) { ++pred_miss; continue; }             // predicted, and the solve goes on: this trip did not happen
-      if (verdict != 0) {
-        check_why = (verdict & 3) == 1 ? 0 : 1; mode = 2;
-        if (verdict < 4) continue;                             // (the products of this trip are wasted)
-        ++pred_hit;                                            // kx is a row of K (x - x0): on to the tail of mode 2
-      }
-    }
-    if (mode == 1) {
-      ++iters;
-      if (own) {
-        z_ = cs.first ? kx : (kx + cs.beta * z_);
-        q_ = cs.first ? m_ : (m_ + cs.beta * q_);
-        s_ = cs.first ? w_ : (w_ + cs.beta * s_);
-        p_ = cs.first ? u_ : (u_ + cs.beta * p_);
-        x_ += cs.alpha * p_;
-        r_ -= cs.alpha * s_;
-        u_ -= cs.alpha * q_;
-        w_ -= cs.alpha * z_;
-      }
-      WTL(4);
-      if (iters >= 64) { check_why = 2; mode = 2; pred = false; }
-      continue;
-    }
-    if (mode == 2) {
-      const double rt = r0_ - kx;
-      if (!scal_exchange(0.0, 0.0, own ? rt * rt : 0.0)) { failed = true; break; }
-      if (sc[2] <= 2.0 * tol2) { conv = true; break; }
-      // continue from the true residual with fresh directions; the recurrences are switched off for this K when they
-      // had claimed convergence or broken down (not when the solve was merely long)
-      if (own) { r_ = rt; u_ = mi * rt; }
-      gam_old = 0.0; alp_old = 0.0;
-      if (check_why == 3) ++checks3;
-      if (g == 0 && t == 0) { if (check_why != 2) st->res_chk_fail += 1; if (check_why < 2) st->res_pipe_off = 1; }   // (a long solve cut at 64 iterations has not failed anything)
-      __syncthreads();          // sc[] is rewritten by the next exchange
-      mode = 3;
-      continue;
-    }
-    if (!prod) w_ = kx;
-    if (!scal_exchange(own ? r_ * u_ : 0.0, own ? w_ * u_ : 0.0, own ? r_ * r_ : 0.0)) { failed = true; break; }
-    const double gam = sc[0], del = sc[1], rr = sc[2];
-    cs = cg_step(rr, gam, del, gam_old, alp_old, tol2, iters, 0, prm, false);
-    if (cs.stop) {
-      // a converged solve is checked against the true residual here too (twice at most: on a system whose attainable
-      // accuracy sits above the stop the recursive residual's verdict stands, as on the launch-per-step path)
-      if (cs.conv && checks3 < 2) { check_why = 3; mode = 2; continue; }
-      conv = cs.conv; bad = cs.bad && !cs.conv; break;
-    }
-    ++iters; gam_old = gam; alp_old = cs.alpha;
-    if (own) {
-      p_ = cs.first ? u_ : (u_ + cs.beta * p_);
-      s_ = cs.first ? w_ : (w_ + cs.beta * s_);
-      x_ += cs.alpha * p_;
-      r_ -= cs.alpha * s_;
-      u_ = mi * r_;
-    }
-  }
-  if (failed) {
-    if (t == 0) {
-      __hip_atomic_store(&st->res_fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      int *d = rc.dbg + (size_t)RES_DBG * g;
-      d[0] = nx; d[1] = mode; d[2] = iters;
-      if (sabotage) { d[3] = 4; d[7] = (int)__builtin_amdgcn_s_getreg((3 << 11) | 20); d[8] = (int)(unsigned)wall_clock64(); }
-    }
-    return;
-  }
-  if (own && iters > 0) c.va[j] = x_;
-#ifdef OSQP_AMD_TIMELINE
-  if (g == 0 && t == 0) {
-    const int cnt = (nx < 64 ? nx : 64) * 5;
-    const unsigned long long k0 = atomicAdd(c.tl, (unsigned long long)cnt + 1);
-    if (k0 + cnt + 1 < TL_CAP - 2) {
-      for (int q = 0; q < cnt; ++q) c.tl[1 + k0 + q] = ((unsigned long long)(10 + q % 5) << 56) | ((unsigned long long)tls[q] & 0x00FFFFFFFFFFFFFFull);
-      c.tl[1 + k0 + cnt] = (15ull << 56) | (wall_clock64() & 0x00FFFFFFFFFFFFFFull);
-    }
-    if (nx >= 8) {
-      const unsigned long long k1 = atomicAdd(c.tl, 80ull);
-      if (k1 + 80 < TL_CAP - 2) {
-        for (int q = 0; q < 40; ++q) c.tl[1 + k1 + q] = ((unsigned long long)(20 + q) << 56) | ((unsigned long long)(wtl[q] - wtl[0]) & 0x00FFFFFFFFFFFFFFull);
-        for (int q = 0; q < 40; ++q) c.tl[1 + k1 + 40 + q] = ((unsigned long long)(60 + q) << 56) | ((unsigned long long)(wtl[40 + q] - wtl[80]) & 0x00FFFFFFFFFFFFFFull);   // first trip, since kernel entry
-      }
-    }
-  }
-#endif
-  if (g == 0 && t == 0) {
-    st->iters[0] = iters; st->iters[1] = 0;
-    st->done = conv ? 1 : 2;
-    if (bad) st->neg_curv = 1;
-    st->tol2 = tol2;
-    st->res_epoch = ep0 + (unsigned)nx;
-    st->res_trips += nx; st->res_solves += 1; st->res_pred_hit += pred_hit; st->res_pred_miss += pred_miss;
-    if (rc.predict && !st->res_pred_off) {
-      const int ws = st->res_pred_win[0] + 1, wh = st->res_pred_win[1] + pred_hit, wm = st->res_pred_win[2] + pred_miss;
-      const bool full = ws >= RES_PRED_WINDOW;
-      if (full && wm > wh) st->res_pred_off = 1;
-      st->res_pred_win[0] = full ? 0 : ws; st->res_pred_win[1] = full ? 0 : wh; st->res_pred_win[2] = full ? 0 : wm;
-    }
-  }
-}
-
-
-// ---------------------------------------------------------------------------
-// Block-resident PCG: the resident idea for the portfolio family (BASELINE config 5), whose n = 50 000 is far beyond
-// the vector exchange of k_pcg_resident -- and which needs none.  If P consists of dense diagonal blocks only and every
-// row of A either has a single entry (bounds) or is one of at most four huge rows (a budget constraint), then
-//     K = blockdiag(P_b + sigma I + diag(sum_i rho_i a_ij^2))  +  sum_h rho_h a_h a_h'
-// and a workgroup that owns whole blocks needs nobody else's vector elements: K_b u_b is a dense product from registers
-// (each row of a block split over two threads, 64 entries each), the low-rank part needs the scalars s_h = a_h'u, and
-// delta = (Ku, u) = sum_g (K_b u_b, u_b) + sum_h rho_h s_h^2.  So ONE exchange of 3 + nh scalars per workgroup and
-// iteration (tagged 8-byte granules, the exchange (2) of k_pcg_resident) carries gamma, delta', ||r||^2 and the s_h;
-// everything else is local.  Chronopoulos-Gear recurrences with a fresh product (cg_step), 3 barriers per iteration.
-// The 50 MB of blocks are read once per launch instead of once per PCG iteration.
-// ---------------------------------------------------------------------------
-struct BrCtx { int nwg; const int *blk0; double *sbuf; int *dbg; };
-
-template <int NH>
-__global__ void __launch_bounds__(RES_TB) k_pcg_blockres(Ctx c, BrCtx bc) {
-  constexpr int NV = 3 + NH;                 // scalars per workgroup and iteration
-  __shared__ double ul[256];                 // u of the own rows
-  __shared__ double red[8 * 8];              // per-wavefront partials
-  __shared__ double tot[8];                  // totals; [7]: a wait timed out
-  __shared__ double sval[256 * NV];          // every workgroup's scalars during the exchange
-  State *st = c.st;
-  TL_MARK(c, 6);
-  if (st->stalled || !st->run || st->res_fail) return;
-  const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6, nwg = bc.nwg;
-#ifdef OSQP_AMD_TIMELINE
-  __shared__ long long btl[6 * 64];          // phase stamps of the first 64 iterations (workgroup 0)
-#define BTL(k) do { if (blockIdx.x == 0 && threadIdx.x == 0 && nx >= 1 && nx <= 64) btl[(nx - 1) * 6 + (k)] = wall_clock64(); } while (0)
-#else
-#define BTL(k) do { } while (0)
-#endif
-  const Params prm = *c.prm;
-  const unsigned ep0 = st->res_epoch;
-  // the row of this thread pair: row rl of the workgroup's (at most two) blocks, columns [64 h, 64 h + 64) of its block
-  const int rl = t >> 1, h = t & 1;
-  int j = -1, cb = 0, bw = 0, c0 = 0, pitch = 0; size_t off = 0;
-  {
-    int base = 0;
-    for (int q = bc.blk0[g]; q < bc.blk0[g + 1]; ++q) {
-      const DenseBlk d = c.dP.blk[q];
-      if (rl >= base && rl < base + d.b) { j = d.c0 + (rl - base); cb = base; bw = d.b; c0 = d.c0; off = (size_t)d.off; pitch = d.pitch; }
-      base += d.b;
-    }
-  }
-  const bool row = j >= 0, own = row && h == 0;
-  double dadd = 0.0, hc[NH > 0 ? NH : 1], hrho[NH > 0 ? NH : 1];
-#pragma unroll
-  for (int q = 0; q < NH; ++q) { hc[q] = 0.0; hrho[q] = c.rho[c.hrow[q]]; }
-  if (row) {
-    dadd = prm.sigma;
-    for (int k = c.M.split[j]; k < c.M.rowptr[j + 1]; ++k) {          // single-entry rows of A at this column
-      const int i = c.M.col[k] - c.n;
-      bool huge = false;
-#pragma unroll
-      for (int q = 0; q < NH; ++q) huge |= i == c.hrow[q];
-      if (!huge) { const double a = c.M.val[k]; dadd += c.rho[i] * a * a; }
-    }
-#pragma unroll
-    for (int q = 0; q < NH; ++q) hc[q] = c.hcol[(size_t)q * c.n + j];
-  }
-  double kv[64];
-#pragma unroll
-  for (int k = 0; k < 64; ++k) {
-    const int cc = h * 64 + k;
-    // K_b is symmetric: entry (row, cc) is read as (cc, row), so that the lanes of a wave instruction -- consecutive rows --
-    // read consecutive addresses (row-wise it was one 64-byte segment per lane: 100 us per launch)
-    kv[k] = (row && cc < bw) ? c.dP.val[off + (size_t)cc * pitch + (j - c0)] + (cc == j - c0 ? dadd : 0.0) : 0.0;
-  }
-  double rr0 = 0.0, bb = 0.0;
-  for (int i = lane; i < c.gridM; i += 64) { rr0 += c.part_rr[i]; bb += c.part_bb[i]; }
-  rr0 = wave_sum(rr0); bb = wave_sum(bb);
-  const double tol2 = fmax(prm.eps_rel * prm.eps_rel * bb, prm.eps_abs * prm.eps_abs);
-  if (rr0 <= tol2) {
-    if (g == 0 && t == 0) { st->done = 1; st->tol2 = tol2; }
-    return;
-  }
-  double r_ = 0, u_ = 0, p_ = 0, s_ = 0, x_ = 0, mi = 0;
-  if (own) { r_ = c.init_r[(size_t)j * c.init_stride]; u_ = c.init_z[j]; x_ = c.vx[j]; mi = c.minv[j]; }
-  if (t < 256) ul[t] = 0.0;
-  if (t == 0) tot[7] = 0.0;
-  __syncthreads();
-  double gam_old = 0.0, alp_old = 0.0;
-  int iters = 0, nx = 0;
-  bool conv = false, bad = false, failed = false;
-  while (true) {
-    ++nx;
-    const unsigned tag = ep0 + (unsigned)nx;
-    const int par = (int)(tag & 1u);
-    BTL(0);
-    if (own) ul[rl] = u_;
-    __syncthreads();
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < 64; ++k) acc += kv[k] * ul[cb + h * 64 + k];
-    acc += dpp_move<0xB1>(acc);                      // the two halves of the row
-    BTL(1);
-    double v[NV];
-    v[0] = own ? r_ * u_ : 0.0; v[1] = own ? acc * u_ : 0.0; v[2] = own ? r_ * r_ : 0.0;
-#pragma unroll
-    for (int q = 0; q < NH; ++q) v[3 + q] = own ? hc[q] * u_ : 0.0;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) { const double w_ = wave_sum(v[i]); if (lane == 0) red[wv * 8 + i] = w_; }
-    __syncthreads();
-    BTL(2);
-    unsigned long long *gb = reinterpret_cast<unsigned long long *>(bc.sbuf) + (size_t)par * nwg * RES_GSTRIDE;
-    if (wv == 0 && lane < 2 * NV) {
-      const int i = lane >> 1;
-      double sv = 0.0;
-#pragma unroll
-      for (int w8 = 0; w8 < 8; ++w8) sv += red[w8 * 8 + i];
-      const unsigned half = (lane & 1) ? (unsigned)__double2hiint(sv) : (unsigned)__double2loint(sv);
-      __hip_atomic_store(gb + (size_t)g * RES_GSTRIDE + lane, ((unsigned long long)tag << 32) | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (wv < ((nwg + 63) >> 6)) {
-      // one workgroup's 2 NV granules per lane, all loads in flight together, only what is still missing (see k_pcg_resident)
-      const int o = t;
-      const __amdgpu_buffer_rsrc_t rg = res_rsrc(gb, (size_t)nwg * RES_GSTRIDE * 8);
-      unsigned pend = o < nwg ? (1u << (2 * NV)) - 1u : 0u;
-      int miss16 = -1;
-      unsigned *svw = reinterpret_cast<unsigned *>(sval) + 2 * NV * o;
-      unsigned seen = 0, rounds = 0;
-      long long t0 = wall_clock64();
-      int late = 0;
-      bool gave = false;
-      while (true) {
-        u32x2 gv[2 * NV];
-#pragma unroll
-        for (int q = 0; q < 2 * NV; ++q) if (pend & (1u << q)) gv[q] = __builtin_amdgcn_raw_buffer_load_b64(rg, (o * RES_GSTRIDE + q) * 8, 0, AUX_SC1 | AUX_VOL);
-#pragma unroll
-        for (int q = 0; q < 2 * NV; ++q)
-          if (pend & (1u << q)) { if (gv[q].y == tag) { svw[q] = gv[q].x; pend &= ~(1u << q); } else seen = gv[q].y; }
-        if (!__any(pend != 0)) break;
-        asm volatile("" ::: "memory");
-        if (++rounds & 15u) { __builtin_amdgcn_s_sleep(1); continue; }
-        const int verdict = res_spin_check(st, t0, late);
-        if (verdict) {
-          const unsigned long long miss = __ballot(pend != 0);
-          const int fl = miss ? (int)__ffsll((long long)miss) - 1 : 0;
-          const unsigned sv = (unsigned)__builtin_amdgcn_readlane((int)seen, fl);
-          const int gi = __builtin_amdgcn_readlane((int)pend, fl);
-          if (lane == 0) { res_note(st, bc.dbg, g, verdict, 2, nx, miss ? 64 * wv + fl : -1, sv, t0, rounds, gi); tot[7] = 1.0; }
-          gave = true;
-          break;
-        }
-        if (rounds == 16u) { const unsigned long long ms = __ballot(pend != 0); miss16 = ms ? 64 * wv + (int)__ffsll((long long)ms) - 1 : -1; }
-        if ((rounds & 63u) == 0 && wv == 0) {          // a long wait: say it again
-          if (lane < 2 * NV) {
-            const int i = lane >> 1;
-            double sv2 = 0.0;
-#pragma unroll
-            for (int w8 = 0; w8 < 8; ++w8) sv2 += red[w8 * 8 + i];
-            const unsigned half = (lane & 1) ? (unsigned)__double2hiint(sv2) : (unsigned)__double2loint(sv2);
-            __hip_atomic_store(gb + (size_t)g * RES_GSTRIDE + lane, ((unsigned long long)tag << 32) | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          if (lane == 0) atomicAdd(&st->res_repub, 1);
-        }
-        if ((rounds & 255u) == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        __builtin_amdgcn_s_sleep(1);
-      }
-      if (rounds >= 16u && lane == 0 && !gave) res_slow_note(st, t0, nx, g, miss16, 2);
-    }
-    BTL(3);
-    __syncthreads();
-    if (wv == 0) {
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        double a = 0.0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) if (lane + 64 * q < nwg) a += sval[NV * (lane + 64 * q) + i];
-        a = wave_sum(a);
-        if (lane == 0) tot[i] = a;
-      }
-    }
-    __syncthreads();
-    BTL(4);
-    if (tot[7] != 0.0) { failed = true; break; }
-    const double gam = tot[0], rr = tot[2];
-    double del = tot[1];
-#pragma unroll
-    for (int q = 0; q < NH; ++q) del += hrho[q] * (tot[3 + q] * tot[3 + q]);
-    const CgStep cs = cg_step(rr, gam, del, gam_old, alp_old, tol2, iters, 0, prm, false);
-    if (cs.stop) { conv = cs.conv; bad = cs.bad && !cs.conv; break; }
-    ++iters; gam_old = gam; alp_old = cs.alpha;
-    if (own) {
-      double w_ = acc;
-#pragma unroll
-      for (int q = 0; q < NH; ++q) w_ += (hrho[q] * tot[3 + q]) * hc[q];
-      p_ = cs.first ? u_ : (u_ + cs.beta * p_);
-      s_ = cs.first ? w_ : (w_ + cs.beta * s_);
-      x_ += cs.alpha * p_;
-      r_ -= cs.alpha * s_;
-      u_ = mi * r_;
-    }
-    BTL(5);
-  }
-#ifdef OSQP_AMD_TIMELINE
-  if (g == 0 && t == 0 && !failed) {
-    const int cnt = (nx - 1 < 64 ? nx - 1 : 64) * 6;          // (the last trip broke out before its stamp 5)
-    const unsigned long long k0 = atomicAdd(c.tl, (unsigned long long)cnt + 1);
-    if (k0 + cnt + 1 < TL_CAP - 2) {
-      for (int q = 0; q < cnt; ++q) c.tl[1 + k0 + q] = ((unsigned long long)(40 + q % 6) << 56) | ((unsigned long long)btl[q] & 0x00FFFFFFFFFFFFFFull);
-      c.tl[1 + k0 + cnt] = (46ull << 56) | (wall_clock64() & 0x00FFFFFFFFFFFFFFull);
-    }
-  }
-#endif
-  if (failed) {
-    if (t == 0) {
-      __hip_atomic_store(&st->res_fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      int *d = bc.dbg + (size_t)RES_DBG * g;
-      d[0] = nx; d[1] = 3; d[2] = iters;
-    }
-    return;
-  }
-  if (own && iters > 0) c.va[j] = x_;
-  if (g == 0 && t == 0) {
-    st->iters[0] = iters; st->iters[1] = 0;
-    st->done = conv ? 1 : 2;
-    if (bad) st->neg_curv = 1;
-    st->tol2 = tol2;
-    st->res_epoch = ep0 + (unsigned)nx;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Block-direct solve: the portfolio family (BASELINE config 5) without any iteration at all.
-//
-// Same structure as k_pcg_blockres accepts: P = dense diagonal blocks only, every row of A single-entry except nh <= 4
-// huge rows.  Then  K = B + A_h' R_h A_h  with B = blockdiag(P_b + sigma I + diag(sum_i rho_i a_ij^2)) and the nh huge
-// rows as a low-rank term, and by the Woodbury identity
-//     K^-1 r = t - W c,     t = B^-1 r,   W = B^-1 A_h' (n x nh),   c = (R_h^-1 + A_h W)^-1 (A_h t).
-// The blocks are inverted explicitly (k_blk_invert: in-place Gauss-Jordan in LDS, no pivoting -- B_b is positive
-// definite or the problem is not convex: a non-positive pivot is reported as negative curvature) whenever rho, sigma or
-// the matrices change, and kept in HBM in the layout of the dense blocks of P.  One linear solve is then
-//     k_blk_apply   t = B^-1 r0 : ONE pass over the 50 MB of inverse blocks (the dense_block_mv of k_cg_B, which the PCG
-//                   ran 26 times per ADMM iteration) + the partials of A_h t
-//     k_blk_finish  c from the partials (nh x nh system, inverted on the host at refresh), x~ = x~0 + t - W c
-// applied to the residual r0 = b - K x~0 of the warm start k_pcg_init forms anyway (one step of iterative refinement
-// on top of the previous x~: the error of the explicit inverse, ~cond(B) eps, multiplies the CORRECTION, not x~).
-// Config 5: 258 -> 4x us per ADMM iteration.  OSQP_AMD_BLOCK_DIRECT=0 keeps the block-resident PCG.
-// ---------------------------------------------------------------------------
-struct BdCtx {
-  double *binv;            // inverse blocks, layout of Ctx::dP.val (DenseBlk::off / pitch)
-  double *t;               // [n] B^-1 r
-  double *wh;              // [nh][n] W = B^-1 A_h'
-  double *cinv;            // [nh][nh] (R_h^-1 + A_h W)^-1
-  double *part;            // [MAX_HUGE_FOLD][nblk] partials of A_h t per block
-  int    *flag;            // [0] a pivot was not positive
-  double *chk;             // [2] checks of a fresh inverse (bit patterns of non-negative doubles, atomicMax): blocks, capacitance matrix
-  double *cap0;            // [kc][kc] the capacitance matrix as formed (coupled form): its inverse is checked against it
-  int     fin_dots;        // the kernel that writes x~ also leaves the folded huge rows' partials of A x~ for k_admm_finalize (no k_huge_dot launch)
-  // coupled form (kc > 0): EVERY row of A with two or more entries -- sector rows, the budget row, whatever their length -- is a
-  // term of the low-rank part; nothing of W is stored (see k_cpl_dot)
-  int     kc;
-  const int *crow;         // [kc] the coupling rows of A
-  const int *cidx;         // [m] position of a row in crow, -1 for the single-entry rows
-  const int *chuge;        // [kc] which folded huge row (Ctx::hrow) a coupling row is, -1: none
-  const int *cbptr;        // [n + 1] / cbent: per column j the entries of the coupling rows, {position in crow, slot of the value in M.val}
-  const int2 *cbent;
-  double *cs, *cc;         // [kc] S t and Cinv S t
-  double *cap;             // [kc][kc] capacitance matrix R^-1 + S B^-1 S', inverted in place (k_cap_invert)
-  double *cap2;            // [kc][kc] the other copy of the pivot steps
-  double *wm;              // [16][n] scratch of the refresh: B^-1 S' for 16 coupling rows
-};
-
-#define INV_TB 1024
-__global__ void __launch_bounds__(INV_TB) k_blk_invert(Ctx c, BdCtx bd) {
-  extern __shared__ __attribute__((aligned(16))) double bl[];       // b x b, row pitch b
-  __shared__ double colp[DENSE_MAX], rowp[DENSE_MAX];
-  const double sigma = c.prm->sigma;
-  // thread -> column j and the rows i = i0, i0 + 8, ... (no index arithmetic in the sweep: a division per element made this
-  // kernel 2.85 ms for the 400 blocks of config 5; with 256 threads -- one wavefront per SIMD, nothing to hide the LDS round trips
-  // of the sweep behind -- it was 1.9 ms)
-  constexpr int RS = INV_TB / DENSE_MAX, RU = DENSE_MAX / RS;        // row step 8, up to 16 rows per thread
-  const int t = threadIdx.x, j = t & (DENSE_MAX - 1), i0 = t / DENSE_MAX;
-  for (int db = blockIdx.x; db < c.dP.nblk; db += gridDim.x) {
-    const DenseBlk d = c.dP.blk[db];
-    const int b = d.b;
-    if (j < b) for (int i = i0; i < b; i += RS) bl[i * b + j] = c.dP.val[d.off + (size_t)i * d.pitch + j];
-    __syncthreads();
-    if (t < b) {                       // diagonal: sigma + the single-entry rows of A at this column (the huge rows are the low-rank part)
-      const int jj = d.c0 + t;
-      double dadd = sigma;
-      for (int k = c.Mk.rowptr[jj]; k < c.Mk.rowptr[jj + 1]; ++k) {
-        const int row = c.Mk.col[k] - c.n;
-        if (bd.kc && bd.cidx[row] >= 0) continue;           // (coupled form: such a row is part of S)
-        const double a = c.Mk.val[k]; dadd += c.rho[row] * a * a;
-      }
-      bl[t * b + t] += dadd;
-    }
-    __syncthreads();
-    for (int p = 0; p < b; ++p) {
-      if (t < b) { colp[t] = bl[t * b + p]; rowp[t] = bl[p * b + t]; }
-      __syncthreads();
-      const double piv = rowp[p];
-      if (!(piv > 0.0) && t == 0) atomicOr(bd.flag, 1);
-      const double inv = 1.0 / piv;
-      if (j < b) {
-        const double rj = rowp[j] * inv;              // row p of the result (j != p)
-        double cur[RU], cp[RU];                       // all rows of the thread: their LDS reads are in flight together
-#pragma unroll
-        for (int u = 0; u < RU; ++u) { const int i = i0 + RS * u; if (i < b) { cur[u] = bl[i * b + j]; cp[u] = colp[i]; } else { cur[u] = 0.0; cp[u] = 0.0; } }
-#pragma unroll
-        for (int u = 0; u < RU; ++u) {
-          const int i = i0 + RS * u;
-          if (i >= b) continue;
-          double v;
-          if (i == p) v = (j == p) ? inv : rj;
-          else if (j == p) v = -cp[u] * inv;
-          else v = cur[u] - cp[u] * rj;
-          bl[i * b + j] = v;
-        }
-      }
-      __syncthreads();
-    }
-    if (j < d.pitch) for (int i = i0; i < b; i += RS) bd.binv[d.off + (size_t)i * d.pitch + j] = j < b ? bl[i * b + j] : 0.0;
-    __syncthreads();
-  }
-}
-
-// out_b = Binv_b in_b for every block (in, out contiguous n-vectors), and the partials of A_h out for the huge rows
-__global__ void __launch_bounds__(TB) k_blk_apply(Ctx c, BdCtx bd, const double *in, double *out, int gated) {
-  if (gated) { const State *st = c.st; if (st->stalled || !st->run) return; }
-  __shared__ double scratch[5 * DENSE_MAX];
-  __shared__ double red[16];
-  const DenseP inv{c.dP.nblk, c.dP.blk, bd.binv};
-  for (int db = blockIdx.x; db < c.dP.nblk; db += gridDim.x) {
-    const DenseBlk d = c.dP.blk[db];
-    const double y = dense_block_mv(inv, d, in, scratch);
-    const int j = d.c0 + threadIdx.x;
-    const bool on = (int)threadIdx.x < d.b;
-    if (on) out[j] = y;
-    for (int h = 0; h < c.nh; ++h) {
-      const double s = block_sum(on ? c.hcol[(size_t)h * c.n + j] * y : 0.0, red);
-      if (threadIdx.x == 0) bd.part[(size_t)h * c.dP.nblk + db] = s;
-    }
-    __syncthreads();
-  }
-}
-
-// (A x~)_h of the folded huge rows for k_admm_finalize, by the kernel that has just written x~: this workgroup's partial into its
-// slot of Ctx::part_h, zeros into the slots no workgroup of this launch owns (k_huge_dot, which other paths run, fills all gridA)
-__device__ __forceinline__ void fin_huge_partials(const Ctx &c, const double *hd, double *red) {
-  for (int h = 0; h < c.nh; ++h) {
-    const double s = block_sum(hd[h], red);
-    if (threadIdx.x == 0)
-      for (int slot = blockIdx.x; slot < c.gridA; slot += gridDim.x) c.part_h[(size_t)h * c.gridA + slot] = slot == (int)blockIdx.x ? s : 0.0;
-  }
-}
-
-// x~ = x~0 + t - W c with c = Cinv (A_h t); the linear solve is complete (one "PCG iteration" in the statistics)
-__global__ void __launch_bounds__(TB) k_blk_finish(Ctx c, BdCtx bd) {
-  State *st = c.st;
-  if (st->stalled || !st->run) return;
-  __shared__ double red[16];
-  __shared__ double cs[MAX_HUGE_FOLD];
-  double sh[MAX_HUGE_FOLD];
-#pragma unroll
-  for (int h = 0; h < MAX_HUGE_FOLD; ++h) {
-    double s = 0.0;
-    if (h < c.nh) for (int i = threadIdx.x; i < c.dP.nblk; i += TB) s += bd.part[(size_t)h * c.dP.nblk + i];
-    sh[h] = h < c.nh ? block_sum(s, red) : 0.0;
-    // plain form: K^-1 b = t0 - W Cinv (A_h t0 - R^-1 beta), t0 = B^-1 b0, b = b0 + A_h' beta: beta_h = rho_h z_h - y_h is what
-    // made `t - W c` cancel to eight digits when it sat inside b (rho_eq = 4 050 on the budget row); here it never meets B^-1
-    if (c.plain_rhs && h < c.nh) sh[h] -= c.vb[c.n + c.hrow[h]] / c.rho[c.hrow[h]];
-  }
-  if (threadIdx.x < MAX_HUGE_FOLD) {
-    double v = 0.0;
-    for (int h = 0; h < c.nh; ++h) v += bd.cinv[threadIdx.x * MAX_HUGE_FOLD + h] * sh[h];
-    cs[threadIdx.x] = (int)threadIdx.x < c.nh ? v : 0.0;
-  }
-  __syncthreads();
-  static_assert(MAX_HUGE_FOLD == 4, "initialisers below");
-  double hd[MAX_HUGE_FOLD] = {0.0, 0.0, 0.0, 0.0};
-  for (int j = blockIdx.x * TB + threadIdx.x; j < c.n; j += gridDim.x * TB) {
-    double v = bd.t[j];
-    for (int h = 0; h < c.nh; ++h) v -= bd.wh[(size_t)h * c.n + j] * cs[h];
-    const double xt = c.plain_rhs ? v : c.vx[j] + v;
-    c.va[j] = xt;
-    if (bd.fin_dots) for (int h = 0; h < c.nh; ++h) hd[h] += c.hcol[(size_t)h * c.n + j] * xt;
-  }
-  if (bd.fin_dots) fin_huge_partials(c, hd, red);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    st->iters[0] = 1; st->iters[1] = 0; st->done = 1;
-    if (*bd.flag) st->neg_curv = 1;
-  }
-}
-
-// ---- coupled form: P = dense diagonal blocks, A = single-entry rows + kc <= CPL_MAX rows of any shape ---------------------------
-// (SURVEY C5 "+ 500 sparse sector rows": rows that tie variables of different blocks together.)  K = B + S' R S with S the kc
-// coupling rows, and   K^-1 r = t - B^-1 S' c,   t = B^-1 r,   c = (R^-1 + S B^-1 S')^-1 S t.   W = B^-1 S' would be n x kc dense
-// (200 MB at 500 rows), so it is never formed: the second term is a second pass over the inverse blocks (50 MB).  Per solve:
-//     k_blk_apply (t)  ->  k_cpl_dot (S t, one workgroup per coupling row)  ->  k_cpl_solve (c: kc x kc dense product, one wavefront
-//     per row)  ->  k_blk_apply_back (S' c gathered on the fly as the input of the block product; x~ = x~0 + t - result).
-// The capacitance matrix is built at refresh from kc block passes (column r = S B^-1 S' e_r) and inverted by one workgroup
-// in place (k_cap_invert: Gauss-Jordan without pivoting, the matrix is positive definite when K is).
-#define CPL_MAX 512
-// out[blockIdx.y * ostride + r] = (row crow[r] of A) . x[blockIdx.y * xstride ...]; use_part: a folded huge row takes the per-block
-// partials the block pass left instead of walking its 50 000 entries (single right-hand side only)
-__global__ void __launch_bounds__(TB) k_cpl_dot(Ctx c, BdCtx bd, const double *x, double *out, int gated, int use_part, long long xstride, long long ostride, int nrhs) {
-  if (gated) { const State *st = c.st; if (st->stalled || !st->run) return; }
-  if ((int)blockIdx.y >= nrhs) return;
-  __shared__ double red[16];
-  x += (size_t)blockIdx.y * xstride; out += (size_t)blockIdx.y * ostride;
-  const int i = bd.crow[blockIdx.x], h = use_part ? bd.chuge[blockIdx.x] : -1;
-  double s = 0.0;
-  if (h >= 0) {
-    for (int q = threadIdx.x; q < c.dP.nblk; q += TB) s += bd.part[(size_t)h * c.dP.nblk + q];
-  } else {
-    const int k0 = c.A.rowptr[i], k1 = c.A.rowptr[i + 1];
-    int k = k0 + (int)threadIdx.x;
-    for (; k + 3 * TB < k1; k += 4 * TB) {
-      const double v0 = c.A.val[k], v1 = c.A.val[k + TB], v2 = c.A.val[k + 2 * TB], v3 = c.A.val[k + 3 * TB];
-      const double x0 = x[c.A.col[k]], x1 = x[c.A.col[k + TB]], x2 = x[c.A.col[k + 2 * TB]], x3 = x[c.A.col[k + 3 * TB]];
-      s += v0 * x0; s += v1 * x1; s += v2 * x2; s += v3 * x3;
-    }
-    for (; k < k1; k += TB) s += c.A.val[k] * x[c.A.col[k]];
-  }
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) out[blockIdx.x] = s;
-}
-__global__ void __launch_bounds__(TB) k_cpl_solve(Ctx c, BdCtx bd) {
-  { const State *st = c.st; if (st->stalled || !st->run) return; }
-  const int r = blockIdx.x * (TB / 64) + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (r >= bd.kc) return;
-  double s = 0.0;
-  if (c.plain_rhs) for (int q = lane; q < bd.kc; q += 64) { const int i = bd.crow[q]; s += bd.cap[(size_t)r * bd.kc + q] * (bd.cs[q] - c.vb[c.n + i] / c.rho[i]); }   // (S t0 - R^-1 beta)
-  else for (int q = lane; q < bd.kc; q += 64) s += bd.cap[(size_t)r * bd.kc + q] * bd.cs[q];
-  s = wave_sum(s);
-  if (lane == 0) bd.cc[r] = s;
-}
-// entry j of S' v for a kc-vector v: the coupling rows' entries of column j as (position in crow, slot of the value in M), a list
-// of their own (through M itself: split/rowptr -> col -> cidx -> v, four dependent loads; here three)
-__device__ __forceinline__ double cpl_back_entry(const Ctx &c, const BdCtx &bd, const double *v, int j) {
-  double s = 0.0;
-  for (int k = bd.cbptr[j]; k < bd.cbptr[j + 1]; ++k) { const int2 e = bd.cbent[k]; s += c.M.val[e.y] * v[e.x]; }
-  return s;
-}
-// x~ = x~0 + t - B^-1 S' c, the solve is complete
-__global__ void __launch_bounds__(TB) k_blk_apply_back(Ctx c, BdCtx bd) {
-  State *st = c.st;
-  if (st->stalled || !st->run) return;
-  __shared__ double scratch[5 * DENSE_MAX];
-  __shared__ double red[16];
-  const DenseP inv{c.dP.nblk, c.dP.blk, bd.binv};
-  double hd[MAX_HUGE_FOLD] = {0.0, 0.0, 0.0, 0.0};
-  for (int db = blockIdx.x; db < c.dP.nblk; db += gridDim.x) {
-    const DenseBlk d = c.dP.blk[db];
-    const double y = dense_block_mv_x<true>(inv, d, [&](int j) { return cpl_back_entry(c, bd, bd.cc, j); }, scratch);
-    const int j = d.c0 + threadIdx.x;
-    if ((int)threadIdx.x < d.b) {
-      const double xt = c.plain_rhs ? bd.t[j] - y : c.vx[j] + (bd.t[j] - y);
-      c.va[j] = xt;
-      if (bd.fin_dots) for (int h = 0; h < c.nh; ++h) hd[h] += c.hcol[(size_t)h * c.n + j] * xt;
-    }
-    __syncthreads();
-  }
-  if (bd.fin_dots) fin_huge_partials(c, hd, red);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    st->iters[0] = 1; st->iters[1] = 0; st->done = 1;
-    if (*bd.flag) st->neg_curv = 1;
-  }
-}
-// Refresh: W_g = B^-1 S_g' for a group of 16 coupling rows [r0, r0 + 16) at once -- the one place of this path where a block
-// meets several vectors, so the product runs on the matrix cores: v_mfma_f64_16x16x4_f64, D (16 rows of the block x 16
-// right-hand sides) += A (16 x 4 tile of the inverse block, read transposed: the block is symmetric, so 4 rows x 16
-// contiguous doubles per wave load) x B (4 x 16 tile of S_g' from LDS).  Wavefront w owns rows [32 w, 32 w + 32) of the block.
-// One pass over the 50 MB of inverse blocks serves 16 columns of the capacitance matrix (the VALU kernel above: one).
-// out: [16][n].
-typedef double mfma_d4 __attribute__((ext_vector_type(4)));
-__global__ void __launch_bounds__(TB) k_blk_apply_multi(Ctx c, BdCtx bd, int r0, double *out) {
-  __shared__ double xl[DENSE_MAX * 16];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
-  static_assert(TB == 256 && DENSE_MAX == 128, "four wavefronts x two 16-row tiles cover a block");
-  for (int db = blockIdx.x; db < c.dP.nblk; db += gridDim.x) {
-    const DenseBlk d = c.dP.blk[db];
-    const double *dv = bd.binv + d.off;
-    double a[2][DENSE_MAX / 4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int kt = 0; kt < DENSE_MAX / 4; ++kt) {
-        const int k = 4 * kt + lk, i = 32 * w + 16 * t + li;
-        a[t][kt] = (k < d.b && i < d.b) ? dv[(size_t)k * d.pitch + i] : 0.0;
-      }
-    for (int q = threadIdx.x; q < DENSE_MAX * 16; q += TB) xl[q] = 0.0;
-    __syncthreads();
-    if ((int)threadIdx.x < d.b) {
-      const int j = d.c0 + threadIdx.x;
-      for (int k = c.M.split[j]; k < c.M.rowptr[j + 1]; ++k) {
-        const int q = bd.cidx[c.M.col[k] - c.n] - r0;
-        if (q >= 0 && q < 16) xl[threadIdx.x * 16 + q] = c.M.val[k];
-      }
-    }
-    __syncthreads();
-    mfma_d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kt = 0; kt < DENSE_MAX / 4; ++kt) {
-      const double bv = xl[(4 * kt + lk) * 16 + li];
-      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0][kt], bv, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[1][kt], bv, acc1, 0, 0, 0);
-    }
-    // D[row = lk + 4 r][col = li]
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i0 = 32 * w + lk + 4 * r, i1 = i0 + 16;
-      if (i0 < d.b) out[(size_t)li * c.n + d.c0 + i0] = acc0[r];
-      if (i1 < d.b) out[(size_t)li * c.n + d.c0 + i1] = acc1[r];
-    }
-    __syncthreads();
-  }
-}
-// cap <- (cap + R^-1)^-1: Gauss-Jordan without pivoting (the matrix is positive definite when K is), one launch per pivot over
-// the whole machine, from one copy of the matrix into the other (no element is read after it was rewritten).  One workgroup
-// walking the 2 MB in global memory took 61 us per pivot (31 ms at 501 rows); a launch takes 3.
-__global__ void __launch_bounds__(TB) k_cap_diag(Ctx c, BdCtx bd) {
-  const int r = blockIdx.x * TB + threadIdx.x;
-  if (r >= bd.kc) return;
-  const double rho = c.rho[bd.crow[r]];
-  if (!(rho > 0.0)) atomicOr(bd.flag, 1);
-  bd.cap[(size_t)r * bd.kc + r] += 1.0 / rho;
-}
-__global__ void __launch_bounds__(TB) k_cap_step(BdCtx bd, const double *src, double *dst, int p) {
-  const int kc = bd.kc;
-  const long long e = (long long)blockIdx.x * TB + threadIdx.x;
-  if (e >= (long long)kc * kc) return;
-  const int i = (int)(e / kc), j = (int)(e - (long long)i * kc);
-  const double piv = src[(size_t)p * kc + p];
-  if (e == 0 && !(piv > 0.0)) atomicOr(bd.flag, 1);
-  const double inv = 1.0 / piv, rj = src[(size_t)p * kc + j] * inv, ci = src[(size_t)i * kc + p];
-  double v;
-  if (i == p) v = (j == p) ? inv : rj;
-  else if (j == p) v = -ci * inv;
-  else v = src[e] - ci * rj;
-  dst[e] = v;
-}
+#include "engine_pcg_resident.h"
+#include "engine_pcg_blockres.h"
+#include "engine_block_direct.h"
 
 #include "dense_direct.h"
-
-// Checks of the block-direct solve's fresh inverses (blk_refresh), as the dense-direct solve has them: k_blk_invert and the
-// capacitance steps are Gauss-Jordan (error ~ cond^2 eps).  Per block: u = probe values, y = Binv_b u, z = B_b y with B_b = P_b +
-// diag as k_blk_invert forms it; chk[0] = max |z - u| over all blocks.
-__global__ void __launch_bounds__(TB) k_blk_check(Ctx c, BdCtx bd) {
-  __shared__ double scratch[5 * DENSE_MAX];
-  __shared__ double red[16];
-  const double sigma = c.prm->sigma;
-  const DenseP inv{c.dP.nblk, c.dP.blk, bd.binv};
-  double worst = 0.0;
-  for (int db = blockIdx.x; db < c.dP.nblk; db += gridDim.x) {
-    const DenseBlk d = c.dP.blk[db];
-    const double y = dense_block_mv_x(inv, d, [](int j) { return dd_probe_value(j); }, scratch);
-    const int j = d.c0 + threadIdx.x;
-    const bool on = (int)threadIdx.x < d.b;
-    if (on) bd.t[j] = y;
-    __syncthreads();
-    double z = dense_block_mv_x(c.dP, d, [&](int jj) { return bd.t[jj]; }, scratch);
-    if (on) {
-      double dadd = sigma;
-      for (int k = c.Mk.rowptr[j]; k < c.Mk.rowptr[j + 1]; ++k) {
-        const int row = c.Mk.col[k] - c.n;
-        if (bd.kc && bd.cidx[row] >= 0) continue;
-        const double a = c.Mk.val[k]; dadd += c.rho[row] * a * a;
-      }
-      z += dadd * y;
-      const double e = fabs(z - dd_probe_value(j));
-      worst = fmax(worst, e == e ? e : 1e300);
-    }
-    __syncthreads();
-  }
-  for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = worst;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned long long *>(bd.chk), (unsigned long long)__double_as_longlong(fmax(fmax(red[0], red[1]), fmax(red[2], red[3]))));
-}
-// coupled form: w = cap u, z = cap0 w (cap0: the capacitance matrix as formed, cap: its inverse); chk[1] = max |z - u|.  One workgroup.
-__global__ void __launch_bounds__(TB) k_cap_check(BdCtx bd) {
-  __shared__ double u[CPL_MAX], w[CPL_MAX], red[16];
-  const int kc = bd.kc;
-  for (int r = threadIdx.x; r < kc; r += TB) u[r] = dd_probe_value(r);
-  __syncthreads();
-  for (int r = threadIdx.x; r < kc; r += TB) { double s = 0.0; for (int q = 0; q < kc; ++q) s += bd.cap[(size_t)r * kc + q] * u[q]; w[r] = s; }
-  __syncthreads();
-  double worst = 0.0;
-  for (int r = threadIdx.x; r < kc; r += TB) { double s = 0.0; for (int q = 0; q < kc; ++q) s += bd.cap0[(size_t)r * kc + q] * w[q]; const double e = fabs(s - u[r]); worst = fmax(worst, e == e ? e : 1e300); }
-  for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = worst;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned long long *>(bd.chk + 1), (unsigned long long)__double_as_longlong(fmax(fmax(red[0], red[1]), fmax(red[2], red[3]))));
-}
+#include "engine_block_check.h"
 
 // ---------------------------------------------------------------------------
 // Elimination of slack-like variables from the linear system (launch-per-step kernels and the resident PCG).
@@ -3842,12 +2527,16 @@ static int build_resident(hipeng *e, int plan_nwg = 0, ResPlanOut *po = nullptr)
 }
 
 
-// Block-direct form (k_blk_invert / k_blk_apply / k_blk_finish): same eligibility as the block-resident PCG.
-static bool blocks_eligible(hipeng *e) {
+// P consists of dense diagonal blocks only: they tile 0..n, none above DENSE_MAX.
+static bool blocks_tile(hipeng *e) {
   if (e->dP_blks.empty()) return false;
   int next = 0;
   for (const DenseBlk &d : e->dP_blks) { if (d.c0 != next || d.b > DENSE_MAX) return false; next += d.b; }
-  if (next != e->n) return false;
+  return next == e->n;
+}
+// What the block-resident PCG (k_pcg_blockres) and the plain block-direct form (k_blk_invert / k_blk_apply / k_blk_finish) accept.
+static bool blocks_eligible(hipeng *e) {
+  if (!blocks_tile(e)) return false;
   // rows of A: one entry each, except the folded huge rows (all of the huge ones must be folded)
   if ((int)e->A.blk.size() - e->A.nwave != (int)e->hrows.size()) return false;
   std::vector<char> ishuge(std::max(1, e->m), 0);
@@ -3858,10 +2547,7 @@ static bool blocks_eligible(hipeng *e) {
 // Coupled form of the block-direct solve: the blocks tile 0..n and at most CPL_MAX rows of A have two or more entries (any
 // length, any pattern).  `rows` receives them.
 static bool blocks_coupled_eligible(hipeng *e, std::vector<int> &rows) {
-  if (e->dP_blks.empty()) return false;
-  int next = 0;
-  for (const DenseBlk &d : e->dP_blks) { if (d.c0 != next || d.b > DENSE_MAX) return false; next += d.b; }
-  if (next != e->n) return false;
+  if (!blocks_tile(e)) return false;
   const int cap = e->sw.block_coupled_max;
   rows.clear();
   for (int i = 0; i < e->m; i++) if (e->A.rowptr[i + 1] - e->A.rowptr[i] >= 2) { if ((int)rows.size() >= cap) return false; rows.push_back(i); }
@@ -4019,17 +2705,7 @@ static int blk_refresh(hipeng *e) {
 
 // Block-resident form (k_pcg_blockres): P = dense diagonal blocks only, rows of A single-entry or folded huge rows.
 static int build_blockres(hipeng *e) {
-  const int n = e->n;
-  if (!e->sw.resident || !e->sw.resident_blocks || e->dP_blks.empty()) return 0;
-  // the blocks tile 0..n
-  int next = 0;
-  for (const DenseBlk &d : e->dP_blks) { if (d.c0 != next || d.b > DENSE_MAX) return 0; next += d.b; }
-  if (next != n) return 0;
-  // rows of A: one entry each, except the folded huge rows (all of the huge ones must be folded)
-  if ((int)e->A.blk.size() - e->A.nwave != (int)e->hrows.size()) return 0;
-  std::vector<char> ishuge(std::max(1, e->m), 0);
-  for (int hr : e->hrows) ishuge[hr] = 1;
-  for (int i = 0; i < e->m; i++) if (!ishuge[i] && e->A.rowptr[i + 1] - e->A.rowptr[i] != 1) return 0;
+  if (!e->sw.resident || !e->sw.resident_blocks || !blocks_eligible(e)) return 0;
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, e->device));
   const int nwg = std::min(256, prop.multiProcessorCount) - 8;       // one CU per XCD stays free (see build_resident)
@@ -4957,311 +3633,7 @@ extern "C" int hipeng_kkt_solve(hipeng *e, c_float *b) {
   for (int q = 0; q < n + m; q++) b[q] += r[(size_t)q];
   return 0;
 }
-
-// ---- kernel-level entry points for tests and the roofline measurement -------
-extern "C" int hipeng_spmv(hipeng *e, int which, const c_float *x, c_float *y) {
-  if (!e || !x || !y || which < 0 || which > 2) return HIPENG_ERR_ARG;
-  HIPCHK(hipSetDevice(e->device));
-  const int n = e->n, m = e->m;
-  double *in = e->c.pt0, *out = e->c.pt1;   // scratch of n+m doubles each
-  HIPCHK(hipMemsetAsync(in, 0, (size_t)std::max(1, n + m) * sizeof(double), e->stream));
-  // A x from x in [0, n); A' y (selector 2) from y behind n unused slots, P x (selector 1) from x in [0, n), both through the fused rows of M
-  if (which == 1 ? upload_vec(e, in + n, x, m) : upload_vec(e, in, x, n)) return HIPENG_ERR_HIP;
-  if (which == 0) launch_spmv(e, e->c.A, in, out, 0);
-  else launch_spmv(e, e->c.M, in, out, which == 1 ? 2 : 1);
-  HIPCHK(hipMemcpyAsync(y, out, (size_t)(which == 0 ? m : n) * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
-}
-
-// Device-to-device SpMV with the engine's matrices (which as in hipeng_spmv), on the engine's stream, no sync:
-// the building block of the row-partitioned multi-GPU variant (osqp_amd/rowpart.py), whose vectors live in
-// torch tensors.  d_x / d_y are device pointers of n (A x: in, A' y / P x: out) or m doubles.
-extern "C" int hipeng_spmv_dev(hipeng *e, int which, const double *d_x, double *d_y) {
-  if (!e || !d_x || !d_y || which < 0 || which > 2) return HIPENG_ERR_ARG;
-  HIPCHK(hipSetDevice(e->device));
-  const int n = e->n, m = e->m;
-  if (which == 0) {
-    if (m > 0) launch_spmv(e, e->c.A, d_x, d_y, 0);
-  } else {
-    // the fused row matrix reads y at column ids n + i: stage it behind n unused slots.  x is staged too: k_spmv stages the products of whole
-    // rows of [P | A'] (the A' entries gather at column ids up to n + m - 1) before it sums the P part, so the input must be n + m long
-    double *in = e->c.pt0;
-    if (which == 2 || m > 0) HIPCHK(hipMemcpyAsync(which == 1 ? in + n : in, d_x, (size_t)(which == 1 ? m : n) * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-    launch_spmv(e, e->c.M, in, d_y, which == 1 ? 2 : 1);
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int hipeng_time_kernel(hipeng *e, int which, int reps, double *usec) {
-  if (!e || !usec || reps <= 0 || which < 0 || which > 8) return HIPENG_ERR_ARG;
-  if (which == 8 && !e->resident_available()) return HIPENG_ERR_ARG;
-  HIPCHK(hipSetDevice(e->device));
-  CuLease lease;
-  if (which == 8 && e->one_launch()) lease.take(e->device, e->res_cus, e->one_launch_grid());
-  auto one = [&](int it) {
-    // the first two kernels of a resident ADMM iteration: right-hand side + start residual, then the whole linear solve
-    // (without k_admm_finalize the iterates do not move: every repetition solves the same system from the same start)
-    if (which == 8) { launch_init(e, 1, true); launch_resident(e); return; }
-    if (which == 5) { launch_init(e, 1); return; }   // first kernel of an ADMM iteration
-    if (which == 6) { launch_pcg_iter(e, it, 4); return; }   // one whole PCG iteration (all its launches, in loop order)
-
-    if (which == 7) { hipLaunchKernelGGL(k_fill, dim3(1), dim3(TB), 0, e->stream, e->c.cvec, 0.0, 0); return; }   // empty dependent launch
-    if (which == 0) launch_cg_A(e, it, 4);
-    else if (which == 3) launch_cg_A(e, it, 4 | 16);
-    else if (which == 4) launch_cg_A(e, it, 4 | 32);
-    else launch_cg_B(e, it, 4);
-  };
-  // the launches are captured into one graph so the measurement is not bound by
-  // the host's eager launch rate (~3-4 us per launch)
-  hipGraph_t g = nullptr;
-  hipGraphExec_t ge = nullptr;
-  HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-  for (int i = 0; i < reps; i++) one(i);
-  HIPCHK(hipStreamEndCapture(e->stream, &g));
-  HIPCHK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-  HIPCHK(hipGraphDestroy(g));
-  HIPCHK(hipGraphLaunch(ge, e->stream));            // warm-up replay
-  HIPCHK(hipEventRecord(e->ev0, e->stream));
-  HIPCHK(hipGraphLaunch(ge, e->stream));
-  HIPCHK(hipEventRecord(e->ev1, e->stream));
-  HIPCHK(hipEventSynchronize(e->ev1));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-  HIPCHK(hipGraphExecDestroy(ge));
-  *usec = 1e3 * (double)ms / reps;
-  if (which == 8) {
-    // a resident launch of the timed run may have given up: the number is void then; leave the engine as the run loop would
-    State s;
-    if (read_state(e, &s)) return HIPENG_ERR_HIP;
-    if (s.res_fail) {
-      if (resident_gave_up(e, s, false)) return HIPENG_ERR_HIP;
-      return HIPENG_ERR_HIP;
-    }
-  }
-  return 0;
-}
-
-// For the CPU tests (no device needed): the host side of the resident PCG set-up -- symbolic K, row partition, positions
-// in the exchanged vector, register layout -- for a machine of `nwg` CUs.  stats: [0] the problem qualifies, [1] entries of K
-// per thread, [2] length of the exchanged vector, [3] nnz(K), [4] workgroups that own rows, [5] most rows per workgroup,
-// [6] most entries per workgroup, [7] 448.  Optional outputs (NULL to skip): Kptr (n + 1), Kcol / kdst (cap entries at most:
-// column and register slot of every entry of K, row by row), rowpos (n), slotcol (nwg * E * 448: the position held in every
-// slot), wg4 (4 ints per workgroup: first row, rows, entries, first position).
-extern "C" int hipeng_resident_plan(const csc *P, const csc *A, int nwg, long long stats[8], int *Kptr, int *Kcol, int *kdst, long long cap,
-                                    unsigned short *rowpos, unsigned short *slotcol, int *wg4) {
-  if (!P || !A || !stats || P->n > 0x7ffffff0LL || A->m > 0x7ffffff0LL) return HIPENG_ERR_ARG;
-  hipeng tmp;
-  tmp.n = (int)P->n; tmp.m = (int)A->m;
-  build_A(&tmp, A); build_M(&tmp, P, A); build_dense(&tmp, P);
-  ResPlanOut po;
-  const int rc = build_resident(&tmp, nwg, &po);
-  for (int k = 0; k < 8; k++) stats[k] = 0;
-  if (rc) return rc;
-  stats[0] = po.ok; stats[7] = RES_PT;
-  if (!po.ok) return 0;
-  stats[1] = po.E; stats[2] = po.npad; stats[3] = po.nnzK;
-  for (const ResWG &w : po.wg) { if (w.nr) stats[4]++; stats[5] = std::max<long long>(stats[5], w.nr); stats[6] = std::max<long long>(stats[6], w.cnt); }
-  if (Kptr) std::copy(po.Kptr.begin(), po.Kptr.end(), Kptr);
-  if (po.nnzK <= cap) { if (Kcol) std::copy(po.Kcol.begin(), po.Kcol.end(), Kcol); if (kdst) std::copy(po.kdst.begin(), po.kdst.end(), kdst); }
-  else if (Kcol || kdst) return HIPENG_ERR_ARG;
-  if (rowpos) std::copy(po.rowpos.begin(), po.rowpos.end(), rowpos);
-  if (slotcol) std::copy(po.col.begin(), po.col.end(), slotcol);
-  if (wg4) for (size_t g = 0; g < po.wg.size(); g++) { wg4[4 * g] = po.wg[g].r0; wg4[4 * g + 1] = po.wg[g].nr; wg4[4 * g + 2] = po.wg[g].cnt; wg4[4 * g + 3] = po.wg[g].pos; }
-  return 0;
-}
-
-// The contribution lists of that plan (k_form_K_lists), for the CPU tests: Kcp (nnz(K) + 1 offsets, entries in the order of the
-// plan's Kcol), Kcm / Kca (slot in M of a_ki, slot in the CSR copy of A of a_kj; cap terms at most).  Outputs may be NULL.
-// Returns the number of terms, -1 when the problem does not qualify for the resident PCG, -2 when it does but the lists are
-// switched off or over their budget (OSQP_AMD_FORM_K_LISTS, OSQP_AMD_FORM_K_LIST_MB), or a HIPENG_ERR_* code.
-extern "C" long long hipeng_resident_plan_lists(const csc *P, const csc *A, int nwg, int *Kcp, int *Kcm, int *Kca, long long cap) {
-  if (!P || !A || P->n > 0x7ffffff0LL || A->m > 0x7ffffff0LL) return HIPENG_ERR_ARG;
-  hipeng tmp;
-  tmp.n = (int)P->n; tmp.m = (int)A->m;
-  build_A(&tmp, A); build_M(&tmp, P, A); build_dense(&tmp, P);
-  ResPlanOut po;
-  if (const int rc = build_resident(&tmp, nwg, &po)) return rc;
-  if (!po.ok) return -1;
-  if (!po.lists) return -2;
-  const long long terms = (long long)po.Kcm.size();
-  if (Kcp) std::copy(po.Kcp.begin(), po.Kcp.end(), Kcp);
-  if (terms <= cap) { if (Kcm) std::copy(po.Kcm.begin(), po.Kcm.end(), Kcm); if (Kca) std::copy(po.Kca.begin(), po.Kca.end(), Kca); }
-  else if (Kcm || Kca) return HIPENG_ERR_ARG;
-  return terms;
-}
-
-// The switch table from outside, for the tests and the documentation check (no device, no HIP call).  Row `index` of SW_TABLE: its name,
-// kind (SwKind), default as text ("unset" where unset is distinct: the use site works it out), that bit, and the one-line description;
-// outputs may be NULL.  Returns the number of rows, whatever the index.
-extern "C" int hipeng_switch_row(int index, const char **name, int *kind, char *def_text, int def_cap, int *unset_distinct, const char **what) {
-  if (index < 0 || index >= SW_COUNT) return SW_COUNT;
-  const SwRow &r = SW_TABLE[index];
-  if (name) *name = r.name;
-  if (kind) *kind = r.kind;
-  if (unset_distinct) *unset_distinct = r.unset_distinct;
-  if (what) *what = r.what;
-  if (def_text && def_cap > 0) {
-    if (r.unset_distinct) snprintf(def_text, (size_t)def_cap, "unset");
-    else if (r.kind == SW_TEXT) def_text[0] = 0;
-    else if (r.kind == SW_INT_PAIR) snprintf(def_text, (size_t)def_cap, "%d,%d", (int)r.def, (int)r.def2);
-    else if (r.kind == SW_DOUBLE) snprintf(def_text, (size_t)def_cap, "%g", r.def);
-    else snprintf(def_text, (size_t)def_cap, "%d", (int)r.def);
-  }
-  return SW_COUNT;
-}
-// What read_switches() makes of the current environment: two doubles per row, rows at most of them (out[2 i]: the value -- SW_UNSET where
-// unset is distinct and the variable is not set, the length of a text; out[2 i + 1]: the second number of a pair, else 0).  Returns the number of rows.
-extern "C" int hipeng_switch_values(double *out, int rows) {
-  if (!out) return SW_COUNT;
-  const Switches sw = read_switches();
-  for (int i = 0; i < std::min(rows, SW_COUNT); i++) {
-    const SwRow &r = SW_TABLE[i];
-    const char *at = reinterpret_cast<const char *>(&sw) + r.field;
-    const int *iv = reinterpret_cast<const int *>(at);
-    out[2 * i + 1] = r.kind == SW_INT_PAIR ? (double)iv[1] : 0.0;
-    out[2 * i] = r.kind == SW_TEXT ? (double)strlen(at) : r.kind == SW_DOUBLE ? *reinterpret_cast<const double *>(at) : (double)iv[0];
-  }
-  return SW_COUNT;
-}
-
-#ifdef OSQP_AMD_TIMELINE
-// make TIMELINE=1 builds only: copy out (and reset) the kernel start marks; returns their number
-extern "C" long long hipeng_timeline(hipeng *e, unsigned long long *out, long long cap) {
-  if (!e || !out) return -1;
-  if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return -1;
-  unsigned long long cnt = 0;
-  if (hipMemcpy(&cnt, e->c.tl, sizeof cnt, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  const long long k = (long long)std::min<unsigned long long>(std::min<unsigned long long>(cnt, TL_CAP - 2), (unsigned long long)cap);
-  if (k > 0 && hipMemcpy(out, e->c.tl + 1, (size_t)k * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  if (hipMemset(e->c.tl, 0, sizeof(unsigned long long)) != hipSuccess) return -1;
-  return k;
-}
-#endif
-
-// 1 if the vector update and the operator apply of k_cg_A run as two launches (A dominated by long rows)
-extern "C" int hipeng_is_split(hipeng *e) { return e && e->split ? 1 : 0; }
-// For the tests: how the PCG kernels see (P, A) -- host-side fields only, nothing is launched.  out[0] dense blocks of P,
-// [1] rows inside them, [2] stream blocks of A, [3] long (one-wavefront) rows of A, [4] huge rows of A, [5] huge rows folded
-// into k_cg_B, [6] split, [7] A / [8] M / [9] the matrix k_cg_B streams (Mr when it exists, else M) has 16-bit column ids,
-// [10] long rows of the matrix k_cg_B streams, [11] gridA, [12] gridM; the rest 0.
-extern "C" int hipeng_pcg_layout(hipeng *e, long long out[16]) {
-  if (!e || !out) return HIPENG_ERR_ARG;
-  for (int k = 0; k < 16; k++) out[k] = 0;
-  const HostMat &B = (!e->dP_blks.empty() || !e->hrows.empty()) ? e->Mr : e->M;
-  out[0] = (long long)e->dP_blks.size();
-  for (const DenseBlk &d : e->dP_blks) out[1] += d.b;
-  out[2] = e->A.nstream; out[3] = e->A.nwave - e->A.nstream; out[4] = (long long)e->A.blk.size() - e->A.nwave;
-  out[5] = (long long)e->hrows.size(); out[6] = e->split ? 1 : 0;
-  out[7] = e->A.d_col16 != nullptr; out[8] = e->M.d_col16 != nullptr; out[9] = B.d_col16 != nullptr;
-  out[10] = B.nwave - B.nstream; out[11] = e->c.gridA; out[12] = e->c.gridM;
-  return 0;
-}
-extern "C" int hipeng_row_eliminated(hipeng *e, c_int i) { return e && !e->ecol.empty() && i >= 0 && i < (c_int)e->ecol.size() && e->ecol[(size_t)i] >= 0 ? 1 : 0; }
-extern "C" c_int hipeng_elim_count(hipeng *e) { return e ? e->c.nelim : 0; }
-// ---- for the tests: one of the per-row arrays of the elimination on the host (reads only) ----
-extern "C" int hipeng_elim_peek(hipeng *e, int which, c_float *out) {
-  if (!e || !out || which < 0 || which > 3 || !e->c.nelim) return HIPENG_ERR_ARG;
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  const double *src[] = {e->c.rhoe, e->c.ecoef, e->c.edinv, e->c.xte};
-  HIPCHK(hipMemcpy(out, src[which], (size_t)e->m * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// Resident PCG: out[0] structures built, [1] in use, [2] entries of K per thread, [3] workgroups, [4] nnz(K),
-// [5] LDS bytes per workgroup, [6] PCG iterations of the most recent linear solve, [7] pipelined phase switched off for this K,
-// [8] true-residual checks that failed since create, [9] form: 1 k_pcg_resident, 2 k_pcg_blockres,
-// [10] launches that gave up waiting (the third one ends the mode for this engine)
-extern "C" int hipeng_resident_info(hipeng *e, long long out[16]) {
-  if (!e || !out) return HIPENG_ERR_ARG;
-  HIPCHK(hipSetDevice(e->device));
-  State s;
-  if (read_state(e, &s)) return HIPENG_ERR_HIP;
-  out[0] = e->form != FORM_STEPS; out[1] = e->resident_available(); out[2] = e->rc.E; out[3] = e->rc.nwg; out[4] = e->res_nnz; out[5] = (long long)e->res_lds;
-  out[6] = std::max(s.iters[0], s.iters[1]); out[7] = s.res_pipe_off; out[8] = s.res_chk_fail; out[9] = e->form; out[10] = e->res_gave_up; out[11] = e->res_slow + s.res_slow;
-  out[12] = std::max<long long>(e->res_slow_max, s.res_slow_max); out[13] = e->res_repub + s.res_repub; out[14] = e->res_fails; out[15] = 0;
-  if (e->form == FORM_BLOCKRES) { out[2] = 64; out[3] = e->bc.nwg; out[4] = 0; out[5] = 0; }
-  if (e->form == FORM_BLOCK_DIRECT) { out[2] = 0; out[3] = e->c.dP.nblk; out[4] = 0; out[5] = 0; out[15] = e->bd.kc; }
-  if (e->form == FORM_DENSE_DIRECT) { out[2] = 0; out[3] = e->dd.na; out[4] = (long long)e->dd.nap * e->dd.nap; out[5] = e->dd_chol ? 1 : 0; out[15] = e->dd.nb2; }
-  return 0;
-}
-
-// How the resident PCG forms K: out[0] 1 k_form_K_lists (contribution lists built at set-up), 0 k_form_K; [1] terms of the
-// lists (sum over the rows of A of nnz^2, whether or not they were built), [2] bytes of the list arrays on the device (0: none),
-// [3] their budget in bytes (OSQP_AMD_FORM_K_LIST_MB).  All 0 for an engine on another form.
-extern "C" int hipeng_form_k_info(hipeng *e, long long out[4]) {
-  if (!e || !out) return HIPENG_ERR_ARG;
-  const bool res = e->form == FORM_RESIDENT;
-  out[0] = res && e->fk_lists; out[1] = res ? e->fk_terms : 0; out[2] = res ? e->fk_bytes : 0; out[3] = res ? e->fk_budget : 0;
-  return 0;
-}
-
-// k_pcg_resident since create: out[0] vector trips of its launches (start-up product, iterations, predicted / wasted trip, check),
-// [1] launches that ran a solve, [2] predicted last trips whose products served the true-residual check, [3] predicted last trips
-// that were not the last, [4] predicted trips switched off for the current K, [5] the switch (OSQP_AMD_RESIDENT_PREDICT), [6] solves /
-// [7] misses minus hits of the current window of RES_PRED_WINDOW solves.
-extern "C" int hipeng_resident_trips(hipeng *e, long long out[8]) {
-  if (!e || !out) return HIPENG_ERR_ARG;
-  HIPCHK(hipSetDevice(e->device));
-  State s;
-  if (read_state(e, &s)) return HIPENG_ERR_HIP;
-  out[0] = s.res_trips; out[1] = s.res_solves; out[2] = s.res_pred_hit; out[3] = s.res_pred_miss;
-  out[4] = s.res_pred_off; out[5] = e->form == FORM_RESIDENT ? e->rc.predict : 0; out[6] = s.res_pred_win[0]; out[7] = s.res_pred_win[2] - s.res_pred_win[1];
-  return 0;
-}
-
-// Resident PCG, for the tests: what the start-up of the last launch summed.  Returns gridM (or a negative code); part_bb receives
-// min(gridM, cap) partials of ||b||^2 as the last k_pcg_init left them, *tol2 State::tol2 as the last launch stored it.
-extern "C" long long hipeng_resident_start_peek(hipeng *e, double *part_bb, long long cap, double *tol2) {
-  if (!e || e->form != FORM_RESIDENT || !part_bb || !tol2 || cap < 0) return HIPENG_ERR_ARG;
-  if (hipSetDevice(e->device) != hipSuccess) return HIPENG_ERR_HIP;
-  State s;
-  if (read_state(e, &s)) return HIPENG_ERR_HIP;       // (synchronises the stream)
-  const long long cnt = std::min<long long>(e->c.gridM, cap);
-  if (cnt > 0 && hipMemcpy(part_bb, e->c.part_bb, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return HIPENG_ERR_HIP;
-  *tol2 = s.tol2;
-  return e->c.gridM;
-}
-
-// Resident PCG, for the tests: the rows of K as the resident kernel holds them.  row/col/val receive nnz(K) triplets
-// (row by row, columns ascending; values read from the slots the threads load them from); returns the count or a negative code.
-extern "C" long long hipeng_resident_dump(hipeng *e, int *row, int *col, double *val, long long cap) {
-  if (!e || e->form != FORM_RESIDENT || !row || !col || !val) return HIPENG_ERR_ARG;
-  if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return HIPENG_ERR_HIP;
-  const ResCtx &rc = e->rc;
-  const size_t slots = (size_t)rc.nwg * rc.E * RES_PT;
-  const long long nnz = e->res_nnz;
-  if (nnz > cap) return HIPENG_ERR_ARG;
-  std::vector<double> v(slots); std::vector<int> krp(e->n + 1), kcj((size_t)nnz), kdst((size_t)nnz);
-  if (hipMemcpy(v.data(), rc.val, slots * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(krp.data(), rc.krp, krp.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(kcj.data(), rc.kcj, kcj.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(kdst.data(), rc.kdst, kdst.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return HIPENG_ERR_HIP;
-  long long k = 0;
-  for (int i = 0; i < e->n; i++)
-    for (int q = krp[i]; q < krp[i + 1]; q++) { row[k] = i; col[k] = kcj[q]; val[k] = v[kdst[q]]; k++; }
-  return k;
-}
-
-extern "C" int hipeng_kernel_bytes(hipeng *e, int which, double *bytes) {
-  if (!e || !bytes) return HIPENG_ERR_ARG;
-  const double n = e->n, m = e->m;
-  const double nnzA = (double)e->A.val.size();
-  const double nnzPtriu = (double)e->P_toM_up.size();
-  // device layout: fp64 values + int32 indices (12 B per stored entry), one
-  // int32 row pointer per row, fp64 vectors; gathers counted once per vector
-  // k_cg_A: A stream; u,w,p,s,r,Minv,x read + p,s,r,x,u written (12n); rho read, t written (2m)
-  if (which == 0)      *bytes = nnzA * 12 + (m + 1) * 4 + 8 * (12 * n + 2 * m);
-  // k_cg_B: [P|A'] stream; [u|t] and r read, w written.  P is counted as its stored upper
-  // triangle (each stored entry serves both triangles) although the fused row
-  // matrix M holds both, so the figure does not reward the expanded layout.
-  else if (which == 1) *bytes = (nnzA + nnzPtriu) * 12 + (n + 1) * 4 + 8 * ((n + m) + 2 * n);
-  else                 *bytes = 0;
-  return 0;
-}
+#include "engine_hooks.h"
 
 // ---- ONE QP over several GPUs by rows, driven from C (include/osqp_amd_rowpart.h) ----
 #include "kkt_sens.h"

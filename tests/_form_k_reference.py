@@ -1,4 +1,4 @@
-"""Host replay of the values of the resident K (engine.hip: k_form_K, k_form_K_lists), independent of both kernels and of the
+"""Host replay of the values of the resident K (engine_pcg_resident.h: k_form_K, k_form_K_lists), independent of both kernels and of the
 contribution lists.  The library is built with -ffp-contract=off and both kernels document one association and one order,
 
     v = (P_ij or 0) + (sigma if i == j else 0);   for the rows k of A holding both i and j, k ascending:  v = v + rho_k * (a_ki * a_kj)

@@ -1,4 +1,4 @@
-"""The start-up sum of k_pcg_resident (engine.hip), restated in numpy float64 for the tests.
+"""The start-up sum of k_pcg_resident (engine_pcg_resident.h), restated in numpy float64 for the tests.
 
 k_pcg_init leaves one partial of ||b||^2 per workgroup (gridM of them, at most 1024).  Wavefront 0 of every workgroup of the resident
 launch sums them: lane l adds the partials l, l + 64, l + 128, ... in ascending order, starting from 0.0; the 64 lane sums go through

@@ -301,7 +301,7 @@ def test_every_environment_variable_is_documented():
     from tests.test_engine_switches_host import table
     names = {row[0] for row in table()}
     assert len(names) == 39
-    for pat in ("osqp_amd/csrc/*.c", "osqp_amd/csrc/*.hip", "osqp_amd/*.py"):
+    for pat in ("osqp_amd/csrc/*.c", "osqp_amd/csrc/*.hip", "osqp_amd/csrc/*.h", "osqp_amd/*.py"):
         for f in glob.glob(os.path.join(ROOT, pat)):
             txt = open(f, errors="ignore").read()
             names |= set(re.findall(r'getenv\("(OSQP_AMD_[A-Z0-9_]+)"\)', txt))

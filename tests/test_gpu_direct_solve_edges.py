@@ -1,7 +1,7 @@
 """GPU tests of the two direct linear-solve forms one KKT solve at a time, at their structural edges.
 
 Dense-direct (res_kind 4, csrc/dense_direct.h, dense_direct_host.h) and block-direct (res_kind 3, k_blk_* / k_cap_* /
-k_blk_apply_multi in engine.hip) are driven through the C shim: hipeng_create with no q, l, u, hipeng_kkt_solve, and the
+k_blk_apply_multi in engine_block_direct.h) are driven through the C shim: hipeng_create with no q, l, u, hipeng_kkt_solve, and the
 three calls that form the inverse again (hipeng_upload_rho, hipeng_upload_matrices, hipeng_set_params with a new sigma).
 Every case first asserts which form and which route inside it served the solve (hipeng_resident_info: [9] form, [3] dense
 unknowns or blocks, [5] Cholesky route, [15] coupling rows kc or sparse-Schur variables nb2), then measures [x~; z~]

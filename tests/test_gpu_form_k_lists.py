@@ -1,4 +1,4 @@
-"""k_form_K_lists (engine.hip): the values of the resident K summed from the contribution lists of the set-up, against k_form_K
+"""k_form_K_lists (engine_pcg_resident.h): the values of the resident K summed from the contribution lists of the set-up, against k_form_K
 (OSQP_AMD_FORM_K_LISTS=0), which merges the patterns on the device each time.  Same operands, same association, same order of
 the terms: the two must agree to the bit (hipeng_resident_dump), whatever rho, sigma and the matrices' values are, with
 eliminated variables, at the turns of either kernel's loops.  Then whole solves: lists against no lists (same bits), against the

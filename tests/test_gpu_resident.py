@@ -1,4 +1,4 @@
-"""Resident PCG (engine.hip: k_form_K, k_pcg_resident): the reduced matrix K = P + sigma I + A' diag(rho) A held in
+"""Resident PCG (engine_pcg_resident.h: k_form_K, k_pcg_resident): the reduced matrix K = P + sigma I + A' diag(rho) A held in
 registers and the whole linear solve of an ADMM iteration in one launch.  Checks: K itself against scipy, the three
 modes of the kernel (pipelined, pipelined handed over after a failed true-residual check, Chronopoulos-Gear only)
 against the oracle through the C ABI, problems far below the size the mode is meant for, and two processes sharing

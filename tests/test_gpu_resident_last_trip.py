@@ -1,4 +1,4 @@
-"""GPU tests of the predicted last trip of k_pcg_resident (engine.hip) and of the row state overlaid on the registers of K.
+"""GPU tests of the predicted last trip of k_pcg_resident (engine_pcg_resident.h) and of the row state overlaid on the registers of K.
 
 A pipelined solve of N PCG iterations makes N + 3 vector trips: the start-up product, N iterations, one trip whose exchange only
 delivers the ||r||^2 that says "converged", and the true-residual check.  When wavefront 0 predicts that the coming trip is that
@@ -43,8 +43,8 @@ from tests._hipeng import Engine
 pytestmark = pytest.mark.gpu
 
 ALPHA = 1.6
-WINDOW = 16                                   # RES_PRED_WINDOW of engine.hip
-CAP = 64                                      # iterations after which a solve leaves the pipelined phase (engine.hip, k_pcg_resident)
+WINDOW = 16                                   # RES_PRED_WINDOW of engine_pcg_resident.h
+CAP = 64                                      # iterations after which a solve leaves the pipelined phase (engine_pcg_resident.h, k_pcg_resident)
 STEPS = 24                                    # consecutive ADMM iterations of the res_e<E> cases
 SETTINGS = {"default": {}, "predict0": dict(OSQP_AMD_RESIDENT_PREDICT=0), "margin1e30": dict(OSQP_AMD_RESIDENT_PREDICT_MARGIN="1e30"),
             "pipe0": dict(OSQP_AMD_RESIDENT_PIPE=0)}
@@ -159,7 +159,7 @@ def _base_trips(n):
 def _check_margin_1e30(tag, rows):
     """rows of (N, trips, hits, misses, off) per solve at margin 1e30: the rule fires after the second iteration -- a miss when
     N > 2 (one trip more), a hit when N == 2 (trip 3 is the one that learns "converged"), nothing when N < 2; the window of
-    WINDOW solves is judged as engine.hip's RES_PRED_WINDOW says."""
+    WINDOW solves is judged as engine_pcg_resident.h's RES_PRED_WINDOW says."""
     ws = wh = wm = 0
     is_off = False
     for k, (n, t, h, m, off) in enumerate(rows):
@@ -194,7 +194,7 @@ def test_trip_counts(E):
         fired.append(h)
     print(f"[last-trip] res_e{E}: default margin, hit (N + 2 trips) per solve {fired}: fired and hit in {sum(fired)} of {len(inside)} solves with 2 < N < 64")
     # margin 1e30: fires after the second iteration: a miss when N > 2 (N + 4, or N + 5 past the cap), a hit when N == 2; the window
-    # of WINDOW solves is judged as engine.hip's RES_PRED_WINDOW says
+    # of WINDOW solves is judged as engine_pcg_resident.h's RES_PRED_WINDOW says
     _check_margin_1e30(f"res_e{E}", rows["margin1e30"])
     for k, (n, t, h, m, off) in enumerate(rows["pipe0"]):
         assert (h, m) == (0, 0), (E, "PIPE=0", k, h, m)

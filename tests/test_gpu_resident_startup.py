@@ -1,4 +1,4 @@
-"""GPU tests of the start-up of k_pcg_resident (engine.hip): the entry, the start-up sums of wavefront 0, u0 taken in before the loop.
+"""GPU tests of the start-up of k_pcg_resident (engine_pcg_resident.h): the entry, the start-up sums of wavefront 0, u0 taken in before the loop.
 
 Wavefront 0 alone sums k_pcg_init's partials of ||r0||^2 and ||b||^2 (every load in flight at once, added in the order the sum has
 always had) and hands tol2 and the verdict "the start vector already passes" to the other seven through LDS; all eight leave
