@@ -162,7 +162,7 @@ int hipeng_is_split(hipeng *e);   /* k_cg_A as two launches (update-only + apply
  * (the remainder Mr when it exists, else M) has them, [10] long rows of that matrix, [11] gridA, [12] gridM; the rest 0. */
 int hipeng_pcg_layout(hipeng *e, long long out[16]);
 /* Slack-like variables (one entry in their column of A, no coupling in P) are eliminated from the linear system exactly
- * (engine.hip, k_elim_refresh; launch-per-step engines).  hipeng_row_eliminated: does row i of A carry such a variable?
+ * (engine_aux_kernels.h, k_elim_refresh; launch-per-step engines).  hipeng_row_eliminated: does row i of A carry such a variable?
  * hipeng_elim_count: how many variables are eliminated. */
 int hipeng_row_eliminated(hipeng *e, c_int i);
 c_int hipeng_elim_count(hipeng *e);

@@ -6,7 +6,7 @@
  * include/lin_alg.h and the KKT assembly of include/kkt.h.  libosqp_amd.so exports them with the
  * reference's names and signatures so that such translation units link against it unchanged
  * (SURVEY.md section 8(b)).  They are plain host C on host arrays -- set-up and test utilities,
- * not part of the device hot path (whose SpMV / reductions live in engine.hip).
+ * not part of the device hot path (whose SpMV / reductions live in csrc/engine_device.h).
  *
  * Each prototype cites the reference declaration it matches (paths relative to /root/reference).
  */

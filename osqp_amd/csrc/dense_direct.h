@@ -1,5 +1,5 @@
 // dense_direct.h -- included by engine.hip after engine_block_direct.h and before engine_block_check.h (it uses Ctx, State and the
-// dense_block_mv helpers of engine.hip and INV_TB of engine_block_direct.h; k_blk_check / k_cap_check use its dd_probe_value).
+// dense_block_mv helpers of engine_device.h and INV_TB of engine_block_direct.h; k_blk_check / k_cap_check use its dd_probe_value).
 //
 // Dense-direct solve (FORM_DENSE_DIRECT): problems whose reduced matrix K = P + sigma I + A' rho~ A is SMALL AND DENSE -- BASELINE
 // config 3, the Lasso QP: 5 000 feature variables tied together by 10 000 data rows of 750 entries.  There the PCG streams the

@@ -29,23 +29,33 @@
 // kernel, so results are bitwise reproducible and PCG scalars never visit the
 // host.
 //
-// What stays in this file: the shared descriptors and device building blocks, the launch-per-step PCG with k_pcg_init and
-// k_admm_finalize, the kernels that belong to no single form, and the host side.  The device code of the one-launch forms and
-// the test hooks stand in fragments, each included exactly once at the place where its text belongs.  They are pieces of this
-// file, not headers that compile alone; each opens with what it holds and what must stand before it.  In include order:
+// What stays in this file: the host side.  All device code, the dense-direct form's host side and the test hooks stand in
+// fragments, each included exactly once at the place where its text belongs.  They are pieces of this file, not headers that
+// compile alone; each opens with where it is included, what it holds and what must stand before it.  In include order:
+//  device, ahead of the host side
+//   engine_device.h         constants, HIPCHK, RowBlk / G4 / DevMat / DenseP / State / Params / Ctx, timeline macros, scalar slots,
+//                           reductions, the stream / long-row / dense-block SpMV pieces, LDS_DECL
+//   engine_pcg_steps.h      launch-per-step PCG: k_vd, k_pcg_init, cg_step, k_cg_A, k_huge_reduce, k_cg_B, k_huge_dot, k_admm_finalize
 //   engine_pcg_resident.h   resident PCG: ResCtx, the bounded waits, k_form_K, k_form_K_lists, k_pcg_resident
 //   engine_pcg_blockres.h   block-resident PCG: BrCtx, k_pcg_blockres
 //   engine_block_direct.h   block-direct solve: BdCtx, k_blk_*, k_cpl_*, k_cap_diag, k_cap_step
 //   dense_direct.h          dense-direct solve: DdCtx, k_dd_*
 //   engine_block_check.h    block-direct solve: k_blk_check, k_cap_check (they use dense_direct.h's probe vector)
+//   engine_aux_kernels.h    k_elim_refresh, k_elim_split, k_precond, k_refresh_m, k_spmv
+//   engine_check_kernels.h  k_residuals, k_final_sums, k_certificates
+//   engine_ruiz_kernels.h   Ruiz equilibration: k_ruiz_*
+//   engine_util_kernels.h   k_fill, k_fill_ranges, k_start_reset, k_window_begin, k_repack
+//  inside and behind the host side
 //   dense_direct_host.h     build_dense_direct, dd_refresh, launch_dense_direct, the dense-direct test hooks
 //   engine_hooks.h          entry points for tests and measurements
 //   kkt_sens.h              derivatives of the solution (k_sens_*)
 //   verify.h                a point against the raw problem (k_ver_*)
 //   rowpart_native.h        one QP over several GPUs by rows (k_rp_*)
 // The order is pinned: the kernels, and the instantiations of the kernel templates, stand in the code object in the order of
-// the text, the hand-tuned kernels are sensitive to their place there, and the check of a change that only moves text is that
-// the device assembly of this translation unit stays what it was.  A new fragment goes where its text would have gone.
+// the text (host text included: a host launch instantiates its kernel template), the hand-tuned kernels are sensitive to their
+// place there, and the check of a change that only moves text is that the device assembly of this translation unit stays what it
+// was.  A new fragment goes where its text would have gone.  Macros cross the seams (HIPCHK, TB and the other constants, TL_MARK /
+// TLK_*, LDS_DECL): the header of a fragment that uses one names the fragment that defines it.
 
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -66,1635 +76,18 @@
 #include <chrono>
 #include "../../include/osqp_amd_engine.h"
 
-#define TB 256            // threads per workgroup (4 wavefronts of 64)
-#define MAX_CHUNK 2048    // products staged in LDS per workgroup (x2 for dual stream)
-#define LONG_ROW 512      // a row with at least this many entries gets a workgroup of its own (no LDS staging)
-#define HUGE_ROW 8192     // A rows this long are sliced over the whole grid in k_cg_A (partials finished by k_huge_reduce)
-#define MAX_PARTS 1024    // upper bound on workgroups that emit dot partials
-#define MAX_HUGE_FOLD 4   // up to this many huge rows are folded into k_cg_B (more: k_huge_reduce finishes them)
-#define INF_BOUND 1e26    // OSQP_INFTY * MIN_SCALING
-
-#define HIPCHK(call)                                                            \
-  do {                                                                          \
-    hipError_t _e = (call);                                                     \
-    if (_e != hipSuccess) {                                                     \
-      fprintf(stderr, "osqp_amd: HIP error %s at %s:%d (%s)\n",                 \
-              hipGetErrorString(_e), __FILE__, __LINE__, #call);                \
-      return HIPENG_ERR_HIP;                                                    \
-    }                                                                           \
-  } while (0)
-
-// ---------------------------------------------------------------------------
-// device-side descriptors
-// ---------------------------------------------------------------------------
-struct RowBlk { int r0, r1, k0, k1; };
-#define IS_LONG(b) ((b).r1 - (b).r0 == 1 && (b).k1 - (b).k0 >= LONG_ROW)
-// per-column record gathered by k_cg_A: one 32-byte access instead of four 8-byte
-// gathers from four arrays (residual, w = K u, s = K p, Jacobi inverse)
-struct __attribute__((aligned(32))) G4 { double r, w, s, m; };
-
-struct DevMat {
-  int nrows, nblk;
-  int nstream;           // blocks [0,nstream) are multi-row stream blocks, [nstream,nblk) single long rows
-  int nwave;             // PCG kernels: long rows [nstream,nwave) take one wavefront each, [nwave,nblk) are huge
-  const int    *rowptr;
-  const int    *col;
-  const unsigned short *col16;   // the same column ids as 16-bit words where every id fits (null otherwise): the long-row passes
-                                 // stream 10 instead of 12 bytes per entry (config 3: 26 -> 22 us per pass over A)
-  const double *val;
-  const int    *split;   // M only: first entry of the A' part of each row
-  const RowBlk *blk;
-};
-
-// Dense diagonal blocks of P (portfolio-style block-diagonal covariance): such a block is
-// kept as a plain dense b x b array (8 B per entry, no index) for the PCG operator kernel;
-// everything else of its rows (the A' part) stays in the sparse remainder matrix.
-#define DENSE_MAX 128          // lanes cover the block's columns in two 64-lane halves
-struct DenseBlk { int c0, b, off, pitch; };   // first row/column, size, offset into val, row pitch in doubles (even, zero padded)
-struct DenseP {
-  int nblk;                  // dense blocks (0: feature off)
-  const DenseBlk *blk;
-  const double *val;         // blocks back to back, each b rows of `pitch` doubles (zero padded; row-major = column-major: symmetric)
-};
-
-// Written by kernels only; read by the host between windows.
-struct State {
-  int    run;          // this ADMM iteration is active (written by the first kernel)
-  int    done;         // PCG converged (written by k_cg_A)
-  int    stalled;      // PCG ran out of unrolled iterations (written by finalize)
-  int    neg_curv;     // p'Kp <= 0 seen
-  int    iters[2];     // PCG iterations of the current solve (ping-pong on parity)
-  int    neg_curv_seen;
-  int    iters_last;
-  int    iters_max;
-  int    iters_min;        // smallest PCG iteration count of a solve since the host last reset it
-  int    forced;
-  long long iters_total;
-  long long admm_done;
-  double rz[2];
-  double tol2;
-  double gam[2], alp[2];   // Chronopoulos-Gear scalars (ping-pong on parity)
-  int    hist_r;           // ADMM iterations since the PCG start vector history was reset (k_pcg_init counts)
-  long long admm_target;   // k_pcg_init starts no new ADMM iteration once admm_done has reached this
-  unsigned res_epoch;      // resident PCG: tag of the last exchange of the previous launch
-  int    res_fail;         // resident PCG: a wait timed out (workgroups not co-resident); the host falls back to the launch-per-step path
-  int    res_pipe_off;     // resident PCG: the pipelined recurrences failed a true-residual check for this K (k_form_K clears it)
-  int    res_chk_fail;     // resident PCG: true-residual checks that failed since create (each continued the solve from the true residual)
-  int    res_dbg[4];       // resident PCG, first timed-out wait: 1 = flags / 2 = granules, exchange number, waiting workgroup, first missing workgroup
-  int    res_slow;         // resident PCG: waits that ended well but took more than 50 us (the host adds them up: hipeng_resident_info)
-  int    res_slow_max;     // ... the longest of them, in ticks of the 100 MHz clock
-  int    res_repub;        // ... flags / granules that a workgroup stored again because its own wait went on (every 64th round)
-  int    res_slow_hist[4]; // ... slow waits by length: 50-200 us, 200-500 us, 0.5-2 ms, longer
-  unsigned res_slow_xcc;   // ... bit k: a wavefront on XCC k had one
-  int    res_slow_last[4]; // ... the latest: exchange number, workgroup, first workgroup it had missed at its 16th round, wait kind (1 flags, 2 granules)
-  // k_pcg_resident, since create (hipeng_resident_trips): vector trips of its launches, launches that ran a solve, predicted last
-  // trips whose products served the true-residual check (hits), predicted last trips that were not the last (misses)
-  long long res_trips, res_solves, res_pred_hit, res_pred_miss;
-  int    res_pred_win[3];  // the current window of RES_PRED_WINDOW solves on this K: solves, hits, misses
-  int    res_pred_off;     // misses outnumbered hits over a window: no predicted trips until K changes (k_form_K clears it)
-};
-
-struct Params {          // mutable scalars (host writes, kernels read)
-  double sigma, alpha, eps_rel, eps_abs, cinv;
-  int    pcg_max_iter, use_cvec, has_scaling, pad0;
-  double ex_theta;         // extrapolation of the PCG start vector (0 = plain warm start)
-  int    ex_h0, ex_h1;     // no extrapolation before iteration ex_h0 after a reset, half a step before ex_h1
-  int    no_restart;       // setup-time convexity probe: any loss of positivity counts as negative curvature
-};
-
-struct Ctx {             // static pointers / sizes, passed by value
-  int n, m;
-  DevMat A, M;
-  DevMat Mk;             // what k_cg_B streams: M itself, or its remainder when P has dense blocks
-  DenseP dP;
-  int nh, hrow[MAX_HUGE_FOLD];     // huge rows of A folded into k_cg_B, and hcol: nh dense vectors hcol_k[j] = A(h_k, j)
-  const double *hcol;
-  int gridA, gridM;      // launch grids (>=1) of row kernels over A / over M
-  double *xy, *z, *zt, *va, *vb, *q, *l, *u, *rho, *rhoinv, *minv, *pdiag;
-  double *r, *zz, *kp, *pt0, *pt1, *dxy, *dy, *cvec;
-  double *init_r, *init_z;        // where k_pcg_init puts r0 and Minv r0
-  double *vx, *vold;               // PCG start vector [x~0 | rho z~0] (extrapolated) and the previous [x~ | rho z~]
-  double *pdir, *ut;               // Chronopoulos-Gear PCG: p, [u|t]
-  G4     *g4;                      // ... and {r, w, s, Minv} records, ping-ponged on parity (2n)
-  int     init_stride;             // element stride of init_r (4 when it points into g4)
-  int     fin_wave_rows;           // k_admm_finalize: one wavefront per long row of A (dense-direct engines)
-  double *vd;                      // dense-direct engines: vb - vx over all n + m entries (k_vd, before k_pcg_init): the long rows of k_pcg_init then
-                                   // gather ONE vector per entry -- they need the residual b - K x~0 only, not b itself
-  int     plain_rhs;               // block-direct engines: k_pcg_init leaves b0 = b - S' beta (the right-hand side without the low-rank rows' terms) instead of
-  const int *plain_skip;           // the residual b - K x~0: no pass over P.  plain_skip[i] >= 0: row i of A is a coupling row (null: only the folded huge rows are)
-  // resident PCG: k_pcg_init also leaves u0 = Minv r0 in the layout of the exchanged vector (position u0map[j] of u0pos), so that
-  // the resident launch takes it in with one coalesced sweep instead of a 2-byte-indexed gather (null: not a k_pcg_resident engine)
-  const unsigned short *u0map;
-  double *u0pos;
-  // Slack-like variables eliminated from the linear system (k_elim_refresh): nelim = 0 switches all of it off (rhoe == rho then)
-  int     nelim;
-  const int *erow, *ecol, *epos;   // [n] row of an eliminated variable (-1: not eliminated); [m] the row's eliminated variable (-1: none), slot of that entry in A.val
-  double *rhoe, *ecoef, *edinv, *xte;   // [m] effective rho of the row, A(i, ecol[i]), 1 / D_y, x~ of the row's eliminated variable
-  double *D, *Dinv, *E, *Einv;
-  double *part_rz, *part_rr, *part_bb, *part_pkp, *part_s0, *part_s1, *part_s2, *part_gam, *part_del;
-  const double *fin_rr;  // where k_admm_finalize finds the partials of the last ||r||^2, and how many
-  int fin_cnt;
-  double *scal;          // reduction outputs (see SC_* below)
-  double *part_h;        // huge A rows: [row][workgroup of k_cg_A] partial dots
-  State  *st;
-  const Params *prm;
-#ifdef OSQP_AMD_TIMELINE
-  unsigned long long *tl;  // make TIMELINE=1: [0] = count, then one word per kernel start: id << 56 | wall_clock64 (100 MHz)
-#endif
-};
-
-#ifdef OSQP_AMD_TIMELINE
-#define TL_CAP (1 << 20)
-#define TL_MARK(c, id) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long k_ = atomicAdd((c).tl, 1ull); \
-    if (k_ < TL_CAP - 2) (c).tl[1 + k_] = ((unsigned long long)(id) << 56) | (wall_clock64() & 0x00FFFFFFFFFFFFFFull); } } while (0)
-// Stamps inside k_pcg_init / k_admm_finalize (workgroup 0, thread 0): TLK_AT(k, v) reads the clock once v -- the last value a
-// flight of loads brings -- is in its register; the kernel's end writes them out as ids base + k (tools/loop_probe.py,
-// profiles/iter_kernels_chain_timeline.txt).
-// TLK_LAST(k): entry (0) and end (1, after its stores are acknowledged) of the LAST workgroup of the grid, ids base + 20 + k.
-#define TLK_N 10
-#define TLK_DECL long long tlk_[TLK_N], tll_[2] = {0, 0}; for (int q_ = 0; q_ < TLK_N; ++q_) tlk_[q_] = 0
-#define TLK_LAST(k) do { if (k) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) tll_[k] = wall_clock64(); } while (0)
-#define TLK_AT(k, v) do { asm volatile("" :: "v"(v)); if (blockIdx.x == 0 && threadIdx.x == 0) tlk_[k] = wall_clock64(); } while (0)
-#define TLK_FLUSH(c, base, n) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long k_ = atomicAdd((c).tl, (unsigned long long)(n)); \
-    if (k_ + (n) < TL_CAP - 2) for (int q_ = 0; q_ < (n); ++q_) (c).tl[1 + k_ + q_] = ((unsigned long long)((base) + q_) << 56) | ((unsigned long long)tlk_[q_] & 0x00FFFFFFFFFFFFFFull); } \
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) { const unsigned long long k_ = atomicAdd((c).tl, 2ull); \
-    if (k_ + 2 < TL_CAP - 2) for (int q_ = 0; q_ < 2; ++q_) (c).tl[1 + k_ + q_] = ((unsigned long long)((base) + 20 + q_) << 56) | ((unsigned long long)tll_[q_] & 0x00FFFFFFFFFFFFFFull); } } while (0)
-#else
-#define TL_MARK(c, id) do { } while (0)
-#define TLK_DECL do { } while (0)
-#define TLK_AT(k, v) do { } while (0)
-#define TLK_LAST(k) do { } while (0)
-#define TLK_FLUSH(c, base, n) do { } while (0)
-#endif
-
-enum {  // slots of Ctx::scal (max slots are bit patterns of non-negative doubles)
-  SC_PRI_U, SC_PRI_S, SC_Z_U, SC_Z_S, SC_AX_U, SC_AX_S,
-  SC_DUA_U, SC_DUA_S, SC_Q_U, SC_Q_S, SC_ATY_U, SC_ATY_S, SC_PX_U, SC_PX_S,
-  SC_DYN_U, SC_DYN_S, SC_DXN_U, SC_DXN_S,
-  SC_ATDY_U, SC_ATDY_S, SC_PDX_U, SC_PDX_S, SC_ADX_VIOL,
-  SC_OBJ, SC_DYLHS, SC_QDX,
-  SC_COUNT
-};
-#define SCI(x) ((x) * 16)   // one 128-byte line per slot: atomics on different slots do not serialise
-
-// ---------------------------------------------------------------------------
-// wavefront / workgroup reductions (wave = 64 lanes on gfx950)
-// ---------------------------------------------------------------------------
-// Sum over the 64 lanes, result in every lane.  Four DPP exchanges inside the 16-lane rows
-// (quad xor 1, quad xor 2, half-row mirror, row mirror: no LDS traffic, unlike ds_bpermute
-// shuffles), then the four row totals are read out by lane and added in a fixed order.
-template <int CTRL>
-__device__ __forceinline__ double dpp_move(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true); hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double lane_value(double v, int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-__device__ __forceinline__ double wave_sum(double v) {
-  v += dpp_move<0xB1>(v); v += dpp_move<0x4E>(v); v += dpp_move<0x141>(v); v += dpp_move<0x140>(v);
-  return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
-}
-
-// Sum over the workgroup, result broadcast to every thread.  `red` holds >= 5
-// doubles of LDS.  Fixed tree => deterministic.
-__device__ __forceinline__ double block_sum(double v, double *red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) red[4] = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return red[4];
-}
-
-// Three sums in one pass (one barrier pair instead of three); results broadcast.
-// `red` holds >= 16 doubles.
-__device__ __forceinline__ void block_sum3(double &a, double &b, double &c, double *red) {
-  a = wave_sum(a); b = wave_sum(b); c = wave_sum(c);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) { red[w] = a; red[4 + w] = b; red[8 + w] = c; }
-  __syncthreads();
-  a = (red[0] + red[1]) + (red[2] + red[3]);
-  b = (red[4] + red[5]) + (red[6] + red[7]);
-  c = (red[8] + red[9]) + (red[10] + red[11]);
-}
-
-// Re-reduce up to three arrays of per-workgroup partials (same length).
-template <int NA>
-__device__ __forceinline__ void reduce_parts(const double *a0, const double *a1,
-                                             const double *a2, int count,
-                                             double *red, double out[NA]) {
-  double s0 = 0, s1 = 0, s2 = 0;
-  for (int i = threadIdx.x; i < count; i += TB) {
-    s0 += a0[i];
-    if (NA > 1) s1 += a1[i];
-    if (NA > 2) s2 += a2[i];
-  }
-  if (NA == 1) { out[0] = block_sum(s0, red); return; }
-  block_sum3(s0, s1, s2, red);
-  out[0] = s0; out[1] = s1;
-  if (NA > 2) out[2] = s2;
-}
-
-__device__ __forceinline__ void atomic_max_pos(double *slot, double v) {
-  // v >= 0: IEEE ordering of non-negative doubles equals unsigned ordering
-  atomicMax(reinterpret_cast<unsigned long long *>(slot),
-            static_cast<unsigned long long>(__double_as_longlong(v)));
-}
-
-__device__ __forceinline__ void block_max_to(double v, double *slot, double *red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) atomic_max_pos(slot, fmax(fmax(red[0], red[1]), fmax(red[2], red[3])));
-}
-
-// ---------------------------------------------------------------------------
-// CSR-stream building blocks
-// ---------------------------------------------------------------------------
-// Stage products of the block's entries with one or two input vectors.
-// GATHER_P: input 0 is formed on the fly as zz[c] + beta*pold[c] for c < n
-// (the PCG direction update fused into the gather).
-template <int NV>
-__device__ __forceinline__ void stage_products(const DevMat &Mx, const RowBlk b,
-                                               const double *in0, const double *in1,
-                                               double *l0, double *l1) {
-  // all index/value loads of the chunk are issued first, then all gathers, then
-  // the LDS writes: up to 2*MAX_CHUNK/TB independent loads in flight per lane
-  constexpr int E = MAX_CHUNK / TB;
-  const int cnt = b.k1 - b.k0;
-  int cc[E]; double vv[E], x0[E], x1[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const int k = threadIdx.x + e * TB;
-    if (k < cnt) { cc[e] = Mx.col[b.k0 + k]; vv[e] = Mx.val[b.k0 + k]; }
-  }
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const int k = threadIdx.x + e * TB;
-    if (k < cnt) { x0[e] = in0[cc[e]]; if (NV == 2) x1[e] = in1[cc[e]]; }
-  }
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const int k = threadIdx.x + e * TB;
-    if (k < cnt) { l0[k] = vv[e] * x0[e]; if (NV == 2) l1[k] = vv[e] * x1[e]; }
-  }
-}
-
-// Sequential (reference-order) sum of one row segment held in LDS.
-__device__ __forceinline__ double row_sum(const double *l, int a, int b) {
-  double s = 0.0;
-  for (int k = a; k < b; ++k) s += l[k];
-  return s;
-}
-
-// Row segment summed by L adjacent lanes (strided) + xor tree: used by the PCG
-// kernels, where the summation order is free; every lane returns the sum.
-__device__ __forceinline__ double row_sum_par(const double *l, int a, int b, int lane, int L) {
-  double s = 0.0;
-  for (int k = a + lane; k < b; k += L) s += l[k];
-  // L is a power of two <= 64; the first four butterfly steps stay inside a 16-lane row (DPP)
-  if (L >= 2) s += dpp_move<0xB1>(s);
-  if (L >= 4) s += dpp_move<0x4E>(s);
-  if (L >= 8) s += dpp_move<0x141>(s);
-  if (L >= 16) s += dpp_move<0x140>(s);
-  if (L >= 32) s += __shfl_xor(s, 16, 64);
-  if (L == 64) s += __shfl_xor(s, 32, 64);
-  return s;
-}
-// lanes per row for a block: as many as fit one pass over its rows (1..64)
-__device__ __forceinline__ int lanes_for(int nrows) {
-  int L = 64;
-  while (L > 1 && L * nrows > TB) L >>= 1;
-  return L;
-}
-
-// A row that does not fit one chunk: whole-workgroup strided reduction of
-// sum_k val[k]*in[col[k]] over [ka, kb).  (Summation order differs from the
-// sequential reference order; only rows longer than MAX_CHUNK take this path.)
-__device__ __forceinline__ double long_row_dot(const DevMat &Mx, int ka, int kb,
-                                               const double *in, double *red) {
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-  int k = ka + threadIdx.x;
-  for (; k + 3 * TB < kb; k += 4 * TB) {          // four independent index/value/gather chains
-    const int c0 = Mx.col[k], c1 = Mx.col[k + TB], c2 = Mx.col[k + 2 * TB], c3 = Mx.col[k + 3 * TB];
-    const double v0 = Mx.val[k], v1 = Mx.val[k + TB], v2 = Mx.val[k + 2 * TB], v3 = Mx.val[k + 3 * TB];
-    s0 += v0 * in[c0]; s1 += v1 * in[c1]; s2 += v2 * in[c2]; s3 += v3 * in[c3];
-  }
-  for (; k < kb; k += TB) s0 += Mx.val[k] * in[Mx.col[k]];
-  return block_sum((s0 + s1) + (s2 + s3), red);
-}
-
-// One wavefront per long row; no LDS, no barrier.  The row is taken in chunks of 64 x ROW_U entries: every index and value
-// load of a chunk is issued before the first gather, every gather before the first product, lanes beyond the row's end
-// are masked (clamped address, zero value).  Measured on the Lasso's pass over A (75 MB with 16-bit column ids): 24.5 us, of which
-// 7.7 us are the gathers (16.8 us with the gathered value replaced by a constant: 4.5 TB/s for the stream alone) -- 64 scattered
-// 8-byte reads per wave instruction keep the vector L1 busy far longer than their bytes; round 2's form (four chains per lane and
-// a one-load-at-a-time remainder loop) took the same time, so neither loop shape is the bound.
-#define ROW_U 12
-template <bool NARROW, class F>
-__device__ __forceinline__ double wave_row_dot_t(const DevMat &Mx, int ka, int kb, F xval) {
-  const int lane = threadIdx.x & 63;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-  for (int k0 = ka + lane; k0 - lane < kb; k0 += 64 * ROW_U) {
-    int cc[ROW_U]; double vv[ROW_U], xx[ROW_U];
-#pragma unroll
-    for (int q = 0; q < ROW_U; ++q) {
-      const int kc = min(k0 + 64 * q, kb - 1);           // (unconditional loads at a clamped address: no branch per entry)
-      cc[q] = NARROW ? (int)Mx.col16[kc] : Mx.col[kc];
-      vv[q] = Mx.val[kc];
-    }
-#pragma unroll
-    for (int q = 0; q < ROW_U; ++q) xx[q] = xval(cc[q]);
-#pragma unroll
-    for (int q = 0; q < ROW_U; ++q) if (k0 + 64 * q >= kb) vv[q] = 0.0;
-#pragma unroll
-    for (int q = 0; q < ROW_U; q += 4) { s0 += vv[q] * xx[q]; s1 += vv[q + 1] * xx[q + 1]; s2 += vv[q + 2] * xx[q + 2]; s3 += vv[q + 3] * xx[q + 3]; }
-  }
-  return wave_sum((s0 + s1) + (s2 + s3));      // valid in lane 0
-}
-template <class F>
-__device__ __forceinline__ double wave_row_dot(const DevMat &Mx, int ka, int kb, F xval) {
-  return Mx.col16 ? wave_row_dot_t<true>(Mx, ka, kb, xval) : wave_row_dot_t<false>(Mx, ka, kb, xval);
-}
-
-// y = P_b x_b for one dense diagonal block by the whole workgroup.  P_b is symmetric, so
-// y_r = sum_j P_b[j][r] x_j: a lane walks DOWN its columns while the wavefront reads row j contiguously.
-// Rows are stored with an even pitch (b rounded up; never a multiple of 32 doubles -- rows that all start on the
-// same 256-byte phase camp on a few memory channels: 19.5 instead of 12 us at pitch 128), so one wave instruction
-// fetches a whole row with 16-byte loads: lane l owns columns 2l and 2l+1 (measured against 8-byte loads at pitch b and
-// against v_mfma_f64_16x16x4_f64 in tools/mfma_dense_probe.hip: 7.65 vs 9.21 vs 9.83 us for the 400 blocks of
-// config 5, profiles/r02_mfma_dense_probe.json -- one right-hand side leaves the matrix cores nothing to do).
-// Wavefront w takes the rows j = w, w+4, ...; every load of the block is issued before anything is consumed
-// (<= 32 rows per wavefront); the four partial vectors meet in LDS.  No index loads, no gathers.
-// Returns y_r for r = threadIdx.x < b (0 otherwise); scratch: 5*DENSE_MAX doubles, x_b is left
-// in scratch[4*DENSE_MAX ...].  Ends with a barrier; the caller adds one before reusing scratch.
-// EARLY: the input element comes out of a chain of dependent loads (k_blk_apply_back).  vmcnt completes in order, so behind the
-// 32 block loads every link of the chain would wait for all of them; the chain runs first, alone, and is waited for.
-template <bool EARLY = false, class XL>
-__device__ __forceinline__ double dense_block_mv_x(const DenseP &dP, const DenseBlk d, XL xload, double *scratch) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const double2 *dv = reinterpret_cast<const double2 *>(dP.val + d.off);
-  const int hp = d.pitch >> 1;
-  double xe = 0.0;
-  if (EARLY) {
-    if ((int)threadIdx.x < d.b) xe = xload(d.c0 + (int)threadIdx.x);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  double2 v[DENSE_MAX / 4];
-#pragma unroll
-  for (int q = 0; q < DENSE_MAX / 4; ++q) {
-    const int j = w + 4 * q;
-    v[q] = (j < d.b && lane < hp) ? dv[(size_t)j * hp + lane] : double2{0.0, 0.0};
-  }
-  double *xl = scratch + 4 * DENSE_MAX;
-  if ((int)threadIdx.x < DENSE_MAX) xl[threadIdx.x] = EARLY ? xe : ((int)threadIdx.x < d.b ? xload(d.c0 + (int)threadIdx.x) : 0.0);
-  __syncthreads();
-  double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-  for (int q = 0; q < DENSE_MAX / 4; ++q) {
-    const double u = xl[min(w + 4 * q, DENSE_MAX - 1)];
-    a0 += v[q].x * u; a1 += v[q].y * u;
-  }
-  scratch[w * DENSE_MAX + 2 * lane] = a0; scratch[w * DENSE_MAX + 2 * lane + 1] = a1;
-  __syncthreads();
-  const int r = threadIdx.x;
-  return r < d.b ? (scratch[r] + scratch[DENSE_MAX + r]) + (scratch[2 * DENSE_MAX + r] + scratch[3 * DENSE_MAX + r]) : 0.0;
-}
-__device__ __forceinline__ double dense_block_mv(const DenseP &dP, const DenseBlk d, const double *x, double *scratch) {
-  return dense_block_mv_x<false>(dP, d, [x](int j) { return x[j]; }, scratch);
-}
-
-#define LDS_DECL(NV)                                   \
-  __shared__ double lprod[(NV) * MAX_CHUNK];           \
-  __shared__ double red[16]
-
-// ---------------------------------------------------------------------------
-// PCG kernels
-// ---------------------------------------------------------------------------
-// Every row kernel walks its row blocks with a workgroup-stride loop, so the
-// number of dot-product partials equals the launch grid (<= MAX_PARTS).
-
-// First kernel of an ADMM iteration: right-hand side b = sigma x - q + A'(rho z - y)
-// (compute_rhs folded into the reduced system), initial residual r = b - K x~0
-// with the warm start x~0 (the previous x~, linearly extrapolated by k_admm_finalize once the
-// iterates move smoothly: ADMM iterates follow a linear recurrence, so 2 x~_k - x~_{k-1} is 2-10x
-// closer to x~_{k+1} than x~_k is), preconditioned residual and the three start-up dot
-// products.  One dual-stream pass over M.
-__global__ void __launch_bounds__(TB) k_vd(Ctx c) {
-  for (int k = blockIdx.x * TB + threadIdx.x; k < c.n + c.m; k += gridDim.x * TB) c.vd[k] = c.vb[k] - c.vx[k];
-}
-// RESFORM (the K == 0 graphs of a k_pcg_resident engine, launch_init): the only reader of r0 and u0 = Minv r0 is the resident launch,
-// which wants its own rows of both, and they sit side by side in the exchanged vector's layout.  This form stores r0 at
-// r0pos[u0map[j]] and u0 at u0pos[u0map[j]] -- whole lines per workgroup of the resident launch -- and leaves out init_r (one
-// double in every 32-byte record) and init_z.  Same arithmetic, same partials, same returns.
-template <bool DENSE, bool RESFORM>
-__global__ void __launch_bounds__(TB) k_pcg_init(Ctx c, int bench, double *r0pos) {
-  State *st = c.st;
-  TL_MARK(c, 1);
-  TLK_DECL;
-  TLK_AT(0, 0); TLK_LAST(0);
-  LDS_DECL(2);
-  // rows inside dense diagonal blocks of P: P x~0 by the block product, A' part from the remainder
-  // matrix; all other rows below (Mm = remainder matrix then, M itself otherwise)
-  const DevMat &Mm = DENSE ? c.Mk : c.M;
-  // Loads in three flights, as in k_admm_finalize (see there): the early returns gate stores only, every prefetch is an
-  // unconditional load at a clamped index.  Flight A: the state, the parameters and this workgroup's first stream block (engines without dense
-  // blocks of P; with them the dense rows come first and the stream blocks keep the plain form).
-  const int s_stalled = st->stalled, s_fail = st->res_fail, s_hist = st->hist_r;
-  const long long s_admm = st->admm_done, s_target = st->admm_target;
-  const Params prm = *c.prm;
-  // (the DENSE instantiation loads nothing here: everything below folds to the empty block)
-  RowBlk b = RowBlk{0, 0, 0, 0};
-  if constexpr (!DENSE) {
-    b = Mm.blk[max(min((int)blockIdx.x, Mm.nstream - 1), 0)];
-    if ((int)blockIdx.x >= Mm.nstream) b = RowBlk{0, 0, 0, 0};
-  }
-  TLK_AT(1, b.k1);
-  // what the start-up of one row reads besides its two sums
-  struct RowIn { double base0, base1, vx, minv; int u0, er; };
-  // (u0 and er are looked at only where c.u0pos / c.nelim say so; where their arrays do not exist the load goes to minv instead of
-  // into a branch, whose merge would wait for the whole flight)
-  const unsigned short *u0m = c.u0pos ? c.u0map : reinterpret_cast<const unsigned short *>(c.minv);
-  const int *erw = c.nelim ? c.erow : reinterpret_cast<const int *>(c.minv);
-  auto row_load = [&](int j) {
-    RowIn r;
-    r.base0 = (prm.use_cvec ? c.cvec : c.xy)[j]; r.base1 = c.q[j];
-    r.vx = c.vx[j]; r.minv = c.minv[j];
-    r.u0 = (int)u0m[j]; r.er = erw[j];
-    return r;
-  };
-  // Flight B: the chunk's indices and values, the row pointers of the row this thread helps to sum in the first round, and
-  // that row's scalars in the lane that will start it.
-  constexpr int E = MAX_CHUNK / TB;
-  const int cnt = b.k1 - b.k0;
-  int cc[E] = {}; double vv[E] = {};
-  const int RL = lanes_for(b.r1 - b.r0), rg = threadIdx.x / RL, rlane = threadIdx.x % RL;
-  const int jf = b.r0 + rg, jfc = max(min(jf, b.r1 - 1), 0);
-  int p0 = 0, p1 = 0;
-  RowIn rf = {};
-  if constexpr (!DENSE) {
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int kc = max(min(b.k0 + (int)threadIdx.x + e * TB, b.k1 - 1), 0);
-      cc[e] = Mm.col[kc]; vv[e] = Mm.val[kc];
-    }
-    p0 = Mm.rowptr[jfc]; p1 = Mm.rowptr[jfc + 1];
-    rf = row_load(jfc);
-  }
-  // A solve that ran out of unrolled PCG iterations (`stalled`, raised by k_admm_finalize) is continued by
-  // this graph launch: no new right-hand side, the iteration kernels below pick the recurrences up where they
-  // stopped (K is even, so the parity of every ping-pong buffer is preserved).
-  if (!bench) {
-    if (s_stalled || s_fail) return;
-    if (s_admm >= s_target) { if (blockIdx.x == 0 && threadIdx.x == 0) st->run = 0; return; }
-  }
-  double prz = 0, prr = 0, pbb = 0;
-  if (DENSE)
-  for (int db = blockIdx.x; db < c.dP.nblk; db += gridDim.x) {
-    const DenseBlk d = c.dP.blk[db];
-    // plain_rhs (block-direct engines): no P x~0 -- the 50 MB pass over the blocks of P that the residual form needs -- and the
-    // low-rank rows' terms stay out of the right-hand side (k_blk_finish / k_cpl_solve put them back in closed form)
-    double sA = c.plain_rhs ? 0.0 : dense_block_mv(c.dP, d, c.vx, lprod);
-    if ((int)threadIdx.x < d.b) {
-      const int j = d.c0 + threadIdx.x;
-      double sB = 0.0;
-      if (c.plain_rhs) {
-        for (int k = Mm.rowptr[j]; k < Mm.rowptr[j + 1]; ++k) { const int cc = Mm.col[k]; if (c.plain_skip && c.plain_skip[cc - c.n] >= 0) continue; sB += Mm.val[k] * c.vb[cc]; }
-      } else {
-        for (int k = Mm.rowptr[j]; k < Mm.rowptr[j + 1]; ++k) { const int cc = Mm.col[k]; const double v = Mm.val[k]; sA += v * c.vx[cc]; sB += v * c.vb[cc]; }
-        for (int k = 0; k < c.nh; ++k) { const double hc = c.hcol[(size_t)k * c.n + j]; sA += hc * c.vx[c.n + c.hrow[k]]; sB += hc * c.vb[c.n + c.hrow[k]]; }   // huge rows of A live outside Mk
-      }
-      const double base = prm.use_cvec ? c.cvec[j] : (prm.sigma * c.xy[j] - c.q[j]);
-      const double bj = base + sB;
-      const double rj = c.plain_rhs ? bj : bj - prm.sigma * c.vx[j] - sA;
-      const double zj = c.minv[j] * rj;
-      if constexpr (RESFORM) { const int p = (int)c.u0map[j]; r0pos[p] = rj; c.u0pos[p] = zj; }
-      else {
-        c.init_r[(size_t)j * c.init_stride] = rj;
-        c.init_z[j] = zj;
-        if (c.u0pos) c.u0pos[c.u0map[j]] = zj;
-      }
-      prz += rj * zj; prr += rj * rj; pbb += bj * bj;
-    }
-    __syncthreads();
-  }
-  // row j of the start-up given sA = (M [x~0 | rho z~0])_j and sB = (M [0 | rho z - y])_j, by one thread
-  auto row_apply = [&](int j, double sA, double sB, const RowIn &r) {
-    if (DENSE) for (int k = 0; k < c.nh; ++k) { const double hc = c.hcol[(size_t)k * c.n + j]; sA += hc * c.vx[c.n + c.hrow[k]]; sB += hc * c.vb[c.n + c.hrow[k]]; }
-    const double base = prm.use_cvec ? r.base0 : (prm.sigma * r.base0 - r.base1);
-    const bool gone = c.nelim && r.er >= 0;                // eliminated from the system: no residual, no direction
-    const double bj = gone ? 0.0 : base + sB;
-    const double rj = gone ? 0.0 : bj - prm.sigma * r.vx - sA;
-    const double zj = r.minv * rj;
-    if constexpr (RESFORM) { r0pos[r.u0] = rj; c.u0pos[r.u0] = zj; }
-    else {
-      c.init_r[(size_t)j * c.init_stride] = rj;
-      c.init_z[j] = zj;
-      if (c.u0pos) c.u0pos[r.u0] = zj;
-    }
-    prz += rj * zj; prr += rj * rj; pbb += bj * bj;
-  };
-  auto row_start = [&](int j, double sA, double sB) { row_apply(j, sA, sB, row_load(j)); };
-  // this workgroup's first stream block -- Flight C: the two gathers per entry; then the row sums, and the first round of
-  // rows on what flight B brought
-  if (!DENSE) {
-    double xa[E], xb[E];
-    TLK_AT(2, cc[E - 1]);
-#pragma unroll
-    for (int e = 0; e < E; ++e) { xa[e] = c.vx[cc[e]]; xb[e] = c.vb[cc[e]]; }      // (beyond the chunk: the clamped entry's column again)
-    TLK_AT(3, xb[E - 1]);
-#pragma unroll
-    for (int e = 0; e < E; ++e) { const int k = threadIdx.x + e * TB; if (k < cnt) { lprod[k] = vv[e] * xa[e]; lprod[MAX_CHUNK + k] = vv[e] * xb[e]; } }
-    __syncthreads();
-    TLK_AT(4, 0);
-    // the summation order is free here (PCG-internal): several lanes per row
-    if (jf < b.r1) {
-      const double sA = row_sum_par(lprod, p0 - b.k0, p1 - b.k0, rlane, RL);
-      const double sB = row_sum_par(lprod + MAX_CHUNK, p0 - b.k0, p1 - b.k0, rlane, RL);
-      if (rlane == 0) row_apply(jf, sA, sB, rf);
-    }
-    TLK_AT(5, prz);
-    for (int j = jf + TB / RL; j < b.r1; j += TB / RL) {
-      const int a0 = Mm.rowptr[j] - b.k0, a1 = Mm.rowptr[j + 1] - b.k0;
-      const double sA = row_sum_par(lprod, a0, a1, rlane, RL);
-      const double sB = row_sum_par(lprod + MAX_CHUNK, a0, a1, rlane, RL);
-      if (rlane == 0) row_start(j, sA, sB);
-    }
-    __syncthreads();
-  }
-  // ... the blocks beyond the grid (with dense blocks of P: all stream blocks) in the plain form
-  for (int bi = DENSE ? blockIdx.x : blockIdx.x + gridDim.x; bi < Mm.nstream; bi += gridDim.x) {
-    const RowBlk bb = Mm.blk[bi];
-    stage_products<2>(Mm, bb, c.vx, c.vb, lprod, lprod + MAX_CHUNK);
-    __syncthreads();
-    const int RLb = lanes_for(bb.r1 - bb.r0), rgb = threadIdx.x / RLb, rlb = threadIdx.x % RLb;
-    for (int j = bb.r0 + rgb; j < bb.r1; j += TB / RLb) {
-      const int a0 = Mm.rowptr[j] - bb.k0, a1 = Mm.rowptr[j + 1] - bb.k0;
-      const double sA = row_sum_par(lprod, a0, a1, rlb, RLb);
-      const double sB = row_sum_par(lprod + MAX_CHUNK, a0, a1, rlb, RLb);
-      if (rlb == 0) row_start(j, sA, sB);
-    }
-    __syncthreads();
-  }
-  // long rows: one wavefront each, both products in one pass over the row (two whole-workgroup reductions per row made this
-  // kernel 44 us on the Lasso)
-  for (int bi = Mm.nstream + blockIdx.x * (TB / 64) + (threadIdx.x >> 6); bi < Mm.nblk; bi += gridDim.x * (TB / 64)) {
-    const RowBlk lb = Mm.blk[bi];
-    const int lane = threadIdx.x & 63;
-    if (c.vd) {              // r_j = base - sigma x~0_j + (M (vb - vx))_j: one gather per entry
-      const double acc = wave_row_dot(Mm, lb.k0, lb.k1, [&](int cc) { return c.vd[cc]; });
-      if (lane == 0) row_start(lb.r0, -acc, 0.0);
-      continue;
-    }
-    double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
-    const bool narrow = Mm.col16 != nullptr;
-    constexpr int UI = 8;
-    for (int k0 = lb.k0 + lane; k0 - lane < lb.k1; k0 += 64 * UI) {
-      int cc[UI]; double vv[UI], xa[UI], xb[UI];
-#pragma unroll
-      for (int q = 0; q < UI; ++q) {
-        const int kc = min(k0 + 64 * q, lb.k1 - 1);
-        cc[q] = narrow ? (int)Mm.col16[kc] : Mm.col[kc];
-        vv[q] = Mm.val[kc];
-      }
-#pragma unroll
-      for (int q = 0; q < UI; ++q) { xa[q] = c.vx[cc[q]]; xb[q] = c.vb[cc[q]]; }
-#pragma unroll
-      for (int q = 0; q < UI; ++q) if (k0 + 64 * q >= lb.k1) vv[q] = 0.0;
-#pragma unroll
-      for (int q = 0; q < UI; q += 2) { a0 += vv[q] * xa[q]; b0 += vv[q] * xb[q]; a1 += vv[q + 1] * xa[q + 1]; b1 += vv[q + 1] * xb[q + 1]; }
-    }
-    const double sA = wave_sum(a0 + a1), sB = wave_sum(b0 + b1);
-    if (lane == 0) row_start(lb.r0, sA, sB);
-  }
-  block_sum3(prz, prr, pbb, red);
-  TLK_AT(6, prz);
-  if (threadIdx.x == 0) {
-    c.part_rz[blockIdx.x] = prz; c.part_rr[blockIdx.x] = prr; c.part_bb[blockIdx.x] = pbb;
-    if (blockIdx.x == 0) {
-      st->run = 1; st->done = 0; st->neg_curv = 0; st->iters[0] = 0; st->iters[1] = 0;
-      if (s_hist < (1 << 20)) st->hist_r = s_hist + 1;
-    }
-  }
-  TLK_LAST(1);
-  TLK_FLUSH(c, 100, 7);
-}
-
-// ---------------------------------------------------------------------------
-// Chronopoulos-Gear PCG: two kernels per iteration instead of three.
-//   u = Minv r, w = K u, gamma = (r,u), delta = (w,u)
-//   beta = gamma/gamma_old, alpha = gamma / (delta - beta*gamma/alpha_old)
-//   p = u + beta p ; s = w + beta s ; x += alpha p ; r -= alpha s
-// k_cg_A does the vector update for its own slice AND t = rho.(A u_new), with
-// u_new recomputed from (r_old, w, s_old, Minv) at every gathered column (same
-// expression, hence the same bits, as the value the owner stores); r and s are
-// ping-ponged on the parity of `it` so gathers never see half-updated data.
-// k_cg_B applies w = [P|A'][u;t] + sigma u and emits the three dot partials.
-// flags: bit2 = benchmark, bit3 = "pre" pass (pure operator apply on u0, first convergence test),
-//        bit4 / bit5 = vector update only / operator apply only (split mode)
-// ---------------------------------------------------------------------------
-#define EPT (MAX_CHUNK / TB)
-
-// Scalars of one Chronopoulos-Gear step from the three reduced dot products.
-struct CgStep { double alpha, beta; bool first, stop, conv, bad; };
-__device__ __forceinline__ CgStep cg_step(double rr, double gam, double del, double gam_old, double alp_old,
-                                          double tol2, int iters_prev, int neg, const Params &prm, bool bench) {
-  CgStep s;
-  s.first = gam_old == 0.0;              // the pre pass zeroes gam[1]: first update of this solve
-  s.bad = false;
-  if (s.first) { s.beta = 0.0; s.alpha = gam / del; }
-  else {
-    s.beta = gam / gam_old;
-    const double den = del - s.beta * gam / alp_old;     // = p'Kp in exact arithmetic
-    if (!(den > 0.0) && del > 0.0) {
-      // u'Ku > 0 but the two-term recurrence lost positivity.  Near the stop (||r|| within 1e4 of the
-      // tolerance) this is the rounding floor of an ill-conditioned system: restart the directions
-      // from u (p = u, s = w).  Anywhere else -- and always during the setup-time convexity probe --
-      // it is what an indefinite K produces, and is reported as negative curvature.
-      if (!prm.no_restart && rr <= 1e8 * tol2) { s.first = true; s.beta = 0.0; s.alpha = gam / del; }
-      else { s.alpha = gam / den; s.bad = true; }
-    } else s.alpha = gam / den;
-  }
-  if (bench) { s.beta = 0.5; s.alpha = 1e-3; s.bad = false; }
-  s.conv = rr <= tol2;
-  s.bad = s.bad || !(s.alpha > 0.0) || !(del > 0.0);      // breakdown / negative curvature
-  s.stop = !bench && (s.conv || iters_prev >= prm.pcg_max_iter || neg || s.bad);
-  return s;
-}
-__global__ void __launch_bounds__(TB) k_cg_A(Ctx c, int it, int flags) {
-  State *st = c.st;
-  TL_MARK(c, 2);
-  const bool bench = flags & 4, upd_only = flags & 16, apply_only = flags & 32;
-  const bool pre = (flags & 8) || apply_only;   // gather u directly (no recompute)
-  // An unrolled slot whose turn never comes costs a whole kernel if it prefetches its operands before it
-  // looks at the flags (the wave cannot retire before its loads land: 4-6 us instead of 1.4, measured with
-  // `make TIMELINE=1`).  Slots at or beyond the PREVIOUS solve's iteration count (left in the state by
-  // k_admm_finalize, same cache line as the flags) therefore look first; so does a graph that continues a
-  // stalled solve.  The count moves by about one between consecutive ADMM iterations.  Looking first costs a
-  // dependent load before anything else is issued, so slots below the smallest count of the last window
-  // (baked into the graph node: flags >> 8) skip it.
-  if (!bench && it >= (flags >> 8) && (it >= st->iters_last || st->stalled) && (!st->run || st->done)) return;
-  // ---- issue every independent load before looking at the flags ----
-  const int stalled = st->stalled, run = st->run, done = st->done, neg = st->neg_curv;
-  const int iters_prev = st->iters[(it + 1) & 1];
-  const double tol2_old = st->tol2, gam_old = st->gam[(it + 1) & 1], alp_old = st->alp[(it + 1) & 1];
-  const Params prm = *c.prm;
-  const bool has_blk = (int)blockIdx.x < c.A.nstream;
-  RowBlk b = {0, 0, 0, 0};
-  if (has_blk) b = c.A.blk[blockIdx.x];
-  const int cnt = b.k1 - b.k0;
-  const bool small = has_blk;
-  const G4 *gold = c.g4 + (size_t)((it + 1) & 1) * c.n;
-  G4 *gnew = c.g4 + (size_t)(it & 1) * c.n;
-  int ecol[EPT]; double eval[EPT], g0[EPT], g1[EPT], g2[EPT], g3[EPT];
-  int RL = lanes_for(b.r1 - b.r0);
-  int rg = threadIdx.x / RL, rlane = threadIdx.x % RL;
-  int rp0 = 0, rp1 = 0;
-  double prho = 0.0;                   // rho of this lane group's first row
-  if (small) {
-    if (b.r0 + rg < b.r1) { rp0 = c.A.rowptr[b.r0 + rg]; rp1 = c.A.rowptr[b.r0 + rg + 1]; prho = c.rhoe[b.r0 + rg]; }
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      const int k = threadIdx.x + e * TB;
-      if (k < cnt) { ecol[e] = c.A.col[b.k0 + k]; eval[e] = c.A.val[b.k0 + k]; }
-    }
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      const int k = threadIdx.x + e * TB;
-      if (k < cnt) {
-        const int cc = ecol[e];
-        if (pre) g0[e] = c.ut[cc];
-        else { const G4 g = gold[cc]; g0[e] = g.r; g1[e] = g.w; g2[e] = g.s; g3[e] = g.m; }
-      }
-    }
-  }
-  // dot-product partials of the previous kernel (pre: rr, bb ; else: rr, gamma, delta)
-  double q0 = 0, q1 = 0, q2 = 0;
-  if (!apply_only) {
-    const double *a1 = pre ? c.part_bb : c.part_gam;
-    for (int i = threadIdx.x; i < c.gridM; i += TB) { q0 += c.part_rr[i]; q1 += a1[i]; if (!pre) q2 += c.part_del[i]; }
-  }
-  const int j0 = blockIdx.x * TB + threadIdx.x;
-  double o_u = 0, o_w = 0, o_p = 0, o_s = 0, o_r = 0, o_x = 0, o_m = 0;
-  if (!pre && j0 < c.n) {
-    const G4 g = gold[j0];
-    o_u = c.ut[j0]; o_w = g.w; o_p = c.pdir[j0]; o_s = g.s; o_r = g.r; o_x = gam_old == 0.0 ? c.vx[j0] : c.va[j0]; o_m = g.m;
-  }
-  if (!bench && (!run || done || ((flags & 8) && stalled))) return;   // pre pass: skipped when this graph continues a solve
-  LDS_DECL(1);
-  double sums[3];
-  bool first = false;
-  double alpha = 0.0, beta = 0.0, tol2 = tol2_old;
-  sums[0] = q0; sums[1] = q1; sums[2] = q2;
-  if (!apply_only) block_sum3(sums[0], sums[1], sums[2], red);
-  if (apply_only) {
-    // second half of a split iteration: the update kernel before this one did the scalars
-  } else if (pre) {
-    tol2 = fmax(prm.eps_rel * prm.eps_rel * sums[1], prm.eps_abs * prm.eps_abs);
-    if (!bench && sums[0] <= tol2) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->tol2 = tol2; }
-      return;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { st->tol2 = tol2; st->gam[1] = 0.0; st->alp[1] = 0.0; }
-  } else {
-    const double gam = sums[1];
-    const bool fresh = gam_old == 0.0;
-    const CgStep cs = cg_step(sums[0], gam, sums[2], gam_old, alp_old, tol2, iters_prev, neg, prm, bench);
-    first = cs.first; alpha = cs.alpha; beta = cs.beta;
-    if (cs.stop) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = cs.conv ? 1 : 2; if (cs.bad && !cs.conv) st->neg_curv = 1; }
-      return;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      st->gam[it & 1] = gam; st->alp[it & 1] = alpha; st->iters[it & 1] = iters_prev + 1;
-    }
-    // own slice: p, s, x, r, u (first element per thread was prefetched above)
-    for (int j = j0; j < c.n; j += gridDim.x * TB) {
-      double uj, wj, po, so, ro, xo, mi;
-      if (j == j0) { uj = o_u; wj = o_w; po = o_p; so = o_s; ro = o_r; xo = o_x; mi = o_m; }
-      else { const G4 g = gold[j]; uj = c.ut[j]; wj = g.w; po = c.pdir[j]; so = g.s; ro = g.r; xo = fresh ? c.vx[j] : c.va[j]; mi = g.m; }
-      const double pj = first ? uj : (uj + beta * po);
-      const double sj = first ? wj : (wj + beta * so);
-      const double rj = ro - alpha * sj;
-      c.pdir[j] = pj; gnew[j].s = sj; gnew[j].r = rj;
-      c.va[j] = xo + alpha * pj;
-      c.ut[j] = mi * rj;
-    }
-  }
-  if (upd_only) return;
-  // ---- t = rho . (A u_new) ----
-  double *t = c.ut + c.n;
-  for (int bi = blockIdx.x; bi < c.A.nstream; bi += gridDim.x) {
-    if (bi != (int)blockIdx.x) { b = c.A.blk[bi]; RL = lanes_for(b.r1 - b.r0); rg = threadIdx.x / RL; rlane = threadIdx.x % RL; }
-    const int cn = b.k1 - b.k0;
-    if (bi != (int)blockIdx.x) {
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) {
-        const int k = threadIdx.x + e * TB;
-        if (k < cn) { ecol[e] = c.A.col[b.k0 + k]; eval[e] = c.A.val[b.k0 + k]; }
-      }
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) {
-        const int k = threadIdx.x + e * TB;
-        if (k < cn) {
-          const int cc = ecol[e];
-          if (pre) g0[e] = c.ut[cc];
-          else { const G4 g = gold[cc]; g0[e] = g.r; g1[e] = g.w; g2[e] = g.s; g3[e] = g.m; }
-        }
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      const int k = threadIdx.x + e * TB;
-      if (k < cn) {
-        double uv;
-        if (pre) uv = g0[e];
-        else {
-          const double sj = first ? g1[e] : (g1[e] + beta * g2[e]);
-          uv = g3[e] * (g0[e] - alpha * sj);
-        }
-        lprod[k] = eval[e] * uv;
-      }
-    }
-    __syncthreads();
-    for (int i = b.r0 + rg; i < b.r1; i += TB / RL) {
-      int a0, a1;
-      if (bi == (int)blockIdx.x && i == b.r0 + rg) { a0 = rp0; a1 = rp1; }
-      else { a0 = c.A.rowptr[i]; a1 = c.A.rowptr[i + 1]; }
-      const double acc = row_sum_par(lprod, a0 - b.k0, a1 - b.k0, rlane, RL);
-      if (rlane == 0) t[i] = ((bi == (int)blockIdx.x && i == b.r0 + rg) ? prho : c.rhoe[i]) * acc;
-    }
-    __syncthreads();
-  }
-  // long rows: one wavefront each
-  for (int bi = c.A.nstream + blockIdx.x * (TB / 64) + (threadIdx.x >> 6); bi < c.A.nwave; bi += gridDim.x * (TB / 64)) {
-    const RowBlk lb = c.A.blk[bi];
-    double acc;
-    if (pre) acc = wave_row_dot(c.A, lb.k0, lb.k1, [&](int cc) { return c.ut[cc]; });
-    else acc = wave_row_dot(c.A, lb.k0, lb.k1, [&](int cc) {
-      const G4 g = gold[cc];
-      const double sj = first ? g.w : (g.w + beta * g.s);
-      return g.m * (g.r - alpha * sj);
-    });
-    if ((threadIdx.x & 63) == 0) t[lb.r0] = c.rhoe[lb.r0] * acc;
-  }
-  // huge rows (a budget constraint over every variable, ...): every workgroup takes a
-  // strided slice and leaves one partial; k_huge_reduce adds them in a fixed order
-  for (int bi = c.A.nwave; bi < c.A.nblk; ++bi) {
-    const RowBlk hb = c.A.blk[bi];
-    double s0 = 0.0, s1 = 0.0;
-    int k = hb.k0 + blockIdx.x * TB + threadIdx.x;
-    const int stride = gridDim.x * TB;
-    auto xv = [&](int cc) -> double {
-      if (pre) return c.ut[cc];
-      const G4 g = gold[cc];
-      const double sj = first ? g.w : (g.w + beta * g.s);
-      return g.m * (g.r - alpha * sj);
-    };
-    for (; k + stride < hb.k1; k += 2 * stride) {
-      const int c0 = c.A.col[k], c1 = c.A.col[k + stride];
-      const double v0 = c.A.val[k], v1 = c.A.val[k + stride];
-      s0 += v0 * xv(c0); s1 += v1 * xv(c1);
-    }
-    if (k < hb.k1) s0 += c.A.val[k] * xv(c.A.col[k]);
-    const double tot = block_sum(s0 + s1, red);
-    if (threadIdx.x == 0) c.part_h[(size_t)(bi - c.A.nwave) * gridDim.x + blockIdx.x] = tot;
-  }
-}
-
-// t_i = rho_i * (sum of the k_cg_A partials) for the huge rows of A; one workgroup per row.
-__global__ void __launch_bounds__(TB) k_huge_reduce(Ctx c, int flags) {
-  const State *st = c.st;
-  if (!(flags & 4) && (!st->run || st->done)) return;
-  __shared__ double red[16];
-  const int row = c.A.blk[c.A.nwave + blockIdx.x].r0;
-  const double *part = c.part_h + (size_t)blockIdx.x * c.gridA;
-  double s = 0.0;
-  for (int i = threadIdx.x; i < c.gridA; i += TB) s += part[i];
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) c.ut[c.n + row] = c.rhoe[row] * s;
-}
-
-// DENSE: P has dense diagonal blocks (their column walk keeps 64 loads per lane in flight and
-// needs ~190 registers; the plain instantiation stays lean for the sparse stream path).
-template <bool DENSE, bool FOLD>
-__global__ void __launch_bounds__(TB) k_cg_B(Ctx c, int it, int flags) {
-  State *st = c.st;
-  TL_MARK(c, 3);
-  const bool bench = flags & 4;
-  if (!bench && it >= (flags >> 8) && (it >= st->iters_last || st->stalled) && (!st->run || st->done)) return;     // see k_cg_A
-  const int run = st->run, done = st->done, skip_pre = it < 0 && st->stalled;
-  const double sigma = c.prm->sigma;
-  const bool has_blk = (int)blockIdx.x < c.Mk.nstream;
-  RowBlk b = {0, 0, 0, 0};
-  if (has_blk) b = c.Mk.blk[blockIdx.x];
-  const int cnt = b.k1 - b.k0;
-  const bool small = has_blk;
-  double ev[EPT];
-  int RL = lanes_for(b.r1 - b.r0);
-  int rg = threadIdx.x / RL, rlane = threadIdx.x % RL;
-  int rp0 = 0, rp1 = 0;
-  G4 *gc = c.g4 + (size_t)(it & 1) * c.n;
-  double pu = 0.0, pr = 0.0;           // u_j, r_j of this lane group's first row (off the tail's critical path)
-  // huge rows of A folded in: this thread's share of the k_cg_A partials of each (summed below), and the
-  // entries hcol_k[j] of this lane group's first row
-  double hs[MAX_HUGE_FOLD], ph[MAX_HUGE_FOLD], hrho[MAX_HUGE_FOLD];
-#pragma unroll
-  for (int k = 0; k < MAX_HUGE_FOLD; ++k) {
-    hs[k] = 0.0; ph[k] = 0.0; hrho[k] = 0.0;
-    if (FOLD && k < c.nh) {
-      hrho[k] = c.rhoe[c.hrow[k]];
-      for (int i = threadIdx.x; i < c.gridA; i += TB) hs[k] += c.part_h[(size_t)k * c.gridA + i];
-    }
-  }
-  if (small) {
-    if (b.r0 + rg < b.r1) {
-      rp0 = c.Mk.rowptr[b.r0 + rg]; rp1 = c.Mk.rowptr[b.r0 + rg + 1];
-      pu = c.ut[b.r0 + rg]; pr = gc[b.r0 + rg].r;
-#pragma unroll
-      for (int k = 0; k < MAX_HUGE_FOLD; ++k) if (FOLD && k < c.nh) ph[k] = c.hcol[(size_t)k * c.n + b.r0 + rg];
-    }
-    int ecol[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      const int k = threadIdx.x + e * TB;
-      if (k < cnt) { ecol[e] = c.Mk.col[b.k0 + k]; ev[e] = c.Mk.val[b.k0 + k]; }
-    }
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-      const int k = threadIdx.x + e * TB;
-      if (k < cnt) ev[e] = ev[e] * c.ut[ecol[e]];
-    }
-  }
-  if (!bench && (!run || done || skip_pre)) return;
-  LDS_DECL(1);
-  double th[MAX_HUGE_FOLD];            // t_h = rho_h * (A u)_h of the folded huge rows, formed by every workgroup itself
-#pragma unroll
-  for (int k = 0; k < MAX_HUGE_FOLD; ++k) th[k] = (FOLD && k < c.nh) ? hrho[k] * block_sum(hs[k], red) : 0.0;
-  auto hterm = [&](int j, bool pref) {
-    double s = 0.0;
-    if (FOLD) {
-#pragma unroll
-      for (int k = 0; k < MAX_HUGE_FOLD; ++k) if (k < c.nh) s += (pref ? ph[k] : c.hcol[(size_t)k * c.n + j]) * th[k];
-    }
-    return s;
-  };
-  double pg = 0, pd = 0, prr = 0;
-  for (int bi = blockIdx.x; bi < c.Mk.nstream; bi += gridDim.x) {
-    if (bi != (int)blockIdx.x) { b = c.Mk.blk[bi]; RL = lanes_for(b.r1 - b.r0); rg = threadIdx.x / RL; rlane = threadIdx.x % RL; }
-    const int cn = b.k1 - b.k0;
-    if (bi == (int)blockIdx.x) {
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) { const int k = threadIdx.x + e * TB; if (k < cn) lprod[k] = ev[e]; }
-    } else stage_products<1>(c.Mk, b, c.ut, nullptr, lprod, nullptr);
-    __syncthreads();
-    for (int j = b.r0 + rg; j < b.r1; j += TB / RL) {
-      int a0, a1;
-      if (bi == (int)blockIdx.x && j == b.r0 + rg) { a0 = rp0; a1 = rp1; }
-      else { a0 = c.Mk.rowptr[j]; a1 = c.Mk.rowptr[j + 1]; }
-      const double acc = row_sum_par(lprod, a0 - b.k0, a1 - b.k0, rlane, RL);
-      if (rlane == 0) {
-        const bool first = bi == (int)blockIdx.x && j == b.r0 + rg;
-        const double uj = first ? pu : c.ut[j], rj = first ? pr : gc[j].r;
-        const double wj = (c.nelim && c.erow[j] >= 0) ? 0.0 : (acc + sigma * uj) + hterm(j, first);
-        gc[j].w = wj;
-        pg += rj * uj; pd += wj * uj; prr += rj * rj;
-      }
-    }
-    __syncthreads();
-  }
-  // long rows: one wavefront each
-  for (int bi = c.Mk.nstream + blockIdx.x * (TB / 64) + (threadIdx.x >> 6); bi < c.Mk.nblk; bi += gridDim.x * (TB / 64)) {
-    const RowBlk lb = c.Mk.blk[bi];
-    const double acc = wave_row_dot(c.Mk, lb.k0, lb.k1, [&](int cc) { return c.ut[cc]; });
-    if ((threadIdx.x & 63) == 0) {
-      const int j = lb.r0;
-      const double uj = c.ut[j], wj = (acc + sigma * uj) + hterm(j, false), rj = gc[j].r;
-      gc[j].w = wj; pg += rj * uj; pd += wj * uj; prr += rj * rj;
-    }
-  }
-  // dense diagonal blocks of P, one workgroup per block
-  if (DENSE)
-  for (int db = blockIdx.x; db < c.dP.nblk; db += gridDim.x) {
-    const DenseBlk d = c.dP.blk[db];
-    double acc = dense_block_mv(c.dP, d, c.ut, lprod);
-    if ((int)threadIdx.x < d.b) {
-      const int jrow = d.c0 + threadIdx.x;
-      for (int k = c.Mk.rowptr[jrow]; k < c.Mk.rowptr[jrow + 1]; ++k) acc += c.Mk.val[k] * c.ut[c.Mk.col[k]];   // A' part
-      const double uj = lprod[4 * DENSE_MAX + threadIdx.x], wj = (acc + sigma * uj) + hterm(jrow, false), rj = gc[jrow].r;
-      gc[jrow].w = wj; pg += rj * uj; pd += wj * uj; prr += rj * rj;
-    }
-    __syncthreads();
-  }
-  block_sum3(pg, pd, prr, red);
-  if (threadIdx.x == 0) { c.part_gam[blockIdx.x] = pg; c.part_del[blockIdx.x] = pd; c.part_rr[blockIdx.x] = prr; }
-}
-
-
-// Slices of A_i . x for the huge rows of A (every workgroup one strided slice, one partial
-// each); the consumer adds the partials in a fixed order.  Launched only when A has huge rows.
-__global__ void __launch_bounds__(TB) k_huge_dot(Ctx c, const double *x, int always) {
-  if (!always && !c.st->run) return;
-  if (!x) {   // x~ as k_admm_finalize will see it (the start vector when no PCG update ran)
-    const State *st = c.st;
-    x = (c.vx != c.va && st->iters[0] == 0 && st->iters[1] == 0) ? c.vx : c.va;
-  }
-  __shared__ double red[16];
-  for (int bi = c.A.nwave; bi < c.A.nblk; ++bi) {
-    const RowBlk hb = c.A.blk[bi];
-    double s0 = 0.0, s1 = 0.0;
-    int k = hb.k0 + blockIdx.x * TB + threadIdx.x;
-    const int stride = gridDim.x * TB;
-    for (; k + stride < hb.k1; k += 2 * stride) {
-      const int c0 = c.A.col[k], c1 = c.A.col[k + stride];
-      s0 += c.A.val[k] * x[c0]; s1 += c.A.val[k + stride] * x[c1];
-    }
-    if (k < hb.k1) s0 += c.A.val[k] * x[c.A.col[k]];
-    const double tot = block_sum(s0 + s1, red);
-    if (threadIdx.x == 0) c.part_h[(size_t)(bi - c.A.nwave) * gridDim.x + blockIdx.x] = tot;
-  }
-}
-__device__ __forceinline__ double huge_row_sum(const Ctx &c, int bi, double *red) {
-  const double *part = c.part_h + (size_t)(bi - c.A.nwave) * c.gridA;
-  double s = 0.0;
-  for (int i = threadIdx.x; i < c.gridA; i += TB) s += part[i];
-  return block_sum(s, red);
-}
-
-// what the next right-hand side carries for row i: rho z - y, minus rho a b_y / D_y where the row has an eliminated variable y
-__device__ __forceinline__ double elim_vb(const Ctx &c, const Params &prm, int i, double rho, double vbn, double x_y) {
-  const int y = c.ecol[i];
-  if (y < 0) return vbn;
-  const double a = c.ecoef[i];
-  const double by = (prm.use_cvec ? c.cvec[y] : (prm.sigma * x_y - c.q[y])) + a * vbn;
-  return vbn - rho * a * by * c.edinv[i];
-}
-
-// Last kernel of an ADMM iteration: z~ = A x~, then update_x / update_z (+project)
-// / update_y (auxil.c:185-225, proj.c:4-14) and the m-parts of the next
-// right-hand side.  If the PCG has not converged within the unrolled
-// iterations the iteration is left untouched and `stalled` is raised.
-__global__ void __launch_bounds__(TB) k_admm_finalize(Ctx c) {
-  State *st = c.st;
-  TL_MARK(c, 4);
-  TLK_DECL;
-  TLK_AT(0, 0); TLK_LAST(0);
-  LDS_DECL(1);
-  // A launch starts with cold vector L1 and translation caches, so what this kernel costs at config 2 is not its 2.4 MB but its
-  // chain of dependent round trips.  The loads are therefore issued in three flights, each as soon as its addresses are known, and
-  // the early returns below gate stores only.  The prefetches are unconditional loads at clamped indices (no branch per load: a
-  // use the compiler moves into such a branch would wait there), so they are in bounds in every thread of every workgroup
-  // whatever the verdict turns out to be; every array of the engine holds at least one element.
-  // Flight A (addresses from blockIdx / threadIdx alone): the state, the parameters, this workgroup's first row block, the
-  // partials of ||r||^2 and the first round of the x part (both candidates for x~: the choice needs `iters`).
-  const int s_run = st->run, s_fail = st->res_fail, s_done = st->done, s_neg = st->neg_curv, s_hist = st->hist_r;
-  const int s_it0 = st->iters[0], s_it1 = st->iters[1];
-  const double s_tol2 = st->tol2;
-  const long long s_admm = st->admm_done, s_total = st->iters_total;
-  const int s_max = st->iters_max, s_min = st->iters_min, s_forced = st->forced, s_negseen = st->neg_curv_seen;
-  const Params prm = *c.prm;
-  const bool ex = c.vx != c.va;
-  const bool have = (int)blockIdx.x < c.A.nstream;
-  RowBlk b = c.A.blk[max(min((int)blockIdx.x, c.A.nstream - 1), 0)];
-  if (!have) b = RowBlk{0, 0, 0, 0};
-  TLK_AT(1, b.k1);
-  constexpr int NP = MAX_PARTS / TB;
-  double fp[NP];
-#pragma unroll
-  for (int k = 0; k < NP; ++k) fp[k] = c.fin_rr[max(min((int)threadIdx.x + k * TB, c.fin_cnt - 1), 0)];
-  double *x = c.xy, *y = c.xy + c.n;
-  const int j0 = blockIdx.x * TB + threadIdx.x, jc = max(min(j0, c.n - 1), 0);
-  const double xo0 = x[jc], xa0 = c.va[jc], xv0 = c.vx[jc], vo0 = c.vold[jc];
-  // what update_z / update_y of one row read besides z~
-  struct RowIn { double rho, rinv, yo, zo, lo, up, vo, ea, edi, rhe; int ye; };
-  auto row_load = [&](int i) {
-    RowIn r;
-    r.rho = c.rho[i]; r.rinv = c.rhoinv[i]; r.yo = y[i]; r.zo = c.z[i]; r.lo = c.l[i]; r.up = c.u[i];
-    r.vo = c.vold[c.n + i];
-    r.ye = -1; r.ea = 0.0; r.edi = 0.0; r.rhe = 0.0;
-    if (c.nelim) { r.ye = c.ecol[i]; r.ea = c.ecoef[i]; r.edi = c.edinv[i]; r.rhe = c.rhoe[i]; }
-    return r;
-  };
-  // Flight B (addresses from the block descriptor): the chunk's indices and values, the row pointers of the row this thread
-  // helps to sum in the first round, and that row's scalars in the lane that will update it.
-  constexpr int E = MAX_CHUNK / TB;
-  const int cnt = b.k1 - b.k0;
-  int cc[E]; double vv[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const int kc = max(min(b.k0 + (int)threadIdx.x + e * TB, b.k1 - 1), 0);
-    cc[e] = c.A.col[kc]; vv[e] = c.A.val[kc];
-  }
-  const int RL = lanes_for(b.r1 - b.r0), rg = threadIdx.x / RL, rlane = threadIdx.x % RL;
-  const int i0 = b.r0 + rg, ic = max(min(i0, b.r1 - 1), 0);
-  const int p0 = c.A.rowptr[ic], p1 = c.A.rowptr[min(ic + 1, c.A.nrows)];
-  const RowIn ri0 = row_load(ic);
-  const int er0 = (c.nelim ? c.erow : reinterpret_cast<const int *>(c.rho))[c.nelim ? jc : 0];   // (looked at only where c.nelim; no branch, whose merge would wait)
-  TLK_AT(2, fp[NP - 1]);
-  if (!s_run || s_fail) return;
-  // A solve that ended converged (done == 1: every resident launch that did, every k_cg_A that saw its stop test pass) has its
-  // verdict already; only done == 0 (the last unrolled iteration's residual is still in the partials) and done == 2 (a forced
-  // stop counts as `forced` only if that residual misses the tolerance) read ||r||^2.  s_done is the same in every thread.
-  double rr[1] = {0.0};
-  if (s_done != 1) {
-    // reduce_parts<1> on the prefetched partials: the same additions in the same order
-    double s0 = 0;
-#pragma unroll
-    for (int k = 0; k < NP; ++k) s0 = (int)threadIdx.x + k * TB < c.fin_cnt ? s0 + fp[k] : s0;
-    for (int i = threadIdx.x + NP * TB; i < c.fin_cnt; i += TB) s0 += c.fin_rr[i];
-    rr[0] = block_sum(s0, red);
-  }
-  TLK_AT(3, rr[0]);
-  const int iters = s_it0 > s_it1 ? s_it0 : s_it1;
-  const bool conv = s_done == 1 || rr[0] <= s_tol2;
-  const bool force = s_done == 2 || iters >= prm.pcg_max_iter || s_neg;
-  if (!conv && !force) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->stalled = 1;
-    return;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    st->stalled = 0;
-    st->admm_done = s_admm + 1;
-    st->iters_last = iters;
-    st->iters_total = s_total + iters;
-    if (iters > s_max) st->iters_max = iters;
-    if (iters < s_min) st->iters_min = iters;
-    if (!conv) st->forced = s_forced + 1;
-    if (s_neg) st->neg_curv_seen = s_negseen + 1;
-  }
-  const double alpha = prm.alpha, oma = 1.0 - prm.alpha;
-  // start vector of the next PCG solve: [x~ | rho z~] + theta * (change since the previous ADMM
-  // iteration).  No extrapolation in the first iterations after a reset (the iterates still jump),
-  // half a step for a while, then the full linear step.  hist_r is advanced by k_pcg_init only.
-  const int hist = s_hist;
-  const double th = (hist < prm.ex_h0 ? 0.0 : (hist < prm.ex_h1 ? 0.5 : 1.0)) * prm.ex_theta;
-  // the start vector itself passed the stop test (no PCG update ran): x~ is the start vector
-  const bool from_start = ex && iters == 0;
-  const double *xts = from_start ? c.vx : c.va;
-  auto x_update = [&](int j, double xo, double xt, double vo) {
-    const double xn = alpha * xt + oma * xo;
-    c.dxy[j] = xn - xo;
-    x[j] = xn;
-    // (from_start: the rows below gather x~ from vx in every workgroup while this one runs, so vx must stay what it is -- the next
-    // solve then starts from x~ itself; the iterates have all but stopped moving when a start vector passes the stop test)
-    if (ex) { if (!from_start) c.vx[j] = xt + th * (xt - vo); c.vold[j] = xt; }
-    if (from_start) c.va[j] = xt;
-  };
-  // (eliminated from the linear system: its row's thread back-substitutes and updates it below)
-  if (j0 < c.n && !(c.nelim && er0 >= 0)) x_update(j0, xo0, from_start ? xv0 : xa0, vo0);
-  for (int j = j0 + gridDim.x * TB; j < c.n; j += gridDim.x * TB) {
-    if (c.nelim && c.erow[j] >= 0) continue;
-    x_update(j, x[j], xts[j], c.vold[j]);
-  }
-  // update_z / update_y of row i given z~_i = (A x~)_i (without the eliminated variable's term), by one thread
-  auto row_apply = [&](int i, double zt, const RowIn &r) {
-    const double rho = r.rho, rinv = r.rinv, yo = r.yo, zo = r.zo;
-    const int ye = r.ye;
-    double rz = rho * zt, xny = 0.0;
-    if (ye >= 0) {
-      // zt so far is (A_X x~_X)_i: the PCG vector is zero at the eliminated variable.  Back substitution
-      // x~_y = (b_y - rho a (A_X x~_X)_i) / D_y with the b_y of the system just solved, then the variable's own update_x.
-      const double a = r.ea, xoy = x[ye];
-      const double by = (prm.use_cvec ? c.cvec[ye] : (prm.sigma * xoy - c.q[ye])) + a * (rho * zo - yo);
-      const double xty = (by - rho * a * zt) * r.edi;
-      rz = r.rhe * zt;                         // what the operator of the reduced system applies to this row
-      zt += a * xty;
-      xny = alpha * xty + oma * xoy;
-      c.dxy[ye] = xny - xoy; x[ye] = xny; c.xte[i] = xty;
-    }
-    double v = alpha * zt + oma * zo + rinv * yo;
-    v = fmax(v, r.lo);
-    const double zn = fmin(v, r.up);
-    const double dy = rho * (alpha * zt + oma * zo - zn);
-    const double yn = yo + dy;
-    c.z[i] = zn; y[i] = yn; c.dy[i] = dy; c.zt[i] = zt;
-    c.va[c.n + i] = rz;
-    if (ex) { c.vx[c.n + i] = rz + th * (rz - r.vo); c.vold[c.n + i] = rz; }
-    c.vb[c.n + i] = ye >= 0 ? elim_vb(c, prm, i, rho, rho * zn - yn, xny) : rho * zn - yn;
-  };
-  auto row_update = [&](int i, double zt) { row_apply(i, zt, row_load(i)); };
-  // stream blocks (whole rows staged through LDS).  This workgroup's first block -- Flight C: the gathers from the vector the
-  // verdict selected; then the row sums, and the first round of rows on what flight B brought
-  {
-    double xg[E];
-    TLK_AT(4, cc[E - 1]);
-#pragma unroll
-    for (int e = 0; e < E; ++e) xg[e] = xts[cc[e]];      // (beyond the chunk: the clamped entry's column again)
-    TLK_AT(5, xg[E - 1]);
-#pragma unroll
-    for (int e = 0; e < E; ++e) { const int k = threadIdx.x + e * TB; if (k < cnt) lprod[k] = vv[e] * xg[e]; }
-    __syncthreads();
-    TLK_AT(6, 0);
-    if (i0 < b.r1) {
-      const double zt = row_sum_par(lprod, p0 - b.k0, p1 - b.k0, rlane, RL);
-      if (rlane == 0) row_apply(i0, zt, ri0);
-    }
-    TLK_AT(7, 0);
-    for (int i = i0 + TB / RL; i < b.r1; i += TB / RL) {
-      const double zt = row_sum_par(lprod, c.A.rowptr[i] - b.k0, c.A.rowptr[i + 1] - b.k0, rlane, RL);
-      if (rlane == 0) row_update(i, zt);
-    }
-    __syncthreads();
-  }
-  // ... and the blocks beyond the grid, in the plain form
-  for (int bi = blockIdx.x + gridDim.x; bi < c.A.nstream; bi += gridDim.x) {
-    const RowBlk bb = c.A.blk[bi];
-    stage_products<1>(c.A, bb, xts, nullptr, lprod, nullptr);
-    __syncthreads();
-    const int RLb = lanes_for(bb.r1 - bb.r0), rgb = threadIdx.x / RLb, rlb = threadIdx.x % RLb;
-    for (int i = bb.r0 + rgb; i < bb.r1; i += TB / RLb) {
-      const double zt = row_sum_par(lprod, c.A.rowptr[i] - bb.k0, c.A.rowptr[i + 1] - bb.k0, rlb, RLb);
-      if (rlb == 0) row_update(i, zt);
-    }
-    __syncthreads();
-  }
-  // long rows: the whole workgroup per row.  (One wavefront per row as in the PCG kernels is twice as fast on the Lasso's 10 000 rows
-  // -- 2 % of its ADMM iteration -- but z~ then differs in its last bits, and a solve at the floor of attainable accuracy
-  // (test_tight_tolerance_on_ill_conditioned_system, eps = 1e-9 on a cond 1e6 system) moved from 225 to 325 iterations: not worth it.)
-  if (c.fin_wave_rows) {
-    // dense-direct engines (dense_direct.h): one wavefront per long row with the PCG kernels' row dot -- there this pass is
-    // 40 % of an ADMM iteration (72 -> 2x us at the Lasso's 10 000 rows), and the linear solves no longer stop on a residual
-    // that the last bits of z~ could move
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int bi = c.A.nstream + blockIdx.x * (TB / 64) + wv; bi < c.A.nwave; bi += gridDim.x * (TB / 64)) {
-      const RowBlk lb = c.A.blk[bi];
-      const double zt = wave_row_dot(c.A, lb.k0, lb.k1, [&](int cc) { return xts[cc]; });
-      if (lane == 0) row_update(lb.r0, zt);
-    }
-  } else
-  for (int bi = c.A.nstream + blockIdx.x; bi < c.A.nwave; bi += gridDim.x) {
-    const RowBlk lb = c.A.blk[bi];
-    const double zt = long_row_dot(c.A, lb.k0, lb.k1, xts, red);
-    if (threadIdx.x == 0) row_update(lb.r0, zt);
-    __syncthreads();
-  }
-  // huge rows: partials left by k_huge_dot
-  for (int bi = c.A.nwave + blockIdx.x; bi < c.A.nblk; bi += gridDim.x) {
-    const double zt = huge_row_sum(c, bi, red);
-    if (threadIdx.x == 0) row_update(c.A.blk[bi].r0, zt);
-    __syncthreads();
-  }
-  TLK_AT(8, 0); TLK_LAST(1);
-  TLK_FLUSH(c, 110, 9);
-}
+// device (the map above says what each fragment holds)
+#include "engine_device.h"
+#include "engine_pcg_steps.h"
 #include "engine_pcg_resident.h"
 #include "engine_pcg_blockres.h"
 #include "engine_block_direct.h"
-
 #include "dense_direct.h"
 #include "engine_block_check.h"
-
-// ---------------------------------------------------------------------------
-// Elimination of slack-like variables from the linear system (launch-per-step kernels and the resident PCG).
-//
-// A variable y that (1) appears in exactly ONE row i of A (coefficient a), (2) has no off-diagonal entry in P and
-// (3) shares its row with no other such variable couples to the rest of K = P + sigma I + A' rho A only through that row:
-//     K_yy = D_y = P_yy + sigma + rho_i a^2,     K_Xy = rho_i a A(i,X)'.
-// Eliminating all such y exactly (a block elimination with a DIAGONAL block) leaves, for the other variables X,
-//     S = P_XX + sigma I + A_X' diag(rho~) A_X,     rho~_i = rho_i (P_yy + sigma) / D_y   (rho~_i = rho_i on rows without a y),
-// i.e. the same operator with another weight on those rows; right-hand side b~_X = b_X - K_Xy b_y / D_y, back substitution
-// x~_y = (b_y - rho_i a (A_X x~_X)_i) / D_y.  Why it pays: on equality rows rho_i = 1e3 rho (include/constants.h:70), so K_yy
-// is huge against the Schur complement it hides and K is badly conditioned (Lasso, docs/examples/lasso.rst:41-63: the
-// residual variables y with y = Ad x - b; config 3 ran 98.6 PCG iterations per ADMM iteration); S has rho~ ~ P_yy + sigma
-// there.  Inertia: K > 0 <=> S > 0 and D > 0, so the convexity probe may run on the reduced operator too.
-// In the kernels: the PCG vectors are zero at the eliminated variables (k_pcg_init starts them so, k_cg_B keeps w_y = 0;
-// k_form_K gives their rows and columns of the resident K nothing but a diagonal entry and weighs the rows with rho~),
-// k_cg_A weighs rows with rho~ (Ctx::rhoe), k_admm_finalize back-substitutes and folds b_y into the m-part of the next
-// right-hand side.  The ADMM iterates themselves (x, z, y, residuals) never see any of this.
-// ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(TB) k_elim_refresh(Ctx c) {
-  const double sigma = c.prm->sigma;
-  for (int i = blockIdx.x * TB + threadIdx.x; i < c.m; i += gridDim.x * TB) {
-    const int y = c.ecol[i];
-    const double rho = c.rho[i];
-    if (y < 0) { c.rhoe[i] = rho; c.ecoef[i] = 0.0; c.edinv[i] = 0.0; continue; }
-    const double a = c.A.val[c.epos[i]], d0 = c.pdiag[y] + sigma, D = d0 + rho * a * a;
-    c.ecoef[i] = a; c.edinv[i] = 1.0 / D; c.rhoe[i] = rho * d0 / D;
-  }
-}
-// x~ of the eliminated variables lives in xte (per row), the PCG vectors are zero there: after the host wrote va's n-part
-__global__ void __launch_bounds__(TB) k_elim_split(Ctx c) {
-  for (int j = blockIdx.x * TB + threadIdx.x; j < c.n; j += gridDim.x * TB) {
-    const int i = c.erow[j];
-    if (i >= 0) { c.xte[i] = c.va[j]; c.va[j] = 0.0; }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// auxiliary kernels
-// ---------------------------------------------------------------------------
-// Jacobi preconditioner: Minv_j = 1 / (P_jj + sigma + sum_i rho_i A_ij^2)
-__global__ void __launch_bounds__(TB) k_precond(Ctx c) {
-  const double sigma = c.prm->sigma;
-  for (int j = blockIdx.x * TB + threadIdx.x; j < c.n; j += gridDim.x * TB) {
-    double s = c.pdiag[j] + sigma;
-    for (int k = c.M.split[j]; k < c.M.rowptr[j + 1]; ++k) {
-      const double a = c.M.val[k];
-      s += c.rhoe[c.M.col[k] - c.n] * a * a;
-    }
-    if (c.nelim && c.erow[j] >= 0) s = 1.0;       // (not part of the PCG system)
-    c.minv[j] = 1.0 / s;
-    c.g4[j].m = 1.0 / s; c.g4[c.n + j].m = 1.0 / s;
-  }
-}
-
-// m-parts of the PCG input vectors from (z, z~, y, rho); rhoinv from rho.  zt_partial: zt holds A x~ WITHOUT the
-// eliminated variables' terms (it was just recomputed from the PCG vector): complete it first.
-__global__ void __launch_bounds__(TB) k_refresh_m(Ctx c, int zt_partial) {
-  const double *y = c.xy + c.n;
-  const Params prm = *c.prm;
-  for (int i = blockIdx.x * TB + threadIdx.x; i < c.m; i += gridDim.x * TB) {
-    const double rho = c.rho[i];
-    c.rhoinv[i] = 1.0 / rho;
-    const double vbn = rho * c.z[i] - y[i];
-    if (c.nelim && c.ecol[i] >= 0) {
-      const double a = c.ecoef[i], xt = c.xte[i];
-      double ax = c.zt[i];
-      if (zt_partial) c.zt[i] = ax + a * xt; else ax -= a * xt;
-      c.va[c.n + i] = c.rhoe[i] * ax;
-      c.vb[c.n + i] = elim_vb(c, prm, i, rho, vbn, c.xy[c.ecol[i]]);
-    } else {
-      c.va[c.n + i] = rho * c.zt[i];
-      c.vb[c.n + i] = vbn;
-    }
-  }
-}
-
-// Generic SpMV used by set_iterates (z = A x) and by the kernel-level tests.
-// sel: 0 = whole row, 1 = entries before split (P part), 2 = from split (A' part)
-__global__ void __launch_bounds__(TB) k_spmv(DevMat Mx, const double *in, double *out, int sel) {
-  LDS_DECL(1);
-  for (int bi = blockIdx.x; bi < Mx.nblk; bi += gridDim.x) {
-    const RowBlk b = Mx.blk[bi];
-    if (IS_LONG(b)) {
-      int ka = b.k0, kb = b.k1;
-      if (sel == 1) kb = Mx.split[b.r0];
-      if (sel == 2) ka = Mx.split[b.r0];
-      const double s = long_row_dot(Mx, ka, kb, in, red);
-      if (threadIdx.x == 0) out[b.r0] = s;
-    } else {
-      stage_products<1>(Mx, b, in, nullptr, lprod, nullptr);
-      __syncthreads();
-      for (int r = b.r0 + threadIdx.x; r < b.r1; r += TB) {
-        int a0 = Mx.rowptr[r] - b.k0, a1 = Mx.rowptr[r + 1] - b.k0;
-        if (sel == 1) a1 = Mx.split[r] - b.k0;
-        if (sel == 2) a0 = Mx.split[r] - b.k0;
-        out[r] = row_sum(lprod, a0, a1);
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// Residuals, tolerances' norms, rho-estimate norms, objective and the cheap
-// halves of both infeasibility tests in ONE launch:
-//   workgroups [0, gridA)          : rows of A (A x, primal side, delta_y)
-//   workgroups [gridA, gridA+gridM): rows of M (P x, A'y, dual side, delta_x)
-__global__ void __launch_bounds__(TB) k_residuals(Ctx c) {
-  LDS_DECL(1);
-  const Params prm = *c.prm;
-  const bool sc = prm.has_scaling;
-  double *x = c.xy;
-  if ((int)blockIdx.x < c.gridA) {
-    double m_pu = 0, m_ps = 0, m_zu = 0, m_zs = 0, m_au = 0, m_as = 0, m_du = 0, m_ds = 0, lhs = 0;
-    for (int bi = blockIdx.x; bi < c.A.nblk; bi += c.gridA) {
-      const RowBlk b = c.A.blk[bi];
-      const bool longrow = IS_LONG(b);
-      if (!longrow) { stage_products<1>(c.A, b, x, nullptr, lprod, nullptr); __syncthreads(); }
-      for (int i = b.r0 + (longrow ? 0 : threadIdx.x); i < b.r1; i += (longrow ? 1 : TB)) {
-        double ax;
-        if (longrow) ax = bi >= c.A.nwave ? huge_row_sum(c, bi, red) : long_row_dot(c.A, b.k0, b.k1, x, red);
-        else ax = row_sum(lprod, c.A.rowptr[i] - b.k0, c.A.rowptr[i + 1] - b.k0);
-        if (!longrow || threadIdx.x == 0) {
-          const double zi = c.z[i], pr = ax + (-1.0) * zi;
-          const double ei = sc ? c.Einv[i] : 1.0, e = sc ? c.E[i] : 1.0;
-          m_pu = fmax(m_pu, fabs(ei * pr)); m_ps = fmax(m_ps, fabs(pr));
-          m_zu = fmax(m_zu, fabs(ei * zi)); m_zs = fmax(m_zs, fabs(zi));
-          m_au = fmax(m_au, fabs(ei * ax)); m_as = fmax(m_as, fabs(ax));
-          // delta_y projected on the polar of the recession cone (auxil.c:375-388)
-          double dy = c.dy[i];
-          const double li = c.l[i], ui = c.u[i];
-          if (ui > INF_BOUND) { if (li < -INF_BOUND) dy = 0.0; else dy = fmin(dy, 0.0); }
-          else if (li < -INF_BOUND) dy = fmax(dy, 0.0);
-          c.dxy[c.n + i] = dy;
-          m_du = fmax(m_du, fabs(e * dy)); m_ds = fmax(m_ds, fabs(dy));
-          lhs += ui * fmax(dy, 0.0) + li * fmin(dy, 0.0);
-        }
-      }
-      __syncthreads();
-    }
-    block_max_to(m_pu, c.scal + SCI(SC_PRI_U), red); block_max_to(m_ps, c.scal + SCI(SC_PRI_S), red);
-    block_max_to(m_zu, c.scal + SCI(SC_Z_U), red);   block_max_to(m_zs, c.scal + SCI(SC_Z_S), red);
-    block_max_to(m_au, c.scal + SCI(SC_AX_U), red);  block_max_to(m_as, c.scal + SCI(SC_AX_S), red);
-    block_max_to(m_du, c.scal + SCI(SC_DYN_U), red); block_max_to(m_ds, c.scal + SCI(SC_DYN_S), red);
-    lhs = block_sum(lhs, red);
-    if (threadIdx.x == 0) c.part_s0[blockIdx.x] = lhs;
-    return;
-  }
-  const int bid = blockIdx.x - c.gridA;
-  double m_du = 0, m_ds = 0, m_qu = 0, m_qs = 0, m_tu = 0, m_ts = 0, m_pu = 0, m_ps = 0;
-  double m_xu = 0, m_xs = 0, obj = 0, qdx = 0;
-  for (int bi = bid; bi < c.M.nblk; bi += c.gridM) {
-    const RowBlk b = c.M.blk[bi];
-    const bool longrow = IS_LONG(b);
-    if (!longrow) { stage_products<1>(c.M, b, c.xy, nullptr, lprod, nullptr); __syncthreads(); }
-    for (int j = b.r0 + (longrow ? 0 : threadIdx.x); j < b.r1; j += (longrow ? 1 : TB)) {
-      double px, aty;
-      if (longrow) {
-        px  = long_row_dot(c.M, b.k0, c.M.split[j], c.xy, red);
-        aty = long_row_dot(c.M, c.M.split[j], b.k1, c.xy, red);
-      } else {
-        const int a0 = c.M.rowptr[j] - b.k0, as = c.M.split[j] - b.k0, a1 = c.M.rowptr[j + 1] - b.k0;
-        px = row_sum(lprod, a0, as);
-        aty = row_sum(lprod, as, a1);
-      }
-      if (!longrow || threadIdx.x == 0) {
-        const double qj = c.q[j], xj = x[j], dxj = c.dxy[j];
-        double dr = qj + px;
-        if (c.m > 0) dr = dr + aty;
-        const double di = sc ? c.Dinv[j] : 1.0, d = sc ? c.D[j] : 1.0;
-        m_du = fmax(m_du, fabs(di * dr));  m_ds = fmax(m_ds, fabs(dr));
-        m_qu = fmax(m_qu, fabs(di * qj));  m_qs = fmax(m_qs, fabs(qj));
-        m_tu = fmax(m_tu, fabs(di * aty)); m_ts = fmax(m_ts, fabs(aty));
-        m_pu = fmax(m_pu, fabs(di * px));  m_ps = fmax(m_ps, fabs(px));
-        m_xu = fmax(m_xu, fabs(d * dxj));  m_xs = fmax(m_xs, fabs(dxj));
-        obj += xj * (0.5 * px + qj);
-        qdx += qj * dxj;
-      }
-    }
-    __syncthreads();
-  }
-  block_max_to(m_du, c.scal + SCI(SC_DUA_U), red); block_max_to(m_ds, c.scal + SCI(SC_DUA_S), red);
-  block_max_to(m_qu, c.scal + SCI(SC_Q_U), red);   block_max_to(m_qs, c.scal + SCI(SC_Q_S), red);
-  block_max_to(m_tu, c.scal + SCI(SC_ATY_U), red); block_max_to(m_ts, c.scal + SCI(SC_ATY_S), red);
-  block_max_to(m_pu, c.scal + SCI(SC_PX_U), red);  block_max_to(m_ps, c.scal + SCI(SC_PX_S), red);
-  block_max_to(m_xu, c.scal + SCI(SC_DXN_U), red); block_max_to(m_xs, c.scal + SCI(SC_DXN_S), red);
-  obj = block_sum(obj, red); qdx = block_sum(qdx, red);
-  if (threadIdx.x == 0) { c.part_s1[bid] = obj; c.part_s2[bid] = qdx; }
-}
-
-// Fixed-order final sums of the three partial arrays above (one workgroup).
-__global__ void __launch_bounds__(TB) k_final_sums(Ctx c) {
-  __shared__ double red[16];
-  double s[1];
-  reduce_parts<1>(c.part_s0, nullptr, nullptr, c.gridA, red, s);
-  if (threadIdx.x == 0) c.scal[SCI(SC_DYLHS)] = s[0];
-  reduce_parts<1>(c.part_s1, nullptr, nullptr, c.gridM, red, s);
-  if (threadIdx.x == 0) c.scal[SCI(SC_OBJ)] = s[0];
-  reduce_parts<1>(c.part_s2, nullptr, nullptr, c.gridM, red, s);
-  if (threadIdx.x == 0) c.scal[SCI(SC_QDX)] = s[0];
-}
-
-// Second stage of the infeasibility tests (auxil.c:401-417, 456-497):
-// A' dy_proj, P dx over M; A dx row test over A.
-__global__ void __launch_bounds__(TB) k_certificates(Ctx c, double eps_dx, int unscaled) {
-  LDS_DECL(1);
-  const bool sc = c.prm->has_scaling && unscaled;
-  if ((int)blockIdx.x < c.gridA) {
-    double viol = 0;
-    for (int bi = blockIdx.x; bi < c.A.nblk; bi += c.gridA) {
-      const RowBlk b = c.A.blk[bi];
-      const bool longrow = IS_LONG(b);
-      if (!longrow) { stage_products<1>(c.A, b, c.dxy, nullptr, lprod, nullptr); __syncthreads(); }
-      for (int i = b.r0 + (longrow ? 0 : threadIdx.x); i < b.r1; i += (longrow ? 1 : TB)) {
-        double adx;
-        if (longrow) adx = long_row_dot(c.A, b.k0, b.k1, c.dxy, red);
-        else adx = row_sum(lprod, c.A.rowptr[i] - b.k0, c.A.rowptr[i + 1] - b.k0);
-        if (!longrow || threadIdx.x == 0) {
-          if (sc) adx = c.Einv[i] * adx;
-          if ((c.u[i] < INF_BOUND && adx > eps_dx) || (c.l[i] > -INF_BOUND && adx < -eps_dx)) viol += 1.0;
-        }
-      }
-      __syncthreads();
-    }
-    viol = block_sum(viol, red);
-    if (threadIdx.x == 0 && viol > 0) atomic_max_pos(c.scal + SCI(SC_ADX_VIOL), viol);
-    return;
-  }
-  const int bid = blockIdx.x - c.gridA;
-  double m_tu = 0, m_ts = 0, m_pu = 0, m_ps = 0;
-  for (int bi = bid; bi < c.M.nblk; bi += c.gridM) {
-    const RowBlk b = c.M.blk[bi];
-    const bool longrow = IS_LONG(b);
-    if (!longrow) { stage_products<1>(c.M, b, c.dxy, nullptr, lprod, nullptr); __syncthreads(); }
-    for (int j = b.r0 + (longrow ? 0 : threadIdx.x); j < b.r1; j += (longrow ? 1 : TB)) {
-      double pdx, atdy;
-      if (longrow) {
-        pdx  = long_row_dot(c.M, b.k0, c.M.split[j], c.dxy, red);
-        atdy = long_row_dot(c.M, c.M.split[j], b.k1, c.dxy, red);
-      } else {
-        const int a0 = c.M.rowptr[j] - b.k0, as = c.M.split[j] - b.k0, a1 = c.M.rowptr[j + 1] - b.k0;
-        pdx = row_sum(lprod, a0, as);
-        atdy = row_sum(lprod, as, a1);
-      }
-      if (!longrow || threadIdx.x == 0) {
-        const double di = sc ? c.Dinv[j] : 1.0;
-        m_tu = fmax(m_tu, fabs(di * atdy)); m_ts = fmax(m_ts, fabs(atdy));
-        m_pu = fmax(m_pu, fabs(di * pdx));  m_ps = fmax(m_ps, fabs(pdx));
-      }
-    }
-    __syncthreads();
-  }
-  block_max_to(m_tu, c.scal + SCI(SC_ATDY_U), red); block_max_to(m_ts, c.scal + SCI(SC_ATDY_S), red);
-  block_max_to(m_pu, c.scal + SCI(SC_PDX_U), red);  block_max_to(m_ps, c.scal + SCI(SC_PDX_S), red);
-}
-
-// ---------------------------------------------------------------------------
-// Ruiz equilibration on the device (reference src/scaling.c:44-156).  One wavefront
-// per matrix row; the products are formed in the reference's order
-// ((val * row factor) * column factor, then * c) so both device copies of A hold the
-// same bits.  Scratch: dn (n), en (m) live in kp / dy; scalars in scal[SC_RUIZ..].
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ double clip_scaling(double v) {
-  if (v < 1e-4) v = 1.0;
-  if (v > 1e4) v = 1e4;
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-  return v;
-}
-
-// dn[j] = 1/sqrt(clip(max |column j of [P;A]|)), en[i] = 1/sqrt(clip(max |row i of A|))
-__global__ void __launch_bounds__(TB) k_ruiz_norms(Ctx c, double *dn, double *en) {
-  const int lane = threadIdx.x & 63;
-  const int w = blockIdx.x * (TB / 64) + (threadIdx.x >> 6), nw = gridDim.x * (TB / 64);
-  for (int r = w; r < c.n + c.m; r += nw) {
-    const bool isM = r < c.n;
-    const DevMat &X = isM ? c.M : c.A;
-    const int row = isM ? r : r - c.n;
-    double mx = 0.0;
-    for (int k = X.rowptr[row] + lane; k < X.rowptr[row + 1]; k += 64) mx = fmax(mx, fabs(X.val[k]));
-    mx = wave_max(mx);
-    if (lane == 0) { if (isM) dn[row] = 1.0 / sqrt(clip_scaling(mx)); else en[row] = 1.0 / sqrt(clip_scaling(mx)); }
-  }
-}
-
-// apply the pass: matrices, q, accumulated D and E
-__global__ void __launch_bounds__(TB) k_ruiz_apply(Ctx c, const double *dn, const double *en,
-                                                   double *Mval, double *Aval) {
-  const int lane = threadIdx.x & 63;
-  const int w = blockIdx.x * (TB / 64) + (threadIdx.x >> 6), nw = gridDim.x * (TB / 64);
-  for (int r = w; r < c.n + c.m; r += nw) {
-    if (r < c.n) {
-      const int j = r, sp = c.M.split[j];
-      const double dj = dn[j];
-      for (int k = c.M.rowptr[j] + lane; k < c.M.rowptr[j + 1]; k += 64) {
-        const int cc = c.M.col[k];
-        // P(j,cc): row factor of the stored entry, then column factor; A'(j, n+i): E_i then D_j
-        if (k < sp) {
-          // the stored triu entry has row = min(j,cc), column = max(j,cc)
-          const double fr = j < cc ? dj : dn[cc], fc = j < cc ? dn[cc] : dj;
-          Mval[k] = (Mval[k] * fr) * fc;
-        } else Mval[k] = (Mval[k] * en[cc - c.n]) * dj;
-      }
-      if (lane == 0) { c.q[j] = c.q[j] * dj; c.D[j] = dj * c.D[j]; }
-    } else {
-      const int i = r - c.n;
-      const double ei = en[i];
-      for (int k = c.A.rowptr[i] + lane; k < c.A.rowptr[i + 1]; k += 64) Aval[k] = (Aval[k] * ei) * dn[c.A.col[k]];
-      if (lane == 0) c.E[i] = ei * c.E[i];
-    }
-  }
-}
-
-// cost normalisation, step 1: per-workgroup partial sums of the P column norms, max |q|
-__global__ void __launch_bounds__(TB) k_ruiz_cost_norms(Ctx c) {
-  __shared__ double red[16];
-  const int lane = threadIdx.x & 63;
-  const int w = blockIdx.x * (TB / 64) + (threadIdx.x >> 6), nw = gridDim.x * (TB / 64);
-  double acc = 0.0, qm = 0.0;
-  for (int j = w; j < c.n; j += nw) {
-    double mx = 0.0;
-    for (int k = c.M.rowptr[j] + lane; k < c.M.split[j]; k += 64) mx = fmax(mx, fabs(c.M.val[k]));
-    mx = wave_max(mx);
-    if (lane == 0) { acc += mx; qm = fmax(qm, fabs(c.q[j])); }
-  }
-  acc = block_sum(acc, red);
-  block_max_to(qm, c.scal + SCI(SC_QDX), red);      // reuse a slot: max |q|
-  if (threadIdx.x == 0) c.part_s0[blockIdx.x] = acc;
-}
-
-// step 2 (one workgroup): c_t = 1 / clip(max(mean colnorm, clip(|q|_inf))), c *= c_t
-__global__ void __launch_bounds__(TB) k_ruiz_cost_scalar(Ctx c, int nparts) {
-  __shared__ double red[16];
-  double s[1];
-  reduce_parts<1>(c.part_s0, nullptr, nullptr, nparts, red, s);
-  if (threadIdx.x == 0) {
-    const double mean = s[0] / (double)c.n;
-    double ct = fmax(mean, clip_scaling(c.scal[SCI(SC_QDX)]));
-    ct = 1.0 / clip_scaling(ct);
-    c.scal[SCI(SC_OBJ)] = ct;                          // this pass's factor
-    c.scal[SCI(SC_DYLHS)] = c.scal[SCI(SC_DYLHS)] * ct;  // accumulated c
-    c.scal[SCI(SC_QDX)] = 0.0;
-  }
-}
-
-// step 3: P <- c_t P, q <- c_t q
-__global__ void __launch_bounds__(TB) k_ruiz_cost_apply(Ctx c, double *Mval) {
-  const double ct = c.scal[SCI(SC_OBJ)];
-  const int lane = threadIdx.x & 63;
-  const int w = blockIdx.x * (TB / 64) + (threadIdx.x >> 6), nw = gridDim.x * (TB / 64);
-  for (int j = w; j < c.n; j += nw) {
-    for (int k = c.M.rowptr[j] + lane; k < c.M.split[j]; k += 64) Mval[k] *= ct;
-    if (lane == 0) c.q[j] *= ct;
-  }
-}
-
-// finish: l, u <- E l, E u ; Dinv, Einv
-__global__ void __launch_bounds__(TB) k_ruiz_finish(Ctx c) {
-  for (int i = blockIdx.x * TB + threadIdx.x; i < c.m; i += gridDim.x * TB) {
-    const double e = c.E[i];
-    c.l[i] = c.l[i] * e; c.u[i] = c.u[i] * e; c.Einv[i] = 1.0 / e;
-  }
-  for (int j = blockIdx.x * TB + threadIdx.x; j < c.n; j += gridDim.x * TB) c.Dinv[j] = 1.0 / c.D[j];
-}
-
-__global__ void __launch_bounds__(TB) k_fill(double *p, double v, int cnt) {
-  for (int i = blockIdx.x * TB + threadIdx.x; i < cnt; i += gridDim.x * TB) p[i] = v;
-}
-
-// Up to FILL_RANGES arrays set to zero in one launch (hipeng_cold_start: one launch instead of one memset per array).
-#define FILL_RANGES 6
-struct FillRanges { double *p[FILL_RANGES]; int cnt[FILL_RANGES]; };
-__global__ void __launch_bounds__(TB) k_fill_ranges(FillRanges f) {
-  for (int k = 0; k < FILL_RANGES; k++) {
-    double *p = f.p[k];
-    const int cnt = f.cnt[k];
-    for (int i = blockIdx.x * TB + threadIdx.x; i < cnt; i += gridDim.x * TB) p[i] = 0.0;
-  }
-}
-
-// reset_start in one launch: vx = vold = va over all n + m entries, and the history count back to zero.
-__global__ void __launch_bounds__(TB) k_start_reset(Ctx c, int cnt) {
-  for (int i = blockIdx.x * TB + threadIdx.x; i < cnt; i += gridDim.x * TB) {
-    const double v = c.va[i];
-    c.vx[i] = v; c.vold[i] = v;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) c.st->hist_r = 0;
-}
-
-// What a window of hipeng_run_admm starts from: the target and the window's extremes of the PCG iteration count.
-__global__ void k_window_begin(State *st, long long target) {
-  if (threadIdx.x == 0) { st->admm_target = target; st->iters_max = 0; st->iters_min = 0x7f7f7f7f; }
-}
-
-// dst[k] = src_val[map[k]] (map < 0: structural zero inside a dense block)
-__global__ void __launch_bounds__(TB) k_repack(const double *src, const int *map, double *dst, long long cnt) {
-  for (long long k = (long long)blockIdx.x * TB + threadIdx.x; k < cnt; k += (long long)gridDim.x * TB) {
-    const int q = map[k];
-    dst[k] = q >= 0 ? src[q] : 0.0;
-  }
-}
+#include "engine_aux_kernels.h"
+#include "engine_check_kernels.h"
+#include "engine_ruiz_kernels.h"
+#include "engine_util_kernels.h"
 
 // ---------------------------------------------------------------------------
 // host side

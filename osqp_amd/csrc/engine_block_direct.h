@@ -1,5 +1,5 @@
 // engine_block_direct.h -- included by engine.hip after engine_pcg_blockres.h and before dense_direct.h (it uses Ctx, DenseP and
-// dense_block_mv_x; dense_direct.h uses its INV_TB for k_dd_pivot and k_dd_chol).
+// dense_block_mv_x of engine_device.h; dense_direct.h uses its INV_TB for k_dd_pivot and k_dd_chol).
 // The block-direct solve (FORM_BLOCK_DIRECT): BdCtx, k_blk_invert, k_blk_apply, k_blk_finish, the coupled form's k_cpl_dot /
 // k_cpl_solve / k_blk_apply_back / k_blk_apply_multi, and the capacitance inverse k_cap_diag / k_cap_step.
 

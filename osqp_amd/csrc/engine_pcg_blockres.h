@@ -1,5 +1,5 @@
 // engine_pcg_blockres.h -- included by engine.hip after engine_pcg_resident.h (it uses the RES_* constants, the bounded waits and
-// the granule exchange defined there, and cg_step).
+// the granule exchange defined there, and cg_step of engine_pcg_steps.h).
 // The block-resident PCG (FORM_BLOCKRES): BrCtx and k_pcg_blockres.
 
 

@@ -1,5 +1,5 @@
-// engine_pcg_resident.h -- included by engine.hip after k_admm_finalize, the last of the launch-per-step PCG kernels (it uses
-// cg_step, Ctx, State and the wavefront / workgroup reductions).
+// engine_pcg_resident.h -- included by engine.hip after engine_pcg_steps.h, which ends with k_admm_finalize (it uses cg_step from
+// there; Ctx, State and the wavefront / workgroup reductions of engine_device.h).
 // The resident PCG (FORM_RESIDENT): the RES_* constants, ResWG / ResCtx, the bounded waits inside a resident launch (res_spin_check,
 // res_note, res_slow_note: k_pcg_blockres uses them too), k_form_K, k_form_K_lists and k_pcg_resident.
 

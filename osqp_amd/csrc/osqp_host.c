@@ -787,7 +787,7 @@ c_int osqp_solve(OSQPWorkspace *w) {
     /* Equality rows carry rho_eq = 1e3 rho (constants.h:70): ||b|| is then dominated by their terms and a stop
      * relative to ||b|| leaves the rest of x~ far less accurate (configs 3 and 5: x, y within 1e-4 of the direct
      * solve at 1e-10, within 1e-6 at 1e-12).  Such problems get a stop 1e3 times tighter. */
-    /* ... unless the engine has eliminated a slack-like variable through that row (engine.hip, k_elim_refresh): the row then
+    /* ... unless the engine has eliminated a slack-like variable through that row (engine_aux_kernels.h, k_elim_refresh): the row then
      * enters the reduced system with rho~ = rho (P_yy + sigma) / (P_yy + sigma + rho a^2), not with 1e3 rho. */
     for (c_int i = 0; i < w->data->m; i++)
       if (w->constr_type[i] == 1 && !hipeng_row_eliminated(s->eng, i)) { prm.pcg_eps_rel = HMAX(1e-13, 1e-3 * prm.pcg_eps_rel); break; }

@@ -1,4 +1,5 @@
-// rowpart_native.h -- included at the end of engine.hip (it uses the engine's k_spmv, DevMat and allocation helpers).
+// rowpart_native.h -- included at the end of engine.hip (it uses the engine's k_spmv of engine_aux_kernels.h, DevMat of
+// engine_device.h and the allocation helpers of the host side).
 //
 // ONE QP over several GPUs by rows, the whole loop driven from C: include/osqp_amd_rowpart.h has the contract.  Per rank:
 // the shard (P_g, A_g) in an ordinary engine, n-vectors replicated, m-vectors of the rank's rows.  All kernels and

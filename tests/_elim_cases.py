@@ -1,4 +1,4 @@
-"""Seeded cases for the slack-elimination path of the single-QP engine (engine.hip: build_elim, k_elim_refresh) at
+"""Seeded cases for the slack-elimination path of the single-QP engine (engine.hip: build_elim, engine_aux_kernels.h: k_elim_refresh) at
 its edges, a Python restatement of build_elim's rule, the reduced system in long double and the bar on an eliminated ADMM step.
 tests/test_elim_cases_host.py checks all of it on the CPU, tests/test_gpu_elim_edges.py runs the cases on the device.  Nothing
 here touches the library.

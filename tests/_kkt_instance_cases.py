@@ -42,7 +42,7 @@ from tests import _form_cases as FC
 from tests import _pcg_cases as PC
 
 LD = np.longdouble
-MAX_PARTS, TB = 1024, 256                  # engine.hip: the grid cap of k_sens_grad / k_sens_tan_rhs, threads per workgroup
+MAX_PARTS, TB = 1024, 256                  # engine_device.h: the grid cap of k_sens_grad / k_sens_tan_rhs, threads per workgroup
 SPARSE_ABOVE = 3000                        # members above this n hold their matrices sparse
 F1_ENV = lambda nwg: dict(OSQP_AMD_DENSE_DIRECT=0, OSQP_AMD_RESIDENT_MIN_N=1, OSQP_AMD_RESIDENT_NWG=nwg, OSQP_AMD_RESIDENT_PIPE=1)
 

@@ -21,7 +21,7 @@ def lane_sums(part):
 
 
 def wave_sum(v):
-    """engine.hip's wave_sum on 64 lane values, addition by addition."""
+    """engine_device.h's wave_sum on 64 lane values, addition by addition."""
     v = np.asarray(v, np.float64).copy()
     i = np.arange(LANES)
     for partner in (i ^ 1, i ^ 2, (i & ~7) | (7 - (i & 7)), (i & ~15) | (15 - (i & 15))):

@@ -1,4 +1,4 @@
-"""Slack-like variables eliminated from the linear system (engine.hip: k_elim_refresh; launch-per-step engines).
+"""Slack-like variables eliminated from the linear system (engine_aux_kernels.h: k_elim_refresh; launch-per-step engines).
 A variable with one entry in its column of A and no coupling in P is taken out of the PCG system exactly (a block elimination
 with a diagonal block); the ADMM iterates must not notice.  Checks, through the C ABI, against the oracle's direct solve and
 against the same engine with OSQP_AMD_ELIM=0: Lasso (docs/examples/lasso.rst:41-63: the residual variables y), with

@@ -1,4 +1,4 @@
-"""GPU tests of the slack-elimination path of the single-QP engine (engine.hip: build_elim, k_elim_refresh, k_elim_split, the
+"""GPU tests of the slack-elimination path of the single-QP engine (engine.hip: build_elim; engine_aux_kernels.h: k_elim_refresh, k_elim_split; the
 `gone` / rhoe / elim_vb / row_apply special cases of k_precond, k_refresh_m, k_pcg_init, k_cg_A, k_cg_B, k_form_K and
 k_admm_finalize, the xte read-back of hipeng_kkt_solve, elim_rhs_dirty on the host) one ADMM step at a time through the C shim,
 against _engine_reference.admm_step -- a long-double-refined solve of the FULL K = P + sigma I + A' rho A that knows nothing of

@@ -35,7 +35,7 @@ from tests.test_gpu_resident_last_trip import ALPHA, _reference, _res_env, _same
 
 pytestmark = pytest.mark.gpu
 
-CAP = 1024                                    # MAX_PARTS of engine.hip
+CAP = 1024                                    # MAX_PARTS of engine_device.h
 
 
 def peek(e):

@@ -1,4 +1,4 @@
-"""Slack elimination (engine.hip, k_elim_refresh) against the oracle and against OSQP_AMD_ELIM=0 on Lasso QPs:
+"""Slack elimination (engine_aux_kernels.h, k_elim_refresh) against the oracle and against OSQP_AMD_ELIM=0 on Lasso QPs:
 iteration counts, x, y, PCG iterations per ADMM iteration.   usage: python tools/elim_check.py [n_feat m_data ...]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -2,7 +2,7 @@
 // 400 symmetric blocks of 125 x 125, ONE right-hand side per PCG iteration).
 //
 // Four kernels compute y_b = P_b x_b for all blocks, one workgroup (4 wavefronts) per block:
-//   k_valu      the product path of engine.hip (dense_block_mv): pitch 125, 8-byte loads, VALU column walk
+//   k_valu      the product path of engine_device.h (dense_block_mv): pitch 125, 8-byte loads, VALU column walk
 //   k_valu_wide the same walk on blocks padded to pitch 128 with 16-byte loads (one 1-KiB row per wave instruction)
 //   k_mfma      v_mfma_f64_16x16x4_f64: A = a 16 x 4 tile of P_b, B = x_b broadcast over the 16 columns (a GEMV uses
 //               1/16 of the instruction: 15 of the 16 result columns are copies), pitch 128
